@@ -14,8 +14,16 @@ only the synthesis of the reads (the stand-in for BAM decode) happens before it.
 slabs (reads are independent: no data-path collective, weak scaling); `value` is the whole-job sites/s = sum of sites
 over ranks / max time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--workload arabidopsis|human_slice] [--e2e-dist] [--no-extras] [--no-e2e] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--workload arabidopsis|human_slice] [--dump-outputs DIR] [--e2e-dist]
+                    [--full [--no-extras] [--no-e2e] [--no-cpu-baseline]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line (headline, roofline from the timed run's own counters,
+per-rank figures).  `--full` adds what takes runs of its own, after the timed region: the CPU baseline with the in-run parity
+check against the oracle, the secondary measurements (resident slab, feature extraction, strict fp32) and the end-to-end CLI
+run; `--no-cpu-baseline`, `--no-extras` and `--no-e2e` drop single legs of it.  `--dump-outputs DIR` writes the records of the
+last timed step (a fixed strided sample of at most DUMP_RECORDS of them) as DIR/<field>.npy, so that two builds can be compared
+output for output: the slabs are seeded, so the same arguments give the same inputs.
 
 `python bench.py --gpus N` with N > 1 and no torchrun environment STARTS the N ranks itself (launch_ranks: fresh child processes
 through torch.distributed.run, started before this process has made any HIP / torch.cuda call; never an exec), one device per rank,
@@ -328,11 +336,12 @@ def make_slabs(n, reads, seed, gc=0.36, cpg_oe=1.0):
         return list(ex.map(lambda i: synth_slab(reads, seed=seed + 7919 * i, gc=gc, cpg_oe=cpg_oe), range(n)))
 
 
-def stream(mc, slabs, order, keep=None):
+def stream(mc, slabs, order, keep=None, last=None):
     """Runs slabs[order[0]], slabs[order[1]], ... through the batch pipeline; returns the sites per context.
     `slabs` hold ReadBlocks (descriptors = pointers to the reads' SEQ / kinetics arrays, what a BAM decoder hands over):
     a step stages its slab with ONE hm_batch_submit_reads call, whose copies into the pinned slab run on a few host threads.
-    keep = (read ids, dict): the streamed records of those reads of the FIRST slab are copied into the dict."""
+    keep = (read ids, dict): the streamed records of those reads of the FIRST slab are copied into the dict.
+    last = dict: receives the LAST slab's sites per context and a strided sample of its records (dump_outputs)."""
     sites = [0, 0, 0]
     calls_seen = 0
 
@@ -346,10 +355,30 @@ def stream(mc, slabs, order, keep=None):
             for i in keep[0]:
                 lo, hi = np.searchsorted(rid, [i, i + 1])
                 keep[1][i] = calls[lo:hi].copy()
+        if last is not None and k == len(order) - 1:   # the view is only valid in here: one strided copy (~10 ms at full size)
+            stride = max(1, -(-len(calls) // DUMP_RECORDS))
+            last.update(sites=[batch.num_sites(c) for c in range(3)], stride=stride, calls=calls[::stride].copy())
 
     mc.stream((slabs[i] for i in order), on_batch=on_batch)
     assert calls_seen == sum(sites)
     return sites
+
+
+DUMP_RECORDS = 1 << 20   # records of the last step written by --dump-outputs: 40 B each over the seven files, 42 MB at most
+
+
+def dump_outputs(path, last):
+    """The last timed step's output as DIR/<name>.npy (float32 / float64, exact for every field): the sampled records' fields,
+    their index in the step's record list, and the step's sites per context (what batch.num_sites gives a caller)."""
+    os.makedirs(path, exist_ok=True)
+    calls = last["calls"]
+    arrays = {"index": np.arange(len(calls), dtype=np.float64) * last["stride"],
+              "read_id": calls["read_id"].astype(np.float64), "qoff": calls["qoff"].astype(np.float64),
+              "strand": calls["strand"].astype(np.float32), "ctx": calls["ctx"].astype(np.float32),
+              "scaled_prob": calls["scaled_prob"].astype(np.float32), "p": calls["p"].astype(np.float32),
+              "sites_by_context": np.asarray(last["sites"], np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def main():
@@ -362,9 +391,13 @@ def main():
     ap.add_argument("--reads", type=int, default=11700,
                     help="reads per slab = per step (~15 kb each); default: 20 steps cover BASELINE.json configs[2] (~1.1 G sites)")
     ap.add_argument("--pool", type=int, default=6, help="distinct slabs synthesised up front; steps cycle through them")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (fp32 mode, resident slab, windows)")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end CLI run (BAM in -> BAM out, default flags)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the records of the last timed step (fixed strided sample of at most 2^20) as DIR/<field>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the CPU baseline + in-run parity, the secondary measurements and the end-to-end CLI run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the in-run parity check")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary measurements (fp32 mode, resident slab, windows) and the end-to-end run")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the end-to-end CLI run (BAM in -> BAM out, default flags)")
     ap.add_argument("--e2e-reads", type=int, default=96000, help="reads of the synthetic BAM of the end-to-end run (96000 ~ 5 GB: start-up amortised)")
     ap.add_argument("--e2e-cycles", type=int, default=2, help="how often the end-to-end file may repeat the read pool (4 with --e2e-reads 234000: configs[2] in full)")
     ap.add_argument("--e2e-dist", action="store_true",
@@ -381,6 +414,8 @@ def main():
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: this process only launches the N ranks (before anything here has touched the GPU) and waits
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -427,19 +462,22 @@ def main():
     order_t = [(args.warmup + i) % n_pool for i in range(args.steps)]
     # the oracle sample: reads of slab 0 from its first, a middle and its last trunk group; their records are taken from the
     # STREAMED run of that slab (warm-up step 0: same pipeline, same multi-group launches as the timed steps)
-    want_parity = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_parity = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     sample_ids, n_groups = parity_sample(slabs[0]) if want_parity else ([], 0)
     streamed = {}
     keep = (sample_ids, streamed) if sample_ids else None
     if order_w:
         stream(mc, blocks, order_w, keep=keep)   # untimed: buffers grow to their steady-state size here
+    last = {} if args.dump_outputs and rank == 0 else None
     mc.timing(reset=True)
     barrier()
     t0 = time.perf_counter()
-    sites_ctx = stream(mc, blocks, order_t)
+    sites_ctx = stream(mc, blocks, order_t, last=last)
     barrier()
     dt = time.perf_counter() - t0
     tm = mc.timing()
+    if last is not None:
+        dump_outputs(args.dump_outputs, last)
 
     sites_job = sum(sites_ctx)
     bases_job = sum(bases_slab[i] for i in order_t)
@@ -451,7 +489,7 @@ def main():
     extras = {}
     if keep is not None and not streamed:
         stream(mc, blocks, [0], keep=keep)   # --warmup 0: the sample's records from an extra, untimed streamed run of slab 0
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         # ---- secondary measurements, all OUTSIDE the timed region -----------------------------------------------
         # (a) the same slab resident in HBM, re-run without staging / copies: the kernel-path rate of round 1
         small = slabs[0][:96]
@@ -676,7 +714,7 @@ def main():
             "effective_tflops_all_layers": sum(2.0 * MAC_TOTAL[c] * sites_ctx[c] for c in range(3)) / dt_max / 1e12,
         }
         out.update(extras)
-        if world == 1 and not args.no_extras and not args.no_e2e:
+        if args.full and world == 1 and not args.no_extras and not args.no_e2e:
             mc.close()   # the CLI is a process of its own on the same device
             out["end_to_end"] = end_to_end(slabs, args.e2e_reads, extra_flags=("-Z",) if args.e2e_cycles <= 2 else (), cycles=args.e2e_cycles)
         if want_parity and streamed:

@@ -3,6 +3,7 @@ include/hifimeth_hip.h declares; no compute call is made (no GPU here)."""
 import ctypes
 import os
 import re
+import struct
 
 import numpy as np
 import pytest
@@ -103,19 +104,127 @@ def test_synth_density():
     assert abs(sites / bases - expected_sites_per_base(0.36)) < 0.02
 
 
+def _pb_key(fno, wt):
+    return _pb_varint(fno << 3 | wt)
+
+
+def _pb_varint(v):
+    out = bytearray()
+    while True:
+        b = v & 0x7F
+        v >>= 7
+        out.append(b | (0x80 if v else 0))
+        if not v:
+            return bytes(out)
+
+
+def _pb_int(fno, v):
+    return _pb_key(fno, 0) + _pb_varint(v & 0xFFFFFFFFFFFFFFFF)
+
+
+def _pb_bytes(fno, b):
+    b = b.encode() if isinstance(b, str) else b
+    return _pb_key(fno, 2) + _pb_varint(len(b)) + b
+
+
+def _onnx_tensor(name, arr, float_data=False):
+    """TensorProto: dims (1), data_type (2: 1 = FLOAT, 7 = INT64), float_data (4, packed), name (8), raw_data (9)"""
+    arr = np.asarray(arr)
+    msg = b"".join(_pb_int(1, d) for d in arr.shape) + _pb_int(2, 1 if arr.dtype == np.float32 else 7)
+    if float_data:
+        msg += _pb_bytes(4, arr.astype("<f4").tobytes())
+    else:
+        msg += _pb_bytes(9, arr.astype("<f4" if arr.dtype == np.float32 else "<i8").tobytes())
+    return msg + (_pb_bytes(8, name) if name else b"")
+
+
+def _onnx_attr(name, v):
+    """AttributeProto: name (1), f (2), i (3), t (5), ints (8), type (20)"""
+    msg = _pb_bytes(1, name)
+    if isinstance(v, float):
+        return msg + _pb_key(2, 5) + struct.pack("<f", v) + _pb_int(20, 1)
+    if isinstance(v, int):
+        return msg + _pb_int(3, v) + _pb_int(20, 2)
+    if isinstance(v, bytes):
+        return msg + _pb_bytes(5, v) + _pb_int(20, 4)
+    return msg + b"".join(_pb_int(8, x) for x in v) + _pb_int(20, 7)
+
+
+def _onnx_node(op, inputs, outputs, **attrs):
+    """NodeProto: input (1), output (2), op_type (4), attribute (5)"""
+    return (b"".join(_pb_bytes(1, x) for x in inputs) + b"".join(_pb_bytes(2, x) for x in outputs) + _pb_bytes(4, op)
+            + b"".join(_pb_bytes(5, _onnx_attr(k, v)) for k, v in attrs.items()))
+
+
+def _write_onnx(w, path, dialect):
+    """The model `w` as an ONNX file in one of the two dialects the readers accept (hifimeth_amd/onnx_weights.py):
+    "initializers" -- opset 17, weights as graph initializers, FC = Gemm(transB=1) on [out, in];
+    "constants"    -- opset 11, weights as Constant nodes (biases as float_data), FC = MatMul on [in, out] + Add.
+    Both carry ops and an int64 shape tensor that the readers must pass over."""
+    inits, nodes = [], []
+
+    def param(name, arr):
+        if dialect == "initializers":
+            inits.append(_onnx_tensor(name, arr))
+        else:
+            nodes.append(_onnx_node("Constant", [], [name], value=_onnx_tensor("", arr, float_data=arr.ndim == 1)))
+        return name
+
+    x = "input"
+    bn = [param(f"bn0.{k}", t) for k, t in zip(("weight", "bias", "running_mean", "running_var"),
+                                               (w.bn_gamma, w.bn_beta, w.bn_mean, w.bn_var))]
+    nodes.append(_onnx_node("Transpose", [x], ["x_t"], perm=[0, 2, 1]))
+    nodes.append(_onnx_node("BatchNormalization", ["x_t"] + bn, ["bn0_out"], epsilon=w.bn_eps, momentum=0.9))
+    x = "bn0_out"
+    for i, (cw, cb) in enumerate(zip(w.conv_w, w.conv_b)):
+        ins = [x, param(f"conv{i + 1}.weight", cw), param(f"conv{i + 1}.bias", cb)]
+        nodes.append(_onnx_node("Conv", ins, [f"conv{i + 1}_out"], dilations=[1], group=1, kernel_shape=[cw.shape[2]],
+                                pads=[1, 1], strides=[2]))
+        nodes.append(_onnx_node("Relu", [f"conv{i + 1}_out"], [f"relu{i + 1}"]))
+        x = f"relu{i + 1}"
+    shape = np.array([-1, 128], np.int64)
+    if dialect == "initializers":
+        inits.append(_onnx_tensor("flat_shape", shape))
+    else:
+        nodes.append(_onnx_node("Constant", [], ["flat_shape"], value=_onnx_tensor("", shape)))
+    nodes.append(_onnx_node("Reshape", [x, "flat_shape"], ["flat"]))
+    x = "flat"
+    for i, (fw, fb) in enumerate(((w.fc1_w, w.fc1_b), (w.fc2_w, w.fc2_b))):
+        if dialect == "initializers":
+            nodes.append(_onnx_node("Gemm", [x, param(f"fc{i + 1}.weight", fw), param(f"fc{i + 1}.bias", fb)], [f"fc{i + 1}_out"],
+                                    alpha=1.0, beta=1.0, transB=1))
+        else:
+            nodes.append(_onnx_node("MatMul", [x, param(f"fc{i + 1}.weight", np.ascontiguousarray(fw.T))], [f"mm{i + 1}"]))
+            nodes.append(_onnx_node("Add", [param(f"fc{i + 1}.bias", fb), f"mm{i + 1}"], [f"fc{i + 1}_out"]))
+        x = f"fc{i + 1}_out"
+        if i == 0:
+            nodes.append(_onnx_node("Relu", [x], ["fc1_relu"]))
+            x = "fc1_relu"
+    nodes.append(_onnx_node("Softmax", [x], ["output"], axis=1))
+    graph = b"".join(_pb_bytes(1, n) for n in nodes) + _pb_bytes(2, "cnn") + b"".join(_pb_bytes(5, t) for t in inits)
+    opset = _pb_bytes(1, "") + _pb_int(2, 17 if dialect == "initializers" else 11)
+    with open(path, "wb") as f:
+        f.write(_pb_int(1, 8) + _pb_bytes(2, "pytorch") + _pb_bytes(7, graph) + _pb_bytes(8, opset))
+
+
 def test_cxx_onnx_reader_matches_python_reader(tmp_path):
-    """The C++ model reader of the product (both ONNX dialects) against the committed .hmw files,
-    which the Python reader produced from the same ONNX files.  Needs /root/reference (build container)."""
-    ref = "/root/reference/models"
-    if not os.path.isdir(ref):
-        pytest.skip("reference models absent")
+    """The C++ model reader of the product and the Python reader, in both ONNX dialects, on ONNX files holding the committed
+    weights: each gives back the committed .hmw file byte for byte."""
     from hifimeth_amd import _lib
+    from hifimeth_amd.onnx_weights import load_hmw, load_onnx, save_hmw
     L = _lib.lib()
     for ctx in ("CpG", "CHG", "CHH"):
-        out = str(tmp_path / (ctx + ".hmw"))
-        assert L.hm_convert_model(os.path.join(ref, ctx + ".onnx").encode(), out.encode()) == 0, L.hm_last_error(None)
-        assert open(out, "rb").read() == open(os.path.join(ROOT, "hifimeth_amd", "weights", ctx + ".hmw"), "rb").read()
-    assert L.hm_convert_model(b"/nonexistent.onnx", b"/tmp/x.hmw") < 0
+        hmw = os.path.join(ROOT, "hifimeth_amd", "weights", ctx + ".hmw")
+        want = open(hmw, "rb").read()
+        for dialect in ("initializers", "constants"):
+            src = str(tmp_path / f"{ctx}.{dialect}.onnx")
+            _write_onnx(load_hmw(hmw), src, dialect)
+            out = str(tmp_path / f"{ctx}.{dialect}.hmw")
+            assert L.hm_convert_model(src.encode(), out.encode()) == 0, L.hm_last_error(None)
+            assert open(out, "rb").read() == want, (ctx, dialect)
+            save_hmw(load_onnx(src), out)
+            assert open(out, "rb").read() == want, (ctx, dialect)
+    assert L.hm_convert_model(str(tmp_path / "nonexistent.onnx").encode(), str(tmp_path / "x.hmw").encode()) < 0
     assert b"cannot read" in L.hm_last_error(None)
 
 

@@ -47,7 +47,7 @@ def _check_common(d, n_gpus):
 
 
 def test_bench_line_single_gpu_with_cpu_baseline():
-    d = _line([sys.executable, BENCH] + SMALL)
+    d = _line([sys.executable, BENCH, "--full"] + SMALL)
     _check_common(d, 1)
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["unit"] == "sites/s" and cb["cores"] >= 1 and cb["value"] > 0 and cb["sample"]
@@ -67,6 +67,33 @@ def test_bench_line_single_gpu_with_cpu_baseline():
     assert e2e["value"] > 0 and e2e["unit"] == "sites/s" and e2e["reads"] == 72 and e2e["host_threads"] >= 1   # the pool of 3 x 12 reads, twice
     assert e2e["with_flag"]["-Z"]["exit"] == 0
     assert e2e["sites"] > 100000 and "defaults" in e2e["flags"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_repeatable_outputs(tmp_path):
+    """without --full the line carries no leg that takes runs of its own; --dump-outputs writes the last timed step's records
+    (float32 / float64 .npy), and two runs with the same arguments write the same arrays"""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        d = _line([sys.executable, BENCH, "--dump-outputs", str(out)] + SMALL)
+        _check_common(d, 1)
+        for k in ("cpu_baseline", "parity", "end_to_end", "resident_slab", "feature_extraction", "fp32_mode"):
+            assert k not in d, k
+        files = sorted(out.glob("*.npy"))
+        assert sum(f.stat().st_size for f in files) <= 64 << 20
+        arrays = {f.stem: np.load(f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        n = int(arrays["sites_by_context"].sum())
+        assert 0 < n < 2 * d["config"]["sites_per_gpu_step"]   # one step's sites (12-read slabs differ from step to step)
+        for k in ("index", "read_id", "qoff", "strand", "ctx", "scaled_prob", "p"):
+            assert len(arrays[k]) == n, k   # small slabs: every record of the step
+        assert np.array_equal(arrays["index"], np.arange(n)) and ((arrays["p"] >= 0) & (arrays["p"] <= 1)).all()
+        assert set(np.unique(arrays["ctx"])) <= {0, 1, 2} and np.all(np.diff(arrays["read_id"]) >= 0)
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys()
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
 
 
 def test_bench_rccl_world_of_one():
