@@ -27,6 +27,7 @@ class MappedRecord:
     l_qseq: int
     mm: Optional[str]
     ml: Optional[np.ndarray]
+    hp: Optional[int] = None  # value of the first HP aux field (phasing haplotype) if it has an integer type
 
     def cigar_u32(self) -> np.ndarray:
         return self.cigar
@@ -38,15 +39,22 @@ class MappedRecord:
         return _DEC[nib[:self.l_qseq]].tobytes().decode()
 
 
-def _aux_tags(aux: bytes, want=(b"MM", b"ML", b"Mm", b"Ml")):
+_INT_FMT = {"c": "b", "C": "B", "s": "h", "S": "H", "i": "i", "I": "I"}   # integer aux types -> struct codes
+
+
+def _aux_tags(aux: bytes, want=(b"MM", b"ML", b"Mm", b"Ml", b"HP")):
+    """-> {tag: value} of the wanted tags.  HP (phasing haplotype) is decided by its first occurrence: its value if that
+    has an integer type (c C s S i I), else None."""
     out, p, n = {}, 0, len(aux)
     size = {"A": 1, "c": 1, "C": 1, "s": 2, "S": 2, "i": 4, "I": 4, "f": 4}
     while p + 3 <= n:
         tag, t = aux[p:p + 2], chr(aux[p + 2])
         p += 3
+        if tag == b"HP" and tag in want and tag not in out:
+            out[tag] = struct.unpack_from("<" + _INT_FMT[t], aux, p)[0] if t in _INT_FMT else None
         if t in "ZH":
             e = aux.index(b"\0", p)
-            if tag in want:
+            if tag in want and tag != b"HP":
                 out[tag] = aux[p:e].decode()
             p = e + 1
         elif t == "B":
@@ -54,7 +62,7 @@ def _aux_tags(aux: bytes, want=(b"MM", b"ML", b"Mm", b"Ml")):
             cnt = struct.unpack_from("<I", aux, p + 1)[0]
             p += 5
             w = size[sub]
-            if tag in want:
+            if tag in want and tag != b"HP":
                 dt = {"C": "<u1", "c": "<i1", "S": "<u2", "s": "<i2", "I": "<u4", "i": "<i4", "f": "<f4"}[sub]
                 out[tag] = np.frombuffer(aux, dt, cnt, p).copy()
             p += w * cnt
@@ -93,7 +101,7 @@ def read_bam(path: str) -> Tuple[str, List[Tuple[str, int]], Iterator[MappedReco
             tags = _aux_tags(body[o:])
             mm = tags.get(b"MM", tags.get(b"Mm"))
             ml = tags.get(b"ML", tags.get(b"Ml"))
-            yield MappedRecord(name, flag, tid, pos, mapq, cigar, seq4, l_seq, mm, ml)
+            yield MappedRecord(name, flag, tid, pos, mapq, cigar, seq4, l_seq, mm, ml, tags.get(b"HP"))
         f.close()
     return text, refs, records()
 

@@ -5,6 +5,8 @@
 // The host parses the BAM and the MM/ML lists (parallel over the reads of a batch); alignment projection,
 // histograms and per-locus counting run on the GPU through the hm_pileup_* C ABI.  No temporary file is written:
 // the projected calls stay in HBM until the thresholds are known.
+// -H (ours): also <prefix>.hap1.<ctx>.cov.bed / <prefix>.hap2.<ctx>.cov.bed from the records' integer HP tag, counted with
+// the combined thresholds, each locus in its combined context.
 #include <strings.h>
 #include <zlib.h>
 
@@ -57,6 +59,7 @@ struct PileupOptions {
     int threads = 8;      // kNumThreads
     int device = 0;
     int read_batch = 512;
+    bool haplotypes = false;  // -H: also <prefix>.hap1.* / <prefix>.hap2.* from the HP tag
     std::string ref, bam, prefix;
 };
 
@@ -69,7 +72,9 @@ void pileup_usage(const char* exe) {
             "  -f <Alignment identity>\n    Default: 0\n"
             "  -t <CPU threads>\n    Number of CPU threads\n    Default: 8\n"
             "  -d <int>\n    GPU ordinal\n    Default: 0\n"
-            "  -b <int>\n    BAM records per GPU batch\n    Default: 512\n",
+            "  -b <int>\n    BAM records per GPU batch\n    Default: 512\n"
+            "  -H\n    Haplotype-resolved output: records tagged HP:i:1 / HP:i:2 are also counted into\n"
+            "    <prefix>.hap1.<ctx>.cov.bed / <prefix>.hap2.<ctx>.cov.bed (same thresholds as the combined files)\n",
             exe);
 }
 
@@ -673,6 +678,49 @@ void report_thresholds(const uint64_t* bins, uint8_t thr[3]) {
 }
 }  // namespace
 
+namespace {
+// rows of the three <prefix>.<ctx>.cov.bed files (pileup.cpp:562-590) from planes (pcov, ncov, key): all NULL = the
+// engine's own combined planes, else DEVICE planes over the whole concatenated reference.  The context of a row is the
+// key's motif.  false on an engine error (hm_pileup_last_error).
+bool write_bed(hm_pileup_t* pe, const Fasta& fa, const void* pcov, const void* ncov, const void* key, FILE* out[3], int threads) {
+    std::vector<hm_locus_t> loci;
+    const int fmt_threads = std::max(1, threads);
+    std::vector<std::string> text((size_t)fmt_threads * 3);
+    int64_t off = 0;
+    for (size_t s = 0; s < fa.names.size(); ++s) {
+        const int64_t lo = off, hi = off + fa.length[s];
+        off = hi;
+        int64_t n = hm_pileup_fetch_loci(pe, pcov, ncov, key, 0, lo, hi, nullptr, 0);
+        if (n < 0) return false;
+        if (n == 0) continue;
+        loci.resize((size_t)n);
+        n = hm_pileup_fetch_loci(pe, pcov, ncov, key, 0, lo, hi, loci.data(), n);
+        if (n < 0) return false;
+        // rows are formatted by `fmt_threads` workers over contiguous slices and written slice by slice (pileup.cpp:562-590)
+        parallel_run(fmt_threads, fmt_threads, [&](int w) {
+            for (int c = 0; c < 3; ++c) text[(size_t)w * 3 + c].clear();
+            const size_t a = (size_t)n * w / fmt_threads, b = (size_t)n * (w + 1) / fmt_threads;
+            char row[256];
+            for (size_t i = a; i < b; ++i) {
+                const hm_locus_t& l = loci[i];
+                const int64_t k = l.gpos - lo;
+                const double freq = 100.0 * l.pcov / (l.pcov + l.ncov);
+                const int len = snprintf(row, sizeof row, "\t%lld\t%lld\t%g\t%d\t%d\n", (long long)k, (long long)k + 1, freq, l.pcov, l.ncov);
+                std::string& t = text[(size_t)w * 3 + (l.motif < 3 ? l.motif : 2)];
+                t += fa.names[s];
+                t.append(row, (size_t)len);
+            }
+        });
+        for (int c = 0; c < 3; ++c)
+            for (int w = 0; w < fmt_threads; ++w) {
+                const std::string& t = text[(size_t)w * 3 + c];
+                if (!t.empty()) fwrite(t.data(), 1, t.size(), out[c]);
+            }
+    }
+    return true;
+}
+}  // namespace
+
 int cmd_pileup(int argc, char** argv) {
     PileupOptions o;
     int i = 2;
@@ -680,6 +728,7 @@ int cmd_pileup(int argc, char** argv) {
         const std::string a = argv[i];
         if (a == "-h") { pileup_usage(argv[0]); return 0; }
         if (a.size() < 2 || a[0] != '-') break;
+        if (a == "-H") { o.haplotypes = true; continue; }  // a flag: takes no value
         if (i + 1 >= argc) { pileup_usage(argv[0]); return EXIT_FAILURE; }
         if (a == "-q") o.min_mapq = atoi(argv[++i]);
         else if (a == "-f") o.min_pi = atof(argv[++i]);
@@ -693,8 +742,10 @@ int cmd_pileup(int argc, char** argv) {
     o.bam = argv[i + 1];
     o.prefix = argv[i + 2];
     fprintf(stderr, "\n\n====================> Parameters:\nmin-mapQ: %d\nmin-identity: %g\nCPU threads: %d\n"
-                    "Genomic reference: %s\nmod-bam: %s\noutput prefix: %s\n\n\n",
+                    "Genomic reference: %s\nmod-bam: %s\noutput prefix: %s\n",
             o.min_mapq, o.min_pi, o.threads, o.ref.c_str(), o.bam.c_str(), o.prefix.c_str());
+    if (o.haplotypes) fprintf(stderr, "haplotypes: HP 1 / 2 -> %s.hap1.* / %s.hap2.*\n", o.prefix.c_str(), o.prefix.c_str());
+    fprintf(stderr, "\n\n");
 
     using clk = std::chrono::steady_clock;
     auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
@@ -720,6 +771,7 @@ int cmd_pileup(int argc, char** argv) {
     };
     hm_pileup_set_option(pe, "min_mapq", o.min_mapq);
     hm_pileup_set_option(pe, "min_pi", o.min_pi);
+    if (o.haplotypes && hm_pileup_set_option(pe, "partitions", 2) != HM_OK) return die("partitions");
     if (fa.names.empty()) { fprintf(stderr, "ERROR: no sequence in %s\n", o.ref.c_str()); hm_pileup_destroy(pe); return EXIT_FAILURE; }
     if (hm_pileup_set_reference(pe, (int32_t)fa.names.size(), fa.length.data(), fa.bases.data()) != HM_OK) return die("reference");
 
@@ -783,9 +835,9 @@ int cmd_pileup(int argc, char** argv) {
                 return fail_out();
             }
             real_cigar(r, cig);
-            const int rc = hm_pileup_submit_read(pe, (uint32_t)order, r.flag(), tid2sid[(size_t)tid], r.pos(), r.mapq(), r.l_qseq(),
-                                                 r.seq4(), (int32_t)cig.size(), cig.data(), (int64_t)b.mods[(size_t)k].size(),
-                                                 b.mods[(size_t)k].data());
+            const int rc = hm_pileup_submit_read_hp(pe, (uint32_t)order, r.flag(), tid2sid[(size_t)tid], r.pos(), r.mapq(), r.l_qseq(),
+                                                    r.seq4(), (int32_t)cig.size(), cig.data(), (int64_t)b.mods[(size_t)k].size(),
+                                                    b.mods[(size_t)k].data(), o.haplotypes ? haplotype_of(r) : 0);
             if (rc < 0) {
                 fprintf(stderr, "ERROR: read %s: %s\n", reinterpret_cast<const char*>(r.data.data() + 32), hm_pileup_last_error(pe));
                 return fail_out();
@@ -809,47 +861,35 @@ int cmd_pileup(int argc, char** argv) {
     report_thresholds(bins, thr);
     if (hm_pileup_count(pe, thr) != HM_OK) return die("count");
 
-    FILE* out[3];
-    for (int c = 0; c < 3; ++c) {
-        const std::string path = o.prefix + "." + cn[c] + ".cov.bed";
-        out[c] = fopen(path.c_str(), "w");
-        if (!out[c]) { fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str()); hm_pileup_destroy(pe); return EXIT_FAILURE; }
+    // one set of three files per output: the combined planes, then (-H) each partition's pcov / ncov with the combined key
+    std::vector<std::string> tags{""};
+    std::vector<const void*> planes{nullptr, nullptr, nullptr};
+    if (o.haplotypes) {
+        void* key = nullptr;
+        if (hm_pileup_planes(pe, nullptr, nullptr, &key, nullptr) != HM_OK) return die("planes");
+        for (int part = 1; part <= 2; ++part) {
+            void *pc = nullptr, *nc = nullptr;
+            if (hm_pileup_partition_planes(pe, part, &pc, &nc) != HM_OK) return die("partition planes");
+            tags.push_back("hap" + std::to_string(part) + ".");
+            planes.insert(planes.end(), {pc, nc, key});
+        }
     }
-    std::vector<hm_locus_t> loci;
-    const int fmt_threads = std::max(1, o.threads);
-    std::vector<std::string> text((size_t)fmt_threads * 3);
-    int64_t off = 0;
-    for (size_t s = 0; s < fa.names.size(); ++s) {
-        const int64_t lo = off, hi = off + fa.length[s];
-        off = hi;
-        int64_t n = hm_pileup_fetch_loci(pe, nullptr, nullptr, nullptr, 0, lo, hi, nullptr, 0);
-        if (n < 0) return die("loci");
-        if (n == 0) continue;
-        loci.resize((size_t)n);
-        n = hm_pileup_fetch_loci(pe, nullptr, nullptr, nullptr, 0, lo, hi, loci.data(), n);
-        if (n < 0) return die("loci");
-        // rows are formatted by `fmt_threads` workers over contiguous slices and written slice by slice (pileup.cpp:562-590)
-        parallel_run(fmt_threads, fmt_threads, [&](int w) {
-            for (int c = 0; c < 3; ++c) text[(size_t)w * 3 + c].clear();
-            const size_t a = (size_t)n * w / fmt_threads, b = (size_t)n * (w + 1) / fmt_threads;
-            char row[256];
-            for (size_t i = a; i < b; ++i) {
-                const hm_locus_t& l = loci[i];
-                const int64_t k = l.gpos - lo;
-                const double freq = 100.0 * l.pcov / (l.pcov + l.ncov);
-                const int len = snprintf(row, sizeof row, "\t%lld\t%lld\t%g\t%d\t%d\n", (long long)k, (long long)k + 1, freq, l.pcov, l.ncov);
-                std::string& t = text[(size_t)w * 3 + (l.motif < 3 ? l.motif : 2)];
-                t += fa.names[s];
-                t.append(row, (size_t)len);
+    for (size_t t = 0; t < tags.size(); ++t) {
+        FILE* out[3];
+        for (int c = 0; c < 3; ++c) {
+            const std::string path = o.prefix + "." + tags[t] + cn[c] + ".cov.bed";
+            out[c] = fopen(path.c_str(), "w");
+            if (!out[c]) {
+                fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str());
+                for (int d = 0; d < c; ++d) fclose(out[d]);
+                hm_pileup_destroy(pe);
+                return EXIT_FAILURE;
             }
-        });
-        for (int c = 0; c < 3; ++c)
-            for (int w = 0; w < fmt_threads; ++w) {
-                const std::string& t = text[(size_t)w * 3 + c];
-                if (!t.empty()) fwrite(t.data(), 1, t.size(), out[c]);
-            }
+        }
+        const bool ok = write_bed(pe, fa, planes[3 * t], planes[3 * t + 1], planes[3 * t + 2], out, o.threads);
+        for (FILE* f : out) fclose(f);
+        if (!ok) return die("loci");
     }
-    for (FILE* f : out) fclose(f);
     hm_pileup_destroy(pe);
     fprintf(stderr, "## %llu records in %.2f s: [producer thread: BAM read %.2f s, MM/ML parse %.2f s] overlapped with "
                     "[staging %.2f s, GPU projection %.2f s]; thresholds + count + BED %.2f s\n",

@@ -701,6 +701,31 @@ bool next_aux(const uint8_t*& p, const uint8_t* end, AuxField& f) {
     return true;
 }
 
+bool aux_int(const BamRecord& r, const char tag[2], int64_t& value) {
+    const uint8_t* p = r.data.data() + r.aux_offset();
+    const uint8_t* end = r.data.data() + r.data.size();
+    AuxField f;
+    while (p < end && next_aux(p, end, f)) {
+        if (f.tag[0] != tag[0] || f.tag[1] != tag[1]) continue;
+        const uint8_t* v = f.payload;
+        switch (f.type) {
+        case 'c': value = (int8_t)v[0]; return true;
+        case 'C': value = v[0]; return true;
+        case 's': value = (int16_t)(v[0] | (v[1] << 8)); return true;
+        case 'S': value = (uint16_t)(v[0] | (v[1] << 8)); return true;
+        case 'i': value = (int32_t)rd32(v); return true;
+        case 'I': value = rd32(v); return true;
+        default: return false;  // first occurrence wins (bam_aux_get), and it is not an integer
+        }
+    }
+    return false;
+}
+
+int haplotype_of(const BamRecord& r) {
+    int64_t hp = 0;
+    return aux_int(r, "HP", hp) && (hp == 1 || hp == 2) ? (int)hp : 0;
+}
+
 KineticsView kinetics_of(const BamRecord& r) {
     KineticsView kv{{nullptr, nullptr, nullptr, nullptr}, {1, 1, 1, 1}};
     static const char* names[4] = {"fi", "fp", "ri", "rp"};

@@ -115,6 +115,11 @@ struct AuxField {
 
 // walks the aux block; returns false (and stops) on a corrupt field
 bool next_aux(const uint8_t*& p, const uint8_t* end, AuxField& f);
+// the first aux field named `tag`: true with its value if that field has an integer type (c C s S i I); false if the
+// record has no such field, the first one is of another type, or the aux block is corrupt before it
+bool aux_int(const BamRecord& r, const char tag[2], int64_t& value);
+// haplotype partition of a record (HiPhase / WhatsHap phasing): the first HP field if integer-typed with value 1 or 2, else 0
+int haplotype_of(const BamRecord& r);
 
 bool read_header(BgzfReader& in, BamHeader& h, std::string& err);
 // libdeflate (dlopen'ed when the system has it) inflates and checksums BGZF blocks; the writer deflates with zlib unless asked otherwise

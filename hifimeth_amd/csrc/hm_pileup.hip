@@ -16,6 +16,7 @@
 //   identity_kernel thread per column      : matches per read (only when -f > 0)
 //   project_kernel  thread per column      : motif tests, plane lookup, wave-aggregated append of 12-byte records
 //   count_kernel    thread per record      : atomic add into pcov / ncov, atomic max into the motif key
+//   count_hp_kernel the same + one more atomic add into the record's haplotype planes (partitions = 2 only)
 //   loci_*          covered loci of a range in ascending order (count per block, scan, write)
 #include <hip/hip_runtime.h>
 
@@ -75,7 +76,7 @@ struct PRead {
     int32_t l_qseq;
     uint32_t order;
     int32_t as_size;    // alignment columns incl. gaps (denominator of the identity)
-    uint8_t rev, primary, pass, pad;
+    uint8_t rev, primary, pass, hp;  // hp: haplotype partition 0 (none), 1, 2
 };
 
 struct PRun {
@@ -94,7 +95,7 @@ struct PMod {
 
 struct PRec {           // 12 bytes
     uint32_t glo;       // gpos & 0xffffffff
-    uint32_t hi;        // gpos >> 32 (8 bits) | prob << 8 | motif << 16
+    uint32_t hi;        // gpos >> 32 (8 bits) | prob << 8 | motif << 16 | hp << 18 (consumers mask motif with & 3)
     uint32_t order;
 };
 
@@ -244,7 +245,7 @@ __global__ __launch_bounds__(TPB) void project_kernel(const PRun* __restrict__ r
                     if (v & 0x100u) {
                         e = true;
                         r.glo = (uint32_t)soff;
-                        r.hi = (uint32_t)((uint64_t)soff >> 32) | ((v & 255u) << 8) | (motif << 16);
+                        r.hi = (uint32_t)((uint64_t)soff >> 32) | ((v & 255u) << 8) | (motif << 16) | ((uint32_t)rd.hp << 18);
                         r.order = rd.order;
                     }
                 };
@@ -285,6 +286,26 @@ __global__ __launch_bounds__(TPB) void count_kernel(const PRec* __restrict__ rec
         const uint32_t thr = (thr_packed >> (8 * motif)) & 255u;
         atomicAdd(prob >= thr ? &pcov[g] : &ncov[g], 1);
         atomicMax(&key[g], (r.order << 2) | motif);
+    }
+}
+
+// count_kernel plus the haplotype partitions: a record tagged hp 1 / 2 also adds to that partition's pcov / ncov with the
+// same threshold.  No key atomics here: a partition's loci take their motif from the combined key plane.
+__global__ __launch_bounds__(TPB) void count_hp_kernel(const PRec* __restrict__ recs, int64_t n, uint32_t thr_packed,
+                                                        int32_t* __restrict__ pcov, int32_t* __restrict__ ncov,
+                                                        uint32_t* __restrict__ key, int32_t* __restrict__ pcov1,
+                                                        int32_t* __restrict__ ncov1, int32_t* __restrict__ pcov2,
+                                                        int32_t* __restrict__ ncov2) {
+    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
+        const PRec r = recs[i];
+        const int64_t g = (int64_t)r.glo | ((int64_t)(r.hi & 255u) << 32);
+        const uint32_t prob = (r.hi >> 8) & 255u, motif = (r.hi >> 16) & 3u, hp = (r.hi >> 18) & 3u;
+        const uint32_t thr = (thr_packed >> (8 * motif)) & 255u;
+        const bool pos = prob >= thr;
+        atomicAdd(pos ? &pcov[g] : &ncov[g], 1);
+        atomicMax(&key[g], (r.order << 2) | motif);
+        if (hp == 1u) atomicAdd(pos ? &pcov1[g] : &ncov1[g], 1);
+        else if (hp == 2u) atomicAdd(pos ? &pcov2[g] : &ncov2[g], 1);
     }
 }
 
@@ -402,6 +423,11 @@ struct hm_pileup {
     int32_t* pcov = nullptr;
     int32_t* ncov = nullptr;
     uint32_t* key = nullptr;
+    // haplotype partitions ("partitions" = 2): pcov / ncov planes of HP 1 and HP 2, +16 B per reference base
+    int partitions = 0;
+    DevBuf d_hp_pcov[2], d_hp_ncov[2];
+    int32_t* hp_pcov[2] = {nullptr, nullptr};
+    int32_t* hp_ncov[2] = {nullptr, nullptr};
 
     // staged batch (host)
     std::vector<uint8_t> slab;
@@ -488,7 +514,7 @@ void hm_pileup_destroy(hm_pileup_t* p) {
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     for (DevBuf* b : {&p->d_ref, &p->d_pcov, &p->d_ncov, &p->d_key, &p->d_slab, &p->d_reads, &p->d_runs, &p->d_col0,
                       &p->d_mods, &p->d_plane, &p->d_matches, &p->d_bins, &p->d_counter, &p->d_recs, &p->d_blk,
-                      &p->d_offs, &p->d_loci})
+                      &p->d_offs, &p->d_loci, &p->d_hp_pcov[0], &p->d_hp_pcov[1], &p->d_hp_ncov[0], &p->d_hp_ncov[1]})
         b->release();
     if (p->stream) (void)hipStreamDestroy(p->stream);
     delete p;
@@ -501,7 +527,12 @@ int hm_pileup_set_option(hm_pileup_t* p, const char* key, double value) {
     const std::string k = key;
     if (k == "min_mapq") p->min_mapq = (int)value;
     else if (k == "min_pi") p->min_pi = value;
-    else return pfail(p, HM_EINVAL, "unknown option " + k);
+    else if (k == "partitions") {  // the planes are sized when the reference arrives: decide before that
+        if (!p->seq_off.empty() || !p->own_planes)
+            return pfail(p, HM_ESTATE, "partitions must be set before hm_pileup_set_reference / hm_pileup_use_planes");
+        if (value != 0.0 && value != 2.0) return pfail(p, HM_EINVAL, "partitions must be 0 or 2");
+        p->partitions = (int)value;
+    } else return pfail(p, HM_EINVAL, "unknown option " + k);
     return HM_OK;
 }
 
@@ -511,6 +542,23 @@ int hm_pileup_use_planes(hm_pileup_t* p, void* pcov, void* ncov, void* key) {
     p->pcov = static_cast<int32_t*>(pcov);
     p->ncov = static_cast<int32_t*>(ncov);
     p->key = static_cast<uint32_t*>(key);
+    return HM_OK;
+}
+
+int hm_pileup_use_partition_planes(hm_pileup_t* p, int32_t part, void* pcov, void* ncov) {
+    if (!p || !pcov || !ncov || (part != 1 && part != 2)) return pfail(p, HM_EINVAL, "hm_pileup_use_partition_planes: bad argument");
+    if (p->partitions != 2) return pfail(p, HM_ESTATE, "hm_pileup_use_partition_planes without the partitions option");
+    p->hp_pcov[part - 1] = static_cast<int32_t*>(pcov);
+    p->hp_ncov[part - 1] = static_cast<int32_t*>(ncov);
+    return HM_OK;
+}
+
+int hm_pileup_partition_planes(hm_pileup_t* p, int32_t part, void** pcov, void** ncov) {
+    if (!p || (part != 1 && part != 2)) return pfail(p, HM_EINVAL, "hm_pileup_partition_planes: part must be 1 or 2");
+    if (p->partitions != 2 || !p->hp_pcov[part - 1])
+        return pfail(p, HM_ESTATE, "no partition planes (partitions option off, or before hm_pileup_set_reference)");
+    if (pcov) *pcov = p->hp_pcov[part - 1];
+    if (ncov) *ncov = p->hp_ncov[part - 1];
     return HM_OK;
 }
 
@@ -539,6 +587,18 @@ int hm_pileup_set_reference(hm_pileup_t* p, int32_t n_seqs, const int64_t* seq_l
             HIP_TRY(hipMemsetAsync(p->ncov, 0, bytes, p->stream));
             HIP_TRY(hipMemsetAsync(p->key, 0, bytes, p->stream));
         }
+        if (p->partitions == 2) {
+            const size_t bytes = (size_t)std::max<int64_t>(total, 1) * 4;
+            for (int k = 0; k < 2; ++k) {
+                if (p->hp_pcov[k]) continue;  // caller-owned (hm_pileup_use_partition_planes)
+                p->d_hp_pcov[k].reserve(bytes, 0, nullptr, true);
+                p->d_hp_ncov[k].reserve(bytes, 0, nullptr, true);
+                p->hp_pcov[k] = p->d_hp_pcov[k].as<int32_t>();
+                p->hp_ncov[k] = p->d_hp_ncov[k].as<int32_t>();
+                HIP_TRY(hipMemsetAsync(p->hp_pcov[k], 0, bytes, p->stream));
+                HIP_TRY(hipMemsetAsync(p->hp_ncov[k], 0, bytes, p->stream));
+            }
+        }
         HIP_TRY(hipStreamSynchronize(p->stream));
     } catch (const HipErr& h) {
         return pfail_hip(p, h);
@@ -558,7 +618,15 @@ int hm_pileup_planes(hm_pileup_t* p, void** pcov, void** ncov, void** key, int64
 int hm_pileup_submit_read(hm_pileup_t* p, uint32_t order, int32_t flag, int32_t sid, int64_t pos, int32_t mapq,
                           int32_t l_qseq, const uint8_t* seq4, int32_t n_cigar, const uint32_t* cigar, int64_t n_mods,
                           const hm_mod_t* mods) {
+    return hm_pileup_submit_read_hp(p, order, flag, sid, pos, mapq, l_qseq, seq4, n_cigar, cigar, n_mods, mods, 0);
+}
+
+int hm_pileup_submit_read_hp(hm_pileup_t* p, uint32_t order, int32_t flag, int32_t sid, int64_t pos, int32_t mapq,
+                             int32_t l_qseq, const uint8_t* seq4, int32_t n_cigar, const uint32_t* cigar, int64_t n_mods,
+                             const hm_mod_t* mods, int32_t hp) {
     if (!p) return HM_EINVAL;
+    if (hp < 0 || hp > 2) return pfail(p, HM_EINVAL, "haplotype partition must be 0, 1 or 2");
+    if (hp && p->partitions != 2) return pfail(p, HM_ESTATE, "haplotype partition given but the partitions option is off");
     if (p->seq_off.empty()) return pfail(p, HM_ESTATE, "hm_pileup_submit_read before hm_pileup_set_reference");
     if (n_mods <= 0 || (flag & 4)) return 0;  // pileup.cpp:233-235
     if (n_mods >= (int64_t(1) << 22)) return pfail(p, HM_EINVAL, "more than 2^22 modification entries in one read");
@@ -636,6 +704,7 @@ int hm_pileup_submit_read(hm_pileup_t* p, uint32_t order, int32_t flag, int32_t 
     r.rev = (flag & 16) ? 1 : 0;
     r.primary = (flag & 0x900) ? 0 : 1;
     r.pass = mapq >= p->min_mapq ? 1 : 0;
+    r.hp = (uint8_t)hp;
     const int32_t ri = (int32_t)p->reads.size();
     const size_t mods_before = p->mods.size();
     const int64_t m_before = p->n_m_mods;
@@ -779,13 +848,20 @@ int hm_pileup_label_histograms(hm_pileup_t* p, const int8_t* labels, int64_t n_l
 int hm_pileup_count(hm_pileup_t* p, const uint8_t thr[3]) {
     if (!p || !thr) return HM_EINVAL;
     if (!p->pcov) return pfail(p, HM_ESTATE, "hm_pileup_count before hm_pileup_set_reference / hm_pileup_use_planes");
+    if (p->partitions == 2 && (!p->hp_pcov[0] || !p->hp_pcov[1]))
+        return pfail(p, HM_ESTATE, "hm_pileup_count without partition planes (hm_pileup_set_reference / hm_pileup_use_partition_planes)");
     try {
         HIP_TRY(hipSetDevice(p->device));
         ensure_bins(p);
         if (p->n_recs) {
             const uint32_t packed = thr[0] | ((uint32_t)thr[1] << 8) | ((uint32_t)thr[2] << 16);
-            hipLaunchKernelGGL(count_kernel, dim3(grid_for(p->n_recs, 1 << 16)), dim3(TPB), 0, p->stream, p->d_recs.as<PRec>(),
-                               p->n_recs, packed, p->pcov, p->ncov, p->key);
+            if (p->partitions == 2)
+                hipLaunchKernelGGL(count_hp_kernel, dim3(grid_for(p->n_recs, 1 << 16)), dim3(TPB), 0, p->stream,
+                                   p->d_recs.as<PRec>(), p->n_recs, packed, p->pcov, p->ncov, p->key, p->hp_pcov[0],
+                                   p->hp_ncov[0], p->hp_pcov[1], p->hp_ncov[1]);
+            else
+                hipLaunchKernelGGL(count_kernel, dim3(grid_for(p->n_recs, 1 << 16)), dim3(TPB), 0, p->stream, p->d_recs.as<PRec>(),
+                                   p->n_recs, packed, p->pcov, p->ncov, p->key);
             HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipMemsetAsync(p->d_counter.p, 0, sizeof(unsigned long long), p->stream));

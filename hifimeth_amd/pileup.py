@@ -9,6 +9,10 @@
     loci = pu.loci()                          # rows of the three BED files
     text = pu.bed(loci)
 
+Haplotype-resolved (`partitions=True`): records whose `hp` is 1 or 2 (the BAM's HP tag) are also counted into that
+partition's planes with the same thresholds; `pu.loci(partition=1)` / `pu.loci(partition=2)` are the rows of
+<prefix>.hap1.* / <prefix>.hap2.*, each locus in the context of the combined output.
+
 Multi-GPU (one process per GPU, records dealt to ranks in slabs): `reduce_over_ranks` sums the histograms with an
 all-reduce before the thresholds are resolved, and after counting reduce-scatters the per-locus planes (sum for
 pcov / ncov, max for the motif key) so that every rank ends up owning one contiguous range of loci.
@@ -86,9 +90,11 @@ def resolve_threshold(bins) -> Tuple[int, int]:
 
 class MethylationPileup:
     def __init__(self, genome: Sequence[Tuple[str, str]], device: int = 0, min_mapq: int = 0, min_pi: float = 0.0,
-                 planes=None):
+                 planes=None, partitions: bool = False, partition_planes=None):
         """planes: optional (pcov, ncov, key) torch CUDA tensors (int32, int32, int32-as-bits) of total genome length
-        that the engine counts into -- used when a collective consumes them afterwards."""
+        that the engine counts into -- used when a collective consumes them afterwards.
+        partitions: also count per haplotype (HP 1 / 2); partition_planes: optional ((pcov1, ncov1), (pcov2, ncov2)) int32
+        torch CUDA tensors for them, like `planes`."""
         self._L = lib()
         self._h = C.c_void_p()
         if self._L.hm_pileup_create(C.byref(self._h), device) != 0:
@@ -98,8 +104,15 @@ class MethylationPileup:
         self.offsets = np.concatenate([[0], np.cumsum(self.lengths)])
         self._planes = planes
         self._order = 0
+        self.partitions = bool(partitions)
         self._check(self._L.hm_pileup_set_option(self._h, b"min_mapq", float(min_mapq)))
         self._check(self._L.hm_pileup_set_option(self._h, b"min_pi", float(min_pi)))
+        if self.partitions:
+            self._check(self._L.hm_pileup_set_option(self._h, b"partitions", 2.0))
+            for part, pair in enumerate(partition_planes or (), 1):
+                self._check(self._L.hm_pileup_use_partition_planes(self._h, part, *(C.c_void_p(t.data_ptr()) for t in pair)))
+        elif partition_planes is not None:
+            raise HifimethError("partition_planes without partitions=True")
         if planes is not None:
             self._check(self._L.hm_pileup_use_planes(self._h, *(C.c_void_p(t.data_ptr()) for t in planes)))
         bases = "".join(s for _, s in genome).upper().encode()
@@ -127,7 +140,8 @@ class MethylationPileup:
         return int(self.offsets[-1])
 
     def add(self, read, order: Optional[int] = None) -> int:
-        """read: synth.AlignedRead-like (flag, tid, pos, mapq, cigar_u32(), seq, seq4, mm, ml).  -> 1 staged / 0 skipped"""
+        """read: synth.AlignedRead-like (flag, tid, pos, mapq, cigar_u32(), seq, seq4, mm, ml[, hp]).  -> 1 staged / 0 skipped.
+        With partitions, a read whose hp is 1 or 2 is also counted in that partition; any other hp only in the combined output."""
         if order is None:
             order = self._order
         self._order = order + 1
@@ -136,9 +150,12 @@ class MethylationPileup:
             return 0
         seq4 = np.ascontiguousarray(read.seq4, np.uint8)
         cig = np.ascontiguousarray(read.cigar_u32(), np.uint32)
-        return self._check(self._L.hm_pileup_submit_read(
-            self._h, order, read.flag, read.tid, read.pos, read.mapq, len(read.seq), seq4.ctypes.data_as(C.c_void_p),
-            len(cig), cig.ctypes.data_as(C.c_void_p), len(mods), mods.ctypes.data_as(C.c_void_p)))
+        args = (self._h, order, read.flag, read.tid, read.pos, read.mapq, len(read.seq), seq4.ctypes.data_as(C.c_void_p),
+                len(cig), cig.ctypes.data_as(C.c_void_p), len(mods), mods.ctypes.data_as(C.c_void_p))
+        if not self.partitions:
+            return self._check(self._L.hm_pileup_submit_read(*args))
+        hp = getattr(read, "hp", None)
+        return self._check(self._L.hm_pileup_submit_read_hp(*args, hp if hp in (1, 2) else 0))
 
     def flush(self):
         self._check(self._L.hm_pileup_run(self._h))
@@ -175,10 +192,18 @@ class MethylationPileup:
         t = np.asarray(thresholds, np.uint8)
         self._check(self._L.hm_pileup_count(self._h, t.ctypes.data_as(C.c_void_p)))
 
-    def loci(self, lo: int = 0, hi: Optional[int] = None, planes=None, plane_base: int = 0) -> np.ndarray:
-        """covered loci of [lo, hi) (plane coordinates) in ascending order; planes = torch tensors or None (own)"""
+    def loci(self, lo: int = 0, hi: Optional[int] = None, planes=None, plane_base: int = 0, partition: int = 0) -> np.ndarray:
+        """covered loci of [lo, hi) (plane coordinates) in ascending order; planes = torch tensors or None (own).
+        partition 1 / 2 (planes None): that haplotype's counts, motif from the combined key plane."""
         hi = self.n_loci if hi is None else hi
-        ptrs = [None, None, None] if planes is None else [C.c_void_p(t.data_ptr()) for t in planes]
+        if planes is not None:
+            ptrs = [C.c_void_p(t.data_ptr()) for t in planes]
+        elif partition:
+            pc, nc = C.c_void_p(), C.c_void_p()
+            self._check(self._L.hm_pileup_partition_planes(self._h, partition, C.byref(pc), C.byref(nc)))
+            ptrs = [pc, nc, None]                 # key NULL = the engine's combined key plane
+        else:
+            ptrs = [None, None, None]
         n = self._check(self._L.hm_pileup_fetch_loci(self._h, *ptrs, plane_base, lo, hi, None, 0))
         out = np.zeros(n, LOCUS_DTYPE)
         if n:
@@ -208,6 +233,28 @@ def allreduce_histograms(dist, bins: np.ndarray, device: str = "cpu") -> np.ndar
     if dist.is_initialized():
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
     return t.cpu().numpy().astype(np.uint64).reshape(3, 256)
+
+
+def reduce_scatter_sum(dist, planes, force: bool = False):
+    """the SUM half of reduce_scatter_planes for further count planes (the haplotype partitions' pcov / ncov) -> (slices,
+    base); same layout and the same RCCL / gloo split"""
+    world = dist.get_world_size() if dist.is_initialized() else 1
+    rank = dist.get_rank() if dist.is_initialized() else 0
+    if world == 1 and not (force and dist.is_initialized()):
+        return list(planes), 0
+    import torch
+    outs = []
+    for t in planes:
+        assert t.numel() % world == 0
+        chunk = t.numel() // world
+        if t.is_cuda:
+            o = torch.empty(chunk, dtype=t.dtype, device=t.device)
+            dist.reduce_scatter_tensor(o, t, op=dist.ReduceOp.SUM)
+        else:
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+            o = t[rank * chunk:(rank + 1) * chunk].clone()
+        outs.append(o)
+    return outs, rank * (planes[0].numel() // world)
 
 
 def reduce_scatter_planes(dist, pcov, ncov, key, force: bool = False):

@@ -1,7 +1,7 @@
 """`hifimeth pileup` over N GPUs of one node, one process per GPU (the path's only exchange step).
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
-        -m hifimeth_amd.pileup_dist [-q mapQ] [-f identity] reference.fa mod.bam output-prefix
+        -m hifimeth_amd.pileup_dist [-q mapQ] [-f identity] [-H] reference.fa mod.bam output-prefix
 
 Records are dealt to the ranks in slabs of `--slab` records (round-robin, like the `call` path).  Each rank projects its
 records and histograms them on its own GPU; then
@@ -11,6 +11,8 @@ records and histograms them on its own GPU; then
                                                                  -> rank r owns loci [r*chunk, (r+1)*chunk),
   4. every rank compacts and formats its range; rank 0 concatenates the parts in rank order (= locus order).
 A single process (no torchrun) runs the same code with the collectives skipped.
+-H (haplotypes): four more planes (pcov / ncov of HP 1 and HP 2) are counted with the same thresholds, reduce-scattered
+with SUM next to the three above, and rank 0 also writes <prefix>.hap1.<ctx>.cov.bed / <prefix>.hap2.<ctx>.cov.bed.
 """
 from __future__ import annotations
 
@@ -22,11 +24,12 @@ import numpy as np
 
 from . import dist as D
 from .bamio import is_coordinate_sorted, load_fasta, read_bam
-from .pileup import CTX_NAMES, MethylationPileup, allreduce_histograms, locus_ranges, reduce_scatter_planes, resolve_threshold
+from .pileup import (CTX_NAMES, MethylationPileup, allreduce_histograms, locus_ranges, reduce_scatter_planes, reduce_scatter_sum,
+                     resolve_threshold)
 
 
 def run(reference: str, bam: str, prefix: str, min_mapq: int = 0, min_pi: float = 0.0, slab: int = 256,
-        batch: int = 256, backend: str | None = None, log=sys.stderr):
+        batch: int = 256, backend: str | None = None, log=sys.stderr, haplotypes: bool = False):
     import torch
     rank, local_rank, world = D.env_world()
     dist = D.init_process_group(backend, force=bool(os.environ.get("HM_FORCE_COLLECTIVES")))
@@ -55,8 +58,10 @@ def run(reference: str, bam: str, prefix: str, min_mapq: int = 0, min_pi: float 
     dev = torch.device("cuda", local_rank % ndev)
     torch.cuda.set_device(dev)
     planes = [torch.zeros(world * chunk, dtype=torch.int32, device=dev) for _ in range(3)]
+    hp_planes = [torch.zeros(world * chunk, dtype=torch.int32, device=dev) for _ in range(4)] if haplotypes else []
     torch.cuda.synchronize()
-    pu = MethylationPileup(genome, device=dev.index, min_mapq=min_mapq, min_pi=min_pi, planes=planes)
+    pu = MethylationPileup(genome, device=dev.index, min_mapq=min_mapq, min_pi=min_pi, planes=planes, partitions=haplotypes,
+                           partition_planes=(hp_planes[0:2], hp_planes[2:4]) if haplotypes else None)
     staged = 0
     for order, rec in enumerate(records):
         if (order // slab) % world != rank or rec.flag & 4 or rec.mm is None:
@@ -95,24 +100,30 @@ def run(reference: str, bam: str, prefix: str, min_mapq: int = 0, min_pi: float 
             host = [t.cpu() for t in planes]
             pc, nc, key, base = reduce_scatter_planes(dist, *host)
             pc, nc, key = (t.to(dev) for t in (pc, nc, key))
+            hp = [t.to(dev) for t in reduce_scatter_sum(dist, [t.cpu() for t in hp_planes])[0]] if haplotypes else []
         else:
             pc, nc, key, base = reduce_scatter_planes(dist, *planes, force=True)
+            hp = reduce_scatter_sum(dist, hp_planes, force=True)[0] if haplotypes else []
         torch.cuda.synchronize()
     else:
         pc, nc, key, base = planes[0], planes[1], planes[2], 0
+        hp = hp_planes
     lo, hi = ranges[rank]
     loci = pu.loci(0, hi - lo, planes=(pc, nc, key), plane_base=base)
-    part = pu.bed(loci)
+    part = {"": pu.bed(loci)}                               # file tag -> {context: text}
+    for k in range(len(hp) // 2):                           # a partition: its counts, the combined key's motif
+        part[f"hap{k + 1}."] = pu.bed(pu.loci(0, hi - lo, planes=(hp[2 * k], hp[2 * k + 1], key), plane_base=base))
     if dist is not None:
         parts = [None] * world if rank == 0 else None
         dist.gather_object(part, parts, dst=0)
     else:
         parts = [part]
     if rank == 0:
-        for c in CTX_NAMES:
-            with open(f"{prefix}.{c}.cov.bed", "w") as f:
-                for p in parts:
-                    f.write(p[c])
+        for tag in parts[0]:
+            for c in CTX_NAMES:
+                with open(f"{prefix}.{tag}{c}.cov.bed", "w") as f:
+                    for p in parts:
+                        f.write(p[tag][c])
     pu.close()
     if dist is not None:
         dist.barrier()
@@ -126,11 +137,13 @@ def main(argv=None):
     ap.add_argument("-f", type=float, default=0.0, help="minimum alignment identity (percent)")
     ap.add_argument("--slab", type=int, default=256, help="records per slab dealt to a rank")
     ap.add_argument("--backend", default=None, help="nccl (RCCL, default on GPUs) or gloo")
+    ap.add_argument("-H", dest="haplotypes", action="store_true",
+                    help="haplotype-resolved output: also <prefix>.hap1.* / <prefix>.hap2.* from the HP tag")
     ap.add_argument("reference")
     ap.add_argument("mod_bam")
     ap.add_argument("output_prefix")
     a = ap.parse_args(argv)
-    return run(a.reference, a.mod_bam, a.output_prefix, a.q, a.f, slab=a.slab, backend=a.backend)
+    return run(a.reference, a.mod_bam, a.output_prefix, a.q, a.f, slab=a.slab, backend=a.backend, haplotypes=a.haplotypes)
 
 
 if __name__ == "__main__":

@@ -225,6 +225,7 @@ class AlignedRead:
     seq: str             # SEQ as stored (reference orientation)
     mm: Optional[str]
     ml: Optional[np.ndarray]
+    hp: Optional[int] = None   # HP aux tag (phasing haplotype); None = untagged
 
     @property
     def l_qseq(self) -> int:

@@ -205,8 +205,8 @@ int hm_reset_timing(hm_engine_t* e);
  *   3 x 256 probability histograms          (pileup.cpp:237-272)                     -> hm_pileup_histograms
  *   per-locus pcov / ncov / motif           (pileup.cpp:519-560)                     -> hm_pileup_count
  *   rows of <prefix>.<ctx>.cov.bed          (pileup.cpp:562-590)                     -> hm_pileup_fetch_loci
- * The whole genome's counters stay resident in HBM (12 B per reference base) and the projected calls wait in
- * HBM (12 B each) until the thresholds are known -- the reference spills them to a temporary file instead.
+ * The whole genome's counters stay resident in HBM (12 B per reference base, 28 B with the haplotype partitions) and the
+ * projected calls wait in HBM (12 B each) until the thresholds are known -- the reference spills them to a temporary file.
  * MM/ML parsing and BED text formatting stay on the host (hm_bam.h).                                           */
 typedef struct hm_pileup hm_pileup_t;
 
@@ -230,7 +230,8 @@ typedef struct {
 int hm_pileup_create(hm_pileup_t** out, int device);
 void hm_pileup_destroy(hm_pileup_t* p);
 const char* hm_pileup_last_error(const hm_pileup_t* p); /* p may be NULL: error of a failed create */
-/* options: "min_mapq" (-q, default 0), "min_pi" (-f, default 0.0) */
+/* options: "min_mapq" (-q, default 0), "min_pi" (-f, default 0.0), "partitions" (0 default, or 2: haplotype-resolved
+ * counting, see hm_pileup_submit_read_hp; must be set before hm_pileup_set_reference / hm_pileup_use_planes, else HM_ESTATE) */
 int hm_pileup_set_option(hm_pileup_t* p, const char* key, double value);
 /* HbnDatabase: n_seqs upper-cased sequences back to back in `bases` (seq_len[i] bytes each).  Allocates and
  * zeroes the per-locus planes unless hm_pileup_use_planes was called before. */
@@ -239,6 +240,13 @@ int hm_pileup_set_reference(hm_pileup_t* p, int32_t n_seqs, const int64_t* seq_l
  * e.g. torch tensors that a RCCL reduce-scatter will consume.  The caller zeroes them. */
 int hm_pileup_use_planes(hm_pileup_t* p, void* pcov, void* ncov, void* key);
 int hm_pileup_planes(hm_pileup_t* p, void** pcov, void** ncov, void** key, int64_t* n_loci);
+/* Haplotype partitions (option "partitions" = 2): two more int32 pcov / ncov plane pairs (+16 B per reference base), counted
+ * with the combined thresholds; a partition has no key plane of its own -- its loci take the combined motif.  `part` is 1 or 2.
+ * hm_pileup_set_reference allocates and zeroes the pairs that were not registered here before (caller-owned DEVICE planes
+ * of total-reference-length elements, zeroed by the caller).  A partition's covered loci come from hm_pileup_fetch_loci
+ * with that partition's pcov / ncov and the combined key plane. */
+int hm_pileup_use_partition_planes(hm_pileup_t* p, int32_t part, void* pcov, void* ncov);
+int hm_pileup_partition_planes(hm_pileup_t* p, int32_t part, void** pcov, void** ncov);
 /* One mapped record: `order` = its index in the BAM, < 2^29 (decides the motif of a locus hit by two classes), `sid` =
  * index into the reference sequences, SEQ 4-bit packed and CIGAR as the BAM record stores them, `mods` = its
  * parsed MM/ML lists.  Returns 1 if staged, 0 if the record contributes nothing (unmapped, no mods), < 0 on
@@ -246,6 +254,11 @@ int hm_pileup_planes(hm_pileup_t* p, void** pcov, void** ncov, void** key, int64
 int hm_pileup_submit_read(hm_pileup_t* p, uint32_t order, int32_t flag, int32_t sid, int64_t pos, int32_t mapq,
                           int32_t l_qseq, const uint8_t* seq4, int32_t n_cigar, const uint32_t* cigar,
                           int64_t n_mods, const hm_mod_t* mods);
+/* the same with the record's haplotype partition `hp`: 0 (combined output only; = hm_pileup_submit_read), 1 or 2 (also
+ * counted in that partition).  HM_EINVAL for hp outside {0, 1, 2}, HM_ESTATE for hp != 0 without the partitions option. */
+int hm_pileup_submit_read_hp(hm_pileup_t* p, uint32_t order, int32_t flag, int32_t sid, int64_t pos, int32_t mapq,
+                             int32_t l_qseq, const uint8_t* seq4, int32_t n_cigar, const uint32_t* cigar,
+                             int64_t n_mods, const hm_mod_t* mods, int32_t hp);
 /* histograms + projection of the staged records; the projected calls are appended to the HBM-resident list */
 int hm_pileup_run(hm_pileup_t* p);
 int64_t hm_pileup_num_records(hm_pileup_t* p);
@@ -259,7 +272,8 @@ int64_t hm_pileup_fetch_records(hm_pileup_t* p, int64_t* gpos, uint8_t* prob, ui
  * eval.cpp:42-114) -- into bins[(motif * 2 + label) * 256 + scaled_prob].  The records stay resident. */
 int hm_pileup_label_histograms(hm_pileup_t* p, const int8_t* labels, int64_t n_labels, uint64_t* bins1536);
 /* zero-free accumulate of all resident records into the planes with the given per-context thresholds
- * (prob >= thr -> pcov else ncov; key = max(order << 2 | motif)); then drops the records */
+ * (prob >= thr -> pcov else ncov; key = max(order << 2 | motif)), with partitions also into the record's partition
+ * planes; then drops the records */
 int hm_pileup_count(hm_pileup_t* p, const uint8_t thr[3]);
 /* covered loci (pcov + ncov > 0) of planes[lo, hi) in ascending order; planes NULL = the engine's own, else
  * DEVICE pointers whose element 0 is locus `plane_base`.  Returns the number of loci (may exceed cap: then

@@ -5,8 +5,10 @@ A random genome, error-free reads (one '=' CIGAR op each, both strands) with cal
 parsed once on the host and the staged batches are replayed, so the timed region is what the GPU does per batch:
 H2D of the staged records, plane memset, mods_kernel, project_kernel, then count_kernel and the covered-loci
 compaction at the end.  Prints one JSON object; `--check` verifies that the per-locus counters add up to the number of projected calls.
+`--partitions`: the haplotype-resolved engine (`pileup -H`), every read tagged with a random HP of {none, 1, 2}; the loci
+fetch then also compacts the two partitions' planes.
 
-    python tools/pileup_bench.py --genome-mb 20 --coverage 10
+    python tools/pileup_bench.py --genome-mb 20 --coverage 10 [--partitions]
 """
 import argparse
 import ctypes as C
@@ -80,6 +82,7 @@ def main():
     ap.add_argument("--batch", type=int, default=512, help="reads per hm_pileup_run")
     ap.add_argument("--repeat", type=int, default=3, help="timed passes over the staged read set")
     ap.add_argument("--check", action="store_true")
+    ap.add_argument("--partitions", action="store_true", help="haplotype partitions on, reads tagged with random HP")
     ap.add_argument("--cpu-baseline", action="store_true",
                     help="time the reference's own projection code (oracle/_ref/ref_align -t) on a bounded sample")
     a = ap.parse_args()
@@ -104,14 +107,16 @@ def main():
         staged.append((16 if rev else 0, int(s), pack_codes(lut[seq]), np.array([(a.read_len << 4) | 7], np.uint32), mods))
     t_prep = time.perf_counter() - t0
     n_mods = sum(len(x[4]) for x in staged)
+    hp = np.random.default_rng(2).integers(0, 3, n_reads) if a.partitions else np.zeros(n_reads, np.int64)
 
-    pu = MethylationPileup(genome)
+    pu = MethylationPileup(genome, partitions=a.partitions)
     L = pu._L
 
     def one_pass():
         for i, (flag, pos, seq4, cig, mods) in enumerate(staged):
-            rc = L.hm_pileup_submit_read(pu._h, i, flag, 0, pos, 60, a.read_len, seq4.ctypes.data_as(C.c_void_p), 1,
-                                         cig.ctypes.data_as(C.c_void_p), len(mods), mods.ctypes.data_as(C.c_void_p))
+            args = (pu._h, i, flag, 0, pos, 60, a.read_len, seq4.ctypes.data_as(C.c_void_p), 1,
+                    cig.ctypes.data_as(C.c_void_p), len(mods), mods.ctypes.data_as(C.c_void_p))
+            rc = L.hm_pileup_submit_read_hp(*args, int(hp[i])) if a.partitions else L.hm_pileup_submit_read(*args)
             assert rc == 1
             if (i + 1) % a.batch == 0:
                 pu.flush()
@@ -130,6 +135,11 @@ def main():
     t0 = time.perf_counter()
     loci = pu.loci()
     t_loci = time.perf_counter() - t0
+    hp_loci = []
+    if a.partitions:
+        t0 = time.perf_counter()
+        hp_loci = [pu.loci(partition=k) for k in (1, 2)]
+        t_hp_loci = time.perf_counter() - t0
     cols = n_reads * a.read_len
     out = dict(genome_bases=G, reads=n_reads, aligned_columns=cols, mods=n_mods, records_per_pass=recs_per_pass,
                host_prep_s=round(t_prep, 2),
@@ -138,10 +148,19 @@ def main():
                count_s=round(t_count, 4), records_counted=recs_per_pass * a.repeat,
                records_per_s_count=round(recs_per_pass * a.repeat / t_count),
                covered_loci=int(len(loci)), loci_fetch_s=round(t_loci, 4),
-               loci_scan_bases_per_s=round(G / t_loci))
+               loci_scan_bases_per_s=round(G / t_loci), partitions=a.partitions)
+    if a.partitions:
+        out.update(partition_loci=[int(len(x)) for x in hp_loci], partition_loci_fetch_s=round(t_hp_loci, 4))
     if a.check:                                    # every pass (and the warm-up) adds the same records
         total = int((loci["pcov"].astype(np.int64) + loci["ncov"]).sum())
         out["check_total_records"] = total == recs_per_pass * (a.repeat + 1)
+        if a.partitions:                           # hap1 + hap2 <= combined at every locus, and the tagged share is counted once
+            add = np.zeros((len(loci), 2), np.int64)
+            for x in hp_loci:                      # both lists ascending; a partition locus is a combined locus
+                j = np.searchsorted(loci["gpos"], x["gpos"])
+                np.add.at(add, (j, 0), x["pcov"])
+                np.add.at(add, (j, 1), x["ncov"])
+            out["check_partitions_within_combined"] = bool((add[:, 0] <= loci["pcov"]).all() and (add[:, 1] <= loci["ncov"]).all())
     if a.cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(genome, chrom, starts, staged, a.read_len)
     print(json.dumps(out))
