@@ -207,6 +207,14 @@ class MethylationCaller:
         self._check(self._L.hm_scan_sites(self._h, ctx, _vp(rid), _vp(qoff), _vp(strand), n), "hm_scan_sites")
         return rid, qoff, strand
 
+    def site_logits(self, ctx: int) -> np.ndarray:
+        """The CNN's logits [n, 2] float32 for the staged batch's sites of context ctx, in scan_sites order."""
+        self.sync()
+        n = self.num_sites(ctx)
+        out = np.empty((n, 2), np.float32)
+        got = self._check(self._L.hm_site_logits(self._h, ctx, _vp(out), n), "hm_site_logits")
+        return out[:got]
+
     def windows(self, ctx: int, first: int = 0, n: Optional[int] = None, fetch: bool = True):
         """get_next_sample_features for sites [first, first+n) of context ctx -> float32 [n, 401, 8]."""
         if n is None:

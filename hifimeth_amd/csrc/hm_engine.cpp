@@ -973,6 +973,8 @@ int hm_set_option(hm_engine_t* e, const char* key, int64_t value) {
         e->edge_impl = (int)value;
     } else if (k == "tail_impl") {
         if (value < 0 || value > 3) return fail(e, HM_EINVAL, "tail_impl must be 0, 1, 2 or 3");
+        if (e->precision == 2 && (value == 0 || value == 2))   // those tails have no fp16-weight variant: they would run precision 1
+            return fail(e, HM_EINVAL, "tail_impl 0 and 2 do not carry precision 2 (fp16 weights in conv8 and fc1): use tail_impl 1 or 3");
         e->tail_impl = (int)value;
     } else if (k == "tail_slice") {
         if (value < 16) return fail(e, HM_EINVAL, "tail_slice must be at least 16");
@@ -1312,6 +1314,34 @@ int64_t hm_scan_sites(hm_engine_t* e, int ctx, int32_t* read_id, int32_t* qoff, 
             if (read_id) read_id[i] = b->reads.p[(size_t)s[(size_t)i].read_idx].read_id;
             if (qoff) qoff[i] = s[(size_t)i].qoff;
             if (strand) strand[i] = tag[(size_t)s[(size_t)i].uidx] >> 2;
+        }
+        return n;
+    } catch (const HipErr& h) {
+        return fail_hip(e, h);
+    }
+}
+
+int64_t hm_site_logits(hm_engine_t* e, int ctx, float* logits, int64_t cap) {
+    if (!e || ctx < 0 || ctx > 2) return HM_EINVAL;
+    hm_batch* b = legacy(e);
+    if (!b->ran) return fail(e, HM_ESTATE, "hm_site_logits: hm_run first");
+    int rc = hm_sync(e);
+    if (rc < 0) return rc;
+    const int64_t n = b->totals[ctx];
+    if (n > cap) return fail(e, HM_EINVAL, "hm_site_logits: output capacity too small");
+    if (n == 0) return 0;
+    if (!logits) return HM_EINVAL;
+    try {
+        // every tail kernel writes logits[2 * uidx]: gather them in the order of the context's list
+        std::vector<Site> s((size_t)n);
+        std::vector<float> lg((size_t)b->totals[3] * 2);
+        HIP_TRY(hipMemcpy(s.data(), b->d_csites.as<Site>() + b->totals[4 + ctx], (size_t)n * sizeof(Site), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(lg.data(), b->d_logits.p, lg.size() * sizeof(float), hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < n; ++i) {
+            const size_t u = (size_t)s[(size_t)i].uidx;
+            if (u >= (size_t)b->totals[3]) return fail(e, HM_EDEVICE, "hm_site_logits: site index out of range");
+            logits[2 * i] = lg[2 * u];
+            logits[2 * i + 1] = lg[2 * u + 1];
         }
         return n;
     } catch (const HipErr& h) {

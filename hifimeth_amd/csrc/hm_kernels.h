@@ -112,7 +112,7 @@ size_t trunk3_dump_bytes(int grid);
 void launch_trunk3(hipStream_t st, int k1, const TrunkTile* tiles, int n_tiles, int n_views, int ctx, const RInfo* rinfo,
                    const uint8_t* bases, const uint32_t* kin, const uint8_t* sctx, int64_t n_bases, const CtxWeights& w, const TrunkMaps& maps,
                    uint16_t* dump, int32_t* list_steps, const int32_t* tcost, int grid, bool w3_single = false);   // n_bases: bytes of sctx
-// (w3_single: conv3 with plain fp16 weights -- its w_lo x_hi product dropped -- engine option precision = 2)
+// (w3_single: conv3 with plain fp16 weights -- its w_lo x_hi product dropped -- engine option conv3_w16 = 1)
 // the same path in strict fp32 (precision 0; hm_trunk_f32.hip): fp32 maps and edge rows, v_mfma_f32_16x16x4_f32
 void launch_trunk_f32(hipStream_t st, int k1, const TrunkTile* tiles, int n_tiles, int n_views, int ctx, const RInfo* rinfo,
                       const uint8_t* bases, const uint32_t* kin, const uint8_t* sctx, const CtxWeights& w,

@@ -284,7 +284,7 @@ __global__ __launch_bounds__(64) void rowlist3_kernel(const TrunkTile* __restric
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
-// W3LO = false (engine option precision = 2, BASELINE.json configs[4]'s best variant that holds its bar): conv3 runs with plain fp16 WEIGHTS --
+// W3LO = false (engine option conv3_w16 = 1, with trunk_impl 3; precision = 2 drops w_lo in conv8 + fc1 instead): conv3 runs with plain fp16 WEIGHTS --
 // its w_lo x_hi product is dropped, 12 of a tile's 53 MFMAs per position; activations stay hi + lo everywhere
 template <int K1, bool W3LO = true>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))

@@ -176,6 +176,9 @@ int hm_batch_release(hm_batch_t* b); /* the slot may be handed out again */
 /* ---- seams used by the parity tests and the feature-extraction roofline ------------------- */
 /* extract_*_samples: site list of one context after hm_run, in (read, qoff) order */
 int64_t hm_scan_sites(hm_engine_t* e, int ctx, int32_t* read_id, int32_t* qoff, uint8_t* strand, int64_t cap);
+/* logits [n][2] (l0, l1) the CNN computed for the sites of one context after hm_run, in hm_scan_sites order, whichever kernels
+ * ran (per site, dense trunk, any tail); returns n, HM_EINVAL when n > cap */
+int64_t hm_site_logits(hm_engine_t* e, int ctx, float* logits, int64_t cap);
 /* get_next_sample_features: raw 401x8 fp32 windows of sites [first, first+n) of context ctx;
  * out_host may be NULL (device-only run for timing) */
 int hm_windows(hm_engine_t* e, int ctx, int64_t first, int64_t n, float* out_host);

@@ -52,6 +52,39 @@ def _mixed_reads():
     return reads
 
 
+def _extreme_reads():
+    """Saturated (255), zero and alternating kinetics codes and u16 frame arrays at and above the 952 cap, on poly-C,
+    CG repeats, random sequence and CCA repeats, stored forward and reversed."""
+    rng = np.random.default_rng(5)
+    L = 1400
+    seqs = [b"C" * L, b"CG" * (L // 2), bytes(rng.choice(np.frombuffer(b"ACGT", np.uint8), L).tobytes()),
+            b"CCA" * (L // 3) + b"CC"]
+    reads = []
+    for i, sq in enumerate(seqs):
+        for j, fill in enumerate((255, 0, None)):
+            if fill is None:
+                k = [np.where(np.arange(len(sq)) % 2 == 0, 255, 0).astype(np.uint8) for _ in range(4)]
+            else:
+                k = [np.full(len(sq), fill, np.uint8) for _ in range(4)]
+            reads.append(read_from_ascii(sq, *k, flag=4 if (i + j) % 2 else 20, name=f"x{i}_{j}"))
+        wide = [np.full(len(sq), v, np.uint16) for v in (952, 2000, 65535, 447)]
+        reads.append(read_from_ascii(sq, *wide, flag=4, name=f"w{i}"))
+    return reads
+
+
+def _run(m, reads):
+    """m.call(reads), also returning the staged batch's logits of every context (hm_site_logits) as bytes: two kernels whose
+    calls agree can still differ in logits where p saturates."""
+    m.clear()
+    m.submit_all(reads)
+    m.upload()
+    m.run()
+    calls = m.fetch().copy()
+    logits = b"".join(m.site_logits(c).tobytes() for c in range(3))
+    m.clear()
+    return calls, logits
+
+
 def test_scan_sites_match_oracle(mc, oracle):
     reads = _mixed_reads()
     mc.clear()
@@ -288,13 +321,14 @@ def test_fp16_weight_mode_holds_its_bar_and_the_literal_config_stays_closed(orac
         with MethylationCaller(device=0, timing=True) as m:
             m.set_option("trunk", 1)
             m.set_option("precision", 2)
-            got = m.call(reads).copy()
+            got, got_lg = _run(m, reads)
             assert m.timing()["tail_strip_passes"] > 0, "CHH runs on the strip tail in this mode too (w16: a run-time parameter of the kernel)"
         with MethylationCaller(device=0) as m:   # the same mode on tail_kernel_r<true> for every context: the same bytes
             m.set_option("trunk", 1)
             m.set_option("precision", 2)
             m.set_option("tail_impl", 1)
-            assert m.call(reads).tobytes() == got.tobytes()
+            calls, logits = _run(m, reads)
+            assert calls.tobytes() == got.tobytes() and logits == got_lg
         assert len(got) == len(ref) > 5000
         for f in ("read_id", "qoff", "strand", "ctx"):
             assert np.array_equal(got[f], ref[f])
@@ -310,6 +344,32 @@ def test_fp16_weight_mode_holds_its_bar_and_the_literal_config_stays_closed(orac
             worst = max(worst, float(np.abs(g["p"] - want["p"][order]).max()))
             assert int(np.abs(g["scaled_prob"].astype(int) - want["ml"][order].astype(int)).max()) <= 1
         assert worst <= 1e-3, worst   # the tolerance BASELINE.json configs[4] states
+
+
+@pytest.mark.parametrize("tail_impl", [0, 2])
+def test_precision_2_is_refused_with_a_tail_that_has_no_fp16_weights(tail_impl):
+    """tail_impl 0 and 2 have no plain-fp16-weight variant: with them the engine would run precision 1's arithmetic.  Either
+    order of setting the two options is refused, and the options in force stay as they were."""
+    from hifimeth_amd import HifimethError, MethylationCaller
+    reads = _mixed_reads()[:3]
+    with MethylationCaller(device=0) as m:
+        m.set_option("trunk", 1)
+        m.set_option("tail_impl", tail_impl)
+        with pytest.raises(HifimethError):
+            m.set_option("precision", 2)
+        ref, ref_lg = _run(m, reads)         # precision 1 with this tail
+    with MethylationCaller(device=0) as m:
+        m.set_option("trunk", 1)
+        m.set_option("tail_impl", 1)
+        m.set_option("precision", 2)
+        with pytest.raises(HifimethError):
+            m.set_option("tail_impl", tail_impl)
+        got, got_lg = _run(m, reads)         # still precision 2 on tail_impl 1
+        m.set_option("precision", 1)
+        m.set_option("tail_impl", tail_impl)  # accepted once precision 2 is off
+        again, again_lg = _run(m, reads)
+    assert len(ref) > 100 and again.tobytes() == ref.tobytes() and again_lg == ref_lg
+    assert got_lg != ref_lg
 
 
 def test_group_size_option_is_bounded():
@@ -442,21 +502,7 @@ def test_extreme_kinetics_and_homopolymers(mc, oracle, oracle_models):
     """saturated (255 = 952 frames), zero and alternating kinetics codes, u16 frame arrays at and above the 952 cap,
     on poly-C / CG-repeat / random sequence: the largest activations the network can see must stay finite in the
     split-half planes and within tolerance of the fp32 oracle."""
-    from hifimeth_amd.synth import read_from_ascii
-    rng = np.random.default_rng(5)
-    L = 1400
-    seqs = [b"C" * L, b"CG" * (L // 2), bytes(rng.choice(np.frombuffer(b"ACGT", np.uint8), L).tobytes()),
-            b"CCA" * (L // 3) + b"CC"]
-    reads = []
-    for i, sq in enumerate(seqs):
-        for j, fill in enumerate((255, 0, None)):
-            if fill is None:
-                k = [np.where(np.arange(len(sq)) % 2 == 0, 255, 0).astype(np.uint8) for _ in range(4)]
-            else:
-                k = [np.full(len(sq), fill, np.uint8) for _ in range(4)]
-            reads.append(read_from_ascii(sq, *k, flag=4 if (i + j) % 2 else 20, name=f"x{i}_{j}"))
-        wide = [np.full(len(sq), v, np.uint16) for v in (952, 2000, 65535, 447)]
-        reads.append(read_from_ascii(sq, *wide, flag=4, name=f"w{i}"))
+    reads = _extreme_reads()
     calls = mc.call(reads)
     assert np.isfinite(calls["p"]).all()
     n, nml, worst = _check_calls(calls, reads, oracle, oracle_models, 7)
@@ -600,14 +646,17 @@ def test_streaming_trunk_is_byte_identical_to_the_8_wave_form():
     wide kinetics."""
     from hifimeth_amd import MethylationCaller
     reads = _mixed_reads() + synth_reads(6, seed=77, median_len=5000, sigma=0.5, frac_wide=0.3)
-    out = []
+    out, lg = [], []
     for impl in (0, 1, 2, 3):  # 8-wave ConvH form, streaming on 4 waves, streaming on 8 waves, sliding window (default)
         with MethylationCaller(device=0) as m:
             m.set_option("trunk", 1)
             m.set_option("trunk_impl", impl)
-            out.append(m.call(reads).copy())
+            calls, logits = _run(m, reads)
+            out.append(calls)
+            lg.append(logits)
     assert len(out[0]) == len(out[1]) == len(out[2]) == len(out[3]) > 1000
     assert out[0].tobytes() == out[1].tobytes() == out[2].tobytes() == out[3].tobytes()
+    assert len(lg[0]) == 8 * len(out[0]) and lg[0] == lg[1] == lg[2] == lg[3]
 
 
 @pytest.mark.gpu
@@ -622,7 +671,7 @@ def test_sliding_window_trunk_is_byte_identical_whatever_the_runs_of_tiles():
     with MethylationCaller(device=0) as m:
         m.set_option("trunk", 1)
         m.set_option("trunk_impl", 1)
-        ref = m.call(reads).copy()
+        ref, ref_lg = _run(m, reads)
     assert len(ref) > 1000
     for num_cu, group_bases in ((1, 0), (3, 0), (7, 32768), (256, 0), (1024, 4096)):
         with MethylationCaller(device=0) as m:
@@ -631,10 +680,11 @@ def test_sliding_window_trunk_is_byte_identical_whatever_the_runs_of_tiles():
             m.set_option("num_cu", num_cu)
             if group_bases:
                 m.set_option("group_bases", group_bases)
-            a = m.call(reads).copy()
+            a, a_lg = _run(m, reads)
             b = m.call(reads[::-1]).copy()     # other reads first: stale kept rows / maps of the previous batch must not leak
-            c = m.call(reads).copy()
+            c, c_lg = _run(m, reads)
         assert a.tobytes() == ref.tobytes() == c.tobytes(), (num_cu, group_bases)
+        assert a_lg == ref_lg == c_lg, (num_cu, group_bases)
         assert len(b) == len(ref)
 
 
@@ -651,7 +701,7 @@ def test_constant_steps_store_what_a_computed_step_would():
     with MethylationCaller(device=0) as m:
         m.set_option("trunk", 1)
         m.set_option("trunk_impl", 1)
-        ref = m.call(reads).copy()
+        ref, ref_lg = _run(m, reads)
     want = 0
     for rd in reads:
         L = rd.l_qseq
@@ -662,9 +712,9 @@ def test_constant_steps_store_what_a_computed_step_would():
             m.set_option("trunk", 1)
             m.set_option("trunk_impl", 3)
             m.set_option("num_cu", num_cu)
-            got = m.call(reads).copy()
+            got, got_lg = _run(m, reads)
             tm = m.timing()
-        assert got.tobytes() == ref.tobytes(), num_cu
+        assert got.tobytes() == ref.tobytes() and got_lg == ref_lg, num_cu
         assert list(tm["trunk_const_steps"]) == [want, want, 2 * want], (num_cu, tm["trunk_const_steps"], want)
         tiles = [p // 112 for p in tm["trunk_positions"]]
         assert all(0 < c < t // 4 for c, t in zip(tm["trunk_const_steps"], tiles))
@@ -680,17 +730,20 @@ def test_edge2_is_byte_identical_to_the_staging_edge_kernel():
     reads = _mixed_reads() + synth_reads(8, seed=79, median_len=6000, sigma=0.5, frac_wide=0.3)
     cases = [("cpg,chg,chh", reads, None), ("cpg,chg,chh", reads[:1], None), ("cpg", reads[:3], None), ("chg", reads, None), ("chh", reads, 32768)]
     for spec, rs, group_bases in cases:
-        out = []
+        out, lg = [], []
         for impl in (0, 1):
             with MethylationCaller(contexts=spec, device=0, timing=True) as m:
                 m.set_option("trunk", 1)
                 m.set_option("edge_impl", impl)
                 if group_bases:
                     m.set_option("group_bases", group_bases)
-                out.append(m.call(rs).copy())
-                out.append(m.call(rs).copy())      # a second batch through the same engine (buffers reused)
+                for _ in range(2):                 # a second batch through the same engine (buffers reused)
+                    calls, logits = _run(m, rs)
+                    out.append(calls)
+                    lg.append(logits)
         assert len(out[0]) == len(out[2]) > 50, (spec, len(out[0]))
         assert out[0].tobytes() == out[1].tobytes() == out[2].tobytes() == out[3].tobytes(), spec
+        assert lg[0] == lg[1] == lg[2] == lg[3], spec
 
 
 def test_resident_tail_is_byte_identical_to_the_streaming_tail():
@@ -703,28 +756,31 @@ def test_resident_tail_is_byte_identical_to_the_streaming_tail():
     reads = _mixed_reads() + synth_reads(8, seed=78, median_len=6000, sigma=0.5, frac_wide=0.3)
     cases = [("cpg,chg,chh", reads, None), ("cpg,chg,chh", reads[:1], None), ("cpg", reads[:3], None), ("chh", reads, 32768)]
     for spec, rs, group_bases in cases:
-        out = []
+        out, lg = [], []
         for impl in (0, 1, 2):   # 2 = the split tail (hm_tail_s.hip: conv5 + conv6 | conv7 .. softmax over 16 sites per pass)
             with MethylationCaller(contexts=spec, device=0, timing=True) as m:
                 m.set_option("trunk", 1)
                 m.set_option("tail_impl", impl)
                 if group_bases:
                     m.set_option("group_bases", group_bases)
-                out.append(m.call(rs).copy())
-                out.append(m.call(rs).copy())      # a second batch through the same engine (buffers reused)
+                for _ in range(2):                 # a second batch through the same engine (buffers reused)
+                    calls, logits = _run(m, rs)
+                    out.append(calls)
+                    lg.append(logits)
         assert len(out[0]) == len(out[2]) == len(out[4]) > 50, (spec, len(out[0]))
         assert out[0].tobytes() == out[1].tobytes() == out[2].tobytes() == out[3].tobytes() == out[4].tobytes() == out[5].tobytes(), spec
+        assert lg[0] == lg[1] == lg[2] == lg[3] == lg[4] == lg[5], spec
     # the split tail in launches of 64 sites (engine option tail_slice): many launch pairs per context, the hand-off buffer reused
     with MethylationCaller(device=0) as m:
         m.set_option("trunk", 1)
         m.set_option("tail_impl", 0)
-        ref = m.call(reads).copy()
+        ref, ref_lg = _run(m, reads)
     with MethylationCaller(device=0) as m:
         m.set_option("trunk", 1)
         m.set_option("tail_impl", 2)
         m.set_option("tail_slice", 64)
-        got = m.call(reads).copy()
-    assert got.tobytes() == ref.tobytes()
+        got, got_lg = _run(m, reads)
+    assert got.tobytes() == ref.tobytes() and got_lg == ref_lg
 
 
 @pytest.mark.gpu
@@ -740,7 +796,7 @@ def test_strip_tail_is_byte_identical_to_the_resident_tail():
     cases = [("cpg,chg,chh", reads, None, None), ("chh", reads[:1], None, None), ("chh", reads, 32768, None), ("chh", reads, None, 1),
              ("chh", reads, 65536, 7)]
     for spec, rs, group_bases, ncu in cases:
-        out = []
+        out, lg = [], []
         for impl in (1, 3):
             with MethylationCaller(contexts=spec, device=0, timing=True) as m:
                 m.set_option("trunk", 1)
@@ -749,22 +805,27 @@ def test_strip_tail_is_byte_identical_to_the_resident_tail():
                     m.set_option("group_bases", group_bases)
                 if ncu:
                     m.set_option("num_cu", ncu)
-                out.append(m.call(rs).copy())
-                out.append(m.call(rs[::-1]).copy())      # a second, different batch through the same engine (buffers reused)
+                for batch in (rs, rs[::-1]):       # a second, different batch through the same engine (buffers reused)
+                    calls, logits = _run(m, batch)
+                    out.append(calls)
+                    lg.append(logits)
         assert len(out[0]) == len(out[2]) > 50, (spec, len(out[0]))
         assert out[0].tobytes() == out[2].tobytes() and out[1].tobytes() == out[3].tobytes(), (spec, group_bases, ncu)
+        assert lg[0] == lg[2] and lg[1] == lg[3], (spec, group_bases, ncu)
     # site densities from sparse to dense (GC 0.2 ... 0.7: CHH 0.16 ... 0.27 sites per base; the strip holds 11 ... 16 sites per pass) and
     # CpG-depleted, human-like reads: passes of every fill, classes that run dry inside a strip
     from hifimeth_amd.synth import synth_slab
     for gc, oe in ((0.2, 1.0), (0.5, 1.0), (0.7, 1.0), (0.41, 0.24)):
         rs = synth_slab(6, seed=int(1000 * gc), gc=gc, cpg_oe=oe, median_len=9000, sigma=0.5, frac_wide=0.2)
-        out = []
+        out, lg = [], []
         for impl in (1, 3):
             with MethylationCaller(contexts="chh", device=0) as m:
                 m.set_option("trunk", 1)
                 m.set_option("tail_impl", impl)
-                out.append(m.call(rs).copy())
-        assert len(out[0]) > 5000 and out[0].tobytes() == out[1].tobytes(), (gc, oe)
+                calls, logits = _run(m, rs)
+                out.append(calls)
+                lg.append(logits)
+        assert len(out[0]) > 5000 and out[0].tobytes() == out[1].tobytes() and lg[0] == lg[1], (gc, oe)
 
 
 @pytest.mark.gpu
@@ -787,14 +848,16 @@ def test_fc_kernel_tiles_of_16_with_ragged_ends():
     ks = [1, 15, 16, 17, 33]
     reads = [read_with(k) for k in ks]
     for rs, want in [([r], k) for r, k in zip(reads, ks)] + [(reads, sum(ks))]:
-        out = []
+        out, lg = [], []
         for impl in (1, 3):
             with MethylationCaller(contexts="chh", device=0) as m:
                 m.set_option("trunk", 1)
                 m.set_option("tail_impl", impl)
-                out.append(m.call(rs).copy())
+                calls, logits = _run(m, rs)
+                out.append(calls)
+                lg.append(logits)
         assert len(out[0]) == len(out[1]) == want, (want, len(out[0]), len(out[1]))
-        assert out[0].tobytes() == out[1].tobytes(), want
+        assert out[0].tobytes() == out[1].tobytes() and lg[0] == lg[1], want
 
 
 @pytest.mark.gpu
