@@ -15,6 +15,9 @@ GPU box never needs the reference.  Three sources, each the reference's own code
 
   align.json     alignment columns, identity and mapped CpG/CHG/CHH samples from the reference's BamMapInfo and
                  5mc_motif_finder.cpp (oracle/_ref/ref_align) -- pins the pileup oracle's projection
+  align_edges.json, modparse_edges.json
+                 the same reference code (ref_align, ref_modparse) on the edge alignments and MM/ML dialects of
+                 tests/pileup_cases.py; `python tools/make_golden.py <reference> edges` makes only these two
 
 usage: python tools/make_golden.py [/root/reference [align]]
 """
@@ -405,6 +408,71 @@ def make_align():
           f"{sum(len(d['chh']) for d in out if d)} CHH samples")
 
 
+def _edge_cases():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import pileup_cases
+    return pileup_cases
+
+
+def _dump_rows(path, head, key, rows):
+    """compact JSON with one row of `key` per line, so that a change of one record is one line of a diff"""
+    c = dict(separators=(",", ":"))
+    with open(path, "w") as f:
+        f.write("{" + "".join(json.dumps(k) + ":" + json.dumps(v, **c) + ",\n" for k, v in head.items()) + json.dumps(key) + ":[\n")
+        f.write(",\n".join(json.dumps(r, **c) for r in rows) + "\n]}\n")
+
+
+def make_align_edges():
+    """align_edges.json: the same reference code as align.json (oracle/_ref/ref_align) on the hand-built edge alignments of
+    tests/pileup_cases.py (pileup_cases.fixture_reads(): cigar_zoo, a sample of boundaries and of tiny_crowd; the empty-CIGAR
+    records of REF_UNDEFINED are left out)."""
+    from oracle import pileup_oracle as P
+    C = _edge_cases()
+    genome = C.genome()
+    reads = C.fixture_reads()
+    fa = os.path.join(GOLD, "_align_edges.fa")
+    with open(fa, "w") as f:
+        for n, sq in genome:
+            f.write(f">{n}\n")
+            for i in range(0, len(sq), 70):
+                f.write(sq[i:i + 70] + "\n")
+    try:
+        assert P.load_fasta(fa) == genome
+        out = P.ref_align(fa, [(r.flag, r.tid, r.pos, r.cigar_string(), r.seq) for r in reads])
+    finally:
+        os.remove(fa)
+    assert len(out) == len(reads) and all(d is not None for d in out)
+    recs = [dict(name=r.name, flag=r.flag, tid=r.tid, pos=r.pos, cigar=r.cigar_string(), seq=r.seq, ref=d) for r, d in zip(reads, out)]
+    _dump_rows(os.path.join(GOLD, "align_edges.json"), dict(genome=genome), "reads", recs)
+    print(f"align_edges.json: {len(recs)} records, {sum(d['as_size'] for d in out)} columns, "
+          f"{sum(len(d['cpg']) + len(d['chg']) + len(d['chh']) for d in out)} samples")
+
+
+def make_modparse_edges():
+    """modparse_edges.json: the reference's own parser core (oracle/_ref/ref_modparse, as for modparse.json) on the MM/ML
+    dialects of pileup_cases.fixture_tag_reads(), one process per record: where the reference refuses a list (it aborts on every
+    ChEBI code, see make_modparse, and on base / code pairs outside its table) the record holds "mods": null, and only the
+    oracle, the host mirror and the CLI are compared on it."""
+    import subprocess
+    C = _edge_cases()
+    recs = []
+    for r in C.fixture_tag_reads():
+        ml = [int(v) for v in r.ml]
+        txt = f"1\n{r.flag} {r.seq} {r.mm} {len(ml)} " + " ".join(str(v) for v in ml) + "\n"
+        p = subprocess.run([os.path.join(ROOT, "oracle", "_ref", "ref_modparse")], input=txt, capture_output=True, text=True)
+        mods = None
+        if p.returncode == 0:
+            lines = p.stdout.split("\n")
+            mods = []
+            for k in range(int(lines[0])):
+                q, st, ub, code, pr = lines[1 + k].split()
+                mods.append([int(q), int(st), ub, code, int(pr)])
+        recs.append(dict(name=r.name, flag=r.flag, seq=r.seq, mm=r.mm, ml=ml, mods=mods))
+    _dump_rows(os.path.join(GOLD, "modparse_edges.json"), {}, "records", recs)
+    print(f"modparse_edges.json: {len(recs)} records, {sum(r['mods'] is not None for r in recs)} parsed by the reference, refused: "
+          + ", ".join(r["name"] for r in recs if r["mods"] is None))
+
+
 def make_helpers():
     """helpers.json: the reference's own `cov2bed` and `corr` subcommands (src/app/hifimeth/cov_to_bed.cpp,
     pileup_correlation.cpp), built by oracle/ref_build into oracle/_ref/ref_tools, run on a synthetic genome with
@@ -610,7 +678,11 @@ if __name__ == "__main__":
     if len(sys.argv) > 2 and sys.argv[2] == "align":      # only the pileup fixtures
         make_align()
         raise SystemExit(0)
-    if len(sys.argv) > 2 and sys.argv[2] == "helpers":    # only the cov2bed / corr fixtures
+    if len(sys.argv) > 2 and sys.argv[2] == "edges":      # only the edge-alignment and MM-dialect fixtures (tests/pileup_cases.py)
+        make_align_edges()
+        make_modparse_edges()
+        raise SystemExit(0)
+    if len(sys.argv) > 2 and sys.argv[2] == "helpers":   # only the cov2bed / corr fixtures
         make_helpers()
         raise SystemExit(0)
     if len(sys.argv) > 2 and sys.argv[2] == "modparse":    # only the MM/ML parser fixture
@@ -637,6 +709,8 @@ if __name__ == "__main__":
     make_cnn_chg(w)
     make_config_goldens()
     make_align()
+    make_align_edges()
+    make_modparse_edges()
     make_helpers()
     make_pileup_thresholds()
     make_softmax()
