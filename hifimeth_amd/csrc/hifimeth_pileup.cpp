@@ -7,6 +7,9 @@
 // the projected calls stay in HBM until the thresholds are known.
 // -H (ours): also <prefix>.hap1.<ctx>.cov.bed / <prefix>.hap2.<ctx>.cov.bed from the records' integer HP tag, counted with
 // the combined thresholds, each locus in its combined context.
+// -A (ours, with -H): also <prefix>.asm.<ctx>.bed, one row per locus where each haplotype has at least -a (default 5) counted
+// calls:  chrom <tab> soff <tab> soff+1 <tab> diff <tab> pvalue <tab> pcov1 <tab> ncov1 <tab> pcov2 <tab> ncov2
+// (difference of the two methylation percentages, two-sided Fisher exact test; both computed on the GPU).
 #include <strings.h>
 #include <zlib.h>
 
@@ -60,6 +63,9 @@ struct PileupOptions {
     int device = 0;
     int read_batch = 512;
     bool haplotypes = false;  // -H: also <prefix>.hap1.* / <prefix>.hap2.* from the HP tag
+    bool asm_test = false;    // -A: per-locus haplotype difference + Fisher exact test -> <prefix>.asm.*
+    int asm_min_cov = 5;      // -a: minimum pcov + ncov of each haplotype for a locus to be tested
+    bool asm_min_cov_given = false;
     std::string ref, bam, prefix;
 };
 
@@ -74,7 +80,10 @@ void pileup_usage(const char* exe) {
             "  -d <int>\n    GPU ordinal\n    Default: 0\n"
             "  -b <int>\n    BAM records per GPU batch\n    Default: 512\n"
             "  -H\n    Haplotype-resolved output: records tagged HP:i:1 / HP:i:2 are also counted into\n"
-            "    <prefix>.hap1.<ctx>.cov.bed / <prefix>.hap2.<ctx>.cov.bed (same thresholds as the combined files)\n",
+            "    <prefix>.hap1.<ctx>.cov.bed / <prefix>.hap2.<ctx>.cov.bed (same thresholds as the combined files)\n"
+            "  -A\n    With -H: test every locus where both haplotypes are covered for a difference between them and write\n"
+            "    <prefix>.asm.<ctx>.bed: chrom, start, end, hap1 %% - hap2 %%, two-sided Fisher exact p-value, pcov1, ncov1, pcov2, ncov2\n"
+            "  -a <int>\n    With -A: minimum coverage (pcov + ncov) of each haplotype at a tested locus\n    Default: 5\n",
             exe);
 }
 
@@ -719,6 +728,38 @@ bool write_bed(hm_pileup_t* pe, const Fasta& fa, const void* pcov, const void* n
     }
     return true;
 }
+
+// rows of the three <prefix>.asm.<ctx>.bed files from the engine's own partition and key planes, fetched per sequence like the
+// rows above (48 B per tested row on the device and here).  false on an engine error.
+bool write_asm(hm_pileup_t* pe, const Fasta& fa, int min_cov, FILE* out[3]) {
+    std::vector<hm_asm_t> rows;
+    std::string text[3];
+    int64_t off = 0;
+    for (size_t s = 0; s < fa.names.size(); ++s) {
+        const int64_t lo = off, hi = off + fa.length[s];
+        off = hi;
+        int64_t n = hm_pileup_fetch_asm(pe, nullptr, nullptr, nullptr, nullptr, nullptr, 0, lo, hi, min_cov, nullptr, 0);
+        if (n < 0) return false;
+        if (n == 0) continue;
+        rows.resize((size_t)n);
+        n = hm_pileup_fetch_asm(pe, nullptr, nullptr, nullptr, nullptr, nullptr, 0, lo, hi, min_cov, rows.data(), n);
+        if (n < 0) return false;
+        for (std::string& t : text) t.clear();
+        char row[256];
+        for (int64_t i = 0; i < n; ++i) {
+            const hm_asm_t& r = rows[(size_t)i];
+            const int64_t k = r.gpos - lo;
+            const int len = snprintf(row, sizeof row, "\t%lld\t%lld\t%g\t%.6g\t%d\t%d\t%d\t%d\n", (long long)k, (long long)k + 1, r.diff,
+                                     r.pvalue, r.pcov1, r.ncov1, r.pcov2, r.ncov2);
+            std::string& t = text[r.motif < 3 ? r.motif : 2];
+            t += fa.names[s];
+            t.append(row, (size_t)len);
+        }
+        for (int c = 0; c < 3; ++c)
+            if (!text[c].empty()) fwrite(text[c].data(), 1, text[c].size(), out[c]);
+    }
+    return true;
+}
 }  // namespace
 
 int cmd_pileup(int argc, char** argv) {
@@ -729,15 +770,21 @@ int cmd_pileup(int argc, char** argv) {
         if (a == "-h") { pileup_usage(argv[0]); return 0; }
         if (a.size() < 2 || a[0] != '-') break;
         if (a == "-H") { o.haplotypes = true; continue; }  // a flag: takes no value
+        if (a == "-A") { o.asm_test = true; continue; }
         if (i + 1 >= argc) { pileup_usage(argv[0]); return EXIT_FAILURE; }
         if (a == "-q") o.min_mapq = atoi(argv[++i]);
         else if (a == "-f") o.min_pi = atof(argv[++i]);
         else if (a == "-t") o.threads = std::max(1, atoi(argv[++i]));
         else if (a == "-d") o.device = atoi(argv[++i]);
         else if (a == "-b") o.read_batch = std::max(1, atoi(argv[++i]));
+        else if (a == "-a") { o.asm_min_cov = atoi(argv[++i]); o.asm_min_cov_given = true; }
         else { fprintf(stderr, "ERROR: unrecognised option %s", a.c_str()); pileup_usage(argv[0]); return EXIT_FAILURE; }
     }
     if (argc - i != 3) { pileup_usage(argv[0]); return EXIT_FAILURE; }
+    const char* bad_asm = o.asm_test && !o.haplotypes ? "-A needs -H (the test compares the two haplotypes)"
+                          : o.asm_min_cov_given && !o.asm_test ? "-a needs -A"
+                          : o.asm_min_cov < 1 ? "-a must be >= 1" : nullptr;
+    if (bad_asm) { fprintf(stderr, "ERROR: %s\n", bad_asm); pileup_usage(argv[0]); return EXIT_FAILURE; }
     o.ref = argv[i];
     o.bam = argv[i + 1];
     o.prefix = argv[i + 2];
@@ -745,6 +792,7 @@ int cmd_pileup(int argc, char** argv) {
                     "Genomic reference: %s\nmod-bam: %s\noutput prefix: %s\n",
             o.min_mapq, o.min_pi, o.threads, o.ref.c_str(), o.bam.c_str(), o.prefix.c_str());
     if (o.haplotypes) fprintf(stderr, "haplotypes: HP 1 / 2 -> %s.hap1.* / %s.hap2.*\n", o.prefix.c_str(), o.prefix.c_str());
+    if (o.asm_test) fprintf(stderr, "asm: min haplotype coverage %d -> %s.asm.*\n", o.asm_min_cov, o.prefix.c_str());
     fprintf(stderr, "\n\n");
 
     using clk = std::chrono::steady_clock;
@@ -889,6 +937,22 @@ int cmd_pileup(int argc, char** argv) {
         const bool ok = write_bed(pe, fa, planes[3 * t], planes[3 * t + 1], planes[3 * t + 2], out, o.threads);
         for (FILE* f : out) fclose(f);
         if (!ok) return die("loci");
+    }
+    if (o.asm_test) {
+        FILE* out[3];
+        for (int c = 0; c < 3; ++c) {
+            const std::string path = o.prefix + ".asm." + cn[c] + ".bed";
+            out[c] = fopen(path.c_str(), "w");
+            if (!out[c]) {
+                fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str());
+                for (int d = 0; d < c; ++d) fclose(out[d]);
+                hm_pileup_destroy(pe);
+                return EXIT_FAILURE;
+            }
+        }
+        const bool ok = write_asm(pe, fa, o.asm_min_cov, out);
+        for (FILE* f : out) fclose(f);
+        if (!ok) return die("asm");
     }
     hm_pileup_destroy(pe);
     fprintf(stderr, "## %llu records in %.2f s: [producer thread: BAM read %.2f s, MM/ML parse %.2f s] overlapped with "

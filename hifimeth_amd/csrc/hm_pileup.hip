@@ -18,10 +18,14 @@
 //   count_kernel    thread per record      : atomic add into pcov / ncov, atomic max into the motif key
 //   count_hp_kernel the same + one more atomic add into the record's haplotype planes (partitions = 2 only)
 //   loci_*          covered loci of a range in ascending order (count per block, scan, write)
+//   asm_*           loci where both haplotypes reach a minimum coverage, compacted the same way (count, loci_scan, write),
+//                   then one thread per compact row: methylation difference + two-sided Fisher exact test
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <array>
+#include <cfloat>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -405,6 +409,115 @@ __global__ __launch_bounds__(TPB) void loci_write_kernel(const int32_t* __restri
     }
 }
 
+// ---- allele-specific methylation: loci tested between the two haplotype partitions -----------------
+// A locus is tested when each haplotype has pcov + ncov >= min_cov.  The planes may be the caller's: counters that are not
+// plain counts (negative) never pass, so the table lookups below stay inside [0, total].
+constexpr int LFACT_N = 65536;  // log n! for n < LFACT_N from the uploaded table, beyond it from lgamma in the kernel
+
+__device__ __forceinline__ bool asm_tested(int32_t p1, int32_t n1, int32_t p2, int32_t n2, int32_t min_cov) {
+    return (p1 | n1 | p2 | n2) >= 0 && (int64_t)p1 + n1 >= min_cov && (int64_t)p2 + n2 >= min_cov;
+}
+
+__global__ __launch_bounds__(TPB) void asm_count_kernel(const int32_t* __restrict__ pcov1, const int32_t* __restrict__ ncov1,
+                                                         const int32_t* __restrict__ pcov2, const int32_t* __restrict__ ncov2,
+                                                         int64_t lo, int64_t hi, int32_t min_cov,
+                                                         int32_t* __restrict__ block_counts) {
+    __shared__ int wsum[TPB / 64];
+    const int64_t base = lo + (int64_t)blockIdx.x * LOCI_PER_BLOCK;
+    int cnt = 0;
+    for (int k = 0; k < LOCI_PER_BLOCK / TPB; ++k) {
+        const int64_t i = base + k * TPB + threadIdx.x;
+        if (i < hi && asm_tested(pcov1[i], ncov1[i], pcov2[i], ncov2[i], min_cov)) ++cnt;
+    }
+    for (int d = 32; d; d >>= 1) cnt += __shfl_down(cnt, d);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+// compact rows in ascending locus order; diff and pvalue are filled by asm_test_kernel
+__global__ __launch_bounds__(TPB) void asm_write_kernel(const int32_t* __restrict__ pcov1, const int32_t* __restrict__ ncov1,
+                                                         const int32_t* __restrict__ pcov2, const int32_t* __restrict__ ncov2,
+                                                         const uint32_t* __restrict__ key, int64_t plane_base, int64_t lo,
+                                                         int64_t hi, int32_t min_cov, const int64_t* __restrict__ offs,
+                                                         hm_asm_t* __restrict__ out) {
+    __shared__ int wsum[TPB / 64];
+    __shared__ int carry;
+    if (threadIdx.x == 0) carry = 0;
+    const int64_t base = lo + (int64_t)blockIdx.x * LOCI_PER_BLOCK;
+    const int64_t o0 = offs[blockIdx.x];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int k = 0; k < LOCI_PER_BLOCK / TPB; ++k) {
+        __syncthreads();
+        const int64_t i = base + k * TPB + threadIdx.x;
+        int32_t p1 = 0, n1 = 0, p2 = 0, n2 = 0;
+        if (i < hi) { p1 = pcov1[i]; n1 = ncov1[i]; p2 = pcov2[i]; n2 = ncov2[i]; }
+        const bool sel = i < hi && asm_tested(p1, n1, p2, n2, min_cov);
+        const unsigned long long b = __ballot(sel);
+        if (lane == 0) wsum[w] = __popcll(b);
+        __syncthreads();
+        int before = carry;
+        for (int j = 0; j < w; ++j) before += wsum[j];
+        if (sel) {
+            hm_asm_t r;
+            r.gpos = plane_base + i;
+            r.pcov1 = p1;
+            r.ncov1 = n1;
+            r.pcov2 = p2;
+            r.ncov2 = n2;
+            r.motif = key[i] & 3u;
+            r.reserved = 0;
+            r.diff = 0.0;
+            r.pvalue = 0.0;
+            out[o0 + before + __popcll(b & ((1ull << lane) - 1ull))] = r;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) carry += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    }
+}
+
+__device__ __forceinline__ double lfact(const double* __restrict__ tab, int64_t k) {
+    return k < LFACT_N ? tab[k] : lgamma((double)k + 1.0);
+}
+
+// One thread per tested row.  With the margins of [[p1, n1], [p2, n2]] fixed the first cell x runs over
+// [max(0, c1 - r2), min(r1, c1)] and P(x) is proportional to exp(l(x)), l(x) = -log(x! (r1-x)! (c1-x)! (r2-c1+x)!).
+// Two-sided p, R's fisher.test rule: the sum of P(x) over the tables with P(x) <= P(observed) * (1 + 1e-7), taken in logs as
+// l(x) - l(observed) <= log1p(1e-7): ties that differ by rounding only fall on the same side.  Numerator and denominator are
+// both summed as exp(l(x) - l(near the mode)) in ascending x, so the value is a pure function of the four counts, terms never
+// overflow, and a row where every table is included gives num == den bit for bit, i.e. exactly 1.
+__global__ __launch_bounds__(TPB) void asm_test_kernel(hm_asm_t* __restrict__ rows, int64_t n_rows, const double* __restrict__ tab) {
+    const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (i >= n_rows) return;
+    const int64_t a = rows[i].pcov1, b = rows[i].ncov1, c = rows[i].pcov2, d = rows[i].ncov2;
+    const int64_t r1 = a + b, r2 = c + d, c1 = a + c;
+    // IEEE multiply, divide, subtract, each rounded once: bit-equal to the host's 100.0 * p1 / (p1 + n1) - 100.0 * p2 / (p2 + n2)
+    rows[i].diff = __dsub_rn(__ddiv_rn(__dmul_rn(100.0, (double)a), (double)r1), __ddiv_rn(__dmul_rn(100.0, (double)c), (double)r2));
+    const int64_t xlo = c1 > r2 ? c1 - r2 : 0, xhi = r1 < c1 ? r1 : c1;
+    auto l = [&](int64_t x) { return -(((lfact(tab, x) + lfact(tab, r1 - x)) + lfact(tab, c1 - x)) + lfact(tab, r2 - c1 + x)); };
+    int64_t xm = (int64_t)(((double)c1 + 1.0) * ((double)r1 + 1.0) / ((double)(r1 + r2) + 2.0));  // the mode, give or take rounding
+    xm = xm < xlo ? xlo : xm > xhi ? xhi : xm;
+    const double lref = l(xm), lobs = l(a);
+    const double band = 9.9999995000000333e-08;  // log1p(1e-7)
+    double num = 0.0, den = 0.0;
+    for (int64_t x = xlo; x <= xhi; ++x) {
+        const double lx = l(x);
+        const double e = exp(lx - lref);
+        den += e;
+        if (lx - lobs <= band) num += e;
+    }
+    double p = num / den;
+    if (lobs - lref < -600.0) {  // exp(l(observed) - lref) nears the subnormals: sum the included tables relative to the observed one
+        double rel = 0.0;
+        for (int64_t x = xlo; x <= xhi; ++x) {
+            const double t = l(x) - lobs;
+            if (t <= band) rel += exp(t);
+        }
+        p = exp((lobs - lref) + log(rel / den));
+    }
+    rows[i].pvalue = p > 1.0 ? 1.0 : p >= DBL_MIN ? p : DBL_MIN;  // never 0: a p-value below the smallest normal double is reported as that
+}
+
 }  // namespace
 
 // ================================================ host ==========================================================
@@ -440,6 +553,7 @@ struct hm_pileup {
     // device
     DevBuf d_slab, d_reads, d_runs, d_col0, d_mods, d_plane, d_matches, d_bins, d_counter, d_recs;
     DevBuf d_blk, d_offs, d_loci, d_labels, d_lbins;
+    DevBuf d_asm, d_lfact;  // tested rows of hm_pileup_fetch_asm; log n! table, uploaded by its first call
     int64_t n_recs = 0;
     bool bins_ready = false;
 };
@@ -514,7 +628,7 @@ void hm_pileup_destroy(hm_pileup_t* p) {
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     for (DevBuf* b : {&p->d_ref, &p->d_pcov, &p->d_ncov, &p->d_key, &p->d_slab, &p->d_reads, &p->d_runs, &p->d_col0,
                       &p->d_mods, &p->d_plane, &p->d_matches, &p->d_bins, &p->d_counter, &p->d_recs, &p->d_blk,
-                      &p->d_offs, &p->d_loci, &p->d_hp_pcov[0], &p->d_hp_pcov[1], &p->d_hp_ncov[0], &p->d_hp_ncov[1]})
+                      &p->d_offs, &p->d_loci, &p->d_asm, &p->d_lfact, &p->d_hp_pcov[0], &p->d_hp_pcov[1], &p->d_hp_ncov[0], &p->d_hp_ncov[1]})
         b->release();
     if (p->stream) (void)hipStreamDestroy(p->stream);
     delete p;
@@ -900,6 +1014,59 @@ int64_t hm_pileup_fetch_loci(hm_pileup_t* p, const void* pcov, const void* ncov,
                            p->d_offs.as<int64_t>(), p->d_loci.as<hm_locus_t>());
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(out, p->d_loci.p, sizeof(hm_locus_t) * (size_t)total, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return total;
+    } catch (const HipErr& h) {
+        return pfail_hip(p, h);
+    }
+}
+
+int64_t hm_pileup_fetch_asm(hm_pileup_t* p, const void* pcov1, const void* ncov1, const void* pcov2, const void* ncov2,
+                            const void* key, int64_t plane_base, int64_t lo, int64_t hi, int32_t min_cov, hm_asm_t* out,
+                            int64_t cap) {
+    if (!p) return HM_EINVAL;
+    if (min_cov < 1) return pfail(p, HM_EINVAL, "hm_pileup_fetch_asm: min_cov must be >= 1");
+    if (lo < 0 || hi < lo) return pfail(p, HM_EINVAL, "hm_pileup_fetch_asm: bad range");
+    const int given = (pcov1 != nullptr) + (ncov1 != nullptr) + (pcov2 != nullptr) + (ncov2 != nullptr) + (key != nullptr);
+    if (given != 0 && given != 5) return pfail(p, HM_EINVAL, "hm_pileup_fetch_asm: give all five planes or none");
+    const int32_t *p1 = static_cast<const int32_t*>(pcov1), *n1 = static_cast<const int32_t*>(ncov1);
+    const int32_t *p2 = static_cast<const int32_t*>(pcov2), *n2 = static_cast<const int32_t*>(ncov2);
+    const uint32_t* ky = static_cast<const uint32_t*>(key);
+    if (!given) {
+        if (p->partitions != 2 || !p->hp_pcov[0] || !p->hp_pcov[1] || !p->key)
+            return pfail(p, HM_ESTATE, "hm_pileup_fetch_asm without partition planes (option partitions = 2, then hm_pileup_set_reference)");
+        if (!p->seq_off.empty() && hi > p->seq_off.back()) return pfail(p, HM_EINVAL, "hm_pileup_fetch_asm: range past the reference");
+        p1 = p->hp_pcov[0]; n1 = p->hp_ncov[0]; p2 = p->hp_pcov[1]; n2 = p->hp_ncov[1]; ky = p->key;
+        plane_base = 0;
+    }
+    if (hi == lo) return 0;
+    const int64_t nblk = (hi - lo + LOCI_PER_BLOCK - 1) / LOCI_PER_BLOCK;
+    if (nblk >= (int64_t(1) << 31)) return pfail(p, HM_EINVAL, "range too large: fetch per sequence");
+    try {
+        HIP_TRY(hipSetDevice(p->device));
+        hipStream_t st = p->stream;
+        p->d_blk.reserve(4 * (size_t)nblk);
+        p->d_offs.reserve(8 * ((size_t)nblk + 1));
+        hipLaunchKernelGGL(asm_count_kernel, dim3((unsigned)nblk), dim3(TPB), 0, st, p1, n1, p2, n2, lo, hi, min_cov, p->d_blk.as<int32_t>());
+        hipLaunchKernelGGL(loci_scan_kernel, dim3(1), dim3(1024), 0, st, p->d_blk.as<int32_t>(), (int)nblk, p->d_offs.as<int64_t>());
+        int64_t total = 0;
+        HIP_TRY(hipMemcpyAsync(&total, p->d_offs.as<int64_t>() + nblk, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (total > cap || !out || total == 0) return total;
+        if (!p->d_lfact.p) {  // log n!, n < LFACT_N: once per engine
+            std::vector<double> t((size_t)LFACT_N);
+            for (int k = 0; k < LFACT_N; ++k) t[(size_t)k] = std::lgamma((double)k + 1.0);
+            p->d_lfact.reserve(sizeof(double) * t.size(), 0, nullptr, true);
+            HIP_TRY(hipMemcpyAsync(p->d_lfact.p, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        p->d_asm.reserve(sizeof(hm_asm_t) * (size_t)total);
+        hipLaunchKernelGGL(asm_write_kernel, dim3((unsigned)nblk), dim3(TPB), 0, st, p1, n1, p2, n2, ky, plane_base, lo, hi, min_cov,
+                           p->d_offs.as<int64_t>(), p->d_asm.as<hm_asm_t>());
+        hipLaunchKernelGGL(asm_test_kernel, dim3((unsigned)((total + TPB - 1) / TPB)), dim3(TPB), 0, st, p->d_asm.as<hm_asm_t>(), total,
+                           p->d_lfact.as<double>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(out, p->d_asm.p, sizeof(hm_asm_t) * (size_t)total, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         return total;
     } catch (const HipErr& h) {

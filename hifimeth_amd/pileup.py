@@ -13,6 +13,10 @@ Haplotype-resolved (`partitions=True`): records whose `hp` is 1 or 2 (the BAM's 
 partition's planes with the same thresholds; `pu.loci(partition=1)` / `pu.loci(partition=2)` are the rows of
 <prefix>.hap1.* / <prefix>.hap2.*, each locus in the context of the combined output.
 
+Allele-specific methylation (`pileup -H -A`): `pu.asm(min_cov=5)` are the loci where each haplotype has at least `min_cov`
+counted calls, with the difference of the two methylation percentages and the two-sided Fisher exact p-value of
+[[pcov1, ncov1], [pcov2, ncov2]], both computed on the device; `pu.asm_bed(rows)` is the text of <prefix>.asm.<ctx>.bed.
+
 Multi-GPU (one process per GPU, records dealt to ranks in slabs): `reduce_over_ranks` sums the histograms with an
 all-reduce before the thresholds are resolved, and after counting reduce-scatters the per-locus planes (sum for
 pcov / ncov, max for the motif key) so that every rank ends up owning one contiguous range of loci.
@@ -30,6 +34,8 @@ from .caller import HifimethError
 
 MOD_DTYPE = np.dtype([("qoff", "<i4"), ("strand", "u1"), ("unmod_base", "S1"), ("code", "S1"), ("prob", "u1")])
 LOCUS_DTYPE = np.dtype([("gpos", "<i8"), ("pcov", "<i4"), ("ncov", "<i4"), ("motif", "<u4"), ("reserved", "<u4")])
+ASM_DTYPE = np.dtype([("gpos", "<i8"), ("pcov1", "<i4"), ("ncov1", "<i4"), ("pcov2", "<i4"), ("ncov2", "<i4"), ("motif", "<u4"),
+                      ("reserved", "<u4"), ("diff", "<f8"), ("pvalue", "<f8")])     # hm_asm_t, 48 bytes
 CTX_NAMES = ("CpG", "CHG", "CHH")
 _CHEBI = {27551: "m", 76792: "h", 76794: "f", 76793: "c", 16964: "g", 80961: "e", 17477: "b", 28871: "a",
           44605: "o", 18107: "n"}
@@ -218,6 +224,28 @@ class MethylationPileup:
         for s, k, p, n, m in zip(sid, soff, loci["pcov"], loci["ncov"], loci["motif"]):
             rows[CTX_NAMES[int(m)]].append("%s\t%d\t%d\t%g\t%d\t%d\n" % (self.names[s], k, k + 1, 100.0 * p / (p + n), p, n))
         return {k: "".join(v) for k, v in rows.items()}
+
+    def asm(self, lo: int = 0, hi: Optional[int] = None, min_cov: int = 5, planes=None, plane_base: int = 0) -> np.ndarray:
+        """tested loci of [lo, hi) (plane coordinates) in ascending order: each haplotype with pcov + ncov >= min_cov.
+        planes = (pcov1, ncov1, pcov2, ncov2, key) torch tensors whose element 0 is locus plane_base, or None (own; needs
+        partitions=True).  diff = 100 p1 / (p1 + n1) - 100 p2 / (p2 + n2), pvalue = two-sided Fisher exact test (R's rule)."""
+        hi = self.n_loci if hi is None else hi
+        ptrs = [None] * 5 if planes is None else [C.c_void_p(t.data_ptr()) for t in planes]
+        n = self._check(self._L.hm_pileup_fetch_asm(self._h, *ptrs, plane_base, lo, hi, min_cov, None, 0))
+        out = np.zeros(n, ASM_DTYPE)
+        if n:
+            self._check(self._L.hm_pileup_fetch_asm(self._h, *ptrs, plane_base, lo, hi, min_cov, out.ctypes.data_as(C.c_void_p), n))
+        return out
+
+    def asm_bed(self, rows: np.ndarray) -> dict:
+        """the text of <prefix>.asm.{CpG,CHG,CHH}.bed: chrom, k, k+1, diff, pvalue, pcov1, ncov1, pcov2, ncov2"""
+        sid = np.searchsorted(self.offsets, rows["gpos"], side="right") - 1
+        soff = rows["gpos"] - self.offsets[sid]
+        text = {k: [] for k in CTX_NAMES}
+        for s, k, r in zip(sid, soff, rows):
+            text[CTX_NAMES[int(r["motif"])]].append("%s\t%d\t%d\t%g\t%.6g\t%d\t%d\t%d\t%d\n" % (
+                self.names[s], k, k + 1, r["diff"], r["pvalue"], r["pcov1"], r["ncov1"], r["pcov2"], r["ncov2"]))
+        return {k: "".join(v) for k, v in text.items()}
 
 
 # ---- multi-GPU exchange (SURVEY.md section 8e): histograms all-reduced, per-locus planes reduce-scattered ------------

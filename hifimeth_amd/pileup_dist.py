@@ -1,7 +1,7 @@
 """`hifimeth pileup` over N GPUs of one node, one process per GPU (the path's only exchange step).
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
-        -m hifimeth_amd.pileup_dist [-q mapQ] [-f identity] [-H] reference.fa mod.bam output-prefix
+        -m hifimeth_amd.pileup_dist [-q mapQ] [-f identity] [-H [-A [-a min-cov]]] reference.fa mod.bam output-prefix
 
 Records are dealt to the ranks in slabs of `--slab` records (round-robin, like the `call` path).  Each rank projects its
 records and histograms them on its own GPU; then
@@ -13,6 +13,8 @@ records and histograms them on its own GPU; then
 A single process (no torchrun) runs the same code with the collectives skipped.
 -H (haplotypes): four more planes (pcov / ncov of HP 1 and HP 2) are counted with the same thresholds, reduce-scattered
 with SUM next to the three above, and rank 0 also writes <prefix>.hap1.<ctx>.cov.bed / <prefix>.hap2.<ctx>.cov.bed.
+-A (with -H): every rank tests its own chunk of the reduce-scattered haplotype planes (hm_pileup_fetch_asm, plane_base = the
+chunk's first locus) and rank 0 also writes <prefix>.asm.<ctx>.bed; no further collective.
 """
 from __future__ import annotations
 
@@ -29,7 +31,8 @@ from .pileup import (CTX_NAMES, MethylationPileup, allreduce_histograms, locus_r
 
 
 def run(reference: str, bam: str, prefix: str, min_mapq: int = 0, min_pi: float = 0.0, slab: int = 256,
-        batch: int = 256, backend: str | None = None, log=sys.stderr, haplotypes: bool = False):
+        batch: int = 256, backend: str | None = None, log=sys.stderr, haplotypes: bool = False, asm: bool = False,
+        asm_min_cov: int = 5):
     import torch
     rank, local_rank, world = D.env_world()
     dist = D.init_process_group(backend, force=bool(os.environ.get("HM_FORCE_COLLECTIVES")))
@@ -113,6 +116,8 @@ def run(reference: str, bam: str, prefix: str, min_mapq: int = 0, min_pi: float 
     part = {"": pu.bed(loci)}                               # file tag -> {context: text}
     for k in range(len(hp) // 2):                           # a partition: its counts, the combined key's motif
         part[f"hap{k + 1}."] = pu.bed(pu.loci(0, hi - lo, planes=(hp[2 * k], hp[2 * k + 1], key), plane_base=base))
+    if asm:                                                 # the two partitions' chunks and the key's lie on the same range
+        part["asm."] = pu.asm_bed(pu.asm(0, hi - lo, asm_min_cov, planes=(*hp, key), plane_base=base))
     if dist is not None:
         parts = [None] * world if rank == 0 else None
         dist.gather_object(part, parts, dst=0)
@@ -121,7 +126,7 @@ def run(reference: str, bam: str, prefix: str, min_mapq: int = 0, min_pi: float 
     if rank == 0:
         for tag in parts[0]:
             for c in CTX_NAMES:
-                with open(f"{prefix}.{tag}{c}.cov.bed", "w") as f:
+                with open(f"{prefix}.{tag}{c}" + (".bed" if tag == "asm." else ".cov.bed"), "w") as f:
                     for p in parts:
                         f.write(p[tag][c])
     pu.close()
@@ -139,11 +144,21 @@ def main(argv=None):
     ap.add_argument("--backend", default=None, help="nccl (RCCL, default on GPUs) or gloo")
     ap.add_argument("-H", dest="haplotypes", action="store_true",
                     help="haplotype-resolved output: also <prefix>.hap1.* / <prefix>.hap2.* from the HP tag")
+    ap.add_argument("-A", dest="asm", action="store_true",
+                    help="with -H: per-locus haplotype difference + Fisher exact test -> <prefix>.asm.<ctx>.bed")
+    ap.add_argument("-a", dest="asm_min_cov", type=int, default=None, help="with -A: minimum coverage of each haplotype (default 5)")
     ap.add_argument("reference")
     ap.add_argument("mod_bam")
     ap.add_argument("output_prefix")
     a = ap.parse_args(argv)
-    return run(a.reference, a.mod_bam, a.output_prefix, a.q, a.f, slab=a.slab, backend=a.backend, haplotypes=a.haplotypes)
+    if a.asm and not a.haplotypes:
+        ap.error("-A needs -H")
+    if a.asm_min_cov is not None and not a.asm:
+        ap.error("-a needs -A")
+    if a.asm_min_cov is not None and a.asm_min_cov < 1:
+        ap.error("-a must be >= 1")
+    return run(a.reference, a.mod_bam, a.output_prefix, a.q, a.f, slab=a.slab, backend=a.backend, haplotypes=a.haplotypes,
+               asm=a.asm, asm_min_cov=5 if a.asm_min_cov is None else a.asm_min_cov)
 
 
 if __name__ == "__main__":

@@ -208,6 +208,7 @@ int hm_reset_timing(hm_engine_t* e);
  *   3 x 256 probability histograms          (pileup.cpp:237-272)                     -> hm_pileup_histograms
  *   per-locus pcov / ncov / motif           (pileup.cpp:519-560)                     -> hm_pileup_count
  *   rows of <prefix>.<ctx>.cov.bed          (pileup.cpp:562-590)                     -> hm_pileup_fetch_loci
+ *   (ours) haplotype difference per locus, rows of <prefix>.asm.<ctx>.bed         -> hm_pileup_fetch_asm
  * The whole genome's counters stay resident in HBM (12 B per reference base, 28 B with the haplotype partitions) and the
  * projected calls wait in HBM (12 B each) until the thresholds are known -- the reference spills them to a temporary file.
  * MM/ML parsing and BED text formatting stay on the host (hm_bam.h).                                           */
@@ -283,6 +284,26 @@ int hm_pileup_count(hm_pileup_t* p, const uint8_t thr[3]);
  * nothing is written). */
 int64_t hm_pileup_fetch_loci(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key,
                              int64_t plane_base, int64_t lo, int64_t hi, hm_locus_t* out, int64_t cap);
+
+/* ---- allele-specific methylation (`pileup -H -A`): where do the two haplotypes differ -------------
+ * A locus is tested when EACH haplotype partition has pcov + ncov >= min_cov.  diff = 100 * p1 / (p1 + n1) - 100 * p2 / (p2 + n2)
+ * in fp64 (bit-equal to the host's), pvalue = two-sided Fisher exact test of [[p1, n1], [p2, n2]] with R's rule (margins fixed,
+ * sum of the hypergeometric probabilities of all tables with probability <= P(observed) * (1 + 1e-7)), <= 1.0 and never 0
+ * (a value below DBL_MIN is reported as DBL_MIN).  Computed on the device from a log n! table (65 536 entries, uploaded by the
+ * first call; larger totals use lgamma in the kernel); a pure function of the four counts. */
+typedef struct {            /* one tested locus = one row of <prefix>.asm.<ctx>.bed; 48 bytes */
+    int64_t gpos;
+    int32_t pcov1, ncov1, pcov2, ncov2;
+    uint32_t motif, reserved;
+    double diff, pvalue;
+} hm_asm_t;
+/* tested loci of planes[lo, hi) in ascending order.  All five plane pointers NULL = the engine's own partition and key planes;
+ * else DEVICE pointers whose element 0 is locus plane_base (what a reduce-scatter leaves on a rank).  Returns the number of
+ * rows (may exceed cap: then nothing is written).  HM_ESTATE without option "partitions" = 2 when the planes are NULL,
+ * HM_EINVAL for min_cov < 1, lo > hi, or a mix of NULL and non-NULL planes. */
+int64_t hm_pileup_fetch_asm(hm_pileup_t* p, const void* pcov1, const void* ncov1, const void* pcov2, const void* ncov2,
+                            const void* key, int64_t plane_base, int64_t lo, int64_t hi, int32_t min_cov,
+                            hm_asm_t* out, int64_t cap);
 
 #ifdef __cplusplus
 }

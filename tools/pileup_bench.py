@@ -7,8 +7,9 @@ H2D of the staged records, plane memset, mods_kernel, project_kernel, then count
 compaction at the end.  Prints one JSON object; `--check` verifies that the per-locus counters add up to the number of projected calls.
 `--partitions`: the haplotype-resolved engine (`pileup -H`), every read tagged with a random HP of {none, 1, 2}; the loci
 fetch then also compacts the two partitions' planes.
+`--asm` (with `--partitions`): the allele-specific test of `pileup -H -A` over the counted planes: select + Fisher test + D2H per pass.
 
-    python tools/pileup_bench.py --genome-mb 20 --coverage 10 [--partitions]
+    python tools/pileup_bench.py --genome-mb 20 --coverage 10 [--partitions [--asm]]
 """
 import argparse
 import ctypes as C
@@ -83,9 +84,13 @@ def main():
     ap.add_argument("--repeat", type=int, default=3, help="timed passes over the staged read set")
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--partitions", action="store_true", help="haplotype partitions on, reads tagged with random HP")
+    ap.add_argument("--asm", action="store_true", help="with --partitions: time the per-locus haplotype test (pileup -H -A)")
+    ap.add_argument("--asm-min-cov", type=int, default=5)
     ap.add_argument("--cpu-baseline", action="store_true",
                     help="time the reference's own projection code (oracle/_ref/ref_align -t) on a bounded sample")
     a = ap.parse_args()
+    if a.asm and not a.partitions:
+        ap.error("--asm needs --partitions")
 
     rng = np.random.default_rng(1)
     G = int(a.genome_mb * 1e6)
@@ -151,6 +156,23 @@ def main():
                loci_scan_bases_per_s=round(G / t_loci), partitions=a.partitions)
     if a.partitions:
         out.update(partition_loci=[int(len(x)) for x in hp_loci], partition_loci_fetch_s=round(t_hp_loci, 4))
+    if a.asm:                                      # select + test + fetch of every tested locus, as the CLI does per sequence
+        pu.asm(min_cov=a.asm_min_cov)              # warm-up: the log n! table and the row buffer
+        t0 = time.perf_counter()
+        for _ in range(a.repeat):
+            rows = pu.asm(min_cov=a.asm_min_cov)
+        t_asm = (time.perf_counter() - t0) / a.repeat
+        t0 = time.perf_counter()
+        for _ in range(a.repeat):                  # the count-only call: predicate + scan, no test
+            n_rows = pu._L.hm_pileup_fetch_asm(pu._h, None, None, None, None, None, 0, 0, G, a.asm_min_cov, None, 0)
+        t_sel = (time.perf_counter() - t0) / a.repeat
+        assert n_rows == len(rows)
+        steps = np.minimum(np.minimum(rows["pcov1"] + rows["ncov1"], rows["pcov2"] + rows["ncov2"]),
+                           np.minimum(rows["pcov1"] + rows["pcov2"], rows["ncov1"] + rows["ncov2"])).astype(np.int64) + 1
+        out.update(asm_min_cov=a.asm_min_cov, asm_rows=int(len(rows)), asm_s_per_pass=round(t_asm, 4),
+                   asm_count_only_s=round(t_sel, 4), asm_rows_per_s=round(len(rows) / t_asm),
+                   asm_mean_tables_per_row=round(float(steps.mean()), 1) if len(rows) else 0.0,
+                   asm_share_of_pass=round(t_asm / (t_project / a.repeat + t_count / a.repeat + t_loci + t_hp_loci + t_asm), 4))
     if a.check:                                    # every pass (and the warm-up) adds the same records
         total = int((loci["pcov"].astype(np.int64) + loci["ncov"]).sum())
         out["check_total_records"] = total == recs_per_pass * (a.repeat + 1)
