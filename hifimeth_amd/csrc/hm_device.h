@@ -49,12 +49,24 @@ constexpr int NCNT = 5;
 // totals == nullptr: `base` is the list itself (or nullptr for caller-supplied windows) and `cap` the exact count.
 struct SiteRange {
     const Site* base;       // the three per-context lists back to back
-    const int32_t* totals;  // [0..2] sites per context, [3] all, [4..6] first element of each context's list
+    const int32_t* totals;  // [ctx] sites per context, [TOT_ALL] all, [TOT_CTX_BASE + ctx] first element of each context's list
     int32_t ctx, off, cap;
     // optional sub-range [*lo, *hi) of the context's list: the sites of one read group (the scanned per-chunk counters
     // at the group's first chunk and at the first chunk behind it); nullptr = the whole list
     const int32_t* lo;
     const int32_t* hi;
+};
+
+// The slots of a batch's totals array as the host reads them.  The scan kernel writes the first eight ([ctx] = sites of
+// context ctx); the sliding-window trunk and the strip tail count their work into the rest.
+enum TotalsSlot {
+    TOT_ALL = 3,            // sites of all contexts = calls of the batch
+    TOT_CTX_BASE = 4,       // + ctx: first element of the context's list in the per-context site lists
+    TOT_REVERSE = 7,        // reverse-strand sites
+    TOT_LIST_STEPS = 8,     // + ctx: the trunk's listed-row steps
+    TOT_STRIP_PASSES = 11,  // passes of the strip tail
+    TOT_CONST_STEPS = 12,   // + ctx: the trunk's constant steps
+    TOT_COUNT = 16
 };
 
 // ---- dense trunk (hm_trunk.hip) ---------------------------------------------------------------------------------------

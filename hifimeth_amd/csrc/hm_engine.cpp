@@ -24,6 +24,7 @@
 
 #include "../../include/hifimeth_hip.h"
 #include "hm_device.h"
+#include "hm_host.h"
 #include "hm_kernels.h"
 #include "hm_weights.h"
 
@@ -33,70 +34,12 @@ namespace {
 
 thread_local std::string g_create_error;
 
-struct HipErr {
-    hipError_t code;
-    const char* what;
-};
-
-#define HIP_TRY(expr)                                  \
-    do {                                               \
-        hipError_t _e = (expr);                        \
-        if (_e != hipSuccess) throw HipErr{_e, #expr}; \
-    } while (0)
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    void reserve(size_t bytes) {
-        if (bytes <= cap) return;
-        if (p) HIP_TRY(hipFree(p));
-        p = nullptr;
-        cap = 0;
-        size_t want = bytes + bytes / 4 + 256;
-        HIP_TRY(hipMalloc(&p, want));
-        cap = want;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    template <class T>
-    T* as() const { return reinterpret_cast<T*>(p); }
-};
-
-// grow-only pinned host array: what an asynchronous copy may read from / write to
-template <class T>
-struct PinnedArr {
-    T* p = nullptr;
-    size_t n = 0, cap = 0;
-    void reserve(size_t want) {
-        if (want <= cap) return;
-        want = std::max(want + want / 2, size_t(4096) / sizeof(T) + 1);
-        T* q = nullptr;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&q), want * sizeof(T), hipHostMallocDefault));
-        if (n) memcpy(q, p, n * sizeof(T));
-        if (p) (void)hipHostFree(p);
-        p = q;
-        cap = want;
-    }
-    void push_back(const T& v) {
-        if (n == cap) reserve(n + 1);
-        p[n++] = v;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        n = cap = 0;
-    }
-};
-
 enum Kind { K_PREP, K_SCAN, K_EMIT, K_PACK, K_WINDOW, K_FRONT, K_TAIL, K_TRUNK, K_EDGE, K_TAILG };
 
 struct TimedSpan {
     int kind, ctx;
     int64_t off, cap;  // CNN spans: launch window into the context's site list; K_WINDOW: cap = sites
-    hipEvent_t a, b;
+    Event a, b;
 };
 
 struct DeviceModel {
@@ -114,8 +57,8 @@ struct hm_batch {
     int id = 0;
     enum State { FREE, STAGING, QUEUED } state = FREE;
     bool uploaded = false, ran = false, have_totals = false, have_calls = false;
-    hipStream_t s_io = nullptr;  // this slot's copies in and out
-    hipEvent_t ev_in = nullptr, ev_comp = nullptr, ev_out = nullptr;
+    Stream s_io;  // this slot's copies in and out.  Declared before every buffer: destroyed after them
+    Event ev_in, ev_comp, ev_out;
 
     // staged batch (host, pinned)
     PinnedArr<uint8_t> slab;
@@ -135,13 +78,38 @@ struct hm_batch {
     // device
     DevBuf d_raw, d_reads, d_chunks, d_rinfo, d_tiles, d_tcost, d_bases, d_kin, d_sctx, d_counts, d_offs, d_totals, d_err;
     DevBuf d_usites, d_utag, d_csites, d_opos, d_logits, d_p, d_ml, d_calls;
-    int32_t* h_totals = nullptr;  // pinned [16]: the scan kernel's 8 totals + the trunk's [8..10] listed-row and [12..14] constant steps per context
-    int32_t* h_err = nullptr;     // pinned
+    Pinned<int32_t> h_totals;  // [TOT_COUNT]: the scan kernel's 8 totals + what the trunk and the strip tail count (TotalsSlot)
+    Pinned<int32_t> h_err;
     PinnedArr<hm_call_t> h_calls;
-    int32_t totals[16] = {};
+    int32_t totals[TOT_COUNT] = {};
 
     std::vector<TimedSpan> spans;
+
+    ~hm_batch() {  // (the engine's destructor has made the device current)
+        if (s_io) (void)hipStreamSynchronize(s_io);
+    }
 };
+
+namespace {
+
+// Scratch of one read group: what hm_get_timing reports as group_bytes and GROUP_BYTES_PER_BASE budgets for
+struct GroupBufs {
+    DevBuf d_map[3], d_e4, d_edge4, d_e4row, d_rowlist;  // dense trunk: maps of one read group, edge rows of its sites
+    DevBuf d_x6;                // split tail: conv6's rows of one launch (hm_tail_s.hip)
+    DevBuf d_mark, d_ccnt, d_order, d_okey;  // strip tail (hm_tail_p.hip): per-map-row marks, class counters, the class-sorted site order and its keys
+    DevBuf d_odst;              // strip tail: list position -> the site's slot in the batch's result arrays (tail_fc_kernel's stores)
+    DevBuf d_x8;                // the rows of a launch's sites on their way from the strip tail kernel to its second kernel (TAIL_STRIP_HANDOVER_BYTES per site)
+    DevBuf d_dump;              // sliding-window trunk: where a warm-up step's conv4 rows go (hm_trunk3.hip)
+    int64_t bytes() const {
+        const DevBuf* all[] = {&d_map[0], &d_map[1], &d_map[2], &d_e4, &d_edge4, &d_e4row, &d_rowlist, &d_x6, &d_mark, &d_ccnt, &d_order, &d_okey, &d_odst, &d_x8, &d_dump};
+        static_assert(sizeof(GroupBufs) == sizeof all / sizeof *all * sizeof(DevBuf), "a member of GroupBufs is missing from bytes()");
+        int64_t sum = 0;
+        for (const DevBuf* d : all) sum += (int64_t)d->cap;
+        return sum;
+    }
+};
+
+}  // namespace
 
 struct hm_engine {
     int device = 0;
@@ -190,27 +158,28 @@ struct hm_engine {
     bool stamps_on = false;
     std::vector<unsigned long long> stamp_sum;
     bool timing = false;
-    hipStream_t stream = nullptr;  // compute
-    DeviceModel model[3];
     std::string err;
 
     std::mutex mu;  // slot states, error string, event pool, timing
     std::mutex order_mu;  // the kernels of two batches must not interleave on the compute stream
     std::condition_variable cv;
+    hm_timing_t acc{};
+    int64_t x6_sites = 0;  // the site count grp.d_x6's plane stride was laid out for
+
+    // What the engine holds on the device, in the order it is given back -- members are destroyed last to first: the slots,
+    // the models, the scratch all batches share, the event pool, the compute stream.
+    Stream stream;  // compute.  Declared before everything that runs on it: destroyed last
+    std::vector<Event> pool;
+    // scratch shared by all batches: only touched by kernels on the compute stream, which runs batches in order
+    DevBuf d_act4, d_win, d_dbg, d_stamps, d_zeros;
+    GroupBufs grp;
+    DeviceModel model[3];
     std::vector<std::unique_ptr<hm_batch>> slots;  // [0] = the batch of the legacy (synchronous) calls
 
-    // scratch shared by all batches: only touched by kernels on the compute stream, which runs batches in order
-    DevBuf d_act4, d_win, d_dbg, d_stamps;
-    DevBuf d_map[3], d_e4, d_edge4, d_e4row, d_zeros, d_rowlist;  // dense trunk: maps of one read group, edge rows of its sites
-    DevBuf d_x6;                // split tail: conv6's rows of one launch (hm_tail_s.hip)
-    DevBuf d_mark, d_ccnt, d_order, d_okey;  // strip tail (hm_tail_p.hip): per-map-row marks, class counters, the class-sorted site order and its keys
-    DevBuf d_odst;              // strip tail: list position -> the site's slot in the batch's result arrays (tail_fc_kernel's stores)
-    DevBuf d_x8;                // the rows of a launch's sites on their way from the strip tail kernel to its second kernel (TAIL_STRIP_HANDOVER_BYTES per site)
-    DevBuf d_dump;              // sliding-window trunk: where a warm-up step's conv4 rows go (hm_trunk3.hip)
-    int64_t x6_sites = 0;       // the site count d_x6's plane stride was laid out for
-
-    std::vector<hipEvent_t> pool;
-    hm_timing_t acc{};
+    ~hm_engine() {
+        (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
 };
 
 namespace {
@@ -278,20 +247,26 @@ int fail(hm_engine* e, int code, const std::string& msg) {
 }
 
 int fail_hip(hm_engine* e, const HipErr& h) {
-    return fail(e, HM_EDEVICE, std::string("HIP error: ") + hipGetErrorString(h.code) + " at " + h.what);
+    return fail(e, HM_EDEVICE, hip_error_text(h));
 }
 
-hipEvent_t get_event(hm_engine* e) {
+// every ABI entry point's device work: the engine's device current, a HipErr recorded as the engine's error -> HM_EDEVICE
+template <class Body>
+auto guarded(hm_engine* e, Body&& body) -> decltype(body()) {
+    return hip_guard(e->device, [e](const HipErr& h) { return fail_hip(e, h); }, body);
+}
+
+Event get_event(hm_engine* e) {
+    Event ev;
     {
         std::lock_guard<std::mutex> lk(e->mu);
         if (!e->pool.empty()) {
-            hipEvent_t ev = e->pool.back();
+            ev = std::move(e->pool.back());
             e->pool.pop_back();
             return ev;
         }
     }
-    hipEvent_t ev;
-    HIP_TRY(hipEventCreate(&ev));
+    HIP_TRY(hipEventCreate(&ev.h));
     return ev;
 }
 
@@ -314,7 +289,7 @@ struct Span {
     void end() {
         if (!on) return;
         HIP_TRY(hipEventRecord(ts.b, e->stream));
-        sink->push_back(ts);
+        sink->push_back(std::move(ts));
         on = false;
     }
 };
@@ -323,9 +298,9 @@ struct Span {
 void collect_timing(hm_engine* e, std::vector<TimedSpan>& spans, const int32_t* totals) {
     if (!spans.empty() && totals) {  // once per timed run of a batch
         std::lock_guard<std::mutex> lk(e->mu);
-        for (int c = 0; c < 3; ++c) e->acc.trunk_list_steps[c] += totals[8 + c];
-        for (int c = 0; c < 3; ++c) e->acc.trunk_const_steps[c] += totals[12 + c];
-        e->acc.tail_strip_passes += totals[11];
+        for (int c = 0; c < 3; ++c) e->acc.trunk_list_steps[c] += totals[TOT_LIST_STEPS + c];
+        for (int c = 0; c < 3; ++c) e->acc.trunk_const_steps[c] += totals[TOT_CONST_STEPS + c];
+        e->acc.tail_strip_passes += totals[TOT_STRIP_PASSES];
     }
     for (auto& s : spans) {
         float ms = 0.f;
@@ -351,8 +326,8 @@ void collect_timing(hm_engine* e, std::vector<TimedSpan>& spans, const int32_t* 
             else { t.empty_ms += ms; ++t.empty_launches; }
             break;
         }
-        e->pool.push_back(s.a);
-        e->pool.push_back(s.b);
+        e->pool.push_back(std::move(s.a));
+        e->pool.push_back(std::move(s.b));
     }
     spans.clear();
 }
@@ -446,45 +421,17 @@ hm_batch* new_slot(hm_engine* e, int id) {
     std::unique_ptr<hm_batch> b(new hm_batch());
     b->e = e;
     b->id = id;
-    HIP_TRY(hipStreamCreateWithFlags(&b->s_io, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&b->ev_in, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&b->ev_comp, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&b->ev_out, hipEventDisableTiming));
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->h_totals), 16 * sizeof(int32_t), hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b->h_err), sizeof(int32_t), hipHostMallocDefault));
-    memset(b->h_totals, 0, 16 * sizeof(int32_t));
-    *b->h_err = 0;
-    b->d_totals.reserve(16 * sizeof(int32_t));
+    HIP_TRY(hipStreamCreateWithFlags(&b->s_io.h, hipStreamNonBlocking));
+    for (Event* ev : {&b->ev_in, &b->ev_comp, &b->ev_out}) HIP_TRY(hipEventCreateWithFlags(&ev->h, hipEventDisableTiming));
+    b->h_totals.alloc(TOT_COUNT);
+    b->h_err.alloc();
+    b->d_totals.reserve(TOT_COUNT * sizeof(int32_t));
     b->d_err.reserve(sizeof(int32_t));
     HIP_TRY(hipMemset(b->d_err.p, 0, sizeof(int32_t)));
-    HIP_TRY(hipMemset(b->d_totals.p, 0, 16 * sizeof(int32_t)));
+    HIP_TRY(hipMemset(b->d_totals.p, 0, TOT_COUNT * sizeof(int32_t)));
     hm_batch* raw = b.get();
     e->slots.push_back(std::move(b));
     return raw;
-}
-
-void free_slot(hm_batch* b) {
-    if (b->s_io) (void)hipStreamSynchronize(b->s_io);
-    for (DevBuf* d : {&b->d_raw, &b->d_reads, &b->d_chunks, &b->d_rinfo, &b->d_tiles, &b->d_tcost, &b->d_bases, &b->d_kin, &b->d_sctx, &b->d_counts, &b->d_offs,
-                      &b->d_totals, &b->d_err, &b->d_usites, &b->d_utag, &b->d_csites, &b->d_opos, &b->d_logits, &b->d_p,
-                      &b->d_ml, &b->d_calls})
-        d->release();
-    b->slab.release();
-    b->reads.release();
-    b->chunks.release();
-    b->rinfo.release();
-    b->tiles.release();
-    b->tcost.release();
-    b->h_calls.release();
-    if (b->h_totals) (void)hipHostFree(b->h_totals);
-    if (b->h_err) (void)hipHostFree(b->h_err);
-    for (auto& s : b->spans) {
-        (void)hipEventDestroy(s.a);
-        (void)hipEventDestroy(s.b);
-    }
-    for (hipEvent_t ev : {b->ev_in, b->ev_comp, b->ev_out})
-        if (ev) (void)hipEventDestroy(ev);
-    if (b->s_io) (void)hipStreamDestroy(b->s_io);
 }
 
 void reset_staging(hm_batch* b) {
@@ -500,52 +447,75 @@ void reset_staging(hm_batch* b) {
     memset(b->totals, 0, sizeof b->totals);
 }
 
-// EvalKmerFeaturesGenerator::init: copy one read into the slot's pinned slab exactly as the BAM record stores it
+// ---- staging: EvalKmerFeaturesGenerator::init, a read into the slot's pinned slab exactly as the BAM record stores it ----
+// hm_submit_read / hm_batch_submit_read (stage_read) and hm_batch_submit_reads share check_read and place_read; they differ
+// in how they grow the slab and in when the bytes are copied.
+
+// Is the read staged?  1 = yes; 0 = passed through uncalled; < 0 = error, recorded for `who` (`full` = what to do about a full
+// batch).  tb = the batch's bases including the accepted reads in front of this one.
+int check_read(hm_engine* e, const hm_read_t& r, int64_t tb, const char* who, const char* full) {
+    if (r.l_qseq < 0) return fail(e, HM_EINVAL, std::string(who) + ": negative read length");
+    if (r.l_qseq < e->min_read_size) return 0;                   // mod_main.cpp:189-192
+    if (!r.kin[0] || !r.kin[1] || !r.kin[2] || !r.kin[3]) return 0;  // BamKinetics::init false (bam_info.cpp:572-603)
+    if (!r.seq4) return fail(e, HM_EINVAL, std::string(who) + ": seq4 is NULL");
+    for (int k = 0; k < 4; ++k)
+        if (r.width[k] != 1 && r.width[k] != 2) return fail(e, HM_EINVAL, "kinetics element width must be 1 (B:C) or 2 (B:S)");
+    // site ranks and per-base offsets inside one batch are 32-bit on the device: keep a batch under 2^31 bases
+    if (tb + (int64_t)r.l_qseq + 4 >= (int64_t(1) << 31)) return fail(e, HM_ENOMEM, std::string(who) + ": batch would exceed 2^31 bases; " + full);
+    return 1;
+}
+
+int64_t padded_bases(int32_t l_qseq) { return ((int64_t)l_qseq + 3) & ~int64_t(3); }
+
+struct SlabCopy {
+    const void* src;
+    size_t off, bytes;
+};
+
+// An accepted read takes its place in the batch: descriptor, chunk / tile lists, total_bases, and room in the slab (which the
+// caller has reserved) for its five arrays -- the bytes themselves are the caller's to copy: copies[0..4]
+void place_read(hm_batch* b, const hm_read_t& r, SlabCopy* copies) {
+    const size_t L = (size_t)r.l_qseq;
+    auto place = [&](const void* src, size_t bytes) {
+        const int64_t off = (int64_t)b->slab.n;
+        *copies++ = SlabCopy{src, (size_t)off, bytes};
+        b->slab.n += align16(bytes);
+        return off;
+    };
+    ReadDesc rd{};
+    rd.off_seq = place(r.seq4, (L + 1) / 2);
+    rd.off_fi = place(r.kin[0], L * r.width[0]);
+    rd.off_fp = place(r.kin[1], L * r.width[1]);
+    rd.off_ri = place(r.kin[2], L * r.width[2]);
+    rd.off_rp = place(r.kin[3], L * r.width[3]);
+    rd.base_off = b->total_bases;
+    rd.len = r.l_qseq;
+    rd.flag = r.flag;
+    rd.read_id = r.read_id;
+    for (int k = 0; k < 4; ++k) rd.w[k] = r.width[k];
+    const int ridx = (int)b->reads.n;
+    // dense trunk: the read's maps cover view positions [-200, L + 200) in tiles of TR_OWN; a new group starts when
+    // the current one holds group_bases
+    b->reads.push_back(rd);
+    add_read_tiles(b->e, b, ridx, r.l_qseq);
+    b->total_bases += padded_bases(r.l_qseq);
+}
+
 int stage_read(hm_batch* b, int32_t read_id, int32_t l_qseq, int32_t flag, const uint8_t* seq4, const void* fi, int fi_w,
                const void* fp, int fp_w, const void* ri, int ri_w, const void* rp, int rp_w) {
-    hm_engine* e = b->e;
-    if (l_qseq < 0) return HM_EINVAL;
-    if (l_qseq < e->min_read_size) return 0;        // mod_main.cpp:189-192
-    if (!fi || !fp || !ri || !rp) return 0;          // BamKinetics::init false (bam_info.cpp:572-603)
-    if (!seq4) return fail(e, HM_EINVAL, "hm_submit_read: seq4 is NULL");
-    // site ranks and per-base offsets inside one batch are 32-bit on the device: keep a batch under 2^31 bases
-    if (b->total_bases + (int64_t)l_qseq + 4 >= (int64_t(1) << 31))
-        return fail(e, HM_ENOMEM, "hm_submit_read: batch would exceed 2^31 bases; flush / queue it first");
-    const int w[4] = {fi_w, fp_w, ri_w, rp_w};
-    for (int k = 0; k < 4; ++k)
-        if (w[k] != 1 && w[k] != 2) return fail(e, HM_EINVAL, "kinetics element width must be 1 (B:C) or 2 (B:S)");
-    try {
-        HIP_TRY(hipSetDevice(e->device));  // the pinned allocations below belong to this engine's device
+    auto width = [](int w) { return (uint8_t)std::clamp(w, 0, 255); };  // (anything but 1 and 2 stays something else)
+    const hm_read_t r{read_id, l_qseq, flag, {width(fi_w), width(fp_w), width(ri_w), width(rp_w)}, seq4, {fi, fp, ri, rp}};
+    const int rc = check_read(b->e, r, b->total_bases, "hm_submit_read", "flush / queue it first");
+    if (rc <= 0) return rc;
+    return guarded(b->e, [&] {  // (the pinned allocations belong to this engine's device)
         const size_t L = (size_t)l_qseq;
         const size_t need = align16((L + 1) / 2) + align16(L * fi_w) + align16(L * fp_w) + align16(L * ri_w) + align16(L * rp_w);
         if (b->slab.n + need > b->slab.cap) b->slab.reserve(std::max<size_t>((b->slab.n + need) * 2, size_t(64) << 20));
-        ReadDesc rd{};
-        auto put = [&](const void* src, size_t bytes) {
-            const int64_t off = (int64_t)b->slab.n;
-            memcpy(b->slab.p + off, src, bytes);
-            b->slab.n += align16(bytes);
-            return off;
-        };
-        rd.off_seq = put(seq4, (L + 1) / 2);
-        rd.off_fi = put(fi, L * fi_w);
-        rd.off_fp = put(fp, L * fp_w);
-        rd.off_ri = put(ri, L * ri_w);
-        rd.off_rp = put(rp, L * rp_w);
-        rd.base_off = b->total_bases;
-        rd.len = l_qseq;
-        rd.flag = flag;
-        rd.read_id = read_id;
-        for (int k = 0; k < 4; ++k) rd.w[k] = (uint8_t)w[k];
-        const int ridx = (int)b->reads.n;
-        // dense trunk: the read's maps cover view positions [-200, L + 200) in tiles of TR_OWN; a new group starts when
-        // the current one holds group_bases
-        b->reads.push_back(rd);
-        add_read_tiles(e, b, ridx, l_qseq);
-        b->total_bases += (int64_t)((L + 3) & ~size_t(3));
-    } catch (const HipErr& h) {
-        return fail_hip(e, h);
-    }
-    return 1;
+        SlabCopy copies[5];
+        place_read(b, r, copies);
+        for (const SlabCopy& c : copies) memcpy(b->slab.p + c.off, c.src, c.bytes);
+        return 1;
+    });
 }
 
 // staged slab + descriptors -> HBM, asynchronously on the slot's stream (everything it reads is pinned)
@@ -593,19 +563,19 @@ void run_trunk_path(hm_batch* b, std::vector<TimedSpan>* spans, int ctx_mask) {
         max_rows = std::max(max_rows, g.rows);
         max_bases = std::max(max_bases, g.bases);
     }
-    for (int i = 0; i < 3; ++i) e->d_map[i].reserve((size_t)max_rows * 2 * 256 * sizeof(uint16_t));
-    e->d_e4.reserve((size_t)max_rows * 2 * C4_CH * sizeof(float));
-    e->d_rowlist.reserve(std::max((size_t)(max_rows / TR_OWN + 1) * 2 * 3 * TR_OWN, trunk3_rowlist_bytes((max_rows / TR_OWN + 1) * 2)));
-    e->d_dump.reserve(trunk3_dump_bytes(e->num_cu));
-    e->d_edge4.reserve((size_t)max_bases * 2 * C4_CH * sizeof(float));
-    e->d_e4row.reserve((size_t)max_bases * sizeof(int32_t));
+    for (int i = 0; i < 3; ++i) e->grp.d_map[i].reserve((size_t)max_rows * 2 * 256 * sizeof(uint16_t));
+    e->grp.d_e4.reserve((size_t)max_rows * 2 * C4_CH * sizeof(float));
+    e->grp.d_rowlist.reserve(std::max((size_t)(max_rows / TR_OWN + 1) * 2 * 3 * TR_OWN, trunk3_rowlist_bytes((max_rows / TR_OWN + 1) * 2)));
+    e->grp.d_dump.reserve(trunk3_dump_bytes(e->num_cu));
+    e->grp.d_edge4.reserve((size_t)max_bases * 2 * C4_CH * sizeof(float));
+    e->grp.d_e4row.reserve((size_t)max_bases * sizeof(int32_t));
     if (e->tail_impl == 3 && e->precision >= 1 && (ctx_mask >> CHH & 1)) {   // strip tail: sized for the largest group, before anything is queued
-        e->d_mark.reserve(tail_strip_mark_bytes(2 * max_rows));
-        e->d_ccnt.reserve(tail_strip_count_bytes(2 * max_rows));
-        e->d_order.reserve((size_t)max_bases * sizeof(int32_t));
-        e->d_okey.reserve((size_t)max_bases * sizeof(int32_t));
-        e->d_odst.reserve((size_t)max_bases * sizeof(int32_t));
-        e->d_x8.reserve(tail_strip_handover_bytes(max_bases));
+        e->grp.d_mark.reserve(tail_strip_mark_bytes(2 * max_rows));
+        e->grp.d_ccnt.reserve(tail_strip_count_bytes(2 * max_rows));
+        e->grp.d_order.reserve((size_t)max_bases * sizeof(int32_t));
+        e->grp.d_okey.reserve((size_t)max_bases * sizeof(int32_t));
+        e->grp.d_odst.reserve((size_t)max_bases * sizeof(int32_t));
+        e->grp.d_x8.reserve(tail_strip_handover_bytes(max_bases));
     }
     if (!e->d_zeros.p) {
         e->d_zeros.reserve(1024);
@@ -614,8 +584,8 @@ void run_trunk_path(hm_batch* b, std::vector<TimedSpan>* spans, int ctx_mask) {
     const bool w16 = false;
     const int32_t* offs = b->d_offs.as<int32_t>();
     for (const auto& g : b->groups) {
-        const TrunkMaps maps{{e->d_map[0].as<uint16_t>(), e->d_map[1].as<uint16_t>(), e->d_map[2].as<uint16_t>()},
-                             e->d_e4.as<uint16_t>(), g.rows, e->d_zeros.as<uint16_t>(), e->d_rowlist.as<uint8_t>()};
+        const TrunkMaps maps{{e->grp.d_map[0].as<uint16_t>(), e->grp.d_map[1].as<uint16_t>(), e->grp.d_map[2].as<uint16_t>()},
+                             e->grp.d_e4.as<uint16_t>(), g.rows, e->d_zeros.as<uint16_t>(), e->grp.d_rowlist.as<uint8_t>()};
         const int n_tiles = g.tile_hi - g.tile_lo;
         for (int c = 0; c < 3; ++c) {
             if (!(ctx_mask >> c & 1)) continue;
@@ -633,11 +603,11 @@ void run_trunk_path(hm_batch* b, std::vector<TimedSpan>* spans, int ctx_mask) {
                 {
                     Span sp(e, spans, K_EDGE, c);
                     launch_edge_f32(e->stream, dm.k1, sr, b->d_rinfo.as<RInfo>(), b->d_bases.as<uint8_t>(), b->d_kin.as<uint32_t>(), dm.w,
-                                    maps, e->d_edge4.as<float>(), e->d_e4row.as<int32_t>(), e->num_cu);
+                                    maps, e->grp.d_edge4.as<float>(), e->grp.d_e4row.as<int32_t>(), e->num_cu);
                     sp.end();
                 }
                 Span sp(e, spans, K_TAILG, c);
-                launch_tail_gather_f32(e->stream, sr, dm.w, maps, e->d_edge4.as<float>(), e->d_e4row.as<int32_t>(),
+                launch_tail_gather_f32(e->stream, sr, dm.w, maps, e->grp.d_edge4.as<float>(), e->grp.d_e4row.as<int32_t>(),
                                        b->d_logits.as<float>(), b->d_p.as<float>(), b->d_ml.as<uint8_t>(), e->num_cu);
                 sp.end();
                 continue;
@@ -646,8 +616,8 @@ void run_trunk_path(hm_batch* b, std::vector<TimedSpan>* spans, int ctx_mask) {
                 Span sp(e, spans, K_TRUNK, c, 0, (int64_t)n_tiles * TR_OWN * n_views);
                 if (e->trunk_impl == 3)
                     launch_trunk3(e->stream, dm.k1, b->d_tiles.as<TrunkTile>() + g.tile_lo, n_tiles, n_views, c, b->d_rinfo.as<RInfo>(),
-                                  b->d_bases.as<uint8_t>(), b->d_kin.as<uint32_t>(), b->d_sctx.as<uint8_t>(), b->total_bases, dm.w, maps, e->d_dump.as<uint16_t>(),
-                                  b->d_totals.as<int32_t>() + 8, b->d_tcost.as<int32_t>() + g.cost_lo, e->num_cu, e->conv3_w16 != 0);
+                                  b->d_bases.as<uint8_t>(), b->d_kin.as<uint32_t>(), b->d_sctx.as<uint8_t>(), b->total_bases, dm.w, maps, e->grp.d_dump.as<uint16_t>(),
+                                  b->d_totals.as<int32_t>() + TOT_LIST_STEPS, b->d_tcost.as<int32_t>() + g.cost_lo, e->num_cu, e->conv3_w16 != 0);
                 else if (e->trunk_impl)
                     launch_trunk2(e->stream, dm.k1, b->d_tiles.as<TrunkTile>() + g.tile_lo, n_tiles, n_views, c, b->d_rinfo.as<RInfo>(),
                                   b->d_bases.as<uint8_t>(), b->d_kin.as<uint32_t>(), b->d_sctx.as<uint8_t>(), dm.w, maps, e->num_cu, w16,
@@ -661,10 +631,10 @@ void run_trunk_path(hm_batch* b, std::vector<TimedSpan>* spans, int ctx_mask) {
                 Span sp(e, spans, K_EDGE, c);
                 if (e->edge_impl == 1)
                     launch_edge2(e->stream, dm.k1, sr, b->d_rinfo.as<RInfo>(), b->d_bases.as<uint8_t>(), b->d_kin.as<uint32_t>(), dm.w,
-                                 maps, e->d_edge4.as<uint16_t>(), e->d_e4row.as<int32_t>(), e->num_cu);
+                                 maps, e->grp.d_edge4.as<uint16_t>(), e->grp.d_e4row.as<int32_t>(), e->num_cu);
                 else
                     launch_edge(e->stream, dm.k1, sr, b->d_rinfo.as<RInfo>(), b->d_bases.as<uint8_t>(), b->d_kin.as<uint32_t>(), dm.w,
-                                maps, e->d_edge4.as<uint16_t>(), e->d_e4row.as<int32_t>(), e->num_cu, w16);
+                                maps, e->grp.d_edge4.as<uint16_t>(), e->grp.d_e4row.as<int32_t>(), e->num_cu, w16);
                 sp.end();
             }
             {
@@ -674,8 +644,8 @@ void run_trunk_path(hm_batch* b, std::vector<TimedSpan>* spans, int ctx_mask) {
                     // written) once, for the largest launch seen
                     const int64_t slice = std::min<int64_t>(e->tail_slice, std::max<int64_t>(max_bases, 1));
                     if (slice > e->x6_sites) {
-                        e->d_x6.reserve(tail_split_x6_bytes(slice));
-                        HIP_TRY(hipMemsetAsync(e->d_x6.p, 0, tail_split_x6_bytes(slice), e->stream));
+                        e->grp.d_x6.reserve(tail_split_x6_bytes(slice));
+                        HIP_TRY(hipMemsetAsync(e->grp.d_x6.p, 0, tail_split_x6_bytes(slice), e->stream));
                         e->x6_sites = slice;
                     }
                     const size_t ph = tail_split_x6_plane_halves(e->x6_sites);
@@ -683,19 +653,19 @@ void run_trunk_path(hm_batch* b, std::vector<TimedSpan>* spans, int ctx_mask) {
                         SiteRange s2 = sr;
                         s2.off = (int32_t)off;
                         s2.cap = (int32_t)std::min<int64_t>(e->x6_sites, g.bases - off);
-                        launch_tail_split(e->stream, s2, dm.w, maps, e->d_edge4.as<uint16_t>() + (size_t)off * (4 * C4_CH),
-                                          e->d_e4row.as<int32_t>() + off, e->d_x6.as<uint16_t>(), ph, b->d_logits.as<float>(),
+                        launch_tail_split(e->stream, s2, dm.w, maps, e->grp.d_edge4.as<uint16_t>() + (size_t)off * (4 * C4_CH),
+                                          e->grp.d_e4row.as<int32_t>() + off, e->grp.d_x6.as<uint16_t>(), ph, b->d_logits.as<float>(),
                                           b->d_p.as<float>(), b->d_ml.as<uint8_t>(), e->num_cu);
                     }
                 } else if (e->tail_impl == 3 && e->precision >= 1 && c == CHH) {
-                    launch_tail_strip(e->stream, sr, dm.w, maps, n_views, e->d_edge4.as<uint16_t>(), e->d_e4row.as<int32_t>(), e->d_mark.as<int32_t>(),
-                                      e->d_ccnt.as<int32_t>(), e->d_order.as<int32_t>(), e->d_okey.as<int32_t>(), e->d_odst.as<int32_t>(), e->d_x8.as<uint16_t>(),
-                                      b->d_logits.as<float>(), b->d_p.as<float>(), b->d_ml.as<uint8_t>(), b->d_totals.as<int32_t>() + 11, e->num_cu, e->precision == 2);
+                    launch_tail_strip(e->stream, sr, dm.w, maps, n_views, e->grp.d_edge4.as<uint16_t>(), e->grp.d_e4row.as<int32_t>(), e->grp.d_mark.as<int32_t>(),
+                                      e->grp.d_ccnt.as<int32_t>(), e->grp.d_order.as<int32_t>(), e->grp.d_okey.as<int32_t>(), e->grp.d_odst.as<int32_t>(), e->grp.d_x8.as<uint16_t>(),
+                                      b->d_logits.as<float>(), b->d_p.as<float>(), b->d_ml.as<uint8_t>(), b->d_totals.as<int32_t>() + TOT_STRIP_PASSES, e->num_cu, e->precision == 2);
                 } else if ((e->tail_impl == 1 || e->tail_impl == 3) && e->precision >= 1)
-                    launch_tail_gather_r(e->stream, sr, dm.w, maps, e->d_edge4.as<uint16_t>(), e->d_e4row.as<int32_t>(),
+                    launch_tail_gather_r(e->stream, sr, dm.w, maps, e->grp.d_edge4.as<uint16_t>(), e->grp.d_e4row.as<int32_t>(),
                                          b->d_logits.as<float>(), b->d_p.as<float>(), b->d_ml.as<uint8_t>(), e->num_cu, e->precision == 2);
                 else
-                    launch_tail_gather(e->stream, sr, dm.w, maps, e->d_edge4.as<uint16_t>(), e->d_e4row.as<int32_t>(),
+                    launch_tail_gather(e->stream, sr, dm.w, maps, e->grp.d_edge4.as<uint16_t>(), e->grp.d_e4row.as<int32_t>(),
                                        b->d_logits.as<float>(), b->d_p.as<float>(), b->d_ml.as<uint8_t>(), e->num_cu, 0);
                 sp.end();
             }
@@ -813,7 +783,7 @@ void enqueue_run(hm_batch* b) {
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(b->ev_comp, e->stream));
     HIP_TRY(hipStreamWaitEvent(b->s_io, b->ev_comp, 0));
-    HIP_TRY(hipMemcpyAsync(b->h_totals, b->d_totals.p, 16 * sizeof(int32_t), hipMemcpyDeviceToHost, b->s_io));
+    HIP_TRY(hipMemcpyAsync(b->h_totals, b->d_totals.p, TOT_COUNT * sizeof(int32_t), hipMemcpyDeviceToHost, b->s_io));
     HIP_TRY(hipMemcpyAsync(b->h_err, b->d_err.p, sizeof(int32_t), hipMemcpyDeviceToHost, b->s_io));
     HIP_TRY(hipEventRecord(b->ev_out, b->s_io));
     b->ran = true;
@@ -844,7 +814,7 @@ int fetch_calls(hm_batch* b) {
     int rc = wait_totals(b);
     if (rc < 0) return rc;
     if (b->have_calls) return HM_OK;
-    const size_t n = (size_t)b->totals[3];
+    const size_t n = (size_t)b->totals[TOT_ALL];
     b->h_calls.reserve(std::max<size_t>(n, 1));
     if (n) {
         HIP_TRY(hipMemcpyAsync(b->h_calls.p, b->d_calls.p, n * sizeof(hm_call_t), hipMemcpyDeviceToHost, b->s_io));
@@ -867,55 +837,34 @@ extern "C" {
 int hm_create(hm_engine_t** out, const char* model_dir, int ctx_mask, int device) {
     if (!out || !model_dir || !(ctx_mask & 7)) return fail(nullptr, HM_EINVAL, "hm_create: bad argument");
     *out = nullptr;
-    hm_engine* e = new hm_engine();
-    try {
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-            delete e;
-            return fail(nullptr, HM_EDEVICE, "hm_create: no usable HIP device (this library has no CPU fallback)");
-        }
-        HIP_TRY(hipSetDevice(device));
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev)
+        return fail(nullptr, HM_EDEVICE, "hm_create: no usable HIP device (this library has no CPU fallback)");
+    std::unique_ptr<hm_engine> e(new hm_engine());  // (a failure below gives back what was made so far: ~hm_engine)
+    e->device = device;
+    const int rc = hip_guard(device, [](const HipErr& h) { return fail_hip(nullptr, h); }, [&] {
         hipDeviceProp_t prop;
         HIP_TRY(hipGetDeviceProperties(&prop, device));
-        e->device = device;
         e->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
         e->ctx_mask = ctx_mask & 7;
-        HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+        HIP_TRY(hipStreamCreateWithFlags(&e->stream.h, hipStreamNonBlocking));
         static const char* names[3] = {"CpG", "CHG", "CHH"};  // mod_main.cpp:76,85,94
         for (int c = 0; c < 3; ++c) {
             if (!(e->ctx_mask >> c & 1)) continue;
             HostModel hmw;
             std::string msg;
-            if (!load_model_dir(model_dir, names[c], hmw, msg)) {
-                hm_destroy(e);
-                return fail(nullptr, HM_EMODEL, msg);
-            }
-            upload_model(e, c, hmw);
+            if (!load_model_dir(model_dir, names[c], hmw, msg)) return fail(nullptr, HM_EMODEL, msg);
+            upload_model(e.get(), c, hmw);
         }
-        new_slot(e, 0)->state = hm_batch::STAGING;
-    } catch (const HipErr& h) {
-        int rc = fail_hip(nullptr, h);
-        hm_destroy(e);
-        return rc;
-    }
-    *out = e;
+        new_slot(e.get(), 0)->state = hm_batch::STAGING;
+        return HM_OK;
+    });
+    if (rc < 0) return rc;
+    *out = e.release();
     return HM_OK;
 }
 
-void hm_destroy(hm_engine_t* e) {
-    if (!e) return;
-    (void)hipSetDevice(e->device);
-    if (e->stream) (void)hipStreamSynchronize(e->stream);
-    for (auto& b : e->slots) free_slot(b.get());
-    e->slots.clear();
-    for (auto& m : e->model) m.params.release();
-    for (DevBuf* b : {&e->d_act4, &e->d_win, &e->d_dbg, &e->d_stamps, &e->d_map[0], &e->d_map[1], &e->d_map[2], &e->d_e4, &e->d_rowlist,
-                      &e->d_edge4, &e->d_e4row, &e->d_zeros, &e->d_x6, &e->d_dump, &e->d_mark, &e->d_ccnt, &e->d_order, &e->d_okey, &e->d_odst, &e->d_x8})
-        b->release();
-    for (auto ev : e->pool) (void)hipEventDestroy(ev);
-    if (e->stream) (void)hipStreamDestroy(e->stream);
-    delete e;
-}
+void hm_destroy(hm_engine_t* e) { delete e; }  // ~hm_engine: device current, compute stream drained, then the members
 
 const char* hm_last_error(const hm_engine_t* e) { return e ? e->err.c_str() : g_create_error.c_str(); }
 
@@ -936,16 +885,14 @@ int hm_set_option(hm_engine_t* e, const char* key, int64_t value) {
         e->conv3_w16 = value != 0;
     } else if (k == "stamps") {
         e->stamps_on = value != 0;
-        if (e->stamps_on) {
-            try {
+        if (e->stamps_on)
+            return guarded(e, [&] {
                 const size_t bytes = (size_t)e->num_cu * 8 * front_stamp_slots() * sizeof(unsigned long long);
                 e->d_stamps.reserve(bytes);
                 HIP_TRY(hipMemset(e->d_stamps.p, 0, bytes));
                 e->stamp_sum.assign((size_t)front_stamp_slots() * 8, 0);
-            } catch (const HipErr& h) {
-                return fail_hip(e, h);
-            }
-        }
+                return HM_OK;
+            });
     } else if (k == "front_waves") {
         if (value != 4 && value != 8) return fail(e, HM_EINVAL, "front_waves must be 4 or 8");
         e->front_waves = (int)value;
@@ -1016,73 +963,53 @@ int hm_clear(hm_engine_t* e) {
 
 int hm_upload(hm_engine_t* e) {
     if (!e) return HM_EINVAL;
-    try {
-        HIP_TRY(hipSetDevice(e->device));
+    return guarded(e, [&] {
         enqueue_upload(legacy(e));
-    } catch (const HipErr& h) {
-        return fail_hip(e, h);
-    }
-    return HM_OK;
+        return HM_OK;
+    });
 }
 
 int hm_run(hm_engine_t* e) {
     if (!e) return HM_EINVAL;
     hm_batch* b = legacy(e);
     if (!b->uploaded) return fail(e, HM_ESTATE, "hm_run: nothing uploaded");
-    try {
-        HIP_TRY(hipSetDevice(e->device));
+    return guarded(e, [&] {
         if (b->ran && !b->have_totals) {  // a re-run: fold the previous run's spans first
             int rc = wait_totals(b);
             if (rc < 0) return rc;
         }
         enqueue_run(b);
-    } catch (const HipErr& h) {
-        return fail_hip(e, h);
-    }
-    return HM_OK;
+        return HM_OK;
+    });
 }
 
 int hm_sync(hm_engine_t* e) {
     if (!e) return HM_EINVAL;
     hm_batch* b = legacy(e);
-    try {
-        HIP_TRY(hipSetDevice(e->device));
+    return guarded(e, [&] {
         if (!b->ran) {
             if (b->uploaded) HIP_TRY(hipEventSynchronize(b->ev_in));
             return HM_OK;
         }
         return wait_totals(b);
-    } catch (const HipErr& h) {
-        return fail_hip(e, h);
-    }
+    });
 }
 
 int64_t hm_num_sites(hm_engine_t* e, int ctx) {
     if (!e || ctx < 0 || ctx > 3) return HM_EINVAL;
     hm_batch* b = legacy(e);
     if (!b->ran) return fail(e, HM_ESTATE, "hm_num_sites: hm_run first");
-    try {
-        HIP_TRY(hipSetDevice(e->device));
-        int rc = wait_totals(b);
-        if (rc < 0) return rc;
-    } catch (const HipErr& h) {
-        return fail_hip(e, h);
-    }
-    return b->totals[ctx];
+    const int rc = guarded(e, [&] { return wait_totals(b); });
+    return rc < 0 ? rc : b->totals[ctx];
 }
 
 int64_t hm_fetch(hm_engine_t* e, hm_call_t* out, int64_t cap) {
     if (!e || (!out && cap > 0)) return HM_EINVAL;
     hm_batch* b = legacy(e);
     if (!b->ran) return fail(e, HM_ESTATE, "hm_fetch: hm_run first");
-    try {
-        HIP_TRY(hipSetDevice(e->device));
-        int rc = fetch_calls(b);
-        if (rc < 0) return rc;
-    } catch (const HipErr& h) {
-        return fail_hip(e, h);
-    }
-    const int64_t n = b->totals[3];
+    const int rc = guarded(e, [&] { return fetch_calls(b); });
+    if (rc < 0) return rc;
+    const int64_t n = b->totals[TOT_ALL];
     if (n > cap) return fail(e, HM_EINVAL, "hm_fetch: output capacity too small");
     if (n) memcpy(out, b->h_calls.p, (size_t)n * sizeof(hm_call_t));
     return n;
@@ -1112,15 +1039,15 @@ hm_batch_t* hm_batch_begin(hm_engine_t* e) {
                 return b;
             }
         if ((int)e->slots.size() - 1 < e->max_slots) {
-            try {
-                HIP_TRY(hipSetDevice(e->device));
+            auto failed = [e](const HipErr& h) {  // e->mu is held: not through fail()
+                e->err = hip_error_text(h);
+                return nullptr;
+            };
+            return hip_guard(e->device, failed, [e] {
                 hm_batch* b = new_slot(e, (int)e->slots.size());
                 b->state = hm_batch::STAGING;
                 return b;
-            } catch (const HipErr& h) {
-                e->err = std::string("HIP error: ") + hipGetErrorString(h.code) + " at " + h.what;
-                return nullptr;
-            }
+            });
         }
         e->cv.wait(lk);  // every slot is staged or in flight: wait for an hm_batch_release
     }
@@ -1137,70 +1064,34 @@ int64_t hm_batch_submit_reads(hm_batch_t* b, const hm_read_t* reads, int64_t n, 
     if (!b || (!reads && n > 0) || n < 0) return HM_EINVAL;
     hm_engine* e = b->e;
     if (b->state != hm_batch::STAGING) return fail(e, HM_ESTATE, "hm_batch_submit_reads: batch is not being staged");
-    // pass 1 (serial): descriptors, chunk / tile lists and every read's place in the slab -- stage_read with the copies left out
-    struct Copy {
-        const void* src;
-        size_t off, bytes;
-    };
-    std::vector<Copy> copies;
+    // pass 1 (serial): every read's place in the batch and in the slab
+    std::vector<SlabCopy> copies;
     copies.reserve((size_t)n * 5);
-    int64_t taken = 0;
-    try {
-        HIP_TRY(hipSetDevice(e->device));
+    const int64_t taken = guarded(e, [&]() -> int64_t {
+        // every read is checked before the first one is placed: an error leaves the batch exactly as it was
+        std::vector<uint8_t> take((size_t)n);
         size_t need_total = 0;
+        int64_t tb = b->total_bases;
         for (int64_t i = 0; i < n; ++i) {
-            const hm_read_t& r = reads[i];
-            const size_t L = (size_t)std::max(r.l_qseq, 0);
-            need_total += align16((L + 1) / 2) + 4 * align16(L * 2);
+            const int rc = check_read(e, reads[i], tb, "hm_batch_submit_reads", "nothing was staged -- submit fewer reads per batch");
+            if (rc < 0) return rc;
+            take[(size_t)i] = (uint8_t)rc;
+            const size_t L = (size_t)reads[i].l_qseq;
+            need_total += align16((L + 1) / 2) + 4 * align16(L * 2);  // (room for every read of the block, as B:S)
+            if (rc) tb += padded_bases(reads[i].l_qseq);
         }
         if (b->slab.n + need_total > b->slab.cap) b->slab.reserve(std::max<size_t>(b->slab.n + need_total, size_t(64) << 20));
-        // every read is checked before the first one is placed: an error leaves the batch exactly as it was
-        {
-            int64_t tb = b->total_bases;
-            for (int64_t i = 0; i < n; ++i) {
-                const hm_read_t& r = reads[i];
-                if (r.l_qseq < 0) return fail(e, HM_EINVAL, "hm_batch_submit_reads: negative read length");
-                if (r.l_qseq < e->min_read_size || !r.kin[0] || !r.kin[1] || !r.kin[2] || !r.kin[3]) continue;
-                if (!r.seq4) return fail(e, HM_EINVAL, "hm_batch_submit_reads: seq4 is NULL");
-                for (int k = 0; k < 4; ++k)
-                    if (r.width[k] != 1 && r.width[k] != 2) return fail(e, HM_EINVAL, "kinetics element width must be 1 (B:C) or 2 (B:S)");
-                if (tb + (int64_t)r.l_qseq + 4 >= (int64_t(1) << 31))
-                    return fail(e, HM_ENOMEM, "hm_batch_submit_reads: batch would exceed 2^31 bases; nothing was staged -- submit fewer reads per batch");
-                tb += ((int64_t)r.l_qseq + 3) & ~int64_t(3);
-            }
-        }
+        int64_t placed = 0;
         for (int64_t i = 0; i < n; ++i) {
-            const hm_read_t& r = reads[i];
-            if (accepted) accepted[i] = 0;
-            if (r.l_qseq < e->min_read_size || !r.kin[0] || !r.kin[1] || !r.kin[2] || !r.kin[3]) continue;
-            const size_t L = (size_t)r.l_qseq;
-            ReadDesc rd{};
-            auto place = [&](const void* src, size_t bytes) {
-                const int64_t off = (int64_t)b->slab.n;
-                copies.push_back(Copy{src, (size_t)off, bytes});
-                b->slab.n += align16(bytes);
-                return off;
-            };
-            rd.off_seq = place(r.seq4, (L + 1) / 2);
-            rd.off_fi = place(r.kin[0], L * r.width[0]);
-            rd.off_fp = place(r.kin[1], L * r.width[1]);
-            rd.off_ri = place(r.kin[2], L * r.width[2]);
-            rd.off_rp = place(r.kin[3], L * r.width[3]);
-            rd.base_off = b->total_bases;
-            rd.len = r.l_qseq;
-            rd.flag = r.flag;
-            rd.read_id = r.read_id;
-            for (int k = 0; k < 4; ++k) rd.w[k] = r.width[k];
-            const int ridx = (int)b->reads.n;
-            b->reads.push_back(rd);
-            add_read_tiles(e, b, ridx, r.l_qseq);
-            b->total_bases += (int64_t)((L + 3) & ~size_t(3));
-            if (accepted) accepted[i] = 1;
-            ++taken;
+            if (accepted) accepted[i] = take[(size_t)i];
+            if (!take[(size_t)i]) continue;
+            copies.resize(copies.size() + 5);
+            place_read(b, reads[i], &copies[copies.size() - 5]);
+            ++placed;
         }
-    } catch (const HipErr& h) {
-        return fail_hip(e, h);
-    }
+        return placed;
+    });
+    if (taken < 0) return taken;
     // pass 2: the copies, dealt to the host threads
     const int nt = (int)std::clamp<int64_t>(threads, 1, 64);
     uint8_t* base = b->slab.p;
@@ -1229,8 +1120,7 @@ int hm_batch_enqueue(hm_batch_t* b) {
     if (!b) return HM_EINVAL;
     hm_engine* e = b->e;
     if (b->state != hm_batch::STAGING) return fail(e, HM_ESTATE, "hm_batch_enqueue: batch is not being staged");
-    try {
-        HIP_TRY(hipSetDevice(e->device));
+    return guarded(e, [&] {
         enqueue_upload(b);  // slot stream: independent of every other batch
         {
             std::lock_guard<std::mutex> lk(e->mu);
@@ -1238,10 +1128,8 @@ int hm_batch_enqueue(hm_batch_t* b) {
         }
         std::lock_guard<std::mutex> lk(e->order_mu);  // the compute stream takes batches in the order they are queued
         enqueue_run(b);
-    } catch (const HipErr& h) {
-        return fail_hip(e, h);
-    }
-    return HM_OK;
+        return HM_OK;
+    });
 }
 
 int hm_batch_done(hm_batch_t* b) {
@@ -1258,15 +1146,10 @@ int64_t hm_batch_wait(hm_batch_t* b, const hm_call_t** calls) {
     if (!b) return HM_EINVAL;
     hm_engine* e = b->e;
     if (b->state != hm_batch::QUEUED) return fail(e, HM_ESTATE, "hm_batch_wait: batch was not queued");
-    try {
-        HIP_TRY(hipSetDevice(e->device));
-        int rc = calls ? fetch_calls(b) : wait_totals(b);
-        if (rc < 0) return rc;
-    } catch (const HipErr& h) {
-        return fail_hip(e, h);
-    }
+    const int rc = guarded(e, [&] { return calls ? fetch_calls(b) : wait_totals(b); });
+    if (rc < 0) return rc;
     if (calls) *calls = b->h_calls.p;
-    return b->totals[3];
+    return b->totals[TOT_ALL];
 }
 
 int64_t hm_batch_num_sites(hm_batch_t* b, int ctx) {
@@ -1305,10 +1188,10 @@ int64_t hm_scan_sites(hm_engine_t* e, int ctx, int32_t* read_id, int32_t* qoff, 
     const int64_t n = b->totals[ctx];
     if (n > cap) return fail(e, HM_EINVAL, "hm_scan_sites: output capacity too small");
     if (n == 0) return 0;
-    try {
+    return guarded(e, [&] {
         std::vector<Site> s((size_t)n);
-        std::vector<uint8_t> tag((size_t)b->totals[3]);
-        HIP_TRY(hipMemcpy(s.data(), b->d_csites.as<Site>() + b->totals[4 + ctx], (size_t)n * sizeof(Site), hipMemcpyDeviceToHost));
+        std::vector<uint8_t> tag((size_t)b->totals[TOT_ALL]);
+        HIP_TRY(hipMemcpy(s.data(), b->d_csites.as<Site>() + b->totals[TOT_CTX_BASE + ctx], (size_t)n * sizeof(Site), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(tag.data(), b->d_utag.p, tag.size(), hipMemcpyDeviceToHost));
         for (int64_t i = 0; i < n; ++i) {
             if (read_id) read_id[i] = b->reads.p[(size_t)s[(size_t)i].read_idx].read_id;
@@ -1316,9 +1199,7 @@ int64_t hm_scan_sites(hm_engine_t* e, int ctx, int32_t* read_id, int32_t* qoff, 
             if (strand) strand[i] = tag[(size_t)s[(size_t)i].uidx] >> 2;
         }
         return n;
-    } catch (const HipErr& h) {
-        return fail_hip(e, h);
-    }
+    });
 }
 
 int64_t hm_site_logits(hm_engine_t* e, int ctx, float* logits, int64_t cap) {
@@ -1331,22 +1212,20 @@ int64_t hm_site_logits(hm_engine_t* e, int ctx, float* logits, int64_t cap) {
     if (n > cap) return fail(e, HM_EINVAL, "hm_site_logits: output capacity too small");
     if (n == 0) return 0;
     if (!logits) return HM_EINVAL;
-    try {
+    return guarded(e, [&]() -> int64_t {
         // every tail kernel writes logits[2 * uidx]: gather them in the order of the context's list
         std::vector<Site> s((size_t)n);
-        std::vector<float> lg((size_t)b->totals[3] * 2);
-        HIP_TRY(hipMemcpy(s.data(), b->d_csites.as<Site>() + b->totals[4 + ctx], (size_t)n * sizeof(Site), hipMemcpyDeviceToHost));
+        std::vector<float> lg((size_t)b->totals[TOT_ALL] * 2);
+        HIP_TRY(hipMemcpy(s.data(), b->d_csites.as<Site>() + b->totals[TOT_CTX_BASE + ctx], (size_t)n * sizeof(Site), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(lg.data(), b->d_logits.p, lg.size() * sizeof(float), hipMemcpyDeviceToHost));
         for (int64_t i = 0; i < n; ++i) {
             const size_t u = (size_t)s[(size_t)i].uidx;
-            if (u >= (size_t)b->totals[3]) return fail(e, HM_EDEVICE, "hm_site_logits: site index out of range");
+            if (u >= (size_t)b->totals[TOT_ALL]) return fail(e, HM_EDEVICE, "hm_site_logits: site index out of range");
             logits[2 * i] = lg[2 * u];
             logits[2 * i + 1] = lg[2 * u + 1];
         }
         return n;
-    } catch (const HipErr& h) {
-        return fail_hip(e, h);
-    }
+    });
 }
 
 int hm_windows(hm_engine_t* e, int ctx, int64_t first, int64_t n, float* out_host) {
@@ -1357,13 +1236,12 @@ int hm_windows(hm_engine_t* e, int ctx, int64_t first, int64_t n, float* out_hos
     if (rc < 0) return rc;
     if (first + n > b->totals[ctx]) return fail(e, HM_EINVAL, "hm_windows: site range out of bounds");
     if (n == 0) return HM_OK;
-    try {
-        HIP_TRY(hipSetDevice(e->device));
+    return guarded(e, [&] {
         const size_t bytes = (size_t)n * KMER * FEATS * sizeof(float);
         e->d_win.reserve(bytes);
         std::vector<TimedSpan> spans;
         Span sp(e, &spans, K_WINDOW, 0, 0, n);
-        launch_windows(e->stream, b->d_csites.as<Site>() + b->totals[4 + ctx] + first, (int)n, b->d_reads.as<ReadDesc>(),
+        launch_windows(e->stream, b->d_csites.as<Site>() + b->totals[TOT_CTX_BASE + ctx] + first, (int)n, b->d_reads.as<ReadDesc>(),
                        b->d_bases.as<uint8_t>(), b->d_kin.as<uint32_t>(), e->model[ctx].w.bn, e->d_win.as<float>(),
                        e->num_cu * 8);
         sp.end();
@@ -1371,37 +1249,28 @@ int hm_windows(hm_engine_t* e, int ctx, int64_t first, int64_t n, float* out_hos
         if (out_host) HIP_TRY(hipMemcpyAsync(out_host, e->d_win.p, bytes, hipMemcpyDeviceToHost, e->stream));
         HIP_TRY(hipStreamSynchronize(e->stream));
         collect_timing(e, spans, nullptr);
-    } catch (const HipErr& h) {
-        return fail_hip(e, h);
-    }
-    return HM_OK;
+        return HM_OK;
+    });
 }
 
 int hm_cnn_logits(hm_engine_t* e, int ctx, const float* windows, int64_t n, float* logits, float* p, uint8_t* ml) {
     if (!e || ctx < 0 || ctx > 2 || n < 0 || (!windows && n)) return HM_EINVAL;
     if (!e->model[ctx].loaded) return fail(e, HM_EINVAL, "hm_cnn_logits: context not enabled");
     if (n == 0) return HM_OK;
-    try {
-        HIP_TRY(hipSetDevice(e->device));
+    return guarded(e, [&] {
         const size_t bytes = (size_t)n * KMER * FEATS * sizeof(float);
         e->d_win.reserve(bytes);
         DevBuf d_lg, d_p, d_ml;  // results of this call only: the staged batch's buffers stay untouched
         d_lg.reserve((size_t)n * 2 * sizeof(float));
         d_p.reserve((size_t)n * sizeof(float));
         d_ml.reserve((size_t)n);
-        struct Guard {
-            DevBuf &a, &b, &c;
-            ~Guard() { a.release(); b.release(); c.release(); }
-        } guard{d_lg, d_p, d_ml};
         HIP_TRY(hipMemcpyAsync(e->d_win.p, windows, bytes, hipMemcpyHostToDevice, e->stream));
         run_cnn_windows(e, ctx, e->d_win.as<float>(), n, d_lg.as<float>(), d_p.as<float>(), d_ml.as<uint8_t>(), nullptr, 0);
         if (logits) HIP_TRY(hipMemcpy(logits, d_lg.p, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost));
         if (p) HIP_TRY(hipMemcpy(p, d_p.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
         if (ml) HIP_TRY(hipMemcpy(ml, d_ml.p, (size_t)n, hipMemcpyDeviceToHost));
-    } catch (const HipErr& h) {
-        return fail_hip(e, h);
-    }
-    return HM_OK;
+        return HM_OK;
+    });
 }
 
 int64_t hm_debug_layer(hm_engine_t* e, int ctx, const float* window, int layer, float* out, int64_t cap) {
@@ -1413,27 +1282,20 @@ int64_t hm_debug_layer(hm_engine_t* e, int ctx, const float* window, int layer, 
     for (int i = 1; i <= layer; ++i) len = (len + 2 - (i == 1 ? k1 : 3)) / 2 + 1;
     const int64_t nf = (int64_t)len * chans[layer];
     if (nf > cap) return fail(e, HM_EINVAL, "hm_debug_layer: output capacity too small");
-    try {
-        HIP_TRY(hipSetDevice(e->device));
+    return guarded(e, [&] {
         const size_t bytes = (size_t)KMER * FEATS * sizeof(float);
         e->d_win.reserve(bytes);
         e->d_dbg.reserve((size_t)nf * sizeof(float));
         DevBuf res;  // logits / p / ml of the one window
         res.reserve(64);
-        struct Guard {
-            DevBuf& a;
-            ~Guard() { a.release(); }
-        } guard{res};
         HIP_TRY(hipMemcpyAsync(e->d_win.p, window, bytes, hipMemcpyHostToDevice, e->stream));
         run_cnn_windows(e, ctx, e->d_win.as<float>(), 1, res.as<float>(), res.as<float>() + 2,
                         reinterpret_cast<uint8_t*>(res.as<float>() + 3), e->d_dbg.as<float>(), layer);
         // conv4 is the front->tail hand-off and already sits in HBM
         const void* src = layer == 4 ? e->d_act4.p : e->d_dbg.p;
         HIP_TRY(hipMemcpy(out, src, (size_t)nf * sizeof(float), hipMemcpyDeviceToHost));
-    } catch (const HipErr& h) {
-        return fail_hip(e, h);
-    }
-    return nf;
+        return nf;
+    });
 }
 
 int hm_convert_model(const char* src_path, const char* dst_hmw_path) {
@@ -1459,9 +1321,7 @@ int hm_get_timing(hm_engine_t* e, hm_timing_t* t) {
     std::lock_guard<std::mutex> lk(e->mu);
     *t = e->acc;
     t->group_bases = effective_group_bases(e);  // (sized from free device memory now if no read has been staged yet)
-    t->group_bytes = 0;
-    for (const DevBuf* d : {&e->d_map[0], &e->d_map[1], &e->d_map[2], &e->d_e4, &e->d_rowlist, &e->d_edge4, &e->d_e4row, &e->d_x6, &e->d_dump, &e->d_mark, &e->d_ccnt, &e->d_order, &e->d_okey, &e->d_odst, &e->d_x8})
-        t->group_bytes += (int64_t)d->cap;
+    t->group_bytes = e->grp.bytes();
     return HM_OK;
 }
 

@@ -14,7 +14,8 @@ namespace hm {
 void launch_prep(hipStream_t st, const uint8_t* raw, const ReadDesc* reads, const Chunk* chunks, int n_chunks,
                  int ctx_mask, uint8_t* bases, uint32_t* kin, uint8_t* sctx, int32_t* chunk_counts, int32_t* err);
 // S: exclusive scan of the NCNT chunk counters -> chunk offsets [n_chunks + 1][NCNT] (last row = totals),
-//    totals[12]: CpG, CHG, CHH, all, ctx_base[3], reverse-strand sites; [8..10] zeroed (the sliding-window trunk counts its listed-row steps there).
+//    totals[12]: CpG, CHG, CHH, all (TOT_ALL), ctx_base[3] (TOT_CTX_BASE), reverse-strand sites (TOT_REVERSE); [8..10] zeroed (TOT_LIST_STEPS:
+//    the sliding-window trunk counts its listed-row steps there).  hm_device.h names the slots (TotalsSlot).
 void launch_scan(hipStream_t st, const int32_t* chunk_counts, int n_chunks, int32_t* chunk_offs, int32_t* totals);
 // B: emit the unified (read, qoff)-ordered site list, the per-context lists and opos[uidx] = position of the site's
 //    call in the output order (per read: forward-strand calls by qoff, then reverse-strand calls; mod_main.cpp:217-251).

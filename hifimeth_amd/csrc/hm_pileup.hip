@@ -28,50 +28,18 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/hifimeth_hip.h"
+#include "hm_host.h"
+
+using namespace hm;
 
 namespace {
 
 thread_local std::string g_pileup_create_error;
-
-struct HipErr {
-    hipError_t code;
-    const char* what;
-};
-#define HIP_TRY(expr)                                  \
-    do {                                               \
-        hipError_t _e = (expr);                        \
-        if (_e != hipSuccess) throw HipErr{_e, #expr}; \
-    } while (0)
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    // grow to at least `bytes`, keeping the first `keep` bytes
-    void reserve(size_t bytes, size_t keep = 0, hipStream_t st = nullptr, bool exact = false) {
-        if (bytes <= cap) return;
-        const size_t want = exact ? bytes : bytes + bytes / 2 + 256;  // exact: genome-sized buffers, allocated once
-        void* q = nullptr;
-        HIP_TRY(hipMalloc(&q, want));
-        if (keep) {
-            HIP_TRY(hipMemcpyAsync(q, p, keep, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(hipStreamSynchronize(st));
-        }
-        if (p) (void)hipFree(p);
-        p = q;
-        cap = want;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    template <class T>
-    T* as() const { return reinterpret_cast<T*>(p); }
-};
 
 // ---- device-side records -----------------------------------------------------------------------------------
 struct PRead {
@@ -522,23 +490,24 @@ __global__ __launch_bounds__(TPB) void asm_test_kernel(hm_asm_t* __restrict__ ro
 
 // ================================================ host ==========================================================
 struct hm_pileup {
+    static constexpr DevBuf::Room EXACT = DevBuf::EXACT, HALF = DevBuf::HALF;  // genome-sized, allocated once / grows with the batches
     int device = 0;
-    hipStream_t stream = nullptr;
+    Stream stream;  // declared before every buffer: destroyed after them
     std::string err;
     int min_mapq = 0;
     double min_pi = 0.0;
 
     // reference
     std::vector<int64_t> seq_off;  // n_seqs + 1
-    DevBuf d_ref;
+    DevBuf d_ref{EXACT};
     bool own_planes = true;
-    DevBuf d_pcov, d_ncov, d_key;
+    DevBuf d_pcov{EXACT}, d_ncov{EXACT}, d_key{EXACT};
     int32_t* pcov = nullptr;
     int32_t* ncov = nullptr;
     uint32_t* key = nullptr;
     // haplotype partitions ("partitions" = 2): pcov / ncov planes of HP 1 and HP 2, +16 B per reference base
     int partitions = 0;
-    DevBuf d_hp_pcov[2], d_hp_ncov[2];
+    DevBuf d_hp_pcov[2]{DevBuf(EXACT), DevBuf(EXACT)}, d_hp_ncov[2]{DevBuf(EXACT), DevBuf(EXACT)};
     int32_t* hp_pcov[2] = {nullptr, nullptr};
     int32_t* hp_ncov[2] = {nullptr, nullptr};
 
@@ -551,11 +520,16 @@ struct hm_pileup {
     int64_t plane_len = 0, n_m_mods = 0;
 
     // device
-    DevBuf d_slab, d_reads, d_runs, d_col0, d_mods, d_plane, d_matches, d_bins, d_counter, d_recs;
-    DevBuf d_blk, d_offs, d_loci, d_labels, d_lbins;
-    DevBuf d_asm, d_lfact;  // tested rows of hm_pileup_fetch_asm; log n! table, uploaded by its first call
+    DevBuf d_slab{HALF}, d_reads{HALF}, d_runs{HALF}, d_col0{HALF}, d_mods{HALF}, d_plane{HALF}, d_matches{HALF}, d_bins{HALF}, d_counter{HALF}, d_recs{HALF};
+    DevBuf d_blk{HALF}, d_offs{HALF}, d_loci{HALF}, d_labels{HALF}, d_lbins{HALF};
+    DevBuf d_asm{HALF}, d_lfact{EXACT};  // tested rows of hm_pileup_fetch_asm; log n! table, uploaded by its first call
     int64_t n_recs = 0;
     bool bins_ready = false;
+
+    ~hm_pileup() {
+        (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
 };
 
 namespace {
@@ -566,7 +540,13 @@ int pfail(hm_pileup* p, int code, const std::string& msg) {
     return code;
 }
 int pfail_hip(hm_pileup* p, const HipErr& h) {
-    return pfail(p, HM_EDEVICE, std::string("HIP error: ") + hipGetErrorString(h.code) + " at " + h.what);
+    return pfail(p, HM_EDEVICE, hip_error_text(h));
+}
+
+// every ABI entry point's device work: the engine's device current, a HipErr recorded as the engine's error -> HM_EDEVICE
+template <class Body>
+auto guarded(hm_pileup* p, Body&& body) -> decltype(body()) {
+    return hip_guard(p->device, [p](const HipErr& h) { return pfail_hip(p, h); }, body);
 }
 
 inline int grid_for(int64_t n, int cap = 1 << 20) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + TPB - 1) / TPB, cap)); }
@@ -601,38 +581,22 @@ int hm_pileup_create(hm_pileup_t** out, int device) {
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
         return pfail(nullptr, HM_EDEVICE, "no HIP device: the pileup kernels need a gfx950 GPU (there is no CPU fallback)");
     if (device < 0 || device >= n) return pfail(nullptr, HM_EINVAL, "device ordinal out of range");
-    hm_pileup* p = new hm_pileup;
+    std::unique_ptr<hm_pileup> p(new hm_pileup);
     p->device = device;
-    try {
-        HIP_TRY(hipSetDevice(device));
+    const int rc = hip_guard(device, [](const HipErr& h) { return pfail_hip(nullptr, h); }, [&] {
         hipDeviceProp_t prop;
         HIP_TRY(hipGetDeviceProperties(&prop, device));
-        if (!strstr(prop.gcnArchName, "gfx950")) {
-            const std::string a = prop.gcnArchName;
-            delete p;
-            return pfail(nullptr, HM_EDEVICE, "device is " + a + ", this library holds gfx950 code only");
-        }
-        HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-    } catch (const HipErr& h) {
-        const int rc = pfail_hip(nullptr, h);
-        delete p;
-        return rc;
-    }
-    *out = p;
+        if (!strstr(prop.gcnArchName, "gfx950"))
+            return pfail(nullptr, HM_EDEVICE, "device is " + std::string(prop.gcnArchName) + ", this library holds gfx950 code only");
+        HIP_TRY(hipStreamCreateWithFlags(&p->stream.h, hipStreamNonBlocking));
+        return HM_OK;
+    });
+    if (rc < 0) return rc;
+    *out = p.release();
     return HM_OK;
 }
 
-void hm_pileup_destroy(hm_pileup_t* p) {
-    if (!p) return;
-    (void)hipSetDevice(p->device);
-    if (p->stream) (void)hipStreamSynchronize(p->stream);
-    for (DevBuf* b : {&p->d_ref, &p->d_pcov, &p->d_ncov, &p->d_key, &p->d_slab, &p->d_reads, &p->d_runs, &p->d_col0,
-                      &p->d_mods, &p->d_plane, &p->d_matches, &p->d_bins, &p->d_counter, &p->d_recs, &p->d_blk,
-                      &p->d_offs, &p->d_loci, &p->d_asm, &p->d_lfact, &p->d_hp_pcov[0], &p->d_hp_pcov[1], &p->d_hp_ncov[0], &p->d_hp_ncov[1]})
-        b->release();
-    if (p->stream) (void)hipStreamDestroy(p->stream);
-    delete p;
-}
+void hm_pileup_destroy(hm_pileup_t* p) { delete p; }  // ~hm_pileup: device current, stream drained, then the members
 
 const char* hm_pileup_last_error(const hm_pileup_t* p) { return p ? p->err.c_str() : g_pileup_create_error.c_str(); }
 
@@ -685,15 +649,14 @@ int hm_pileup_set_reference(hm_pileup_t* p, int32_t n_seqs, const int64_t* seq_l
     }
     const int64_t total = p->seq_off.back();
     if (total >= (int64_t(1) << 40)) return pfail(p, HM_EINVAL, "reference longer than 2^40 bases");
-    try {
-        HIP_TRY(hipSetDevice(p->device));
-        p->d_ref.reserve((size_t)total + 4, 0, nullptr, true);
+    return guarded(p, [&] {
+        p->d_ref.reserve((size_t)total + 4);
         HIP_TRY(hipMemcpyAsync(p->d_ref.p, bases, (size_t)total, hipMemcpyHostToDevice, p->stream));
         if (p->own_planes) {
             const size_t bytes = (size_t)std::max<int64_t>(total, 1) * 4;
-            p->d_pcov.reserve(bytes, 0, nullptr, true);
-            p->d_ncov.reserve(bytes, 0, nullptr, true);
-            p->d_key.reserve(bytes, 0, nullptr, true);
+            p->d_pcov.reserve(bytes);
+            p->d_ncov.reserve(bytes);
+            p->d_key.reserve(bytes);
             p->pcov = p->d_pcov.as<int32_t>();
             p->ncov = p->d_ncov.as<int32_t>();
             p->key = p->d_key.as<uint32_t>();
@@ -705,8 +668,8 @@ int hm_pileup_set_reference(hm_pileup_t* p, int32_t n_seqs, const int64_t* seq_l
             const size_t bytes = (size_t)std::max<int64_t>(total, 1) * 4;
             for (int k = 0; k < 2; ++k) {
                 if (p->hp_pcov[k]) continue;  // caller-owned (hm_pileup_use_partition_planes)
-                p->d_hp_pcov[k].reserve(bytes, 0, nullptr, true);
-                p->d_hp_ncov[k].reserve(bytes, 0, nullptr, true);
+                p->d_hp_pcov[k].reserve(bytes);
+                p->d_hp_ncov[k].reserve(bytes);
                 p->hp_pcov[k] = p->d_hp_pcov[k].as<int32_t>();
                 p->hp_ncov[k] = p->d_hp_ncov[k].as<int32_t>();
                 HIP_TRY(hipMemsetAsync(p->hp_pcov[k], 0, bytes, p->stream));
@@ -714,10 +677,8 @@ int hm_pileup_set_reference(hm_pileup_t* p, int32_t n_seqs, const int64_t* seq_l
             }
         }
         HIP_TRY(hipStreamSynchronize(p->stream));
-    } catch (const HipErr& h) {
-        return pfail_hip(p, h);
-    }
-    return HM_OK;
+        return HM_OK;
+    });
 }
 
 int hm_pileup_planes(hm_pileup_t* p, void** pcov, void** ncov, void** key, int64_t* n_loci) {
@@ -845,8 +806,7 @@ int hm_pileup_submit_read_hp(hm_pileup_t* p, uint32_t order, int32_t flag, int32
 int hm_pileup_run(hm_pileup_t* p) {
     if (!p) return HM_EINVAL;
     if (p->reads.empty()) return HM_OK;
-    try {
-        HIP_TRY(hipSetDevice(p->device));
+    return guarded(p, [&] {
         ensure_bins(p);
         hipStream_t st = p->stream;
         const int n_reads = (int)p->reads.size(), n_runs = (int)p->runs.size();
@@ -894,39 +854,33 @@ int hm_pileup_run(hm_pileup_t* p) {
         HIP_TRY(hipMemcpyAsync(&n, p->d_counter.p, sizeof n, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         p->n_recs = (int64_t)n;
-    } catch (const HipErr& h) {
-        return pfail_hip(p, h);
-    }
-    clear_batch(p);
-    return HM_OK;
+        clear_batch(p);
+        return HM_OK;
+    });
 }
 
 int64_t hm_pileup_num_records(hm_pileup_t* p) { return p ? p->n_recs : HM_EINVAL; }
 
 int hm_pileup_histograms(hm_pileup_t* p, uint64_t* bins768) {
     if (!p || !bins768) return HM_EINVAL;
-    try {
-        HIP_TRY(hipSetDevice(p->device));
+    return guarded(p, [&] {
         ensure_bins(p);
         HIP_TRY(hipMemcpyAsync(bins768, p->d_bins.p, 768 * sizeof(uint64_t), hipMemcpyDeviceToHost, p->stream));
         HIP_TRY(hipStreamSynchronize(p->stream));
-    } catch (const HipErr& h) {
-        return pfail_hip(p, h);
-    }
-    return HM_OK;
+        return HM_OK;
+    });
 }
 
 int64_t hm_pileup_fetch_records(hm_pileup_t* p, int64_t* gpos, uint8_t* prob, uint8_t* motif, uint32_t* order, int64_t cap) {
     if (!p) return HM_EINVAL;
     if (cap < p->n_recs) return p->n_recs;
     std::vector<PRec> h((size_t)p->n_recs);
-    try {
-        HIP_TRY(hipSetDevice(p->device));
+    const int rc = guarded(p, [&] {
         if (p->n_recs) HIP_TRY(hipMemcpyAsync(h.data(), p->d_recs.p, sizeof(PRec) * h.size(), hipMemcpyDeviceToHost, p->stream));
         HIP_TRY(hipStreamSynchronize(p->stream));
-    } catch (const HipErr& e) {
-        return pfail_hip(p, e);
-    }
+        return HM_OK;
+    });
+    if (rc < 0) return rc;
     for (size_t i = 0; i < h.size(); ++i) {
         if (gpos) gpos[i] = (int64_t)h[i].glo | ((int64_t)(h[i].hi & 255u) << 32);
         if (prob) prob[i] = (uint8_t)(h[i].hi >> 8);
@@ -940,8 +894,7 @@ int hm_pileup_label_histograms(hm_pileup_t* p, const int8_t* labels, int64_t n_l
     if (!p || !labels || !bins1536) return HM_EINVAL;
     if (p->seq_off.empty()) return pfail(p, HM_ESTATE, "hm_pileup_label_histograms before hm_pileup_set_reference");
     if (n_labels != p->seq_off.back()) return pfail(p, HM_EINVAL, "hm_pileup_label_histograms: one label per reference base expected");
-    try {
-        HIP_TRY(hipSetDevice(p->device));
+    return guarded(p, [&] {
         p->d_labels.reserve((size_t)n_labels + 1);
         p->d_lbins.reserve(1536 * sizeof(unsigned long long));
         HIP_TRY(hipMemcpyAsync(p->d_labels.p, labels, (size_t)n_labels, hipMemcpyHostToDevice, p->stream));
@@ -953,10 +906,8 @@ int hm_pileup_label_histograms(hm_pileup_t* p, const int8_t* labels, int64_t n_l
         }
         HIP_TRY(hipMemcpyAsync(bins1536, p->d_lbins.p, 1536 * sizeof(uint64_t), hipMemcpyDeviceToHost, p->stream));
         HIP_TRY(hipStreamSynchronize(p->stream));
-    } catch (const HipErr& h) {
-        return pfail_hip(p, h);
-    }
-    return HM_OK;
+        return HM_OK;
+    });
 }
 
 int hm_pileup_count(hm_pileup_t* p, const uint8_t thr[3]) {
@@ -964,8 +915,7 @@ int hm_pileup_count(hm_pileup_t* p, const uint8_t thr[3]) {
     if (!p->pcov) return pfail(p, HM_ESTATE, "hm_pileup_count before hm_pileup_set_reference / hm_pileup_use_planes");
     if (p->partitions == 2 && (!p->hp_pcov[0] || !p->hp_pcov[1]))
         return pfail(p, HM_ESTATE, "hm_pileup_count without partition planes (hm_pileup_set_reference / hm_pileup_use_partition_planes)");
-    try {
-        HIP_TRY(hipSetDevice(p->device));
+    return guarded(p, [&] {
         ensure_bins(p);
         if (p->n_recs) {
             const uint32_t packed = thr[0] | ((uint32_t)thr[1] << 8) | ((uint32_t)thr[2] << 16);
@@ -981,10 +931,8 @@ int hm_pileup_count(hm_pileup_t* p, const uint8_t thr[3]) {
         HIP_TRY(hipMemsetAsync(p->d_counter.p, 0, sizeof(unsigned long long), p->stream));
         HIP_TRY(hipStreamSynchronize(p->stream));
         p->n_recs = 0;
-    } catch (const HipErr& h) {
-        return pfail_hip(p, h);
-    }
-    return HM_OK;
+        return HM_OK;
+    });
 }
 
 int64_t hm_pileup_fetch_loci(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t plane_base,
@@ -998,8 +946,7 @@ int64_t hm_pileup_fetch_loci(hm_pileup_t* p, const void* pcov, const void* ncov,
     if (hi == lo) return 0;
     const int64_t nblk = (hi - lo + LOCI_PER_BLOCK - 1) / LOCI_PER_BLOCK;
     if (nblk >= (int64_t(1) << 31)) return pfail(p, HM_EINVAL, "range too large: fetch per sequence");
-    try {
-        HIP_TRY(hipSetDevice(p->device));
+    return guarded(p, [&] {
         hipStream_t st = p->stream;
         p->d_blk.reserve(4 * (size_t)nblk);
         p->d_offs.reserve(8 * ((size_t)nblk + 1));
@@ -1016,9 +963,7 @@ int64_t hm_pileup_fetch_loci(hm_pileup_t* p, const void* pcov, const void* ncov,
         HIP_TRY(hipMemcpyAsync(out, p->d_loci.p, sizeof(hm_locus_t) * (size_t)total, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         return total;
-    } catch (const HipErr& h) {
-        return pfail_hip(p, h);
-    }
+    });
 }
 
 int64_t hm_pileup_fetch_asm(hm_pileup_t* p, const void* pcov1, const void* ncov1, const void* pcov2, const void* ncov2,
@@ -1042,8 +987,7 @@ int64_t hm_pileup_fetch_asm(hm_pileup_t* p, const void* pcov1, const void* ncov1
     if (hi == lo) return 0;
     const int64_t nblk = (hi - lo + LOCI_PER_BLOCK - 1) / LOCI_PER_BLOCK;
     if (nblk >= (int64_t(1) << 31)) return pfail(p, HM_EINVAL, "range too large: fetch per sequence");
-    try {
-        HIP_TRY(hipSetDevice(p->device));
+    return guarded(p, [&] {
         hipStream_t st = p->stream;
         p->d_blk.reserve(4 * (size_t)nblk);
         p->d_offs.reserve(8 * ((size_t)nblk + 1));
@@ -1056,7 +1000,7 @@ int64_t hm_pileup_fetch_asm(hm_pileup_t* p, const void* pcov1, const void* ncov1
         if (!p->d_lfact.p) {  // log n!, n < LFACT_N: once per engine
             std::vector<double> t((size_t)LFACT_N);
             for (int k = 0; k < LFACT_N; ++k) t[(size_t)k] = std::lgamma((double)k + 1.0);
-            p->d_lfact.reserve(sizeof(double) * t.size(), 0, nullptr, true);
+            p->d_lfact.reserve(sizeof(double) * t.size());
             HIP_TRY(hipMemcpyAsync(p->d_lfact.p, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice, st));
             HIP_TRY(hipStreamSynchronize(st));
         }
@@ -1069,9 +1013,7 @@ int64_t hm_pileup_fetch_asm(hm_pileup_t* p, const void* pcov1, const void* ncov1
         HIP_TRY(hipMemcpyAsync(out, p->d_asm.p, sizeof(hm_asm_t) * (size_t)total, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         return total;
-    } catch (const HipErr& h) {
-        return pfail_hip(p, h);
-    }
+    });
 }
 
 }  // extern "C"

@@ -608,6 +608,54 @@ def test_bulk_submit_matches_read_by_read(mc):
         assert got.tobytes() == want.tobytes()
 
 
+def test_the_three_staging_entry_points_are_one_path(mc):
+    """hm_submit_read, hm_batch_submit_read and hm_batch_submit_reads check and place a read with the same code: one list with a short
+    read, a read without one kinetics tag, B:C and B:S arrays and lengths that are no multiple of 4 (total_bases is padded per read) is
+    accepted, laid out and called identically through all three; a block with a bad read is refused whole, with the codes of the ABI."""
+    import ctypes as C
+    from hifimeth_amd.caller import ReadBlock
+    rng = np.random.default_rng(41)
+
+    def rd(L, wide=False):
+        return read_from_ascii("".join("ACGT"[i] for i in rng.choice(4, L)).encode(), *_kin(L, rng, wide=wide))
+
+    missing = rd(1200)
+    missing.ri = None
+    reads = [rd(400), missing, rd(1500), rd(1500, wide=True), rd(1001), rd(1003), rd(2600)]
+    taken = [1500, 1500, 1001, 1003, 2600]
+    mc.clear()
+    n_legacy = mc.submit_all(reads)
+    mc.upload()
+    mc.run()
+    want = mc.fetch().copy()
+    mc.clear()
+    assert n_legacy == len(taken) and len(want) > 100
+
+    def refused(b, field, value):
+        """the raw return code of a block whose last read is ill-formed"""
+        blk = ReadBlock(reads + [rd(1200)])
+        blk.desc[field][-1] = value
+        return mc._L.hm_batch_submit_reads(b._h, blk.desc.ctypes.data_as(C.c_void_p), len(blk.desc), 2, None)
+
+    staged = []
+    for bulk in (False, True):
+        b = mc.begin_batch()
+        n = b.submit_block(ReadBlock(reads), 3) if bulk else b.submit_all(reads)
+        staged.append(b.staged_bases())
+        assert n == n_legacy
+        assert refused(b, "width", [1, 1, 3, 1]) == -1 and b.staged_bases() == staged[-1]  # HM_EINVAL, and nothing of the block was staged
+        assert refused(b, "l_qseq", -5) == -1 and b.staged_bases() == staged[-1]
+        args = list(mc._read_args(reads[2])[0])
+        for w in (3, 257):  # the read-by-read form takes its widths as int
+            args[4] = w
+            assert mc._L.hm_batch_submit_read(b._h, 99, *args) == -1 and b.staged_bases() == staged[-1]
+        b.enqueue()
+        got = b.wait().copy()
+        b.release()
+        assert got.tobytes() == want.tobytes()
+    assert staged[0] == staged[1] == sum((L + 3) // 4 * 4 for L in taken)
+
+
 def test_batches_staged_from_several_threads(mc):
     """Different batches may be staged by different host threads (the reference's workers pull from a shared queue,
     sam_batch.hpp:38-54); an empty batch and a batch of skipped reads go through the pipeline too."""
@@ -900,3 +948,30 @@ def test_two_engines_on_one_device_fit_at_the_default_group_size():
         assert (1 << 20) <= t["group_bases"] <= (16 << 20) and t["group_bases"] % (1 << 20) == 0, t["group_bases"]
         assert 0 < t["group_bytes"] <= free0 // 4 + (64 << 20), (t["group_bytes"], free0)
         assert t["group_bases"] * 5800 <= free0 // 4 + (1 << 30), (t["group_bases"], free0)
+
+
+@pytest.mark.gpu
+def test_engines_give_their_memory_back():
+    """Eight engines made, used (the synchronous calls and one batch of the pipeline, so that a second slot exists) and closed, twice
+    over: the device's free memory must not go down round after round.  One engine that kept its buffers would hold its group_bytes, so
+    a round may lose less than half of that -- a leak shows in every round, another tenant's allocation on a shared card does not."""
+    import torch
+    from hifimeth_amd import MethylationCaller
+    reads = synth_reads(12, seed=93, median_len=5000, sigma=0.4)
+    lost, group_bytes = [], None
+    for _ in range(2):
+        free0 = torch.cuda.mem_get_info(0)[0]
+        for _ in range(8):
+            mc = MethylationCaller(device=0)
+            n = len(mc.call(reads))
+            b = mc.begin_batch()
+            b.submit_all(reads)
+            b.enqueue()
+            assert len(b.wait()) == n > 1000
+            b.release()
+            if group_bytes is None:
+                group_bytes = mc.timing()["group_bytes"]
+            mc.close()
+        lost.append(free0 - torch.cuda.mem_get_info(0)[0])
+    print(f"free memory lost per round of 8 engines: {lost}, group_bytes {group_bytes}")
+    assert group_bytes > 0 and min(lost) < group_bytes // 2, (lost, group_bytes)
