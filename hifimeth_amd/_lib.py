@@ -115,6 +115,7 @@ def lib():
         "hm_pileup_planes": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]),
         "hm_pileup_submit_read": (C.c_int, [vp, C.c_uint32, i32, i32, i64, i32, i32, vp, i32, vp, i64, vp]),
         "hm_pileup_submit_read_hp": (C.c_int, [vp, C.c_uint32, i32, i32, i64, i32, i32, vp, i32, vp, i64, vp, i32]),
+        "hm_pileup_submit_read_calls": (C.c_int, [vp, C.c_uint32, i32, i32, i64, i32, i32, vp, i32, vp, i64, vp, i32]),
         "hm_pileup_use_partition_planes": (C.c_int, [vp, i32, vp, vp]),
         "hm_pileup_partition_planes": (C.c_int, [vp, i32, C.POINTER(vp), C.POINTER(vp)]),
         "hm_pileup_run": (C.c_int, [vp]),

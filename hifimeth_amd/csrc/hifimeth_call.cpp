@@ -105,22 +105,6 @@ void usage() {
             kName, kName, kName);
 }
 
-bool parse_ctx(const char* arg, int& mask) {
-    mask = 0;
-    std::string s(arg), tok;
-    for (size_t i = 0; i <= s.size(); ++i) {
-        if (i == s.size() || s[i] == ',') {
-            for (auto& c : tok) c = (char)toupper(c);
-            if (tok == "CPG") mask |= 1;
-            else if (tok == "CHG") mask |= 2;
-            else if (tok == "CHH") mask |= 4;
-            else return false;
-            tok.clear();
-        } else tok += s[i];
-    }
-    return mask != 0;
-}
-
 // host threads this process may really use: the affinity mask, capped by the cgroup CPU quota (a container that is granted
 // 16 of a node's 256 hardware threads must not start 256 workers); the reference's default is the physical core count
 // (mod_options.cpp:73,129-131)
@@ -136,15 +120,6 @@ int default_threads() {
         fclose(f);
     }
     return n;
-}
-
-std::string exe_dir() {
-    char buf[4096];
-    ssize_t n = readlink("/proc/self/exe", buf, sizeof buf - 1);
-    if (n <= 0) return ".";
-    buf[n] = 0;
-    std::string p(buf);
-    return p.substr(0, p.find_last_of('/'));
 }
 
 bool parse(int argc, char** argv, Options& o) {

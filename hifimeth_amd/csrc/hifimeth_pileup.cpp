@@ -10,6 +10,9 @@
 // -A (ours, with -H): also <prefix>.asm.<ctx>.bed, one row per locus where each haplotype has at least -a (default 5) counted
 // calls:  chrom <tab> soff <tab> soff+1 <tab> diff <tab> pvalue <tab> pcov1 <tab> ncov1 <tab> pcov2 <tab> ncov2
 // (difference of the two methylation percentages, two-sided Fisher exact test; both computed on the GPU).
+// -K (ours): the input is an aligned BAM that still carries the kinetics tags (pbmm2 keeps fi / fp / ri / rp): the reads are called
+// on the fly by the call engine and their calls go straight to the pileup engine (hm_pileup_submit_read_calls) -- the files
+// `call` followed by `pileup` writes, without the mod-BAM between the two.
 #include <strings.h>
 #include <zlib.h>
 
@@ -66,6 +69,14 @@ struct PileupOptions {
     bool asm_test = false;    // -A: per-locus haplotype difference + Fisher exact test -> <prefix>.asm.*
     int asm_min_cov = 5;      // -a: minimum pcov + ncov of each haplotype for a locus to be tested
     bool asm_min_cov_given = false;
+    // -K: call on the fly; the options below are `call`'s (hifimeth_call.cpp), same meaning and defaults
+    bool kinetics = false;
+    bool call_option_given = false;  // any of -m -c -l -p -T: a usage error without -K
+    std::string model_dir;           // -m, default <exe_dir>/../weights
+    int ctx_mask = 7;                // -c
+    int min_read_size = 1000;        // -l
+    int precision = 1;               // -p
+    int trunk = -1;                  // -T; -1: the call engine decides per context from its first batch
     std::string ref, bam, prefix;
 };
 
@@ -83,8 +94,18 @@ void pileup_usage(const char* exe) {
             "    <prefix>.hap1.<ctx>.cov.bed / <prefix>.hap2.<ctx>.cov.bed (same thresholds as the combined files)\n"
             "  -A\n    With -H: test every locus where both haplotypes are covered for a difference between them and write\n"
             "    <prefix>.asm.<ctx>.bed: chrom, start, end, hap1 %% - hap2 %%, two-sided Fisher exact p-value, pcov1, ncov1, pcov2, ncov2\n"
-            "  -a <int>\n    With -A: minimum coverage (pcov + ncov) of each haplotype at a tested locus\n    Default: 5\n",
-            exe);
+            "  -a <int>\n    With -A: minimum coverage (pcov + ncov) of each haplotype at a tested locus\n    Default: 5\n"
+            "  -K\n    The input is an aligned BAM that carries the kinetics tags fi / fp / ri / rp instead of MM / ML: call 5mC on the\n"
+            "    fly and pile the calls up directly.  For equal -c -l -p -T -q -f the output files are byte-identical to those of\n"
+            "    `%s call` on that BAM followed by `%s pileup` on its output; no mod-BAM is written.  (Give -T explicitly\n"
+            "    for that comparison: its default is chosen per run from the data and moves p by up to 1e-5.)  -b is not used:\n"
+            "    records are batched by bases.  Only with -K, with the meaning and defaults of `call`:\n"
+            "  -m <dir>\n    Model directory holding {CpG,CHG,CHH}.onnx or .hmw\n    Default: <exe_dir>/../weights\n"
+            "  -c <list>\n    Contexts to call: cpg,chg,chh\n    Default: all\n"
+            "  -l <int>\n    Minimum read length to call\n    Default: 1000\n"
+            "  -p <0|1|2>\n    Arithmetic of the CNN (see `call`)\n    Default: 1\n"
+            "  -T <0|1>\n    conv1..conv4 once per site (0) / once per read position (1)\n    Default: per context, from the first batch\n",
+            exe, exe, exe);
 }
 
 // s_bam_is_mapped_and_sorted (pileup.cpp:438-459)
@@ -762,6 +783,130 @@ bool write_asm(hm_pileup_t* pe, const Fasta& fa, int min_cov, FILE* out[3]) {
 }
 }  // namespace
 
+namespace {
+// -K: the record loop of the fused path.  Batches of at most kSlabBases bases (the slab of `call`) go through the call engine's
+// batch pipeline on two slots: while this thread waits for batch k's calls, hands them to the pileup engine read by read and
+// runs the projection, a producer thread inflates batch k+1, stages its kinetics and queues it on the device.  What `call`
+// followed by `pileup` does with a record decides what happens here: an accepted read's calls replace whatever MM / ML it
+// carried; a read the engine passes through (shorter than -l, a kinetics tag missing or of the wrong length) leaves `call`
+// with its MM / ML stripped (apply_calls), so it contributes nothing; unmapped records are not called at all.
+// The call engine is created here, after the pileup engine holds its reference and planes: it sizes its read groups from the
+// device memory that is still free.  false (message printed) on any error; t = {read, stage + queue, hand-off, wait + GPU} seconds.
+bool fused_record_loop(const PileupOptions& o, BgzfReader& in, hm_pileup_t* pe, const std::function<int(const BamRecord&)>& sid_of,
+                       uint64_t& n_records, double t[4]) {
+    constexpr int64_t kSlabBases = int64_t(6) << 20;
+    using clk = std::chrono::steady_clock;
+    auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+    if (hm_abi_version() != HM_ABI_VERSION) { fprintf(stderr, "ERROR: libhifimeth_hip.so was built from another include/hifimeth_hip.h\n"); return false; }
+    hm_engine_t* eng = nullptr;
+    if (hm_create(&eng, o.model_dir.c_str(), o.ctx_mask, o.device) < 0) { fprintf(stderr, "ERROR: call engine: %s\n", hm_last_error(nullptr)); return false; }
+    hm_set_option(eng, "min_read_size", o.min_read_size);
+    hm_set_option(eng, "precision", o.precision);
+    hm_set_option(eng, "slots", 2);
+    if (o.trunk >= 0) hm_set_option(eng, "trunk_mask", o.trunk ? o.ctx_mask : 0);  // as `call -T`
+
+    struct Batch {
+        std::vector<BamRecord> recs;
+        std::vector<hm_read_t> reads;   // the mapped records, read_id = index in recs
+        std::vector<uint8_t> accepted;  // per entry of reads
+        hm_batch_t* slot = nullptr;     // queued on the device; NULL when the batch has no mapped record
+        bool more = true;
+        std::string err;
+        double t_read = 0, t_stage = 0;
+    };
+    Batch bb[2];
+    auto produce = [&](Batch& b) {
+        const auto t0 = clk::now();
+        b.recs.clear();
+        b.reads.clear();
+        b.err.clear();
+        b.slot = nullptr;
+        for (int64_t bases = 0; bases < kSlabBases;) {
+            BamRecord r;
+            if (!(b.more = read_record(in, r, b.err))) break;
+            bases += r.l_qseq();
+            b.recs.push_back(std::move(r));
+        }
+        const auto t1 = clk::now();
+        b.t_read = secs(t0, t1);
+        if (!b.err.empty()) { b.err = "Could not read BAM record: " + b.err; return; }
+        for (size_t k = 0; k < b.recs.size(); ++k) {
+            const BamRecord& r = b.recs[k];
+            if (r.flag() & 4) continue;
+            const KineticsView kv = kinetics_of(r);
+            hm_read_t d{};
+            d.read_id = (int32_t)k;
+            d.l_qseq = r.l_qseq();
+            d.flag = r.flag();
+            d.seq4 = r.seq4();
+            for (int j = 0; j < 4; ++j) { d.kin[j] = kv.arr[j]; d.width[j] = (uint8_t)kv.width[j]; }
+            b.reads.push_back(d);
+        }
+        if (b.reads.empty()) return;
+        b.accepted.assign(b.reads.size(), 0);
+        b.slot = hm_batch_begin(eng);
+        if (!b.slot || hm_batch_submit_reads(b.slot, b.reads.data(), (int64_t)b.reads.size(), o.threads, b.accepted.data()) < 0 ||
+            hm_batch_enqueue(b.slot) < 0)
+            b.err = std::string("call engine: ") + hm_last_error(eng);
+        b.t_stage = secs(t1, clk::now());
+    };
+    std::thread producer;
+    auto finish = [&](bool ok) {  // every exit: no thread left, no slot held, then the engine
+        if (producer.joinable()) producer.join();
+        for (Batch& b : bb)
+            if (b.slot) hm_batch_release(b.slot);
+        hm_destroy(eng);
+        return ok;
+    };
+    std::vector<uint32_t> cig;
+    int cur = 0;
+    produce(bb[0]);
+    while (true) {
+        Batch& b = bb[cur];
+        t[0] += b.t_read;
+        t[1] += b.t_stage;
+        if (!b.err.empty()) { fprintf(stderr, "ERROR: %s\n", b.err.c_str()); return finish(false); }
+        if (b.more) producer = std::thread(produce, std::ref(bb[cur ^ 1]));
+        const auto t2 = clk::now();
+        const hm_call_t* calls = nullptr;
+        const int64_t got = b.slot ? hm_batch_wait(b.slot, &calls) : 0;
+        if (got < 0) { fprintf(stderr, "ERROR: call engine: %s\n", hm_last_error(eng)); return finish(false); }
+        const auto t3 = clk::now();
+        int64_t ci = 0;
+        size_t ri = 0;
+        for (size_t k = 0; k < b.recs.size(); ++k) {
+            const BamRecord& r = b.recs[k];
+            const uint64_t order = n_records++;
+            if (r.flag() & 4) continue;
+            const bool accepted = b.accepted[ri++] != 0;
+            const int64_t c0 = ci;  // calls come grouped by read, in submission order
+            while (ci < got && calls[ci].read_id == (int32_t)k) ++ci;
+            if (!accepted || ci == c0) continue;
+            const int sid = sid_of(r);
+            if (sid < 0) return finish(false);
+            real_cigar(r, cig);
+            const int rc = hm_pileup_submit_read_calls(pe, (uint32_t)order, r.flag(), sid, r.pos(), r.mapq(), r.l_qseq(), r.seq4(),
+                                                       (int32_t)cig.size(), cig.data(), ci - c0, calls + c0, o.haplotypes ? haplotype_of(r) : 0);
+            if (rc < 0) {
+                fprintf(stderr, "ERROR: read %s: %s\n", reinterpret_cast<const char*>(r.data.data() + 32), hm_pileup_last_error(pe));
+                return finish(false);
+            }
+        }
+        if (b.slot) hm_batch_release(b.slot);  // the calls are staged in the pileup engine: the slot can take batch k+2
+        b.slot = nullptr;
+        const auto t4 = clk::now();
+        const int rrc = hm_pileup_run(pe);
+        t[2] += secs(t3, t4);
+        t[3] += secs(t2, t3) + secs(t4, clk::now());
+        if (producer.joinable()) producer.join();
+        if (rrc != HM_OK) { fprintf(stderr, "ERROR: projection: %s\n", hm_pileup_last_error(pe)); return finish(false); }
+        if (!b.more) break;
+        cur ^= 1;
+    }
+    return finish(true);
+}
+}  // namespace
+
 int cmd_pileup(int argc, char** argv) {
     PileupOptions o;
     int i = 2;
@@ -771,6 +916,7 @@ int cmd_pileup(int argc, char** argv) {
         if (a.size() < 2 || a[0] != '-') break;
         if (a == "-H") { o.haplotypes = true; continue; }  // a flag: takes no value
         if (a == "-A") { o.asm_test = true; continue; }
+        if (a == "-K") { o.kinetics = true; continue; }
         if (i + 1 >= argc) { pileup_usage(argv[0]); return EXIT_FAILURE; }
         if (a == "-q") o.min_mapq = atoi(argv[++i]);
         else if (a == "-f") o.min_pi = atof(argv[++i]);
@@ -778,6 +924,15 @@ int cmd_pileup(int argc, char** argv) {
         else if (a == "-d") o.device = atoi(argv[++i]);
         else if (a == "-b") o.read_batch = std::max(1, atoi(argv[++i]));
         else if (a == "-a") { o.asm_min_cov = atoi(argv[++i]); o.asm_min_cov_given = true; }
+        else if (a == "-m" || a == "-c" || a == "-l" || a == "-p" || a == "-T") {
+            o.call_option_given = true;
+            const char* v = argv[++i];
+            if (a == "-m") o.model_dir = v;
+            else if (a == "-l") o.min_read_size = atoi(v);
+            else if (a == "-p") o.precision = atoi(v);
+            else if (a == "-T") o.trunk = atoi(v);
+            else if (!parse_ctx(v, o.ctx_mask)) { fprintf(stderr, "Illegal argument to option '-c'\n"); pileup_usage(argv[0]); return EXIT_FAILURE; }
+        }
         else { fprintf(stderr, "ERROR: unrecognised option %s", a.c_str()); pileup_usage(argv[0]); return EXIT_FAILURE; }
     }
     if (argc - i != 3) { pileup_usage(argv[0]); return EXIT_FAILURE; }
@@ -785,6 +940,12 @@ int cmd_pileup(int argc, char** argv) {
                           : o.asm_min_cov_given && !o.asm_test ? "-a needs -A"
                           : o.asm_min_cov < 1 ? "-a must be >= 1" : nullptr;
     if (bad_asm) { fprintf(stderr, "ERROR: %s\n", bad_asm); pileup_usage(argv[0]); return EXIT_FAILURE; }
+    const char* bad_call = o.call_option_given && !o.kinetics ? "-m, -c, -l, -p and -T need -K (they configure the on-the-fly caller)"
+                           : o.min_read_size < 0 ? "-l must be >= 0"
+                           : o.precision < 0 || o.precision > 2 ? "-p must be 0, 1 or 2"
+                           : o.call_option_given && (o.trunk < -1 || o.trunk > 1) ? "-T must be 0 or 1" : nullptr;
+    if (bad_call) { fprintf(stderr, "ERROR: %s\n", bad_call); pileup_usage(argv[0]); return EXIT_FAILURE; }
+    if (o.kinetics && o.model_dir.empty()) o.model_dir = exe_dir() + "/../weights";
     o.ref = argv[i];
     o.bam = argv[i + 1];
     o.prefix = argv[i + 2];
@@ -793,6 +954,10 @@ int cmd_pileup(int argc, char** argv) {
             o.min_mapq, o.min_pi, o.threads, o.ref.c_str(), o.bam.c_str(), o.prefix.c_str());
     if (o.haplotypes) fprintf(stderr, "haplotypes: HP 1 / 2 -> %s.hap1.* / %s.hap2.*\n", o.prefix.c_str(), o.prefix.c_str());
     if (o.asm_test) fprintf(stderr, "asm: min haplotype coverage %d -> %s.asm.*\n", o.asm_min_cov, o.prefix.c_str());
+    if (o.kinetics)
+        fprintf(stderr, "kinetics: called on the fly (models %s, contexts%s%s%s, min read length %d, precision %d, trunk %s)\n", o.model_dir.c_str(),
+                o.ctx_mask & 1 ? " CpG" : "", o.ctx_mask & 2 ? " CHG" : "", o.ctx_mask & 4 ? " CHH" : "", o.min_read_size, o.precision,
+                o.trunk < 0 ? "auto" : o.trunk ? "1" : "0");
     fprintf(stderr, "\n\n");
 
     using clk = std::chrono::steady_clock;
@@ -823,82 +988,92 @@ int cmd_pileup(int argc, char** argv) {
     if (fa.names.empty()) { fprintf(stderr, "ERROR: no sequence in %s\n", o.ref.c_str()); hm_pileup_destroy(pe); return EXIT_FAILURE; }
     if (hm_pileup_set_reference(pe, (int32_t)fa.names.size(), fa.length.data(), fa.bases.data()) != HM_OK) return die("reference");
 
-    // Two batches in flight: a producer thread inflates + parses batch k+1 (parse_mods over `threads` workers) while
-    // this thread stages batch k and runs the GPU.
-    struct Batch {
-        std::vector<BamRecord> recs;
-        std::vector<std::vector<BaseMod>> mods;
-        std::vector<std::string> perr;
-        int n = 0;
-        bool more = true;
-        std::string err;
-        double t_read = 0, t_parse = 0;
-    };
-    Batch bb[2];
-    for (Batch& b : bb) {
-        b.recs.resize((size_t)o.read_batch);
-        b.mods.resize((size_t)o.read_batch);
-        b.perr.resize((size_t)o.read_batch);
-    }
-    auto produce = [&](Batch& b) {
-        auto t0 = clk::now();
-        b.n = 0;
-        b.err.clear();
-        while (b.n < o.read_batch && (b.more = read_record(in, b.recs[(size_t)b.n], b.err))) ++b.n;
-        auto t1 = clk::now();
-        parallel_run(b.n, o.threads, [&](int k) {
-            b.mods[(size_t)k].clear();
-            b.perr[(size_t)k].clear();
-            if (!parse_mods(b.recs[(size_t)k], b.mods[(size_t)k], b.perr[(size_t)k])) b.mods[(size_t)k].clear();
-        });
-        b.t_read = secs(t0, t1);
-        b.t_parse = secs(t1, clk::now());
+    // index of a mapped record's reference sequence in the FASTA; -1 (message printed) if the record has none or the name is unknown
+    auto sid_of = [&](const BamRecord& r) {
+        const int tid = r.ref_id();
+        if (tid < 0 || tid >= (int)hdr.refs.size()) { fprintf(stderr, "ERROR: mapped record without a reference id\n"); return -1; }
+        if (tid2sid[(size_t)tid] == -2) tid2sid[(size_t)tid] = fa.find(hdr.refs[(size_t)tid].first);
+        if (tid2sid[(size_t)tid] < 0) fprintf(stderr, "ERROR: Sequence name %s does not exist\n", hdr.refs[(size_t)tid].first.c_str());
+        return std::max(tid2sid[(size_t)tid], -1);
     };
     uint64_t n_records = 0;
-    int cur = 0;
-    produce(bb[0]);
-    std::vector<uint32_t> cig;
-    while (true) {
-        Batch& b = bb[cur];
-        t_read += b.t_read;
-        t_parse += b.t_parse;
-        if (!b.err.empty()) { fprintf(stderr, "ERROR: Could not read BAM record: %s\n", b.err.c_str()); hm_pileup_destroy(pe); return EXIT_FAILURE; }
-        std::thread producer;
-        if (b.more) producer = std::thread(produce, std::ref(bb[cur ^ 1]));
-        auto fail_out = [&]() { if (producer.joinable()) producer.join(); hm_pileup_destroy(pe); return EXIT_FAILURE; };
-        auto t2 = clk::now();
-        for (int k = 0; k < b.n; ++k) {
-            const BamRecord& r = b.recs[(size_t)k];
-            const uint64_t order = n_records++;
-            if (!b.perr[(size_t)k].empty()) {
-                fprintf(stderr, "ERROR at parsing read %s\n%s\n", reinterpret_cast<const char*>(r.data.data() + 32), b.perr[(size_t)k].c_str());
-                return fail_out();
-            }
-            if (b.mods[(size_t)k].empty() || (r.flag() & 4)) continue;
-            const int tid = r.ref_id();
-            if (tid < 0 || tid >= (int)hdr.refs.size()) { fprintf(stderr, "ERROR: mapped record without a reference id\n"); return fail_out(); }
-            if (tid2sid[(size_t)tid] == -2) tid2sid[(size_t)tid] = fa.find(hdr.refs[(size_t)tid].first);
-            if (tid2sid[(size_t)tid] < 0) {
-                fprintf(stderr, "ERROR: Sequence name %s does not exist\n", hdr.refs[(size_t)tid].first.c_str());
-                return fail_out();
-            }
-            real_cigar(r, cig);
-            const int rc = hm_pileup_submit_read_hp(pe, (uint32_t)order, r.flag(), tid2sid[(size_t)tid], r.pos(), r.mapq(), r.l_qseq(),
-                                                    r.seq4(), (int32_t)cig.size(), cig.data(), (int64_t)b.mods[(size_t)k].size(),
-                                                    b.mods[(size_t)k].data(), o.haplotypes ? haplotype_of(r) : 0);
-            if (rc < 0) {
-                fprintf(stderr, "ERROR: read %s: %s\n", reinterpret_cast<const char*>(r.data.data() + 32), hm_pileup_last_error(pe));
-                return fail_out();
-            }
+    if (o.kinetics) {
+        double t[4] = {0, 0, 0, 0};
+        const bool ok = fused_record_loop(o, in, pe, sid_of, n_records, t);
+        t_read = t[0]; t_parse = t[1]; t_submit = t[2]; t_gpu = t[3];
+        if (!ok) { hm_pileup_destroy(pe); return EXIT_FAILURE; }
+    } else {
+        // Two batches in flight: a producer thread inflates + parses batch k+1 (parse_mods over `threads` workers) while
+        // this thread stages batch k and runs the GPU.
+        struct Batch {
+            std::vector<BamRecord> recs;
+            std::vector<std::vector<BaseMod>> mods;
+            std::vector<std::string> perr;
+            int n = 0;
+            bool more = true;
+            std::string err;
+            double t_read = 0, t_parse = 0;
+        };
+        Batch bb[2];
+        for (Batch& b : bb) {
+            b.recs.resize((size_t)o.read_batch);
+            b.mods.resize((size_t)o.read_batch);
+            b.perr.resize((size_t)o.read_batch);
         }
-        auto t3 = clk::now();
-        t_submit += secs(t2, t3);
-        const int rrc = hm_pileup_run(pe);
-        t_gpu += secs(t3, clk::now());
-        if (producer.joinable()) producer.join();
-        if (rrc != HM_OK) return die("projection");
-        if (!b.more) break;
-        cur ^= 1;
+        auto produce = [&](Batch& b) {
+            auto t0 = clk::now();
+            b.n = 0;
+            b.err.clear();
+            while (b.n < o.read_batch && (b.more = read_record(in, b.recs[(size_t)b.n], b.err))) ++b.n;
+            auto t1 = clk::now();
+            parallel_run(b.n, o.threads, [&](int k) {
+                b.mods[(size_t)k].clear();
+                b.perr[(size_t)k].clear();
+                if (!parse_mods(b.recs[(size_t)k], b.mods[(size_t)k], b.perr[(size_t)k])) b.mods[(size_t)k].clear();
+            });
+            b.t_read = secs(t0, t1);
+            b.t_parse = secs(t1, clk::now());
+        };
+        int cur = 0;
+        produce(bb[0]);
+        std::vector<uint32_t> cig;
+        while (true) {
+            Batch& b = bb[cur];
+            t_read += b.t_read;
+            t_parse += b.t_parse;
+            if (!b.err.empty()) { fprintf(stderr, "ERROR: Could not read BAM record: %s\n", b.err.c_str()); hm_pileup_destroy(pe); return EXIT_FAILURE; }
+            std::thread producer;
+            if (b.more) producer = std::thread(produce, std::ref(bb[cur ^ 1]));
+            auto fail_out = [&]() { if (producer.joinable()) producer.join(); hm_pileup_destroy(pe); return EXIT_FAILURE; };
+            auto t2 = clk::now();
+            for (int k = 0; k < b.n; ++k) {
+                const BamRecord& r = b.recs[(size_t)k];
+                const uint64_t order = n_records++;
+                if (!b.perr[(size_t)k].empty()) {
+                    fprintf(stderr, "ERROR at parsing read %s\n%s\n", reinterpret_cast<const char*>(r.data.data() + 32), b.perr[(size_t)k].c_str());
+                    return fail_out();
+                }
+                if (b.mods[(size_t)k].empty() || (r.flag() & 4)) continue;
+                const int sid = sid_of(r);
+                if (sid < 0) return fail_out();
+                real_cigar(r, cig);
+                const int rc = hm_pileup_submit_read_hp(pe, (uint32_t)order, r.flag(), sid, r.pos(), r.mapq(), r.l_qseq(),
+                                                        r.seq4(), (int32_t)cig.size(), cig.data(), (int64_t)b.mods[(size_t)k].size(),
+                                                        b.mods[(size_t)k].data(), o.haplotypes ? haplotype_of(r) : 0);
+                if (rc < 0) {
+                    fprintf(stderr, "ERROR: read %s: %s\n", reinterpret_cast<const char*>(r.data.data() + 32), hm_pileup_last_error(pe));
+                    return fail_out();
+                }
+            }
+            auto t3 = clk::now();
+            t_submit += secs(t2, t3);
+            const int rrc = hm_pileup_run(pe);
+            t_gpu += secs(t3, clk::now());
+            if (producer.joinable()) producer.join();
+            if (rrc != HM_OK) return die("projection");
+            if (!b.more) break;
+            cur ^= 1;
+        }
     }
     const auto t_loop = clk::now();
 
@@ -955,8 +1130,10 @@ int cmd_pileup(int argc, char** argv) {
         if (!ok) return die("asm");
     }
     hm_pileup_destroy(pe);
-    fprintf(stderr, "## %llu records in %.2f s: [producer thread: BAM read %.2f s, MM/ML parse %.2f s] overlapped with "
-                    "[staging %.2f s, GPU projection %.2f s]; thresholds + count + BED %.2f s\n",
+    fprintf(stderr, o.kinetics ? "## %llu records in %.2f s: [producer thread: BAM read %.2f s, kinetics staging + queueing %.2f s] overlapped with "
+                                 "[call hand-off %.2f s, waiting for calls + GPU projection %.2f s]; thresholds + count + BED %.2f s\n"
+                               : "## %llu records in %.2f s: [producer thread: BAM read %.2f s, MM/ML parse %.2f s] overlapped with "
+                                 "[staging %.2f s, GPU projection %.2f s]; thresholds + count + BED %.2f s\n",
             (unsigned long long)n_records, secs(t_start, clk::now()), t_read, t_parse, t_submit, t_gpu, secs(t_loop, clk::now()));
     return 0;
 }

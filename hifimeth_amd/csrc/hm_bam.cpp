@@ -2,6 +2,7 @@
 #include "hm_bam.h"
 
 #include <dlfcn.h>
+#include <unistd.h>
 #include <zlib.h>
 
 #include <algorithm>
@@ -1059,6 +1060,32 @@ bool load_fasta(const std::string& path, Fasta& fa, std::string& err) {
     for (const std::string& nm : fa.names)
         if (!seen.insert(nm).second) { err = "Duplicate sequence name " + nm; return false; }
     return true;
+}
+
+// ---- command-line helpers shared by the front ends ---------------------------------------------------------------
+bool parse_ctx(const char* arg, int& mask) {
+    mask = 0;
+    std::string s(arg), tok;
+    for (size_t i = 0; i <= s.size(); ++i) {
+        if (i == s.size() || s[i] == ',') {
+            for (auto& c : tok) c = (char)toupper(c);
+            if (tok == "CPG") mask |= 1;
+            else if (tok == "CHG") mask |= 2;
+            else if (tok == "CHH") mask |= 4;
+            else return false;
+            tok.clear();
+        } else tok += s[i];
+    }
+    return mask != 0;
+}
+
+std::string exe_dir() {
+    char buf[4096];
+    ssize_t n = readlink("/proc/self/exe", buf, sizeof buf - 1);
+    if (n <= 0) return ".";
+    buf[n] = 0;
+    std::string p(buf);
+    return p.substr(0, p.find_last_of('/'));
 }
 
 }  // namespace hmbam

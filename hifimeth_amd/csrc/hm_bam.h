@@ -172,4 +172,10 @@ struct Fasta {
 };
 bool load_fasta(const std::string& path, Fasta& fa, std::string& err);
 
+// ---- command-line helpers shared by the front ends -----------------------------------------------------------------------
+// the reference's `-c cpg,chg,chh` (mod_options.cpp:61-134) -> context mask (bit c = context c); false on an unknown name
+bool parse_ctx(const char* arg, int& mask);
+// directory of the running program: the default model directory is <exe_dir>/../weights
+std::string exe_dir();
+
 }  // namespace hmbam

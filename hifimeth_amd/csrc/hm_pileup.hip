@@ -13,6 +13,8 @@
 // bytes.  This is byte / integer work bound by HBM traffic; no LDS tiling or MFMA applies.  Kernels:
 //   mods_kernel     thread per MM/ML entry : ML byte -> per-base plane (last entry wins, as the reference's
 //                   sequential overwrite), context histograms through LDS
+//   calls_kernel    thread per call        : the same for records submitted with their hm_call_t calls instead of parsed
+//                   MM/ML lists (hm_pileup_submit_read_calls, the fused `pileup -K` path)
 //   identity_kernel thread per column      : matches per read (only when -f > 0)
 //   project_kernel  thread per column      : motif tests, plane lookup, wave-aggregated append of 12-byte records
 //   count_kernel    thread per record      : atomic add into pcov / ncov, atomic max into the motif key
@@ -65,6 +67,13 @@ struct PMod {
     uint32_t bits;      // idx_in_read << 10 | is_m << 9 | unmod_is_CG << 8 | prob
 };
 
+struct PCall {          // 12 bytes: hm_call_t without p, read_id replaced by the index of the staged read
+    int32_t read;
+    int32_t qoff;
+    uint8_t strand, ctx, prob, reserved;
+};
+static_assert(sizeof(PCall) == 12 && sizeof(hm_call_t) == 16, "staged calls are the first 12 bytes of hm_call_t");
+
 struct PRec {           // 12 bytes
     uint32_t glo;       // gpos & 0xffffffff
     uint32_t hi;        // gpos >> 32 (8 bits) | prob << 8 | motif << 16 | hp << 18 (consumers mask motif with & 3)
@@ -91,6 +100,30 @@ __device__ __forceinline__ bool isH(char c) { return c == 'A' || c == 'C' || c =
 __device__ __forceinline__ bool isD(char c) { return c == 'A' || c == 'G' || c == 'T'; }
 
 // ---- mods: plane scatter + histograms (pileup.cpp:237-284) ---------------------------------------------------
+// One entry of a read (an MM/ML entry, or a call): a 5mC entry writes the per-base plane word project_kernel reads
+// (bit 0x100 + ML byte; `rank` above them orders the entries of one position: the largest wins); an entry on C / G of a
+// primary record counts in the workgroup's context histogram h[3][256], the context taken from the read's own bases.
+__device__ __forceinline__ void mod_entry(const PRead& r, int q, uint32_t prob, uint32_t rank, bool is_m, bool cg,
+                                          const uint8_t* __restrict__ slab, uint32_t* __restrict__ plane, uint32_t* h) {
+    if (is_m)  // code 'm': read_mods[qoff] = prob, later entries overwrite earlier ones
+        atomicMax(&plane[r.plane_off + q], (rank << 9) | 0x100u | prob);
+    if (r.primary && cg) {
+        const int L = r.l_qseq;
+        const char c0 = fwd_base(slab, r, q);
+        int ctx = -1;
+        if (c0 == 'C') {
+            const char c1 = q + 1 < L ? fwd_base(slab, r, q + 1) : 'N';
+            const char c2 = q + 2 < L ? fwd_base(slab, r, q + 2) : 'N';
+            if (q + 1 < L && c1 == 'G') ctx = 0;
+            else if (q + 2 < L && isH(c1) && c2 == 'G') ctx = 1;
+            else if (q + 2 < L && isH(c1) && isH(c2)) ctx = 2;
+        } else if (q - 2 >= 0) {  // the G of [AGT][AGT]G
+            if (c0 == 'G' && isD(fwd_base(slab, r, q - 1)) && isD(fwd_base(slab, r, q - 2))) ctx = 2;
+        }
+        if (ctx >= 0) atomicAdd(&h[ctx * 256 + prob], 1u);
+    }
+}
+
 __global__ __launch_bounds__(TPB) void mods_kernel(const PMod* __restrict__ mods, int64_t n, const PRead* __restrict__ reads,
                                                     const uint8_t* __restrict__ slab, uint32_t* __restrict__ plane,
                                                     unsigned long long* __restrict__ bins) {
@@ -99,25 +132,25 @@ __global__ __launch_bounds__(TPB) void mods_kernel(const PMod* __restrict__ mods
     __syncthreads();
     for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
         const PMod m = mods[i];
-        const PRead r = reads[m.read];
-        const uint32_t prob = m.bits & 255u;
-        if (m.bits & 0x200u)  // code 'm': read_mods[qoff] = prob, later entries overwrite earlier ones
-            atomicMax(&plane[r.plane_off + m.qoff], (((m.bits >> 10) + 1u) << 9) | 0x100u | prob);
-        if (r.primary && (m.bits & 0x100u)) {
-            const int q = m.qoff, L = r.l_qseq;
-            const char c0 = fwd_base(slab, r, q);
-            int ctx = -1;
-            if (c0 == 'C') {
-                const char c1 = q + 1 < L ? fwd_base(slab, r, q + 1) : 'N';
-                const char c2 = q + 2 < L ? fwd_base(slab, r, q + 2) : 'N';
-                if (q + 1 < L && c1 == 'G') ctx = 0;
-                else if (q + 2 < L && isH(c1) && c2 == 'G') ctx = 1;
-                else if (q + 2 < L && isH(c1) && isH(c2)) ctx = 2;
-            } else if (q - 2 >= 0) {  // the G of [AGT][AGT]G
-                if (c0 == 'G' && isD(fwd_base(slab, r, q - 1)) && isD(fwd_base(slab, r, q - 2))) ctx = 2;
-            }
-            if (ctx >= 0) atomicAdd(&h[ctx * 256 + prob], 1u);
-        }
+        mod_entry(reads[m.read], m.qoff, m.bits & 255u, (m.bits >> 10) + 1u, m.bits & 0x200u, m.bits & 0x100u, slab, plane, h);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 768; i += TPB)
+        if (h[i]) atomicAdd(&bins[i], (unsigned long long)h[i]);
+}
+
+// The counterpart for calls: every call is a 5mC entry on a C (FWD) or G (REV), and a read has at most one per position,
+// so the rank is a constant.  hm_call_t::ctx is not used: at read ends and next to N it is not what the bases of the
+// written-and-parsed MM list give.
+__global__ __launch_bounds__(TPB) void calls_kernel(const PCall* __restrict__ calls, int64_t n, const PRead* __restrict__ reads,
+                                                     const uint8_t* __restrict__ slab, uint32_t* __restrict__ plane,
+                                                     unsigned long long* __restrict__ bins) {
+    __shared__ uint32_t h[3 * 256];
+    for (int i = threadIdx.x; i < 768; i += TPB) h[i] = 0;
+    __syncthreads();
+    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
+        const PCall c = calls[i];
+        mod_entry(reads[c.read], c.qoff, c.prob, 1u, true, true, slab, plane, h);
     }
     __syncthreads();
     for (int i = threadIdx.x; i < 768; i += TPB)
@@ -517,10 +550,11 @@ struct hm_pileup {
     std::vector<PRun> runs;
     std::vector<int64_t> col0;
     std::vector<PMod> mods;
+    std::vector<PCall> calls;  // of the records submitted with calls; n_m_mods counts them too
     int64_t plane_len = 0, n_m_mods = 0;
 
     // device
-    DevBuf d_slab{HALF}, d_reads{HALF}, d_runs{HALF}, d_col0{HALF}, d_mods{HALF}, d_plane{HALF}, d_matches{HALF}, d_bins{HALF}, d_counter{HALF}, d_recs{HALF};
+    DevBuf d_slab{HALF}, d_reads{HALF}, d_runs{HALF}, d_col0{HALF}, d_mods{HALF}, d_calls{HALF}, d_plane{HALF}, d_matches{HALF}, d_bins{HALF}, d_counter{HALF}, d_recs{HALF};
     DevBuf d_blk{HALF}, d_offs{HALF}, d_loci{HALF}, d_labels{HALF}, d_lbins{HALF};
     DevBuf d_asm{HALF}, d_lfact{EXACT};  // tested rows of hm_pileup_fetch_asm; log n! table, uploaded by its first call
     int64_t n_recs = 0;
@@ -566,8 +600,106 @@ void clear_batch(hm_pileup* p) {
     p->runs.clear();
     p->col0.clear();
     p->mods.clear();
+    p->calls.clear();
     p->plane_len = 0;
     p->n_m_mods = 0;
+}
+
+// The record-level part of a submission, shared by the MM/ML and the calls form: every argument check, the CIGAR turned into
+// match runs (appended to p->runs from `runs_before` on) and the PRead `r`, which the caller pushes once the record's `n_entries`
+// entries (mods or calls, at `entries`) are staged as well.  Returns 1 to go on, else the submission's return value.
+int stage_alignment(hm_pileup* p, uint32_t order, int32_t flag, int32_t sid, int64_t pos, int32_t mapq, int32_t l_qseq,
+                    const uint8_t* seq4, int32_t n_cigar, const uint32_t* cigar, int64_t n_entries, const void* entries, int32_t hp,
+                    PRead& r, size_t& runs_before) {
+    if (!p) return HM_EINVAL;
+    if (hp < 0 || hp > 2) return pfail(p, HM_EINVAL, "haplotype partition must be 0, 1 or 2");
+    if (hp && p->partitions != 2) return pfail(p, HM_ESTATE, "haplotype partition given but the partitions option is off");
+    if (p->seq_off.empty()) return pfail(p, HM_ESTATE, "hm_pileup_submit_read before hm_pileup_set_reference");
+    if (n_entries <= 0 || (flag & 4)) return 0;  // pileup.cpp:233-235
+    if (n_entries >= (int64_t(1) << 22)) return pfail(p, HM_EINVAL, "more than 2^22 modification entries in one read");
+    if (l_qseq < 0 || !seq4 || n_cigar < 0 || (n_cigar && !cigar) || !entries) return pfail(p, HM_EINVAL, "hm_pileup_submit_read: bad argument");
+    // key = order << 2 | motif must stay below 2^31: the multi-GPU path max-reduces the key plane as int32
+    // (hifimeth_amd/pileup.py: reduce_scatter_planes), where a set top bit would lose against an empty locus
+    if (order >= (1u << 29)) return pfail(p, HM_EINVAL, "record order must be < 2^29");
+    if (l_qseq >= (1 << 22)) return pfail(p, HM_EINVAL, "reads of 2^22 bases or more are not supported");
+    const int n_seqs = (int)p->seq_off.size() - 1;
+    if (sid < 0 || sid >= n_seqs) return pfail(p, HM_EINVAL, "sequence index out of range");
+    const int64_t ssize = p->seq_off[sid + 1] - p->seq_off[sid];
+    if (pos < 0 || pos > ssize) return pfail(p, HM_EDATA, "alignment position outside the reference sequence");
+    {   // s_decode_bam_query_base accepts the nibbles 1, 2, 4, 8, 15 only (bam_info.cpp:100-121); two per byte
+        static const auto ok = [] {
+            std::array<uint8_t, 256> t{};
+            auto good = [](int c) { return c == 1 || c == 2 || c == 4 || c == 8 || c == 15; };
+            for (int b = 0; b < 256; ++b) t[(size_t)b] = good(b >> 4) && good(b & 15);
+            return t;
+        }();
+        const int full = l_qseq >> 1;
+        int bad = -1;
+        for (int i = 0; i < full; ++i)
+            if (!ok[seq4[i]]) { bad = i; break; }
+        if (bad < 0 && (l_qseq & 1) && !ok[(seq4[full] & 0xf0) | 1]) bad = full;
+        if (bad >= 0) {
+            const int hi = seq4[bad] >> 4, lo = seq4[bad] & 15;
+            const bool hi_bad = !(hi == 1 || hi == 2 || hi == 4 || hi == 8 || hi == 15);
+            return pfail(p, HM_EDATA, "Illegal BAM base encoded value " + std::to_string(hi_bad ? hi : lo));
+        }
+    }
+    // cigar_to_alignment (bam_info.cpp:262-371) without the strings: match runs + column count
+    runs_before = p->runs.size();
+    int opi = 0;
+    int64_t qi = -1, si = -1;
+    if (n_cigar > 0) {
+        const int op0 = cigar[0] & 15;
+        if (op0 == 4) { qi = (int64_t)(cigar[0] >> 4) - 1; opi = 1; }
+        else if (op0 == 5) opi = 1;
+    }
+    int64_t as_size = 0;
+    bool open = false;  // the previous column-producing op was a match-type op
+    for (; opi < n_cigar; ++opi) {
+        const int op = cigar[opi] & 15;
+        const int64_t num = cigar[opi] >> 4;
+        if (op == 0 || op == 7 || op == 8) {  // M = X
+            if (num == 0) continue;
+            if (open) p->runs.back().len += (int32_t)num;
+            else p->runs.push_back(PRun{p->seq_off[sid] + pos + si + 1, (int32_t)p->reads.size(), (int32_t)(qi + 1), (int32_t)num, 0});
+            open = true;
+            qi += num; si += num; as_size += num;
+        } else if (op == 1) {  // I
+            qi += num; as_size += num;
+            if (num) open = false;
+        } else if (op == 2 || op == 3) {  // D N
+            si += num; as_size += num;
+            if (num) open = false;
+        } else if (op == 4 || op == 5 || op == 6) {  // S H P: no columns
+        } else {
+            p->runs.resize(runs_before);
+            return pfail(p, HM_EDATA, "Unrecognised CIGAR operation");
+        }
+        if (qi >= l_qseq || pos + si >= ssize) {
+            p->runs.resize(runs_before);
+            return pfail(p, HM_EDATA, qi >= l_qseq ? "CIGAR consumes more bases than SEQ holds"
+                                                    : "alignment runs past the end of the reference sequence");
+        }
+    }
+    if (as_size >= (int64_t(1) << 31)) { p->runs.resize(runs_before); return pfail(p, HM_EINVAL, "alignment too long"); }
+    r = PRead{};
+    r.seq4_off = (int64_t)p->slab.size();
+    r.plane_off = p->plane_len;
+    r.l_qseq = l_qseq;
+    r.order = order;
+    r.as_size = (int32_t)as_size;
+    r.rev = (flag & 16) ? 1 : 0;
+    r.primary = (flag & 0x900) ? 0 : 1;
+    r.pass = mapq >= p->min_mapq ? 1 : 0;
+    r.hp = (uint8_t)hp;
+    return 1;
+}
+
+// the record joins the staged batch (after its entries)
+void commit_read(hm_pileup* p, const PRead& r, const uint8_t* seq4) {
+    p->slab.insert(p->slab.end(), seq4, seq4 + (r.l_qseq + 1) / 2);
+    p->plane_len += r.l_qseq;
+    p->reads.push_back(r);
 }
 
 }  // namespace
@@ -699,87 +831,10 @@ int hm_pileup_submit_read(hm_pileup_t* p, uint32_t order, int32_t flag, int32_t 
 int hm_pileup_submit_read_hp(hm_pileup_t* p, uint32_t order, int32_t flag, int32_t sid, int64_t pos, int32_t mapq,
                              int32_t l_qseq, const uint8_t* seq4, int32_t n_cigar, const uint32_t* cigar, int64_t n_mods,
                              const hm_mod_t* mods, int32_t hp) {
-    if (!p) return HM_EINVAL;
-    if (hp < 0 || hp > 2) return pfail(p, HM_EINVAL, "haplotype partition must be 0, 1 or 2");
-    if (hp && p->partitions != 2) return pfail(p, HM_ESTATE, "haplotype partition given but the partitions option is off");
-    if (p->seq_off.empty()) return pfail(p, HM_ESTATE, "hm_pileup_submit_read before hm_pileup_set_reference");
-    if (n_mods <= 0 || (flag & 4)) return 0;  // pileup.cpp:233-235
-    if (n_mods >= (int64_t(1) << 22)) return pfail(p, HM_EINVAL, "more than 2^22 modification entries in one read");
-    if (l_qseq < 0 || !seq4 || n_cigar < 0 || (n_cigar && !cigar) || !mods) return pfail(p, HM_EINVAL, "hm_pileup_submit_read: bad argument");
-    // key = order << 2 | motif must stay below 2^31: the multi-GPU path max-reduces the key plane as int32
-    // (hifimeth_amd/pileup.py: reduce_scatter_planes), where a set top bit would lose against an empty locus
-    if (order >= (1u << 29)) return pfail(p, HM_EINVAL, "record order must be < 2^29");
-    if (l_qseq >= (1 << 22)) return pfail(p, HM_EINVAL, "reads of 2^22 bases or more are not supported");
-    const int n_seqs = (int)p->seq_off.size() - 1;
-    if (sid < 0 || sid >= n_seqs) return pfail(p, HM_EINVAL, "sequence index out of range");
-    const int64_t ssize = p->seq_off[sid + 1] - p->seq_off[sid];
-    if (pos < 0 || pos > ssize) return pfail(p, HM_EDATA, "alignment position outside the reference sequence");
-    {   // s_decode_bam_query_base accepts the nibbles 1, 2, 4, 8, 15 only (bam_info.cpp:100-121); two per byte
-        static const auto ok = [] {
-            std::array<uint8_t, 256> t{};
-            auto good = [](int c) { return c == 1 || c == 2 || c == 4 || c == 8 || c == 15; };
-            for (int b = 0; b < 256; ++b) t[(size_t)b] = good(b >> 4) && good(b & 15);
-            return t;
-        }();
-        const int full = l_qseq >> 1;
-        int bad = -1;
-        for (int i = 0; i < full; ++i)
-            if (!ok[seq4[i]]) { bad = i; break; }
-        if (bad < 0 && (l_qseq & 1) && !ok[(seq4[full] & 0xf0) | 1]) bad = full;
-        if (bad >= 0) {
-            const int hi = seq4[bad] >> 4, lo = seq4[bad] & 15;
-            const bool hi_bad = !(hi == 1 || hi == 2 || hi == 4 || hi == 8 || hi == 15);
-            return pfail(p, HM_EDATA, "Illegal BAM base encoded value " + std::to_string(hi_bad ? hi : lo));
-        }
-    }
-    // cigar_to_alignment (bam_info.cpp:262-371) without the strings: match runs + column count
-    const size_t runs_before = p->runs.size();
-    int opi = 0;
-    int64_t qi = -1, si = -1;
-    if (n_cigar > 0) {
-        const int op0 = cigar[0] & 15;
-        if (op0 == 4) { qi = (int64_t)(cigar[0] >> 4) - 1; opi = 1; }
-        else if (op0 == 5) opi = 1;
-    }
-    int64_t as_size = 0;
-    bool open = false;  // the previous column-producing op was a match-type op
-    for (; opi < n_cigar; ++opi) {
-        const int op = cigar[opi] & 15;
-        const int64_t num = cigar[opi] >> 4;
-        if (op == 0 || op == 7 || op == 8) {  // M = X
-            if (num == 0) continue;
-            if (open) p->runs.back().len += (int32_t)num;
-            else p->runs.push_back(PRun{p->seq_off[sid] + pos + si + 1, (int32_t)p->reads.size(), (int32_t)(qi + 1), (int32_t)num, 0});
-            open = true;
-            qi += num; si += num; as_size += num;
-        } else if (op == 1) {  // I
-            qi += num; as_size += num;
-            if (num) open = false;
-        } else if (op == 2 || op == 3) {  // D N
-            si += num; as_size += num;
-            if (num) open = false;
-        } else if (op == 4 || op == 5 || op == 6) {  // S H P: no columns
-        } else {
-            p->runs.resize(runs_before);
-            return pfail(p, HM_EDATA, "Unrecognised CIGAR operation");
-        }
-        if (qi >= l_qseq || pos + si >= ssize) {
-            p->runs.resize(runs_before);
-            return pfail(p, HM_EDATA, qi >= l_qseq ? "CIGAR consumes more bases than SEQ holds"
-                                                    : "alignment runs past the end of the reference sequence");
-        }
-    }
-    if (as_size >= (int64_t(1) << 31)) { p->runs.resize(runs_before); return pfail(p, HM_EINVAL, "alignment too long"); }
-    PRead r{};
-    r.seq4_off = (int64_t)p->slab.size();
-    r.plane_off = p->plane_len;
-    r.l_qseq = l_qseq;
-    r.order = order;
-    r.as_size = (int32_t)as_size;
-    r.rev = (flag & 16) ? 1 : 0;
-    r.primary = (flag & 0x900) ? 0 : 1;
-    r.pass = mapq >= p->min_mapq ? 1 : 0;
-    r.hp = (uint8_t)hp;
+    PRead r;
+    size_t runs_before;
+    const int rc = stage_alignment(p, order, flag, sid, pos, mapq, l_qseq, seq4, n_cigar, cigar, n_mods, mods, hp, r, runs_before);
+    if (rc != 1) return rc;
     const int32_t ri = (int32_t)p->reads.size();
     const size_t mods_before = p->mods.size();
     const int64_t m_before = p->n_m_mods;
@@ -797,9 +852,39 @@ int hm_pileup_submit_read_hp(hm_pileup_t* p, uint32_t order, int32_t flag, int32
         p->mods.push_back(PMod{ri, m.qoff, ((uint32_t)i << 10) | (is_m ? 0x200u : 0u) | (cg ? 0x100u : 0u) | m.prob});
         if (is_m) ++p->n_m_mods;
     }
-    p->slab.insert(p->slab.end(), seq4, seq4 + (l_qseq + 1) / 2);
-    p->plane_len += l_qseq;
-    p->reads.push_back(r);
+    commit_read(p, r, seq4);
+    return 1;
+}
+
+int hm_pileup_submit_read_calls(hm_pileup_t* p, uint32_t order, int32_t flag, int32_t sid, int64_t pos, int32_t mapq,
+                                int32_t l_qseq, const uint8_t* seq4, int32_t n_cigar, const uint32_t* cigar,
+                                int64_t n_calls, const hm_call_t* calls, int32_t hp) {
+    PRead r;
+    size_t runs_before;
+    const int rc = stage_alignment(p, order, flag, sid, pos, mapq, l_qseq, seq4, n_cigar, cigar, n_calls, calls, hp, r, runs_before);
+    if (rc != 1) return rc;
+    // what apply_calls refuses (hm_bam.cpp): an offset outside the read; calls not strictly increasing per strand, FWD first
+    const int32_t ri = (int32_t)p->reads.size();
+    const size_t calls_before = p->calls.size();
+    p->calls.resize(calls_before + (size_t)n_calls);
+    PCall* dst = p->calls.data() + calls_before;
+    int strand = 0;
+    int32_t last = -1;
+    for (int64_t i = 0; i < n_calls; ++i) {
+        const hm_call_t& c = calls[i];
+        const bool outside = c.qoff < 0 || c.qoff >= l_qseq;
+        if (c.strand != strand && c.strand == 1) { strand = 1; last = -1; }
+        if (outside || c.strand != strand || c.qoff <= last) {  // leave the staged batch as it was
+            p->runs.resize(runs_before);
+            p->calls.resize(calls_before);
+            return outside ? pfail(p, HM_EDATA, "call offset outside the read")
+                           : pfail(p, HM_EINVAL, "calls are not strictly increasing per strand, FWD strand first");
+        }
+        last = c.qoff;
+        dst[i] = PCall{ri, c.qoff, c.strand, c.ctx, c.scaled_prob, 0};
+    }
+    p->n_m_mods += n_calls;
+    commit_read(p, r, seq4);
     return 1;
 }
 
@@ -814,13 +899,14 @@ int hm_pileup_run(hm_pileup_t* p) {
         int64_t cols = 0;
         for (int i = 0; i < n_runs; ++i) { p->col0[i] = cols; cols += p->runs[i].len; }
         p->col0[n_runs] = cols;
-        const int64_t n_mods = (int64_t)p->mods.size();
+        const int64_t n_mods = (int64_t)p->mods.size(), n_calls = (int64_t)p->calls.size();
 
         p->d_slab.reserve(p->slab.size() + 4);
         p->d_reads.reserve(sizeof(PRead) * (size_t)n_reads);
         p->d_runs.reserve(sizeof(PRun) * (size_t)std::max(n_runs, 1));
         p->d_col0.reserve(sizeof(int64_t) * ((size_t)n_runs + 1));
         p->d_mods.reserve(sizeof(PMod) * (size_t)std::max<int64_t>(n_mods, 1));
+        if (n_calls) p->d_calls.reserve(sizeof(PCall) * (size_t)n_calls);
         p->d_plane.reserve(4 * (size_t)std::max<int64_t>(p->plane_len, 1));
         p->d_matches.reserve(4 * (size_t)n_reads);
         p->d_recs.reserve(sizeof(PRec) * (size_t)(p->n_recs + p->n_m_mods + 1), sizeof(PRec) * (size_t)p->n_recs, st);
@@ -830,11 +916,16 @@ int hm_pileup_run(hm_pileup_t* p) {
         if (n_runs) HIP_TRY(hipMemcpyAsync(p->d_runs.p, p->runs.data(), sizeof(PRun) * (size_t)n_runs, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(p->d_col0.p, p->col0.data(), sizeof(int64_t) * ((size_t)n_runs + 1), hipMemcpyHostToDevice, st));
         if (n_mods) HIP_TRY(hipMemcpyAsync(p->d_mods.p, p->mods.data(), sizeof(PMod) * (size_t)n_mods, hipMemcpyHostToDevice, st));
+        if (n_calls) HIP_TRY(hipMemcpyAsync(p->d_calls.p, p->calls.data(), sizeof(PCall) * (size_t)n_calls, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemsetAsync(p->d_plane.p, 0, 4 * (size_t)std::max<int64_t>(p->plane_len, 1), st));
         HIP_TRY(hipMemsetAsync(p->d_matches.p, 0, 4 * (size_t)n_reads, st));
 
         if (n_mods)  // <= 1024 workgroups: each flushes up to 768 histogram bins with same-address global atomics (~10 ns each)
             hipLaunchKernelGGL(mods_kernel, dim3(grid_for(n_mods, 1024)), dim3(TPB), 0, st, p->d_mods.as<PMod>(), n_mods,
+                               p->d_reads.as<PRead>(), p->d_slab.as<uint8_t>(), p->d_plane.as<uint32_t>(),
+                               p->d_bins.as<unsigned long long>());
+        if (n_calls)  // the records submitted with calls: their plane words and histogram counts, same grid rule
+            hipLaunchKernelGGL(calls_kernel, dim3(grid_for(n_calls, 1024)), dim3(TPB), 0, st, p->d_calls.as<PCall>(), n_calls,
                                p->d_reads.as<PRead>(), p->d_slab.as<uint8_t>(), p->d_plane.as<uint32_t>(),
                                p->d_bins.as<unsigned long long>());
         if (cols > 0) {

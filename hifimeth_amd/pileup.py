@@ -17,6 +17,9 @@ Allele-specific methylation (`pileup -H -A`): `pu.asm(min_cov=5)` are the loci w
 counted calls, with the difference of the two methylation percentages and the two-sided Fisher exact p-value of
 [[pcov1, ncov1], [pcov2, ncov2]], both computed on the device; `pu.asm_bed(rows)` is the text of <prefix>.asm.<ctx>.bed.
 
+Fused with the caller (`pileup -K`): `pu.add_called(read, calls)` takes the records `MethylationCaller` returned for an aligned read
+instead of parsed MM / ML -- the same effect as add() of that read carrying the calls as tags, without the tag text.
+
 Multi-GPU (one process per GPU, records dealt to ranks in slabs): `reduce_over_ranks` sums the histograms with an
 all-reduce before the thresholds are resolved, and after counting reduce-scatters the per-locus planes (sum for
 pcov / ncov, max for the motif key) so that every rank ends up owning one contiguous range of loci.
@@ -162,6 +165,23 @@ class MethylationPileup:
             return self._check(self._L.hm_pileup_submit_read(*args))
         hp = getattr(read, "hp", None)
         return self._check(self._L.hm_pileup_submit_read_hp(*args, hp if hp in (1, 2) else 0))
+
+    def add_called(self, read, calls: np.ndarray, order: Optional[int] = None, hp: int = 0) -> int:
+        """The fused path (hm_pileup_submit_read_calls): `read` as for add() -- its mm / ml are not looked at --, `calls` = the
+        caller.CALL_DTYPE records the caller mirror returned for this read (FWD strand by ascending qoff, then REV), handed to the
+        engine as they are: no MM/ML text is written or parsed.  Same effect as add() of the read carrying those calls as tags.
+        -> 1 staged / 0 skipped (no calls, unmapped)."""
+        from .caller import CALL_DTYPE
+        if order is None:
+            order = self._order
+        self._order = order + 1
+        if calls.dtype != CALL_DTYPE or not calls.flags.c_contiguous:   # (a slice of the caller's result is a view: no copy)
+            calls = np.ascontiguousarray(calls, CALL_DTYPE)
+        seq4 = np.ascontiguousarray(read.seq4, np.uint8)
+        cig = np.ascontiguousarray(read.cigar_u32(), np.uint32)
+        return self._check(self._L.hm_pileup_submit_read_calls(
+            self._h, order, read.flag, read.tid, read.pos, read.mapq, len(read.seq), seq4.ctypes.data_as(C.c_void_p), len(cig),
+            cig.ctypes.data_as(C.c_void_p), len(calls), calls.ctypes.data_as(C.c_void_p), hp))
 
     def flush(self):
         self._check(self._L.hm_pileup_run(self._h))

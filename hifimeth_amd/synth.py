@@ -365,3 +365,88 @@ def synth_alignments(genome, n_reads: int = 40, seed: int = 5, median_len: int =
         mm, ml = _call_like_mods(s, rng, lambda k: 0.5)
         reads.append(AlignedRead(f"un{i}", 4, -1, -1, 0, [], s, mm, ml))
     return reads
+
+
+# ---- aligned reads that still carry their kinetics: the input of `pileup -K` ----------------------------------------
+def aligned_kinetics(reads, seed: int = 11, wide=()):
+    """fi / fp / ri / rp of every AlignedRead, in ORIGINAL read orientation (pbmm2 copies the tags of the unaligned record: for a
+    flag-0x10 record they run against the stored SEQ): uint8 (B:C codev1) arrays, uint16 (B:S frames) for the indices in
+    `wide`.  Length = the whole read: l_qseq plus the hard-clipped bases of the CIGAR -- a hard-clipped supplementary record
+    keeps full-length tags that no longer match its SEQ, so `call` passes it through uncalled."""
+    rng = np.random.default_rng(seed)
+    wide = set(wide)
+    out = []
+    for i, r in enumerate(reads):    # the distributions of _kinetics, drawn through the quantile tables (fast enough for the bench's GB inputs)
+        n = r.l_qseq + sum(k for op, k in r.cigar if op == "H")
+        bits = rng.integers(0, 1 << 16, size=(4, n), dtype=np.uint16)
+        if i in wide:
+            out.append([_quantile_table(2.0, s, 2000, np.uint16)[bits[j]] for j, s in enumerate((30.0, 12.0, 30.0, 12.0))])
+        else:
+            out.append([_quantile_table(k, th, 255, np.uint8)[bits[j]] for j, (k, th) in enumerate(((2.0, 12.0), (3.0, 5.0), (2.0, 12.0), (3.0, 5.0)))])
+    return out
+
+
+def kinetics_read(r: AlignedRead, kin) -> Read:
+    """The record as the call engine sees it: SEQ as stored, the flag (0x10 = kinetics run against SEQ), the four arrays."""
+    return Read(r.name, r.l_qseq, r.flag, r.seq4, *kin)
+
+
+def write_aligned_kinetics_bam(path: str, genome, reads, kinetics=None, seed: int = 11, wide=(), keep_mods=(), level: int = 1,
+                               threads: int = 8, sort_order: str = "coordinate") -> int:
+    """Coordinate-sorted BAM of AlignedRead records as pbmm2 writes them from a HiFi BAM with kinetics: the same alignments
+    tests/bamutil.aligned_to_bam writes, WITHOUT MM / ML / MN, with fi / fp / ri / rp (`kinetics`, default
+    aligned_kinetics(reads, seed, wide); `wide`: indices written as B:S) and HP:i of the reads that have one.  `keep_mods`:
+    indices whose record also keeps the read's own mm / ml -- stale tags, which `call` drops.  BGZF blocks are deflated on
+    `threads` threads.  Returns the number of payload bytes."""
+    import struct
+    import zlib
+    from concurrent.futures import ThreadPoolExecutor
+
+    def block(data: bytes) -> bytes:
+        co = zlib.compressobj(level, zlib.DEFLATED, -15)
+        comp = co.compress(data) + co.flush()
+        return (b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + struct.pack("<H", 18 + len(comp) + 8 - 1) + comp
+                + struct.pack("<II", zlib.crc32(data) & 0xffffffff, len(data)))
+
+    def aux_b(tag: bytes, a) -> bytes:
+        a = np.ascontiguousarray(a)
+        return tag + (b"BC" if a.dtype.itemsize == 1 else b"BS") + struct.pack("<I", len(a)) + a.astype(a.dtype.newbyteorder("<")).tobytes()
+
+    if kinetics is None:
+        kinetics = aligned_kinetics(reads, seed, wide)
+    keep_mods = set(keep_mods)
+    text = f"@HD\tVN:1.6\tSO:{sort_order}\tpb:5.0.0\n" + "".join(f"@SQ\tSN:{n}\tLN:{len(s)}\n" for n, s in genome)
+    buf = bytearray(b"BAM\1" + struct.pack("<I", len(text)) + text.encode() + struct.pack("<I", len(genome)))
+    for n, s in genome:
+        nm = n.encode() + b"\0"
+        buf += struct.pack("<I", len(nm)) + nm + struct.pack("<I", len(s))
+    BLK, total = 0xff00, 0
+    with open(path, "wb") as f, ThreadPoolExecutor(max_workers=max(1, threads)) as ex:
+        def drain(final: bool):
+            nonlocal buf, total
+            n = len(buf) if final else len(buf) // BLK * BLK
+            mv = bytes(buf[:n])
+            for comp in ex.map(block, (mv[i:i + BLK] for i in range(0, n, BLK))):
+                f.write(comp)
+            total += n
+            del buf[:n]
+
+        for i, (r, kin) in enumerate(zip(reads, kinetics)):
+            aux = b"RGZrg0\0"
+            for tag, a in zip((b"fi", b"fp", b"ri", b"rp"), kin):
+                if a is not None:
+                    aux += aux_b(tag, a)
+            if i in keep_mods and r.mm is not None:
+                aux += b"MMZ" + r.mm.encode() + b"\0" + aux_b(b"ML", np.asarray(r.ml, np.uint8)) + b"MNi" + struct.pack("<i", r.l_qseq)
+            if r.hp is not None:
+                aux += b"HPi" + struct.pack("<i", r.hp)
+            qn = r.name.encode() + b"\0"
+            cig, seq4 = r.cigar_u32(), bytes(r.seq4)
+            core = struct.pack("<iiBBHHHiiii", r.tid, r.pos, len(qn), r.mapq, 4680, len(cig), r.flag, r.l_qseq, -1, -1, 0)
+            body_len = len(core) + len(qn) + 4 * len(cig) + len(seq4) + r.l_qseq + len(aux)
+            buf += struct.pack("<I", body_len) + core + qn + cig.astype("<u4").tobytes() + seq4 + b"\xff" * r.l_qseq + aux
+            if len(buf) >= (64 << 20):
+                drain(False)
+        drain(True)
+        f.write(bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000"))
+    return total

@@ -203,6 +203,7 @@ int hm_reset_timing(hm_engine_t* e);
  * Replaces the body of s_genomic_methy_freq_thread + the counting loop of s_compute_methy_freq
  * (src/app/hifimeth/pileup.cpp:208-353, 514-560) and the classes they drive:
  *   BamMapInfo::init / cigar_to_alignment   (src/corelib/bam_info.cpp:262-439)     -> hm_pileup_submit_read
+ *   (ours) the calls of hm_batch_wait straight into the pileup, no mod-BAM between  -> hm_pileup_submit_read_calls
  *   extract_chh_mapped_samples              (src/corelib/5mc_motif_finder.cpp:104-144)
  *   CpG / CHG loops                         (pileup.cpp:292-335)                     -> hm_pileup_run
  *   3 x 256 probability histograms          (pileup.cpp:237-272)                     -> hm_pileup_histograms
@@ -263,6 +264,17 @@ int hm_pileup_submit_read(hm_pileup_t* p, uint32_t order, int32_t flag, int32_t 
 int hm_pileup_submit_read_hp(hm_pileup_t* p, uint32_t order, int32_t flag, int32_t sid, int64_t pos, int32_t mapq,
                              int32_t l_qseq, const uint8_t* seq4, int32_t n_cigar, const uint32_t* cigar,
                              int64_t n_mods, const hm_mod_t* mods, int32_t hp);
+/* The fused path (`pileup -K`): the same record with its 5mC CALLS instead of parsed MM/ML lists --
+ * `calls` exactly as hm_batch_wait / hm_fetch deliver them for this read (FWD strand by ascending qoff, then REV strand by
+ * ascending qoff; read_id is ignored).  The effect on the engine -- histograms, projected records, planes after
+ * hm_pileup_count, return value -- is that of writing the calls into the record as MM/ML (hmbam::apply_calls), parsing them
+ * back (hmbam::parse_mods) and passing the result to hm_pileup_submit_read_hp; no tag text is built.  n_calls == 0 returns 0
+ * like a record without MM.  Every check of hm_pileup_submit_read_hp holds; in addition HM_EDATA for a qoff outside
+ * [0, l_qseq) and HM_EINVAL for calls that are not strictly increasing per strand, FWD before REV.  On an error the staged
+ * batch is as it was.  One batch (hm_pileup_run) may mix records submitted with mods and records submitted with calls. */
+int hm_pileup_submit_read_calls(hm_pileup_t* p, uint32_t order, int32_t flag, int32_t sid, int64_t pos, int32_t mapq,
+                                int32_t l_qseq, const uint8_t* seq4, int32_t n_cigar, const uint32_t* cigar,
+                                int64_t n_calls, const hm_call_t* calls, int32_t hp);
 /* histograms + projection of the staged records; the projected calls are appended to the HBM-resident list */
 int hm_pileup_run(hm_pileup_t* p);
 int64_t hm_pileup_num_records(hm_pileup_t* p);
