@@ -10,6 +10,10 @@
 // -A (ours, with -H): also <prefix>.asm.<ctx>.bed, one row per locus where each haplotype has at least -a (default 5) counted
 // calls:  chrom <tab> soff <tab> soff+1 <tab> diff <tab> pvalue <tab> pcov1 <tab> ncov1 <tab> pcov2 <tab> ncov2
 // (difference of the two methylation percentages, two-sided Fisher exact test; both computed on the GPU).
+// -B <control sequence> or -e <r_cpg,r_chg,r_chh> (ours): also <prefix>.sites.<ctx>.bed, the rows of <prefix>.<ctx>.cov.bed followed
+// by pvalue and qvalue -- the one-sided binomial test of the locus against the context's false-positive rate (measured on the
+// unmethylated control sequence, or given) and its Benjamini-Hochberg q-value within the context -- and <prefix>.sites.rates.tsv
+// (DESIGN.md section 10).
 // -K (ours): the input is an aligned BAM that still carries the kinetics tags (pbmm2 keeps fi / fp / ri / rp): the reads are called
 // on the fly by the call engine and their calls go straight to the pileup engine (hm_pileup_submit_read_calls) -- the files
 // `call` followed by `pileup` writes, without the mod-BAM between the two.
@@ -17,6 +21,7 @@
 #include <zlib.h>
 
 #include <algorithm>
+#include <cctype>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -69,6 +74,9 @@ struct PileupOptions {
     bool asm_test = false;    // -A: per-locus haplotype difference + Fisher exact test -> <prefix>.asm.*
     int asm_min_cov = 5;      // -a: minimum pcov + ncov of each haplotype for a locus to be tested
     bool asm_min_cov_given = false;
+    std::string control;      // -B: name of the unmethylated control sequence -> rates measured there, <prefix>.sites.*
+    bool rates_given = false; // -e: the three rates given directly (NaN: context not tested)
+    double rates[3] = {0, 0, 0};
     // -K: call on the fly; the options below are `call`'s (hifimeth_call.cpp), same meaning and defaults
     bool kinetics = false;
     bool call_option_given = false;  // any of -m -c -l -p -T: a usage error without -K
@@ -95,6 +103,12 @@ void pileup_usage(const char* exe) {
             "  -A\n    With -H: test every locus where both haplotypes are covered for a difference between them and write\n"
             "    <prefix>.asm.<ctx>.bed: chrom, start, end, hap1 %% - hap2 %%, two-sided Fisher exact p-value, pcov1, ncov1, pcov2, ncov2\n"
             "  -a <int>\n    With -A: minimum coverage (pcov + ncov) of each haplotype at a tested locus\n    Default: 5\n"
+            "  -B <sequence name>\n    Test every covered locus for methylation above the caller's false-positive rate, measured per context on this\n"
+            "    unmethylated control sequence (chloroplast, spiked-in lambda) as sum(pcov) / sum(pcov + ncov): write <prefix>.sites.<ctx>.bed,\n"
+            "    the rows of <prefix>.<ctx>.cov.bed followed by the one-sided binomial p-value and its Benjamini-Hochberg q-value within\n"
+            "    the context, and <prefix>.sites.rates.tsv: ctx, P, N, rate, loci\n"
+            "  -e <r_cpg,r_chg,r_chh>\n    Instead of -B: the three rates, each a decimal in [0, 1] or nan (context not tested), e.g. those an earlier\n"
+            "    run wrote to <prefix>.sites.rates.tsv\n"
             "  -K\n    The input is an aligned BAM that carries the kinetics tags fi / fp / ri / rp instead of MM / ML: call 5mC on the\n"
             "    fly and pile the calls up directly.  For equal -c -l -p -T -q -f the output files are byte-identical to those of\n"
             "    `%s call` on that BAM followed by `%s pileup` on its output; no mod-BAM is written.  (Give -T explicitly\n"
@@ -907,6 +921,117 @@ bool fused_record_loop(const PileupOptions& o, BgzfReader& in, hm_pileup_t* pe, 
 }
 }  // namespace
 
+namespace {
+// the argument of -e: three comma-separated fields, each `nan` or a plain decimal in [0, 1]
+bool parse_rates(const char* text, double rates[3]) {
+    const char* p = text;
+    for (int c = 0; c < 3; ++c) {
+        const char* e = strchr(p, c < 2 ? ',' : '\0');
+        if (!e || e == p) return false;
+        const std::string t(p, e);
+        if (t == "nan") rates[c] = std::nan("");
+        else {
+            if (t.find_first_not_of("0123456789.eE+-") != std::string::npos || !(isdigit((unsigned char)t[0]) || t[0] == '.')) return false;
+            char* end = nullptr;
+            rates[c] = strtod(t.c_str(), &end);
+            if (end != t.c_str() + t.size() || !(rates[c] >= 0.0 && rates[c] <= 1.0)) return false;
+        }
+        p = e + 1;
+    }
+    return true;
+}
+
+// `pileup -B / -e` after hm_pileup_count: rates (measured on the control sequence `control_sid`, unless given), histogram of the
+// whole reference, the table, then the rows per sequence as write_bed fetches them (40 B per row on the device and here), and
+// <prefix>.sites.rates.tsv.  1 done, -1 engine error (hm_pileup_last_error), 0 another error (message printed).
+int write_sites(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, int control_sid, int threads) {
+    static const char* cn[3] = {"CpG", "CHG", "CHH"};
+    const auto file_error = [&](const std::string& path) { fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str()); return 0; };
+    std::vector<int64_t> start(fa.names.size() + 1, 0);
+    for (size_t s = 0; s < fa.names.size(); ++s) start[s + 1] = start[s] + fa.length[s];
+    uint64_t sums[6] = {0, 0, 0, 0, 0, 0};
+    double rates[3] = {o.rates[0], o.rates[1], o.rates[2]};
+    if (control_sid >= 0) {
+        if (hm_pileup_control_sums(pe, nullptr, nullptr, nullptr, start[(size_t)control_sid], start[(size_t)control_sid + 1], sums) != HM_OK) return -1;
+        for (int c = 0; c < 3; ++c) rates[c] = sums[c] + sums[3 + c] ? (double)sums[c] / (double)(sums[c] + sums[3 + c]) : std::nan("");
+    }
+    for (int c = 0; c < 3; ++c) {
+        if (std::isnan(rates[c])) fprintf(stderr, "WARNING: %s is not tested: %s\n", cn[c], control_sid >= 0 ? "the control sequence has no calls in this context" : "its rate is nan");
+        else fprintf(stderr, "%s false-positive rate: %.17g\n", cn[c], rates[c]);
+    }
+    std::vector<uint64_t> bins((size_t)HM_SITE_BINS, 0);
+    std::vector<hm_locus_t> big;
+    int64_t n_big = hm_pileup_site_histogram(pe, nullptr, nullptr, nullptr, 0, 0, start.back(), bins.data(), nullptr, 0);
+    if (n_big > 0) {  // nothing was added: again, with room for the loci beyond the histogram
+        big.resize((size_t)n_big);
+        n_big = hm_pileup_site_histogram(pe, nullptr, nullptr, nullptr, 0, 0, start.back(), bins.data(), big.data(), n_big);
+    }
+    if (n_big < 0) return -1;
+    std::vector<double> ptab((size_t)HM_SITE_BINS), qtab((size_t)HM_SITE_BINS), big_p(big.size()), big_q(big.size());
+    uint64_t m[3];
+    if (hm_sites_table(rates, bins.data(), big.data(), n_big, ptab.data(), qtab.data(), big_p.data(), big_q.data(), m) != HM_OK) {
+        fprintf(stderr, "ERROR: sites: the histogram of the planes is not one of counts\n");
+        return 0;
+    }
+    int ctx_mask = 0;
+    FILE* out[3] = {nullptr, nullptr, nullptr};
+    const auto close_all = [&] { for (FILE* f : out) if (f) fclose(f); };
+    for (int c = 0; c < 3; ++c) {
+        if (!std::isnan(rates[c])) ctx_mask |= 1 << c;  // an untested context keeps its file, without rows
+        const std::string path = o.prefix + ".sites." + cn[c] + ".bed";
+        if (!(out[c] = fopen(path.c_str(), "w"))) { close_all(); return file_error(path); }
+    }
+    std::vector<hm_site_t> rows;
+    const int fmt_threads = std::max(1, threads);
+    std::vector<std::string> text((size_t)fmt_threads * 3);
+    for (size_t s = 0; s < fa.names.size() && ctx_mask; ++s) {
+        const int64_t lo = start[s], hi = start[s + 1];
+        auto fetch = [&](hm_site_t* dst, int64_t cap) {
+            return hm_pileup_fetch_sites(pe, nullptr, nullptr, nullptr, 0, lo, hi, ctx_mask, ptab.data(), qtab.data(), big.data(), big_p.data(),
+                                         big_q.data(), n_big, dst, cap);
+        };
+        int64_t n = fetch(nullptr, 0);
+        if (n > 0) {
+            rows.resize((size_t)n);
+            n = fetch(rows.data(), n);
+        }
+        if (n < 0) { close_all(); return -1; }
+        if (n == 0) continue;
+        parallel_run(fmt_threads, fmt_threads, [&](int w) {  // formatted in slices and written slice by slice, as write_bed does
+            for (int c = 0; c < 3; ++c) text[(size_t)w * 3 + c].clear();
+            const size_t a = (size_t)n * w / fmt_threads, b = (size_t)n * (w + 1) / fmt_threads;
+            char row[320];
+            for (size_t i = a; i < b; ++i) {
+                const hm_site_t& r = rows[i];
+                const int64_t k = r.gpos - lo;
+                const double freq = 100.0 * r.pcov / (r.pcov + r.ncov);
+                const int len = snprintf(row, sizeof row, "\t%lld\t%lld\t%g\t%d\t%d\t%.6g\t%.6g\n", (long long)k, (long long)k + 1, freq, r.pcov,
+                                         r.ncov, r.pvalue, r.qvalue);
+                std::string& t = text[(size_t)w * 3 + (r.motif < 3 ? r.motif : 2)];
+                t += fa.names[s];
+                t.append(row, (size_t)len);
+            }
+        });
+        for (int c = 0; c < 3; ++c)
+            for (int w = 0; w < fmt_threads; ++w) {
+                const std::string& t = text[(size_t)w * 3 + c];
+                if (!t.empty() && out[c]) fwrite(t.data(), 1, t.size(), out[c]);
+            }
+    }
+    close_all();
+    const std::string path = o.prefix + ".sites.rates.tsv";
+    FILE* f = fopen(path.c_str(), "w");
+    if (!f) return file_error(path);
+    for (int c = 0; c < 3; ++c) {
+        char rate[64] = "nan";
+        if (!std::isnan(rates[c])) snprintf(rate, sizeof rate, "%.17g", rates[c]);
+        fprintf(f, "%s\t%llu\t%llu\t%s\t%llu\n", cn[c], (unsigned long long)sums[c], (unsigned long long)sums[3 + c], rate, (unsigned long long)m[c]);
+    }
+    fclose(f);
+    return 1;
+}
+}  // namespace
+
 int cmd_pileup(int argc, char** argv) {
     PileupOptions o;
     int i = 2;
@@ -924,6 +1049,15 @@ int cmd_pileup(int argc, char** argv) {
         else if (a == "-d") o.device = atoi(argv[++i]);
         else if (a == "-b") o.read_batch = std::max(1, atoi(argv[++i]));
         else if (a == "-a") { o.asm_min_cov = atoi(argv[++i]); o.asm_min_cov_given = true; }
+        else if (a == "-B") o.control = argv[++i];
+        else if (a == "-e") {
+            o.rates_given = true;
+            if (!parse_rates(argv[++i], o.rates)) {
+                fprintf(stderr, "ERROR: -e takes three comma-separated rates, each a decimal in [0, 1] or nan\n");
+                pileup_usage(argv[0]);
+                return EXIT_FAILURE;
+            }
+        }
         else if (a == "-m" || a == "-c" || a == "-l" || a == "-p" || a == "-T") {
             o.call_option_given = true;
             const char* v = argv[++i];
@@ -945,6 +1079,9 @@ int cmd_pileup(int argc, char** argv) {
                            : o.precision < 0 || o.precision > 2 ? "-p must be 0, 1 or 2"
                            : o.call_option_given && (o.trunk < -1 || o.trunk > 1) ? "-T must be 0 or 1" : nullptr;
     if (bad_call) { fprintf(stderr, "ERROR: %s\n", bad_call); pileup_usage(argv[0]); return EXIT_FAILURE; }
+    const char* bad_sites = !o.control.empty() && o.rates_given ? "-B and -e exclude each other (the rates are measured, or given)" : nullptr;
+    if (bad_sites) { fprintf(stderr, "ERROR: %s\n", bad_sites); pileup_usage(argv[0]); return EXIT_FAILURE; }
+    const bool sites = !o.control.empty() || o.rates_given;
     if (o.kinetics && o.model_dir.empty()) o.model_dir = exe_dir() + "/../weights";
     o.ref = argv[i];
     o.bam = argv[i + 1];
@@ -954,6 +1091,8 @@ int cmd_pileup(int argc, char** argv) {
             o.min_mapq, o.min_pi, o.threads, o.ref.c_str(), o.bam.c_str(), o.prefix.c_str());
     if (o.haplotypes) fprintf(stderr, "haplotypes: HP 1 / 2 -> %s.hap1.* / %s.hap2.*\n", o.prefix.c_str(), o.prefix.c_str());
     if (o.asm_test) fprintf(stderr, "asm: min haplotype coverage %d -> %s.asm.*\n", o.asm_min_cov, o.prefix.c_str());
+    if (!o.control.empty()) fprintf(stderr, "sites: binomial test against the rates of control sequence %s -> %s.sites.*\n", o.control.c_str(), o.prefix.c_str());
+    if (o.rates_given) fprintf(stderr, "sites: binomial test against the rates %g,%g,%g -> %s.sites.*\n", o.rates[0], o.rates[1], o.rates[2], o.prefix.c_str());
     if (o.kinetics)
         fprintf(stderr, "kinetics: called on the fly (models %s, contexts%s%s%s, min read length %d, precision %d, trunk %s)\n", o.model_dir.c_str(),
                 o.ctx_mask & 1 ? " CpG" : "", o.ctx_mask & 2 ? " CHG" : "", o.ctx_mask & 4 ? " CHH" : "", o.min_read_size, o.precision,
@@ -974,6 +1113,8 @@ int cmd_pileup(int argc, char** argv) {
     if (!load_fasta(o.ref, fa, err)) { fprintf(stderr, "ERROR: %s\n", err.c_str()); return EXIT_FAILURE; }
     fprintf(stderr, "Load %zu sequences (%zu bases) from %s\n", fa.names.size(), fa.bases.size(), o.ref.c_str());
     std::vector<int> tid2sid(hdr.refs.size(), -2);  // resolved at first use, as HbnDatabase::seq_name2id
+    const int control_sid = o.control.empty() ? -1 : fa.find(o.control);
+    if (!o.control.empty() && control_sid < 0) { fprintf(stderr, "ERROR: control sequence %s (-B) is not in %s\n", o.control.c_str(), o.ref.c_str()); return EXIT_FAILURE; }
 
     hm_pileup_t* pe = nullptr;
     if (hm_pileup_create(&pe, o.device) != HM_OK) { fprintf(stderr, "ERROR: %s\n", hm_pileup_last_error(nullptr)); return EXIT_FAILURE; }
@@ -1128,6 +1269,11 @@ int cmd_pileup(int argc, char** argv) {
         const bool ok = write_asm(pe, fa, o.asm_min_cov, out);
         for (FILE* f : out) fclose(f);
         if (!ok) return die("asm");
+    }
+    if (sites) {
+        const int rc = write_sites(pe, fa, o, control_sid, o.threads);
+        if (rc < 0) return die("sites");
+        if (rc == 0) { hm_pileup_destroy(pe); return EXIT_FAILURE; }
     }
     hm_pileup_destroy(pe);
     fprintf(stderr, o.kinetics ? "## %llu records in %.2f s: [producer thread: BAM read %.2f s, kinetics staging + queueing %.2f s] overlapped with "

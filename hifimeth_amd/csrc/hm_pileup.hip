@@ -22,6 +22,8 @@
 //   loci_*          covered loci of a range in ascending order (count per block, scan, write)
 //   asm_*           loci where both haplotypes reach a minimum coverage, compacted the same way (count, loci_scan, write),
 //                   then one thread per compact row: methylation difference + two-sided Fisher exact test
+//   sites_*         binomial test per locus (`pileup -B / -e`): control sums, histogram of (motif, pcov, pcov + ncov) through LDS,
+//                   the loci beyond the histogram listed, rows written by table lookup (count, loci_scan, write)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,6 +33,7 @@
 #include <cstdio>
 #include <cstring>
 #include <memory>
+#include <numeric>
 #include <string>
 #include <vector>
 
@@ -519,6 +522,182 @@ __global__ __launch_bounds__(TPB) void asm_test_kernel(hm_asm_t* __restrict__ ro
     rows[i].pvalue = p > 1.0 ? 1.0 : p >= DBL_MIN ? p : DBL_MIN;  // never 0: a p-value below the smallest normal double is reported as that
 }
 
+// ---- per-locus binomial test against a false-positive rate (`pileup -B / -e`) ----------------------
+// With the rates fixed, p and q of a locus are functions of (motif, pcov, pcov + ncov) alone, so the device only counts how many
+// loci carry each triple (sites_hist_kernel), the host solves the table (hm_sites_table) and a second pass writes the rows by
+// lookup (sites_write_kernel).  A locus takes part when both counters are counts and one is positive: the planes may be the
+// caller's, and a negative counter never indexes a table.  A key whose low bits are 3 is CHH, as in the BED writers.
+constexpr int SITE_N = 256;      // loci with pcov + ncov below this are histogrammed, the others listed ("big" loci)
+constexpr int SITE_LDS_N = 64;   // ... and below this in the workgroup's LDS histogram: 3 x 64 x 64 x 4 B = 48 KB
+
+__device__ __forceinline__ bool site_counted(int32_t p, int32_t n) { return (p | n) > 0; }
+__device__ __forceinline__ uint32_t site_motif(uint32_t key) { return min(key & 3u, 2u); }
+
+// sums[motif] += pcov, sums[3 + motif] += ncov over the counted loci of [lo, hi): registers, wavefront shuffle, LDS, then at
+// most six global atomics per workgroup
+__global__ __launch_bounds__(TPB) void sites_sums_kernel(const int32_t* __restrict__ pcov, const int32_t* __restrict__ ncov,
+                                                          const uint32_t* __restrict__ key, int64_t lo, int64_t hi,
+                                                          unsigned long long* __restrict__ sums) {
+    __shared__ unsigned long long part[TPB / 64][6];
+    unsigned long long s[6] = {0, 0, 0, 0, 0, 0};
+    for (int64_t i = lo + (int64_t)blockIdx.x * TPB + threadIdx.x; i < hi; i += (int64_t)gridDim.x * TPB) {
+        const int32_t p = pcov[i], n = ncov[i];
+        if (!site_counted(p, n)) continue;
+        const uint32_t m = site_motif(key[i]);
+        for (uint32_t c = 0; c < 3; ++c) {  // (no dynamic register indexing)
+            s[c] += m == c ? (unsigned long long)p : 0ull;
+            s[3 + c] += m == c ? (unsigned long long)n : 0ull;
+        }
+    }
+    for (int c = 0; c < 6; ++c) {
+        for (int d = 32; d; d >>= 1) s[c] += __shfl_down(s[c], d);
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][c] = s[c];
+    }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        unsigned long long t = 0;
+        for (int w = 0; w < TPB / 64; ++w) t += part[w][threadIdx.x];
+        if (t) atomicAdd(&sums[threadIdx.x], t);
+    }
+}
+
+// bins[(motif * 256 + n) * 256 + k] += 1 for every counted locus with k = pcov, n = pcov + ncov < 256; block_big[b] = number of
+// loci with n >= 256 in the b-th LOCI_PER_BLOCK loci of the range (the counts loci_scan_kernel turns into offsets).  At 30x
+// nearly every locus falls on a few dozen triples, so the corner n < 64 is counted in LDS and reaches `bins` once per
+// workgroup, as in mods_kernel; only the rare loci outside it pay a global atomic each.  A workgroup walks the blocks
+// b = blockIdx.x, + gridDim.x, ...: the host keeps that below 2^19 blocks, so an LDS counter (uint32) cannot wrap.
+__global__ __launch_bounds__(TPB) void sites_hist_kernel(const int32_t* __restrict__ pcov, const int32_t* __restrict__ ncov,
+                                                          const uint32_t* __restrict__ key, int64_t lo, int64_t hi, int64_t nblk,
+                                                          unsigned long long* __restrict__ bins, int32_t* __restrict__ block_big) {
+    __shared__ uint32_t h[3 * SITE_LDS_N * SITE_LDS_N];
+    __shared__ int wsum[TPB / 64];
+    for (int i = threadIdx.x; i < 3 * SITE_LDS_N * SITE_LDS_N; i += TPB) h[i] = 0u;
+    __syncthreads();
+    for (int64_t b = blockIdx.x; b < nblk; b += gridDim.x) {  // (uniform over the workgroup: the barriers below are safe)
+        const int64_t base = lo + b * LOCI_PER_BLOCK;
+        int big = 0;
+        for (int k = 0; k < LOCI_PER_BLOCK / TPB; ++k) {
+            const int64_t i = base + k * TPB + threadIdx.x;
+            if (i >= hi) continue;
+            const int32_t p = pcov[i], n = ncov[i];
+            if (!site_counted(p, n)) continue;
+            const int64_t tot = (int64_t)p + n;
+            const uint32_t m = site_motif(key[i]);
+            if (tot < SITE_LDS_N) atomicAdd(&h[(m * SITE_LDS_N + (uint32_t)tot) * SITE_LDS_N + (uint32_t)p], 1u);
+            else if (tot < SITE_N) atomicAdd(&bins[(m * SITE_N + (uint32_t)tot) * SITE_N + (uint32_t)p], 1ull);
+            else ++big;
+        }
+        for (int d = 32; d; d >>= 1) big += __shfl_down(big, d);
+        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = big;
+        __syncthreads();
+        if (threadIdx.x == 0) block_big[b] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        __syncthreads();
+    }
+    for (int i = threadIdx.x; i < 3 * SITE_LDS_N * SITE_LDS_N; i += TPB)
+        if (h[i]) {
+            const uint32_t m = (uint32_t)i / (SITE_LDS_N * SITE_LDS_N), n = ((uint32_t)i / SITE_LDS_N) % SITE_LDS_N, k = (uint32_t)i % SITE_LDS_N;
+            atomicAdd(&bins[(m * SITE_N + n) * SITE_N + k], (unsigned long long)h[i]);
+        }
+}
+
+// The write step of the count / loci_scan_kernel / write scheme for the two lists below: the rows of the workgroup's
+// LOCI_PER_BLOCK loci for which take(i, row) holds, in ascending order from out[offs[blockIdx.x]] on.
+template <class Row, class Take>
+__device__ __forceinline__ void compact_block(int64_t lo, int64_t hi, const int64_t* __restrict__ offs, Row* __restrict__ out, Take take) {
+    __shared__ int wsum[TPB / 64];
+    __shared__ int carry;
+    if (threadIdx.x == 0) carry = 0;
+    const int64_t base = lo + (int64_t)blockIdx.x * LOCI_PER_BLOCK;
+    const int64_t o0 = offs[blockIdx.x];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int k = 0; k < LOCI_PER_BLOCK / TPB; ++k) {
+        __syncthreads();
+        const int64_t i = base + k * TPB + threadIdx.x;
+        Row r;
+        const bool sel = i < hi && take(i, r);
+        const unsigned long long b = __ballot(sel);
+        if (lane == 0) wsum[w] = __popcll(b);
+        __syncthreads();
+        int before = carry;
+        for (int j = 0; j < w; ++j) before += wsum[j];
+        if (sel) out[o0 + before + __popcll(b & ((1ull << lane) - 1ull))] = r;
+        __syncthreads();
+        if (threadIdx.x == 0) carry += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    }
+}
+
+// the big loci (n >= 256) of the range, where sites_hist_kernel counted them
+__global__ __launch_bounds__(TPB) void sites_big_write_kernel(const int32_t* __restrict__ pcov, const int32_t* __restrict__ ncov,
+                                                               const uint32_t* __restrict__ key, int64_t plane_base, int64_t lo,
+                                                               int64_t hi, const int64_t* __restrict__ offs, hm_locus_t* __restrict__ out) {
+    compact_block(lo, hi, offs, out, [&](int64_t i, hm_locus_t& l) {
+        const int32_t p = pcov[i], n = ncov[i];
+        if (!site_counted(p, n) || (int64_t)p + n < SITE_N) return false;
+        l.gpos = plane_base + i;
+        l.pcov = p;
+        l.ncov = n;
+        l.motif = site_motif(key[i]);
+        l.reserved = 0;
+        return true;
+    });
+}
+
+// a row of <prefix>.sites.<ctx>.bed: a counted locus whose context is tested (bit `motif` of ctx_mask)
+__device__ __forceinline__ bool site_tested(int32_t p, int32_t n, uint32_t key, uint32_t ctx_mask) {
+    return site_counted(p, n) && ((ctx_mask >> site_motif(key)) & 1u);
+}
+
+__global__ __launch_bounds__(TPB) void sites_count_kernel(const int32_t* __restrict__ pcov, const int32_t* __restrict__ ncov,
+                                                           const uint32_t* __restrict__ key, int64_t lo, int64_t hi, uint32_t ctx_mask,
+                                                           int32_t* __restrict__ block_counts) {
+    __shared__ int wsum[TPB / 64];
+    const int64_t base = lo + (int64_t)blockIdx.x * LOCI_PER_BLOCK;
+    int cnt = 0;
+    for (int k = 0; k < LOCI_PER_BLOCK / TPB; ++k) {
+        const int64_t i = base + k * TPB + threadIdx.x;
+        if (i < hi && site_tested(pcov[i], ncov[i], key[i], ctx_mask)) ++cnt;
+    }
+    for (int d = 32; d; d >>= 1) cnt += __shfl_down(cnt, d);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+// rows with pvalue / qvalue looked up: n < 256 in tab[(motif * 256 + n) * 256 + k] (ptab, then qtab behind it), a big locus by
+// its position in the ascending list `big` (big_p / big_q run parallel to it; NaN if the list does not hold the locus)
+__global__ __launch_bounds__(TPB) void sites_write_kernel(const int32_t* __restrict__ pcov, const int32_t* __restrict__ ncov,
+                                                           const uint32_t* __restrict__ key, int64_t plane_base, int64_t lo,
+                                                           int64_t hi, uint32_t ctx_mask, const double* __restrict__ tab,
+                                                           const hm_locus_t* __restrict__ big, const double* __restrict__ big_pq,
+                                                           int64_t n_big, const int64_t* __restrict__ offs, hm_site_t* __restrict__ out) {
+    compact_block(lo, hi, offs, out, [&](int64_t i, hm_site_t& r) {
+        const int32_t p = pcov[i], n = ncov[i];
+        const uint32_t ky = key[i];
+        if (!site_tested(p, n, ky, ctx_mask)) return false;
+        r.gpos = plane_base + i;
+        r.pcov = p;
+        r.ncov = n;
+        r.motif = site_motif(ky);
+        r.reserved = 0;
+        const int64_t tot = (int64_t)p + n;
+        if (tot < SITE_N) {
+            const uint32_t t = (r.motif * SITE_N + (uint32_t)tot) * SITE_N + (uint32_t)p;
+            r.pvalue = tab[t];
+            r.qvalue = tab[3 * SITE_N * SITE_N + t];
+        } else {
+            int64_t a = 0, b = n_big;  // first entry with gpos >= r.gpos
+            while (a < b) {
+                const int64_t mid = (a + b) >> 1;
+                if (big[mid].gpos < r.gpos) a = mid + 1; else b = mid;
+            }
+            const bool found = a < n_big && big[a].gpos == r.gpos;
+            r.pvalue = found ? big_pq[a] : __longlong_as_double(0x7ff8000000000000ll);
+            r.qvalue = found ? big_pq[n_big + a] : __longlong_as_double(0x7ff8000000000000ll);
+        }
+        return true;
+    });
+}
+
 }  // namespace
 
 // ================================================ host ==========================================================
@@ -557,6 +736,9 @@ struct hm_pileup {
     DevBuf d_slab{HALF}, d_reads{HALF}, d_runs{HALF}, d_col0{HALF}, d_mods{HALF}, d_calls{HALF}, d_plane{HALF}, d_matches{HALF}, d_bins{HALF}, d_counter{HALF}, d_recs{HALF};
     DevBuf d_blk{HALF}, d_offs{HALF}, d_loci{HALF}, d_labels{HALF}, d_lbins{HALF};
     DevBuf d_asm{HALF}, d_lfact{EXACT};  // tested rows of hm_pileup_fetch_asm; log n! table, uploaded by its first call
+    // `pileup -B / -e`, allocated by the first call that needs them: control sums, 3 x 256 x 256 bins, ptab + qtab, the big loci
+    // (the histogram's list, or the caller's with p and q behind it), rows of hm_pileup_fetch_sites
+    DevBuf d_ssums{EXACT}, d_sbins{EXACT}, d_stab{EXACT}, d_sbig{HALF}, d_sbigpq{HALF}, d_sites{HALF};
     int64_t n_recs = 0;
     bool bins_ready = false;
 
@@ -581,6 +763,16 @@ int pfail_hip(hm_pileup* p, const HipErr& h) {
 template <class Body>
 auto guarded(hm_pileup* p, Body&& body) -> decltype(body()) {
     return hip_guard(p->device, [p](const HipErr& h) { return pfail_hip(p, h); }, body);
+}
+
+// log n! for n < LFACT_N from the host's libm, filled once: what hm_pileup_fetch_asm uploads and hm_sites_table sums with
+const std::vector<double>& host_lfact() {
+    static const std::vector<double> tab = [] {
+        std::vector<double> t((size_t)LFACT_N);
+        for (int k = 0; k < LFACT_N; ++k) t[(size_t)k] = std::lgamma((double)k + 1.0);
+        return t;
+    }();
+    return tab;
 }
 
 inline int grid_for(int64_t n, int cap = 1 << 20) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + TPB - 1) / TPB, cap)); }
@@ -1089,8 +1281,7 @@ int64_t hm_pileup_fetch_asm(hm_pileup_t* p, const void* pcov1, const void* ncov1
         HIP_TRY(hipStreamSynchronize(st));
         if (total > cap || !out || total == 0) return total;
         if (!p->d_lfact.p) {  // log n!, n < LFACT_N: once per engine
-            std::vector<double> t((size_t)LFACT_N);
-            for (int k = 0; k < LFACT_N; ++k) t[(size_t)k] = std::lgamma((double)k + 1.0);
+            const std::vector<double>& t = host_lfact();
             p->d_lfact.reserve(sizeof(double) * t.size());
             HIP_TRY(hipMemcpyAsync(p->d_lfact.p, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice, st));
             HIP_TRY(hipStreamSynchronize(st));
@@ -1102,6 +1293,209 @@ int64_t hm_pileup_fetch_asm(hm_pileup_t* p, const void* pcov1, const void* ncov1
                            p->d_lfact.as<double>());
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(out, p->d_asm.p, sizeof(hm_asm_t) * (size_t)total, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return total;
+    });
+}
+
+// ---- `pileup -B / -e` ---------------------------------------------------------------------------------------------------------
+}  // extern "C"
+
+namespace {
+
+struct SitePlanes {
+    const int32_t *pc, *nc;
+    const uint32_t* ky;
+};
+
+// the plane arguments of the three sites calls, as hm_pileup_fetch_loci reads them; false (error recorded) if there are none
+bool site_planes(hm_pileup* p, const void* pcov, const void* ncov, const void* key, int64_t& plane_base, SitePlanes& s) {
+    s.pc = pcov ? static_cast<const int32_t*>(pcov) : p->pcov;
+    s.nc = ncov ? static_cast<const int32_t*>(ncov) : p->ncov;
+    s.ky = key ? static_cast<const uint32_t*>(key) : p->key;
+    if (!pcov) plane_base = 0;
+    if (s.pc && s.nc && s.ky) return true;
+    pfail(p, HM_ESTATE, "no planes");
+    return false;
+}
+
+// P(X >= k), X ~ Binomial(n, e), 0 < e < 1, 0 < k <= n: the sum the header spells out
+double binomial_tail(int64_t k, int64_t n, double log_e, double log1m_e) {
+    const std::vector<double>& tab = host_lfact();
+    auto lf = [&](int64_t j) { return j < LFACT_N ? tab[(size_t)j] : std::lgamma((double)j + 1.0); };
+    const double lfn = lf(n);
+    double p = 0.0;
+    for (int64_t x = k; x <= n; ++x) p += std::exp(((lfn - lf(x)) - lf(n - x)) + ((double)x * log_e + (double)(n - x) * log1m_e));
+    return p > 1.0 ? 1.0 : p >= DBL_MIN ? p : DBL_MIN;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hm_pileup_control_sums(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t lo, int64_t hi,
+                           uint64_t sums[6]) {
+    if (!p) return HM_EINVAL;
+    if (lo < 0 || hi < lo || !sums) return pfail(p, HM_EINVAL, "hm_pileup_control_sums: bad argument");
+    SitePlanes s;
+    int64_t base = 0;
+    if (!site_planes(p, pcov, ncov, key, base, s)) return HM_ESTATE;
+    std::fill(sums, sums + 6, uint64_t(0));
+    if (hi == lo) return HM_OK;
+    return guarded(p, [&] {
+        hipStream_t st = p->stream;
+        p->d_ssums.reserve(6 * sizeof(unsigned long long));
+        HIP_TRY(hipMemsetAsync(p->d_ssums.p, 0, 6 * sizeof(unsigned long long), st));
+        hipLaunchKernelGGL(sites_sums_kernel, dim3(grid_for(hi - lo, 1024)), dim3(TPB), 0, st, s.pc, s.nc, s.ky, lo, hi,
+                           p->d_ssums.as<unsigned long long>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(sums, p->d_ssums.p, 6 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return HM_OK;
+    });
+}
+
+int64_t hm_pileup_site_histogram(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t plane_base,
+                                 int64_t lo, int64_t hi, uint64_t* bins, hm_locus_t* big, int64_t cap) {
+    if (!p) return HM_EINVAL;
+    if (lo < 0 || hi < lo || !bins) return pfail(p, HM_EINVAL, "hm_pileup_site_histogram: bad argument");
+    SitePlanes s;
+    if (!site_planes(p, pcov, ncov, key, plane_base, s)) return HM_ESTATE;
+    if (hi == lo) return 0;
+    const int64_t nblk = (hi - lo + LOCI_PER_BLOCK - 1) / LOCI_PER_BLOCK;
+    if (nblk >= (int64_t(1) << 31)) return pfail(p, HM_EINVAL, "range too large: histogram per sequence");
+    return guarded(p, [&]() -> int64_t {
+        hipStream_t st = p->stream;
+        p->d_blk.reserve(4 * (size_t)nblk);
+        p->d_offs.reserve(8 * ((size_t)nblk + 1));
+        p->d_sbins.reserve(HM_SITE_BINS * sizeof(unsigned long long));
+        HIP_TRY(hipMemsetAsync(p->d_sbins.p, 0, HM_SITE_BINS * sizeof(unsigned long long), st));
+        // <= 512 workgroups of 48 KB LDS (two per CU), more only to keep a workgroup below 2^19 blocks = 2^31 loci (its LDS counters)
+        const int64_t grid = std::max(std::min<int64_t>(nblk, 512), (nblk + (int64_t(1) << 19) - 1) >> 19);
+        hipLaunchKernelGGL(sites_hist_kernel, dim3((unsigned)grid), dim3(TPB), 0, st, s.pc, s.nc, s.ky, lo, hi, nblk,
+                           p->d_sbins.as<unsigned long long>(), p->d_blk.as<int32_t>());
+        hipLaunchKernelGGL(loci_scan_kernel, dim3(1), dim3(1024), 0, st, p->d_blk.as<int32_t>(), (int)nblk, p->d_offs.as<int64_t>());
+        HIP_TRY(hipGetLastError());
+        int64_t n_big = 0;
+        HIP_TRY(hipMemcpyAsync(&n_big, p->d_offs.as<int64_t>() + nblk, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (n_big > cap || (n_big && !big)) return n_big;
+        std::vector<uint64_t> h((size_t)HM_SITE_BINS);
+        HIP_TRY(hipMemcpyAsync(h.data(), p->d_sbins.p, HM_SITE_BINS * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        if (n_big) {
+            p->d_sbig.reserve(sizeof(hm_locus_t) * (size_t)n_big);
+            hipLaunchKernelGGL(sites_big_write_kernel, dim3((unsigned)nblk), dim3(TPB), 0, st, s.pc, s.nc, s.ky, plane_base, lo, hi,
+                               p->d_offs.as<int64_t>(), p->d_sbig.as<hm_locus_t>());
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(big, p->d_sbig.p, sizeof(hm_locus_t) * (size_t)n_big, hipMemcpyDeviceToHost, st));
+        }
+        HIP_TRY(hipStreamSynchronize(st));
+        for (size_t i = 0; i < h.size(); ++i) bins[i] += h[i];
+        return n_big;
+    });
+}
+
+int hm_sites_table(const double rates[3], const uint64_t* bins, const hm_locus_t* big, int64_t n_big, double* ptab, double* qtab,
+                   double* big_p, double* big_q, uint64_t m[3]) {
+    if (!rates || !bins || !ptab || !qtab || !m || n_big < 0 || (n_big && (!big || !big_p || !big_q))) return HM_EINVAL;
+    for (int c = 0; c < 3; ++c)
+        if (!std::isnan(rates[c]) && !(rates[c] >= 0.0 && rates[c] <= 1.0)) return HM_EINVAL;
+    for (int t = 0; t < HM_SITE_BINS; ++t)
+        if (bins[t] && ((t & 255) > ((t >> 8) & 255) || ((t >> 8) & 255) == 0)) return HM_EINVAL;
+    for (int64_t i = 0; i < n_big; ++i)
+        if (big[i].motif > 2u || big[i].pcov < 0 || big[i].ncov < 0 || (int64_t)big[i].pcov + big[i].ncov < SITE_N) return HM_EINVAL;
+    const double nan = std::nan("");
+    std::fill(ptab, ptab + HM_SITE_BINS, nan);
+    std::fill(qtab, qtab + HM_SITE_BINS, nan);
+    std::fill(big_p, big_p + n_big, nan);
+    std::fill(big_q, big_q + n_big, nan);
+    struct Entry {      // the loci that share one p: a bin (where >= 0: its index) or one big locus (where < 0: ~index)
+        double p;
+        uint64_t loci;
+        int64_t where;
+    };
+    std::vector<Entry> ent;
+    for (int c = 0; c < 3; ++c) {
+        m[c] = std::accumulate(bins + c * SITE_N * SITE_N, bins + (c + 1) * SITE_N * SITE_N, uint64_t(0));
+        for (int64_t i = 0; i < n_big; ++i) m[c] += big[i].motif == (uint32_t)c;
+        const double e = rates[c];
+        if (std::isnan(e)) continue;
+        const double log_e = std::log(e), log1m_e = std::log1p(-e);
+        auto pvalue = [&](int64_t k, int64_t n) { return k == 0 || e == 1.0 ? 1.0 : e == 0.0 ? DBL_MIN : binomial_tail(k, n, log_e, log1m_e); };
+        ent.clear();
+        for (int n = 0; n < SITE_N; ++n)
+            for (int k = 0; k <= n; ++k) {
+                const int t = (c * SITE_N + n) * SITE_N + k;
+                ptab[t] = pvalue(k, n);
+                if (bins[t]) ent.push_back(Entry{ptab[t], bins[t], t});
+            }
+        for (int64_t i = 0; i < n_big; ++i) {
+            if (big[i].motif != (uint32_t)c) continue;
+            // an organelle's loci repeat their counts: the previous locus of the context with the same (k, n) has the value
+            const int64_t j = ent.empty() || ent.back().where >= 0 ? -1 : ~ent.back().where;
+            big_p[i] = j >= 0 && big[j].pcov == big[i].pcov && big[j].ncov == big[i].ncov
+                           ? big_p[j] : pvalue(big[i].pcov, (int64_t)big[i].pcov + big[i].ncov);
+            ent.push_back(Entry{big_p[i], 1, ~i});
+        }
+        std::sort(ent.begin(), ent.end(), [](const Entry& a, const Entry& b) { return a.p < b.p; });
+        // R below the distinct p (the loci with p <= it), then q from the largest p down
+        std::vector<uint64_t> R(ent.size());
+        uint64_t seen = 0;
+        for (size_t a = 0; a < ent.size();) {
+            size_t b = a;
+            while (b < ent.size() && ent[b].p == ent[a].p) seen += ent[b++].loci;
+            for (; a < b; ++a) R[a] = seen;
+        }
+        double q = 1.0;
+        for (size_t a = ent.size(); a-- > 0;) {
+            q = std::min(q, std::min(1.0, ent[a].p * (double)m[c] / (double)R[a]));
+            if (ent[a].where >= 0) qtab[ent[a].where] = q;
+            else big_q[~ent[a].where] = q;
+        }
+    }
+    return HM_OK;
+}
+
+int64_t hm_pileup_fetch_sites(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t plane_base, int64_t lo,
+                              int64_t hi, int32_t ctx_mask, const double* ptab, const double* qtab, const hm_locus_t* big,
+                              const double* big_p, const double* big_q, int64_t n_big, hm_site_t* out, int64_t cap) {
+    if (!p) return HM_EINVAL;
+    if (lo < 0 || hi < lo || !ptab || !qtab || n_big < 0 || (n_big && (!big || !big_p || !big_q)) || (ctx_mask & ~7))
+        return pfail(p, HM_EINVAL, "hm_pileup_fetch_sites: bad argument");
+    SitePlanes s;
+    if (!site_planes(p, pcov, ncov, key, plane_base, s)) return HM_ESTATE;
+    if (hi == lo) return 0;
+    const int64_t nblk = (hi - lo + LOCI_PER_BLOCK - 1) / LOCI_PER_BLOCK;
+    if (nblk >= (int64_t(1) << 31)) return pfail(p, HM_EINVAL, "range too large: fetch per sequence");
+    return guarded(p, [&]() -> int64_t {
+        hipStream_t st = p->stream;
+        p->d_blk.reserve(4 * (size_t)nblk);
+        p->d_offs.reserve(8 * ((size_t)nblk + 1));
+        hipLaunchKernelGGL(sites_count_kernel, dim3((unsigned)nblk), dim3(TPB), 0, st, s.pc, s.nc, s.ky, lo, hi, (uint32_t)ctx_mask,
+                           p->d_blk.as<int32_t>());
+        hipLaunchKernelGGL(loci_scan_kernel, dim3(1), dim3(1024), 0, st, p->d_blk.as<int32_t>(), (int)nblk, p->d_offs.as<int64_t>());
+        HIP_TRY(hipGetLastError());
+        int64_t total = 0;
+        HIP_TRY(hipMemcpyAsync(&total, p->d_offs.as<int64_t>() + nblk, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (total > cap || !out || total == 0) return total;
+        const size_t tab_bytes = HM_SITE_BINS * sizeof(double);
+        p->d_stab.reserve(2 * tab_bytes);
+        HIP_TRY(hipMemcpyAsync(p->d_stab.p, ptab, tab_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(p->d_stab.as<char>() + tab_bytes, qtab, tab_bytes, hipMemcpyHostToDevice, st));
+        if (n_big) {
+            p->d_sbig.reserve(sizeof(hm_locus_t) * (size_t)n_big);
+            p->d_sbigpq.reserve(2 * sizeof(double) * (size_t)n_big);
+            HIP_TRY(hipMemcpyAsync(p->d_sbig.p, big, sizeof(hm_locus_t) * (size_t)n_big, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(p->d_sbigpq.p, big_p, sizeof(double) * (size_t)n_big, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(p->d_sbigpq.as<double>() + n_big, big_q, sizeof(double) * (size_t)n_big, hipMemcpyHostToDevice, st));
+        }
+        p->d_sites.reserve(sizeof(hm_site_t) * (size_t)total);
+        hipLaunchKernelGGL(sites_write_kernel, dim3((unsigned)nblk), dim3(TPB), 0, st, s.pc, s.nc, s.ky, plane_base, lo, hi,
+                           (uint32_t)ctx_mask, p->d_stab.as<double>(), p->d_sbig.as<hm_locus_t>(), p->d_sbigpq.as<double>(), n_big,
+                           p->d_offs.as<int64_t>(), p->d_sites.as<hm_site_t>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(out, p->d_sites.p, sizeof(hm_site_t) * (size_t)total, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         return total;
     });

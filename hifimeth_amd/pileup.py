@@ -17,6 +17,12 @@ Allele-specific methylation (`pileup -H -A`): `pu.asm(min_cov=5)` are the loci w
 counted calls, with the difference of the two methylation percentages and the two-sided Fisher exact p-value of
 [[pcov1, ncov1], [pcov2, ncov2]], both computed on the device; `pu.asm_bed(rows)` is the text of <prefix>.asm.<ctx>.bed.
 
+Binomial test per locus (`pileup -B control` / `-e r,r,r`): is a locus methylated at all, against the caller's false-positive
+rate?  `pu.control_sums(lo, hi)` over an unmethylated control sequence gives the rates (`rates_from_sums`), `pu.site_histogram()`
+counts the loci per (motif, pcov, pcov + ncov), `sites_table(rates, bins, big)` -- host only, the C library's -- solves p-values
+and Benjamini-Hochberg q-values for every triple, `pu.sites(table)` are the rows and `pu.sites_bed(rows)` the text of
+<prefix>.sites.<ctx>.bed; `sites_rates_tsv` is <prefix>.sites.rates.tsv.
+
 Fused with the caller (`pileup -K`): `pu.add_called(read, calls)` takes the records `MethylationCaller` returned for an aligned read
 instead of parsed MM / ML -- the same effect as add() of that read carrying the calls as tags, without the tag text.
 
@@ -39,6 +45,9 @@ MOD_DTYPE = np.dtype([("qoff", "<i4"), ("strand", "u1"), ("unmod_base", "S1"), (
 LOCUS_DTYPE = np.dtype([("gpos", "<i8"), ("pcov", "<i4"), ("ncov", "<i4"), ("motif", "<u4"), ("reserved", "<u4")])
 ASM_DTYPE = np.dtype([("gpos", "<i8"), ("pcov1", "<i4"), ("ncov1", "<i4"), ("pcov2", "<i4"), ("ncov2", "<i4"), ("motif", "<u4"),
                       ("reserved", "<u4"), ("diff", "<f8"), ("pvalue", "<f8")])     # hm_asm_t, 48 bytes
+SITE_DTYPE = np.dtype([("gpos", "<i8"), ("pcov", "<i4"), ("ncov", "<i4"), ("motif", "<u4"), ("reserved", "<u4"), ("pvalue", "<f8"),
+                       ("qvalue", "<f8")])                                            # hm_site_t, 40 bytes
+SITE_BINS = 3 * 256 * 256                                                             # HM_SITE_BINS
 CTX_NAMES = ("CpG", "CHG", "CHH")
 _CHEBI = {27551: "m", 76792: "h", 76794: "f", 76793: "c", 16964: "g", 80961: "e", 17477: "b", 28871: "a",
           44605: "o", 18107: "n"}
@@ -95,6 +104,64 @@ def resolve_threshold(bins) -> Tuple[int, int]:
     w = a[st:en]
     total = int(w.sum())
     return (128 if total < 10000 else st + int(np.argmin(w))), total
+
+
+def parse_rates(text: str) -> List[float]:
+    """the argument of -e: three decimals in [0, 1] or `nan` (context not tested), comma-separated; ValueError otherwise"""
+    import re
+    parts = text.split(",")
+    if len(parts) != 3:
+        raise ValueError("three comma-separated rates expected (CpG,CHG,CHH)")
+    out = []
+    for t in parts:
+        if t == "nan":
+            out.append(float("nan"))
+        elif re.fullmatch(r"(\d+\.?\d*|\.\d+)([eE][+-]?\d+)?", t) and 0.0 <= float(t) <= 1.0:
+            out.append(float(t))
+        else:
+            raise ValueError(f"rate {t!r} is neither a decimal in [0, 1] nor nan")
+    return out
+
+
+def rates_from_sums(sums) -> List[float]:
+    """sums = (P_cpg, P_chg, P_chh, N_cpg, N_chg, N_chh) of the control sequence -> e_c = P_c / (P_c + N_c), NaN without calls"""
+    s = [int(x) for x in sums]
+    return [float(s[c]) / float(s[c] + s[3 + c]) if s[c] + s[3 + c] else float("nan") for c in range(3)]
+
+
+class SitesTable:
+    """what hm_sites_table returns: ptab / qtab [3, 256, 256] indexed [motif, n, k], the big loci (n >= 256) with big_p / big_q,
+    m[3] = loci per context, and the rates it was solved for"""
+    def __init__(self, rates, ptab, qtab, big, big_p, big_q, m):
+        self.rates, self.ptab, self.qtab, self.big, self.big_p, self.big_q, self.m = rates, ptab, qtab, big, big_p, big_q, m
+
+    @property
+    def ctx_mask(self) -> int:
+        return sum(1 << c for c in range(3) if not np.isnan(self.rates[c]))
+
+
+def sites_table(rates, bins: np.ndarray, big: Optional[np.ndarray] = None) -> SitesTable:
+    """p-values and BH q-values of every (motif, pcov, pcov + ncov), by the C library (host only: no GPU is needed).
+    bins: uint64 [3, 256, 256] (or flat) from site_histogram, summed over the job; big: its LOCUS_DTYPE list, ascending."""
+    L = lib()
+    r = np.ascontiguousarray(rates, np.float64)
+    b = np.ascontiguousarray(bins, np.uint64).reshape(-1)
+    big = np.zeros(0, LOCUS_DTYPE) if big is None else np.ascontiguousarray(big, LOCUS_DTYPE)
+    if r.shape != (3,) or b.size != SITE_BINS:
+        raise HifimethError("sites_table: three rates and 3 x 256 x 256 bins expected")
+    ptab, qtab = np.empty(SITE_BINS, np.float64), np.empty(SITE_BINS, np.float64)
+    big_p, big_q = np.empty(len(big), np.float64), np.empty(len(big), np.float64)
+    m = np.zeros(3, np.uint64)
+    if L.hm_sites_table(*(x.ctypes.data_as(C.c_void_p) for x in (r, b, big)), len(big),
+                        *(x.ctypes.data_as(C.c_void_p) for x in (ptab, qtab, big_p, big_q, m))) != 0:
+        raise HifimethError("hm_sites_table: a rate outside [0, 1], or bins / big loci that are no counts")
+    return SitesTable(r, ptab.reshape(3, 256, 256), qtab.reshape(3, 256, 256), big, big_p, big_q, m)
+
+
+def sites_rates_tsv(sums, rates, m) -> str:
+    """the text of <prefix>.sites.rates.tsv: ctx, P_c, N_c, rate, m_c (the counts are 0 when the rates were given with -e)"""
+    return "".join("%s\t%d\t%d\t%s\t%d\n" % (CTX_NAMES[c], int(sums[c]), int(sums[3 + c]),
+                                             "nan" if np.isnan(rates[c]) else "%.17g" % rates[c], int(m[c])) for c in range(3))
 
 
 class MethylationPileup:
@@ -265,6 +332,53 @@ class MethylationPileup:
         for s, k, r in zip(sid, soff, rows):
             text[CTX_NAMES[int(r["motif"])]].append("%s\t%d\t%d\t%g\t%.6g\t%d\t%d\t%d\t%d\n" % (
                 self.names[s], k, k + 1, r["diff"], r["pvalue"], r["pcov1"], r["ncov1"], r["pcov2"], r["ncov2"]))
+        return {k: "".join(v) for k, v in text.items()}
+
+    def _plane_ptrs(self, planes):
+        return [None, None, None] if planes is None else [C.c_void_p(t.data_ptr()) for t in planes]
+
+    def control_sums(self, lo: int, hi: int, planes=None) -> np.ndarray:
+        """(P_cpg, P_chg, P_chh, N_cpg, N_chg, N_chh): pcov and ncov summed per context over the covered loci of [lo, hi) (plane
+        coordinates) -- the control sequence's range, or a rank's part of it"""
+        s = np.zeros(6, np.uint64)
+        self._check(self._L.hm_pileup_control_sums(self._h, *self._plane_ptrs(planes), lo, hi, s.ctypes.data_as(C.c_void_p)))
+        return s
+
+    def site_histogram(self, lo: int = 0, hi: Optional[int] = None, planes=None, plane_base: int = 0, bins: Optional[np.ndarray] = None):
+        """-> (bins, big): bins[motif, n, k] (uint64 [3, 256, 256]; added into `bins` when given) = covered loci of [lo, hi) with
+        pcov = k, pcov + ncov = n < 256; big = the loci with n >= 256, ascending (LOCUS_DTYPE)"""
+        hi = self.n_loci if hi is None else hi
+        bins = np.zeros((3, 256, 256), np.uint64) if bins is None else bins
+        assert bins.dtype == np.uint64 and bins.size == SITE_BINS and bins.flags.c_contiguous
+        ptrs, pb = self._plane_ptrs(planes), bins.ctypes.data_as(C.c_void_p)
+        big = np.zeros(0, LOCUS_DTYPE)
+        n = self._check(self._L.hm_pileup_site_histogram(self._h, *ptrs, plane_base, lo, hi, pb, None, 0))
+        if n:                                     # nothing was added: again, with room for the list
+            big = np.zeros(n, LOCUS_DTYPE)
+            self._check(self._L.hm_pileup_site_histogram(self._h, *ptrs, plane_base, lo, hi, pb, big.ctypes.data_as(C.c_void_p), n))
+        return bins, big
+
+    def sites(self, table: SitesTable, lo: int = 0, hi: Optional[int] = None, planes=None, plane_base: int = 0) -> np.ndarray:
+        """rows of [lo, hi) (plane coordinates), ascending: the covered loci of the contexts `table` tests, pvalue / qvalue looked
+        up in it on the device"""
+        hi = self.n_loci if hi is None else hi
+        args = (*self._plane_ptrs(planes), plane_base, lo, hi, table.ctx_mask,
+                *(x.ctypes.data_as(C.c_void_p) for x in (table.ptab, table.qtab, table.big, table.big_p, table.big_q)), len(table.big))
+        n = self._check(self._L.hm_pileup_fetch_sites(self._h, *args, None, 0))
+        out = np.zeros(n, SITE_DTYPE)
+        if n:
+            self._check(self._L.hm_pileup_fetch_sites(self._h, *args, out.ctypes.data_as(C.c_void_p), n))
+        return out
+
+    def sites_bed(self, rows: np.ndarray) -> dict:
+        """the text of <prefix>.sites.{CpG,CHG,CHH}.bed: the six columns of the cov.bed row, then pvalue and qvalue"""
+        sid = np.searchsorted(self.offsets, rows["gpos"], side="right") - 1
+        soff = rows["gpos"] - self.offsets[sid]
+        text = {k: [] for k in CTX_NAMES}
+        for s, k, r in zip(sid, soff, rows):
+            p, n = int(r["pcov"]), int(r["ncov"])
+            text[CTX_NAMES[int(r["motif"])]].append("%s\t%d\t%d\t%g\t%d\t%d\t%.6g\t%.6g\n" % (
+                self.names[s], k, k + 1, 100.0 * p / (p + n), p, n, r["pvalue"], r["qvalue"]))
         return {k: "".join(v) for k, v in text.items()}
 
 

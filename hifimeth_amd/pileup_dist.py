@@ -1,7 +1,7 @@
 """`hifimeth pileup` over N GPUs of one node, one process per GPU (the path's only exchange step).
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
-        -m hifimeth_amd.pileup_dist [-q mapQ] [-f identity] [-H [-A [-a min-cov]]] reference.fa mod.bam output-prefix
+        -m hifimeth_amd.pileup_dist [-q mapQ] [-f identity] [-H [-A [-a min-cov]]] [-B control | -e r,r,r] reference.fa mod.bam output-prefix
 
 Records are dealt to the ranks in slabs of `--slab` records (round-robin, like the `call` path).  Each rank projects its
 records and histograms them on its own GPU; then
@@ -15,6 +15,10 @@ A single process (no torchrun) runs the same code with the collectives skipped.
 with SUM next to the three above, and rank 0 also writes <prefix>.hap1.<ctx>.cov.bed / <prefix>.hap2.<ctx>.cov.bed.
 -A (with -H): every rank tests its own chunk of the reduce-scattered haplotype planes (hm_pileup_fetch_asm, plane_base = the
 chunk's first locus) and rank 0 also writes <prefix>.asm.<ctx>.bed; no further collective.
+-B control / -e rates: the per-locus binomial test.  After step 3 every rank sums the control sequence's part of its chunk
+(all-reduce of 6 int64 -> the same rates everywhere), histograms its chunk per (motif, pcov, pcov + ncov) (all-reduce of
+196 608 int64; the few loci beyond the histogram by all_gather_object), solves the same table (hm_sites_table) and writes its
+chunk's rows by lookup; rank 0 also writes <prefix>.sites.<ctx>.bed and <prefix>.sites.rates.tsv.  No p-value crosses ranks.
 """
 from __future__ import annotations
 
@@ -26,13 +30,13 @@ import numpy as np
 
 from . import dist as D
 from .bamio import is_coordinate_sorted, load_fasta, read_bam
-from .pileup import (CTX_NAMES, MethylationPileup, allreduce_histograms, locus_ranges, reduce_scatter_planes, reduce_scatter_sum,
-                     resolve_threshold)
+from .pileup import (CTX_NAMES, LOCUS_DTYPE, MethylationPileup, allreduce_histograms, locus_ranges, parse_rates, rates_from_sums,
+                     reduce_scatter_planes, reduce_scatter_sum, resolve_threshold, sites_rates_tsv, sites_table)
 
 
 def run(reference: str, bam: str, prefix: str, min_mapq: int = 0, min_pi: float = 0.0, slab: int = 256,
         batch: int = 256, backend: str | None = None, log=sys.stderr, haplotypes: bool = False, asm: bool = False,
-        asm_min_cov: int = 5):
+        asm_min_cov: int = 5, control: str | None = None, rates=None):
     import torch
     rank, local_rank, world = D.env_world()
     dist = D.init_process_group(backend, force=bool(os.environ.get("HM_FORCE_COLLECTIVES")))
@@ -53,6 +57,10 @@ def run(reference: str, bam: str, prefix: str, min_mapq: int = 0, min_pi: float 
         return leave(1)                                      # every rank sees the same header: all leave together
     genome = load_fasta(reference)
     sid_of = {n: i for i, (n, _) in enumerate(genome)}
+    if control is not None and control not in sid_of:       # every rank reads the same FASTA: all leave together, before the device
+        if rank == 0:
+            print(f"ERROR: control sequence {control} (-B) is not in {reference}", file=log)
+        return leave(1)
     missing = None
     n_loci = sum(len(s) for _, s in genome)
     ranges = locus_ranges(n_loci, world)
@@ -118,6 +126,38 @@ def run(reference: str, bam: str, prefix: str, min_mapq: int = 0, min_pi: float 
         part[f"hap{k + 1}."] = pu.bed(pu.loci(0, hi - lo, planes=(hp[2 * k], hp[2 * k + 1], key), plane_base=base))
     if asm:                                                 # the two partitions' chunks and the key's lie on the same range
         part["asm."] = pu.asm_bed(pu.asm(0, hi - lo, asm_min_cov, planes=(*hp, key), plane_base=base))
+    if control is not None or rates is not None:
+        mine, n_mine = (pc, nc, key), hi - lo               # this rank's chunk: element 0 is locus `base`
+        where = "cpu" if dist is not None and not on_gpu else dev
+
+        def allreduce_i64(a):
+            if dist is None:
+                return a
+            t = torch.from_numpy(a.astype(np.int64).reshape(-1)).to(where)
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+            return t.cpu().numpy().astype(np.uint64).reshape(a.shape)
+
+        sums = np.zeros(6, np.uint64)
+        if control is not None:
+            c0 = int(pu.offsets[sid_of[control]])
+            c1 = c0 + len(genome[sid_of[control]][1])
+            a, b = min(max(c0 - base, 0), n_mine), min(max(c1 - base, 0), n_mine)
+            sums = allreduce_i64(pu.control_sums(a, b, planes=mine) if a < b else sums)
+            rates = rates_from_sums(sums)
+        bins, big = pu.site_histogram(0, n_mine, planes=mine, plane_base=base)
+        bins = allreduce_i64(bins)
+        if dist is not None:
+            bigs = [None] * world
+            dist.all_gather_object(bigs, big)
+            big = np.concatenate(bigs).astype(LOCUS_DTYPE)  # rank order = locus order
+        table = sites_table(rates, bins, big)
+        part["sites."] = pu.sites_bed(pu.sites(table, 0, n_mine, planes=mine, plane_base=base))
+        if rank == 0:
+            for c in range(3):
+                print(f"WARNING: {CTX_NAMES[c]} is not tested: no rate" if np.isnan(rates[c])
+                      else f"{CTX_NAMES[c]} false-positive rate: {rates[c]:.17g}", file=log)
+            with open(f"{prefix}.sites.rates.tsv", "w") as f:
+                f.write(sites_rates_tsv(sums, rates, table.m))
     if dist is not None:
         parts = [None] * world if rank == 0 else None
         dist.gather_object(part, parts, dst=0)
@@ -126,7 +166,7 @@ def run(reference: str, bam: str, prefix: str, min_mapq: int = 0, min_pi: float 
     if rank == 0:
         for tag in parts[0]:
             for c in CTX_NAMES:
-                with open(f"{prefix}.{tag}{c}" + (".bed" if tag == "asm." else ".cov.bed"), "w") as f:
+                with open(f"{prefix}.{tag}{c}" + (".bed" if tag in ("asm.", "sites.") else ".cov.bed"), "w") as f:
                     for p in parts:
                         f.write(p[tag][c])
     pu.close()
@@ -147,6 +187,11 @@ def main(argv=None):
     ap.add_argument("-A", dest="asm", action="store_true",
                     help="with -H: per-locus haplotype difference + Fisher exact test -> <prefix>.asm.<ctx>.bed")
     ap.add_argument("-a", dest="asm_min_cov", type=int, default=None, help="with -A: minimum coverage of each haplotype (default 5)")
+    ap.add_argument("-B", dest="control", default=None, metavar="NAME",
+                    help="per-locus binomial test against the false-positive rates measured on this unmethylated control sequence "
+                         "-> <prefix>.sites.<ctx>.bed, <prefix>.sites.rates.tsv")
+    ap.add_argument("-e", dest="rates", default=None, metavar="R,R,R",
+                    help="instead of -B: the three rates (CpG,CHG,CHH), each a decimal in [0, 1] or nan (context not tested)")
     ap.add_argument("reference")
     ap.add_argument("mod_bam")
     ap.add_argument("output_prefix")
@@ -157,8 +202,16 @@ def main(argv=None):
         ap.error("-a needs -A")
     if a.asm_min_cov is not None and a.asm_min_cov < 1:
         ap.error("-a must be >= 1")
+    if a.control is not None and a.rates is not None:
+        ap.error("-B and -e exclude each other")
+    rates = None
+    if a.rates is not None:
+        try:
+            rates = parse_rates(a.rates)
+        except ValueError as e:
+            ap.error(f"-e: {e}")
     return run(a.reference, a.mod_bam, a.output_prefix, a.q, a.f, slab=a.slab, backend=a.backend, haplotypes=a.haplotypes,
-               asm=a.asm, asm_min_cov=5 if a.asm_min_cov is None else a.asm_min_cov)
+               asm=a.asm, asm_min_cov=5 if a.asm_min_cov is None else a.asm_min_cov, control=a.control, rates=rates)
 
 
 if __name__ == "__main__":

@@ -317,6 +317,54 @@ int64_t hm_pileup_fetch_asm(hm_pileup_t* p, const void* pcov1, const void* ncov1
                             const void* key, int64_t plane_base, int64_t lo, int64_t hi, int32_t min_cov,
                             hm_asm_t* out, int64_t cap);
 
+/* ---- per-locus binomial test (`pileup -B / -e`): is a locus methylated at all ------------------------
+ * Against a false-positive rate e per context -- given, or measured on an unmethylated control sequence as sum(pcov) /
+ * sum(pcov + ncov) -- a covered locus with k = pcov, n = pcov + ncov gets p = P(X >= k), X ~ Binomial(n, e), and the
+ * Benjamini-Hochberg q of that p among all covered loci of its context.  p and q are functions of (motif, k, n) alone, so the
+ * device counts loci per triple (hm_pileup_site_histogram), the host solves the table once (hm_sites_table) and the device
+ * writes the rows by lookup (hm_pileup_fetch_sites); no p-value is sorted or exchanged.
+ * In the three device calls the planes follow hm_pileup_fetch_loci: all of pcov / ncov / key NULL = the engine's own combined
+ * planes (plane_base is then 0), else DEVICE pointers whose element 0 is locus plane_base; [lo, hi) in plane coordinates.  A
+ * locus takes part when pcov >= 0, ncov >= 0 and pcov + ncov > 0 (a negative value in caller-owned planes is no count: such a
+ * locus is skipped); its context is min(key & 3, 2), the file the BED writers put it in. */
+typedef struct {            /* one row of <prefix>.sites.<ctx>.bed; 40 bytes */
+    int64_t gpos;
+    int32_t pcov, ncov;
+    uint32_t motif, reserved;
+    double pvalue, qvalue;
+} hm_site_t;
+#define HM_SITE_BINS 196608 /* 3 x 256 x 256: index (motif * 256 + n) * 256 + k, for n < 256 */
+/* sums[c] = sum of pcov, sums[3 + c] = sum of ncov over the loci of context c in planes[lo, hi) (the control sequence, or a
+ * rank's part of it); exact.  There is no plane_base: nothing positional is returned. */
+int hm_pileup_control_sums(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t lo, int64_t hi,
+                           uint64_t sums[6]);
+/* ADDS the loci of planes[lo, hi) with n < 256 into the caller's bins[HM_SITE_BINS] and writes those with n >= 256 (an organelle
+ * at thousands-fold coverage) to big[] in ascending order.  Returns the number of big loci; when that exceeds cap, or big is
+ * NULL while there are some, nothing is written and nothing is added.  hi == lo returns 0. */
+int64_t hm_pileup_site_histogram(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t plane_base,
+                                 int64_t lo, int64_t hi, uint64_t* bins, hm_locus_t* big, int64_t cap);
+/* The test and the q-values, host only (no device is touched): the one implementation behind every front end.
+ * rates[c] in [0, 1], or NaN = context c is not tested.  bins / big: what hm_pileup_site_histogram gave, summed / concatenated
+ * over the job.  For every (c, n, k) with k <= n < 256 of a tested context ptab[(c * 256 + n) * 256 + k] is
+ *   1.0 if k == 0 or e == 1;  DBL_MIN if e == 0 (and k > 0);  else the sum over x = k .. n, ascending, in fp64, of
+ *   exp(((lf(n) - lf(x)) - lf(n - x)) + (x * log(e) + (n - x) * log1p(-e))),  lf(j) = lgamma(j + 1) of the host's libm,
+ * clamped to [DBL_MIN, 1] (never 0, as hm_asm_t::pvalue); every other entry of ptab is NaN.  big_p[i] is the same for big[i].
+ * m[c] = number of loci of context c (bins + big).  q (R's p.adjust(method = "BH") within the context): over the distinct p in
+ * ascending order, R = number of loci with p <= this one, q = min over this and all larger p of min(1, p * (double)m / (double)R);
+ * qtab is filled where the bin is not empty (NaN elsewhere), big_q[i] for every big locus of a tested context (NaN otherwise).
+ * HM_EINVAL for a rate outside [0, 1], a non-empty bin with k > n or n == 0, a big locus with motif > 2, negative counts or
+ * n < 256. */
+int hm_sites_table(const double rates[3], const uint64_t* bins, const hm_locus_t* big, int64_t n_big, double* ptab,
+                   double* qtab, double* big_p, double* big_q, uint64_t m[3]);
+/* rows of planes[lo, hi) in ascending order: the loci above whose context has bit `motif` set in ctx_mask (the tested contexts),
+ * pvalue / qvalue from ptab / qtab[HM_SITE_BINS] for n < 256, else from big_p / big_q at the locus' place in big[0, n_big) --
+ * the job-wide list, ascending in gpos; NaN if it is not there.  Returns the number of rows (may exceed cap: then nothing is
+ * written). */
+int64_t hm_pileup_fetch_sites(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t plane_base,
+                              int64_t lo, int64_t hi, int32_t ctx_mask, const double* ptab, const double* qtab,
+                              const hm_locus_t* big, const double* big_p, const double* big_q, int64_t n_big,
+                              hm_site_t* out, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,8 +8,9 @@ compaction at the end.  Prints one JSON object; `--check` verifies that the per-
 `--partitions`: the haplotype-resolved engine (`pileup -H`), every read tagged with a random HP of {none, 1, 2}; the loci
 fetch then also compacts the two partitions' planes.
 `--asm` (with `--partitions`): the allele-specific test of `pileup -H -A` over the counted planes: select + Fisher test + D2H per pass.
+`--sites`: the binomial test of `pileup -B / -e` over the counted planes: histogram + table + rows (D2H included) per pass.
 
-    python tools/pileup_bench.py --genome-mb 20 --coverage 10 [--partitions [--asm]]
+    python tools/pileup_bench.py --genome-mb 20 --coverage 10 [--partitions [--asm]] [--sites]
 """
 import argparse
 import ctypes as C
@@ -86,6 +87,8 @@ def main():
     ap.add_argument("--partitions", action="store_true", help="haplotype partitions on, reads tagged with random HP")
     ap.add_argument("--asm", action="store_true", help="with --partitions: time the per-locus haplotype test (pileup -H -A)")
     ap.add_argument("--asm-min-cov", type=int, default=5)
+    ap.add_argument("--sites", action="store_true", help="time the per-locus binomial test (pileup -B / -e)")
+    ap.add_argument("--sites-rate", type=float, default=0.013, help="with --sites: the false-positive rate of all three contexts")
     ap.add_argument("--cpu-baseline", action="store_true",
                     help="time the reference's own projection code (oracle/_ref/ref_align -t) on a bounded sample")
     a = ap.parse_args()
@@ -173,6 +176,28 @@ def main():
                    asm_count_only_s=round(t_sel, 4), asm_rows_per_s=round(len(rows) / t_asm),
                    asm_mean_tables_per_row=round(float(steps.mean()), 1) if len(rows) else 0.0,
                    asm_share_of_pass=round(t_asm / (t_project / a.repeat + t_count / a.repeat + t_loci + t_hp_loci + t_asm), 4))
+    if a.sites:                                    # histogram, table (host), rows of every covered locus, as the CLI does
+        from hifimeth_amd.pileup import sites_table
+        pu.sites(sites_table([a.sites_rate] * 3, *pu.site_histogram()))    # warm-up: buffers, the log n! table
+        t_hist = t_tab = t_rows = 0.0
+        for _ in range(a.repeat):
+            t0 = time.perf_counter()
+            bins, big = pu.site_histogram()
+            t1 = time.perf_counter()
+            table = sites_table([a.sites_rate] * 3, bins, big)
+            t2 = time.perf_counter()
+            rows = pu.sites(table)
+            t_hist, t_tab, t_rows = t_hist + t1 - t0, t_tab + t2 - t1, t_rows + time.perf_counter() - t2
+        t_sites = (t_hist + t_tab + t_rows) / a.repeat
+        t_pass = t_project / a.repeat + t_count / a.repeat + t_loci
+        out.update(sites_rate=a.sites_rate, sites_rows=int(len(rows)), sites_big_loci=int(len(big)), sites_triples=int((bins > 0).sum()),
+                   sites_histogram_s=round(t_hist / a.repeat, 4), sites_table_s=round(t_tab / a.repeat, 4),
+                   sites_rows_s=round(t_rows / a.repeat, 4), sites_s_per_pass=round(t_sites, 4),
+                   sites_loci_per_s=round(len(rows) / t_sites) if t_sites else 0,
+                   sites_share_of_pass=round(t_sites / (t_pass + t_sites), 4))
+        if a.check:
+            out["check_sites_rows_are_the_loci"] = bool(len(rows) == len(loci) and (rows["gpos"] == loci["gpos"]).all()
+                                                        and int(bins.sum()) + len(big) == len(loci))
     if a.check:                                    # every pass (and the warm-up) adds the same records
         total = int((loci["pcov"].astype(np.int64) + loci["ncov"]).sum())
         out["check_total_records"] = total == recs_per_pass * (a.repeat + 1)
