@@ -7,6 +7,10 @@ GPU box never needs the reference.  Three sources, each the reference's own code
   scan.json      site lists from the reference's C++ scanner, compiled from its sources by
                  oracle/ref_build (-> oracle/_ref/ref_scan):
                  src/app/hifimeth/eval_kmer_features.cpp:67-126, src/corelib/bam_info.cpp:169-222
+  scan_edges.json
+                 the same scanner (ref_scan) on the hand-built reads of tests/scan_cases.py: motifs across the thread, wave and
+                 first chunk boundaries, and reads cut at every l_qseq % 4; `python tools/make_golden.py <reference> scan_edges`
+                 makes only this one
   windows.npz    401x8 windows from the reference's Python training-time assembler
                  training/sample_dataset.py:84-139 (imported, not copied)
   cnn_<ctx>.npz  logits of the reference's shipped TorchScript models models/CpG.pt, CHH.pt
@@ -63,6 +67,23 @@ def make_scan():
     js = [dict(flag=f, seq=s, **d) for (f, s), d in zip(recs, out)]
     json.dump(js, open(os.path.join(GOLD, "scan.json"), "w"))
     print(f"scan.json: {len(js)} records, {sum(len(d['cpg']) + len(d['chg']) + len(d['chh']) for d in js)} sites")
+
+
+def make_scan_edges():
+    """scan_edges.json: the reference's own scanner (oracle/_ref/ref_scan, as for scan.json) on scan_cases.golden_records():
+    the boundary_motifs() reads at the boundaries up to 1020, cut a few bases behind the boundary (what follows is site-free
+    background; the four longest boundaries are left out, for the file's size), and tail_lengths().  Same keys as scan.json, plus
+    the read's name."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import scan_cases
+    recs = scan_cases.golden_records()
+    out = O.ref_scan([(f, s) for _n, f, s in recs])
+    rows = [dict(name=n, flag=f, seq=s, cpg=d["cpg"], chg=d["chg"], chh=d["chh"]) for (n, f, s), d in zip(recs, out)]
+    path = os.path.join(GOLD, "scan_edges.json")
+    with open(path, "w") as f:     # one record per line, so that a change of one read is one line of a diff
+        f.write("[\n" + ",\n".join(json.dumps(r, separators=(",", ":")) for r in rows) + "\n]\n")
+    print(f"scan_edges.json: {len(rows)} records, {sum(len(d['cpg']) + len(d['chg']) + len(d['chh']) for d in rows)} sites, "
+          f"{os.path.getsize(path)} bytes")
 
 
 def make_windows():
@@ -682,6 +703,9 @@ if __name__ == "__main__":
         make_align_edges()
         make_modparse_edges()
         raise SystemExit(0)
+    if len(sys.argv) > 2 and sys.argv[2] == "scan_edges":  # only the scanner's edge fixture (tests/scan_cases.py)
+        make_scan_edges()
+        raise SystemExit(0)
     if len(sys.argv) > 2 and sys.argv[2] == "helpers":   # only the cov2bed / corr fixtures
         make_helpers()
         raise SystemExit(0)
@@ -704,6 +728,7 @@ if __name__ == "__main__":
         make_cnn_chg(np.load(os.path.join(GOLD, "cnn_CpG.npz"))["windows"])
         raise SystemExit(0)
     make_scan()
+    make_scan_edges()
     w = make_windows()
     make_cnn(w)
     make_cnn_chg(w)
