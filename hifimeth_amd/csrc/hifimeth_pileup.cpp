@@ -723,36 +723,36 @@ void report_thresholds(const uint64_t* bins, uint8_t thr[3]) {
 }  // namespace
 
 namespace {
-// rows of the three <prefix>.<ctx>.cov.bed files (pileup.cpp:562-590) from planes (pcov, ncov, key): all NULL = the
-// engine's own combined planes, else DEVICE planes over the whole concatenated reference.  The context of a row is the
-// key's motif.  false on an engine error (hm_pileup_last_error).
-bool write_bed(hm_pileup_t* pe, const Fasta& fa, const void* pcov, const void* ncov, const void* key, FILE* out[3], int threads) {
-    std::vector<hm_locus_t> loci;
+// The rows of three per-context BED files, sequence by sequence.  fetch(lo, hi, dst, cap) is the engine's row fetch over the
+// plane range of one sequence (dst NULL: the number of rows only); format(row, k, buf) prints the columns behind the sequence
+// name of a row at offset k and returns their length; the file of a row is its motif.  Rows are formatted by `threads` workers
+// over contiguous slices and written slice by slice (pileup.cpp:562-590).  false on an engine error (hm_pileup_last_error).
+template <class Row, class Fetch, class Format>
+bool write_rows(const Fasta& fa, FILE* const out[3], int threads, Fetch fetch, Format format) {
+    std::vector<Row> rows;
     const int fmt_threads = std::max(1, threads);
     std::vector<std::string> text((size_t)fmt_threads * 3);
     int64_t off = 0;
     for (size_t s = 0; s < fa.names.size(); ++s) {
         const int64_t lo = off, hi = off + fa.length[s];
         off = hi;
-        int64_t n = hm_pileup_fetch_loci(pe, pcov, ncov, key, 0, lo, hi, nullptr, 0);
+        int64_t n = fetch(lo, hi, static_cast<Row*>(nullptr), 0);
+        if (n > 0) {
+            rows.resize((size_t)n);
+            n = fetch(lo, hi, rows.data(), n);
+        }
         if (n < 0) return false;
         if (n == 0) continue;
-        loci.resize((size_t)n);
-        n = hm_pileup_fetch_loci(pe, pcov, ncov, key, 0, lo, hi, loci.data(), n);
-        if (n < 0) return false;
-        // rows are formatted by `fmt_threads` workers over contiguous slices and written slice by slice (pileup.cpp:562-590)
         parallel_run(fmt_threads, fmt_threads, [&](int w) {
             for (int c = 0; c < 3; ++c) text[(size_t)w * 3 + c].clear();
             const size_t a = (size_t)n * w / fmt_threads, b = (size_t)n * (w + 1) / fmt_threads;
-            char row[256];
+            char buf[320];
             for (size_t i = a; i < b; ++i) {
-                const hm_locus_t& l = loci[i];
-                const int64_t k = l.gpos - lo;
-                const double freq = 100.0 * l.pcov / (l.pcov + l.ncov);
-                const int len = snprintf(row, sizeof row, "\t%lld\t%lld\t%g\t%d\t%d\n", (long long)k, (long long)k + 1, freq, l.pcov, l.ncov);
-                std::string& t = text[(size_t)w * 3 + (l.motif < 3 ? l.motif : 2)];
+                const Row& r = rows[i];
+                const int len = format(r, r.gpos - lo, buf);
+                std::string& t = text[(size_t)w * 3 + (r.motif < 3 ? r.motif : 2)];
                 t += fa.names[s];
-                t.append(row, (size_t)len);
+                t.append(buf, (size_t)len);
             }
         });
         for (int c = 0; c < 3; ++c)
@@ -764,36 +764,31 @@ bool write_bed(hm_pileup_t* pe, const Fasta& fa, const void* pcov, const void* n
     return true;
 }
 
-// rows of the three <prefix>.asm.<ctx>.bed files from the engine's own partition and key planes, fetched per sequence like the
-// rows above (48 B per tested row on the device and here).  false on an engine error.
-bool write_asm(hm_pileup_t* pe, const Fasta& fa, int min_cov, FILE* out[3]) {
-    std::vector<hm_asm_t> rows;
-    std::string text[3];
-    int64_t off = 0;
-    for (size_t s = 0; s < fa.names.size(); ++s) {
-        const int64_t lo = off, hi = off + fa.length[s];
-        off = hi;
-        int64_t n = hm_pileup_fetch_asm(pe, nullptr, nullptr, nullptr, nullptr, nullptr, 0, lo, hi, min_cov, nullptr, 0);
-        if (n < 0) return false;
-        if (n == 0) continue;
-        rows.resize((size_t)n);
-        n = hm_pileup_fetch_asm(pe, nullptr, nullptr, nullptr, nullptr, nullptr, 0, lo, hi, min_cov, rows.data(), n);
-        if (n < 0) return false;
-        for (std::string& t : text) t.clear();
-        char row[256];
-        for (int64_t i = 0; i < n; ++i) {
-            const hm_asm_t& r = rows[(size_t)i];
-            const int64_t k = r.gpos - lo;
-            const int len = snprintf(row, sizeof row, "\t%lld\t%lld\t%g\t%.6g\t%d\t%d\t%d\t%d\n", (long long)k, (long long)k + 1, r.diff,
-                                     r.pvalue, r.pcov1, r.ncov1, r.pcov2, r.ncov2);
-            std::string& t = text[r.motif < 3 ? r.motif : 2];
-            t += fa.names[s];
-            t.append(row, (size_t)len);
-        }
-        for (int c = 0; c < 3; ++c)
-            if (!text[c].empty()) fwrite(text[c].data(), 1, text[c].size(), out[c]);
-    }
-    return true;
+// rows of the three <prefix>.<ctx>.cov.bed files (pileup.cpp:562-590) from planes (pcov, ncov, key): all NULL = the
+// engine's own combined planes, else DEVICE planes over the whole concatenated reference.  The context of a row is the
+// key's motif.  false on an engine error (hm_pileup_last_error).
+bool write_bed(hm_pileup_t* pe, const Fasta& fa, const void* pcov, const void* ncov, const void* key, FILE* out[3], int threads) {
+    return write_rows<hm_locus_t>(
+        fa, out, threads,
+        [&](int64_t lo, int64_t hi, hm_locus_t* dst, int64_t cap) { return hm_pileup_fetch_loci(pe, pcov, ncov, key, 0, lo, hi, dst, cap); },
+        [](const hm_locus_t& l, int64_t k, char (&buf)[320]) {
+            const double freq = 100.0 * l.pcov / (l.pcov + l.ncov);
+            return snprintf(buf, sizeof buf, "\t%lld\t%lld\t%g\t%d\t%d\n", (long long)k, (long long)k + 1, freq, l.pcov, l.ncov);
+        });
+}
+
+// rows of the three <prefix>.asm.<ctx>.bed files from the engine's own partition and key planes (48 B per tested row on the
+// device and here).  false on an engine error.
+bool write_asm(hm_pileup_t* pe, const Fasta& fa, int min_cov, FILE* out[3], int threads) {
+    return write_rows<hm_asm_t>(
+        fa, out, threads,
+        [&](int64_t lo, int64_t hi, hm_asm_t* dst, int64_t cap) {
+            return hm_pileup_fetch_asm(pe, nullptr, nullptr, nullptr, nullptr, nullptr, 0, lo, hi, min_cov, dst, cap);
+        },
+        [](const hm_asm_t& r, int64_t k, char (&buf)[320]) {
+            return snprintf(buf, sizeof buf, "\t%lld\t%lld\t%g\t%.6g\t%d\t%d\t%d\t%d\n", (long long)k, (long long)k + 1, r.diff, r.pvalue,
+                            r.pcov1, r.ncov1, r.pcov2, r.ncov2);
+        });
 }
 }  // namespace
 
@@ -942,7 +937,7 @@ bool parse_rates(const char* text, double rates[3]) {
 }
 
 // `pileup -B / -e` after hm_pileup_count: rates (measured on the control sequence `control_sid`, unless given), histogram of the
-// whole reference, the table, then the rows per sequence as write_bed fetches them (40 B per row on the device and here), and
+// whole reference, the table, then the rows (40 B per row on the device and here), and
 // <prefix>.sites.rates.tsv.  1 done, -1 engine error (hm_pileup_last_error), 0 another error (message printed).
 int write_sites(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, int control_sid, int threads) {
     static const char* cn[3] = {"CpG", "CHG", "CHH"};
@@ -981,44 +976,19 @@ int write_sites(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, int co
         const std::string path = o.prefix + ".sites." + cn[c] + ".bed";
         if (!(out[c] = fopen(path.c_str(), "w"))) { close_all(); return file_error(path); }
     }
-    std::vector<hm_site_t> rows;
-    const int fmt_threads = std::max(1, threads);
-    std::vector<std::string> text((size_t)fmt_threads * 3);
-    for (size_t s = 0; s < fa.names.size() && ctx_mask; ++s) {
-        const int64_t lo = start[s], hi = start[s + 1];
-        auto fetch = [&](hm_site_t* dst, int64_t cap) {
+    const bool ok = !ctx_mask || write_rows<hm_site_t>(
+        fa, out, threads,
+        [&](int64_t lo, int64_t hi, hm_site_t* dst, int64_t cap) {
             return hm_pileup_fetch_sites(pe, nullptr, nullptr, nullptr, 0, lo, hi, ctx_mask, ptab.data(), qtab.data(), big.data(), big_p.data(),
                                          big_q.data(), n_big, dst, cap);
-        };
-        int64_t n = fetch(nullptr, 0);
-        if (n > 0) {
-            rows.resize((size_t)n);
-            n = fetch(rows.data(), n);
-        }
-        if (n < 0) { close_all(); return -1; }
-        if (n == 0) continue;
-        parallel_run(fmt_threads, fmt_threads, [&](int w) {  // formatted in slices and written slice by slice, as write_bed does
-            for (int c = 0; c < 3; ++c) text[(size_t)w * 3 + c].clear();
-            const size_t a = (size_t)n * w / fmt_threads, b = (size_t)n * (w + 1) / fmt_threads;
-            char row[320];
-            for (size_t i = a; i < b; ++i) {
-                const hm_site_t& r = rows[i];
-                const int64_t k = r.gpos - lo;
-                const double freq = 100.0 * r.pcov / (r.pcov + r.ncov);
-                const int len = snprintf(row, sizeof row, "\t%lld\t%lld\t%g\t%d\t%d\t%.6g\t%.6g\n", (long long)k, (long long)k + 1, freq, r.pcov,
-                                         r.ncov, r.pvalue, r.qvalue);
-                std::string& t = text[(size_t)w * 3 + (r.motif < 3 ? r.motif : 2)];
-                t += fa.names[s];
-                t.append(row, (size_t)len);
-            }
+        },
+        [](const hm_site_t& r, int64_t k, char (&buf)[320]) {
+            const double freq = 100.0 * r.pcov / (r.pcov + r.ncov);
+            return snprintf(buf, sizeof buf, "\t%lld\t%lld\t%g\t%d\t%d\t%.6g\t%.6g\n", (long long)k, (long long)k + 1, freq, r.pcov, r.ncov,
+                            r.pvalue, r.qvalue);
         });
-        for (int c = 0; c < 3; ++c)
-            for (int w = 0; w < fmt_threads; ++w) {
-                const std::string& t = text[(size_t)w * 3 + c];
-                if (!t.empty() && out[c]) fwrite(t.data(), 1, t.size(), out[c]);
-            }
-    }
     close_all();
+    if (!ok) return -1;
     const std::string path = o.prefix + ".sites.rates.tsv";
     FILE* f = fopen(path.c_str(), "w");
     if (!f) return file_error(path);
@@ -1266,7 +1236,7 @@ int cmd_pileup(int argc, char** argv) {
                 return EXIT_FAILURE;
             }
         }
-        const bool ok = write_asm(pe, fa, o.asm_min_cov, out);
+        const bool ok = write_asm(pe, fa, o.asm_min_cov, out, o.threads);
         for (FILE* f : out) fclose(f);
         if (!ok) return die("asm");
     }

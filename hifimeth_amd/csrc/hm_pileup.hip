@@ -339,19 +339,62 @@ __global__ __launch_bounds__(TPB) void label_kernel(const PRec* __restrict__ rec
 // ---- covered loci of a range, ascending ---------------------------------------------------------------------
 constexpr int LOCI_PER_BLOCK = 4096;  // 16 per thread
 
-__global__ __launch_bounds__(TPB) void loci_count_kernel(const int32_t* __restrict__ pcov, const int32_t* __restrict__ ncov,
-                                                          int64_t lo, int64_t hi, int32_t* __restrict__ block_counts) {
+// One skeleton for every "rows of the selected loci of [lo, hi), ascending" output: a count kernel (count_block with the
+// selection), loci_scan_kernel, a write kernel (compact_block with the selection and the row), one workgroup per
+// LOCI_PER_BLOCK loci in both; compact_rows() on the host drives the three.
+
+// the sum of v over the workgroup, in every thread; a barrier is due before the next call
+__device__ __forceinline__ int block_sum(int v) {
     __shared__ int wsum[TPB / 64];
+    for (int d = 32; d; d >>= 1) v += __shfl_down(v, d);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+// The count step: block_counts[blockIdx.x] = the number of the workgroup's LOCI_PER_BLOCK loci i for which pred(i) holds.
+template <class Pred>
+__device__ __forceinline__ void count_block(int64_t lo, int64_t hi, int32_t* __restrict__ block_counts, Pred pred) {
     const int64_t base = lo + (int64_t)blockIdx.x * LOCI_PER_BLOCK;
     int cnt = 0;
     for (int k = 0; k < LOCI_PER_BLOCK / TPB; ++k) {
         const int64_t i = base + k * TPB + threadIdx.x;
-        if (i < hi && (pcov[i] | ncov[i])) ++cnt;
+        if (i < hi && pred(i)) ++cnt;
     }
-    for (int d = 32; d; d >>= 1) cnt += __shfl_down(cnt, d);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) block_counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    cnt = block_sum(cnt);
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = cnt;
+}
+
+// The write step: the rows of the workgroup's LOCI_PER_BLOCK loci for which take(i, row) holds, in ascending order from
+// out[offs[blockIdx.x]] on.  take must select what the count step's pred selected.
+template <class Row, class Take>
+__device__ __forceinline__ void compact_block(int64_t lo, int64_t hi, const int64_t* __restrict__ offs, Row* __restrict__ out, Take take) {
+    __shared__ int wsum[TPB / 64];
+    __shared__ int carry;
+    if (threadIdx.x == 0) carry = 0;
+    const int64_t base = lo + (int64_t)blockIdx.x * LOCI_PER_BLOCK;
+    const int64_t o0 = offs[blockIdx.x];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int k = 0; k < LOCI_PER_BLOCK / TPB; ++k) {
+        __syncthreads();
+        const int64_t i = base + k * TPB + threadIdx.x;
+        Row r;
+        const bool sel = i < hi && take(i, r);
+        const unsigned long long b = __ballot(sel);
+        if (lane == 0) wsum[w] = __popcll(b);
+        __syncthreads();
+        int before = carry;
+        for (int j = 0; j < w; ++j) before += wsum[j];
+        if (sel) out[o0 + before + __popcll(b & ((1ull << lane) - 1ull))] = r;
+        __syncthreads();
+        if (threadIdx.x == 0) carry += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    }
+}
+
+// covered loci: a counter of either sign counts
+__global__ __launch_bounds__(TPB) void loci_count_kernel(const int32_t* __restrict__ pcov, const int32_t* __restrict__ ncov,
+                                                          int64_t lo, int64_t hi, int32_t* __restrict__ block_counts) {
+    count_block(lo, hi, block_counts, [&](int64_t i) { return (pcov[i] | ncov[i]) != 0; });
 }
 
 // single-workgroup exclusive scan; total -> offs[n]
@@ -382,35 +425,16 @@ __global__ __launch_bounds__(TPB) void loci_write_kernel(const int32_t* __restri
                                                           const uint32_t* __restrict__ key, int64_t plane_base,
                                                           int64_t lo, int64_t hi, const int64_t* __restrict__ offs,
                                                           hm_locus_t* __restrict__ out) {
-    __shared__ int wsum[TPB / 64];
-    __shared__ int carry;
-    if (threadIdx.x == 0) carry = 0;
-    const int64_t base = lo + (int64_t)blockIdx.x * LOCI_PER_BLOCK;
-    const int64_t o0 = offs[blockIdx.x];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (int k = 0; k < LOCI_PER_BLOCK / TPB; ++k) {
-        __syncthreads();
-        const int64_t i = base + k * TPB + threadIdx.x;
-        int32_t p = 0, n = 0;
-        if (i < hi) { p = pcov[i]; n = ncov[i]; }
-        const bool cov = (p | n) != 0;
-        const unsigned long long b = __ballot(cov);
-        if (lane == 0) wsum[w] = __popcll(b);
-        __syncthreads();
-        int before = carry;
-        for (int j = 0; j < w; ++j) before += wsum[j];
-        if (cov) {
-            hm_locus_t l;
-            l.gpos = plane_base + i;
-            l.pcov = p;
-            l.ncov = n;
-            l.motif = key[i] & 3u;
-            l.reserved = 0;
-            out[o0 + before + __popcll(b & ((1ull << lane) - 1ull))] = l;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) carry += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    }
+    compact_block(lo, hi, offs, out, [&](int64_t i, hm_locus_t& l) {
+        const int32_t p = pcov[i], n = ncov[i];
+        if ((p | n) == 0) return false;
+        l.gpos = plane_base + i;
+        l.pcov = p;
+        l.ncov = n;
+        l.motif = key[i] & 3u;
+        l.reserved = 0;
+        return true;
+    });
 }
 
 // ---- allele-specific methylation: loci tested between the two haplotype partitions -----------------
@@ -426,17 +450,7 @@ __global__ __launch_bounds__(TPB) void asm_count_kernel(const int32_t* __restric
                                                          const int32_t* __restrict__ pcov2, const int32_t* __restrict__ ncov2,
                                                          int64_t lo, int64_t hi, int32_t min_cov,
                                                          int32_t* __restrict__ block_counts) {
-    __shared__ int wsum[TPB / 64];
-    const int64_t base = lo + (int64_t)blockIdx.x * LOCI_PER_BLOCK;
-    int cnt = 0;
-    for (int k = 0; k < LOCI_PER_BLOCK / TPB; ++k) {
-        const int64_t i = base + k * TPB + threadIdx.x;
-        if (i < hi && asm_tested(pcov1[i], ncov1[i], pcov2[i], ncov2[i], min_cov)) ++cnt;
-    }
-    for (int d = 32; d; d >>= 1) cnt += __shfl_down(cnt, d);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) block_counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    count_block(lo, hi, block_counts, [&](int64_t i) { return asm_tested(pcov1[i], ncov1[i], pcov2[i], ncov2[i], min_cov); });
 }
 
 // compact rows in ascending locus order; diff and pvalue are filled by asm_test_kernel
@@ -445,39 +459,20 @@ __global__ __launch_bounds__(TPB) void asm_write_kernel(const int32_t* __restric
                                                          const uint32_t* __restrict__ key, int64_t plane_base, int64_t lo,
                                                          int64_t hi, int32_t min_cov, const int64_t* __restrict__ offs,
                                                          hm_asm_t* __restrict__ out) {
-    __shared__ int wsum[TPB / 64];
-    __shared__ int carry;
-    if (threadIdx.x == 0) carry = 0;
-    const int64_t base = lo + (int64_t)blockIdx.x * LOCI_PER_BLOCK;
-    const int64_t o0 = offs[blockIdx.x];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (int k = 0; k < LOCI_PER_BLOCK / TPB; ++k) {
-        __syncthreads();
-        const int64_t i = base + k * TPB + threadIdx.x;
-        int32_t p1 = 0, n1 = 0, p2 = 0, n2 = 0;
-        if (i < hi) { p1 = pcov1[i]; n1 = ncov1[i]; p2 = pcov2[i]; n2 = ncov2[i]; }
-        const bool sel = i < hi && asm_tested(p1, n1, p2, n2, min_cov);
-        const unsigned long long b = __ballot(sel);
-        if (lane == 0) wsum[w] = __popcll(b);
-        __syncthreads();
-        int before = carry;
-        for (int j = 0; j < w; ++j) before += wsum[j];
-        if (sel) {
-            hm_asm_t r;
-            r.gpos = plane_base + i;
-            r.pcov1 = p1;
-            r.ncov1 = n1;
-            r.pcov2 = p2;
-            r.ncov2 = n2;
-            r.motif = key[i] & 3u;
-            r.reserved = 0;
-            r.diff = 0.0;
-            r.pvalue = 0.0;
-            out[o0 + before + __popcll(b & ((1ull << lane) - 1ull))] = r;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) carry += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    }
+    compact_block(lo, hi, offs, out, [&](int64_t i, hm_asm_t& r) {
+        const int32_t p1 = pcov1[i], n1 = ncov1[i], p2 = pcov2[i], n2 = ncov2[i];
+        if (!asm_tested(p1, n1, p2, n2, min_cov)) return false;
+        r.gpos = plane_base + i;
+        r.pcov1 = p1;
+        r.ncov1 = n1;
+        r.pcov2 = p2;
+        r.ncov2 = n2;
+        r.motif = key[i] & 3u;
+        r.reserved = 0;
+        r.diff = 0.0;
+        r.pvalue = 0.0;
+        return true;
+    });
 }
 
 __device__ __forceinline__ double lfact(const double* __restrict__ tab, int64_t k) {
@@ -570,7 +565,6 @@ __global__ __launch_bounds__(TPB) void sites_hist_kernel(const int32_t* __restri
                                                           const uint32_t* __restrict__ key, int64_t lo, int64_t hi, int64_t nblk,
                                                           unsigned long long* __restrict__ bins, int32_t* __restrict__ block_big) {
     __shared__ uint32_t h[3 * SITE_LDS_N * SITE_LDS_N];
-    __shared__ int wsum[TPB / 64];
     for (int i = threadIdx.x; i < 3 * SITE_LDS_N * SITE_LDS_N; i += TPB) h[i] = 0u;
     __syncthreads();
     for (int64_t b = blockIdx.x; b < nblk; b += gridDim.x) {  // (uniform over the workgroup: the barriers below are safe)
@@ -587,10 +581,8 @@ __global__ __launch_bounds__(TPB) void sites_hist_kernel(const int32_t* __restri
             else if (tot < SITE_N) atomicAdd(&bins[(m * SITE_N + (uint32_t)tot) * SITE_N + (uint32_t)p], 1ull);
             else ++big;
         }
-        for (int d = 32; d; d >>= 1) big += __shfl_down(big, d);
-        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = big;
-        __syncthreads();
-        if (threadIdx.x == 0) block_big[b] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        big = block_sum(big);
+        if (threadIdx.x == 0) block_big[b] = big;
         __syncthreads();
     }
     for (int i = threadIdx.x; i < 3 * SITE_LDS_N * SITE_LDS_N; i += TPB)
@@ -598,32 +590,6 @@ __global__ __launch_bounds__(TPB) void sites_hist_kernel(const int32_t* __restri
             const uint32_t m = (uint32_t)i / (SITE_LDS_N * SITE_LDS_N), n = ((uint32_t)i / SITE_LDS_N) % SITE_LDS_N, k = (uint32_t)i % SITE_LDS_N;
             atomicAdd(&bins[(m * SITE_N + n) * SITE_N + k], (unsigned long long)h[i]);
         }
-}
-
-// The write step of the count / loci_scan_kernel / write scheme for the two lists below: the rows of the workgroup's
-// LOCI_PER_BLOCK loci for which take(i, row) holds, in ascending order from out[offs[blockIdx.x]] on.
-template <class Row, class Take>
-__device__ __forceinline__ void compact_block(int64_t lo, int64_t hi, const int64_t* __restrict__ offs, Row* __restrict__ out, Take take) {
-    __shared__ int wsum[TPB / 64];
-    __shared__ int carry;
-    if (threadIdx.x == 0) carry = 0;
-    const int64_t base = lo + (int64_t)blockIdx.x * LOCI_PER_BLOCK;
-    const int64_t o0 = offs[blockIdx.x];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (int k = 0; k < LOCI_PER_BLOCK / TPB; ++k) {
-        __syncthreads();
-        const int64_t i = base + k * TPB + threadIdx.x;
-        Row r;
-        const bool sel = i < hi && take(i, r);
-        const unsigned long long b = __ballot(sel);
-        if (lane == 0) wsum[w] = __popcll(b);
-        __syncthreads();
-        int before = carry;
-        for (int j = 0; j < w; ++j) before += wsum[j];
-        if (sel) out[o0 + before + __popcll(b & ((1ull << lane) - 1ull))] = r;
-        __syncthreads();
-        if (threadIdx.x == 0) carry += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    }
 }
 
 // the big loci (n >= 256) of the range, where sites_hist_kernel counted them
@@ -650,17 +616,7 @@ __device__ __forceinline__ bool site_tested(int32_t p, int32_t n, uint32_t key, 
 __global__ __launch_bounds__(TPB) void sites_count_kernel(const int32_t* __restrict__ pcov, const int32_t* __restrict__ ncov,
                                                            const uint32_t* __restrict__ key, int64_t lo, int64_t hi, uint32_t ctx_mask,
                                                            int32_t* __restrict__ block_counts) {
-    __shared__ int wsum[TPB / 64];
-    const int64_t base = lo + (int64_t)blockIdx.x * LOCI_PER_BLOCK;
-    int cnt = 0;
-    for (int k = 0; k < LOCI_PER_BLOCK / TPB; ++k) {
-        const int64_t i = base + k * TPB + threadIdx.x;
-        if (i < hi && site_tested(pcov[i], ncov[i], key[i], ctx_mask)) ++cnt;
-    }
-    for (int d = 32; d; d >>= 1) cnt += __shfl_down(cnt, d);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) block_counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    count_block(lo, hi, block_counts, [&](int64_t i) { return site_tested(pcov[i], ncov[i], key[i], ctx_mask); });
 }
 
 // rows with pvalue / qvalue looked up: n < 256 in tab[(motif * 256 + n) * 256 + k] (ptab, then qtab behind it), a big locus by
@@ -734,11 +690,11 @@ struct hm_pileup {
 
     // device
     DevBuf d_slab{HALF}, d_reads{HALF}, d_runs{HALF}, d_col0{HALF}, d_mods{HALF}, d_calls{HALF}, d_plane{HALF}, d_matches{HALF}, d_bins{HALF}, d_counter{HALF}, d_recs{HALF};
-    DevBuf d_blk{HALF}, d_offs{HALF}, d_loci{HALF}, d_labels{HALF}, d_lbins{HALF};
-    DevBuf d_asm{HALF}, d_lfact{EXACT};  // tested rows of hm_pileup_fetch_asm; log n! table, uploaded by its first call
+    DevBuf d_blk{HALF}, d_offs{HALF}, d_rows{HALF}, d_labels{HALF}, d_lbins{HALF};  // d_rows: the rows of whichever fetch ran last
+    DevBuf d_lfact{EXACT};  // log n! table, uploaded by the first hm_pileup_fetch_asm
     // `pileup -B / -e`, allocated by the first call that needs them: control sums, 3 x 256 x 256 bins, ptab + qtab, the big loci
-    // (the histogram's list, or the caller's with p and q behind it), rows of hm_pileup_fetch_sites
-    DevBuf d_ssums{EXACT}, d_sbins{EXACT}, d_stab{EXACT}, d_sbig{HALF}, d_sbigpq{HALF}, d_sites{HALF};
+    // (the histogram's list, or the caller's with p and q behind it: they stay while hm_pileup_fetch_sites writes d_rows)
+    DevBuf d_ssums{EXACT}, d_sbins{EXACT}, d_stab{EXACT}, d_sbig{HALF}, d_sbigpq{HALF};
     int64_t n_recs = 0;
     bool bins_ready = false;
 
@@ -776,6 +732,67 @@ const std::vector<double>& host_lfact() {
 }
 
 inline int grid_for(int64_t n, int cap = 1 << 20) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + TPB - 1) / TPB, cap)); }
+
+struct RangePlanes {
+    const int32_t *pc, *nc;
+    const uint32_t* ky;
+};
+
+// the (pcov, ncov, key) arguments of a call over a plane range: each the caller's plane or, where NULL, the engine's own (with
+// pcov NULL plane_base is 0); false (error recorded) if there are none
+bool range_planes(hm_pileup* p, const void* pcov, const void* ncov, const void* key, int64_t& plane_base, RangePlanes& s) {
+    s.pc = pcov ? static_cast<const int32_t*>(pcov) : p->pcov;
+    s.nc = ncov ? static_cast<const int32_t*>(ncov) : p->ncov;
+    s.ky = key ? static_cast<const uint32_t*>(key) : p->key;
+    if (!pcov) plane_base = 0;
+    if (s.pc && s.nc && s.ky) return true;
+    pfail(p, HM_ESTATE, "no planes");
+    return false;
+}
+
+// ---- the host side of count_block / loci_scan_kernel / compact_block ------------------------------------------------------
+inline int64_t range_blocks(int64_t lo, int64_t hi) { return (hi - lo + LOCI_PER_BLOCK - 1) / LOCI_PER_BLOCK; }
+
+// a count kernel has filled d_blk[0, nblk): their exclusive scan into d_offs, the total returned
+int64_t scan_blocks(hm_pileup* p, int64_t nblk) {
+    hipLaunchKernelGGL(loci_scan_kernel, dim3(1), dim3(1024), 0, p->stream, p->d_blk.as<int32_t>(), (int)nblk, p->d_offs.as<int64_t>());
+    HIP_TRY(hipGetLastError());
+    int64_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, p->d_offs.as<int64_t>() + nblk, 8, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    return total;
+}
+
+// launch_write(offs, dst) compacts the `total` rows scan_blocks counted into `buf`; they are in `out` when this returns
+template <class Row, class Write>
+void write_rows(hm_pileup* p, DevBuf& buf, int64_t total, Row* out, Write launch_write) {
+    buf.reserve(sizeof(Row) * (size_t)total);
+    launch_write(p->d_offs.as<int64_t>(), buf.as<Row>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, buf.p, sizeof(Row) * (size_t)total, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+}
+
+// The rows of the non-empty range [lo, hi) in ascending order -> their number, or an error code.  launch_count(grid, block_counts)
+// and launch_write(grid, offs, dst, total) start a count_block and a compact_block kernel with the same selection;
+// before_write() uploads what the write needs.  More rows than cap, or no `out`: only counted, nothing is written.
+template <class Row, class Count, class Before, class Write>
+int64_t compact_rows(hm_pileup* p, int64_t lo, int64_t hi, Row* out, int64_t cap, Count launch_count, Before before_write,
+                     Write launch_write) {
+    const int64_t nblk = range_blocks(lo, hi);
+    if (nblk >= (int64_t(1) << 31)) return pfail(p, HM_EINVAL, "range too large: fetch per sequence");
+    return guarded(p, [&]() -> int64_t {
+        const dim3 grid((unsigned)nblk);
+        p->d_blk.reserve(4 * (size_t)nblk);
+        p->d_offs.reserve(8 * ((size_t)nblk + 1));
+        launch_count(grid, p->d_blk.as<int32_t>());
+        const int64_t total = scan_blocks(p, nblk);
+        if (total > cap || !out || total == 0) return total;
+        before_write();
+        write_rows(p, p->d_rows, total, out, [&](const int64_t* offs, Row* dst) { launch_write(grid, offs, dst, total); });
+        return total;
+    });
+}
 
 void ensure_bins(hm_pileup* p) {
     if (p->bins_ready) return;
@@ -1221,32 +1238,17 @@ int hm_pileup_count(hm_pileup_t* p, const uint8_t thr[3]) {
 int64_t hm_pileup_fetch_loci(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t plane_base,
                              int64_t lo, int64_t hi, hm_locus_t* out, int64_t cap) {
     if (!p || lo < 0 || hi < lo) return pfail(p, HM_EINVAL, "hm_pileup_fetch_loci: bad range");
-    const int32_t* pc = pcov ? static_cast<const int32_t*>(pcov) : p->pcov;
-    const int32_t* nc = ncov ? static_cast<const int32_t*>(ncov) : p->ncov;
-    const uint32_t* ky = key ? static_cast<const uint32_t*>(key) : p->key;
-    if (!pcov) plane_base = 0;
-    if (!pc || !nc || !ky) return pfail(p, HM_ESTATE, "no planes");
+    RangePlanes s;
+    if (!range_planes(p, pcov, ncov, key, plane_base, s)) return HM_ESTATE;
     if (hi == lo) return 0;
-    const int64_t nblk = (hi - lo + LOCI_PER_BLOCK - 1) / LOCI_PER_BLOCK;
-    if (nblk >= (int64_t(1) << 31)) return pfail(p, HM_EINVAL, "range too large: fetch per sequence");
-    return guarded(p, [&] {
-        hipStream_t st = p->stream;
-        p->d_blk.reserve(4 * (size_t)nblk);
-        p->d_offs.reserve(8 * ((size_t)nblk + 1));
-        hipLaunchKernelGGL(loci_count_kernel, dim3((unsigned)nblk), dim3(TPB), 0, st, pc, nc, lo, hi, p->d_blk.as<int32_t>());
-        hipLaunchKernelGGL(loci_scan_kernel, dim3(1), dim3(1024), 0, st, p->d_blk.as<int32_t>(), (int)nblk, p->d_offs.as<int64_t>());
-        int64_t total = 0;
-        HIP_TRY(hipMemcpyAsync(&total, p->d_offs.as<int64_t>() + nblk, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (total > cap || !out || total == 0) return total;
-        p->d_loci.reserve(sizeof(hm_locus_t) * (size_t)total);
-        hipLaunchKernelGGL(loci_write_kernel, dim3((unsigned)nblk), dim3(TPB), 0, st, pc, nc, ky, plane_base, lo, hi,
-                           p->d_offs.as<int64_t>(), p->d_loci.as<hm_locus_t>());
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(out, p->d_loci.p, sizeof(hm_locus_t) * (size_t)total, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return total;
-    });
+    hipStream_t st = p->stream;
+    return compact_rows(
+        p, lo, hi, out, cap,
+        [&](dim3 grid, int32_t* counts) { hipLaunchKernelGGL(loci_count_kernel, grid, dim3(TPB), 0, st, s.pc, s.nc, lo, hi, counts); },
+        [] {},
+        [&](dim3 grid, const int64_t* offs, hm_locus_t* dst, int64_t) {
+            hipLaunchKernelGGL(loci_write_kernel, grid, dim3(TPB), 0, st, s.pc, s.nc, s.ky, plane_base, lo, hi, offs, dst);
+        });
 }
 
 int64_t hm_pileup_fetch_asm(hm_pileup_t* p, const void* pcov1, const void* ncov1, const void* pcov2, const void* ncov2,
@@ -1268,56 +1270,30 @@ int64_t hm_pileup_fetch_asm(hm_pileup_t* p, const void* pcov1, const void* ncov1
         plane_base = 0;
     }
     if (hi == lo) return 0;
-    const int64_t nblk = (hi - lo + LOCI_PER_BLOCK - 1) / LOCI_PER_BLOCK;
-    if (nblk >= (int64_t(1) << 31)) return pfail(p, HM_EINVAL, "range too large: fetch per sequence");
-    return guarded(p, [&] {
-        hipStream_t st = p->stream;
-        p->d_blk.reserve(4 * (size_t)nblk);
-        p->d_offs.reserve(8 * ((size_t)nblk + 1));
-        hipLaunchKernelGGL(asm_count_kernel, dim3((unsigned)nblk), dim3(TPB), 0, st, p1, n1, p2, n2, lo, hi, min_cov, p->d_blk.as<int32_t>());
-        hipLaunchKernelGGL(loci_scan_kernel, dim3(1), dim3(1024), 0, st, p->d_blk.as<int32_t>(), (int)nblk, p->d_offs.as<int64_t>());
-        int64_t total = 0;
-        HIP_TRY(hipMemcpyAsync(&total, p->d_offs.as<int64_t>() + nblk, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (total > cap || !out || total == 0) return total;
-        if (!p->d_lfact.p) {  // log n!, n < LFACT_N: once per engine
+    hipStream_t st = p->stream;
+    return compact_rows(
+        p, lo, hi, out, cap,
+        [&](dim3 grid, int32_t* counts) {
+            hipLaunchKernelGGL(asm_count_kernel, grid, dim3(TPB), 0, st, p1, n1, p2, n2, lo, hi, min_cov, counts);
+        },
+        [&] {
+            if (p->d_lfact.p) return;  // log n!, n < LFACT_N: once per engine
             const std::vector<double>& t = host_lfact();
             p->d_lfact.reserve(sizeof(double) * t.size());
             HIP_TRY(hipMemcpyAsync(p->d_lfact.p, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice, st));
             HIP_TRY(hipStreamSynchronize(st));
-        }
-        p->d_asm.reserve(sizeof(hm_asm_t) * (size_t)total);
-        hipLaunchKernelGGL(asm_write_kernel, dim3((unsigned)nblk), dim3(TPB), 0, st, p1, n1, p2, n2, ky, plane_base, lo, hi, min_cov,
-                           p->d_offs.as<int64_t>(), p->d_asm.as<hm_asm_t>());
-        hipLaunchKernelGGL(asm_test_kernel, dim3((unsigned)((total + TPB - 1) / TPB)), dim3(TPB), 0, st, p->d_asm.as<hm_asm_t>(), total,
-                           p->d_lfact.as<double>());
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(out, p->d_asm.p, sizeof(hm_asm_t) * (size_t)total, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return total;
-    });
+        },
+        [&](dim3 grid, const int64_t* offs, hm_asm_t* dst, int64_t total) {
+            hipLaunchKernelGGL(asm_write_kernel, grid, dim3(TPB), 0, st, p1, n1, p2, n2, ky, plane_base, lo, hi, min_cov, offs, dst);
+            hipLaunchKernelGGL(asm_test_kernel, dim3((unsigned)((total + TPB - 1) / TPB)), dim3(TPB), 0, st, dst, total,
+                               p->d_lfact.as<double>());
+        });
 }
 
 // ---- `pileup -B / -e` ---------------------------------------------------------------------------------------------------------
 }  // extern "C"
 
 namespace {
-
-struct SitePlanes {
-    const int32_t *pc, *nc;
-    const uint32_t* ky;
-};
-
-// the plane arguments of the three sites calls, as hm_pileup_fetch_loci reads them; false (error recorded) if there are none
-bool site_planes(hm_pileup* p, const void* pcov, const void* ncov, const void* key, int64_t& plane_base, SitePlanes& s) {
-    s.pc = pcov ? static_cast<const int32_t*>(pcov) : p->pcov;
-    s.nc = ncov ? static_cast<const int32_t*>(ncov) : p->ncov;
-    s.ky = key ? static_cast<const uint32_t*>(key) : p->key;
-    if (!pcov) plane_base = 0;
-    if (s.pc && s.nc && s.ky) return true;
-    pfail(p, HM_ESTATE, "no planes");
-    return false;
-}
 
 // P(X >= k), X ~ Binomial(n, e), 0 < e < 1, 0 < k <= n: the sum the header spells out
 double binomial_tail(int64_t k, int64_t n, double log_e, double log1m_e) {
@@ -1337,9 +1313,9 @@ int hm_pileup_control_sums(hm_pileup_t* p, const void* pcov, const void* ncov, c
                            uint64_t sums[6]) {
     if (!p) return HM_EINVAL;
     if (lo < 0 || hi < lo || !sums) return pfail(p, HM_EINVAL, "hm_pileup_control_sums: bad argument");
-    SitePlanes s;
+    RangePlanes s;
     int64_t base = 0;
-    if (!site_planes(p, pcov, ncov, key, base, s)) return HM_ESTATE;
+    if (!range_planes(p, pcov, ncov, key, base, s)) return HM_ESTATE;
     std::fill(sums, sums + 6, uint64_t(0));
     if (hi == lo) return HM_OK;
     return guarded(p, [&] {
@@ -1359,10 +1335,10 @@ int64_t hm_pileup_site_histogram(hm_pileup_t* p, const void* pcov, const void* n
                                  int64_t lo, int64_t hi, uint64_t* bins, hm_locus_t* big, int64_t cap) {
     if (!p) return HM_EINVAL;
     if (lo < 0 || hi < lo || !bins) return pfail(p, HM_EINVAL, "hm_pileup_site_histogram: bad argument");
-    SitePlanes s;
-    if (!site_planes(p, pcov, ncov, key, plane_base, s)) return HM_ESTATE;
+    RangePlanes s;
+    if (!range_planes(p, pcov, ncov, key, plane_base, s)) return HM_ESTATE;
     if (hi == lo) return 0;
-    const int64_t nblk = (hi - lo + LOCI_PER_BLOCK - 1) / LOCI_PER_BLOCK;
+    const int64_t nblk = range_blocks(lo, hi);
     if (nblk >= (int64_t(1) << 31)) return pfail(p, HM_EINVAL, "range too large: histogram per sequence");
     return guarded(p, [&]() -> int64_t {
         hipStream_t st = p->stream;
@@ -1374,22 +1350,15 @@ int64_t hm_pileup_site_histogram(hm_pileup_t* p, const void* pcov, const void* n
         const int64_t grid = std::max(std::min<int64_t>(nblk, 512), (nblk + (int64_t(1) << 19) - 1) >> 19);
         hipLaunchKernelGGL(sites_hist_kernel, dim3((unsigned)grid), dim3(TPB), 0, st, s.pc, s.nc, s.ky, lo, hi, nblk,
                            p->d_sbins.as<unsigned long long>(), p->d_blk.as<int32_t>());
-        hipLaunchKernelGGL(loci_scan_kernel, dim3(1), dim3(1024), 0, st, p->d_blk.as<int32_t>(), (int)nblk, p->d_offs.as<int64_t>());
-        HIP_TRY(hipGetLastError());
-        int64_t n_big = 0;
-        HIP_TRY(hipMemcpyAsync(&n_big, p->d_offs.as<int64_t>() + nblk, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        const int64_t n_big = scan_blocks(p, nblk);
         if (n_big > cap || (n_big && !big)) return n_big;
         std::vector<uint64_t> h((size_t)HM_SITE_BINS);
         HIP_TRY(hipMemcpyAsync(h.data(), p->d_sbins.p, HM_SITE_BINS * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        if (n_big) {
-            p->d_sbig.reserve(sizeof(hm_locus_t) * (size_t)n_big);
-            hipLaunchKernelGGL(sites_big_write_kernel, dim3((unsigned)nblk), dim3(TPB), 0, st, s.pc, s.nc, s.ky, plane_base, lo, hi,
-                               p->d_offs.as<int64_t>(), p->d_sbig.as<hm_locus_t>());
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(big, p->d_sbig.p, sizeof(hm_locus_t) * (size_t)n_big, hipMemcpyDeviceToHost, st));
-        }
-        HIP_TRY(hipStreamSynchronize(st));
+        if (n_big)  // the list, and with it the bins, are on the host when write_rows returns
+            write_rows(p, p->d_sbig, n_big, big, [&](const int64_t* offs, hm_locus_t* dst) {
+                hipLaunchKernelGGL(sites_big_write_kernel, dim3((unsigned)nblk), dim3(TPB), 0, st, s.pc, s.nc, s.ky, plane_base, lo, hi, offs, dst);
+            });
+        else HIP_TRY(hipStreamSynchronize(st));
         for (size_t i = 0; i < h.size(); ++i) bins[i] += h[i];
         return n_big;
     });
@@ -1462,43 +1431,31 @@ int64_t hm_pileup_fetch_sites(hm_pileup_t* p, const void* pcov, const void* ncov
     if (!p) return HM_EINVAL;
     if (lo < 0 || hi < lo || !ptab || !qtab || n_big < 0 || (n_big && (!big || !big_p || !big_q)) || (ctx_mask & ~7))
         return pfail(p, HM_EINVAL, "hm_pileup_fetch_sites: bad argument");
-    SitePlanes s;
-    if (!site_planes(p, pcov, ncov, key, plane_base, s)) return HM_ESTATE;
+    RangePlanes s;
+    if (!range_planes(p, pcov, ncov, key, plane_base, s)) return HM_ESTATE;
     if (hi == lo) return 0;
-    const int64_t nblk = (hi - lo + LOCI_PER_BLOCK - 1) / LOCI_PER_BLOCK;
-    if (nblk >= (int64_t(1) << 31)) return pfail(p, HM_EINVAL, "range too large: fetch per sequence");
-    return guarded(p, [&]() -> int64_t {
-        hipStream_t st = p->stream;
-        p->d_blk.reserve(4 * (size_t)nblk);
-        p->d_offs.reserve(8 * ((size_t)nblk + 1));
-        hipLaunchKernelGGL(sites_count_kernel, dim3((unsigned)nblk), dim3(TPB), 0, st, s.pc, s.nc, s.ky, lo, hi, (uint32_t)ctx_mask,
-                           p->d_blk.as<int32_t>());
-        hipLaunchKernelGGL(loci_scan_kernel, dim3(1), dim3(1024), 0, st, p->d_blk.as<int32_t>(), (int)nblk, p->d_offs.as<int64_t>());
-        HIP_TRY(hipGetLastError());
-        int64_t total = 0;
-        HIP_TRY(hipMemcpyAsync(&total, p->d_offs.as<int64_t>() + nblk, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (total > cap || !out || total == 0) return total;
-        const size_t tab_bytes = HM_SITE_BINS * sizeof(double);
-        p->d_stab.reserve(2 * tab_bytes);
-        HIP_TRY(hipMemcpyAsync(p->d_stab.p, ptab, tab_bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(p->d_stab.as<char>() + tab_bytes, qtab, tab_bytes, hipMemcpyHostToDevice, st));
-        if (n_big) {
+    hipStream_t st = p->stream;
+    return compact_rows(
+        p, lo, hi, out, cap,
+        [&](dim3 grid, int32_t* counts) {
+            hipLaunchKernelGGL(sites_count_kernel, grid, dim3(TPB), 0, st, s.pc, s.nc, s.ky, lo, hi, (uint32_t)ctx_mask, counts);
+        },
+        [&] {
+            const size_t tab_bytes = HM_SITE_BINS * sizeof(double);
+            p->d_stab.reserve(2 * tab_bytes);
+            HIP_TRY(hipMemcpyAsync(p->d_stab.p, ptab, tab_bytes, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(p->d_stab.as<char>() + tab_bytes, qtab, tab_bytes, hipMemcpyHostToDevice, st));
+            if (!n_big) return;
             p->d_sbig.reserve(sizeof(hm_locus_t) * (size_t)n_big);
             p->d_sbigpq.reserve(2 * sizeof(double) * (size_t)n_big);
             HIP_TRY(hipMemcpyAsync(p->d_sbig.p, big, sizeof(hm_locus_t) * (size_t)n_big, hipMemcpyHostToDevice, st));
             HIP_TRY(hipMemcpyAsync(p->d_sbigpq.p, big_p, sizeof(double) * (size_t)n_big, hipMemcpyHostToDevice, st));
             HIP_TRY(hipMemcpyAsync(p->d_sbigpq.as<double>() + n_big, big_q, sizeof(double) * (size_t)n_big, hipMemcpyHostToDevice, st));
-        }
-        p->d_sites.reserve(sizeof(hm_site_t) * (size_t)total);
-        hipLaunchKernelGGL(sites_write_kernel, dim3((unsigned)nblk), dim3(TPB), 0, st, s.pc, s.nc, s.ky, plane_base, lo, hi,
-                           (uint32_t)ctx_mask, p->d_stab.as<double>(), p->d_sbig.as<hm_locus_t>(), p->d_sbigpq.as<double>(), n_big,
-                           p->d_offs.as<int64_t>(), p->d_sites.as<hm_site_t>());
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(out, p->d_sites.p, sizeof(hm_site_t) * (size_t)total, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return total;
-    });
+        },
+        [&](dim3 grid, const int64_t* offs, hm_site_t* dst, int64_t) {
+            hipLaunchKernelGGL(sites_write_kernel, grid, dim3(TPB), 0, st, s.pc, s.nc, s.ky, plane_base, lo, hi, (uint32_t)ctx_mask,
+                               p->d_stab.as<double>(), p->d_sbig.as<hm_locus_t>(), p->d_sbigpq.as<double>(), n_big, offs, dst);
+        });
 }
 
 }  // extern "C"

@@ -211,6 +211,14 @@ class MethylationPileup:
             raise HifimethError(self._L.hm_pileup_last_error(self._h).decode())
         return rc
 
+    def _rows(self, fn, dtype, *args) -> np.ndarray:
+        """the rows of one of the engine's row fetches fn(handle, *args, out, cap): asked for their number, then fetched"""
+        n = self._check(fn(self._h, *args, None, 0))
+        out = np.zeros(n, dtype)
+        if n:
+            self._check(fn(self._h, *args, out.ctypes.data_as(C.c_void_p), n))
+        return out
+
     @property
     def n_loci(self) -> int:
         return int(self.offsets[-1])
@@ -297,11 +305,7 @@ class MethylationPileup:
             ptrs = [pc, nc, None]                 # key NULL = the engine's combined key plane
         else:
             ptrs = [None, None, None]
-        n = self._check(self._L.hm_pileup_fetch_loci(self._h, *ptrs, plane_base, lo, hi, None, 0))
-        out = np.zeros(n, LOCUS_DTYPE)
-        if n:
-            self._check(self._L.hm_pileup_fetch_loci(self._h, *ptrs, plane_base, lo, hi, out.ctypes.data_as(C.c_void_p), n))
-        return out
+        return self._rows(self._L.hm_pileup_fetch_loci, LOCUS_DTYPE, *ptrs, plane_base, lo, hi)
 
     def bed(self, loci: np.ndarray) -> dict:
         """the text of <prefix>.{CpG,CHG,CHH}.cov.bed (pileup.cpp:562-590)"""
@@ -318,11 +322,7 @@ class MethylationPileup:
         partitions=True).  diff = 100 p1 / (p1 + n1) - 100 p2 / (p2 + n2), pvalue = two-sided Fisher exact test (R's rule)."""
         hi = self.n_loci if hi is None else hi
         ptrs = [None] * 5 if planes is None else [C.c_void_p(t.data_ptr()) for t in planes]
-        n = self._check(self._L.hm_pileup_fetch_asm(self._h, *ptrs, plane_base, lo, hi, min_cov, None, 0))
-        out = np.zeros(n, ASM_DTYPE)
-        if n:
-            self._check(self._L.hm_pileup_fetch_asm(self._h, *ptrs, plane_base, lo, hi, min_cov, out.ctypes.data_as(C.c_void_p), n))
-        return out
+        return self._rows(self._L.hm_pileup_fetch_asm, ASM_DTYPE, *ptrs, plane_base, lo, hi, min_cov)
 
     def asm_bed(self, rows: np.ndarray) -> dict:
         """the text of <prefix>.asm.{CpG,CHG,CHH}.bed: chrom, k, k+1, diff, pvalue, pcov1, ncov1, pcov2, ncov2"""
@@ -362,13 +362,8 @@ class MethylationPileup:
         """rows of [lo, hi) (plane coordinates), ascending: the covered loci of the contexts `table` tests, pvalue / qvalue looked
         up in it on the device"""
         hi = self.n_loci if hi is None else hi
-        args = (*self._plane_ptrs(planes), plane_base, lo, hi, table.ctx_mask,
-                *(x.ctypes.data_as(C.c_void_p) for x in (table.ptab, table.qtab, table.big, table.big_p, table.big_q)), len(table.big))
-        n = self._check(self._L.hm_pileup_fetch_sites(self._h, *args, None, 0))
-        out = np.zeros(n, SITE_DTYPE)
-        if n:
-            self._check(self._L.hm_pileup_fetch_sites(self._h, *args, out.ctypes.data_as(C.c_void_p), n))
-        return out
+        return self._rows(self._L.hm_pileup_fetch_sites, SITE_DTYPE, *self._plane_ptrs(planes), plane_base, lo, hi, table.ctx_mask,
+                          *(x.ctypes.data_as(C.c_void_p) for x in (table.ptab, table.qtab, table.big, table.big_p, table.big_q)), len(table.big))
 
     def sites_bed(self, rows: np.ndarray) -> dict:
         """the text of <prefix>.sites.{CpG,CHG,CHH}.bed: the six columns of the cov.bed row, then pvalue and qvalue"""

@@ -243,6 +243,192 @@ def test_loci_ranges_beyond_1024_blocks():
     pu.close()
 
 
+# ---- the shared count / scan / write skeleton: loci, asm, site histogram and sites rows on one set of crafted planes --------------
+SK_N = 3 * BLK + 5
+SK_NEG = {"pcov1": 5000, "ncov1": 5001, "pcov2": 5002, "ncov2": 5003}     # the locus whose counter in that plane is negative
+SK_BIG = (6000, 7000)                                                    # pcov + ncov >= 256
+SK_EDGES = (0, 63, 64, 255, 256, BLK - 1, BLK, 2 * BLK - 1, 2 * BLK, SK_N - 1)
+SK_RANGES = ((0, SK_N), (1, SK_N - 1), (BLK - 1, BLK + 1), (BLK + 1, BLK + 1))
+SK_SLICE = 100                                                           # planes handed over from this locus on, plane_base = it
+
+
+def _skeleton_planes():
+    """-> dict of int32 planes.  Block 0 is fully selected (with it locus 0 and both sides of the lane boundary 63 / 64, of the
+    256-thread iteration boundary 255 / 256 and, with locus 4096, of the block boundary); block 1 holds the sparse loci, the
+    negative counters and the big loci; of block 2 only its first locus is selected, and the last locus of the planes is.  Every
+    aligned block of (0, n) therefore holds a selected locus (0, 4096, 8192 and the last one must be selected), so the block with
+    no selected locus is the third block of the range (1, n - 1), [8193, 12289)."""
+    i = np.arange(SK_N)
+    rng = np.random.default_rng(302)
+    h = {k: np.zeros(SK_N, np.int64) for k in ("pcov1", "ncov1", "pcov2", "ncov2")}
+    full = i < BLK
+    h["pcov1"][full], h["ncov1"][full] = 1 + i[full] % 5, 2 + i[full] % 3            # each haplotype's sum >= 3
+    h["pcov2"][full], h["ncov2"][full] = 3 + i[full] % 2, i[full] % 7
+    sparse = BLK + 1 + rng.choice(BLK - 2, 700, replace=False)                       # inside block 1, its two ends left alone
+    for k in h:                                                                      # 0 .. 4 per counter: some loci fail min_cov 1 or 3
+        h[k][sparse] = rng.integers(0, 5, len(sparse))
+    for e in (BLK, 2 * BLK - 1, 2 * BLK, SK_N - 1):
+        h["pcov1"][e], h["ncov1"][e], h["pcov2"][e], h["ncov2"][e] = 4, 1, 2, 3
+    for k, at in SK_NEG.items():
+        for j in h:
+            h[j][at] = 0 if j[0] == k[0] else 6                                      # the other haplotype's same counter is 0: the sum is negative too
+        h[k][at] = -2
+    h["pcov1"][SK_BIG[0]], h["ncov1"][SK_BIG[0]], h["pcov2"][SK_BIG[0]], h["ncov2"][SK_BIG[0]] = 200, 100, 50, 30
+    h["pcov1"][SK_BIG[1]], h["ncov1"][SK_BIG[1]], h["pcov2"][SK_BIG[1]], h["ncov2"][SK_BIG[1]] = 0, 128, 128, 0
+    h["pcov"], h["ncov"] = h["pcov1"] + h["pcov2"], h["ncov1"] + h["ncov2"]
+    h["key"] = (rng.integers(0, 1 << 20, SK_N) << 2) | (i & 3)
+    return {k: v.astype(np.int32) for k, v in h.items()}
+
+
+def _sk_loci(h):
+    return (h["pcov"] | h["ncov"]) != 0                                              # a negative counter counts as covered
+
+
+def _sk_asm(h, min_cov):
+    p1, n1, p2, n2 = (h[k].astype(np.int64) for k in ("pcov1", "ncov1", "pcov2", "ncov2"))
+    return ((p1 | n1 | p2 | n2) >= 0) & (p1 + n1 >= min_cov) & (p2 + n2 >= min_cov)
+
+
+def _sk_counted(h):
+    return (h["pcov"] | h["ncov"]) > 0
+
+
+def _sk_sites(h, ctx_mask):
+    return _sk_counted(h) & (((ctx_mask >> np.minimum(h["key"] & 3, 2)) & 1) != 0)
+
+
+def _sk_histogram(h, lo, hi):
+    """-> (bins [3, 256, 256], selection of the big loci) of planes[lo, hi)"""
+    big = _sk_counted(h) & (h["pcov"].astype(np.int64) + h["ncov"] >= 256)
+    at = np.nonzero((_sk_counted(h) & ~big)[lo:hi])[0] + lo
+    bins = np.zeros((3, 256, 256), np.uint64)
+    np.add.at(bins, (np.minimum(h["key"][at] & 3, 2), h["pcov"][at].astype(np.int64) + h["ncov"][at], h["pcov"][at]), 1)
+    return bins, big
+
+
+def test_skeleton_planes_hold_the_cases():
+    h = _skeleton_planes()
+    assert len(h["key"]) == SK_N == 3 * 4096 + 5
+    assert (h["pcov"] == h["pcov1"] + h["pcov2"]).all() and (h["ncov"] == h["ncov1"] + h["ncov2"]).all()
+    every = _sk_loci(h) & _sk_asm(h, 3) & _sk_sites(h, 7)
+    assert (every & _sk_sites(h, 5))[list(SK_EDGES)].all()      # 0, 63 | 64, 255 | 256, 4095 | 4096, 8191 | 8192, the last locus
+    assert every[:BLK].all()                                    # one block fully selected ...
+    for sel in (_sk_loci(h), _sk_asm(h, 1), _sk_sites(h, 7)):   # ... and one with none, in the ranges whose third block is [8193, 12289)
+        assert not sel[2 * BLK + 1:3 * BLK + 1].any()
+        assert 0 < sel[BLK:2 * BLK].sum() < BLK
+    assert (1, SK_N - 1) in SK_RANGES and 1 + 3 * BLK < SK_N - 1                     # [1 + 2 * 4096, 1 + 3 * 4096) is a whole block of it
+    for k, at in SK_NEG.items():                                # in loci, not in sites, not in asm
+        assert h[k][at] < 0 and sum(h[j][at] < 0 for j in ("pcov1", "ncov1", "pcov2", "ncov2")) == 1
+        assert _sk_loci(h)[at] and not _sk_counted(h)[at] and not _sk_asm(h, 1)[at]
+    assert (h["pcov"][list(SK_NEG.values())] < 0).sum() == 2 and (h["ncov"][list(SK_NEG.values())] < 0).sum() == 2
+    tot = h["pcov"].astype(np.int64) + h["ncov"]
+    assert (tot[list(SK_BIG)] >= 256).all() and (_sk_counted(h) & (tot >= 256)).sum() == len(SK_BIG)
+    assert {0, 1, 2, 3} == set((h["key"] & 3)[_sk_loci(h)].tolist()) and ((h["key"] & 3) == 3)[_sk_counted(h)].sum() > 1000
+    assert _sk_asm(h, 1).sum() > _sk_asm(h, 3).sum() > BLK and _sk_loci(h).sum() > _sk_asm(h, 1).sum()
+    assert _sk_sites(h, 7).sum() > _sk_sites(h, 5).sum() > 0
+
+
+def test_one_skeleton_behind_loci_asm_and_sites():
+    """pu.loci, pu.asm (min_cov 1 and 3), pu.site_histogram and pu.sites (ctx_mask 7 and 5) over the crafted planes against NumPy,
+    field for field, with the three predicates written out above (_sk_loci, _sk_asm, _sk_sites; big loci: _sk_histogram): the
+    whole planes, (1, n - 1), two loci across a block boundary, an empty range, and sliced planes with a plane_base.  p and q of a sites row are the table's entries bit for bit; asm's diff is numpy's bit for bit and its pvalue is
+    within the bounds test_gpu_pileup_asm.py derives (1e-9 relative for row sums <= 24, 1e-6 above).  Through the raw ABI each of
+    the three fetches, given cap = n - 1, returns n and leaves `out` as it was."""
+    import torch
+    from hifimeth_amd.pileup import ASM_DTYPE, LOCUS_DTYPE, SITE_DTYPE, MethylationPileup, sites_table
+    from test_gpu_pileup_asm import _np_diff, _rel_err, fisher_exact
+    h = _skeleton_planes()
+    dev = {k: torch.from_numpy(v.copy()).cuda() for k, v in h.items()}
+    pu = MethylationPileup([("c", "ACGT" * 8)])
+    i64 = {k: v.astype(np.int64) for k, v in h.items()}
+    motif3, motif2 = i64["key"] & 3, np.minimum(i64["key"] & 3, 2)
+    fisher = {}
+
+    def planes(names, start=0):
+        return [dev[k][start:] for k in names]
+
+    def check_common(rows, sel, lo, hi, fields, motif):
+        at = np.nonzero(sel[lo:hi])[0] + lo
+        assert len(rows) == len(at) and (rows["gpos"] == at).all() and (rows["reserved"] == 0).all(), (lo, hi)
+        for f in fields:
+            assert (rows[f] == h[f][at]).all(), (f, lo, hi)
+        assert (rows["motif"] == motif[at]).all(), (lo, hi)
+        return at
+
+    def check_asm(rows, at):
+        want = _np_diff(*(i64[k][at] for k in ("pcov1", "ncov1", "pcov2", "ncov2")))
+        assert (rows["diff"].view(np.uint64) == want.view(np.uint64)).all()
+        distinct = np.unique(np.stack([i64[k][at] for k in ("pcov1", "ncov1", "pcov2", "ncov2")] + [rows["pvalue"].view(np.int64)], axis=1), axis=0)
+        for *t, bits in distinct.tolist():                               # every distinct (table, value) once
+            t = tuple(t)
+            if t not in fisher:
+                fisher[t] = fisher_exact(*t)
+            pvalue = float(np.array(bits, np.int64).view(np.float64))
+            assert _rel_err(pvalue, fisher[t]) <= (1e-9 if max(t[0] + t[1], t[2] + t[3]) <= 24 else 1e-6), t
+
+    # one histogram and one table per ctx_mask for the whole planes: a range's rows look their p and q up in it
+    bins, big = pu.site_histogram(0, SK_N, planes=planes(("pcov", "ncov", "key")))
+    assert [int(g) for g in big["gpos"]] == list(SK_BIG)
+    tables = {7: sites_table([0.02, 0.05, 0.013], bins, big), 5: sites_table([0.02, float("nan"), 0.013], bins, big)}
+    assert {m: t.ctx_mask for m, t in tables.items()} == {7: 7, 5: 5}
+    big_at = {int(g): k for k, g in enumerate(big["gpos"])}
+
+    def check_sites(rows, at, table):
+        tot = i64["pcov"][at] + i64["ncov"][at]
+        small = tot < 256
+        for name, tab, bigtab in (("pvalue", table.ptab, table.big_p), ("qvalue", table.qtab, table.big_q)):
+            want = np.empty(len(at))
+            want[small] = tab[motif2[at][small], tot[small], i64["pcov"][at][small]]
+            want[~small] = bigtab[[big_at[int(g)] for g in at[~small]]]
+            assert (rows[name].view(np.uint64) == want.view(np.uint64)).all(), name
+            assert not np.isnan(rows[name]).any()
+
+    seen = dict(loci=0, asm=0, sites=0, big=0)
+    for lo, hi, start in [(lo, hi, 0) for lo, hi in SK_RANGES] + [(5, SK_N - SK_SLICE, SK_SLICE)]:
+        a, b = start + lo, start + hi                                # the same range in the coordinates of the whole planes
+        assert 0 <= a <= b <= SK_N                                   # the engine trusts the caller's range: stay inside the planes
+        kw = dict(plane_base=start)
+        rows = pu.loci(lo, hi, planes=planes(("pcov", "ncov", "key"), start), **kw)
+        seen["loci"] += len(check_common(rows, _sk_loci(h), a, b, ("pcov", "ncov"), motif3))
+        for min_cov in (1, 3):
+            rows = pu.asm(lo, hi, min_cov=min_cov, planes=planes(("pcov1", "ncov1", "pcov2", "ncov2", "key"), start), **kw)
+            at = check_common(rows, _sk_asm(h, min_cov), a, b, ("pcov1", "ncov1", "pcov2", "ncov2"), motif3)
+            check_asm(rows, at)
+            seen["asm"] += len(at)
+        got_bins, got_big = pu.site_histogram(lo, hi, planes=planes(("pcov", "ncov", "key"), start), **kw)
+        want_bins, big_sel = _sk_histogram(h, a, b)
+        assert (got_bins == want_bins).all(), (lo, hi)
+        seen["big"] += len(check_common(got_big, big_sel, a, b, ("pcov", "ncov"), motif2))
+        for mask, table in tables.items():
+            rows = pu.sites(table, lo, hi, planes=planes(("pcov", "ncov", "key"), start), **kw)
+            at = check_common(rows, _sk_sites(h, mask), a, b, ("pcov", "ncov"), motif2)
+            check_sites(rows, at, table)
+            seen["sites"] += len(at)
+    assert min(seen.values()) > 0
+    # the point of the negative counters: such a locus is a row of loci and of nothing else
+    neg = sorted(SK_NEG.values())
+    lo, hi = neg[0] - 1, neg[-1] + 2
+    assert set(neg) <= set(pu.loci(lo, hi, planes=planes(("pcov", "ncov", "key")))["gpos"].tolist())
+    assert not set(neg) & set(pu.asm(lo, hi, min_cov=1, planes=planes(("pcov1", "ncov1", "pcov2", "ncov2", "key")))["gpos"].tolist())
+    assert not set(neg) & set(pu.sites(tables[7], lo, hi, planes=planes(("pcov", "ncov", "key")))["gpos"].tolist())
+
+    # cap one below the count, raw ABI: the count comes back and the sentinel-filled rows stay as they were
+    vp = ctypes.c_void_p
+    ptr3 = [vp(dev[k].data_ptr()) for k in ("pcov", "ncov", "key")]
+    ptr5 = [vp(dev[k].data_ptr()) for k in ("pcov1", "ncov1", "pcov2", "ncov2", "key")]
+    t7 = tables[7]
+    tab_args = (*(x.ctypes.data_as(vp) for x in (t7.ptab, t7.qtab, t7.big, t7.big_p, t7.big_q)), len(t7.big))
+    for dtype, n, call in (
+            (LOCUS_DTYPE, int(_sk_loci(h).sum()), lambda out, cap: pu._L.hm_pileup_fetch_loci(pu._h, *ptr3, 0, 0, SK_N, out, cap)),
+            (ASM_DTYPE, int(_sk_asm(h, 1).sum()), lambda out, cap: pu._L.hm_pileup_fetch_asm(pu._h, *ptr5, 0, 0, SK_N, 1, out, cap)),
+            (SITE_DTYPE, int(_sk_sites(h, 7).sum()), lambda out, cap: pu._L.hm_pileup_fetch_sites(pu._h, *ptr3, 0, 0, SK_N, 7, *tab_args, out, cap))):
+        out = np.frombuffer(b"\xa5" * (dtype.itemsize * n), dtype).copy()
+        assert n > BLK and call(out.ctypes.data_as(vp), n - 1) == n
+        assert out.tobytes() == b"\xa5" * (dtype.itemsize * n), dtype
+        assert call(None, 0) == n
+    pu.close()
+
+
 # ---- submit-time errors ---------------------------------------------------------------------------------------------
 def _submit(pu, read, mods=None):
     """hm_pileup_submit_read as MethylationPileup.add calls it, returning (code, message) instead of raising"""
