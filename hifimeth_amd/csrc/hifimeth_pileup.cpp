@@ -10,6 +10,8 @@
 // -A (ours, with -H): also <prefix>.asm.<ctx>.bed, one row per locus where each haplotype has at least -a (default 5) counted
 // calls:  chrom <tab> soff <tab> soff+1 <tab> diff <tab> pvalue <tab> pcov1 <tab> ncov1 <tab> pcov2 <tab> ncov2
 // (difference of the two methylation percentages, two-sided Fisher exact test; both computed on the GPU).
+// -Q (ours, with -A): a tenth column qvalue in those rows, the Benjamini-Hochberg q of the p-value among all tested loci of the context,
+// and <prefix>.asm.summary.tsv: ctx, tested loci, loci with q <= 0.05, loci with q <= 0.01.
 // -B <control sequence> or -e <r_cpg,r_chg,r_chh> (ours): also <prefix>.sites.<ctx>.bed, the rows of <prefix>.<ctx>.cov.bed followed
 // by pvalue and qvalue -- the one-sided binomial test of the locus against the context's false-positive rate (measured on the
 // unmethylated control sequence, or given) and its Benjamini-Hochberg q-value within the context -- and <prefix>.sites.rates.tsv
@@ -74,6 +76,7 @@ struct PileupOptions {
     bool asm_test = false;    // -A: per-locus haplotype difference + Fisher exact test -> <prefix>.asm.*
     int asm_min_cov = 5;      // -a: minimum pcov + ncov of each haplotype for a locus to be tested
     bool asm_min_cov_given = false;
+    bool asm_q = false;       // -Q: Benjamini-Hochberg q-value per tested locus, <prefix>.asm.summary.tsv
     std::string control;      // -B: name of the unmethylated control sequence -> rates measured there, <prefix>.sites.*
     bool rates_given = false; // -e: the three rates given directly (NaN: context not tested)
     double rates[3] = {0, 0, 0};
@@ -103,6 +106,8 @@ void pileup_usage(const char* exe) {
             "  -A\n    With -H: test every locus where both haplotypes are covered for a difference between them and write\n"
             "    <prefix>.asm.<ctx>.bed: chrom, start, end, hap1 %% - hap2 %%, two-sided Fisher exact p-value, pcov1, ncov1, pcov2, ncov2\n"
             "  -a <int>\n    With -A: minimum coverage (pcov + ncov) of each haplotype at a tested locus\n    Default: 5\n"
+            "  -Q\n    With -A: a tenth column, the Benjamini-Hochberg q-value of the p-value among all tested loci of the context, and\n"
+            "    <prefix>.asm.summary.tsv: ctx, tested loci, loci with q <= 0.05, loci with q <= 0.01\n"
             "  -B <sequence name>\n    Test every covered locus for methylation above the caller's false-positive rate, measured per context on this\n"
             "    unmethylated control sequence (chloroplast, spiked-in lambda) as sum(pcov) / sum(pcov + ncov): write <prefix>.sites.<ctx>.bed,\n"
             "    the rows of <prefix>.<ctx>.cov.bed followed by the one-sided binomial p-value and its Benjamini-Hochberg q-value within\n"
@@ -790,6 +795,64 @@ bool write_asm(hm_pileup_t* pe, const Fasta& fa, int min_cov, FILE* out[3], int 
                             r.pcov1, r.ncov1, r.pcov2, r.ncov2);
         });
 }
+
+// `pileup -H -A -Q` after hm_pileup_count: the tested loci of the whole reference counted per tuple, the p of every tuple that
+// occurs, the q-values (hm_asm_qvalues), then the rows of write_asm with their q looked up (56 B per row on the device and here),
+// and <prefix>.asm.summary.tsv from the table's weights.  1 done, -1 engine error (hm_pileup_last_error), 0 another error (message
+// printed).
+int write_asm_q(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, FILE* out[3], int threads) {
+    static const char* cn[3] = {"CpG", "CHG", "CHH"};
+    int64_t n_loci = 0;
+    for (size_t s = 0; s < fa.names.size(); ++s) n_loci += fa.length[s];
+    const int min_cov = o.asm_min_cov;
+    std::vector<uint64_t> bins((size_t)HM_ASM_BINS, 0);
+    std::vector<hm_asm_t> big(4096);  // big loci are rare at HiFi coverage: room for them in the first call
+    int64_t n_big = hm_pileup_asm_histogram(pe, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, n_loci, min_cov, bins.data(), big.data(),
+                                            (int64_t)big.size());
+    if (n_big > (int64_t)big.size()) {  // nothing was written or added: again, with room for the list
+        big.resize((size_t)n_big);
+        n_big = hm_pileup_asm_histogram(pe, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, n_loci, min_cov, bins.data(), big.data(), n_big);
+    }
+    if (n_big < 0) return -1;
+    big.resize((size_t)n_big);
+    int64_t n_tab = 0;  // the non-empty bins are counted here: one upload and one compaction on the device
+    for (const uint64_t b : bins) n_tab += b != 0;
+    std::vector<hm_asm_bin_t> tab((size_t)n_tab);
+    n_tab = hm_pileup_asm_bin_pvalues(pe, bins.data(), tab.data(), n_tab);
+    if (n_tab < 0) return -1;
+    std::vector<uint64_t>().swap(bins);
+    std::vector<double> big_q(big.size());
+    uint64_t m[3];
+    if (hm_asm_qvalues(tab.data(), n_tab, big.data(), n_big, big_q.data(), m) != HM_OK) {
+        fprintf(stderr, "ERROR: asm: the table of the tested loci is not one the engine wrote\n");
+        return 0;
+    }
+    const bool ok = write_rows<hm_asmq_t>(
+        fa, out, threads,
+        [&](int64_t lo, int64_t hi, hm_asmq_t* dst, int64_t cap) {
+            return hm_pileup_fetch_asm_q(pe, nullptr, nullptr, nullptr, nullptr, nullptr, 0, lo, hi, min_cov, tab.data(), n_tab, big.data(),
+                                         big_q.data(), n_big, dst, cap);
+        },
+        [](const hm_asmq_t& r, int64_t k, char (&buf)[320]) {
+            return snprintf(buf, sizeof buf, "\t%lld\t%lld\t%g\t%.6g\t%d\t%d\t%d\t%d\t%.6g\n", (long long)k, (long long)k + 1, r.diff, r.pvalue,
+                            r.pcov1, r.ncov1, r.pcov2, r.ncov2, r.qvalue);
+        });
+    if (!ok) return -1;
+    uint64_t below[3][2] = {{0, 0}, {0, 0}, {0, 0}};  // loci with q <= 0.05, q <= 0.01
+    const auto tally = [&](uint32_t c, uint64_t loci, double q) {
+        if (q <= 0.05) below[c][0] += loci;
+        if (q <= 0.01) below[c][1] += loci;
+    };
+    for (const hm_asm_bin_t& t : tab) tally(t.bin / (HM_ASM_PAIRS * HM_ASM_PAIRS), t.count, t.qvalue);
+    for (size_t i = 0; i < big.size(); ++i) tally(std::min(big[i].motif, 2u), 1, big_q[i]);
+    const std::string path = o.prefix + ".asm.summary.tsv";
+    FILE* f = fopen(path.c_str(), "w");
+    if (!f) { fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str()); return 0; }
+    for (int c = 0; c < 3; ++c)
+        fprintf(f, "%s\t%llu\t%llu\t%llu\n", cn[c], (unsigned long long)m[c], (unsigned long long)below[c][0], (unsigned long long)below[c][1]);
+    fclose(f);
+    return 1;
+}
 }  // namespace
 
 namespace {
@@ -1011,6 +1074,7 @@ int cmd_pileup(int argc, char** argv) {
         if (a.size() < 2 || a[0] != '-') break;
         if (a == "-H") { o.haplotypes = true; continue; }  // a flag: takes no value
         if (a == "-A") { o.asm_test = true; continue; }
+        if (a == "-Q") { o.asm_q = true; continue; }
         if (a == "-K") { o.kinetics = true; continue; }
         if (i + 1 >= argc) { pileup_usage(argv[0]); return EXIT_FAILURE; }
         if (a == "-q") o.min_mapq = atoi(argv[++i]);
@@ -1042,6 +1106,7 @@ int cmd_pileup(int argc, char** argv) {
     if (argc - i != 3) { pileup_usage(argv[0]); return EXIT_FAILURE; }
     const char* bad_asm = o.asm_test && !o.haplotypes ? "-A needs -H (the test compares the two haplotypes)"
                           : o.asm_min_cov_given && !o.asm_test ? "-a needs -A"
+                          : o.asm_q && !o.asm_test ? "-Q needs -A (the q-values are those of its p-values)"
                           : o.asm_min_cov < 1 ? "-a must be >= 1" : nullptr;
     if (bad_asm) { fprintf(stderr, "ERROR: %s\n", bad_asm); pileup_usage(argv[0]); return EXIT_FAILURE; }
     const char* bad_call = o.call_option_given && !o.kinetics ? "-m, -c, -l, -p and -T need -K (they configure the on-the-fly caller)"
@@ -1061,6 +1126,7 @@ int cmd_pileup(int argc, char** argv) {
             o.min_mapq, o.min_pi, o.threads, o.ref.c_str(), o.bam.c_str(), o.prefix.c_str());
     if (o.haplotypes) fprintf(stderr, "haplotypes: HP 1 / 2 -> %s.hap1.* / %s.hap2.*\n", o.prefix.c_str(), o.prefix.c_str());
     if (o.asm_test) fprintf(stderr, "asm: min haplotype coverage %d -> %s.asm.*\n", o.asm_min_cov, o.prefix.c_str());
+    if (o.asm_q) fprintf(stderr, "asm: Benjamini-Hochberg q-values per context -> tenth column, %s.asm.summary.tsv\n", o.prefix.c_str());
     if (!o.control.empty()) fprintf(stderr, "sites: binomial test against the rates of control sequence %s -> %s.sites.*\n", o.control.c_str(), o.prefix.c_str());
     if (o.rates_given) fprintf(stderr, "sites: binomial test against the rates %g,%g,%g -> %s.sites.*\n", o.rates[0], o.rates[1], o.rates[2], o.prefix.c_str());
     if (o.kinetics)
@@ -1236,9 +1302,10 @@ int cmd_pileup(int argc, char** argv) {
                 return EXIT_FAILURE;
             }
         }
-        const bool ok = write_asm(pe, fa, o.asm_min_cov, out, o.threads);
+        const int rc = o.asm_q ? write_asm_q(pe, fa, o, out, o.threads) : write_asm(pe, fa, o.asm_min_cov, out, o.threads) ? 1 : -1;
         for (FILE* f : out) fclose(f);
-        if (!ok) return die("asm");
+        if (rc < 0) return die("asm");
+        if (rc == 0) { hm_pileup_destroy(pe); return EXIT_FAILURE; }
     }
     if (sites) {
         const int rc = write_sites(pe, fa, o, control_sid, o.threads);

@@ -22,6 +22,8 @@
 //   loci_*          covered loci of a range in ascending order (count per block, scan, write)
 //   asm_*           loci where both haplotypes reach a minimum coverage, compacted the same way (count, loci_scan, write),
 //                   then one thread per compact row: methylation difference + two-sided Fisher exact test
+//   asm_hist / asm_bins_* / asm_q_write   Benjamini-Hochberg q-values of that test (`pileup -H -A -Q`): tested loci counted per
+//                   (context, p1, n1, p2, n2), the non-empty bins compacted and given their p by asm_test_kernel, q looked up per row
 //   sites_*         binomial test per locus (`pileup -B / -e`): control sums, histogram of (motif, pcov, pcov + ncov) through LDS,
 //                   the loci beyond the histogram listed, rows written by table lookup (count, loci_scan, write)
 #include <hip/hip_runtime.h>
@@ -654,6 +656,155 @@ __global__ __launch_bounds__(TPB) void sites_write_kernel(const int32_t* __restr
     });
 }
 
+// ---- Benjamini-Hochberg q-values of the haplotype test (`pileup -H -A -Q`) --------------------------------
+// asm_test_kernel makes pvalue a function of (p1, n1, p2, n2), so BH needs the number of tested loci per tuple and context only.
+// Tuples with both haplotype totals below ASM_T are counted in bins[HM_ASM_BINS] (asm_hist_kernel), the others ("big" loci) listed;
+// the non-empty bins are compacted (asm_bins_*), turned into pseudo-rows for asm_test_kernel (asm_bin_rows_kernel) and take its p
+// (asm_bin_p_kernel); the host solves the q-values (hm_asm_qvalues) and asm_q_write_kernel puts them next to the rows
+// asm_write_kernel + asm_test_kernel produced.  Only counters that pass asm_tested ever form a bin index.
+constexpr int ASM_T = HM_ASM_T;
+constexpr uint32_t ASM_PAIRS = HM_ASM_PAIRS;
+static_assert(ASM_T * (ASM_T + 1) / 2 == HM_ASM_PAIRS && 3ll * HM_ASM_PAIRS * HM_ASM_PAIRS == HM_ASM_BINS, "the dense tuple space");
+
+// of a tested locus: both haplotype totals below ASM_T
+__device__ __forceinline__ bool asm_dense(int32_t p1, int32_t n1, int32_t p2, int32_t n2) {
+    return (int64_t)p1 + n1 < ASM_T && (int64_t)p2 + n2 < ASM_T;
+}
+__device__ __forceinline__ uint32_t asm_pair(int32_t p, int32_t n) {  // 0 <= p, n and p + n < ASM_T -> [0, ASM_PAIRS)
+    const uint32_t t = (uint32_t)(p + n);
+    return t * (t + 1) / 2 + (uint32_t)p;
+}
+__device__ __forceinline__ void asm_unpair(uint32_t pair, int32_t& p, int32_t& n) {
+    uint32_t t = 0;
+    while ((t + 1) * (t + 2) / 2 <= pair) ++t;
+    p = (int32_t)(pair - t * (t + 1) / 2);
+    n = (int32_t)t - p;
+}
+__device__ __forceinline__ uint32_t asm_bin(uint32_t key, int32_t p1, int32_t n1, int32_t p2, int32_t n2) {  // of a tested dense locus
+    return (site_motif(key) * ASM_PAIRS + asm_pair(p1, n1)) * ASM_PAIRS + asm_pair(p2, n2);
+}
+
+// bins[asm_bin] += 1 for every tested dense locus of [lo, hi), block_big[b] = number of tested big loci in the b-th LOCI_PER_BLOCK
+// loci.  Tested loci are a few percent of the reference and spread over far more bins than LDS holds (104 MB): one 64-bit global
+// atomic each.
+__global__ __launch_bounds__(TPB) void asm_hist_kernel(const int32_t* __restrict__ pcov1, const int32_t* __restrict__ ncov1,
+                                                        const int32_t* __restrict__ pcov2, const int32_t* __restrict__ ncov2,
+                                                        const uint32_t* __restrict__ key, int64_t lo, int64_t hi, int32_t min_cov,
+                                                        unsigned long long* __restrict__ bins, int32_t* __restrict__ block_big) {
+    count_block(lo, hi, block_big, [&](int64_t i) {
+        const int32_t p1 = pcov1[i], n1 = ncov1[i], p2 = pcov2[i], n2 = ncov2[i];
+        if (!asm_tested(p1, n1, p2, n2, min_cov)) return false;
+        if (!asm_dense(p1, n1, p2, n2)) return true;
+        atomicAdd(&bins[asm_bin(key[i], p1, n1, p2, n2)], 1ull);
+        return false;
+    });
+}
+
+// the big loci of the range, where asm_hist_kernel counted them: rows as asm_write_kernel's, for asm_test_kernel
+__global__ __launch_bounds__(TPB) void asm_big_write_kernel(const int32_t* __restrict__ pcov1, const int32_t* __restrict__ ncov1,
+                                                             const int32_t* __restrict__ pcov2, const int32_t* __restrict__ ncov2,
+                                                             const uint32_t* __restrict__ key, int64_t plane_base, int64_t lo,
+                                                             int64_t hi, int32_t min_cov, const int64_t* __restrict__ offs,
+                                                             hm_asm_t* __restrict__ out) {
+    compact_block(lo, hi, offs, out, [&](int64_t i, hm_asm_t& r) {
+        const int32_t p1 = pcov1[i], n1 = ncov1[i], p2 = pcov2[i], n2 = ncov2[i];
+        if (!asm_tested(p1, n1, p2, n2, min_cov) || asm_dense(p1, n1, p2, n2)) return false;
+        r.gpos = plane_base + i;
+        r.pcov1 = p1;
+        r.ncov1 = n1;
+        r.pcov2 = p2;
+        r.ncov2 = n2;
+        r.motif = key[i] & 3u;
+        r.reserved = 0;
+        r.diff = 0.0;
+        r.pvalue = 0.0;
+        return true;
+    });
+}
+
+// the non-empty bins of bins[0, n) in ascending index: the skeleton over the bin array instead of a plane range
+__global__ __launch_bounds__(TPB) void asm_bins_count_kernel(const unsigned long long* __restrict__ bins, int64_t n,
+                                                              int32_t* __restrict__ block_counts) {
+    count_block(0, n, block_counts, [&](int64_t i) { return bins[i] != 0ull; });
+}
+
+__global__ __launch_bounds__(TPB) void asm_bins_write_kernel(const unsigned long long* __restrict__ bins, int64_t n,
+                                                              const int64_t* __restrict__ offs, hm_asm_bin_t* __restrict__ out) {
+    compact_block(0, n, offs, out, [&](int64_t i, hm_asm_bin_t& r) {
+        const unsigned long long c = bins[i];
+        if (!c) return false;
+        r.bin = (uint32_t)i;
+        r.reserved = 0;
+        r.count = c;
+        r.pvalue = 0.0;
+        r.qvalue = __longlong_as_double(0x7ff8000000000000ll);
+        return true;
+    });
+}
+
+// One thread per compact bin: the hm_asm_t row of a locus carrying the bin's tuple (gpos = the bin index, motif = its context).
+__global__ __launch_bounds__(TPB) void asm_bin_rows_kernel(const hm_asm_bin_t* __restrict__ tab, int64_t n, hm_asm_t* __restrict__ rows) {
+    const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t b = tab[i].bin;
+    hm_asm_t r;
+    r.gpos = b;
+    asm_unpair((b / ASM_PAIRS) % ASM_PAIRS, r.pcov1, r.ncov1);
+    asm_unpair(b % ASM_PAIRS, r.pcov2, r.ncov2);
+    r.motif = b / (ASM_PAIRS * ASM_PAIRS);
+    r.reserved = 0;
+    r.diff = 0.0;
+    r.pvalue = 0.0;
+    rows[i] = r;
+}
+
+// ... and what asm_test_kernel computed for it, back into the bin's entry
+__global__ __launch_bounds__(TPB) void asm_bin_p_kernel(const hm_asm_t* __restrict__ rows, int64_t n, hm_asm_bin_t* __restrict__ tab) {
+    const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (i < n) tab[i].pvalue = rows[i].pvalue;
+}
+
+// One thread per tested row (asm_write_kernel's, after asm_test_kernel): the row with its qvalue -- a dense row's from the entry of
+// its bin in tab[0, n_tab) (ascending in bin), a big row's from big_q at its place in big[0, n_big) (ascending in gpos); NaN when
+// the entry is not there (a table made with another min_cov, a list that misses the locus).
+__global__ __launch_bounds__(TPB) void asm_q_write_kernel(const hm_asm_t* __restrict__ rows, int64_t n_rows,
+                                                           const hm_asm_bin_t* __restrict__ tab, int64_t n_tab,
+                                                           const hm_asm_t* __restrict__ big, const double* __restrict__ big_q,
+                                                           int64_t n_big, hm_asmq_t* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (i >= n_rows) return;
+    const hm_asm_t r = rows[i];
+    double q = __longlong_as_double(0x7ff8000000000000ll);
+    if (asm_dense(r.pcov1, r.ncov1, r.pcov2, r.ncov2)) {
+        const uint32_t bin = asm_bin(r.motif, r.pcov1, r.ncov1, r.pcov2, r.ncov2);
+        int64_t a = 0, b = n_tab;  // first entry with bin >= the row's
+        while (a < b) {
+            const int64_t mid = (a + b) >> 1;
+            if (tab[mid].bin < bin) a = mid + 1; else b = mid;
+        }
+        if (a < n_tab && tab[a].bin == bin) q = tab[a].qvalue;
+    } else {
+        int64_t a = 0, b = n_big;  // first entry with gpos >= the row's
+        while (a < b) {
+            const int64_t mid = (a + b) >> 1;
+            if (big[mid].gpos < r.gpos) a = mid + 1; else b = mid;
+        }
+        if (a < n_big && big[a].gpos == r.gpos) q = big_q[a];
+    }
+    hm_asmq_t o;
+    o.gpos = r.gpos;
+    o.pcov1 = r.pcov1;
+    o.ncov1 = r.ncov1;
+    o.pcov2 = r.pcov2;
+    o.ncov2 = r.ncov2;
+    o.motif = r.motif;
+    o.reserved = r.reserved;
+    o.diff = r.diff;
+    o.pvalue = r.pvalue;
+    o.qvalue = q;
+    out[i] = o;
+}
+
 }  // namespace
 
 // ================================================ host ==========================================================
@@ -695,6 +846,9 @@ struct hm_pileup {
     // `pileup -B / -e`, allocated by the first call that needs them: control sums, 3 x 256 x 256 bins, ptab + qtab, the big loci
     // (the histogram's list, or the caller's with p and q behind it: they stay while hm_pileup_fetch_sites writes d_rows)
     DevBuf d_ssums{EXACT}, d_sbins{EXACT}, d_stab{EXACT}, d_sbig{HALF}, d_sbigpq{HALF};
+    // `pileup -H -A -Q`, allocated by the first call that needs them: HM_ASM_BINS bins (104 MB), hm_asm_t rows (the big loci, the
+    // bins' pseudo-rows, the rows hm_pileup_fetch_asm_q adds q to), and the caller's table, big list and its q for that lookup
+    DevBuf d_abins{EXACT}, d_arows{HALF}, d_atab{HALF}, d_abig{HALF}, d_abigq{HALF};
     int64_t n_recs = 0;
     bool bins_ready = false;
 
@@ -775,10 +929,10 @@ void write_rows(hm_pileup* p, DevBuf& buf, int64_t total, Row* out, Write launch
 
 // The rows of the non-empty range [lo, hi) in ascending order -> their number, or an error code.  launch_count(grid, block_counts)
 // and launch_write(grid, offs, dst, total) start a count_block and a compact_block kernel with the same selection;
-// before_write() uploads what the write needs.  More rows than cap, or no `out`: only counted, nothing is written.
-template <class Row, class Count, class Before, class Write>
-int64_t compact_rows(hm_pileup* p, int64_t lo, int64_t hi, Row* out, int64_t cap, Count launch_count, Before before_write,
-                     Write launch_write) {
+// before_write() uploads what the write needs.  room(total) names the host memory for the rows once their number is known, or
+// NULL: only counted, nothing is written.
+template <class Row, class Room, class Count, class Before, class Write>
+int64_t compact_rows_to(hm_pileup* p, int64_t lo, int64_t hi, Room room, Count launch_count, Before before_write, Write launch_write) {
     const int64_t nblk = range_blocks(lo, hi);
     if (nblk >= (int64_t(1) << 31)) return pfail(p, HM_EINVAL, "range too large: fetch per sequence");
     return guarded(p, [&]() -> int64_t {
@@ -787,11 +941,102 @@ int64_t compact_rows(hm_pileup* p, int64_t lo, int64_t hi, Row* out, int64_t cap
         p->d_offs.reserve(8 * ((size_t)nblk + 1));
         launch_count(grid, p->d_blk.as<int32_t>());
         const int64_t total = scan_blocks(p, nblk);
-        if (total > cap || !out || total == 0) return total;
+        Row* out = total ? room(total) : nullptr;
+        if (!out) return total;
         before_write();
         write_rows(p, p->d_rows, total, out, [&](const int64_t* offs, Row* dst) { launch_write(grid, offs, dst, total); });
         return total;
     });
+}
+
+// ... into the caller's out[cap]: more rows than cap, or no `out`: only counted
+template <class Row, class Count, class Before, class Write>
+int64_t compact_rows(hm_pileup* p, int64_t lo, int64_t hi, Row* out, int64_t cap, Count launch_count, Before before_write,
+                     Write launch_write) {
+    return compact_rows_to<Row>(
+        p, lo, hi, [&](int64_t total) { return total > cap ? nullptr : out; }, launch_count, before_write, launch_write);
+}
+
+// log n!, n < LFACT_N, for asm_test_kernel: uploaded once per engine
+void ensure_lfact(hm_pileup* p) {
+    if (p->d_lfact.p) return;
+    const std::vector<double>& t = host_lfact();
+    p->d_lfact.reserve(sizeof(double) * t.size());
+    HIP_TRY(hipMemcpyAsync(p->d_lfact.p, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+}
+
+struct AsmPlanes {
+    const int32_t *p1, *n1, *p2, *n2;
+    const uint32_t* ky;
+};
+
+// The arguments every call over the haplotype planes shares, by hm_pileup_fetch_asm's rules: the caller's five planes or, where all
+// are NULL, the engine's own partition and key planes (plane_base is then 0).  HM_OK, or the error recorded in the name of `who`.
+int asm_planes(hm_pileup* p, const char* who, const void* pcov1, const void* ncov1, const void* pcov2, const void* ncov2,
+               const void* key, int64_t& plane_base, int64_t lo, int64_t hi, int32_t min_cov, AsmPlanes& s) {
+    const std::string w = who;
+    if (min_cov < 1) return pfail(p, HM_EINVAL, w + ": min_cov must be >= 1");
+    if (lo < 0 || hi < lo) return pfail(p, HM_EINVAL, w + ": bad range");
+    const int given = (pcov1 != nullptr) + (ncov1 != nullptr) + (pcov2 != nullptr) + (ncov2 != nullptr) + (key != nullptr);
+    if (given != 0 && given != 5) return pfail(p, HM_EINVAL, w + ": give all five planes or none");
+    s = AsmPlanes{static_cast<const int32_t*>(pcov1), static_cast<const int32_t*>(ncov1), static_cast<const int32_t*>(pcov2),
+                  static_cast<const int32_t*>(ncov2), static_cast<const uint32_t*>(key)};
+    if (given) return HM_OK;
+    if (p->partitions != 2 || !p->hp_pcov[0] || !p->hp_pcov[1] || !p->key)
+        return pfail(p, HM_ESTATE, w + " without partition planes (option partitions = 2, then hm_pileup_set_reference)");
+    if (!p->seq_off.empty() && hi > p->seq_off.back()) return pfail(p, HM_EINVAL, w + ": range past the reference");
+    s = AsmPlanes{p->hp_pcov[0], p->hp_ncov[0], p->hp_pcov[1], p->hp_ncov[1], p->key};
+    plane_base = 0;
+    return HM_OK;
+}
+
+// The non-empty bins of d_abins in ascending index, in one count and one write pass -> their number, or an error code
+// (compact_rows_to's rule for room).  with_p: each entry's pvalue is what asm_test_kernel gives a row carrying the bin's tuple;
+// else it is 0.
+template <class Room>
+int64_t nonempty_bins(hm_pileup* p, Room room, bool with_p) {
+    hipStream_t st = p->stream;
+    const unsigned long long* bins = p->d_abins.as<unsigned long long>();
+    return compact_rows_to<hm_asm_bin_t>(
+        p, 0, HM_ASM_BINS, room,
+        [&](dim3 grid, int32_t* counts) { hipLaunchKernelGGL(asm_bins_count_kernel, grid, dim3(TPB), 0, st, bins, (int64_t)HM_ASM_BINS, counts); },
+        [&] { if (with_p) ensure_lfact(p); },
+        [&](dim3 grid, const int64_t* offs, hm_asm_bin_t* dst, int64_t total) {
+            hipLaunchKernelGGL(asm_bins_write_kernel, grid, dim3(TPB), 0, st, bins, (int64_t)HM_ASM_BINS, offs, dst);
+            if (!with_p) return;
+            const dim3 per_row((unsigned)((total + TPB - 1) / TPB));
+            p->d_arows.reserve(sizeof(hm_asm_t) * (size_t)total);
+            hm_asm_t* rows = p->d_arows.as<hm_asm_t>();
+            hipLaunchKernelGGL(asm_bin_rows_kernel, per_row, dim3(TPB), 0, st, dst, total, rows);
+            hipLaunchKernelGGL(asm_test_kernel, per_row, dim3(TPB), 0, st, rows, total, p->d_lfact.as<double>());
+            hipLaunchKernelGGL(asm_bin_p_kernel, per_row, dim3(TPB), 0, st, rows, total, dst);
+        });
+}
+
+// Benjamini-Hochberg over entries that each stand for `loci` loci sharing one p (R's p.adjust(method = "BH") among m loci): over
+// the distinct p in ascending order R = the loci with p <= it, then from the largest p down q = the running minimum of
+// min(1, p * (double)m / (double)R); store(where, q) takes the q of every entry.
+struct BhEntry {
+    double p;
+    uint64_t loci;
+    int64_t where;
+};
+template <class Store>
+void bh_qvalues(std::vector<BhEntry>& ent, uint64_t m, Store store) {
+    std::sort(ent.begin(), ent.end(), [](const BhEntry& a, const BhEntry& b) { return a.p < b.p; });
+    std::vector<uint64_t> R(ent.size());
+    uint64_t seen = 0;
+    for (size_t a = 0; a < ent.size();) {
+        size_t b = a;
+        while (b < ent.size() && ent[b].p == ent[a].p) seen += ent[b++].loci;
+        for (; a < b; ++a) R[a] = seen;
+    }
+    double q = 1.0;
+    for (size_t a = ent.size(); a-- > 0;) {
+        q = std::min(q, std::min(1.0, ent[a].p * (double)m / (double)R[a]));
+        store(ent[a].where, q);
+    }
 }
 
 void ensure_bins(hm_pileup* p) {
@@ -1255,38 +1500,150 @@ int64_t hm_pileup_fetch_asm(hm_pileup_t* p, const void* pcov1, const void* ncov1
                             const void* key, int64_t plane_base, int64_t lo, int64_t hi, int32_t min_cov, hm_asm_t* out,
                             int64_t cap) {
     if (!p) return HM_EINVAL;
-    if (min_cov < 1) return pfail(p, HM_EINVAL, "hm_pileup_fetch_asm: min_cov must be >= 1");
-    if (lo < 0 || hi < lo) return pfail(p, HM_EINVAL, "hm_pileup_fetch_asm: bad range");
-    const int given = (pcov1 != nullptr) + (ncov1 != nullptr) + (pcov2 != nullptr) + (ncov2 != nullptr) + (key != nullptr);
-    if (given != 0 && given != 5) return pfail(p, HM_EINVAL, "hm_pileup_fetch_asm: give all five planes or none");
-    const int32_t *p1 = static_cast<const int32_t*>(pcov1), *n1 = static_cast<const int32_t*>(ncov1);
-    const int32_t *p2 = static_cast<const int32_t*>(pcov2), *n2 = static_cast<const int32_t*>(ncov2);
-    const uint32_t* ky = static_cast<const uint32_t*>(key);
-    if (!given) {
-        if (p->partitions != 2 || !p->hp_pcov[0] || !p->hp_pcov[1] || !p->key)
-            return pfail(p, HM_ESTATE, "hm_pileup_fetch_asm without partition planes (option partitions = 2, then hm_pileup_set_reference)");
-        if (!p->seq_off.empty() && hi > p->seq_off.back()) return pfail(p, HM_EINVAL, "hm_pileup_fetch_asm: range past the reference");
-        p1 = p->hp_pcov[0]; n1 = p->hp_ncov[0]; p2 = p->hp_pcov[1]; n2 = p->hp_ncov[1]; ky = p->key;
-        plane_base = 0;
-    }
+    AsmPlanes s;
+    const int rc = asm_planes(p, "hm_pileup_fetch_asm", pcov1, ncov1, pcov2, ncov2, key, plane_base, lo, hi, min_cov, s);
+    if (rc != HM_OK) return rc;
     if (hi == lo) return 0;
     hipStream_t st = p->stream;
     return compact_rows(
         p, lo, hi, out, cap,
         [&](dim3 grid, int32_t* counts) {
-            hipLaunchKernelGGL(asm_count_kernel, grid, dim3(TPB), 0, st, p1, n1, p2, n2, lo, hi, min_cov, counts);
+            hipLaunchKernelGGL(asm_count_kernel, grid, dim3(TPB), 0, st, s.p1, s.n1, s.p2, s.n2, lo, hi, min_cov, counts);
         },
-        [&] {
-            if (p->d_lfact.p) return;  // log n!, n < LFACT_N: once per engine
-            const std::vector<double>& t = host_lfact();
-            p->d_lfact.reserve(sizeof(double) * t.size());
-            HIP_TRY(hipMemcpyAsync(p->d_lfact.p, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipStreamSynchronize(st));
-        },
+        [&] { ensure_lfact(p); },
         [&](dim3 grid, const int64_t* offs, hm_asm_t* dst, int64_t total) {
-            hipLaunchKernelGGL(asm_write_kernel, grid, dim3(TPB), 0, st, p1, n1, p2, n2, ky, plane_base, lo, hi, min_cov, offs, dst);
+            hipLaunchKernelGGL(asm_write_kernel, grid, dim3(TPB), 0, st, s.p1, s.n1, s.p2, s.n2, s.ky, plane_base, lo, hi, min_cov, offs, dst);
             hipLaunchKernelGGL(asm_test_kernel, dim3((unsigned)((total + TPB - 1) / TPB)), dim3(TPB), 0, st, dst, total,
                                p->d_lfact.as<double>());
+        });
+}
+
+// ---- `pileup -H -A -Q` ------------------------------------------------------------------------------------------------------------
+int64_t hm_pileup_asm_histogram(hm_pileup_t* p, const void* pcov1, const void* ncov1, const void* pcov2, const void* ncov2,
+                                const void* key, int64_t plane_base, int64_t lo, int64_t hi, int32_t min_cov, uint64_t* bins,
+                                hm_asm_t* big, int64_t cap) {
+    if (!p) return HM_EINVAL;
+    if (!bins) return pfail(p, HM_EINVAL, "hm_pileup_asm_histogram: no bins");
+    AsmPlanes s;
+    const int rc = asm_planes(p, "hm_pileup_asm_histogram", pcov1, ncov1, pcov2, ncov2, key, plane_base, lo, hi, min_cov, s);
+    if (rc != HM_OK) return rc;
+    if (hi == lo) return 0;
+    const int64_t nblk = range_blocks(lo, hi);
+    if (nblk >= (int64_t(1) << 31)) return pfail(p, HM_EINVAL, "range too large: histogram per sequence");
+    hipStream_t st = p->stream;
+    const int64_t n_big = guarded(p, [&]() -> int64_t {
+        p->d_blk.reserve(4 * (size_t)nblk);
+        p->d_offs.reserve(8 * ((size_t)nblk + 1));
+        p->d_abins.reserve(HM_ASM_BINS * sizeof(unsigned long long));
+        HIP_TRY(hipMemsetAsync(p->d_abins.p, 0, HM_ASM_BINS * sizeof(unsigned long long), st));
+        hipLaunchKernelGGL(asm_hist_kernel, dim3((unsigned)nblk), dim3(TPB), 0, st, s.p1, s.n1, s.p2, s.n2, s.ky, lo, hi, min_cov,
+                           p->d_abins.as<unsigned long long>(), p->d_blk.as<int32_t>());
+        const int64_t n = scan_blocks(p, nblk);
+        if (n == 0 || n > cap || !big) return n;
+        ensure_lfact(p);
+        write_rows(p, p->d_arows, n, big, [&](const int64_t* offs, hm_asm_t* dst) {
+            hipLaunchKernelGGL(asm_big_write_kernel, dim3((unsigned)nblk), dim3(TPB), 0, st, s.p1, s.n1, s.p2, s.n2, s.ky, plane_base, lo,
+                               hi, min_cov, offs, dst);
+            hipLaunchKernelGGL(asm_test_kernel, dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, st, dst, n, p->d_lfact.as<double>());
+        });
+        return n;
+    });
+    if (n_big < 0 || n_big > cap || (n_big && !big)) return n_big;
+    // the range's non-empty bins (few next to HM_ASM_BINS) come to the host compacted and are added there
+    std::vector<hm_asm_bin_t> tab;
+    const int64_t n_tab = nonempty_bins(p, [&](int64_t n) { tab.resize((size_t)n); return tab.data(); }, false);
+    if (n_tab < 0) return n_tab;
+    for (const hm_asm_bin_t& t : tab) bins[t.bin] += t.count;
+    return n_big;
+}
+
+int64_t hm_pileup_asm_bin_pvalues(hm_pileup_t* p, const uint64_t* bins, hm_asm_bin_t* out, int64_t cap) {
+    if (!p) return HM_EINVAL;
+    if (!bins) return pfail(p, HM_EINVAL, "hm_pileup_asm_bin_pvalues: no bins");
+    // a tested locus has no haplotype total of 0: pair 0 on either side is no tuple the histogram counts
+    for (size_t c = 0; c < 3; ++c)
+        for (size_t u = 0; u < ASM_PAIRS; ++u)
+            if (bins[(c * ASM_PAIRS + u) * ASM_PAIRS] || bins[c * ASM_PAIRS * ASM_PAIRS + u])
+                return pfail(p, HM_EINVAL, "hm_pileup_asm_bin_pvalues: a non-empty bin of a haplotype without calls");
+    const int rc = guarded(p, [&] {
+        p->d_abins.reserve(HM_ASM_BINS * sizeof(unsigned long long));
+        HIP_TRY(hipMemcpyAsync(p->d_abins.p, bins, HM_ASM_BINS * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        return HM_OK;
+    });
+    return rc != HM_OK ? rc : nonempty_bins(p, [&](int64_t n) { return n > cap ? nullptr : out; }, true);
+}
+
+int hm_asm_qvalues(hm_asm_bin_t* tab, int64_t n_tab, const hm_asm_t* big, int64_t n_big, double* big_q, uint64_t m[3]) {
+    if (n_tab < 0 || n_big < 0 || (n_tab && !tab) || (n_big && (!big || !big_q)) || !m) return HM_EINVAL;
+    const auto is_p = [](double v) { return v >= DBL_MIN && v <= 1.0; };  // false for NaN
+    for (int64_t i = 0; i < n_tab; ++i)
+        if (tab[i].bin >= (uint32_t)HM_ASM_BINS || (i && tab[i].bin <= tab[i - 1].bin) || tab[i].count == 0 || !is_p(tab[i].pvalue))
+            return HM_EINVAL;
+    for (int64_t i = 0; i < n_big; ++i) {
+        const hm_asm_t& b = big[i];
+        if (b.motif > 3u || (b.pcov1 | b.ncov1 | b.pcov2 | b.ncov2) < 0 || !is_p(b.pvalue) ||
+            ((int64_t)b.pcov1 + b.ncov1 < ASM_T && (int64_t)b.pcov2 + b.ncov2 < ASM_T))
+            return HM_EINVAL;
+    }
+    std::vector<BhEntry> ent;
+    int64_t i = 0;
+    for (uint32_t c = 0; c < 3; ++c) {
+        ent.clear();
+        m[c] = 0;
+        for (; i < n_tab && tab[i].bin / (ASM_PAIRS * ASM_PAIRS) == c; ++i) {  // (ascending in bin: the contexts follow each other)
+            ent.push_back(BhEntry{tab[i].pvalue, tab[i].count, i});
+            m[c] += tab[i].count;
+        }
+        for (int64_t j = 0; j < n_big; ++j)
+            if (std::min(big[j].motif, 2u) == c) {
+                ent.push_back(BhEntry{big[j].pvalue, 1, ~j});
+                ++m[c];
+            }
+        bh_qvalues(ent, m[c], [&](int64_t where, double q) {
+            if (where >= 0) tab[where].qvalue = q;
+            else big_q[~where] = q;
+        });
+    }
+    return HM_OK;
+}
+
+int64_t hm_pileup_fetch_asm_q(hm_pileup_t* p, const void* pcov1, const void* ncov1, const void* pcov2, const void* ncov2,
+                              const void* key, int64_t plane_base, int64_t lo, int64_t hi, int32_t min_cov, const hm_asm_bin_t* tab,
+                              int64_t n_tab, const hm_asm_t* big, const double* big_q, int64_t n_big, hm_asmq_t* out, int64_t cap) {
+    if (!p) return HM_EINVAL;
+    if (n_tab < 0 || n_big < 0 || (n_tab && !tab) || (n_big && (!big || !big_q))) return pfail(p, HM_EINVAL, "hm_pileup_fetch_asm_q: bad table");
+    AsmPlanes s;
+    const int rc = asm_planes(p, "hm_pileup_fetch_asm_q", pcov1, ncov1, pcov2, ncov2, key, plane_base, lo, hi, min_cov, s);
+    if (rc != HM_OK) return rc;
+    if (hi == lo) return 0;
+    hipStream_t st = p->stream;
+    return compact_rows(
+        p, lo, hi, out, cap,
+        [&](dim3 grid, int32_t* counts) {
+            hipLaunchKernelGGL(asm_count_kernel, grid, dim3(TPB), 0, st, s.p1, s.n1, s.p2, s.n2, lo, hi, min_cov, counts);
+        },
+        [&] {
+            ensure_lfact(p);
+            if (n_tab) {
+                p->d_atab.reserve(sizeof(hm_asm_bin_t) * (size_t)n_tab);
+                HIP_TRY(hipMemcpyAsync(p->d_atab.p, tab, sizeof(hm_asm_bin_t) * (size_t)n_tab, hipMemcpyHostToDevice, st));
+            }
+            if (n_big) {
+                p->d_abig.reserve(sizeof(hm_asm_t) * (size_t)n_big);
+                p->d_abigq.reserve(sizeof(double) * (size_t)n_big);
+                HIP_TRY(hipMemcpyAsync(p->d_abig.p, big, sizeof(hm_asm_t) * (size_t)n_big, hipMemcpyHostToDevice, st));
+                HIP_TRY(hipMemcpyAsync(p->d_abigq.p, big_q, sizeof(double) * (size_t)n_big, hipMemcpyHostToDevice, st));
+            }
+        },
+        [&](dim3 grid, const int64_t* offs, hm_asmq_t* dst, int64_t total) {  // hm_pileup_fetch_asm's rows, then q next to each
+            const dim3 per_row((unsigned)((total + TPB - 1) / TPB));
+            p->d_arows.reserve(sizeof(hm_asm_t) * (size_t)total);
+            hm_asm_t* rows = p->d_arows.as<hm_asm_t>();
+            hipLaunchKernelGGL(asm_write_kernel, grid, dim3(TPB), 0, st, s.p1, s.n1, s.p2, s.n2, s.ky, plane_base, lo, hi, min_cov, offs, rows);
+            hipLaunchKernelGGL(asm_test_kernel, per_row, dim3(TPB), 0, st, rows, total, p->d_lfact.as<double>());
+            hipLaunchKernelGGL(asm_q_write_kernel, per_row, dim3(TPB), 0, st, rows, total, p->d_atab.as<hm_asm_bin_t>(), n_tab,
+                               p->d_abig.as<hm_asm_t>(), p->d_abigq.as<double>(), n_big, dst);
         });
 }
 
@@ -1378,12 +1735,7 @@ int hm_sites_table(const double rates[3], const uint64_t* bins, const hm_locus_t
     std::fill(qtab, qtab + HM_SITE_BINS, nan);
     std::fill(big_p, big_p + n_big, nan);
     std::fill(big_q, big_q + n_big, nan);
-    struct Entry {      // the loci that share one p: a bin (where >= 0: its index) or one big locus (where < 0: ~index)
-        double p;
-        uint64_t loci;
-        int64_t where;
-    };
-    std::vector<Entry> ent;
+    std::vector<BhEntry> ent;  // the loci that share one p: a bin (where >= 0: its index) or one big locus (where < 0: ~index)
     for (int c = 0; c < 3; ++c) {
         m[c] = std::accumulate(bins + c * SITE_N * SITE_N, bins + (c + 1) * SITE_N * SITE_N, uint64_t(0));
         for (int64_t i = 0; i < n_big; ++i) m[c] += big[i].motif == (uint32_t)c;
@@ -1396,7 +1748,7 @@ int hm_sites_table(const double rates[3], const uint64_t* bins, const hm_locus_t
             for (int k = 0; k <= n; ++k) {
                 const int t = (c * SITE_N + n) * SITE_N + k;
                 ptab[t] = pvalue(k, n);
-                if (bins[t]) ent.push_back(Entry{ptab[t], bins[t], t});
+                if (bins[t]) ent.push_back(BhEntry{ptab[t], bins[t], t});
             }
         for (int64_t i = 0; i < n_big; ++i) {
             if (big[i].motif != (uint32_t)c) continue;
@@ -1404,23 +1756,12 @@ int hm_sites_table(const double rates[3], const uint64_t* bins, const hm_locus_t
             const int64_t j = ent.empty() || ent.back().where >= 0 ? -1 : ~ent.back().where;
             big_p[i] = j >= 0 && big[j].pcov == big[i].pcov && big[j].ncov == big[i].ncov
                            ? big_p[j] : pvalue(big[i].pcov, (int64_t)big[i].pcov + big[i].ncov);
-            ent.push_back(Entry{big_p[i], 1, ~i});
+            ent.push_back(BhEntry{big_p[i], 1, ~i});
         }
-        std::sort(ent.begin(), ent.end(), [](const Entry& a, const Entry& b) { return a.p < b.p; });
-        // R below the distinct p (the loci with p <= it), then q from the largest p down
-        std::vector<uint64_t> R(ent.size());
-        uint64_t seen = 0;
-        for (size_t a = 0; a < ent.size();) {
-            size_t b = a;
-            while (b < ent.size() && ent[b].p == ent[a].p) seen += ent[b++].loci;
-            for (; a < b; ++a) R[a] = seen;
-        }
-        double q = 1.0;
-        for (size_t a = ent.size(); a-- > 0;) {
-            q = std::min(q, std::min(1.0, ent[a].p * (double)m[c] / (double)R[a]));
-            if (ent[a].where >= 0) qtab[ent[a].where] = q;
-            else big_q[~ent[a].where] = q;
-        }
+        bh_qvalues(ent, m[c], [&](int64_t where, double q) {
+            if (where >= 0) qtab[where] = q;
+            else big_q[~where] = q;
+        });
     }
     return HM_OK;
 }

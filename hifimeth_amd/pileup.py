@@ -17,6 +17,11 @@ Allele-specific methylation (`pileup -H -A`): `pu.asm(min_cov=5)` are the loci w
 counted calls, with the difference of the two methylation percentages and the two-sided Fisher exact p-value of
 [[pcov1, ncov1], [pcov2, ncov2]], both computed on the device; `pu.asm_bed(rows)` is the text of <prefix>.asm.<ctx>.bed.
 
+With q-values (`pileup -H -A -Q`): `pu.asm_histogram()` counts the tested loci per (context, pcov1, ncov1, pcov2, ncov2) -- a fixed
+table of 3 x 2080 x 2080 bins for haplotype totals below 64, the few loci beyond it listed --, `pu.asm_bin_pvalues(bins)` gives every
+tuple that occurs the p the device computes for it, `asm_qvalues(tab, big)` -- host only, the C library's -- solves the
+Benjamini-Hochberg q-values per context, and `pu.asm(table=...)` are the rows with a `qvalue` field, the tenth column of `asm_bed`.
+
 Binomial test per locus (`pileup -B control` / `-e r,r,r`): is a locus methylated at all, against the caller's false-positive
 rate?  `pu.control_sums(lo, hi)` over an unmethylated control sequence gives the rates (`rates_from_sums`), `pu.site_histogram()`
 counts the loci per (motif, pcov, pcov + ncov), `sites_table(rates, bins, big)` -- host only, the C library's -- solves p-values
@@ -45,6 +50,10 @@ MOD_DTYPE = np.dtype([("qoff", "<i4"), ("strand", "u1"), ("unmod_base", "S1"), (
 LOCUS_DTYPE = np.dtype([("gpos", "<i8"), ("pcov", "<i4"), ("ncov", "<i4"), ("motif", "<u4"), ("reserved", "<u4")])
 ASM_DTYPE = np.dtype([("gpos", "<i8"), ("pcov1", "<i4"), ("ncov1", "<i4"), ("pcov2", "<i4"), ("ncov2", "<i4"), ("motif", "<u4"),
                       ("reserved", "<u4"), ("diff", "<f8"), ("pvalue", "<f8")])     # hm_asm_t, 48 bytes
+ASMQ_DTYPE = np.dtype(ASM_DTYPE.descr + [("qvalue", "<f8")])                          # hm_asmq_t, 56 bytes
+ASM_BIN_DTYPE = np.dtype([("bin", "<u4"), ("reserved", "<u4"), ("count", "<u8"), ("pvalue", "<f8"), ("qvalue", "<f8")])  # hm_asm_bin_t, 32 bytes
+ASM_T, ASM_PAIRS = 64, 2080                                                           # HM_ASM_T, HM_ASM_PAIRS
+ASM_BINS = 3 * ASM_PAIRS * ASM_PAIRS                                                  # HM_ASM_BINS
 SITE_DTYPE = np.dtype([("gpos", "<i8"), ("pcov", "<i4"), ("ncov", "<i4"), ("motif", "<u4"), ("reserved", "<u4"), ("pvalue", "<f8"),
                        ("qvalue", "<f8")])                                            # hm_site_t, 40 bytes
 SITE_BINS = 3 * 256 * 256                                                             # HM_SITE_BINS
@@ -156,6 +165,35 @@ def sites_table(rates, bins: np.ndarray, big: Optional[np.ndarray] = None) -> Si
                         *(x.ctypes.data_as(C.c_void_p) for x in (ptab, qtab, big_p, big_q, m))) != 0:
         raise HifimethError("hm_sites_table: a rate outside [0, 1], or bins / big loci that are no counts")
     return SitesTable(r, ptab.reshape(3, 256, 256), qtab.reshape(3, 256, 256), big, big_p, big_q, m)
+
+
+class AsmTable:
+    """what asm_qvalues returns: tab (ASM_BIN_DTYPE: the tuples that occur, ascending in bin, with count, pvalue, qvalue), the big loci
+    (ASM_DTYPE, a haplotype total >= 64) with big_q, and m[3] = tested loci per context"""
+    def __init__(self, tab, big, big_q, m):
+        self.tab, self.big, self.big_q, self.m = tab, big, big_q, m
+
+
+def asm_qvalues(tab: np.ndarray, big: Optional[np.ndarray] = None) -> AsmTable:
+    """Benjamini-Hochberg q-values per context of the haplotype test, by the C library (host only: no GPU is needed).
+    tab: what asm_bin_pvalues gave for the job-wide bins; big: the job's big loci (asm_histogram), ascending in gpos."""
+    tab = np.array(tab, ASM_BIN_DTYPE)                      # a copy: the q-values are written into it
+    big = np.zeros(0, ASM_DTYPE) if big is None else np.ascontiguousarray(big, ASM_DTYPE)
+    big_q = np.full(len(big), np.nan)
+    m = np.zeros(3, np.uint64)
+    if lib().hm_asm_qvalues(tab.ctypes.data_as(C.c_void_p), len(tab), big.ctypes.data_as(C.c_void_p), len(big),
+                            big_q.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p)) != 0:
+        raise HifimethError("hm_asm_qvalues: bins that are not ascending or empty, a p outside [DBL_MIN, 1], or big loci that are none")
+    return AsmTable(tab, big, big_q, m)
+
+
+def asm_summary_tsv(table: AsmTable) -> str:
+    """the text of <prefix>.asm.summary.tsv: ctx, tested loci, loci with q <= 0.05, loci with q <= 0.01 -- from the table's weights"""
+    ctx = np.concatenate([table.tab["bin"] // (ASM_PAIRS * ASM_PAIRS), np.minimum(table.big["motif"], 2)]).astype(np.int64)
+    w = np.concatenate([table.tab["count"], np.ones(len(table.big), np.uint64)])
+    q = np.concatenate([table.tab["qvalue"], table.big_q])
+    return "".join("%s\t%d\t%d\t%d\n" % (CTX_NAMES[c], int(table.m[c]), int(w[(ctx == c) & (q <= 0.05)].sum()),
+                                          int(w[(ctx == c) & (q <= 0.01)].sum())) for c in range(3))
 
 
 def sites_rates_tsv(sums, rates, m) -> str:
@@ -316,22 +354,62 @@ class MethylationPileup:
             rows[CTX_NAMES[int(m)]].append("%s\t%d\t%d\t%g\t%d\t%d\n" % (self.names[s], k, k + 1, 100.0 * p / (p + n), p, n))
         return {k: "".join(v) for k, v in rows.items()}
 
-    def asm(self, lo: int = 0, hi: Optional[int] = None, min_cov: int = 5, planes=None, plane_base: int = 0) -> np.ndarray:
+    def asm(self, lo: int = 0, hi: Optional[int] = None, min_cov: int = 5, planes=None, plane_base: int = 0,
+            table: Optional[AsmTable] = None) -> np.ndarray:
         """tested loci of [lo, hi) (plane coordinates) in ascending order: each haplotype with pcov + ncov >= min_cov.
         planes = (pcov1, ncov1, pcov2, ncov2, key) torch tensors whose element 0 is locus plane_base, or None (own; needs
-        partitions=True).  diff = 100 p1 / (p1 + n1) - 100 p2 / (p2 + n2), pvalue = two-sided Fisher exact test (R's rule)."""
+        partitions=True).  diff = 100 p1 / (p1 + n1) - 100 p2 / (p2 + n2), pvalue = two-sided Fisher exact test (R's rule).
+        table (asm_qvalues, solved for the same min_cov): the rows also carry its qvalue (ASMQ_DTYPE), NaN where it has none."""
         hi = self.n_loci if hi is None else hi
         ptrs = [None] * 5 if planes is None else [C.c_void_p(t.data_ptr()) for t in planes]
-        return self._rows(self._L.hm_pileup_fetch_asm, ASM_DTYPE, *ptrs, plane_base, lo, hi, min_cov)
+        if table is None:
+            return self._rows(self._L.hm_pileup_fetch_asm, ASM_DTYPE, *ptrs, plane_base, lo, hi, min_cov)
+        return self._rows(self._L.hm_pileup_fetch_asm_q, ASMQ_DTYPE, *ptrs, plane_base, lo, hi, min_cov,
+                          table.tab.ctypes.data_as(C.c_void_p), len(table.tab), table.big.ctypes.data_as(C.c_void_p),
+                          table.big_q.ctypes.data_as(C.c_void_p), len(table.big))
+
+    def asm_histogram(self, lo: int = 0, hi: Optional[int] = None, min_cov: int = 5, planes=None, plane_base: int = 0,
+                      bins: Optional[np.ndarray] = None):
+        """-> (bins, big): bins (uint64 [ASM_BINS]; added into `bins` when given) = tested loci of [lo, hi) per dense tuple, index
+        (motif * 2080 + pair(pcov1, ncov1)) * 2080 + pair(pcov2, ncov2), pair(p, n) = t (t + 1) / 2 + p, t = p + n < 64; big = the
+        tested loci with a haplotype total >= 64, ascending, as asm() rows (ASM_DTYPE)"""
+        hi = self.n_loci if hi is None else hi
+        bins = np.zeros(ASM_BINS, np.uint64) if bins is None else bins
+        if not (isinstance(bins, np.ndarray) and bins.dtype == np.uint64 and bins.size == ASM_BINS and bins.flags.c_contiguous
+                and bins.flags.writeable):
+            raise HifimethError("asm_histogram: bins must be a contiguous uint64 array of 3 x 2080 x 2080")
+        ptrs = [None] * 5 if planes is None else [C.c_void_p(t.data_ptr()) for t in planes]
+        pb = bins.ctypes.data_as(C.c_void_p)
+        big = np.zeros(4096, ASM_DTYPE)           # big loci are rare at HiFi coverage: room for them in the first call
+        n = self._check(self._L.hm_pileup_asm_histogram(self._h, *ptrs, plane_base, lo, hi, min_cov, pb, big.ctypes.data_as(C.c_void_p), len(big)))
+        if n > len(big):                          # nothing was written or added: again, with room for the list
+            big = np.zeros(n, ASM_DTYPE)
+            self._check(self._L.hm_pileup_asm_histogram(self._h, *ptrs, plane_base, lo, hi, min_cov, pb, big.ctypes.data_as(C.c_void_p), n))
+        return bins, big[:n].copy()
+
+    def asm_bin_pvalues(self, bins: np.ndarray) -> np.ndarray:
+        """the non-empty bins of the job-wide `bins`, ascending (ASM_BIN_DTYPE): count, and the pvalue the device computes for a
+        row carrying the bin's tuple; qvalue NaN until asm_qvalues"""
+        b = np.ascontiguousarray(bins, np.uint64).reshape(-1)
+        if b.size != ASM_BINS:
+            raise HifimethError("asm_bin_pvalues: 3 x 2080 x 2080 bins expected")
+        tab = np.zeros(int(np.count_nonzero(b)), ASM_BIN_DTYPE)   # their number is known here: one upload, one compaction
+        n = self._check(self._L.hm_pileup_asm_bin_pvalues(self._h, b.ctypes.data_as(C.c_void_p), tab.ctypes.data_as(C.c_void_p), len(tab)))
+        if n != len(tab):
+            raise HifimethError("asm_bin_pvalues: the engine found %d non-empty bins, the host %d" % (n, len(tab)))
+        return tab
 
     def asm_bed(self, rows: np.ndarray) -> dict:
-        """the text of <prefix>.asm.{CpG,CHG,CHH}.bed: chrom, k, k+1, diff, pvalue, pcov1, ncov1, pcov2, ncov2"""
+        """the text of <prefix>.asm.{CpG,CHG,CHH}.bed: chrom, k, k+1, diff, pvalue, pcov1, ncov1, pcov2, ncov2; rows with a qvalue
+        (ASMQ_DTYPE) print it as a tenth column"""
         sid = np.searchsorted(self.offsets, rows["gpos"], side="right") - 1
         soff = rows["gpos"] - self.offsets[sid]
         text = {k: [] for k in CTX_NAMES}
+        with_q = "qvalue" in rows.dtype.names
         for s, k, r in zip(sid, soff, rows):
-            text[CTX_NAMES[int(r["motif"])]].append("%s\t%d\t%d\t%g\t%.6g\t%d\t%d\t%d\t%d\n" % (
-                self.names[s], k, k + 1, r["diff"], r["pvalue"], r["pcov1"], r["ncov1"], r["pcov2"], r["ncov2"]))
+            text[CTX_NAMES[int(r["motif"])]].append("%s\t%d\t%d\t%g\t%.6g\t%d\t%d\t%d\t%d" % (
+                self.names[s], k, k + 1, r["diff"], r["pvalue"], r["pcov1"], r["ncov1"], r["pcov2"], r["ncov2"])
+                + ("\t%.6g\n" % r["qvalue"] if with_q else "\n"))
         return {k: "".join(v) for k, v in text.items()}
 
     def _plane_ptrs(self, planes):

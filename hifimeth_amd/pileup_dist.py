@@ -1,7 +1,7 @@
 """`hifimeth pileup` over N GPUs of one node, one process per GPU (the path's only exchange step).
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
-        -m hifimeth_amd.pileup_dist [-q mapQ] [-f identity] [-H [-A [-a min-cov]]] [-B control | -e r,r,r] reference.fa mod.bam output-prefix
+        -m hifimeth_amd.pileup_dist [-q mapQ] [-f identity] [-H [-A [-a min-cov] [-Q]]] [-B control | -e r,r,r] reference.fa mod.bam output-prefix
 
 Records are dealt to the ranks in slabs of `--slab` records (round-robin, like the `call` path).  Each rank projects its
 records and histograms them on its own GPU; then
@@ -15,6 +15,9 @@ A single process (no torchrun) runs the same code with the collectives skipped.
 with SUM next to the three above, and rank 0 also writes <prefix>.hap1.<ctx>.cov.bed / <prefix>.hap2.<ctx>.cov.bed.
 -A (with -H): every rank tests its own chunk of the reduce-scattered haplotype planes (hm_pileup_fetch_asm, plane_base = the
 chunk's first locus) and rank 0 also writes <prefix>.asm.<ctx>.bed; no further collective.
+-Q (with -A): every rank counts the tested loci of its chunk per (context, pcov1, ncov1, pcov2, ncov2) (all-reduce of 12 979 200
+int64; the few loci beyond the bins by all_gather_object), computes the p of every tuple that occurs on its own device, solves the same
+Benjamini-Hochberg q-values (hm_asm_qvalues) and writes its rows with the tenth column; rank 0 also writes <prefix>.asm.summary.tsv.
 -B control / -e rates: the per-locus binomial test.  After step 3 every rank sums the control sequence's part of its chunk
 (all-reduce of 6 int64 -> the same rates everywhere), histograms its chunk per (motif, pcov, pcov + ncov) (all-reduce of
 196 608 int64; the few loci beyond the histogram by all_gather_object), solves the same table (hm_sites_table) and writes its
@@ -30,13 +33,14 @@ import numpy as np
 
 from . import dist as D
 from .bamio import is_coordinate_sorted, load_fasta, read_bam
-from .pileup import (CTX_NAMES, LOCUS_DTYPE, MethylationPileup, allreduce_histograms, locus_ranges, parse_rates, rates_from_sums,
-                     reduce_scatter_planes, reduce_scatter_sum, resolve_threshold, sites_rates_tsv, sites_table)
+from .pileup import (ASM_DTYPE, CTX_NAMES, LOCUS_DTYPE, MethylationPileup, allreduce_histograms, asm_qvalues, asm_summary_tsv,
+                     locus_ranges, parse_rates, rates_from_sums, reduce_scatter_planes, reduce_scatter_sum, resolve_threshold,
+                     sites_rates_tsv, sites_table)
 
 
 def run(reference: str, bam: str, prefix: str, min_mapq: int = 0, min_pi: float = 0.0, slab: int = 256,
         batch: int = 256, backend: str | None = None, log=sys.stderr, haplotypes: bool = False, asm: bool = False,
-        asm_min_cov: int = 5, control: str | None = None, rates=None):
+        asm_min_cov: int = 5, control: str | None = None, rates=None, asm_q: bool = False):
     import torch
     rank, local_rank, world = D.env_world()
     dist = D.init_process_group(backend, force=bool(os.environ.get("HM_FORCE_COLLECTIVES")))
@@ -124,19 +128,32 @@ def run(reference: str, bam: str, prefix: str, min_mapq: int = 0, min_pi: float 
     part = {"": pu.bed(loci)}                               # file tag -> {context: text}
     for k in range(len(hp) // 2):                           # a partition: its counts, the combined key's motif
         part[f"hap{k + 1}."] = pu.bed(pu.loci(0, hi - lo, planes=(hp[2 * k], hp[2 * k + 1], key), plane_base=base))
+    where = "cpu" if dist is not None and not on_gpu else dev
+
+    def allreduce_i64(a):
+        if dist is None:
+            return a
+        t = torch.from_numpy(a.astype(np.int64).reshape(-1)).to(where)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        return t.cpu().numpy().astype(np.uint64).reshape(a.shape)
+
     if asm:                                                 # the two partitions' chunks and the key's lie on the same range
-        part["asm."] = pu.asm_bed(pu.asm(0, hi - lo, asm_min_cov, planes=(*hp, key), plane_base=base))
+        asm_planes, table = (*hp, key), None
+        if asm_q:
+            bins, big = pu.asm_histogram(0, hi - lo, asm_min_cov, planes=asm_planes, plane_base=base)
+            bins = allreduce_i64(bins)
+            if dist is not None:
+                bigs = [None] * world
+                dist.all_gather_object(bigs, big)
+                big = np.concatenate(bigs).astype(ASM_DTYPE)  # rank order = locus order
+            table = asm_qvalues(pu.asm_bin_pvalues(bins), big)
+            del bins
+            if rank == 0:
+                with open(f"{prefix}.asm.summary.tsv", "w") as f:
+                    f.write(asm_summary_tsv(table))
+        part["asm."] = pu.asm_bed(pu.asm(0, hi - lo, asm_min_cov, planes=asm_planes, plane_base=base, table=table))
     if control is not None or rates is not None:
         mine, n_mine = (pc, nc, key), hi - lo               # this rank's chunk: element 0 is locus `base`
-        where = "cpu" if dist is not None and not on_gpu else dev
-
-        def allreduce_i64(a):
-            if dist is None:
-                return a
-            t = torch.from_numpy(a.astype(np.int64).reshape(-1)).to(where)
-            dist.all_reduce(t, op=dist.ReduceOp.SUM)
-            return t.cpu().numpy().astype(np.uint64).reshape(a.shape)
-
         sums = np.zeros(6, np.uint64)
         if control is not None:
             c0 = int(pu.offsets[sid_of[control]])
@@ -187,6 +204,8 @@ def main(argv=None):
     ap.add_argument("-A", dest="asm", action="store_true",
                     help="with -H: per-locus haplotype difference + Fisher exact test -> <prefix>.asm.<ctx>.bed")
     ap.add_argument("-a", dest="asm_min_cov", type=int, default=None, help="with -A: minimum coverage of each haplotype (default 5)")
+    ap.add_argument("-Q", dest="asm_q", action="store_true",
+                    help="with -A: Benjamini-Hochberg q-value per tested locus (tenth column), <prefix>.asm.summary.tsv")
     ap.add_argument("-B", dest="control", default=None, metavar="NAME",
                     help="per-locus binomial test against the false-positive rates measured on this unmethylated control sequence "
                          "-> <prefix>.sites.<ctx>.bed, <prefix>.sites.rates.tsv")
@@ -202,6 +221,8 @@ def main(argv=None):
         ap.error("-a needs -A")
     if a.asm_min_cov is not None and a.asm_min_cov < 1:
         ap.error("-a must be >= 1")
+    if a.asm_q and not a.asm:
+        ap.error("-Q needs -A")
     if a.control is not None and a.rates is not None:
         ap.error("-B and -e exclude each other")
     rates = None
@@ -211,7 +232,8 @@ def main(argv=None):
         except ValueError as e:
             ap.error(f"-e: {e}")
     return run(a.reference, a.mod_bam, a.output_prefix, a.q, a.f, slab=a.slab, backend=a.backend, haplotypes=a.haplotypes,
-               asm=a.asm, asm_min_cov=5 if a.asm_min_cov is None else a.asm_min_cov, control=a.control, rates=rates)
+               asm=a.asm, asm_min_cov=5 if a.asm_min_cov is None else a.asm_min_cov, control=a.control, rates=rates,
+               asm_q=a.asm_q)
 
 
 if __name__ == "__main__":

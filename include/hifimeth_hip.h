@@ -317,6 +317,57 @@ int64_t hm_pileup_fetch_asm(hm_pileup_t* p, const void* pcov1, const void* ncov1
                             const void* key, int64_t plane_base, int64_t lo, int64_t hi, int32_t min_cov,
                             hm_asm_t* out, int64_t cap);
 
+/* ---- Benjamini-Hochberg q-values of the test above (`pileup -H -A -Q`) -------------------------------------
+ * pvalue is a function of (pcov1, ncov1, pcov2, ncov2) alone, so the q of a locus -- R's p.adjust(method = "BH") among all tested
+ * loci of its context, min(key & 3, 2) -- needs only the number of tested loci per tuple: the device counts them
+ * (hm_pileup_asm_histogram), computes the p of every tuple that occurs with the kernel that computes a row's
+ * (hm_pileup_asm_bin_pvalues), the host solves the q-values once (hm_asm_qvalues) and the device writes the rows by lookup
+ * (hm_pileup_fetch_asm_q); no p-value is sorted on the device or exchanged between ranks, and the q next to a p is the q of that
+ * exact double.  Tuples with both haplotype totals < HM_ASM_T are dense: with pair(p, n) = t (t + 1) / 2 + p, t = p + n, they fall
+ * in bin (c * HM_ASM_PAIRS + pair(pcov1, ncov1)) * HM_ASM_PAIRS + pair(pcov2, ncov2); a tested locus with either total >=
+ * HM_ASM_T is "big" and listed instead.  The device bins (104 MB) are allocated by the first of these calls.
+ * In the three device calls the planes follow hm_pileup_fetch_asm: all five NULL = the engine's own, else DEVICE pointers whose
+ * element 0 is locus plane_base; a mix is HM_EINVAL, NULL without partitions HM_ESTATE; min_cov >= 1 and lo <= hi as there. */
+#define HM_ASM_T 64
+#define HM_ASM_PAIRS 2080      /* HM_ASM_T (HM_ASM_T + 1) / 2 */
+#define HM_ASM_BINS 12979200   /* 3 x 2080 x 2080 */
+typedef struct {            /* the tested loci that share one dense tuple; 32 bytes */
+    uint32_t bin, reserved;
+    uint64_t count;
+    double pvalue, qvalue;
+} hm_asm_bin_t;
+typedef struct {            /* hm_asm_t + qvalue: one row of <prefix>.asm.<ctx>.bed under -Q; 56 bytes */
+    int64_t gpos;
+    int32_t pcov1, ncov1, pcov2, ncov2;
+    uint32_t motif, reserved;
+    double diff, pvalue, qvalue;
+} hm_asmq_t;
+/* ADDS the tested loci of planes[lo, hi) whose haplotype totals are both < HM_ASM_T into the caller's bins[HM_ASM_BINS] and writes
+ * the big ones to big[] in ascending order, as hm_pileup_fetch_asm would (diff and pvalue computed).  Returns the number of big
+ * loci; when that exceeds cap, or big is NULL while there are some, nothing is written and nothing is added.  hi == lo returns 0. */
+int64_t hm_pileup_asm_histogram(hm_pileup_t* p, const void* pcov1, const void* ncov1, const void* pcov2, const void* ncov2,
+                                const void* key, int64_t plane_base, int64_t lo, int64_t hi, int32_t min_cov, uint64_t* bins,
+                                hm_asm_t* big, int64_t cap);
+/* The non-empty bins of bins[HM_ASM_BINS] (the job-wide sum) in ascending bin index, each with the pvalue the device computes for a
+ * row carrying its tuple; qvalue = NaN.  Returns their number (may exceed cap: then nothing is written).  HM_EINVAL for a
+ * non-empty bin of a tuple no tested locus has (a haplotype total of 0).  Needs neither reference nor planes. */
+int64_t hm_pileup_asm_bin_pvalues(hm_pileup_t* p, const uint64_t* bins, hm_asm_bin_t* out, int64_t cap);
+/* The q-values, host only (no device is touched): the one implementation behind every front end.  tab[0, n_tab): what
+ * hm_pileup_asm_bin_pvalues gave; big[0, n_big): the big loci of the job.  A bin weighs `count` loci of context bin / HM_ASM_PAIRS^2,
+ * a big locus one of context min(motif, 2); m[c] = tested loci of context c.  Per context, over the distinct p (bit-equal values
+ * grouped) in ascending order: R = number of loci with p <= this one, q = min over this and all larger p of
+ * min(1.0, p * (double)m / (double)R), left to right in fp64 -> tab[i].qvalue, big_q[i].  HM_EINVAL, with nothing written, for tab
+ * not strictly ascending in bin (or a bin >= HM_ASM_BINS), count == 0, a p outside [DBL_MIN, 1] or NaN, a big locus with
+ * motif > 3, negative counts or both totals < HM_ASM_T. */
+int hm_asm_qvalues(hm_asm_bin_t* tab, int64_t n_tab, const hm_asm_t* big, int64_t n_big, double* big_q, uint64_t m[3]);
+/* The rows of hm_pileup_fetch_asm for the same arguments, field for field, plus qvalue: a dense row's from the entry of its bin
+ * in tab, a big row's from big_q at its gpos' place in big (both found by binary search; tab ascending in bin, big in gpos); NaN if
+ * the entry is not there.  Returns the number of rows (may exceed cap: then nothing is written). */
+int64_t hm_pileup_fetch_asm_q(hm_pileup_t* p, const void* pcov1, const void* ncov1, const void* pcov2, const void* ncov2,
+                              const void* key, int64_t plane_base, int64_t lo, int64_t hi, int32_t min_cov,
+                              const hm_asm_bin_t* tab, int64_t n_tab, const hm_asm_t* big, const double* big_q, int64_t n_big,
+                              hm_asmq_t* out, int64_t cap);
+
 /* ---- per-locus binomial test (`pileup -B / -e`): is a locus methylated at all ------------------------
  * Against a false-positive rate e per context -- given, or measured on an unmethylated control sequence as sum(pcov) /
  * sum(pcov + ncov) -- a covered locus with k = pcov, n = pcov + ncov gets p = P(X >= k), X ~ Binomial(n, e), and the

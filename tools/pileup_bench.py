@@ -8,9 +8,10 @@ compaction at the end.  Prints one JSON object; `--check` verifies that the per-
 `--partitions`: the haplotype-resolved engine (`pileup -H`), every read tagged with a random HP of {none, 1, 2}; the loci
 fetch then also compacts the two partitions' planes.
 `--asm` (with `--partitions`): the allele-specific test of `pileup -H -A` over the counted planes: select + Fisher test + D2H per pass.
+`--asm-q` (with `--asm`): the q-values of `pileup -H -A -Q`: histogram + bin p-values + table (host) + rows with q (D2H included) per pass.
 `--sites`: the binomial test of `pileup -B / -e` over the counted planes: histogram + table + rows (D2H included) per pass.
 
-    python tools/pileup_bench.py --genome-mb 20 --coverage 10 [--partitions [--asm]] [--sites]
+    python tools/pileup_bench.py --genome-mb 20 --coverage 10 [--partitions [--asm [--asm-q]]] [--sites]
 """
 import argparse
 import ctypes as C
@@ -87,6 +88,7 @@ def main():
     ap.add_argument("--partitions", action="store_true", help="haplotype partitions on, reads tagged with random HP")
     ap.add_argument("--asm", action="store_true", help="with --partitions: time the per-locus haplotype test (pileup -H -A)")
     ap.add_argument("--asm-min-cov", type=int, default=5)
+    ap.add_argument("--asm-q", action="store_true", help="with --asm: time the Benjamini-Hochberg q-values of the test (pileup -H -A -Q)")
     ap.add_argument("--sites", action="store_true", help="time the per-locus binomial test (pileup -B / -e)")
     ap.add_argument("--sites-rate", type=float, default=0.013, help="with --sites: the false-positive rate of all three contexts")
     ap.add_argument("--cpu-baseline", action="store_true",
@@ -94,6 +96,8 @@ def main():
     a = ap.parse_args()
     if a.asm and not a.partitions:
         ap.error("--asm needs --partitions")
+    if a.asm_q and not a.asm:
+        ap.error("--asm-q needs --asm")
 
     rng = np.random.default_rng(1)
     G = int(a.genome_mb * 1e6)
@@ -176,6 +180,38 @@ def main():
                    asm_count_only_s=round(t_sel, 4), asm_rows_per_s=round(len(rows) / t_asm),
                    asm_mean_tables_per_row=round(float(steps.mean()), 1) if len(rows) else 0.0,
                    asm_share_of_pass=round(t_asm / (t_project / a.repeat + t_count / a.repeat + t_loci + t_hp_loci + t_asm), 4))
+    if a.asm_q:                                    # histogram, p per tuple, q-values (host), rows of every tested locus, as the CLI does
+        from hifimeth_amd.pileup import asm_qvalues
+
+        def q_pass():
+            t = [time.perf_counter()]
+            bins, big = pu.asm_histogram(min_cov=a.asm_min_cov)
+            t.append(time.perf_counter())
+            tab = pu.asm_bin_pvalues(bins)
+            t.append(time.perf_counter())
+            table = asm_qvalues(tab, big)
+            t.append(time.perf_counter())
+            rows_q = pu.asm(min_cov=a.asm_min_cov, table=table)
+            t.append(time.perf_counter())
+            return np.diff(t), table, rows_q
+
+        q_pass()                                   # warm-up: the 104 MB of bins, the row buffers
+        legs = np.zeros(4)
+        for _ in range(a.repeat):
+            dt, table, rows_q = q_pass()
+            legs += dt
+        legs /= a.repeat
+        t_q = float(legs.sum())
+        t_hp_pass = t_project / a.repeat + t_count / a.repeat + t_loci + t_hp_loci + t_asm     # a -H -A pass
+        out.update(asmq_rows=int(len(rows_q)), asmq_big_loci=int(len(table.big)), asmq_tuples=int(len(table.tab)),
+                   asmq_histogram_s=round(float(legs[0]), 4), asmq_bin_pvalues_s=round(float(legs[1]), 4),
+                   asmq_table_s=round(float(legs[2]), 4), asmq_rows_s=round(float(legs[3]), 4), asmq_s_per_pass=round(t_q, 4),
+                   asmq_rows_per_s=round(len(rows_q) / t_q) if t_q else 0, asmq_share_of_asm_pass=round(t_q / t_hp_pass, 4),
+                   asmq_significant=[int((rows_q["qvalue"] <= x).sum()) for x in (0.05, 0.01)])
+        if a.check:                                # the rows of --asm with a q each; the table's weights are the rows
+            plain = np.ascontiguousarray(rows_q[list(rows.dtype.names)]).astype(rows.dtype)
+            out["check_asmq_rows_are_the_asm_rows"] = bool(plain.tobytes() == rows.tobytes() and not np.isnan(rows_q["qvalue"]).any()
+                                                           and int(table.m.sum()) == len(rows))
     if a.sites:                                    # histogram, table (host), rows of every covered locus, as the CLI does
         from hifimeth_amd.pileup import sites_table
         pu.sites(sites_table([a.sites_rate] * 3, *pu.site_histogram()))    # warm-up: buffers, the log n! table
