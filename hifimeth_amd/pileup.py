@@ -202,10 +202,24 @@ def sites_rates_tsv(sums, rates, m) -> str:
                                              "nan" if np.isnan(rates[c]) else "%.17g" % rates[c], int(m[c])) for c in range(3))
 
 
+def locate(offsets, gpos) -> Tuple[np.ndarray, np.ndarray]:
+    """loci of the concatenated reference -> (sequence index, offset in that sequence), both int64; offsets = the n + 1 sequence
+    starts.  What every BED writer below names its rows by; a locus on a sequence boundary belongs to the sequence that starts
+    there, and empty sequences own none."""
+    offsets = np.asarray(offsets, np.int64)
+    gpos = np.asarray(gpos, np.int64)
+    sid = np.searchsorted(offsets, gpos, side="right") - 1
+    return sid, gpos - offsets[sid]
+
+
 class MethylationPileup:
     def __init__(self, genome: Sequence[Tuple[str, str]], device: int = 0, min_mapq: int = 0, min_pi: float = 0.0,
-                 planes=None, partitions: bool = False, partition_planes=None):
-        """planes: optional (pcov, ncov, key) torch CUDA tensors (int32, int32, int32-as-bits) of total genome length
+                 planes=None, partitions: bool = False, partition_planes=None, bases=None):
+        """genome: [(name, SEQUENCE)].  bases: optional, the concatenated upper-case bases of the whole reference as a
+        C-contiguous uint8 buffer (ndarray, bytes, memoryview), handed to the engine as it is -- for references of gigabases,
+        where joining, upper-casing and encoding strings would copy them three times; the second member of each genome entry
+        may then be the sequence's length instead of its text.
+        planes: optional (pcov, ncov, key) torch CUDA tensors (int32, int32, int32-as-bits) of total genome length
         that the engine counts into -- used when a collective consumes them afterwards.
         partitions: also count per haplotype (HP 1 / 2); partition_planes: optional ((pcov1, ncov1), (pcov2, ncov2)) int32
         torch CUDA tensors for them, like `planes`."""
@@ -214,7 +228,7 @@ class MethylationPileup:
         if self._L.hm_pileup_create(C.byref(self._h), device) != 0:
             raise HifimethError(self._L.hm_pileup_last_error(None).decode())
         self.names = [n for n, _ in genome]
-        self.lengths = np.array([len(s) for _, s in genome], np.int64)
+        self.lengths = np.array([int(s) if isinstance(s, (int, np.integer)) else len(s) for _, s in genome], np.int64)
         self.offsets = np.concatenate([[0], np.cumsum(self.lengths)])
         self._planes = planes
         self._order = 0
@@ -229,9 +243,15 @@ class MethylationPileup:
             raise HifimethError("partition_planes without partitions=True")
         if planes is not None:
             self._check(self._L.hm_pileup_use_planes(self._h, *(C.c_void_p(t.data_ptr()) for t in planes)))
-        bases = "".join(s for _, s in genome).upper().encode()
+        if bases is None:
+            if any(isinstance(s, (int, np.integer)) for _, s in genome):
+                raise HifimethError("a genome entry that gives a length needs `bases`")
+            bases = "".join(s for _, s in genome).upper().encode()
+        flat = np.frombuffer(bases, np.uint8) if not isinstance(bases, np.ndarray) else bases
+        if flat.dtype != np.uint8 or flat.ndim != 1 or not flat.flags.c_contiguous or flat.size != self.n_loci:
+            raise HifimethError("bases: one contiguous uint8 per reference base expected (%d)" % self.n_loci)
         self._check(self._L.hm_pileup_set_reference(self._h, len(genome), self.lengths.ctypes.data_as(C.c_void_p),
-                                                    C.c_char_p(bases)))
+                                                    flat.ctypes.data_as(C.c_void_p)))
 
     def close(self):
         if self._h:
@@ -347,8 +367,7 @@ class MethylationPileup:
 
     def bed(self, loci: np.ndarray) -> dict:
         """the text of <prefix>.{CpG,CHG,CHH}.cov.bed (pileup.cpp:562-590)"""
-        sid = np.searchsorted(self.offsets, loci["gpos"], side="right") - 1
-        soff = loci["gpos"] - self.offsets[sid]
+        sid, soff = locate(self.offsets, loci["gpos"])
         rows = {k: [] for k in CTX_NAMES}
         for s, k, p, n, m in zip(sid, soff, loci["pcov"], loci["ncov"], loci["motif"]):
             rows[CTX_NAMES[int(m)]].append("%s\t%d\t%d\t%g\t%d\t%d\n" % (self.names[s], k, k + 1, 100.0 * p / (p + n), p, n))
@@ -402,8 +421,7 @@ class MethylationPileup:
     def asm_bed(self, rows: np.ndarray) -> dict:
         """the text of <prefix>.asm.{CpG,CHG,CHH}.bed: chrom, k, k+1, diff, pvalue, pcov1, ncov1, pcov2, ncov2; rows with a qvalue
         (ASMQ_DTYPE) print it as a tenth column"""
-        sid = np.searchsorted(self.offsets, rows["gpos"], side="right") - 1
-        soff = rows["gpos"] - self.offsets[sid]
+        sid, soff = locate(self.offsets, rows["gpos"])
         text = {k: [] for k in CTX_NAMES}
         with_q = "qvalue" in rows.dtype.names
         for s, k, r in zip(sid, soff, rows):
@@ -445,8 +463,7 @@ class MethylationPileup:
 
     def sites_bed(self, rows: np.ndarray) -> dict:
         """the text of <prefix>.sites.{CpG,CHG,CHH}.bed: the six columns of the cov.bed row, then pvalue and qvalue"""
-        sid = np.searchsorted(self.offsets, rows["gpos"], side="right") - 1
-        soff = rows["gpos"] - self.offsets[sid]
+        sid, soff = locate(self.offsets, rows["gpos"])
         text = {k: [] for k in CTX_NAMES}
         for s, k, r in zip(sid, soff, rows):
             p, n = int(r["pcov"]), int(r["ncov"])

@@ -175,17 +175,34 @@ def test_bin_pvalues_are_the_rows_pvalues(solved):
     assert len(solved[1][2].tab) > len(solved[5][2].tab) > 200
 
 
+def _moved(rows, shift):
+    out = rows.copy()
+    out["gpos"] += shift
+    return out
+
+
 def test_histogram_of_two_halves_with_plane_base(crafted, solved):
+    """`shift` is what locus 0 of the crafted planes is called.  Beyond 0 it puts the second half's first locus (mid = 6001) on
+    2^31 and on 2^32: the rows' gpos = plane_base + i and the binary search by gpos in the job's big list then run over loci on
+    both sides of the boundary."""
+    from hifimeth_amd.pileup import AsmTable
     pu, _host, dev = crafted
-    for mid in (4096, 6001):                                                                                      # (d)
-        bins, big_lo = pu.asm_histogram(0, mid, 5, planes=dev)
-        chunk = [t[mid:] for t in dev]                        # a rank's chunk: element 0 is locus `mid`
-        _b, big_hi = pu.asm_histogram(0, N_LOCI - mid, 5, planes=chunk, plane_base=mid, bins=bins)
-        assert (bins == solved[5][0]).all()
-        assert len(big_lo) and len(big_hi) and (np.concatenate([big_lo, big_hi]) == solved[5][1]).all()
-        rq = pu.asm(0, N_LOCI - mid, 5, planes=chunk, plane_base=mid, table=solved[5][2])
-        want = solved[5][4]
-        assert (rq == want[want["gpos"] >= mid]).all()
+    for shift in (0, (1 << 31) - 6001, (1 << 32) - 6001):
+        table = solved[5][2]
+        table = AsmTable(table.tab, _moved(table.big, shift), table.big_q, table.m)     # the job-wide list, where the job's loci are
+        B = shift + 6001
+        assert shift == 0 or ((table.big["gpos"] < B).sum() > 10 and (table.big["gpos"] >= B).sum() > 10)
+        for mid in (4096, 6001):                                                                                  # (d)
+            bins, big_lo = pu.asm_histogram(0, mid, 5, planes=dev, plane_base=shift)
+            chunk = [t[mid:] for t in dev]                    # a rank's chunk: element 0 is locus `mid`
+            _b, big_hi = pu.asm_histogram(0, N_LOCI - mid, 5, planes=chunk, plane_base=shift + mid, bins=bins)
+            assert (bins == solved[5][0]).all()
+            assert len(big_lo) and len(big_hi) and (np.concatenate([big_lo, big_hi]) == _moved(solved[5][1], shift)).all()
+            rq = pu.asm(0, N_LOCI - mid, 5, planes=chunk, plane_base=shift + mid, table=table)
+            want = _moved(solved[5][4], shift)
+            assert (rq == want[want["gpos"] >= shift + mid]).all() and not np.isnan(rq["qvalue"]).any()
+            whole = pu.asm(0, N_LOCI, 5, planes=dev, plane_base=shift, table=table)
+            assert whole.tobytes() == want.tobytes()
 
 
 def test_cap_rule(crafted, solved):

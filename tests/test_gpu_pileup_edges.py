@@ -250,6 +250,10 @@ SK_BIG = (6000, 7000)                                                    # pcov 
 SK_EDGES = (0, 63, 64, 255, 256, BLK - 1, BLK, 2 * BLK - 1, 2 * BLK, SK_N - 1)
 SK_RANGES = ((0, SK_N), (1, SK_N - 1), (BLK - 1, BLK + 1), (BLK + 1, BLK + 1))
 SK_SLICE = 100                                                           # planes handed over from this locus on, plane_base = it
+# what locus 0 of the crafted planes is called: 0, or a rank's base that puts the rows' gpos across B = 2^31 / 2^32 -- the two big
+# loci on either side of B (the binary search in the job-wide big list then runs over entries that differ in bit 31 / 32), or a
+# block boundary of the planes on B
+SK_BASES = [0] + [B - x for B in (1 << 31, 1 << 32) for x in (SK_BIG[0] + 1, BLK)]
 
 
 def _skeleton_planes():
@@ -328,8 +332,11 @@ def test_skeleton_planes_hold_the_cases():
     assert _sk_sites(h, 7).sum() > _sk_sites(h, 5).sum() > 0
 
 
-def test_one_skeleton_behind_loci_asm_and_sites():
-    """pu.loci, pu.asm (min_cov 1 and 3), pu.site_histogram and pu.sites (ctx_mask 7 and 5) over the crafted planes against NumPy,
+@pytest.mark.parametrize("base", SK_BASES, ids=["base0", "big_loci_at_2^31", "block_at_2^31", "big_loci_at_2^32", "block_at_2^32"])
+def test_one_skeleton_behind_loci_asm_and_sites(base):
+    """With `base` the planes' first locus is called `base` instead of 0 (every plane_base below is counted from it): the rows'
+    gpos = plane_base + i and the lookups by gpos in the big list then cross 2^31 / 2^32.
+    pu.loci, pu.asm (min_cov 1 and 3), pu.site_histogram and pu.sites (ctx_mask 7 and 5) over the crafted planes against NumPy,
     field for field, with the three predicates written out above (_sk_loci, _sk_asm, _sk_sites; big loci: _sk_histogram): the
     whole planes, (1, n - 1), two loci across a block boundary, an empty range, and sliced planes with a plane_base.  p and q of a sites row are the table's entries bit for bit; asm's diff is numpy's bit for bit and its pvalue is
     within the bounds test_gpu_pileup_asm.py derives (1e-9 relative for row sums <= 24, 1e-6 above).  Through the raw ABI each of
@@ -349,7 +356,8 @@ def test_one_skeleton_behind_loci_asm_and_sites():
 
     def check_common(rows, sel, lo, hi, fields, motif):
         at = np.nonzero(sel[lo:hi])[0] + lo
-        assert len(rows) == len(at) and (rows["gpos"] == at).all() and (rows["reserved"] == 0).all(), (lo, hi)
+        assert len(rows) == len(at) and rows["gpos"].dtype == np.int64 and (rows["gpos"] == base + at).all(), (lo, hi)
+        assert (rows["reserved"] == 0).all(), (lo, hi)
         for f in fields:
             assert (rows[f] == h[f][at]).all(), (f, lo, hi)
         assert (rows["motif"] == motif[at]).all(), (lo, hi)
@@ -367,11 +375,14 @@ def test_one_skeleton_behind_loci_asm_and_sites():
             assert _rel_err(pvalue, fisher[t]) <= (1e-9 if max(t[0] + t[1], t[2] + t[3]) <= 24 else 1e-6), t
 
     # one histogram and one table per ctx_mask for the whole planes: a range's rows look their p and q up in it
-    bins, big = pu.site_histogram(0, SK_N, planes=planes(("pcov", "ncov", "key")))
-    assert [int(g) for g in big["gpos"]] == list(SK_BIG)
+    bins, big = pu.site_histogram(0, SK_N, planes=planes(("pcov", "ncov", "key")), plane_base=base)
+    assert [int(g) for g in big["gpos"]] == [base + g for g in SK_BIG]
+    if base:
+        B = base + SK_BIG[0] + 1 if base & (BLK - 1) else base + BLK
+        assert B in (1 << 31, 1 << 32) and base < B < base + SK_N and (big["gpos"][0] < B <= big["gpos"][1]) == bool(base & (BLK - 1))
     tables = {7: sites_table([0.02, 0.05, 0.013], bins, big), 5: sites_table([0.02, float("nan"), 0.013], bins, big)}
     assert {m: t.ctx_mask for m, t in tables.items()} == {7: 7, 5: 5}
-    big_at = {int(g): k for k, g in enumerate(big["gpos"])}
+    big_at = {int(g) - base: k for k, g in enumerate(big["gpos"])}
 
     def check_sites(rows, at, table):
         tot = i64["pcov"][at] + i64["ncov"][at]
@@ -387,7 +398,7 @@ def test_one_skeleton_behind_loci_asm_and_sites():
     for lo, hi, start in [(lo, hi, 0) for lo, hi in SK_RANGES] + [(5, SK_N - SK_SLICE, SK_SLICE)]:
         a, b = start + lo, start + hi                                # the same range in the coordinates of the whole planes
         assert 0 <= a <= b <= SK_N                                   # the engine trusts the caller's range: stay inside the planes
-        kw = dict(plane_base=start)
+        kw = dict(plane_base=base + start)
         rows = pu.loci(lo, hi, planes=planes(("pcov", "ncov", "key"), start), **kw)
         seen["loci"] += len(check_common(rows, _sk_loci(h), a, b, ("pcov", "ncov"), motif3))
         for min_cov in (1, 3):

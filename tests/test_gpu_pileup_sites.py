@@ -116,6 +116,7 @@ def crafted():
 
 
 RANGES = ((0, 0), (1, 4097), (4095, 8193), DEAD, (0, N_LOCI), (7, 7), (12288, 20480))
+BIG_SHIFTS = (0, (1 << 31) - 8192, (1 << 32) - 8192)         # plane_base of the whole crafted planes: 0, or locus 8192 lies on 2^31 / 2^32
 
 
 def _big_rows(big):
@@ -143,11 +144,14 @@ def test_histogram_and_big_list(crafted):
     full, _ = pu.site_histogram(planes=dev)
     assert full[2, 30, 3] >= 10000 and full[:, 64:, :].sum() > 0 and full.sum() + len(_) == counted(host[0], host[1]).sum()
     # a rank's chunk: planes that start at locus `base`; the bins add into what the caller holds
+    # `shift` is what locus 0 of the crafted planes is called: beyond 0 it puts locus 8192 on 2^31 / 2^32, inside the chunk's range
     base, lo, hi = 5000, 123, 9000
-    acc = np.full((3, 256, 256), 5, np.uint64)
-    bins, big = pu.site_histogram(lo, hi, planes=[t[base:] for t in dev], plane_base=base, bins=acc)
-    want_bins, want_big = ref_histogram(*host, base + lo, base + hi)
-    assert bins is acc and (acc == want_bins + 5).all() and (_big_rows(big) == want_big).all() and len(want_big) > 100
+    for shift in BIG_SHIFTS:
+        acc = np.full((3, 256, 256), 5, np.uint64)
+        bins, big = pu.site_histogram(lo, hi, planes=[t[base:] for t in dev], plane_base=shift + base, bins=acc)
+        want_bins, want_big = ref_histogram(*host, base + lo, base + hi, plane_base=shift)
+        assert bins is acc and (acc == want_bins + 5).all() and (_big_rows(big) == want_big).all() and len(want_big) > 100
+        assert shift == 0 or (want_big[:, 0] < shift + 8192).sum() > 100 < (want_big[:, 0] >= shift + 8192).sum()
 
 
 def test_cap_overflow_leaves_everything_untouched(crafted):
@@ -214,6 +218,22 @@ def test_rows_by_table_lookup(crafted, rates):
     assert NEGATIVE not in pu.sites(table, 4096, 4200, planes=dev)["gpos"]
     base, lo, hi = 5000, 123, 9000
     check(pu.sites(table, lo, hi, planes=[t[base:] for t in dev], plane_base=base), base + lo, base + hi)
+    # the job's loci called shift + i: the rows' gpos and the binary search by gpos in the big list (more than 1000 entries, on both
+    # sides of 2^31 / 2^32) must give the rows above, moved
+    from hifimeth_amd.pileup import SitesTable
+    for shift in BIG_SHIFTS[1:]:
+        moved_big = big.copy()
+        moved_big["gpos"] += shift
+        _bins, got_big = pu.site_histogram(planes=dev, plane_base=shift)
+        assert got_big.tobytes() == moved_big.tobytes()
+        B = shift + 8192
+        assert (moved_big["gpos"] < B).sum() > 100 and (moved_big["gpos"] >= B).sum() > 100
+        moved = SitesTable(table.rates, table.ptab, table.qtab, moved_big, table.big_p, table.big_q, table.m)
+        for (lo, hi), start in [(r, 0) for r in RANGES] + [((123, 9000), 5000)]:
+            want = pu.sites(table, lo, hi, planes=[t[start:] for t in dev], plane_base=start)
+            want["gpos"] += shift
+            got = pu.sites(moved, lo, hi, planes=[t[start:] for t in dev], plane_base=shift + start)
+            assert got.tobytes() == want.tobytes(), (shift, lo, hi)
     # cap below the count: the count comes back, nothing is written; a list that lacks a big locus gives NaN there
     from hifimeth_amd.pileup import SITE_DTYPE
     out = np.zeros(4, SITE_DTYPE)
