@@ -12,6 +12,10 @@
 // (difference of the two methylation percentages, two-sided Fisher exact test; both computed on the GPU).
 // -Q (ours, with -A): a tenth column qvalue in those rows, the Benjamini-Hochberg q of the p-value among all tested loci of the context,
 // and <prefix>.asm.summary.tsv: ctx, tested loci, loci with q <= 0.05, loci with q <= 0.01.
+// -G (ours, with -A): also <prefix>.asm.regions.<ctx>.bed, one row per run of at least -n (default 3) consecutive tested loci of
+// the context that all have p <= -s (default 0.01) and a difference of the same sign, each at most -g (default 500) bases from
+// the one before:  chrom <tab> start <tab> end <tab> n_loci <tab> +|- <tab> diff <tab> pmin <tab> pcov1 <tab> ncov1 <tab> pcov2 <tab> ncov2
+// (the counts pooled over the run's loci; chained on the GPU).
 // -B <control sequence> or -e <r_cpg,r_chg,r_chh> (ours): also <prefix>.sites.<ctx>.bed, the rows of <prefix>.<ctx>.cov.bed followed
 // by pvalue and qvalue -- the one-sided binomial test of the locus against the context's false-positive rate (measured on the
 // unmethylated control sequence, or given) and its Benjamini-Hochberg q-value within the context -- and <prefix>.sites.rates.tsv
@@ -24,6 +28,8 @@
 
 #include <algorithm>
 #include <cctype>
+#include <cerrno>
+#include <climits>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -77,6 +83,11 @@ struct PileupOptions {
     int asm_min_cov = 5;      // -a: minimum pcov + ncov of each haplotype for a locus to be tested
     bool asm_min_cov_given = false;
     bool asm_q = false;       // -Q: Benjamini-Hochberg q-value per tested locus, <prefix>.asm.summary.tsv
+    bool asm_regions = false; // -G: chains of tested loci that lean the same way -> <prefix>.asm.regions.*
+    double region_max_p = 0.01;     // -s: a locus is a hit when its p-value is at most this
+    long long region_max_gap = 500; // -g: largest distance between two consecutive loci of a region
+    int region_min_loci = 3;        // -n: smallest region written
+    bool region_option_given = false, region_option_bad = false;  // any of -s -g -n; one of them with a value out of range
     std::string control;      // -B: name of the unmethylated control sequence -> rates measured there, <prefix>.sites.*
     bool rates_given = false; // -e: the three rates given directly (NaN: context not tested)
     double rates[3] = {0, 0, 0};
@@ -108,6 +119,14 @@ void pileup_usage(const char* exe) {
             "  -a <int>\n    With -A: minimum coverage (pcov + ncov) of each haplotype at a tested locus\n    Default: 5\n"
             "  -Q\n    With -A: a tenth column, the Benjamini-Hochberg q-value of the p-value among all tested loci of the context, and\n"
             "    <prefix>.asm.summary.tsv: ctx, tested loci, loci with q <= 0.05, loci with q <= 0.01\n"
+            "  -G\n    With -A: chain the tested loci of each context into regions and write <prefix>.asm.regions.<ctx>.bed: chrom, start, end,\n"
+            "    loci, + or - (the sign of hap1 %% - hap2 %% at every locus), hap1 %% - hap2 %% of the pooled counts, smallest p-value,\n"
+            "    pcov1, ncov1, pcov2, ncov2 summed over the loci.  A region is a run of consecutive tested loci that all have p <= -s and a\n"
+            "    difference of the same sign, each at most -g bases after the one before; a tested locus that does not qualify ends it.\n"
+            "    The pooled difference can have the other sign than the loci; there is no region-level p-value (the loci were selected by p)\n"
+            "  -s <p>\n    With -G: largest p-value of a locus in a region, in (0, 1]\n    Default: 0.01\n"
+            "  -g <bp>\n    With -G: largest distance between consecutive loci of a region, >= 1\n    Default: 500\n"
+            "  -n <int>\n    With -G: smallest number of loci of a region, >= 1\n    Default: 3\n"
             "  -B <sequence name>\n    Test every covered locus for methylation above the caller's false-positive rate, measured per context on this\n"
             "    unmethylated control sequence (chloroplast, spiked-in lambda) as sum(pcov) / sum(pcov + ncov): write <prefix>.sites.<ctx>.bed,\n"
             "    the rows of <prefix>.<ctx>.cov.bed followed by the one-sided binomial p-value and its Benjamini-Hochberg q-value within\n"
@@ -796,6 +815,36 @@ bool write_asm(hm_pileup_t* pe, const Fasta& fa, int min_cov, FILE* out[3], int 
         });
 }
 
+// rows of the three <prefix>.asm.regions.<ctx>.bed files, sequence by sequence: a region never crosses a sequence.  false on an
+// engine error.
+bool write_asm_regions(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, FILE* out[3]) {
+    std::vector<hm_asm_region_t> rows;
+    int64_t off = 0;
+    for (size_t s = 0; s < fa.names.size(); ++s) {
+        const int64_t lo = off, hi = off + fa.length[s];
+        off = hi;
+        for (int c = 0; c < 3; ++c) {
+            const auto fetch = [&](hm_asm_region_t* dst, int64_t cap) {
+                return hm_pileup_fetch_asm_regions(pe, nullptr, nullptr, nullptr, nullptr, nullptr, 0, lo, hi, o.asm_min_cov, c, o.region_max_p,
+                                                   o.region_max_gap, o.region_min_loci, 0, nullptr, dst, cap);
+            };
+            int64_t n = fetch(nullptr, 0);
+            if (n > 0) {
+                rows.resize((size_t)n);
+                n = fetch(rows.data(), n);
+            }
+            if (n < 0) return false;
+            for (int64_t i = 0; i < n; ++i) {
+                const hm_asm_region_t& r = rows[(size_t)i];
+                fprintf(out[c], "%s\t%lld\t%lld\t%d\t%c\t%g\t%.6g\t%lld\t%lld\t%lld\t%lld\n", fa.names[s].c_str(), (long long)(r.start - lo),
+                        (long long)(r.end - lo), r.n_loci, r.sign > 0 ? '+' : '-', r.diff, r.pmin, (long long)r.pcov1, (long long)r.ncov1,
+                        (long long)r.pcov2, (long long)r.ncov2);
+            }
+        }
+    }
+    return true;
+}
+
 // `pileup -H -A -Q` after hm_pileup_count: the tested loci of the whole reference counted per tuple, the p of every tuple that
 // occurs, the q-values (hm_asm_qvalues), then the rows of write_asm with their q looked up (56 B per row on the device and here),
 // and <prefix>.asm.summary.tsv from the table's weights.  1 done, -1 engine error (hm_pileup_last_error), 0 another error (message
@@ -1075,6 +1124,7 @@ int cmd_pileup(int argc, char** argv) {
         if (a == "-H") { o.haplotypes = true; continue; }  // a flag: takes no value
         if (a == "-A") { o.asm_test = true; continue; }
         if (a == "-Q") { o.asm_q = true; continue; }
+        if (a == "-G") { o.asm_regions = true; continue; }
         if (a == "-K") { o.kinetics = true; continue; }
         if (i + 1 >= argc) { pileup_usage(argv[0]); return EXIT_FAILURE; }
         if (a == "-q") o.min_mapq = atoi(argv[++i]);
@@ -1083,6 +1133,22 @@ int cmd_pileup(int argc, char** argv) {
         else if (a == "-d") o.device = atoi(argv[++i]);
         else if (a == "-b") o.read_batch = std::max(1, atoi(argv[++i]));
         else if (a == "-a") { o.asm_min_cov = atoi(argv[++i]); o.asm_min_cov_given = true; }
+        else if (a == "-s" || a == "-g" || a == "-n") {  // the whole value must parse, and lie in the option's range
+            o.region_option_given = true;
+            const char* v = argv[++i];
+            char* end = nullptr;
+            errno = 0;
+            if (a == "-s") {
+                o.region_max_p = strtod(v, &end);
+                if (!(o.region_max_p > 0.0 && o.region_max_p <= 1.0)) o.region_option_bad = true;
+            } else {
+                const long long x = strtoll(v, &end, 10);
+                if (x < 1 || (a == "-n" && x > INT_MAX)) o.region_option_bad = true;
+                else if (a == "-g") o.region_max_gap = x;
+                else o.region_min_loci = (int)x;
+            }
+            if (end == v || *end || errno) o.region_option_bad = true;
+        }
         else if (a == "-B") o.control = argv[++i];
         else if (a == "-e") {
             o.rates_given = true;
@@ -1107,7 +1173,10 @@ int cmd_pileup(int argc, char** argv) {
     const char* bad_asm = o.asm_test && !o.haplotypes ? "-A needs -H (the test compares the two haplotypes)"
                           : o.asm_min_cov_given && !o.asm_test ? "-a needs -A"
                           : o.asm_q && !o.asm_test ? "-Q needs -A (the q-values are those of its p-values)"
-                          : o.asm_min_cov < 1 ? "-a must be >= 1" : nullptr;
+                          : o.asm_min_cov < 1 ? "-a must be >= 1"
+                          : o.asm_regions && !o.asm_test ? "-G needs -A (the regions are chains of its tested loci)"
+                          : o.region_option_given && !o.asm_regions ? "-s, -g and -n need -G"
+                          : o.region_option_bad ? "-s must be in (0, 1], -g and -n integers >= 1" : nullptr;
     if (bad_asm) { fprintf(stderr, "ERROR: %s\n", bad_asm); pileup_usage(argv[0]); return EXIT_FAILURE; }
     const char* bad_call = o.call_option_given && !o.kinetics ? "-m, -c, -l, -p and -T need -K (they configure the on-the-fly caller)"
                            : o.min_read_size < 0 ? "-l must be >= 0"
@@ -1127,6 +1196,9 @@ int cmd_pileup(int argc, char** argv) {
     if (o.haplotypes) fprintf(stderr, "haplotypes: HP 1 / 2 -> %s.hap1.* / %s.hap2.*\n", o.prefix.c_str(), o.prefix.c_str());
     if (o.asm_test) fprintf(stderr, "asm: min haplotype coverage %d -> %s.asm.*\n", o.asm_min_cov, o.prefix.c_str());
     if (o.asm_q) fprintf(stderr, "asm: Benjamini-Hochberg q-values per context -> tenth column, %s.asm.summary.tsv\n", o.prefix.c_str());
+    if (o.asm_regions)
+        fprintf(stderr, "asm: regions of >= %d loci with p <= %g and one sign, gaps <= %lld -> %s.asm.regions.*\n", o.region_min_loci, o.region_max_p,
+                o.region_max_gap, o.prefix.c_str());
     if (!o.control.empty()) fprintf(stderr, "sites: binomial test against the rates of control sequence %s -> %s.sites.*\n", o.control.c_str(), o.prefix.c_str());
     if (o.rates_given) fprintf(stderr, "sites: binomial test against the rates %g,%g,%g -> %s.sites.*\n", o.rates[0], o.rates[1], o.rates[2], o.prefix.c_str());
     if (o.kinetics)
@@ -1306,6 +1378,22 @@ int cmd_pileup(int argc, char** argv) {
         for (FILE* f : out) fclose(f);
         if (rc < 0) return die("asm");
         if (rc == 0) { hm_pileup_destroy(pe); return EXIT_FAILURE; }
+    }
+    if (o.asm_regions) {
+        FILE* out[3];
+        for (int c = 0; c < 3; ++c) {
+            const std::string path = o.prefix + ".asm.regions." + cn[c] + ".bed";
+            out[c] = fopen(path.c_str(), "w");
+            if (!out[c]) {
+                fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str());
+                for (int d = 0; d < c; ++d) fclose(out[d]);
+                hm_pileup_destroy(pe);
+                return EXIT_FAILURE;
+            }
+        }
+        const bool ok = write_asm_regions(pe, fa, o, out);
+        for (FILE* f : out) fclose(f);
+        if (!ok) return die("asm regions");
     }
     if (sites) {
         const int rc = write_sites(pe, fa, o, control_sid, o.threads);

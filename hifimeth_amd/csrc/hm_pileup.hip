@@ -24,6 +24,8 @@
 //                   then one thread per compact row: methylation difference + two-sided Fisher exact test
 //   asm_hist / asm_bins_* / asm_q_write   Benjamini-Hochberg q-values of that test (`pileup -H -A -Q`): tested loci counted per
 //                   (context, p1, n1, p2, n2), the non-empty bins compacted and given their p by asm_test_kernel, q looked up per row
+//   asm_ctx_* / asm_region_*   allele-specific regions (`pileup -H -A -G`): the tested rows of one context compacted and tested, then
+//                   the same count / scan / write over ROW indices: a thread that owns a chain head walks to the chain's tail
 //   sites_*         binomial test per locus (`pileup -B / -e`): control sums, histogram of (motif, pcov, pcov + ncov) through LDS,
 //                   the loci beyond the histogram listed, rows written by table lookup (count, loci_scan, write)
 #include <hip/hip_runtime.h>
@@ -455,7 +457,20 @@ __global__ __launch_bounds__(TPB) void asm_count_kernel(const int32_t* __restric
     count_block(lo, hi, block_counts, [&](int64_t i) { return asm_tested(pcov1[i], ncov1[i], pcov2[i], ncov2[i], min_cov); });
 }
 
-// compact rows in ascending locus order; diff and pvalue are filled by asm_test_kernel
+// the row of a tested locus; diff and pvalue are filled by asm_test_kernel
+__device__ __forceinline__ void asm_row(hm_asm_t& r, int64_t gpos, int32_t p1, int32_t n1, int32_t p2, int32_t n2, uint32_t key) {
+    r.gpos = gpos;
+    r.pcov1 = p1;
+    r.ncov1 = n1;
+    r.pcov2 = p2;
+    r.ncov2 = n2;
+    r.motif = key & 3u;
+    r.reserved = 0;
+    r.diff = 0.0;
+    r.pvalue = 0.0;
+}
+
+// compact rows in ascending locus order
 __global__ __launch_bounds__(TPB) void asm_write_kernel(const int32_t* __restrict__ pcov1, const int32_t* __restrict__ ncov1,
                                                          const int32_t* __restrict__ pcov2, const int32_t* __restrict__ ncov2,
                                                          const uint32_t* __restrict__ key, int64_t plane_base, int64_t lo,
@@ -464,15 +479,7 @@ __global__ __launch_bounds__(TPB) void asm_write_kernel(const int32_t* __restric
     compact_block(lo, hi, offs, out, [&](int64_t i, hm_asm_t& r) {
         const int32_t p1 = pcov1[i], n1 = ncov1[i], p2 = pcov2[i], n2 = ncov2[i];
         if (!asm_tested(p1, n1, p2, n2, min_cov)) return false;
-        r.gpos = plane_base + i;
-        r.pcov1 = p1;
-        r.ncov1 = n1;
-        r.pcov2 = p2;
-        r.ncov2 = n2;
-        r.motif = key[i] & 3u;
-        r.reserved = 0;
-        r.diff = 0.0;
-        r.pvalue = 0.0;
+        asm_row(r, plane_base + i, p1, n1, p2, n2, key[i]);
         return true;
     });
 }
@@ -709,15 +716,7 @@ __global__ __launch_bounds__(TPB) void asm_big_write_kernel(const int32_t* __res
     compact_block(lo, hi, offs, out, [&](int64_t i, hm_asm_t& r) {
         const int32_t p1 = pcov1[i], n1 = ncov1[i], p2 = pcov2[i], n2 = ncov2[i];
         if (!asm_tested(p1, n1, p2, n2, min_cov) || asm_dense(p1, n1, p2, n2)) return false;
-        r.gpos = plane_base + i;
-        r.pcov1 = p1;
-        r.ncov1 = n1;
-        r.pcov2 = p2;
-        r.ncov2 = n2;
-        r.motif = key[i] & 3u;
-        r.reserved = 0;
-        r.diff = 0.0;
-        r.pvalue = 0.0;
+        asm_row(r, plane_base + i, p1, n1, p2, n2, key[i]);
         return true;
     });
 }
@@ -803,6 +802,109 @@ __global__ __launch_bounds__(TPB) void asm_q_write_kernel(const hm_asm_t* __rest
     o.pvalue = r.pvalue;
     o.qvalue = q;
     out[i] = o;
+}
+
+// ---- `pileup -H -A -G`: chains of tested rows that lean the same way (include/hifimeth_hip.h has the definition) ----------------
+// Step 1 is the skeleton over the loci with the context added to the selection; asm_test_kernel then fills diff and pvalue.
+__global__ __launch_bounds__(TPB) void asm_ctx_count_kernel(const int32_t* __restrict__ pcov1, const int32_t* __restrict__ ncov1,
+                                                             const int32_t* __restrict__ pcov2, const int32_t* __restrict__ ncov2,
+                                                             const uint32_t* __restrict__ key, int64_t lo, int64_t hi, int32_t min_cov,
+                                                             uint32_t ctx, int32_t* __restrict__ block_counts) {
+    count_block(lo, hi, block_counts, [&](int64_t i) {
+        return asm_tested(pcov1[i], ncov1[i], pcov2[i], ncov2[i], min_cov) && site_motif(key[i]) == ctx;
+    });
+}
+
+__global__ __launch_bounds__(TPB) void asm_ctx_write_kernel(const int32_t* __restrict__ pcov1, const int32_t* __restrict__ ncov1,
+                                                             const int32_t* __restrict__ pcov2, const int32_t* __restrict__ ncov2,
+                                                             const uint32_t* __restrict__ key, int64_t plane_base, int64_t lo,
+                                                             int64_t hi, int32_t min_cov, uint32_t ctx, const int64_t* __restrict__ offs,
+                                                             hm_asm_t* __restrict__ out) {
+    compact_block(lo, hi, offs, out, [&](int64_t i, hm_asm_t& r) {
+        const int32_t p1 = pcov1[i], n1 = ncov1[i], p2 = pcov2[i], n2 = ncov2[i];
+        if (!asm_tested(p1, n1, p2, n2, min_cov) || site_motif(key[i]) != ctx) return false;
+        asm_row(r, plane_base + i, p1, n1, p2, n2, key[i]);
+        return true;
+    });
+}
+
+// Step 2 runs over the row indices [0, n_rows) the way the kernels above run over loci: the selected index is the head of a
+// returned chain, and the thread that owns it walks the rows forward to the chain's tail.  Only comparisons and integer sums: the
+// result does not depend on how the rows fall on threads and workgroups, and a chain may cross any number of them.
+struct RegionRule {
+    double max_p;
+    int64_t max_gap;
+    int32_t min_loci, keep_edges;
+};
+
+// +1 / -1: rows[i] is a hit of that sign; 0: it is none
+__device__ __forceinline__ int region_sign(const hm_asm_t* __restrict__ rows, int64_t i, double max_p) {
+    const double d = rows[i].diff;
+    return rows[i].pvalue <= max_p ? (d > 0.0) - (d < 0.0) : 0;
+}
+// rows i - 1 and i, i >= 1, are within max_gap: linked when both are also hits of one sign
+__device__ __forceinline__ bool region_near(const hm_asm_t* __restrict__ rows, int64_t i, const RegionRule& rule) {
+    return rows[i].gpos - rows[i - 1].gpos <= rule.max_gap;
+}
+// rows[i] starts a chain (of sign s)
+__device__ __forceinline__ bool region_head(const hm_asm_t* __restrict__ rows, int64_t i, const RegionRule& rule, int& s) {
+    s = region_sign(rows, i, rule.max_p);
+    return s != 0 && !(i > 0 && region_sign(rows, i - 1, rule.max_p) == s && region_near(rows, i, rule));
+}
+// rows[j] continues the chain of sign s that holds rows[j - 1]
+__device__ __forceinline__ bool region_next(const hm_asm_t* __restrict__ rows, int64_t j, int64_t n_rows, int s, const RegionRule& rule) {
+    return j < n_rows && region_sign(rows, j, rule.max_p) == s && region_near(rows, j, rule);
+}
+__device__ __forceinline__ bool region_returned(int64_t n_loci, uint32_t flags, const RegionRule& rule) {
+    return n_loci >= rule.min_loci || (rule.keep_edges && flags);
+}
+
+// The walk stops after min_loci rows: a chain that long is returned whatever its flags, a shorter one has been walked to its tail.
+__global__ __launch_bounds__(TPB) void asm_region_count_kernel(const hm_asm_t* __restrict__ rows, int64_t n_rows, RegionRule rule,
+                                                                int32_t* __restrict__ block_counts) {
+    count_block(0, n_rows, block_counts, [&](int64_t i) {
+        int s;
+        if (!region_head(rows, i, rule, s)) return false;
+        int64_t j = i + 1;
+        while (j - i < rule.min_loci && region_next(rows, j, n_rows, s, rule)) ++j;
+        return region_returned(j - i, (i == 0 ? HM_REGION_FIRST : 0u) | (j == n_rows ? HM_REGION_LAST : 0u), rule);
+    });
+}
+
+__global__ __launch_bounds__(TPB) void asm_region_write_kernel(const hm_asm_t* __restrict__ rows, int64_t n_rows, RegionRule rule,
+                                                                uint32_t ctx, const int64_t* __restrict__ offs,
+                                                                hm_asm_region_t* __restrict__ out) {
+    compact_block(0, n_rows, offs, out, [&](int64_t i, hm_asm_region_t& g) {
+        int s;
+        if (!region_head(rows, i, rule, s)) return false;
+        int64_t P1 = 0, N1 = 0, P2 = 0, N2 = 0;
+        double pmin = rows[i].pvalue;
+        int64_t j = i;
+        do {
+            P1 += rows[j].pcov1;
+            N1 += rows[j].ncov1;
+            P2 += rows[j].pcov2;
+            N2 += rows[j].ncov2;
+            const double pv = rows[j].pvalue;
+            pmin = pv < pmin ? pv : pmin;
+            ++j;
+        } while (region_next(rows, j, n_rows, s, rule));
+        g.flags = (i == 0 ? HM_REGION_FIRST : 0u) | (j == n_rows ? HM_REGION_LAST : 0u);
+        if (!region_returned(j - i, g.flags, rule)) return false;
+        g.start = rows[i].gpos;
+        g.end = rows[j - 1].gpos + 1;
+        g.pcov1 = P1;
+        g.ncov1 = N1;
+        g.pcov2 = P2;
+        g.ncov2 = N2;
+        g.n_loci = (int32_t)(j - i);
+        g.sign = s;
+        g.motif = ctx;
+        // as asm_test_kernel's diff, on the pooled sums: each haplotype total is >= min_cov >= 1
+        g.diff = __dsub_rn(__ddiv_rn(__dmul_rn(100.0, (double)P1), (double)(P1 + N1)), __ddiv_rn(__dmul_rn(100.0, (double)P2), (double)(P2 + N2)));
+        g.pmin = pmin;
+        return true;
+    });
 }
 
 }  // namespace
@@ -1644,6 +1746,53 @@ int64_t hm_pileup_fetch_asm_q(hm_pileup_t* p, const void* pcov1, const void* nco
             hipLaunchKernelGGL(asm_test_kernel, per_row, dim3(TPB), 0, st, rows, total, p->d_lfact.as<double>());
             hipLaunchKernelGGL(asm_q_write_kernel, per_row, dim3(TPB), 0, st, rows, total, p->d_atab.as<hm_asm_bin_t>(), n_tab,
                                p->d_abig.as<hm_asm_t>(), p->d_abigq.as<double>(), n_big, dst);
+        });
+}
+
+// ---- `pileup -H -A -G` ------------------------------------------------------------------------------------------------------------
+int64_t hm_pileup_fetch_asm_regions(hm_pileup_t* p, const void* pcov1, const void* ncov1, const void* pcov2, const void* ncov2,
+                                    const void* key, int64_t plane_base, int64_t lo, int64_t hi, int32_t min_cov, int32_t ctx,
+                                    double max_p, int64_t max_gap, int32_t min_loci, int32_t keep_edges, int64_t* n_ctx_rows,
+                                    hm_asm_region_t* out, int64_t cap) {
+    if (!p) return HM_EINVAL;
+    if (ctx < 0 || ctx > 2) return pfail(p, HM_EINVAL, "hm_pileup_fetch_asm_regions: ctx must be 0, 1 or 2");
+    if (!(max_p > 0.0 && max_p <= 1.0)) return pfail(p, HM_EINVAL, "hm_pileup_fetch_asm_regions: max_p must be in (0, 1]");
+    if (max_gap < 1 || min_loci < 1) return pfail(p, HM_EINVAL, "hm_pileup_fetch_asm_regions: max_gap and min_loci must be >= 1");
+    AsmPlanes s;
+    const int rc = asm_planes(p, "hm_pileup_fetch_asm_regions", pcov1, ncov1, pcov2, ncov2, key, plane_base, lo, hi, min_cov, s);
+    if (rc != HM_OK) return rc;
+    if (n_ctx_rows) *n_ctx_rows = 0;
+    if (hi == lo) return 0;
+    const int64_t nblk = range_blocks(lo, hi);
+    if (nblk >= (int64_t(1) << 31)) return pfail(p, HM_EINVAL, "range too large: fetch per sequence");
+    hipStream_t st = p->stream;
+    const int64_t R = guarded(p, [&]() -> int64_t {  // the context's rows, tested, stay in d_arows
+        const dim3 grid((unsigned)nblk);
+        p->d_blk.reserve(4 * (size_t)nblk);
+        p->d_offs.reserve(8 * ((size_t)nblk + 1));
+        hipLaunchKernelGGL(asm_ctx_count_kernel, grid, dim3(TPB), 0, st, s.p1, s.n1, s.p2, s.n2, s.ky, lo, hi, min_cov, (uint32_t)ctx,
+                           p->d_blk.as<int32_t>());
+        const int64_t total = scan_blocks(p, nblk);
+        if (!total) return 0;
+        ensure_lfact(p);
+        p->d_arows.reserve(sizeof(hm_asm_t) * (size_t)total);
+        hm_asm_t* rows = p->d_arows.as<hm_asm_t>();
+        hipLaunchKernelGGL(asm_ctx_write_kernel, grid, dim3(TPB), 0, st, s.p1, s.n1, s.p2, s.n2, s.ky, plane_base, lo, hi, min_cov,
+                           (uint32_t)ctx, p->d_offs.as<int64_t>(), rows);
+        hipLaunchKernelGGL(asm_test_kernel, dim3((unsigned)((total + TPB - 1) / TPB)), dim3(TPB), 0, st, rows, total, p->d_lfact.as<double>());
+        HIP_TRY(hipGetLastError());
+        return total;
+    });
+    if (R <= 0) return R;
+    if (n_ctx_rows) *n_ctx_rows = R;
+    const hm_asm_t* rows = p->d_arows.as<hm_asm_t>();
+    const RegionRule rule{max_p, max_gap, min_loci, keep_edges != 0};
+    return compact_rows(
+        p, 0, R, out, cap,
+        [&](dim3 grid, int32_t* counts) { hipLaunchKernelGGL(asm_region_count_kernel, grid, dim3(TPB), 0, st, rows, R, rule, counts); },
+        [] {},
+        [&](dim3 grid, const int64_t* offs, hm_asm_region_t* dst, int64_t) {
+            hipLaunchKernelGGL(asm_region_write_kernel, grid, dim3(TPB), 0, st, rows, R, rule, (uint32_t)ctx, offs, dst);
         });
 }
 

@@ -22,6 +22,11 @@ table of 3 x 2080 x 2080 bins for haplotype totals below 64, the few loci beyond
 tuple that occurs the p the device computes for it, `asm_qvalues(tab, big)` -- host only, the C library's -- solves the
 Benjamini-Hochberg q-values per context, and `pu.asm(table=...)` are the rows with a `qvalue` field, the tenth column of `asm_bed`.
 
+Allele-specific regions (`pileup -H -A -G`): `pu.asm_regions(ctx)` chains the context's tested rows on the device -- consecutive
+rows with pvalue <= max_p and a difference of the same sign, at most max_gap apart, broken by any tested row that is none -- into
+rows with the pooled counts (ASM_REGION_DTYPE); `pu.asm_regions_bed(rows)` is the text of <prefix>.asm.regions.<ctx>.bed, and
+`stitch_asm_regions(parts, ...)` -- host only -- joins the chains of adjacent ranges into what one fetch over their union returns.
+
 Binomial test per locus (`pileup -B control` / `-e r,r,r`): is a locus methylated at all, against the caller's false-positive
 rate?  `pu.control_sums(lo, hi)` over an unmethylated control sequence gives the rates (`rates_from_sums`), `pu.site_histogram()`
 counts the loci per (motif, pcov, pcov + ncov), `sites_table(rates, bins, big)` -- host only, the C library's -- solves p-values
@@ -52,6 +57,10 @@ ASM_DTYPE = np.dtype([("gpos", "<i8"), ("pcov1", "<i4"), ("ncov1", "<i4"), ("pco
                       ("reserved", "<u4"), ("diff", "<f8"), ("pvalue", "<f8")])     # hm_asm_t, 48 bytes
 ASMQ_DTYPE = np.dtype(ASM_DTYPE.descr + [("qvalue", "<f8")])                          # hm_asmq_t, 56 bytes
 ASM_BIN_DTYPE = np.dtype([("bin", "<u4"), ("reserved", "<u4"), ("count", "<u8"), ("pvalue", "<f8"), ("qvalue", "<f8")])  # hm_asm_bin_t, 32 bytes
+ASM_REGION_DTYPE = np.dtype([("start", "<i8"), ("end", "<i8"), ("pcov1", "<i8"), ("ncov1", "<i8"), ("pcov2", "<i8"), ("ncov2", "<i8"),
+                             ("n_loci", "<i4"), ("sign", "<i4"), ("motif", "<u4"), ("flags", "<u4"), ("diff", "<f8"),
+                             ("pmin", "<f8")])                                      # hm_asm_region_t, 80 bytes
+REGION_FIRST, REGION_LAST = 1, 2                                                      # HM_REGION_FIRST, HM_REGION_LAST
 ASM_T, ASM_PAIRS = 64, 2080                                                           # HM_ASM_T, HM_ASM_PAIRS
 ASM_BINS = 3 * ASM_PAIRS * ASM_PAIRS                                                  # HM_ASM_BINS
 SITE_DTYPE = np.dtype([("gpos", "<i8"), ("pcov", "<i4"), ("ncov", "<i4"), ("motif", "<u4"), ("reserved", "<u4"), ("pvalue", "<f8"),
@@ -194,6 +203,42 @@ def asm_summary_tsv(table: AsmTable) -> str:
     q = np.concatenate([table.tab["qvalue"], table.big_q])
     return "".join("%s\t%d\t%d\t%d\n" % (CTX_NAMES[c], int(table.m[c]), int(w[(ctx == c) & (q <= 0.05)].sum()),
                                           int(w[(ctx == c) & (q <= 0.01)].sum())) for c in range(3))
+
+
+def stitch_asm_regions(parts, max_gap: int, min_loci: int, keep_edges: bool = False) -> Tuple[np.ndarray, int]:
+    """parts = [(rows, n_ctx_rows)]: what asm_regions(..., keep_edges=True) gave for adjacent ranges of one sequence and one
+    context, in ascending order, all with the same max_p / max_gap / min_loci.  -> (rows, n_ctx_rows) equal, byte for byte, to
+    one fetch over the union of the ranges with this keep_edges.  Host only.
+    A part without rows of the context (n_ctx_rows == 0) neither links nor breaks.  The chain that holds a part's last row (LAST)
+    and the one that holds the next non-empty part's first row (FIRST) are one chain when they have the same sign and
+    right.start - (left.end - 1) <= max_gap: sums and n_loci add, pmin is the minimum, diff is recomputed from the sums; a chain
+    may span many parts.  FIRST / LAST survive only on a chain that reaches the first / last row of the whole."""
+    parts = [(np.ascontiguousarray(r, ASM_REGION_DTYPE), int(n)) for r, n in parts if int(n)]
+    out: List[np.ndarray] = []
+    open_ = None                                  # the chain that holds the last row seen so far, if that row is a hit
+    for k, (rows, _) in enumerate(parts):
+        for g in rows:
+            g = g.copy()
+            f = int(g["flags"])
+            g["flags"] = (f & REGION_FIRST if k == 0 else 0) | (f & REGION_LAST if k == len(parts) - 1 else 0)
+            if open_ is not None and f & REGION_FIRST and g["sign"] == open_["sign"] and g["start"] - (open_["end"] - 1) <= max_gap:
+                for c in ("pcov1", "ncov1", "pcov2", "ncov2", "n_loci"):
+                    open_[c] += g[c]
+                open_["end"] = g["end"]
+                open_["pmin"] = min(open_["pmin"], g["pmin"])
+                open_["flags"] |= g["flags"]
+                P1, N1, P2, N2 = (np.float64(open_[c]) for c in ("pcov1", "ncov1", "pcov2", "ncov2"))
+                open_["diff"] = np.float64(100.0) * P1 / (P1 + N1) - np.float64(100.0) * P2 / (P2 + N2)
+            else:
+                out.append(g)
+                open_ = g
+            if not f & REGION_LAST:
+                open_ = None
+        if not len(rows) or not int(rows[-1]["flags"]) & REGION_LAST:
+            open_ = None
+    keep = [g for g in out if g["n_loci"] >= min_loci or (keep_edges and g["flags"])]
+    rows = np.array(keep, ASM_REGION_DTYPE) if keep else np.zeros(0, ASM_REGION_DTYPE)
+    return rows, sum(n for _, n in parts)
 
 
 def sites_rates_tsv(sums, rates, m) -> str:
@@ -428,6 +473,31 @@ class MethylationPileup:
             text[CTX_NAMES[int(r["motif"])]].append("%s\t%d\t%d\t%g\t%.6g\t%d\t%d\t%d\t%d" % (
                 self.names[s], k, k + 1, r["diff"], r["pvalue"], r["pcov1"], r["ncov1"], r["pcov2"], r["ncov2"])
                 + ("\t%.6g\n" % r["qvalue"] if with_q else "\n"))
+        return {k: "".join(v) for k, v in text.items()}
+
+    def asm_regions(self, ctx: int, lo: int = 0, hi: Optional[int] = None, min_cov: int = 5, max_p: float = 0.01, max_gap: int = 500,
+                    min_loci: int = 3, planes=None, plane_base: int = 0, keep_edges: bool = False) -> Tuple[np.ndarray, int]:
+        """-> (rows, n_ctx_rows): the chains of context ctx (0 CpG, 1 CHG, 2 CHH) among the asm() rows of [lo, hi), ascending
+        (ASM_REGION_DTYPE), and the number of those rows.  A row is a hit when pvalue <= max_p and diff != 0; consecutive rows of
+        the context are linked when both are hits of one sign at most max_gap apart; a chain is a maximal run of linked hits, so a
+        tested row that is no hit breaks it.  Returned: the chains of at least min_loci loci and, with keep_edges, every chain
+        that holds the first or the last row (flags REGION_FIRST / REGION_LAST), for stitch_asm_regions.  `sign` is the loci's;
+        `diff`, on the pooled counts, can disagree with it.  planes as for asm()."""
+        hi = self.n_loci if hi is None else hi
+        ptrs = [None] * 5 if planes is None else [C.c_void_p(t.data_ptr()) for t in planes]
+        n_ctx_rows = C.c_int64(0)
+        rows = self._rows(self._L.hm_pileup_fetch_asm_regions, ASM_REGION_DTYPE, *ptrs, plane_base, lo, hi, min_cov, ctx, max_p,
+                          max_gap, min_loci, int(bool(keep_edges)), C.byref(n_ctx_rows))
+        return rows, int(n_ctx_rows.value)
+
+    def asm_regions_bed(self, rows: np.ndarray) -> dict:
+        """the text of <prefix>.asm.regions.{CpG,CHG,CHH}.bed: chrom, start, end, n_loci, +|-, diff, pmin, pcov1, ncov1, pcov2, ncov2"""
+        sid, soff = locate(self.offsets, rows["start"])
+        text = {k: [] for k in CTX_NAMES}
+        for s, k, r in zip(sid, soff, rows):
+            text[CTX_NAMES[int(r["motif"])]].append("%s\t%d\t%d\t%d\t%s\t%g\t%.6g\t%d\t%d\t%d\t%d\n" % (
+                self.names[s], k, k + (r["end"] - r["start"]), r["n_loci"], "+" if r["sign"] > 0 else "-", r["diff"], r["pmin"],
+                r["pcov1"], r["ncov1"], r["pcov2"], r["ncov2"]))
         return {k: "".join(v) for k, v in text.items()}
 
     def _plane_ptrs(self, planes):

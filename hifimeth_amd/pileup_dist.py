@@ -1,7 +1,7 @@
 """`hifimeth pileup` over N GPUs of one node, one process per GPU (the path's only exchange step).
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
-        -m hifimeth_amd.pileup_dist [-q mapQ] [-f identity] [-H [-A [-a min-cov] [-Q]]] [-B control | -e r,r,r] reference.fa mod.bam output-prefix
+        -m hifimeth_amd.pileup_dist [-q mapQ] [-f identity] [-H [-A [-a min-cov] [-Q] [-G [-s max-p] [-g max-gap] [-n min-loci]]]] [-B control | -e r,r,r] reference.fa mod.bam output-prefix
 
 Records are dealt to the ranks in slabs of `--slab` records (round-robin, like the `call` path).  Each rank projects its
 records and histograms them on its own GPU; then
@@ -18,6 +18,9 @@ chunk's first locus) and rank 0 also writes <prefix>.asm.<ctx>.bed; no further c
 -Q (with -A): every rank counts the tested loci of its chunk per (context, pcov1, ncov1, pcov2, ncov2) (all-reduce of 12 979 200
 int64; the few loci beyond the bins by all_gather_object), computes the p of every tuple that occurs on its own device, solves the same
 Benjamini-Hochberg q-values (hm_asm_qvalues) and writes its rows with the tenth column; rank 0 also writes <prefix>.asm.summary.tsv.
+-G (with -A): every rank chains the tested loci of each (sequence, context) inside its chunk (hm_pileup_fetch_asm_regions with
+keep_edges), the chains and the numbers of tested rows travel by all_gather_object, and rank 0 stitches the chains that cross a
+chunk boundary (stitch_asm_regions) and writes <prefix>.asm.regions.<ctx>.bed.
 -B control / -e rates: the per-locus binomial test.  After step 3 every rank sums the control sequence's part of its chunk
 (all-reduce of 6 int64 -> the same rates everywhere), histograms its chunk per (motif, pcov, pcov + ncov) (all-reduce of
 196 608 int64; the few loci beyond the histogram by all_gather_object), solves the same table (hm_sites_table) and writes its
@@ -35,12 +38,13 @@ from . import dist as D
 from .bamio import is_coordinate_sorted, load_fasta, read_bam
 from .pileup import (ASM_DTYPE, CTX_NAMES, LOCUS_DTYPE, MethylationPileup, allreduce_histograms, asm_qvalues, asm_summary_tsv,
                      locus_ranges, parse_rates, rates_from_sums, reduce_scatter_planes, reduce_scatter_sum, resolve_threshold,
-                     sites_rates_tsv, sites_table)
+                     sites_rates_tsv, sites_table, stitch_asm_regions)
 
 
 def run(reference: str, bam: str, prefix: str, min_mapq: int = 0, min_pi: float = 0.0, slab: int = 256,
         batch: int = 256, backend: str | None = None, log=sys.stderr, haplotypes: bool = False, asm: bool = False,
-        asm_min_cov: int = 5, control: str | None = None, rates=None, asm_q: bool = False):
+        asm_min_cov: int = 5, control: str | None = None, rates=None, asm_q: bool = False,
+        asm_regions: bool = False, max_p: float = 0.01, max_gap: int = 500, min_loci: int = 3):
     import torch
     rank, local_rank, world = D.env_world()
     dist = D.init_process_group(backend, force=bool(os.environ.get("HM_FORCE_COLLECTIVES")))
@@ -152,6 +156,23 @@ def run(reference: str, bam: str, prefix: str, min_mapq: int = 0, min_pi: float 
                 with open(f"{prefix}.asm.summary.tsv", "w") as f:
                     f.write(asm_summary_tsv(table))
         part["asm."] = pu.asm_bed(pu.asm(0, hi - lo, asm_min_cov, planes=asm_planes, plane_base=base, table=table))
+    if asm_regions:                                         # per (sequence, context): this rank's chains, edge chains kept
+        chains = {}
+        for sid in range(len(genome)):
+            a, b = max(int(pu.offsets[sid]), lo), min(int(pu.offsets[sid + 1]), hi)
+            for c in range(3 if a < b else 0):
+                chains[sid, c] = pu.asm_regions(c, a - base, b - base, asm_min_cov, max_p, max_gap, min_loci, planes=(*hp, key),
+                                              plane_base=base, keep_edges=True)
+        every = [chains]
+        if dist is not None:
+            every = [None] * world
+            dist.all_gather_object(every, chains)             # rank order = locus order
+        if rank == 0:
+            for c in range(3):
+                with open(f"{prefix}.asm.regions.{CTX_NAMES[c]}.bed", "w") as f:
+                    for sid in range(len(genome)):
+                        rows, _ = stitch_asm_regions([m[sid, c] for m in every if (sid, c) in m], max_gap, min_loci)
+                        f.write(pu.asm_regions_bed(rows)[CTX_NAMES[c]])
     if control is not None or rates is not None:
         mine, n_mine = (pc, nc, key), hi - lo               # this rank's chunk: element 0 is locus `base`
         sums = np.zeros(6, np.uint64)
@@ -206,6 +227,11 @@ def main(argv=None):
     ap.add_argument("-a", dest="asm_min_cov", type=int, default=None, help="with -A: minimum coverage of each haplotype (default 5)")
     ap.add_argument("-Q", dest="asm_q", action="store_true",
                     help="with -A: Benjamini-Hochberg q-value per tested locus (tenth column), <prefix>.asm.summary.tsv")
+    ap.add_argument("-G", dest="asm_regions", action="store_true",
+                    help="with -A: runs of tested loci with p <= -s and a difference of one sign -> <prefix>.asm.regions.<ctx>.bed")
+    ap.add_argument("-s", dest="max_p", type=float, default=None, help="with -G: largest p-value of a locus in a region, in (0, 1] (default 0.01)")
+    ap.add_argument("-g", dest="max_gap", type=int, default=None, help="with -G: largest distance between consecutive loci, >= 1 (default 500)")
+    ap.add_argument("-n", dest="min_loci", type=int, default=None, help="with -G: smallest number of loci of a region, >= 1 (default 3)")
     ap.add_argument("-B", dest="control", default=None, metavar="NAME",
                     help="per-locus binomial test against the false-positive rates measured on this unmethylated control sequence "
                          "-> <prefix>.sites.<ctx>.bed, <prefix>.sites.rates.tsv")
@@ -223,6 +249,14 @@ def main(argv=None):
         ap.error("-a must be >= 1")
     if a.asm_q and not a.asm:
         ap.error("-Q needs -A")
+    if a.asm_regions and not a.asm:
+        ap.error("-G needs -A")
+    if not a.asm_regions and not (a.max_p is None and a.max_gap is None and a.min_loci is None):
+        ap.error("-s, -g and -n need -G")
+    if a.max_p is not None and not 0.0 < a.max_p <= 1.0:
+        ap.error("-s must be in (0, 1]")
+    if (a.max_gap is not None and a.max_gap < 1) or (a.min_loci is not None and not 1 <= a.min_loci < 2 ** 31):
+        ap.error("-g and -n must be >= 1")
     if a.control is not None and a.rates is not None:
         ap.error("-B and -e exclude each other")
     rates = None
@@ -233,7 +267,8 @@ def main(argv=None):
             ap.error(f"-e: {e}")
     return run(a.reference, a.mod_bam, a.output_prefix, a.q, a.f, slab=a.slab, backend=a.backend, haplotypes=a.haplotypes,
                asm=a.asm, asm_min_cov=5 if a.asm_min_cov is None else a.asm_min_cov, control=a.control, rates=rates,
-               asm_q=a.asm_q)
+               asm_q=a.asm_q, asm_regions=a.asm_regions, max_p=0.01 if a.max_p is None else a.max_p,
+               max_gap=500 if a.max_gap is None else a.max_gap, min_loci=3 if a.min_loci is None else a.min_loci)
 
 
 if __name__ == "__main__":

@@ -368,6 +368,39 @@ int64_t hm_pileup_fetch_asm_q(hm_pileup_t* p, const void* pcov1, const void* nco
                               const hm_asm_bin_t* tab, int64_t n_tab, const hm_asm_t* big, const double* big_q, int64_t n_big,
                               hm_asmq_t* out, int64_t cap);
 
+/* ---- allele-specific methylated regions (`pileup -H -A -G`): runs of loci that lean the same way ----------
+ * Per context c (0 CpG, 1 CHG, 2 CHH) and plane range [lo, hi).  ROWS r_0 .. r_{R-1}: the rows hm_pileup_fetch_asm returns for
+ * [lo, hi) and min_cov whose min(motif, 2) == c, ascending in gpos (the rows of <prefix>.asm.<ctx>.bed for the range); a locus of
+ * another context, or one that is not tested, is no row and neither links nor breaks anything.  Row i is a HIT when
+ * pvalue_i <= max_p and diff_i != 0; its sign is +1 for diff_i > 0, -1 for diff_i < 0.  Rows i-1 and i are LINKED when both are
+ * hits, of the same sign, and gpos_i - gpos_{i-1} <= max_gap.  A CHAIN is a maximal set of consecutively linked hits: a tested
+ * row of the context that is no hit breaks it on purpose (it is evidence against the region); a single hit is a chain of one.
+ * One hm_asm_region_t per chain: start = gpos of its first locus, end = gpos of its last + 1; pcov1 .. ncov2 the exact int64 sums
+ * over its rows; diff = 100 * P1 / (P1 + N1) - 100 * P2 / (P2 + N2) on those pooled sums, the three correctly rounded fp64
+ * operations of hm_asm_t::diff in the same order (bit-equal to the host's); pmin = the smallest pvalue among its rows, that row's
+ * bits.  `sign` is the property of the LOCI: the pooled diff can have the other sign (Simpson's paradox) or be 0.  flags are
+ * always set, whatever keep_edges is.  There is no region-level p-value: the loci were selected by their p, so a test of the
+ * pooled counts would not be one.  The rows are a pure function of the hm_asm_t rows and (max_p, max_gap, min_loci, keep_edges):
+ * integer sums only, nothing depends on launch geometry. */
+#define HM_REGION_FIRST 1u  /* the chain contains r_0 */
+#define HM_REGION_LAST 2u   /* the chain contains r_{R-1} */
+typedef struct {            /* one chain = one row of <prefix>.asm.regions.<ctx>.bed; 80 bytes */
+    int64_t start, end;
+    int64_t pcov1, ncov1, pcov2, ncov2;
+    int32_t n_loci, sign;
+    uint32_t motif, flags;  /* motif = c */
+    double diff, pmin;
+} hm_asm_region_t;
+/* The chains of context ctx in planes[lo, hi), ascending in start: those with n_loci >= min_loci and, when keep_edges != 0, also
+ * every chain with flags != 0 whatever its length (what a caller needs to stitch adjacent ranges).  Planes as in
+ * hm_pileup_fetch_asm.  Returns the number of regions (may exceed cap: then nothing is written); *n_ctx_rows, if not NULL,
+ * receives R.  hi == lo returns 0.  HM_EINVAL for ctx outside 0..2, max_p NaN or outside (0, 1], max_gap < 1, min_loci < 1 and
+ * what hm_pileup_fetch_asm refuses. */
+int64_t hm_pileup_fetch_asm_regions(hm_pileup_t* p, const void* pcov1, const void* ncov1, const void* pcov2, const void* ncov2,
+                                    const void* key, int64_t plane_base, int64_t lo, int64_t hi, int32_t min_cov, int32_t ctx,
+                                    double max_p, int64_t max_gap, int32_t min_loci, int32_t keep_edges, int64_t* n_ctx_rows,
+                                    hm_asm_region_t* out, int64_t cap);
+
 /* ---- per-locus binomial test (`pileup -B / -e`): is a locus methylated at all ------------------------
  * Against a false-positive rate e per context -- given, or measured on an unmethylated control sequence as sum(pcov) /
  * sum(pcov + ncov) -- a covered locus with k = pcov, n = pcov + ncov gets p = P(X >= k), X ~ Binomial(n, e), and the

@@ -9,9 +9,10 @@ compaction at the end.  Prints one JSON object; `--check` verifies that the per-
 fetch then also compacts the two partitions' planes.
 `--asm` (with `--partitions`): the allele-specific test of `pileup -H -A` over the counted planes: select + Fisher test + D2H per pass.
 `--asm-q` (with `--asm`): the q-values of `pileup -H -A -Q`: histogram + bin p-values + table (host) + rows with q (D2H included) per pass.
+`--asm-regions` (with `--asm`): the regions of `pileup -H -A -G`: per context, select + test + chain + D2H of the region rows per pass.
 `--sites`: the binomial test of `pileup -B / -e` over the counted planes: histogram + table + rows (D2H included) per pass.
 
-    python tools/pileup_bench.py --genome-mb 20 --coverage 10 [--partitions [--asm [--asm-q]]] [--sites]
+    python tools/pileup_bench.py --genome-mb 20 --coverage 10 [--partitions [--asm [--asm-q] [--asm-regions]]] [--sites]
 """
 import argparse
 import ctypes as C
@@ -89,6 +90,10 @@ def main():
     ap.add_argument("--asm", action="store_true", help="with --partitions: time the per-locus haplotype test (pileup -H -A)")
     ap.add_argument("--asm-min-cov", type=int, default=5)
     ap.add_argument("--asm-q", action="store_true", help="with --asm: time the Benjamini-Hochberg q-values of the test (pileup -H -A -Q)")
+    ap.add_argument("--asm-regions", action="store_true", help="with --asm: time the chaining of tested loci into regions (pileup -H -A -G)")
+    ap.add_argument("--regions-max-p", type=float, default=0.01)
+    ap.add_argument("--regions-max-gap", type=int, default=500)
+    ap.add_argument("--regions-min-loci", type=int, default=3)
     ap.add_argument("--sites", action="store_true", help="time the per-locus binomial test (pileup -B / -e)")
     ap.add_argument("--sites-rate", type=float, default=0.013, help="with --sites: the false-positive rate of all three contexts")
     ap.add_argument("--cpu-baseline", action="store_true",
@@ -98,6 +103,8 @@ def main():
         ap.error("--asm needs --partitions")
     if a.asm_q and not a.asm:
         ap.error("--asm-q needs --asm")
+    if a.asm_regions and not a.asm:
+        ap.error("--asm-regions needs --asm")
 
     rng = np.random.default_rng(1)
     G = int(a.genome_mb * 1e6)
@@ -212,6 +219,25 @@ def main():
             plain = np.ascontiguousarray(rows_q[list(rows.dtype.names)]).astype(rows.dtype)
             out["check_asmq_rows_are_the_asm_rows"] = bool(plain.tobytes() == rows.tobytes() and not np.isnan(rows_q["qvalue"]).any()
                                                            and int(table.m.sum()) == len(rows))
+    if a.asm_regions:                              # the three contexts over the whole sequence, as the CLI does
+        def regions_pass():
+            return [pu.asm_regions(c, min_cov=a.asm_min_cov, max_p=a.regions_max_p, max_gap=a.regions_max_gap,
+                                   min_loci=a.regions_min_loci) for c in range(3)]
+
+        regions_pass()                             # warm-up: the row buffers
+        t0 = time.perf_counter()
+        for _ in range(a.repeat):
+            found = regions_pass()
+        t_reg = (time.perf_counter() - t0) / a.repeat
+        ctx_rows = sum(n for _r, n in found)
+        t_hp_pass = t_project / a.repeat + t_count / a.repeat + t_loci + t_hp_loci + t_asm     # a -H -A pass
+        out.update(regions_max_p=a.regions_max_p, regions_max_gap=a.regions_max_gap, regions_min_loci=a.regions_min_loci,
+                   regions_ctx_rows=int(ctx_rows), regions=[int(len(r)) for r, _n in found],
+                   regions_longest_chain=int(max((int(r["n_loci"].max()) for r, _n in found if len(r)), default=0)),
+                   regions_s_per_pass=round(t_reg, 4), regions_rows_per_s=round(ctx_rows / t_reg) if t_reg else 0,
+                   regions_share_of_asm_pass=round(t_reg / t_hp_pass, 4))
+        if a.check:                                # every tested row belongs to exactly one context
+            out["check_regions_rows_are_the_asm_rows"] = bool(ctx_rows == len(rows))
     if a.sites:                                    # histogram, table (host), rows of every covered locus, as the CLI does
         from hifimeth_amd.pileup import sites_table
         pu.sites(sites_table([a.sites_rate] * 3, *pu.site_histogram()))    # warm-up: buffers, the log n! table
