@@ -853,7 +853,7 @@ int hm_create(hm_engine_t** out, const char* model_dir, int ctx_mask, int device
             if (!(e->ctx_mask >> c & 1)) continue;
             HostModel hmw;
             std::string msg;
-            if (!load_model_dir(model_dir, names[c], hmw, msg)) return fail(nullptr, HM_EMODEL, msg);
+            if (!load_model_dir(model_dir, names[c], hmw, msg) || !check_model(hmw, names[c], msg)) return fail(nullptr, HM_EMODEL, msg);
             upload_model(e.get(), c, hmw);
         }
         new_slot(e.get(), 0)->state = hm_batch::STAGING;

@@ -411,6 +411,62 @@ static void align_blob(std::vector<float>& blob) {
     while (blob.size() % 64) blob.push_back(0.f);  // 256-byte alignment of every section
 }
 
+// bn0 as ONNX BatchNormalization computes it: y = (x - mean) / sqrt(var + eps) * gamma + beta in fp32
+static float bn0(const HostModel& m, int c, float x) {
+    volatile float t = (x - m.bn_mean[c]) / sqrtf(m.bn_var[c] + m.bn_eps);
+    volatile float u = t * m.bn_gamma[c];
+    return (float)(u + m.bn_beta[c]);
+}
+
+// bn0 of kinetics channel 4 + c as value = kb + ka * frames (frames: the decoded codev1 byte, 0..952): its slope
+static float kin_slope(const HostModel& m, int c) {
+    const double sd = sqrt((double)m.bn_var[4 + c] + m.bn_eps), g = m.bn_gamma[4 + c];
+    return (float)(g / (sd * 952.0));
+}
+
+// what conv1's weights of input channel c are multiplied by when bn0 is folded into them (see pack_model)
+static float conv1_slope(const HostModel& m, int c) {
+    return c < 4 ? bn0(m, c, 1.f) - bn0(m, c, 0.f) : kin_slope(m, c - 4) * 32.0f;
+}
+
+static bool half_is_finite(float x) {
+    return std::isfinite((float)(_Float16)x);
+}
+
+bool check_model(const HostModel& m, const char* name, std::string& err) {
+    char txt[64];
+    auto refuse = [&](const std::string& layer, const char* what, float v) {
+        snprintf(txt, sizeof txt, "%g", (double)v);
+        err = std::string("model ") + name + ": " + layer + " " + what + " " + txt;
+        return false;
+    };
+    auto finite = [&](const std::string& layer, const float* p, size_t n) {
+        for (size_t i = 0; i < n; ++i)
+            if (!std::isfinite(p[i])) return refuse(layer, "holds a value that is not finite:", p[i]);
+        return true;
+    };
+    // the split-half kernels hold every conv and fc1 weight as fp16 hi + lo: at |w| >= 65520 the hi half is an infinity
+    auto splits = [&](const std::string& layer, const std::vector<float>& w) {
+        for (float v : w)
+            if (!half_is_finite(v)) return refuse(layer, "holds a weight whose fp16 half is not finite (|w| must stay below 65520):", v);
+        return true;
+    };
+    if (!finite("bn0", m.bn_gamma, 8) || !finite("bn0", m.bn_beta, 8) || !finite("bn0", m.bn_mean, 8) || !finite("bn0", m.bn_var, 8)) return false;
+    for (int i = 0; i < 8; ++i) {
+        const std::string layer = "conv" + std::to_string(i + 1);
+        if (!finite(layer, m.conv_w[i].data(), m.conv_w[i].size()) || !finite(layer + " bias", m.conv_b[i].data(), m.conv_b[i].size())) return false;
+        if (!splits(layer, m.conv_w[i])) return false;
+    }
+    if (!finite("fc1", m.fc1_w.data(), m.fc1_w.size()) || !finite("fc1 bias", m.fc1_b.data(), m.fc1_b.size()) || !splits("fc1", m.fc1_w)) return false;
+    if (!finite("fc2", m.fc2_w.data(), m.fc2_w.size()) || !finite("fc2 bias", m.fc2_b.data(), m.fc2_b.size())) return false;
+    const int k1 = m.kernel[0];
+    for (size_t i = 0; i < m.conv_w[0].size(); ++i) {
+        const float f = m.conv_w[0][i] * conv1_slope(m, (int)(i / k1 % 8));  // [128][8][k1]
+        if (!half_is_finite(f)) return refuse("conv1 folded with bn0", "holds a weight x slope whose fp16 half is not finite:", f);
+    }
+    return true;
+}
+
 PackedModel pack_model(const HostModel& m) {
     PackedModel pk;
     std::vector<float>& b = pk.blob;
@@ -446,8 +502,7 @@ PackedModel pack_model(const HostModel& m) {
     pk.fc2_b_off = b.size();
     b.insert(b.end(), m.fc2_b.begin(), m.fc2_b.end());
 
-    // bn0 tables: ONNX BatchNormalization y = (x - mean) / sqrt(var + eps) * gamma + beta in fp32
-    BnTables bn;
+    BnTables bn;  // bn0 tables
     int dec[256];
     {
         int p = 0;  // codev1 table, bam_info.cpp:562-570
@@ -456,11 +511,7 @@ PackedModel pack_model(const HostModel& m) {
         for (int i = 128; i < 192; ++i) dec[p++] = (i - 128) * 4 + 192;
         for (int i = 192; i < 256; ++i) dec[p++] = (i - 192) * 8 + 448;
     }
-    auto bnf = [&](int c, float x) {
-        volatile float t = (x - m.bn_mean[c]) / sqrtf(m.bn_var[c] + m.bn_eps);
-        volatile float u = t * m.bn_gamma[c];
-        return (float)(u + m.bn_beta[c]);
-    };
+    auto bnf = [&](int c, float x) { return bn0(m, c, x); };
     for (int c = 0; c < 8; ++c) {
         bn.zero[c] = bnf(c, 0.f);
         bn.mean[c] = m.bn_mean[c];
@@ -525,7 +576,7 @@ PackedModel pack_model(const HostModel& m) {
         bh.hot[c] = split(bn.hot[c]);
         for (int t = 0; t < 256; ++t) bh.lut[c][t] = split(bn.lut[c][t]);
         const double sd = sqrt((double)m.bn_var[4 + c] + m.bn_eps), g = m.bn_gamma[4 + c];
-        bh.ka[c] = (float)(g / (sd * 952.0));
+        bh.ka[c] = kin_slope(m, c);
         bh.kb[c] = (float)(m.bn_beta[4 + c] - m.bn_mean[4 + c] * g / sd);
     }
     align_blob(b);
@@ -548,7 +599,7 @@ PackedModel pack_model(const HostModel& m) {
         auto W = [&](int co, int c, int t) { return w[((size_t)co * 8 + c) * k1 + t]; };
         // the frame counts reach the MFMA as frames / 32 (still exact in fp16: a power-of-two scale) and the weights take the
         // x32: ka ~ 2^-5, and weights that small would leave their fp16 lo halves in the subnormal range (4 bits instead of 11)
-        auto slope = [&](int c) { return c < 4 ? bn.hot[c] - bn.zero[c] : bh.ka[c - 4] * 32.0f; };
+        auto slope = [&](int c) { return conv1_slope(m, c); };  // hot[c] - zero[c] | ka[c - 4] * 32
         auto konst = [&](int c) { return c < 4 ? (double)bn.zero[c] : (double)bh.kb[c - 4]; };
         std::vector<uint16_t> hw((size_t)8 * KB * 64 * 8);
         size_t o = 0;

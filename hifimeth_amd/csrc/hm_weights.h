@@ -31,6 +31,9 @@ struct PackedModel {
 bool load_model_dir(const char* dir, const char* name, HostModel& out, std::string& err);
 bool load_hmw(const std::string& path, HostModel& out, std::string& err);
 bool load_onnx(const std::string& path, HostModel& out, std::string& err);
+// Can pack_model hold the model?  Every parameter finite, and every weight the split-half kernels keep as fp16 hi + lo -- conv1 .. conv8,
+// fc1, conv1 with bn0's slopes folded in -- with a finite hi half.  If not: false, `err` names the context `name` and the layer.
+bool check_model(const HostModel& m, const char* name, std::string& err);
 PackedModel pack_model(const HostModel& m);
 bool save_hmw(const HostModel& m, const std::string& path, std::string& err);
 

@@ -44,7 +44,7 @@ extern "C" {
 
 #define HM_OK 0
 #define HM_EINVAL (-1)  /* bad argument                                             */
-#define HM_EMODEL (-2)  /* model file missing / ill-formed (mod_main.cpp:40-52)     */
+#define HM_EMODEL (-2)  /* model file missing / ill-formed (mod_main.cpp:40-52), or a weight that is not finite (as fp32, or as the fp16 half the kernels keep) */
 #define HM_EDEVICE (-3) /* HIP runtime error or no gfx950 device                    */
 #define HM_EDATA (-4)   /* illegal base nibble in a read (bam_info.cpp:100-121)     */
 #define HM_ESTATE (-5)  /* call out of order (e.g. hm_fetch before hm_run)          */

@@ -156,11 +156,12 @@ def _onnx_node(op, inputs, outputs, **attrs):
             + b"".join(_pb_bytes(5, _onnx_attr(k, v)) for k, v in attrs.items()))
 
 
-def _write_onnx(w, path, dialect):
+def _write_onnx(w, path, dialect, omit_bias=()):
     """The model `w` as an ONNX file in one of the two dialects the readers accept (hifimeth_amd/onnx_weights.py):
     "initializers" -- opset 17, weights as graph initializers, FC = Gemm(transB=1) on [out, in];
     "constants"    -- opset 11, weights as Constant nodes (biases as float_data), FC = MatMul on [in, out] + Add.
-    Both carry ops and an int64 shape tensor that the readers must pass over."""
+    Both carry ops and an int64 shape tensor that the readers must pass over.  The convs whose 0-based index is in `omit_bias` get no
+    bias input (their bias must be all zero: the readers supply zeros)."""
     inits, nodes = [], []
 
     def param(name, arr):
@@ -177,7 +178,11 @@ def _write_onnx(w, path, dialect):
     nodes.append(_onnx_node("BatchNormalization", ["x_t"] + bn, ["bn0_out"], epsilon=w.bn_eps, momentum=0.9))
     x = "bn0_out"
     for i, (cw, cb) in enumerate(zip(w.conv_w, w.conv_b)):
-        ins = [x, param(f"conv{i + 1}.weight", cw), param(f"conv{i + 1}.bias", cb)]
+        ins = [x, param(f"conv{i + 1}.weight", cw)]
+        if i in omit_bias:
+            assert not np.asarray(cb).any(), i
+        else:
+            ins.append(param(f"conv{i + 1}.bias", cb))
         nodes.append(_onnx_node("Conv", ins, [f"conv{i + 1}_out"], dilations=[1], group=1, kernel_shape=[cw.shape[2]],
                                 pads=[1, 1], strides=[2]))
         nodes.append(_onnx_node("Relu", [f"conv{i + 1}_out"], [f"relu{i + 1}"]))
