@@ -20,6 +20,9 @@
 // by pvalue and qvalue -- the one-sided binomial test of the locus against the context's false-positive rate (measured on the
 // unmethylated control sequence, or given) and its Benjamini-Hochberg q-value within the context -- and <prefix>.sites.rates.tsv
 // (DESIGN.md section 10).
+// -D (ours): also <prefix>.domains.<ctx>.bed, the covered loci of each context cut into low and high methylated stretches by an
+// exact two-state Viterbi scan on the GPU (levels -u, switch penalty -x, largest linking distance -j):
+//   chrom <tab> start <tab> end <tab> n_loci <tab> L|H <tab> level <tab> pcov <tab> ncov <tab> score      (DESIGN.md section 10).
 // -K (ours): the input is an aligned BAM that still carries the kinetics tags (pbmm2 keeps fi / fp / ri / rp): the reads are called
 // on the fly by the call engine and their calls go straight to the pileup engine (hm_pileup_submit_read_calls) -- the files
 // `call` followed by `pileup` writes, without the mod-BAM between the two.
@@ -91,6 +94,11 @@ struct PileupOptions {
     std::string control;      // -B: name of the unmethylated control sequence -> rates measured there, <prefix>.sites.*
     bool rates_given = false; // -e: the three rates given directly (NaN: context not tested)
     double rates[3] = {0, 0, 0};
+    bool domains = false;     // -D: low / high methylated stretches -> <prefix>.domains.*
+    double domain_lo[3] = {0.1, 0.05, 0.02}, domain_hi[3] = {0.8, 0.5, 0.2};  // -u: the two levels per context; NaN: not segmented
+    double domain_penalty = 8.0;       // -x: cost of a change of state, in nats
+    long long domain_max_gap = 1000;   // -j: largest distance that still links two loci
+    bool domain_option_given = false, domain_option_bad = false;  // any of -u -x -j; one of them with a value out of range
     // -K: call on the fly; the options below are `call`'s (hifimeth_call.cpp), same meaning and defaults
     bool kinetics = false;
     bool call_option_given = false;  // any of -m -c -l -p -T: a usage error without -K
@@ -133,6 +141,15 @@ void pileup_usage(const char* exe) {
             "    the context, and <prefix>.sites.rates.tsv: ctx, P, N, rate, loci\n"
             "  -e <r_cpg,r_chg,r_chh>\n    Instead of -B: the three rates, each a decimal in [0, 1] or nan (context not tested), e.g. those an earlier\n"
             "    run wrote to <prefix>.sites.rates.tsv\n"
+            "  -D\n    Cut the covered loci of each context into low (L) and high (H) methylated stretches and write <prefix>.domains.<ctx>.bed:\n"
+            "    chrom, start, end, loci, L or H, 100 * pcov / (pcov + ncov) of the pooled counts, pcov, ncov, score (the pooled log-likelihood\n"
+            "    ratio high : low in nats).  The stretches are the best path of a two-state model: a read counts log(hi / lo) when methylated\n"
+            "    and log((1 - hi) / (1 - lo)) when not, a change of state costs -x, and loci more than -j bases apart are not linked.  The\n"
+            "    combined counts are segmented, with or without -H.  The defaults below are conventions; nobody has tuned them on data\n"
+            "  -u <lo:hi[,lo:hi,lo:hi]>\n    With -D: the low and the high methylation level, 0 < lo < hi < 1, one pair for all contexts or one per\n"
+            "    context (CpG,CHG,CHH); nan instead of a pair: that context is not segmented\n    Default: 0.1:0.8,0.05:0.5,0.02:0.2\n"
+            "  -x <nats>\n    With -D: penalty of a change of state, in [0, 256]\n    Default: 8\n"
+            "  -j <bp>\n    With -D: largest distance between two loci that still links them, >= 1\n    Default: 1000\n"
             "  -K\n    The input is an aligned BAM that carries the kinetics tags fi / fp / ri / rp instead of MM / ML: call 5mC on the\n"
             "    fly and pile the calls up directly.  For equal -c -l -p -T -q -f the output files are byte-identical to those of\n"
             "    `%s call` on that BAM followed by `%s pileup` on its output; no mod-BAM is written.  (Give -T explicitly\n"
@@ -747,6 +764,11 @@ void report_thresholds(const uint64_t* bins, uint8_t thr[3]) {
 }  // namespace
 
 namespace {
+// the locus a row is named by
+template <class Row>
+int64_t row_pos(const Row& r) { return r.gpos; }
+inline int64_t row_pos(const hm_domain_t& r) { return r.start; }
+
 // The rows of three per-context BED files, sequence by sequence.  fetch(lo, hi, dst, cap) is the engine's row fetch over the
 // plane range of one sequence (dst NULL: the number of rows only); format(row, k, buf) prints the columns behind the sequence
 // name of a row at offset k and returns their length; the file of a row is its motif.  Rows are formatted by `threads` workers
@@ -773,7 +795,7 @@ bool write_rows(const Fasta& fa, FILE* const out[3], int threads, Fetch fetch, F
             char buf[320];
             for (size_t i = a; i < b; ++i) {
                 const Row& r = rows[i];
-                const int len = format(r, r.gpos - lo, buf);
+                const int len = format(r, row_pos(r) - lo, buf);
                 std::string& t = text[(size_t)w * 3 + (r.motif < 3 ? r.motif : 2)];
                 t += fa.names[s];
                 t.append(buf, (size_t)len);
@@ -843,6 +865,51 @@ bool write_asm_regions(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o,
         }
     }
     return true;
+}
+
+// -u: one lo:hi pair for all contexts or three, each pair possibly nan; false unless the whole text parses
+bool parse_levels(const char* text, double lo[3], double hi[3]) {
+    std::vector<std::string> items(1);
+    for (const char* p = text; *p; ++p) {
+        if (*p == ',') items.emplace_back();
+        else items.back() += *p;
+    }
+    if (items.size() != 1 && items.size() != 3) return false;
+    for (int c = 0; c < 3; ++c) {
+        const std::string& t = items[items.size() == 1 ? 0 : (size_t)c];
+        if (t == "nan") { lo[c] = hi[c] = std::nan(""); continue; }
+        const size_t colon = t.find(':');
+        if (colon == std::string::npos || t.find_first_not_of("0123456789.eE+-:") != std::string::npos) return false;
+        const std::string a = t.substr(0, colon), b = t.substr(colon + 1);
+        char *ea = nullptr, *eb = nullptr;
+        lo[c] = strtod(a.c_str(), &ea);
+        hi[c] = strtod(b.c_str(), &eb);
+        if (a.empty() || b.empty() || *ea || *eb) return false;
+    }
+    return true;
+}
+
+// rows of the three <prefix>.domains.<ctx>.bed files from the engine's combined planes, sequence by sequence: a segment never
+// crosses a sequence.  A sequence's rows are the segments of the first segmented context, then the next one's.  false on an engine
+// error.
+bool write_domains(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, const int64_t A[3], const int64_t B[3], int64_t S, FILE* out[3]) {
+    return write_rows<hm_domain_t>(
+        fa, out, o.threads,
+        [&](int64_t lo, int64_t hi, hm_domain_t* dst, int64_t cap) -> int64_t {
+            int64_t total = 0;
+            for (int c = 0; c < 3; ++c) {
+                if (std::isnan(o.domain_lo[c])) continue;
+                const int64_t n = hm_pileup_fetch_domains(pe, nullptr, nullptr, nullptr, 0, lo, hi, c, A[c], B[c], S, o.domain_max_gap, nullptr,
+                                                          dst ? dst + total : nullptr, dst ? cap - total : 0);
+                if (n < 0) return n;
+                total += n;
+            }
+            return total;
+        },
+        [](const hm_domain_t& r, int64_t k, char (&buf)[320]) {
+            return snprintf(buf, sizeof buf, "\t%lld\t%lld\t%d\t%c\t%g\t%lld\t%lld\t%.6g\n", (long long)k, (long long)(k + (r.end - r.start)),
+                            r.n_loci, r.state ? 'H' : 'L', r.level, (long long)r.pcov, (long long)r.ncov, r.score);
+        });
 }
 
 // `pileup -H -A -Q` after hm_pileup_count: the tested loci of the whole reference counted per tuple, the p of every tuple that
@@ -1126,6 +1193,7 @@ int cmd_pileup(int argc, char** argv) {
         if (a == "-Q") { o.asm_q = true; continue; }
         if (a == "-G") { o.asm_regions = true; continue; }
         if (a == "-K") { o.kinetics = true; continue; }
+        if (a == "-D") { o.domains = true; continue; }
         if (i + 1 >= argc) { pileup_usage(argv[0]); return EXIT_FAILURE; }
         if (a == "-q") o.min_mapq = atoi(argv[++i]);
         else if (a == "-f") o.min_pi = atof(argv[++i]);
@@ -1148,6 +1216,21 @@ int cmd_pileup(int argc, char** argv) {
                 else o.region_min_loci = (int)x;
             }
             if (end == v || *end || errno) o.region_option_bad = true;
+        }
+        else if (a == "-u" || a == "-x" || a == "-j") {  // the whole value must parse, and lie in the option's range
+            o.domain_option_given = true;
+            const char* v = argv[++i];
+            char* end = nullptr;
+            errno = 0;
+            if (a == "-u") {
+                if (!parse_levels(v, o.domain_lo, o.domain_hi)) o.domain_option_bad = true;
+            } else if (a == "-x") {
+                o.domain_penalty = strtod(v, &end);
+                if (end == v || *end || errno || !(o.domain_penalty >= 0.0 && o.domain_penalty <= 256.0)) o.domain_option_bad = true;
+            } else {
+                o.domain_max_gap = strtoll(v, &end, 10);
+                if (end == v || *end || errno || o.domain_max_gap < 1) o.domain_option_bad = true;
+            }
         }
         else if (a == "-B") o.control = argv[++i];
         else if (a == "-e") {
@@ -1185,6 +1268,14 @@ int cmd_pileup(int argc, char** argv) {
     if (bad_call) { fprintf(stderr, "ERROR: %s\n", bad_call); pileup_usage(argv[0]); return EXIT_FAILURE; }
     const char* bad_sites = !o.control.empty() && o.rates_given ? "-B and -e exclude each other (the rates are measured, or given)" : nullptr;
     if (bad_sites) { fprintf(stderr, "ERROR: %s\n", bad_sites); pileup_usage(argv[0]); return EXIT_FAILURE; }
+    int64_t dom_A[3] = {0, 0, 0}, dom_B[3] = {0, 0, 0}, dom_S = 0;  // the integer weights of the levels (hm_domain_scores)
+    for (int c = 0; c < 3 && o.domains && !o.domain_option_bad; ++c)
+        if (!std::isnan(o.domain_lo[c]) && hm_domain_scores(o.domain_lo[c], o.domain_hi[c], o.domain_penalty, &dom_A[c], &dom_B[c], &dom_S) != HM_OK)
+            o.domain_option_bad = true;
+    const char* bad_domains = o.domain_option_given && !o.domains ? "-u, -x and -j need -D"
+                              : o.domain_option_bad ? "-u takes lo:hi with 0 < lo < hi < 1 (levels a 2^24-th of a nat apart at least) or nan, once or per context; "
+                                                      "-x must be in [0, 256], -j an integer >= 1" : nullptr;
+    if (bad_domains) { fprintf(stderr, "ERROR: %s\n", bad_domains); pileup_usage(argv[0]); return EXIT_FAILURE; }
     const bool sites = !o.control.empty() || o.rates_given;
     if (o.kinetics && o.model_dir.empty()) o.model_dir = exe_dir() + "/../weights";
     o.ref = argv[i];
@@ -1201,6 +1292,16 @@ int cmd_pileup(int argc, char** argv) {
                 o.region_max_gap, o.prefix.c_str());
     if (!o.control.empty()) fprintf(stderr, "sites: binomial test against the rates of control sequence %s -> %s.sites.*\n", o.control.c_str(), o.prefix.c_str());
     if (o.rates_given) fprintf(stderr, "sites: binomial test against the rates %g,%g,%g -> %s.sites.*\n", o.rates[0], o.rates[1], o.rates[2], o.prefix.c_str());
+    if (o.domains) {
+        std::string levels;
+        for (int c = 0; c < 3; ++c) {
+            char t[64] = "nan";
+            if (!std::isnan(o.domain_lo[c])) snprintf(t, sizeof t, "%g:%g", o.domain_lo[c], o.domain_hi[c]);
+            levels += (c ? "," : "") + std::string(t);
+        }
+        fprintf(stderr, "domains: levels %s, switch penalty %g nats, loci linked up to %lld bases -> %s.domains.*\n", levels.c_str(), o.domain_penalty,
+                o.domain_max_gap, o.prefix.c_str());
+    }
     if (o.kinetics)
         fprintf(stderr, "kinetics: called on the fly (models %s, contexts%s%s%s, min read length %d, precision %d, trunk %s)\n", o.model_dir.c_str(),
                 o.ctx_mask & 1 ? " CpG" : "", o.ctx_mask & 2 ? " CHG" : "", o.ctx_mask & 4 ? " CHH" : "", o.min_read_size, o.precision,
@@ -1394,6 +1495,22 @@ int cmd_pileup(int argc, char** argv) {
         const bool ok = write_asm_regions(pe, fa, o, out);
         for (FILE* f : out) fclose(f);
         if (!ok) return die("asm regions");
+    }
+    if (o.domains) {
+        FILE* out[3];
+        for (int c = 0; c < 3; ++c) {
+            const std::string path = o.prefix + ".domains." + cn[c] + ".bed";
+            out[c] = fopen(path.c_str(), "w");
+            if (!out[c]) {
+                fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str());
+                for (int d = 0; d < c; ++d) fclose(out[d]);
+                hm_pileup_destroy(pe);
+                return EXIT_FAILURE;
+            }
+        }
+        const bool ok = write_domains(pe, fa, o, dom_A, dom_B, dom_S, out);
+        for (FILE* f : out) fclose(f);
+        if (!ok) return die("domains");
     }
     if (sites) {
         const int rc = write_sites(pe, fa, o, control_sid, o.threads);

@@ -28,6 +28,9 @@
 //                   the same count / scan / write over ROW indices: a thread that owns a chain head walks to the chain's tail
 //   sites_*         binomial test per locus (`pileup -B / -e`): control sums, histogram of (motif, pcov, pcov + ncov) through LDS,
 //                   the loci beyond the histogram listed, rows written by table lookup (count, loci_scan, write)
+//   domain_* / rowscan_*   methylation domains (`pileup -D`): the rows of one context compacted, a two-state Viterbi path as two scans
+//                   over a monoid (reduce per workgroup, one workgroup scans the aggregates, re-scan), segment heads compacted,
+//                   one thread per segment
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -907,6 +910,251 @@ __global__ __launch_bounds__(TPB) void asm_region_write_kernel(const hm_asm_t* _
     });
 }
 
+// ---- `pileup -D`: methylation domains by a two-state Viterbi scan (include/hifimeth_hip.h has the definition) -------------------
+// Step 1 is the skeleton over the loci with the context in the selection; the rows stay on the device.
+struct DomRow {
+    int64_t gpos;
+    int32_t pcov, ncov;
+};
+struct DomSum {  // pcov and ncov summed over rows 0 .. t
+    int64_t P, N;
+};
+struct DomRule {
+    int64_t A, B, S, max_gap;
+};
+constexpr int64_t DOM_W = int64_t(1) << 24;        // |A|, |B|, S <= this
+constexpr int32_t DOM_COV = (int32_t(1) << 20) - 1;  // a counter enters e_t clamped to this
+
+__device__ __forceinline__ bool domain_row(int32_t p, int32_t n, uint32_t key, uint32_t ctx) {
+    return site_counted(p, n) && site_motif(key) == ctx;
+}
+
+__global__ __launch_bounds__(TPB) void domain_rows_count_kernel(const int32_t* __restrict__ pcov, const int32_t* __restrict__ ncov,
+                                                                 const uint32_t* __restrict__ key, int64_t lo, int64_t hi, uint32_t ctx,
+                                                                 int32_t* __restrict__ block_counts) {
+    count_block(lo, hi, block_counts, [&](int64_t i) { return domain_row(pcov[i], ncov[i], key[i], ctx); });
+}
+
+__global__ __launch_bounds__(TPB) void domain_rows_write_kernel(const int32_t* __restrict__ pcov, const int32_t* __restrict__ ncov,
+                                                                 const uint32_t* __restrict__ key, int64_t plane_base, int64_t lo,
+                                                                 int64_t hi, uint32_t ctx, const int64_t* __restrict__ offs,
+                                                                 DomRow* __restrict__ out) {
+    compact_block(lo, hi, offs, out, [&](int64_t i, DomRow& r) {
+        const int32_t p = pcov[i], n = ncov[i];
+        if (!domain_row(p, n, key[i], ctx)) return false;
+        r.gpos = plane_base + i;
+        r.pcov = p;
+        r.ncov = n;
+        return true;
+    });
+}
+
+// Step 2, the row-scan skeleton: the inclusive scan of n elements under an associative operation, in three launches -- every
+// workgroup reduces its SCAN_ROWS elements to one aggregate (rowscan_reduce_kernel), ONE workgroup turns the aggregates into
+// their exclusive scan (rowscan_carry_kernel), every workgroup scans its elements again from its carry (rowscan_apply_kernel).
+// No workgroup waits for another inside a launch.  A scan Sc brings: T, identity(), shfl_up(v, d) (v of the lane d below),
+// op(a, b) with a the earlier operand, load(j) = element j, store(j, v) = what to keep of the inclusive scan at j.
+constexpr int SCAN_ITEMS = 4;                 // consecutive elements per thread
+constexpr int SCAN_ROWS = TPB * SCAN_ITEMS;   // elements per workgroup
+
+// v = one value per thread of a workgroup of NT threads -> the combination of the values of all lower threads (identity for thread
+// 0), and `total` = that of all NT, in every thread.  Wave64 shuffle scan, then the wavefront totals through LDS.
+template <int NT, class Sc>
+__device__ __forceinline__ typename Sc::T block_scan(const Sc& sc, typename Sc::T v, typename Sc::T& total) {
+    using T = typename Sc::T;
+    __shared__ T wtot[NT / 64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int d = 1; d < 64; d <<= 1) {
+        const T o = Sc::shfl_up(v, d);
+        if (lane >= d) v = sc.op(o, v);
+    }
+    if (lane == 63) wtot[w] = v;
+    __syncthreads();
+    T ex = Sc::shfl_up(v, 1);
+    if (lane == 0) ex = Sc::identity();
+    T pre = Sc::identity();
+    total = Sc::identity();
+    for (int j = 0; j < NT / 64; ++j) {
+        if (j == w) pre = total;
+        total = sc.op(total, wtot[j]);
+    }
+    return sc.op(pre, ex);
+}
+
+template <class Sc>
+__global__ __launch_bounds__(TPB) void rowscan_reduce_kernel(Sc sc, int64_t n, typename Sc::T* __restrict__ agg) {
+    using T = typename Sc::T;
+    const int64_t j0 = (int64_t)blockIdx.x * SCAN_ROWS + (int64_t)threadIdx.x * SCAN_ITEMS;
+    T v = Sc::identity();
+#pragma unroll
+    for (int k = 0; k < SCAN_ITEMS; ++k)
+        if (j0 + k < n) v = sc.op(v, sc.load(j0 + k));
+    T total;
+    block_scan<TPB>(sc, v, total);
+    if (threadIdx.x == 0) agg[blockIdx.x] = total;
+}
+
+// agg[0, nagg) -> their exclusive scan, in place: a thread owns a contiguous slice
+template <class Sc>
+__global__ __launch_bounds__(1024) void rowscan_carry_kernel(Sc sc, typename Sc::T* __restrict__ agg, int64_t nagg) {
+    using T = typename Sc::T;
+    const int64_t per = (nagg + 1023) / 1024;
+    const int64_t lo = (int64_t)threadIdx.x * per, hi = min(nagg, lo + per);
+    T v = Sc::identity();
+    for (int64_t i = lo; i < hi; ++i) v = sc.op(v, agg[i]);
+    T total;
+    T run = block_scan<1024>(sc, v, total);
+    for (int64_t i = lo; i < hi; ++i) {
+        const T a = agg[i];
+        agg[i] = run;
+        run = sc.op(run, a);
+    }
+}
+
+template <class Sc>
+__global__ __launch_bounds__(TPB) void rowscan_apply_kernel(Sc sc, int64_t n, const typename Sc::T* __restrict__ carry) {
+    using T = typename Sc::T;
+    const int64_t j0 = (int64_t)blockIdx.x * SCAN_ROWS + (int64_t)threadIdx.x * SCAN_ITEMS;
+    T item[SCAN_ITEMS];
+    T v = Sc::identity();
+#pragma unroll
+    for (int k = 0; k < SCAN_ITEMS; ++k) {
+        item[k] = j0 + k < n ? sc.load(j0 + k) : Sc::identity();
+        v = sc.op(v, item[k]);
+    }
+    T total;
+    const T before = block_scan<TPB>(sc, v, total);
+    T run = sc.op(carry[blockIdx.x], before);
+#pragma unroll
+    for (int k = 0; k < SCAN_ITEMS; ++k) {
+        run = sc.op(run, item[k]);
+        if (j0 + k < n) sc.store(j0 + k, run);
+    }
+}
+
+// The forward scan.  With d_t = delta_t(1) - delta_t(0) the Viterbi recurrence is d_t = clamp(d_{t-1}, -S_t, S_t) + e_t, d_{-1} = 0
+// (DESIGN.md section 10 has the derivation).  Row t is the function x -> clamp(x + c, lo, hi) with c = e_t, lo = e_t - S_t,
+// hi = e_t + S_t; such functions are closed under composition, so d_t = (f_t o ... o f_0)(0) is an inclusive scan.  Every d lies
+// within +-2^46 and so do lo and hi of anything that holds a row; the sum c is kept within +-DOM_CSAT = 2^48: beyond that the
+// function is constant on [-2^46, 2^46], which is recorded as lo == hi, and from then on c no longer matters.  P and N ride along.
+constexpr int64_t DOM_INF = int64_t(1) << 62, DOM_CSAT = int64_t(1) << 48;
+
+struct DomFwd {
+    struct T {
+        int64_t c, lo, hi, P, N;
+    };
+    const DomRow* rows;
+    int64_t n;
+    DomRule rule;
+    DomSum* sums;   // out: inclusive sums per row
+    uint8_t* code;  // out: the back-pointer function from row t + 1 to row t, or at the last row the end state
+    enum : uint8_t { TO0 = 0, TO1 = 1, KEEP = 2 };
+
+    __device__ __forceinline__ static T identity() { return T{0, -DOM_INF, DOM_INF, 0, 0}; }
+    __device__ __forceinline__ static T shfl_up(const T& v, int d) {
+        return T{__shfl_up(v.c, d), __shfl_up(v.lo, d), __shfl_up(v.hi, d), __shfl_up(v.P, d), __shfl_up(v.N, d)};
+    }
+    // S_t, t >= 1
+    __device__ __forceinline__ int64_t switch_cost(int64_t t) const {
+        return rows[t].gpos - rows[t - 1].gpos <= rule.max_gap ? rule.S : 0;
+    }
+    __device__ __forceinline__ T load(int64_t t) const {
+        const DomRow r = rows[t];
+        const int64_t e = (int64_t)min(r.pcov, DOM_COV) * rule.A + (int64_t)min(r.ncov, DOM_COV) * rule.B;
+        const int64_t s = t > 0 ? switch_cost(t) : 0;
+        return T{e, e - s, e + s, r.pcov, r.ncov};
+    }
+    __device__ __forceinline__ static T op(const T& a, const T& b) {  // b after a
+        T r;
+        r.c = a.c + b.c;
+        r.lo = min(max(a.lo + b.c, b.lo), b.hi);
+        r.hi = min(max(a.hi + b.c, b.lo), b.hi);
+        if (r.c >= DOM_CSAT) {
+            r.c = DOM_CSAT;
+            r.lo = r.hi;
+        } else if (r.c <= -DOM_CSAT) {
+            r.c = -DOM_CSAT;
+            r.hi = r.lo;
+        }
+        r.P = a.P + b.P;
+        r.N = a.N + b.N;
+        return r;
+    }
+    __device__ __forceinline__ void store(int64_t t, const T& f) const {
+        const int64_t d = min(max(f.c, f.lo), f.hi);  // f(0)
+        sums[t] = DomSum{f.P, f.N};
+        if (t + 1 == n) {
+            code[t] = d > 0 ? TO1 : TO0;
+        } else {
+            const int64_t s = switch_cost(t + 1);
+            code[t] = d > s ? TO1 : d < -s ? TO0 : KEEP;
+        }
+    }
+};
+
+// The backward scan.  The back-pointer from row t + 1 is constant 1, constant 0 or the identity, never a swap, so the state of row
+// t is the nearest code at or right of t that is no identity (the last row's code is its end state): element j of this scan is
+// row n - 1 - j, and the later operand wins unless it is the identity.
+struct DomBwd {
+    using T = int;
+    const uint8_t* code;
+    int64_t n;
+    uint8_t* state;  // out: z_t
+
+    __device__ __forceinline__ static T identity() { return DomFwd::KEEP; }
+    __device__ __forceinline__ static T shfl_up(T v, int d) { return __shfl_up(v, d); }
+    __device__ __forceinline__ T load(int64_t j) const { return code[n - 1 - j]; }
+    __device__ __forceinline__ static T op(T a, T b) { return b != DomFwd::KEEP ? b : a; }
+    __device__ __forceinline__ void store(int64_t j, T z) const { state[n - 1 - j] = (uint8_t)z; }
+};
+
+// Steps 3 and 4 run over the row indices [0, n): a head is row 0, a row that follows a break, or one whose state differs from its
+// predecessor's; the heads are compacted, and one thread per segment reads its tail off the next head.  No thread walks a segment.
+__device__ __forceinline__ bool domain_break(const DomRow* __restrict__ rows, int64_t i, int64_t max_gap) {  // between rows i - 1 and i, i >= 1
+    return rows[i].gpos - rows[i - 1].gpos > max_gap;
+}
+__device__ __forceinline__ bool domain_head(const DomRow* __restrict__ rows, const uint8_t* __restrict__ state, int64_t i, int64_t max_gap) {
+    return i == 0 || state[i] != state[i - 1] || domain_break(rows, i, max_gap);
+}
+
+__global__ __launch_bounds__(TPB) void domain_head_count_kernel(const DomRow* __restrict__ rows, const uint8_t* __restrict__ state,
+                                                                 int64_t n, int64_t max_gap, int32_t* __restrict__ block_counts) {
+    count_block(0, n, block_counts, [&](int64_t i) { return domain_head(rows, state, i, max_gap); });
+}
+
+__global__ __launch_bounds__(TPB) void domain_head_write_kernel(const DomRow* __restrict__ rows, const uint8_t* __restrict__ state,
+                                                                 int64_t n, int64_t max_gap, const int64_t* __restrict__ offs,
+                                                                 int64_t* __restrict__ heads) {
+    compact_block(0, n, offs, heads, [&](int64_t i, int64_t& h) {
+        h = i;
+        return domain_head(rows, state, i, max_gap);
+    });
+}
+
+__global__ __launch_bounds__(TPB) void domain_build_kernel(const DomRow* __restrict__ rows, const DomSum* __restrict__ sums,
+                                                            const uint8_t* __restrict__ state, const int64_t* __restrict__ heads,
+                                                            int64_t n_seg, int64_t n, DomRule rule, uint32_t ctx,
+                                                            hm_domain_t* __restrict__ out) {
+    const int64_t s = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (s >= n_seg) return;
+    const int64_t h = heads[s], next = s + 1 < n_seg ? heads[s + 1] : n;
+    const int64_t P = sums[next - 1].P - (h ? sums[h - 1].P : 0), N = sums[next - 1].N - (h ? sums[h - 1].N : 0);
+    hm_domain_t g;
+    g.start = rows[h].gpos;
+    g.end = rows[next - 1].gpos + 1;
+    g.pcov = P;
+    g.ncov = N;
+    g.n_loci = (int32_t)(next - h);
+    g.state = state[h];
+    g.motif = ctx;
+    g.flags = (h == 0 || domain_break(rows, h, rule.max_gap) ? HM_DOMAIN_AFTER_BREAK : 0u) |
+              (next == n || domain_break(rows, next, rule.max_gap) ? HM_DOMAIN_BEFORE_BREAK : 0u);
+    // each operation rounded once: bit-equal to the host's 100.0 * P / (P + N) and (P * A + N * B) / 65536.0; P + N > 0 in every row
+    g.level = __ddiv_rn(__dmul_rn(100.0, (double)P), (double)(P + N));
+    g.score = __ddiv_rn(__dadd_rn(__dmul_rn((double)P, (double)rule.A), __dmul_rn((double)N, (double)rule.B)), 65536.0);
+    out[s] = g;
+}
+
 }  // namespace
 
 // ================================================ host ==========================================================
@@ -951,6 +1199,9 @@ struct hm_pileup {
     // `pileup -H -A -Q`, allocated by the first call that needs them: HM_ASM_BINS bins (104 MB), hm_asm_t rows (the big loci, the
     // bins' pseudo-rows, the rows hm_pileup_fetch_asm_q adds q to), and the caller's table, big list and its q for that lookup
     DevBuf d_abins{EXACT}, d_arows{HALF}, d_atab{HALF}, d_abig{HALF}, d_abigq{HALF};
+    // `pileup -D`, allocated by the first hm_pileup_fetch_domains: per row of the context DomRow, DomSum, code and state (34 B), the
+    // workgroup aggregates of the scan that runs, and the segment heads
+    DevBuf d_drows{HALF}, d_dsums{HALF}, d_dcode{HALF}, d_dstate{HALF}, d_dagg{HALF}, d_dheads{HALF};
     int64_t n_recs = 0;
     bool bins_ready = false;
 
@@ -1794,6 +2045,96 @@ int64_t hm_pileup_fetch_asm_regions(hm_pileup_t* p, const void* pcov1, const voi
         [&](dim3 grid, const int64_t* offs, hm_asm_region_t* dst, int64_t) {
             hipLaunchKernelGGL(asm_region_write_kernel, grid, dim3(TPB), 0, st, rows, R, rule, (uint32_t)ctx, offs, dst);
         });
+}
+
+// ---- `pileup -D` ----------------------------------------------------------------------------------------------------------------
+}  // extern "C"
+
+namespace {
+
+// the three launches of the row-scan skeleton over n >= 1 elements; d_dagg holds the aggregates
+template <class Sc>
+void row_scan(hm_pileup* p, const Sc& sc, int64_t n) {
+    using T = typename Sc::T;
+    const int64_t nagg = (n + SCAN_ROWS - 1) / SCAN_ROWS;
+    p->d_dagg.reserve(sizeof(T) * (size_t)nagg);
+    T* agg = p->d_dagg.as<T>();
+    hipLaunchKernelGGL(rowscan_reduce_kernel<Sc>, dim3((unsigned)nagg), dim3(TPB), 0, p->stream, sc, n, agg);
+    hipLaunchKernelGGL(rowscan_carry_kernel<Sc>, dim3(1), dim3(1024), 0, p->stream, sc, agg, nagg);
+    hipLaunchKernelGGL(rowscan_apply_kernel<Sc>, dim3((unsigned)nagg), dim3(TPB), 0, p->stream, sc, n, agg);
+    HIP_TRY(hipGetLastError());
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t hm_pileup_fetch_domains(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t plane_base, int64_t lo,
+                                int64_t hi, int32_t ctx, int64_t A, int64_t B, int64_t S, int64_t max_gap, int64_t* n_ctx_rows,
+                                hm_domain_t* out, int64_t cap) {
+    if (!p) return HM_EINVAL;
+    if (lo < 0 || hi < lo) return pfail(p, HM_EINVAL, "hm_pileup_fetch_domains: bad range");
+    if (ctx < 0 || ctx > 2) return pfail(p, HM_EINVAL, "hm_pileup_fetch_domains: ctx must be 0, 1 or 2");
+    if (A < 1 || A > DOM_W || B > -1 || B < -DOM_W || S < 0 || S > DOM_W)
+        return pfail(p, HM_EINVAL, "hm_pileup_fetch_domains: A must be in (0, 2^24], B in [-2^24, 0), S in [0, 2^24]");
+    if (max_gap < 1) return pfail(p, HM_EINVAL, "hm_pileup_fetch_domains: max_gap must be >= 1");
+    RangePlanes s;
+    if (!range_planes(p, pcov, ncov, key, plane_base, s)) return HM_ESTATE;
+    if ((!pcov || !ncov || !key) && !p->seq_off.empty() && hi > p->seq_off.back())  // an own plane ends with the reference
+        return pfail(p, HM_EINVAL, "hm_pileup_fetch_domains: range past the reference");
+    if (n_ctx_rows) *n_ctx_rows = 0;
+    if (hi == lo) return 0;
+    const int64_t nblk = range_blocks(lo, hi);
+    if (nblk >= (int64_t(1) << 31)) return pfail(p, HM_EINVAL, "range too large: fetch per sequence");
+    hipStream_t st = p->stream;
+    const DomRule rule{A, B, S, max_gap};
+    const int64_t R = guarded(p, [&]() -> int64_t {  // the context's rows with their sums and states stay on the device
+        const dim3 grid((unsigned)nblk);
+        p->d_blk.reserve(4 * (size_t)nblk);
+        p->d_offs.reserve(8 * ((size_t)nblk + 1));
+        hipLaunchKernelGGL(domain_rows_count_kernel, grid, dim3(TPB), 0, st, s.pc, s.nc, s.ky, lo, hi, (uint32_t)ctx, p->d_blk.as<int32_t>());
+        const int64_t total = scan_blocks(p, nblk);
+        if (!total) return 0;
+        if ((total + SCAN_ROWS - 1) / SCAN_ROWS >= (int64_t(1) << 31)) return pfail(p, HM_EINVAL, "range too large: fetch per sequence");
+        p->d_drows.reserve(sizeof(DomRow) * (size_t)total);
+        p->d_dsums.reserve(sizeof(DomSum) * (size_t)total);
+        p->d_dcode.reserve((size_t)total);
+        p->d_dstate.reserve((size_t)total);
+        hipLaunchKernelGGL(domain_rows_write_kernel, grid, dim3(TPB), 0, st, s.pc, s.nc, s.ky, plane_base, lo, hi, (uint32_t)ctx,
+                           p->d_offs.as<int64_t>(), p->d_drows.as<DomRow>());
+        row_scan(p, DomFwd{p->d_drows.as<DomRow>(), total, rule, p->d_dsums.as<DomSum>(), p->d_dcode.as<uint8_t>()}, total);
+        row_scan(p, DomBwd{p->d_dcode.as<uint8_t>(), total, p->d_dstate.as<uint8_t>()}, total);
+        return total;
+    });
+    if (R <= 0) return R;
+    if (n_ctx_rows) *n_ctx_rows = R;
+    const DomRow* rows = p->d_drows.as<DomRow>();
+    const uint8_t* state = p->d_dstate.as<uint8_t>();
+    return compact_rows(
+        p, 0, R, out, cap,
+        [&](dim3 grid, int32_t* counts) { hipLaunchKernelGGL(domain_head_count_kernel, grid, dim3(TPB), 0, st, rows, state, R, max_gap, counts); },
+        [] {},
+        [&](dim3 grid, const int64_t* offs, hm_domain_t* dst, int64_t n_seg) {
+            p->d_dheads.reserve(8 * (size_t)n_seg);
+            int64_t* heads = p->d_dheads.as<int64_t>();
+            hipLaunchKernelGGL(domain_head_write_kernel, grid, dim3(TPB), 0, st, rows, state, R, max_gap, offs, heads);
+            hipLaunchKernelGGL(domain_build_kernel, dim3((unsigned)((n_seg + TPB - 1) / TPB)), dim3(TPB), 0, st, rows,
+                               p->d_dsums.as<DomSum>(), state, heads, n_seg, R, rule, (uint32_t)ctx, dst);
+        });
+}
+
+int hm_domain_scores(double level_lo, double level_hi, double penalty, int64_t* A, int64_t* B, int64_t* S) {
+    if (!A || !B || !S) return HM_EINVAL;
+    if (!(level_lo > 0.0 && level_lo < level_hi && level_hi < 1.0) || !(penalty >= 0.0)) return HM_EINVAL;
+    const double a = 65536.0 * std::log(level_hi / level_lo), b = 65536.0 * std::log((1.0 - level_hi) / (1.0 - level_lo)),
+                 s = 65536.0 * penalty;
+    if (!(a <= (double)DOM_W && b >= -(double)DOM_W && s <= (double)DOM_W)) return HM_EINVAL;  // also what llround could not hold
+    const int64_t ia = std::llround(a), ib = std::llround(b);
+    if (ia < 1 || ib > -1) return HM_EINVAL;  // levels so close that a weight rounds to 0
+    *A = ia;
+    *B = ib;
+    *S = std::llround(s);
+    return HM_OK;
 }
 
 // ---- `pileup -B / -e` ---------------------------------------------------------------------------------------------------------

@@ -33,6 +33,11 @@ counts the loci per (motif, pcov, pcov + ncov), `sites_table(rates, bins, big)` 
 and Benjamini-Hochberg q-values for every triple, `pu.sites(table)` are the rows and `pu.sites_bed(rows)` the text of
 <prefix>.sites.<ctx>.bed; `sites_rates_tsv` is <prefix>.sites.rates.tsv.
 
+Methylation domains (`pileup -D`): `pu.domains(ctx, A=..., B=..., S=...)` segments the context's covered loci into low and high
+stretches on the device -- the one optimal path of a two-state model whose weights are integers (`domain_scores(lo, hi, penalty)`,
+host only, the C library's) -- one row per segment with the pooled counts (DOMAIN_DTYPE); `pu.domains_bed(rows)` is the text of
+<prefix>.domains.<ctx>.bed.
+
 Fused with the caller (`pileup -K`): `pu.add_called(read, calls)` takes the records `MethylationCaller` returned for an aligned read
 instead of parsed MM / ML -- the same effect as add() of that read carrying the calls as tags, without the tag text.
 
@@ -66,6 +71,11 @@ ASM_BINS = 3 * ASM_PAIRS * ASM_PAIRS                                            
 SITE_DTYPE = np.dtype([("gpos", "<i8"), ("pcov", "<i4"), ("ncov", "<i4"), ("motif", "<u4"), ("reserved", "<u4"), ("pvalue", "<f8"),
                        ("qvalue", "<f8")])                                            # hm_site_t, 40 bytes
 SITE_BINS = 3 * 256 * 256                                                             # HM_SITE_BINS
+DOMAIN_DTYPE = np.dtype([("start", "<i8"), ("end", "<i8"), ("pcov", "<i8"), ("ncov", "<i8"), ("n_loci", "<i4"), ("state", "<u4"),
+                         ("motif", "<u4"), ("flags", "<u4"), ("level", "<f8"), ("score", "<f8")])  # hm_domain_t, 64 bytes
+DOMAIN_AFTER_BREAK, DOMAIN_BEFORE_BREAK = 1, 2                                        # HM_DOMAIN_AFTER_BREAK, HM_DOMAIN_BEFORE_BREAK
+DOMAIN_LEVELS = ((0.1, 0.8), (0.05, 0.5), (0.02, 0.2))  # `pileup -D`'s default low : high level per context: conventions, not tuned on data
+DOMAIN_PENALTY, DOMAIN_MAX_GAP = 8.0, 1000               # ... its default switch penalty (nats) and largest linking distance
 CTX_NAMES = ("CpG", "CHG", "CHH")
 _CHEBI = {27551: "m", 76792: "h", 76794: "f", 76793: "c", 16964: "g", 80961: "e", 17477: "b", 28871: "a",
           44605: "o", 18107: "n"}
@@ -239,6 +249,26 @@ def stitch_asm_regions(parts, max_gap: int, min_loci: int, keep_edges: bool = Fa
     keep = [g for g in out if g["n_loci"] >= min_loci or (keep_edges and g["flags"])]
     rows = np.array(keep, ASM_REGION_DTYPE) if keep else np.zeros(0, ASM_REGION_DTYPE)
     return rows, sum(n for _, n in parts)
+
+
+def domain_scores(level_lo: float, level_hi: float, penalty: float = DOMAIN_PENALTY) -> Tuple[int, int, int]:
+    """-> (A, B, S), the integer weights of domains() in Q16 nats for a low and a high methylation level (fractions) and a switch
+    penalty in nats: A = round(65536 log(hi / lo)) per methylated read, B = round(65536 log((1 - hi) / (1 - lo))) per unmethylated
+    read, S = round(65536 penalty).  By the C library (host only: no GPU is needed)."""
+    A, B, S = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    if lib().hm_domain_scores(level_lo, level_hi, penalty, C.byref(A), C.byref(B), C.byref(S)) != 0:
+        raise HifimethError("hm_domain_scores: 0 < level_lo < level_hi < 1 and penalty >= 0 expected, with weights of at most 2^24")
+    return int(A.value), int(B.value), int(S.value)
+
+
+def domains_bed(rows: np.ndarray, names: Sequence[str], offsets) -> dict:
+    """the text of <prefix>.domains.{CpG,CHG,CHH}.bed: chrom, start, end, n_loci, L|H, level, pcov, ncov, score"""
+    sid, soff = locate(offsets, rows["start"])
+    text = {k: [] for k in CTX_NAMES}
+    for s, k, r in zip(sid, soff, rows):
+        text[CTX_NAMES[int(r["motif"])]].append("%s\t%d\t%d\t%d\t%s\t%g\t%d\t%d\t%.6g\n" % (
+            names[s], k, k + (r["end"] - r["start"]), r["n_loci"], "H" if r["state"] else "L", r["level"], r["pcov"], r["ncov"], r["score"]))
+    return {k: "".join(v) for k, v in text.items()}
 
 
 def sites_rates_tsv(sums, rates, m) -> str:
@@ -540,6 +570,26 @@ class MethylationPileup:
             text[CTX_NAMES[int(r["motif"])]].append("%s\t%d\t%d\t%g\t%d\t%d\t%.6g\t%.6g\n" % (
                 self.names[s], k, k + 1, 100.0 * p / (p + n), p, n, r["pvalue"], r["qvalue"]))
         return {k: "".join(v) for k, v in text.items()}
+
+    def domains(self, ctx: int, lo: int = 0, hi: Optional[int] = None, A: Optional[int] = None, B: Optional[int] = None,
+                S: Optional[int] = None, max_gap: int = DOMAIN_MAX_GAP, planes=None, plane_base: int = 0) -> Tuple[np.ndarray, int]:
+        """-> (rows, n_ctx_rows): the segments of context ctx (0 CpG, 1 CHG, 2 CHH) over [lo, hi), ascending (DOMAIN_DTYPE), and
+        the number of loci they partition -- those with pcov, ncov >= 0 and pcov + ncov > 0 in that context.  A locus with k
+        methylated and u unmethylated reads (each clamped to 2^20 - 1) scores k * A + u * B in the high state; a change of state
+        between loci at most max_gap apart costs S, beyond that nothing (a break); the path of the largest total is found exactly
+        (hm_pileup_fetch_domains has the tie rule) and a segment is a maximal run of one state without a break.  A, B, S default to
+        domain_scores() of DOMAIN_LEVELS[ctx] and DOMAIN_PENALTY.  planes as for loci()."""
+        hi = self.n_loci if hi is None else hi
+        if A is None or B is None or S is None:
+            A, B, S = domain_scores(*DOMAIN_LEVELS[ctx])
+        n_ctx_rows = C.c_int64(0)
+        rows = self._rows(self._L.hm_pileup_fetch_domains, DOMAIN_DTYPE, *self._plane_ptrs(planes), plane_base, lo, hi, ctx, A, B, S,
+                          max_gap, C.byref(n_ctx_rows))
+        return rows, int(n_ctx_rows.value)
+
+    def domains_bed(self, rows: np.ndarray) -> dict:
+        """domains_bed() with this reference's names"""
+        return domains_bed(rows, self.names, self.offsets)
 
 
 # ---- multi-GPU exchange (SURVEY.md section 8e): histograms all-reduced, per-locus planes reduce-scattered ------------

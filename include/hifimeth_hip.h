@@ -449,6 +449,46 @@ int64_t hm_pileup_fetch_sites(hm_pileup_t* p, const void* pcov, const void* ncov
                               const hm_locus_t* big, const double* big_p, const double* big_q, int64_t n_big,
                               hm_site_t* out, int64_t cap);
 
+/* ---- methylation domains (`pileup -D`): low and high stretches by a two-state Viterbi scan ---------------
+ * Per context c (0 CpG, 1 CHG, 2 CHH) and plane range [lo, hi).  ROWS r_0 .. r_{R-1}: the loci of the range with pcov >= 0,
+ * ncov >= 0, pcov + ncov > 0 (the loci of the binomial test above) and min(key & 3, 2) == c, ascending in gpos; any other locus
+ * is no row and neither links nor breaks anything.
+ * Two states, 0 = low and 1 = high, and integer parameters in Q16 fixed-point nats: A in (0, 2^24] the weight of a methylated
+ * read, B in [-2^24, 0) that of an unmethylated one, S in [0, 2^24] the switch penalty; max_gap >= 1.  Row t with
+ * k = min(pcov, 2^20 - 1), u = min(ncov, 2^20 - 1) scores e_t = k * A + u * B in state 1 and 0 in state 0.  A change of state
+ * between rows t-1 and t costs S_t = S when gpos_t - gpos_{t-1} <= max_gap, and S_t = 0 (a BREAK) otherwise and for t = 0.  The
+ * path z maximises sum e_t z_t - sum over t >= 1 with z_t != z_{t-1} of S_t.  Among the optimal paths it is the one of plain
+ * sequential Viterbi from delta_{-1} = (0, 0) whose back-pointers move only on a strict gain: into state 0 from 1 only if
+ * delta(1) - S_t > delta(0), into state 1 from 0 only if delta(0) - S_t > delta(1), and the end state is 1 only if
+ * delta_{R-1}(1) > delta_{R-1}(0).
+ * A SEGMENT is a maximal run of consecutive rows with equal state and no break inside; the segments partition the rows.  One
+ * hm_domain_t per segment: start = gpos of its first row, end = gpos of its last + 1; pcov / ncov the exact sums of the unclamped
+ * counters; level = 100 * P / (P + N), rounded like hm_asm_t::diff; score = ((double)P * (double)A + (double)N * (double)B) /
+ * 65536.0, four correctly rounded fp64 operations in this order without contraction (bit-equal to the host's): the pooled
+ * log-likelihood ratio high : low in nats, for ranking.  Everything is an exact integer function of the planes and
+ * (A, B, S, max_gap): nothing depends on launch geometry. */
+#define HM_DOMAIN_AFTER_BREAK 1u  /* the first row follows a break or is r_0 */
+#define HM_DOMAIN_BEFORE_BREAK 2u /* the last row precedes a break or is r_{R-1} */
+typedef struct {                  /* one segment = one row of <prefix>.domains.<ctx>.bed; 64 bytes */
+    int64_t start, end;
+    int64_t pcov, ncov;
+    int32_t n_loci;
+    uint32_t state, motif, flags; /* state 0 low / 1 high; motif = c */
+    double level, score;
+} hm_domain_t;
+/* The segments of context ctx in planes[lo, hi), ascending in start.  Planes as in hm_pileup_fetch_loci.  Returns the number of
+ * segments (may exceed cap: then nothing is written); *n_ctx_rows, if not NULL, receives R.  hi == lo returns 0.  HM_EINVAL for
+ * A, B, S or max_gap outside the ranges above, ctx outside 0..2, lo > hi, and a range over the engine's own planes that ends
+ * past the reference. */
+int64_t hm_pileup_fetch_domains(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t plane_base,
+                                int64_t lo, int64_t hi, int32_t ctx, int64_t A, int64_t B, int64_t S, int64_t max_gap,
+                                int64_t* n_ctx_rows, hm_domain_t* out, int64_t cap);
+/* Host only.  The weights for two methylation levels 0 < level_lo < level_hi < 1 (fractions) and a switch penalty in nats:
+ * A = llround(65536 * log(level_hi / level_lo)), B = llround(65536 * log((1 - level_hi) / (1 - level_lo))),
+ * S = llround(65536 * penalty) -- a read's log-likelihood ratio high : low.  HM_EINVAL unless 0 < level_lo < level_hi < 1,
+ * penalty >= 0 and the results lie in hm_pileup_fetch_domains' ranges. */
+int hm_domain_scores(double level_lo, double level_hi, double penalty, int64_t* A, int64_t* B, int64_t* S);
+
 #ifdef __cplusplus
 }
 #endif

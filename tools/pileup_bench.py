@@ -11,8 +11,9 @@ fetch then also compacts the two partitions' planes.
 `--asm-q` (with `--asm`): the q-values of `pileup -H -A -Q`: histogram + bin p-values + table (host) + rows with q (D2H included) per pass.
 `--asm-regions` (with `--asm`): the regions of `pileup -H -A -G`: per context, select + test + chain + D2H of the region rows per pass.
 `--sites`: the binomial test of `pileup -B / -e` over the counted planes: histogram + table + rows (D2H included) per pass.
+`--domains`: the segmentation of `pileup -D` over the counted planes: per context, select + two scans + heads + D2H of the segments per pass.
 
-    python tools/pileup_bench.py --genome-mb 20 --coverage 10 [--partitions [--asm [--asm-q] [--asm-regions]]] [--sites]
+    python tools/pileup_bench.py --genome-mb 20 --coverage 10 [--partitions [--asm [--asm-q] [--asm-regions]]] [--sites] [--domains]
 """
 import argparse
 import ctypes as C
@@ -96,6 +97,7 @@ def main():
     ap.add_argument("--regions-min-loci", type=int, default=3)
     ap.add_argument("--sites", action="store_true", help="time the per-locus binomial test (pileup -B / -e)")
     ap.add_argument("--sites-rate", type=float, default=0.013, help="with --sites: the false-positive rate of all three contexts")
+    ap.add_argument("--domains", action="store_true", help="time the low / high segmentation of the covered loci (pileup -D, its default weights)")
     ap.add_argument("--cpu-baseline", action="store_true",
                     help="time the reference's own projection code (oracle/_ref/ref_align -t) on a bounded sample")
     a = ap.parse_args()
@@ -260,6 +262,27 @@ def main():
         if a.check:
             out["check_sites_rows_are_the_loci"] = bool(len(rows) == len(loci) and (rows["gpos"] == loci["gpos"]).all()
                                                         and int(bins.sum()) + len(big) == len(loci))
+    if a.domains:                                  # the three contexts over the whole sequence, as the CLI does
+        def domains_pass():
+            return [pu.domains(c) for c in range(3)]
+
+        domains_pass()                             # warm-up: the row buffers
+        t0 = time.perf_counter()
+        for _ in range(a.repeat):
+            found = domains_pass()
+        t_dom = (time.perf_counter() - t0) / a.repeat
+        ctx_rows = sum(n for _r, n in found)
+        t_pass = t_project / a.repeat + t_count / a.repeat + t_loci
+        out.update(domains_ctx_rows=int(ctx_rows), domains=[int(len(r)) for r, _n in found],
+                   domains_high=[int((r["state"] == 1).sum()) for r, _n in found],
+                   domains_longest=int(max((int(r["n_loci"].max()) for r, _n in found if len(r)), default=0)),
+                   domains_s_per_pass=round(t_dom, 4), domains_rows_per_s=round(ctx_rows / t_dom) if t_dom else 0,
+                   domains_share_of_pass=round(t_dom / (t_pass + t_dom), 4))
+        if a.check:                                # the segments partition the covered loci and their counts
+            out["check_domains_partition_the_loci"] = bool(
+                ctx_rows == len(loci) == sum(int(r["n_loci"].sum()) for r, _n in found)
+                and sum(int(r["pcov"].sum()) for r, _n in found) == int(loci["pcov"].astype(np.int64).sum())
+                and sum(int(r["ncov"].sum()) for r, _n in found) == int(loci["ncov"].astype(np.int64).sum()))
     if a.check:                                    # every pass (and the warm-up) adds the same records
         total = int((loci["pcov"].astype(np.int64) + loci["ncov"]).sum())
         out["check_total_records"] = total == recs_per_pass * (a.repeat + 1)
