@@ -137,6 +137,7 @@ def lib():
         "hm_sites_table": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp]),
         "hm_pileup_fetch_sites": (i64, [vp, vp, vp, vp, i64, i64, i64, i32, vp, vp, vp, vp, vp, i64, vp, i64]),
         "hm_pileup_fetch_domains": (i64, [vp, vp, vp, vp, i64, i64, i64, i32, i64, i64, i64, i64, C.POINTER(i64), vp, i64]),
+        "hm_pileup_fetch_domains_part": (i64, [vp, vp, vp, vp, i64, i64, i64, i32, i64, i64, i64, i64, i32, vp, vp, i64]),
         "hm_domain_scores": (C.c_int, [C.c_double, C.c_double, C.c_double, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
     }
     for name, (res, args) in sig.items():

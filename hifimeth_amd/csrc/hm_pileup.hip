@@ -1050,7 +1050,7 @@ struct DomFwd {
     uint8_t* code;  // out: the back-pointer function from row t + 1 to row t, or at the last row the end state
     enum : uint8_t { TO0 = 0, TO1 = 1, KEEP = 2 };
 
-    __device__ __forceinline__ static T identity() { return T{0, -DOM_INF, DOM_INF, 0, 0}; }
+    __host__ __device__ __forceinline__ static T identity() { return T{0, -DOM_INF, DOM_INF, 0, 0}; }
     __device__ __forceinline__ static T shfl_up(const T& v, int d) {
         return T{__shfl_up(v.c, d), __shfl_up(v.lo, d), __shfl_up(v.hi, d), __shfl_up(v.P, d), __shfl_up(v.N, d)};
     }
@@ -1092,6 +1092,35 @@ struct DomFwd {
     }
 };
 
+// The forward scan of a PIECE of the rows (hm_pileup_fetch_domains_part): the rows before the piece enter through the nearest one's
+// gpos and d.  Row 0 becomes the constant function d_0 = clamp(d_prev, -S_0, S_0) + e_0, S_0 = S only if that row exists within
+// max_gap, d_prev = 0 without it -- composing a constant (lo == hi) is exact, c no longer matters -- so every d, sum and code
+// equals the whole scan's.  The last row's code is what the caller says (`last_code`), or its end state; its d goes to *d_last.
+// mask_first (pass S, reduce only): row 0 is the identity instead, the composite of rows 1 .. n - 1 needs no carry.
+struct DomFwdPart : DomFwd {
+    bool mask_first, has_prev;
+    int64_t prev_gpos, prev_d;
+    int last_code;     // TO0, TO1, KEEP, or -1: d > 0 decides
+    int64_t* d_last;   // out
+
+    __device__ __forceinline__ T load(int64_t t) const {
+        if (t > 0) return DomFwd::load(t);
+        if (mask_first) return identity();
+        const DomRow r = rows[0];
+        const int64_t e = (int64_t)min(r.pcov, DOM_COV) * rule.A + (int64_t)min(r.ncov, DOM_COV) * rule.B;
+        const int64_t s = has_prev && r.gpos - prev_gpos <= rule.max_gap ? rule.S : 0;
+        const int64_t d = min(max(has_prev ? prev_d : 0, -s), s) + e;
+        return T{d, d, d, r.pcov, r.ncov};
+    }
+    __device__ __forceinline__ void store(int64_t t, const T& f) const {
+        if (t + 1 < n) return DomFwd::store(t, f);
+        const int64_t d = min(max(f.c, f.lo), f.hi);
+        sums[t] = DomSum{f.P, f.N};
+        code[t] = last_code >= 0 ? (uint8_t)last_code : d > 0 ? TO1 : TO0;
+        *d_last = d;
+    }
+};
+
 // The backward scan.  The back-pointer from row t + 1 is constant 1, constant 0 or the identity, never a swap, so the state of row
 // t is the nearest code at or right of t that is no identity (the last row's code is its end state): element j of this scan is
 // row n - 1 - j, and the later operand wins unless it is the identity.
@@ -1101,7 +1130,7 @@ struct DomBwd {
     int64_t n;
     uint8_t* state;  // out: z_t
 
-    __device__ __forceinline__ static T identity() { return DomFwd::KEEP; }
+    __host__ __device__ __forceinline__ static T identity() { return DomFwd::KEEP; }
     __device__ __forceinline__ static T shfl_up(T v, int d) { return __shfl_up(v, d); }
     __device__ __forceinline__ T load(int64_t j) const { return code[n - 1 - j]; }
     __device__ __forceinline__ static T op(T a, T b) { return b != DomFwd::KEEP ? b : a; }
@@ -1131,12 +1160,11 @@ __global__ __launch_bounds__(TPB) void domain_head_write_kernel(const DomRow* __
     });
 }
 
-__global__ __launch_bounds__(TPB) void domain_build_kernel(const DomRow* __restrict__ rows, const DomSum* __restrict__ sums,
-                                                            const uint8_t* __restrict__ state, const int64_t* __restrict__ heads,
-                                                            int64_t n_seg, int64_t n, DomRule rule, uint32_t ctx,
-                                                            hm_domain_t* __restrict__ out) {
-    const int64_t s = (int64_t)blockIdx.x * TPB + threadIdx.x;
-    if (s >= n_seg) return;
+// the segment s of n_seg; first_break / last_break: whether a break lies before row 0 / behind row n - 1
+__device__ __forceinline__ hm_domain_t domain_segment(const DomRow* __restrict__ rows, const DomSum* __restrict__ sums,
+                                                      const uint8_t* __restrict__ state, const int64_t* __restrict__ heads, int64_t s,
+                                                      int64_t n_seg, int64_t n, const DomRule& rule, uint32_t ctx, bool first_break,
+                                                      bool last_break) {
     const int64_t h = heads[s], next = s + 1 < n_seg ? heads[s + 1] : n;
     const int64_t P = sums[next - 1].P - (h ? sums[h - 1].P : 0), N = sums[next - 1].N - (h ? sums[h - 1].N : 0);
     hm_domain_t g;
@@ -1147,12 +1175,31 @@ __global__ __launch_bounds__(TPB) void domain_build_kernel(const DomRow* __restr
     g.n_loci = (int32_t)(next - h);
     g.state = state[h];
     g.motif = ctx;
-    g.flags = (h == 0 || domain_break(rows, h, rule.max_gap) ? HM_DOMAIN_AFTER_BREAK : 0u) |
-              (next == n || domain_break(rows, next, rule.max_gap) ? HM_DOMAIN_BEFORE_BREAK : 0u);
+    g.flags = ((h == 0 ? first_break : domain_break(rows, h, rule.max_gap)) ? HM_DOMAIN_AFTER_BREAK : 0u) |
+              ((next == n ? last_break : domain_break(rows, next, rule.max_gap)) ? HM_DOMAIN_BEFORE_BREAK : 0u);
     // each operation rounded once: bit-equal to the host's 100.0 * P / (P + N) and (P * A + N * B) / 65536.0; P + N > 0 in every row
     g.level = __ddiv_rn(__dmul_rn(100.0, (double)P), (double)(P + N));
     g.score = __ddiv_rn(__dadd_rn(__dmul_rn((double)P, (double)rule.A), __dmul_rn((double)N, (double)rule.B)), 65536.0);
-    out[s] = g;
+    return g;
+}
+
+__global__ __launch_bounds__(TPB) void domain_build_kernel(const DomRow* __restrict__ rows, const DomSum* __restrict__ sums,
+                                                            const uint8_t* __restrict__ state, const int64_t* __restrict__ heads,
+                                                            int64_t n_seg, int64_t n, DomRule rule, uint32_t ctx,
+                                                            hm_domain_t* __restrict__ out) {
+    const int64_t s = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (s >= n_seg) return;
+    out[s] = domain_segment(rows, sums, state, heads, s, n_seg, n, rule, ctx, true, true);
+}
+
+// ... of a piece: its edges break only where the caller says so
+__global__ __launch_bounds__(TPB) void domain_build_part_kernel(const DomRow* __restrict__ rows, const DomSum* __restrict__ sums,
+                                                                 const uint8_t* __restrict__ state, const int64_t* __restrict__ heads,
+                                                                 int64_t n_seg, int64_t n, DomRule rule, uint32_t ctx, bool first_break,
+                                                                 bool last_break, hm_domain_t* __restrict__ out) {
+    const int64_t s = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (s >= n_seg) return;
+    out[s] = domain_segment(rows, sums, state, heads, s, n_seg, n, rule, ctx, first_break, last_break);
 }
 
 }  // namespace
@@ -1202,6 +1249,7 @@ struct hm_pileup {
     // `pileup -D`, allocated by the first hm_pileup_fetch_domains: per row of the context DomRow, DomSum, code and state (34 B), the
     // workgroup aggregates of the scan that runs, and the segment heads
     DevBuf d_drows{HALF}, d_dsums{HALF}, d_dcode{HALF}, d_dstate{HALF}, d_dagg{HALF}, d_dheads{HALF};
+    DevBuf d_dlast{EXACT};  // hm_pileup_fetch_domains_part: the d of a piece's last row, 8 B
     int64_t n_recs = 0;
     bool bins_ready = false;
 
@@ -2065,6 +2113,25 @@ void row_scan(hm_pileup* p, const Sc& sc, int64_t n) {
     HIP_TRY(hipGetLastError());
 }
 
+// the combination of all n >= 1 elements, without the re-scan: the reduce, then the carry kernel over the aggregates and one
+// identity behind them, whose exclusive scan is the total
+template <class Sc>
+typename Sc::T row_reduce(hm_pileup* p, const Sc& sc, int64_t n) {
+    using T = typename Sc::T;
+    const int64_t nagg = (n + SCAN_ROWS - 1) / SCAN_ROWS;
+    p->d_dagg.reserve(sizeof(T) * (size_t)(nagg + 1));
+    T* agg = p->d_dagg.as<T>();
+    T total = Sc::identity();
+    HIP_TRY(hipMemcpyAsync(agg + nagg, &total, sizeof(T), hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    hipLaunchKernelGGL(rowscan_reduce_kernel<Sc>, dim3((unsigned)nagg), dim3(TPB), 0, p->stream, sc, n, agg);
+    hipLaunchKernelGGL(rowscan_carry_kernel<Sc>, dim3(1), dim3(1024), 0, p->stream, sc, agg, nagg + 1);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&total, agg + nagg, sizeof(T), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    return total;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2120,6 +2187,97 @@ int64_t hm_pileup_fetch_domains(hm_pileup_t* p, const void* pcov, const void* nc
             hipLaunchKernelGGL(domain_head_write_kernel, grid, dim3(TPB), 0, st, rows, state, R, max_gap, offs, heads);
             hipLaunchKernelGGL(domain_build_kernel, dim3((unsigned)((n_seg + TPB - 1) / TPB)), dim3(TPB), 0, st, rows,
                                p->d_dsums.as<DomSum>(), state, heads, n_seg, R, rule, (uint32_t)ctx, dst);
+        });
+}
+
+int64_t hm_pileup_fetch_domains_part(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t plane_base, int64_t lo,
+                                     int64_t hi, int32_t ctx, int64_t A, int64_t B, int64_t S, int64_t max_gap, int32_t pass,
+                                     hm_domain_part_t* part, hm_domain_t* out, int64_t cap) {
+    if (!p) return HM_EINVAL;
+    const char* const fn = "hm_pileup_fetch_domains_part: ";
+    if (!part) return pfail(p, HM_EINVAL, std::string(fn) + "no part");
+    if (pass < HM_DOMAIN_PASS_SUMMARY || pass > HM_DOMAIN_PASS_SEGMENTS) return pfail(p, HM_EINVAL, std::string(fn) + "pass must be 0, 1 or 2");
+    if (lo < 0 || hi < lo) return pfail(p, HM_EINVAL, std::string(fn) + "bad range");
+    if (ctx < 0 || ctx > 2) return pfail(p, HM_EINVAL, std::string(fn) + "ctx must be 0, 1 or 2");
+    if (A < 1 || A > DOM_W || B > -1 || B < -DOM_W || S < 0 || S > DOM_W)
+        return pfail(p, HM_EINVAL, std::string(fn) + "A must be in (0, 2^24], B in [-2^24, 0), S in [0, 2^24]");
+    if (max_gap < 1) return pfail(p, HM_EINVAL, std::string(fn) + "max_gap must be >= 1");
+    RangePlanes s;
+    if (!range_planes(p, pcov, ncov, key, plane_base, s)) return HM_ESTATE;
+    if ((!pcov || !ncov || !key) && !p->seq_off.empty() && hi > p->seq_off.back())  // an own plane ends with the reference
+        return pfail(p, HM_EINVAL, std::string(fn) + "range past the reference");
+    const bool carried = pass != HM_DOMAIN_PASS_SUMMARY;
+    const bool has_prev = carried && part->has_prev, has_next = pass == HM_DOMAIN_PASS_SEGMENTS && part->has_next;
+    constexpr int64_t DOM_D = int64_t(1) << 46;  // every d lies within +-2^46
+    if (has_prev && (part->prev_d < -DOM_D || part->prev_d > DOM_D)) return pfail(p, HM_EINVAL, std::string(fn) + "prev_d outside [-2^46, 2^46]");
+    if (has_prev && (part->prev_gpos < 0 || part->prev_gpos >= plane_base + lo))
+        return pfail(p, HM_EINVAL, std::string(fn) + "prev_gpos must lie below the piece's first locus");
+    if (has_next && part->next_gpos < plane_base + hi) return pfail(p, HM_EINVAL, std::string(fn) + "next_gpos must lie behind the piece's last locus");
+    if (has_next && part->last_state != 0 && part->last_state != 1) return pfail(p, HM_EINVAL, std::string(fn) + "last_state must be 0 or 1");
+    part->n_rows = 0;
+    if (hi == lo) return 0;
+    const int64_t nblk = range_blocks(lo, hi);
+    if (nblk >= (int64_t(1) << 31)) return pfail(p, HM_EINVAL, "range too large: fetch per sequence");
+    hipStream_t st = p->stream;
+    const DomRule rule{A, B, S, max_gap};
+    DomRow ends[2];  // the piece's first and last row
+    const int64_t R = guarded(p, [&]() -> int64_t {
+        const dim3 grid((unsigned)nblk);
+        p->d_blk.reserve(4 * (size_t)nblk);
+        p->d_offs.reserve(8 * ((size_t)nblk + 1));
+        hipLaunchKernelGGL(domain_rows_count_kernel, grid, dim3(TPB), 0, st, s.pc, s.nc, s.ky, lo, hi, (uint32_t)ctx, p->d_blk.as<int32_t>());
+        const int64_t total = scan_blocks(p, nblk);
+        if (!total) return 0;
+        if ((total + SCAN_ROWS - 1) / SCAN_ROWS >= (int64_t(1) << 31) - 1) return pfail(p, HM_EINVAL, "range too large: fetch per sequence");
+        p->d_drows.reserve(sizeof(DomRow) * (size_t)total);
+        p->d_dsums.reserve(sizeof(DomSum) * (size_t)total);
+        p->d_dcode.reserve((size_t)total);
+        p->d_dstate.reserve((size_t)total);
+        p->d_dlast.reserve(8);
+        DomRow* rows = p->d_drows.as<DomRow>();
+        hipLaunchKernelGGL(domain_rows_write_kernel, grid, dim3(TPB), 0, st, s.pc, s.nc, s.ky, plane_base, lo, hi, (uint32_t)ctx,
+                           p->d_offs.as<int64_t>(), rows);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&ends[0], rows, sizeof(DomRow), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&ends[1], rows + (total - 1), sizeof(DomRow), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        DomFwdPart fwd{{rows, total, rule, p->d_dsums.as<DomSum>(), p->d_dcode.as<uint8_t>()}, !carried, has_prev,
+                       has_prev ? part->prev_gpos : 0, has_prev ? part->prev_d : 0, DomFwd::KEEP, p->d_dlast.as<int64_t>()};
+        if (pass == HM_DOMAIN_PASS_SUMMARY) {  // rows 1 .. R - 1 composed; nothing is stored
+            const DomFwd::T f = row_reduce(p, fwd, total);
+            part->c = f.c;
+            part->lo = f.lo;
+            part->hi = f.hi;
+            return total;
+        }
+        if (pass == HM_DOMAIN_PASS_SEGMENTS) fwd.last_code = has_next ? part->last_state : -1;
+        row_scan(p, fwd, total);
+        HIP_TRY(hipMemcpyAsync(&part->d_last, p->d_dlast.p, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        const DomBwd bwd{p->d_dcode.as<uint8_t>(), total, p->d_dstate.as<uint8_t>()};
+        if (pass == HM_DOMAIN_PASS_CODES) part->back = row_reduce(p, bwd, total);  // the last row's code is KEEP: the transitions inside
+        else row_scan(p, bwd, total);
+        return total;
+    });
+    if (R <= 0) return R;
+    part->n_rows = R;
+    part->first_gpos = ends[0].gpos;
+    part->last_gpos = ends[1].gpos;
+    part->e_first = (int64_t)std::min(ends[0].pcov, DOM_COV) * A + (int64_t)std::min(ends[0].ncov, DOM_COV) * B;
+    if (pass != HM_DOMAIN_PASS_SEGMENTS) return R;
+    const DomRow* rows = p->d_drows.as<DomRow>();
+    const uint8_t* state = p->d_dstate.as<uint8_t>();
+    const bool first_break = !has_prev || ends[0].gpos - part->prev_gpos > max_gap, last_break = !has_next || part->next_gpos - ends[1].gpos > max_gap;
+    return compact_rows(
+        p, 0, R, out, cap,
+        [&](dim3 grid, int32_t* counts) { hipLaunchKernelGGL(domain_head_count_kernel, grid, dim3(TPB), 0, st, rows, state, R, max_gap, counts); },
+        [] {},
+        [&](dim3 grid, const int64_t* offs, hm_domain_t* dst, int64_t n_seg) {
+            p->d_dheads.reserve(8 * (size_t)n_seg);
+            int64_t* heads = p->d_dheads.as<int64_t>();
+            hipLaunchKernelGGL(domain_head_write_kernel, grid, dim3(TPB), 0, st, rows, state, R, max_gap, offs, heads);
+            hipLaunchKernelGGL(domain_build_part_kernel, dim3((unsigned)((n_seg + TPB - 1) / TPB)), dim3(TPB), 0, st, rows,
+                               p->d_dsums.as<DomSum>(), state, heads, n_seg, R, rule, (uint32_t)ctx, first_break, last_break, dst);
         });
 }
 

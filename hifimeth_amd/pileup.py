@@ -38,6 +38,11 @@ stretches on the device -- the one optimal path of a two-state model whose weigh
 host only, the C library's) -- one row per segment with the pooled counts (DOMAIN_DTYPE); `pu.domains_bed(rows)` is the text of
 <prefix>.domains.<ctx>.bed.
 
+The same segments from pieces (`pileup_dist -D`): `pu.domains_part(ctx, lo, hi, pass_, carry)` is one stateless pass over a piece
+(summary, codes, segments), `chain_domain_parts(pieces, A, B, S, max_gap)` chains the passes of consecutive pieces through O(1) carries
+(`domain_forward_carries`, `domain_backward_carries`: host only, Python ints) and `stitch_domains(parts, A, B)` joins the segments
+that cross a cut -- byte for byte what one `pu.domains` over the whole gives.
+
 Fused with the caller (`pileup -K`): `pu.add_called(read, calls)` takes the records `MethylationCaller` returned for an aligned read
 instead of parsed MM / ML -- the same effect as add() of that read carrying the calls as tags, without the tag text.
 
@@ -74,6 +79,7 @@ SITE_BINS = 3 * 256 * 256                                                       
 DOMAIN_DTYPE = np.dtype([("start", "<i8"), ("end", "<i8"), ("pcov", "<i8"), ("ncov", "<i8"), ("n_loci", "<i4"), ("state", "<u4"),
                          ("motif", "<u4"), ("flags", "<u4"), ("level", "<f8"), ("score", "<f8")])  # hm_domain_t, 64 bytes
 DOMAIN_AFTER_BREAK, DOMAIN_BEFORE_BREAK = 1, 2                                        # HM_DOMAIN_AFTER_BREAK, HM_DOMAIN_BEFORE_BREAK
+DOMAIN_PASS_SUMMARY, DOMAIN_PASS_CODES, DOMAIN_PASS_SEGMENTS, DOMAIN_KEEP = 0, 1, 2, 2   # HM_DOMAIN_PASS_*, HM_DOMAIN_KEEP
 DOMAIN_LEVELS = ((0.1, 0.8), (0.05, 0.5), (0.02, 0.2))  # `pileup -D`'s default low : high level per context: conventions, not tuned on data
 DOMAIN_PENALTY, DOMAIN_MAX_GAP = 8.0, 1000               # ... its default switch penalty (nats) and largest linking distance
 CTX_NAMES = ("CpG", "CHG", "CHH")
@@ -259,6 +265,102 @@ def domain_scores(level_lo: float, level_hi: float, penalty: float = DOMAIN_PENA
     if lib().hm_domain_scores(level_lo, level_hi, penalty, C.byref(A), C.byref(B), C.byref(S)) != 0:
         raise HifimethError("hm_domain_scores: 0 < level_lo < level_hi < 1 and penalty >= 0 expected, with weights of at most 2^24")
     return int(A.value), int(B.value), int(S.value)
+
+
+class _DomainPart(C.Structure):                                                       # hm_domain_part_t, 104 bytes
+    _fields_ = [(n, C.c_int64) for n in ("prev_gpos", "prev_d", "next_gpos")] + \
+               [(n, C.c_int32) for n in ("has_prev", "has_next", "last_state", "back")] + \
+               [(n, C.c_int64) for n in ("n_rows", "first_gpos", "last_gpos", "e_first", "c", "lo", "hi", "d_last")]
+
+
+def domain_forward_carries(summaries, S: int, max_gap: int) -> List[dict]:
+    """summaries: what pass S gave for the consecutive pieces of one context and sequence -> per piece the carry that passes C and
+    G take: has_prev, prev_gpos, prev_d -- whether a row precedes the piece, and the nearest one's locus and d.  A piece without
+    rows hands its carry on.  A composite is only ever applied to a d within +-2^46 and two are never composed, so its constant
+    form (lo == hi) is exact here."""
+    out, has, g, d = [], False, 0, 0
+    for s in summaries:
+        out.append({"has_prev": has, "prev_gpos": g, "prev_d": d})
+        if s["n_rows"]:
+            s0 = S if has and s["first_gpos"] - g <= max_gap else 0
+            d = min(max(d if has else 0, -s0), s0) + s["e_first"]                  # row 0
+            d = min(max(d + s["c"], s["lo"]), s["hi"])                             # rows 1 .. R - 1
+            has, g = True, s["last_gpos"]
+    return out
+
+
+def domain_backward_carries(summaries, codes, S: int, max_gap: int) -> List[dict]:
+    """... and, with what pass C gave (d_last, back), per piece what pass G takes besides: has_next, next_gpos -- whether a row
+    follows the piece, and the nearest one's locus -- and last_state, the state of the piece's last row: the back-pointer across
+    the cut (1 if d_last > S_link, 0 if d_last < -S_link, else the state of the row behind it; S_link = S up to max_gap, else
+    0), or d_last > 0 where nothing follows."""
+    out, has, g, z = [None] * len(summaries), False, 0, 0
+    for i in range(len(summaries) - 1, -1, -1):
+        s, c = summaries[i], codes[i]
+        out[i] = {"has_next": has, "next_gpos": g, "last_state": z}
+        if not s["n_rows"]:
+            continue
+        link = S if has and g - s["last_gpos"] <= max_gap else 0
+        last = (1 if c["d_last"] > 0 else 0) if not has else 1 if c["d_last"] > link else 0 if c["d_last"] < -link else z
+        out[i]["last_state"] = last
+        z = last if c["back"] == DOMAIN_KEEP else c["back"]                        # the state of the piece's first row
+        has, g = True, s["first_gpos"]
+    return out
+
+
+def chain_domain_parts(pieces, A: int, B: int, S: int, max_gap: int) -> List[np.ndarray]:
+    """pieces: consecutive pieces of one context and sequence, each a callable piece(pass_, carry, A, B, S, max_gap) -> dict like
+    functools.partial(pu.domains_part, ctx, lo, hi, planes=..., plane_base=...).  -> the segments of every piece, for
+    stitch_domains: pass S on every piece, the carries from left to right, pass C, the carries from right to left, pass G.  Where
+    the pieces live in several processes, those run the same three passes with the two carry functions between their exchanges."""
+    rule = (A, B, S, max_gap)
+    summaries = [p(DOMAIN_PASS_SUMMARY, {}, *rule) for p in pieces]
+    fwd = domain_forward_carries(summaries, S, max_gap)
+    codes = [p(DOMAIN_PASS_CODES, f, *rule) if s["n_rows"] else {} for p, s, f in zip(pieces, summaries, fwd)]
+    bwd = domain_backward_carries(summaries, codes, S, max_gap)
+    return [p(DOMAIN_PASS_SEGMENTS, {**f, **b}, *rule)["segments"] if s["n_rows"] else np.zeros(0, DOMAIN_DTYPE)
+            for p, s, f, b in zip(pieces, summaries, fwd, bwd)]
+
+
+def stitch_domains(parts, A: int, B: int) -> np.ndarray:
+    """parts: the segments chain_domain_parts gave for consecutive pieces -> the segments of the whole.  A piece's first segment
+    always starts at its first row; it continues the last segment before it when the states are equal and no break lies between
+    (it lacks DOMAIN_AFTER_BREAK): pcov, ncov and n_loci add, end is the right one's, the flags are the outer ends', level and
+    score are recomputed from the sums, each operation rounded once in fp64 as the device does."""
+    out: List[np.ndarray] = []
+    for rows in parts:
+        for k, g in enumerate(np.ascontiguousarray(rows, DOMAIN_DTYPE)):
+            g = g.copy()
+            if k == 0 and out and out[-1]["state"] == g["state"] and not int(g["flags"]) & DOMAIN_AFTER_BREAK:
+                o = out[-1]
+                for c in ("pcov", "ncov", "n_loci"):
+                    o[c] += g[c]
+                o["end"] = g["end"]
+                o["flags"] = (int(o["flags"]) & DOMAIN_AFTER_BREAK) | (int(g["flags"]) & DOMAIN_BEFORE_BREAK)
+                P, N = np.float64(int(o["pcov"])), np.float64(int(o["ncov"]))
+                o["level"] = np.float64(100.0) * P / (P + N)
+                o["score"] = (P * np.float64(A) + N * np.float64(B)) / np.float64(65536.0)
+            else:
+                out.append(g)
+    return np.array(out, DOMAIN_DTYPE) if out else np.zeros(0, DOMAIN_DTYPE)
+
+
+def parse_domain_levels(text: str) -> List[Optional[Tuple[float, float]]]:
+    """the value of -u: lo:hi once for all contexts or three times (CpG,CHG,CHH), `nan` instead of a pair: that context is not
+    segmented (None); ValueError unless the whole text parses"""
+    items = text.split(",")
+    if len(items) not in (1, 3):
+        raise ValueError("one lo:hi pair or three expected")
+    out = []
+    for t in items:
+        if t == "nan":
+            out.append(None)
+            continue
+        if ":" not in t or set(t) - set("0123456789.eE+-:"):
+            raise ValueError("lo:hi or nan expected")
+        a, b = t.split(":", 1)
+        out.append((float(a), float(b)))
+    return out * 3 if len(out) == 1 else out
 
 
 def domains_bed(rows: np.ndarray, names: Sequence[str], offsets) -> dict:
@@ -586,6 +688,32 @@ class MethylationPileup:
         rows = self._rows(self._L.hm_pileup_fetch_domains, DOMAIN_DTYPE, *self._plane_ptrs(planes), plane_base, lo, hi, ctx, A, B, S,
                           max_gap, C.byref(n_ctx_rows))
         return rows, int(n_ctx_rows.value)
+
+    def domains_part(self, ctx: int, lo: int, hi: int, pass_: int, carry: Optional[dict] = None, A: Optional[int] = None,
+                     B: Optional[int] = None, S: Optional[int] = None, max_gap: int = DOMAIN_MAX_GAP, planes=None,
+                     plane_base: int = 0) -> dict:
+        """one pass of hm_pileup_fetch_domains_part over the piece [lo, hi) of context ctx -> its results as Python ints.
+        pass_ DOMAIN_PASS_SUMMARY: n_rows, first_gpos, last_gpos, e_first, c, lo, hi.  DOMAIN_PASS_CODES, carry = {has_prev,
+        prev_gpos, prev_d}: also d_last and back.  DOMAIN_PASS_SEGMENTS, carry = that and {has_next, next_gpos, last_state}: also
+        d_last and "segments" (DOMAIN_DTYPE).  A piece without rows gives n_rows = 0 and nothing else.  The carries are those of
+        domain_forward_carries / domain_backward_carries; chain_domain_parts runs all of it."""
+        if A is None or B is None or S is None:
+            A, B, S = domain_scores(*DOMAIN_LEVELS[ctx])
+        part = _DomainPart(**{k: int(v) for k, v in (carry or {}).items()})
+        args = (*self._plane_ptrs(planes), plane_base, lo, hi, ctx, A, B, S, max_gap, pass_, C.byref(part))
+        rows = np.zeros(64, DOMAIN_DTYPE)                     # most pieces fit; a pass is repeated only for one that does not
+        n = self._check(self._L.hm_pileup_fetch_domains_part(self._h, *args, rows.ctypes.data_as(C.c_void_p), len(rows)))
+        if pass_ == DOMAIN_PASS_SEGMENTS and n > len(rows):
+            rows = np.zeros(n, DOMAIN_DTYPE)
+            self._check(self._L.hm_pileup_fetch_domains_part(self._h, *args, rows.ctypes.data_as(C.c_void_p), n))
+        out = {"n_rows": int(part.n_rows)}
+        if out["n_rows"]:
+            names = ("first_gpos", "last_gpos", "e_first") + (("c", "lo", "hi") if pass_ == DOMAIN_PASS_SUMMARY else ("d_last",)) \
+                + (("back",) if pass_ == DOMAIN_PASS_CODES else ())
+            out.update((k, int(getattr(part, k))) for k in names)
+        if pass_ == DOMAIN_PASS_SEGMENTS:
+            out["segments"] = rows[:n].copy()
+        return out
 
     def domains_bed(self, rows: np.ndarray) -> dict:
         """domains_bed() with this reference's names"""

@@ -1,7 +1,7 @@
 """`hifimeth pileup` over N GPUs of one node, one process per GPU (the path's only exchange step).
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
-        -m hifimeth_amd.pileup_dist [-q mapQ] [-f identity] [-H [-A [-a min-cov] [-Q] [-G [-s max-p] [-g max-gap] [-n min-loci]]]] [-B control | -e r,r,r] reference.fa mod.bam output-prefix
+        -m hifimeth_amd.pileup_dist [-q mapQ] [-f identity] [-H [-A [-a min-cov] [-Q] [-G [-s max-p] [-g max-gap] [-n min-loci]]]] [-B control | -e r,r,r] [-D [-u lo:hi[,lo:hi,lo:hi]] [-x nats] [-j bp]] reference.fa mod.bam output-prefix
 
 Records are dealt to the ranks in slabs of `--slab` records (round-robin, like the `call` path).  Each rank projects its
 records and histograms them on its own GPU; then
@@ -25,6 +25,12 @@ chunk boundary (stitch_asm_regions) and writes <prefix>.asm.regions.<ctx>.bed.
 (all-reduce of 6 int64 -> the same rates everywhere), histograms its chunk per (motif, pcov, pcov + ncov) (all-reduce of
 196 608 int64; the few loci beyond the histogram by all_gather_object), solves the same table (hm_sites_table) and writes its
 chunk's rows by lookup; rank 0 also writes <prefix>.sites.<ctx>.bed and <prefix>.sites.rates.tsv.  No p-value crosses ranks.
+-D: methylation domains of the combined planes.  A rank's pieces are its chunk cut at the sequence starts, one per (sequence,
+context); a domain may cross any number of chunks.  Every rank runs pass S of hm_pileup_fetch_domains_part on its pieces, the
+summaries travel by all_gather_object, every rank walks the same carries from left to right (domain_forward_carries), runs pass C,
+gathers (d_last, back), walks from right to left (domain_backward_carries), runs pass G; the segments are gathered and rank 0 joins
+those that cross a chunk boundary (stitch_domains) and writes <prefix>.domains.<ctx>.bed: three small exchanges in all, and
+files byte-identical to `pileup -D`.
 """
 from __future__ import annotations
 
@@ -36,15 +42,20 @@ import numpy as np
 
 from . import dist as D
 from .bamio import is_coordinate_sorted, load_fasta, read_bam
-from .pileup import (ASM_DTYPE, CTX_NAMES, LOCUS_DTYPE, MethylationPileup, allreduce_histograms, asm_qvalues, asm_summary_tsv,
-                     locus_ranges, parse_rates, rates_from_sums, reduce_scatter_planes, reduce_scatter_sum, resolve_threshold,
-                     sites_rates_tsv, sites_table, stitch_asm_regions)
+from .caller import HifimethError
+from .pileup import (ASM_DTYPE, CTX_NAMES, DOMAIN_LEVELS, DOMAIN_MAX_GAP, DOMAIN_PASS_CODES, DOMAIN_PASS_SEGMENTS, DOMAIN_PASS_SUMMARY,
+                     DOMAIN_PENALTY, LOCUS_DTYPE, MethylationPileup, allreduce_histograms, asm_qvalues, asm_summary_tsv,
+                     domain_backward_carries, domain_forward_carries, domain_scores, locus_ranges, parse_domain_levels, parse_rates,
+                     rates_from_sums, reduce_scatter_planes, reduce_scatter_sum, resolve_threshold, sites_rates_tsv, sites_table,
+                     stitch_asm_regions, stitch_domains)
 
 
 def run(reference: str, bam: str, prefix: str, min_mapq: int = 0, min_pi: float = 0.0, slab: int = 256,
         batch: int = 256, backend: str | None = None, log=sys.stderr, haplotypes: bool = False, asm: bool = False,
         asm_min_cov: int = 5, control: str | None = None, rates=None, asm_q: bool = False,
-        asm_regions: bool = False, max_p: float = 0.01, max_gap: int = 500, min_loci: int = 3):
+        asm_regions: bool = False, max_p: float = 0.01, max_gap: int = 500, min_loci: int = 3, domain_rules=None,
+        domain_max_gap: int = DOMAIN_MAX_GAP):
+    """domain_rules (-D): per context (A, B, S) of domain_scores, or None for a context that is not segmented"""
     import torch
     rank, local_rank, world = D.env_world()
     dist = D.init_process_group(backend, force=bool(os.environ.get("HM_FORCE_COLLECTIVES")))
@@ -173,6 +184,48 @@ def run(reference: str, bam: str, prefix: str, min_mapq: int = 0, min_pi: float 
                     for sid in range(len(genome)):
                         rows, _ = stitch_asm_regions([m[sid, c] for m in every if (sid, c) in m], max_gap, min_loci)
                         f.write(pu.asm_regions_bed(rows)[CTX_NAMES[c]])
+    if domain_rules is not None:                            # per (sequence, context): this rank's piece of the combined planes
+        pieces = {}
+        for sid in range(len(genome)):
+            a, b = max(int(pu.offsets[sid]), lo), min(int(pu.offsets[sid + 1]), hi)
+            for c in range(3 if a < b else 0):
+                if domain_rules[c] is not None:
+                    pieces[sid, c] = (a - base, b - base)
+
+        def run_pass(pass_, carries=None):
+            """one pass over this rank's pieces (after pass S: over those with rows) -> every rank's results, in rank order"""
+            got = {k: pu.domains_part(k[1], a, b, pass_, carries and carries[k], *domain_rules[k[1]], domain_max_gap, planes=(pc, nc, key),
+                                      plane_base=base) if carries is None or k in carries else {"n_rows": 0}
+                   for k, (a, b) in pieces.items()}
+            every = [got]
+            if dist is not None:
+                every = [None] * world
+                dist.all_gather_object(every, got)
+            return every
+
+        def chains(every):                                   # (sequence, context) -> [(rank, result)], rank order = locus order
+            out = {}
+            for r, m in enumerate(every):
+                for k, v in m.items():
+                    out.setdefault(k, []).append((r, v))
+            return out
+
+        sums = chains(run_pass(DOMAIN_PASS_SUMMARY))
+        fwd = {k: domain_forward_carries([v for _, v in ch], domain_rules[k[1]][2], domain_max_gap) for k, ch in sums.items()}
+        mine_of = lambda k: [r for r, _ in sums[k]].index(rank)  # noqa: E731  this rank's place in the chain of pieces k
+        carry = {k: fwd[k][mine_of(k)] for k in pieces if sums[k][mine_of(k)][1]["n_rows"]}
+        codes = chains(run_pass(DOMAIN_PASS_CODES, carry))
+        bwd = {k: domain_backward_carries([v for _, v in sums[k]], [v for _, v in ch], domain_rules[k[1]][2], domain_max_gap)
+               for k, ch in codes.items()}
+        carry = {k: {**f, **bwd[k][mine_of(k)]} for k, f in carry.items()}
+        segs = chains(run_pass(DOMAIN_PASS_SEGMENTS, carry))
+        if rank == 0:
+            for c in range(3):
+                with open(f"{prefix}.domains.{CTX_NAMES[c]}.bed", "w") as f:
+                    for sid in range(len(genome)):
+                        if (sid, c) in segs:
+                            rows = stitch_domains([v["segments"] for _, v in segs[sid, c] if v["n_rows"]], *domain_rules[c][:2])
+                            f.write(pu.domains_bed(rows)[CTX_NAMES[c]])
     if control is not None or rates is not None:
         mine, n_mine = (pc, nc, key), hi - lo               # this rank's chunk: element 0 is locus `base`
         sums = np.zeros(6, np.uint64)
@@ -237,6 +290,13 @@ def main(argv=None):
                          "-> <prefix>.sites.<ctx>.bed, <prefix>.sites.rates.tsv")
     ap.add_argument("-e", dest="rates", default=None, metavar="R,R,R",
                     help="instead of -B: the three rates (CpG,CHG,CHH), each a decimal in [0, 1] or nan (context not tested)")
+    ap.add_argument("-D", dest="domains", action="store_true",
+                    help="cut the covered loci of each context into low (L) and high (H) methylated stretches -> <prefix>.domains.<ctx>.bed")
+    ap.add_argument("-u", dest="domain_levels", default=None, metavar="LO:HI[,LO:HI,LO:HI]",
+                    help="with -D: the low and the high methylation level, 0 < lo < hi < 1, once or per context (CpG,CHG,CHH); nan instead "
+                         "of a pair: that context is not segmented (default 0.1:0.8,0.05:0.5,0.02:0.2)")
+    ap.add_argument("-x", dest="domain_penalty", type=float, default=None, help="with -D: penalty of a change of state in nats, in [0, 256] (default 8)")
+    ap.add_argument("-j", dest="domain_max_gap", type=int, default=None, help="with -D: largest distance between two loci that still links them, >= 1 (default 1000)")
     ap.add_argument("reference")
     ap.add_argument("mod_bam")
     ap.add_argument("output_prefix")
@@ -265,10 +325,25 @@ def main(argv=None):
             rates = parse_rates(a.rates)
         except ValueError as e:
             ap.error(f"-e: {e}")
+    if not a.domains and not (a.domain_levels is None and a.domain_penalty is None and a.domain_max_gap is None):
+        ap.error("-u, -x and -j need -D")
+    domain_rules = None
+    if a.domains:
+        bad = "-u takes lo:hi with 0 < lo < hi < 1 (levels a 2^24-th of a nat apart at least) or nan, once or per context; " \
+              "-x must be in [0, 256], -j an integer >= 1"
+        penalty = DOMAIN_PENALTY if a.domain_penalty is None else a.domain_penalty
+        if not 0.0 <= penalty <= 256.0 or (a.domain_max_gap is not None and a.domain_max_gap < 1):
+            ap.error(bad)
+        try:
+            levels = list(DOMAIN_LEVELS) if a.domain_levels is None else parse_domain_levels(a.domain_levels)
+            domain_rules = [None if lv is None else domain_scores(*lv, penalty) for lv in levels]
+        except (ValueError, HifimethError):
+            ap.error(bad)
     return run(a.reference, a.mod_bam, a.output_prefix, a.q, a.f, slab=a.slab, backend=a.backend, haplotypes=a.haplotypes,
                asm=a.asm, asm_min_cov=5 if a.asm_min_cov is None else a.asm_min_cov, control=a.control, rates=rates,
                asm_q=a.asm_q, asm_regions=a.asm_regions, max_p=0.01 if a.max_p is None else a.max_p,
-               max_gap=500 if a.max_gap is None else a.max_gap, min_loci=3 if a.min_loci is None else a.min_loci)
+               max_gap=500 if a.max_gap is None else a.max_gap, min_loci=3 if a.min_loci is None else a.min_loci,
+               domain_rules=domain_rules, domain_max_gap=DOMAIN_MAX_GAP if a.domain_max_gap is None else a.domain_max_gap)
 
 
 if __name__ == "__main__":

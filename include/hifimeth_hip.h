@@ -483,6 +483,45 @@ typedef struct {                  /* one segment = one row of <prefix>.domains.<
 int64_t hm_pileup_fetch_domains(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t plane_base,
                                 int64_t lo, int64_t hi, int32_t ctx, int64_t A, int64_t B, int64_t S, int64_t max_gap,
                                 int64_t* n_ctx_rows, hm_domain_t* out, int64_t cap);
+/* The same segments from PIECES (`pileup_dist -D`).  Cut [lo, hi) into consecutive pieces in any way -- empty
+ * ones, pieces without a row of the context, pieces of separate planes with their own plane_base: the segments of the pieces,
+ * chained as below and joined where a segment crosses a cut, are those of one hm_pileup_fetch_domains over [lo, hi), byte for byte.
+ * Every pass is stateless (it compacts the piece's rows and scans them again) and takes and gives O(1) bytes in hm_domain_part_t:
+ *   pass S (HM_DOMAIN_PASS_SUMMARY), no input: n_rows = R, first_gpos, last_gpos, e_first = e of row 0, and (c, lo, hi), the
+ *     function x -> clamp(x + c, lo, hi) that takes d of row 0 to d of row R - 1 (the identity c = 0, lo = -2^62, hi = 2^62 for
+ *     R = 1).  Once |c| >= 2^48 the function is constant on [-2^46, 2^46] and given as lo == hi; apply it to values within
+ *     +-2^46 only, as min(max(x + c, lo), hi), and never compose two of them.
+ *   pass C (HM_DOMAIN_PASS_CODES), input has_prev, prev_gpos, prev_d -- whether a row of the context precedes the piece, and the
+ *     nearest one's locus and d: d_last = d of row R - 1, and back = the state of row 0 as a function of the state of row R - 1:
+ *     0, 1 or HM_DOMAIN_KEEP (the same state).  d of row 0 is clamp(prev_d, -S_0, S_0) + e_first with S_0 = S if has_prev and
+ *     first_gpos - prev_gpos <= max_gap, else clamp(0, 0, 0) + e_first.
+ *   pass G (HM_DOMAIN_PASS_SEGMENTS), input as pass C and has_next, next_gpos, last_state -- whether a row follows the piece, the
+ *     nearest one's locus, and the state of row R - 1 (0 or 1; without has_next it is d_last > 0): the segments in out[cap] as
+ *     hm_pileup_fetch_domains writes them, except that row 0 starts a segment of its own whatever precedes it (joining is the
+ *     caller's), and HM_DOMAIN_AFTER_BREAK / HM_DOMAIN_BEFORE_BREAK at the piece's edges say whether prev / next is missing or
+ *     more than max_gap away.  Also d_last.
+ * The caller chains: d from left to right through e_first and (c, lo, hi); then from right to left the state of a piece's last
+ * row -- 1 if d_last > S_link, 0 if d_last < -S_link, else the next piece's first state, S_link = S or 0 by the gap between the
+ * two rows -- and of its first row (back applied to it).  Passes S and C return R, pass G the number of segments (may exceed cap:
+ * then none is written); all three fill n_rows, first_gpos, last_gpos, e_first when R > 0 and only n_rows = 0 otherwise.
+ * Errors as hm_pileup_fetch_domains, and HM_EINVAL for a pass outside 0..2, part NULL, has_prev with prev_d outside
+ * [-2^46, 2^46] or prev_gpos negative or not below plane_base + lo, has_next with next_gpos below plane_base + hi or last_state
+ * not 0 or 1. */
+#define HM_DOMAIN_PASS_SUMMARY 0
+#define HM_DOMAIN_PASS_CODES 1
+#define HM_DOMAIN_PASS_SEGMENTS 2
+#define HM_DOMAIN_KEEP 2
+typedef struct {                             /* 104 bytes */
+    int64_t prev_gpos, prev_d, next_gpos;    /* in */
+    int32_t has_prev, has_next, last_state;  /* in */
+    int32_t back;                            /* out, pass C */
+    int64_t n_rows, first_gpos, last_gpos, e_first; /* out */
+    int64_t c, lo, hi;                       /* out, pass S */
+    int64_t d_last;                          /* out, passes C and G */
+} hm_domain_part_t;
+int64_t hm_pileup_fetch_domains_part(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t plane_base,
+                                     int64_t lo, int64_t hi, int32_t ctx, int64_t A, int64_t B, int64_t S, int64_t max_gap,
+                                     int32_t pass, hm_domain_part_t* part, hm_domain_t* out, int64_t cap);
 /* Host only.  The weights for two methylation levels 0 < level_lo < level_hi < 1 (fractions) and a switch penalty in nats:
  * A = llround(65536 * log(level_hi / level_lo)), B = llround(65536 * log((1 - level_hi) / (1 - level_lo))),
  * S = llround(65536 * penalty) -- a read's log-likelihood ratio high : low.  HM_EINVAL unless 0 < level_lo < level_hi < 1,

@@ -12,8 +12,9 @@ fetch then also compacts the two partitions' planes.
 `--asm-regions` (with `--asm`): the regions of `pileup -H -A -G`: per context, select + test + chain + D2H of the region rows per pass.
 `--sites`: the binomial test of `pileup -B / -e` over the counted planes: histogram + table + rows (D2H included) per pass.
 `--domains`: the segmentation of `pileup -D` over the counted planes: per context, select + two scans + heads + D2H of the segments per pass.
+`--parts N` (with `--domains`): the same segments chained from N equal pieces next to the single fetch (three stateless passes per piece).
 
-    python tools/pileup_bench.py --genome-mb 20 --coverage 10 [--partitions [--asm [--asm-q] [--asm-regions]]] [--sites] [--domains]
+    python tools/pileup_bench.py --genome-mb 20 --coverage 10 [--partitions [--asm [--asm-q] [--asm-regions]]] [--sites] [--domains [--parts N]]
 """
 import argparse
 import ctypes as C
@@ -98,6 +99,8 @@ def main():
     ap.add_argument("--sites", action="store_true", help="time the per-locus binomial test (pileup -B / -e)")
     ap.add_argument("--sites-rate", type=float, default=0.013, help="with --sites: the false-positive rate of all three contexts")
     ap.add_argument("--domains", action="store_true", help="time the low / high segmentation of the covered loci (pileup -D, its default weights)")
+    ap.add_argument("--parts", type=int, default=0, metavar="N",
+                    help="with --domains: also the same segments chained from N equal pieces (hm_pileup_fetch_domains_part, what pileup_dist -D runs)")
     ap.add_argument("--cpu-baseline", action="store_true",
                     help="time the reference's own projection code (oracle/_ref/ref_align -t) on a bounded sample")
     a = ap.parse_args()
@@ -278,6 +281,30 @@ def main():
                    domains_longest=int(max((int(r["n_loci"].max()) for r, _n in found if len(r)), default=0)),
                    domains_s_per_pass=round(t_dom, 4), domains_rows_per_s=round(ctx_rows / t_dom) if t_dom else 0,
                    domains_share_of_pass=round(t_dom / (t_pass + t_dom), 4))
+        if a.parts:                                # the same segments from a.parts equal pieces: three stateless passes each, chained
+            from functools import partial
+
+            from hifimeth_amd.pileup import DOMAIN_LEVELS, DOMAIN_MAX_GAP, chain_domain_parts, domain_scores, stitch_domains
+            edges = [pu.n_loci * k // a.parts for k in range(a.parts + 1)]
+
+            def chained_pass():
+                rows = []
+                for c in range(3):
+                    A, B, S = domain_scores(*DOMAIN_LEVELS[c])
+                    pieces = [partial(pu.domains_part, c, lo, hi) for lo, hi in zip(edges, edges[1:])]
+                    rows.append(stitch_domains(chain_domain_parts(pieces, A, B, S, DOMAIN_MAX_GAP), A, B))
+                return rows
+
+            chained_pass()
+            t0 = time.perf_counter()
+            for _ in range(a.repeat):
+                chained = chained_pass()
+            t_parts = (time.perf_counter() - t0) / a.repeat
+            out.update(domains_parts=a.parts, domains_parts_s_per_pass=round(t_parts, 4),
+                       domains_parts_rows_per_s=round(ctx_rows / t_parts) if t_parts else 0,
+                       domains_parts_over_single=round(t_parts / t_dom, 3) if t_dom else 0)
+            if a.check:
+                out["check_domains_parts_equal_the_single_fetch"] = bool(all(x.tobytes() == r.tobytes() for x, (r, _n) in zip(chained, found)))
         if a.check:                                # the segments partition the covered loci and their counts
             out["check_domains_partition_the_loci"] = bool(
                 ctx_rows == len(loci) == sum(int(r["n_loci"].sum()) for r, _n in found)
