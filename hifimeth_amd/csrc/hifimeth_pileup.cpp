@@ -39,6 +39,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <random>
 #include <string>
 #include <thread>
@@ -769,6 +770,29 @@ template <class Row>
 int64_t row_pos(const Row& r) { return r.gpos; }
 inline int64_t row_pos(const hm_domain_t& r) { return r.start; }
 
+// The three files <prefix>.<tag><ctx>.<suffix> of one output, closed when their owner goes.
+struct CtxFiles {
+    FILE* f[3] = {nullptr, nullptr, nullptr};
+    CtxFiles() = default;
+    CtxFiles(const CtxFiles&) = delete;
+    CtxFiles& operator=(const CtxFiles&) = delete;
+    ~CtxFiles() {
+        for (FILE* x : f)
+            if (x) fclose(x);
+    }
+    // false (message printed) if one of them cannot be opened
+    bool open(const std::string& prefix, const std::string& tag, const char* suffix) {
+        static const char* cn[3] = {"CpG", "CHG", "CHH"};
+        for (int c = 0; c < 3; ++c) {
+            const std::string path = prefix + "." + tag + cn[c] + suffix;
+            if ((f[c] = fopen(path.c_str(), "w"))) continue;
+            fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str());
+            return false;
+        }
+        return true;
+    }
+};
+
 // The rows of three per-context BED files, sequence by sequence.  fetch(lo, hi, dst, cap) is the engine's row fetch over the
 // plane range of one sequence (dst NULL: the number of rows only); format(row, k, buf) prints the columns behind the sequence
 // name of a row at offset k and returns their length; the file of a row is its motif.  Rows are formatted by `threads` workers
@@ -1120,7 +1144,6 @@ bool parse_rates(const char* text, double rates[3]) {
 // <prefix>.sites.rates.tsv.  1 done, -1 engine error (hm_pileup_last_error), 0 another error (message printed).
 int write_sites(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, int control_sid, int threads) {
     static const char* cn[3] = {"CpG", "CHG", "CHH"};
-    const auto file_error = [&](const std::string& path) { fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str()); return 0; };
     std::vector<int64_t> start(fa.names.size() + 1, 0);
     for (size_t s = 0; s < fa.names.size(); ++s) start[s + 1] = start[s] + fa.length[s];
     uint64_t sums[6] = {0, 0, 0, 0, 0, 0};
@@ -1148,15 +1171,12 @@ int write_sites(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, int co
         return 0;
     }
     int ctx_mask = 0;
-    FILE* out[3] = {nullptr, nullptr, nullptr};
-    const auto close_all = [&] { for (FILE* f : out) if (f) fclose(f); };
-    for (int c = 0; c < 3; ++c) {
+    for (int c = 0; c < 3; ++c)
         if (!std::isnan(rates[c])) ctx_mask |= 1 << c;  // an untested context keeps its file, without rows
-        const std::string path = o.prefix + ".sites." + cn[c] + ".bed";
-        if (!(out[c] = fopen(path.c_str(), "w"))) { close_all(); return file_error(path); }
-    }
+    CtxFiles out;
+    if (!out.open(o.prefix, "sites.", ".bed")) return 0;
     const bool ok = !ctx_mask || write_rows<hm_site_t>(
-        fa, out, threads,
+        fa, out.f, threads,
         [&](int64_t lo, int64_t hi, hm_site_t* dst, int64_t cap) {
             return hm_pileup_fetch_sites(pe, nullptr, nullptr, nullptr, 0, lo, hi, ctx_mask, ptab.data(), qtab.data(), big.data(), big_p.data(),
                                          big_q.data(), n_big, dst, cap);
@@ -1166,11 +1186,13 @@ int write_sites(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, int co
             return snprintf(buf, sizeof buf, "\t%lld\t%lld\t%g\t%d\t%d\t%.6g\t%.6g\n", (long long)k, (long long)k + 1, freq, r.pcov, r.ncov,
                             r.pvalue, r.qvalue);
         });
-    close_all();
     if (!ok) return -1;
     const std::string path = o.prefix + ".sites.rates.tsv";
     FILE* f = fopen(path.c_str(), "w");
-    if (!f) return file_error(path);
+    if (!f) {
+        fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str());
+        return 0;
+    }
     for (int c = 0; c < 3; ++c) {
         char rate[64] = "nan";
         if (!std::isnan(rates[c])) snprintf(rate, sizeof rate, "%.17g", rates[c]);
@@ -1327,15 +1349,15 @@ int cmd_pileup(int argc, char** argv) {
 
     hm_pileup_t* pe = nullptr;
     if (hm_pileup_create(&pe, o.device) != HM_OK) { fprintf(stderr, "ERROR: %s\n", hm_pileup_last_error(nullptr)); return EXIT_FAILURE; }
+    std::unique_ptr<hm_pileup_t, decltype(&hm_pileup_destroy)> engine(pe, hm_pileup_destroy);  // destroyed on every way out
     auto die = [&](const std::string& what) {
         fprintf(stderr, "ERROR: %s: %s\n", what.c_str(), hm_pileup_last_error(pe));
-        hm_pileup_destroy(pe);
         return EXIT_FAILURE;
     };
     hm_pileup_set_option(pe, "min_mapq", o.min_mapq);
     hm_pileup_set_option(pe, "min_pi", o.min_pi);
     if (o.haplotypes && hm_pileup_set_option(pe, "partitions", 2) != HM_OK) return die("partitions");
-    if (fa.names.empty()) { fprintf(stderr, "ERROR: no sequence in %s\n", o.ref.c_str()); hm_pileup_destroy(pe); return EXIT_FAILURE; }
+    if (fa.names.empty()) { fprintf(stderr, "ERROR: no sequence in %s\n", o.ref.c_str()); return EXIT_FAILURE; }
     if (hm_pileup_set_reference(pe, (int32_t)fa.names.size(), fa.length.data(), fa.bases.data()) != HM_OK) return die("reference");
 
     // index of a mapped record's reference sequence in the FASTA; -1 (message printed) if the record has none or the name is unknown
@@ -1351,7 +1373,7 @@ int cmd_pileup(int argc, char** argv) {
         double t[4] = {0, 0, 0, 0};
         const bool ok = fused_record_loop(o, in, pe, sid_of, n_records, t);
         t_read = t[0]; t_parse = t[1]; t_submit = t[2]; t_gpu = t[3];
-        if (!ok) { hm_pileup_destroy(pe); return EXIT_FAILURE; }
+        if (!ok) return EXIT_FAILURE;
     } else {
         // Two batches in flight: a producer thread inflates + parses batch k+1 (parse_mods over `threads` workers) while
         // this thread stages batch k and runs the GPU.
@@ -1391,10 +1413,10 @@ int cmd_pileup(int argc, char** argv) {
             Batch& b = bb[cur];
             t_read += b.t_read;
             t_parse += b.t_parse;
-            if (!b.err.empty()) { fprintf(stderr, "ERROR: Could not read BAM record: %s\n", b.err.c_str()); hm_pileup_destroy(pe); return EXIT_FAILURE; }
+            if (!b.err.empty()) { fprintf(stderr, "ERROR: Could not read BAM record: %s\n", b.err.c_str()); return EXIT_FAILURE; }
             std::thread producer;
             if (b.more) producer = std::thread(produce, std::ref(bb[cur ^ 1]));
-            auto fail_out = [&]() { if (producer.joinable()) producer.join(); hm_pileup_destroy(pe); return EXIT_FAILURE; };
+            auto fail_out = [&]() { if (producer.joinable()) producer.join(); return EXIT_FAILURE; };
             auto t2 = clk::now();
             for (int k = 0; k < b.n; ++k) {
                 const BamRecord& r = b.recs[(size_t)k];
@@ -1430,7 +1452,6 @@ int cmd_pileup(int argc, char** argv) {
     static uint64_t bins[768];
     if (hm_pileup_histograms(pe, bins) != HM_OK) return die("histograms");
     uint8_t thr[3];
-    static const char* cn[3] = {"CpG", "CHG", "CHH"};
     report_thresholds(bins, thr);
     if (hm_pileup_count(pe, thr) != HM_OK) return die("count");
 
@@ -1448,76 +1469,33 @@ int cmd_pileup(int argc, char** argv) {
         }
     }
     for (size_t t = 0; t < tags.size(); ++t) {
-        FILE* out[3];
-        for (int c = 0; c < 3; ++c) {
-            const std::string path = o.prefix + "." + tags[t] + cn[c] + ".cov.bed";
-            out[c] = fopen(path.c_str(), "w");
-            if (!out[c]) {
-                fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str());
-                for (int d = 0; d < c; ++d) fclose(out[d]);
-                hm_pileup_destroy(pe);
-                return EXIT_FAILURE;
-            }
-        }
-        const bool ok = write_bed(pe, fa, planes[3 * t], planes[3 * t + 1], planes[3 * t + 2], out, o.threads);
-        for (FILE* f : out) fclose(f);
-        if (!ok) return die("loci");
+        CtxFiles out;
+        if (!out.open(o.prefix, tags[t], ".cov.bed")) return EXIT_FAILURE;
+        if (!write_bed(pe, fa, planes[3 * t], planes[3 * t + 1], planes[3 * t + 2], out.f, o.threads)) return die("loci");
     }
     if (o.asm_test) {
-        FILE* out[3];
-        for (int c = 0; c < 3; ++c) {
-            const std::string path = o.prefix + ".asm." + cn[c] + ".bed";
-            out[c] = fopen(path.c_str(), "w");
-            if (!out[c]) {
-                fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str());
-                for (int d = 0; d < c; ++d) fclose(out[d]);
-                hm_pileup_destroy(pe);
-                return EXIT_FAILURE;
-            }
-        }
-        const int rc = o.asm_q ? write_asm_q(pe, fa, o, out, o.threads) : write_asm(pe, fa, o.asm_min_cov, out, o.threads) ? 1 : -1;
-        for (FILE* f : out) fclose(f);
+        CtxFiles out;
+        if (!out.open(o.prefix, "asm.", ".bed")) return EXIT_FAILURE;
+        const int rc = o.asm_q ? write_asm_q(pe, fa, o, out.f, o.threads) : write_asm(pe, fa, o.asm_min_cov, out.f, o.threads) ? 1 : -1;
         if (rc < 0) return die("asm");
-        if (rc == 0) { hm_pileup_destroy(pe); return EXIT_FAILURE; }
+        if (rc == 0) return EXIT_FAILURE;
     }
     if (o.asm_regions) {
-        FILE* out[3];
-        for (int c = 0; c < 3; ++c) {
-            const std::string path = o.prefix + ".asm.regions." + cn[c] + ".bed";
-            out[c] = fopen(path.c_str(), "w");
-            if (!out[c]) {
-                fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str());
-                for (int d = 0; d < c; ++d) fclose(out[d]);
-                hm_pileup_destroy(pe);
-                return EXIT_FAILURE;
-            }
-        }
-        const bool ok = write_asm_regions(pe, fa, o, out);
-        for (FILE* f : out) fclose(f);
-        if (!ok) return die("asm regions");
+        CtxFiles out;
+        if (!out.open(o.prefix, "asm.regions.", ".bed")) return EXIT_FAILURE;
+        if (!write_asm_regions(pe, fa, o, out.f)) return die("asm regions");
     }
     if (o.domains) {
-        FILE* out[3];
-        for (int c = 0; c < 3; ++c) {
-            const std::string path = o.prefix + ".domains." + cn[c] + ".bed";
-            out[c] = fopen(path.c_str(), "w");
-            if (!out[c]) {
-                fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str());
-                for (int d = 0; d < c; ++d) fclose(out[d]);
-                hm_pileup_destroy(pe);
-                return EXIT_FAILURE;
-            }
-        }
-        const bool ok = write_domains(pe, fa, o, dom_A, dom_B, dom_S, out);
-        for (FILE* f : out) fclose(f);
-        if (!ok) return die("domains");
+        CtxFiles out;
+        if (!out.open(o.prefix, "domains.", ".bed")) return EXIT_FAILURE;
+        if (!write_domains(pe, fa, o, dom_A, dom_B, dom_S, out.f)) return die("domains");
     }
     if (sites) {
         const int rc = write_sites(pe, fa, o, control_sid, o.threads);
         if (rc < 0) return die("sites");
-        if (rc == 0) { hm_pileup_destroy(pe); return EXIT_FAILURE; }
+        if (rc == 0) return EXIT_FAILURE;
     }
-    hm_pileup_destroy(pe);
+    engine.reset();
     fprintf(stderr, o.kinetics ? "## %llu records in %.2f s: [producer thread: BAM read %.2f s, kinetics staging + queueing %.2f s] overlapped with "
                                  "[call hand-off %.2f s, waiting for calls + GPU projection %.2f s]; thresholds + count + BED %.2f s\n"
                                : "## %llu records in %.2f s: [producer thread: BAM read %.2f s, MM/ML parse %.2f s] overlapped with "

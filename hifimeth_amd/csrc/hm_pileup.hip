@@ -19,18 +19,20 @@
 //   project_kernel  thread per column      : motif tests, plane lookup, wave-aggregated append of 12-byte records
 //   count_kernel    thread per record      : atomic add into pcov / ncov, atomic max into the motif key
 //   count_hp_kernel the same + one more atomic add into the record's haplotype planes (partitions = 2 only)
-//   loci_*          covered loci of a range in ascending order (count per block, scan, write)
-//   asm_*           loci where both haplotypes reach a minimum coverage, compacted the same way (count, loci_scan, write),
-//                   then one thread per compact row: methylation difference + two-sided Fisher exact test
-//   asm_hist / asm_bins_* / asm_q_write   Benjamini-Hochberg q-values of that test (`pileup -H -A -Q`): tested loci counted per
+//   select_count / loci_scan / select_write   the rows of a SELECTION over a range in ascending order (count per block, scan,
+//                   write); every output below is a selection struct (its planes, pred, take) plus per-row kernels
+//   LociSel         covered loci
+//   AsmSel          loci where both haplotypes reach a minimum coverage; asm_test_kernel then runs one thread per compact row:
+//                   methylation difference + two-sided Fisher exact test
+//   asm_hist / BinsSel / asm_q_write   Benjamini-Hochberg q-values of that test (`pileup -H -A -Q`): tested loci counted per
 //                   (context, p1, n1, p2, n2), the non-empty bins compacted and given their p by asm_test_kernel, q looked up per row
-//   asm_ctx_* / asm_region_*   allele-specific regions (`pileup -H -A -G`): the tested rows of one context compacted and tested, then
-//                   the same count / scan / write over ROW indices: a thread that owns a chain head walks to the chain's tail
-//   sites_*         binomial test per locus (`pileup -B / -e`): control sums, histogram of (motif, pcov, pcov + ncov) through LDS,
-//                   the loci beyond the histogram listed, rows written by table lookup (count, loci_scan, write)
-//   domain_* / rowscan_*   methylation domains (`pileup -D`): the rows of one context compacted, a two-state Viterbi path as two scans
-//                   over a monoid (reduce per workgroup, one workgroup scans the aggregates, re-scan), segment heads compacted,
-//                   one thread per segment
+//   AsmSel<ASM_CTX> / RegionSel   allele-specific regions (`pileup -H -A -G`): the tested rows of one context compacted and tested,
+//                   then a selection over ROW indices: a thread that owns a chain head walks to the chain's tail
+//   sites_* / SitesSel   binomial test per locus (`pileup -B / -e`): control sums, histogram of (motif, pcov, pcov + ncov) through
+//                   LDS, the loci beyond the histogram listed (SitesBigSel), rows written by table lookup
+//   DomRowSel / rowscan_* / DomHeadSel   methylation domains (`pileup -D`): the rows of one context compacted, a two-state Viterbi
+//                   path as two scans over a monoid (reduce per workgroup, one workgroup scans the aggregates, re-scan), segment
+//                   heads compacted, one thread per segment (domain_build_part_kernel)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -346,9 +348,10 @@ __global__ __launch_bounds__(TPB) void label_kernel(const PRec* __restrict__ rec
 // ---- covered loci of a range, ascending ---------------------------------------------------------------------
 constexpr int LOCI_PER_BLOCK = 4096;  // 16 per thread
 
-// One skeleton for every "rows of the selected loci of [lo, hi), ascending" output: a count kernel (count_block with the
-// selection), loci_scan_kernel, a write kernel (compact_block with the selection and the row), one workgroup per
-// LOCI_PER_BLOCK loci in both; compact_rows() on the host drives the three.
+// One skeleton for every "rows of the selected indices of [lo, hi), ascending" output: select_count_kernel (count_block),
+// loci_scan_kernel, select_write_kernel (compact_block), one workgroup per LOCI_PER_BLOCK indices in both, over a SELECTION
+// passed by value: a struct of planes and parameters with Row, pred(i) = what the count step counts, and take(i, row) = the
+// same selection with the row built.  stage_rows() on the host drives the three.
 
 // the sum of v over the workgroup, in every thread; a barrier is due before the next call
 __device__ __forceinline__ int block_sum(int v) {
@@ -398,10 +401,15 @@ __device__ __forceinline__ void compact_block(int64_t lo, int64_t hi, const int6
     }
 }
 
-// covered loci: a counter of either sign counts
-__global__ __launch_bounds__(TPB) void loci_count_kernel(const int32_t* __restrict__ pcov, const int32_t* __restrict__ ncov,
-                                                          int64_t lo, int64_t hi, int32_t* __restrict__ block_counts) {
-    count_block(lo, hi, block_counts, [&](int64_t i) { return (pcov[i] | ncov[i]) != 0; });
+template <class Sel>
+__global__ __launch_bounds__(TPB) void select_count_kernel(Sel sel, int64_t lo, int64_t hi, int32_t* __restrict__ block_counts) {
+    count_block(lo, hi, block_counts, [&](int64_t i) { return sel.pred(i); });
+}
+
+template <class Sel>
+__global__ __launch_bounds__(TPB) void select_write_kernel(Sel sel, int64_t lo, int64_t hi, const int64_t* __restrict__ offs,
+                                                            typename Sel::Row* __restrict__ out) {
+    compact_block(lo, hi, offs, out, [&](int64_t i, typename Sel::Row& r) { return sel.take(i, r); });
 }
 
 // single-workgroup exclusive scan; total -> offs[n]
@@ -428,21 +436,28 @@ __global__ __launch_bounds__(1024) void loci_scan_kernel(const int32_t* __restri
     if (threadIdx.x == 1023) offs[n] = part[1023];
 }
 
-__global__ __launch_bounds__(TPB) void loci_write_kernel(const int32_t* __restrict__ pcov, const int32_t* __restrict__ ncov,
-                                                          const uint32_t* __restrict__ key, int64_t plane_base,
-                                                          int64_t lo, int64_t hi, const int64_t* __restrict__ offs,
-                                                          hm_locus_t* __restrict__ out) {
-    compact_block(lo, hi, offs, out, [&](int64_t i, hm_locus_t& l) {
-        const int32_t p = pcov[i], n = ncov[i];
+struct RangePlanes {  // of a call over a plane range: (pcov, ncov, key)
+    const int32_t *pc, *nc;
+    const uint32_t* ky;
+};
+
+// covered loci: a counter of either sign counts
+struct LociSel {
+    using Row = hm_locus_t;
+    RangePlanes s;
+    int64_t plane_base;
+    __device__ bool pred(int64_t i) const { return (s.pc[i] | s.nc[i]) != 0; }
+    __device__ bool take(int64_t i, Row& l) const {
+        const int32_t p = s.pc[i], n = s.nc[i];
         if ((p | n) == 0) return false;
         l.gpos = plane_base + i;
         l.pcov = p;
         l.ncov = n;
-        l.motif = key[i] & 3u;
+        l.motif = s.ky[i] & 3u;
         l.reserved = 0;
         return true;
-    });
-}
+    }
+};
 
 // ---- allele-specific methylation: loci tested between the two haplotype partitions -----------------
 // A locus is tested when each haplotype has pcov + ncov >= min_cov.  The planes may be the caller's: counters that are not
@@ -451,13 +466,6 @@ constexpr int LFACT_N = 65536;  // log n! for n < LFACT_N from the uploaded tabl
 
 __device__ __forceinline__ bool asm_tested(int32_t p1, int32_t n1, int32_t p2, int32_t n2, int32_t min_cov) {
     return (p1 | n1 | p2 | n2) >= 0 && (int64_t)p1 + n1 >= min_cov && (int64_t)p2 + n2 >= min_cov;
-}
-
-__global__ __launch_bounds__(TPB) void asm_count_kernel(const int32_t* __restrict__ pcov1, const int32_t* __restrict__ ncov1,
-                                                         const int32_t* __restrict__ pcov2, const int32_t* __restrict__ ncov2,
-                                                         int64_t lo, int64_t hi, int32_t min_cov,
-                                                         int32_t* __restrict__ block_counts) {
-    count_block(lo, hi, block_counts, [&](int64_t i) { return asm_tested(pcov1[i], ncov1[i], pcov2[i], ncov2[i], min_cov); });
 }
 
 // the row of a tested locus; diff and pvalue are filled by asm_test_kernel
@@ -471,20 +479,6 @@ __device__ __forceinline__ void asm_row(hm_asm_t& r, int64_t gpos, int32_t p1, i
     r.reserved = 0;
     r.diff = 0.0;
     r.pvalue = 0.0;
-}
-
-// compact rows in ascending locus order
-__global__ __launch_bounds__(TPB) void asm_write_kernel(const int32_t* __restrict__ pcov1, const int32_t* __restrict__ ncov1,
-                                                         const int32_t* __restrict__ pcov2, const int32_t* __restrict__ ncov2,
-                                                         const uint32_t* __restrict__ key, int64_t plane_base, int64_t lo,
-                                                         int64_t hi, int32_t min_cov, const int64_t* __restrict__ offs,
-                                                         hm_asm_t* __restrict__ out) {
-    compact_block(lo, hi, offs, out, [&](int64_t i, hm_asm_t& r) {
-        const int32_t p1 = pcov1[i], n1 = ncov1[i], p2 = pcov2[i], n2 = ncov2[i];
-        if (!asm_tested(p1, n1, p2, n2, min_cov)) return false;
-        asm_row(r, plane_base + i, p1, n1, p2, n2, key[i]);
-        return true;
-    });
 }
 
 __device__ __forceinline__ double lfact(const double* __restrict__ tab, int64_t k) {
@@ -532,7 +526,7 @@ __global__ __launch_bounds__(TPB) void asm_test_kernel(hm_asm_t* __restrict__ ro
 // ---- per-locus binomial test against a false-positive rate (`pileup -B / -e`) ----------------------
 // With the rates fixed, p and q of a locus are functions of (motif, pcov, pcov + ncov) alone, so the device only counts how many
 // loci carry each triple (sites_hist_kernel), the host solves the table (hm_sites_table) and a second pass writes the rows by
-// lookup (sites_write_kernel).  A locus takes part when both counters are counts and one is positive: the planes may be the
+// lookup (SitesSel).  A locus takes part when both counters are counts and one is positive: the planes may be the
 // caller's, and a negative counter never indexes a table.  A key whose low bits are 3 is CHH, as in the BED writers.
 constexpr int SITE_N = 256;      // loci with pcov + ncov below this are histogrammed, the others listed ("big" loci)
 constexpr int SITE_LDS_N = 64;   // ... and below this in the workgroup's LDS histogram: 3 x 64 x 64 x 4 B = 48 KB
@@ -605,42 +599,43 @@ __global__ __launch_bounds__(TPB) void sites_hist_kernel(const int32_t* __restri
 }
 
 // the big loci (n >= 256) of the range, where sites_hist_kernel counted them
-__global__ __launch_bounds__(TPB) void sites_big_write_kernel(const int32_t* __restrict__ pcov, const int32_t* __restrict__ ncov,
-                                                               const uint32_t* __restrict__ key, int64_t plane_base, int64_t lo,
-                                                               int64_t hi, const int64_t* __restrict__ offs, hm_locus_t* __restrict__ out) {
-    compact_block(lo, hi, offs, out, [&](int64_t i, hm_locus_t& l) {
-        const int32_t p = pcov[i], n = ncov[i];
+struct SitesBigSel {
+    using Row = hm_locus_t;
+    RangePlanes s;
+    int64_t plane_base;
+    __device__ bool pred(int64_t i) const { return site_counted(s.pc[i], s.nc[i]) && (int64_t)s.pc[i] + s.nc[i] >= SITE_N; }
+    __device__ bool take(int64_t i, Row& l) const {
+        const int32_t p = s.pc[i], n = s.nc[i];
         if (!site_counted(p, n) || (int64_t)p + n < SITE_N) return false;
         l.gpos = plane_base + i;
         l.pcov = p;
         l.ncov = n;
-        l.motif = site_motif(key[i]);
+        l.motif = site_motif(s.ky[i]);
         l.reserved = 0;
         return true;
-    });
-}
+    }
+};
 
 // a row of <prefix>.sites.<ctx>.bed: a counted locus whose context is tested (bit `motif` of ctx_mask)
 __device__ __forceinline__ bool site_tested(int32_t p, int32_t n, uint32_t key, uint32_t ctx_mask) {
     return site_counted(p, n) && ((ctx_mask >> site_motif(key)) & 1u);
 }
 
-__global__ __launch_bounds__(TPB) void sites_count_kernel(const int32_t* __restrict__ pcov, const int32_t* __restrict__ ncov,
-                                                           const uint32_t* __restrict__ key, int64_t lo, int64_t hi, uint32_t ctx_mask,
-                                                           int32_t* __restrict__ block_counts) {
-    count_block(lo, hi, block_counts, [&](int64_t i) { return site_tested(pcov[i], ncov[i], key[i], ctx_mask); });
-}
-
 // rows with pvalue / qvalue looked up: n < 256 in tab[(motif * 256 + n) * 256 + k] (ptab, then qtab behind it), a big locus by
 // its position in the ascending list `big` (big_p / big_q run parallel to it; NaN if the list does not hold the locus)
-__global__ __launch_bounds__(TPB) void sites_write_kernel(const int32_t* __restrict__ pcov, const int32_t* __restrict__ ncov,
-                                                           const uint32_t* __restrict__ key, int64_t plane_base, int64_t lo,
-                                                           int64_t hi, uint32_t ctx_mask, const double* __restrict__ tab,
-                                                           const hm_locus_t* __restrict__ big, const double* __restrict__ big_pq,
-                                                           int64_t n_big, const int64_t* __restrict__ offs, hm_site_t* __restrict__ out) {
-    compact_block(lo, hi, offs, out, [&](int64_t i, hm_site_t& r) {
-        const int32_t p = pcov[i], n = ncov[i];
-        const uint32_t ky = key[i];
+struct SitesSel {
+    using Row = hm_site_t;
+    RangePlanes s;
+    int64_t plane_base;
+    uint32_t ctx_mask;
+    const double* tab;
+    const hm_locus_t* big;
+    const double* big_pq;
+    int64_t n_big;
+    __device__ bool pred(int64_t i) const { return site_tested(s.pc[i], s.nc[i], s.ky[i], ctx_mask); }
+    __device__ bool take(int64_t i, Row& r) const {
+        const int32_t p = s.pc[i], n = s.nc[i];
+        const uint32_t ky = s.ky[i];
         if (!site_tested(p, n, ky, ctx_mask)) return false;
         r.gpos = plane_base + i;
         r.pcov = p;
@@ -663,15 +658,15 @@ __global__ __launch_bounds__(TPB) void sites_write_kernel(const int32_t* __restr
             r.qvalue = found ? big_pq[n_big + a] : __longlong_as_double(0x7ff8000000000000ll);
         }
         return true;
-    });
-}
+    }
+};
 
 // ---- Benjamini-Hochberg q-values of the haplotype test (`pileup -H -A -Q`) --------------------------------
 // asm_test_kernel makes pvalue a function of (p1, n1, p2, n2), so BH needs the number of tested loci per tuple and context only.
 // Tuples with both haplotype totals below ASM_T are counted in bins[HM_ASM_BINS] (asm_hist_kernel), the others ("big" loci) listed;
-// the non-empty bins are compacted (asm_bins_*), turned into pseudo-rows for asm_test_kernel (asm_bin_rows_kernel) and take its p
+// the non-empty bins are compacted (BinsSel), turned into pseudo-rows for asm_test_kernel (asm_bin_rows_kernel) and take its p
 // (asm_bin_p_kernel); the host solves the q-values (hm_asm_qvalues) and asm_q_write_kernel puts them next to the rows
-// asm_write_kernel + asm_test_kernel produced.  Only counters that pass asm_tested ever form a bin index.
+// AsmSel + asm_test_kernel produced.  Only counters that pass asm_tested ever form a bin index.
 constexpr int ASM_T = HM_ASM_T;
 constexpr uint32_t ASM_PAIRS = HM_ASM_PAIRS;
 static_assert(ASM_T * (ASM_T + 1) / 2 == HM_ASM_PAIRS && 3ll * HM_ASM_PAIRS * HM_ASM_PAIRS == HM_ASM_BINS, "the dense tuple space");
@@ -710,29 +705,39 @@ __global__ __launch_bounds__(TPB) void asm_hist_kernel(const int32_t* __restrict
     });
 }
 
-// the big loci of the range, where asm_hist_kernel counted them: rows as asm_write_kernel's, for asm_test_kernel
-__global__ __launch_bounds__(TPB) void asm_big_write_kernel(const int32_t* __restrict__ pcov1, const int32_t* __restrict__ ncov1,
-                                                             const int32_t* __restrict__ pcov2, const int32_t* __restrict__ ncov2,
-                                                             const uint32_t* __restrict__ key, int64_t plane_base, int64_t lo,
-                                                             int64_t hi, int32_t min_cov, const int64_t* __restrict__ offs,
-                                                             hm_asm_t* __restrict__ out) {
-    compact_block(lo, hi, offs, out, [&](int64_t i, hm_asm_t& r) {
-        const int32_t p1 = pcov1[i], n1 = ncov1[i], p2 = pcov2[i], n2 = ncov2[i];
-        if (!asm_tested(p1, n1, p2, n2, min_cov) || asm_dense(p1, n1, p2, n2)) return false;
-        asm_row(r, plane_base + i, p1, n1, p2, n2, key[i]);
+struct AsmPlanes {  // of a call over the haplotype planes: (pcov, ncov) of HP 1 and HP 2, key
+    const int32_t *p1, *n1, *p2, *n2;
+    const uint32_t* ky;
+};
+
+// The tested loci (ASM_ALL), those of context `ctx` (ASM_CTX: step 1 of `-G`), or the big ones where asm_hist_kernel counted them
+// (ASM_BIG), as rows for asm_test_kernel.  Only ASM_CTX reads the key to select.
+enum AsmWhich { ASM_ALL, ASM_CTX, ASM_BIG };
+template <AsmWhich W>
+struct AsmSel {
+    using Row = hm_asm_t;
+    AsmPlanes s;
+    int64_t plane_base;
+    int32_t min_cov;
+    uint32_t ctx;
+    __device__ bool selects(int64_t i, int32_t p1, int32_t n1, int32_t p2, int32_t n2) const {
+        return asm_tested(p1, n1, p2, n2, min_cov) && (W != ASM_CTX || site_motif(s.ky[i]) == ctx) && (W != ASM_BIG || !asm_dense(p1, n1, p2, n2));
+    }
+    __device__ bool pred(int64_t i) const { return selects(i, s.p1[i], s.n1[i], s.p2[i], s.n2[i]); }
+    __device__ bool take(int64_t i, Row& r) const {
+        const int32_t p1 = s.p1[i], n1 = s.n1[i], p2 = s.p2[i], n2 = s.n2[i];
+        if (!selects(i, p1, n1, p2, n2)) return false;
+        asm_row(r, plane_base + i, p1, n1, p2, n2, s.ky[i]);
         return true;
-    });
-}
+    }
+};
 
 // the non-empty bins of bins[0, n) in ascending index: the skeleton over the bin array instead of a plane range
-__global__ __launch_bounds__(TPB) void asm_bins_count_kernel(const unsigned long long* __restrict__ bins, int64_t n,
-                                                              int32_t* __restrict__ block_counts) {
-    count_block(0, n, block_counts, [&](int64_t i) { return bins[i] != 0ull; });
-}
-
-__global__ __launch_bounds__(TPB) void asm_bins_write_kernel(const unsigned long long* __restrict__ bins, int64_t n,
-                                                              const int64_t* __restrict__ offs, hm_asm_bin_t* __restrict__ out) {
-    compact_block(0, n, offs, out, [&](int64_t i, hm_asm_bin_t& r) {
+struct BinsSel {
+    using Row = hm_asm_bin_t;
+    const unsigned long long* bins;
+    __device__ bool pred(int64_t i) const { return bins[i] != 0ull; }
+    __device__ bool take(int64_t i, Row& r) const {
         const unsigned long long c = bins[i];
         if (!c) return false;
         r.bin = (uint32_t)i;
@@ -741,8 +746,8 @@ __global__ __launch_bounds__(TPB) void asm_bins_write_kernel(const unsigned long
         r.pvalue = 0.0;
         r.qvalue = __longlong_as_double(0x7ff8000000000000ll);
         return true;
-    });
-}
+    }
+};
 
 // One thread per compact bin: the hm_asm_t row of a locus carrying the bin's tuple (gpos = the bin index, motif = its context).
 __global__ __launch_bounds__(TPB) void asm_bin_rows_kernel(const hm_asm_bin_t* __restrict__ tab, int64_t n, hm_asm_t* __restrict__ rows) {
@@ -766,7 +771,7 @@ __global__ __launch_bounds__(TPB) void asm_bin_p_kernel(const hm_asm_t* __restri
     if (i < n) tab[i].pvalue = rows[i].pvalue;
 }
 
-// One thread per tested row (asm_write_kernel's, after asm_test_kernel): the row with its qvalue -- a dense row's from the entry of
+// One thread per tested row (AsmSel's, after asm_test_kernel): the row with its qvalue -- a dense row's from the entry of
 // its bin in tab[0, n_tab) (ascending in bin), a big row's from big_q at its place in big[0, n_big) (ascending in gpos); NaN when
 // the entry is not there (a table made with another min_cov, a list that misses the locus).
 __global__ __launch_bounds__(TPB) void asm_q_write_kernel(const hm_asm_t* __restrict__ rows, int64_t n_rows,
@@ -808,30 +813,9 @@ __global__ __launch_bounds__(TPB) void asm_q_write_kernel(const hm_asm_t* __rest
 }
 
 // ---- `pileup -H -A -G`: chains of tested rows that lean the same way (include/hifimeth_hip.h has the definition) ----------------
-// Step 1 is the skeleton over the loci with the context added to the selection; asm_test_kernel then fills diff and pvalue.
-__global__ __launch_bounds__(TPB) void asm_ctx_count_kernel(const int32_t* __restrict__ pcov1, const int32_t* __restrict__ ncov1,
-                                                             const int32_t* __restrict__ pcov2, const int32_t* __restrict__ ncov2,
-                                                             const uint32_t* __restrict__ key, int64_t lo, int64_t hi, int32_t min_cov,
-                                                             uint32_t ctx, int32_t* __restrict__ block_counts) {
-    count_block(lo, hi, block_counts, [&](int64_t i) {
-        return asm_tested(pcov1[i], ncov1[i], pcov2[i], ncov2[i], min_cov) && site_motif(key[i]) == ctx;
-    });
-}
-
-__global__ __launch_bounds__(TPB) void asm_ctx_write_kernel(const int32_t* __restrict__ pcov1, const int32_t* __restrict__ ncov1,
-                                                             const int32_t* __restrict__ pcov2, const int32_t* __restrict__ ncov2,
-                                                             const uint32_t* __restrict__ key, int64_t plane_base, int64_t lo,
-                                                             int64_t hi, int32_t min_cov, uint32_t ctx, const int64_t* __restrict__ offs,
-                                                             hm_asm_t* __restrict__ out) {
-    compact_block(lo, hi, offs, out, [&](int64_t i, hm_asm_t& r) {
-        const int32_t p1 = pcov1[i], n1 = ncov1[i], p2 = pcov2[i], n2 = ncov2[i];
-        if (!asm_tested(p1, n1, p2, n2, min_cov) || site_motif(key[i]) != ctx) return false;
-        asm_row(r, plane_base + i, p1, n1, p2, n2, key[i]);
-        return true;
-    });
-}
-
-// Step 2 runs over the row indices [0, n_rows) the way the kernels above run over loci: the selected index is the head of a
+// Step 1 is the skeleton over the loci with the context added to the selection (AsmSel<ASM_CTX>); asm_test_kernel then fills diff
+// and pvalue.
+// Step 2 runs over the row indices [0, n_rows) the way the selections above run over loci: the selected index is the head of a
 // returned chain, and the thread that owns it walks the rows forward to the chain's tail.  Only comparisons and integer sums: the
 // result does not depend on how the rows fall on threads and workgroups, and a chain may cross any number of them.
 struct RegionRule {
@@ -862,22 +846,21 @@ __device__ __forceinline__ bool region_returned(int64_t n_loci, uint32_t flags, 
     return n_loci >= rule.min_loci || (rule.keep_edges && flags);
 }
 
-// The walk stops after min_loci rows: a chain that long is returned whatever its flags, a shorter one has been walked to its tail.
-__global__ __launch_bounds__(TPB) void asm_region_count_kernel(const hm_asm_t* __restrict__ rows, int64_t n_rows, RegionRule rule,
-                                                                int32_t* __restrict__ block_counts) {
-    count_block(0, n_rows, block_counts, [&](int64_t i) {
+struct RegionSel {
+    using Row = hm_asm_region_t;
+    const hm_asm_t* rows;
+    int64_t n_rows;
+    RegionRule rule;
+    uint32_t ctx;
+    // The walk stops after min_loci rows: a chain that long is returned whatever its flags, a shorter one has been walked to its tail.
+    __device__ bool pred(int64_t i) const {
         int s;
         if (!region_head(rows, i, rule, s)) return false;
         int64_t j = i + 1;
         while (j - i < rule.min_loci && region_next(rows, j, n_rows, s, rule)) ++j;
         return region_returned(j - i, (i == 0 ? HM_REGION_FIRST : 0u) | (j == n_rows ? HM_REGION_LAST : 0u), rule);
-    });
-}
-
-__global__ __launch_bounds__(TPB) void asm_region_write_kernel(const hm_asm_t* __restrict__ rows, int64_t n_rows, RegionRule rule,
-                                                                uint32_t ctx, const int64_t* __restrict__ offs,
-                                                                hm_asm_region_t* __restrict__ out) {
-    compact_block(0, n_rows, offs, out, [&](int64_t i, hm_asm_region_t& g) {
+    }
+    __device__ bool take(int64_t i, Row& g) const {
         int s;
         if (!region_head(rows, i, rule, s)) return false;
         int64_t P1 = 0, N1 = 0, P2 = 0, N2 = 0;
@@ -907,8 +890,8 @@ __global__ __launch_bounds__(TPB) void asm_region_write_kernel(const hm_asm_t* _
         g.diff = __dsub_rn(__ddiv_rn(__dmul_rn(100.0, (double)P1), (double)(P1 + N1)), __ddiv_rn(__dmul_rn(100.0, (double)P2), (double)(P2 + N2)));
         g.pmin = pmin;
         return true;
-    });
-}
+    }
+};
 
 // ---- `pileup -D`: methylation domains by a two-state Viterbi scan (include/hifimeth_hip.h has the definition) -------------------
 // Step 1 is the skeleton over the loci with the context in the selection; the rows stay on the device.
@@ -925,29 +908,22 @@ struct DomRule {
 constexpr int64_t DOM_W = int64_t(1) << 24;        // |A|, |B|, S <= this
 constexpr int32_t DOM_COV = (int32_t(1) << 20) - 1;  // a counter enters e_t clamped to this
 
-__device__ __forceinline__ bool domain_row(int32_t p, int32_t n, uint32_t key, uint32_t ctx) {
-    return site_counted(p, n) && site_motif(key) == ctx;
-}
-
-__global__ __launch_bounds__(TPB) void domain_rows_count_kernel(const int32_t* __restrict__ pcov, const int32_t* __restrict__ ncov,
-                                                                 const uint32_t* __restrict__ key, int64_t lo, int64_t hi, uint32_t ctx,
-                                                                 int32_t* __restrict__ block_counts) {
-    count_block(lo, hi, block_counts, [&](int64_t i) { return domain_row(pcov[i], ncov[i], key[i], ctx); });
-}
-
-__global__ __launch_bounds__(TPB) void domain_rows_write_kernel(const int32_t* __restrict__ pcov, const int32_t* __restrict__ ncov,
-                                                                 const uint32_t* __restrict__ key, int64_t plane_base, int64_t lo,
-                                                                 int64_t hi, uint32_t ctx, const int64_t* __restrict__ offs,
-                                                                 DomRow* __restrict__ out) {
-    compact_block(lo, hi, offs, out, [&](int64_t i, DomRow& r) {
-        const int32_t p = pcov[i], n = ncov[i];
-        if (!domain_row(p, n, key[i], ctx)) return false;
+struct DomRowSel {
+    using Row = DomRow;
+    RangePlanes s;
+    int64_t plane_base;
+    uint32_t ctx;
+    __device__ static bool selects(int32_t p, int32_t n, uint32_t key, uint32_t ctx) { return site_counted(p, n) && site_motif(key) == ctx; }
+    __device__ bool pred(int64_t i) const { return selects(s.pc[i], s.nc[i], s.ky[i], ctx); }
+    __device__ bool take(int64_t i, Row& r) const {
+        const int32_t p = s.pc[i], n = s.nc[i];
+        if (!selects(p, n, s.ky[i], ctx)) return false;
         r.gpos = plane_base + i;
         r.pcov = p;
         r.ncov = n;
         return true;
-    });
-}
+    }
+};
 
 // Step 2, the row-scan skeleton: the inclusive scan of n elements under an associative operation, in three launches -- every
 // workgroup reduces its SCAN_ROWS elements to one aggregate (rowscan_reduce_kernel), ONE workgroup turns the aggregates into
@@ -1037,6 +1013,12 @@ __global__ __launch_bounds__(TPB) void rowscan_apply_kernel(Sc sc, int64_t n, co
 // hi = e_t + S_t; such functions are closed under composition, so d_t = (f_t o ... o f_0)(0) is an inclusive scan.  Every d lies
 // within +-2^46 and so do lo and hi of anything that holds a row; the sum c is kept within +-DOM_CSAT = 2^48: beyond that the
 // function is constant on [-2^46, 2^46], which is recorded as lo == hi, and from then on c no longer matters.  P and N ride along.
+// The rows may be a PIECE of a range's (hm_pileup_fetch_domains_part): the rows before the piece enter through the nearest one's
+// gpos and d.  Row 0 is loaded as the constant function d_0 = clamp(d_prev, -S_0, S_0) + e_0, S_0 = S only if that row exists within
+// max_gap, d_prev = 0 without it -- composing a constant (lo == hi) is exact, c no longer matters -- so every d, sum and code
+// equals the whole scan's; with no row before it that is d_0 = e_0, the whole range's start.  The last row's code is what the
+// caller says (`last_code`), or its end state; its d goes to *d_last.  mask_first (pass S, reduce only): row 0 is the identity
+// instead, the composite of rows 1 .. n - 1 needs no carry.
 constexpr int64_t DOM_INF = int64_t(1) << 62, DOM_CSAT = int64_t(1) << 48;
 
 struct DomFwd {
@@ -1048,6 +1030,10 @@ struct DomFwd {
     DomRule rule;
     DomSum* sums;   // out: inclusive sums per row
     uint8_t* code;  // out: the back-pointer function from row t + 1 to row t, or at the last row the end state
+    bool mask_first, has_prev;
+    int64_t prev_gpos, prev_d;
+    int last_code;     // TO0, TO1, KEEP, or -1: d > 0 decides
+    int64_t* d_last;   // out
     enum : uint8_t { TO0 = 0, TO1 = 1, KEEP = 2 };
 
     __host__ __device__ __forceinline__ static T identity() { return T{0, -DOM_INF, DOM_INF, 0, 0}; }
@@ -1059,10 +1045,16 @@ struct DomFwd {
         return rows[t].gpos - rows[t - 1].gpos <= rule.max_gap ? rule.S : 0;
     }
     __device__ __forceinline__ T load(int64_t t) const {
+        if (t == 0 && mask_first) return identity();
         const DomRow r = rows[t];
         const int64_t e = (int64_t)min(r.pcov, DOM_COV) * rule.A + (int64_t)min(r.ncov, DOM_COV) * rule.B;
-        const int64_t s = t > 0 ? switch_cost(t) : 0;
-        return T{e, e - s, e + s, r.pcov, r.ncov};
+        if (t > 0) {
+            const int64_t s = switch_cost(t);
+            return T{e, e - s, e + s, r.pcov, r.ncov};
+        }
+        const int64_t s = has_prev && r.gpos - prev_gpos <= rule.max_gap ? rule.S : 0;
+        const int64_t d = min(max(has_prev ? prev_d : 0, -s), s) + e;
+        return T{d, d, d, r.pcov, r.ncov};
     }
     __device__ __forceinline__ static T op(const T& a, const T& b) {  // b after a
         T r;
@@ -1084,40 +1076,12 @@ struct DomFwd {
         const int64_t d = min(max(f.c, f.lo), f.hi);  // f(0)
         sums[t] = DomSum{f.P, f.N};
         if (t + 1 == n) {
-            code[t] = d > 0 ? TO1 : TO0;
+            code[t] = last_code >= 0 ? (uint8_t)last_code : d > 0 ? TO1 : TO0;
+            *d_last = d;
         } else {
             const int64_t s = switch_cost(t + 1);
             code[t] = d > s ? TO1 : d < -s ? TO0 : KEEP;
         }
-    }
-};
-
-// The forward scan of a PIECE of the rows (hm_pileup_fetch_domains_part): the rows before the piece enter through the nearest one's
-// gpos and d.  Row 0 becomes the constant function d_0 = clamp(d_prev, -S_0, S_0) + e_0, S_0 = S only if that row exists within
-// max_gap, d_prev = 0 without it -- composing a constant (lo == hi) is exact, c no longer matters -- so every d, sum and code
-// equals the whole scan's.  The last row's code is what the caller says (`last_code`), or its end state; its d goes to *d_last.
-// mask_first (pass S, reduce only): row 0 is the identity instead, the composite of rows 1 .. n - 1 needs no carry.
-struct DomFwdPart : DomFwd {
-    bool mask_first, has_prev;
-    int64_t prev_gpos, prev_d;
-    int last_code;     // TO0, TO1, KEEP, or -1: d > 0 decides
-    int64_t* d_last;   // out
-
-    __device__ __forceinline__ T load(int64_t t) const {
-        if (t > 0) return DomFwd::load(t);
-        if (mask_first) return identity();
-        const DomRow r = rows[0];
-        const int64_t e = (int64_t)min(r.pcov, DOM_COV) * rule.A + (int64_t)min(r.ncov, DOM_COV) * rule.B;
-        const int64_t s = has_prev && r.gpos - prev_gpos <= rule.max_gap ? rule.S : 0;
-        const int64_t d = min(max(has_prev ? prev_d : 0, -s), s) + e;
-        return T{d, d, d, r.pcov, r.ncov};
-    }
-    __device__ __forceinline__ void store(int64_t t, const T& f) const {
-        if (t + 1 < n) return DomFwd::store(t, f);
-        const int64_t d = min(max(f.c, f.lo), f.hi);
-        sums[t] = DomSum{f.P, f.N};
-        code[t] = last_code >= 0 ? (uint8_t)last_code : d > 0 ? TO1 : TO0;
-        *d_last = d;
     }
 };
 
@@ -1146,19 +1110,17 @@ __device__ __forceinline__ bool domain_head(const DomRow* __restrict__ rows, con
     return i == 0 || state[i] != state[i - 1] || domain_break(rows, i, max_gap);
 }
 
-__global__ __launch_bounds__(TPB) void domain_head_count_kernel(const DomRow* __restrict__ rows, const uint8_t* __restrict__ state,
-                                                                 int64_t n, int64_t max_gap, int32_t* __restrict__ block_counts) {
-    count_block(0, n, block_counts, [&](int64_t i) { return domain_head(rows, state, i, max_gap); });
-}
-
-__global__ __launch_bounds__(TPB) void domain_head_write_kernel(const DomRow* __restrict__ rows, const uint8_t* __restrict__ state,
-                                                                 int64_t n, int64_t max_gap, const int64_t* __restrict__ offs,
-                                                                 int64_t* __restrict__ heads) {
-    compact_block(0, n, offs, heads, [&](int64_t i, int64_t& h) {
+struct DomHeadSel {
+    using Row = int64_t;  // the head's row index
+    const DomRow* rows;
+    const uint8_t* state;
+    int64_t max_gap;
+    __device__ bool pred(int64_t i) const { return domain_head(rows, state, i, max_gap); }
+    __device__ bool take(int64_t i, Row& h) const {
         h = i;
-        return domain_head(rows, state, i, max_gap);
-    });
-}
+        return pred(i);
+    }
+};
 
 // the segment s of n_seg; first_break / last_break: whether a break lies before row 0 / behind row n - 1
 __device__ __forceinline__ hm_domain_t domain_segment(const DomRow* __restrict__ rows, const DomSum* __restrict__ sums,
@@ -1183,16 +1145,7 @@ __device__ __forceinline__ hm_domain_t domain_segment(const DomRow* __restrict__
     return g;
 }
 
-__global__ __launch_bounds__(TPB) void domain_build_kernel(const DomRow* __restrict__ rows, const DomSum* __restrict__ sums,
-                                                            const uint8_t* __restrict__ state, const int64_t* __restrict__ heads,
-                                                            int64_t n_seg, int64_t n, DomRule rule, uint32_t ctx,
-                                                            hm_domain_t* __restrict__ out) {
-    const int64_t s = (int64_t)blockIdx.x * TPB + threadIdx.x;
-    if (s >= n_seg) return;
-    out[s] = domain_segment(rows, sums, state, heads, s, n_seg, n, rule, ctx, true, true);
-}
-
-// ... of a piece: its edges break only where the caller says so
+// one thread per segment; the edges of a piece break only where the caller says so, those of a whole range always
 __global__ __launch_bounds__(TPB) void domain_build_part_kernel(const DomRow* __restrict__ rows, const DomSum* __restrict__ sums,
                                                                  const uint8_t* __restrict__ state, const int64_t* __restrict__ heads,
                                                                  int64_t n_seg, int64_t n, DomRule rule, uint32_t ctx, bool first_break,
@@ -1288,11 +1241,6 @@ const std::vector<double>& host_lfact() {
 
 inline int grid_for(int64_t n, int cap = 1 << 20) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + TPB - 1) / TPB, cap)); }
 
-struct RangePlanes {
-    const int32_t *pc, *nc;
-    const uint32_t* ky;
-};
-
 // the (pcov, ncov, key) arguments of a call over a plane range: each the caller's plane or, where NULL, the engine's own (with
 // pcov NULL plane_base is 0); false (error recorded) if there are none
 bool range_planes(hm_pileup* p, const void* pcov, const void* ncov, const void* key, int64_t& plane_base, RangePlanes& s) {
@@ -1305,57 +1253,83 @@ bool range_planes(hm_pileup* p, const void* pcov, const void* ncov, const void* 
     return false;
 }
 
-// ---- the host side of count_block / loci_scan_kernel / compact_block ------------------------------------------------------
-inline int64_t range_blocks(int64_t lo, int64_t hi) { return (hi - lo + LOCI_PER_BLOCK - 1) / LOCI_PER_BLOCK; }
+// ---- the host side of the selection skeleton ---------------------------------------------------------------------------------
+inline dim3 row_grid(int64_t n) { return dim3((unsigned)((n + TPB - 1) / TPB)); }  // one thread per row
+const auto no_hook = [](auto&&...) {};
 
-// a count kernel has filled d_blk[0, nblk): their exclusive scan into d_offs, the total returned
-int64_t scan_blocks(hm_pileup* p, int64_t nblk) {
-    hipLaunchKernelGGL(loci_scan_kernel, dim3(1), dim3(1024), 0, p->stream, p->d_blk.as<int32_t>(), (int)nblk, p->d_offs.as<int64_t>());
+// The rows of a selection over the non-empty [lo, hi), ascending, into `buf` on the device -> their number, or an error code;
+// under the caller's guard.  launch_count(nblk, block_counts) counts them per LOCI_PER_BLOCK indices.  Once their number is known
+// and not 0, want(total) says whether they are written at all and uploads what the write needs; after_write(rows, total) launches
+// the per-row kernels that follow the write.  Nothing waits for the write.  `what` is done per sequence when the range is too large.
+template <class Sel, class Count, class Want, class After>
+int64_t stage_counted_rows(hm_pileup* p, const char* what, const Sel& sel, int64_t lo, int64_t hi, DevBuf& buf, Count launch_count,
+                           Want want, After after_write) {
+    using Row = typename Sel::Row;
+    const int64_t nblk = (hi - lo + LOCI_PER_BLOCK - 1) / LOCI_PER_BLOCK;
+    if (nblk >= (int64_t(1) << 31)) return pfail(p, HM_EINVAL, std::string("range too large: ") + what + " per sequence");
+    p->d_blk.reserve(4 * (size_t)nblk);
+    p->d_offs.reserve(8 * ((size_t)nblk + 1));
+    int64_t* offs = p->d_offs.as<int64_t>();
+    launch_count(nblk, p->d_blk.as<int32_t>());
+    hipLaunchKernelGGL(loci_scan_kernel, dim3(1), dim3(1024), 0, p->stream, p->d_blk.as<int32_t>(), (int)nblk, offs);
     HIP_TRY(hipGetLastError());
     int64_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, p->d_offs.as<int64_t>() + nblk, 8, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipMemcpyAsync(&total, offs + nblk, 8, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    if (!total || !want(total)) return total;
+    buf.reserve(sizeof(Row) * (size_t)total);
+    hipLaunchKernelGGL(select_write_kernel<Sel>, dim3((unsigned)nblk), dim3(TPB), 0, p->stream, sel, lo, hi, offs, buf.as<Row>());
+    after_write(buf.as<Row>(), total);
+    HIP_TRY(hipGetLastError());
+    return total;
+}
+
+// ... counted by the selection itself
+template <class Sel, class Want, class After>
+int64_t stage_rows(hm_pileup* p, const Sel& sel, int64_t lo, int64_t hi, DevBuf& buf, Want want, After after_write) {
+    return stage_counted_rows(
+        p, "fetch", sel, lo, hi, buf,
+        [&](int64_t nblk, int32_t* counts) {
+            hipLaunchKernelGGL(select_count_kernel<Sel>, dim3((unsigned)nblk), dim3(TPB), 0, p->stream, sel, lo, hi, counts);
+        },
+        want, after_write);
+}
+
+// the cap rule of every fetch: more rows than cap, or no `out`: only counted
+inline bool fits(int64_t total, const void* out, int64_t cap) { return total > 0 && total <= cap && out; }
+
+// total staged rows of buf are in `out` when this returns; -> total
+template <class Row>
+int64_t rows_to_host(hm_pileup* p, const DevBuf& buf, Row* out, int64_t total) {
+    HIP_TRY(hipMemcpyAsync(out, buf.p, sizeof(Row) * (size_t)total, hipMemcpyDeviceToHost, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
     return total;
 }
 
-// launch_write(offs, dst) compacts the `total` rows scan_blocks counted into `buf`; they are in `out` when this returns
-template <class Row, class Write>
-void write_rows(hm_pileup* p, DevBuf& buf, int64_t total, Row* out, Write launch_write) {
-    buf.reserve(sizeof(Row) * (size_t)total);
-    launch_write(p->d_offs.as<int64_t>(), buf.as<Row>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, buf.p, sizeof(Row) * (size_t)total, hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-}
-
-// The rows of the non-empty range [lo, hi) in ascending order -> their number, or an error code.  launch_count(grid, block_counts)
-// and launch_write(grid, offs, dst, total) start a count_block and a compact_block kernel with the same selection;
-// before_write() uploads what the write needs.  room(total) names the host memory for the rows once their number is known, or
-// NULL: only counted, nothing is written.
-template <class Row, class Room, class Count, class Before, class Write>
-int64_t compact_rows_to(hm_pileup* p, int64_t lo, int64_t hi, Room room, Count launch_count, Before before_write, Write launch_write) {
-    const int64_t nblk = range_blocks(lo, hi);
-    if (nblk >= (int64_t(1) << 31)) return pfail(p, HM_EINVAL, "range too large: fetch per sequence");
+// The rows of a selection over the non-empty [lo, hi) -> their number, or an error code: staged in d_rows, then copied.
+// room(total) names the host memory for the rows once their number is known, or NULL: only counted, nothing is written;
+// before_write() uploads what the write needs; after_write as above.
+template <class Sel, class Room, class Before, class After>
+int64_t compact_rows_to(hm_pileup* p, const Sel& sel, int64_t lo, int64_t hi, Room room, Before before_write, After after_write) {
     return guarded(p, [&]() -> int64_t {
-        const dim3 grid((unsigned)nblk);
-        p->d_blk.reserve(4 * (size_t)nblk);
-        p->d_offs.reserve(8 * ((size_t)nblk + 1));
-        launch_count(grid, p->d_blk.as<int32_t>());
-        const int64_t total = scan_blocks(p, nblk);
-        Row* out = total ? room(total) : nullptr;
-        if (!out) return total;
-        before_write();
-        write_rows(p, p->d_rows, total, out, [&](const int64_t* offs, Row* dst) { launch_write(grid, offs, dst, total); });
-        return total;
+        typename Sel::Row* out = nullptr;
+        const int64_t total = stage_rows(
+            p, sel, lo, hi, p->d_rows,
+            [&](int64_t n) {
+                if (!(out = room(n))) return false;
+                before_write();
+                return true;
+            },
+            after_write);
+        return total > 0 && out ? rows_to_host(p, p->d_rows, out, total) : total;
     });
 }
 
-// ... into the caller's out[cap]: more rows than cap, or no `out`: only counted
-template <class Row, class Count, class Before, class Write>
-int64_t compact_rows(hm_pileup* p, int64_t lo, int64_t hi, Row* out, int64_t cap, Count launch_count, Before before_write,
-                     Write launch_write) {
-    return compact_rows_to<Row>(
-        p, lo, hi, [&](int64_t total) { return total > cap ? nullptr : out; }, launch_count, before_write, launch_write);
+// ... into the caller's out[cap]
+template <class Sel, class Before, class After>
+int64_t compact_rows(hm_pileup* p, const Sel& sel, int64_t lo, int64_t hi, typename Sel::Row* out, int64_t cap, Before before_write,
+                     After after_write) {
+    return compact_rows_to(p, sel, lo, hi, [&](int64_t total) { return total > cap ? nullptr : out; }, before_write, after_write);
 }
 
 // log n!, n < LFACT_N, for asm_test_kernel: uploaded once per engine
@@ -1367,10 +1341,10 @@ void ensure_lfact(hm_pileup* p) {
     HIP_TRY(hipStreamSynchronize(p->stream));
 }
 
-struct AsmPlanes {
-    const int32_t *p1, *n1, *p2, *n2;
-    const uint32_t* ky;
-};
+// diff and pvalue of n compact rows
+void test_rows(hm_pileup* p, hm_asm_t* rows, int64_t n) {
+    hipLaunchKernelGGL(asm_test_kernel, row_grid(n), dim3(TPB), 0, p->stream, rows, n, p->d_lfact.as<double>());
+}
 
 // The arguments every call over the haplotype planes shares, by hm_pileup_fetch_asm's rules: the caller's five planes or, where all
 // are NULL, the engine's own partition and key planes (plane_base is then 0).  HM_OK, or the error recorded in the name of `who`.
@@ -1397,21 +1371,15 @@ int asm_planes(hm_pileup* p, const char* who, const void* pcov1, const void* nco
 // else it is 0.
 template <class Room>
 int64_t nonempty_bins(hm_pileup* p, Room room, bool with_p) {
-    hipStream_t st = p->stream;
-    const unsigned long long* bins = p->d_abins.as<unsigned long long>();
-    return compact_rows_to<hm_asm_bin_t>(
-        p, 0, HM_ASM_BINS, room,
-        [&](dim3 grid, int32_t* counts) { hipLaunchKernelGGL(asm_bins_count_kernel, grid, dim3(TPB), 0, st, bins, (int64_t)HM_ASM_BINS, counts); },
-        [&] { if (with_p) ensure_lfact(p); },
-        [&](dim3 grid, const int64_t* offs, hm_asm_bin_t* dst, int64_t total) {
-            hipLaunchKernelGGL(asm_bins_write_kernel, grid, dim3(TPB), 0, st, bins, (int64_t)HM_ASM_BINS, offs, dst);
+    return compact_rows_to(
+        p, BinsSel{p->d_abins.as<unsigned long long>()}, 0, HM_ASM_BINS, room, [&] { if (with_p) ensure_lfact(p); },
+        [&](hm_asm_bin_t* tab, int64_t total) {
             if (!with_p) return;
-            const dim3 per_row((unsigned)((total + TPB - 1) / TPB));
             p->d_arows.reserve(sizeof(hm_asm_t) * (size_t)total);
             hm_asm_t* rows = p->d_arows.as<hm_asm_t>();
-            hipLaunchKernelGGL(asm_bin_rows_kernel, per_row, dim3(TPB), 0, st, dst, total, rows);
-            hipLaunchKernelGGL(asm_test_kernel, per_row, dim3(TPB), 0, st, rows, total, p->d_lfact.as<double>());
-            hipLaunchKernelGGL(asm_bin_p_kernel, per_row, dim3(TPB), 0, st, rows, total, dst);
+            hipLaunchKernelGGL(asm_bin_rows_kernel, row_grid(total), dim3(TPB), 0, p->stream, tab, total, rows);
+            test_rows(p, rows, total);
+            hipLaunchKernelGGL(asm_bin_p_kernel, row_grid(total), dim3(TPB), 0, p->stream, rows, total, tab);
         });
 }
 
@@ -1887,14 +1855,7 @@ int64_t hm_pileup_fetch_loci(hm_pileup_t* p, const void* pcov, const void* ncov,
     RangePlanes s;
     if (!range_planes(p, pcov, ncov, key, plane_base, s)) return HM_ESTATE;
     if (hi == lo) return 0;
-    hipStream_t st = p->stream;
-    return compact_rows(
-        p, lo, hi, out, cap,
-        [&](dim3 grid, int32_t* counts) { hipLaunchKernelGGL(loci_count_kernel, grid, dim3(TPB), 0, st, s.pc, s.nc, lo, hi, counts); },
-        [] {},
-        [&](dim3 grid, const int64_t* offs, hm_locus_t* dst, int64_t) {
-            hipLaunchKernelGGL(loci_write_kernel, grid, dim3(TPB), 0, st, s.pc, s.nc, s.ky, plane_base, lo, hi, offs, dst);
-        });
+    return compact_rows(p, LociSel{s, plane_base}, lo, hi, out, cap, no_hook, no_hook);
 }
 
 int64_t hm_pileup_fetch_asm(hm_pileup_t* p, const void* pcov1, const void* ncov1, const void* pcov2, const void* ncov2,
@@ -1905,18 +1866,9 @@ int64_t hm_pileup_fetch_asm(hm_pileup_t* p, const void* pcov1, const void* ncov1
     const int rc = asm_planes(p, "hm_pileup_fetch_asm", pcov1, ncov1, pcov2, ncov2, key, plane_base, lo, hi, min_cov, s);
     if (rc != HM_OK) return rc;
     if (hi == lo) return 0;
-    hipStream_t st = p->stream;
     return compact_rows(
-        p, lo, hi, out, cap,
-        [&](dim3 grid, int32_t* counts) {
-            hipLaunchKernelGGL(asm_count_kernel, grid, dim3(TPB), 0, st, s.p1, s.n1, s.p2, s.n2, lo, hi, min_cov, counts);
-        },
-        [&] { ensure_lfact(p); },
-        [&](dim3 grid, const int64_t* offs, hm_asm_t* dst, int64_t total) {
-            hipLaunchKernelGGL(asm_write_kernel, grid, dim3(TPB), 0, st, s.p1, s.n1, s.p2, s.n2, s.ky, plane_base, lo, hi, min_cov, offs, dst);
-            hipLaunchKernelGGL(asm_test_kernel, dim3((unsigned)((total + TPB - 1) / TPB)), dim3(TPB), 0, st, dst, total,
-                               p->d_lfact.as<double>());
-        });
+        p, AsmSel<ASM_ALL>{s, plane_base, min_cov, 0u}, lo, hi, out, cap, [&] { ensure_lfact(p); },
+        [&](hm_asm_t* rows, int64_t total) { test_rows(p, rows, total); });
 }
 
 // ---- `pileup -H -A -Q` ------------------------------------------------------------------------------------------------------------
@@ -1929,25 +1881,22 @@ int64_t hm_pileup_asm_histogram(hm_pileup_t* p, const void* pcov1, const void* n
     const int rc = asm_planes(p, "hm_pileup_asm_histogram", pcov1, ncov1, pcov2, ncov2, key, plane_base, lo, hi, min_cov, s);
     if (rc != HM_OK) return rc;
     if (hi == lo) return 0;
-    const int64_t nblk = range_blocks(lo, hi);
-    if (nblk >= (int64_t(1) << 31)) return pfail(p, HM_EINVAL, "range too large: histogram per sequence");
-    hipStream_t st = p->stream;
     const int64_t n_big = guarded(p, [&]() -> int64_t {
-        p->d_blk.reserve(4 * (size_t)nblk);
-        p->d_offs.reserve(8 * ((size_t)nblk + 1));
-        p->d_abins.reserve(HM_ASM_BINS * sizeof(unsigned long long));
-        HIP_TRY(hipMemsetAsync(p->d_abins.p, 0, HM_ASM_BINS * sizeof(unsigned long long), st));
-        hipLaunchKernelGGL(asm_hist_kernel, dim3((unsigned)nblk), dim3(TPB), 0, st, s.p1, s.n1, s.p2, s.n2, s.ky, lo, hi, min_cov,
-                           p->d_abins.as<unsigned long long>(), p->d_blk.as<int32_t>());
-        const int64_t n = scan_blocks(p, nblk);
-        if (n == 0 || n > cap || !big) return n;
-        ensure_lfact(p);
-        write_rows(p, p->d_arows, n, big, [&](const int64_t* offs, hm_asm_t* dst) {
-            hipLaunchKernelGGL(asm_big_write_kernel, dim3((unsigned)nblk), dim3(TPB), 0, st, s.p1, s.n1, s.p2, s.n2, s.ky, plane_base, lo,
-                               hi, min_cov, offs, dst);
-            hipLaunchKernelGGL(asm_test_kernel, dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, st, dst, n, p->d_lfact.as<double>());
-        });
-        return n;
+        const int64_t n = stage_counted_rows(
+            p, "histogram", AsmSel<ASM_BIG>{s, plane_base, min_cov, 0u}, lo, hi, p->d_arows,
+            [&](int64_t nblk, int32_t* block_big) {
+                p->d_abins.reserve(HM_ASM_BINS * sizeof(unsigned long long));
+                HIP_TRY(hipMemsetAsync(p->d_abins.p, 0, HM_ASM_BINS * sizeof(unsigned long long), p->stream));
+                hipLaunchKernelGGL(asm_hist_kernel, dim3((unsigned)nblk), dim3(TPB), 0, p->stream, s.p1, s.n1, s.p2, s.n2, s.ky, lo, hi,
+                                   min_cov, p->d_abins.as<unsigned long long>(), block_big);
+            },
+            [&](int64_t n) {
+                if (!fits(n, big, cap)) return false;
+                ensure_lfact(p);
+                return true;
+            },
+            [&](hm_asm_t* rows, int64_t n) { test_rows(p, rows, n); });
+        return fits(n, big, cap) ? rows_to_host(p, p->d_arows, big, n) : n;
     });
     if (n_big < 0 || n_big > cap || (n_big && !big)) return n_big;
     // the range's non-empty bins (few next to HM_ASM_BINS) come to the host compacted and are added there
@@ -2019,33 +1968,32 @@ int64_t hm_pileup_fetch_asm_q(hm_pileup_t* p, const void* pcov1, const void* nco
     if (rc != HM_OK) return rc;
     if (hi == lo) return 0;
     hipStream_t st = p->stream;
-    return compact_rows(
-        p, lo, hi, out, cap,
-        [&](dim3 grid, int32_t* counts) {
-            hipLaunchKernelGGL(asm_count_kernel, grid, dim3(TPB), 0, st, s.p1, s.n1, s.p2, s.n2, lo, hi, min_cov, counts);
-        },
-        [&] {
-            ensure_lfact(p);
-            if (n_tab) {
-                p->d_atab.reserve(sizeof(hm_asm_bin_t) * (size_t)n_tab);
-                HIP_TRY(hipMemcpyAsync(p->d_atab.p, tab, sizeof(hm_asm_bin_t) * (size_t)n_tab, hipMemcpyHostToDevice, st));
-            }
-            if (n_big) {
-                p->d_abig.reserve(sizeof(hm_asm_t) * (size_t)n_big);
-                p->d_abigq.reserve(sizeof(double) * (size_t)n_big);
-                HIP_TRY(hipMemcpyAsync(p->d_abig.p, big, sizeof(hm_asm_t) * (size_t)n_big, hipMemcpyHostToDevice, st));
-                HIP_TRY(hipMemcpyAsync(p->d_abigq.p, big_q, sizeof(double) * (size_t)n_big, hipMemcpyHostToDevice, st));
-            }
-        },
-        [&](dim3 grid, const int64_t* offs, hm_asmq_t* dst, int64_t total) {  // hm_pileup_fetch_asm's rows, then q next to each
-            const dim3 per_row((unsigned)((total + TPB - 1) / TPB));
-            p->d_arows.reserve(sizeof(hm_asm_t) * (size_t)total);
-            hm_asm_t* rows = p->d_arows.as<hm_asm_t>();
-            hipLaunchKernelGGL(asm_write_kernel, grid, dim3(TPB), 0, st, s.p1, s.n1, s.p2, s.n2, s.ky, plane_base, lo, hi, min_cov, offs, rows);
-            hipLaunchKernelGGL(asm_test_kernel, per_row, dim3(TPB), 0, st, rows, total, p->d_lfact.as<double>());
-            hipLaunchKernelGGL(asm_q_write_kernel, per_row, dim3(TPB), 0, st, rows, total, p->d_atab.as<hm_asm_bin_t>(), n_tab,
-                               p->d_abig.as<hm_asm_t>(), p->d_abigq.as<double>(), n_big, dst);
-        });
+    return guarded(p, [&]() -> int64_t {  // hm_pileup_fetch_asm's rows in d_arows, then q next to each in d_rows
+        const int64_t total = stage_rows(
+            p, AsmSel<ASM_ALL>{s, plane_base, min_cov, 0u}, lo, hi, p->d_arows,
+            [&](int64_t n) {
+                if (!fits(n, out, cap)) return false;
+                ensure_lfact(p);
+                if (n_tab) {
+                    p->d_atab.reserve(sizeof(hm_asm_bin_t) * (size_t)n_tab);
+                    HIP_TRY(hipMemcpyAsync(p->d_atab.p, tab, sizeof(hm_asm_bin_t) * (size_t)n_tab, hipMemcpyHostToDevice, st));
+                }
+                if (n_big) {
+                    p->d_abig.reserve(sizeof(hm_asm_t) * (size_t)n_big);
+                    p->d_abigq.reserve(sizeof(double) * (size_t)n_big);
+                    HIP_TRY(hipMemcpyAsync(p->d_abig.p, big, sizeof(hm_asm_t) * (size_t)n_big, hipMemcpyHostToDevice, st));
+                    HIP_TRY(hipMemcpyAsync(p->d_abigq.p, big_q, sizeof(double) * (size_t)n_big, hipMemcpyHostToDevice, st));
+                }
+                return true;
+            },
+            [&](hm_asm_t* rows, int64_t n) {
+                test_rows(p, rows, n);
+                p->d_rows.reserve(sizeof(hm_asmq_t) * (size_t)n);
+                hipLaunchKernelGGL(asm_q_write_kernel, row_grid(n), dim3(TPB), 0, st, rows, n, p->d_atab.as<hm_asm_bin_t>(), n_tab,
+                                   p->d_abig.as<hm_asm_t>(), p->d_abigq.as<double>(), n_big, p->d_rows.as<hm_asmq_t>());
+            });
+        return fits(total, out, cap) ? rows_to_host(p, p->d_rows, out, total) : total;
+    });
 }
 
 // ---- `pileup -H -A -G` ------------------------------------------------------------------------------------------------------------
@@ -2062,37 +2010,19 @@ int64_t hm_pileup_fetch_asm_regions(hm_pileup_t* p, const void* pcov1, const voi
     if (rc != HM_OK) return rc;
     if (n_ctx_rows) *n_ctx_rows = 0;
     if (hi == lo) return 0;
-    const int64_t nblk = range_blocks(lo, hi);
-    if (nblk >= (int64_t(1) << 31)) return pfail(p, HM_EINVAL, "range too large: fetch per sequence");
-    hipStream_t st = p->stream;
-    const int64_t R = guarded(p, [&]() -> int64_t {  // the context's rows, tested, stay in d_arows
-        const dim3 grid((unsigned)nblk);
-        p->d_blk.reserve(4 * (size_t)nblk);
-        p->d_offs.reserve(8 * ((size_t)nblk + 1));
-        hipLaunchKernelGGL(asm_ctx_count_kernel, grid, dim3(TPB), 0, st, s.p1, s.n1, s.p2, s.n2, s.ky, lo, hi, min_cov, (uint32_t)ctx,
-                           p->d_blk.as<int32_t>());
-        const int64_t total = scan_blocks(p, nblk);
-        if (!total) return 0;
-        ensure_lfact(p);
-        p->d_arows.reserve(sizeof(hm_asm_t) * (size_t)total);
-        hm_asm_t* rows = p->d_arows.as<hm_asm_t>();
-        hipLaunchKernelGGL(asm_ctx_write_kernel, grid, dim3(TPB), 0, st, s.p1, s.n1, s.p2, s.n2, s.ky, plane_base, lo, hi, min_cov,
-                           (uint32_t)ctx, p->d_offs.as<int64_t>(), rows);
-        hipLaunchKernelGGL(asm_test_kernel, dim3((unsigned)((total + TPB - 1) / TPB)), dim3(TPB), 0, st, rows, total, p->d_lfact.as<double>());
-        HIP_TRY(hipGetLastError());
-        return total;
+    return guarded(p, [&]() -> int64_t {
+        const int64_t R = stage_rows(  // the context's rows, tested, stay in d_arows
+            p, AsmSel<ASM_CTX>{s, plane_base, min_cov, (uint32_t)ctx}, lo, hi, p->d_arows,
+            [&](int64_t) {
+                ensure_lfact(p);
+                return true;
+            },
+            [&](hm_asm_t* rows, int64_t n) { test_rows(p, rows, n); });
+        if (R <= 0) return R;
+        if (n_ctx_rows) *n_ctx_rows = R;
+        const RegionSel chains{p->d_arows.as<hm_asm_t>(), R, RegionRule{max_p, max_gap, min_loci, keep_edges != 0}, (uint32_t)ctx};
+        return compact_rows(p, chains, 0, R, out, cap, no_hook, no_hook);
     });
-    if (R <= 0) return R;
-    if (n_ctx_rows) *n_ctx_rows = R;
-    const hm_asm_t* rows = p->d_arows.as<hm_asm_t>();
-    const RegionRule rule{max_p, max_gap, min_loci, keep_edges != 0};
-    return compact_rows(
-        p, 0, R, out, cap,
-        [&](dim3 grid, int32_t* counts) { hipLaunchKernelGGL(asm_region_count_kernel, grid, dim3(TPB), 0, st, rows, R, rule, counts); },
-        [] {},
-        [&](dim3 grid, const int64_t* offs, hm_asm_region_t* dst, int64_t) {
-            hipLaunchKernelGGL(asm_region_write_kernel, grid, dim3(TPB), 0, st, rows, R, rule, (uint32_t)ctx, offs, dst);
-        });
 }
 
 // ---- `pileup -D` ----------------------------------------------------------------------------------------------------------------
@@ -2132,6 +2062,87 @@ typename Sc::T row_reduce(hm_pileup* p, const Sc& sc, int64_t n) {
     return total;
 }
 
+// Both `-D` entry points, in the name of `who`: pass `pass` over the piece that `part` describes, or with no `part` the whole
+// range, which is the one-piece segments pass with no row before or behind it: nothing of a piece is then copied to the host.
+// *n_rows takes the number of the context's rows.
+int64_t fetch_domains(hm_pileup* p, const std::string& who, const void* pcov, const void* ncov, const void* key, int64_t plane_base,
+                      int64_t lo, int64_t hi, int32_t ctx, int64_t A, int64_t B, int64_t S, int64_t max_gap, int32_t pass,
+                      hm_domain_part_t* part, int64_t* n_rows, hm_domain_t* out, int64_t cap) {
+    if (lo < 0 || hi < lo) return pfail(p, HM_EINVAL, who + ": bad range");
+    if (ctx < 0 || ctx > 2) return pfail(p, HM_EINVAL, who + ": ctx must be 0, 1 or 2");
+    if (A < 1 || A > DOM_W || B > -1 || B < -DOM_W || S < 0 || S > DOM_W)
+        return pfail(p, HM_EINVAL, who + ": A must be in (0, 2^24], B in [-2^24, 0), S in [0, 2^24]");
+    if (max_gap < 1) return pfail(p, HM_EINVAL, who + ": max_gap must be >= 1");
+    RangePlanes s;
+    if (!range_planes(p, pcov, ncov, key, plane_base, s)) return HM_ESTATE;
+    if ((!pcov || !ncov || !key) && !p->seq_off.empty() && hi > p->seq_off.back())  // an own plane ends with the reference
+        return pfail(p, HM_EINVAL, who + ": range past the reference");
+    const bool carried = pass != HM_DOMAIN_PASS_SUMMARY;
+    const bool has_prev = part && carried && part->has_prev, has_next = part && pass == HM_DOMAIN_PASS_SEGMENTS && part->has_next;
+    constexpr int64_t DOM_D = int64_t(1) << 46;  // every d lies within +-2^46
+    if (has_prev && (part->prev_d < -DOM_D || part->prev_d > DOM_D)) return pfail(p, HM_EINVAL, who + ": prev_d outside [-2^46, 2^46]");
+    if (has_prev && (part->prev_gpos < 0 || part->prev_gpos >= plane_base + lo))
+        return pfail(p, HM_EINVAL, who + ": prev_gpos must lie below the piece's first locus");
+    if (has_next && part->next_gpos < plane_base + hi) return pfail(p, HM_EINVAL, who + ": next_gpos must lie behind the piece's last locus");
+    if (has_next && part->last_state != 0 && part->last_state != 1) return pfail(p, HM_EINVAL, who + ": last_state must be 0 or 1");
+    if (n_rows) *n_rows = 0;
+    if (hi == lo) return 0;
+    hipStream_t st = p->stream;
+    const DomRule rule{A, B, S, max_gap};
+    return guarded(p, [&]() -> int64_t {
+        // the context's rows with their sums and states stay on the device
+        const int64_t R = stage_rows(p, DomRowSel{s, plane_base, (uint32_t)ctx}, lo, hi, p->d_drows, [](int64_t) { return true; }, no_hook);
+        if (R <= 0) return R;
+        if ((R + SCAN_ROWS - 1) / SCAN_ROWS >= (int64_t(1) << 31) - 1) return pfail(p, HM_EINVAL, "range too large: fetch per sequence");
+        p->d_dsums.reserve(sizeof(DomSum) * (size_t)R);
+        p->d_dcode.reserve((size_t)R);
+        p->d_dstate.reserve((size_t)R);
+        p->d_dlast.reserve(8);
+        const DomRow* rows = p->d_drows.as<DomRow>();
+        const uint8_t* state = p->d_dstate.as<uint8_t>();
+        DomRow ends[2];  // a piece's first and last row
+        if (part) {
+            HIP_TRY(hipMemcpyAsync(&ends[0], rows, sizeof(DomRow), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(&ends[1], rows + (R - 1), sizeof(DomRow), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        DomFwd fwd{rows, R, rule, p->d_dsums.as<DomSum>(), p->d_dcode.as<uint8_t>(), !carried, has_prev, has_prev ? part->prev_gpos : 0,
+                   has_prev ? part->prev_d : 0, DomFwd::KEEP, p->d_dlast.as<int64_t>()};
+        if (pass == HM_DOMAIN_PASS_SUMMARY) {  // rows 1 .. R - 1 composed; nothing is stored
+            const DomFwd::T f = row_reduce(p, fwd, R);
+            part->c = f.c;
+            part->lo = f.lo;
+            part->hi = f.hi;
+        } else {
+            if (pass == HM_DOMAIN_PASS_SEGMENTS) fwd.last_code = has_next ? part->last_state : -1;
+            row_scan(p, fwd, R);
+            if (part) {
+                HIP_TRY(hipMemcpyAsync(&part->d_last, p->d_dlast.p, 8, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipStreamSynchronize(st));
+            }
+            const DomBwd bwd{p->d_dcode.as<uint8_t>(), R, p->d_dstate.as<uint8_t>()};
+            if (pass == HM_DOMAIN_PASS_CODES) part->back = row_reduce(p, bwd, R);  // the last row's code is KEEP: the transitions inside
+            else row_scan(p, bwd, R);
+        }
+        if (n_rows) *n_rows = R;
+        if (part) {
+            part->first_gpos = ends[0].gpos;
+            part->last_gpos = ends[1].gpos;
+            part->e_first = (int64_t)std::min(ends[0].pcov, DOM_COV) * A + (int64_t)std::min(ends[0].ncov, DOM_COV) * B;
+        }
+        if (pass != HM_DOMAIN_PASS_SEGMENTS) return R;
+        const bool first_break = !has_prev || ends[0].gpos - part->prev_gpos > max_gap, last_break = !has_next || part->next_gpos - ends[1].gpos > max_gap;
+        const int64_t n_seg = stage_rows(
+            p, DomHeadSel{rows, state, max_gap}, 0, R, p->d_dheads, [&](int64_t n) { return fits(n, out, cap); },
+            [&](int64_t* heads, int64_t n) {
+                p->d_rows.reserve(sizeof(hm_domain_t) * (size_t)n);
+                hipLaunchKernelGGL(domain_build_part_kernel, row_grid(n), dim3(TPB), 0, st, rows, p->d_dsums.as<DomSum>(), state, heads, n, R,
+                                   rule, (uint32_t)ctx, first_break, last_break, p->d_rows.as<hm_domain_t>());
+            });
+        return fits(n_seg, out, cap) ? rows_to_host(p, p->d_rows, out, n_seg) : n_seg;
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -2140,145 +2151,18 @@ int64_t hm_pileup_fetch_domains(hm_pileup_t* p, const void* pcov, const void* nc
                                 int64_t hi, int32_t ctx, int64_t A, int64_t B, int64_t S, int64_t max_gap, int64_t* n_ctx_rows,
                                 hm_domain_t* out, int64_t cap) {
     if (!p) return HM_EINVAL;
-    if (lo < 0 || hi < lo) return pfail(p, HM_EINVAL, "hm_pileup_fetch_domains: bad range");
-    if (ctx < 0 || ctx > 2) return pfail(p, HM_EINVAL, "hm_pileup_fetch_domains: ctx must be 0, 1 or 2");
-    if (A < 1 || A > DOM_W || B > -1 || B < -DOM_W || S < 0 || S > DOM_W)
-        return pfail(p, HM_EINVAL, "hm_pileup_fetch_domains: A must be in (0, 2^24], B in [-2^24, 0), S in [0, 2^24]");
-    if (max_gap < 1) return pfail(p, HM_EINVAL, "hm_pileup_fetch_domains: max_gap must be >= 1");
-    RangePlanes s;
-    if (!range_planes(p, pcov, ncov, key, plane_base, s)) return HM_ESTATE;
-    if ((!pcov || !ncov || !key) && !p->seq_off.empty() && hi > p->seq_off.back())  // an own plane ends with the reference
-        return pfail(p, HM_EINVAL, "hm_pileup_fetch_domains: range past the reference");
-    if (n_ctx_rows) *n_ctx_rows = 0;
-    if (hi == lo) return 0;
-    const int64_t nblk = range_blocks(lo, hi);
-    if (nblk >= (int64_t(1) << 31)) return pfail(p, HM_EINVAL, "range too large: fetch per sequence");
-    hipStream_t st = p->stream;
-    const DomRule rule{A, B, S, max_gap};
-    const int64_t R = guarded(p, [&]() -> int64_t {  // the context's rows with their sums and states stay on the device
-        const dim3 grid((unsigned)nblk);
-        p->d_blk.reserve(4 * (size_t)nblk);
-        p->d_offs.reserve(8 * ((size_t)nblk + 1));
-        hipLaunchKernelGGL(domain_rows_count_kernel, grid, dim3(TPB), 0, st, s.pc, s.nc, s.ky, lo, hi, (uint32_t)ctx, p->d_blk.as<int32_t>());
-        const int64_t total = scan_blocks(p, nblk);
-        if (!total) return 0;
-        if ((total + SCAN_ROWS - 1) / SCAN_ROWS >= (int64_t(1) << 31)) return pfail(p, HM_EINVAL, "range too large: fetch per sequence");
-        p->d_drows.reserve(sizeof(DomRow) * (size_t)total);
-        p->d_dsums.reserve(sizeof(DomSum) * (size_t)total);
-        p->d_dcode.reserve((size_t)total);
-        p->d_dstate.reserve((size_t)total);
-        hipLaunchKernelGGL(domain_rows_write_kernel, grid, dim3(TPB), 0, st, s.pc, s.nc, s.ky, plane_base, lo, hi, (uint32_t)ctx,
-                           p->d_offs.as<int64_t>(), p->d_drows.as<DomRow>());
-        row_scan(p, DomFwd{p->d_drows.as<DomRow>(), total, rule, p->d_dsums.as<DomSum>(), p->d_dcode.as<uint8_t>()}, total);
-        row_scan(p, DomBwd{p->d_dcode.as<uint8_t>(), total, p->d_dstate.as<uint8_t>()}, total);
-        return total;
-    });
-    if (R <= 0) return R;
-    if (n_ctx_rows) *n_ctx_rows = R;
-    const DomRow* rows = p->d_drows.as<DomRow>();
-    const uint8_t* state = p->d_dstate.as<uint8_t>();
-    return compact_rows(
-        p, 0, R, out, cap,
-        [&](dim3 grid, int32_t* counts) { hipLaunchKernelGGL(domain_head_count_kernel, grid, dim3(TPB), 0, st, rows, state, R, max_gap, counts); },
-        [] {},
-        [&](dim3 grid, const int64_t* offs, hm_domain_t* dst, int64_t n_seg) {
-            p->d_dheads.reserve(8 * (size_t)n_seg);
-            int64_t* heads = p->d_dheads.as<int64_t>();
-            hipLaunchKernelGGL(domain_head_write_kernel, grid, dim3(TPB), 0, st, rows, state, R, max_gap, offs, heads);
-            hipLaunchKernelGGL(domain_build_kernel, dim3((unsigned)((n_seg + TPB - 1) / TPB)), dim3(TPB), 0, st, rows,
-                               p->d_dsums.as<DomSum>(), state, heads, n_seg, R, rule, (uint32_t)ctx, dst);
-        });
+    return fetch_domains(p, "hm_pileup_fetch_domains", pcov, ncov, key, plane_base, lo, hi, ctx, A, B, S, max_gap, HM_DOMAIN_PASS_SEGMENTS,
+                         nullptr, n_ctx_rows, out, cap);
 }
 
 int64_t hm_pileup_fetch_domains_part(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t plane_base, int64_t lo,
                                      int64_t hi, int32_t ctx, int64_t A, int64_t B, int64_t S, int64_t max_gap, int32_t pass,
                                      hm_domain_part_t* part, hm_domain_t* out, int64_t cap) {
     if (!p) return HM_EINVAL;
-    const char* const fn = "hm_pileup_fetch_domains_part: ";
-    if (!part) return pfail(p, HM_EINVAL, std::string(fn) + "no part");
-    if (pass < HM_DOMAIN_PASS_SUMMARY || pass > HM_DOMAIN_PASS_SEGMENTS) return pfail(p, HM_EINVAL, std::string(fn) + "pass must be 0, 1 or 2");
-    if (lo < 0 || hi < lo) return pfail(p, HM_EINVAL, std::string(fn) + "bad range");
-    if (ctx < 0 || ctx > 2) return pfail(p, HM_EINVAL, std::string(fn) + "ctx must be 0, 1 or 2");
-    if (A < 1 || A > DOM_W || B > -1 || B < -DOM_W || S < 0 || S > DOM_W)
-        return pfail(p, HM_EINVAL, std::string(fn) + "A must be in (0, 2^24], B in [-2^24, 0), S in [0, 2^24]");
-    if (max_gap < 1) return pfail(p, HM_EINVAL, std::string(fn) + "max_gap must be >= 1");
-    RangePlanes s;
-    if (!range_planes(p, pcov, ncov, key, plane_base, s)) return HM_ESTATE;
-    if ((!pcov || !ncov || !key) && !p->seq_off.empty() && hi > p->seq_off.back())  // an own plane ends with the reference
-        return pfail(p, HM_EINVAL, std::string(fn) + "range past the reference");
-    const bool carried = pass != HM_DOMAIN_PASS_SUMMARY;
-    const bool has_prev = carried && part->has_prev, has_next = pass == HM_DOMAIN_PASS_SEGMENTS && part->has_next;
-    constexpr int64_t DOM_D = int64_t(1) << 46;  // every d lies within +-2^46
-    if (has_prev && (part->prev_d < -DOM_D || part->prev_d > DOM_D)) return pfail(p, HM_EINVAL, std::string(fn) + "prev_d outside [-2^46, 2^46]");
-    if (has_prev && (part->prev_gpos < 0 || part->prev_gpos >= plane_base + lo))
-        return pfail(p, HM_EINVAL, std::string(fn) + "prev_gpos must lie below the piece's first locus");
-    if (has_next && part->next_gpos < plane_base + hi) return pfail(p, HM_EINVAL, std::string(fn) + "next_gpos must lie behind the piece's last locus");
-    if (has_next && part->last_state != 0 && part->last_state != 1) return pfail(p, HM_EINVAL, std::string(fn) + "last_state must be 0 or 1");
-    part->n_rows = 0;
-    if (hi == lo) return 0;
-    const int64_t nblk = range_blocks(lo, hi);
-    if (nblk >= (int64_t(1) << 31)) return pfail(p, HM_EINVAL, "range too large: fetch per sequence");
-    hipStream_t st = p->stream;
-    const DomRule rule{A, B, S, max_gap};
-    DomRow ends[2];  // the piece's first and last row
-    const int64_t R = guarded(p, [&]() -> int64_t {
-        const dim3 grid((unsigned)nblk);
-        p->d_blk.reserve(4 * (size_t)nblk);
-        p->d_offs.reserve(8 * ((size_t)nblk + 1));
-        hipLaunchKernelGGL(domain_rows_count_kernel, grid, dim3(TPB), 0, st, s.pc, s.nc, s.ky, lo, hi, (uint32_t)ctx, p->d_blk.as<int32_t>());
-        const int64_t total = scan_blocks(p, nblk);
-        if (!total) return 0;
-        if ((total + SCAN_ROWS - 1) / SCAN_ROWS >= (int64_t(1) << 31) - 1) return pfail(p, HM_EINVAL, "range too large: fetch per sequence");
-        p->d_drows.reserve(sizeof(DomRow) * (size_t)total);
-        p->d_dsums.reserve(sizeof(DomSum) * (size_t)total);
-        p->d_dcode.reserve((size_t)total);
-        p->d_dstate.reserve((size_t)total);
-        p->d_dlast.reserve(8);
-        DomRow* rows = p->d_drows.as<DomRow>();
-        hipLaunchKernelGGL(domain_rows_write_kernel, grid, dim3(TPB), 0, st, s.pc, s.nc, s.ky, plane_base, lo, hi, (uint32_t)ctx,
-                           p->d_offs.as<int64_t>(), rows);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&ends[0], rows, sizeof(DomRow), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(&ends[1], rows + (total - 1), sizeof(DomRow), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        DomFwdPart fwd{{rows, total, rule, p->d_dsums.as<DomSum>(), p->d_dcode.as<uint8_t>()}, !carried, has_prev,
-                       has_prev ? part->prev_gpos : 0, has_prev ? part->prev_d : 0, DomFwd::KEEP, p->d_dlast.as<int64_t>()};
-        if (pass == HM_DOMAIN_PASS_SUMMARY) {  // rows 1 .. R - 1 composed; nothing is stored
-            const DomFwd::T f = row_reduce(p, fwd, total);
-            part->c = f.c;
-            part->lo = f.lo;
-            part->hi = f.hi;
-            return total;
-        }
-        if (pass == HM_DOMAIN_PASS_SEGMENTS) fwd.last_code = has_next ? part->last_state : -1;
-        row_scan(p, fwd, total);
-        HIP_TRY(hipMemcpyAsync(&part->d_last, p->d_dlast.p, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        const DomBwd bwd{p->d_dcode.as<uint8_t>(), total, p->d_dstate.as<uint8_t>()};
-        if (pass == HM_DOMAIN_PASS_CODES) part->back = row_reduce(p, bwd, total);  // the last row's code is KEEP: the transitions inside
-        else row_scan(p, bwd, total);
-        return total;
-    });
-    if (R <= 0) return R;
-    part->n_rows = R;
-    part->first_gpos = ends[0].gpos;
-    part->last_gpos = ends[1].gpos;
-    part->e_first = (int64_t)std::min(ends[0].pcov, DOM_COV) * A + (int64_t)std::min(ends[0].ncov, DOM_COV) * B;
-    if (pass != HM_DOMAIN_PASS_SEGMENTS) return R;
-    const DomRow* rows = p->d_drows.as<DomRow>();
-    const uint8_t* state = p->d_dstate.as<uint8_t>();
-    const bool first_break = !has_prev || ends[0].gpos - part->prev_gpos > max_gap, last_break = !has_next || part->next_gpos - ends[1].gpos > max_gap;
-    return compact_rows(
-        p, 0, R, out, cap,
-        [&](dim3 grid, int32_t* counts) { hipLaunchKernelGGL(domain_head_count_kernel, grid, dim3(TPB), 0, st, rows, state, R, max_gap, counts); },
-        [] {},
-        [&](dim3 grid, const int64_t* offs, hm_domain_t* dst, int64_t n_seg) {
-            p->d_dheads.reserve(8 * (size_t)n_seg);
-            int64_t* heads = p->d_dheads.as<int64_t>();
-            hipLaunchKernelGGL(domain_head_write_kernel, grid, dim3(TPB), 0, st, rows, state, R, max_gap, offs, heads);
-            hipLaunchKernelGGL(domain_build_part_kernel, dim3((unsigned)((n_seg + TPB - 1) / TPB)), dim3(TPB), 0, st, rows,
-                               p->d_dsums.as<DomSum>(), state, heads, n_seg, R, rule, (uint32_t)ctx, first_break, last_break, dst);
-        });
+    const std::string who = "hm_pileup_fetch_domains_part";
+    if (!part) return pfail(p, HM_EINVAL, who + ": no part");
+    if (pass < HM_DOMAIN_PASS_SUMMARY || pass > HM_DOMAIN_PASS_SEGMENTS) return pfail(p, HM_EINVAL, who + ": pass must be 0, 1 or 2");
+    return fetch_domains(p, who, pcov, ncov, key, plane_base, lo, hi, ctx, A, B, S, max_gap, pass, part, &part->n_rows, out, cap);
 }
 
 int hm_domain_scores(double level_lo, double level_hi, double penalty, int64_t* A, int64_t* B, int64_t* S) {
@@ -2343,27 +2227,32 @@ int64_t hm_pileup_site_histogram(hm_pileup_t* p, const void* pcov, const void* n
     RangePlanes s;
     if (!range_planes(p, pcov, ncov, key, plane_base, s)) return HM_ESTATE;
     if (hi == lo) return 0;
-    const int64_t nblk = range_blocks(lo, hi);
-    if (nblk >= (int64_t(1) << 31)) return pfail(p, HM_EINVAL, "range too large: histogram per sequence");
     return guarded(p, [&]() -> int64_t {
         hipStream_t st = p->stream;
-        p->d_blk.reserve(4 * (size_t)nblk);
-        p->d_offs.reserve(8 * ((size_t)nblk + 1));
-        p->d_sbins.reserve(HM_SITE_BINS * sizeof(unsigned long long));
-        HIP_TRY(hipMemsetAsync(p->d_sbins.p, 0, HM_SITE_BINS * sizeof(unsigned long long), st));
-        // <= 512 workgroups of 48 KB LDS (two per CU), more only to keep a workgroup below 2^19 blocks = 2^31 loci (its LDS counters)
-        const int64_t grid = std::max(std::min<int64_t>(nblk, 512), (nblk + (int64_t(1) << 19) - 1) >> 19);
-        hipLaunchKernelGGL(sites_hist_kernel, dim3((unsigned)grid), dim3(TPB), 0, st, s.pc, s.nc, s.ky, lo, hi, nblk,
-                           p->d_sbins.as<unsigned long long>(), p->d_blk.as<int32_t>());
-        const int64_t n_big = scan_blocks(p, nblk);
-        if (n_big > cap || (n_big && !big)) return n_big;
         std::vector<uint64_t> h((size_t)HM_SITE_BINS);
-        HIP_TRY(hipMemcpyAsync(h.data(), p->d_sbins.p, HM_SITE_BINS * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        if (n_big)  // the list, and with it the bins, are on the host when write_rows returns
-            write_rows(p, p->d_sbig, n_big, big, [&](const int64_t* offs, hm_locus_t* dst) {
-                hipLaunchKernelGGL(sites_big_write_kernel, dim3((unsigned)nblk), dim3(TPB), 0, st, s.pc, s.nc, s.ky, plane_base, lo, hi, offs, dst);
-            });
-        else HIP_TRY(hipStreamSynchronize(st));
+        const auto bins_to_host = [&] { HIP_TRY(hipMemcpyAsync(h.data(), p->d_sbins.p, HM_SITE_BINS * sizeof(uint64_t), hipMemcpyDeviceToHost, st)); };
+        const int64_t n_big = stage_counted_rows(
+            p, "histogram", SitesBigSel{s, plane_base}, lo, hi, p->d_sbig,
+            [&](int64_t nblk, int32_t* block_big) {
+                p->d_sbins.reserve(HM_SITE_BINS * sizeof(unsigned long long));
+                HIP_TRY(hipMemsetAsync(p->d_sbins.p, 0, HM_SITE_BINS * sizeof(unsigned long long), st));
+                // <= 512 workgroups of 48 KB LDS (two per CU), more only to keep a workgroup below 2^19 blocks = 2^31 loci (its LDS counters)
+                const int64_t grid = std::max(std::min<int64_t>(nblk, 512), (nblk + (int64_t(1) << 19) - 1) >> 19);
+                hipLaunchKernelGGL(sites_hist_kernel, dim3((unsigned)grid), dim3(TPB), 0, st, s.pc, s.nc, s.ky, lo, hi, nblk,
+                                   p->d_sbins.as<unsigned long long>(), block_big);
+            },
+            [&](int64_t n) {  // the bins' copy is queued before the list's write
+                if (!fits(n, big, cap)) return false;
+                bins_to_host();
+                return true;
+            },
+            no_hook);
+        if (n_big < 0 || n_big > cap || (n_big && !big)) return n_big;
+        if (n_big) rows_to_host(p, p->d_sbig, big, n_big);  // the list, and with it the bins, are on the host when this returns
+        else {
+            bins_to_host();
+            HIP_TRY(hipStreamSynchronize(st));
+        }
         for (size_t i = 0; i < h.size(); ++i) bins[i] += h[i];
         return n_big;
     });
@@ -2424,27 +2313,24 @@ int64_t hm_pileup_fetch_sites(hm_pileup_t* p, const void* pcov, const void* ncov
     if (!range_planes(p, pcov, ncov, key, plane_base, s)) return HM_ESTATE;
     if (hi == lo) return 0;
     hipStream_t st = p->stream;
-    return compact_rows(
-        p, lo, hi, out, cap,
-        [&](dim3 grid, int32_t* counts) {
-            hipLaunchKernelGGL(sites_count_kernel, grid, dim3(TPB), 0, st, s.pc, s.nc, s.ky, lo, hi, (uint32_t)ctx_mask, counts);
-        },
-        [&] {
-            const size_t tab_bytes = HM_SITE_BINS * sizeof(double);
-            p->d_stab.reserve(2 * tab_bytes);
-            HIP_TRY(hipMemcpyAsync(p->d_stab.p, ptab, tab_bytes, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(p->d_stab.as<char>() + tab_bytes, qtab, tab_bytes, hipMemcpyHostToDevice, st));
-            if (!n_big) return;
-            p->d_sbig.reserve(sizeof(hm_locus_t) * (size_t)n_big);
-            p->d_sbigpq.reserve(2 * sizeof(double) * (size_t)n_big);
-            HIP_TRY(hipMemcpyAsync(p->d_sbig.p, big, sizeof(hm_locus_t) * (size_t)n_big, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(p->d_sbigpq.p, big_p, sizeof(double) * (size_t)n_big, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(p->d_sbigpq.as<double>() + n_big, big_q, sizeof(double) * (size_t)n_big, hipMemcpyHostToDevice, st));
-        },
-        [&](dim3 grid, const int64_t* offs, hm_site_t* dst, int64_t) {
-            hipLaunchKernelGGL(sites_write_kernel, grid, dim3(TPB), 0, st, s.pc, s.nc, s.ky, plane_base, lo, hi, (uint32_t)ctx_mask,
-                               p->d_stab.as<double>(), p->d_sbig.as<hm_locus_t>(), p->d_sbigpq.as<double>(), n_big, offs, dst);
-        });
+    const size_t tab_bytes = HM_SITE_BINS * sizeof(double);
+    return guarded(p, [&]() -> int64_t {
+        p->d_stab.reserve(2 * tab_bytes);  // before the selection takes their addresses
+        p->d_sbig.reserve(sizeof(hm_locus_t) * (size_t)n_big);
+        p->d_sbigpq.reserve(2 * sizeof(double) * (size_t)n_big);
+        const SitesSel rows{s, plane_base, (uint32_t)ctx_mask, p->d_stab.as<double>(), p->d_sbig.as<hm_locus_t>(), p->d_sbigpq.as<double>(), n_big};
+        return compact_rows(
+            p, rows, lo, hi, out, cap,
+            [&] {
+                HIP_TRY(hipMemcpyAsync(p->d_stab.p, ptab, tab_bytes, hipMemcpyHostToDevice, st));
+                HIP_TRY(hipMemcpyAsync(p->d_stab.as<char>() + tab_bytes, qtab, tab_bytes, hipMemcpyHostToDevice, st));
+                if (!n_big) return;
+                HIP_TRY(hipMemcpyAsync(p->d_sbig.p, big, sizeof(hm_locus_t) * (size_t)n_big, hipMemcpyHostToDevice, st));
+                HIP_TRY(hipMemcpyAsync(p->d_sbigpq.p, big_p, sizeof(double) * (size_t)n_big, hipMemcpyHostToDevice, st));
+                HIP_TRY(hipMemcpyAsync(p->d_sbigpq.as<double>() + n_big, big_q, sizeof(double) * (size_t)n_big, hipMemcpyHostToDevice, st));
+            },
+            no_hook);
+    });
 }
 
 }  // extern "C"
