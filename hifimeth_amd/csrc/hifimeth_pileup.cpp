@@ -23,6 +23,8 @@
 // -D (ours): also <prefix>.domains.<ctx>.bed, the covered loci of each context cut into low and high methylated stretches by an
 // exact two-state Viterbi scan on the GPU (levels -u, switch penalty -x, largest linking distance -j):
 //   chrom <tab> start <tab> end <tab> n_loci <tab> L|H <tab> level <tab> pcov <tab> ncov <tab> score      (DESIGN.md section 10).
+// -D -Y n (ours): the two levels are fitted from the data first, from -u in at most n iterations of hard EM over the state sums
+// the GPU gives (hm_pileup_domain_sums); also <prefix>.domains.fit.tsv, the iterations and the fitted levels.
 // -K (ours): the input is an aligned BAM that still carries the kinetics tags (pbmm2 keeps fi / fp / ri / rp): the reads are called
 // on the fly by the call engine and their calls go straight to the pileup engine (hm_pileup_submit_read_calls) -- the files
 // `call` followed by `pileup` writes, without the mod-BAM between the two.
@@ -100,6 +102,8 @@ struct PileupOptions {
     double domain_penalty = 8.0;       // -x: cost of a change of state, in nats
     long long domain_max_gap = 1000;   // -j: largest distance that still links two loci
     bool domain_option_given = false, domain_option_bad = false;  // any of -u -x -j; one of them with a value out of range
+    long long domain_fit_iter = 0;     // -Y: fit the two levels from the data, at most this many iterations; 0: not asked for
+    bool domain_fit_bad = false;
     // -K: call on the fly; the options below are `call`'s (hifimeth_call.cpp), same meaning and defaults
     bool kinetics = false;
     bool call_option_given = false;  // any of -m -c -l -p -T: a usage error without -K
@@ -151,6 +155,10 @@ void pileup_usage(const char* exe) {
             "    context (CpG,CHG,CHH); nan instead of a pair: that context is not segmented\n    Default: 0.1:0.8,0.05:0.5,0.02:0.2\n"
             "  -x <nats>\n    With -D: penalty of a change of state, in [0, 256]\n    Default: 8\n"
             "  -j <bp>\n    With -D: largest distance between two loci that still links them, >= 1\n    Default: 1000\n"
+            "  -Y <n>\n    With -D: fit the two levels of every segmented context from the data, starting from -u: segment, take each\n"
+            "    state's pooled methylation level as its new level, at most n times (hard EM; it stops when the integer weights repeat).\n"
+            "    Also writes <prefix>.domains.fit.tsv: per context and iteration ctx, iter, lo, hi, A, B, P0, N0, R0, P1, N1, R1, then\n"
+            "    ctx, status, lo, hi -- the fitted levels, which -u takes back\n"
             "  -K\n    The input is an aligned BAM that carries the kinetics tags fi / fp / ri / rp instead of MM / ML: call 5mC on the\n"
             "    fly and pile the calls up directly.  For equal -c -l -p -T -q -f the output files are byte-identical to those of\n"
             "    `%s call` on that BAM followed by `%s pileup` on its output; no mod-BAM is written.  (Give -T explicitly\n"
@@ -936,6 +944,69 @@ bool write_domains(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, con
         });
 }
 
+// `pileup -D -Y` after hm_pileup_count: the two levels of every segmented context fitted by hard EM (include/hifimeth_hip.h has the
+// definition), o.domain_lo / domain_hi and A / B replaced by the result, <prefix>.domains.fit.tsv written.  Per iteration the state
+// sums of all sequences (hm_pileup_domain_sums: no segment is built), then hm_domain_refit and the stop rule.  1 done, -1 engine
+// error (hm_pileup_last_error), 0 another error (message printed).
+int fit_domains(hm_pileup_t* pe, const Fasta& fa, PileupOptions& o, int64_t A[3], int64_t B[3], int64_t S) {
+    static const char* cn[3] = {"CpG", "CHG", "CHH"};
+    const std::string path = o.prefix + ".domains.fit.tsv";
+    FILE* f = fopen(path.c_str(), "w");
+    if (!f) { fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str()); return 0; }
+    struct Iter { double lo, hi; int64_t A, B; };
+    for (int c = 0; c < 3; ++c) {
+        if (std::isnan(o.domain_lo[c])) continue;
+        std::vector<Iter> seen;
+        Iter cur{o.domain_lo[c], o.domain_hi[c], A[c], B[c]}, result = cur;
+        const char* status = nullptr;
+        while (!status) {
+            int64_t sums[6] = {0, 0, 0, 0, 0, 0}, off = 0;
+            for (size_t s = 0; s < fa.names.size(); ++s) {
+                int64_t one[6];
+                const int64_t lo = off, hi = off + fa.length[s];
+                off = hi;
+                if (hm_pileup_domain_sums(pe, nullptr, nullptr, nullptr, 0, lo, hi, c, cur.A, cur.B, S, o.domain_max_gap, one) < 0) { fclose(f); return -1; }
+                for (int k = 0; k < 6; ++k) sums[k] += one[k];
+            }
+            fprintf(f, "%s\t%zu\t%.17g\t%.17g\t%lld\t%lld", cn[c], seen.size(), cur.lo, cur.hi, (long long)cur.A, (long long)cur.B);
+            for (int k = 0; k < 6; ++k) fprintf(f, "\t%lld", (long long)sums[k]);
+            fputc('\n', f);
+            seen.push_back(cur);
+            Iter next = cur;
+            int64_t s_unused = 0;
+            const int rc = hm_domain_refit(sums, o.domain_penalty, &next.lo, &next.hi);
+            if (rc != HM_OK && rc != HM_EDATA) { fclose(f); fprintf(stderr, "ERROR: hm_domain_refit failed\n"); return 0; }
+            if (rc == HM_EDATA) { status = sums[2] == 0 || sums[5] == 0 ? "one_state" : "degenerate"; break; }
+            if (hm_domain_scores(next.lo, next.hi, o.domain_penalty, &next.A, &next.B, &s_unused) != HM_OK) { status = "degenerate"; break; }
+            const auto same = [&](const Iter& x) { return x.A == next.A && x.B == next.B; };
+            const auto j = std::find_if(seen.begin(), seen.end(), same);
+            if (same(cur)) status = "converged";
+            else if (j != seen.end()) {  // iterations j .. i, j with the levels that closed the cycle: the smallest (A, B)
+                status = "cycle";
+                result = next;
+                for (auto m = j + 1; m != seen.end(); ++m)
+                    if (std::make_pair(m->A, m->B) < std::make_pair(result.A, result.B)) result = *m;
+            } else if ((long long)seen.size() == o.domain_fit_iter) {
+                status = "max_iter";
+                result = next;
+            } else result = cur = next;
+        }
+        fprintf(f, "%s\t%s\t%.17g\t%.17g\n", cn[c], status, result.lo, result.hi);
+        fprintf(stderr, "domains: %s levels fitted in %zu iteration%s (%s): %.17g:%.17g\n", cn[c], seen.size(), seen.size() == 1 ? "" : "s", status,
+                result.lo, result.hi);
+        o.domain_lo[c] = result.lo;
+        o.domain_hi[c] = result.hi;
+        int64_t s_again = 0;
+        if (hm_domain_scores(result.lo, result.hi, o.domain_penalty, &A[c], &B[c], &s_again) != HM_OK) {
+            fclose(f);
+            fprintf(stderr, "ERROR: the fitted %s levels are no valid pair\n", cn[c]);
+            return 0;
+        }
+    }
+    fclose(f);
+    return 1;
+}
+
 // `pileup -H -A -Q` after hm_pileup_count: the tested loci of the whole reference counted per tuple, the p of every tuple that
 // occurs, the q-values (hm_asm_qvalues), then the rows of write_asm with their q looked up (56 B per row on the device and here),
 // and <prefix>.asm.summary.tsv from the table's weights.  1 done, -1 engine error (hm_pileup_last_error), 0 another error (message
@@ -1254,6 +1325,13 @@ int cmd_pileup(int argc, char** argv) {
                 if (end == v || *end || errno || o.domain_max_gap < 1) o.domain_option_bad = true;
             }
         }
+        else if (a == "-Y") {
+            const char* v = argv[++i];
+            char* end = nullptr;
+            errno = 0;
+            o.domain_fit_iter = strtoll(v, &end, 10);
+            if (end == v || *end || errno || o.domain_fit_iter < 1) o.domain_fit_bad = true;
+        }
         else if (a == "-B") o.control = argv[++i];
         else if (a == "-e") {
             o.rates_given = true;
@@ -1295,6 +1373,8 @@ int cmd_pileup(int argc, char** argv) {
         if (!std::isnan(o.domain_lo[c]) && hm_domain_scores(o.domain_lo[c], o.domain_hi[c], o.domain_penalty, &dom_A[c], &dom_B[c], &dom_S) != HM_OK)
             o.domain_option_bad = true;
     const char* bad_domains = o.domain_option_given && !o.domains ? "-u, -x and -j need -D"
+                              : (o.domain_fit_iter || o.domain_fit_bad) && !o.domains ? "-Y needs -D (it fits the levels of -D)"
+                              : o.domain_fit_bad ? "-Y takes the largest number of iterations, an integer >= 1"
                               : o.domain_option_bad ? "-u takes lo:hi with 0 < lo < hi < 1 (levels a 2^24-th of a nat apart at least) or nan, once or per context; "
                                                       "-x must be in [0, 256], -j an integer >= 1" : nullptr;
     if (bad_domains) { fprintf(stderr, "ERROR: %s\n", bad_domains); pileup_usage(argv[0]); return EXIT_FAILURE; }
@@ -1323,6 +1403,8 @@ int cmd_pileup(int argc, char** argv) {
         }
         fprintf(stderr, "domains: levels %s, switch penalty %g nats, loci linked up to %lld bases -> %s.domains.*\n", levels.c_str(), o.domain_penalty,
                 o.domain_max_gap, o.prefix.c_str());
+        if (o.domain_fit_iter)
+            fprintf(stderr, "domains: the levels are fitted from the data, %lld iterations at most -> %s.domains.fit.tsv\n", o.domain_fit_iter, o.prefix.c_str());
     }
     if (o.kinetics)
         fprintf(stderr, "kinetics: called on the fly (models %s, contexts%s%s%s, min read length %d, precision %d, trunk %s)\n", o.model_dir.c_str(),
@@ -1486,6 +1568,11 @@ int cmd_pileup(int argc, char** argv) {
         if (!write_asm_regions(pe, fa, o, out.f)) return die("asm regions");
     }
     if (o.domains) {
+        if (o.domain_fit_iter) {
+            const int rc = fit_domains(pe, fa, o, dom_A, dom_B, dom_S);
+            if (rc < 0) return die("domains fit");
+            if (rc == 0) return EXIT_FAILURE;
+        }
         CtxFiles out;
         if (!out.open(o.prefix, "domains.", ".bed")) return EXIT_FAILURE;
         if (!write_domains(pe, fa, o, dom_A, dom_B, dom_S, out.f)) return die("domains");

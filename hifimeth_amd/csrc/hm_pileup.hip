@@ -32,7 +32,8 @@
 //                   LDS, the loci beyond the histogram listed (SitesBigSel), rows written by table lookup
 //   DomRowSel / rowscan_* / DomHeadSel   methylation domains (`pileup -D`): the rows of one context compacted, a two-state Viterbi
 //                   path as two scans over a monoid (reduce per workgroup, one workgroup scans the aggregates, re-scan), segment
-//                   heads compacted, one thread per segment (domain_build_part_kernel)
+//                   heads compacted, one thread per segment (domain_build_part_kernel); for the fit of the levels (`-D -Y`) the
+//                   rows' counters summed by state behind the two scans instead (domain_sums_kernel)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1155,6 +1156,37 @@ __global__ __launch_bounds__(TPB) void domain_build_part_kernel(const DomRow* __
     out[s] = domain_segment(rows, sums, state, heads, s, n_seg, n, rule, ctx, first_break, last_break);
 }
 
+// `pileup -D -Y`: sums[0..5] += P0, N0, R0, P1, N1, R1 -- the unclamped pcov and ncov and the number of the n compact rows by
+// their state.  Registers over a grid stride, wavefront shuffle, LDS, then at most six integer atomics per workgroup, as
+// sites_sums_kernel; the host keeps the grid at DOM_SUMS_WGS workgroups at most.
+constexpr int DOM_SUMS_WGS = 1024;
+
+__global__ __launch_bounds__(TPB) void domain_sums_kernel(const DomRow* __restrict__ rows, const uint8_t* __restrict__ state, int64_t n,
+                                                           unsigned long long* __restrict__ sums) {
+    __shared__ unsigned long long part[TPB / 64][6];
+    unsigned long long s[6] = {0, 0, 0, 0, 0, 0};
+    for (int64_t t = (int64_t)blockIdx.x * TPB + threadIdx.x; t < n; t += (int64_t)gridDim.x * TPB) {
+        const DomRow r = rows[t];
+        const bool high = state[t] != 0;
+        s[0] += high ? 0ull : (unsigned long long)r.pcov;
+        s[1] += high ? 0ull : (unsigned long long)r.ncov;
+        s[2] += high ? 0ull : 1ull;
+        s[3] += high ? (unsigned long long)r.pcov : 0ull;
+        s[4] += high ? (unsigned long long)r.ncov : 0ull;
+        s[5] += high ? 1ull : 0ull;
+    }
+    for (int c = 0; c < 6; ++c) {
+        for (int d = 32; d; d >>= 1) s[c] += __shfl_down(s[c], d);
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][c] = s[c];
+    }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        unsigned long long t = 0;
+        for (int w = 0; w < TPB / 64; ++w) t += part[w][threadIdx.x];
+        if (t) atomicAdd(&sums[threadIdx.x], t);
+    }
+}
+
 }  // namespace
 
 // ================================================ host ==========================================================
@@ -1203,6 +1235,7 @@ struct hm_pileup {
     // workgroup aggregates of the scan that runs, and the segment heads
     DevBuf d_drows{HALF}, d_dsums{HALF}, d_dcode{HALF}, d_dstate{HALF}, d_dagg{HALF}, d_dheads{HALF};
     DevBuf d_dlast{EXACT};  // hm_pileup_fetch_domains_part: the d of a piece's last row, 8 B
+    DevBuf d_dstate_sums{EXACT};  // hm_pileup_domain_sums, allocated by its first call: the six state sums, 48 B
     int64_t n_recs = 0;
     bool bins_ready = false;
 
@@ -2064,10 +2097,11 @@ typename Sc::T row_reduce(hm_pileup* p, const Sc& sc, int64_t n) {
 
 // Both `-D` entry points, in the name of `who`: pass `pass` over the piece that `part` describes, or with no `part` the whole
 // range, which is the one-piece segments pass with no row before or behind it: nothing of a piece is then copied to the host.
-// *n_rows takes the number of the context's rows.
+// *n_rows takes the number of the context's rows.  With `state_sums` (`pileup -D -Y`, the segments pass only) the rows' states are
+// summed instead of cut into segments: no heads, no segment, nothing of the piece but the six sums comes back; -> R.
 int64_t fetch_domains(hm_pileup* p, const std::string& who, const void* pcov, const void* ncov, const void* key, int64_t plane_base,
                       int64_t lo, int64_t hi, int32_t ctx, int64_t A, int64_t B, int64_t S, int64_t max_gap, int32_t pass,
-                      hm_domain_part_t* part, int64_t* n_rows, hm_domain_t* out, int64_t cap) {
+                      hm_domain_part_t* part, int64_t* n_rows, hm_domain_t* out, int64_t cap, int64_t* state_sums = nullptr) {
     if (lo < 0 || hi < lo) return pfail(p, HM_EINVAL, who + ": bad range");
     if (ctx < 0 || ctx > 2) return pfail(p, HM_EINVAL, who + ": ctx must be 0, 1 or 2");
     if (A < 1 || A > DOM_W || B > -1 || B < -DOM_W || S < 0 || S > DOM_W)
@@ -2086,9 +2120,11 @@ int64_t fetch_domains(hm_pileup* p, const std::string& who, const void* pcov, co
     if (has_next && part->next_gpos < plane_base + hi) return pfail(p, HM_EINVAL, who + ": next_gpos must lie behind the piece's last locus");
     if (has_next && part->last_state != 0 && part->last_state != 1) return pfail(p, HM_EINVAL, who + ": last_state must be 0 or 1");
     if (n_rows) *n_rows = 0;
+    if (state_sums) std::fill(state_sums, state_sums + 6, int64_t(0));
     if (hi == lo) return 0;
     hipStream_t st = p->stream;
     const DomRule rule{A, B, S, max_gap};
+    const bool piece_out = part && !state_sums;  // a piece's ends, d_last and summary go back to the caller
     return guarded(p, [&]() -> int64_t {
         // the context's rows with their sums and states stay on the device
         const int64_t R = stage_rows(p, DomRowSel{s, plane_base, (uint32_t)ctx}, lo, hi, p->d_drows, [](int64_t) { return true; }, no_hook);
@@ -2101,7 +2137,7 @@ int64_t fetch_domains(hm_pileup* p, const std::string& who, const void* pcov, co
         const DomRow* rows = p->d_drows.as<DomRow>();
         const uint8_t* state = p->d_dstate.as<uint8_t>();
         DomRow ends[2];  // a piece's first and last row
-        if (part) {
+        if (piece_out) {
             HIP_TRY(hipMemcpyAsync(&ends[0], rows, sizeof(DomRow), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(&ends[1], rows + (R - 1), sizeof(DomRow), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
@@ -2116,7 +2152,7 @@ int64_t fetch_domains(hm_pileup* p, const std::string& who, const void* pcov, co
         } else {
             if (pass == HM_DOMAIN_PASS_SEGMENTS) fwd.last_code = has_next ? part->last_state : -1;
             row_scan(p, fwd, R);
-            if (part) {
+            if (piece_out) {
                 HIP_TRY(hipMemcpyAsync(&part->d_last, p->d_dlast.p, 8, hipMemcpyDeviceToHost, st));
                 HIP_TRY(hipStreamSynchronize(st));
             }
@@ -2125,6 +2161,17 @@ int64_t fetch_domains(hm_pileup* p, const std::string& who, const void* pcov, co
             else row_scan(p, bwd, R);
         }
         if (n_rows) *n_rows = R;
+        if (state_sums) {
+            static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the sums are added as unsigned long long");
+            p->d_dstate_sums.reserve(6 * sizeof(int64_t));
+            HIP_TRY(hipMemsetAsync(p->d_dstate_sums.p, 0, 6 * sizeof(int64_t), st));
+            hipLaunchKernelGGL(domain_sums_kernel, dim3(grid_for(R, DOM_SUMS_WGS)), dim3(TPB), 0, st, rows, state, R,
+                               p->d_dstate_sums.as<unsigned long long>());
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(state_sums, p->d_dstate_sums.p, 6 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            return R;
+        }
         if (part) {
             part->first_gpos = ends[0].gpos;
             part->last_gpos = ends[1].gpos;
@@ -2165,6 +2212,26 @@ int64_t hm_pileup_fetch_domains_part(hm_pileup_t* p, const void* pcov, const voi
     return fetch_domains(p, who, pcov, ncov, key, plane_base, lo, hi, ctx, A, B, S, max_gap, pass, part, &part->n_rows, out, cap);
 }
 
+int64_t hm_pileup_domain_sums(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t plane_base, int64_t lo,
+                              int64_t hi, int32_t ctx, int64_t A, int64_t B, int64_t S, int64_t max_gap, int64_t sums[6]) {
+    if (!p) return HM_EINVAL;
+    if (!sums) return pfail(p, HM_EINVAL, "hm_pileup_domain_sums: no sums");
+    return fetch_domains(p, "hm_pileup_domain_sums", pcov, ncov, key, plane_base, lo, hi, ctx, A, B, S, max_gap, HM_DOMAIN_PASS_SEGMENTS,
+                         nullptr, nullptr, nullptr, 0, sums);
+}
+
+int64_t hm_pileup_domain_sums_part(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t plane_base, int64_t lo,
+                                   int64_t hi, int32_t ctx, int64_t A, int64_t B, int64_t S, int64_t max_gap,
+                                   const hm_domain_part_t* part, int64_t sums[6]) {
+    if (!p) return HM_EINVAL;
+    const std::string who = "hm_pileup_domain_sums_part";
+    if (!part) return pfail(p, HM_EINVAL, who + ": no part");
+    if (!sums) return pfail(p, HM_EINVAL, who + ": no sums");
+    hm_domain_part_t carry = *part;  // only read: the pass's outputs stay here
+    return fetch_domains(p, who, pcov, ncov, key, plane_base, lo, hi, ctx, A, B, S, max_gap, HM_DOMAIN_PASS_SEGMENTS, &carry, nullptr,
+                         nullptr, 0, sums);
+}
+
 int hm_domain_scores(double level_lo, double level_hi, double penalty, int64_t* A, int64_t* B, int64_t* S) {
     if (!A || !B || !S) return HM_EINVAL;
     if (!(level_lo > 0.0 && level_lo < level_hi && level_hi < 1.0) || !(penalty >= 0.0)) return HM_EINVAL;
@@ -2176,6 +2243,22 @@ int hm_domain_scores(double level_lo, double level_hi, double penalty, int64_t* 
     *A = ia;
     *B = ib;
     *S = std::llround(s);
+    return HM_OK;
+}
+
+int hm_domain_refit(const int64_t sums[6], double penalty, double* level_lo, double* level_hi) {
+    if (!sums || !level_lo || !level_hi || !(penalty >= 0.0)) return HM_EINVAL;
+    for (int k = 0; k < 6; ++k)
+        if (sums[k] < 0) return HM_EINVAL;
+    const int64_t P0 = sums[0], N0 = sums[1], R0 = sums[2], P1 = sums[3], N1 = sums[4], R1 = sums[5];
+    if (R0 == 0 || R1 == 0 || P0 + N0 <= 0 || P1 + N1 <= 0) return HM_EDATA;  // one state; (a row has pcov + ncov > 0)
+    constexpr double EPS = 1e-6;
+    const double lo = std::min(std::max((double)P0 / (double)(P0 + N0), EPS), 1.0 - EPS);
+    const double hi = std::min(std::max((double)P1 / (double)(P1 + N1), EPS), 1.0 - EPS);
+    int64_t A, B, S;
+    if (!(lo < hi) || hm_domain_scores(lo, hi, penalty, &A, &B, &S) != HM_OK) return HM_EDATA;
+    *level_lo = lo;
+    *level_hi = hi;
     return HM_OK;
 }
 

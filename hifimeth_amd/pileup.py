@@ -43,6 +43,12 @@ The same segments from pieces (`pileup_dist -D`): `pu.domains_part(ctx, lo, hi, 
 (`domain_forward_carries`, `domain_backward_carries`: host only, Python ints) and `stitch_domains(parts, A, B)` joins the segments
 that cross a cut -- byte for byte what one `pu.domains` over the whole gives.
 
+The two levels fitted from the data (`pileup -D -Y n`): `pu.domain_sums(ctx, lo, hi, A, B, S)` are pcov, ncov and the number of
+loci summed per state on the device, without a segment being built; `domain_refit(sums, penalty)` -- host only, the C library's --
+turns them into the next levels; `DomainFit` is the stop rule of the iteration (hard EM), `pu.fit_domain_levels(ctx, lo, hi, ...)`
+runs it over the sequences of the reference and `domains_fit_tsv` is the text of <prefix>.domains.fit.tsv.  All of it is integer
+sums and one rounded division per level: the fit is the same however the planes are cut into pieces or over ranks.
+
 Fused with the caller (`pileup -K`): `pu.add_called(read, calls)` takes the records `MethylationCaller` returned for an aligned read
 instead of parsed MM / ML -- the same effect as add() of that read carrying the calls as tags, without the tag text.
 
@@ -265,6 +271,80 @@ def domain_scores(level_lo: float, level_hi: float, penalty: float = DOMAIN_PENA
     if lib().hm_domain_scores(level_lo, level_hi, penalty, C.byref(A), C.byref(B), C.byref(S)) != 0:
         raise HifimethError("hm_domain_scores: 0 < level_lo < level_hi < 1 and penalty >= 0 expected, with weights of at most 2^24")
     return int(A.value), int(B.value), int(S.value)
+
+
+def domain_refit(sums, penalty: float = DOMAIN_PENALTY) -> Optional[Tuple[float, float]]:
+    """sums = (P0, N0, R0, P1, N1, R1), the counters and loci per state -> the next levels (P0 / (P0 + N0), P1 / (P1 + N1)), each
+    clamped to [1e-6, 1 - 1e-6]; None where the fit ends here: a state without loci, or levels that are no valid pair for
+    domain_scores.  By the C library (host only)."""
+    lo, hi = C.c_double(0.0), C.c_double(0.0)
+    rc = lib().hm_domain_refit((C.c_int64 * 6)(*(int(x) for x in sums)), penalty, C.byref(lo), C.byref(hi))
+    if rc not in (0, -4):                                                             # HM_OK, HM_EDATA
+        raise HifimethError("hm_domain_refit: six sums >= 0 and penalty >= 0 expected")
+    return (float(lo.value), float(hi.value)) if rc == 0 else None
+
+
+class DomainFit:
+    """The iteration that fits the two levels of one context (include/hifimeth_hip.h has the definition).  While `status` is None,
+    `rule` = (A, B, S) is what the state sums are wanted under; step(sums) takes them.  Then `status` is one of converged, cycle,
+    max_iter, one_state, degenerate, (`lo`, `hi`) the result and `rule` its scores.  `history`: per iteration
+    (i, lo, hi, A, B, sums)."""
+
+    def __init__(self, level_lo: float, level_hi: float, penalty: float = DOMAIN_PENALTY, max_iter: int = 20):
+        if max_iter < 1:
+            raise ValueError("max_iter must be >= 1")
+        self.lo, self.hi, self.penalty, self.max_iter = float(level_lo), float(level_hi), penalty, max_iter
+        self.rule = domain_scores(self.lo, self.hi, penalty)
+        self.status: Optional[str] = None
+        self.history: List[tuple] = []
+
+    def _end(self, status: str, lo: float, hi: float) -> None:
+        self.status, self.lo, self.hi = status, lo, hi
+        self.rule = domain_scores(lo, hi, self.penalty)
+
+    def step(self, sums) -> None:
+        assert self.status is None
+        sums = tuple(int(x) for x in sums)
+        i, (A, B, _) = len(self.history), self.rule
+        self.history.append((i, self.lo, self.hi, A, B, sums))
+        new = domain_refit(sums, self.penalty)
+        if new is None:
+            return self._end("one_state" if sums[2] == 0 or sums[5] == 0 else "degenerate", self.lo, self.hi)
+        A2, B2, _ = domain_scores(*new, self.penalty)
+        seen = [(h[3], h[4]) for h in self.history]
+        if (A2, B2) == (A, B):
+            return self._end("converged", self.lo, self.hi)
+        if (A2, B2) in seen:                                  # iterations j .. i, j with the levels that closed the cycle
+            j = seen.index((A2, B2))
+            members = [((A2, B2), new)] + [((h[3], h[4]), (h[1], h[2])) for h in self.history[j + 1:]]
+            return self._end("cycle", *min(members)[1])
+        if i + 1 == self.max_iter:
+            return self._end("max_iter", *new)
+        self.lo, self.hi = new
+        self.rule = (A2, B2, self.rule[2])
+
+
+def fit_levels(sums_of, level_lo: float, level_hi: float, penalty: float = DOMAIN_PENALTY, max_iter: int = 20):
+    """sums_of(A, B, S) -> the six state sums of everything that is fitted -> (lo, hi, status, history) of DomainFit"""
+    fit = DomainFit(level_lo, level_hi, penalty, max_iter)
+    while fit.status is None:
+        fit.step(sums_of(*fit.rule))
+    return fit.lo, fit.hi, fit.status, fit.history
+
+
+def domains_fit_tsv(fits) -> str:
+    """the text of <prefix>.domains.fit.tsv.  fits: per context None (not segmented) or (lo, hi, status, history).  One row per
+    context and iteration -- ctx, iter, level_lo, level_hi, A, B, P0, N0, R0, P1, N1, R1 -- then ctx, status, level_lo, level_hi:
+    the result, which -u takes back as it stands."""
+    text = []
+    for c, fit in enumerate(fits):
+        if fit is None:
+            continue
+        lo, hi, status, history = fit
+        for i, l, h, A, B, sums in history:
+            text.append("%s\t%d\t%.17g\t%.17g\t%d\t%d\t" % (CTX_NAMES[c], i, l, h, A, B) + "\t".join("%d" % x for x in sums) + "\n")
+        text.append("%s\t%s\t%.17g\t%.17g\n" % (CTX_NAMES[c], status, lo, hi))
+    return "".join(text)
 
 
 class _DomainPart(C.Structure):                                                       # hm_domain_part_t, 104 bytes
@@ -718,6 +798,36 @@ class MethylationPileup:
     def domains_bed(self, rows: np.ndarray) -> dict:
         """domains_bed() with this reference's names"""
         return domains_bed(rows, self.names, self.offsets)
+
+    def domain_sums(self, ctx: int, lo: int = 0, hi: Optional[int] = None, A: Optional[int] = None, B: Optional[int] = None,
+                    S: Optional[int] = None, max_gap: int = DOMAIN_MAX_GAP, planes=None, plane_base: int = 0,
+                    carry: Optional[dict] = None) -> Tuple[int, ...]:
+        """-> (P0, N0, R0, P1, N1, R1): pcov, ncov and the number of loci of context ctx over [lo, hi), by the state domains()
+        gives each locus (0 low, 1 high) -- summed on the device without building a segment (hm_pileup_domain_sums).  With
+        `carry` [lo, hi) is a PIECE and the states are those the chain gives it: the carry of domains_part's segments pass
+        (hm_pileup_domain_sums_part).  Arguments as for domains()."""
+        hi = self.n_loci if hi is None else hi
+        if A is None or B is None or S is None:
+            A, B, S = domain_scores(*DOMAIN_LEVELS[ctx])
+        sums = (C.c_int64 * 6)()
+        args = (*self._plane_ptrs(planes), plane_base, lo, hi, ctx, A, B, S, max_gap)
+        if carry is None:
+            self._check(self._L.hm_pileup_domain_sums(self._h, *args, sums))
+        else:
+            part = _DomainPart(**{k: int(v) for k, v in carry.items()})
+            self._check(self._L.hm_pileup_domain_sums_part(self._h, *args, C.byref(part), sums))
+        return tuple(int(x) for x in sums)
+
+    def fit_domain_levels(self, ctx: int, lo: float, hi: float, penalty: float = DOMAIN_PENALTY, max_gap: int = DOMAIN_MAX_GAP,
+                          max_iter: int = 20, planes=None, plane_base: int = 0):
+        """-> (lo, hi, status, history): the two levels of context ctx fitted to the planes from the start (lo, hi), by hard EM
+        over the sequences of the reference: domain_sums per sequence under the current levels, the levels refitted from the
+        sums (DomainFit has the stop rule).  The planes span the whole reference."""
+        def sums_of(A, B, S):
+            per_seq = [self.domain_sums(ctx, int(a) - plane_base, int(b) - plane_base, A, B, S, max_gap, planes, plane_base)
+                       for a, b in zip(self.offsets[:-1], self.offsets[1:])]
+            return [sum(col) for col in zip(*per_seq)] if per_seq else [0] * 6
+        return fit_levels(sums_of, lo, hi, penalty, max_iter)
 
 
 # ---- multi-GPU exchange (SURVEY.md section 8e): histograms all-reduced, per-locus planes reduce-scattered ------------

@@ -31,6 +31,10 @@ summaries travel by all_gather_object, every rank walks the same carries from le
 gathers (d_last, back), walks from right to left (domain_backward_carries), runs pass G; the segments are gathered and rank 0 joins
 those that cross a chunk boundary (stitch_domains) and writes <prefix>.domains.<ctx>.bed: three small exchanges in all, and
 files byte-identical to `pileup -D`.
+-D -Y n: the two levels fitted from the data first.  Per iteration passes S and C and the two walks as above, then
+hm_pileup_domain_sums_part per piece (no segment is built) and one all-reduce of 18 int64, the three contexts' state sums; every
+rank runs the same hm_domain_refit and stop rule (DomainFit) on them, so no level crosses ranks.  Rank 0 writes
+<prefix>.domains.fit.tsv; it and the segments are byte-identical to `pileup -D -Y n`.
 """
 from __future__ import annotations
 
@@ -44,8 +48,8 @@ from . import dist as D
 from .bamio import is_coordinate_sorted, load_fasta, read_bam
 from .caller import HifimethError
 from .pileup import (ASM_DTYPE, CTX_NAMES, DOMAIN_LEVELS, DOMAIN_MAX_GAP, DOMAIN_PASS_CODES, DOMAIN_PASS_SEGMENTS, DOMAIN_PASS_SUMMARY,
-                     DOMAIN_PENALTY, LOCUS_DTYPE, MethylationPileup, allreduce_histograms, asm_qvalues, asm_summary_tsv,
-                     domain_backward_carries, domain_forward_carries, domain_scores, locus_ranges, parse_domain_levels, parse_rates,
+                     DOMAIN_PENALTY, LOCUS_DTYPE, DomainFit, MethylationPileup, allreduce_histograms, asm_qvalues, asm_summary_tsv,
+                     domain_backward_carries, domain_forward_carries, domain_scores, domains_fit_tsv, locus_ranges, parse_domain_levels, parse_rates,
                      rates_from_sums, reduce_scatter_planes, reduce_scatter_sum, resolve_threshold, sites_rates_tsv, sites_table,
                      stitch_asm_regions, stitch_domains)
 
@@ -54,8 +58,9 @@ def run(reference: str, bam: str, prefix: str, min_mapq: int = 0, min_pi: float 
         batch: int = 256, backend: str | None = None, log=sys.stderr, haplotypes: bool = False, asm: bool = False,
         asm_min_cov: int = 5, control: str | None = None, rates=None, asm_q: bool = False,
         asm_regions: bool = False, max_p: float = 0.01, max_gap: int = 500, min_loci: int = 3, domain_rules=None,
-        domain_max_gap: int = DOMAIN_MAX_GAP):
-    """domain_rules (-D): per context (A, B, S) of domain_scores, or None for a context that is not segmented"""
+        domain_max_gap: int = DOMAIN_MAX_GAP, domain_fit=None):
+    """domain_rules (-D): per context (A, B, S) of domain_scores, or None for a context that is not segmented.  domain_fit (-Y):
+    {"levels": per context (lo, hi) or None, "penalty", "max_iter"}: the levels are fitted from those and replace domain_rules"""
     import torch
     rank, local_rank, world = D.env_world()
     dist = D.init_process_group(backend, force=bool(os.environ.get("HM_FORCE_COLLECTIVES")))
@@ -210,15 +215,43 @@ def run(reference: str, bam: str, prefix: str, min_mapq: int = 0, min_pi: float 
                     out.setdefault(k, []).append((r, v))
             return out
 
-        sums = chains(run_pass(DOMAIN_PASS_SUMMARY))
-        fwd = {k: domain_forward_carries([v for _, v in ch], domain_rules[k[1]][2], domain_max_gap) for k, ch in sums.items()}
-        mine_of = lambda k: [r for r, _ in sums[k]].index(rank)  # noqa: E731  this rank's place in the chain of pieces k
-        carry = {k: fwd[k][mine_of(k)] for k in pieces if sums[k][mine_of(k)][1]["n_rows"]}
-        codes = chains(run_pass(DOMAIN_PASS_CODES, carry))
-        bwd = {k: domain_backward_carries([v for _, v in sums[k]], [v for _, v in ch], domain_rules[k[1]][2], domain_max_gap)
-               for k, ch in codes.items()}
-        carry = {k: {**f, **bwd[k][mine_of(k)]} for k, f in carry.items()}
-        segs = chains(run_pass(DOMAIN_PASS_SEGMENTS, carry))
+        def segment_carries():
+            """passes S and C under domain_rules with the two walks -> the carry of every piece of this rank that has rows"""
+            sums = chains(run_pass(DOMAIN_PASS_SUMMARY))
+            fwd = {k: domain_forward_carries([v for _, v in ch], domain_rules[k[1]][2], domain_max_gap) for k, ch in sums.items()}
+            mine_of = lambda k: [r for r, _ in sums[k]].index(rank)  # noqa: E731  this rank's place in the chain of pieces k
+            carry = {k: fwd[k][mine_of(k)] for k in pieces if sums[k][mine_of(k)][1]["n_rows"]}
+            codes = chains(run_pass(DOMAIN_PASS_CODES, carry))
+            bwd = {k: domain_backward_carries([v for _, v in sums[k]], [v for _, v in ch], domain_rules[k[1]][2], domain_max_gap)
+                   for k, ch in codes.items()}
+            return {k: {**f, **bwd[k][mine_of(k)]} for k, f in carry.items()}
+
+        if domain_fit is not None:                           # -Y: every rank walks the same iteration, only the sums travel
+            every_piece, domain_rules = pieces, list(domain_rules)
+            fits = [None if lv is None else DomainFit(*lv, domain_fit["penalty"], domain_fit["max_iter"]) for lv in domain_fit["levels"]]
+            while any(f is not None and f.status is None for f in fits):
+                active = [f is not None and f.status is None for f in fits]
+                pieces = {k: v for k, v in every_piece.items() if active[k[1]]}
+                for c in range(3):
+                    if active[c]:
+                        domain_rules[c] = fits[c].rule
+                carry = segment_carries()
+                mine = np.zeros((3, 6), np.int64)
+                for k, cr in carry.items():
+                    mine[k[1]] += np.array(pu.domain_sums(k[1], *pieces[k], *domain_rules[k[1]], domain_max_gap, planes=(pc, nc, key),
+                                                          plane_base=base, carry=cr), np.int64)
+                total = allreduce_i64(mine).astype(np.int64)
+                for c in range(3):
+                    if active[c]:
+                        fits[c].step(total[c])
+            pieces = every_piece
+            for c in range(3):
+                if fits[c] is not None:
+                    domain_rules[c] = fits[c].rule
+            if rank == 0:
+                with open(f"{prefix}.domains.fit.tsv", "w") as f:
+                    f.write(domains_fit_tsv([None if x is None else (x.lo, x.hi, x.status, x.history) for x in fits]))
+        segs = chains(run_pass(DOMAIN_PASS_SEGMENTS, segment_carries()))
         if rank == 0:
             for c in range(3):
                 with open(f"{prefix}.domains.{CTX_NAMES[c]}.bed", "w") as f:
@@ -297,6 +330,9 @@ def main(argv=None):
                          "of a pair: that context is not segmented (default 0.1:0.8,0.05:0.5,0.02:0.2)")
     ap.add_argument("-x", dest="domain_penalty", type=float, default=None, help="with -D: penalty of a change of state in nats, in [0, 256] (default 8)")
     ap.add_argument("-j", dest="domain_max_gap", type=int, default=None, help="with -D: largest distance between two loci that still links them, >= 1 (default 1000)")
+    ap.add_argument("-Y", dest="domain_fit", type=int, default=None, metavar="N",
+                    help="with -D: fit the two levels of every segmented context from the data, starting from -u, at most N iterations "
+                         "-> also <prefix>.domains.fit.tsv")
     ap.add_argument("reference")
     ap.add_argument("mod_bam")
     ap.add_argument("output_prefix")
@@ -327,7 +363,11 @@ def main(argv=None):
             ap.error(f"-e: {e}")
     if not a.domains and not (a.domain_levels is None and a.domain_penalty is None and a.domain_max_gap is None):
         ap.error("-u, -x and -j need -D")
-    domain_rules = None
+    if a.domain_fit is not None and not a.domains:
+        ap.error("-Y needs -D")
+    if a.domain_fit is not None and a.domain_fit < 1:
+        ap.error("-Y takes the largest number of iterations, an integer >= 1")
+    domain_rules = domain_fit = None
     if a.domains:
         bad = "-u takes lo:hi with 0 < lo < hi < 1 (levels a 2^24-th of a nat apart at least) or nan, once or per context; " \
               "-x must be in [0, 256], -j an integer >= 1"
@@ -337,13 +377,16 @@ def main(argv=None):
         try:
             levels = list(DOMAIN_LEVELS) if a.domain_levels is None else parse_domain_levels(a.domain_levels)
             domain_rules = [None if lv is None else domain_scores(*lv, penalty) for lv in levels]
+            if a.domain_fit is not None:
+                domain_fit = {"levels": levels, "penalty": penalty, "max_iter": a.domain_fit}
         except (ValueError, HifimethError):
             ap.error(bad)
     return run(a.reference, a.mod_bam, a.output_prefix, a.q, a.f, slab=a.slab, backend=a.backend, haplotypes=a.haplotypes,
                asm=a.asm, asm_min_cov=5 if a.asm_min_cov is None else a.asm_min_cov, control=a.control, rates=rates,
                asm_q=a.asm_q, asm_regions=a.asm_regions, max_p=0.01 if a.max_p is None else a.max_p,
                max_gap=500 if a.max_gap is None else a.max_gap, min_loci=3 if a.min_loci is None else a.min_loci,
-               domain_rules=domain_rules, domain_max_gap=DOMAIN_MAX_GAP if a.domain_max_gap is None else a.domain_max_gap)
+               domain_rules=domain_rules, domain_max_gap=DOMAIN_MAX_GAP if a.domain_max_gap is None else a.domain_max_gap,
+               domain_fit=domain_fit)
 
 
 if __name__ == "__main__":

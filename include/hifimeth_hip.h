@@ -528,6 +528,40 @@ int64_t hm_pileup_fetch_domains_part(hm_pileup_t* p, const void* pcov, const voi
  * penalty >= 0 and the results lie in hm_pileup_fetch_domains' ranges. */
 int hm_domain_scores(double level_lo, double level_hi, double penalty, int64_t* A, int64_t* B, int64_t* S);
 
+/* ---- the two levels fitted from the data (`pileup -D -Y`): hard EM (Viterbi training) ---------------------
+ * Fix a context c, penalty, max_gap, starting levels (l_0, h_0) and max_iter >= 1.  A CHAIN is one sequence of the reference: one
+ * [lo, hi) of hm_pileup_fetch_domains.  Iteration i = 0, 1, ...:
+ *   1. (A_i, B_i, S) = hm_domain_scores(l_i, h_i, penalty).  An error ends the fit with status `degenerate` and iteration i - 1's
+ *      levels; for i = 0 it is the caller's error.
+ *   2. STATE SUMS (P0, N0, R0, P1, N1, R1): over all rows of context c in all chains the exact int64 sums of the unclamped pcov
+ *      and ncov and the number of rows, by the row's state z_t.  Rows and z_t are those of hm_pileup_fetch_domains under
+ *      (A_i, B_i, S, max_gap); every chain starts from delta = (0, 0) and decides its own end state.
+ *   3. REFIT (hm_domain_refit).  R0 == 0 or R1 == 0: status `one_state`, result (l_i, h_i).  Otherwise
+ *      l' = clamp((double)P0 / (double)(P0 + N0)), h' = clamp((double)P1 / (double)(P1 + N1)): one correctly rounded division
+ *      each, then the clamp to [1e-6, 1 - 1e-6].  If !(l' < h') or hm_domain_scores(l', h', penalty) fails: status `degenerate`,
+ *      result (l_i, h_i).
+ *   4. STOP RULE, with (A', B') the scores of (l', h').  (A', B') == (A_i, B_i): status `converged`, result (l_i, h_i) -- the
+ *      segmentation that produced the levels is the one that is written.  (A', B') == (A_j, B_j) for a j < i: status `cycle`; the
+ *      members of the cycle are the iterations j .. i, j taken with the levels (l', h') that closed it (they have its scores), and
+ *      the result is the member with the smallest (A, B) in lexicographic order: it depends on the cycle alone, not on where it
+ *      was entered.  i + 1 == max_iter: status `max_iter`, result (l', h').  Otherwise (l_{i+1}, h_{i+1}) = (l', h').
+ * The result goes through hm_domain_scores once more and the segments are written with it.  The sums are an integer function of
+ * the planes and (A_i, B_i, S, max_gap), and the levels a function of the sums: the fit depends neither on launch geometry nor
+ * on how the planes are cut into pieces.
+ *
+ * sums[6] = P0, N0, R0, P1, N1, R1 of context ctx in planes[lo, hi); returns R = R0 + R1, or < 0.  Arguments and errors as
+ * hm_pileup_fetch_domains; HM_EINVAL for sums NULL.  No segment is built and only the sums come back from the device. */
+int64_t hm_pileup_domain_sums(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t plane_base, int64_t lo,
+                              int64_t hi, int32_t ctx, int64_t A, int64_t B, int64_t S, int64_t max_gap, int64_t sums[6]);
+/* The same for a PIECE: `part` filled as for HM_DOMAIN_PASS_SEGMENTS (has_prev, prev_gpos, prev_d, has_next, next_gpos,
+ * last_state) and only read.  The sums of the pieces of a chain add up to the chain's.  Errors as hm_pileup_fetch_domains_part. */
+int64_t hm_pileup_domain_sums_part(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t plane_base,
+                                   int64_t lo, int64_t hi, int32_t ctx, int64_t A, int64_t B, int64_t S, int64_t max_gap,
+                                   const hm_domain_part_t* part, int64_t sums[6]);
+/* Host only.  Step 3 above: HM_OK and the new levels; HM_EDATA, the levels untouched, where the step ends the fit (`one_state`
+ * if R0 == 0 or R1 == 0, else `degenerate`); HM_EINVAL for a NULL, a negative sum or a penalty that is not >= 0. */
+int hm_domain_refit(const int64_t sums[6], double penalty, double* level_lo, double* level_hi);
+
 #ifdef __cplusplus
 }
 #endif

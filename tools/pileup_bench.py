@@ -12,9 +12,11 @@ fetch then also compacts the two partitions' planes.
 `--asm-regions` (with `--asm`): the regions of `pileup -H -A -G`: per context, select + test + chain + D2H of the region rows per pass.
 `--sites`: the binomial test of `pileup -B / -e` over the counted planes: histogram + table + rows (D2H included) per pass.
 `--domains`: the segmentation of `pileup -D` over the counted planes: per context, select + two scans + heads + D2H of the segments per pass.
+`--fit` (with `--domains`): one state-sums pass (`pileup -D -Y`: select + two scans + one reduction, 48 bytes back) next to one fetch of the
+segments over the same planes, and the fit of the three contexts from the default levels: iterations, status, seconds.
 `--parts N` (with `--domains`): the same segments chained from N equal pieces next to the single fetch (three stateless passes per piece).
 
-    python tools/pileup_bench.py --genome-mb 20 --coverage 10 [--partitions [--asm [--asm-q] [--asm-regions]]] [--sites] [--domains [--parts N]]
+    python tools/pileup_bench.py --genome-mb 20 --coverage 10 [--partitions [--asm [--asm-q] [--asm-regions]]] [--sites] [--domains [--fit] [--parts N]]
 """
 import argparse
 import ctypes as C
@@ -99,6 +101,9 @@ def main():
     ap.add_argument("--sites", action="store_true", help="time the per-locus binomial test (pileup -B / -e)")
     ap.add_argument("--sites-rate", type=float, default=0.013, help="with --sites: the false-positive rate of all three contexts")
     ap.add_argument("--domains", action="store_true", help="time the low / high segmentation of the covered loci (pileup -D, its default weights)")
+    ap.add_argument("--fit", action="store_true",
+                    help="with --domains: also one state-sums pass (hm_pileup_domain_sums) next to one fetch, and the fit of the levels (pileup -D -Y)")
+    ap.add_argument("--fit-iter", type=int, default=50, help="with --fit: the largest number of iterations per context")
     ap.add_argument("--parts", type=int, default=0, metavar="N",
                     help="with --domains: also the same segments chained from N equal pieces (hm_pileup_fetch_domains_part, what pileup_dist -D runs)")
     ap.add_argument("--cpu-baseline", action="store_true",
@@ -281,6 +286,28 @@ def main():
                    domains_longest=int(max((int(r["n_loci"].max()) for r, _n in found if len(r)), default=0)),
                    domains_s_per_pass=round(t_dom, 4), domains_rows_per_s=round(ctx_rows / t_dom) if t_dom else 0,
                    domains_share_of_pass=round(t_dom / (t_pass + t_dom), 4))
+        if a.fit:                                  # the sums pass the fit repeats, and the fit itself from the default levels
+            from hifimeth_amd.pileup import DOMAIN_LEVELS, DOMAIN_MAX_GAP, DOMAIN_PENALTY
+
+            def sums_pass():
+                return [pu.domain_sums(c) for c in range(3)]
+
+            sums_pass()
+            t0 = time.perf_counter()
+            for _ in range(a.repeat):
+                state_sums = sums_pass()
+            t_sums = (time.perf_counter() - t0) / a.repeat
+            t0 = time.perf_counter()
+            fits = [pu.fit_domain_levels(c, *DOMAIN_LEVELS[c], DOMAIN_PENALTY, DOMAIN_MAX_GAP, a.fit_iter) for c in range(3)]
+            t_fit = time.perf_counter() - t0
+            out.update(domains_sums_s_per_pass=round(t_sums, 4), domains_sums_rows_per_s=round(ctx_rows / t_sums) if t_sums else 0,
+                       domains_sums_over_fetch=round(t_sums / t_dom, 3) if t_dom else 0, domains_fit_s=round(t_fit, 4),
+                       domains_fit_iterations=[len(f[3]) for f in fits], domains_fit_status=[f[2] for f in fits],
+                       domains_fit_levels=[[float("%.6g" % f[0]), float("%.6g" % f[1])] for f in fits])
+            if a.check:                            # the sums are those of the fetched segments, state by state
+                out["check_domains_sums_equal_the_segments"] = bool(all(
+                    s == tuple(int(r[f][r["state"] == z].sum()) for z in (0, 1) for f in ("pcov", "ncov", "n_loci"))
+                    for s, (r, _n) in zip(state_sums, found)))
         if a.parts:                                # the same segments from a.parts equal pieces: three stateless passes each, chained
             from functools import partial
 
