@@ -142,6 +142,9 @@ def lib():
         "hm_pileup_domain_sums": (i64, [vp, vp, vp, vp, i64, i64, i64, i32, i64, i64, i64, i64, C.POINTER(i64)]),
         "hm_pileup_domain_sums_part": (i64, [vp, vp, vp, vp, i64, i64, i64, i32, i64, i64, i64, i64, vp, C.POINTER(i64)]),
         "hm_domain_refit": (C.c_int, [C.POINTER(i64), C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "hm_pileup_num_pattern_records": (i64, [vp]),
+        "hm_pileup_fetch_patterns": (i64, [vp, i64, i64, i64, vp, i64]),
+        "hm_pattern_stats": (C.c_int, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

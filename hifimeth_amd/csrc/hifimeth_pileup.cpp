@@ -104,6 +104,10 @@ struct PileupOptions {
     bool domain_option_given = false, domain_option_bad = false;  // any of -u -x -j; one of them with a value out of range
     long long domain_fit_iter = 0;     // -Y: fit the two levels from the data, at most this many iterations; 0: not asked for
     bool domain_fit_bad = false;
+    int patterns = 0;                  // -E: read-level patterns over windows of k adjacent reference CpGs -> <prefix>.patterns.CpG.bed
+    long long pattern_span = 150;      // -w: largest distance between the first and the last locus of a window
+    long long pattern_min_reads = 10;  // -o: smallest number of reads spanning a window that is written
+    bool pattern_option_given = false, pattern_option_bad = false;  // -w or -o; -E, -w or -o with a value out of range
     // -K: call on the fly; the options below are `call`'s (hifimeth_call.cpp), same meaning and defaults
     bool kinetics = false;
     bool call_option_given = false;  // any of -m -c -l -p -T: a usage error without -K
@@ -159,6 +163,13 @@ void pileup_usage(const char* exe) {
             "    state's pooled methylation level as its new level, at most n times (hard EM; it stops when the integer weights repeat).\n"
             "    Also writes <prefix>.domains.fit.tsv: per context and iteration ctx, iter, lo, hi, A, B, P0, N0, R0, P1, N1, R1, then\n"
             "    ctx, status, lo, hi -- the fitted levels, which -u takes back\n"
+            "  -E <2|3|4>\n    Read-level CpG patterns: every reference CpG heads a window of k adjacent reference CpGs; a read with a call at all\n"
+            "    k of them counts under its pattern (bit i set: the i-th call is methylated; a deletion, mismatch or missing call at any\n"
+            "    of the loci and the read does not count).  Writes <prefix>.patterns.CpG.bed: chrom, start, end, reads, methylation entropy\n"
+            "    (bits per CpG), epipolymorphism, proportion of discordant reads, methylation level of those reads in %%, the 2^k counts by\n"
+            "    pattern.  The combined reads are counted, with or without -H\n"
+            "  -w <bp>\n    With -E: largest distance between the first and the last CpG of a window, in [1, 65536]\n    Default: 150\n"
+            "  -o <int>\n    With -E: smallest number of reads spanning a window that is written, >= 1\n    Default: 10\n"
             "  -K\n    The input is an aligned BAM that carries the kinetics tags fi / fp / ri / rp instead of MM / ML: call 5mC on the\n"
             "    fly and pile the calls up directly.  For equal -c -l -p -T -q -f the output files are byte-identical to those of\n"
             "    `%s call` on that BAM followed by `%s pileup` on its output; no mod-BAM is written.  (Give -T explicitly\n"
@@ -777,6 +788,11 @@ namespace {
 template <class Row>
 int64_t row_pos(const Row& r) { return r.gpos; }
 inline int64_t row_pos(const hm_domain_t& r) { return r.start; }
+inline int64_t row_pos(const hm_pattern_t& r) { return r.start; }
+// ... and the context whose file it goes to
+template <class Row>
+uint32_t row_ctx(const Row& r) { return r.motif < 3 ? r.motif : 2; }
+inline uint32_t row_ctx(const hm_pattern_t&) { return 0; }
 
 // The three files <prefix>.<tag><ctx>.<suffix> of one output, closed when their owner goes.
 struct CtxFiles {
@@ -828,7 +844,7 @@ bool write_rows(const Fasta& fa, FILE* const out[3], int threads, Fetch fetch, F
             for (size_t i = a; i < b; ++i) {
                 const Row& r = rows[i];
                 const int len = format(r, row_pos(r) - lo, buf);
-                std::string& t = text[(size_t)w * 3 + (r.motif < 3 ? r.motif : 2)];
+                std::string& t = text[(size_t)w * 3 + row_ctx(r)];
                 t += fa.names[s];
                 t.append(buf, (size_t)len);
             }
@@ -897,6 +913,23 @@ bool write_asm_regions(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o,
         }
     }
     return true;
+}
+
+// rows of <prefix>.patterns.CpG.bed (out[0]; a window never crosses a sequence): the statistics are hm_pattern_stats'.  false on an
+// engine error.
+bool write_patterns(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, FILE* out[3]) {
+    return write_rows<hm_pattern_t>(
+        fa, out, o.threads,
+        [&](int64_t lo, int64_t hi, hm_pattern_t* dst, int64_t cap) { return hm_pileup_fetch_patterns(pe, lo, hi, o.pattern_min_reads, dst, cap); },
+        [](const hm_pattern_t& r, int64_t k, char (&buf)[320]) {
+            double st[4] = {0, 0, 0, 0};
+            hm_pattern_stats(&r, st);
+            int len = snprintf(buf, sizeof buf, "\t%lld\t%lld\t%u\t%.6g\t%.6g\t%.6g\t%.6g", (long long)k, (long long)(k + (r.end - r.start)), r.n,
+                               st[0], st[1], st[2], st[3]);
+            for (uint32_t b = 0; b < (1u << r.k); ++b) len += snprintf(buf + len, sizeof buf - (size_t)len, "%c%u", b ? ',' : '\t', r.counts[b]);
+            len += snprintf(buf + len, sizeof buf - (size_t)len, "\n");
+            return len;
+        });
 }
 
 // -u: one lo:hi pair for all contexts or three, each pair possibly nan; false unless the whole text parses
@@ -1325,6 +1358,17 @@ int cmd_pileup(int argc, char** argv) {
                 if (end == v || *end || errno || o.domain_max_gap < 1) o.domain_option_bad = true;
             }
         }
+        else if (a == "-E" || a == "-w" || a == "-o") {  // the whole value must parse, and lie in the option's range
+            if (a != "-E") o.pattern_option_given = true;
+            const char* v = argv[++i];
+            char* end = nullptr;
+            errno = 0;
+            const long long x = strtoll(v, &end, 10);
+            if (end == v || *end || errno) o.pattern_option_bad = true;
+            else if (a == "-E") { if (x < 2 || x > 4) o.pattern_option_bad = true; else o.patterns = (int)x; }
+            else if (a == "-w") { if (x < 1 || x > 65536) o.pattern_option_bad = true; else o.pattern_span = x; }
+            else { if (x < 1) o.pattern_option_bad = true; else o.pattern_min_reads = x; }
+        }
         else if (a == "-Y") {
             const char* v = argv[++i];
             char* end = nullptr;
@@ -1378,6 +1422,9 @@ int cmd_pileup(int argc, char** argv) {
                               : o.domain_option_bad ? "-u takes lo:hi with 0 < lo < hi < 1 (levels a 2^24-th of a nat apart at least) or nan, once or per context; "
                                                       "-x must be in [0, 256], -j an integer >= 1" : nullptr;
     if (bad_domains) { fprintf(stderr, "ERROR: %s\n", bad_domains); pileup_usage(argv[0]); return EXIT_FAILURE; }
+    const char* bad_patterns = o.pattern_option_bad ? "-E must be 2, 3 or 4, -w an integer in [1, 65536], -o an integer >= 1"
+                               : o.pattern_option_given && !o.patterns ? "-w and -o need -E" : nullptr;
+    if (bad_patterns) { fprintf(stderr, "ERROR: %s\n", bad_patterns); pileup_usage(argv[0]); return EXIT_FAILURE; }
     const bool sites = !o.control.empty() || o.rates_given;
     if (o.kinetics && o.model_dir.empty()) o.model_dir = exe_dir() + "/../weights";
     o.ref = argv[i];
@@ -1406,6 +1453,9 @@ int cmd_pileup(int argc, char** argv) {
         if (o.domain_fit_iter)
             fprintf(stderr, "domains: the levels are fitted from the data, %lld iterations at most -> %s.domains.fit.tsv\n", o.domain_fit_iter, o.prefix.c_str());
     }
+    if (o.patterns)
+        fprintf(stderr, "patterns: windows of %d reference CpGs within %lld bases, spanned by >= %lld reads -> %s.patterns.CpG.bed\n", o.patterns,
+                o.pattern_span, o.pattern_min_reads, o.prefix.c_str());
     if (o.kinetics)
         fprintf(stderr, "kinetics: called on the fly (models %s, contexts%s%s%s, min read length %d, precision %d, trunk %s)\n", o.model_dir.c_str(),
                 o.ctx_mask & 1 ? " CpG" : "", o.ctx_mask & 2 ? " CHG" : "", o.ctx_mask & 4 ? " CHH" : "", o.min_read_size, o.precision,
@@ -1439,6 +1489,8 @@ int cmd_pileup(int argc, char** argv) {
     hm_pileup_set_option(pe, "min_mapq", o.min_mapq);
     hm_pileup_set_option(pe, "min_pi", o.min_pi);
     if (o.haplotypes && hm_pileup_set_option(pe, "partitions", 2) != HM_OK) return die("partitions");
+    if (o.patterns && (hm_pileup_set_option(pe, "patterns", o.patterns) != HM_OK || hm_pileup_set_option(pe, "pattern_span", (double)o.pattern_span) != HM_OK))
+        return die("patterns");
     if (fa.names.empty()) { fprintf(stderr, "ERROR: no sequence in %s\n", o.ref.c_str()); return EXIT_FAILURE; }
     if (hm_pileup_set_reference(pe, (int32_t)fa.names.size(), fa.length.data(), fa.bases.data()) != HM_OK) return die("reference");
 
@@ -1576,6 +1628,13 @@ int cmd_pileup(int argc, char** argv) {
         CtxFiles out;
         if (!out.open(o.prefix, "domains.", ".bed")) return EXIT_FAILURE;
         if (!write_domains(pe, fa, o, dom_A, dom_B, dom_S, out.f)) return die("domains");
+    }
+    if (o.patterns) {
+        FILE* out[3] = {fopen((o.prefix + ".patterns.CpG.bed").c_str(), "w"), nullptr, nullptr};
+        if (!out[0]) { fprintf(stderr, "ERROR: cannot open %s.patterns.CpG.bed for writing\n", o.prefix.c_str()); return EXIT_FAILURE; }
+        const bool ok = write_patterns(pe, fa, o, out);
+        fclose(out[0]);
+        if (!ok) return die("patterns");
     }
     if (sites) {
         const int rc = write_sites(pe, fa, o, control_sid, o.threads);

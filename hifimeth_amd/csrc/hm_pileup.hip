@@ -19,6 +19,9 @@
 //   project_kernel  thread per column      : motif tests, plane lookup, wave-aggregated append of 12-byte records
 //   count_kernel    thread per record      : atomic add into pcov / ncov, atomic max into the motif key
 //   count_hp_kernel the same + one more atomic add into the record's haplotype planes (partitions = 2 only)
+//   pattern_kernel  thread per column      : (`pileup -E`) a CpG member that heads a window of k reference CpGs looks the other
+//                   k - 1 up in the read's following runs and appends one 8-byte window record; pattern_count_kernel adds
+//                   the records into 16 bins per reference CpG; RefCpgSel lists the reference CpGs, PatSel the rows
 //   select_count / loci_scan / select_write   the rows of a SELECTION over a range in ascending order (count per block, scan,
 //                   write); every output below is a selection struct (its planes, pred, take) plus per-row kernels
 //   LociSel         covered loci
@@ -205,7 +208,8 @@ __global__ __launch_bounds__(TPB) void identity_kernel(const PRun* __restrict__ 
 }
 
 // append one record per lane with `pred` to the workgroup's LDS stage: one LDS atomic per wavefront
-__device__ __forceinline__ void stage_record(bool pred, const PRec& rec, PRec* __restrict__ stage, int* __restrict__ n_stage) {
+template <class Rec>
+__device__ __forceinline__ void stage_record(bool pred, const Rec& rec, Rec* __restrict__ stage, int* __restrict__ n_stage) {
     const unsigned long long b = __ballot(pred);
     if (!b) return;
     const int lane = threadIdx.x & 63;
@@ -456,6 +460,184 @@ struct LociSel {
         l.ncov = n;
         l.motif = s.ky[i] & 3u;
         l.reserved = 0;
+        return true;
+    }
+};
+
+// ---- read-level CpG patterns (`pileup -E`; include/hifimeth_hip.h has the definition) ----------------------------------------
+constexpr int PAT_MAX_SPAN = 65536;
+
+struct PWin {            // 8 bytes: a record that is a member at all k loci of the window headed by reference CpG `rank`
+    uint32_t rank;
+    uint8_t prob[4];     // by locus, leftmost first; beyond k: 0
+};
+static_assert(sizeof(PWin) == 8, "window records move as two dwords");
+
+// end of the reference sequence that holds locus g: seq_off[s + 1] for the largest s with seq_off[s] <= g
+__device__ __forceinline__ int64_t seq_end_of(const int64_t* __restrict__ seq_off, int n_seqs, int64_t g) {
+    int lo = 0, hi = n_seqs;  // seq_off[lo] <= g < seq_off[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (seq_off[mid] <= g) lo = mid; else hi = mid;
+    }
+    return seq_off[hi];
+}
+
+// first index in a[0, n) with a[i] >= g
+__device__ __forceinline__ int64_t lower_rank(const int64_t* __restrict__ a, int64_t n, int64_t g) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (a[mid] < g) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// the reference CpGs over [0, total): C and G of one sequence (the pair that straddles two sequences is none)
+struct RefCpgSel {
+    using Row = int64_t;
+    const char* ref;
+    const int64_t* seq_off;
+    int n_seqs;
+    int64_t total;
+    __device__ bool pred(int64_t i) const {
+        return i + 1 < total && ref[i] == 'C' && ref[i + 1] == 'G' && i + 1 < seq_end_of(seq_off, n_seqs, i);
+    }
+    __device__ bool take(int64_t i, Row& g) const {
+        g = i;
+        return pred(i);
+    }
+};
+
+// what a window is made of, for the kernels and the selection below
+struct PatRule {
+    const int64_t* cpg_pos;  // the reference CpGs, ascending
+    int64_t n_cpg;
+    const int64_t* seq_off;
+    int n_seqs;
+    int k, max_span;
+    // window r exists: k loci of one sequence within max_span
+    __device__ bool valid(int64_t r) const {
+        if (r + k - 1 >= n_cpg) return false;
+        const int64_t first = cpg_pos[r], last = cpg_pos[r + k - 1];
+        return last - first <= max_span && last < seq_end_of(seq_off, n_seqs, first);
+    }
+};
+
+// One thread per aligned column, project_kernel's geometry.  A column that is a CpG member (project_kernel's motif-0 test) and
+// whose locus heads a valid window walks the read's runs forward to the other k - 1 loci and applies the member test there; a read
+// that is a member at all of them leaves one PWin.  The walk ends within max_span <= PAT_MAX_SPAN reference bases.
+__global__ __launch_bounds__(TPB) void pattern_kernel(const PRun* __restrict__ runs, const int64_t* __restrict__ col0, int n_runs,
+                                                       int64_t n_cols, const PRead* __restrict__ reads,
+                                                       const uint8_t* __restrict__ slab, const char* __restrict__ ref,
+                                                       const uint32_t* __restrict__ plane, const int32_t* __restrict__ matches,
+                                                       double min_pi, PatRule rule, PWin* __restrict__ out,
+                                                       unsigned long long* __restrict__ counter) {
+    __shared__ PWin stage[PTILE];  // a column heads at most one window
+    __shared__ int n_stage;
+    __shared__ int run_range[2];
+    __shared__ unsigned long long out_base;
+    if (threadIdx.x == 0) n_stage = 0;
+    if (threadIdx.x < 2) {
+        const int64_t c = min((int64_t)blockIdx.x * PTILE + (threadIdx.x ? PTILE - 1 : 0), n_cols - 1);
+        run_range[threadIdx.x] = find_run(col0, n_runs, c) + (int)threadIdx.x;
+    }
+    __syncthreads();
+    const int run_lo = run_range[0], run_hi = run_range[1];
+    for (int it = 0; it < PTILE / TPB; ++it) {
+        const int64_t c = (int64_t)blockIdx.x * PTILE + it * TPB + threadIdx.x;
+        bool e = false;
+        PWin w{};
+        if (c < n_cols) {
+            const int ri = find_run(col0, n_runs, c, run_lo, run_hi);
+            const PRun run = runs[ri];
+            const int o = (int)(c - col0[ri]);
+            const PRead rd = reads[run.read];
+            bool live = rd.pass && run.len - o >= 2;
+            if (live && min_pi > 0.0) live = !(100.0 * matches[run.read] / rd.as_size < min_pi);
+            // the member test at offset `off` of run `r`, whose two columns lie in the run: the call's ML byte, or -1
+            auto member = [&](const PRun& r, int off) -> int {
+                const int qp = r.q0 + off;
+                const int64_t g = r.g0 + off;
+                if (stored_base(slab, rd, qp) != 'C' || stored_base(slab, rd, qp + 1) != 'G' || ref[g] != 'C' || ref[g + 1] != 'G') return -1;
+                const uint32_t v = plane[rd.plane_off + (rd.rev ? rd.l_qseq - 1 - (qp + 1) : qp)];
+                return (v & 0x100u) ? (int)(v & 255u) : -1;
+            };
+            const int p0 = live ? member(run, o) : -1;
+            if (p0 >= 0) {
+                const int64_t g = run.g0 + o;
+                const int64_t r = lower_rank(rule.cpg_pos, rule.n_cpg, g);
+                if (r < rule.n_cpg && rule.cpg_pos[r] == g && rule.valid(r)) {
+                    w.rank = (uint32_t)r;
+                    w.prob[0] = (uint8_t)p0;
+                    e = true;
+                    int rj = ri;
+                    PRun cur = run;
+                    for (int i = 1; i < rule.k && e; ++i) {
+                        const int64_t gi = rule.cpg_pos[r + i];
+                        while (cur.g0 + cur.len <= gi) {  // the run that holds g_i, if one of this read's does
+                            if (++rj >= n_runs) { e = false; break; }
+                            cur = runs[rj];
+                            if (cur.read != run.read) { e = false; break; }
+                        }
+                        if (!e || cur.g0 > gi || cur.g0 + cur.len - gi < 2) { e = false; break; }
+                        const int pi = member(cur, (int)(gi - cur.g0));
+                        if (pi < 0) e = false;
+                        else w.prob[i] = (uint8_t)pi;
+                    }
+                }
+            }
+        }
+        stage_record(e, w, stage, &n_stage);
+    }
+    __syncthreads();
+    const int n = n_stage;
+    if (threadIdx.x == 0 && n) out_base = atomicAdd(counter, (unsigned long long)n);
+    __syncthreads();
+    if (n) {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(stage);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(out + out_base);
+        for (int i = threadIdx.x; i < 2 * n; i += TPB) dst[i] = src[i];
+    }
+}
+
+// hist[rank * 16 + pattern] += 1 per window record, bit i of the pattern = prob[i] >= thr: integer atomics, any order
+__global__ __launch_bounds__(TPB) void pattern_count_kernel(const PWin* __restrict__ wins, int64_t n, uint32_t thr, int k,
+                                                             uint32_t* __restrict__ hist) {
+    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
+        const PWin w = wins[i];
+        uint32_t pat = 0;
+        for (int j = 0; j < k; ++j) pat |= (w.prob[j] >= thr ? 1u : 0u) << j;
+        atomicAdd(&hist[(size_t)w.rank * 16 + pat], 1u);
+    }
+}
+
+// ranks[0], ranks[1] = the first reference CpG at or behind lo, hi: the windows whose first locus lies in [lo, hi)
+__global__ void pattern_ranks_kernel(const int64_t* __restrict__ cpg_pos, int64_t n_cpg, int64_t lo, int64_t hi, int64_t* __restrict__ ranks) {
+    if (threadIdx.x < 2) ranks[threadIdx.x] = lower_rank(cpg_pos, n_cpg, threadIdx.x ? hi : lo);
+}
+
+// the rows over RANKS: a valid window with at least min_reads contributing records
+struct PatSel {
+    using Row = hm_pattern_t;
+    PatRule rule;
+    const uint32_t* hist;
+    int64_t min_reads;
+    __device__ bool pred(int64_t r) const {
+        if (!rule.valid(r)) return false;
+        int64_t n = 0;
+        for (int b = 0; b < 16; ++b) n += hist[r * 16 + b];
+        return n >= min_reads;
+    }
+    __device__ bool take(int64_t r, Row& w) const {
+        if (!rule.valid(r)) return false;
+        int64_t n = 0;
+        for (int b = 0; b < 16; ++b) n += (w.counts[b] = hist[r * 16 + b]);
+        if (n < min_reads) return false;
+        w.start = rule.cpg_pos[r];
+        w.end = rule.cpg_pos[r + rule.k - 1] + 2;
+        w.n = (uint32_t)n;
+        w.k = (uint32_t)rule.k;
         return true;
     }
 };
@@ -1236,6 +1418,13 @@ struct hm_pileup {
     DevBuf d_drows{HALF}, d_dsums{HALF}, d_dcode{HALF}, d_dstate{HALF}, d_dagg{HALF}, d_dheads{HALF};
     DevBuf d_dlast{EXACT};  // hm_pileup_fetch_domains_part: the d of a piece's last row, 8 B
     DevBuf d_dstate_sums{EXACT};  // hm_pileup_domain_sums, allocated by its first call: the six state sums, 48 B
+    // `pileup -E` ("patterns" = k), all of it only with the option on: the sequence starts and the reference CpGs (8 B each) with
+    // their 16 bins (64 B each), resident from hm_pileup_set_reference on; the window records, which grow with the batches as
+    // d_recs does, and their counter; the two ranks that bound a fetch
+    int patterns = 0, pattern_span = 150;
+    DevBuf d_seqoff{EXACT}, d_cpg{EXACT}, d_phist{EXACT}, d_pcounter{EXACT}, d_pranks{EXACT}, d_precs{HALF};
+    int64_t n_cpg = 0, n_precs = 0;
+    bool patterns_counted = false;
     int64_t n_recs = 0;
     bool bins_ready = false;
 
@@ -1450,6 +1639,34 @@ void ensure_bins(hm_pileup* p) {
     p->bins_ready = true;
 }
 
+PatRule pattern_rule(const hm_pileup* p) {
+    return PatRule{p->d_cpg.as<int64_t>(), p->n_cpg, p->d_seqoff.as<int64_t>(), (int)p->seq_off.size() - 1, p->patterns, p->pattern_span};
+}
+
+// `pileup -E`, under hm_pileup_set_reference's guard once the bases are on their way: the sequence starts, the reference CpGs of
+// the whole reference through the selection skeleton (they stay on the device), their bins and the record counter zeroed
+int list_reference_cpgs(hm_pileup* p) {
+    const int n_seqs = (int)p->seq_off.size() - 1;
+    const int64_t total = p->seq_off.back();
+    p->d_seqoff.reserve(8 * p->seq_off.size());
+    HIP_TRY(hipMemcpyAsync(p->d_seqoff.p, p->seq_off.data(), 8 * p->seq_off.size(), hipMemcpyHostToDevice, p->stream));
+    p->d_pcounter.reserve(sizeof(unsigned long long));
+    p->d_pranks.reserve(16);
+    HIP_TRY(hipMemsetAsync(p->d_pcounter.p, 0, sizeof(unsigned long long), p->stream));
+    p->n_cpg = p->n_precs = 0;
+    p->patterns_counted = false;
+    if (total >= 2) {
+        const int64_t n = stage_rows(p, RefCpgSel{p->d_ref.as<char>(), p->d_seqoff.as<int64_t>(), n_seqs, total}, 0, total, p->d_cpg,
+                                     [](int64_t) { return true; }, no_hook);
+        if (n < 0) return (int)n;
+        if (n >= (int64_t(1) << 32)) return pfail(p, HM_EINVAL, "patterns: 2^32 reference CpGs or more");
+        p->n_cpg = n;
+    }
+    p->d_phist.reserve(64 * (size_t)std::max<int64_t>(p->n_cpg, 1));
+    HIP_TRY(hipMemsetAsync(p->d_phist.p, 0, 64 * (size_t)std::max<int64_t>(p->n_cpg, 1), p->stream));
+    return HM_OK;
+}
+
 void clear_batch(hm_pileup* p) {
     p->slab.clear();
     p->reads.clear();
@@ -1598,6 +1815,16 @@ int hm_pileup_set_option(hm_pileup_t* p, const char* key, double value) {
             return pfail(p, HM_ESTATE, "partitions must be set before hm_pileup_set_reference / hm_pileup_use_planes");
         if (value != 0.0 && value != 2.0) return pfail(p, HM_EINVAL, "partitions must be 0 or 2");
         p->partitions = (int)value;
+    } else if (k == "patterns" || k == "pattern_span") {  // the reference CpGs are listed when the reference arrives
+        if (!p->seq_off.empty()) return pfail(p, HM_ESTATE, k + " must be set before hm_pileup_set_reference");
+        if (k == "patterns") {
+            if (value != 0.0 && value != 2.0 && value != 3.0 && value != 4.0) return pfail(p, HM_EINVAL, "patterns must be 0, 2, 3 or 4");
+            p->patterns = (int)value;
+        } else {
+            if (!(value >= 1.0 && value <= (double)PAT_MAX_SPAN) || value != std::floor(value))
+                return pfail(p, HM_EINVAL, "pattern_span must be an integer in 1 .. 65536");
+            p->pattern_span = (int)value;
+        }
     } else return pfail(p, HM_EINVAL, "unknown option " + k);
     return HM_OK;
 }
@@ -1663,6 +1890,10 @@ int hm_pileup_set_reference(hm_pileup_t* p, int32_t n_seqs, const int64_t* seq_l
                 HIP_TRY(hipMemsetAsync(p->hp_pcov[k], 0, bytes, p->stream));
                 HIP_TRY(hipMemsetAsync(p->hp_ncov[k], 0, bytes, p->stream));
             }
+        }
+        if (p->patterns) {
+            const int rc = list_reference_cpgs(p);
+            if (rc != HM_OK) return rc;
         }
         HIP_TRY(hipStreamSynchronize(p->stream));
         return HM_OK;
@@ -1766,6 +1997,8 @@ int hm_pileup_run(hm_pileup_t* p) {
         p->d_plane.reserve(4 * (size_t)std::max<int64_t>(p->plane_len, 1));
         p->d_matches.reserve(4 * (size_t)n_reads);
         p->d_recs.reserve(sizeof(PRec) * (size_t)(p->n_recs + p->n_m_mods + 1), sizeof(PRec) * (size_t)p->n_recs, st);
+        if (p->patterns)  // a window record has a member at its head, a member a 5mC entry of its own
+            p->d_precs.reserve(sizeof(PWin) * (size_t)(p->n_precs + p->n_m_mods + 1), sizeof(PWin) * (size_t)p->n_precs, st);
 
         HIP_TRY(hipMemcpyAsync(p->d_slab.p, p->slab.data(), p->slab.size(), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(p->d_reads.p, p->reads.data(), sizeof(PRead) * (size_t)n_reads, hipMemcpyHostToDevice, st));
@@ -1795,12 +2028,19 @@ int hm_pileup_run(hm_pileup_t* p) {
                                p->d_col0.as<int64_t>(), n_runs, cols, p->d_reads.as<PRead>(), p->d_slab.as<uint8_t>(),
                                p->d_ref.as<char>(), p->d_plane.as<uint32_t>(), p->d_matches.as<int32_t>(), p->min_pi,
                                p->d_recs.as<PRec>(), p->d_counter.as<unsigned long long>());
+            if (p->patterns && p->n_cpg)
+                hipLaunchKernelGGL(pattern_kernel, dim3((unsigned)pblocks), dim3(TPB), 0, st, p->d_runs.as<PRun>(), p->d_col0.as<int64_t>(),
+                                   n_runs, cols, p->d_reads.as<PRead>(), p->d_slab.as<uint8_t>(), p->d_ref.as<char>(),
+                                   p->d_plane.as<uint32_t>(), p->d_matches.as<int32_t>(), p->min_pi, pattern_rule(p), p->d_precs.as<PWin>(),
+                                   p->d_pcounter.as<unsigned long long>());
         }
         HIP_TRY(hipGetLastError());
-        unsigned long long n = 0;
+        unsigned long long n = 0, n_win = 0;
         HIP_TRY(hipMemcpyAsync(&n, p->d_counter.p, sizeof n, hipMemcpyDeviceToHost, st));
+        if (p->patterns) HIP_TRY(hipMemcpyAsync(&n_win, p->d_pcounter.p, sizeof n_win, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         p->n_recs = (int64_t)n;
+        p->n_precs = (int64_t)n_win;
         clear_batch(p);
         return HM_OK;
     });
@@ -1875,9 +2115,17 @@ int hm_pileup_count(hm_pileup_t* p, const uint8_t thr[3]) {
                                    p->n_recs, packed, p->pcov, p->ncov, p->key);
             HIP_TRY(hipGetLastError());
         }
+        if (p->patterns && p->n_precs) {  // <= 1024 workgroups: every record is one fire-and-forget atomic
+            hipLaunchKernelGGL(pattern_count_kernel, dim3(grid_for(p->n_precs, 1024)), dim3(TPB), 0, p->stream, p->d_precs.as<PWin>(),
+                               p->n_precs, (uint32_t)thr[0], p->patterns, p->d_phist.as<uint32_t>());
+            HIP_TRY(hipGetLastError());
+        }
+        if (p->patterns) HIP_TRY(hipMemsetAsync(p->d_pcounter.p, 0, sizeof(unsigned long long), p->stream));
         HIP_TRY(hipMemsetAsync(p->d_counter.p, 0, sizeof(unsigned long long), p->stream));
         HIP_TRY(hipStreamSynchronize(p->stream));
         p->n_recs = 0;
+        p->n_precs = 0;
+        p->patterns_counted = p->patterns != 0;
         return HM_OK;
     });
 }
@@ -1889,6 +2137,53 @@ int64_t hm_pileup_fetch_loci(hm_pileup_t* p, const void* pcov, const void* ncov,
     if (!range_planes(p, pcov, ncov, key, plane_base, s)) return HM_ESTATE;
     if (hi == lo) return 0;
     return compact_rows(p, LociSel{s, plane_base}, lo, hi, out, cap, no_hook, no_hook);
+}
+
+// ---- `pileup -E` ------------------------------------------------------------------------------------------------------------------
+int64_t hm_pileup_num_pattern_records(hm_pileup_t* p) { return p ? p->n_precs : HM_EINVAL; }
+
+int64_t hm_pileup_fetch_patterns(hm_pileup_t* p, int64_t lo, int64_t hi, int64_t min_reads, hm_pattern_t* out, int64_t cap) {
+    if (!p) return HM_EINVAL;
+    if (!p->patterns || p->seq_off.empty()) return pfail(p, HM_ESTATE, "hm_pileup_fetch_patterns without option patterns (then hm_pileup_set_reference)");
+    if (!p->patterns_counted) return pfail(p, HM_ESTATE, "hm_pileup_fetch_patterns before hm_pileup_count");
+    if (lo < 0 || hi < lo) return pfail(p, HM_EINVAL, "hm_pileup_fetch_patterns: bad range");
+    if (min_reads < 1) return pfail(p, HM_EINVAL, "hm_pileup_fetch_patterns: min_reads must be >= 1");
+    if (hi == lo || !p->n_cpg) return 0;
+    int64_t ranks[2] = {0, 0};
+    const int rc = guarded(p, [&] {  // the windows of [lo, hi) are those of the ranks [ranks[0], ranks[1])
+        hipLaunchKernelGGL(pattern_ranks_kernel, dim3(1), dim3(64), 0, p->stream, p->d_cpg.as<int64_t>(), p->n_cpg, lo, hi, p->d_pranks.as<int64_t>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(ranks, p->d_pranks.p, sizeof ranks, hipMemcpyDeviceToHost, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        return HM_OK;
+    });
+    if (rc != HM_OK) return rc;
+    if (ranks[1] <= ranks[0]) return 0;
+    return compact_rows(p, PatSel{pattern_rule(p), p->d_phist.as<uint32_t>(), min_reads}, ranks[0], ranks[1], out, cap, no_hook, no_hook);
+}
+
+int hm_pattern_stats(const hm_pattern_t* w, double out[4]) {
+    if (!w || !out || w->k < 2 || w->k > 4 || !w->n) return HM_EINVAL;
+    const uint32_t bins = 1u << w->k;
+    uint64_t n = 0;
+    for (uint32_t b = 0; b < bins; ++b) n += w->counts[b];
+    if (n != w->n) return HM_EINVAL;
+    const double dn = (double)n;
+    double h = 0.0, sq = 0.0;
+    uint64_t meth = 0;
+    for (uint32_t b = 0; b < bins; ++b) {
+        const uint32_t c = w->counts[b];
+        if (!c) continue;
+        const double f = (double)c / dn;
+        h += f * std::log2(f);
+        sq += f * f;
+        meth += (uint64_t)__builtin_popcount(b) * c;
+    }
+    out[0] = (0.0 - h) / (double)w->k;  // 0 - h: one pattern gives +0.0
+    out[1] = 1.0 - sq;
+    out[2] = 1.0 - (double)((uint64_t)w->counts[0] + w->counts[bins - 1]) / dn;
+    out[3] = 100.0 * (double)meth / ((double)w->k * dn);
+    return HM_OK;
 }
 
 int64_t hm_pileup_fetch_asm(hm_pileup_t* p, const void* pcov1, const void* ncov1, const void* pcov2, const void* ncov2,

@@ -49,6 +49,12 @@ turns them into the next levels; `DomainFit` is the stop rule of the iteration (
 runs it over the sequences of the reference and `domains_fit_tsv` is the text of <prefix>.domains.fit.tsv.  All of it is integer
 sums and one rounded division per level: the fit is the same however the planes are cut into pieces or over ranks.
 
+Read-level CpG patterns (`pileup -E k`, `patterns=k`): every reference CpG heads a window of k adjacent reference CpGs at most
+`pattern_span` bases apart; a read that carries a call at all k of them adds one to the window's count of its pattern (bit i = the
+i-th call is methylated) -- the one output that keeps the calls of a molecule together.  `pu.patterns(lo, hi, min_reads)` are the
+windows with at least min_reads such reads (PATTERN_DTYPE), `pattern_stats(row)` -- host only, the C library's -- their methylation
+entropy, epipolymorphism, proportion of discordant reads and level, `pu.patterns_bed(rows)` the text of <prefix>.patterns.CpG.bed.
+
 Fused with the caller (`pileup -K`): `pu.add_called(read, calls)` takes the records `MethylationCaller` returned for an aligned read
 instead of parsed MM / ML -- the same effect as add() of that read carrying the calls as tags, without the tag text.
 
@@ -84,6 +90,8 @@ SITE_DTYPE = np.dtype([("gpos", "<i8"), ("pcov", "<i4"), ("ncov", "<i4"), ("moti
 SITE_BINS = 3 * 256 * 256                                                             # HM_SITE_BINS
 DOMAIN_DTYPE = np.dtype([("start", "<i8"), ("end", "<i8"), ("pcov", "<i8"), ("ncov", "<i8"), ("n_loci", "<i4"), ("state", "<u4"),
                          ("motif", "<u4"), ("flags", "<u4"), ("level", "<f8"), ("score", "<f8")])  # hm_domain_t, 64 bytes
+PATTERN_DTYPE = np.dtype([("start", "<i8"), ("end", "<i8"), ("counts", "<u4", (16,)), ("n", "<u4"), ("k", "<u4")])  # hm_pattern_t, 88 bytes
+PATTERN_SPAN, PATTERN_MIN_READS = 150, 10                # `pileup -E`'s default -w and -o
 DOMAIN_AFTER_BREAK, DOMAIN_BEFORE_BREAK = 1, 2                                        # HM_DOMAIN_AFTER_BREAK, HM_DOMAIN_BEFORE_BREAK
 DOMAIN_PASS_SUMMARY, DOMAIN_PASS_CODES, DOMAIN_PASS_SEGMENTS, DOMAIN_KEEP = 0, 1, 2, 2   # HM_DOMAIN_PASS_*, HM_DOMAIN_KEEP
 DOMAIN_LEVELS = ((0.1, 0.8), (0.05, 0.5), (0.02, 0.2))  # `pileup -D`'s default low : high level per context: conventions, not tuned on data
@@ -453,6 +461,17 @@ def domains_bed(rows: np.ndarray, names: Sequence[str], offsets) -> dict:
     return {k: "".join(v) for k, v in text.items()}
 
 
+def pattern_stats(row) -> Tuple[float, float, float, float]:
+    """one PATTERN_DTYPE row -> (entropy, epipolymorphism, pdr, level) by the C library (host only: no GPU is needed): with
+    f = counts / n over the non-empty patterns, (0 - sum f log2 f) / k, 1 - sum f^2, 1 - (counts[0] + counts[2^k - 1]) / n and
+    100 sum popcount(pattern) counts / (k n)"""
+    w = np.array(row, PATTERN_DTYPE).reshape(1)
+    out = np.zeros(4, np.float64)
+    if lib().hm_pattern_stats(w.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)) != 0:
+        raise HifimethError("hm_pattern_stats: k in 2..4 and n = the sum of the 2^k counts > 0 expected")
+    return tuple(float(x) for x in out)
+
+
 def sites_rates_tsv(sums, rates, m) -> str:
     """the text of <prefix>.sites.rates.tsv: ctx, P_c, N_c, rate, m_c (the counts are 0 when the rates were given with -e)"""
     return "".join("%s\t%d\t%d\t%s\t%d\n" % (CTX_NAMES[c], int(sums[c]), int(sums[3 + c]),
@@ -471,7 +490,8 @@ def locate(offsets, gpos) -> Tuple[np.ndarray, np.ndarray]:
 
 class MethylationPileup:
     def __init__(self, genome: Sequence[Tuple[str, str]], device: int = 0, min_mapq: int = 0, min_pi: float = 0.0,
-                 planes=None, partitions: bool = False, partition_planes=None, bases=None):
+                 planes=None, partitions: bool = False, partition_planes=None, bases=None, patterns: int = 0,
+                 pattern_span: int = PATTERN_SPAN):
         """genome: [(name, SEQUENCE)].  bases: optional, the concatenated upper-case bases of the whole reference as a
         C-contiguous uint8 buffer (ndarray, bytes, memoryview), handed to the engine as it is -- for references of gigabases,
         where joining, upper-casing and encoding strings would copy them three times; the second member of each genome entry
@@ -479,7 +499,9 @@ class MethylationPileup:
         planes: optional (pcov, ncov, key) torch CUDA tensors (int32, int32, int32-as-bits) of total genome length
         that the engine counts into -- used when a collective consumes them afterwards.
         partitions: also count per haplotype (HP 1 / 2); partition_planes: optional ((pcov1, ncov1), (pcov2, ncov2)) int32
-        torch CUDA tensors for them, like `planes`."""
+        torch CUDA tensors for them, like `planes`.
+        patterns: 0, or k in (2, 3, 4): also count the read-level patterns over windows of k adjacent reference CpGs whose first
+        and last locus are at most pattern_span (1 .. 65 536) bases apart (+72 B per reference CpG, 8 B per window record)."""
         self._L = lib()
         self._h = C.c_void_p()
         if self._L.hm_pileup_create(C.byref(self._h), device) != 0:
@@ -498,6 +520,10 @@ class MethylationPileup:
                 self._check(self._L.hm_pileup_use_partition_planes(self._h, part, *(C.c_void_p(t.data_ptr()) for t in pair)))
         elif partition_planes is not None:
             raise HifimethError("partition_planes without partitions=True")
+        self.pattern_k = int(patterns)
+        if patterns:
+            self._check(self._L.hm_pileup_set_option(self._h, b"patterns", float(patterns)))
+            self._check(self._L.hm_pileup_set_option(self._h, b"pattern_span", float(pattern_span)))
         if planes is not None:
             self._check(self._L.hm_pileup_use_planes(self._h, *(C.c_void_p(t.data_ptr()) for t in planes)))
         if bases is None:
@@ -752,6 +778,26 @@ class MethylationPileup:
             text[CTX_NAMES[int(r["motif"])]].append("%s\t%d\t%d\t%g\t%d\t%d\t%.6g\t%.6g\n" % (
                 self.names[s], k, k + 1, 100.0 * p / (p + n), p, n, r["pvalue"], r["qvalue"]))
         return {k: "".join(v) for k, v in text.items()}
+
+    def num_pattern_records(self) -> int:
+        return int(self._L.hm_pileup_num_pattern_records(self._h))
+
+    def patterns(self, lo: int = 0, hi: Optional[int] = None, min_reads: int = PATTERN_MIN_READS) -> np.ndarray:
+        """the windows whose first reference CpG lies in [lo, hi), ascending (PATTERN_DTYPE), with at least min_reads reads that
+        carry a call at all k loci: counts[pattern], bit i of the pattern = the read's call at the i-th locus reaches the CpG
+        threshold count() was given.  Needs patterns=k, after count()."""
+        hi = self.n_loci if hi is None else hi
+        return self._rows(self._L.hm_pileup_fetch_patterns, PATTERN_DTYPE, lo, hi, min_reads)
+
+    def patterns_bed(self, rows: np.ndarray) -> str:
+        """the text of <prefix>.patterns.CpG.bed: chrom, start, end, n, entropy, epipolymorphism, pdr, level, the 2^k counts joined
+        by commas"""
+        sid, soff = locate(self.offsets, rows["start"])
+        text = []
+        for s, k, r in zip(sid, soff, rows):
+            text.append("%s\t%d\t%d\t%d\t%.6g\t%.6g\t%.6g\t%.6g\t" % (self.names[s], k, k + (r["end"] - r["start"]), r["n"], *pattern_stats(r))
+                        + ",".join("%d" % c for c in r["counts"][:1 << int(r["k"])]) + "\n")
+        return "".join(text)
 
     def domains(self, ctx: int, lo: int = 0, hi: Optional[int] = None, A: Optional[int] = None, B: Optional[int] = None,
                 S: Optional[int] = None, max_gap: int = DOMAIN_MAX_GAP, planes=None, plane_base: int = 0) -> Tuple[np.ndarray, int]:

@@ -236,7 +236,8 @@ int hm_pileup_create(hm_pileup_t** out, int device);
 void hm_pileup_destroy(hm_pileup_t* p);
 const char* hm_pileup_last_error(const hm_pileup_t* p); /* p may be NULL: error of a failed create */
 /* options: "min_mapq" (-q, default 0), "min_pi" (-f, default 0.0), "partitions" (0 default, or 2: haplotype-resolved
- * counting, see hm_pileup_submit_read_hp; must be set before hm_pileup_set_reference / hm_pileup_use_planes, else HM_ESTATE) */
+ * counting, see hm_pileup_submit_read_hp; must be set before hm_pileup_set_reference / hm_pileup_use_planes, else HM_ESTATE),
+ * "patterns" and "pattern_span" (read-level CpG patterns, at the end of this header) */
 int hm_pileup_set_option(hm_pileup_t* p, const char* key, double value);
 /* HbnDatabase: n_seqs upper-cased sequences back to back in `bases` (seq_len[i] bytes each).  Allocates and
  * zeroes the per-locus planes unless hm_pileup_use_planes was called before. */
@@ -561,6 +562,40 @@ int64_t hm_pileup_domain_sums_part(hm_pileup_t* p, const void* pcov, const void*
 /* Host only.  Step 3 above: HM_OK and the new levels; HM_EDATA, the levels untouched, where the step ends the fit (`one_state`
  * if R0 == 0 or R1 == 0, else `degenerate`); HM_EINVAL for a NULL, a negative sum or a penalty that is not >= 0. */
 int hm_domain_refit(const int64_t sums[6], double penalty, double* level_lo, double* level_hi);
+
+/* ---- read-level CpG patterns (`pileup -E`): which molecules carry which combination of calls -----------------
+ * Everything above is a function of the per-locus counters; this is the one output that keeps the calls of a read together.
+ * REFERENCE CpGs: per reference sequence the loci g with ref[g] == 'C' && ref[g + 1] == 'G', both bases inside the sequence (the
+ * byte comparison of the projection: lower case never matches), c_0 < c_1 < ...; a locus's RANK is its place in the job-wide
+ * ascending list.  A record is a MEMBER at reference CpG g exactly when it contributes a CpG (motif 0) record at g to the counters:
+ * it passes -q / -f, g and g + 1 lie in one match run, the read's bases as stored are C, G, and the read carries a 5mC call there
+ * (the strand rule of the projection); its probability is that call's ML byte.
+ * WINDOW j, for k in {2, 3, 4}: the loci c_j .. c_{j+k-1} of one sequence; valid when c_{j+k-1} - c_j <= max_span.  A record
+ * CONTRIBUTES to window j iff it is a member at all k loci -- a deletion, mismatch, missing call or run break at any of them and it
+ * contributes nothing to that window; an insertion between two loci does not matter.  Its PATTERN has bit i (bit 0 = the leftmost
+ * locus) set iff prob_i >= thr[CpG], the >= of hm_pileup_count.  counts[pattern] = the number of contributing records; a window is
+ * a ROW when it is valid and n = the sum of its counts >= min_reads.  All integers: nothing depends on launch geometry.
+ * Options "patterns" (k: 0 off = default, 2, 3 or 4) and "pattern_span" (max_span, 1 .. 65 536, default 150), both before
+ * hm_pileup_set_reference (else HM_ESTATE; HM_EINVAL out of range).  With patterns on, hm_pileup_set_reference lists the reference
+ * CpGs (8 B each) and allocates 16 uint32 bins per CpG (64 B), hm_pileup_run also appends one 8-byte window record per member head
+ * whose window the read spans, and hm_pileup_count adds them into the bins with thr[0] and drops them.  Not here: CHG / CHH
+ * windows, the haplotype partitions, windows with tolerated gaps, any statistical test. */
+typedef struct {            /* one window = one row of <prefix>.patterns.CpG.bed; 88 bytes */
+    int64_t start, end;     /* c_j, c_{j+k-1} + 2 */
+    uint32_t counts[16];    /* by pattern; bins >= 2^k are 0 */
+    uint32_t n, k;
+} hm_pattern_t;
+/* window records resident since the last hm_pileup_count */
+int64_t hm_pileup_num_pattern_records(hm_pileup_t* p);
+/* The rows whose first locus lies in [lo, hi), ascending.  Returns their number (may exceed cap, or out NULL: then nothing is
+ * written).  hi == lo returns 0.  HM_ESTATE without option "patterns" or before hm_pileup_count, HM_EINVAL for lo < 0, lo > hi or
+ * min_reads < 1. */
+int64_t hm_pileup_fetch_patterns(hm_pileup_t* p, int64_t lo, int64_t hi, int64_t min_reads, hm_pattern_t* out, int64_t cap);
+/* Host only: the one implementation behind every front end.  With f_b = counts[b] / n over the non-empty bins b in ascending
+ * order, in fp64:  out[0] entropy = (0 - sum f_b log2 f_b) / k, in [0, 1];  out[1] epipolymorphism = 1 - sum f_b^2;
+ * out[2] pdr = 1 - (double)(counts[0] + counts[2^k - 1]) / n, the proportion of discordant reads;
+ * out[3] level = 100 * sum popcount(b) counts[b] / (k n).  HM_EINVAL for k outside 2..4, n == 0 or n != the sum of the 2^k bins. */
+int hm_pattern_stats(const hm_pattern_t* w, double out[4]);
 
 #ifdef __cplusplus
 }

@@ -14,9 +14,12 @@ fetch then also compacts the two partitions' planes.
 `--domains`: the segmentation of `pileup -D` over the counted planes: per context, select + two scans + heads + D2H of the segments per pass.
 `--fit` (with `--domains`): one state-sums pass (`pileup -D -Y`: select + two scans + one reduction, 48 bytes back) next to one fetch of the
 segments over the same planes, and the fit of the three contexts from the default levels: iterations, status, seconds.
+`--patterns K`: the read-level CpG patterns of `pileup -E K`: the timed passes run on an engine without the option first and then on one
+with it; the leg is what the option adds to projection and counting plus one fetch of the rows (D2H included): window records per second,
+rows, share of a pass.
 `--parts N` (with `--domains`): the same segments chained from N equal pieces next to the single fetch (three stateless passes per piece).
 
-    python tools/pileup_bench.py --genome-mb 20 --coverage 10 [--partitions [--asm [--asm-q] [--asm-regions]]] [--sites] [--domains [--fit] [--parts N]]
+    python tools/pileup_bench.py --genome-mb 20 --coverage 10 [--partitions [--asm [--asm-q] [--asm-regions]]] [--sites] [--domains [--fit] [--parts N]] [--patterns K]
 """
 import argparse
 import ctypes as C
@@ -106,6 +109,8 @@ def main():
     ap.add_argument("--fit-iter", type=int, default=50, help="with --fit: the largest number of iterations per context")
     ap.add_argument("--parts", type=int, default=0, metavar="N",
                     help="with --domains: also the same segments chained from N equal pieces (hm_pileup_fetch_domains_part, what pileup_dist -D runs)")
+    ap.add_argument("--patterns", type=int, default=0, metavar="K", choices=(0, 2, 3, 4),
+                    help="time what the read-level CpG patterns over windows of K reference CpGs add (pileup -E K, default span and min reads)")
     ap.add_argument("--cpu-baseline", action="store_true",
                     help="time the reference's own projection code (oracle/_ref/ref_align -t) on a bounded sample")
     a = ap.parse_args()
@@ -141,7 +146,7 @@ def main():
     pu = MethylationPileup(genome, partitions=a.partitions)
     L = pu._L
 
-    def one_pass():
+    def one_pass(pu=pu):
         for i, (flag, pos, seq4, cig, mods) in enumerate(staged):
             args = (pu._h, i, flag, 0, pos, 60, a.read_len, seq4.ctypes.data_as(C.c_void_p), 1,
                     cig.ctypes.data_as(C.c_void_p), len(mods), mods.ctypes.data_as(C.c_void_p))
@@ -151,12 +156,25 @@ def main():
                 pu.flush()
         pu.flush()
 
-    one_pass()                                     # warm-up (allocations)
+    if a.patterns:                                 # the same passes without the option first: the leg is the difference
+        one_pass()
+        pu.count([128, 128, 128])
+        t0 = time.perf_counter()
+        for _ in range(a.repeat):
+            one_pass()
+        t_project_off = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        pu.count([128, 128, 128])
+        t_count_off = time.perf_counter() - t0
+        pu.close()
+        pu = MethylationPileup(genome, partitions=a.partitions, patterns=a.patterns)
+    one_pass(pu)                                   # warm-up (allocations)
+    wins_per_pass = pu.num_pattern_records()
     recs_per_pass = pu.num_records()
     pu.count([128, 128, 128])
     t0 = time.perf_counter()
     for _ in range(a.repeat):
-        one_pass()
+        one_pass(pu)
     t_project = time.perf_counter() - t0
     t0 = time.perf_counter()
     pu.count([128, 128, 128])
@@ -180,6 +198,22 @@ def main():
                loci_scan_bases_per_s=round(G / t_loci), partitions=a.partitions)
     if a.partitions:
         out.update(partition_loci=[int(len(x)) for x in hp_loci], partition_loci_fetch_s=round(t_hp_loci, 4))
+    if a.patterns:
+        pu.patterns()                              # warm-up: the row buffer
+        t0 = time.perf_counter()
+        for _ in range(a.repeat):
+            rows = pu.patterns()
+        t_rows = (time.perf_counter() - t0) / a.repeat
+        t_leg = max((t_project - t_project_off + t_count - t_count_off) / a.repeat, 0.0) + t_rows
+        t_pass = (t_project_off + t_count_off) / a.repeat + t_loci
+        out.update(patterns_k=a.patterns, patterns_window_records_per_pass=int(wins_per_pass), patterns_rows=int(len(rows)),
+                   patterns_project_s_per_pass=[round(t_project_off / a.repeat, 4), round(t_project / a.repeat, 4)],
+                   patterns_count_s=[round(t_count_off, 4), round(t_count, 4)], patterns_rows_s=round(t_rows, 4),
+                   patterns_leg_s_per_pass=round(t_leg, 4), patterns_window_records_per_s=round(wins_per_pass / t_leg) if t_leg else 0,
+                   patterns_share_of_pass=round(t_leg / (t_pass + t_leg), 4))
+        if a.check:                                # a row's reads are window records: all of them at min_reads 1
+            n_all = int(pu.patterns(min_reads=1)["n"].astype(np.int64).sum())
+            out["check_patterns_rows_hold_the_records"] = bool(n_all == wins_per_pass * (a.repeat + 1))
     if a.asm:                                      # select + test + fetch of every tested locus, as the CLI does per sequence
         pu.asm(min_cov=a.asm_min_cov)              # warm-up: the log n! table and the row buffer
         t0 = time.perf_counter()
