@@ -145,6 +145,7 @@ def lib():
         "hm_pileup_num_pattern_records": (i64, [vp]),
         "hm_pileup_fetch_patterns": (i64, [vp, i64, i64, i64, vp, i64]),
         "hm_pattern_stats": (C.c_int, [vp, vp]),
+        "hm_pileup_fetch_bedmethyl": (i64, [vp, i32, i64, i64, i64, vp, i64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

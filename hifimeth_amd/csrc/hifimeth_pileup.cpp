@@ -25,6 +25,9 @@
 //   chrom <tab> start <tab> end <tab> n_loci <tab> L|H <tab> level <tab> pcov <tab> ncov <tab> score      (DESIGN.md section 10).
 // -D -Y n (ours): the two levels are fitted from the data first, from -u in at most n iterations of hard EM over the state sums
 // the GPU gives (hm_pileup_domain_sums); also <prefix>.domains.fit.tsv, the iterations and the fitted levels.
+// -M (ours): also <prefix>.bedmethyl.CpG.bed (under -H also <prefix>.hap1. / <prefix>.hap2.bedmethyl.CpG.bed), modkit's 18 bedMethyl
+// columns per reference CpG: besides the methylated and unmethylated calls the reads that covered the CpG without giving one --
+// no call, another base, a deletion -- counted on the GPU (hm_pileup_fetch_bedmethyl).
 // -K (ours): the input is an aligned BAM that still carries the kinetics tags (pbmm2 keeps fi / fp / ri / rp): the reads are called
 // on the fly by the call engine and their calls go straight to the pileup engine (hm_pileup_submit_read_calls) -- the files
 // `call` followed by `pileup` writes, without the mod-BAM between the two.
@@ -108,6 +111,9 @@ struct PileupOptions {
     long long pattern_span = 150;      // -w: largest distance between the first and the last locus of a window
     long long pattern_min_reads = 10;  // -o: smallest number of reads spanning a window that is written
     bool pattern_option_given = false, pattern_option_bad = false;  // -w or -o; -E, -w or -o with a value out of range
+    bool bedmethyl = false;            // -M: bedMethyl rows with the depth classes per reference CpG -> <prefix>.bedmethyl.CpG.bed
+    long long bedmethyl_min_valid = 1; // -v: smallest n_mod + n_canon of a row that is written
+    bool bedmethyl_option_given = false, bedmethyl_option_bad = false;  // -v; -v with a value out of range
     // -K: call on the fly; the options below are `call`'s (hifimeth_call.cpp), same meaning and defaults
     bool kinetics = false;
     bool call_option_given = false;  // any of -m -c -l -p -T: a usage error without -K
@@ -170,6 +176,12 @@ void pileup_usage(const char* exe) {
             "    pattern.  The combined reads are counted, with or without -H\n"
             "  -w <bp>\n    With -E: largest distance between the first and the last CpG of a window, in [1, 65536]\n    Default: 150\n"
             "  -o <int>\n    With -E: smallest number of reads spanning a window that is written, >= 1\n    Default: 10\n"
+            "  -M\n    bedMethyl output: write <prefix>.bedmethyl.CpG.bed (with -H also <prefix>.hap1. and <prefix>.hap2.bedmethyl.CpG.bed), one row\n"
+            "    per reference CpG in modkit's 18 columns: chrom, start, end, m, min(1000, Nvalid), ., start, end, 255,0,0, Nvalid, percent\n"
+            "    modified, Nmod, Ncanonical, Nother_mod (0), Ndelete, Nfail (0), Ndiff, Nnocall.  Nvalid = Nmod + Ncanonical; of the reads that\n"
+            "    pass -q and -f, Nnocall covered the intact CG without a call, Ndiff show another base at the C or the G (or break off between\n"
+            "    them), Ndelete have the C inside a deletion\n"
+            "  -v <int>\n    With -M: smallest Nvalid of a row that is written, >= 0 (0: also CpGs seen only as nocall, diff or delete)\n    Default: 1\n"
             "  -K\n    The input is an aligned BAM that carries the kinetics tags fi / fp / ri / rp instead of MM / ML: call 5mC on the\n"
             "    fly and pile the calls up directly.  For equal -c -l -p -T -q -f the output files are byte-identical to those of\n"
             "    `%s call` on that BAM followed by `%s pileup` on its output; no mod-BAM is written.  (Give -T explicitly\n"
@@ -793,6 +805,7 @@ inline int64_t row_pos(const hm_pattern_t& r) { return r.start; }
 template <class Row>
 uint32_t row_ctx(const Row& r) { return r.motif < 3 ? r.motif : 2; }
 inline uint32_t row_ctx(const hm_pattern_t&) { return 0; }
+inline uint32_t row_ctx(const hm_bedmethyl_t&) { return 0; }
 
 // The three files <prefix>.<tag><ctx>.<suffix> of one output, closed when their owner goes.
 struct CtxFiles {
@@ -929,6 +942,20 @@ bool write_patterns(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, FI
             for (uint32_t b = 0; b < (1u << r.k); ++b) len += snprintf(buf + len, sizeof buf - (size_t)len, "%c%u", b ? ',' : '\t', r.counts[b]);
             len += snprintf(buf + len, sizeof buf - (size_t)len, "\n");
             return len;
+        });
+}
+
+// rows of <prefix>[.hapN].bedmethyl.CpG.bed (out[0]) from set `part` of the depth counters.  false on an engine error.
+bool write_bedmethyl(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, int part, FILE* out[3]) {
+    return write_rows<hm_bedmethyl_t>(
+        fa, out, o.threads,
+        [&](int64_t lo, int64_t hi, hm_bedmethyl_t* dst, int64_t cap) { return hm_pileup_fetch_bedmethyl(pe, part, lo, hi, o.bedmethyl_min_valid, dst, cap); },
+        [](const hm_bedmethyl_t& r, int64_t k, char (&buf)[320]) {
+            const unsigned long long valid = (unsigned long long)r.n_mod + r.n_canon;
+            const double percent = valid ? 100.0 * (double)r.n_mod / (double)valid : 0.0;
+            return snprintf(buf, sizeof buf, "\t%lld\t%lld\tm\t%llu\t.\t%lld\t%lld\t255,0,0\t%llu\t%.2f\t%u\t%u\t0\t%u\t0\t%u\t%u\n", (long long)k,
+                            (long long)k + 1, std::min(1000ull, valid), (long long)k, (long long)k + 1, valid, percent, r.n_mod, r.n_canon,
+                            r.n_delete, r.n_diff, r.n_nocall);
         });
 }
 
@@ -1320,6 +1347,7 @@ int cmd_pileup(int argc, char** argv) {
         if (a == "-G") { o.asm_regions = true; continue; }
         if (a == "-K") { o.kinetics = true; continue; }
         if (a == "-D") { o.domains = true; continue; }
+        if (a == "-M") { o.bedmethyl = true; continue; }
         if (i + 1 >= argc) { pileup_usage(argv[0]); return EXIT_FAILURE; }
         if (a == "-q") o.min_mapq = atoi(argv[++i]);
         else if (a == "-f") o.min_pi = atof(argv[++i]);
@@ -1368,6 +1396,14 @@ int cmd_pileup(int argc, char** argv) {
             else if (a == "-E") { if (x < 2 || x > 4) o.pattern_option_bad = true; else o.patterns = (int)x; }
             else if (a == "-w") { if (x < 1 || x > 65536) o.pattern_option_bad = true; else o.pattern_span = x; }
             else { if (x < 1) o.pattern_option_bad = true; else o.pattern_min_reads = x; }
+        }
+        else if (a == "-v") {  // the whole value must parse
+            o.bedmethyl_option_given = true;
+            const char* v = argv[++i];
+            char* end = nullptr;
+            errno = 0;
+            o.bedmethyl_min_valid = strtoll(v, &end, 10);
+            if (end == v || *end || errno || o.bedmethyl_min_valid < 0) o.bedmethyl_option_bad = true;
         }
         else if (a == "-Y") {
             const char* v = argv[++i];
@@ -1425,6 +1461,8 @@ int cmd_pileup(int argc, char** argv) {
     const char* bad_patterns = o.pattern_option_bad ? "-E must be 2, 3 or 4, -w an integer in [1, 65536], -o an integer >= 1"
                                : o.pattern_option_given && !o.patterns ? "-w and -o need -E" : nullptr;
     if (bad_patterns) { fprintf(stderr, "ERROR: %s\n", bad_patterns); pileup_usage(argv[0]); return EXIT_FAILURE; }
+    const char* bad_bedmethyl = o.bedmethyl_option_given && !o.bedmethyl ? "-v needs -M" : o.bedmethyl_option_bad ? "-v must be an integer >= 0" : nullptr;
+    if (bad_bedmethyl) { fprintf(stderr, "ERROR: %s\n", bad_bedmethyl); pileup_usage(argv[0]); return EXIT_FAILURE; }
     const bool sites = !o.control.empty() || o.rates_given;
     if (o.kinetics && o.model_dir.empty()) o.model_dir = exe_dir() + "/../weights";
     o.ref = argv[i];
@@ -1456,6 +1494,9 @@ int cmd_pileup(int argc, char** argv) {
     if (o.patterns)
         fprintf(stderr, "patterns: windows of %d reference CpGs within %lld bases, spanned by >= %lld reads -> %s.patterns.CpG.bed\n", o.patterns,
                 o.pattern_span, o.pattern_min_reads, o.prefix.c_str());
+    if (o.bedmethyl)
+        fprintf(stderr, "bedmethyl: reference CpGs with Nvalid >= %lld, 18 columns -> %s.bedmethyl.CpG.bed%s\n", o.bedmethyl_min_valid, o.prefix.c_str(),
+                o.haplotypes ? ", .hap1. and .hap2. as well" : "");
     if (o.kinetics)
         fprintf(stderr, "kinetics: called on the fly (models %s, contexts%s%s%s, min read length %d, precision %d, trunk %s)\n", o.model_dir.c_str(),
                 o.ctx_mask & 1 ? " CpG" : "", o.ctx_mask & 2 ? " CHG" : "", o.ctx_mask & 4 ? " CHH" : "", o.min_read_size, o.precision,
@@ -1491,6 +1532,7 @@ int cmd_pileup(int argc, char** argv) {
     if (o.haplotypes && hm_pileup_set_option(pe, "partitions", 2) != HM_OK) return die("partitions");
     if (o.patterns && (hm_pileup_set_option(pe, "patterns", o.patterns) != HM_OK || hm_pileup_set_option(pe, "pattern_span", (double)o.pattern_span) != HM_OK))
         return die("patterns");
+    if (o.bedmethyl && hm_pileup_set_option(pe, "bedmethyl", 1) != HM_OK) return die("bedmethyl");
     if (fa.names.empty()) { fprintf(stderr, "ERROR: no sequence in %s\n", o.ref.c_str()); return EXIT_FAILURE; }
     if (hm_pileup_set_reference(pe, (int32_t)fa.names.size(), fa.length.data(), fa.bases.data()) != HM_OK) return die("reference");
 
@@ -1635,6 +1677,14 @@ int cmd_pileup(int argc, char** argv) {
         const bool ok = write_patterns(pe, fa, o, out);
         fclose(out[0]);
         if (!ok) return die("patterns");
+    }
+    for (int part = 0; o.bedmethyl && part <= (o.haplotypes ? 2 : 0); ++part) {
+        const std::string path = o.prefix + (part ? ".hap" + std::to_string(part) : std::string()) + ".bedmethyl.CpG.bed";
+        FILE* out[3] = {fopen(path.c_str(), "w"), nullptr, nullptr};
+        if (!out[0]) { fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str()); return EXIT_FAILURE; }
+        const bool ok = write_bedmethyl(pe, fa, o, part, out);
+        fclose(out[0]);
+        if (!ok) return die("bedmethyl");
     }
     if (sites) {
         const int rc = write_sites(pe, fa, o, control_sid, o.threads);

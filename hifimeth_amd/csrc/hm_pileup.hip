@@ -22,6 +22,9 @@
 //   pattern_kernel  thread per column      : (`pileup -E`) a CpG member that heads a window of k reference CpGs looks the other
 //                   k - 1 up in the read's following runs and appends one 8-byte window record; pattern_count_kernel adds
 //                   the records into 16 bins per reference CpG; RefCpgSel lists the reference CpGs, PatSel the rows
+//   depth_kernel    thread per column      : (`pileup -M`) a column on the C of a reference CG whose read is no member there adds
+//                   NOCALL or DIFF to the CpG's depth counters; depth_gap_kernel, thread per D operation, adds DELETE;
+//                   depth_count_kernel, thread per resident record, adds MOD or CANON; BmSel the bedMethyl rows
 //   select_count / loci_scan / select_write   the rows of a SELECTION over a range in ascending order (count per block, scan,
 //                   write); every output below is a selection struct (its planes, pred, take) plus per-row kernels
 //   LociSel         covered loci
@@ -638,6 +641,126 @@ struct PatSel {
         w.end = rule.cpg_pos[r + rule.k - 1] + 2;
         w.n = (uint32_t)n;
         w.k = (uint32_t)rule.k;
+        return true;
+    }
+};
+
+// ---- bedMethyl depth classes (`pileup -M`; include/hifimeth_hip.h has the definition) ----------------------------------------
+// Five uint32 counters per reference CpG and set (0 = every record, 1 / 2 = the haplotype partitions):
+// bm[(set * n_cpg + rank) * BM_CLASSES + class].  NOCALL and DIFF come from the aligned columns (depth_kernel), DELETE from the
+// D operations (depth_gap_kernel), both behind the projection; MOD and CANON from the resident records once the threshold is
+// known (depth_count_kernel).  Integer atomics only: any order gives the same counters.
+enum BmClass { BM_MOD = 0, BM_CANON, BM_NOCALL, BM_DIFF, BM_DELETE, BM_CLASSES };
+
+struct PGap {           // 16 bytes: one D operation of non-zero length
+    int64_t g0;         // reference offset (concatenated) of the first deleted base
+    int32_t len;
+    int32_t read;
+};
+
+struct BmCounters {
+    const int64_t* cpg_pos;  // the reference CpGs, ascending
+    int64_t n_cpg;
+    uint32_t* bm;
+    // rank of the reference CpG whose C is g, or -1 (the C | G that straddles two sequences is none)
+    __device__ int64_t rank_of(int64_t g) const {
+        const int64_t r = lower_rank(cpg_pos, n_cpg, g);
+        return r < n_cpg && cpg_pos[r] == g ? r : -1;
+    }
+    // hp is 1 or 2 only on an engine with the partitions option, whose counters hold three sets
+    __device__ void add(int64_t rank, int cls, uint32_t hp) const {
+        atomicAdd(&bm[rank * BM_CLASSES + cls], 1u);
+        if (hp) atomicAdd(&bm[((int64_t)hp * n_cpg + rank) * BM_CLASSES + cls], 1u);
+    }
+};
+
+// -q and -f, as project_kernel applies them
+__device__ __forceinline__ bool read_takes_part(const PRead& rd, int read, const int32_t* __restrict__ matches, double min_pi) {
+    return rd.pass && !(min_pi > 0.0 && 100.0 * matches[read] / rd.as_size < min_pi);
+}
+
+// One thread per aligned column, project_kernel's geometry.  Only a column on the C of a reference CG goes further: the
+// alignment ends on it (nothing), its run ends on it or the stored bases are not C, G (DIFF), the read carries no 5mC entry there
+// (NOCALL); a member column adds nothing here, its record does in depth_count_kernel.
+__global__ __launch_bounds__(TPB) void depth_kernel(const PRun* __restrict__ runs, const int64_t* __restrict__ col0, int n_runs,
+                                                     int64_t n_cols, const PRead* __restrict__ reads, const uint8_t* __restrict__ slab,
+                                                     const char* __restrict__ ref, int64_t total, const uint32_t* __restrict__ plane,
+                                                     const int32_t* __restrict__ matches, double min_pi, BmCounters cnt) {
+    __shared__ int run_range[2];
+    if (threadIdx.x < 2) {
+        const int64_t c = min((int64_t)blockIdx.x * PTILE + (threadIdx.x ? PTILE - 1 : 0), n_cols - 1);
+        run_range[threadIdx.x] = find_run(col0, n_runs, c) + (int)threadIdx.x;
+    }
+    __syncthreads();
+    const int run_lo = run_range[0], run_hi = run_range[1];
+    for (int it = 0; it < PTILE / TPB; ++it) {
+        const int64_t c = (int64_t)blockIdx.x * PTILE + it * TPB + threadIdx.x;
+        if (c >= n_cols) continue;
+        const int ri = find_run(col0, n_runs, c, run_lo, run_hi);
+        const PRun run = runs[ri];
+        const int o = (int)(c - col0[ri]);
+        const int64_t g = run.g0 + o;
+        if (ref[g] != 'C' || g + 1 >= total || ref[g + 1] != 'G') continue;
+        const PRead rd = reads[run.read];
+        if (!read_takes_part(rd, run.read, matches, min_pi)) continue;
+        int cls = BM_DIFF;
+        if (o == run.len - 1) {  // the run ends on the C
+            if (ri + 1 == n_runs || runs[ri + 1].read != run.read) continue;  // ... and so does the alignment
+        } else {
+            const int qp = run.q0 + o;
+            if (stored_base(slab, rd, qp) == 'C' && stored_base(slab, rd, qp + 1) == 'G') {
+                if (plane[rd.plane_off + (rd.rev ? rd.l_qseq - 1 - (qp + 1) : qp)] & 0x100u) continue;  // a member
+                cls = BM_NOCALL;
+            }
+        }
+        const int64_t r = cnt.rank_of(g);
+        if (r >= 0) cnt.add(r, cls, rd.hp);
+    }
+}
+
+// One thread per D operation: DELETE at every reference CpG whose C it removes.  A long deletion is a loop in one thread.
+__global__ __launch_bounds__(TPB) void depth_gap_kernel(const PGap* __restrict__ gaps, int64_t n, const PRead* __restrict__ reads,
+                                                         const int32_t* __restrict__ matches, double min_pi, BmCounters cnt) {
+    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
+        const PGap gap = gaps[i];
+        const PRead rd = reads[gap.read];
+        if (!read_takes_part(rd, gap.read, matches, min_pi)) continue;
+        const int64_t r1 = lower_rank(cnt.cpg_pos, cnt.n_cpg, gap.g0 + gap.len);
+        for (int64_t r = lower_rank(cnt.cpg_pos, cnt.n_cpg, gap.g0); r < r1; ++r) cnt.add(r, BM_DELETE, rd.hp);
+    }
+}
+
+// One thread per resident record: a CpG (motif 0) record is a member at the reference CpG gpos -> MOD or CANON by thr[CpG]
+__global__ __launch_bounds__(TPB) void depth_count_kernel(const PRec* __restrict__ recs, int64_t n, uint32_t thr, BmCounters cnt) {
+    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
+        const PRec rec = recs[i];
+        if ((rec.hi >> 16) & 3u) continue;
+        const int64_t r = cnt.rank_of((int64_t)rec.glo | ((int64_t)(rec.hi & 255u) << 32));
+        if (r >= 0) cnt.add(r, ((rec.hi >> 8) & 255u) >= thr ? BM_MOD : BM_CANON, (rec.hi >> 18) & 3u);
+    }
+}
+
+// the rows over RANKS of one set (bm points at the set's counters): a reference CpG some record was classed at, with
+// n_mod + n_canon >= min_valid
+struct BmSel {
+    using Row = hm_bedmethyl_t;
+    const int64_t* cpg_pos;
+    const uint32_t* bm;
+    int64_t min_valid;
+    __device__ bool pred(int64_t r) const {
+        const uint32_t* c = bm + r * BM_CLASSES;
+        return ((uint64_t)c[0] + c[1] + c[2] + c[3] + c[4]) >= 1 && (int64_t)c[BM_MOD] + c[BM_CANON] >= min_valid;
+    }
+    __device__ bool take(int64_t r, Row& w) const {
+        if (!pred(r)) return false;
+        const uint32_t* c = bm + r * BM_CLASSES;
+        w.gpos = cpg_pos[r];
+        w.n_mod = c[BM_MOD];
+        w.n_canon = c[BM_CANON];
+        w.n_nocall = c[BM_NOCALL];
+        w.n_diff = c[BM_DIFF];
+        w.n_delete = c[BM_DELETE];
+        w.reserved = 0;
         return true;
     }
 };
@@ -1401,6 +1524,7 @@ struct hm_pileup {
     std::vector<int64_t> col0;
     std::vector<PMod> mods;
     std::vector<PCall> calls;  // of the records submitted with calls; n_m_mods counts them too
+    std::vector<PGap> gaps;    // `pileup -M`: the D operations of the staged records
     int64_t plane_len = 0, n_m_mods = 0;
 
     // device
@@ -1425,6 +1549,12 @@ struct hm_pileup {
     DevBuf d_seqoff{EXACT}, d_cpg{EXACT}, d_phist{EXACT}, d_pcounter{EXACT}, d_pranks{EXACT}, d_precs{HALF};
     int64_t n_cpg = 0, n_precs = 0;
     bool patterns_counted = false;
+    // `pileup -M` ("bedmethyl" = 1), all of it only with the option on: d_seqoff, d_cpg and d_pranks above, shared with -E; five
+    // uint32 depth counters per reference CpG and set (20 B, 60 B with partitions), resident from hm_pileup_set_reference on; the
+    // staged D operations of a batch
+    int bedmethyl = 0;
+    DevBuf d_bm{EXACT}, d_gaps{HALF};
+    bool bedmethyl_counted = false;
     int64_t n_recs = 0;
     bool bins_ready = false;
 
@@ -1643,27 +1773,41 @@ PatRule pattern_rule(const hm_pileup* p) {
     return PatRule{p->d_cpg.as<int64_t>(), p->n_cpg, p->d_seqoff.as<int64_t>(), (int)p->seq_off.size() - 1, p->patterns, p->pattern_span};
 }
 
-// `pileup -E`, under hm_pileup_set_reference's guard once the bases are on their way: the sequence starts, the reference CpGs of
-// the whole reference through the selection skeleton (they stay on the device), their bins and the record counter zeroed
+BmCounters depth_counters(const hm_pileup* p, int set = 0) {
+    return BmCounters{p->d_cpg.as<int64_t>(), p->n_cpg, p->d_bm.as<uint32_t>() + (size_t)set * (size_t)p->n_cpg * BM_CLASSES};
+}
+
+// `pileup -E` and `pileup -M`, under hm_pileup_set_reference's guard once the bases are on their way: the sequence starts, the
+// reference CpGs of the whole reference through the selection skeleton (they stay on the device); then what each option keeps per
+// reference CpG, zeroed: -E's bins and record counter, -M's depth counters
 int list_reference_cpgs(hm_pileup* p) {
     const int n_seqs = (int)p->seq_off.size() - 1;
     const int64_t total = p->seq_off.back();
     p->d_seqoff.reserve(8 * p->seq_off.size());
     HIP_TRY(hipMemcpyAsync(p->d_seqoff.p, p->seq_off.data(), 8 * p->seq_off.size(), hipMemcpyHostToDevice, p->stream));
-    p->d_pcounter.reserve(sizeof(unsigned long long));
     p->d_pranks.reserve(16);
-    HIP_TRY(hipMemsetAsync(p->d_pcounter.p, 0, sizeof(unsigned long long), p->stream));
+    if (p->patterns) {
+        p->d_pcounter.reserve(sizeof(unsigned long long));
+        HIP_TRY(hipMemsetAsync(p->d_pcounter.p, 0, sizeof(unsigned long long), p->stream));
+    }
     p->n_cpg = p->n_precs = 0;
-    p->patterns_counted = false;
+    p->patterns_counted = p->bedmethyl_counted = false;
     if (total >= 2) {
         const int64_t n = stage_rows(p, RefCpgSel{p->d_ref.as<char>(), p->d_seqoff.as<int64_t>(), n_seqs, total}, 0, total, p->d_cpg,
                                      [](int64_t) { return true; }, no_hook);
         if (n < 0) return (int)n;
-        if (n >= (int64_t(1) << 32)) return pfail(p, HM_EINVAL, "patterns: 2^32 reference CpGs or more");
+        if (n >= (int64_t(1) << 32)) return pfail(p, HM_EINVAL, std::string(p->patterns ? "patterns" : "bedmethyl") + ": 2^32 reference CpGs or more");
         p->n_cpg = n;
     }
-    p->d_phist.reserve(64 * (size_t)std::max<int64_t>(p->n_cpg, 1));
-    HIP_TRY(hipMemsetAsync(p->d_phist.p, 0, 64 * (size_t)std::max<int64_t>(p->n_cpg, 1), p->stream));
+    if (p->patterns) {
+        p->d_phist.reserve(64 * (size_t)std::max<int64_t>(p->n_cpg, 1));
+        HIP_TRY(hipMemsetAsync(p->d_phist.p, 0, 64 * (size_t)std::max<int64_t>(p->n_cpg, 1), p->stream));
+    }
+    if (p->bedmethyl) {
+        const size_t bytes = sizeof(uint32_t) * BM_CLASSES * (p->partitions == 2 ? 3 : 1) * (size_t)std::max<int64_t>(p->n_cpg, 1);
+        p->d_bm.reserve(bytes);
+        HIP_TRY(hipMemsetAsync(p->d_bm.p, 0, bytes, p->stream));
+    }
     return HM_OK;
 }
 
@@ -1674,16 +1818,26 @@ void clear_batch(hm_pileup* p) {
     p->col0.clear();
     p->mods.clear();
     p->calls.clear();
+    p->gaps.clear();
     p->plane_len = 0;
     p->n_m_mods = 0;
 }
 
 // The record-level part of a submission, shared by the MM/ML and the calls form: every argument check, the CIGAR turned into
-// match runs (appended to p->runs from `runs_before` on) and the PRead `r`, which the caller pushes once the record's `n_entries`
-// entries (mods or calls, at `entries`) are staged as well.  Returns 1 to go on, else the submission's return value.
+// match runs (appended to p->runs from `mark` on; with `pileup -M` its D operations to p->gaps as well) and the PRead `r`, which
+// the caller pushes once the record's `n_entries` entries (mods or calls, at `entries`) are staged as well.  Returns 1 to go on,
+// else the submission's return value.
+struct BatchMark {  // where a record's runs and gap records begin: what an error rolls back to
+    size_t runs, gaps;
+};
+void roll_back(hm_pileup* p, const BatchMark& m) {
+    p->runs.resize(m.runs);
+    p->gaps.resize(m.gaps);
+}
+
 int stage_alignment(hm_pileup* p, uint32_t order, int32_t flag, int32_t sid, int64_t pos, int32_t mapq, int32_t l_qseq,
                     const uint8_t* seq4, int32_t n_cigar, const uint32_t* cigar, int64_t n_entries, const void* entries, int32_t hp,
-                    PRead& r, size_t& runs_before) {
+                    PRead& r, BatchMark& mark) {
     if (!p) return HM_EINVAL;
     if (hp < 0 || hp > 2) return pfail(p, HM_EINVAL, "haplotype partition must be 0, 1 or 2");
     if (hp && p->partitions != 2) return pfail(p, HM_ESTATE, "haplotype partition given but the partitions option is off");
@@ -1718,7 +1872,7 @@ int stage_alignment(hm_pileup* p, uint32_t order, int32_t flag, int32_t sid, int
         }
     }
     // cigar_to_alignment (bam_info.cpp:262-371) without the strings: match runs + column count
-    runs_before = p->runs.size();
+    mark = BatchMark{p->runs.size(), p->gaps.size()};
     int opi = 0;
     int64_t qi = -1, si = -1;
     if (n_cigar > 0) {
@@ -1741,20 +1895,21 @@ int stage_alignment(hm_pileup* p, uint32_t order, int32_t flag, int32_t sid, int
             qi += num; as_size += num;
             if (num) open = false;
         } else if (op == 2 || op == 3) {  // D N
+            if (p->bedmethyl && op == 2 && num) p->gaps.push_back(PGap{p->seq_off[sid] + pos + si + 1, (int32_t)num, (int32_t)p->reads.size()});
             si += num; as_size += num;
             if (num) open = false;
         } else if (op == 4 || op == 5 || op == 6) {  // S H P: no columns
         } else {
-            p->runs.resize(runs_before);
+            roll_back(p, mark);
             return pfail(p, HM_EDATA, "Unrecognised CIGAR operation");
         }
         if (qi >= l_qseq || pos + si >= ssize) {
-            p->runs.resize(runs_before);
+            roll_back(p, mark);
             return pfail(p, HM_EDATA, qi >= l_qseq ? "CIGAR consumes more bases than SEQ holds"
                                                     : "alignment runs past the end of the reference sequence");
         }
     }
-    if (as_size >= (int64_t(1) << 31)) { p->runs.resize(runs_before); return pfail(p, HM_EINVAL, "alignment too long"); }
+    if (as_size >= (int64_t(1) << 31)) { roll_back(p, mark); return pfail(p, HM_EINVAL, "alignment too long"); }
     r = PRead{};
     r.seq4_off = (int64_t)p->slab.size();
     r.plane_off = p->plane_len;
@@ -1825,6 +1980,10 @@ int hm_pileup_set_option(hm_pileup_t* p, const char* key, double value) {
                 return pfail(p, HM_EINVAL, "pattern_span must be an integer in 1 .. 65536");
             p->pattern_span = (int)value;
         }
+    } else if (k == "bedmethyl") {  // the reference CpGs are listed and their counters sized when the reference arrives
+        if (!p->seq_off.empty()) return pfail(p, HM_ESTATE, "bedmethyl must be set before hm_pileup_set_reference");
+        if (value != 0.0 && value != 1.0) return pfail(p, HM_EINVAL, "bedmethyl must be 0 or 1");
+        p->bedmethyl = (int)value;
     } else return pfail(p, HM_EINVAL, "unknown option " + k);
     return HM_OK;
 }
@@ -1891,7 +2050,7 @@ int hm_pileup_set_reference(hm_pileup_t* p, int32_t n_seqs, const int64_t* seq_l
                 HIP_TRY(hipMemsetAsync(p->hp_ncov[k], 0, bytes, p->stream));
             }
         }
-        if (p->patterns) {
+        if (p->patterns || p->bedmethyl) {
             const int rc = list_reference_cpgs(p);
             if (rc != HM_OK) return rc;
         }
@@ -1919,8 +2078,8 @@ int hm_pileup_submit_read_hp(hm_pileup_t* p, uint32_t order, int32_t flag, int32
                              int32_t l_qseq, const uint8_t* seq4, int32_t n_cigar, const uint32_t* cigar, int64_t n_mods,
                              const hm_mod_t* mods, int32_t hp) {
     PRead r;
-    size_t runs_before;
-    const int rc = stage_alignment(p, order, flag, sid, pos, mapq, l_qseq, seq4, n_cigar, cigar, n_mods, mods, hp, r, runs_before);
+    BatchMark mark;
+    const int rc = stage_alignment(p, order, flag, sid, pos, mapq, l_qseq, seq4, n_cigar, cigar, n_mods, mods, hp, r, mark);
     if (rc != 1) return rc;
     const int32_t ri = (int32_t)p->reads.size();
     const size_t mods_before = p->mods.size();
@@ -1928,7 +2087,7 @@ int hm_pileup_submit_read_hp(hm_pileup_t* p, uint32_t order, int32_t flag, int32
     for (int64_t i = 0; i < n_mods; ++i) {
         const hm_mod_t& m = mods[i];
         if (m.qoff < 0 || m.qoff >= l_qseq) {  // leave the staged batch as it was
-            p->runs.resize(runs_before);
+            roll_back(p, mark);
             p->mods.resize(mods_before);
             p->n_m_mods = m_before;
             return pfail(p, HM_EDATA, "modification offset outside the read");
@@ -1947,8 +2106,8 @@ int hm_pileup_submit_read_calls(hm_pileup_t* p, uint32_t order, int32_t flag, in
                                 int32_t l_qseq, const uint8_t* seq4, int32_t n_cigar, const uint32_t* cigar,
                                 int64_t n_calls, const hm_call_t* calls, int32_t hp) {
     PRead r;
-    size_t runs_before;
-    const int rc = stage_alignment(p, order, flag, sid, pos, mapq, l_qseq, seq4, n_cigar, cigar, n_calls, calls, hp, r, runs_before);
+    BatchMark mark;
+    const int rc = stage_alignment(p, order, flag, sid, pos, mapq, l_qseq, seq4, n_cigar, cigar, n_calls, calls, hp, r, mark);
     if (rc != 1) return rc;
     // what apply_calls refuses (hm_bam.cpp): an offset outside the read; calls not strictly increasing per strand, FWD first
     const int32_t ri = (int32_t)p->reads.size();
@@ -1962,7 +2121,7 @@ int hm_pileup_submit_read_calls(hm_pileup_t* p, uint32_t order, int32_t flag, in
         const bool outside = c.qoff < 0 || c.qoff >= l_qseq;
         if (c.strand != strand && c.strand == 1) { strand = 1; last = -1; }
         if (outside || c.strand != strand || c.qoff <= last) {  // leave the staged batch as it was
-            p->runs.resize(runs_before);
+            roll_back(p, mark);
             p->calls.resize(calls_before);
             return outside ? pfail(p, HM_EDATA, "call offset outside the read")
                            : pfail(p, HM_EINVAL, "calls are not strictly increasing per strand, FWD strand first");
@@ -1987,6 +2146,7 @@ int hm_pileup_run(hm_pileup_t* p) {
         for (int i = 0; i < n_runs; ++i) { p->col0[i] = cols; cols += p->runs[i].len; }
         p->col0[n_runs] = cols;
         const int64_t n_mods = (int64_t)p->mods.size(), n_calls = (int64_t)p->calls.size();
+        const int64_t n_gaps = p->bedmethyl && p->n_cpg ? (int64_t)p->gaps.size() : 0;
 
         p->d_slab.reserve(p->slab.size() + 4);
         p->d_reads.reserve(sizeof(PRead) * (size_t)n_reads);
@@ -2006,6 +2166,10 @@ int hm_pileup_run(hm_pileup_t* p) {
         HIP_TRY(hipMemcpyAsync(p->d_col0.p, p->col0.data(), sizeof(int64_t) * ((size_t)n_runs + 1), hipMemcpyHostToDevice, st));
         if (n_mods) HIP_TRY(hipMemcpyAsync(p->d_mods.p, p->mods.data(), sizeof(PMod) * (size_t)n_mods, hipMemcpyHostToDevice, st));
         if (n_calls) HIP_TRY(hipMemcpyAsync(p->d_calls.p, p->calls.data(), sizeof(PCall) * (size_t)n_calls, hipMemcpyHostToDevice, st));
+        if (n_gaps) {
+            p->d_gaps.reserve(sizeof(PGap) * (size_t)n_gaps);
+            HIP_TRY(hipMemcpyAsync(p->d_gaps.p, p->gaps.data(), sizeof(PGap) * (size_t)n_gaps, hipMemcpyHostToDevice, st));
+        }
         HIP_TRY(hipMemsetAsync(p->d_plane.p, 0, 4 * (size_t)std::max<int64_t>(p->plane_len, 1), st));
         HIP_TRY(hipMemsetAsync(p->d_matches.p, 0, 4 * (size_t)n_reads, st));
 
@@ -2033,7 +2197,14 @@ int hm_pileup_run(hm_pileup_t* p) {
                                    n_runs, cols, p->d_reads.as<PRead>(), p->d_slab.as<uint8_t>(), p->d_ref.as<char>(),
                                    p->d_plane.as<uint32_t>(), p->d_matches.as<int32_t>(), p->min_pi, pattern_rule(p), p->d_precs.as<PWin>(),
                                    p->d_pcounter.as<unsigned long long>());
+            if (p->bedmethyl && p->n_cpg)
+                hipLaunchKernelGGL(depth_kernel, dim3((unsigned)pblocks), dim3(TPB), 0, st, p->d_runs.as<PRun>(), p->d_col0.as<int64_t>(), n_runs,
+                                   cols, p->d_reads.as<PRead>(), p->d_slab.as<uint8_t>(), p->d_ref.as<char>(), p->seq_off.back(),
+                                   p->d_plane.as<uint32_t>(), p->d_matches.as<int32_t>(), p->min_pi, depth_counters(p));
         }
+        if (n_gaps)  // deletions are rare next to columns: one thread each
+            hipLaunchKernelGGL(depth_gap_kernel, dim3(grid_for(n_gaps, 1024)), dim3(TPB), 0, st, p->d_gaps.as<PGap>(), n_gaps,
+                               p->d_reads.as<PRead>(), p->d_matches.as<int32_t>(), p->min_pi, depth_counters(p));
         HIP_TRY(hipGetLastError());
         unsigned long long n = 0, n_win = 0;
         HIP_TRY(hipMemcpyAsync(&n, p->d_counter.p, sizeof n, hipMemcpyDeviceToHost, st));
@@ -2120,12 +2291,18 @@ int hm_pileup_count(hm_pileup_t* p, const uint8_t thr[3]) {
                                p->n_precs, (uint32_t)thr[0], p->patterns, p->d_phist.as<uint32_t>());
             HIP_TRY(hipGetLastError());
         }
+        if (p->bedmethyl && p->n_cpg && p->n_recs) {  // the records are still resident: the CpG ones are the members
+            hipLaunchKernelGGL(depth_count_kernel, dim3(grid_for(p->n_recs, 1 << 16)), dim3(TPB), 0, p->stream, p->d_recs.as<PRec>(), p->n_recs,
+                               (uint32_t)thr[0], depth_counters(p));
+            HIP_TRY(hipGetLastError());
+        }
         if (p->patterns) HIP_TRY(hipMemsetAsync(p->d_pcounter.p, 0, sizeof(unsigned long long), p->stream));
         HIP_TRY(hipMemsetAsync(p->d_counter.p, 0, sizeof(unsigned long long), p->stream));
         HIP_TRY(hipStreamSynchronize(p->stream));
         p->n_recs = 0;
         p->n_precs = 0;
         p->patterns_counted = p->patterns != 0;
+        p->bedmethyl_counted = p->bedmethyl != 0;
         return HM_OK;
     });
 }
@@ -2160,6 +2337,29 @@ int64_t hm_pileup_fetch_patterns(hm_pileup_t* p, int64_t lo, int64_t hi, int64_t
     if (rc != HM_OK) return rc;
     if (ranks[1] <= ranks[0]) return 0;
     return compact_rows(p, PatSel{pattern_rule(p), p->d_phist.as<uint32_t>(), min_reads}, ranks[0], ranks[1], out, cap, no_hook, no_hook);
+}
+
+// ---- `pileup -M` ------------------------------------------------------------------------------------------------------------------
+int64_t hm_pileup_fetch_bedmethyl(hm_pileup_t* p, int32_t part, int64_t lo, int64_t hi, int64_t min_valid, hm_bedmethyl_t* out, int64_t cap) {
+    if (!p) return HM_EINVAL;
+    if (!p->bedmethyl || p->seq_off.empty()) return pfail(p, HM_ESTATE, "hm_pileup_fetch_bedmethyl without option bedmethyl (then hm_pileup_set_reference)");
+    if (!p->bedmethyl_counted) return pfail(p, HM_ESTATE, "hm_pileup_fetch_bedmethyl before hm_pileup_count");
+    if (part < 0 || part > 2) return pfail(p, HM_EINVAL, "hm_pileup_fetch_bedmethyl: part must be 0, 1 or 2");
+    if (part && p->partitions != 2) return pfail(p, HM_ESTATE, "hm_pileup_fetch_bedmethyl: part 1 / 2 without the partitions option");
+    if (lo < 0 || hi < lo) return pfail(p, HM_EINVAL, "hm_pileup_fetch_bedmethyl: bad range");
+    if (min_valid < 0) return pfail(p, HM_EINVAL, "hm_pileup_fetch_bedmethyl: min_valid must be >= 0");
+    if (hi == lo || !p->n_cpg) return 0;
+    int64_t ranks[2] = {0, 0};
+    const int rc = guarded(p, [&] {  // the reference CpGs of [lo, hi) are the ranks [ranks[0], ranks[1])
+        hipLaunchKernelGGL(pattern_ranks_kernel, dim3(1), dim3(64), 0, p->stream, p->d_cpg.as<int64_t>(), p->n_cpg, lo, hi, p->d_pranks.as<int64_t>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(ranks, p->d_pranks.p, sizeof ranks, hipMemcpyDeviceToHost, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        return HM_OK;
+    });
+    if (rc != HM_OK) return rc;
+    if (ranks[1] <= ranks[0]) return 0;
+    return compact_rows(p, BmSel{p->d_cpg.as<int64_t>(), depth_counters(p, part).bm, min_valid}, ranks[0], ranks[1], out, cap, no_hook, no_hook);
 }
 
 int hm_pattern_stats(const hm_pattern_t* w, double out[4]) {

@@ -55,6 +55,13 @@ i-th call is methylated) -- the one output that keeps the calls of a molecule to
 windows with at least min_reads such reads (PATTERN_DTYPE), `pattern_stats(row)` -- host only, the C library's -- their methylation
 entropy, epipolymorphism, proportion of discordant reads and level, `pu.patterns_bed(rows)` the text of <prefix>.patterns.CpG.bed.
 
+bedMethyl rows (`pileup -M`, `bedmethyl=True`): per reference CpG how many reads that pass -q / -f gave a methylated or an
+unmethylated call (n_mod, n_canon), covered the intact CG without a call (n_nocall), showed another base at the C or the G or
+broke off between them (n_diff), or have the C inside a deletion (n_delete) -- what tells "10 of 10 reads methylated" from "10 of
+the 40 reads there could be called at all".  `pu.bedmethyl(lo, hi, min_valid, partition)` are the CpGs some read was classed at
+with n_mod + n_canon >= min_valid (BEDMETHYL_DTYPE), `pu.bedmethyl_bed(rows)` the text of <prefix>.bedmethyl.CpG.bed in modkit's
+18 columns.
+
 Fused with the caller (`pileup -K`): `pu.add_called(read, calls)` takes the records `MethylationCaller` returned for an aligned read
 instead of parsed MM / ML -- the same effect as add() of that read carrying the calls as tags, without the tag text.
 
@@ -91,6 +98,8 @@ SITE_BINS = 3 * 256 * 256                                                       
 DOMAIN_DTYPE = np.dtype([("start", "<i8"), ("end", "<i8"), ("pcov", "<i8"), ("ncov", "<i8"), ("n_loci", "<i4"), ("state", "<u4"),
                          ("motif", "<u4"), ("flags", "<u4"), ("level", "<f8"), ("score", "<f8")])  # hm_domain_t, 64 bytes
 PATTERN_DTYPE = np.dtype([("start", "<i8"), ("end", "<i8"), ("counts", "<u4", (16,)), ("n", "<u4"), ("k", "<u4")])  # hm_pattern_t, 88 bytes
+BEDMETHYL_DTYPE = np.dtype([("gpos", "<i8"), ("n_mod", "<u4"), ("n_canon", "<u4"), ("n_nocall", "<u4"), ("n_diff", "<u4"),
+                            ("n_delete", "<u4"), ("reserved", "<u4")])                # hm_bedmethyl_t, 32 bytes
 PATTERN_SPAN, PATTERN_MIN_READS = 150, 10                # `pileup -E`'s default -w and -o
 DOMAIN_AFTER_BREAK, DOMAIN_BEFORE_BREAK = 1, 2                                        # HM_DOMAIN_AFTER_BREAK, HM_DOMAIN_BEFORE_BREAK
 DOMAIN_PASS_SUMMARY, DOMAIN_PASS_CODES, DOMAIN_PASS_SEGMENTS, DOMAIN_KEEP = 0, 1, 2, 2   # HM_DOMAIN_PASS_*, HM_DOMAIN_KEEP
@@ -491,7 +500,7 @@ def locate(offsets, gpos) -> Tuple[np.ndarray, np.ndarray]:
 class MethylationPileup:
     def __init__(self, genome: Sequence[Tuple[str, str]], device: int = 0, min_mapq: int = 0, min_pi: float = 0.0,
                  planes=None, partitions: bool = False, partition_planes=None, bases=None, patterns: int = 0,
-                 pattern_span: int = PATTERN_SPAN):
+                 pattern_span: int = PATTERN_SPAN, bedmethyl: bool = False):
         """genome: [(name, SEQUENCE)].  bases: optional, the concatenated upper-case bases of the whole reference as a
         C-contiguous uint8 buffer (ndarray, bytes, memoryview), handed to the engine as it is -- for references of gigabases,
         where joining, upper-casing and encoding strings would copy them three times; the second member of each genome entry
@@ -501,7 +510,8 @@ class MethylationPileup:
         partitions: also count per haplotype (HP 1 / 2); partition_planes: optional ((pcov1, ncov1), (pcov2, ncov2)) int32
         torch CUDA tensors for them, like `planes`.
         patterns: 0, or k in (2, 3, 4): also count the read-level patterns over windows of k adjacent reference CpGs whose first
-        and last locus are at most pattern_span (1 .. 65 536) bases apart (+72 B per reference CpG, 8 B per window record)."""
+        and last locus are at most pattern_span (1 .. 65 536) bases apart (+72 B per reference CpG, 8 B per window record).
+        bedmethyl: also count the depth classes per reference CpG (+28 B per reference CpG, +68 B with partitions)."""
         self._L = lib()
         self._h = C.c_void_p()
         if self._L.hm_pileup_create(C.byref(self._h), device) != 0:
@@ -524,6 +534,8 @@ class MethylationPileup:
         if patterns:
             self._check(self._L.hm_pileup_set_option(self._h, b"patterns", float(patterns)))
             self._check(self._L.hm_pileup_set_option(self._h, b"pattern_span", float(pattern_span)))
+        if bedmethyl:
+            self._check(self._L.hm_pileup_set_option(self._h, b"bedmethyl", 1.0))
         if planes is not None:
             self._check(self._L.hm_pileup_use_planes(self._h, *(C.c_void_p(t.data_ptr()) for t in planes)))
         if bases is None:
@@ -797,6 +809,26 @@ class MethylationPileup:
         for s, k, r in zip(sid, soff, rows):
             text.append("%s\t%d\t%d\t%d\t%.6g\t%.6g\t%.6g\t%.6g\t" % (self.names[s], k, k + (r["end"] - r["start"]), r["n"], *pattern_stats(r))
                         + ",".join("%d" % c for c in r["counts"][:1 << int(r["k"])]) + "\n")
+        return "".join(text)
+
+    def bedmethyl(self, lo: int = 0, hi: Optional[int] = None, min_valid: int = 1, partition: int = 0) -> np.ndarray:
+        """the reference CpGs of [lo, hi), ascending (BEDMETHYL_DTYPE), at which a read was classed and n_mod + n_canon >= min_valid
+        (0: also those seen only as nocall, diff or delete).  partition 1 / 2: the reads of that haplotype.  Needs bedmethyl=True,
+        after count()."""
+        hi = self.n_loci if hi is None else hi
+        return self._rows(self._L.hm_pileup_fetch_bedmethyl, BEDMETHYL_DTYPE, partition, lo, hi, min_valid)
+
+    def bedmethyl_bed(self, rows: np.ndarray) -> str:
+        """the text of <prefix>.bedmethyl.CpG.bed, modkit's 18 columns: chrom, start, end, m, min(1000, Nvalid), ., start, end,
+        255,0,0, Nvalid, percent modified, Nmod, Ncanonical, Nother_mod = 0, Ndelete, Nfail = 0, Ndiff, Nnocall"""
+        sid, soff = locate(self.offsets, rows["gpos"])
+        text = []
+        for s, k, r in zip(sid, soff, rows):
+            nm, nc = int(r["n_mod"]), int(r["n_canon"])
+            nv = nm + nc
+            text.append("%s\t%d\t%d\tm\t%d\t.\t%d\t%d\t255,0,0\t%d\t%.2f\t%d\t%d\t0\t%d\t0\t%d\t%d\n" % (
+                self.names[s], k, k + 1, min(1000, nv), k, k + 1, nv, 100.0 * nm / nv if nv else 0.0, nm, nc, r["n_delete"], r["n_diff"],
+                r["n_nocall"]))
         return "".join(text)
 
     def domains(self, ctx: int, lo: int = 0, hi: Optional[int] = None, A: Optional[int] = None, B: Optional[int] = None,

@@ -237,7 +237,8 @@ void hm_pileup_destroy(hm_pileup_t* p);
 const char* hm_pileup_last_error(const hm_pileup_t* p); /* p may be NULL: error of a failed create */
 /* options: "min_mapq" (-q, default 0), "min_pi" (-f, default 0.0), "partitions" (0 default, or 2: haplotype-resolved
  * counting, see hm_pileup_submit_read_hp; must be set before hm_pileup_set_reference / hm_pileup_use_planes, else HM_ESTATE),
- * "patterns" and "pattern_span" (read-level CpG patterns, at the end of this header) */
+ * "patterns" and "pattern_span" (read-level CpG patterns) and "bedmethyl" (per-CpG depth classes), both near the end of this
+ * header */
 int hm_pileup_set_option(hm_pileup_t* p, const char* key, double value);
 /* HbnDatabase: n_seqs upper-cased sequences back to back in `bases` (seq_len[i] bytes each).  Allocates and
  * zeroes the per-locus planes unless hm_pileup_use_planes was called before. */
@@ -596,6 +597,46 @@ int64_t hm_pileup_fetch_patterns(hm_pileup_t* p, int64_t lo, int64_t hi, int64_t
  * out[2] pdr = 1 - (double)(counts[0] + counts[2^k - 1]) / n, the proportion of discordant reads;
  * out[3] level = 100 * sum popcount(b) counts[b] / (k n).  HM_EINVAL for k outside 2..4, n == 0 or n != the sum of the 2^k bins. */
 int hm_pattern_stats(const hm_pattern_t* w, double out[4]);
+
+/* ---- bedMethyl rows with per-CpG depth classes (`pileup -M`): how many molecules covered a CpG, called or not --
+ * Every output above is built from the reads that carry a usable call at a locus; this one also says how many covered it without
+ * giving one.  REFERENCE CpGs and RANKS are those of the patterns above (ref[g] == 'C' && ref[g + 1] == 'G', both bases in one
+ * sequence, upper-case bytes only); the list is built when either option is on.
+ * A record TAKES PART when hm_pileup_submit_read / _hp / _calls returned 1 for it and it passes -q and -f (the identity test of the
+ * projection); secondary and supplementary records do, as in the counters; a record without entries, or an unmapped one, does not.
+ * A MATCH RUN is a maximal stretch of M / = / X columns with no I, D or N of non-zero length inside; P, S and H neither make
+ * columns nor close a run.  For a record that takes part and a reference CpG g (the C at g, the G at g + 1) at most one CLASS applies:
+ *   1. Column g lies in one of the record's match runs.
+ *      MOD / CANON  the record is a member at g in the patterns' sense: g and g + 1 in one run, the bases as stored C, G, and a 5mC
+ *                   entry at the offset the projection looks up.  MOD when that entry's ML byte is >= thr[CpG] (the >= of
+ *                   hm_pileup_count), else CANON.
+ *      NOCALL       g and g + 1 in one run, the stored bases C, G, and no 5mC entry at that offset.
+ *      nothing      g is the last column of the record's last match run: the alignment ends on the C, the dinucleotide is not covered.
+ *      DIFF         every other case: the stored base at g is not C, the stored base at g + 1 is not G, or the run ends at g with
+ *                   more of the alignment behind it (an insertion between C and G, g + 1 deleted or skipped by N).
+ *   2. DELETE       g lies inside a D operation: a D of length n whose first deleted reference base is s covers s .. s + n - 1.
+ *   3. nothing      g lies inside an N operation, outside the alignment, or only g + 1 is covered.
+ * COUNTERS: five uint32 per reference CpG -- n_mod, n_canon, n_nocall, n_diff, n_delete.  With option "partitions" = 2 there are
+ * three sets: set 0 counts every record that takes part, sets 1 and 2 those submitted with hp 1 or 2.  All of it is an integer
+ * function of the records and thr[0]: nothing depends on launch geometry or on how the records are cut into batches.
+ * A reference CpG is a ROW of a set when its five counters sum to at least 1 and n_mod + n_canon >= min_valid, min_valid >= 0: with
+ * min_valid 0 the CpGs seen only as nocall, diff or delete are listed too.
+ * Option "bedmethyl" (0 off = default, 1), before hm_pileup_set_reference (else HM_ESTATE; HM_EINVAL for another value).  With it
+ * on, hm_pileup_set_reference lists the reference CpGs (8 B each, shared with the patterns; fewer than 2^32) and allocates the
+ * counters (20 B per CpG and set), hm_pileup_run adds NOCALL, DIFF and DELETE behind the projection, and hm_pileup_count adds MOD
+ * and CANON from the resident records before it drops them; the counters accumulate over run / count cycles as the planes do.
+ * Without it nothing is allocated, uploaded or launched.  Not here: CHG / CHH rows; per-strand rows (a read gives one call per CpG
+ * dyad, on its own C, so there is no second strand to report); a no-call band around the threshold (bedMethyl's Nfail is always
+ * 0); codes other than m (Nother_mod is always 0: they never reach the counters); pileup_dist. */
+typedef struct {            /* one reference CpG = one row of <prefix>.bedmethyl.CpG.bed; 32 bytes */
+    int64_t gpos;
+    uint32_t n_mod, n_canon, n_nocall, n_diff, n_delete, reserved;
+} hm_bedmethyl_t;
+/* The rows of set `part` (0 combined, 1 / 2 the haplotype partitions) whose gpos lies in [lo, hi), ascending.  Returns their number
+ * (may exceed cap, or out NULL: then nothing is written).  hi == lo returns 0.  HM_ESTATE without option "bedmethyl", before the
+ * first hm_pileup_count, or for part 1 / 2 without partitions; HM_EINVAL for part outside 0..2, lo < 0, lo > hi or min_valid < 0. */
+int64_t hm_pileup_fetch_bedmethyl(hm_pileup_t* p, int32_t part, int64_t lo, int64_t hi, int64_t min_valid, hm_bedmethyl_t* out,
+                                  int64_t cap);
 
 #ifdef __cplusplus
 }

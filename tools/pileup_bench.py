@@ -17,9 +17,12 @@ segments over the same planes, and the fit of the three contexts from the defaul
 `--patterns K`: the read-level CpG patterns of `pileup -E K`: the timed passes run on an engine without the option first and then on one
 with it; the leg is what the option adds to projection and counting plus one fetch of the rows (D2H included): window records per second,
 rows, share of a pass.
+`--bedmethyl`: the depth classes of `pileup -M`, timed like `--patterns`: the passes on an engine without the option, then on one with
+it; the leg is what the option adds to projection and counting plus one fetch of the rows (D2H included).  The synthetic reads are
+error-free: the column kernel and the record count run at full size, the deletion kernel has nothing to do.
 `--parts N` (with `--domains`): the same segments chained from N equal pieces next to the single fetch (three stateless passes per piece).
 
-    python tools/pileup_bench.py --genome-mb 20 --coverage 10 [--partitions [--asm [--asm-q] [--asm-regions]]] [--sites] [--domains [--fit] [--parts N]] [--patterns K]
+    python tools/pileup_bench.py --genome-mb 20 --coverage 10 [--partitions [--asm [--asm-q] [--asm-regions]]] [--sites] [--domains [--fit] [--parts N]] [--patterns K] [--bedmethyl]
 """
 import argparse
 import ctypes as C
@@ -111,6 +114,7 @@ def main():
                     help="with --domains: also the same segments chained from N equal pieces (hm_pileup_fetch_domains_part, what pileup_dist -D runs)")
     ap.add_argument("--patterns", type=int, default=0, metavar="K", choices=(0, 2, 3, 4),
                     help="time what the read-level CpG patterns over windows of K reference CpGs add (pileup -E K, default span and min reads)")
+    ap.add_argument("--bedmethyl", action="store_true", help="time what the per-CpG depth classes add (pileup -M, min_valid 1)")
     ap.add_argument("--cpu-baseline", action="store_true",
                     help="time the reference's own projection code (oracle/_ref/ref_align -t) on a bounded sample")
     a = ap.parse_args()
@@ -156,7 +160,7 @@ def main():
                 pu.flush()
         pu.flush()
 
-    if a.patterns:                                 # the same passes without the option first: the leg is the difference
+    if a.patterns or a.bedmethyl:                  # the same passes without the option(s) first: the leg is the difference
         one_pass()
         pu.count([128, 128, 128])
         t0 = time.perf_counter()
@@ -167,7 +171,7 @@ def main():
         pu.count([128, 128, 128])
         t_count_off = time.perf_counter() - t0
         pu.close()
-        pu = MethylationPileup(genome, partitions=a.partitions, patterns=a.patterns)
+        pu = MethylationPileup(genome, partitions=a.partitions, patterns=a.patterns, bedmethyl=a.bedmethyl)
     one_pass(pu)                                   # warm-up (allocations)
     wins_per_pass = pu.num_pattern_records()
     recs_per_pass = pu.num_records()
@@ -214,6 +218,27 @@ def main():
         if a.check:                                # a row's reads are window records: all of them at min_reads 1
             n_all = int(pu.patterns(min_reads=1)["n"].astype(np.int64).sum())
             out["check_patterns_rows_hold_the_records"] = bool(n_all == wins_per_pass * (a.repeat + 1))
+    if a.bedmethyl:
+        pu.bedmethyl()                             # warm-up: the row buffer
+        t0 = time.perf_counter()
+        for _ in range(a.repeat):
+            rows = pu.bedmethyl()
+        t_rows = (time.perf_counter() - t0) / a.repeat
+        t_leg = max((t_project - t_project_off + t_count - t_count_off) / a.repeat, 0.0) + t_rows
+        t_pass = (t_project_off + t_count_off) / a.repeat + t_loci
+        out.update(bedmethyl_rows=int(len(rows)), bedmethyl_project_s_per_pass=[round(t_project_off / a.repeat, 4), round(t_project / a.repeat, 4)],
+                   bedmethyl_count_s=[round(t_count_off, 4), round(t_count, 4)], bedmethyl_rows_s=round(t_rows, 4),
+                   bedmethyl_leg_s_per_pass=round(t_leg, 4), bedmethyl_share_of_pass=round(t_leg / (t_pass + t_leg), 4),
+                   bedmethyl_also_patterns=a.patterns)
+        if a.check:                                # Nvalid of a row is the coverage of its locus; a reference CGG also takes CHG records there
+            valid = pu.bedmethyl(min_valid=1)
+            j = np.minimum(np.searchsorted(loci["gpos"], valid["gpos"]), len(loci) - 1)
+            nv = valid["n_mod"].astype(np.int64) + valid["n_canon"]
+            cov = loci["pcov"].astype(np.int64)[j] + loci["ncov"][j]
+            plain = chrom[np.minimum(valid["gpos"] + 2, G - 1)] != 71
+            out["check_bedmethyl_valid_is_the_cpg_coverage"] = bool(
+                len(valid) and (loci["gpos"][j] == valid["gpos"]).all() and (nv <= cov).all() and (nv[plain] == cov[plain]).all()
+                and not valid["n_diff"].any() and not valid["n_delete"].any())
     if a.asm:                                      # select + test + fetch of every tested locus, as the CLI does per sequence
         pu.asm(min_cov=a.asm_min_cov)              # warm-up: the log n! table and the row buffer
         t0 = time.perf_counter()
