@@ -28,6 +28,9 @@
 // -M (ours): also <prefix>.bedmethyl.CpG.bed (under -H also <prefix>.hap1. / <prefix>.hap2.bedmethyl.CpG.bed), modkit's 18 bedMethyl
 // columns per reference CpG: besides the methylated and unmethylated calls the reads that covered the CpG without giving one --
 // no call, another base, a deletion -- counted on the GPU (hm_pileup_fetch_bedmethyl).
+// -L bp (ours): also <prefix>.linkage.CpG.tsv, the within-read co-methylation by distance: per exact distance d <= bp the pairs of
+// calls d bases apart on one molecule by class -- both unmethylated, the two discordant orders, both methylated -- with their
+// concordance and phi coefficient (hm_pileup_fetch_linkage).
 // -K (ours): the input is an aligned BAM that still carries the kinetics tags (pbmm2 keeps fi / fp / ri / rp): the reads are called
 // on the fly by the call engine and their calls go straight to the pileup engine (hm_pileup_submit_read_calls) -- the files
 // `call` followed by `pileup` writes, without the mod-BAM between the two.
@@ -114,6 +117,9 @@ struct PileupOptions {
     bool bedmethyl = false;            // -M: bedMethyl rows with the depth classes per reference CpG -> <prefix>.bedmethyl.CpG.bed
     long long bedmethyl_min_valid = 1; // -v: smallest n_mod + n_canon of a row that is written
     bool bedmethyl_option_given = false, bedmethyl_option_bad = false;  // -v; -v with a value out of range
+    long long linkage = 0;             // -L: within-read co-methylation by distance up to this many bases -> <prefix>.linkage.CpG.tsv
+    long long linkage_min_pairs = 1;   // -z: smallest number of pairs of a distance that is written
+    bool linkage_option_given = false, linkage_option_bad = false;  // -z; -L or -z with a value out of range
     // -K: call on the fly; the options below are `call`'s (hifimeth_call.cpp), same meaning and defaults
     bool kinetics = false;
     bool call_option_given = false;  // any of -m -c -l -p -T: a usage error without -K
@@ -182,6 +188,12 @@ void pileup_usage(const char* exe) {
             "    pass -q and -f, Nnocall covered the intact CG without a call, Ndiff show another base at the C or the G (or break off between\n"
             "    them), Ndelete have the C inside a deletion\n"
             "  -v <int>\n    With -M: smallest Nvalid of a row that is written, >= 0 (0: also CpGs seen only as nocall, diff or delete)\n    Default: 1\n"
+            "  -L <bp>\n    Within-read co-methylation by distance, bp in [2, 16384]: every two CpG calls of one read (one alignment record) that lie\n"
+            "    d <= bp reference bases apart count once under d, as UU, UM, MU or MM (U unmethylated, M methylated by the CpG threshold; the\n"
+            "    first letter is the call at the lower coordinate).  Writes <prefix>.linkage.CpG.tsv: a header line, then per distance dist, n,\n"
+            "    n_uu, n_um, n_mu, n_mm, concordance (n_uu + n_mm) / n and the phi coefficient r (nan when a margin is empty).  The combined\n"
+            "    reads are counted, with or without -H\n"
+            "  -z <int>\n    With -L: smallest number of pairs of a distance that is written, >= 0 (0: every distance from 2 to bp)\n    Default: 1\n"
             "  -K\n    The input is an aligned BAM that carries the kinetics tags fi / fp / ri / rp instead of MM / ML: call 5mC on the\n"
             "    fly and pile the calls up directly.  For equal -c -l -p -T -q -f the output files are byte-identical to those of\n"
             "    `%s call` on that BAM followed by `%s pileup` on its output; no mod-BAM is written.  (Give -T explicitly\n"
@@ -959,6 +971,26 @@ bool write_bedmethyl(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, i
         });
 }
 
+// <prefix>.linkage.CpG.tsv: the header, then one row per distance with at least -z pairs; the statistics are hm_linkage_stats'
+// (a distance without pairs, written under -z 0, has none: nan).  false on an engine error (recorded) or a file error (reported).
+bool write_linkage(hm_pileup_t* pe, const PileupOptions& o) {
+    std::vector<hm_linkage_t> rows((size_t)o.linkage);
+    const int64_t n = hm_pileup_fetch_linkage(pe, o.linkage_min_pairs, rows.data(), (int64_t)rows.size());
+    if (n < 0) return false;
+    const std::string path = o.prefix + ".linkage.CpG.tsv";
+    FILE* f = fopen(path.c_str(), "w");
+    if (!f) { fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str()); return false; }
+    fprintf(f, "#dist\tn\tn_uu\tn_um\tn_mu\tn_mm\tconcordance\tr\n");
+    for (int64_t i = 0; i < n; ++i) {
+        const hm_linkage_t& r = rows[(size_t)i];
+        double st[2] = {NAN, NAN};
+        hm_linkage_stats(&r, st);
+        fprintf(f, "%u\t%llu\t%llu\t%llu\t%llu\t%llu\t%.6g\t%.6g\n", r.dist, (unsigned long long)(r.n_uu + r.n_um + r.n_mu + r.n_mm),
+                (unsigned long long)r.n_uu, (unsigned long long)r.n_um, (unsigned long long)r.n_mu, (unsigned long long)r.n_mm, st[0], st[1]);
+    }
+    return fclose(f) == 0;
+}
+
 // -u: one lo:hi pair for all contexts or three, each pair possibly nan; false unless the whole text parses
 bool parse_levels(const char* text, double lo[3], double hi[3]) {
     std::vector<std::string> items(1);
@@ -1397,6 +1429,16 @@ int cmd_pileup(int argc, char** argv) {
             else if (a == "-w") { if (x < 1 || x > 65536) o.pattern_option_bad = true; else o.pattern_span = x; }
             else { if (x < 1) o.pattern_option_bad = true; else o.pattern_min_reads = x; }
         }
+        else if (a == "-L" || a == "-z") {  // the whole value must parse, and lie in the option's range
+            if (a == "-z") o.linkage_option_given = true;
+            const char* v = argv[++i];
+            char* end = nullptr;
+            errno = 0;
+            const long long x = strtoll(v, &end, 10);
+            if (end == v || *end || errno) o.linkage_option_bad = true;
+            else if (a == "-L") { if (x < 2 || x > 16384) o.linkage_option_bad = true; else o.linkage = x; }
+            else { if (x < 0) o.linkage_option_bad = true; else o.linkage_min_pairs = x; }
+        }
         else if (a == "-v") {  // the whole value must parse
             o.bedmethyl_option_given = true;
             const char* v = argv[++i];
@@ -1463,6 +1505,9 @@ int cmd_pileup(int argc, char** argv) {
     if (bad_patterns) { fprintf(stderr, "ERROR: %s\n", bad_patterns); pileup_usage(argv[0]); return EXIT_FAILURE; }
     const char* bad_bedmethyl = o.bedmethyl_option_given && !o.bedmethyl ? "-v needs -M" : o.bedmethyl_option_bad ? "-v must be an integer >= 0" : nullptr;
     if (bad_bedmethyl) { fprintf(stderr, "ERROR: %s\n", bad_bedmethyl); pileup_usage(argv[0]); return EXIT_FAILURE; }
+    const char* bad_linkage = o.linkage_option_bad ? "-L must be an integer in [2, 16384], -z an integer >= 0"
+                              : o.linkage_option_given && !o.linkage ? "-z needs -L" : nullptr;
+    if (bad_linkage) { fprintf(stderr, "ERROR: %s\n", bad_linkage); pileup_usage(argv[0]); return EXIT_FAILURE; }
     const bool sites = !o.control.empty() || o.rates_given;
     if (o.kinetics && o.model_dir.empty()) o.model_dir = exe_dir() + "/../weights";
     o.ref = argv[i];
@@ -1497,6 +1542,9 @@ int cmd_pileup(int argc, char** argv) {
     if (o.bedmethyl)
         fprintf(stderr, "bedmethyl: reference CpGs with Nvalid >= %lld, 18 columns -> %s.bedmethyl.CpG.bed%s\n", o.bedmethyl_min_valid, o.prefix.c_str(),
                 o.haplotypes ? ", .hap1. and .hap2. as well" : "");
+    if (o.linkage)
+        fprintf(stderr, "linkage: pairs of CpG calls of one read up to %lld bases apart, distances with >= %lld pairs -> %s.linkage.CpG.tsv\n", o.linkage,
+                o.linkage_min_pairs, o.prefix.c_str());
     if (o.kinetics)
         fprintf(stderr, "kinetics: called on the fly (models %s, contexts%s%s%s, min read length %d, precision %d, trunk %s)\n", o.model_dir.c_str(),
                 o.ctx_mask & 1 ? " CpG" : "", o.ctx_mask & 2 ? " CHG" : "", o.ctx_mask & 4 ? " CHH" : "", o.min_read_size, o.precision,
@@ -1533,6 +1581,7 @@ int cmd_pileup(int argc, char** argv) {
     if (o.patterns && (hm_pileup_set_option(pe, "patterns", o.patterns) != HM_OK || hm_pileup_set_option(pe, "pattern_span", (double)o.pattern_span) != HM_OK))
         return die("patterns");
     if (o.bedmethyl && hm_pileup_set_option(pe, "bedmethyl", 1) != HM_OK) return die("bedmethyl");
+    if (o.linkage && hm_pileup_set_option(pe, "linkage", (double)o.linkage) != HM_OK) return die("linkage");
     if (fa.names.empty()) { fprintf(stderr, "ERROR: no sequence in %s\n", o.ref.c_str()); return EXIT_FAILURE; }
     if (hm_pileup_set_reference(pe, (int32_t)fa.names.size(), fa.length.data(), fa.bases.data()) != HM_OK) return die("reference");
 
@@ -1686,6 +1735,7 @@ int cmd_pileup(int argc, char** argv) {
         fclose(out[0]);
         if (!ok) return die("bedmethyl");
     }
+    if (o.linkage && !write_linkage(pe, o)) return die("linkage");
     if (sites) {
         const int rc = write_sites(pe, fa, o, control_sid, o.threads);
         if (rc < 0) return die("sites");

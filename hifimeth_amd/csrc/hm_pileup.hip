@@ -25,6 +25,10 @@
 //   depth_kernel    thread per column      : (`pileup -M`) a column on the C of a reference CG whose read is no member there adds
 //                   NOCALL or DIFF to the CpG's depth counters; depth_gap_kernel, thread per D operation, adds DELETE;
 //                   depth_count_kernel, thread per resident record, adds MOD or CANON; BmSel the bedMethyl rows
+//   linkage_pair_kernel  thread per member : (`pileup -L`) MemberSel lists a batch's CpG members in column order; a member pairs with
+//                   the later members of its record within max_dist and adds each pair to three 256-bin histograms per distance;
+//                   linkage_reduce_kernel, workgroup per distance, turns them into UU / UM / MU / MM once the threshold is known;
+//                   LinkSel the rows
 //   select_count / loci_scan / select_write   the rows of a SELECTION over a range in ascending order (count per block, scan,
 //                   write); every output below is a selection struct (its planes, pred, take) plus per-row kernels
 //   LociSel         covered loci
@@ -761,6 +765,127 @@ struct BmSel {
         w.n_diff = c[BM_DIFF];
         w.n_delete = c[BM_DELETE];
         w.reserved = 0;
+        return true;
+    }
+};
+
+// ---- within-read CpG co-methylation by distance (`pileup -L`; include/hifimeth_hip.h has the definition) ---------------------
+// The thresholds arrive with hm_pileup_count, the pairs of a batch are gone by then, and there are too many to keep.  So the
+// pairs are counted threshold-free: per distance d three 256-bin uint64 histograms over the pair's two ML bytes,
+// lh[(d * 3 + LH_MIN) * 256 + min(pa, pb)], ... LH_MAX ... max(pa, pb), ... LH_FIRST ... pa (the lower coordinate's), from
+// which the four classes follow for any threshold (linkage_reduce_kernel).  Integer atomics only: any order gives the same table.
+constexpr int LINK_MAX_DIST = 16384;
+enum LinkHist { LH_MIN = 0, LH_MAX, LH_FIRST, LH_HISTS };
+
+struct PMember {        // 16 bytes: a member locus of record `read` of the batch
+    int64_t g;
+    int32_t read;
+    uint32_t prob;
+};
+static_assert(sizeof(PMember) == 16, "member entries are 16 bytes");
+
+// The batch's member list over its aligned COLUMNS [0, n_cols): column order keeps the members of a record together and ascending
+// in g.  The member test is pattern_kernel's (restated: that kernel stays as it is) behind -q / -f.
+struct MemberSel {
+    using Row = PMember;
+    const PRun* runs;
+    const int64_t* col0;
+    int n_runs;
+    const PRead* reads;
+    const uint8_t* slab;
+    const char* ref;
+    const uint32_t* plane;
+    const int32_t* matches;
+    double min_pi;
+    // the ML byte of the member at column c, or -1
+    __device__ int member(int64_t c, Row& m) const {
+        const int ri = find_run(col0, n_runs, c);
+        const PRun run = runs[ri];
+        const int o = (int)(c - col0[ri]);
+        if (run.len - o < 2) return -1;
+        const PRead rd = reads[run.read];
+        if (!read_takes_part(rd, run.read, matches, min_pi)) return -1;
+        const int qp = run.q0 + o;
+        const int64_t g = run.g0 + o;
+        if (stored_base(slab, rd, qp) != 'C' || stored_base(slab, rd, qp + 1) != 'G' || ref[g] != 'C' || ref[g + 1] != 'G') return -1;
+        const uint32_t v = plane[rd.plane_off + (rd.rev ? rd.l_qseq - 1 - (qp + 1) : qp)];
+        if (!(v & 0x100u)) return -1;
+        m.g = g;
+        m.read = run.read;
+        m.prob = v & 255u;
+        return (int)m.prob;
+    }
+    __device__ bool pred(int64_t c) const {
+        Row m;
+        return member(c, m) >= 0;
+    }
+    __device__ bool take(int64_t c, Row& m) const { return member(c, m) >= 0; }
+};
+
+// One thread per list entry i: the pairs (i, j), j behind i in the same record with 2 <= g_j - g_i <= max_dist, three atomics each.
+// The walk ends at the record's last member or max_dist bases on; no workgroup waits for another.
+__global__ __launch_bounds__(TPB) void linkage_pair_kernel(const PMember* __restrict__ list, int64_t n, int max_dist,
+                                                            unsigned long long* __restrict__ lh) {
+    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
+        const PMember a = list[i];
+        for (int64_t j = i + 1; j < n; ++j) {
+            const PMember b = list[j];
+            if (b.read != a.read) break;
+            const int64_t d = b.g - a.g;
+            if (d > max_dist) break;
+            if (d < 2) continue;  // members are CG dinucleotides: never nearer than 2
+            unsigned long long* h = lh + (size_t)d * (LH_HISTS * 256);
+            atomicAdd(&h[LH_MIN * 256 + min(a.prob, b.prob)], 1ull);
+            atomicAdd(&h[LH_MAX * 256 + max(a.prob, b.prob)], 1ull);
+            atomicAdd(&h[LH_FIRST * 256 + a.prob], 1ull);
+        }
+    }
+}
+
+// One workgroup per distance d, thread v holds bin v: with t the CpG threshold, n = sum min, MM = sum_{v >= t} min,
+// UU = sum_{v < t} max, MU = sum_{v >= t} first - MM, UM = n - MM - UU - MU -> tab[d * 4 + (UU, UM, MU, MM)]
+__global__ __launch_bounds__(256) void linkage_reduce_kernel(const unsigned long long* __restrict__ lh, uint32_t thr,
+                                                              unsigned long long* __restrict__ tab) {
+    __shared__ unsigned long long part[256 / 64][4];
+    const unsigned long long* h = lh + (size_t)blockIdx.x * (LH_HISTS * 256);
+    const uint32_t v = threadIdx.x;
+    const unsigned long long mn = h[LH_MIN * 256 + v], mx = h[LH_MAX * 256 + v], fi = h[LH_FIRST * 256 + v];
+    unsigned long long s[4] = {mn, v >= thr ? mn : 0ull, v < thr ? mx : 0ull, v >= thr ? fi : 0ull};  // n, MM, UU, M at the first
+    for (int c = 0; c < 4; ++c) {
+        for (int d = 32; d; d >>= 1) s[c] += __shfl_down(s[c], d);
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][c] = s[c];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long t[4];
+        for (int c = 0; c < 4; ++c) t[c] = part[0][c] + part[1][c] + part[2][c] + part[3][c];
+        const unsigned long long n = t[0], mm = t[1], uu = t[2], mu = t[3] - mm;
+        unsigned long long* o = tab + (size_t)blockIdx.x * 4;
+        o[0] = uu;
+        o[1] = n - mm - uu - mu;
+        o[2] = mu;
+        o[3] = mm;
+    }
+}
+
+// the rows over DISTANCES: n = the four counts' sum >= min_pairs
+struct LinkSel {
+    using Row = hm_linkage_t;
+    const unsigned long long* tab;
+    int64_t min_pairs;
+    __device__ bool pred(int64_t d) const {
+        const unsigned long long* c = tab + d * 4;
+        return c[0] + c[1] + c[2] + c[3] >= (unsigned long long)min_pairs;
+    }
+    __device__ bool take(int64_t d, Row& w) const {
+        if (!pred(d)) return false;
+        const unsigned long long* c = tab + d * 4;
+        w.dist = (uint32_t)d;
+        w.reserved = 0;
+        w.n_uu = c[0];
+        w.n_um = c[1];
+        w.n_mu = c[2];
+        w.n_mm = c[3];
         return true;
     }
 };
@@ -1555,6 +1680,13 @@ struct hm_pileup {
     int bedmethyl = 0;
     DevBuf d_bm{EXACT}, d_gaps{HALF};
     bool bedmethyl_counted = false;
+    // `pileup -L` ("linkage" = max_dist), all of it only with the option on: three 256-bin uint64 histograms per distance
+    // (6 144 B each), resident from hm_pileup_set_reference on; the member list of the batch that runs; the four counts per
+    // distance of a fetch
+    int linkage = 0;
+    DevBuf d_lhist{EXACT}, d_ltab{EXACT}, d_members{HALF};
+    bool linkage_counted = false;
+    uint32_t linkage_thr = 0;  // thr[CpG] of the last hm_pileup_count
     int64_t n_recs = 0;
     bool bins_ready = false;
 
@@ -1811,6 +1943,19 @@ int list_reference_cpgs(hm_pileup* p) {
     return HM_OK;
 }
 
+// `pileup -L`, under hm_pileup_run's guard behind the projection: the batch's member list through the selection skeleton (it
+// lives until the next batch), then every pair of it into the histograms.  <= 1024 workgroups: an entry is a loop over its pairs.
+int count_linkage_pairs(hm_pileup* p, int n_runs, int64_t cols) {
+    const MemberSel sel{p->d_runs.as<PRun>(), p->d_col0.as<int64_t>(), n_runs, p->d_reads.as<PRead>(), p->d_slab.as<uint8_t>(),
+                        p->d_ref.as<char>(), p->d_plane.as<uint32_t>(), p->d_matches.as<int32_t>(), p->min_pi};
+    const int64_t n = stage_rows(p, sel, 0, cols, p->d_members, [](int64_t) { return true; }, no_hook);
+    if (n < 0) return (int)n;
+    if (n > 1)
+        hipLaunchKernelGGL(linkage_pair_kernel, dim3(grid_for(n, 1024)), dim3(TPB), 0, p->stream, p->d_members.as<PMember>(), n, p->linkage,
+                           p->d_lhist.as<unsigned long long>());
+    return HM_OK;
+}
+
 void clear_batch(hm_pileup* p) {
     p->slab.clear();
     p->reads.clear();
@@ -1984,6 +2129,11 @@ int hm_pileup_set_option(hm_pileup_t* p, const char* key, double value) {
         if (!p->seq_off.empty()) return pfail(p, HM_ESTATE, "bedmethyl must be set before hm_pileup_set_reference");
         if (value != 0.0 && value != 1.0) return pfail(p, HM_EINVAL, "bedmethyl must be 0 or 1");
         p->bedmethyl = (int)value;
+    } else if (k == "linkage") {  // the histogram table is sized when the reference arrives
+        if (!p->seq_off.empty()) return pfail(p, HM_ESTATE, "linkage must be set before hm_pileup_set_reference");
+        if (value != 0.0 && (!(value >= 2.0 && value <= (double)LINK_MAX_DIST) || value != std::floor(value)))
+            return pfail(p, HM_EINVAL, "linkage must be 0 or an integer in 2 .. 16384");
+        p->linkage = (int)value;
     } else return pfail(p, HM_EINVAL, "unknown option " + k);
     return HM_OK;
 }
@@ -2053,6 +2203,12 @@ int hm_pileup_set_reference(hm_pileup_t* p, int32_t n_seqs, const int64_t* seq_l
         if (p->patterns || p->bedmethyl) {
             const int rc = list_reference_cpgs(p);
             if (rc != HM_OK) return rc;
+        }
+        if (p->linkage) {
+            const size_t bytes = sizeof(unsigned long long) * LH_HISTS * 256 * ((size_t)p->linkage + 1);
+            p->d_lhist.reserve(bytes);
+            HIP_TRY(hipMemsetAsync(p->d_lhist.p, 0, bytes, p->stream));
+            p->linkage_counted = false;
         }
         HIP_TRY(hipStreamSynchronize(p->stream));
         return HM_OK;
@@ -2205,6 +2361,10 @@ int hm_pileup_run(hm_pileup_t* p) {
         if (n_gaps)  // deletions are rare next to columns: one thread each
             hipLaunchKernelGGL(depth_gap_kernel, dim3(grid_for(n_gaps, 1024)), dim3(TPB), 0, st, p->d_gaps.as<PGap>(), n_gaps,
                                p->d_reads.as<PRead>(), p->d_matches.as<int32_t>(), p->min_pi, depth_counters(p));
+        if (p->linkage && cols > 0) {
+            const int rc = count_linkage_pairs(p, n_runs, cols);
+            if (rc != HM_OK) return rc;
+        }
         HIP_TRY(hipGetLastError());
         unsigned long long n = 0, n_win = 0;
         HIP_TRY(hipMemcpyAsync(&n, p->d_counter.p, sizeof n, hipMemcpyDeviceToHost, st));
@@ -2303,6 +2463,8 @@ int hm_pileup_count(hm_pileup_t* p, const uint8_t thr[3]) {
         p->n_precs = 0;
         p->patterns_counted = p->patterns != 0;
         p->bedmethyl_counted = p->bedmethyl != 0;
+        p->linkage_counted = p->linkage != 0;
+        p->linkage_thr = thr[0];
         return HM_OK;
     });
 }
@@ -2360,6 +2522,35 @@ int64_t hm_pileup_fetch_bedmethyl(hm_pileup_t* p, int32_t part, int64_t lo, int6
     if (rc != HM_OK) return rc;
     if (ranks[1] <= ranks[0]) return 0;
     return compact_rows(p, BmSel{p->d_cpg.as<int64_t>(), depth_counters(p, part).bm, min_valid}, ranks[0], ranks[1], out, cap, no_hook, no_hook);
+}
+
+// ---- `pileup -L` ------------------------------------------------------------------------------------------------------------------
+int64_t hm_pileup_fetch_linkage(hm_pileup_t* p, int64_t min_pairs, hm_linkage_t* out, int64_t cap) {
+    if (!p) return HM_EINVAL;
+    if (!p->linkage || p->seq_off.empty()) return pfail(p, HM_ESTATE, "hm_pileup_fetch_linkage without option linkage (then hm_pileup_set_reference)");
+    if (!p->linkage_counted) return pfail(p, HM_ESTATE, "hm_pileup_fetch_linkage before hm_pileup_count");
+    if (min_pairs < 0) return pfail(p, HM_EINVAL, "hm_pileup_fetch_linkage: min_pairs must be >= 0");
+    const int rc = guarded(p, [&] {
+        p->d_ltab.reserve(sizeof(unsigned long long) * 4 * ((size_t)p->linkage + 1));
+        hipLaunchKernelGGL(linkage_reduce_kernel, dim3((unsigned)p->linkage + 1), dim3(256), 0, p->stream, p->d_lhist.as<unsigned long long>(),
+                           p->linkage_thr, p->d_ltab.as<unsigned long long>());
+        HIP_TRY(hipGetLastError());
+        return HM_OK;
+    });
+    if (rc != HM_OK) return rc;
+    return compact_rows(p, LinkSel{p->d_ltab.as<unsigned long long>(), min_pairs}, 2, (int64_t)p->linkage + 1, out, cap, no_hook, no_hook);
+}
+
+int hm_linkage_stats(const hm_linkage_t* w, double out[2]) {
+    if (!w || !out) return HM_EINVAL;
+    const uint64_t n = w->n_uu + w->n_um + w->n_mu + w->n_mm;
+    if (!n) return HM_EINVAL;
+    out[0] = (double)(w->n_uu + w->n_mm) / (double)n;
+    const uint64_t m1 = w->n_mm + w->n_mu, u1 = w->n_um + w->n_uu, m2 = w->n_mm + w->n_um, u2 = w->n_mu + w->n_uu;  // the margins
+    // the numerator as an exact integer (counts below 2^63): the two products may agree in all the digits a double holds
+    const __int128 num = (__int128)w->n_mm * (__int128)w->n_uu - (__int128)w->n_mu * (__int128)w->n_um;
+    out[1] = (!m1 || !u1 || !m2 || !u2) ? std::nan("") : (double)num / std::sqrt((double)m1 * (double)u1 * (double)m2 * (double)u2);
+    return HM_OK;
 }
 
 int hm_pattern_stats(const hm_pattern_t* w, double out[4]) {

@@ -62,6 +62,13 @@ the 40 reads there could be called at all".  `pu.bedmethyl(lo, hi, min_valid, pa
 with n_mod + n_canon >= min_valid (BEDMETHYL_DTYPE), `pu.bedmethyl_bed(rows)` the text of <prefix>.bedmethyl.CpG.bed in modkit's
 18 columns.
 
+Co-methylation by distance (`pileup -L bp`, `linkage=bp`): every two CpG calls of one alignment record that lie d <= bp reference
+bases apart count once under their exact distance d as UU, UM, MU or MM (the first letter for the lower coordinate) -- the decay
+curve of the coupling along single molecules.  The engine counts the pairs threshold-free as they pass (three 256-bin histograms
+per distance) and classes them by the CpG threshold of the last count().  `pu.linkage(min_pairs)` are the distances with at least
+min_pairs pairs (LINKAGE_DTYPE), `linkage_stats(row)` -- host only, the C library's -- their concordance and phi coefficient,
+`pu.linkage_tsv(rows)` the text of <prefix>.linkage.CpG.tsv.
+
 Fused with the caller (`pileup -K`): `pu.add_called(read, calls)` takes the records `MethylationCaller` returned for an aligned read
 instead of parsed MM / ML -- the same effect as add() of that read carrying the calls as tags, without the tag text.
 
@@ -100,6 +107,9 @@ DOMAIN_DTYPE = np.dtype([("start", "<i8"), ("end", "<i8"), ("pcov", "<i8"), ("nc
 PATTERN_DTYPE = np.dtype([("start", "<i8"), ("end", "<i8"), ("counts", "<u4", (16,)), ("n", "<u4"), ("k", "<u4")])  # hm_pattern_t, 88 bytes
 BEDMETHYL_DTYPE = np.dtype([("gpos", "<i8"), ("n_mod", "<u4"), ("n_canon", "<u4"), ("n_nocall", "<u4"), ("n_diff", "<u4"),
                             ("n_delete", "<u4"), ("reserved", "<u4")])                # hm_bedmethyl_t, 32 bytes
+LINKAGE_DTYPE = np.dtype([("dist", "<u4"), ("reserved", "<u4"), ("n_uu", "<u8"), ("n_um", "<u8"), ("n_mu", "<u8"),
+                          ("n_mm", "<u8")])                                          # hm_linkage_t, 40 bytes
+LINKAGE_MAX_DIST = 16384                                 # the largest `pileup -L`
 PATTERN_SPAN, PATTERN_MIN_READS = 150, 10                # `pileup -E`'s default -w and -o
 DOMAIN_AFTER_BREAK, DOMAIN_BEFORE_BREAK = 1, 2                                        # HM_DOMAIN_AFTER_BREAK, HM_DOMAIN_BEFORE_BREAK
 DOMAIN_PASS_SUMMARY, DOMAIN_PASS_CODES, DOMAIN_PASS_SEGMENTS, DOMAIN_KEEP = 0, 1, 2, 2   # HM_DOMAIN_PASS_*, HM_DOMAIN_KEEP
@@ -481,6 +491,27 @@ def pattern_stats(row) -> Tuple[float, float, float, float]:
     return tuple(float(x) for x in out)
 
 
+def linkage_stats(row) -> Tuple[float, float]:
+    """one LINKAGE_DTYPE row -> (concordance, r) by the C library (host only: no GPU is needed): (n_uu + n_mm) / n and the phi
+    coefficient (n_mm n_uu - n_mu n_um) / sqrt of the product of the four margins, nan when a margin is 0"""
+    w = np.array(row, LINKAGE_DTYPE).reshape(1)
+    out = np.zeros(2, np.float64)
+    if lib().hm_linkage_stats(w.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)) != 0:
+        raise HifimethError("hm_linkage_stats: n = n_uu + n_um + n_mu + n_mm > 0 expected")
+    return tuple(float(x) for x in out)
+
+
+def linkage_tsv(rows: np.ndarray) -> str:
+    """the text of <prefix>.linkage.CpG.tsv: the header, then dist, n, n_uu, n_um, n_mu, n_mm, concordance, r per row (a row
+    without pairs has no statistics: nan)"""
+    text = ["#dist\tn\tn_uu\tn_um\tn_mu\tn_mm\tconcordance\tr\n"]
+    for r in rows:
+        c = [int(r[k]) for k in ("n_uu", "n_um", "n_mu", "n_mm")]
+        st = linkage_stats(r) if sum(c) else (float("nan"), float("nan"))
+        text.append("%d\t%d\t%d\t%d\t%d\t%d\t%.6g\t%.6g\n" % (int(r["dist"]), sum(c), *c, *st))
+    return "".join(text)
+
+
 def sites_rates_tsv(sums, rates, m) -> str:
     """the text of <prefix>.sites.rates.tsv: ctx, P_c, N_c, rate, m_c (the counts are 0 when the rates were given with -e)"""
     return "".join("%s\t%d\t%d\t%s\t%d\n" % (CTX_NAMES[c], int(sums[c]), int(sums[3 + c]),
@@ -500,7 +531,7 @@ def locate(offsets, gpos) -> Tuple[np.ndarray, np.ndarray]:
 class MethylationPileup:
     def __init__(self, genome: Sequence[Tuple[str, str]], device: int = 0, min_mapq: int = 0, min_pi: float = 0.0,
                  planes=None, partitions: bool = False, partition_planes=None, bases=None, patterns: int = 0,
-                 pattern_span: int = PATTERN_SPAN, bedmethyl: bool = False):
+                 pattern_span: int = PATTERN_SPAN, bedmethyl: bool = False, linkage: int = 0):
         """genome: [(name, SEQUENCE)].  bases: optional, the concatenated upper-case bases of the whole reference as a
         C-contiguous uint8 buffer (ndarray, bytes, memoryview), handed to the engine as it is -- for references of gigabases,
         where joining, upper-casing and encoding strings would copy them three times; the second member of each genome entry
@@ -511,7 +542,9 @@ class MethylationPileup:
         torch CUDA tensors for them, like `planes`.
         patterns: 0, or k in (2, 3, 4): also count the read-level patterns over windows of k adjacent reference CpGs whose first
         and last locus are at most pattern_span (1 .. 65 536) bases apart (+72 B per reference CpG, 8 B per window record).
-        bedmethyl: also count the depth classes per reference CpG (+28 B per reference CpG, +68 B with partitions)."""
+        bedmethyl: also count the depth classes per reference CpG (+28 B per reference CpG, +68 B with partitions).
+        linkage: 0, or max_dist in 2 .. 16 384: also count the pairs of CpG calls of one record by their distance up to max_dist
+        (+6 144 B per distance, whatever the depth)."""
         self._L = lib()
         self._h = C.c_void_p()
         if self._L.hm_pileup_create(C.byref(self._h), device) != 0:
@@ -536,6 +569,9 @@ class MethylationPileup:
             self._check(self._L.hm_pileup_set_option(self._h, b"pattern_span", float(pattern_span)))
         if bedmethyl:
             self._check(self._L.hm_pileup_set_option(self._h, b"bedmethyl", 1.0))
+        self.linkage_max_dist = int(linkage)
+        if linkage:
+            self._check(self._L.hm_pileup_set_option(self._h, b"linkage", float(linkage)))
         if planes is not None:
             self._check(self._L.hm_pileup_use_planes(self._h, *(C.c_void_p(t.data_ptr()) for t in planes)))
         if bases is None:
@@ -810,6 +846,16 @@ class MethylationPileup:
             text.append("%s\t%d\t%d\t%d\t%.6g\t%.6g\t%.6g\t%.6g\t" % (self.names[s], k, k + (r["end"] - r["start"]), r["n"], *pattern_stats(r))
                         + ",".join("%d" % c for c in r["counts"][:1 << int(r["k"])]) + "\n")
         return "".join(text)
+
+    def linkage(self, min_pairs: int = 1) -> np.ndarray:
+        """the distances d in [2, max_dist] with at least min_pairs pairs, ascending (LINKAGE_DTYPE; min_pairs 0: every distance):
+        the pairs of CpG calls of one record d bases apart by class, M = the call reaches the CpG threshold the last count() was
+        given, the first letter for the lower coordinate.  Needs linkage=max_dist, after count()."""
+        return self._rows(self._L.hm_pileup_fetch_linkage, LINKAGE_DTYPE, min_pairs)
+
+    def linkage_tsv(self, rows: np.ndarray) -> str:
+        """the text of <prefix>.linkage.CpG.tsv"""
+        return linkage_tsv(rows)
 
     def bedmethyl(self, lo: int = 0, hi: Optional[int] = None, min_valid: int = 1, partition: int = 0) -> np.ndarray:
         """the reference CpGs of [lo, hi), ascending (BEDMETHYL_DTYPE), at which a read was classed and n_mod + n_canon >= min_valid

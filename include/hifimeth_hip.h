@@ -237,8 +237,8 @@ void hm_pileup_destroy(hm_pileup_t* p);
 const char* hm_pileup_last_error(const hm_pileup_t* p); /* p may be NULL: error of a failed create */
 /* options: "min_mapq" (-q, default 0), "min_pi" (-f, default 0.0), "partitions" (0 default, or 2: haplotype-resolved
  * counting, see hm_pileup_submit_read_hp; must be set before hm_pileup_set_reference / hm_pileup_use_planes, else HM_ESTATE),
- * "patterns" and "pattern_span" (read-level CpG patterns) and "bedmethyl" (per-CpG depth classes), both near the end of this
- * header */
+ * "patterns" and "pattern_span" (read-level CpG patterns), "bedmethyl" (per-CpG depth classes) and "linkage" (co-methylation by
+ * distance), all near the end of this header */
 int hm_pileup_set_option(hm_pileup_t* p, const char* key, double value);
 /* HbnDatabase: n_seqs upper-cased sequences back to back in `bases` (seq_len[i] bytes each).  Allocates and
  * zeroes the per-locus planes unless hm_pileup_use_planes was called before. */
@@ -637,6 +637,39 @@ typedef struct {            /* one reference CpG = one row of <prefix>.bedmethyl
  * first hm_pileup_count, or for part 1 / 2 without partitions; HM_EINVAL for part outside 0..2, lo < 0, lo > hi or min_valid < 0. */
 int64_t hm_pileup_fetch_bedmethyl(hm_pileup_t* p, int32_t part, int64_t lo, int64_t hi, int64_t min_valid, hm_bedmethyl_t* out,
                                   int64_t cap);
+
+/* ---- within-read CpG co-methylation by distance (`pileup -L`): how the calls of one molecule are coupled --------
+ * The co-methylation decay curve: per distance d, how often two CpGs d bases apart on the SAME molecule are both methylated, both
+ * unmethylated, or discordant.  A record TAKES PART as under the patterns and bedMethyl above: its submission returned 1 and it
+ * passes -q / -f; secondary and supplementary records take part as records of their own.  Its MEMBER LOCI are the reference CpGs at
+ * which it is a member in the patterns' sense (g and g + 1 in one match run, the bases as stored C, G, reference C, G, a 5mC entry at
+ * the offset the projection looks up: the loci where it leaves a motif-0 record), each with that entry's ML byte `prob`.
+ * The counted objects are the unordered pairs of member loci (a, b) of ONE record with a < b and d = b - a in [2, max_dist]; each
+ * counts once.  Pairs never join two records, two alignments of one read name included.  With pa, pb the ML bytes at the lower and
+ * the higher coordinate and t = thr[CpG] of the last hm_pileup_count, a locus is M iff prob >= t (hm_pileup_count's >=), and the pair
+ * falls into one of UU, UM, MU, MM, the first letter for the lower coordinate.
+ * The thresholds are known only after the last read and the pairs are too many to keep, so per d three 256-bin uint64 histograms are
+ * filled at hm_pileup_run time: H_min[d][min(pa, pb)], H_max[d][max(pa, pb)], H_first[d][pa].  For any t: n = sum H_min[d],
+ * MM = sum_{v >= t} H_min[d][v], UU = sum_{v < t} H_max[d][v], MU = sum_{v >= t} H_first[d][v] - MM, UM = n - MM - UU - MU.  Exact
+ * integers; (max_dist + 1) * 6 144 bytes whatever the depth; the histograms accumulate over run / count cycles as the planes do, and
+ * a fetch applies the LAST count's threshold to all of them.
+ * Option "linkage" (max_dist: 0 off = default, else 2 .. 16 384), before hm_pileup_set_reference (else HM_ESTATE; HM_EINVAL out of
+ * range).  With it on, hm_pileup_set_reference allocates and zeroes the table, and hm_pileup_run lists the batch's members (16 B
+ * each, for the batch's lifetime) and adds their pairs behind the projection.  Without it nothing is allocated, uploaded or
+ * launched.  Not here: CHG / CHH pairs, per-haplotype tables, distance bins (rows are exact distances), read-coordinate distances,
+ * any statistical test. */
+typedef struct {            /* one distance = one row of <prefix>.linkage.CpG.tsv; 40 bytes */
+    uint32_t dist, reserved;
+    uint64_t n_uu, n_um, n_mu, n_mm;
+} hm_linkage_t;
+/* The rows of the distances d in [2, max_dist] with n = n_uu + n_um + n_mu + n_mm >= min_pairs, ascending; min_pairs 0 returns every
+ * d, the empty ones included.  Returns their number (may exceed cap, or out NULL: then nothing is written).  HM_ESTATE without
+ * option "linkage" or before the first hm_pileup_count, HM_EINVAL for min_pairs < 0. */
+int64_t hm_pileup_fetch_linkage(hm_pileup_t* p, int64_t min_pairs, hm_linkage_t* out, int64_t cap);
+/* Host only, fp64: the one implementation behind every front end.  out[0] concordance = (n_uu + n_mm) / n;  out[1] the phi
+ * coefficient r = (n_mm n_uu - n_mu n_um) / sqrt((n_mm + n_mu)(n_um + n_uu)(n_mm + n_um)(n_mu + n_uu)), the numerator an exact
+ * integer, NaN when a margin is 0.  HM_EINVAL for n == 0. */
+int hm_linkage_stats(const hm_linkage_t* w, double out[2]);
 
 #ifdef __cplusplus
 }

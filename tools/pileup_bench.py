@@ -17,12 +17,15 @@ segments over the same planes, and the fit of the three contexts from the defaul
 `--patterns K`: the read-level CpG patterns of `pileup -E K`: the timed passes run on an engine without the option first and then on one
 with it; the leg is what the option adds to projection and counting plus one fetch of the rows (D2H included): window records per second,
 rows, share of a pass.
+`--linkage D`: the within-read co-methylation by distance of `pileup -L D`, timed like `--patterns`: the leg is what the option adds to
+a pass (the member list through the selection skeleton -- one 8-byte count copy per batch -- and the pair kernel) plus one fetch of
+all rows (reduce per distance, LinkSel, D2H): pairs per second, rows, share of a pass.
 `--bedmethyl`: the depth classes of `pileup -M`, timed like `--patterns`: the passes on an engine without the option, then on one with
 it; the leg is what the option adds to projection and counting plus one fetch of the rows (D2H included).  The synthetic reads are
 error-free: the column kernel and the record count run at full size, the deletion kernel has nothing to do.
 `--parts N` (with `--domains`): the same segments chained from N equal pieces next to the single fetch (three stateless passes per piece).
 
-    python tools/pileup_bench.py --genome-mb 20 --coverage 10 [--partitions [--asm [--asm-q] [--asm-regions]]] [--sites] [--domains [--fit] [--parts N]] [--patterns K] [--bedmethyl]
+    python tools/pileup_bench.py --genome-mb 20 --coverage 10 [--partitions [--asm [--asm-q] [--asm-regions]]] [--sites] [--domains [--fit] [--parts N]] [--patterns K] [--bedmethyl] [--linkage D]
 """
 import argparse
 import ctypes as C
@@ -114,6 +117,8 @@ def main():
                     help="with --domains: also the same segments chained from N equal pieces (hm_pileup_fetch_domains_part, what pileup_dist -D runs)")
     ap.add_argument("--patterns", type=int, default=0, metavar="K", choices=(0, 2, 3, 4),
                     help="time what the read-level CpG patterns over windows of K reference CpGs add (pileup -E K, default span and min reads)")
+    ap.add_argument("--linkage", type=int, default=0, metavar="D",
+                    help="time what the within-read co-methylation by distance up to D bases adds (pileup -L D, min_pairs 1)")
     ap.add_argument("--bedmethyl", action="store_true", help="time what the per-CpG depth classes add (pileup -M, min_valid 1)")
     ap.add_argument("--cpu-baseline", action="store_true",
                     help="time the reference's own projection code (oracle/_ref/ref_align -t) on a bounded sample")
@@ -160,7 +165,7 @@ def main():
                 pu.flush()
         pu.flush()
 
-    if a.patterns or a.bedmethyl:                  # the same passes without the option(s) first: the leg is the difference
+    if a.patterns or a.bedmethyl or a.linkage:     # the same passes without the option(s) first: the leg is the difference
         one_pass()
         pu.count([128, 128, 128])
         t0 = time.perf_counter()
@@ -171,7 +176,7 @@ def main():
         pu.count([128, 128, 128])
         t_count_off = time.perf_counter() - t0
         pu.close()
-        pu = MethylationPileup(genome, partitions=a.partitions, patterns=a.patterns, bedmethyl=a.bedmethyl)
+        pu = MethylationPileup(genome, partitions=a.partitions, patterns=a.patterns, bedmethyl=a.bedmethyl, linkage=a.linkage)
     one_pass(pu)                                   # warm-up (allocations)
     wins_per_pass = pu.num_pattern_records()
     recs_per_pass = pu.num_records()
@@ -218,6 +223,24 @@ def main():
         if a.check:                                # a row's reads are window records: all of them at min_reads 1
             n_all = int(pu.patterns(min_reads=1)["n"].astype(np.int64).sum())
             out["check_patterns_rows_hold_the_records"] = bool(n_all == wins_per_pass * (a.repeat + 1))
+    if a.linkage:
+        pu.linkage()                               # warm-up: the table and the row buffer
+        t0 = time.perf_counter()
+        for _ in range(a.repeat):
+            rows = pu.linkage()
+        t_rows = (time.perf_counter() - t0) / a.repeat
+        pairs = int(sum(int(rows[k].astype(np.uint64).sum()) for k in ("n_uu", "n_um", "n_mu", "n_mm"))) // (a.repeat + 1)
+        t_leg = max((t_project - t_project_off + t_count - t_count_off) / a.repeat, 0.0) + t_rows
+        t_pass = (t_project_off + t_count_off) / a.repeat + t_loci
+        out.update(linkage_max_dist=a.linkage, linkage_pairs_per_pass=pairs, linkage_rows=int(len(rows)),
+                   linkage_project_s_per_pass=[round(t_project_off / a.repeat, 4), round(t_project / a.repeat, 4)],
+                   linkage_count_s=[round(t_count_off, 4), round(t_count, 4)], linkage_rows_s=round(t_rows, 4),
+                   linkage_leg_s_per_pass=round(t_leg, 4), linkage_pairs_per_s=round(pairs / t_leg) if t_leg else 0,
+                   linkage_share_of_pass=round(t_leg / (t_pass + t_leg), 4), linkage_also=[a.patterns, a.bedmethyl])
+        if a.check:                                # every pass adds the same pairs; the distances are ascending and within reach
+            n_all = sum(int(rows[k].astype(np.uint64).sum()) for k in ("n_uu", "n_um", "n_mu", "n_mm"))
+            out["check_linkage_rows"] = bool(len(rows) and n_all == pairs * (a.repeat + 1) and (np.diff(rows["dist"].astype(np.int64)) > 0).all()
+                                             and rows["dist"][0] >= 2 and rows["dist"][-1] <= a.linkage)
     if a.bedmethyl:
         pu.bedmethyl()                             # warm-up: the row buffer
         t0 = time.perf_counter()
