@@ -11,14 +11,16 @@
 // each CIGAR into "match runs" (maximal stretches of M/=/X columns: read offset, reference offset, length) and one
 // GPU thread per aligned column tests the 2- and 3-column motifs straight from the 4-bit SEQ and the reference
 // bytes.  This is byte / integer work bound by HBM traffic; no LDS tiling or MFMA applies.  Kernels:
-//   mods_kernel     thread per MM/ML entry : ML byte -> per-base plane (last entry wins, as the reference's
+//   entries_kernel<PMod>   thread per MM/ML entry : ML byte -> per-base plane (last entry wins, as the reference's
 //                   sequential overwrite), context histograms through LDS
-//   calls_kernel    thread per call        : the same for records submitted with their hm_call_t calls instead of parsed
+//   entries_kernel<PCall>  thread per call : the same for records submitted with their hm_call_t calls instead of parsed
 //                   MM/ML lists (hm_pileup_submit_read_calls, the fused `pileup -K` path)
 //   identity_kernel thread per column      : matches per read (only when -f > 0)
 //   project_kernel  thread per column      : motif tests, plane lookup, wave-aggregated append of 12-byte records
-//   count_kernel    thread per record      : atomic add into pcov / ncov, atomic max into the motif key
-//   count_hp_kernel the same + one more atomic add into the record's haplotype planes (partitions = 2 only)
+//   count_kernel<CountPlanes>    thread per record : atomic add into pcov / ncov, atomic max into the motif key
+//   count_kernel<CountHpPlanes>  the same + one more atomic add into the record's haplotype planes (partitions = 2 only)
+//   The column kernels (identity, project, pattern, depth) and MemberSel see the staged batch as one BatchView; the tiled ones
+//   walk it with walk_columns, test a CpG member with cpg_columns / cpg_call and append with stage_record / flush_stage.
 //   pattern_kernel  thread per column      : (`pileup -E`) a CpG member that heads a window of k reference CpGs looks the other
 //                   k - 1 up in the read's following runs and appends one 8-byte window record; pattern_count_kernel adds
 //                   the records into 16 bins per reference CpG; RefCpgSel lists the reference CpGs, PatSel the rows
@@ -55,6 +57,7 @@
 #include <memory>
 #include <numeric>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/hifimeth_hip.h"
@@ -84,23 +87,57 @@ struct PRun {
     int32_t pad;
 };
 
+// The two entry types unpack themselves into mod_entry's arguments: ml() the ML byte, rank() what orders the entries of one
+// position, is_m() a 5mC entry, on_cg() unmodified base C or G.
 struct PMod {
     int32_t read;
     int32_t qoff;
     uint32_t bits;      // idx_in_read << 10 | is_m << 9 | unmod_is_CG << 8 | prob
+    __device__ uint32_t ml() const { return bits & 255u; }
+    __device__ uint32_t rank() const { return (bits >> 10) + 1u; }
+    __device__ bool is_m() const { return bits & 0x200u; }
+    __device__ bool on_cg() const { return bits & 0x100u; }
 };
 
+// Every call is a 5mC entry on a C (FWD) or G (REV), and a read has at most one per position, so the rank is a constant.
+// hm_call_t::ctx is not used: at read ends and next to N it is not what the bases of the written-and-parsed MM list give.
 struct PCall {          // 12 bytes: hm_call_t without p, read_id replaced by the index of the staged read
     int32_t read;
     int32_t qoff;
     uint8_t strand, ctx, prob, reserved;
+    __device__ uint32_t ml() const { return prob; }
+    __device__ uint32_t rank() const { return 1u; }
+    __device__ bool is_m() const { return true; }
+    __device__ bool on_cg() const { return true; }
 };
 static_assert(sizeof(PCall) == 12 && sizeof(hm_call_t) == 16, "staged calls are the first 12 bytes of hm_call_t");
 
 struct PRec {           // 12 bytes
     uint32_t glo;       // gpos & 0xffffffff
-    uint32_t hi;        // gpos >> 32 (8 bits) | prob << 8 | motif << 16 | hp << 18 (consumers mask motif with & 3)
+    uint32_t hi;        // gpos >> 32 (8 bits) | prob << 8 | motif << 16 | hp << 18
     uint32_t order;
+    __host__ __device__ int64_t gpos() const { return (int64_t)glo | ((int64_t)(hi & 255u) << 32); }
+    __host__ __device__ uint32_t prob() const { return (hi >> 8) & 255u; }
+    __host__ __device__ uint32_t motif() const { return (hi >> 16) & 3u; }
+    __host__ __device__ uint32_t hp() const { return (hi >> 18) & 3u; }
+    __host__ __device__ static PRec make(int64_t gpos, uint32_t prob, uint32_t motif, uint32_t hp, uint32_t order) {
+        return PRec{(uint32_t)gpos, (uint32_t)((uint64_t)gpos >> 32) | (prob << 8) | (motif << 16) | (hp << 18), order};
+    }
+};
+
+// The staged batch as every column kernel and MemberSel see it: match runs with the batch column of each run's first column
+// (col0[n_runs] = n_cols), the records, their 4-bit SEQ, the reference, the per-base 5mC plane, and what -f needs.
+struct BatchView {
+    const PRun* runs;
+    const int64_t* col0;
+    int n_runs;
+    int64_t n_cols;
+    const PRead* reads;
+    const uint8_t* slab;
+    const char* ref;
+    const uint32_t* plane;
+    const int32_t* matches;
+    double min_pi;
 };
 
 constexpr int TPB = 256;
@@ -147,37 +184,28 @@ __device__ __forceinline__ void mod_entry(const PRead& r, int q, uint32_t prob, 
     }
 }
 
-__global__ __launch_bounds__(TPB) void mods_kernel(const PMod* __restrict__ mods, int64_t n, const PRead* __restrict__ reads,
-                                                    const uint8_t* __restrict__ slab, uint32_t* __restrict__ plane,
-                                                    unsigned long long* __restrict__ bins) {
-    __shared__ uint32_t h[3 * 256];
-    for (int i = threadIdx.x; i < 768; i += TPB) h[i] = 0;
+// A workgroup-private histogram of n bins in LDS: zeroed; and added to the global bins, one atomic per non-empty bin
+__device__ __forceinline__ void hist_zero(uint32_t* h, int n) {
+    for (int i = threadIdx.x; i < n; i += TPB) h[i] = 0u;
     __syncthreads();
-    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
-        const PMod m = mods[i];
-        mod_entry(reads[m.read], m.qoff, m.bits & 255u, (m.bits >> 10) + 1u, m.bits & 0x200u, m.bits & 0x100u, slab, plane, h);
-    }
+}
+__device__ __forceinline__ void hist_flush(const uint32_t* h, int n, unsigned long long* __restrict__ bins) {
     __syncthreads();
-    for (int i = threadIdx.x; i < 768; i += TPB)
+    for (int i = threadIdx.x; i < n; i += TPB)
         if (h[i]) atomicAdd(&bins[i], (unsigned long long)h[i]);
 }
 
-// The counterpart for calls: every call is a 5mC entry on a C (FWD) or G (REV), and a read has at most one per position,
-// so the rank is a constant.  hm_call_t::ctx is not used: at read ends and next to N it is not what the bases of the
-// written-and-parsed MM list give.
-__global__ __launch_bounds__(TPB) void calls_kernel(const PCall* __restrict__ calls, int64_t n, const PRead* __restrict__ reads,
-                                                     const uint8_t* __restrict__ slab, uint32_t* __restrict__ plane,
-                                                     unsigned long long* __restrict__ bins) {
+template <class Entry>  // PMod or PCall
+__global__ __launch_bounds__(TPB) void entries_kernel(const Entry* __restrict__ entries, int64_t n, const PRead* __restrict__ reads,
+                                                       const uint8_t* __restrict__ slab, uint32_t* __restrict__ plane,
+                                                       unsigned long long* __restrict__ bins) {
     __shared__ uint32_t h[3 * 256];
-    for (int i = threadIdx.x; i < 768; i += TPB) h[i] = 0;
-    __syncthreads();
+    hist_zero(h, 768);
     for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
-        const PCall c = calls[i];
-        mod_entry(reads[c.read], c.qoff, c.prob, 1u, true, true, slab, plane, h);
+        const Entry e = entries[i];
+        mod_entry(reads[e.read], e.qoff, e.ml(), e.rank(), e.is_m(), e.on_cg(), slab, plane, h);
     }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 768; i += TPB)
-        if (h[i]) atomicAdd(&bins[i], (unsigned long long)h[i]);
+    hist_flush(h, 768, bins);
 }
 
 // run holding global column c: largest r in [lo, hi) with col0[r] <= c
@@ -191,26 +219,54 @@ __device__ __forceinline__ int find_run(const int64_t* __restrict__ col0, int n_
 }
 
 // ---- identity: s_calc_ident_perc numerator (bam_info.cpp:11-23); gap columns never match ---------------------
-__global__ __launch_bounds__(TPB) void identity_kernel(const PRun* __restrict__ runs, const int64_t* __restrict__ col0,
-                                                        int n_runs, int64_t n_cols, const PRead* __restrict__ reads,
-                                                        const uint8_t* __restrict__ slab, const char* __restrict__ ref,
-                                                        int32_t* __restrict__ matches) {
+__global__ __launch_bounds__(TPB) void identity_kernel(BatchView b, int32_t* __restrict__ matches) {
     const int64_t c = (int64_t)blockIdx.x * TPB + threadIdx.x;
     int rd = -1;
     bool eq = false;
-    if (c < n_cols) {
-        const int ri = find_run(col0, n_runs, c);
-        const PRun run = runs[ri];
-        const int o = (int)(c - col0[ri]);
+    if (c < b.n_cols) {
+        const int ri = find_run(b.col0, b.n_runs, c);
+        const PRun run = b.runs[ri];
+        const int o = (int)(c - b.col0[ri]);
         rd = run.read;
-        eq = stored_base(slab, reads[rd], run.q0 + o) == ref[run.g0 + o];
+        eq = stored_base(b.slab, b.reads[rd], run.q0 + o) == b.ref[run.g0 + o];
     }
     const int first = __shfl(rd, 0);
     if (__all(rd == first)) {  // the common case: one read per wavefront -> one atomic
-        const unsigned long long b = __ballot(eq);
-        if ((threadIdx.x & 63) == 0 && first >= 0 && b) atomicAdd(&matches[first], __popcll(b));
+        const unsigned long long bal = __ballot(eq);
+        if ((threadIdx.x & 63) == 0 && first >= 0 && bal) atomicAdd(&matches[first], __popcll(bal));
     } else if (eq) {
         atomicAdd(&matches[rd], 1);
+    }
+}
+
+// ---- what the tiled column kernels share --------------------------------------------------------------------
+// A workgroup walks PTILE consecutive columns, stages its records in LDS and appends them to the global list with
+// ONE atomic (same-address atomics from every wavefront serialise in L2 and dominated an earlier version).
+constexpr int PTILE = 1024;
+
+// The walk: body(ri, run, o, in_range) per column of the workgroup's tile -- run index, run, offset in the run; beyond the
+// batch's last column in_range is false and the rest unset.  Every lane of a wavefront enters the body on every trip, so a
+// body may hold wavefront collectives (stage_record).  Opens with a barrier: what a kernel set in LDS before it is visible.
+template <class Body>
+__device__ __forceinline__ void walk_columns(const BatchView& b, Body body) {
+    __shared__ int run_range[2];  // runs touched by this tile: the per-column search starts from here
+    if (threadIdx.x < 2) {
+        const int64_t c = min((int64_t)blockIdx.x * PTILE + (threadIdx.x ? PTILE - 1 : 0), b.n_cols - 1);
+        run_range[threadIdx.x] = find_run(b.col0, b.n_runs, c) + (int)threadIdx.x;
+    }
+    __syncthreads();
+    const int run_lo = run_range[0], run_hi = run_range[1];
+    for (int it = 0; it < PTILE / TPB; ++it) {
+        const int64_t c = (int64_t)blockIdx.x * PTILE + it * TPB + threadIdx.x;
+        const bool in_range = c < b.n_cols;
+        int ri = 0, o = 0;
+        PRun run{};
+        if (in_range) {
+            ri = find_run(b.col0, b.n_runs, c, run_lo, run_hi);
+            run = b.runs[ri];
+            o = (int)(c - b.col0[ri]);
+        }
+        body(ri, run, o, in_range);
     }
 }
 
@@ -227,114 +283,121 @@ __device__ __forceinline__ void stage_record(bool pred, const Rec& rec, Rec* __r
     if (pred) stage[base + __popcll(b & ((1ull << lane) - 1ull))] = rec;
 }
 
-// ---- projection (pileup.cpp:286-347, 5mc_motif_finder.cpp:104-144) -----------------------------------------
-// A workgroup walks PTILE consecutive columns, stages its records in LDS and appends them to the global list with
-// ONE atomic (same-address atomics from every wavefront serialise in L2 and dominated an earlier version).
-constexpr int PTILE = 1024;
+// the workgroup's *n_stage staged records appended to `out` behind one atomic on `counter`; they move as a stream of dwords
+template <class Rec>
+__device__ __forceinline__ void flush_stage(const Rec* stage, const int* n_stage, Rec* __restrict__ out,
+                                            unsigned long long* __restrict__ counter) {
+    static_assert(sizeof(Rec) % 4 == 0, "staged records move as dwords");
+    __shared__ unsigned long long out_base;
+    __syncthreads();
+    const int n = *n_stage;
+    if (threadIdx.x == 0 && n) out_base = atomicAdd(counter, (unsigned long long)n);
+    __syncthreads();
+    if (n) {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(stage);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(out + out_base);
+        for (int i = threadIdx.x; i < (int)(sizeof(Rec) / 4) * n; i += TPB) dst[i] = src[i];
+    }
+}
 
-__global__ __launch_bounds__(TPB) void project_kernel(const PRun* __restrict__ runs, const int64_t* __restrict__ col0,
-                                                       int n_runs, int64_t n_cols, const PRead* __restrict__ reads,
-                                                       const uint8_t* __restrict__ slab, const char* __restrict__ ref,
-                                                       const uint32_t* __restrict__ plane,
-                                                       const int32_t* __restrict__ matches, double min_pi,
-                                                       PRec* __restrict__ out, unsigned long long* __restrict__ counter) {
+// -q and -f: the one place that compares a record's identity with min_pi
+__device__ __forceinline__ bool read_takes_part(const PRead& rd, int read, const int32_t* __restrict__ matches, double min_pi) {
+    return rd.pass && !(min_pi > 0.0 && 100.0 * matches[read] / rd.as_size < min_pi);
+}
+
+// The CpG member of include/hifimeth_hip.h, in two halves.  cpg_columns: stored bases and reference both show CG on two
+// columns of one run -- from characters the caller holds, or loaded at offset `off` of `run` (off + 1 < run.len).
+__device__ __forceinline__ bool cpg_columns(char q0, char q1, char s0, char s1) {
+    return q0 == 'C' && q1 == 'G' && s0 == 'C' && s1 == 'G';
+}
+__device__ __forceinline__ bool cpg_columns(const BatchView& b, const PRead& rd, const PRun& run, int off) {
+    const int qp = run.q0 + off;
+    const int64_t g = run.g0 + off;
+    return cpg_columns(stored_base(b.slab, rd, qp), stored_base(b.slab, rd, qp + 1), b.ref[g], b.ref[g + 1]);
+}
+// cpg_call: the ML byte of the 5mC entry of the CpG whose C is stored base qp, or -1: a reverse record carries it on the G
+__device__ __forceinline__ int cpg_call(const BatchView& b, const PRead& rd, int qp) {
+    const uint32_t v = b.plane[rd.plane_off + (rd.rev ? rd.l_qseq - 1 - (qp + 1) : qp)];
+    return (v & 0x100u) ? (int)(v & 255u) : -1;
+}
+// both: the member's ML byte at offset `off` of `run`, or -1
+__device__ __forceinline__ int cpg_member(const BatchView& b, const PRead& rd, const PRun& run, int off) {
+    return cpg_columns(b, rd, run, off) ? cpg_call(b, rd, run.q0 + off) : -1;
+}
+
+// ---- projection (pileup.cpp:286-347, 5mc_motif_finder.cpp:104-144) -----------------------------------------
+__global__ __launch_bounds__(TPB) void project_kernel(BatchView b, PRec* __restrict__ out, unsigned long long* __restrict__ counter) {
     __shared__ PRec stage[2 * PTILE];  // a column yields at most two records (CpG + the reverse-strand CGG of CHG)
     __shared__ int n_stage;
-    __shared__ int run_range[2];  // runs touched by this tile: the per-column search starts from here
-    __shared__ unsigned long long out_base;
     if (threadIdx.x == 0) n_stage = 0;
-    if (threadIdx.x < 2) {
-        const int64_t c = min((int64_t)blockIdx.x * PTILE + (threadIdx.x ? PTILE - 1 : 0), n_cols - 1);
-        run_range[threadIdx.x] = find_run(col0, n_runs, c) + (int)threadIdx.x;
-    }
-    __syncthreads();
-    const int run_lo = run_range[0], run_hi = run_range[1];
-    for (int it = 0; it < PTILE / TPB; ++it) {
-        const int64_t c = (int64_t)blockIdx.x * PTILE + it * TPB + threadIdx.x;
+    walk_columns(b, [&](int, const PRun& run, int o, bool in_range) {
         bool e0 = false, e1 = false;
         PRec r0{}, r1{};
-        if (c < n_cols) {
-            const int ri = find_run(col0, n_runs, c, run_lo, run_hi);
-            const PRun run = runs[ri];
-            const int o = (int)(c - col0[ri]);
-            const int rem = run.len - o;
-            const PRead rd = reads[run.read];
-            bool live = rd.pass && rem >= 2;
-            if (live && min_pi > 0.0) live = !(100.0 * matches[run.read] / rd.as_size < min_pi);
-            if (live) {
+        const int rem = run.len - o;
+        if (in_range && rem >= 2) {
+            const PRead rd = b.reads[run.read];
+            if (read_takes_part(rd, run.read, b.matches, b.min_pi)) {
                 const int qp = run.q0 + o, L = rd.l_qseq;
                 const int64_t g = run.g0 + o;
-                const char q0 = stored_base(slab, rd, qp), q1 = stored_base(slab, rd, qp + 1);
-                const char s0 = ref[g], s1 = ref[g + 1];
+                const char q0 = stored_base(b.slab, rd, qp), q1 = stored_base(b.slab, rd, qp + 1);
+                const char s0 = b.ref[g], s1 = b.ref[g + 1];
                 char q2 = '-', s2 = '*';
-                if (rem >= 3) { q2 = stored_base(slab, rd, qp + 2); s2 = ref[g + 2]; }
+                if (rem >= 3) { q2 = stored_base(b.slab, rd, qp + 2); s2 = b.ref[g + 2]; }
                 const bool eq3 = rem >= 3 && q0 == s0 && q1 == s1 && q2 == s2;
-                auto look = [&](int qoff, int64_t soff, uint32_t motif, bool& e, PRec& r) {
-                    const uint32_t v = plane[rd.plane_off + qoff];
+                auto look = [&](int qoff, int64_t soff, uint32_t motif) {
+                    const uint32_t v = b.plane[rd.plane_off + qoff];
                     if (v & 0x100u) {
-                        e = true;
-                        r.glo = (uint32_t)soff;
-                        r.hi = (uint32_t)((uint64_t)soff >> 32) | ((v & 255u) << 8) | (motif << 16) | ((uint32_t)rd.hp << 18);
-                        r.order = rd.order;
+                        e1 = true;
+                        r1 = PRec::make(soff, v & 255u, motif, rd.hp, rd.order);
                     }
                 };
-                if (q0 == 'C' && q1 == 'G' && s0 == 'C' && s1 == 'G')  // CpG, recorded at the reference C
-                    look(rd.rev ? L - 1 - (qp + 1) : qp, g, 0, e0, r0);
+                if (cpg_columns(q0, q1, s0, s1)) {  // CpG, recorded at the reference C
+                    const int p = cpg_call(b, rd, qp);
+                    if (p >= 0) {
+                        e0 = true;
+                        r0 = PRec::make(g, (uint32_t)p, 0, rd.hp, rd.order);
+                    }
+                }
                 if (eq3 && q0 == 'C' && q2 == 'G') {  // CHG: forward reads CCG/CAG/CTG, reverse reads CGG/CAG/CTG
                     const bool mid = rd.rev ? (q1 == 'G' || q1 == 'A' || q1 == 'T') : (q1 == 'C' || q1 == 'A' || q1 == 'T');
-                    if (mid) look(rd.rev ? L - 1 - (qp + 2) : qp, g, 1, e1, r1);
+                    if (mid) look(rd.rev ? L - 1 - (qp + 2) : qp, g, 1);
                 } else if (eq3 && q0 == 'C' && isH(q1) && isH(q2)) {  // CHH on the reference's forward strand
-                    look(rd.rev ? L - 1 - qp : qp, g, 2, e1, r1);
+                    look(rd.rev ? L - 1 - qp : qp, g, 2);
                 } else if (eq3 && isD(q0) && isD(q1) && q2 == 'G') {  // CHH on the reverse strand, recorded at the G
-                    look(rd.rev ? L - 1 - (qp + 2) : qp + 2, g + 2, 2, e1, r1);
+                    look(rd.rev ? L - 1 - (qp + 2) : qp + 2, g + 2, 2);
                 }
             }
         }
         stage_record(e0, r0, stage, &n_stage);
         stage_record(e1, r1, stage, &n_stage);
-    }
-    __syncthreads();
-    const int n = n_stage;
-    if (threadIdx.x == 0 && n) out_base = atomicAdd(counter, (unsigned long long)n);
-    __syncthreads();
-    if (n) {  // 12-byte records move as a stream of dwords
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(stage);
-        uint32_t* dst = reinterpret_cast<uint32_t*>(out + out_base);
-        for (int i = threadIdx.x; i < 3 * n; i += TPB) dst[i] = src[i];
-    }
+    });
+    flush_stage(stage, &n_stage, out, counter);
 }
 
 // ---- counting (pileup.cpp:529-557) -------------------------------------------------------------------------
-__global__ __launch_bounds__(TPB) void count_kernel(const PRec* __restrict__ recs, int64_t n, uint32_t thr_packed,
-                                                     int32_t* __restrict__ pcov, int32_t* __restrict__ ncov,
-                                                     uint32_t* __restrict__ key) {
-    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
-        const PRec r = recs[i];
-        const int64_t g = (int64_t)r.glo | ((int64_t)(r.hi & 255u) << 32);
-        const uint32_t prob = (r.hi >> 8) & 255u, motif = (r.hi >> 16) & 3u;
-        const uint32_t thr = (thr_packed >> (8 * motif)) & 255u;
-        atomicAdd(prob >= thr ? &pcov[g] : &ncov[g], 1);
-        atomicMax(&key[g], (r.order << 2) | motif);
-    }
-}
+struct CountPlanes {
+    int32_t *pcov, *ncov;
+    uint32_t* key;
+};
+struct CountHpPlanes : CountPlanes {  // + the haplotype partitions' pcov / ncov
+    int32_t *pcov1, *ncov1, *pcov2, *ncov2;
+};
 
-// count_kernel plus the haplotype partitions: a record tagged hp 1 / 2 also adds to that partition's pcov / ncov with the
-// same threshold.  No key atomics here: a partition's loci take their motif from the combined key plane.
-__global__ __launch_bounds__(TPB) void count_hp_kernel(const PRec* __restrict__ recs, int64_t n, uint32_t thr_packed,
-                                                        int32_t* __restrict__ pcov, int32_t* __restrict__ ncov,
-                                                        uint32_t* __restrict__ key, int32_t* __restrict__ pcov1,
-                                                        int32_t* __restrict__ ncov1, int32_t* __restrict__ pcov2,
-                                                        int32_t* __restrict__ ncov2) {
+// With CountHpPlanes a record tagged hp 1 / 2 also adds to that partition's pcov / ncov with the same threshold.  No key
+// atomics there: a partition's loci take their motif from the combined key plane.
+template <class Planes>
+__global__ __launch_bounds__(TPB) void count_kernel(const PRec* __restrict__ recs, int64_t n, uint32_t thr_packed, Planes pl) {
     for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
         const PRec r = recs[i];
-        const int64_t g = (int64_t)r.glo | ((int64_t)(r.hi & 255u) << 32);
-        const uint32_t prob = (r.hi >> 8) & 255u, motif = (r.hi >> 16) & 3u, hp = (r.hi >> 18) & 3u;
-        const uint32_t thr = (thr_packed >> (8 * motif)) & 255u;
-        const bool pos = prob >= thr;
-        atomicAdd(pos ? &pcov[g] : &ncov[g], 1);
-        atomicMax(&key[g], (r.order << 2) | motif);
-        if (hp == 1u) atomicAdd(pos ? &pcov1[g] : &ncov1[g], 1);
-        else if (hp == 2u) atomicAdd(pos ? &pcov2[g] : &ncov2[g], 1);
+        const int64_t g = r.gpos();
+        const uint32_t motif = r.motif();
+        const bool pos = r.prob() >= ((thr_packed >> (8 * motif)) & 255u);
+        atomicAdd(pos ? &pl.pcov[g] : &pl.ncov[g], 1);
+        atomicMax(&pl.key[g], (r.order << 2) | motif);
+        if constexpr (std::is_same_v<Planes, CountHpPlanes>) {
+            if (r.hp() == 1u) atomicAdd(pos ? &pl.pcov1[g] : &pl.ncov1[g], 1);
+            else if (r.hp() == 2u) atomicAdd(pos ? &pl.pcov2[g] : &pl.ncov2[g], 1);
+        }
     }
 }
 
@@ -344,17 +407,13 @@ __global__ __launch_bounds__(TPB) void count_hp_kernel(const PRec* __restrict__ 
 __global__ __launch_bounds__(TPB) void label_kernel(const PRec* __restrict__ recs, int64_t n, const int8_t* __restrict__ labels,
                                                      unsigned long long* __restrict__ bins) {
     __shared__ uint32_t h[1536];
-    for (int i = threadIdx.x; i < 1536; i += TPB) h[i] = 0u;
-    __syncthreads();
+    hist_zero(h, 1536);
     for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
         const PRec r = recs[i];
-        const int64_t g = (int64_t)r.glo | ((int64_t)(r.hi & 255u) << 32);
-        const int lab = labels[g];
-        if (lab >= 0) atomicAdd(&h[(((r.hi >> 16) & 3u) * 2u + (lab ? 1u : 0u)) * 256u + ((r.hi >> 8) & 255u)], 1u);
+        const int lab = labels[r.gpos()];
+        if (lab >= 0) atomicAdd(&h[(r.motif() * 2u + (lab ? 1u : 0u)) * 256u + r.prob()], 1u);
     }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 1536; i += TPB)
-        if (h[i]) atomicAdd(&bins[i], (unsigned long long)h[i]);
+    hist_flush(h, 1536, bins);
 }
 
 // ---- covered loci of a range, ascending ---------------------------------------------------------------------
@@ -531,46 +590,20 @@ struct PatRule {
     }
 };
 
-// One thread per aligned column, project_kernel's geometry.  A column that is a CpG member (project_kernel's motif-0 test) and
-// whose locus heads a valid window walks the read's runs forward to the other k - 1 loci and applies the member test there; a read
-// that is a member at all of them leaves one PWin.  The walk ends within max_span <= PAT_MAX_SPAN reference bases.
-__global__ __launch_bounds__(TPB) void pattern_kernel(const PRun* __restrict__ runs, const int64_t* __restrict__ col0, int n_runs,
-                                                       int64_t n_cols, const PRead* __restrict__ reads,
-                                                       const uint8_t* __restrict__ slab, const char* __restrict__ ref,
-                                                       const uint32_t* __restrict__ plane, const int32_t* __restrict__ matches,
-                                                       double min_pi, PatRule rule, PWin* __restrict__ out,
+// One thread per aligned column, project_kernel's geometry.  A column that is a CpG member and whose locus heads a valid window
+// walks the read's runs forward to the other k - 1 loci and applies the member test there; a read that is a member at all of them
+// leaves one PWin.  The walk ends within max_span <= PAT_MAX_SPAN reference bases.
+__global__ __launch_bounds__(TPB) void pattern_kernel(BatchView b, PatRule rule, PWin* __restrict__ out,
                                                        unsigned long long* __restrict__ counter) {
     __shared__ PWin stage[PTILE];  // a column heads at most one window
     __shared__ int n_stage;
-    __shared__ int run_range[2];
-    __shared__ unsigned long long out_base;
     if (threadIdx.x == 0) n_stage = 0;
-    if (threadIdx.x < 2) {
-        const int64_t c = min((int64_t)blockIdx.x * PTILE + (threadIdx.x ? PTILE - 1 : 0), n_cols - 1);
-        run_range[threadIdx.x] = find_run(col0, n_runs, c) + (int)threadIdx.x;
-    }
-    __syncthreads();
-    const int run_lo = run_range[0], run_hi = run_range[1];
-    for (int it = 0; it < PTILE / TPB; ++it) {
-        const int64_t c = (int64_t)blockIdx.x * PTILE + it * TPB + threadIdx.x;
+    walk_columns(b, [&](int ri, const PRun& run, int o, bool in_range) {
         bool e = false;
         PWin w{};
-        if (c < n_cols) {
-            const int ri = find_run(col0, n_runs, c, run_lo, run_hi);
-            const PRun run = runs[ri];
-            const int o = (int)(c - col0[ri]);
-            const PRead rd = reads[run.read];
-            bool live = rd.pass && run.len - o >= 2;
-            if (live && min_pi > 0.0) live = !(100.0 * matches[run.read] / rd.as_size < min_pi);
-            // the member test at offset `off` of run `r`, whose two columns lie in the run: the call's ML byte, or -1
-            auto member = [&](const PRun& r, int off) -> int {
-                const int qp = r.q0 + off;
-                const int64_t g = r.g0 + off;
-                if (stored_base(slab, rd, qp) != 'C' || stored_base(slab, rd, qp + 1) != 'G' || ref[g] != 'C' || ref[g + 1] != 'G') return -1;
-                const uint32_t v = plane[rd.plane_off + (rd.rev ? rd.l_qseq - 1 - (qp + 1) : qp)];
-                return (v & 0x100u) ? (int)(v & 255u) : -1;
-            };
-            const int p0 = live ? member(run, o) : -1;
+        if (in_range && run.len - o >= 2) {
+            const PRead rd = b.reads[run.read];
+            const int p0 = read_takes_part(rd, run.read, b.matches, b.min_pi) ? cpg_member(b, rd, run, o) : -1;
             if (p0 >= 0) {
                 const int64_t g = run.g0 + o;
                 const int64_t r = lower_rank(rule.cpg_pos, rule.n_cpg, g);
@@ -583,12 +616,12 @@ __global__ __launch_bounds__(TPB) void pattern_kernel(const PRun* __restrict__ r
                     for (int i = 1; i < rule.k && e; ++i) {
                         const int64_t gi = rule.cpg_pos[r + i];
                         while (cur.g0 + cur.len <= gi) {  // the run that holds g_i, if one of this read's does
-                            if (++rj >= n_runs) { e = false; break; }
-                            cur = runs[rj];
+                            if (++rj >= b.n_runs) { e = false; break; }
+                            cur = b.runs[rj];
                             if (cur.read != run.read) { e = false; break; }
                         }
                         if (!e || cur.g0 > gi || cur.g0 + cur.len - gi < 2) { e = false; break; }
-                        const int pi = member(cur, (int)(gi - cur.g0));
+                        const int pi = cpg_member(b, rd, cur, (int)(gi - cur.g0));
                         if (pi < 0) e = false;
                         else w.prob[i] = (uint8_t)pi;
                     }
@@ -596,16 +629,8 @@ __global__ __launch_bounds__(TPB) void pattern_kernel(const PRun* __restrict__ r
             }
         }
         stage_record(e, w, stage, &n_stage);
-    }
-    __syncthreads();
-    const int n = n_stage;
-    if (threadIdx.x == 0 && n) out_base = atomicAdd(counter, (unsigned long long)n);
-    __syncthreads();
-    if (n) {
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(stage);
-        uint32_t* dst = reinterpret_cast<uint32_t*>(out + out_base);
-        for (int i = threadIdx.x; i < 2 * n; i += TPB) dst[i] = src[i];
-    }
+    });
+    flush_stage(stage, &n_stage, out, counter);
 }
 
 // hist[rank * 16 + pattern] += 1 per window record, bit i of the pattern = prob[i] >= thr: integer atomics, any order
@@ -678,48 +703,26 @@ struct BmCounters {
     }
 };
 
-// -q and -f, as project_kernel applies them
-__device__ __forceinline__ bool read_takes_part(const PRead& rd, int read, const int32_t* __restrict__ matches, double min_pi) {
-    return rd.pass && !(min_pi > 0.0 && 100.0 * matches[read] / rd.as_size < min_pi);
-}
-
 // One thread per aligned column, project_kernel's geometry.  Only a column on the C of a reference CG goes further: the
 // alignment ends on it (nothing), its run ends on it or the stored bases are not C, G (DIFF), the read carries no 5mC entry there
 // (NOCALL); a member column adds nothing here, its record does in depth_count_kernel.
-__global__ __launch_bounds__(TPB) void depth_kernel(const PRun* __restrict__ runs, const int64_t* __restrict__ col0, int n_runs,
-                                                     int64_t n_cols, const PRead* __restrict__ reads, const uint8_t* __restrict__ slab,
-                                                     const char* __restrict__ ref, int64_t total, const uint32_t* __restrict__ plane,
-                                                     const int32_t* __restrict__ matches, double min_pi, BmCounters cnt) {
-    __shared__ int run_range[2];
-    if (threadIdx.x < 2) {
-        const int64_t c = min((int64_t)blockIdx.x * PTILE + (threadIdx.x ? PTILE - 1 : 0), n_cols - 1);
-        run_range[threadIdx.x] = find_run(col0, n_runs, c) + (int)threadIdx.x;
-    }
-    __syncthreads();
-    const int run_lo = run_range[0], run_hi = run_range[1];
-    for (int it = 0; it < PTILE / TPB; ++it) {
-        const int64_t c = (int64_t)blockIdx.x * PTILE + it * TPB + threadIdx.x;
-        if (c >= n_cols) continue;
-        const int ri = find_run(col0, n_runs, c, run_lo, run_hi);
-        const PRun run = runs[ri];
-        const int o = (int)(c - col0[ri]);
+__global__ __launch_bounds__(TPB) void depth_kernel(BatchView b, int64_t total, BmCounters cnt) {
+    walk_columns(b, [&](int ri, const PRun& run, int o, bool in_range) {
+        if (!in_range) return;
         const int64_t g = run.g0 + o;
-        if (ref[g] != 'C' || g + 1 >= total || ref[g + 1] != 'G') continue;
-        const PRead rd = reads[run.read];
-        if (!read_takes_part(rd, run.read, matches, min_pi)) continue;
+        if (b.ref[g] != 'C' || g + 1 >= total || b.ref[g + 1] != 'G') return;
+        const PRead rd = b.reads[run.read];
+        if (!read_takes_part(rd, run.read, b.matches, b.min_pi)) return;
         int cls = BM_DIFF;
         if (o == run.len - 1) {  // the run ends on the C
-            if (ri + 1 == n_runs || runs[ri + 1].read != run.read) continue;  // ... and so does the alignment
-        } else {
-            const int qp = run.q0 + o;
-            if (stored_base(slab, rd, qp) == 'C' && stored_base(slab, rd, qp + 1) == 'G') {
-                if (plane[rd.plane_off + (rd.rev ? rd.l_qseq - 1 - (qp + 1) : qp)] & 0x100u) continue;  // a member
-                cls = BM_NOCALL;
-            }
+            if (ri + 1 == b.n_runs || b.runs[ri + 1].read != run.read) return;  // ... and so does the alignment
+        } else if (cpg_columns(b, rd, run, o)) {
+            if (cpg_call(b, rd, run.q0 + o) >= 0) return;  // a member
+            cls = BM_NOCALL;
         }
         const int64_t r = cnt.rank_of(g);
         if (r >= 0) cnt.add(r, cls, rd.hp);
-    }
+    });
 }
 
 // One thread per D operation: DELETE at every reference CpG whose C it removes.  A long deletion is a loop in one thread.
@@ -738,9 +741,9 @@ __global__ __launch_bounds__(TPB) void depth_gap_kernel(const PGap* __restrict__
 __global__ __launch_bounds__(TPB) void depth_count_kernel(const PRec* __restrict__ recs, int64_t n, uint32_t thr, BmCounters cnt) {
     for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
         const PRec rec = recs[i];
-        if ((rec.hi >> 16) & 3u) continue;
-        const int64_t r = cnt.rank_of((int64_t)rec.glo | ((int64_t)(rec.hi & 255u) << 32));
-        if (r >= 0) cnt.add(r, ((rec.hi >> 8) & 255u) >= thr ? BM_MOD : BM_CANON, (rec.hi >> 18) & 3u);
+        if (rec.motif()) continue;
+        const int64_t r = cnt.rank_of(rec.gpos());
+        if (r >= 0) cnt.add(r, rec.prob() >= thr ? BM_MOD : BM_CANON, rec.hp());
     }
 }
 
@@ -785,35 +788,24 @@ struct PMember {        // 16 bytes: a member locus of record `read` of the batc
 static_assert(sizeof(PMember) == 16, "member entries are 16 bytes");
 
 // The batch's member list over its aligned COLUMNS [0, n_cols): column order keeps the members of a record together and ascending
-// in g.  The member test is pattern_kernel's (restated: that kernel stays as it is) behind -q / -f.
+// in g.  The selection skeleton asks per index, not per tile: the run search is the un-hinted one.
 struct MemberSel {
     using Row = PMember;
-    const PRun* runs;
-    const int64_t* col0;
-    int n_runs;
-    const PRead* reads;
-    const uint8_t* slab;
-    const char* ref;
-    const uint32_t* plane;
-    const int32_t* matches;
-    double min_pi;
+    BatchView b;
     // the ML byte of the member at column c, or -1
     __device__ int member(int64_t c, Row& m) const {
-        const int ri = find_run(col0, n_runs, c);
-        const PRun run = runs[ri];
-        const int o = (int)(c - col0[ri]);
+        const int ri = find_run(b.col0, b.n_runs, c);
+        const PRun run = b.runs[ri];
+        const int o = (int)(c - b.col0[ri]);
         if (run.len - o < 2) return -1;
-        const PRead rd = reads[run.read];
-        if (!read_takes_part(rd, run.read, matches, min_pi)) return -1;
-        const int qp = run.q0 + o;
-        const int64_t g = run.g0 + o;
-        if (stored_base(slab, rd, qp) != 'C' || stored_base(slab, rd, qp + 1) != 'G' || ref[g] != 'C' || ref[g + 1] != 'G') return -1;
-        const uint32_t v = plane[rd.plane_off + (rd.rev ? rd.l_qseq - 1 - (qp + 1) : qp)];
-        if (!(v & 0x100u)) return -1;
-        m.g = g;
+        const PRead rd = b.reads[run.read];
+        if (!read_takes_part(rd, run.read, b.matches, b.min_pi)) return -1;
+        const int p = cpg_member(b, rd, run, o);
+        if (p < 0) return -1;
+        m.g = run.g0 + o;
         m.read = run.read;
-        m.prob = v & 255u;
-        return (int)m.prob;
+        m.prob = (uint32_t)p;
+        return p;
     }
     __device__ bool pred(int64_t c) const {
         Row m;
@@ -1673,20 +1665,18 @@ struct hm_pileup {
     int patterns = 0, pattern_span = 150;
     DevBuf d_seqoff{EXACT}, d_cpg{EXACT}, d_phist{EXACT}, d_pcounter{EXACT}, d_pranks{EXACT}, d_precs{HALF};
     int64_t n_cpg = 0, n_precs = 0;
-    bool patterns_counted = false;
     // `pileup -M` ("bedmethyl" = 1), all of it only with the option on: d_seqoff, d_cpg and d_pranks above, shared with -E; five
     // uint32 depth counters per reference CpG and set (20 B, 60 B with partitions), resident from hm_pileup_set_reference on; the
     // staged D operations of a batch
     int bedmethyl = 0;
     DevBuf d_bm{EXACT}, d_gaps{HALF};
-    bool bedmethyl_counted = false;
     // `pileup -L` ("linkage" = max_dist), all of it only with the option on: three 256-bin uint64 histograms per distance
     // (6 144 B each), resident from hm_pileup_set_reference on; the member list of the batch that runs; the four counts per
     // distance of a fetch
     int linkage = 0;
     DevBuf d_lhist{EXACT}, d_ltab{EXACT}, d_members{HALF};
-    bool linkage_counted = false;
     uint32_t linkage_thr = 0;  // thr[CpG] of the last hm_pileup_count
+    bool counted = false;      // hm_pileup_count has run since hm_pileup_set_reference: what the -E, -M and -L fetches wait for
     int64_t n_recs = 0;
     bool bins_ready = false;
 
@@ -1901,8 +1891,25 @@ void ensure_bins(hm_pileup* p) {
     p->bins_ready = true;
 }
 
+// the uploaded batch of n_runs runs over `cols` columns
+BatchView batch_view(const hm_pileup* p, int n_runs, int64_t cols) {
+    return BatchView{p->d_runs.as<PRun>(), p->d_col0.as<int64_t>(), n_runs, cols, p->d_reads.as<PRead>(), p->d_slab.as<uint8_t>(),
+                     p->d_ref.as<char>(), p->d_plane.as<uint32_t>(), p->d_matches.as<int32_t>(), p->min_pi};
+}
+
 PatRule pattern_rule(const hm_pileup* p) {
     return PatRule{p->d_cpg.as<int64_t>(), p->n_cpg, p->d_seqoff.as<int64_t>(), (int)p->seq_off.size() - 1, p->patterns, p->pattern_span};
+}
+
+// ranks[0], ranks[1] = the first reference CpG at or behind lo, hi: the reference CpGs of [lo, hi) are the ranks [ranks[0], ranks[1])
+int cpg_rank_range(hm_pileup* p, int64_t lo, int64_t hi, int64_t ranks[2]) {
+    return guarded(p, [&] {
+        hipLaunchKernelGGL(pattern_ranks_kernel, dim3(1), dim3(64), 0, p->stream, p->d_cpg.as<int64_t>(), p->n_cpg, lo, hi, p->d_pranks.as<int64_t>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(ranks, p->d_pranks.p, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        return HM_OK;
+    });
 }
 
 BmCounters depth_counters(const hm_pileup* p, int set = 0) {
@@ -1923,7 +1930,6 @@ int list_reference_cpgs(hm_pileup* p) {
         HIP_TRY(hipMemsetAsync(p->d_pcounter.p, 0, sizeof(unsigned long long), p->stream));
     }
     p->n_cpg = p->n_precs = 0;
-    p->patterns_counted = p->bedmethyl_counted = false;
     if (total >= 2) {
         const int64_t n = stage_rows(p, RefCpgSel{p->d_ref.as<char>(), p->d_seqoff.as<int64_t>(), n_seqs, total}, 0, total, p->d_cpg,
                                      [](int64_t) { return true; }, no_hook);
@@ -1945,10 +1951,8 @@ int list_reference_cpgs(hm_pileup* p) {
 
 // `pileup -L`, under hm_pileup_run's guard behind the projection: the batch's member list through the selection skeleton (it
 // lives until the next batch), then every pair of it into the histograms.  <= 1024 workgroups: an entry is a loop over its pairs.
-int count_linkage_pairs(hm_pileup* p, int n_runs, int64_t cols) {
-    const MemberSel sel{p->d_runs.as<PRun>(), p->d_col0.as<int64_t>(), n_runs, p->d_reads.as<PRead>(), p->d_slab.as<uint8_t>(),
-                        p->d_ref.as<char>(), p->d_plane.as<uint32_t>(), p->d_matches.as<int32_t>(), p->min_pi};
-    const int64_t n = stage_rows(p, sel, 0, cols, p->d_members, [](int64_t) { return true; }, no_hook);
+int count_linkage_pairs(hm_pileup* p, const BatchView& batch) {
+    const int64_t n = stage_rows(p, MemberSel{batch}, 0, batch.n_cols, p->d_members, [](int64_t) { return true; }, no_hook);
     if (n < 0) return (int)n;
     if (n > 1)
         hipLaunchKernelGGL(linkage_pair_kernel, dim3(grid_for(n, 1024)), dim3(TPB), 0, p->stream, p->d_members.as<PMember>(), n, p->linkage,
@@ -2108,29 +2112,29 @@ const char* hm_pileup_last_error(const hm_pileup_t* p) { return p ? p->err.c_str
 int hm_pileup_set_option(hm_pileup_t* p, const char* key, double value) {
     if (!p || !key) return HM_EINVAL;
     const std::string k = key;
+    // what is sized or listed when the reference arrives (the partition planes, the reference CpGs and their counters, the
+    // linkage histograms) is decided before that; the planes also before the caller hands in planes of their own
+    const bool partitions = k == "partitions";
+    if (partitions || k == "patterns" || k == "pattern_span" || k == "bedmethyl" || k == "linkage") {
+        if (!p->seq_off.empty() || (partitions && !p->own_planes))
+            return pfail(p, HM_ESTATE, k + " must be set before hm_pileup_set_reference" + (partitions ? " / hm_pileup_use_planes" : ""));
+    }
     if (k == "min_mapq") p->min_mapq = (int)value;
     else if (k == "min_pi") p->min_pi = value;
-    else if (k == "partitions") {  // the planes are sized when the reference arrives: decide before that
-        if (!p->seq_off.empty() || !p->own_planes)
-            return pfail(p, HM_ESTATE, "partitions must be set before hm_pileup_set_reference / hm_pileup_use_planes");
+    else if (partitions) {
         if (value != 0.0 && value != 2.0) return pfail(p, HM_EINVAL, "partitions must be 0 or 2");
         p->partitions = (int)value;
-    } else if (k == "patterns" || k == "pattern_span") {  // the reference CpGs are listed when the reference arrives
-        if (!p->seq_off.empty()) return pfail(p, HM_ESTATE, k + " must be set before hm_pileup_set_reference");
-        if (k == "patterns") {
-            if (value != 0.0 && value != 2.0 && value != 3.0 && value != 4.0) return pfail(p, HM_EINVAL, "patterns must be 0, 2, 3 or 4");
-            p->patterns = (int)value;
-        } else {
-            if (!(value >= 1.0 && value <= (double)PAT_MAX_SPAN) || value != std::floor(value))
-                return pfail(p, HM_EINVAL, "pattern_span must be an integer in 1 .. 65536");
-            p->pattern_span = (int)value;
-        }
-    } else if (k == "bedmethyl") {  // the reference CpGs are listed and their counters sized when the reference arrives
-        if (!p->seq_off.empty()) return pfail(p, HM_ESTATE, "bedmethyl must be set before hm_pileup_set_reference");
+    } else if (k == "patterns") {
+        if (value != 0.0 && value != 2.0 && value != 3.0 && value != 4.0) return pfail(p, HM_EINVAL, "patterns must be 0, 2, 3 or 4");
+        p->patterns = (int)value;
+    } else if (k == "pattern_span") {
+        if (!(value >= 1.0 && value <= (double)PAT_MAX_SPAN) || value != std::floor(value))
+            return pfail(p, HM_EINVAL, "pattern_span must be an integer in 1 .. 65536");
+        p->pattern_span = (int)value;
+    } else if (k == "bedmethyl") {
         if (value != 0.0 && value != 1.0) return pfail(p, HM_EINVAL, "bedmethyl must be 0 or 1");
         p->bedmethyl = (int)value;
-    } else if (k == "linkage") {  // the histogram table is sized when the reference arrives
-        if (!p->seq_off.empty()) return pfail(p, HM_ESTATE, "linkage must be set before hm_pileup_set_reference");
+    } else if (k == "linkage") {
         if (value != 0.0 && (!(value >= 2.0 && value <= (double)LINK_MAX_DIST) || value != std::floor(value)))
             return pfail(p, HM_EINVAL, "linkage must be 0 or an integer in 2 .. 16384");
         p->linkage = (int)value;
@@ -2174,6 +2178,7 @@ int hm_pileup_set_reference(hm_pileup_t* p, int32_t n_seqs, const int64_t* seq_l
     const int64_t total = p->seq_off.back();
     if (total >= (int64_t(1) << 40)) return pfail(p, HM_EINVAL, "reference longer than 2^40 bases");
     return guarded(p, [&] {
+        p->counted = false;
         p->d_ref.reserve((size_t)total + 4);
         HIP_TRY(hipMemcpyAsync(p->d_ref.p, bases, (size_t)total, hipMemcpyHostToDevice, p->stream));
         if (p->own_planes) {
@@ -2208,7 +2213,6 @@ int hm_pileup_set_reference(hm_pileup_t* p, int32_t n_seqs, const int64_t* seq_l
             const size_t bytes = sizeof(unsigned long long) * LH_HISTS * 256 * ((size_t)p->linkage + 1);
             p->d_lhist.reserve(bytes);
             HIP_TRY(hipMemsetAsync(p->d_lhist.p, 0, bytes, p->stream));
-            p->linkage_counted = false;
         }
         HIP_TRY(hipStreamSynchronize(p->stream));
         return HM_OK;
@@ -2330,39 +2334,32 @@ int hm_pileup_run(hm_pileup_t* p) {
         HIP_TRY(hipMemsetAsync(p->d_matches.p, 0, 4 * (size_t)n_reads, st));
 
         if (n_mods)  // <= 1024 workgroups: each flushes up to 768 histogram bins with same-address global atomics (~10 ns each)
-            hipLaunchKernelGGL(mods_kernel, dim3(grid_for(n_mods, 1024)), dim3(TPB), 0, st, p->d_mods.as<PMod>(), n_mods,
+            hipLaunchKernelGGL(entries_kernel<PMod>, dim3(grid_for(n_mods, 1024)), dim3(TPB), 0, st, p->d_mods.as<PMod>(), n_mods,
                                p->d_reads.as<PRead>(), p->d_slab.as<uint8_t>(), p->d_plane.as<uint32_t>(),
                                p->d_bins.as<unsigned long long>());
         if (n_calls)  // the records submitted with calls: their plane words and histogram counts, same grid rule
-            hipLaunchKernelGGL(calls_kernel, dim3(grid_for(n_calls, 1024)), dim3(TPB), 0, st, p->d_calls.as<PCall>(), n_calls,
+            hipLaunchKernelGGL(entries_kernel<PCall>, dim3(grid_for(n_calls, 1024)), dim3(TPB), 0, st, p->d_calls.as<PCall>(), n_calls,
                                p->d_reads.as<PRead>(), p->d_slab.as<uint8_t>(), p->d_plane.as<uint32_t>(),
                                p->d_bins.as<unsigned long long>());
+        const BatchView batch = batch_view(p, n_runs, cols);
         if (cols > 0) {
             const int64_t blocks = (cols + TPB - 1) / TPB, pblocks = (cols + PTILE - 1) / PTILE;
             if (blocks >= (int64_t(1) << 31)) return pfail(p, HM_EINVAL, "batch too large: submit fewer records per hm_pileup_run");
             if (p->min_pi > 0.0)
-                hipLaunchKernelGGL(identity_kernel, dim3((unsigned)blocks), dim3(TPB), 0, st, p->d_runs.as<PRun>(),
-                                   p->d_col0.as<int64_t>(), n_runs, cols, p->d_reads.as<PRead>(), p->d_slab.as<uint8_t>(),
-                                   p->d_ref.as<char>(), p->d_matches.as<int32_t>());
-            hipLaunchKernelGGL(project_kernel, dim3((unsigned)pblocks), dim3(TPB), 0, st, p->d_runs.as<PRun>(),
-                               p->d_col0.as<int64_t>(), n_runs, cols, p->d_reads.as<PRead>(), p->d_slab.as<uint8_t>(),
-                               p->d_ref.as<char>(), p->d_plane.as<uint32_t>(), p->d_matches.as<int32_t>(), p->min_pi,
-                               p->d_recs.as<PRec>(), p->d_counter.as<unsigned long long>());
+                hipLaunchKernelGGL(identity_kernel, dim3((unsigned)blocks), dim3(TPB), 0, st, batch, p->d_matches.as<int32_t>());
+            hipLaunchKernelGGL(project_kernel, dim3((unsigned)pblocks), dim3(TPB), 0, st, batch, p->d_recs.as<PRec>(),
+                               p->d_counter.as<unsigned long long>());
             if (p->patterns && p->n_cpg)
-                hipLaunchKernelGGL(pattern_kernel, dim3((unsigned)pblocks), dim3(TPB), 0, st, p->d_runs.as<PRun>(), p->d_col0.as<int64_t>(),
-                                   n_runs, cols, p->d_reads.as<PRead>(), p->d_slab.as<uint8_t>(), p->d_ref.as<char>(),
-                                   p->d_plane.as<uint32_t>(), p->d_matches.as<int32_t>(), p->min_pi, pattern_rule(p), p->d_precs.as<PWin>(),
+                hipLaunchKernelGGL(pattern_kernel, dim3((unsigned)pblocks), dim3(TPB), 0, st, batch, pattern_rule(p), p->d_precs.as<PWin>(),
                                    p->d_pcounter.as<unsigned long long>());
             if (p->bedmethyl && p->n_cpg)
-                hipLaunchKernelGGL(depth_kernel, dim3((unsigned)pblocks), dim3(TPB), 0, st, p->d_runs.as<PRun>(), p->d_col0.as<int64_t>(), n_runs,
-                                   cols, p->d_reads.as<PRead>(), p->d_slab.as<uint8_t>(), p->d_ref.as<char>(), p->seq_off.back(),
-                                   p->d_plane.as<uint32_t>(), p->d_matches.as<int32_t>(), p->min_pi, depth_counters(p));
+                hipLaunchKernelGGL(depth_kernel, dim3((unsigned)pblocks), dim3(TPB), 0, st, batch, p->seq_off.back(), depth_counters(p));
         }
         if (n_gaps)  // deletions are rare next to columns: one thread each
             hipLaunchKernelGGL(depth_gap_kernel, dim3(grid_for(n_gaps, 1024)), dim3(TPB), 0, st, p->d_gaps.as<PGap>(), n_gaps,
                                p->d_reads.as<PRead>(), p->d_matches.as<int32_t>(), p->min_pi, depth_counters(p));
         if (p->linkage && cols > 0) {
-            const int rc = count_linkage_pairs(p, n_runs, cols);
+            const int rc = count_linkage_pairs(p, batch);
             if (rc != HM_OK) return rc;
         }
         HIP_TRY(hipGetLastError());
@@ -2400,9 +2397,9 @@ int64_t hm_pileup_fetch_records(hm_pileup_t* p, int64_t* gpos, uint8_t* prob, ui
     });
     if (rc < 0) return rc;
     for (size_t i = 0; i < h.size(); ++i) {
-        if (gpos) gpos[i] = (int64_t)h[i].glo | ((int64_t)(h[i].hi & 255u) << 32);
-        if (prob) prob[i] = (uint8_t)(h[i].hi >> 8);
-        if (motif) motif[i] = (uint8_t)((h[i].hi >> 16) & 3u);
+        if (gpos) gpos[i] = h[i].gpos();
+        if (prob) prob[i] = (uint8_t)h[i].prob();
+        if (motif) motif[i] = (uint8_t)h[i].motif();
         if (order) order[i] = h[i].order;
     }
     return p->n_recs;
@@ -2437,13 +2434,14 @@ int hm_pileup_count(hm_pileup_t* p, const uint8_t thr[3]) {
         ensure_bins(p);
         if (p->n_recs) {
             const uint32_t packed = thr[0] | ((uint32_t)thr[1] << 8) | ((uint32_t)thr[2] << 16);
+            const CountPlanes own{p->pcov, p->ncov, p->key};
             if (p->partitions == 2)
-                hipLaunchKernelGGL(count_hp_kernel, dim3(grid_for(p->n_recs, 1 << 16)), dim3(TPB), 0, p->stream,
-                                   p->d_recs.as<PRec>(), p->n_recs, packed, p->pcov, p->ncov, p->key, p->hp_pcov[0],
-                                   p->hp_ncov[0], p->hp_pcov[1], p->hp_ncov[1]);
+                hipLaunchKernelGGL(count_kernel<CountHpPlanes>, dim3(grid_for(p->n_recs, 1 << 16)), dim3(TPB), 0, p->stream,
+                                   p->d_recs.as<PRec>(), p->n_recs, packed,
+                                   CountHpPlanes{own, p->hp_pcov[0], p->hp_ncov[0], p->hp_pcov[1], p->hp_ncov[1]});
             else
-                hipLaunchKernelGGL(count_kernel, dim3(grid_for(p->n_recs, 1 << 16)), dim3(TPB), 0, p->stream, p->d_recs.as<PRec>(),
-                                   p->n_recs, packed, p->pcov, p->ncov, p->key);
+                hipLaunchKernelGGL(count_kernel<CountPlanes>, dim3(grid_for(p->n_recs, 1 << 16)), dim3(TPB), 0, p->stream,
+                                   p->d_recs.as<PRec>(), p->n_recs, packed, own);
             HIP_TRY(hipGetLastError());
         }
         if (p->patterns && p->n_precs) {  // <= 1024 workgroups: every record is one fire-and-forget atomic
@@ -2461,9 +2459,7 @@ int hm_pileup_count(hm_pileup_t* p, const uint8_t thr[3]) {
         HIP_TRY(hipStreamSynchronize(p->stream));
         p->n_recs = 0;
         p->n_precs = 0;
-        p->patterns_counted = p->patterns != 0;
-        p->bedmethyl_counted = p->bedmethyl != 0;
-        p->linkage_counted = p->linkage != 0;
+        p->counted = true;
         p->linkage_thr = thr[0];
         return HM_OK;
     });
@@ -2484,18 +2480,12 @@ int64_t hm_pileup_num_pattern_records(hm_pileup_t* p) { return p ? p->n_precs : 
 int64_t hm_pileup_fetch_patterns(hm_pileup_t* p, int64_t lo, int64_t hi, int64_t min_reads, hm_pattern_t* out, int64_t cap) {
     if (!p) return HM_EINVAL;
     if (!p->patterns || p->seq_off.empty()) return pfail(p, HM_ESTATE, "hm_pileup_fetch_patterns without option patterns (then hm_pileup_set_reference)");
-    if (!p->patterns_counted) return pfail(p, HM_ESTATE, "hm_pileup_fetch_patterns before hm_pileup_count");
+    if (!p->counted) return pfail(p, HM_ESTATE, "hm_pileup_fetch_patterns before hm_pileup_count");
     if (lo < 0 || hi < lo) return pfail(p, HM_EINVAL, "hm_pileup_fetch_patterns: bad range");
     if (min_reads < 1) return pfail(p, HM_EINVAL, "hm_pileup_fetch_patterns: min_reads must be >= 1");
     if (hi == lo || !p->n_cpg) return 0;
-    int64_t ranks[2] = {0, 0};
-    const int rc = guarded(p, [&] {  // the windows of [lo, hi) are those of the ranks [ranks[0], ranks[1])
-        hipLaunchKernelGGL(pattern_ranks_kernel, dim3(1), dim3(64), 0, p->stream, p->d_cpg.as<int64_t>(), p->n_cpg, lo, hi, p->d_pranks.as<int64_t>());
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(ranks, p->d_pranks.p, sizeof ranks, hipMemcpyDeviceToHost, p->stream));
-        HIP_TRY(hipStreamSynchronize(p->stream));
-        return HM_OK;
-    });
+    int64_t ranks[2] = {0, 0};  // the windows of [lo, hi) are those headed by its reference CpGs
+    const int rc = cpg_rank_range(p, lo, hi, ranks);
     if (rc != HM_OK) return rc;
     if (ranks[1] <= ranks[0]) return 0;
     return compact_rows(p, PatSel{pattern_rule(p), p->d_phist.as<uint32_t>(), min_reads}, ranks[0], ranks[1], out, cap, no_hook, no_hook);
@@ -2505,20 +2495,14 @@ int64_t hm_pileup_fetch_patterns(hm_pileup_t* p, int64_t lo, int64_t hi, int64_t
 int64_t hm_pileup_fetch_bedmethyl(hm_pileup_t* p, int32_t part, int64_t lo, int64_t hi, int64_t min_valid, hm_bedmethyl_t* out, int64_t cap) {
     if (!p) return HM_EINVAL;
     if (!p->bedmethyl || p->seq_off.empty()) return pfail(p, HM_ESTATE, "hm_pileup_fetch_bedmethyl without option bedmethyl (then hm_pileup_set_reference)");
-    if (!p->bedmethyl_counted) return pfail(p, HM_ESTATE, "hm_pileup_fetch_bedmethyl before hm_pileup_count");
+    if (!p->counted) return pfail(p, HM_ESTATE, "hm_pileup_fetch_bedmethyl before hm_pileup_count");
     if (part < 0 || part > 2) return pfail(p, HM_EINVAL, "hm_pileup_fetch_bedmethyl: part must be 0, 1 or 2");
     if (part && p->partitions != 2) return pfail(p, HM_ESTATE, "hm_pileup_fetch_bedmethyl: part 1 / 2 without the partitions option");
     if (lo < 0 || hi < lo) return pfail(p, HM_EINVAL, "hm_pileup_fetch_bedmethyl: bad range");
     if (min_valid < 0) return pfail(p, HM_EINVAL, "hm_pileup_fetch_bedmethyl: min_valid must be >= 0");
     if (hi == lo || !p->n_cpg) return 0;
     int64_t ranks[2] = {0, 0};
-    const int rc = guarded(p, [&] {  // the reference CpGs of [lo, hi) are the ranks [ranks[0], ranks[1])
-        hipLaunchKernelGGL(pattern_ranks_kernel, dim3(1), dim3(64), 0, p->stream, p->d_cpg.as<int64_t>(), p->n_cpg, lo, hi, p->d_pranks.as<int64_t>());
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(ranks, p->d_pranks.p, sizeof ranks, hipMemcpyDeviceToHost, p->stream));
-        HIP_TRY(hipStreamSynchronize(p->stream));
-        return HM_OK;
-    });
+    const int rc = cpg_rank_range(p, lo, hi, ranks);
     if (rc != HM_OK) return rc;
     if (ranks[1] <= ranks[0]) return 0;
     return compact_rows(p, BmSel{p->d_cpg.as<int64_t>(), depth_counters(p, part).bm, min_valid}, ranks[0], ranks[1], out, cap, no_hook, no_hook);
@@ -2528,7 +2512,7 @@ int64_t hm_pileup_fetch_bedmethyl(hm_pileup_t* p, int32_t part, int64_t lo, int6
 int64_t hm_pileup_fetch_linkage(hm_pileup_t* p, int64_t min_pairs, hm_linkage_t* out, int64_t cap) {
     if (!p) return HM_EINVAL;
     if (!p->linkage || p->seq_off.empty()) return pfail(p, HM_ESTATE, "hm_pileup_fetch_linkage without option linkage (then hm_pileup_set_reference)");
-    if (!p->linkage_counted) return pfail(p, HM_ESTATE, "hm_pileup_fetch_linkage before hm_pileup_count");
+    if (!p->counted) return pfail(p, HM_ESTATE, "hm_pileup_fetch_linkage before hm_pileup_count");
     if (min_pairs < 0) return pfail(p, HM_EINVAL, "hm_pileup_fetch_linkage: min_pairs must be >= 0");
     const int rc = guarded(p, [&] {
         p->d_ltab.reserve(sizeof(unsigned long long) * 4 * ((size_t)p->linkage + 1));

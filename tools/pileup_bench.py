@@ -3,7 +3,7 @@
 
 A random genome, error-free reads (one '=' CIGAR op each, both strands) with call-like MM/ML tags; the MM/ML lists are
 parsed once on the host and the staged batches are replayed, so the timed region is what the GPU does per batch:
-H2D of the staged records, plane memset, mods_kernel, project_kernel, then count_kernel and the covered-loci
+H2D of the staged records, plane memset, entries_kernel, project_kernel, then count_kernel and the covered-loci
 compaction at the end.  Prints one JSON object; `--check` verifies that the per-locus counters add up to the number of projected calls.
 `--partitions`: the haplotype-resolved engine (`pileup -H`), every read tagged with a random HP of {none, 1, 2}; the loci
 fetch then also compacts the two partitions' planes.
@@ -23,12 +23,16 @@ all rows (reduce per distance, LinkSel, D2H): pairs per second, rows, share of a
 `--bedmethyl`: the depth classes of `pileup -M`, timed like `--patterns`: the passes on an engine without the option, then on one with
 it; the leg is what the option adds to projection and counting plus one fetch of the rows (D2H included).  The synthetic reads are
 error-free: the column kernel and the record count run at full size, the deletion kernel has nothing to do.
+`--digest`: a sha256 of every output that must not depend on the build -- the records of one pass (sorted by order, gpos, motif: the
+append order is not fixed), the loci of the combined set and of each partition, and the rows of `--patterns`, `--bedmethyl` (each set)
+and `--linkage` -- under "digest" in the JSON object, for comparing two builds of the library (HM_LIB_PATH) byte for byte.
 `--parts N` (with `--domains`): the same segments chained from N equal pieces next to the single fetch (three stateless passes per piece).
 
     python tools/pileup_bench.py --genome-mb 20 --coverage 10 [--partitions [--asm [--asm-q] [--asm-regions]]] [--sites] [--domains [--fit] [--parts N]] [--patterns K] [--bedmethyl] [--linkage D]
 """
 import argparse
 import ctypes as C
+import hashlib
 import json
 import os
 import sys
@@ -120,6 +124,7 @@ def main():
     ap.add_argument("--linkage", type=int, default=0, metavar="D",
                     help="time what the within-read co-methylation by distance up to D bases adds (pileup -L D, min_pairs 1)")
     ap.add_argument("--bedmethyl", action="store_true", help="time what the per-CpG depth classes add (pileup -M, min_valid 1)")
+    ap.add_argument("--digest", action="store_true", help="add a sha256 of the records, the loci and the rows of the timed options")
     ap.add_argument("--cpu-baseline", action="store_true",
                     help="time the reference's own projection code (oracle/_ref/ref_align -t) on a bounded sample")
     a = ap.parse_args()
@@ -180,6 +185,15 @@ def main():
     one_pass(pu)                                   # warm-up (allocations)
     wins_per_pass = pu.num_pattern_records()
     recs_per_pass = pu.num_records()
+    digest = {}
+
+    def sha(rows):
+        return hashlib.sha256(np.ascontiguousarray(rows).tobytes()).hexdigest()
+
+    if a.digest:                                   # the warm-up pass's records, still resident
+        g, p, m, o = pu.records()
+        at = np.lexsort(((g << 2) | m, o))
+        digest["records"] = sha(np.rec.fromarrays([o[at], g[at], m[at], p[at]]))
     pu.count([128, 128, 128])
     t0 = time.perf_counter()
     for _ in range(a.repeat):
@@ -429,6 +443,16 @@ def main():
                 np.add.at(add, (j, 0), x["pcov"])
                 np.add.at(add, (j, 1), x["ncov"])
             out["check_partitions_within_combined"] = bool((add[:, 0] <= loci["pcov"]).all() and (add[:, 1] <= loci["ncov"]).all())
+    if a.digest:
+        digest["loci"] = sha(loci)
+        digest["partition_loci"] = [sha(x) for x in hp_loci]
+        if a.patterns:
+            digest["patterns"] = sha(pu.patterns())
+        if a.bedmethyl:
+            digest["bedmethyl"] = [sha(pu.bedmethyl(partition=k)) for k in ((0, 1, 2) if a.partitions else (0,))]
+        if a.linkage:
+            digest["linkage"] = sha(pu.linkage())
+        out["digest"] = digest
     if a.cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(genome, chrom, starts, staged, a.read_len)
     print(json.dumps(out))
