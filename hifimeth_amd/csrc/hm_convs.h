@@ -59,6 +59,19 @@ struct SCfg {
     }
 };
 
+// a Copy with `static constexpr bool TIERED = true` also has NT short tiers (slot counts T::tier(0) < .. < T::tier(NT - 1) < CS) and a wave-uniform
+// member `need` (SConvR::run)
+template <class T, class = void>
+struct copy_is_tiered : std::false_type {
+    static constexpr int NT = 0;
+    static constexpr int tier(int) { return 0; }
+};
+template <class T>
+struct copy_is_tiered<T, std::enable_if_t<T::TIERED>> : std::true_type {
+    static constexpr int NT = T::NT;
+    static constexpr int tier(int i) { return T::tier(i); }
+};
+
 template <int I, int N, class F>
 __device__ __forceinline__ void static_for(F&& f) {
     if constexpr (I < N) {
@@ -131,11 +144,17 @@ struct SConvR {
         half8 x[XS][GMAX][2];
         constexpr int CS = Copy::CS;
         static_assert(CS + 2 <= NB, "a copy slot per k-block");
+        // A TIERED copy (Copy::TIERED, hm_trunk3.hip) carries the number of list entries that must be stored: the groups in front of
+        // the last one exist once per tier -- with one of Copy's short slot counts or all CS slots, a wave-uniform branch for the lot -- and the
+        // last group, which refills the weight registers (values that would have to meet in one place behind a branch), exists once
+        constexpr bool TIERED = copy_is_tiered<Copy>::value;
+        constexpr int NHEAD = TIERED ? NB - KB : 0;
+        static_assert(!TIERED || (NG > 1 && CS + 2 <= NHEAD), "a tiered copy's slots end before the last group");
         // copy pipeline over k-blocks: block c fetches the row number of slot c, reads the row of slot c - 1 out of the
         // planes and stores the row of slot c - 2
         int crow[3];
         half8 cdat[2];
-        const uint8_t* cpr = CS > 0 ? cp.rows + 2 * __builtin_amdgcn_readfirstlane(tid >> 6) + (lane >> 5) : nullptr;
+        const uint8_t* cpr = CS > 0 ? cp.rows + 2 * __builtin_amdgcn_readfirstlane(tid >> 6) + (lane >> 5) : nullptr;  // (slot c: list entries 2 NWV c .. + 2 NWV)
 
         auto reads = [&](auto c_) __attribute__((always_inline)) {
             constexpr int c = decltype(c_)::value, g = c / KB, kb = c % KB;
@@ -151,8 +170,9 @@ struct SConvR {
         };
         static_for<0, (C::XD < NB ? C::XD : NB)>(reads);
 
-        static_for<0, NB>([&](auto c_) __attribute__((always_inline)) {
+        auto block = [&](auto c_, auto cs_) __attribute__((always_inline)) {
             constexpr int c = decltype(c_)::value, g = c / KB, kb = c % KB, G = gs[g];
+            constexpr int CS = decltype(cs_)::value;   // this block's copy slots (a tier's)
             if constexpr (kb == 0) {
 #pragma unroll
                 for (int i = 0; i < G; ++i)
@@ -232,7 +252,23 @@ struct SConvR {
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
-        });
+        };
+        using CsAll = std::integral_constant<int, CS>;
+        if constexpr (TIERED) {
+            auto pick = [&](auto self, auto i_) __attribute__((always_inline)) -> void {
+                constexpr int i = decltype(i_)::value;
+                if constexpr (i == copy_is_tiered<Copy>::NT) {
+                    static_for<0, NHEAD>([&](auto c_) __attribute__((always_inline)) { block(c_, CsAll{}); });
+                } else {
+                    using CsI = std::integral_constant<int, copy_is_tiered<Copy>::tier(i)>;
+                    static_assert(CsI::value < CS, "short tiers in ascending order");
+                    if (cp.need <= 2 * Copy::NWV * CsI::value) static_for<0, NHEAD>([&](auto c_) __attribute__((always_inline)) { block(c_, CsI{}); });
+                    else self(self, std::integral_constant<int, i + 1>{});
+                }
+            };
+            pick(pick, std::integral_constant<int, 0>{});
+        }
+        static_for<NHEAD, NB>([&](auto c_) __attribute__((always_inline)) { block(c_, CsAll{}); });
         {
             constexpr int g = NG - 1;
 #pragma unroll

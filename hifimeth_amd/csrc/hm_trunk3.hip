@@ -57,9 +57,17 @@ constexpr int T3_AROWS = T3_M + T3_H3, T3_BROWS = T3_M + T3_H2;             // p
 constexpr int T3_XROWS = 128;                       // feature rows of a step: 112 + K1 - 1 <= 124
 constexpr int T3_LDS_HALVES = 2 * T3_AROWS * TR_RS + 2 * T3_BROWS * TR_RS + 2 * (T3_H1 + T3_H3) * TR_RS;
 // a step's record (rowlist3_kernel): three lists of TR_OWN plane-row numbers (the E1 / E2 / E3 rows an edge chain reads), the list of
-// the E4 rows some site's tail reads (T3_N4 entries, meaningful when there are at most that many) and their number
+// the E4 rows some site's tail reads (T3_N4 entries, meaningful when there are at most that many) and a count word: byte 0 the number
+// of E4 rows (255: all), bytes 1 .. 3 the number of leading entries of the E1 / E2 / E3 list that must be stored (the flagged rows, and
+// the fill row where the layer's last new row is not one of them)
 constexpr int T3_N4 = 64, T3_RL3 = 3 * TR_OWN, T3_RL = T3_RL3 + T3_N4 + 4;
-constexpr int T3_RLW = 3 * 32 + T3_N4 / 4 + 1;      // words of a step's record in LDS: lists at 128-byte strides, the E4 list, its count
+constexpr int T3_RLW = 3 * 32 + T3_N4 / 4 + 1;      // words of a step's record in LDS: lists at 128-byte strides, the E4 list, the count word
+// Copy-slot tiers: a layer's stream exists with 2, 4, 6 and all TR_OWN / 8 = 14 copy slots per wave (16, 32, 48, 112 list entries); a
+// step takes, per layer, the shortest one that covers the entries its record says must be stored (one wave-uniform branch per layer
+// call).  On the bench's reads CpG / CHG steps need <= 16 entries (95 .. 100 %), CHH steps <= 32 (E3: 90 %, E1 / E2: 30 %) or <= 48 (97 %)
+// (profiles/trunk_copy_slot_tiers.txt)
+constexpr int T3_TIER[] = {2, 4, 6};   // (tests/test_gpu_trunk_slots.py mirrors this set: TIERS)
+constexpr int T3_NT = sizeof(T3_TIER) / sizeof(int), T3_CS_ALL = TR_OWN / 8;
 static_assert(T3_M % 16 == 0 && T3_RL % 4 == 0 && T3_RL / 4 <= 256 && T3_XROWS >= T3_M + 12, "tile plan");
 
 // conv4 over the NEEDED rows only: row m of the list -> plane A row rows[m] (its taps 8 and 16 rows further on), map row rows[m].
@@ -103,11 +111,21 @@ struct EpiE43 {  // conv4 rows leave the trunk already split, [hi 96 | lo 96]
         *reinterpret_cast<half4*>(g + (size_t)m * (2 * C4_CH) + C4_CH + col) = l;
     }
 };
-template <int NWV_>
+// CS_ slots cover the first 2 * NWV_ * CS_ entries of the list (slot c of wave w: entries 2 NWV c + 2 w, + 1); the default covers all of it
+template <int NWV_, int CS_ = TR_OWN / (2 * NWV_)>
 struct CopyRows3 {
-    static constexpr int NWV = NWV_, CS = TR_OWN / (2 * NWV_);  // NWV waves x 2 rows x CS slots = one list entry each
+    static constexpr int NWV = NWV_, CS = CS_;  // NWV waves x 2 rows x CS slots = one list entry each
+    static_assert(CS_ >= 0 && 2 * NWV_ * CS_ <= TR_OWN, "slots within the list");
     const uint8_t* rows;  // LDS: this layer's list of TR_OWN plane-row numbers
     half_t* g;            // map row of plane row 0
+};
+// the same with the tier chosen inside the layer's stream (SConvR::run: the groups in front of the last one once per tier)
+template <int NWV_>
+struct CopyRows3T : CopyRows3<NWV_> {
+    static constexpr bool TIERED = true;
+    static constexpr int NT = T3_NT;
+    static constexpr int tier(int i) { return T3_TIER[i]; }
+    int need;             // wave-uniform: leading list entries that must be stored
 };
 
 // workgroup barrier that orders LDS traffic only: vector-memory operations (a step's map-row stores) stay in flight across it
@@ -229,6 +247,7 @@ __global__ __launch_bounds__(64) void rowlist3_kernel(const TrunkTile* __restric
         if (kind[k] == 0) continue;
         const int blk = (int)blockIdx.x * T3_RPB + k;
         int n4 = 255;
+        uint32_t nst = 0;   // bytes 1 .. 3: list entries of E1 / E2 / E3 that must be stored (the all-fill record: 0, the shortest tier's fill entries do)
         if (kind[k] == 1) {
             const int u = tl[k].u0 - (warm[k] ? TR_OWN : 0);
             auto sat = [&](int y) __attribute__((always_inline)) { return (int)sf[k][y - u - W0]; };   // y - u in [W0, W0 + WN)
@@ -265,6 +284,8 @@ __global__ __launch_bounds__(64) void rowlist3_kernel(const TrunkTile* __restric
                 const uint64_t b0 = __ballot((f[0] >> l) & 1), b1 = __ballot((f[1] >> l) & 1);
                 if ((f[0] >> l) & 1) rec[k][l * TR_OWN + __popcll(b0 & below)] = (uint8_t)(first_new[l] + r);
                 if ((f[1] >> l) & 1) rec[k][l * TR_OWN + __popcll(b0) + __popcll(b1 & below)] = (uint8_t)(first_new[l] + r + 64);
+                // the flagged rows, and one fill entry behind them unless the last new row (the fill row) is flagged itself
+                nst |= (uint32_t)(__popcll(b0) + __popcll(b1) + (int)(~(b1 >> (TR_OWN - 1 - 64)) & 1)) << (8 * (l + 1));
             }
             // the E4 list: the needed rows in ascending order, filled up with the first of them (a row is stored twice: harmless)
             const uint64_t n0 = __ballot(need4[0]), n1 = __ballot(need4[1]);
@@ -276,7 +297,7 @@ __global__ __launch_bounds__(64) void rowlist3_kernel(const TrunkTile* __restric
                 if (r >= n4) rec[k][T3_RL3 + r] = n4 > 0 ? rec[k][T3_RL3] : (uint8_t)0;   // (r < 64 = T3_N4)
             }
         }
-        if (r == 0) *reinterpret_cast<uint32_t*>(&rec[k][T3_RL3 + T3_N4]) = (uint32_t)n4;
+        if (r == 0) *reinterpret_cast<uint32_t*>(&rec[k][T3_RL3 + T3_N4]) = (uint32_t)n4 | nst;
         __syncthreads();
         uint32_t* out = reinterpret_cast<uint32_t*>(rowlist + (size_t)blk * T3_RL);
         for (int i = r; i < T3_RL / 4; i += 64) out[i] = reinterpret_cast<const uint32_t*>(rec[k])[i];   // (a dense step's E4 list is never read)
@@ -418,8 +439,9 @@ void trunk3_kernel(const TrunkTile* __restrict__ tiles, int n_tiles, int n_views
     // (b, a) = (1, 2) / (4, 5); the pair on one range of position tiles, a alone on the other
     const int nt04 = wave == 0 ? 0 : wave == 1 ? 1 : wave == 2 ? 3 : 4;
     using L1 = SConv<C1, C2, 0, 2, 2, 3>;
-    using L2 = SConv<C2, C3, 0, 3, 4>;  // the longest group last: it is the window in which the next layer's weights can be fetched
-    using L3 = SConv<C3, C4, 0, 3, 4>;
+    // conv2 / conv3: all copy slots lie in the first two groups (24 k-blocks), the next layer's weights are fetched in the last one
+    using L2 = SConv<C2, C3, 0, 2, 2, 3>;
+    using L3 = SConv<C3, C4, 0, 2, 2, 3>;
     static_assert(T3_XROWS <= NW * 64, "one feature row per thread");
     auto wf = [&](int i) { return reinterpret_cast<const half_t*>(W.wfrag_h[i]); };
     const half_t* c1f = reinterpret_cast<const half_t*>(W.c1f);
@@ -560,6 +582,27 @@ void trunk3_kernel(const TrunkTile* __restrict__ tiles, int n_tiles, int n_views
             warm = bd.warm;
             continue;
         }
+        // the step's count word.  conv2 and conv3 choose their copy-slot tier inside the stream (CopyRows3T); conv4's first call, which
+        // fetches no weights, exists once per tier as a whole
+#ifdef HM_XP_T3_NOCOPY
+        struct Cp23 : CopyRows3<NW, 0> { int need; };
+#else
+        using Cp23 = CopyRows3T<NW>;
+#endif
+        const uint32_t cw = (uint32_t)__builtin_amdgcn_readfirstlane((int)rlist[buf][T3_RLW - 1]);
+        auto with_slots = [&](const int need, auto&& f) __attribute__((always_inline)) {
+#ifdef HM_XP_T3_NOCOPY   // timing ablation (make nocopy): no E1 .. E3 row leaves the trunk -- wrong results
+            f(std::integral_constant<int, 0>{});
+#else
+            auto pick = [&](auto self, auto i_) __attribute__((always_inline)) -> void {
+                constexpr int i = decltype(i_)::value;
+                if constexpr (i == T3_NT) f(std::integral_constant<int, T3_CS_ALL>{});
+                else if (need <= 8 * T3_TIER[i]) f(std::integral_constant<int, T3_TIER[i]>{});
+                else self(self, std::integral_constant<int, i + 1>{});
+            };
+            pick(pick, std::integral_constant<int, 0>{});
+#endif
+        };
         // E1's kept rows come back into plane A (conv4 of the previous step is through with its rows 0 .. 3)
         move_rows<T3_H1, NW * 64>(a_hi, a_lo, h1_hi, h1_lo, threadIdx.x);
         L1::run(xb, xb, wr, EpiTrunk3{a_hi + T3_H1 * TR_RS, a_lo + T3_H1 * TR_RS}, wf(1), W.bias[1], nt0, nt0);
@@ -568,7 +611,7 @@ void trunk3_kernel(const TrunkTile* __restrict__ tiles, int n_tiles, int n_views
         __syncthreads();
         TS(2);
         build_desc2(cur_warm, cur_calib != 0);
-        L2::run(a_hi, a_lo, wr, EpiTrunk3{b_hi + T3_H2 * TR_RS, b_lo + T3_H2 * TR_RS}, wf(2), W.bias[2], nt0, nt0, CopyRows3<NW>{rl, g1});
+        L2::run(a_hi, a_lo, wr, EpiTrunk3{b_hi + T3_H2 * TR_RS, b_lo + T3_H2 * TR_RS}, wf(2), W.bias[2], nt0, nt0, Cp23{{rl, g1}, (int)((cw >> 8) & 255)});
         // E1's last rows wait in H1 for the next step (conv3 is about to overwrite them)
         move_rows<T3_H1, NW * 64>(h1_hi, h1_lo, a_hi + T3_M * TR_RS, a_lo + T3_M * TR_RS, threadIdx.x);
         TS(3);
@@ -578,7 +621,7 @@ void trunk3_kernel(const TrunkTile* __restrict__ tiles, int n_tiles, int n_views
         build_loads();
         // E3's kept rows come back into plane A rows 0 .. 15 (conv2 is through with them; conv3 writes rows 16 ..)
         move_rows<T3_H3, NW * 64>(a_hi, a_lo, h3_hi, h3_lo, threadIdx.x);
-        L3::run(b_hi, b_lo, wr, EpiTrunk3{a_hi + T3_H3 * TR_RS, a_lo + T3_H3 * TR_RS}, wf(3), W.bias[3], nt0, nt04, CopyRows3<NW>{rl + 128, g2});
+        L3::run(b_hi, b_lo, wr, EpiTrunk3{a_hi + T3_H3 * TR_RS, a_lo + T3_H3 * TR_RS}, wf(3), W.bias[3], nt0, nt04, Cp23{{rl + 128, g2}, (int)((cw >> 16) & 255)});
         TS(5);
         __syncthreads();
         TS(6);
@@ -587,7 +630,7 @@ void trunk3_kernel(const TrunkTile* __restrict__ tiles, int n_tiles, int n_views
         move_rows<T3_H2, NW * 64>(b_hi, b_lo, b_hi + T3_M * TR_RS, b_lo + T3_M * TR_RS, threadIdx.x);
         // a warm-up step's E4 rows are not results (its kept rows were not): they go to the dump
         const EpiE43 e4{cur_calib ? dump_cal : cur_warm ? dump : reinterpret_cast<half_t*>(mp.e4) + grow0 * (2 * C4_CH)};
-        const int n4 = __builtin_amdgcn_readfirstlane((int)rlist[buf][T3_RLW - 1]);
+        const int n4 = cw & 255, ns3 = cw >> 24;
         if (!cur_warm && n4 <= T3_N4) {
             ++n_list;
             // ---- conv4 over the listed rows only: four m-tiles of needed rows instead of seven of all (CpG / CHG at their usual densities) ----
@@ -596,20 +639,28 @@ void trunk3_kernel(const TrunkTile* __restrict__ tiles, int n_tiles, int n_views
             const EpiE4L e4l{reinterpret_cast<half_t*>(mp.e4) + grow0 * (2 * C4_CH), rows4};
             using NoCp = typename SConvR<C4, C1, ListRows4, 2, 2>::NoCopy;
             if (wave & 1) {  // a = resident tile 1 alone on list tiles 0, 1 (with the E3 copy slots), the pair on list tiles 2, 3
-                SConvR<C4s, void, ListRows4, 0, 1, 1>::template run<1>(a_hi, a_lo, wr, e4l, c1f, W.c1f_bias, nt04, nt0, CopyRows3<NW>{rl + 256, g3}, rm);
+                with_slots(ns3, [&](auto cs_) __attribute__((always_inline)) {
+                    SConvR<C4s, void, ListRows4, 0, 1, 1>::template run<1>(a_hi, a_lo, wr, e4l, c1f, W.c1f_bias, nt04, nt0, CopyRows3<NW, decltype(cs_)::value>{rl + 256, g3}, rm);
+                });
                 SConvR<C4, C1, ListRows4, 2, 2>::run(a_hi, a_lo, wr, e4l, c1f, W.c1f_bias, nt04, nt0, NoCp{}, rm);
             } else {         // the pair on list tiles 0, 1, a = resident tile 0 alone on list tiles 2, 3
-                SConvR<C4, void, ListRows4, 0, 1, 1>::run(a_hi, a_lo, wr, e4l, c1f, W.c1f_bias, nt04, nt0, CopyRows3<NW>{rl + 256, g3}, rm);
+                with_slots(ns3, [&](auto cs_) __attribute__((always_inline)) {
+                    SConvR<C4, void, ListRows4, 0, 1, 1>::run(a_hi, a_lo, wr, e4l, c1f, W.c1f_bias, nt04, nt0, CopyRows3<NW, decltype(cs_)::value>{rl + 256, g3}, rm);
+                });
                 SConvR<C4s, C1, ListRows4, 2, 2>::template run<0>(a_hi, a_lo, wr, e4l, c1f, W.c1f_bias, nt04, nt0, NoCp{}, rm);
             }
         } else
         // the four-tile part first (it carries the E3 copy slots), the three-tile part last (behind it the next step's conv1
         // weights are fetched into the registers it frees)
         if (wave & 1) {  // a = resident tile 1 alone on position tiles 0 .. 3, the pair on tiles 4 .. 6
-            SConv<C4s, void, 0, 2, 2>::template run<1>(a_hi, a_lo, wr, e4, c1f, W.c1f_bias, nt04, nt0, CopyRows3<NW>{rl + 256, g3});
+            with_slots(ns3, [&](auto cs_) __attribute__((always_inline)) {
+                SConv<C4s, void, 0, 2, 2>::template run<1>(a_hi, a_lo, wr, e4, c1f, W.c1f_bias, nt04, nt0, CopyRows3<NW, decltype(cs_)::value>{rl + 256, g3});
+            });
             SConv<C4, C1, 4, 3>::run(a_hi, a_lo, wr, e4, c1f, W.c1f_bias, nt04, nt0);
         } else {         // the pair on position tiles 0 .. 3, a = resident tile 0 alone on tiles 4 .. 6
-            SConv<C4, void, 0, 2, 2>::run(a_hi, a_lo, wr, e4, c1f, W.c1f_bias, nt04, nt0, CopyRows3<NW>{rl + 256, g3});
+            with_slots(ns3, [&](auto cs_) __attribute__((always_inline)) {
+                SConv<C4, void, 0, 2, 2>::run(a_hi, a_lo, wr, e4, c1f, W.c1f_bias, nt04, nt0, CopyRows3<NW, decltype(cs_)::value>{rl + 256, g3});
+            });
             SConv<C4s, C1, 4, 3>::template run<0>(a_hi, a_lo, wr, e4, c1f, W.c1f_bias, nt04, nt0);
         }
         build_store(buf ^ 1);
