@@ -31,9 +31,6 @@ __device__ __forceinline__ uint32_t split_lo2(uint32_t h01, float x0, float x1) 
         "v_fma_mixhi_f16 %0, -%1, 1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
         : "=&v"(l)
         : "v"(h01), "v"(x0), "v"(x1));
-#ifdef HM_XP_LO_BITS   // experiment: the lo halves rounded to 10 - HM_XP_LO_BITS mantissa bits (operand toggling vs the clock the chip holds)
-    l = (l + ((1u << (HM_XP_LO_BITS - 1)) * 0x00010001u)) & ((0xffffu << HM_XP_LO_BITS & 0xffffu) * 0x00010001u);
-#endif
     return l;
 }
 
@@ -56,7 +53,6 @@ __device__ __forceinline__ void split4(const f32x4& v, half4& hi, half4& lo) {
 //   CIN >= 32 : channels c0 + 8*lk .. +7 of tap (32*kb)/CIN          (a block never straddles taps)
 //   CIN == 8  : all 8 channels of tap 4*kb + lk
 // S sites may be stacked along M (tail kernel): row m -> (site = m / LOUT, p = m % LOUT), site stride ISS halves.
-// WLO = false drops the w_lo*x_hi pass: the layer then runs with plain fp16 WEIGHTS (BASELINE.json configs[4]).
 // XLO = false: the activations are exact fp16 (no lo plane; the w_hi*x_lo pass is dropped).  EDGE: the first and the last
 // position tile are written through epi.edge() (conv1 with bn0 folded into the weights, see hm_weights.cpp).
 // KSTACK = K1 > 0 (conv1 with an exact operand): the hi and the lo halves of the weights are stacked along K as 2*K1
@@ -64,7 +60,7 @@ __device__ __forceinline__ void split4(const f32x4& v, half4& hi, half4& lo) {
 // product per block covers both and only ceil(2*K1 / 4) blocks are needed (7 instead of 4 x 2 for K1 = 13).  KT_ is then
 // the number of tap slots (a multiple of 4) and the weights have no plane dimension.
 template <int NW_, int CIN_, int KT_, int COUT_, int LOUT_, int IRS_, int WM_, int WN_, int BR_ = 2, int S_ = 1,
-          int ISS_ = 0, int ROW0_ = 0, bool WLO = true, bool XLO = true, bool EDGE = false, int KSTACK = 0, bool ILV = false, int LASTT = 0,
+          int ISS_ = 0, int ROW0_ = 0, bool XLO = true, bool EDGE = false, int KSTACK = 0, bool ILV = false, int LASTT = 0,
           int MSTR_ = 2, int DIL_ = 1>
 struct ConvH {
     // MSTR: LDS rows between consecutive output positions (2 = the model's stride-2 conv over one site's rows, 1 = dense
@@ -115,7 +111,7 @@ struct ConvH {
 #pragma unroll
             for (int j = 0; j < NTW; ++j) {
                 h.w[r][j][0] = wp[(size_t)(j * KB + r) * WSTR];
-                if (WLO && !KSTACK) h.w[r][j][1] = wp[(size_t)(j * KB + r) * WSTR + 64];
+                if (!KSTACK) h.w[r][j][1] = wp[(size_t)(j * KB + r) * WSTR + 64];
             }
     }
 
@@ -187,11 +183,11 @@ struct ConvH {
             for (int j = 0; j < NTW; ++j) {
                 if (r < HB) {
                     wq[r][j][0] = head->w[r < HB ? r : 0][j][0];
-                    if (WLO && !KSTACK) wq[r][j][1] = head->w[r < HB ? r : 0][j][1];
+                    if (!KSTACK) wq[r][j][1] = head->w[r < HB ? r : 0][j][1];
                     continue;
                 }
                 wq[r][j][0] = wp[(size_t)(j * KB + r) * WSTR];
-                if (WLO && !KSTACK) wq[r][j][1] = wp[(size_t)(j * KB + r) * WSTR + 64];
+                if (!KSTACK) wq[r][j][1] = wp[(size_t)(j * KB + r) * WSTR + 64];
             }
         {
             const int bo0 = KSTACK ? stack_off(0) : 0;
@@ -210,7 +206,7 @@ struct ConvH {
 #pragma unroll
                 for (int j = 0; j < NTW; ++j) {
                     wq[(RB + BR - 1) % BR][j][0] = wp[(size_t)(j * KB + kw) * WSTR];
-                    if (WLO && !KSTACK) wq[(RB + BR - 1) % BR][j][1] = wp[(size_t)(j * KB + kw) * WSTR + 64];
+                    if (!KSTACK) wq[(RB + BR - 1) % BR][j][1] = wp[(size_t)(j * KB + kw) * WSTR + 64];
                 }
             }
             {
@@ -227,7 +223,7 @@ struct ConvH {
             // MTW*NTW other MFMAs (no back-to-back dependent MFMAs)
 #pragma unroll
             for (int pr = 0; pr < 3; ++pr) {
-                if ((pr == 1 && !XLO) || (pr == 2 && (!WLO || KSTACK))) continue;  // (w_hi, x_hi), (w_hi, x_lo), (w_lo, x_hi)
+                if ((pr == 1 && !XLO) || (pr == 2 && KSTACK)) continue;  // (w_hi, x_hi), (w_hi, x_lo), (w_lo, x_hi)
 #pragma unroll
                 for (int i = 0; i < MTW; ++i)
 #pragma unroll
@@ -236,8 +232,8 @@ struct ConvH {
                                                                            acc[i][j], 0, 0, 0);
             }
             if (ILV) {  // the block's own LDS reads ride between its MFMAs instead of in front of them
-                constexpr int NP = 1 + (XLO ? 1 : 0) + ((WLO && !KSTACK) ? 1 : 0);
-                constexpr int NM = NP * MTW * NTW, ND = MTW * (XLO ? 2 : 1), NV = NTW * ((WLO && !KSTACK) ? 2 : 1);
+                constexpr int NP = 1 + (XLO ? 1 : 0) + (!KSTACK ? 1 : 0);
+                constexpr int NM = NP * MTW * NTW, ND = MTW * (XLO ? 2 : 1), NV = NTW * (!KSTACK ? 2 : 1);
 #pragma unroll
                 for (int q = 0; q < ND; ++q) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -275,7 +271,7 @@ struct ConvH {
                     for (int b = KB - LASTT; b < KB; ++b)
 #pragma unroll
                         for (int pr = 0; pr < 3; ++pr) {
-                            if ((pr == 1 && !XLO) || (pr == 2 && (!WLO || KSTACK))) continue;
+                            if ((pr == 1 && !XLO) || (pr == 2 && KSTACK)) continue;
                             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wq[b % BR][j][pr == 2 ? 1 : 0], x[b % 2][i][pr == 1 ? 1 : 0],
                                                                                acc[i][j], 0, 0, 0);
                         }

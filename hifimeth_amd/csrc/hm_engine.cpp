@@ -118,12 +118,9 @@ struct hm_engine {
     int min_read_size = 1000;  // mod_options.cpp:10
     int64_t sub_batch = 65536;
     int front_waves = 8;
-    // 0 = fp32 MFMA; 1 = split-half f16x3 MFMA with fp32 accumulate (default).  (Rounds 1-2 also had 2 / 3 = plain fp16 WEIGHTS in
-    // conv6..conv8 / conv2..conv8 for BASELINE.json configs[4]: the literal configuration misses its 1e-3 bar -- 2.5e-3 -- and the
-    // part that holds it bought nothing; closed in round 3, see README "configs[4]" and profiles/r02_term_error_table.txt.)
-    // 2 = as 1, with plain fp16 WEIGHTS (the w_lo x_hi product and the lo plane's fetches dropped) in conv8 and fc1: what of BASELINE.json
-    // configs[4] ("fp16 CNN weights, |dp| <= 1e-3") holds its bar with margin over multi-million-site sweeps (conv3 alone --
-    // 11 % of the trunk's MFMAs -- reaches 1.3e-3 over 6.1 M sites: diagnostic option conv3_w16, profiles/r05_parity_sweep_conv3_w16.txt)
+    // 0 = fp32 MFMA; 1 = split-half f16x3 MFMA with fp32 accumulate (default); 2 = as 1, with plain fp16 WEIGHTS (the w_lo x_hi product
+    // and the lo plane's fetches dropped) in conv8 and fc1, |dp| <= 1e-3.  The wider fp16-weight modes of rounds 1 and 2
+    // are closed: README "configs[4]", DESIGN.md.
     int precision = 1;
     int conv3_w16 = 0;   // diagnostic: conv3 of the dense trunk with plain fp16 weights (measured above the 1e-3 bar; not part of any mode)
     int max_slots = 3;  // batch slots of the asynchronous API (the legacy calls use one more, slot 0)
@@ -382,7 +379,7 @@ void launch_cnn_pair(hm_engine* e, std::vector<TimedSpan>* spans, int ctx, const
         Span sp(e, spans, K_FRONT, ctx, sr.off, sr.cap);
         if (e->precision >= 1)
             launch_front_h(e->stream, dm.k1, sr, reads, bases, kin, windows, dm.w, e->d_act4.as<float>(), e->num_cu, dbg,
-                           dbg_layer, e->stamps_on ? e->d_stamps.as<unsigned long long>() : nullptr, false);
+                           dbg_layer, e->stamps_on ? e->d_stamps.as<unsigned long long>() : nullptr);
         else
             launch_front(e->stream, dm.k1, sr, reads, bases, kin, windows, dm.w, e->d_act4.as<float>(), e->num_cu, dbg,
                          dbg_layer, e->front_waves, e->stamps_on ? e->d_stamps.as<unsigned long long>() : nullptr);
@@ -392,7 +389,7 @@ void launch_cnn_pair(hm_engine* e, std::vector<TimedSpan>* spans, int ctx, const
     {
         Span sp(e, spans, K_TAIL, ctx, sr.off, sr.cap);
         if (e->precision >= 1)
-            launch_tail_h(e->stream, e->d_act4.as<float>(), sr, dm.w, logits, p, ml, e->num_cu, dbg, dbg_layer, 0);
+            launch_tail_h(e->stream, e->d_act4.as<float>(), sr, dm.w, logits, p, ml, e->num_cu, dbg, dbg_layer);
         else
             launch_tail(e->stream, e->d_act4.as<float>(), sr, dm.w, logits, p, ml, e->num_cu, dbg, dbg_layer);
         sp.end();
@@ -581,7 +578,6 @@ void run_trunk_path(hm_batch* b, std::vector<TimedSpan>* spans, int ctx_mask) {
         e->d_zeros.reserve(1024);
         HIP_TRY(hipMemsetAsync(e->d_zeros.p, 0, 1024, e->stream));
     }
-    const bool w16 = false;
     const int32_t* offs = b->d_offs.as<int32_t>();
     for (const auto& g : b->groups) {
         const TrunkMaps maps{{e->grp.d_map[0].as<uint16_t>(), e->grp.d_map[1].as<uint16_t>(), e->grp.d_map[2].as<uint16_t>()},
@@ -620,11 +616,11 @@ void run_trunk_path(hm_batch* b, std::vector<TimedSpan>* spans, int ctx_mask) {
                                   b->d_totals.as<int32_t>() + TOT_LIST_STEPS, b->d_tcost.as<int32_t>() + g.cost_lo, e->num_cu, e->conv3_w16 != 0);
                 else if (e->trunk_impl)
                     launch_trunk2(e->stream, dm.k1, b->d_tiles.as<TrunkTile>() + g.tile_lo, n_tiles, n_views, c, b->d_rinfo.as<RInfo>(),
-                                  b->d_bases.as<uint8_t>(), b->d_kin.as<uint32_t>(), b->d_sctx.as<uint8_t>(), dm.w, maps, e->num_cu, w16,
+                                  b->d_bases.as<uint8_t>(), b->d_kin.as<uint32_t>(), b->d_sctx.as<uint8_t>(), dm.w, maps, e->num_cu,
                                   e->trunk_impl == 2);
                 else
                     launch_trunk(e->stream, dm.k1, b->d_tiles.as<TrunkTile>() + g.tile_lo, n_tiles, n_views, c, b->d_rinfo.as<RInfo>(),
-                                 b->d_bases.as<uint8_t>(), b->d_kin.as<uint32_t>(), b->d_sctx.as<uint8_t>(), dm.w, maps, e->num_cu, w16);
+                                 b->d_bases.as<uint8_t>(), b->d_kin.as<uint32_t>(), b->d_sctx.as<uint8_t>(), dm.w, maps, e->num_cu);
                 sp.end();
             }
             {
@@ -634,7 +630,7 @@ void run_trunk_path(hm_batch* b, std::vector<TimedSpan>* spans, int ctx_mask) {
                                  maps, e->grp.d_edge4.as<uint16_t>(), e->grp.d_e4row.as<int32_t>(), e->num_cu);
                 else
                     launch_edge(e->stream, dm.k1, sr, b->d_rinfo.as<RInfo>(), b->d_bases.as<uint8_t>(), b->d_kin.as<uint32_t>(), dm.w,
-                                maps, e->grp.d_edge4.as<uint16_t>(), e->grp.d_e4row.as<int32_t>(), e->num_cu, w16);
+                                maps, e->grp.d_edge4.as<uint16_t>(), e->grp.d_e4row.as<int32_t>(), e->num_cu);
                 sp.end();
             }
             {
@@ -666,7 +662,7 @@ void run_trunk_path(hm_batch* b, std::vector<TimedSpan>* spans, int ctx_mask) {
                                          b->d_logits.as<float>(), b->d_p.as<float>(), b->d_ml.as<uint8_t>(), e->num_cu, e->precision == 2);
                 else
                     launch_tail_gather(e->stream, sr, dm.w, maps, e->grp.d_edge4.as<uint16_t>(), e->grp.d_e4row.as<int32_t>(),
-                                       b->d_logits.as<float>(), b->d_p.as<float>(), b->d_ml.as<uint8_t>(), e->num_cu, 0);
+                                       b->d_logits.as<float>(), b->d_p.as<float>(), b->d_ml.as<uint8_t>(), e->num_cu);
                 sp.end();
             }
         }
@@ -876,8 +872,7 @@ int hm_set_option(hm_engine_t* e, const char* key, int64_t value) {
     else if (k == "precision") {
         if (value < 0 || value > 2)
             return fail(e, HM_EINVAL, "precision must be 0 (fp32 MFMA), 1 (split-half f16x3 MFMA, fp32 accumulate) or 2 (as 1 with plain fp16 weights in "
-                                      "conv8 and fc1: |dp| <= 1e-3); BASELINE.json configs[4] as written -- fp16 weights in every layer -- "
-                                      "misses its 1e-3 bar (round 2's modes 2 / 3, closed)");
+                                      "conv8 and fc1: |dp| <= 1e-3)");
         if (value == 2 && (e->tail_impl == 0 || e->tail_impl == 2))
             return fail(e, HM_EINVAL, "precision 2 needs tail_impl 1 or 3 (the resident / strip tail kernels carry the fp16-weight variants)");
         e->precision = (int)value;

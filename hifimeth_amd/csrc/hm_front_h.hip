@@ -114,7 +114,7 @@ __device__ __forceinline__ void dump_planes(const half_t* hi, const half_t* lo, 
     }
 }
 
-template <int K1, bool RAW, bool STAMP = false, bool W16 = false>
+template <int K1, bool RAW, bool STAMP = false>
 __global__ __launch_bounds__(512) void front_kernel_h(SiteRange sr,
                                                        const ReadDesc* __restrict__ reads,
                                                        const uint8_t* __restrict__ bases,
@@ -253,10 +253,10 @@ __global__ __launch_bounds__(512) void front_kernel_h(SiteRange sr,
         if constexpr (FOLD) build_window_f(cx, t, nt);
         else build_window(s, t, nt);
     };
-    using C2 = ConvH<NW, 128, 3, 128, G::L2, G::RS, 1, 8, 3, 1, 0, 0, !W16, true, false, 0, true, 1>;
-    using C3 = ConvH<NW, 128, 3, 128, G::L3, G::RS, 1, 8, 3, 1, 0, 0, !W16, true, false, 0, true, 1>;
-    using C4 = ConvH<NW, 128, 3, C4_CH, G::L4, G::RS, 1, 6, 3, 1, 0, 0, !W16, true, false, 0, true, 1>;
-    using C1 = ConvH<NW, 8, (2 * K1 + 3) / 4 * 4, 128, G::L1, G::WRS, 1, 8, 4, 1, 0, 0, true, false, true, K1, true>;
+    using C2 = ConvH<NW, 128, 3, 128, G::L2, G::RS, 1, 8, 3, 1, 0, 0, true, false, 0, true, 1>;
+    using C3 = ConvH<NW, 128, 3, 128, G::L3, G::RS, 1, 8, 3, 1, 0, 0, true, false, 0, true, 1>;
+    using C4 = ConvH<NW, 128, 3, C4_CH, G::L4, G::RS, 1, 6, 3, 1, 0, 0, true, false, 0, true, 1>;
+    using C1 = ConvH<NW, 8, (2 * K1 + 3) / 4 * 4, 128, G::L1, G::WRS, 1, 8, 4, 1, 0, 0, false, true, K1, true>;
     constexpr int HB1 = HEADS ? 3 : 0, HB2 = HEADS ? 2 : 0, HB3 = HEADS ? 2 : 0, HB4 = HEADS ? HB4V : 0;
     typename C1::template Head<HB1> h1;
     if constexpr (FOLD) C1::load_head(reinterpret_cast<const half_t*>(W.c1f), W.c1f_bias, h1);
@@ -413,10 +413,7 @@ __device__ __forceinline__ void zero_pad_rows_h(half_t* hi, half_t* lo, int rs, 
 // the same 384 bytes as fp32), so the gather is a pure copy into the input planes: the spare waves of conv6 / conv7 /
 // conv8 issue it as LDS-DMA (global_load_lds_dwordx4: no VGPRs, no VALU split, no ds_write), one 1 KB piece of a plane per
 // wave instruction with a per-lane source address (a zero page for padding rows, row pads and sites past the end).
-// W16T: 0 = split (hi + lo) weights everywhere; 1 = plain fp16 weights in conv6..conv8 -- the part of the network where they hold
-// the |dp| <= 1e-3 bar of BASELINE.json configs[4] (tools/w16_error_table.py); 2 = also in conv5 (with conv2..conv4: the literal
-// configs[4], which misses its bar).  fc1 keeps split weights in every mode.
-template <int W16T, bool GATHER = false>
+template <bool GATHER = false>
 __global__ __launch_bounds__(512) void tail_kernel_h(const float* __restrict__ act4, SiteRange sr, CtxWeights W,
                                                       float* __restrict__ logits,
                                                       float* __restrict__ prob, uint8_t* __restrict__ ml,
@@ -648,12 +645,12 @@ __global__ __launch_bounds__(512) void tail_kernel_h(const float* __restrict__ a
 
         // (wave grids 2x3, 1x6, 4x1 and weight prefetch depths 4, 5 measured the same or worse in same-session A/Bs)
 #ifdef HM_TRUNK_STAMP
-        ConvH<NW, 96, 3, 96, T::L5, T::RS96, 4, 2, 3, S, T::IN_SS, 0, (W16T < 2)>::run(
+        ConvH<NW, 96, 3, 96, T::L5, T::RS96, 4, 2, 3, S, T::IN_SS, 0>::run(
             h0, l0, wf(4), EpiPlanesS<T::L5, T::RS96, T::C5_SS>{h1, l1, W.bias[4]},
             [&](int i) __attribute__((always_inline)) { if (tst) tts[10 + i] = hm_stamp(); });
         if (tst) { tacc[10] += tts[10] - tts[0]; tacc[11] += tts[11] - tts[10]; }
 #else
-        ConvH<NW, 96, 3, 96, T::L5, T::RS96, 4, 2, 3, S, T::IN_SS, 0, (W16T < 2)>::run(
+        ConvH<NW, 96, 3, 96, T::L5, T::RS96, 4, 2, 3, S, T::IN_SS, 0>::run(
             h0, l0, wf(4), EpiPlanesS<T::L5, T::RS96, T::C5_SS>{h1, l1, W.bias[4]});
 #endif
         zero_pad_rows_h<S, T::L5, 96>(h1, l1, T::RS96, T::C5_SS);
@@ -684,7 +681,7 @@ __global__ __launch_bounds__(512) void tail_kernel_h(const float* __restrict__ a
                 for (int k = 0; k < NHI; ++k) fake_def(phi[k]);
             }
         } else {
-            ConvH<NW, 96, 3, 96, T::L6, T::RS96, 1, 6, 3, S, T::C5_SS, 0, (W16T < 1)>::run(
+            ConvH<NW, 96, 3, 96, T::L6, T::RS96, 1, 6, 3, S, T::C5_SS, 0>::run(
                 h1, l1, wf(5), EpiPlanesS<T::L6, T::RS96, T::C6_SS>{h0, l0, W.bias[5]});
 #pragma unroll
             for (int k = 0; k < NHI; ++k) fake_def(phi[k]);
@@ -725,7 +722,7 @@ __global__ __launch_bounds__(512) void tail_kernel_h(const float* __restrict__ a
                 for (int k = 0; k < NLO; ++k) fake_def(plo[k]);
             }
         } else {
-            ConvH<NW, 96, 3, 64, T::L7, T::RS96, 1, 4, 3, S, T::C6_SS, 0, (W16T < 1)>::run(
+            ConvH<NW, 96, 3, 64, T::L7, T::RS96, 1, 4, 3, S, T::C6_SS, 0>::run(
                 h0, l0, wf(6), EpiPlanesS<T::L7, T::RS64, T::C7_SS>{h1, l1, W.bias[6]});
 #pragma unroll
             for (int k = 0; k < NLO; ++k) fake_def(plo[k]);
@@ -756,7 +753,7 @@ __global__ __launch_bounds__(512) void tail_kernel_h(const float* __restrict__ a
                 zero_in_pads(0, SPLIT_SITE, tl - 256, 128);
             }
         } else {
-            ConvH<NW, 64, 3, 64, T::L8, T::RS64, 1, 4, 3, S, T::C7_SS, 0, (W16T < 1)>::run(
+            ConvH<NW, 64, 3, 64, T::L8, T::RS64, 1, 4, 3, S, T::C7_SS, 0>::run(
                 h1, l1, wf(7), EpiRing<T::L8, T::RS64>{r_hi + slot * S * T::RING_SS, r_lo + slot * S * T::RING_SS, W.bias[7]});
         }
         TTS(7);
@@ -834,37 +831,28 @@ static int cnn_grid_h(const SiteRange& sr, int per_group, int grid) {
 }
 
 void launch_tail_h(hipStream_t st, const float* act4, const SiteRange& sr, const CtxWeights& w, float* logits,
-                   float* p, uint8_t* ml, int grid, float* dbg, int dbg_layer, int w16) {
+                   float* p, uint8_t* ml, int grid, float* dbg, int dbg_layer) {
     if (sr.cap <= 0) return;
     const dim3 g(cnn_grid_h(sr, TAIL_SITES, grid));
-#define HM_TAILA(LV)                                                                                                  \
-    hipLaunchKernelGGL((tail_kernel_h<LV, false>), g, dim3(512), 0, st, act4, sr, w, logits, p, ml, dbg, dbg_layer, \
-                       nullptr, nullptr, nullptr, nullptr)
-    (void)w16;  // (plain-fp16-weight variants W16T = 1 / 2: closed in round 3, no longer instantiated)
-    HM_TAILA(0);
-#undef HM_TAILA
+    hipLaunchKernelGGL((tail_kernel_h<false>), g, dim3(512), 0, st, act4, sr, w, logits, p, ml, dbg, dbg_layer,
+                       nullptr, nullptr, nullptr, nullptr);
 }
 
 void launch_tail_gather(hipStream_t st, const SiteRange& sr, const CtxWeights& w, const TrunkMaps& maps, const uint16_t* edge4,
-                        const int32_t* e4row, float* logits, float* p, uint8_t* ml, int grid, int w16) {
+                        const int32_t* e4row, float* logits, float* p, uint8_t* ml, int grid) {
     if (sr.cap <= 0) return;
     const dim3 g(cnn_grid_h(sr, TAIL_SITES, grid));
-#define HM_TAILG(LV)                                                                                                     \
-    hipLaunchKernelGGL((tail_kernel_h<LV, true>), g, dim3(512), 0, st, nullptr, sr, w, logits, p, ml, nullptr, 0,         \
-                       reinterpret_cast<const half_t*>(maps.e4), reinterpret_cast<const half_t*>(edge4), e4row,          \
-                       reinterpret_cast<const half_t*>(maps.zeros))
-    (void)w16;
-    HM_TAILG(0);
-#undef HM_TAILG
+    hipLaunchKernelGGL((tail_kernel_h<true>), g, dim3(512), 0, st, nullptr, sr, w, logits, p, ml, nullptr, 0,
+                       reinterpret_cast<const half_t*>(maps.e4), reinterpret_cast<const half_t*>(edge4), e4row,
+                       reinterpret_cast<const half_t*>(maps.zeros));
 }
 
 void launch_front_h(hipStream_t st, int k1, const SiteRange& sr, const ReadDesc* reads, const uint8_t* bases,
                     const uint32_t* kin, const float* windows, const CtxWeights& w, float* act4, int grid, float* dbg,
-                    int dbg_layer, unsigned long long* stamps, bool w16) {
+                    int dbg_layer, unsigned long long* stamps) {
     if (sr.cap <= 0) return;
     const dim3 g(cnn_grid_h(sr, 1, grid)), b(512);
     const bool raw = windows == nullptr;
-    (void)w16;  // (the fp16-weights variant: closed in round 3, no longer instantiated)
 #define HM_FRONT_H(K1, RAW, ST)                                                                                  \
     hipLaunchKernelGGL((front_kernel_h<K1, RAW, ST>), g, b, 0, st, sr, reads, bases, kin, windows, w, act4, dbg, \
                        dbg_layer, stamps)

@@ -40,9 +40,9 @@ int front_stamp_slots();
 // split-half (f16x3) variant of the front kernel: fp16 hi/lo operands on v_mfma_f32_16x16x32_f16, fp32 accumulate
 void launch_front_h(hipStream_t st, int k1, const SiteRange& sr, const ReadDesc* reads, const uint8_t* bases,
                     const uint32_t* kin, const float* windows, const CtxWeights& w, float* act4, int grid, float* dbg,
-                    int dbg_layer, unsigned long long* stamps, bool w16);
+                    int dbg_layer, unsigned long long* stamps);
 void launch_tail_h(hipStream_t st, const float* act4, const SiteRange& sr, const CtxWeights& w, float* logits,
-                   float* p, uint8_t* ml, int grid, float* dbg, int dbg_layer, int w16_level);
+                   float* p, uint8_t* ml, int grid, float* dbg, int dbg_layer);
 // tail: conv5..conv8, fc1, fc2, softmax for 8 sites per workgroup pass.
 // results go to index sites[i].uidx (or i when sites == nullptr).
 void launch_tail(hipStream_t st, const float* act4, const SiteRange& sr, const CtxWeights& w, float* logits,
@@ -67,16 +67,15 @@ __device__ __forceinline__ int resolve_sites(const SiteRange& sr, const Site*& s
 // conv4 per site, then the tail gathers its conv4 rows from the maps
 void launch_trunk(hipStream_t st, int k1, const TrunkTile* tiles, int n_tiles, int n_views, int ctx, const RInfo* rinfo,
                   const uint8_t* bases, const uint32_t* kin, const uint8_t* sctx, const CtxWeights& w,
-                  const TrunkMaps& maps, int grid, bool w16);
+                  const TrunkMaps& maps, int grid);
 void launch_edge(hipStream_t st, int k1, const SiteRange& sr, const RInfo* rinfo, const uint8_t* bases,
-                 const uint32_t* kin, const CtxWeights& w, const TrunkMaps& maps, uint16_t* edge4, int32_t* e4row, int grid,
-                 bool w16);
+                 const uint32_t* kin, const CtxWeights& w, const TrunkMaps& maps, uint16_t* edge4, int32_t* e4row, int grid);
 // the same edge rows with taps read in place, zero taps skipped and map rows / weights streamed a layer ahead (hm_edge2.hip):
 // bit-identical results
 void launch_edge2(hipStream_t st, int k1, const SiteRange& sr, const RInfo* rinfo, const uint8_t* bases, const uint32_t* kin,
                   const CtxWeights& w, const TrunkMaps& maps, uint16_t* edge4, int32_t* e4row, int grid);
 void launch_tail_gather(hipStream_t st, const SiteRange& sr, const CtxWeights& w, const TrunkMaps& maps, const uint16_t* edge4,
-                        const int32_t* e4row, float* logits, float* p, uint8_t* ml, int grid, int w16_level);
+                        const int32_t* e4row, float* logits, float* p, uint8_t* ml, int grid);
 // the same tail with conv5..conv7's weights resident in registers (hm_tail_r.hip): bit-identical results
 void launch_tail_gather_r(hipStream_t st, const SiteRange& sr, const CtxWeights& w, const TrunkMaps& maps, const uint16_t* edge4,
                           const int32_t* e4row, float* logits, float* p, uint8_t* ml, int grid, bool w16 = false);   // w16: conv8 + fc1 with plain fp16 weights (precision 2)
@@ -103,7 +102,7 @@ void launch_tail_fc(hipStream_t st, const SiteRange& sr, const CtxWeights& w, co
                     uint8_t* ml, int grid, bool w16);
 void launch_trunk2(hipStream_t st, int k1, const TrunkTile* tiles, int n_tiles, int n_views, int ctx, const RInfo* rinfo,
                    const uint8_t* bases, const uint32_t* kin, const uint8_t* sctx, const CtxWeights& w,
-                   const TrunkMaps& maps, int grid, bool w16, bool waves8 = false);
+                   const TrunkMaps& maps, int grid, bool waves8 = false);
 // the trunk as a sliding window (hm_trunk3.hip): a workgroup walks consecutive tiles and keeps every layer's right-hand rows, so that
 // each layer computes 112 rows per tile instead of 144 / 144 / 128 / 112: byte-identical maps, 14 % fewer MFMAs.  `maps.rowlist` must
 // hold trunk3_rowlist_bytes(n_tiles * n_views) bytes, `dump` trunk3_dump_bytes(grid); every read's map region needs 32 rows of slack at its end.

@@ -96,7 +96,7 @@ struct EpiE4 {
 
 }  // namespace
 
-template <int K1, bool W16>
+template <int K1>
 __global__ __launch_bounds__(512) void trunk_kernel(const TrunkTile* __restrict__ tiles, int n_tiles, int n_views, int ctx,
                                                      const RInfo* __restrict__ rinfo, const uint8_t* __restrict__ bases,
                                                      const uint32_t* __restrict__ kin, const uint8_t* __restrict__ sctx,
@@ -154,16 +154,16 @@ __global__ __launch_bounds__(512) void trunk_kernel(const TrunkTile* __restrict_
     };
 
     // conv1: folded bn0, exact fp16 operand, weights' hi / lo halves stacked along K; dense: every position, taps 1 row apart
-    using C1 = ConvH<NW, 8, (2 * K1 + 3) / 4 * 4, 128, TR_M1, TR_WRS, 1, 8, 4, 1, 0, 0, true, false, false, K1, true, 0, 1, 1>;
+    using C1 = ConvH<NW, 8, (2 * K1 + 3) / 4 * 4, 128, TR_M1, TR_WRS, 1, 8, 4, 1, 0, 0, false, false, K1, true, 0, 1, 1>;
 #ifndef TRK_WM
 #define TRK_WM 1
 #define TRK_WN 8
 #define TRK_BR 3
 #define TRK_BR4 3
 #endif
-    using C2 = ConvH<NW, 128, 3, 128, TR_M2, TR_RS, TRK_WM, TRK_WN, TRK_BR, 1, 0, 0, !W16, true, false, 0, true, 1, 1, 2>;
-    using C3 = ConvH<NW, 128, 3, 128, TR_M3, TR_RS, TRK_WM, TRK_WN, TRK_BR, 1, 0, 0, !W16, true, false, 0, true, 1, 1, 4>;
-    using C4 = ConvH<NW, 128, 3, C4_CH, TR_M4, TR_RS, 1, 6, TRK_BR4, 1, 0, 0, !W16, true, false, 0, true, 1, 1, 8>;
+    using C2 = ConvH<NW, 128, 3, 128, TR_M2, TR_RS, TRK_WM, TRK_WN, TRK_BR, 1, 0, 0, true, false, 0, true, 1, 1, 2>;
+    using C3 = ConvH<NW, 128, 3, 128, TR_M3, TR_RS, TRK_WM, TRK_WN, TRK_BR, 1, 0, 0, true, false, 0, true, 1, 1, 4>;
+    using C4 = ConvH<NW, 128, 3, C4_CH, TR_M4, TR_RS, 1, 6, TRK_BR4, 1, 0, 0, true, false, 0, true, 1, 1, 8>;
     auto wf = [&](int i) { return reinterpret_cast<const half_t*>(W.wfrag_h[i]); };
 
     if ((int)blockIdx.x < n_work) build(blockIdx.x, threadIdx.x, NW * 64);
@@ -310,7 +310,7 @@ struct CopyRows {
 
 // NW = 4: one wave per SIMD, 32 channels per wave (the default).  NW = 8: two waves per SIMD, 16 channels per wave -- twice
 // the LDS operand reads, but two waves can issue MFMAs 14 % faster than one (tools/micro/mfma_rate.hip).
-template <int K1, bool W16, int NW>
+template <int K1, int NW>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW / 4, NW / 4)))
 void trunk2_kernel(const TrunkTile* __restrict__ tiles, int n_tiles, int n_views, int ctx, const RInfo* __restrict__ rinfo,
                    const uint8_t* __restrict__ bases, const uint32_t* __restrict__ kin, const uint8_t* __restrict__ sctx,
@@ -383,8 +383,8 @@ void trunk2_kernel(const TrunkTile* __restrict__ tiles, int n_tiles, int n_views
     };
 
     using C1 = SCfg<8, (2 * K1 + 3) / 4 * 4, TR_WRS, 1, true, false, K1, 2, NTW>;
-    using C2 = SCfg<128, 3, TR_RS, 2, !W16, true, 0, 1, NTW>;
-    using C3 = SCfg<128, 3, TR_RS, 4, !W16, true, 0, 1, NTW>;
+    using C2 = SCfg<128, 3, TR_RS, 2, true, true, 0, 1, NTW>;
+    using C3 = SCfg<128, 3, TR_RS, 4, true, true, 0, 1, NTW>;
     // conv4: 96 channels = 6 n-tiles x 7 position tiles = 42 tile pairs.  Four waves: a wave holds TWO n-tiles (a, b) -- 192
     // weight registers, like every other layer -- and runs the pair on one range of position tiles and a alone on the other,
     // b being shared by two waves that take complementary ranges: 11 + 10 + 11 + 10 tile pairs.  (Until round 3 three waves
@@ -392,8 +392,8 @@ void trunk2_kernel(const TrunkTile* __restrict__ tiles, int n_tiles, int n_views
     // x half the positions on four waves needs 288 weight registers and spills.)  The E3 copy slots ride in all four waves.
     // Eight waves (trunk_impl = 2): six of them one n-tile each, as before.
     constexpr bool SPLIT4 = NW == 4;
-    using C4 = SCfg<128, 3, TR_RS, 8, !W16, true, 0, 1, NTW>;
-    using C4s = SCfg<128, 3, TR_RS, 8, !W16, true, 0, 1, 1>;   // one of the wave's two resident n-tiles alone
+    using C4 = SCfg<128, 3, TR_RS, 8, true, true, 0, 1, NTW>;
+    using C4s = SCfg<128, 3, TR_RS, 8, true, true, 0, 1, 1>;   // one of the wave's two resident n-tiles alone
     using L4 = SConv<C4, C1, 0, 4, 3>;
     constexpr int NW4 = SPLIT4 ? NW : 6 / NTW;  // waves with channels in conv4
     // resident n-tiles nt04, nt04 + 1: waves 0 / 2 hold (a, b) = (0, 1) / (3, 4), waves 1 / 3 hold (b, a) = (1, 2) / (4, 5)
@@ -515,7 +515,7 @@ void trunk2_kernel(const TrunkTile* __restrict__ tiles, int n_tiles, int n_views
 //   of the dense map, or the zero padding.
 // ------------------------------------------------------------------------------------------------------------------------
 
-template <int K1, bool W16>
+template <int K1>
 __global__ __launch_bounds__(512) void edge_kernel(SiteRange sr, const RInfo* __restrict__ rinfo,
                                                     const uint8_t* __restrict__ bases, const uint32_t* __restrict__ kin,
                                                     CtxWeights W, TrunkMaps mp, uint16_t* __restrict__ edge4,
@@ -535,12 +535,12 @@ __global__ __launch_bounds__(512) void edge_kernel(SiteRange sr, const RInfo* __
     auto wf = [&](int i) { return reinterpret_cast<const half_t*>(W.wfrag_h[i]); };
 
     // one 3-tap layer over the staged operand rows [pseudo-row][tap][128]
-    using CE128 = ConvH<NW, 128, 3, 128, 1, TR_RS, 1, 8, 3, EG_M, 3 * TR_RS, 0, !W16, true, false, 0, false, 0, 1, 1>;
-    using CE96 = ConvH<NW, 128, 3, C4_CH, 1, TR_RS, 1, 6, 3, EG_M, 3 * TR_RS, 0, !W16, true, false, 0, false, 0, 1, 1>;
+    using CE128 = ConvH<NW, 128, 3, 128, 1, TR_RS, 1, 8, 3, EG_M, 3 * TR_RS, 0, true, false, 0, false, 0, 1, 1>;
+    using CE96 = ConvH<NW, 128, 3, C4_CH, 1, TR_RS, 1, 6, 3, EG_M, 3 * TR_RS, 0, true, false, 0, false, 0, 1, 1>;
     // all of conv1's weight blocks are requested in its prologue (ring depth = blocks + 1): the map rows can then be
     // requested right behind them, before the first MFMA, without standing in front of any later weight load
     constexpr int KB1E = (2 * K1 + 3) / 4 * 4 * 8 / 32;
-    using C1E = ConvH<NW, 8, (2 * K1 + 3) / 4 * 4, 128, 1, TR_WRS, 1, 8, KB1E + 1, EG_M, EG_XROWS * TR_WRS, 0, true, false, false, K1, false, 0, 1, 1>;
+    using C1E = ConvH<NW, 8, (2 * K1 + 3) / 4 * 4, 128, 1, TR_WRS, 1, 8, KB1E + 1, EG_M, EG_XROWS * TR_WRS, 0, false, false, K1, false, 0, 1, 1>;
 
     // Site descriptors + feature rows of the pass that starts at site s0, by threads [0, nt) (t < 0: not taking part).
     // A dependent chain of loads (site -> read -> base) followed by 1024 row builds: done for the NEXT pass by the two
@@ -758,39 +758,35 @@ __global__ __launch_bounds__(512) void edge_kernel(SiteRange sr, const RInfo* __
 // ------------------------------------------------------------------------------------------------------------------------
 void launch_trunk(hipStream_t st, int k1, const TrunkTile* tiles, int n_tiles, int n_views, int ctx, const RInfo* rinfo,
                   const uint8_t* bases, const uint32_t* kin, const uint8_t* sctx, const CtxWeights& w,
-                  const TrunkMaps& maps, int grid, bool w16) {
+                  const TrunkMaps& maps, int grid) {
     if (n_tiles <= 0) return;
     const dim3 g(min(n_tiles * n_views, grid)), b(512);
-#define HM_TRUNK(K1, W16) \
-    hipLaunchKernelGGL((trunk_kernel<K1, W16>), g, b, 0, st, tiles, n_tiles, n_views, ctx, rinfo, bases, kin, sctx, w, maps)
-    (void)w16;  // (plain-fp16-weight variants: closed in round 3, no longer instantiated)
-    if (k1 == 11) HM_TRUNK(11, false); else HM_TRUNK(13, false);
+#define HM_TRUNK(K1) \
+    hipLaunchKernelGGL((trunk_kernel<K1>), g, b, 0, st, tiles, n_tiles, n_views, ctx, rinfo, bases, kin, sctx, w, maps)
+    if (k1 == 11) HM_TRUNK(11); else HM_TRUNK(13);
 #undef HM_TRUNK
 }
 
 void launch_trunk2(hipStream_t st, int k1, const TrunkTile* tiles, int n_tiles, int n_views, int ctx, const RInfo* rinfo,
                    const uint8_t* bases, const uint32_t* kin, const uint8_t* sctx, const CtxWeights& w,
-                   const TrunkMaps& maps, int grid, bool w16, bool waves8) {
+                   const TrunkMaps& maps, int grid, bool waves8) {
     if (n_tiles <= 0) return;
     const dim3 g(min(n_tiles * n_views, grid)), b(waves8 ? 512 : 256);
     if (k1 == 11) hipLaunchKernelGGL(rowlist_kernel<11>, dim3(n_tiles * n_views), dim3(128), 0, st, tiles, n_tiles, ctx, rinfo, bases, sctx, maps.rowlist);
     else hipLaunchKernelGGL(rowlist_kernel<13>, dim3(n_tiles * n_views), dim3(128), 0, st, tiles, n_tiles, ctx, rinfo, bases, sctx, maps.rowlist);
-#define HM_TRUNK(K1, W16) \
-    do { if (waves8) hipLaunchKernelGGL((trunk2_kernel<K1, W16, 8>), g, b, 0, st, tiles, n_tiles, n_views, ctx, rinfo, bases, kin, sctx, w, maps); \
-         else hipLaunchKernelGGL((trunk2_kernel<K1, W16, 4>), g, b, 0, st, tiles, n_tiles, n_views, ctx, rinfo, bases, kin, sctx, w, maps); } while (0)
-    (void)w16;
-    if (k1 == 11) HM_TRUNK(11, false); else HM_TRUNK(13, false);
+#define HM_TRUNK(K1) \
+    do { if (waves8) hipLaunchKernelGGL((trunk2_kernel<K1, 8>), g, b, 0, st, tiles, n_tiles, n_views, ctx, rinfo, bases, kin, sctx, w, maps); \
+         else hipLaunchKernelGGL((trunk2_kernel<K1, 4>), g, b, 0, st, tiles, n_tiles, n_views, ctx, rinfo, bases, kin, sctx, w, maps); } while (0)
+    if (k1 == 11) HM_TRUNK(11); else HM_TRUNK(13);
 #undef HM_TRUNK
 }
 
 void launch_edge(hipStream_t st, int k1, const SiteRange& sr, const RInfo* rinfo, const uint8_t* bases,
-                 const uint32_t* kin, const CtxWeights& w, const TrunkMaps& maps, uint16_t* edge4, int32_t* e4row, int grid,
-                 bool w16) {
+                 const uint32_t* kin, const CtxWeights& w, const TrunkMaps& maps, uint16_t* edge4, int32_t* e4row, int grid) {
     if (sr.cap <= 0) return;
     const dim3 g(sr.totals ? grid : max(1, min((sr.cap + EG_S - 1) / EG_S, grid))), b(512);
-#define HM_EDGE(K1, W16) hipLaunchKernelGGL((edge_kernel<K1, W16>), g, b, 0, st, sr, rinfo, bases, kin, w, maps, edge4, e4row)
-    (void)w16;
-    if (k1 == 11) HM_EDGE(11, false); else HM_EDGE(13, false);
+#define HM_EDGE(K1) hipLaunchKernelGGL((edge_kernel<K1>), g, b, 0, st, sr, rinfo, bases, kin, w, maps, edge4, e4row)
+    if (k1 == 11) HM_EDGE(11); else HM_EDGE(13);
 #undef HM_EDGE
 }
 

@@ -584,16 +584,9 @@ void trunk3_kernel(const TrunkTile* __restrict__ tiles, int n_tiles, int n_views
         }
         // the step's count word.  conv2 and conv3 choose their copy-slot tier inside the stream (CopyRows3T); conv4's first call, which
         // fetches no weights, exists once per tier as a whole
-#ifdef HM_XP_T3_NOCOPY
-        struct Cp23 : CopyRows3<NW, 0> { int need; };
-#else
         using Cp23 = CopyRows3T<NW>;
-#endif
         const uint32_t cw = (uint32_t)__builtin_amdgcn_readfirstlane((int)rlist[buf][T3_RLW - 1]);
         auto with_slots = [&](const int need, auto&& f) __attribute__((always_inline)) {
-#ifdef HM_XP_T3_NOCOPY   // timing ablation (make nocopy): no E1 .. E3 row leaves the trunk -- wrong results
-            f(std::integral_constant<int, 0>{});
-#else
             auto pick = [&](auto self, auto i_) __attribute__((always_inline)) -> void {
                 constexpr int i = decltype(i_)::value;
                 if constexpr (i == T3_NT) f(std::integral_constant<int, T3_CS_ALL>{});
@@ -601,7 +594,6 @@ void trunk3_kernel(const TrunkTile* __restrict__ tiles, int n_tiles, int n_views
                 else self(self, std::integral_constant<int, i + 1>{});
             };
             pick(pick, std::integral_constant<int, 0>{});
-#endif
         };
         // E1's kept rows come back into plane A (conv4 of the previous step is through with its rows 0 .. 3)
         move_rows<T3_H1, NW * 64>(a_hi, a_lo, h1_hi, h1_lo, threadIdx.x);

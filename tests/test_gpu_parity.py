@@ -975,3 +975,19 @@ def test_engines_give_their_memory_back():
         lost.append(free0 - torch.cuda.mem_get_info(0)[0])
     print(f"free memory lost per round of 8 engines: {lost}, group_bytes {group_bytes}")
     assert group_bytes > 0 and min(lost) < group_bytes // 2, (lost, group_bytes)
+
+
+@pytest.mark.gpu
+def test_environment_does_not_reach_the_arithmetic(monkeypatch):
+    """The weight packer once read HM_XP_WLO_MASK_BITS (an experiment: the weights' lo halves rounded to fewer mantissa bits), so that a
+    variable in the environment changed every model's weights in a production run.  The hook is gone: an engine made with the variable
+    set gives the calls of an engine made without it, byte for byte, in all three contexts."""
+    from hifimeth_amd import MethylationCaller
+    reads = synth_reads(3, seed=7, median_len=2500, sigma=0.2, frac_wide=0.34, frac_short=0, frac_missing=0)
+    with MethylationCaller(device=0) as m:
+        want = m.call(reads).copy()
+    monkeypatch.setenv("HM_XP_WLO_MASK_BITS", "8")
+    with MethylationCaller(device=0) as m:
+        got = m.call(reads).copy()
+    assert len(want) > 1000 and {int(c) for c in np.unique(want["ctx"])} == {0, 1, 2}
+    assert got.tobytes() == want.tobytes()
