@@ -148,6 +148,10 @@ def lib():
         "hm_pileup_fetch_bedmethyl": (i64, [vp, i32, i64, i64, i64, vp, i64]),
         "hm_pileup_fetch_linkage": (i64, [vp, i64, vp, i64]),
         "hm_linkage_stats": (C.c_int, [vp, vp]),
+        "hm_pileup_fetch_readpos": (i64, [vp, i64, vp, i64]),
+        "hm_pileup_readpos_histograms": (i64, [vp, vp, i64]),
+        "hm_pileup_add_readpos": (C.c_int, [vp, vp, i64]),
+        "hm_readpos_stats": (C.c_int, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

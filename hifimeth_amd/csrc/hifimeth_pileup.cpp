@@ -31,6 +31,9 @@
 // -L bp (ours): also <prefix>.linkage.CpG.tsv, the within-read co-methylation by distance: per exact distance d <= bp the pairs of
 // calls d bases apart on one molecule by class -- both unmethylated, the two discordant orders, both methylated -- with their
 // concordance and phi coefficient (hm_pileup_fetch_linkage).
+// -P bp (ours): also <prefix>.readpos.tsv, methylation by position in the read: per context the calls 0 .. bp - 1 bases from the read's
+// 5' end, from its 3' end, and all others, with the percentage methylated and the mean ML byte (hm_pileup_fetch_readpos, DESIGN.md
+// section 10).  -I n5[:n3] (ours): the calls in the first n5 and the last n3 bases of a read are left out of every output.
 // -K (ours): the input is an aligned BAM that still carries the kinetics tags (pbmm2 keeps fi / fp / ri / rp): the reads are called
 // on the fly by the call engine and their calls go straight to the pileup engine (hm_pileup_submit_read_calls) -- the files
 // `call` followed by `pileup` writes, without the mod-BAM between the two.
@@ -120,6 +123,10 @@ struct PileupOptions {
     long long linkage = 0;             // -L: within-read co-methylation by distance up to this many bases -> <prefix>.linkage.CpG.tsv
     long long linkage_min_pairs = 1;   // -z: smallest number of pairs of a distance that is written
     bool linkage_option_given = false, linkage_option_bad = false;  // -z; -L or -z with a value out of range
+    long long profile = 0;             // -P: methylation by position in the read, the ends resolved up to this many bases -> <prefix>.readpos.tsv
+    long long profile_min_calls = 1;   // -y: smallest number of calls of a row that is written
+    long long trim5 = 0, trim3 = 0;    // -I: the calls in the first trim5 / last trim3 bases of a read are dropped
+    bool profile_option_given = false, profile_option_bad = false;  // -y; -P, -y or -I with a value out of range
     // -K: call on the fly; the options below are `call`'s (hifimeth_call.cpp), same meaning and defaults
     bool kinetics = false;
     bool call_option_given = false;  // any of -m -c -l -p -T: a usage error without -K
@@ -194,6 +201,13 @@ void pileup_usage(const char* exe) {
             "    n_uu, n_um, n_mu, n_mm, concordance (n_uu + n_mm) / n and the phi coefficient r (nan when a margin is empty).  The combined\n"
             "    reads are counted, with or without -H\n"
             "  -z <int>\n    With -L: smallest number of pairs of a distance that is written, >= 0 (0: every distance from 2 to bp)\n    Default: 1\n"
+            "  -P <bp>\n    Methylation by position in the read, bp in [1, 2048]: every call that is counted also counts by its offset p in the read as\n"
+            "    sequenced (L bases): in row 5' d = p or row 3' d = L - 1 - p when the nearer end is d < bp bases away (ties go to 5'), else in\n"
+            "    the row `interior`.  Writes <prefix>.readpos.tsv: a header line, then per context and row context, end, dist, n, n_m, n_u,\n"
+            "    percent methylated and the mean ML byte.  Calls within 200 bases of a read end saw a zero-padded kinetics window\n"
+            "  -y <int>\n    With -P: smallest n of a row that is written, >= 0 (0: every row)\n    Default: 1\n"
+            "  -I <n5>[:<n3>]\n    Leave the calls in the first n5 and the last n3 bases of every read (as sequenced) out of all outputs; one number\n"
+            "    sets both ends\n    Default: 0:0\n"
             "  -K\n    The input is an aligned BAM that carries the kinetics tags fi / fp / ri / rp instead of MM / ML: call 5mC on the\n"
             "    fly and pile the calls up directly.  For equal -c -l -p -T -q -f the output files are byte-identical to those of\n"
             "    `%s call` on that BAM followed by `%s pileup` on its output; no mod-BAM is written.  (Give -T explicitly\n"
@@ -991,6 +1005,43 @@ bool write_linkage(hm_pileup_t* pe, const PileupOptions& o) {
     return fclose(f) == 0;
 }
 
+// <prefix>.readpos.tsv: the header, then one row per context and bin with at least -y calls; percent as cov.bed's fourth column,
+// both statistics hm_readpos_stats' (a row without calls, written under -y 0, has none: nan).  false on an engine error (recorded)
+// or a file error (reported).
+bool write_readpos(hm_pileup_t* pe, const PileupOptions& o) {
+    std::vector<hm_readpos_t> rows(3 * (2 * (size_t)o.profile + 1));
+    const int64_t n = hm_pileup_fetch_readpos(pe, o.profile_min_calls, rows.data(), (int64_t)rows.size());
+    if (n < 0) return false;
+    const std::string path = o.prefix + ".readpos.tsv";
+    FILE* f = fopen(path.c_str(), "w");
+    if (!f) { fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str()); return false; }
+    static const char* const ctx[3] = {"CpG", "CHG", "CHH"};
+    static const char* const end[3] = {"5p", "3p", "interior"};
+    fprintf(f, "#context\tend\tdist\tn\tn_m\tn_u\tpercent\tmean_ml\n");
+    for (int64_t i = 0; i < n; ++i) {
+        const hm_readpos_t& r = rows[(size_t)i];
+        double st[2] = {NAN, NAN};
+        hm_readpos_stats(&r, st);
+        fprintf(f, "%s\t%s\t%u\t%llu\t%llu\t%llu\t%g\t%.6g\n", ctx[r.motif % 3], end[r.end % 3], r.dist, (unsigned long long)(r.n_m + r.n_u),
+                (unsigned long long)r.n_m, (unsigned long long)r.n_u, st[0], st[1]);
+    }
+    return fclose(f) == 0;
+}
+
+// -I: n5[:n3], integers >= 0, one number for both ends; false unless the whole text parses
+bool parse_trim(const char* text, long long& n5, long long& n3) {
+    char* end = nullptr;
+    errno = 0;
+    if (!isdigit((unsigned char)*text)) return false;
+    n5 = n3 = strtoll(text, &end, 10);
+    if (errno || n5 > INT_MAX) return false;
+    if (!*end) return true;
+    if (*end != ':' || !isdigit((unsigned char)end[1])) return false;
+    const char* second = end + 1;
+    n3 = strtoll(second, &end, 10);
+    return !errno && !*end && n3 <= INT_MAX;
+}
+
 // -u: one lo:hi pair for all contexts or three, each pair possibly nan; false unless the whole text parses
 bool parse_levels(const char* text, double lo[3], double hi[3]) {
     std::vector<std::string> items(1);
@@ -1439,6 +1490,17 @@ int cmd_pileup(int argc, char** argv) {
             else if (a == "-L") { if (x < 2 || x > 16384) o.linkage_option_bad = true; else o.linkage = x; }
             else { if (x < 0) o.linkage_option_bad = true; else o.linkage_min_pairs = x; }
         }
+        else if (a == "-P" || a == "-y") {  // the whole value must parse, and lie in the option's range
+            if (a == "-y") o.profile_option_given = true;
+            const char* v = argv[++i];
+            char* end = nullptr;
+            errno = 0;
+            const long long x = strtoll(v, &end, 10);
+            if (end == v || *end || errno) o.profile_option_bad = true;
+            else if (a == "-P") { if (x < 1 || x > 2048) o.profile_option_bad = true; else o.profile = x; }
+            else { if (x < 0) o.profile_option_bad = true; else o.profile_min_calls = x; }
+        }
+        else if (a == "-I") { if (!parse_trim(argv[++i], o.trim5, o.trim3)) o.profile_option_bad = true; }
         else if (a == "-v") {  // the whole value must parse
             o.bedmethyl_option_given = true;
             const char* v = argv[++i];
@@ -1508,6 +1570,9 @@ int cmd_pileup(int argc, char** argv) {
     const char* bad_linkage = o.linkage_option_bad ? "-L must be an integer in [2, 16384], -z an integer >= 0"
                               : o.linkage_option_given && !o.linkage ? "-z needs -L" : nullptr;
     if (bad_linkage) { fprintf(stderr, "ERROR: %s\n", bad_linkage); pileup_usage(argv[0]); return EXIT_FAILURE; }
+    const char* bad_profile = o.profile_option_bad ? "-P must be an integer in [1, 2048], -y an integer >= 0, -I n5[:n3] with integers >= 0"
+                              : o.profile_option_given && !o.profile ? "-y needs -P" : nullptr;
+    if (bad_profile) { fprintf(stderr, "ERROR: %s\n", bad_profile); pileup_usage(argv[0]); return EXIT_FAILURE; }
     const bool sites = !o.control.empty() || o.rates_given;
     if (o.kinetics && o.model_dir.empty()) o.model_dir = exe_dir() + "/../weights";
     o.ref = argv[i];
@@ -1545,6 +1610,10 @@ int cmd_pileup(int argc, char** argv) {
     if (o.linkage)
         fprintf(stderr, "linkage: pairs of CpG calls of one read up to %lld bases apart, distances with >= %lld pairs -> %s.linkage.CpG.tsv\n", o.linkage,
                 o.linkage_min_pairs, o.prefix.c_str());
+    if (o.profile)
+        fprintf(stderr, "readpos: calls by position in the read, %lld bases from either end resolved, rows with >= %lld calls -> %s.readpos.tsv\n", o.profile,
+                o.profile_min_calls, o.prefix.c_str());
+    if (o.trim5 || o.trim3) fprintf(stderr, "trim: calls in the first %lld and the last %lld bases of a read are left out\n", o.trim5, o.trim3);
     if (o.kinetics)
         fprintf(stderr, "kinetics: called on the fly (models %s, contexts%s%s%s, min read length %d, precision %d, trunk %s)\n", o.model_dir.c_str(),
                 o.ctx_mask & 1 ? " CpG" : "", o.ctx_mask & 2 ? " CHG" : "", o.ctx_mask & 4 ? " CHH" : "", o.min_read_size, o.precision,
@@ -1582,6 +1651,9 @@ int cmd_pileup(int argc, char** argv) {
         return die("patterns");
     if (o.bedmethyl && hm_pileup_set_option(pe, "bedmethyl", 1) != HM_OK) return die("bedmethyl");
     if (o.linkage && hm_pileup_set_option(pe, "linkage", (double)o.linkage) != HM_OK) return die("linkage");
+    if (o.profile && hm_pileup_set_option(pe, "profile", (double)o.profile) != HM_OK) return die("profile");
+    if ((o.trim5 || o.trim3) && (hm_pileup_set_option(pe, "trim5", (double)o.trim5) != HM_OK || hm_pileup_set_option(pe, "trim3", (double)o.trim3) != HM_OK))
+        return die("trim");
     if (fa.names.empty()) { fprintf(stderr, "ERROR: no sequence in %s\n", o.ref.c_str()); return EXIT_FAILURE; }
     if (hm_pileup_set_reference(pe, (int32_t)fa.names.size(), fa.length.data(), fa.bases.data()) != HM_OK) return die("reference");
 
@@ -1736,6 +1808,7 @@ int cmd_pileup(int argc, char** argv) {
         if (!ok) return die("bedmethyl");
     }
     if (o.linkage && !write_linkage(pe, o)) return die("linkage");
+    if (o.profile && !write_readpos(pe, o)) return die("readpos");
     if (sites) {
         const int rc = write_sites(pe, fa, o, control_sid, o.threads);
         if (rc < 0) return die("sites");

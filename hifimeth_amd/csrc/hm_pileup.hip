@@ -31,6 +31,9 @@
 //                   the later members of its record within max_dist and adds each pair to three 256-bin histograms per distance;
 //                   linkage_reduce_kernel, workgroup per distance, turns them into UU / UM / MU / MM once the threshold is known;
 //                   LinkSel the rows
+//   project_kernel<true>  (`pileup -P`) the projection that also adds every record it emits to the read-position table, by its
+//                   offset in the read: rows within D of a read end by global atomics, the interior rows through LDS;
+//                   readpos_reduce_kernel, workgroup per row, sums a row under the thresholds; ReadPosSel the rows
 //   select_count / loci_scan / select_write   the rows of a SELECTION over a range in ascending order (count per block, scan,
 //                   write); every output below is a selection struct (its planes, pred, take) plus per-row kernels
 //   LociSel         covered loci
@@ -163,8 +166,14 @@ __device__ __forceinline__ bool isD(char c) { return c == 'A' || c == 'G' || c =
 // One entry of a read (an MM/ML entry, or a call): a 5mC entry writes the per-base plane word project_kernel reads
 // (bit 0x100 + ML byte; `rank` above them orders the entries of one position: the largest wins); an entry on C / G of a
 // primary record counts in the workgroup's context histogram h[3][256], the context taken from the read's own bases.
-__device__ __forceinline__ void mod_entry(const PRead& r, int q, uint32_t prob, uint32_t rank, bool is_m, bool cg,
+// `pileup -I` (Trim): an entry in the first n5 or the last n3 bases of the read as sequenced does neither -- for every kernel
+// behind this one the read has no entry there.  0:0 drops nothing.
+struct Trim {
+    int32_t n5, n3;
+};
+__device__ __forceinline__ void mod_entry(const PRead& r, int q, uint32_t prob, uint32_t rank, bool is_m, bool cg, Trim trim,
                                           const uint8_t* __restrict__ slab, uint32_t* __restrict__ plane, uint32_t* h) {
+    if (q < trim.n5 || q > r.l_qseq - 1 - trim.n3) return;
     if (is_m)  // code 'm': read_mods[qoff] = prob, later entries overwrite earlier ones
         atomicMax(&plane[r.plane_off + q], (rank << 9) | 0x100u | prob);
     if (r.primary && cg) {
@@ -198,12 +207,12 @@ __device__ __forceinline__ void hist_flush(const uint32_t* h, int n, unsigned lo
 template <class Entry>  // PMod or PCall
 __global__ __launch_bounds__(TPB) void entries_kernel(const Entry* __restrict__ entries, int64_t n, const PRead* __restrict__ reads,
                                                        const uint8_t* __restrict__ slab, uint32_t* __restrict__ plane,
-                                                       unsigned long long* __restrict__ bins) {
+                                                       unsigned long long* __restrict__ bins, Trim trim) {
     __shared__ uint32_t h[3 * 256];
     hist_zero(h, 768);
     for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
         const Entry e = entries[i];
-        mod_entry(reads[e.read], e.qoff, e.ml(), e.rank(), e.is_m(), e.on_cg(), slab, plane, h);
+        mod_entry(reads[e.read], e.qoff, e.ml(), e.rank(), e.is_m(), e.on_cg(), trim, slab, plane, h);
     }
     hist_flush(h, 768, bins);
 }
@@ -325,14 +334,38 @@ __device__ __forceinline__ int cpg_member(const BatchView& b, const PRead& rd, c
     return cpg_columns(b, rd, run, off) ? cpg_call(b, rd, run.q0 + off) : -1;
 }
 
+// ---- methylation by position in the read (`pileup -P`; include/hifimeth_hip.h has the definition) ---------------------------
+// hist[(motif * (2 D + 1) + bin) * 256 + ML byte], uint64: bin d5 < D the 5' rows, D + d3 the 3' rows, 2 D the interior row --
+// the order in which a fetch returns them.  Threshold-free, as the linkage histograms are; integer atomics only.
+constexpr int READPOS_MAX = 2048;
+struct ReadPos {
+    unsigned long long* hist;
+    int D;
+    __host__ __device__ int rows() const { return 2 * D + 1; }
+};
+// One projected record whose 5mC entry sits at plane index p of a read of L bases.  About 1 - 2 D / L of all records are
+// interior: those go to the workgroup's h[3][256] in LDS; an end row is one of 2 D x 256 addresses per context, a global atomic.
+__device__ __forceinline__ void readpos_add(const ReadPos& rp, uint32_t* h, const PRec& r, int p, int L) {
+    const int d5 = p, d3 = L - 1 - p;
+    if (min(d5, d3) >= rp.D) atomicAdd(&h[r.motif() * 256u + r.prob()], 1u);
+    else atomicAdd(&rp.hist[((size_t)r.motif() * rp.rows() + (d5 <= d3 ? d5 : rp.D + d3)) * 256 + r.prob()], 1ull);
+}
+
 // ---- projection (pileup.cpp:286-347, 5mc_motif_finder.cpp:104-144) -----------------------------------------
-__global__ __launch_bounds__(TPB) void project_kernel(BatchView b, PRec* __restrict__ out, unsigned long long* __restrict__ counter) {
+// PROFILE (`pileup -P`): every record also counts in the read-position table, at the plane index its 5mC entry was found at.
+template <bool PROFILE>
+__global__ __launch_bounds__(TPB) void project_kernel(BatchView b, PRec* __restrict__ out, unsigned long long* __restrict__ counter,
+                                                       ReadPos rp) {
     __shared__ PRec stage[2 * PTILE];  // a column yields at most two records (CpG + the reverse-strand CGG of CHG)
     __shared__ int n_stage;
+    __shared__ uint32_t interior[PROFILE ? 3 * 256 : 1];
     if (threadIdx.x == 0) n_stage = 0;
+    if constexpr (PROFILE)
+        for (int i = threadIdx.x; i < 3 * 256; i += TPB) interior[i] = 0u;
     walk_columns(b, [&](int, const PRun& run, int o, bool in_range) {
         bool e0 = false, e1 = false;
         PRec r0{}, r1{};
+        [[maybe_unused]] int p0 = 0, p1 = 0, len = 0;  // PROFILE: the plane indices of r0 and r1, the read's length
         const int rem = run.len - o;
         if (in_range && rem >= 2) {
             const PRead rd = b.reads[run.read];
@@ -349,13 +382,16 @@ __global__ __launch_bounds__(TPB) void project_kernel(BatchView b, PRec* __restr
                     if (v & 0x100u) {
                         e1 = true;
                         r1 = PRec::make(soff, v & 255u, motif, rd.hp, rd.order);
+                        if constexpr (PROFILE) p1 = qoff;
                     }
                 };
+                if constexpr (PROFILE) len = L;
                 if (cpg_columns(q0, q1, s0, s1)) {  // CpG, recorded at the reference C
                     const int p = cpg_call(b, rd, qp);
                     if (p >= 0) {
                         e0 = true;
                         r0 = PRec::make(g, (uint32_t)p, 0, rd.hp, rd.order);
+                        if constexpr (PROFILE) p0 = rd.rev ? L - 1 - (qp + 1) : qp;  // cpg_call's index
                     }
                 }
                 if (eq3 && q0 == 'C' && q2 == 'G') {  // CHG: forward reads CCG/CAG/CTG, reverse reads CGG/CAG/CTG
@@ -370,8 +406,15 @@ __global__ __launch_bounds__(TPB) void project_kernel(BatchView b, PRec* __restr
         }
         stage_record(e0, r0, stage, &n_stage);
         stage_record(e1, r1, stage, &n_stage);
+        if constexpr (PROFILE) {
+            if (e0) readpos_add(rp, interior, r0, p0, len);
+            if (e1) readpos_add(rp, interior, r1, p1, len);
+        }
     });
     flush_stage(stage, &n_stage, out, counter);
+    if constexpr (PROFILE)  // behind flush_stage's barriers: one atomic per non-empty bin, as hist_flush
+        for (int i = threadIdx.x; i < 3 * 256; i += TPB)
+            if (interior[i]) atomicAdd(&rp.hist[((size_t)(i >> 8) * rp.rows() + 2 * rp.D) * 256 + (i & 255)], (unsigned long long)interior[i]);
 }
 
 // ---- counting (pileup.cpp:529-557) -------------------------------------------------------------------------
@@ -881,6 +924,49 @@ struct LinkSel {
         return true;
     }
 };
+
+// ---- the rows of the read-position table (`pileup -P`) -----------------------------------------------------------------------
+// One workgroup per histogram row (motif, bin), thread v holds bin v: with t the motif's threshold, n_m = sum_{v >= t} h[v]
+// (count_kernel's >=), n_u = sum_{v < t} h[v], sum_ml = sum v h[v] -> tab[row * 3 + (n_m, n_u, sum_ml)]
+__global__ __launch_bounds__(256) void readpos_reduce_kernel(ReadPos rp, uint32_t thr_packed, unsigned long long* __restrict__ tab) {
+    __shared__ unsigned long long part[256 / 64][3];
+    const uint32_t thr = (thr_packed >> (8 * (blockIdx.x / (unsigned)rp.rows()))) & 255u;
+    const uint32_t v = threadIdx.x;
+    const unsigned long long h = rp.hist[(size_t)blockIdx.x * 256 + v];
+    unsigned long long s[3] = {v >= thr ? h : 0ull, v < thr ? h : 0ull, h * v};
+    for (int c = 0; c < 3; ++c) {
+        for (int d = 32; d; d >>= 1) s[c] += __shfl_down(s[c], d);
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][c] = s[c];
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) tab[(size_t)blockIdx.x * 3 + threadIdx.x] = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+}
+
+// the rows over the table's ROW indices, which are in output order: n_m + n_u >= min_calls
+struct ReadPosSel {
+    using Row = hm_readpos_t;
+    const unsigned long long* tab;
+    int D;
+    int64_t min_calls;
+    __device__ bool pred(int64_t i) const { return tab[i * 3] + tab[i * 3 + 1] >= (unsigned long long)min_calls; }
+    __device__ bool take(int64_t i, Row& w) const {
+        if (!pred(i)) return false;
+        const int bin = (int)(i % (2 * D + 1));
+        w.motif = (uint32_t)(i / (2 * D + 1));
+        w.end = bin < D ? 0u : bin < 2 * D ? 1u : 2u;
+        w.dist = bin < D ? (uint32_t)bin : bin < 2 * D ? (uint32_t)(bin - D) : 0u;
+        w.reserved = 0;
+        w.n_m = tab[i * 3];
+        w.n_u = tab[i * 3 + 1];
+        w.sum_ml = tab[i * 3 + 2];
+        return true;
+    }
+};
+
+// hm_pileup_add_readpos: counts from elsewhere, counter by counter
+__global__ __launch_bounds__(TPB) void readpos_add_kernel(const unsigned long long* __restrict__ add, int64_t n, unsigned long long* __restrict__ hist) {
+    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) hist[i] += add[i];
+}
 
 // ---- allele-specific methylation: loci tested between the two haplotype partitions -----------------
 // A locus is tested when each haplotype has pcov + ncov >= min_cov.  The planes may be the caller's: counters that are not
@@ -1676,7 +1762,14 @@ struct hm_pileup {
     int linkage = 0;
     DevBuf d_lhist{EXACT}, d_ltab{EXACT}, d_members{HALF};
     uint32_t linkage_thr = 0;  // thr[CpG] of the last hm_pileup_count
-    bool counted = false;      // hm_pileup_count has run since hm_pileup_set_reference: what the -E, -M and -L fetches wait for
+    // `pileup -P` ("profile" = D), all of it only with the option on: 3 x (2 D + 1) histogram rows of 256 uint64 (12.6 MB at
+    // D = 1024, 25.2 MB at the cap), resident from hm_pileup_set_reference on; the three sums per row of a fetch; what
+    // hm_pileup_add_readpos uploads.  `pileup -I` ("trim5", "trim3") travels with entries_kernel's arguments.
+    int profile = 0;
+    Trim trim{0, 0};
+    DevBuf d_rphist{EXACT}, d_rptab{EXACT}, d_rpadd{EXACT};
+    uint32_t thr_packed = 0;   // the three thresholds of the last hm_pileup_count
+    bool counted = false;     // hm_pileup_count has run since hm_pileup_set_reference: what the -E, -M and -L fetches wait for
     int64_t n_recs = 0;
     bool bins_ready = false;
 
@@ -1960,6 +2053,10 @@ int count_linkage_pairs(hm_pileup* p, const BatchView& batch) {
     return HM_OK;
 }
 
+// the read-position table as the kernels see it, and its number of uint64 counters
+ReadPos readpos_table(const hm_pileup* p) { return ReadPos{p->d_rphist.as<unsigned long long>(), p->profile}; }
+size_t readpos_counters(const hm_pileup* p) { return (size_t)3 * (2 * (size_t)p->profile + 1) * 256; }
+
 void clear_batch(hm_pileup* p) {
     p->slab.clear();
     p->reads.clear();
@@ -2115,7 +2212,7 @@ int hm_pileup_set_option(hm_pileup_t* p, const char* key, double value) {
     // what is sized or listed when the reference arrives (the partition planes, the reference CpGs and their counters, the
     // linkage histograms) is decided before that; the planes also before the caller hands in planes of their own
     const bool partitions = k == "partitions";
-    if (partitions || k == "patterns" || k == "pattern_span" || k == "bedmethyl" || k == "linkage") {
+    if (partitions || k == "patterns" || k == "pattern_span" || k == "bedmethyl" || k == "linkage" || k == "profile" || k == "trim5" || k == "trim3") {
         if (!p->seq_off.empty() || (partitions && !p->own_planes))
             return pfail(p, HM_ESTATE, k + " must be set before hm_pileup_set_reference" + (partitions ? " / hm_pileup_use_planes" : ""));
     }
@@ -2138,6 +2235,14 @@ int hm_pileup_set_option(hm_pileup_t* p, const char* key, double value) {
         if (value != 0.0 && (!(value >= 2.0 && value <= (double)LINK_MAX_DIST) || value != std::floor(value)))
             return pfail(p, HM_EINVAL, "linkage must be 0 or an integer in 2 .. 16384");
         p->linkage = (int)value;
+    } else if (k == "profile") {  // the read-position table is sized when the reference arrives
+        if (value != 0.0 && (!(value >= 1.0 && value <= (double)READPOS_MAX) || value != std::floor(value)))
+            return pfail(p, HM_EINVAL, "profile must be 0 or an integer in 1 .. 2048");
+        p->profile = (int)value;
+    } else if (k == "trim5" || k == "trim3") {  // reads are shorter than 2^22 bases: a larger value drops no more
+        if (!(value >= 0.0 && value <= (double)INT32_MAX) || value != std::floor(value))
+            return pfail(p, HM_EINVAL, k + " must be an integer >= 0");
+        (k == "trim5" ? p->trim.n5 : p->trim.n3) = (int32_t)std::min(value, (double)(1 << 22));
     } else return pfail(p, HM_EINVAL, "unknown option " + k);
     return HM_OK;
 }
@@ -2213,6 +2318,11 @@ int hm_pileup_set_reference(hm_pileup_t* p, int32_t n_seqs, const int64_t* seq_l
             const size_t bytes = sizeof(unsigned long long) * LH_HISTS * 256 * ((size_t)p->linkage + 1);
             p->d_lhist.reserve(bytes);
             HIP_TRY(hipMemsetAsync(p->d_lhist.p, 0, bytes, p->stream));
+        }
+        if (p->profile) {
+            const size_t bytes = sizeof(unsigned long long) * readpos_counters(p);
+            p->d_rphist.reserve(bytes);
+            HIP_TRY(hipMemsetAsync(p->d_rphist.p, 0, bytes, p->stream));
         }
         HIP_TRY(hipStreamSynchronize(p->stream));
         return HM_OK;
@@ -2336,19 +2446,23 @@ int hm_pileup_run(hm_pileup_t* p) {
         if (n_mods)  // <= 1024 workgroups: each flushes up to 768 histogram bins with same-address global atomics (~10 ns each)
             hipLaunchKernelGGL(entries_kernel<PMod>, dim3(grid_for(n_mods, 1024)), dim3(TPB), 0, st, p->d_mods.as<PMod>(), n_mods,
                                p->d_reads.as<PRead>(), p->d_slab.as<uint8_t>(), p->d_plane.as<uint32_t>(),
-                               p->d_bins.as<unsigned long long>());
+                               p->d_bins.as<unsigned long long>(), p->trim);
         if (n_calls)  // the records submitted with calls: their plane words and histogram counts, same grid rule
             hipLaunchKernelGGL(entries_kernel<PCall>, dim3(grid_for(n_calls, 1024)), dim3(TPB), 0, st, p->d_calls.as<PCall>(), n_calls,
                                p->d_reads.as<PRead>(), p->d_slab.as<uint8_t>(), p->d_plane.as<uint32_t>(),
-                               p->d_bins.as<unsigned long long>());
+                               p->d_bins.as<unsigned long long>(), p->trim);
         const BatchView batch = batch_view(p, n_runs, cols);
         if (cols > 0) {
             const int64_t blocks = (cols + TPB - 1) / TPB, pblocks = (cols + PTILE - 1) / PTILE;
             if (blocks >= (int64_t(1) << 31)) return pfail(p, HM_EINVAL, "batch too large: submit fewer records per hm_pileup_run");
             if (p->min_pi > 0.0)
                 hipLaunchKernelGGL(identity_kernel, dim3((unsigned)blocks), dim3(TPB), 0, st, batch, p->d_matches.as<int32_t>());
-            hipLaunchKernelGGL(project_kernel, dim3((unsigned)pblocks), dim3(TPB), 0, st, batch, p->d_recs.as<PRec>(),
-                               p->d_counter.as<unsigned long long>());
+            if (p->profile)
+                hipLaunchKernelGGL(project_kernel<true>, dim3((unsigned)pblocks), dim3(TPB), 0, st, batch, p->d_recs.as<PRec>(),
+                                   p->d_counter.as<unsigned long long>(), readpos_table(p));
+            else
+                hipLaunchKernelGGL(project_kernel<false>, dim3((unsigned)pblocks), dim3(TPB), 0, st, batch, p->d_recs.as<PRec>(),
+                                   p->d_counter.as<unsigned long long>(), ReadPos{nullptr, 0});
             if (p->patterns && p->n_cpg)
                 hipLaunchKernelGGL(pattern_kernel, dim3((unsigned)pblocks), dim3(TPB), 0, st, batch, pattern_rule(p), p->d_precs.as<PWin>(),
                                    p->d_pcounter.as<unsigned long long>());
@@ -2432,8 +2546,8 @@ int hm_pileup_count(hm_pileup_t* p, const uint8_t thr[3]) {
         return pfail(p, HM_ESTATE, "hm_pileup_count without partition planes (hm_pileup_set_reference / hm_pileup_use_partition_planes)");
     return guarded(p, [&] {
         ensure_bins(p);
+        const uint32_t packed = thr[0] | ((uint32_t)thr[1] << 8) | ((uint32_t)thr[2] << 16);
         if (p->n_recs) {
-            const uint32_t packed = thr[0] | ((uint32_t)thr[1] << 8) | ((uint32_t)thr[2] << 16);
             const CountPlanes own{p->pcov, p->ncov, p->key};
             if (p->partitions == 2)
                 hipLaunchKernelGGL(count_kernel<CountHpPlanes>, dim3(grid_for(p->n_recs, 1 << 16)), dim3(TPB), 0, p->stream,
@@ -2461,6 +2575,7 @@ int hm_pileup_count(hm_pileup_t* p, const uint8_t thr[3]) {
         p->n_precs = 0;
         p->counted = true;
         p->linkage_thr = thr[0];
+        p->thr_packed = packed;
         return HM_OK;
     });
 }
@@ -2523,6 +2638,61 @@ int64_t hm_pileup_fetch_linkage(hm_pileup_t* p, int64_t min_pairs, hm_linkage_t*
     });
     if (rc != HM_OK) return rc;
     return compact_rows(p, LinkSel{p->d_ltab.as<unsigned long long>(), min_pairs}, 2, (int64_t)p->linkage + 1, out, cap, no_hook, no_hook);
+}
+
+// ---- `pileup -P` ------------------------------------------------------------------------------------------------------------------
+int64_t hm_pileup_fetch_readpos(hm_pileup_t* p, int64_t min_calls, hm_readpos_t* out, int64_t cap) {
+    if (!p) return HM_EINVAL;
+    if (!p->profile || p->seq_off.empty()) return pfail(p, HM_ESTATE, "hm_pileup_fetch_readpos without option profile (then hm_pileup_set_reference)");
+    if (!p->counted) return pfail(p, HM_ESTATE, "hm_pileup_fetch_readpos before hm_pileup_count");
+    if (min_calls < 0) return pfail(p, HM_EINVAL, "hm_pileup_fetch_readpos: min_calls must be >= 0");
+    const int64_t n_rows = 3 * (2 * (int64_t)p->profile + 1);
+    const int rc = guarded(p, [&] {
+        p->d_rptab.reserve(sizeof(unsigned long long) * 3 * (size_t)n_rows);
+        hipLaunchKernelGGL(readpos_reduce_kernel, dim3((unsigned)n_rows), dim3(256), 0, p->stream, readpos_table(p), p->thr_packed,
+                           p->d_rptab.as<unsigned long long>());
+        HIP_TRY(hipGetLastError());
+        return HM_OK;
+    });
+    if (rc != HM_OK) return rc;
+    return compact_rows(p, ReadPosSel{p->d_rptab.as<unsigned long long>(), p->profile, min_calls}, 0, n_rows, out, cap, no_hook, no_hook);
+}
+
+int64_t hm_pileup_readpos_histograms(hm_pileup_t* p, uint64_t* hist, int64_t cap) {
+    if (!p) return HM_EINVAL;
+    if (!p->profile || p->seq_off.empty()) return pfail(p, HM_ESTATE, "hm_pileup_readpos_histograms without option profile (then hm_pileup_set_reference)");
+    const int64_t n = (int64_t)readpos_counters(p);
+    if (!hist || cap < n) return n;
+    const int rc = guarded(p, [&] {
+        HIP_TRY(hipMemcpyAsync(hist, p->d_rphist.p, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        return HM_OK;
+    });
+    return rc != HM_OK ? rc : n;
+}
+
+int hm_pileup_add_readpos(hm_pileup_t* p, const uint64_t* hist, int64_t n) {
+    if (!p || !hist) return HM_EINVAL;
+    if (!p->profile || p->seq_off.empty()) return pfail(p, HM_ESTATE, "hm_pileup_add_readpos without option profile (then hm_pileup_set_reference)");
+    if (n != (int64_t)readpos_counters(p)) return pfail(p, HM_EINVAL, "hm_pileup_add_readpos: 3 x (2 x profile + 1) x 256 counters expected");
+    return guarded(p, [&] {
+        p->d_rpadd.reserve(sizeof(uint64_t) * (size_t)n);
+        HIP_TRY(hipMemcpyAsync(p->d_rpadd.p, hist, sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, p->stream));
+        hipLaunchKernelGGL(readpos_add_kernel, dim3(grid_for(n, 1024)), dim3(TPB), 0, p->stream, p->d_rpadd.as<unsigned long long>(), n,
+                           p->d_rphist.as<unsigned long long>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        return HM_OK;
+    });
+}
+
+int hm_readpos_stats(const hm_readpos_t* w, double out[2]) {
+    if (!w || !out) return HM_EINVAL;
+    const uint64_t n = w->n_m + w->n_u;
+    if (!n) return HM_EINVAL;
+    out[0] = 100.0 * (double)w->n_m / (double)n;  // cov.bed's fourth column
+    out[1] = (double)w->sum_ml / (double)n;
+    return HM_OK;
 }
 
 int hm_linkage_stats(const hm_linkage_t* w, double out[2]) {

@@ -69,6 +69,14 @@ per distance) and classes them by the CpG threshold of the last count().  `pu.li
 min_pairs pairs (LINKAGE_DTYPE), `linkage_stats(row)` -- host only, the C library's -- their concordance and phi coefficient,
 `pu.linkage_tsv(rows)` the text of <prefix>.linkage.CpG.tsv.
 
+Methylation by position in the read (`pileup -P bp`, `profile=bp`) and end trimming (`pileup -I n5:n3`, `trim=(n5, n3)`): every
+call the CNN makes within 200 bases of a read end saw a zero-padded kinetics window.  With profile=D every counted call also counts
+by its offset p in the read as sequenced (L bases): in row (5', p) or (3', L - 1 - p) when the nearer end is fewer than D bases
+away (ties to 5'), else in the row `interior` -- threshold-free histograms of the ML byte on the device, classed by the thresholds
+of the last count().  `pu.readpos(min_calls)` are the rows with at least min_calls calls (READPOS_DTYPE), `readpos_stats(row)` --
+host only, the C library's -- percent methylated and mean ML byte, `readpos_tsv(rows)` the text of <prefix>.readpos.tsv.  With
+trim=(n5, n3) the engine drops the entries in the first n5 and the last n3 bases of every read before anything sees them.
+
 Fused with the caller (`pileup -K`): `pu.add_called(read, calls)` takes the records `MethylationCaller` returned for an aligned read
 instead of parsed MM / ML -- the same effect as add() of that read carrying the calls as tags, without the tag text.
 
@@ -110,6 +118,10 @@ BEDMETHYL_DTYPE = np.dtype([("gpos", "<i8"), ("n_mod", "<u4"), ("n_canon", "<u4"
 LINKAGE_DTYPE = np.dtype([("dist", "<u4"), ("reserved", "<u4"), ("n_uu", "<u8"), ("n_um", "<u8"), ("n_mu", "<u8"),
                           ("n_mm", "<u8")])                                          # hm_linkage_t, 40 bytes
 LINKAGE_MAX_DIST = 16384                                 # the largest `pileup -L`
+READPOS_DTYPE = np.dtype([("motif", "<u4"), ("end", "<u4"), ("dist", "<u4"), ("reserved", "<u4"), ("n_m", "<u8"), ("n_u", "<u8"),
+                          ("sum_ml", "<u8")])                                        # hm_readpos_t, 40 bytes
+READPOS_MAX = 2048                                       # the largest `pileup -P`
+READPOS_ENDS = ("5p", "3p", "interior")                  # hm_readpos_t.end 0, 1, 2 as <prefix>.readpos.tsv names them
 PATTERN_SPAN, PATTERN_MIN_READS = 150, 10                # `pileup -E`'s default -w and -o
 DOMAIN_AFTER_BREAK, DOMAIN_BEFORE_BREAK = 1, 2                                        # HM_DOMAIN_AFTER_BREAK, HM_DOMAIN_BEFORE_BREAK
 DOMAIN_PASS_SUMMARY, DOMAIN_PASS_CODES, DOMAIN_PASS_SEGMENTS, DOMAIN_KEEP = 0, 1, 2, 2   # HM_DOMAIN_PASS_*, HM_DOMAIN_KEEP
@@ -512,6 +524,27 @@ def linkage_tsv(rows: np.ndarray) -> str:
     return "".join(text)
 
 
+def readpos_stats(row) -> Tuple[float, float]:
+    """one READPOS_DTYPE row -> (percent methylated, mean ML byte) by the C library (host only: no GPU is needed)"""
+    w = np.array(row, READPOS_DTYPE).reshape(1)
+    out = np.zeros(2, np.float64)
+    if lib().hm_readpos_stats(w.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)) != 0:
+        raise HifimethError("hm_readpos_stats: n = n_m + n_u > 0 expected")
+    return tuple(float(x) for x in out)
+
+
+def readpos_tsv(rows: np.ndarray) -> str:
+    """the text of <prefix>.readpos.tsv: the header, then context, end, dist, n, n_m, n_u, percent, mean_ml per row (a row without
+    calls has no statistics: nan)"""
+    text = ["#context\tend\tdist\tn\tn_m\tn_u\tpercent\tmean_ml\n"]
+    for r in rows:
+        n_m, n_u = int(r["n_m"]), int(r["n_u"])
+        st = readpos_stats(r) if n_m + n_u else (float("nan"), float("nan"))
+        text.append("%s\t%s\t%d\t%d\t%d\t%d\t%g\t%.6g\n" % (CTX_NAMES[int(r["motif"])], READPOS_ENDS[int(r["end"])], int(r["dist"]), n_m + n_u,
+                                                           n_m, n_u, *st))
+    return "".join(text)
+
+
 def sites_rates_tsv(sums, rates, m) -> str:
     """the text of <prefix>.sites.rates.tsv: ctx, P_c, N_c, rate, m_c (the counts are 0 when the rates were given with -e)"""
     return "".join("%s\t%d\t%d\t%s\t%d\n" % (CTX_NAMES[c], int(sums[c]), int(sums[3 + c]),
@@ -531,7 +564,8 @@ def locate(offsets, gpos) -> Tuple[np.ndarray, np.ndarray]:
 class MethylationPileup:
     def __init__(self, genome: Sequence[Tuple[str, str]], device: int = 0, min_mapq: int = 0, min_pi: float = 0.0,
                  planes=None, partitions: bool = False, partition_planes=None, bases=None, patterns: int = 0,
-                 pattern_span: int = PATTERN_SPAN, bedmethyl: bool = False, linkage: int = 0):
+                 pattern_span: int = PATTERN_SPAN, bedmethyl: bool = False, linkage: int = 0, profile: int = 0,
+                 trim: Tuple[int, int] = (0, 0)):
         """genome: [(name, SEQUENCE)].  bases: optional, the concatenated upper-case bases of the whole reference as a
         C-contiguous uint8 buffer (ndarray, bytes, memoryview), handed to the engine as it is -- for references of gigabases,
         where joining, upper-casing and encoding strings would copy them three times; the second member of each genome entry
@@ -544,7 +578,10 @@ class MethylationPileup:
         and last locus are at most pattern_span (1 .. 65 536) bases apart (+72 B per reference CpG, 8 B per window record).
         bedmethyl: also count the depth classes per reference CpG (+28 B per reference CpG, +68 B with partitions).
         linkage: 0, or max_dist in 2 .. 16 384: also count the pairs of CpG calls of one record by their distance up to max_dist
-        (+6 144 B per distance, whatever the depth)."""
+        (+6 144 B per distance, whatever the depth).
+        profile: 0, or D in 1 .. 2 048: also count every projected call by its position in the read, the D bases at either end one
+        row each (+3 x (2 D + 1) x 2 048 B: 12.6 MB at 1 024).
+        trim: (n5, n3): the entries in the first n5 and the last n3 bases of every read are dropped."""
         self._L = lib()
         self._h = C.c_void_p()
         if self._L.hm_pileup_create(C.byref(self._h), device) != 0:
@@ -572,6 +609,12 @@ class MethylationPileup:
         self.linkage_max_dist = int(linkage)
         if linkage:
             self._check(self._L.hm_pileup_set_option(self._h, b"linkage", float(linkage)))
+        self.profile = int(profile)
+        if profile:
+            self._check(self._L.hm_pileup_set_option(self._h, b"profile", float(profile)))
+        if tuple(trim) != (0, 0):
+            self._check(self._L.hm_pileup_set_option(self._h, b"trim5", float(trim[0])))
+            self._check(self._L.hm_pileup_set_option(self._h, b"trim3", float(trim[1])))
         if planes is not None:
             self._check(self._L.hm_pileup_use_planes(self._h, *(C.c_void_p(t.data_ptr()) for t in planes)))
         if bases is None:
@@ -856,6 +899,23 @@ class MethylationPileup:
     def linkage_tsv(self, rows: np.ndarray) -> str:
         """the text of <prefix>.linkage.CpG.tsv"""
         return linkage_tsv(rows)
+
+    def readpos(self, min_calls: int = 1) -> np.ndarray:
+        """the rows of the read-position table with at least min_calls calls (READPOS_DTYPE; min_calls 0: all 3 x (2 D + 1)): by
+        context, then 5' by ascending distance, 3' by ascending distance, interior; methylated = the ML byte reaches the context's
+        threshold of the last count().  Needs profile=D, after count()."""
+        return self._rows(self._L.hm_pileup_fetch_readpos, READPOS_DTYPE, min_calls)
+
+    def readpos_histograms(self) -> np.ndarray:
+        """the table itself, uint64 [3, 2 D + 1, 256]: context, bin (5' 0 .. D - 1, 3' 0 .. D - 1, interior), ML byte"""
+        h = np.zeros((3, 2 * self.profile + 1, 256), np.uint64)
+        self._check(self._L.hm_pileup_readpos_histograms(self._h, h.ctypes.data_as(C.c_void_p), h.size))
+        return h
+
+    def add_readpos(self, hist: np.ndarray):
+        """add another engine's readpos_histograms() to this one's table (the multi-rank path)"""
+        h = np.ascontiguousarray(hist, np.uint64)
+        self._check(self._L.hm_pileup_add_readpos(self._h, h.ctypes.data_as(C.c_void_p), h.size))
 
     def bedmethyl(self, lo: int = 0, hi: Optional[int] = None, min_valid: int = 1, partition: int = 0) -> np.ndarray:
         """the reference CpGs of [lo, hi), ascending (BEDMETHYL_DTYPE), at which a read was classed and n_mod + n_canon >= min_valid

@@ -1,7 +1,7 @@
 """`hifimeth pileup` over N GPUs of one node, one process per GPU (the path's only exchange step).
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
-        -m hifimeth_amd.pileup_dist [-q mapQ] [-f identity] [-H [-A [-a min-cov] [-Q] [-G [-s max-p] [-g max-gap] [-n min-loci]]]] [-B control | -e r,r,r] [-D [-u lo:hi[,lo:hi,lo:hi]] [-x nats] [-j bp]] [-L bp [-z min-pairs]] reference.fa mod.bam output-prefix
+        -m hifimeth_amd.pileup_dist [-q mapQ] [-f identity] [-H [-A [-a min-cov] [-Q] [-G [-s max-p] [-g max-gap] [-n min-loci]]]] [-B control | -e r,r,r] [-D [-u lo:hi[,lo:hi,lo:hi]] [-x nats] [-j bp]] [-L bp [-z min-pairs]] [-P bp [-y min-calls]] [-I n5[:n3]] reference.fa mod.bam output-prefix
 
 Records are dealt to the ranks in slabs of `--slab` records (round-robin, like the `call` path).  Each rank projects its
 records and histograms them on its own GPU; then
@@ -38,6 +38,10 @@ rank runs the same hm_domain_refit and stop rule (DomainFit) on them, so no leve
 -L bp: within-read co-methylation by distance.  A record lives on one rank, so the four counts per distance are sums over the ranks:
 every rank fetches all its distances (min_pairs 0), the [bp + 1, 4] int64 table goes through one all-reduce, and rank 0 applies -z
 and writes <prefix>.linkage.CpG.tsv, byte-identical to `pileup -L bp`.
+-P bp: methylation by position in the read.  A record lives on one rank and every rank counts with the same thresholds, so the three
+sums of a row (n_m, n_u, sum_ml) are sums over the ranks: every rank fetches all its rows (min_calls 0), the [3 (2 bp + 1), 3] int64
+table goes through one all-reduce, and rank 0 applies -y and writes <prefix>.readpos.tsv, byte-identical to `pileup -P bp`.
+-I n5[:n3]: every rank's engine drops the entries at the read ends, as `pileup -I` does.
 """
 from __future__ import annotations
 
@@ -50,7 +54,7 @@ import numpy as np
 from . import dist as D
 from .bamio import is_coordinate_sorted, load_fasta, read_bam
 from .caller import HifimethError
-from .pileup import (ASM_DTYPE, CTX_NAMES, LINKAGE_DTYPE, LINKAGE_MAX_DIST, linkage_tsv, DOMAIN_LEVELS, DOMAIN_MAX_GAP, DOMAIN_PASS_CODES, DOMAIN_PASS_SEGMENTS, DOMAIN_PASS_SUMMARY,
+from .pileup import (ASM_DTYPE, CTX_NAMES, LINKAGE_DTYPE, LINKAGE_MAX_DIST, linkage_tsv, READPOS_MAX, readpos_tsv, DOMAIN_LEVELS, DOMAIN_MAX_GAP, DOMAIN_PASS_CODES, DOMAIN_PASS_SEGMENTS, DOMAIN_PASS_SUMMARY,
                      DOMAIN_PENALTY, LOCUS_DTYPE, DomainFit, MethylationPileup, allreduce_histograms, asm_qvalues, asm_summary_tsv,
                      domain_backward_carries, domain_forward_carries, domain_scores, domains_fit_tsv, locus_ranges, parse_domain_levels, parse_rates,
                      rates_from_sums, reduce_scatter_planes, reduce_scatter_sum, resolve_threshold, sites_rates_tsv, sites_table,
@@ -61,7 +65,8 @@ def run(reference: str, bam: str, prefix: str, min_mapq: int = 0, min_pi: float 
         batch: int = 256, backend: str | None = None, log=sys.stderr, haplotypes: bool = False, asm: bool = False,
         asm_min_cov: int = 5, control: str | None = None, rates=None, asm_q: bool = False,
         asm_regions: bool = False, max_p: float = 0.01, max_gap: int = 500, min_loci: int = 3, domain_rules=None,
-        domain_max_gap: int = DOMAIN_MAX_GAP, domain_fit=None, linkage: int = 0, linkage_min_pairs: int = 1):
+        domain_max_gap: int = DOMAIN_MAX_GAP, domain_fit=None, linkage: int = 0, linkage_min_pairs: int = 1, profile: int = 0,
+        profile_min_calls: int = 1, trim=(0, 0)):
     """domain_rules (-D): per context (A, B, S) of domain_scores, or None for a context that is not segmented.  domain_fit (-Y):
     {"levels": per context (lo, hi) or None, "penalty", "max_iter"}: the levels are fitted from those and replace domain_rules"""
     import torch
@@ -99,7 +104,8 @@ def run(reference: str, bam: str, prefix: str, min_mapq: int = 0, min_pi: float 
     hp_planes = [torch.zeros(world * chunk, dtype=torch.int32, device=dev) for _ in range(4)] if haplotypes else []
     torch.cuda.synchronize()
     pu = MethylationPileup(genome, device=dev.index, min_mapq=min_mapq, min_pi=min_pi, planes=planes, partitions=haplotypes,
-                           partition_planes=(hp_planes[0:2], hp_planes[2:4]) if haplotypes else None, linkage=linkage)
+                           partition_planes=(hp_planes[0:2], hp_planes[2:4]) if haplotypes else None, linkage=linkage,
+                           profile=profile, trim=trim)
     staged = 0
     for order, rec in enumerate(records):
         if (order // slab) % world != rank or rec.flag & 4 or rec.mm is None:
@@ -275,6 +281,14 @@ def run(reference: str, bam: str, prefix: str, min_mapq: int = 0, min_pi: float 
             rows = rows[2:]
             with open(f"{prefix}.linkage.CpG.tsv", "w") as f:
                 f.write(linkage_tsv(rows[table[2:].sum(axis=1) >= linkage_min_pairs]))
+    if profile:                                             # records are dealt whole and the thresholds are shared: the rows add up
+        rows = pu.readpos(min_calls=0)
+        table = allreduce_i64(np.stack([rows[k] for k in ("n_m", "n_u", "sum_ml")], axis=1).astype(np.int64))
+        if rank == 0:
+            for c, k in enumerate(("n_m", "n_u", "sum_ml")):
+                rows[k] = table[:, c]
+            with open(f"{prefix}.readpos.tsv", "w") as f:
+                f.write(readpos_tsv(rows[table[:, 0] + table[:, 1] >= profile_min_calls]))
     if control is not None or rates is not None:
         mine, n_mine = (pc, nc, key), hi - lo               # this rank's chunk: element 0 is locus `base`
         sums = np.zeros(6, np.uint64)
@@ -352,6 +366,11 @@ def main(argv=None):
     ap.add_argument("-L", dest="linkage", type=int, default=None, metavar="BP",
                     help="within-read co-methylation by distance up to BP bases, in [2, 16384] -> <prefix>.linkage.CpG.tsv")
     ap.add_argument("-z", dest="linkage_min_pairs", type=int, default=None, help="with -L: smallest number of pairs of a distance that is written, >= 0 (default 1)")
+    ap.add_argument("-P", dest="profile", type=int, default=None, metavar="BP",
+                    help="methylation by position in the read, the BP bases at either end a row each, in [1, 2048] -> <prefix>.readpos.tsv")
+    ap.add_argument("-y", dest="profile_min_calls", type=int, default=None, help="with -P: smallest number of calls of a row that is written, >= 0 (default 1)")
+    ap.add_argument("-I", dest="trim", default=None, metavar="N5[:N3]",
+                    help="leave the calls in the first N5 and the last N3 bases of every read out of all outputs (one number: both ends)")
     ap.add_argument("reference")
     ap.add_argument("mod_bam")
     ap.add_argument("output_prefix")
@@ -390,6 +409,13 @@ def main(argv=None):
         ap.error("-z needs -L")
     if (a.linkage is not None and not 2 <= a.linkage <= LINKAGE_MAX_DIST) or (a.linkage_min_pairs is not None and a.linkage_min_pairs < 0):
         ap.error("-L must be an integer in [2, 16384], -z an integer >= 0")
+    if a.profile_min_calls is not None and a.profile is None:
+        ap.error("-y needs -P")
+    parts = (a.trim or "0").split(":")
+    bad_trim = not 1 <= len(parts) <= 2 or not all(t.isascii() and t.isdigit() and int(t) < 2 ** 31 for t in parts)
+    trim = (0, 0) if bad_trim else (int(parts[0]), int(parts[-1]))
+    if bad_trim or (a.profile is not None and not 1 <= a.profile <= READPOS_MAX) or (a.profile_min_calls is not None and a.profile_min_calls < 0):
+        ap.error("-P must be an integer in [1, 2048], -y an integer >= 0, -I n5[:n3] with integers >= 0")
     domain_rules = domain_fit = None
     if a.domains:
         bad = "-u takes lo:hi with 0 < lo < hi < 1 (levels a 2^24-th of a nat apart at least) or nan, once or per context; " \
@@ -409,7 +435,8 @@ def main(argv=None):
                asm_q=a.asm_q, asm_regions=a.asm_regions, max_p=0.01 if a.max_p is None else a.max_p,
                max_gap=500 if a.max_gap is None else a.max_gap, min_loci=3 if a.min_loci is None else a.min_loci,
                domain_rules=domain_rules, domain_max_gap=DOMAIN_MAX_GAP if a.domain_max_gap is None else a.domain_max_gap,
-               domain_fit=domain_fit, linkage=a.linkage or 0, linkage_min_pairs=1 if a.linkage_min_pairs is None else a.linkage_min_pairs)
+               domain_fit=domain_fit, linkage=a.linkage or 0, linkage_min_pairs=1 if a.linkage_min_pairs is None else a.linkage_min_pairs,
+               profile=a.profile or 0, profile_min_calls=1 if a.profile_min_calls is None else a.profile_min_calls, trim=trim)
 
 
 if __name__ == "__main__":

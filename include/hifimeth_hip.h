@@ -237,8 +237,8 @@ void hm_pileup_destroy(hm_pileup_t* p);
 const char* hm_pileup_last_error(const hm_pileup_t* p); /* p may be NULL: error of a failed create */
 /* options: "min_mapq" (-q, default 0), "min_pi" (-f, default 0.0), "partitions" (0 default, or 2: haplotype-resolved
  * counting, see hm_pileup_submit_read_hp; must be set before hm_pileup_set_reference / hm_pileup_use_planes, else HM_ESTATE),
- * "patterns" and "pattern_span" (read-level CpG patterns), "bedmethyl" (per-CpG depth classes) and "linkage" (co-methylation by
- * distance), all near the end of this header */
+ * "patterns" and "pattern_span" (read-level CpG patterns), "bedmethyl" (per-CpG depth classes), "linkage" (co-methylation by
+ * distance), "profile" (methylation by position in the read) and "trim5" / "trim3" (end trimming), all near the end of this header */
 int hm_pileup_set_option(hm_pileup_t* p, const char* key, double value);
 /* HbnDatabase: n_seqs upper-cased sequences back to back in `bases` (seq_len[i] bytes each).  Allocates and
  * zeroes the per-locus planes unless hm_pileup_use_planes was called before. */
@@ -670,6 +670,51 @@ int64_t hm_pileup_fetch_linkage(hm_pileup_t* p, int64_t min_pairs, hm_linkage_t*
  * coefficient r = (n_mm n_uu - n_mu n_um) / sqrt((n_mm + n_mu)(n_um + n_uu)(n_mm + n_um)(n_mu + n_uu)), the numerator an exact
  * integer, NaN when a margin is 0.  HM_EINVAL for n == 0. */
 int hm_linkage_stats(const hm_linkage_t* w, double out[2]);
+
+/* ---- methylation by position in the read, end trimming (`pileup -P`, `pileup -I`) ---------------------------
+ * The M-bias table of bisulfite pipelines, for this caller: every call is centred in a 401-base kinetics window that is zero-padded
+ * within 200 bases of either read end, and this table shows whether the calls made there behave like the others.
+ * PROJECTED RECORD: each record the projection emits (what hm_pileup_num_records counts) has a read position p, the index into the
+ * read's per-base plane at which the projection found the 5mC entry -- the offset in the read's original orientation, as MM counts
+ * it: for a reverse record's CpG the called C of the original strand, for a CHH call on the read's reverse strand the G.
+ * BIN: with L = l_qseq as submitted, d5 = p, d3 = L - 1 - p and the option value D: min(d5, d3) >= D is the INTERIOR bin; else
+ * d5 <= d3 is bin (5', d5) -- ties go to 5' --; else bin (3', d3).
+ * The records that count are exactly those hm_pileup_count will count (a record takes part as everywhere: its submission returned
+ * 1 and it passes -q / -f); secondary and supplementary records count as records of their own, as under the linkage above.
+ * THE TABLE: the thresholds are known only after the last read, so, like the linkage table, this one is threshold-free:
+ * H[motif][bin][ML byte] in uint64, 3 x (2 D + 1) x 256 counters in HBM (12.6 MB at D = 1024, 25.2 MB at D = 2048), filled at
+ * hm_pileup_run time.  It accumulates over run / count cycles as the planes do; a fetch applies the LAST hm_pileup_count's thresholds
+ * with its >=.  One histogram row gives n_m = sum_{v >= thr[motif]} H[v], n_u = sum_{v < thr[motif]} H[v] and sum_ml = sum v H[v],
+ * the sum of the ML bytes, which does not depend on the threshold.  Exact integers.
+ * TRIMMING: with "trim5" = n5 and "trim3" = n3 an entry (MM / ML entry or call) of a read at p < n5 or p > L - 1 - n3 is dropped
+ * where it would enter the per-base plane and the threshold histograms: it writes no plane word and adds no histogram count, so every
+ * output sees "no call" there -- the cov.bed counts, the haplotype, allele-specific, domain, pattern, linkage and fused paths, and
+ * the bedMethyl rows, where the call becomes an Nnocall.  n5 + n3 >= L drops every entry of the read.  0:0, the default, changes
+ * nothing.
+ * Options, before hm_pileup_set_reference (else HM_ESTATE; HM_EINVAL out of range): "profile" (D: 0 off = default, else
+ * 1 .. 2048), "trim5" and "trim3" (integers >= 0, default 0).  With "profile" on, hm_pileup_set_reference allocates and zeroes the
+ * table and hm_pileup_run's projection adds to it; without it nothing is allocated, uploaded or launched.  Not here: per-haplotype
+ * tables, bins wider than a base, np / rq strata, any statistical test, an automatic choice of trim values. */
+typedef struct {            /* one (motif, bin) = one row of <prefix>.readpos.tsv; 40 bytes */
+    uint32_t motif, end, dist, reserved;    /* end: 0 = 5', 1 = 3', 2 = interior (dist 0) */
+    uint64_t n_m, n_u, sum_ml;
+} hm_readpos_t;
+#define HM_READPOS_5P 0
+#define HM_READPOS_3P 1
+#define HM_READPOS_INTERIOR 2
+/* The rows with n_m + n_u >= min_calls: by motif, then 5' by ascending dist, 3' by ascending dist, interior; min_calls 0 returns all
+ * 3 x (2 D + 1) rows.  Returns their number (may exceed cap, or out NULL: then nothing is written).  HM_ESTATE without option
+ * "profile" or before the first hm_pileup_count, HM_EINVAL for min_calls < 0. */
+int64_t hm_pileup_fetch_readpos(hm_pileup_t* p, int64_t min_calls, hm_readpos_t* out, int64_t cap);
+/* The table itself, hist[(motif * (2 D + 1) + bin) * 256 + ML byte] with bin = d5, D + d3 or 2 D (interior): its
+ * 3 x (2 D + 1) x 256 counters into hist[cap] -> their number (may exceed cap, or hist NULL: then nothing is written).
+ * hm_pileup_add_readpos adds n such counters from elsewhere (another engine's table: the multi-rank path), n exactly that number
+ * else HM_EINVAL.  Both HM_ESTATE without option "profile". */
+int64_t hm_pileup_readpos_histograms(hm_pileup_t* p, uint64_t* hist, int64_t cap);
+int hm_pileup_add_readpos(hm_pileup_t* p, const uint64_t* hist, int64_t n);
+/* Host only, fp64: the one implementation behind every front end.  out[0] percent methylated = 100 n_m / (n_m + n_u), out[1] the
+ * mean ML byte = sum_ml / (n_m + n_u).  HM_EINVAL for n_m + n_u == 0. */
+int hm_readpos_stats(const hm_readpos_t* w, double out[2]);
 
 #ifdef __cplusplus
 }

@@ -20,6 +20,9 @@ rows, share of a pass.
 `--linkage D`: the within-read co-methylation by distance of `pileup -L D`, timed like `--patterns`: the leg is what the option adds to
 a pass (the member list through the selection skeleton -- one 8-byte count copy per batch -- and the pair kernel) plus one fetch of
 all rows (reduce per distance, LinkSel, D2H): pairs per second, rows, share of a pass.
+`--readpos D`: methylation by position in the read of `pileup -P D`, timed like `--patterns`: the leg is what the profiling variant of the
+projection adds to a pass (an LDS atomic per interior record, a global one per end record, one flush per workgroup) plus one fetch of all
+rows (reduce per row, ReadPosSel, D2H): records per second, rows, share of a pass.
 `--bedmethyl`: the depth classes of `pileup -M`, timed like `--patterns`: the passes on an engine without the option, then on one with
 it; the leg is what the option adds to projection and counting plus one fetch of the rows (D2H included).  The synthetic reads are
 error-free: the column kernel and the record count run at full size, the deletion kernel has nothing to do.
@@ -28,7 +31,7 @@ append order is not fixed), the loci of the combined set and of each partition, 
 and `--linkage` -- under "digest" in the JSON object, for comparing two builds of the library (HM_LIB_PATH) byte for byte.
 `--parts N` (with `--domains`): the same segments chained from N equal pieces next to the single fetch (three stateless passes per piece).
 
-    python tools/pileup_bench.py --genome-mb 20 --coverage 10 [--partitions [--asm [--asm-q] [--asm-regions]]] [--sites] [--domains [--fit] [--parts N]] [--patterns K] [--bedmethyl] [--linkage D]
+    python tools/pileup_bench.py --genome-mb 20 --coverage 10 [--partitions [--asm [--asm-q] [--asm-regions]]] [--sites] [--domains [--fit] [--parts N]] [--patterns K] [--bedmethyl] [--linkage D] [--readpos D]
 """
 import argparse
 import ctypes as C
@@ -123,6 +126,8 @@ def main():
                     help="time what the read-level CpG patterns over windows of K reference CpGs add (pileup -E K, default span and min reads)")
     ap.add_argument("--linkage", type=int, default=0, metavar="D",
                     help="time what the within-read co-methylation by distance up to D bases adds (pileup -L D, min_pairs 1)")
+    ap.add_argument("--readpos", type=int, default=0, metavar="D",
+                    help="time what the methylation by position in the read adds, D bases from either end resolved (pileup -P D, min_calls 1)")
     ap.add_argument("--bedmethyl", action="store_true", help="time what the per-CpG depth classes add (pileup -M, min_valid 1)")
     ap.add_argument("--digest", action="store_true", help="add a sha256 of the records, the loci and the rows of the timed options")
     ap.add_argument("--cpu-baseline", action="store_true",
@@ -170,7 +175,7 @@ def main():
                 pu.flush()
         pu.flush()
 
-    if a.patterns or a.bedmethyl or a.linkage:     # the same passes without the option(s) first: the leg is the difference
+    if a.patterns or a.bedmethyl or a.linkage or a.readpos:  # the same passes without the option(s) first: the leg is the difference
         one_pass()
         pu.count([128, 128, 128])
         t0 = time.perf_counter()
@@ -181,7 +186,7 @@ def main():
         pu.count([128, 128, 128])
         t_count_off = time.perf_counter() - t0
         pu.close()
-        pu = MethylationPileup(genome, partitions=a.partitions, patterns=a.patterns, bedmethyl=a.bedmethyl, linkage=a.linkage)
+        pu = MethylationPileup(genome, partitions=a.partitions, patterns=a.patterns, bedmethyl=a.bedmethyl, linkage=a.linkage, profile=a.readpos)
     one_pass(pu)                                   # warm-up (allocations)
     wins_per_pass = pu.num_pattern_records()
     recs_per_pass = pu.num_records()
@@ -255,6 +260,24 @@ def main():
             n_all = sum(int(rows[k].astype(np.uint64).sum()) for k in ("n_uu", "n_um", "n_mu", "n_mm"))
             out["check_linkage_rows"] = bool(len(rows) and n_all == pairs * (a.repeat + 1) and (np.diff(rows["dist"].astype(np.int64)) > 0).all()
                                              and rows["dist"][0] >= 2 and rows["dist"][-1] <= a.linkage)
+    if a.readpos:
+        pu.readpos()                               # warm-up: the three sums per row and the row buffer
+        t0 = time.perf_counter()
+        for _ in range(a.repeat):
+            rows = pu.readpos()
+        t_rows = (time.perf_counter() - t0) / a.repeat
+        n_all = int(rows["n_m"].sum() + rows["n_u"].sum())
+        ends = int((rows["n_m"] + rows["n_u"])[rows["end"] != 2].sum()) // (a.repeat + 1)
+        t_leg = max((t_project - t_project_off + t_count - t_count_off) / a.repeat, 0.0) + t_rows
+        t_pass = (t_project_off + t_count_off) / a.repeat + t_loci
+        out.update(readpos_reach=a.readpos, readpos_table_bytes=3 * (2 * a.readpos + 1) * 2048, readpos_rows=int(len(rows)),
+                   readpos_end_records_per_pass=ends,
+                   readpos_project_s_per_pass=[round(t_project_off / a.repeat, 4), round(t_project / a.repeat, 4)],
+                   readpos_count_s=[round(t_count_off, 4), round(t_count, 4)], readpos_rows_s=round(t_rows, 4),
+                   readpos_leg_s_per_pass=round(t_leg, 4), readpos_records_per_s=round(recs_per_pass / t_leg) if t_leg else 0,
+                   readpos_share_of_pass=round(t_leg / (t_pass + t_leg), 4), readpos_also=[a.patterns, a.bedmethyl, a.linkage])
+        if a.check:                                # every pass adds its records once; the methylated ones are the pcov plane
+            out["check_readpos_rows"] = bool(n_all == recs_per_pass * (a.repeat + 1) and int(rows["n_m"].sum()) == int(loci["pcov"].astype(np.int64).sum()))
     if a.bedmethyl:
         pu.bedmethyl()                             # warm-up: the row buffer
         t0 = time.perf_counter()
@@ -452,6 +475,8 @@ def main():
             digest["bedmethyl"] = [sha(pu.bedmethyl(partition=k)) for k in ((0, 1, 2) if a.partitions else (0,))]
         if a.linkage:
             digest["linkage"] = sha(pu.linkage())
+        if a.readpos:
+            digest["readpos"] = sha(pu.readpos())
         out["digest"] = digest
     if a.cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(genome, chrom, starts, staged, a.read_len)
