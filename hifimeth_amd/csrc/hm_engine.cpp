@@ -453,6 +453,9 @@ void reset_staging(hm_batch* b) {
 int check_read(hm_engine* e, const hm_read_t& r, int64_t tb, const char* who, const char* full) {
     if (r.l_qseq < 0) return fail(e, HM_EINVAL, std::string(who) + ": negative read length");
     if (r.l_qseq < e->min_read_size) return 0;                   // mod_main.cpp:189-192
+    // a read without bases (min_read_size 0) has no site: staged, it would own four constant tiles whose feature-row loads clamp their
+    // position to len - 1 = -1 -- the element in front of the batch's base and kinetics arrays when the read is the batch's first
+    if (r.l_qseq == 0) return 0;
     if (!r.kin[0] || !r.kin[1] || !r.kin[2] || !r.kin[3]) return 0;  // BamKinetics::init false (bam_info.cpp:572-603)
     if (!r.seq4) return fail(e, HM_EINVAL, std::string(who) + ": seq4 is NULL");
     for (int k = 0; k < 4; ++k)

@@ -116,7 +116,7 @@ int hm_set_option(hm_engine_t* e, const char* key, int64_t value);
 /* Copies one read into the pinned staging slab exactly as the BAM record stores it: 4-bit
  * packed SEQ, and the fi/fp/ri/rp B-arrays with element width 1 (B:C codev1) or 2 (B:S frames).
  * A NULL array means the tag is missing.  Returns 1 if the read was accepted, 0 if it is passed
- * through uncalled (l_qseq < min_read_size or a missing tag: mod_main.cpp:189-196), < 0 on error.
+ * through uncalled (l_qseq < min_read_size, l_qseq == 0 or a missing tag: mod_main.cpp:189-196), < 0 on error.
  * The caller keeps ownership of all pointers.                                                */
 int hm_submit_read(hm_engine_t* e, int32_t read_id, int32_t l_qseq, int32_t flag, const uint8_t* seq4,
                    const void* fi, int fi_width, const void* fp, int fp_width, const void* ri, int ri_width,

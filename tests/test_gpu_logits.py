@@ -14,7 +14,7 @@ import os
 import numpy as np
 import pytest
 
-from cnn64 import CNN64, bar, reference_sites, site_errors, strata
+from cnn64 import CNN64, STRATA, bar, reference_sites, site_errors, strata
 from conftest import WEIGHTS
 from hifimeth_amd.synth import read_from_ascii, synth_slab
 from test_gpu_parity import _extreme_reads, _kin, _mixed_reads
@@ -93,8 +93,8 @@ def _stage(m, reads):
     m.run()
 
 
-def _errors(m, reads, sites, perm=None):
-    """E per context (and per stratum) of the engine's staged batch; checks that its site lists are the oracle's."""
+def _errors(m, reads, sites, perm=None, names=STRATA):
+    """E per context (and per stratum of `names`) of the engine's staged batch; checks that its site lists are the oracle's."""
     out = []
     for c in range(3):
         s = sites[c]
@@ -106,7 +106,7 @@ def _errors(m, reads, sites, perm=None):
         assert lg.shape == (len(idx), 2) and np.isfinite(lg).all()
         e = np.empty(len(idx))
         e[idx] = site_errors(lg, s["f64"][idx])
-        by = {k: float(e[mk].max()) for k, mk in strata(s, c).items()}
+        by = {k: float(e[mk].max()) for k, mk in strata(s, c, names).items()}
         out.append((float(e.max(initial=0.0)), by))
     return out
 
