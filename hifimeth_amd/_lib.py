@@ -152,6 +152,11 @@ def lib():
         "hm_pileup_readpos_histograms": (i64, [vp, vp, i64]),
         "hm_pileup_add_readpos": (C.c_int, [vp, vp, i64]),
         "hm_readpos_stats": (C.c_int, [vp, vp]),
+        "hm_region_geometry": (C.c_int, [vp]),
+        "hm_pileup_fetch_regions": (C.c_int, [vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, i64, vp]),
+        "hm_pileup_fetch_metaplot": (C.c_int, [vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, i64, i32, i64, i32, vp,
+                                               C.POINTER(i64)]),
+        "hm_region_stats": (C.c_int, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

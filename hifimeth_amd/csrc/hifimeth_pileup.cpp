@@ -34,6 +34,9 @@
 // -P bp (ours): also <prefix>.readpos.tsv, methylation by position in the read: per context the calls 0 .. bp - 1 bases from the read's
 // 5' end, from its 3' end, and all others, with the percentage methylated and the mean ML byte (hm_pileup_fetch_readpos, DESIGN.md
 // section 10).  -I n5[:n3] (ours): the calls in the first n5 and the last n3 bases of a read are left out of every output.
+// -R bed (ours): also <prefix>.regions.<ctx>.tsv, the methylation of each interval of the BED file (loci with coverage >= -C), and with
+// -J bins[:flank:flank_bins] <prefix>.metaplot.<ctx>.tsv, the profile across all intervals and their flanks (hm_pileup_fetch_regions,
+// hm_pileup_fetch_metaplot).  The file is read and checked before the engine exists.
 // -K (ours): the input is an aligned BAM that still carries the kinetics tags (pbmm2 keeps fi / fp / ri / rp): the reads are called
 // on the fly by the call engine and their calls go straight to the pileup engine (hm_pileup_submit_read_calls) -- the files
 // `call` followed by `pileup` writes, without the mod-BAM between the two.
@@ -127,6 +130,11 @@ struct PileupOptions {
     long long profile_min_calls = 1;   // -y: smallest number of calls of a row that is written
     long long trim5 = 0, trim3 = 0;    // -I: the calls in the first trim5 / last trim3 bases of a read are dropped
     bool profile_option_given = false, profile_option_bad = false;  // -y; -P, -y or -I with a value out of range
+    std::string intervals;             // -R: BED file of intervals -> <prefix>.regions.<ctx>.tsv
+    long long interval_min_cov = 1;    // -C: smallest pcov + ncov of a locus that counts under -R / -J
+    int meta_bins = 0, meta_flank_bins = 0;  // -J bins[:flank:flank_bins] -> <prefix>.metaplot.<ctx>.tsv
+    long long meta_flank = 0;
+    bool interval_option_given = false, interval_option_bad = false;  // -C or -J; either with a value out of range
     // -K: call on the fly; the options below are `call`'s (hifimeth_call.cpp), same meaning and defaults
     bool kinetics = false;
     bool call_option_given = false;  // any of -m -c -l -p -T: a usage error without -K
@@ -208,6 +216,17 @@ void pileup_usage(const char* exe) {
             "  -y <int>\n    With -P: smallest n of a row that is written, >= 0 (0: every row)\n    Default: 1\n"
             "  -I <n5>[:<n3>]\n    Leave the calls in the first n5 and the last n3 bases of every read (as sequenced) out of all outputs; one number\n"
             "    sets both ends\n    Default: 0:0\n"
+            "  -R <bed>\n    Methylation of given intervals: a BED file (plain or gzip) of at least 3 tab-separated columns, name in column 4,\n"
+            "    strand in column 6; empty lines and lines starting with #, track or browser are skipped.  Writes <prefix>.regions.<ctx>.tsv\n"
+            "    (with -H also <prefix>.hap1. and <prefix>.hap2.regions.<ctx>.tsv): a header line, then per interval in input order chrom,\n"
+            "    start, end, name, strand, n_loci, pcov, ncov, weighted = 100 pcov / (pcov + ncov) and mean, the mean of the loci's own\n"
+            "    percentages (nan without a counted locus).  Intervals may overlap, nest and come in any order\n"
+            "  -C <int>\n    With -R: smallest coverage (pcov + ncov) of a locus that counts, >= 1\n    Default: 1\n"
+            "  -J <bins>[:<flank_bp>:<flank_bins>]\n    With -R: the metaplot.  Every interval of at least <bins> bases is cut into <bins> in [1, 1000] equal\n"
+            "    bins, and each flank of flank_bp bases (a multiple of flank_bins in [1, 1000]) into flank_bins; a flank ends at its sequence's\n"
+            "    end.  Bins run from upstream to downstream, mirrored for intervals on the - strand, and are summed over the intervals.  Writes\n"
+            "    <prefix>.metaplot.<ctx>.tsv (with -H per haplotype too): `#regions used skipped`, a header line, then per bin bin, part (up,\n"
+            "    body, down), n_regions, n_loci, pcov, ncov, weighted, mean\n    Default flank: 0:0\n"
             "  -K\n    The input is an aligned BAM that carries the kinetics tags fi / fp / ri / rp instead of MM / ML: call 5mC on the\n"
             "    fly and pile the calls up directly.  For equal -c -l -p -T -q -f the output files are byte-identical to those of\n"
             "    `%s call` on that BAM followed by `%s pileup` on its output; no mod-BAM is written.  (Give -T explicitly\n"
@@ -1028,6 +1047,150 @@ bool write_readpos(hm_pileup_t* pe, const PileupOptions& o) {
     return fclose(f) == 0;
 }
 
+// -J: bins[:flank_bp:flank_bins]; false unless the whole text parses and lies in the ranges hm_pileup_fetch_metaplot takes
+bool parse_metaplot(const char* text, int& bins, long long& flank, int& flank_bins) {
+    long long v[3] = {0, 0, 0};
+    int n = 0;
+    for (const char* c = text;; ++n) {
+        char* end = nullptr;
+        errno = 0;
+        if (n == 3 || !isdigit((unsigned char)*c)) return false;
+        v[n] = strtoll(c, &end, 10);
+        if (errno) return false;
+        if (!*end) break;
+        if (*end != ':') return false;
+        c = end + 1;
+    }
+    if (n != 0 && n != 2) return false;
+    if (v[0] < 1 || v[0] > 1000 || v[2] > 1000 || (v[1] == 0) != (v[2] == 0) || (v[2] && v[1] % v[2])) return false;
+    bins = (int)v[0];
+    flank = v[1];
+    flank_bins = (int)v[2];
+    return true;
+}
+
+// -R: the intervals of a BED file in input order, in sequence coordinates
+struct Intervals {
+    std::vector<int> sid;
+    std::vector<int64_t> start, end;
+    std::vector<std::string> name;
+    std::string strand;  // '+', '-' or '.' per interval
+};
+
+// Plain or gzip, at least 3 tab-separated columns; empty lines and lines starting with #, track or browser are skipped; the name is
+// column 4 or ".", the strand column 6 if it is + or -, else ".".  false (message naming the line printed) for a file that cannot
+// be read, too few columns, coordinates that are no integers, an unknown sequence, start < 0, start >= end, end > the sequence.
+bool read_intervals(const std::string& path, const Fasta& fa, Intervals& iv) {
+    gzFile in = gzopen(path.c_str(), "rb");
+    if (!in) { fprintf(stderr, "ERROR: cannot open %s (-R)\n", path.c_str()); return false; }
+    std::string line;
+    char buf[4096];
+    long long no = 0;
+    bool ok = true;
+    auto bad = [&](const std::string& what) {
+        fprintf(stderr, "ERROR: %s:%lld: %s\n", path.c_str(), no, what.c_str());
+        return ok = false;
+    };
+    while (ok) {
+        line.clear();
+        bool got = false;
+        while (gzgets(in, buf, sizeof buf)) {  // a line of any length
+            got = true;
+            line += buf;
+            if (!line.empty() && line.back() == '\n') break;
+        }
+        if (!got) break;
+        ++no;
+        while (!line.empty() && (line.back() == '\n' || line.back() == '\r')) line.pop_back();
+        if (line.empty() || line[0] == '#' || line.compare(0, 5, "track") == 0 || line.compare(0, 7, "browser") == 0) continue;
+        std::vector<std::string> col;
+        for (size_t a = 0;;) {
+            const size_t b = line.find('\t', a);
+            col.push_back(line.substr(a, b == std::string::npos ? b : b - a));
+            if (b == std::string::npos) break;
+            a = b + 1;
+        }
+        if (col.size() < 3) { bad("fewer than 3 tab-separated columns"); break; }
+        long long x[2];
+        bool numbers = true;
+        for (int k = 0; k < 2; ++k) {
+            char* end = nullptr;
+            errno = 0;
+            x[k] = strtoll(col[(size_t)k + 1].c_str(), &end, 10);
+            if (end == col[(size_t)k + 1].c_str() || *end || errno) numbers = false;
+        }
+        if (!numbers) { bad("start and end must be integers"); break; }
+        const int sid = fa.find(col[0]);
+        if (sid < 0) { bad("unknown sequence " + col[0]); break; }
+        if (x[0] < 0) { bad("start < 0"); break; }
+        if (x[0] >= x[1]) { bad("start >= end"); break; }
+        if (x[1] > fa.length[(size_t)sid]) { bad("end " + std::to_string(x[1]) + " is past the end of " + col[0] + " (" + std::to_string(fa.length[(size_t)sid]) + ")"); break; }
+        iv.sid.push_back(sid);
+        iv.start.push_back(x[0]);
+        iv.end.push_back(x[1]);
+        iv.name.push_back(col.size() > 3 && !col[3].empty() ? col[3] : ".");
+        iv.strand.push_back(col.size() > 5 && (col[5] == "+" || col[5] == "-") ? col[5][0] : '.');
+    }
+    gzclose(in);
+    return ok;
+}
+
+// n_loci, pcov, ncov, weighted, mean: the columns both interval outputs end with; the percentages hm_region_stats', nan without a locus
+void print_region_columns(FILE* f, const hm_region_sum_t& r) {
+    double st[2];
+    if (hm_region_stats(&r, st) == HM_OK) fprintf(f, "%lld\t%lld\t%lld\t%.6g\t%.6g\n", (long long)r.n_loci, (long long)r.pcov, (long long)r.ncov, st[0], st[1]);
+    else fprintf(f, "%lld\t%lld\t%lld\tnan\tnan\n", (long long)r.n_loci, (long long)r.pcov, (long long)r.ncov);
+}
+
+// <prefix>.<tag>regions.<ctx>.tsv and, under -J, <prefix>.<tag>metaplot.<ctx>.tsv from one set of planes (NULL: the engine's own).
+// false on an engine error (recorded) or a file error (reported).
+bool write_intervals(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, const Intervals& iv, const std::string& tag, const void* const planes[3]) {
+    std::vector<int64_t> off(fa.length.size() + 1, 0);
+    for (size_t i = 0; i < fa.length.size(); ++i) off[i + 1] = off[i] + fa.length[i];
+    const size_t n = iv.sid.size();
+    std::vector<int64_t> start(n), end(n), s0(n), s1(n);
+    for (size_t i = 0; i < n; ++i) {
+        s0[i] = off[(size_t)iv.sid[i]];
+        s1[i] = off[(size_t)iv.sid[i] + 1];
+        start[i] = s0[i] + iv.start[i];
+        end[i] = s0[i] + iv.end[i];
+    }
+    std::vector<hm_region_sum_t> sums(3 * n);
+    if (hm_pileup_fetch_regions(pe, planes[0], planes[1], planes[2], 0, 0, off.back(), o.interval_min_cov, start.data(), end.data(), (int64_t)n,
+                                sums.data()) != HM_OK)
+        return false;
+    {
+        CtxFiles out;
+        if (!out.open(o.prefix, tag + "regions.", ".tsv")) return false;
+        for (int c = 0; c < 3; ++c) {
+            fprintf(out.f[c], "#chrom\tstart\tend\tname\tstrand\tn_loci\tpcov\tncov\tweighted\tmean\n");
+            for (size_t i = 0; i < n; ++i) {
+                fprintf(out.f[c], "%s\t%lld\t%lld\t%s\t%c\t", fa.names[(size_t)iv.sid[i]].c_str(), (long long)iv.start[i], (long long)iv.end[i],
+                        iv.name[i].c_str(), iv.strand[i]);
+                print_region_columns(out.f[c], sums[3 * i + (size_t)c]);
+            }
+        }
+    }
+    if (!o.meta_bins) return true;
+    const int nb = o.meta_bins + 2 * o.meta_flank_bins;
+    std::vector<hm_metabin_t> rows(3 * (size_t)nb);
+    int64_t n_used = 0;
+    if (hm_pileup_fetch_metaplot(pe, planes[0], planes[1], planes[2], 0, 0, off.back(), o.interval_min_cov, start.data(), end.data(), s0.data(), s1.data(),
+                                 iv.strand.data(), (int64_t)n, o.meta_bins, o.meta_flank, o.meta_flank_bins, rows.data(), &n_used) != HM_OK)
+        return false;
+    CtxFiles out;
+    if (!out.open(o.prefix, tag + "metaplot.", ".tsv")) return false;
+    for (int c = 0; c < 3; ++c) {
+        fprintf(out.f[c], "#regions\t%lld\t%lld\n#bin\tpart\tn_regions\tn_loci\tpcov\tncov\tweighted\tmean\n", (long long)n_used, (long long)n - (long long)n_used);
+        for (int b = 0; b < nb; ++b) {
+            const hm_metabin_t& r = rows[(size_t)c * nb + b];
+            fprintf(out.f[c], "%d\t%s\t%lld\t", b, b < o.meta_flank_bins ? "up" : b < o.meta_flank_bins + o.meta_bins ? "body" : "down", (long long)r.n_regions);
+            print_region_columns(out.f[c], hm_region_sum_t{r.n_loci, r.pcov, r.ncov, r.ppm});
+        }
+    }
+    return true;
+}
+
 // -I: n5[:n3], integers >= 0, one number for both ends; false unless the whole text parses
 bool parse_trim(const char* text, long long& n5, long long& n3) {
     char* end = nullptr;
@@ -1501,6 +1664,19 @@ int cmd_pileup(int argc, char** argv) {
             else { if (x < 0) o.profile_option_bad = true; else o.profile_min_calls = x; }
         }
         else if (a == "-I") { if (!parse_trim(argv[++i], o.trim5, o.trim3)) o.profile_option_bad = true; }
+        else if (a == "-R") o.intervals = argv[++i];
+        else if (a == "-C") {  // the whole value must parse
+            o.interval_option_given = true;
+            const char* v = argv[++i];
+            char* end = nullptr;
+            errno = 0;
+            o.interval_min_cov = strtoll(v, &end, 10);
+            if (end == v || *end || errno || o.interval_min_cov < 1) o.interval_option_bad = true;
+        }
+        else if (a == "-J") {
+            o.interval_option_given = true;
+            if (!parse_metaplot(argv[++i], o.meta_bins, o.meta_flank, o.meta_flank_bins)) o.interval_option_bad = true;
+        }
         else if (a == "-v") {  // the whole value must parse
             o.bedmethyl_option_given = true;
             const char* v = argv[++i];
@@ -1573,6 +1749,10 @@ int cmd_pileup(int argc, char** argv) {
     const char* bad_profile = o.profile_option_bad ? "-P must be an integer in [1, 2048], -y an integer >= 0, -I n5[:n3] with integers >= 0"
                               : o.profile_option_given && !o.profile ? "-y needs -P" : nullptr;
     if (bad_profile) { fprintf(stderr, "ERROR: %s\n", bad_profile); pileup_usage(argv[0]); return EXIT_FAILURE; }
+    const char* bad_intervals = o.interval_option_given && o.intervals.empty() ? "-C and -J need -R"
+                                : o.interval_option_bad ? "-C must be an integer >= 1, -J bins[:flank_bp:flank_bins] with bins in [1, 1000] and flank_bp a "
+                                                          "multiple of flank_bins in [1, 1000]" : nullptr;
+    if (bad_intervals) { fprintf(stderr, "ERROR: %s\n", bad_intervals); pileup_usage(argv[0]); return EXIT_FAILURE; }
     const bool sites = !o.control.empty() || o.rates_given;
     if (o.kinetics && o.model_dir.empty()) o.model_dir = exe_dir() + "/../weights";
     o.ref = argv[i];
@@ -1613,6 +1793,12 @@ int cmd_pileup(int argc, char** argv) {
     if (o.profile)
         fprintf(stderr, "readpos: calls by position in the read, %lld bases from either end resolved, rows with >= %lld calls -> %s.readpos.tsv\n", o.profile,
                 o.profile_min_calls, o.prefix.c_str());
+    if (!o.intervals.empty()) {
+        fprintf(stderr, "regions: intervals of %s, loci with coverage >= %lld -> %s.regions.*\n", o.intervals.c_str(), o.interval_min_cov, o.prefix.c_str());
+        if (o.meta_bins)
+            fprintf(stderr, "metaplot: %d bins per interval, flanks of %lld bases in %d bins -> %s.metaplot.*\n", o.meta_bins, o.meta_flank,
+                    o.meta_flank_bins, o.prefix.c_str());
+    }
     if (o.trim5 || o.trim3) fprintf(stderr, "trim: calls in the first %lld and the last %lld bases of a read are left out\n", o.trim5, o.trim3);
     if (o.kinetics)
         fprintf(stderr, "kinetics: called on the fly (models %s, contexts%s%s%s, min read length %d, precision %d, trunk %s)\n", o.model_dir.c_str(),
@@ -1636,6 +1822,9 @@ int cmd_pileup(int argc, char** argv) {
     std::vector<int> tid2sid(hdr.refs.size(), -2);  // resolved at first use, as HbnDatabase::seq_name2id
     const int control_sid = o.control.empty() ? -1 : fa.find(o.control);
     if (!o.control.empty() && control_sid < 0) { fprintf(stderr, "ERROR: control sequence %s (-B) is not in %s\n", o.control.c_str(), o.ref.c_str()); return EXIT_FAILURE; }
+
+    Intervals intervals;  // read and checked before the engine exists: a bad file needs no device
+    if (!o.intervals.empty() && !read_intervals(o.intervals, fa, intervals)) return EXIT_FAILURE;
 
     hm_pileup_t* pe = nullptr;
     if (hm_pileup_create(&pe, o.device) != HM_OK) { fprintf(stderr, "ERROR: %s\n", hm_pileup_last_error(nullptr)); return EXIT_FAILURE; }
@@ -1809,6 +1998,8 @@ int cmd_pileup(int argc, char** argv) {
     }
     if (o.linkage && !write_linkage(pe, o)) return die("linkage");
     if (o.profile && !write_readpos(pe, o)) return die("readpos");
+    for (size_t t = 0; !o.intervals.empty() && t < tags.size(); ++t)
+        if (!write_intervals(pe, fa, o, intervals, tags[t], &planes[3 * t])) return die("regions");
     if (sites) {
         const int rc = write_sites(pe, fa, o, control_sid, o.threads);
         if (rc < 0) return die("sites");

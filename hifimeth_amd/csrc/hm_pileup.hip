@@ -49,6 +49,9 @@
 //                   path as two scans over a monoid (reduce per workgroup, one workgroup scans the aggregates, re-scan), segment
 //                   heads compacted, one thread per segment (domain_build_part_kernel); for the fit of the levels (`-D -Y`) the
 //                   rows' counters summed by state behind the two scans instead (domain_sums_kernel)
+//   region_block_sums / RegionScan / region_query / metaplot   sums over given intervals (`pileup -R`, `-J`): twelve sums per block of
+//                   HM_REGION_BLOCK loci, their scan by the row-scan skeleton above, then a wavefront per interval (or per bin and
+//                   stride of intervals) reads the index and sums the loci of its two partial blocks
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1695,6 +1698,196 @@ __global__ __launch_bounds__(TPB) void domain_sums_kernel(const DomRow* __restri
     }
 }
 
+// ---- sums over given intervals, metaplots (`pileup -R`, `pileup -J`; include/hifimeth_hip.h has the definition) ----------------
+// Twelve int64 quantities, k = 4 * context + {n_loci, pcov, ncov, ppm}: hm_region_sum_t[3] as one array.  The index of a range
+// [lo, hi) is idx[b * 12 + k] = the sum over the blocks 0 .. b of HM_REGION_BLOCK loci (region_block_sums_kernel, then the row scan
+// above in place with RegionScan: no workgroup waits for another).  A query is answered by ONE wavefront: the loci of at most two
+// partial blocks, strided over its lanes, and two reads of the index.
+constexpr int REGION_LANES = 12;
+static_assert(HM_REGION_BLOCK >= TPB && (HM_REGION_BLOCK & (HM_REGION_BLOCK - 1)) == 0, "a block is a power of two of whole workgroup passes");
+static_assert(HM_REGION_SCAN_BLOCKS == SCAN_ROWS, "the header names the row scan's partition");
+static_assert(sizeof(hm_region_sum_t) * 3 == sizeof(int64_t) * REGION_LANES, "a row of the index is three hm_region_sum_t");
+
+struct RegionAcc {
+    int64_t v[REGION_LANES];
+};
+
+// (2 000 000 p + cov) / (2 cov) for 0 <= p <= cov < 2^32, cov > 0, exactly: the numerator is below 2^53, so the fp64 quotient is
+// within one of the integer one, and the remainder says which way
+__device__ __forceinline__ int64_t region_ppm(int64_t p, int64_t cov) {
+    const int64_t num = 2000000 * p + cov, den = 2 * cov;
+    const int64_t q = (int64_t)((double)num / (double)den);
+    const int64_t r = num - q * den;
+    return r < 0 ? q - 1 : r >= den ? q + 1 : q;
+}
+
+// locus i of the planes, if it counts, into its context's four sums
+__device__ __forceinline__ void region_add(const RangePlanes& s, int64_t min_cov, int64_t i, RegionAcc& a) {
+    const int64_t p = s.pc[i], n = s.nc[i], cov = p + n;
+    if (cov < min_cov) return;
+    const uint32_t c = s.ky[i] & 3u;
+    const int64_t ppm = region_ppm(p, cov);
+#pragma unroll
+    for (uint32_t m = 0; m < 3; ++m) {
+        const bool on = c == m;
+        a.v[4 * m] += on ? 1 : 0;
+        a.v[4 * m + 1] += on ? p : 0;
+        a.v[4 * m + 2] += on ? n : 0;
+        a.v[4 * m + 3] += on ? ppm : 0;
+    }
+}
+
+__device__ __forceinline__ int64_t wave_sum(int64_t v) {  // in every lane
+    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+// the lanes' partial sums -> lane k < REGION_LANES returns quantity k's total plus its `whole`
+__device__ __forceinline__ int64_t wave_lane_totals(const RegionAcc& a, int64_t whole) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < REGION_LANES; ++k) {
+        const int64_t t = wave_sum(a.v[k]);
+        if (lane == k) whole += t;
+    }
+    return whole;
+}
+
+// idx[blockIdx.x * 12 + k] = quantity k summed over block blockIdx.x of [lo, hi)
+__global__ __launch_bounds__(TPB) void region_block_sums_kernel(RangePlanes s, int64_t lo, int64_t hi, int64_t min_cov,
+                                                                 int64_t* __restrict__ idx) {
+    __shared__ int64_t part[TPB / 64][REGION_LANES];
+    const int64_t base = lo + (int64_t)blockIdx.x * HM_REGION_BLOCK;
+    RegionAcc a{};
+#pragma unroll 4
+    for (int k = 0; k < HM_REGION_BLOCK / TPB; ++k) {
+        const int64_t i = base + k * TPB + threadIdx.x;
+        if (i < hi) region_add(s, min_cov, i, a);
+    }
+    const int64_t v = wave_lane_totals(a, 0);
+    if ((threadIdx.x & 63) < REGION_LANES) part[threadIdx.x >> 6][threadIdx.x & 63] = v;
+    __syncthreads();
+    if (threadIdx.x < REGION_LANES) {
+        int64_t t = 0;
+        for (int w = 0; w < TPB / 64; ++w) t += part[w][threadIdx.x];
+        idx[(int64_t)blockIdx.x * REGION_LANES + threadIdx.x] = t;
+    }
+}
+
+// the block sums -> their inclusive scan, in place: an element is loaded and stored by the one thread that owns it
+struct RegionScan {
+    using T = RegionAcc;
+    int64_t* idx;
+    __host__ __device__ __forceinline__ static T identity() { return T{}; }
+    __device__ __forceinline__ static T shfl_up(const T& v, int d) {
+        T r;
+#pragma unroll
+        for (int k = 0; k < REGION_LANES; ++k) r.v[k] = __shfl_up(v.v[k], d);
+        return r;
+    }
+    __device__ __forceinline__ static T op(const T& a, const T& b) {
+        T r;
+#pragma unroll
+        for (int k = 0; k < REGION_LANES; ++k) r.v[k] = a.v[k] + b.v[k];
+        return r;
+    }
+    __device__ __forceinline__ T load(int64_t j) const {
+        T r;
+#pragma unroll
+        for (int k = 0; k < REGION_LANES; ++k) r.v[k] = idx[j * REGION_LANES + k];
+        return r;
+    }
+    __device__ __forceinline__ void store(int64_t j, const T& f) const {
+#pragma unroll
+        for (int k = 0; k < REGION_LANES; ++k) idx[j * REGION_LANES + k] = f.v[k];
+    }
+};
+
+struct RegionIndex {  // of the planes' range [lo, hi) under min_cov
+    RangePlanes s;
+    int64_t lo, hi, min_cov;
+    const int64_t* idx;
+};
+
+// One wavefront adds the sums over [a, b), lo <= a <= b <= hi, both the same in all its lanes: the loci from a to the end of a's
+// block and from the start of b's block to b into the lanes' partial sums, the blocks between them from the index into `whole` of
+// lane k < 12 -- prefix(b) - prefix(a) with a's remainder taken to its block's end, so that nothing is subtracted.  Within one
+// block the loci of [a, b) themselves.
+__device__ __forceinline__ void wave_range_add(const RegionIndex& ix, int64_t a, int64_t b, RegionAcc& acc, int64_t& whole) {
+    const int lane = threadIdx.x & 63;
+    const int64_t ba = (a - ix.lo) / HM_REGION_BLOCK, bb = (b - ix.lo) / HM_REGION_BLOCK;
+    const int64_t head_end = ba == bb ? b : ix.lo + (ba + 1) * HM_REGION_BLOCK;
+    for (int64_t i = a + lane; i < head_end; i += 64) region_add(ix.s, ix.min_cov, i, acc);
+    if (ba == bb) return;
+    for (int64_t i = ix.lo + bb * HM_REGION_BLOCK + lane; i < b; i += 64) region_add(ix.s, ix.min_cov, i, acc);
+    if (lane < REGION_LANES && bb > ba + 1) whole += ix.idx[(bb - 1) * REGION_LANES + lane] - ix.idx[ba * REGION_LANES + lane];
+}
+
+__device__ __forceinline__ int64_t clamp_to(int64_t x, int64_t lo, int64_t hi) { return min(max(x, lo), hi); }
+
+// out[i * 12 + k] = quantity k of interval i, clamped to the range: a wavefront per interval, over a grid stride
+__global__ __launch_bounds__(TPB) void region_query_kernel(RegionIndex ix, int64_t plane_base, const int64_t* __restrict__ start,
+                                                            const int64_t* __restrict__ end, int64_t n, int64_t* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t i = (int64_t)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6); i < n; i += (int64_t)gridDim.x * (TPB / 64)) {
+        RegionAcc acc{};
+        int64_t whole = 0;
+        wave_range_add(ix, clamp_to(start[i] - plane_base, ix.lo, ix.hi), clamp_to(end[i] - plane_base, ix.lo, ix.hi), acc, whole);
+        const int64_t v = wave_lane_totals(acc, whole);
+        if (lane < REGION_LANES) out[i * REGION_LANES + lane] = v;
+    }
+}
+
+struct MetaGeom {
+    int32_t bins, flank_bins;
+    int64_t flank;
+    __host__ __device__ int n_bins() const { return bins + 2 * flank_bins; }
+};
+struct MetaIv {  // a used interval [s, e) on its sequence [S0, S1), global coordinates; 40 bytes
+    int64_t s, e, S0, S1, neg;
+};
+
+// bin `out_bin` of an interval as the output numbers it (mirrored for the reverse strand) -> [a, b), clamped to the sequence
+__host__ __device__ inline void metabin_range(const MetaGeom& m, const MetaIv& r, int out_bin, int64_t& a, int64_t& b) {
+    const int g = r.neg ? m.n_bins() - 1 - out_bin : out_bin;  // in reference direction
+    const int64_t w = m.flank_bins ? m.flank / m.flank_bins : 0;
+    if (g < m.flank_bins) {
+        a = r.s - m.flank + g * w;
+        b = a + w;
+    } else if (g < m.flank_bins + m.bins) {
+        const int64_t j = g - m.flank_bins, len = r.e - r.s;
+        a = r.s + j * len / m.bins;
+        b = r.s + (j + 1) * len / m.bins;
+    } else {
+        a = r.e + (g - m.flank_bins - m.bins) * w;
+        b = a + w;
+    }
+    a = a < r.S0 ? r.S0 : a > r.S1 ? r.S1 : a;
+    b = b < r.S0 ? r.S0 : b > r.S1 ? r.S1 : b;
+}
+
+// tab[bin * 12 + k] += quantity k of bin blockIdx.x over the intervals: a wavefront keeps its partial sums over a stride of the
+// intervals (blockIdx.y), then one reduction and at most twelve 64-bit atomics per workgroup.  Integers: exact in any order.
+__global__ __launch_bounds__(TPB) void metaplot_kernel(RegionIndex ix, int64_t plane_base, MetaGeom m, const MetaIv* __restrict__ iv,
+                                                        int64_t n, unsigned long long* __restrict__ tab) {
+    __shared__ int64_t part[TPB / 64][REGION_LANES];
+    RegionAcc acc{};
+    int64_t whole = 0;
+    for (int64_t i = (int64_t)blockIdx.y * (TPB / 64) + (threadIdx.x >> 6); i < n; i += (int64_t)gridDim.y * (TPB / 64)) {
+        int64_t a, b;
+        metabin_range(m, iv[i], (int)blockIdx.x, a, b);
+        wave_range_add(ix, clamp_to(a - plane_base, ix.lo, ix.hi), clamp_to(b - plane_base, ix.lo, ix.hi), acc, whole);
+    }
+    const int64_t v = wave_lane_totals(acc, whole);
+    if ((threadIdx.x & 63) < REGION_LANES) part[threadIdx.x >> 6][threadIdx.x & 63] = v;
+    __syncthreads();
+    if (threadIdx.x < REGION_LANES) {
+        int64_t t = 0;
+        for (int w = 0; w < TPB / 64; ++w) t += part[w][threadIdx.x];
+        if (t) atomicAdd(&tab[(int64_t)blockIdx.x * REGION_LANES + threadIdx.x], (unsigned long long)t);
+    }
+}
+
 }  // namespace
 
 // ================================================ host ==========================================================
@@ -1768,6 +1961,9 @@ struct hm_pileup {
     int profile = 0;
     Trim trim{0, 0};
     DevBuf d_rphist{EXACT}, d_rptab{EXACT}, d_rpadd{EXACT};
+    // `pileup -R / -J`, allocated by the first call that needs them: the index of the range in hand (96 B per HM_REGION_BLOCK loci),
+    // the caller's intervals, and the sums per interval or the metaplot's table
+    DevBuf d_rgidx{EXACT}, d_rgiv{HALF}, d_rgout{HALF};
     uint32_t thr_packed = 0;   // the three thresholds of the last hm_pileup_count
     bool counted = false;     // hm_pileup_count has run since hm_pileup_set_reference: what the -E, -M and -L fetches wait for
     int64_t n_recs = 0;
@@ -3254,6 +3450,141 @@ int64_t hm_pileup_fetch_sites(hm_pileup_t* p, const void* pcov, const void* ncov
             },
             no_hook);
     });
+}
+
+}  // extern "C"
+
+// ---- `pileup -R / -J` ------------------------------------------------------------------------------------------------------------
+namespace {
+
+// the index of the non-empty [lo, hi) of the planes `s` under min_cov, in d_rgidx: the block sums, then their scan; under the
+// caller's guard
+RegionIndex build_region_index(hm_pileup* p, const RangePlanes& s, int64_t lo, int64_t hi, int64_t min_cov) {
+    const int64_t nblk = (hi - lo + HM_REGION_BLOCK - 1) / HM_REGION_BLOCK;
+    p->d_rgidx.reserve(sizeof(int64_t) * REGION_LANES * (size_t)nblk);
+    int64_t* idx = p->d_rgidx.as<int64_t>();
+    hipLaunchKernelGGL(region_block_sums_kernel, dim3((unsigned)nblk), dim3(TPB), 0, p->stream, s, lo, hi, min_cov, idx);
+    HIP_TRY(hipGetLastError());
+    row_scan(p, RegionScan{idx}, nblk);
+    return RegionIndex{s, lo, hi, min_cov, idx};
+}
+
+// what both fetches check first; the planes into `s`
+int region_call(hm_pileup* p, const char* who, const void* pcov, const void* ncov, const void* key, int64_t& plane_base, int64_t lo,
+                int64_t hi, int64_t min_cov, const int64_t* start, const int64_t* end, int64_t n, bool has_out, RangePlanes& s) {
+    if (lo < 0 || hi < lo || n < 0 || (n && (!start || !end)) || !has_out) return pfail(p, HM_EINVAL, std::string(who) + ": bad argument");
+    if (hi - lo >= (int64_t(1) << 31) * HM_REGION_BLOCK) return pfail(p, HM_EINVAL, std::string(who) + ": range too large");
+    if (min_cov < 1) return pfail(p, HM_EINVAL, std::string(who) + ": min_cov must be >= 1");
+    for (int64_t i = 0; i < n; ++i)
+        if (start[i] > end[i]) return pfail(p, HM_EINVAL, std::string(who) + ": interval " + std::to_string(i) + " has start > end");
+    return range_planes(p, pcov, ncov, key, plane_base, s) ? HM_OK : HM_ESTATE;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hm_region_geometry(int64_t out[2]) {
+    if (!out) return HM_EINVAL;
+    out[0] = HM_REGION_BLOCK;
+    out[1] = HM_REGION_SCAN_BLOCKS;
+    return HM_OK;
+}
+
+int hm_pileup_fetch_regions(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t plane_base, int64_t lo,
+                            int64_t hi, int64_t min_cov, const int64_t* start, const int64_t* end, int64_t n, hm_region_sum_t* out) {
+    if (!p) return HM_EINVAL;
+    RangePlanes s;
+    const int rc = region_call(p, "hm_pileup_fetch_regions", pcov, ncov, key, plane_base, lo, hi, min_cov, start, end, n, !n || out, s);
+    if (rc != HM_OK || !n) return rc;
+    std::fill(out, out + 3 * n, hm_region_sum_t{0, 0, 0, 0});
+    if (hi == lo) return HM_OK;
+    return guarded(p, [&] {
+        hipStream_t st = p->stream;
+        const size_t iv_bytes = sizeof(int64_t) * (size_t)n, out_bytes = sizeof(hm_region_sum_t) * 3 * (size_t)n;
+        p->d_rgiv.reserve(2 * iv_bytes);
+        p->d_rgout.reserve(out_bytes);
+        int64_t* iv = p->d_rgiv.as<int64_t>();
+        HIP_TRY(hipMemcpyAsync(iv, start, iv_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(iv + n, end, iv_bytes, hipMemcpyHostToDevice, st));
+        const RegionIndex ix = build_region_index(p, s, lo, hi, min_cov);
+        hipLaunchKernelGGL(region_query_kernel, dim3(grid_for(n * 64)), dim3(TPB), 0, st, ix, plane_base, iv, iv + n, n, p->d_rgout.as<int64_t>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(out, p->d_rgout.p, out_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return HM_OK;
+    });
+}
+
+int hm_pileup_fetch_metaplot(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t plane_base, int64_t lo,
+                             int64_t hi, int64_t min_cov, const int64_t* start, const int64_t* end, const int64_t* seq_start,
+                             const int64_t* seq_end, const char* strand, int64_t n, int32_t bins, int64_t flank, int32_t flank_bins,
+                             hm_metabin_t* out, int64_t* n_used) {
+    if (!p) return HM_EINVAL;
+    const char* who = "hm_pileup_fetch_metaplot";
+    if (!n_used || (n && (!seq_start || !seq_end))) return pfail(p, HM_EINVAL, std::string(who) + ": bad argument");
+    if (bins < 1 || bins > 1000 || flank < 0 || flank_bins < 0 || flank_bins > 1000 || (flank == 0) != (flank_bins == 0) ||
+        (flank_bins && flank % flank_bins))
+        return pfail(p, HM_EINVAL, std::string(who) + ": bins in [1, 1000], flank >= 0 a multiple of flank_bins in [0, 1000], both 0 or neither, expected");
+    RangePlanes s;
+    const int rc = region_call(p, who, pcov, ncov, key, plane_base, lo, hi, min_cov, start, end, n, out != nullptr, s);
+    if (rc != HM_OK) return rc;
+    const MetaGeom m{bins, flank_bins, flank};
+    const int nb = m.n_bins();
+    std::vector<MetaIv> used;
+    for (int64_t i = 0; i < n; ++i) {
+        if (seq_start[i] > start[i] || end[i] > seq_end[i])
+            return pfail(p, HM_EINVAL, std::string(who) + ": interval " + std::to_string(i) + " is not within its sequence");
+        if (end[i] - start[i] >= bins) used.push_back(MetaIv{start[i], end[i], seq_start[i], seq_end[i], strand && strand[i] == '-'});
+    }
+    *n_used = (int64_t)used.size();
+    for (int c = 0; c < 3; ++c)
+        for (int b = 0; b < nb; ++b) out[c * nb + b] = hm_metabin_t{c, b, 0, 0, 0, 0, 0};
+    for (const MetaIv& r : used)  // the widths after the sequence clamp: the same whatever the planes and the chunk
+        for (int b = 0; b < nb; ++b) {
+            int64_t x0, x1;
+            metabin_range(m, r, b, x0, x1);
+            if (x1 > x0)
+                for (int c = 0; c < 3; ++c) ++out[c * nb + b].n_regions;
+        }
+    if (used.empty() || hi == lo) return HM_OK;
+    std::vector<int64_t> tab((size_t)nb * REGION_LANES);
+    const int gr = guarded(p, [&] {
+        hipStream_t st = p->stream;
+        const size_t iv_bytes = sizeof(MetaIv) * used.size(), tab_bytes = sizeof(int64_t) * tab.size();
+        p->d_rgiv.reserve(iv_bytes);
+        p->d_rgout.reserve(tab_bytes);
+        HIP_TRY(hipMemcpyAsync(p->d_rgiv.p, used.data(), iv_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(p->d_rgout.p, 0, tab_bytes, st));
+        const RegionIndex ix = build_region_index(p, s, lo, hi, min_cov);
+        // about 4 096 workgroups in all: enough to fill the device, few enough that a bin sees few atomics
+        const int64_t waves = ((int64_t)used.size() + TPB / 64 - 1) / (TPB / 64);
+        const unsigned gy = (unsigned)std::max<int64_t>(1, std::min<int64_t>(waves, (4096 + nb - 1) / nb));
+        hipLaunchKernelGGL(metaplot_kernel, dim3((unsigned)nb, gy), dim3(TPB), 0, st, ix, plane_base, m, p->d_rgiv.as<MetaIv>(),
+                           (int64_t)used.size(), p->d_rgout.as<unsigned long long>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(tab.data(), p->d_rgout.p, tab_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return HM_OK;
+    });
+    if (gr != HM_OK) return gr;
+    for (int c = 0; c < 3; ++c)
+        for (int b = 0; b < nb; ++b) {
+            const int64_t* t = &tab[(size_t)b * REGION_LANES + 4 * (size_t)c];
+            hm_metabin_t& o = out[c * nb + b];
+            o.n_loci = t[0];
+            o.pcov = t[1];
+            o.ncov = t[2];
+            o.ppm = t[3];
+        }
+    return HM_OK;
+}
+
+int hm_region_stats(const hm_region_sum_t* w, double out[2]) {
+    if (!w || !out || w->n_loci <= 0 || w->pcov < 0 || w->ncov < 0 || w->pcov + w->ncov <= 0 || w->ppm < 0) return HM_EINVAL;
+    out[0] = 100.0 * (double)w->pcov / (double)(w->pcov + w->ncov);
+    out[1] = (double)w->ppm / (double)w->n_loci / 1e4;
+    return HM_OK;
 }
 
 }  // extern "C"

@@ -77,6 +77,14 @@ of the last count().  `pu.readpos(min_calls)` are the rows with at least min_cal
 host only, the C library's -- percent methylated and mean ML byte, `readpos_tsv(rows)` the text of <prefix>.readpos.tsv.  With
 trim=(n5, n3) the engine drops the entries in the first n5 and the last n3 bases of every read before anything sees them.
 
+Intervals and metaplots (`pileup -R bed [-C min-cov] [-J bins[:flank:flank_bins]]`): `parse_regions_bed(path, names, lengths)`
+reads the intervals (`Regions`), `pu.regions(start, end, min_cov)` sums the planes over each of them per context -- n_loci, pcov,
+ncov and ppm, the sum of the loci's own fractions in parts per million, exact integers (REGION_SUM_DTYPE, [n, 3]) -- from a
+two-level prefix index the call builds on the device, so that an interval costs the same whatever its length.
+`pu.metaplot(**regions.coords(pu.offsets), bins=..)` cuts every interval and its flanks into bins and sums the bins over the
+intervals (METABIN_DTYPE).  `region_stats(row)` -- host only, the C library's -- are the weighted and the mean percentage,
+`regions_tsv` / `metaplot_tsv` the text of <prefix>.regions.<ctx>.tsv / <prefix>.metaplot.<ctx>.tsv.
+
 Fused with the caller (`pileup -K`): `pu.add_called(read, calls)` takes the records `MethylationCaller` returned for an aligned read
 instead of parsed MM / ML -- the same effect as add() of that read carrying the calls as tags, without the tag text.
 
@@ -121,6 +129,9 @@ LINKAGE_MAX_DIST = 16384                                 # the largest `pileup -
 READPOS_DTYPE = np.dtype([("motif", "<u4"), ("end", "<u4"), ("dist", "<u4"), ("reserved", "<u4"), ("n_m", "<u8"), ("n_u", "<u8"),
                           ("sum_ml", "<u8")])                                        # hm_readpos_t, 40 bytes
 READPOS_MAX = 2048                                       # the largest `pileup -P`
+REGION_SUM_DTYPE = np.dtype([("n_loci", "<i8"), ("pcov", "<i8"), ("ncov", "<i8"), ("ppm", "<i8")])                       # hm_region_sum_t, 32 bytes
+METABIN_DTYPE = np.dtype([("motif", "<i4"), ("bin", "<i4"), ("n_regions", "<i8")] + REGION_SUM_DTYPE.descr)           # hm_metabin_t, 48 bytes
+METAPLOT_MAX_BINS = 1000                                 # the largest `pileup -J` bins (and flank_bins)
 READPOS_ENDS = ("5p", "3p", "interior")                  # hm_readpos_t.end 0, 1, 2 as <prefix>.readpos.tsv names them
 PATTERN_SPAN, PATTERN_MIN_READS = 150, 10                # `pileup -E`'s default -w and -o
 DOMAIN_AFTER_BREAK, DOMAIN_BEFORE_BREAK = 1, 2                                        # HM_DOMAIN_AFTER_BREAK, HM_DOMAIN_BEFORE_BREAK
@@ -545,6 +556,119 @@ def readpos_tsv(rows: np.ndarray) -> str:
     return "".join(text)
 
 
+def region_geometry() -> Tuple[int, int]:
+    """(HM_REGION_BLOCK, HM_REGION_SCAN_BLOCKS) of the loaded library: the loci per block of the interval index, and the blocks
+    per workgroup of its scan (host only: no GPU is needed)"""
+    g = np.zeros(2, np.int64)
+    lib().hm_region_geometry(g.ctypes.data_as(C.c_void_p))
+    return int(g[0]), int(g[1])
+
+
+class Regions:
+    """the intervals of a BED file in input order: sid (index of the sequence), start, end (positions in it, int64), name, strand
+    ('+', '-' or '.')"""
+
+    def __init__(self, sid, start, end, name, strand):
+        self.sid, self.start, self.end = (np.asarray(x, np.int64).reshape(-1) for x in (sid, start, end))
+        self.name, self.strand = list(name), list(strand)
+
+    def __len__(self):
+        return len(self.sid)
+
+    def coords(self, offsets) -> dict:
+        """global locus coordinates, as regions() and metaplot() take them: start, end, seq_start, seq_end, strand"""
+        off = np.asarray(offsets, np.int64)
+        return {"start": off[self.sid] + self.start, "end": off[self.sid] + self.end, "seq_start": off[self.sid],
+                "seq_end": off[self.sid + 1], "strand": "".join(self.strand).encode()}
+
+
+def parse_regions_bed(path: str, names: Sequence[str], lengths) -> Regions:
+    """`pileup -R`: a BED file, plain or gzip, of at least 3 tab-separated columns.  Empty lines and lines starting with `#`,
+    `track` or `browser` are skipped; the name is column 4 or `.`, the strand column 6 if it is `+` or `-`, else `.`.  ValueError
+    naming the line for fewer columns, coordinates that are no integers, an unknown sequence, start < 0, start >= end or
+    end > the sequence's length."""
+    import gzip
+    with open(path, "rb") as f:
+        gz = f.read(2) == b"\x1f\x8b"
+    sid_of = {n: i for i, n in enumerate(names)}
+    sid, start, end, name, strand = [], [], [], [], []
+    with (gzip.open(path, "rt") if gz else open(path, "r")) as f:
+        for no, line in enumerate(f, 1):
+            line = line.rstrip("\r\n")
+            if not line or line.startswith(("#", "track", "browser")):
+                continue
+            col = line.split("\t")
+            bad = lambda what: ValueError(f"{path}:{no}: {what}")  # noqa: E731
+            if len(col) < 3:
+                raise bad("fewer than 3 tab-separated columns")
+            try:
+                a, b = int(col[1]), int(col[2])
+            except ValueError:
+                raise bad("start and end must be integers") from None
+            if col[0] not in sid_of:
+                raise bad(f"unknown sequence {col[0]}")
+            if a < 0:
+                raise bad("start < 0")
+            if a >= b:
+                raise bad("start >= end")
+            if b > int(lengths[sid_of[col[0]]]):
+                raise bad(f"end {b} is past the end of {col[0]} ({int(lengths[sid_of[col[0]]])})")
+            sid.append(sid_of[col[0]])
+            start.append(a)
+            end.append(b)
+            name.append(col[3] if len(col) > 3 and col[3] else ".")
+            strand.append(col[5] if len(col) > 5 and col[5] in ("+", "-") else ".")
+    return Regions(sid, start, end, name, strand)
+
+
+def parse_metaplot(text: str) -> Tuple[int, int, int]:
+    """`pileup -J`: bins[:flank_bp:flank_bins] -> (bins, flank, flank_bins); bins in 1 .. 1000, the flank 0:0 or flank_bp >= 1 a
+    multiple of flank_bins in 1 .. 1000.  ValueError otherwise."""
+    parts = text.split(":")
+    if len(parts) not in (1, 3) or not all(t.isascii() and t.isdigit() and len(t) < 18 for t in parts):
+        raise ValueError("bins[:flank_bp:flank_bins] expected")
+    bins, flank, fb = (int(t) for t in parts + ["0", "0"][:3 - len(parts)])
+    if not 1 <= bins <= METAPLOT_MAX_BINS or fb > METAPLOT_MAX_BINS or (flank == 0) != (fb == 0) or (fb and flank % fb):
+        raise ValueError("bins in [1, 1000], flank_bp a multiple of flank_bins in [1, 1000] (or both 0) expected")
+    return bins, flank, fb
+
+
+def region_stats(row) -> Tuple[float, float]:
+    """one REGION_SUM_DTYPE row (or the four sums of a METABIN_DTYPE row) -> (weighted, mean) percent by the C library (host only:
+    no GPU is needed): 100 pcov / (pcov + ncov) and ppm / n_loci / 10^4"""
+    w = np.zeros(1, REGION_SUM_DTYPE)
+    for k in REGION_SUM_DTYPE.names:
+        w[k] = row[k]
+    out = np.zeros(2, np.float64)
+    if lib().hm_region_stats(w.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)) != 0:
+        raise HifimethError("hm_region_stats: n_loci > 0 expected")
+    return tuple(float(x) for x in out)
+
+
+def _region_columns(r) -> str:
+    st = region_stats(r) if int(r["n_loci"]) else (float("nan"), float("nan"))
+    return "%d\t%d\t%d\t%.6g\t%.6g\n" % (int(r["n_loci"]), int(r["pcov"]), int(r["ncov"]), *st)
+
+
+def regions_tsv(regions: Regions, names: Sequence[str], sums: np.ndarray) -> dict:
+    """the text of <prefix>.regions.{CpG,CHG,CHH}.tsv: the header, then chrom, start, end, name, strand, n_loci, pcov, ncov,
+    weighted, mean per interval in input order (an interval without a counted locus has no percentages: nan); sums = [n, 3]"""
+    head = "#chrom\tstart\tend\tname\tstrand\tn_loci\tpcov\tncov\tweighted\tmean\n"
+    return {CTX_NAMES[c]: head + "".join(
+        "%s\t%d\t%d\t%s\t%s\t" % (names[regions.sid[i]], regions.start[i], regions.end[i], regions.name[i], regions.strand[i])
+        + _region_columns(sums[i, c]) for i in range(len(regions))) for c in range(3)}
+
+
+def metaplot_tsv(rows: np.ndarray, n_used: int, n_skipped: int, bins: int, flank_bins: int) -> dict:
+    """the text of <prefix>.metaplot.{CpG,CHG,CHH}.tsv: `#regions used skipped`, the header, then bin, part (up, body, down),
+    n_regions, n_loci, pcov, ncov, weighted, mean per bin; rows = the 3 x (bins + 2 flank_bins) METABIN_DTYPE rows"""
+    nb = bins + 2 * flank_bins
+    head = "#regions\t%d\t%d\n#bin\tpart\tn_regions\tn_loci\tpcov\tncov\tweighted\tmean\n" % (n_used, n_skipped)
+    part = lambda b: "up" if b < flank_bins else "body" if b < flank_bins + bins else "down"  # noqa: E731
+    return {CTX_NAMES[c]: head + "".join("%d\t%s\t%d\t" % (b, part(b), int(rows[c * nb + b]["n_regions"])) + _region_columns(rows[c * nb + b])
+                                         for b in range(nb)) for c in range(3)}
+
+
 def sites_rates_tsv(sums, rates, m) -> str:
     """the text of <prefix>.sites.rates.tsv: ctx, P_c, N_c, rate, m_c (the counts are 0 when the rates were given with -e)"""
     return "".join("%s\t%d\t%d\t%s\t%d\n" % (CTX_NAMES[c], int(sums[c]), int(sums[3 + c]),
@@ -916,6 +1040,45 @@ class MethylationPileup:
         """add another engine's readpos_histograms() to this one's table (the multi-rank path)"""
         h = np.ascontiguousarray(hist, np.uint64)
         self._check(self._L.hm_pileup_add_readpos(self._h, h.ctypes.data_as(C.c_void_p), h.size))
+
+    def _range_ptrs(self, planes, partition: int):
+        """(pcov, ncov, key) of a call over a plane range: the caller's tensors, a partition's counts with the combined key, or own"""
+        if planes is not None or not partition:
+            return self._plane_ptrs(planes)
+        pc, nc = C.c_void_p(), C.c_void_p()
+        self._check(self._L.hm_pileup_partition_planes(self._h, partition, C.byref(pc), C.byref(nc)))
+        return [pc, nc, None]
+
+    def regions(self, start, end, min_cov: int = 1, lo: int = 0, hi: Optional[int] = None, planes=None, plane_base: int = 0,
+                partition: int = 0) -> np.ndarray:
+        """the sums of the intervals [start[i], end[i]) -- GLOBAL locus coordinates, Regions.coords(pu.offsets) -- per context over
+        the loci with pcov + ncov >= min_cov: REGION_SUM_DTYPE [n, 3].  [lo, hi) (plane coordinates), planes, plane_base and
+        partition as for loci(); every interval is clamped to the range, so the results of disjoint ranges add up."""
+        hi = self.n_loci if hi is None else hi
+        a, b = (np.ascontiguousarray(x, np.int64).reshape(-1) for x in (start, end))
+        assert a.size == b.size
+        out = np.zeros((a.size, 3), REGION_SUM_DTYPE)
+        self._check(self._L.hm_pileup_fetch_regions(self._h, *self._range_ptrs(planes, partition), plane_base, lo, hi, min_cov,
+                                                    a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), a.size,
+                                                    out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def metaplot(self, start, end, seq_start, seq_end, strand=None, bins: int = 20, flank: int = 0, flank_bins: int = 0,
+                 min_cov: int = 1, lo: int = 0, hi: Optional[int] = None, planes=None, plane_base: int = 0, partition: int = 0):
+        """-> (rows, n_used): METABIN_DTYPE rows [3 x (bins + 2 flank_bins)], context-major: every interval of at least `bins`
+        bases cut into `bins` body bins and, with flank > 0, flank_bins bins of flank / flank_bins bases on either side (clamped
+        to the interval's sequence [seq_start, seq_end)), numbered from upstream for strand + or . and mirrored for -, and summed
+        over the n_used intervals.  Coordinates, range and planes as for regions(); strand = bytes of +, - or . per interval."""
+        hi = self.n_loci if hi is None else hi
+        a, b, s0, s1 = (np.ascontiguousarray(x, np.int64).reshape(-1) for x in (start, end, seq_start, seq_end))
+        assert a.size == b.size == s0.size == s1.size and (strand is None or len(strand) == a.size)
+        out = np.zeros(3 * (bins + 2 * flank_bins) if bins > 0 and flank_bins >= 0 else 0, METABIN_DTYPE)
+        n_used = C.c_int64(0)
+        self._check(self._L.hm_pileup_fetch_metaplot(
+            self._h, *self._range_ptrs(planes, partition), plane_base, lo, hi, min_cov, *(x.ctypes.data_as(C.c_void_p) for x in (a, b, s0, s1)),
+            bytes(strand) if strand is not None else None, a.size, bins, flank, flank_bins,
+            out.ctypes.data_as(C.c_void_p), C.byref(n_used)))
+        return out, int(n_used.value)
 
     def bedmethyl(self, lo: int = 0, hi: Optional[int] = None, min_valid: int = 1, partition: int = 0) -> np.ndarray:
         """the reference CpGs of [lo, hi), ascending (BEDMETHYL_DTYPE), at which a read was classed and n_mod + n_canon >= min_valid

@@ -1,7 +1,7 @@
 """`hifimeth pileup` over N GPUs of one node, one process per GPU (the path's only exchange step).
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
-        -m hifimeth_amd.pileup_dist [-q mapQ] [-f identity] [-H [-A [-a min-cov] [-Q] [-G [-s max-p] [-g max-gap] [-n min-loci]]]] [-B control | -e r,r,r] [-D [-u lo:hi[,lo:hi,lo:hi]] [-x nats] [-j bp]] [-L bp [-z min-pairs]] [-P bp [-y min-calls]] [-I n5[:n3]] reference.fa mod.bam output-prefix
+        -m hifimeth_amd.pileup_dist [-q mapQ] [-f identity] [-H [-A [-a min-cov] [-Q] [-G [-s max-p] [-g max-gap] [-n min-loci]]]] [-B control | -e r,r,r] [-D [-u lo:hi[,lo:hi,lo:hi]] [-x nats] [-j bp]] [-L bp [-z min-pairs]] [-P bp [-y min-calls]] [-I n5[:n3]] [-R bed [-C min-cov] [-J bins[:flank:flank_bins]]] reference.fa mod.bam output-prefix
 
 Records are dealt to the ranks in slabs of `--slab` records (round-robin, like the `call` path).  Each rank projects its
 records and histograms them on its own GPU; then
@@ -42,6 +42,12 @@ and writes <prefix>.linkage.CpG.tsv, byte-identical to `pileup -L bp`.
 sums of a row (n_m, n_u, sum_ml) are sums over the ranks: every rank fetches all its rows (min_calls 0), the [3 (2 bp + 1), 3] int64
 table goes through one all-reduce, and rank 0 applies -y and writes <prefix>.readpos.tsv, byte-identical to `pileup -P bp`.
 -I n5[:n3]: every rank's engine drops the entries at the read ends, as `pileup -I` does.
+-R bed [-C min-cov] [-J bins[:flank:flank_bins]]: methylation of given intervals and the metaplot.  Every rank reads the same BED file
+(before the device is touched: a bad file ends all ranks alike) and queries its own chunk of the reduce-scattered planes
+(hm_pileup_fetch_regions / hm_pileup_fetch_metaplot with plane_base = the chunk's first locus: every interval and bin is clamped to
+the chunk), the integer columns go through one all-reduce each -- they are exact sums, so the parts add up to the whole -- and rank 0
+writes <prefix>.regions.<ctx>.tsv and <prefix>.metaplot.<ctx>.tsv, under -H per haplotype too, byte-identical to `pileup -R`.  The
+metaplot's n_regions depends on neither planes nor chunk: every rank computes the same value and it is not summed.
 """
 from __future__ import annotations
 
@@ -54,7 +60,7 @@ import numpy as np
 from . import dist as D
 from .bamio import is_coordinate_sorted, load_fasta, read_bam
 from .caller import HifimethError
-from .pileup import (ASM_DTYPE, CTX_NAMES, LINKAGE_DTYPE, LINKAGE_MAX_DIST, linkage_tsv, READPOS_MAX, readpos_tsv, DOMAIN_LEVELS, DOMAIN_MAX_GAP, DOMAIN_PASS_CODES, DOMAIN_PASS_SEGMENTS, DOMAIN_PASS_SUMMARY,
+from .pileup import (ASM_DTYPE, CTX_NAMES, LINKAGE_DTYPE, LINKAGE_MAX_DIST, linkage_tsv, READPOS_MAX, readpos_tsv, REGION_SUM_DTYPE, metaplot_tsv, parse_metaplot, parse_regions_bed, regions_tsv, DOMAIN_LEVELS, DOMAIN_MAX_GAP, DOMAIN_PASS_CODES, DOMAIN_PASS_SEGMENTS, DOMAIN_PASS_SUMMARY,
                      DOMAIN_PENALTY, LOCUS_DTYPE, DomainFit, MethylationPileup, allreduce_histograms, asm_qvalues, asm_summary_tsv,
                      domain_backward_carries, domain_forward_carries, domain_scores, domains_fit_tsv, locus_ranges, parse_domain_levels, parse_rates,
                      rates_from_sums, reduce_scatter_planes, reduce_scatter_sum, resolve_threshold, sites_rates_tsv, sites_table,
@@ -66,9 +72,10 @@ def run(reference: str, bam: str, prefix: str, min_mapq: int = 0, min_pi: float 
         asm_min_cov: int = 5, control: str | None = None, rates=None, asm_q: bool = False,
         asm_regions: bool = False, max_p: float = 0.01, max_gap: int = 500, min_loci: int = 3, domain_rules=None,
         domain_max_gap: int = DOMAIN_MAX_GAP, domain_fit=None, linkage: int = 0, linkage_min_pairs: int = 1, profile: int = 0,
-        profile_min_calls: int = 1, trim=(0, 0)):
+        profile_min_calls: int = 1, trim=(0, 0), regions_bed: str | None = None, region_min_cov: int = 1, metaplot=None):
     """domain_rules (-D): per context (A, B, S) of domain_scores, or None for a context that is not segmented.  domain_fit (-Y):
-    {"levels": per context (lo, hi) or None, "penalty", "max_iter"}: the levels are fitted from those and replace domain_rules"""
+    {"levels": per context (lo, hi) or None, "penalty", "max_iter"}: the levels are fitted from those and replace domain_rules.
+    regions_bed (-R), region_min_cov (-C), metaplot (-J): (bins, flank, flank_bins) or None"""
     import torch
     rank, local_rank, world = D.env_world()
     dist = D.init_process_group(backend, force=bool(os.environ.get("HM_FORCE_COLLECTIVES")))
@@ -93,6 +100,14 @@ def run(reference: str, bam: str, prefix: str, min_mapq: int = 0, min_pi: float 
         if rank == 0:
             print(f"ERROR: control sequence {control} (-B) is not in {reference}", file=log)
         return leave(1)
+    regions = None
+    if regions_bed is not None:                             # every rank reads the same file: all leave together, before the device
+        try:
+            regions = parse_regions_bed(regions_bed, [n for n, _ in genome], [len(s) for _, s in genome])
+        except (OSError, ValueError) as e:
+            if rank == 0:
+                print(f"ERROR: {e}", file=log)
+            return leave(1)
     missing = None
     n_loci = sum(len(s) for _, s in genome)
     ranges = locus_ranges(n_loci, world)
@@ -289,6 +304,29 @@ def run(reference: str, bam: str, prefix: str, min_mapq: int = 0, min_pi: float 
                 rows[k] = table[:, c]
             with open(f"{prefix}.readpos.tsv", "w") as f:
                 f.write(readpos_tsv(rows[table[:, 0] + table[:, 1] >= profile_min_calls]))
+    if regions is not None:                                 # every interval and bin clamped to this rank's chunk: the parts add up
+        xy = regions.coords(pu.offsets)
+        sets = [("", (pc, nc, key))] + [(f"hap{k + 1}.", (hp[2 * k], hp[2 * k + 1], key)) for k in range(len(hp) // 2)]
+        for tag, pl in sets:
+            sums = pu.regions(xy["start"], xy["end"], region_min_cov, 0, hi - lo, planes=pl, plane_base=base)
+            table = allreduce_i64(np.stack([sums[k] for k in REGION_SUM_DTYPE.names], axis=-1)).astype(np.int64)
+            if metaplot is not None:
+                bins, flank, flank_bins = metaplot
+                rows, n_used = pu.metaplot(**xy, bins=bins, flank=flank, flank_bins=flank_bins, min_cov=region_min_cov, lo=0, hi=hi - lo,
+                                           planes=pl, plane_base=base)
+                mtab = allreduce_i64(np.stack([rows[k] for k in REGION_SUM_DTYPE.names], axis=-1)).astype(np.int64)
+            if rank == 0:
+                for c, k in enumerate(REGION_SUM_DTYPE.names):
+                    sums[k] = table[..., c]
+                for ctx, text in regions_tsv(regions, pu.names, sums).items():
+                    with open(f"{prefix}.{tag}regions.{ctx}.tsv", "w") as f:
+                        f.write(text)
+                if metaplot is not None:
+                    for c, k in enumerate(REGION_SUM_DTYPE.names):
+                        rows[k] = mtab[..., c]                  # n_regions stays: the same on every rank
+                    for ctx, text in metaplot_tsv(rows, n_used, len(regions) - n_used, bins, flank_bins).items():
+                        with open(f"{prefix}.{tag}metaplot.{ctx}.tsv", "w") as f:
+                            f.write(text)
     if control is not None or rates is not None:
         mine, n_mine = (pc, nc, key), hi - lo               # this rank's chunk: element 0 is locus `base`
         sums = np.zeros(6, np.uint64)
@@ -371,6 +409,11 @@ def main(argv=None):
     ap.add_argument("-y", dest="profile_min_calls", type=int, default=None, help="with -P: smallest number of calls of a row that is written, >= 0 (default 1)")
     ap.add_argument("-I", dest="trim", default=None, metavar="N5[:N3]",
                     help="leave the calls in the first N5 and the last N3 bases of every read out of all outputs (one number: both ends)")
+    ap.add_argument("-R", dest="regions_bed", default=None, metavar="BED",
+                    help="methylation of the intervals of this BED file (plain or gzip) -> <prefix>.regions.<ctx>.tsv")
+    ap.add_argument("-C", dest="region_min_cov", type=int, default=None, help="with -R: smallest coverage of a locus that counts, >= 1 (default 1)")
+    ap.add_argument("-J", dest="metaplot", default=None, metavar="BINS[:FLANK_BP:FLANK_BINS]",
+                    help="with -R: the metaplot over all intervals and their flanks -> <prefix>.metaplot.<ctx>.tsv")
     ap.add_argument("reference")
     ap.add_argument("mod_bam")
     ap.add_argument("output_prefix")
@@ -416,6 +459,15 @@ def main(argv=None):
     trim = (0, 0) if bad_trim else (int(parts[0]), int(parts[-1]))
     if bad_trim or (a.profile is not None and not 1 <= a.profile <= READPOS_MAX) or (a.profile_min_calls is not None and a.profile_min_calls < 0):
         ap.error("-P must be an integer in [1, 2048], -y an integer >= 0, -I n5[:n3] with integers >= 0")
+    if a.regions_bed is None and not (a.region_min_cov is None and a.metaplot is None):
+        ap.error("-C and -J need -R")
+    metaplot = None
+    try:
+        if a.region_min_cov is not None and a.region_min_cov < 1:
+            raise ValueError
+        metaplot = None if a.metaplot is None else parse_metaplot(a.metaplot)
+    except ValueError:
+        ap.error("-C must be an integer >= 1, -J bins[:flank_bp:flank_bins] with bins in [1, 1000] and flank_bp a multiple of flank_bins in [1, 1000]")
     domain_rules = domain_fit = None
     if a.domains:
         bad = "-u takes lo:hi with 0 < lo < hi < 1 (levels a 2^24-th of a nat apart at least) or nan, once or per context; " \
@@ -436,7 +488,8 @@ def main(argv=None):
                max_gap=500 if a.max_gap is None else a.max_gap, min_loci=3 if a.min_loci is None else a.min_loci,
                domain_rules=domain_rules, domain_max_gap=DOMAIN_MAX_GAP if a.domain_max_gap is None else a.domain_max_gap,
                domain_fit=domain_fit, linkage=a.linkage or 0, linkage_min_pairs=1 if a.linkage_min_pairs is None else a.linkage_min_pairs,
-               profile=a.profile or 0, profile_min_calls=1 if a.profile_min_calls is None else a.profile_min_calls, trim=trim)
+               profile=a.profile or 0, profile_min_calls=1 if a.profile_min_calls is None else a.profile_min_calls, trim=trim,
+               regions_bed=a.regions_bed, region_min_cov=1 if a.region_min_cov is None else a.region_min_cov, metaplot=metaplot)
 
 
 if __name__ == "__main__":

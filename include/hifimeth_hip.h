@@ -716,6 +716,57 @@ int hm_pileup_add_readpos(hm_pileup_t* p, const uint64_t* hist, int64_t n);
  * mean ML byte = sum_ml / (n_m + n_u).  HM_EINVAL for n_m + n_u == 0. */
 int hm_readpos_stats(const hm_readpos_t* w, double out[2]);
 
+/* ---- methylation of given intervals, metaplots (`pileup -R`, `pileup -J`) --------------------------------------
+ * Sums of the planes over intervals the caller names: promoters, CpG islands, windows of a tiling, genes with their flanks.
+ * A LOCUS g with cov = pcov + ncov (64 bits) COUNTS when cov >= min_cov (>= 1).  A counted locus of context c = key & 3 adds to its
+ * context: n_loci += 1, pcov += pcov, ncov += ncov, ppm += (2 000 000 pcov + cov) / (2 cov) in integer division: the locus' fraction
+ * in parts per million, rounded half up.  An interval's sum is that of the loci in [start, end).  All of it exact integers, so the
+ * sums over disjoint plane chunks add up to the whole's and no order of summation matters.
+ * HOW: a call builds a two-level index of its range [lo, hi): the twelve sums of every block of HM_REGION_BLOCK loci (block b =
+ * loci lo + b HM_REGION_BLOCK ...), then their inclusive scan over the blocks, a scan of as many workgroups as there are
+ * HM_REGION_SCAN_BLOCKS blocks (12 x 8 B per block in HBM, allocated by the first call, freed with the engine).  An interval's sum is
+ * the scan's difference over the blocks inside it plus the loci of its two partial blocks, summed by one wavefront: its cost does
+ * not depend on its length, and overlapping, nested or unsorted intervals cost what disjoint ones do.
+ * Without a call nothing is allocated or launched.  Not here: tests between intervals or haplotypes, bigWig output, a tiling made
+ * by the tool. */
+#ifndef HM_REGION_BLOCK
+#define HM_REGION_BLOCK 4096      /* a power of two >= 256: chosen by measurement, DESIGN.md section 10 */
+#endif
+#define HM_REGION_SCAN_BLOCKS 1024 /* blocks per workgroup of the scan: a range of more loci than the product takes several */
+typedef struct {            /* one (interval, context); 32 bytes */
+    int64_t n_loci, pcov, ncov, ppm;
+} hm_region_sum_t;
+/* the two constants the library was built with: out[0] = HM_REGION_BLOCK, out[1] = HM_REGION_SCAN_BLOCKS */
+int hm_region_geometry(int64_t out[2]);
+/* out[i * 3 + c] = the sum of interval i = [start[i], end[i]) in context c.  start / end are GLOBAL locus coordinates (sequence
+ * offset + position, as gpos of the row outputs); planes NULL = the engine's own, else DEVICE pointers whose element 0 is locus
+ * `plane_base`, of which [lo, hi) is looked at, as in hm_pileup_fetch_loci.  Every interval is clamped to [plane_base + lo,
+ * plane_base + hi): the results of disjoint chunks add up to the whole's.  n == 0 is allowed.  HM_ESTATE without planes (as
+ * hm_pileup_fetch_loci), HM_EINVAL for a bad range, min_cov < 1 or start[i] > end[i]. */
+int hm_pileup_fetch_regions(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t plane_base, int64_t lo,
+                            int64_t hi, int64_t min_cov, const int64_t* start, const int64_t* end, int64_t n, hm_region_sum_t* out);
+/* THE METAPLOT: every interval cut into the same number of bins, the bins of all intervals summed.  For an interval [s, e) on a
+ * sequence [S0, S1) (global coordinates): body edges s + floor(j (e - s) / bins), j = 0 .. bins; with w = flank / flank_bins,
+ * upstream edges s - flank + j w and downstream edges e + j w, j = 0 .. flank_bins; every edge clamped to [S0, S1], so a flank never
+ * reads the neighbouring sequence of the concatenated planes.  Bins are numbered upstream, body, downstream for strand '+' (or
+ * anything but '-'; strand NULL: all '+') and mirrored for '-'.  Intervals with e - s < bins are left out; *n_used counts the rest.
+ * out[c * n_bins + b], n_bins = bins + 2 flank_bins: the sums of bin b in context c over the used intervals, each bin clamped to
+ * [plane_base + lo, plane_base + hi) like an interval above; n_regions = the used intervals whose bin b has a non-zero width after
+ * the SEQUENCE clamp: it depends on neither planes nor chunk, so disjoint chunks add up in every field but n_regions, which they
+ * share.  HM_EINVAL: bins outside [1, 1000], flank < 0, flank_bins outside [0, 1000], flank_bins == 0 with flank != 0 or the
+ * reverse, flank % flank_bins != 0, s > e, S0 > S1, or an interval outside its sequence; the rest as hm_pileup_fetch_regions. */
+typedef struct {            /* one (context, bin) = one row of <prefix>.metaplot.<ctx>.tsv; 48 bytes */
+    int32_t motif, bin;
+    int64_t n_regions, n_loci, pcov, ncov, ppm;
+} hm_metabin_t;
+int hm_pileup_fetch_metaplot(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t plane_base, int64_t lo,
+                             int64_t hi, int64_t min_cov, const int64_t* start, const int64_t* end, const int64_t* seq_start,
+                             const int64_t* seq_end, const char* strand, int64_t n, int32_t bins, int64_t flank, int32_t flank_bins,
+                             hm_metabin_t* out, int64_t* n_used);
+/* Host only, fp64: the one implementation behind every front end.  out[0] weighted = 100 pcov / (pcov + ncov), out[1] mean =
+ * ppm / n_loci / 10^4, the mean of the loci's own percentages.  HM_EINVAL for n_loci == 0 (or a negative member). */
+int hm_region_stats(const hm_region_sum_t* w, double out[2]);
+
 #ifdef __cplusplus
 }
 #endif

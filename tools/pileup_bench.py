@@ -128,6 +128,9 @@ def main():
                     help="time what the within-read co-methylation by distance up to D bases adds (pileup -L D, min_pairs 1)")
     ap.add_argument("--readpos", type=int, default=0, metavar="D",
                     help="time what the methylation by position in the read adds, D bases from either end resolved (pileup -P D, min_calls 1)")
+    ap.add_argument("--regions", type=int, default=0, metavar="N",
+                    help="time the interval sums and the metaplot (pileup -R / -J 20:2000:10): N gene-like intervals of 0.5 - 20 kb, "
+                         "and a tiling of the reference in 1 kb windows")
     ap.add_argument("--bedmethyl", action="store_true", help="time what the per-CpG depth classes add (pileup -M, min_valid 1)")
     ap.add_argument("--digest", action="store_true", help="add a sha256 of the records, the loci and the rows of the timed options")
     ap.add_argument("--cpu-baseline", action="store_true",
@@ -456,6 +459,46 @@ def main():
                 ctx_rows == len(loci) == sum(int(r["n_loci"].sum()) for r, _n in found)
                 and sum(int(r["pcov"].sum()) for r, _n in found) == int(loci["pcov"].astype(np.int64).sum())
                 and sum(int(r["ncov"].sum()) for r, _n in found) == int(loci["ncov"].astype(np.int64).sum()))
+    if a.regions:
+        from hifimeth_amd.pileup import locate, region_geometry
+        rng_iv = np.random.default_rng(17)
+        length = np.exp(rng_iv.uniform(np.log(500), np.log(20000), a.regions)).astype(np.int64)
+        start = rng_iv.integers(0, max(G - 20000, 1), a.regions)
+        sid, _ = locate(pu.offsets, start)
+        s0, s1 = pu.offsets[sid], pu.offsets[sid + 1]
+        genes = dict(start=start, end=np.minimum(start + length, s1), seq_start=s0, seq_end=s1, strand=bytes(rng_iv.choice([43, 45], a.regions).astype(np.uint8)))
+        tiles = np.concatenate([np.arange(pu.offsets[k], pu.offsets[k + 1], 1000) for k in range(len(pu.offsets) - 1)])
+        sid, _ = locate(pu.offsets, tiles)
+        tile_end = np.minimum(tiles + 1000, pu.offsets[sid + 1])
+        legs = {"genes": lambda: pu.regions(genes["start"], genes["end"]),
+                "metaplot": lambda: pu.metaplot(**genes, bins=20, flank=2000, flank_bins=10),
+                "tiles": lambda: pu.regions(tiles, tile_end),
+                "index": lambda: pu.regions(tiles[:1], tile_end[:1])}              # one interval: the index build and the fixed costs
+        times = {}
+        for name, leg in legs.items():
+            leg()                                  # warm-up: the buffers, the code objects
+            t = []
+            for _ in range(max(a.repeat, 5)):
+                t0 = time.perf_counter()
+                leg()
+                t.append(time.perf_counter() - t0)
+            times[name] = t
+        t_pass = t_project / a.repeat + t_count + t_loci
+        best = {k: min(v) for k, v in times.items()}
+        out.update(regions_block=region_geometry()[0], regions_intervals=a.regions, regions_tiles=int(len(tiles)),
+                   regions_s={k: [round(x, 5) for x in v] for k, v in times.items()},
+                   regions_index_bytes=int(12 * G), regions_index_bytes_per_s=round(12 * G / best["index"]),
+                   regions_ns_per_interval={"genes": round(1e9 * max(best["genes"] - best["index"], 0) / a.regions, 1),
+                                            "metaplot": round(1e9 * max(best["metaplot"] - best["index"], 0) / a.regions, 1),
+                                            "tiles": round(1e9 * max(best["tiles"] - best["index"], 0) / len(tiles), 1)},
+                   regions_share_of_pass={k: round(v / (t_pass + v), 4) for k, v in best.items()})
+        if a.check:                                # the tiles partition the reference: their sums are the covered loci's
+            t_sum = pu.regions(tiles, tile_end)
+            out["check_regions_tiles_hold_the_loci"] = bool(
+                int(t_sum["n_loci"].sum()) == len(loci) and int(t_sum["pcov"].sum()) == int(loci["pcov"].astype(np.int64).sum())
+                and int(t_sum["ncov"].sum()) == int(loci["ncov"].astype(np.int64).sum()))
+        if a.digest:
+            digest["regions"] = [sha(pu.regions(genes["start"], genes["end"])), sha(pu.metaplot(**genes, bins=20, flank=2000, flank_bins=10)[0])]
     if a.check:                                    # every pass (and the warm-up) adds the same records
         total = int((loci["pcov"].astype(np.int64) + loci["ncov"]).sum())
         out["check_total_records"] = total == recs_per_pass * (a.repeat + 1)
