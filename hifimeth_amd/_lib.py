@@ -157,6 +157,9 @@ def lib():
         "hm_pileup_fetch_metaplot": (C.c_int, [vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, i64, i32, i64, i32, vp,
                                                C.POINTER(i64)]),
         "hm_region_stats": (C.c_int, [vp, vp]),
+        "hm_context_geometry": (C.c_int, [vp]),
+        "hm_pileup_fetch_context": (i64, [vp, vp, vp, vp, i64, i64, i64, i64, i32, vp, i64]),
+        "hm_pileup_fetch_context_path": (i64, [vp, vp, vp, vp, i64, i64, i64, i64, i32, i32, vp, i64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

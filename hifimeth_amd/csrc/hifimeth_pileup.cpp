@@ -37,6 +37,8 @@
 // -R bed (ours): also <prefix>.regions.<ctx>.tsv, the methylation of each interval of the BED file (loci with coverage >= -C), and with
 // -J bins[:flank:flank_bins] <prefix>.metaplot.<ctx>.tsv, the profile across all intervals and their flanks (hm_pileup_fetch_regions,
 // hm_pileup_fetch_metaplot).  The file is read and checked before the engine exists.
+// -S flank (ours): also <prefix>.context.<ctx>.tsv, the methylation by the k = 3 + 2 flank bases around the called cytosine, read on
+// its strand (loci with coverage >= -O; hm_pileup_fetch_context).
 // -K (ours): the input is an aligned BAM that still carries the kinetics tags (pbmm2 keeps fi / fp / ri / rp): the reads are called
 // on the fly by the call engine and their calls go straight to the pileup engine (hm_pileup_submit_read_calls) -- the files
 // `call` followed by `pileup` writes, without the mod-BAM between the two.
@@ -135,6 +137,9 @@ struct PileupOptions {
     int meta_bins = 0, meta_flank_bins = 0;  // -J bins[:flank:flank_bins] -> <prefix>.metaplot.<ctx>.tsv
     long long meta_flank = 0;
     bool interval_option_given = false, interval_option_bad = false;  // -C or -J; either with a value out of range
+    int context_flank = -1;            // -S: 0 .. 3 -> <prefix>.context.<ctx>.tsv by the 3 + 2 flank bases around the cytosine; -1: off
+    long long context_min_cov = 1;     // -O: smallest pcov + ncov of a locus that counts under -S
+    bool context_option_given = false, context_option_bad = false;  // -O; -S or -O with a value out of range
     // -K: call on the fly; the options below are `call`'s (hifimeth_call.cpp), same meaning and defaults
     bool kinetics = false;
     bool call_option_given = false;  // any of -m -c -l -p -T: a usage error without -K
@@ -227,6 +232,12 @@ void pileup_usage(const char* exe) {
             "    end.  Bins run from upstream to downstream, mirrored for intervals on the - strand, and are summed over the intervals.  Writes\n"
             "    <prefix>.metaplot.<ctx>.tsv (with -H per haplotype too): `#regions used skipped`, a header line, then per bin bin, part (up,\n"
             "    body, down), n_regions, n_loci, pcov, ncov, weighted, mean\n    Default flank: 0:0\n"
+            "  -S <flank>\n    Methylation by sequence context: flank in [0, 3] bases on either side of the three-base context, k = 3 + 2 flank\n"
+            "    (3, 5, 7 or 9), read on the strand of the called cytosine.  Writes <prefix>.context.<ctx>.tsv (with -H also\n"
+            "    <prefix>.hap1. and <prefix>.hap2.context.<ctx>.tsv): a header line, then per k-mer with a counted locus, in k-mer order,\n"
+            "    context, n_loci, pcov, ncov, weighted = 100 pcov / (pcov + ncov) and mean, the mean of the loci's own percentages; a last\n"
+            "    row `other` holds the loci whose window leaves their sequence or holds a base outside ACGT\n"
+            "  -O <int>\n    With -S: smallest coverage (pcov + ncov) of a locus that counts, >= 1\n    Default: 1\n"
             "  -K\n    The input is an aligned BAM that carries the kinetics tags fi / fp / ri / rp instead of MM / ML: call 5mC on the\n"
             "    fly and pile the calls up directly.  For equal -c -l -p -T -q -f the output files are byte-identical to those of\n"
             "    `%s call` on that BAM followed by `%s pileup` on its output; no mod-BAM is written.  (Give -T explicitly\n"
@@ -1191,6 +1202,32 @@ bool write_intervals(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, c
     return true;
 }
 
+// <prefix>.<tag>context.<ctx>.tsv from one set of planes (NULL: the engine's own).  false on an engine error (recorded) or a file
+// error (reported).
+bool write_context(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, const std::string& tag, const void* const planes[3]) {
+    int64_t total = 0;
+    for (const int64_t len : fa.length) total += len;
+    const int k = 3 + 2 * o.context_flank;
+    const int64_t rows = (int64_t(1) << (2 * k)) + 1;
+    std::vector<hm_region_sum_t> tab(3 * (size_t)rows);
+    if (hm_pileup_fetch_context(pe, planes[0], planes[1], planes[2], 0, 0, total, o.context_min_cov, o.context_flank, tab.data(), 3 * rows) != 3 * rows)
+        return false;
+    CtxFiles out;
+    if (!out.open(o.prefix, tag + "context.", ".tsv")) return false;
+    std::string kmer((size_t)k, 'A');
+    for (int c = 0; c < 3; ++c) {
+        fprintf(out.f[c], "#context\tn_loci\tpcov\tncov\tweighted\tmean\n");
+        for (int64_t code = 0; code < rows; ++code) {
+            const hm_region_sum_t& r = tab[(size_t)c * rows + code];
+            if (r.n_loci <= 0) continue;
+            for (int j = 0; j < k; ++j) kmer[(size_t)j] = "ACGT"[(code >> (2 * (k - 1 - j))) & 3];
+            fprintf(out.f[c], "%s\t", code == rows - 1 ? "other" : kmer.c_str());
+            print_region_columns(out.f[c], r);
+        }
+    }
+    return true;
+}
+
 // -I: n5[:n3], integers >= 0, one number for both ends; false unless the whole text parses
 bool parse_trim(const char* text, long long& n5, long long& n3) {
     char* end = nullptr;
@@ -1677,6 +1714,17 @@ int cmd_pileup(int argc, char** argv) {
             o.interval_option_given = true;
             if (!parse_metaplot(argv[++i], o.meta_bins, o.meta_flank, o.meta_flank_bins)) o.interval_option_bad = true;
         }
+        else if (a == "-S" || a == "-O") {  // the whole value must parse
+            const bool flank = a == "-S";
+            if (!flank) o.context_option_given = true;
+            const char* v = argv[++i];
+            char* end = nullptr;
+            errno = 0;
+            const long long x = strtoll(v, &end, 10);
+            if (end == v || *end || errno || (flank ? x < 0 || x > 3 : x < 1)) o.context_option_bad = true;
+            else if (flank) o.context_flank = (int)x;
+            else o.context_min_cov = x;
+        }
         else if (a == "-v") {  // the whole value must parse
             o.bedmethyl_option_given = true;
             const char* v = argv[++i];
@@ -1753,6 +1801,9 @@ int cmd_pileup(int argc, char** argv) {
                                 : o.interval_option_bad ? "-C must be an integer >= 1, -J bins[:flank_bp:flank_bins] with bins in [1, 1000] and flank_bp a "
                                                           "multiple of flank_bins in [1, 1000]" : nullptr;
     if (bad_intervals) { fprintf(stderr, "ERROR: %s\n", bad_intervals); pileup_usage(argv[0]); return EXIT_FAILURE; }
+    const char* bad_context = o.context_option_bad ? "-S must be an integer in [0, 3], -O an integer >= 1"
+                              : o.context_option_given && o.context_flank < 0 ? "-O needs -S" : nullptr;
+    if (bad_context) { fprintf(stderr, "ERROR: %s\n", bad_context); pileup_usage(argv[0]); return EXIT_FAILURE; }
     const bool sites = !o.control.empty() || o.rates_given;
     if (o.kinetics && o.model_dir.empty()) o.model_dir = exe_dir() + "/../weights";
     o.ref = argv[i];
@@ -1799,6 +1850,9 @@ int cmd_pileup(int argc, char** argv) {
             fprintf(stderr, "metaplot: %d bins per interval, flanks of %lld bases in %d bins -> %s.metaplot.*\n", o.meta_bins, o.meta_flank,
                     o.meta_flank_bins, o.prefix.c_str());
     }
+    if (o.context_flank >= 0)
+        fprintf(stderr, "context: loci by the %d bases around the cytosine, coverage >= %lld -> %s.context.*\n", 3 + 2 * o.context_flank, o.context_min_cov,
+                o.prefix.c_str());
     if (o.trim5 || o.trim3) fprintf(stderr, "trim: calls in the first %lld and the last %lld bases of a read are left out\n", o.trim5, o.trim3);
     if (o.kinetics)
         fprintf(stderr, "kinetics: called on the fly (models %s, contexts%s%s%s, min read length %d, precision %d, trunk %s)\n", o.model_dir.c_str(),
@@ -2000,6 +2054,8 @@ int cmd_pileup(int argc, char** argv) {
     if (o.profile && !write_readpos(pe, o)) return die("readpos");
     for (size_t t = 0; !o.intervals.empty() && t < tags.size(); ++t)
         if (!write_intervals(pe, fa, o, intervals, tags[t], &planes[3 * t])) return die("regions");
+    for (size_t t = 0; o.context_flank >= 0 && t < tags.size(); ++t)
+        if (!write_context(pe, fa, o, tags[t], &planes[3 * t])) return die("context");
     if (sites) {
         const int rc = write_sites(pe, fa, o, control_sid, o.threads);
         if (rc < 0) return die("sites");

@@ -1888,6 +1888,96 @@ __global__ __launch_bounds__(TPB) void metaplot_kernel(RegionIndex ix, int64_t p
     }
 }
 
+// ---- methylation by the k-mer around the cytosine (`pileup -S`; include/hifimeth_hip.h has the definition) ----------------------
+// tab[((c * (K + 1) + row) * 4 + q]: context c, row = the k-mer's code or K for `other`, q = n_loci, pcov, ncov, ppm -- three
+// tables of K + 1 hm_region_sum_t as one array of 64-bit counters.  The kernel streams pcov / ncov; only a locus with a count looks
+// further: region_add decides whether it counts and what it adds, the reference decides the row.
+constexpr int CX_THREADS = 1024;  // of a workgroup: the loci it takes side by side (HM_CONTEXT_SPAN)
+constexpr int CX_UNROLL = 8;      // loci per thread whose counters are loaded before any of them is looked at
+static_assert(CX_THREADS == HM_CONTEXT_SPAN, "the header names the workgroup's span");
+__host__ __device__ constexpr int context_k(int f) { return 3 + 2 * f; }
+__host__ __device__ constexpr int64_t context_rows(int f) { return (int64_t(1) << (2 * context_k(f))) + 1; }  // K + 1
+__host__ __device__ constexpr int64_t context_counters(int f) { return 3 * context_rows(f) * 4; }
+static_assert(context_counters(HM_CONTEXT_LDS_FLANK) * 8 <= 160 * 1024, "the workgroup-private table must fit the CU's LDS");
+
+struct ContextRef {
+    const char* ref;         // the concatenated reference
+    const int64_t* seq_off;  // n_seqs + 1
+    int n_seqs;
+};
+
+// the row of locus g: the code of the k bases around the called cytosine, read on the cytosine's strand, or K
+template <int F>
+__device__ __forceinline__ uint32_t context_row(const ContextRef& r, int64_t g) {
+    constexpr int k = context_k(F);
+    constexpr uint32_t other = 1u << (2 * k);
+    const char c = r.ref[g];
+    if (c != 'C' && c != 'G') return other;
+    const bool fwd = c == 'C';
+    const int64_t a = fwd ? g - F : g - 2 - F, b = a + k;
+    // a lies in the sequence that ends at seq_end_of(a); the window is inside one sequence iff it ends there or before, and then
+    // that sequence is g's
+    if (a < 0 || b > seq_end_of(r.seq_off, r.n_seqs, a)) return other;
+    uint32_t code = 0;
+#pragma unroll
+    for (int j = 0; j < k; ++j) {
+        const char x = r.ref[fwd ? a + j : b - 1 - j];
+        const uint32_t v = x == 'A' ? 0u : x == 'C' ? 1u : x == 'G' ? 2u : x == 'T' ? 3u : 4u;
+        if (v > 3u) return other;
+        code = (code << 2) | (fwd ? v : 3u - v);
+    }
+    return code;
+}
+
+// plane element i (locus plane_base + i), which has a count, into the table t (LDS or global)
+template <int F>
+__device__ __forceinline__ void context_locus(const RangePlanes& s, const ContextRef& r, int64_t plane_base, int64_t min_cov, int64_t i,
+                                              unsigned long long* t) {
+    RegionAcc a{};
+    region_add(s, min_cov, i, a);
+    if (!(a.v[0] | a.v[4] | a.v[8])) return;  // below min_cov, or a key of no context
+    const uint32_t row = context_row<F>(r, plane_base + i);
+#pragma unroll
+    for (int m = 0; m < 3; ++m)
+        if (a.v[4 * m]) {
+            unsigned long long* q = t + ((int64_t)m * context_rows(F) + row) * 4;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) atomicAdd(q + k, (unsigned long long)a.v[4 * m + k]);
+        }
+}
+
+// tab += the table of [lo, hi): a grid stride of CX_THREADS loci per workgroup, CX_UNROLL strides in flight.  LDS: the workgroup
+// adds into a table of its own and ends with one global atomic per non-zero counter, as hist_flush; else every add is a global
+// 64-bit atomic.  Integers: exact in any order.
+template <int F, bool LDS>
+__global__ __launch_bounds__(CX_THREADS) void context_kernel(RangePlanes s, ContextRef r, int64_t plane_base, int64_t lo, int64_t hi,
+                                                              int64_t min_cov, unsigned long long* __restrict__ tab) {
+    constexpr int N = LDS ? (int)context_counters(F) : 1;
+    __shared__ unsigned long long h[N];
+    unsigned long long* t = LDS ? h : tab;
+    if constexpr (LDS) {
+        for (int j = threadIdx.x; j < N; j += CX_THREADS) h[j] = 0ull;
+        __syncthreads();
+    }
+    const int64_t stride = (int64_t)gridDim.x * CX_THREADS;
+    for (int64_t i0 = lo + (int64_t)blockIdx.x * CX_THREADS + threadIdx.x; i0 < hi; i0 += stride * CX_UNROLL) {
+        int32_t any[CX_UNROLL];
+#pragma unroll
+        for (int u = 0; u < CX_UNROLL; ++u) {
+            const int64_t i = i0 + u * stride;
+            any[u] = i < hi ? (s.pc[i] | s.nc[i]) : 0;
+        }
+#pragma unroll
+        for (int u = 0; u < CX_UNROLL; ++u)
+            if (any[u]) context_locus<F>(s, r, plane_base, min_cov, i0 + u * stride, t);
+    }
+    if constexpr (LDS) {
+        __syncthreads();
+        for (int j = threadIdx.x; j < N; j += CX_THREADS)
+            if (h[j]) atomicAdd(&tab[j], h[j]);
+    }
+}
+
 }  // namespace
 
 // ================================================ host ==========================================================
@@ -1964,6 +2054,10 @@ struct hm_pileup {
     // `pileup -R / -J`, allocated by the first call that needs them: the index of the range in hand (96 B per HM_REGION_BLOCK loci),
     // the caller's intervals, and the sums per interval or the metaplot's table
     DevBuf d_rgidx{EXACT}, d_rgiv{HALF}, d_rgout{HALF};
+    // `pileup -S`, allocated by the first hm_pileup_fetch_context: the table of the flank in hand (6 KB at flank 0, 25 MB at 3),
+    // the sequence starts, and the device's CU count (0: not asked yet)
+    DevBuf d_cxtab{EXACT}, d_cxoff{EXACT};
+    int n_cus = 0;
     uint32_t thr_packed = 0;   // the three thresholds of the last hm_pileup_count
     bool counted = false;     // hm_pileup_count has run since hm_pileup_set_reference: what the -E, -M and -L fetches wait for
     int64_t n_recs = 0;
@@ -3585,6 +3679,95 @@ int hm_region_stats(const hm_region_sum_t* w, double out[2]) {
     out[0] = 100.0 * (double)w->pcov / (double)(w->pcov + w->ncov);
     out[1] = (double)w->ppm / (double)w->n_loci / 1e4;
     return HM_OK;
+}
+
+}  // extern "C"
+
+// ---- `pileup -S` ------------------------------------------------------------------------------------------------------------------
+namespace {
+
+template <int F>
+void launch_context(hm_pileup* p, bool lds, unsigned grid, const RangePlanes& s, const ContextRef& r, int64_t plane_base, int64_t lo,
+                    int64_t hi, int64_t min_cov, unsigned long long* tab) {
+    if constexpr (F <= HM_CONTEXT_LDS_MAX_FLANK) {
+        if (lds) {
+            hipLaunchKernelGGL((context_kernel<F, true>), dim3(grid), dim3(CX_THREADS), 0, p->stream, s, r, plane_base, lo, hi, min_cov, tab);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((context_kernel<F, false>), dim3(grid), dim3(CX_THREADS), 0, p->stream, s, r, plane_base, lo, hi, min_cov, tab);
+}
+
+// both entry points; path: HM_CONTEXT_PATH_AUTO, _LDS or _GLOBAL
+int64_t fetch_context(hm_pileup* p, const void* pcov, const void* ncov, const void* key, int64_t plane_base, int64_t lo, int64_t hi,
+                      int64_t min_cov, int32_t flank, int32_t path, hm_region_sum_t* out, int64_t cap) {
+    if (!p) return HM_EINVAL;
+    const std::string who = "hm_pileup_fetch_context";
+    if (p->seq_off.empty()) return pfail(p, HM_ESTATE, who + " before hm_pileup_set_reference");
+    if (flank < 0 || flank > 3) return pfail(p, HM_EINVAL, who + ": flank must be 0, 1, 2 or 3");
+    if (min_cov < 1) return pfail(p, HM_EINVAL, who + ": min_cov must be >= 1");
+    if (lo < 0 || hi < lo) return pfail(p, HM_EINVAL, who + ": bad range");
+    if ((!pcov || !ncov || !key) && (pcov || ncov || key)) return pfail(p, HM_EINVAL, who + ": pcov, ncov and key must be all NULL or none");
+    if (path != HM_CONTEXT_PATH_AUTO && path != HM_CONTEXT_PATH_GLOBAL && !(path == HM_CONTEXT_PATH_LDS && flank <= HM_CONTEXT_LDS_MAX_FLANK))
+        return pfail(p, HM_EINVAL, who + ": no such accumulation path for this flank");
+    RangePlanes s;
+    if (!range_planes(p, pcov, ncov, key, plane_base, s)) return HM_ESTATE;
+    if (plane_base < 0 || plane_base > p->seq_off.back() || hi > p->seq_off.back() - plane_base)
+        return pfail(p, HM_EINVAL, who + ": range past the reference");
+    const int64_t n = 3 * context_rows(flank);
+    if (!out || cap < n) return n;
+    std::fill(out, out + n, hm_region_sum_t{0, 0, 0, 0});
+    if (hi == lo) return n;
+    const bool lds = path == HM_CONTEXT_PATH_AUTO ? flank <= HM_CONTEXT_LDS_FLANK : path == HM_CONTEXT_PATH_LDS;
+    return guarded(p, [&]() -> int64_t {
+        hipStream_t st = p->stream;
+        const size_t bytes = sizeof(hm_region_sum_t) * (size_t)n;
+        p->d_cxtab.reserve(bytes);
+        p->d_cxoff.reserve(8 * p->seq_off.size());
+        HIP_TRY(hipMemcpyAsync(p->d_cxoff.p, p->seq_off.data(), 8 * p->seq_off.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(p->d_cxtab.p, 0, bytes, st));
+        if (!p->n_cus) {
+            int cus = 0;
+            HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device));
+            p->n_cus = cus > 0 ? cus : 256;
+        }
+        // one workgroup per CU: the LDS table at flank 1 leaves room for no second one, and the loads in flight do not need one
+        const unsigned grid = (unsigned)std::min<int64_t>((hi - lo + CX_THREADS - 1) / CX_THREADS, p->n_cus);
+        const ContextRef r{p->d_ref.as<char>(), p->d_cxoff.as<int64_t>(), (int)p->seq_off.size() - 1};
+        unsigned long long* tab = p->d_cxtab.as<unsigned long long>();
+        switch (flank) {
+            case 0: launch_context<0>(p, lds, grid, s, r, plane_base, lo, hi, min_cov, tab); break;
+            case 1: launch_context<1>(p, lds, grid, s, r, plane_base, lo, hi, min_cov, tab); break;
+            case 2: launch_context<2>(p, lds, grid, s, r, plane_base, lo, hi, min_cov, tab); break;
+            default: launch_context<3>(p, lds, grid, s, r, plane_base, lo, hi, min_cov, tab); break;
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(out, p->d_cxtab.p, bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return n;
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int hm_context_geometry(int64_t out[3]) {
+    if (!out) return HM_EINVAL;
+    out[0] = HM_CONTEXT_SPAN;
+    out[1] = HM_CONTEXT_LDS_FLANK;
+    out[2] = HM_CONTEXT_LDS_MAX_FLANK;
+    return HM_OK;
+}
+
+int64_t hm_pileup_fetch_context(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t plane_base, int64_t lo,
+                                int64_t hi, int64_t min_cov, int32_t flank, hm_region_sum_t* out, int64_t cap) {
+    return fetch_context(p, pcov, ncov, key, plane_base, lo, hi, min_cov, flank, HM_CONTEXT_PATH_AUTO, out, cap);
+}
+
+int64_t hm_pileup_fetch_context_path(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t plane_base, int64_t lo,
+                                     int64_t hi, int64_t min_cov, int32_t flank, int32_t path, hm_region_sum_t* out, int64_t cap) {
+    return fetch_context(p, pcov, ncov, key, plane_base, lo, hi, min_cov, flank, path, out, cap);
 }
 
 }  // extern "C"

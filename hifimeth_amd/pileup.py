@@ -85,6 +85,12 @@ two-level prefix index the call builds on the device, so that an interval costs 
 intervals (METABIN_DTYPE).  `region_stats(row)` -- host only, the C library's -- are the weighted and the mean percentage,
 `regions_tsv` / `metaplot_tsv` the text of <prefix>.regions.<ctx>.tsv / <prefix>.metaplot.<ctx>.tsv.
 
+By sequence context (`pileup -S flank [-O min-cov]`): `pu.context(flank, min_cov)` sums the loci per context and per k-mer around the
+called cytosine, k = 3 + 2 flank, read on the cytosine's strand -- int64 [3, 4^k + 1, 4] of (n_loci, pcov, ncov, ppm), the last row
+`other` (no C / G at the locus, a window that leaves its sequence, a base outside ACGT).  `context_kmer(code, k)` /
+`context_code(kmer)` name the rows, `context_tsv(table, flank)` is the text of <prefix>.context.<ctx>.tsv, with the percentages
+of `region_stats`.
+
 Fused with the caller (`pileup -K`): `pu.add_called(read, calls)` takes the records `MethylationCaller` returned for an aligned read
 instead of parsed MM / ML -- the same effect as add() of that read carrying the calls as tags, without the tag text.
 
@@ -132,6 +138,8 @@ READPOS_MAX = 2048                                       # the largest `pileup -
 REGION_SUM_DTYPE = np.dtype([("n_loci", "<i8"), ("pcov", "<i8"), ("ncov", "<i8"), ("ppm", "<i8")])                       # hm_region_sum_t, 32 bytes
 METABIN_DTYPE = np.dtype([("motif", "<i4"), ("bin", "<i4"), ("n_regions", "<i8")] + REGION_SUM_DTYPE.descr)           # hm_metabin_t, 48 bytes
 METAPLOT_MAX_BINS = 1000                                 # the largest `pileup -J` bins (and flank_bins)
+CONTEXT_MAX_FLANK = 3                                    # the largest `pileup -S`: k = 9
+CONTEXT_PATH_AUTO, CONTEXT_PATH_LDS, CONTEXT_PATH_GLOBAL = -1, 0, 1                   # HM_CONTEXT_PATH_*
 READPOS_ENDS = ("5p", "3p", "interior")                  # hm_readpos_t.end 0, 1, 2 as <prefix>.readpos.tsv names them
 PATTERN_SPAN, PATTERN_MIN_READS = 150, 10                # `pileup -E`'s default -w and -o
 DOMAIN_AFTER_BREAK, DOMAIN_BEFORE_BREAK = 1, 2                                        # HM_DOMAIN_AFTER_BREAK, HM_DOMAIN_BEFORE_BREAK
@@ -669,6 +677,46 @@ def metaplot_tsv(rows: np.ndarray, n_used: int, n_skipped: int, bins: int, flank
                                          for b in range(nb)) for c in range(3)}
 
 
+def context_geometry() -> Tuple[int, int, int]:
+    """(HM_CONTEXT_SPAN, HM_CONTEXT_LDS_FLANK, HM_CONTEXT_LDS_MAX_FLANK) of the loaded library: the loci a workgroup of the
+    k-mer kernel takes side by side, the largest flank that takes the LDS path, and the largest that could (host only)"""
+    g = np.zeros(3, np.int64)
+    lib().hm_context_geometry(g.ctypes.data_as(C.c_void_p))
+    return int(g[0]), int(g[1]), int(g[2])
+
+
+def context_kmer(code: int, k: int) -> str:
+    """row `code` of a `pileup -S` table as its k bases (A = 0, C = 1, G = 2, T = 3, first base most significant); 4^k: `other`"""
+    if not 0 <= code <= 4 ** k:
+        raise ValueError(f"code {code} outside [0, 4^{k}]")
+    return "other" if code == 4 ** k else "".join("ACGT"[(code >> (2 * (k - 1 - j))) & 3] for j in range(k))
+
+
+def context_code(kmer: str) -> int:
+    """the inverse of context_kmer: k bases of ACGT, or `other` (which needs no k: use 4^k)"""
+    code = 0
+    for ch in kmer:
+        code = code * 4 + "ACGT".index(ch)
+    return code
+
+
+def context_tsv(table: np.ndarray, flank: int) -> dict:
+    """the text of <prefix>.context.{CpG,CHG,CHH}.tsv from context()'s [3, K + 1, 4] table: the header, then per k-mer with a
+    counted locus, in k-mer order, context, n_loci, pcov, ncov, weighted, mean; `other` last if it is not empty"""
+    k = 3 + 2 * flank
+    table = np.asarray(table, np.int64)
+    assert table.shape == (3, 4 ** k + 1, 4)
+    head = "#context\tn_loci\tpcov\tncov\tweighted\tmean\n"
+    text = {}
+    for c in range(3):
+        rows = np.zeros(table.shape[1], REGION_SUM_DTYPE)
+        for q, name in enumerate(REGION_SUM_DTYPE.names):
+            rows[name] = table[c, :, q]
+        text[CTX_NAMES[c]] = head + "".join(context_kmer(int(code), k) + "\t" + _region_columns(rows[code])
+                                            for code in np.flatnonzero(rows["n_loci"] > 0))
+    return text
+
+
 def sites_rates_tsv(sums, rates, m) -> str:
     """the text of <prefix>.sites.rates.tsv: ctx, P_c, N_c, rate, m_c (the counts are 0 when the rates were given with -e)"""
     return "".join("%s\t%d\t%d\t%s\t%d\n" % (CTX_NAMES[c], int(sums[c]), int(sums[3 + c]),
@@ -1079,6 +1127,25 @@ class MethylationPileup:
             bytes(strand) if strand is not None else None, a.size, bins, flank, flank_bins,
             out.ctypes.data_as(C.c_void_p), C.byref(n_used)))
         return out, int(n_used.value)
+
+    def context(self, flank: int = 0, min_cov: int = 1, lo: int = 0, hi: Optional[int] = None, planes=None, plane_base: int = 0,
+                partition: int = 0, path: int = CONTEXT_PATH_AUTO) -> np.ndarray:
+        """methylation by the k = 3 + 2 flank bases around each cytosine (`pileup -S`): int64 [3, 4^k + 1, 4] -- context, row
+        (the k-mer's code, context_kmer(); the last row `other`), (n_loci, pcov, ncov, ppm) -- over the loci of [lo, hi) with
+        pcov + ncov >= min_cov.  Range, planes, plane_base and partition as for loci(); the tables of disjoint ranges add up.
+        path: the accumulation path (CONTEXT_PATH_LDS / _GLOBAL), for measurements and tests; both give the same table."""
+        hi = self.n_loci if hi is None else hi
+        ptrs = self._range_ptrs(planes, partition)
+        if ptrs[0] is not None and ptrs[2] is None:         # a partition's counts: the combined key is named, not implied
+            key = C.c_void_p()
+            self._check(self._L.hm_pileup_planes(self._h, None, None, C.byref(key), None))
+            ptrs[2] = key
+        args = (self._h, *ptrs, plane_base, lo, hi, min_cov, flank)
+        if path == CONTEXT_PATH_AUTO:
+            out = self._rows(lambda *a: self._L.hm_pileup_fetch_context(*args, *a[1:]), REGION_SUM_DTYPE)
+        else:
+            out = self._rows(lambda *a: self._L.hm_pileup_fetch_context_path(*args, path, *a[1:]), REGION_SUM_DTYPE)
+        return np.stack([out[k] for k in REGION_SUM_DTYPE.names], axis=-1).reshape(3, -1, 4)
 
     def bedmethyl(self, lo: int = 0, hi: Optional[int] = None, min_valid: int = 1, partition: int = 0) -> np.ndarray:
         """the reference CpGs of [lo, hi), ascending (BEDMETHYL_DTYPE), at which a read was classed and n_mod + n_canon >= min_valid

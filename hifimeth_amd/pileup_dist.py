@@ -1,7 +1,7 @@
 """`hifimeth pileup` over N GPUs of one node, one process per GPU (the path's only exchange step).
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
-        -m hifimeth_amd.pileup_dist [-q mapQ] [-f identity] [-H [-A [-a min-cov] [-Q] [-G [-s max-p] [-g max-gap] [-n min-loci]]]] [-B control | -e r,r,r] [-D [-u lo:hi[,lo:hi,lo:hi]] [-x nats] [-j bp]] [-L bp [-z min-pairs]] [-P bp [-y min-calls]] [-I n5[:n3]] [-R bed [-C min-cov] [-J bins[:flank:flank_bins]]] reference.fa mod.bam output-prefix
+        -m hifimeth_amd.pileup_dist [-q mapQ] [-f identity] [-H [-A [-a min-cov] [-Q] [-G [-s max-p] [-g max-gap] [-n min-loci]]]] [-B control | -e r,r,r] [-D [-u lo:hi[,lo:hi,lo:hi]] [-x nats] [-j bp]] [-L bp [-z min-pairs]] [-P bp [-y min-calls]] [-I n5[:n3]] [-R bed [-C min-cov] [-J bins[:flank:flank_bins]]] [-S flank [-O min-cov]] reference.fa mod.bam output-prefix
 
 Records are dealt to the ranks in slabs of `--slab` records (round-robin, like the `call` path).  Each rank projects its
 records and histograms them on its own GPU; then
@@ -48,6 +48,10 @@ table goes through one all-reduce, and rank 0 applies -y and writes <prefix>.rea
 the chunk), the integer columns go through one all-reduce each -- they are exact sums, so the parts add up to the whole -- and rank 0
 writes <prefix>.regions.<ctx>.tsv and <prefix>.metaplot.<ctx>.tsv, under -H per haplotype too, byte-identical to `pileup -R`.  The
 metaplot's n_regions depends on neither planes nor chunk: every rank computes the same value and it is not summed.
+-S flank [-O min-cov]: methylation by the k = 3 + 2 flank bases around each cytosine.  Every rank takes the table of its own chunk of
+the reduce-scattered planes (hm_pileup_fetch_context with plane_base = the chunk's first locus; the whole reference is on every
+rank's device, so a window reads across a chunk boundary like anywhere else), the [3, 4^k + 1, 4] integer tables go through one
+all-reduce per set of planes, and rank 0 writes <prefix>.context.<ctx>.tsv, under -H per haplotype too, byte-identical to `pileup -S`.
 """
 from __future__ import annotations
 
@@ -60,7 +64,7 @@ import numpy as np
 from . import dist as D
 from .bamio import is_coordinate_sorted, load_fasta, read_bam
 from .caller import HifimethError
-from .pileup import (ASM_DTYPE, CTX_NAMES, LINKAGE_DTYPE, LINKAGE_MAX_DIST, linkage_tsv, READPOS_MAX, readpos_tsv, REGION_SUM_DTYPE, metaplot_tsv, parse_metaplot, parse_regions_bed, regions_tsv, DOMAIN_LEVELS, DOMAIN_MAX_GAP, DOMAIN_PASS_CODES, DOMAIN_PASS_SEGMENTS, DOMAIN_PASS_SUMMARY,
+from .pileup import (ASM_DTYPE, CONTEXT_MAX_FLANK, CTX_NAMES, context_tsv, LINKAGE_DTYPE, LINKAGE_MAX_DIST, linkage_tsv, READPOS_MAX, readpos_tsv, REGION_SUM_DTYPE, metaplot_tsv, parse_metaplot, parse_regions_bed, regions_tsv, DOMAIN_LEVELS, DOMAIN_MAX_GAP, DOMAIN_PASS_CODES, DOMAIN_PASS_SEGMENTS, DOMAIN_PASS_SUMMARY,
                      DOMAIN_PENALTY, LOCUS_DTYPE, DomainFit, MethylationPileup, allreduce_histograms, asm_qvalues, asm_summary_tsv,
                      domain_backward_carries, domain_forward_carries, domain_scores, domains_fit_tsv, locus_ranges, parse_domain_levels, parse_rates,
                      rates_from_sums, reduce_scatter_planes, reduce_scatter_sum, resolve_threshold, sites_rates_tsv, sites_table,
@@ -72,10 +76,12 @@ def run(reference: str, bam: str, prefix: str, min_mapq: int = 0, min_pi: float 
         asm_min_cov: int = 5, control: str | None = None, rates=None, asm_q: bool = False,
         asm_regions: bool = False, max_p: float = 0.01, max_gap: int = 500, min_loci: int = 3, domain_rules=None,
         domain_max_gap: int = DOMAIN_MAX_GAP, domain_fit=None, linkage: int = 0, linkage_min_pairs: int = 1, profile: int = 0,
-        profile_min_calls: int = 1, trim=(0, 0), regions_bed: str | None = None, region_min_cov: int = 1, metaplot=None):
+        profile_min_calls: int = 1, trim=(0, 0), regions_bed: str | None = None, region_min_cov: int = 1, metaplot=None,
+        context_flank: int | None = None, context_min_cov: int = 1):
     """domain_rules (-D): per context (A, B, S) of domain_scores, or None for a context that is not segmented.  domain_fit (-Y):
     {"levels": per context (lo, hi) or None, "penalty", "max_iter"}: the levels are fitted from those and replace domain_rules.
-    regions_bed (-R), region_min_cov (-C), metaplot (-J): (bins, flank, flank_bins) or None"""
+    regions_bed (-R), region_min_cov (-C), metaplot (-J): (bins, flank, flank_bins) or None.  context_flank (-S): 0 .. 3 or None,
+    context_min_cov (-O)"""
     import torch
     rank, local_rank, world = D.env_world()
     dist = D.init_process_group(backend, force=bool(os.environ.get("HM_FORCE_COLLECTIVES")))
@@ -327,6 +333,16 @@ def run(reference: str, bam: str, prefix: str, min_mapq: int = 0, min_pi: float 
                     for ctx, text in metaplot_tsv(rows, n_used, len(regions) - n_used, bins, flank_bins).items():
                         with open(f"{prefix}.{tag}metaplot.{ctx}.tsv", "w") as f:
                             f.write(text)
+    if context_flank is not None:                           # exact integer sums per k-mer: the chunks' tables add up to the whole's
+        sets = [("", (pc, nc, key))] + [(f"hap{k + 1}.", (hp[2 * k], hp[2 * k + 1], key)) for k in range(len(hp) // 2)]
+        for tag, pl in sets:
+            mine = pu.context(context_flank, context_min_cov, 0, hi - lo, planes=pl, plane_base=base) if hi > lo \
+                else np.zeros((3, 4 ** (3 + 2 * context_flank) + 1, 4), np.int64)
+            table = allreduce_i64(mine).astype(np.int64)
+            if rank == 0:
+                for ctx, text in context_tsv(table, context_flank).items():
+                    with open(f"{prefix}.{tag}context.{ctx}.tsv", "w") as f:
+                        f.write(text)
     if control is not None or rates is not None:
         mine, n_mine = (pc, nc, key), hi - lo               # this rank's chunk: element 0 is locus `base`
         sums = np.zeros(6, np.uint64)
@@ -414,6 +430,9 @@ def main(argv=None):
     ap.add_argument("-C", dest="region_min_cov", type=int, default=None, help="with -R: smallest coverage of a locus that counts, >= 1 (default 1)")
     ap.add_argument("-J", dest="metaplot", default=None, metavar="BINS[:FLANK_BP:FLANK_BINS]",
                     help="with -R: the metaplot over all intervals and their flanks -> <prefix>.metaplot.<ctx>.tsv")
+    ap.add_argument("-S", dest="context_flank", type=int, default=None, metavar="FLANK",
+                    help="methylation by the 3 + 2 FLANK bases around each cytosine, FLANK in 0 .. 3 -> <prefix>.context.<ctx>.tsv")
+    ap.add_argument("-O", dest="context_min_cov", type=int, default=None, help="with -S: smallest coverage of a locus that counts, >= 1 (default 1)")
     ap.add_argument("reference")
     ap.add_argument("mod_bam")
     ap.add_argument("output_prefix")
@@ -468,6 +487,10 @@ def main(argv=None):
         metaplot = None if a.metaplot is None else parse_metaplot(a.metaplot)
     except ValueError:
         ap.error("-C must be an integer >= 1, -J bins[:flank_bp:flank_bins] with bins in [1, 1000] and flank_bp a multiple of flank_bins in [1, 1000]")
+    if a.context_flank is None and a.context_min_cov is not None:
+        ap.error("-O needs -S")
+    if (a.context_flank is not None and not 0 <= a.context_flank <= CONTEXT_MAX_FLANK) or (a.context_min_cov is not None and a.context_min_cov < 1):
+        ap.error("-S must be an integer in [0, 3], -O an integer >= 1")
     domain_rules = domain_fit = None
     if a.domains:
         bad = "-u takes lo:hi with 0 < lo < hi < 1 (levels a 2^24-th of a nat apart at least) or nan, once or per context; " \
@@ -489,7 +512,8 @@ def main(argv=None):
                domain_rules=domain_rules, domain_max_gap=DOMAIN_MAX_GAP if a.domain_max_gap is None else a.domain_max_gap,
                domain_fit=domain_fit, linkage=a.linkage or 0, linkage_min_pairs=1 if a.linkage_min_pairs is None else a.linkage_min_pairs,
                profile=a.profile or 0, profile_min_calls=1 if a.profile_min_calls is None else a.profile_min_calls, trim=trim,
-               regions_bed=a.regions_bed, region_min_cov=1 if a.region_min_cov is None else a.region_min_cov, metaplot=metaplot)
+               regions_bed=a.regions_bed, region_min_cov=1 if a.region_min_cov is None else a.region_min_cov, metaplot=metaplot,
+               context_flank=a.context_flank, context_min_cov=1 if a.context_min_cov is None else a.context_min_cov)
 
 
 if __name__ == "__main__":

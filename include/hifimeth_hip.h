@@ -767,6 +767,52 @@ int hm_pileup_fetch_metaplot(hm_pileup_t* p, const void* pcov, const void* ncov,
  * ppm / n_loci / 10^4, the mean of the loci's own percentages.  HM_EINVAL for n_loci == 0 (or a negative member). */
 int hm_region_stats(const hm_region_sum_t* w, double out[2]);
 
+/* ---- methylation by the k-mer around each cytosine (`pileup -S`) ------------------------------------------------
+ * The three contexts split further by the sequence the cytosine sits in: CCG against CAG / CTG, CAA / CTA against the other CHH, or a
+ * caller's error rate that follows a flanking base.  flank = f in {0, 1, 2, 3}, k = 3 + 2 f (3, 5, 7, 9), K = 4^k.
+ * A LOCUS g (global coordinate into the concatenated reference) COUNTS exactly as under hm_pileup_fetch_regions: cov = pcov + ncov
+ * (64 bits) >= min_cov (>= 1); its context c = key & 3; it adds n_loci += 1, pcov, ncov and ppm += (2 000 000 pcov + cov) / (2 cov).
+ * THE ROW it adds to is decided by the reference alone (forward cytosines are recorded at their C, reverse-strand CHH at the G of
+ * DDG).  With [S0, S1) the locus' own sequence:
+ *   ref[g] == 'C': the window is ref[g - f, g + 3 + f), read left to right;
+ *   ref[g] == 'G': the window is ref[g - 2 - f, g + 1 + f), reverse-complemented; the called cytosine is again at offset f;
+ *   row `other` (index K): ref[g] is neither C nor G, or the window is not wholly inside [S0, S1) (a window never reads the
+ *   neighbouring sequence of the concatenation), or it holds a base outside ACGT.
+ * Code: A = 0, C = 1, G = 2, T = 3, first base most significant.  The table is out[c * (K + 1) + code], c = 0 .. 2, code = 0 .. K:
+ * 3 (K + 1) entries.  Per context the n_loci of all rows, `other` included, add up to the loci of [lo, hi) with cov >= min_cov in
+ * that context.  No row is restricted to the k-mers its context can have: planes handed in may carry any key at any base, and a CpG
+ * locus and a reverse-read CGG locus can share g.  All of it exact integers: the tables of disjoint chunks add up to the whole's.
+ * HOW: one grid-stride kernel over [lo, hi) with one workgroup of HM_CONTEXT_SPAN threads per CU.  It streams pcov / ncov; only a
+ * locus with a count reads key, finds its sequence's end and reads its k reference bytes.  Up to flank HM_CONTEXT_LDS_FLANK the
+ * workgroup adds into a table of its own in LDS (6 KB at flank 0, 98 KB at flank 1) and ends with one global atomic per non-zero
+ * counter; above it every add is a 64-bit global atomic into the device table (25 MB at flank 3).  The device table is allocated
+ * by the first call and freed with the engine; without a call nothing is allocated or launched.
+ * Not here: strand-split counts (CpG strands are merged at projection), tests between contexts, IUPAC motif queries, sequence
+ * logos, k above 9. */
+#define HM_CONTEXT_SPAN 1024        /* loci a workgroup takes side by side */
+#define HM_CONTEXT_LDS_MAX_FLANK 1  /* the largest flank whose table fits in LDS at all */
+#ifndef HM_CONTEXT_LDS_FLANK
+#define HM_CONTEXT_LDS_FLANK 1      /* the largest flank that takes the LDS path: chosen by measurement, DESIGN.md section 10 */
+#endif
+#define HM_CONTEXT_PATH_AUTO (-1)
+#define HM_CONTEXT_PATH_LDS 0
+#define HM_CONTEXT_PATH_GLOBAL 1
+/* the constants the library was built with: out[0] = HM_CONTEXT_SPAN, out[1] = HM_CONTEXT_LDS_FLANK, out[2] =
+ * HM_CONTEXT_LDS_MAX_FLANK (host only) */
+int hm_context_geometry(int64_t out[3]);
+/* Returns 3 (K + 1); when that exceeds cap, or out is NULL, nothing is written.  Planes NULL = the engine's own, else DEVICE
+ * pointers whose element 0 is locus `plane_base`, of which [lo, hi) is looked at, as in hm_pileup_fetch_regions; the reference
+ * position of element i is plane_base + i in the engine's reference.  Per haplotype: the same call with a partition's pcov / ncov
+ * and the combined key.  HM_ESTATE before hm_pileup_set_reference and without planes (as hm_pileup_fetch_loci); HM_EINVAL for
+ * flank outside [0, 3], min_cov < 1, a bad range, a mix of NULL and non-NULL planes, or plane_base + hi beyond the reference. */
+int64_t hm_pileup_fetch_context(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t plane_base, int64_t lo,
+                                int64_t hi, int64_t min_cov, int32_t flank, hm_region_sum_t* out, int64_t cap);
+/* The same with the accumulation path named: HM_CONTEXT_PATH_AUTO (what hm_pileup_fetch_context takes), _LDS (HM_EINVAL for a flank
+ * above HM_CONTEXT_LDS_MAX_FLANK) or _GLOBAL.  Both paths give the same table; this is what measures them against each other
+ * (tools/pileup_bench.py --context) and lets a test reach the one the default does not take. */
+int64_t hm_pileup_fetch_context_path(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t plane_base, int64_t lo,
+                                     int64_t hi, int64_t min_cov, int32_t flank, int32_t path, hm_region_sum_t* out, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -98,6 +98,56 @@ def cpu_baseline(genome, chrom, starts, staged, read_len, n_sample=600, repeat=1
                        f"(ref_align -t), {secs:.1f} s")
 
 
+def context_leg(log2_loci, repeat, check):
+    """`pileup -S`: hm_pileup_fetch_context over planes of 2^log2_loci loci, about 5 % of them covered, for flank 0 .. 3 and each
+    accumulation path that exists for the flank, next to the yardstick: one hm_pileup_fetch_regions call of one interval, whose
+    region_block_sums_kernel streams the same pcov / ncov / key and adds neither reference reads nor atomics.  Times are whole
+    calls (memset of the device table, the kernel, the table's download); the kernels' own times come from a run of this leg
+    under a kernel trace (context_kernel<flank, lds> against region_block_sums_kernel)."""
+    import torch
+    from hifimeth_amd.pileup import CONTEXT_PATH_GLOBAL, CONTEXT_PATH_LDS, context_geometry
+    n = 1 << log2_loci
+    rng = np.random.default_rng(3)
+    bases = _ASCII[rng.integers(0, 4, n, dtype=np.uint8)]
+    pu = MethylationPileup([("chr1", n)], bases=bases)
+    gen = torch.Generator(device="cuda").manual_seed(5)
+    on = torch.rand(n, device="cuda", generator=gen) < 0.05
+    zero = torch.zeros(n, dtype=torch.int32, device="cuda")
+    pc = torch.where(on, torch.randint(0, 30, (n,), dtype=torch.int32, device="cuda", generator=gen), zero)
+    nc = torch.where(on, torch.randint(0, 30, (n,), dtype=torch.int32, device="cuda", generator=gen), zero)
+    ky = torch.randint(0, 3, (n,), dtype=torch.int32, device="cuda", generator=gen)
+    del on, zero
+    torch.cuda.synchronize()
+    planes = (pc, nc, ky)
+    span, lds_flank, lds_max = context_geometry()
+    legs = {"regions_index": lambda: pu.regions([0], [1], planes=planes, hi=n)}
+    for f in range(4):
+        for name, path in (("lds", CONTEXT_PATH_LDS), ("global", CONTEXT_PATH_GLOBAL)):
+            if path == CONTEXT_PATH_GLOBAL or f <= lds_max:
+                legs[f"flank{f}_{name}"] = lambda f=f, path=path: pu.context(f, planes=planes, hi=n, path=path)
+    times = {k: [] for k in legs}
+    for leg in legs.values():
+        leg()                                      # warm-up: the buffers, the code objects
+    for _ in range(max(repeat, 5)):                # the legs alternate, so that a drift of the machine falls on all of them
+        for k, leg in legs.items():
+            t0 = time.perf_counter()
+            leg()
+            times[k].append(time.perf_counter() - t0)
+    best = {k: min(v) for k, v in times.items()}
+    out = dict(context_loci=n, context_covered=round(float(((pc + nc) > 0).float().mean()), 4), context_span=span,
+               context_lds_flank=lds_flank, context_call_s={k: [round(x, 5) for x in v] for k, v in times.items()},
+               context_call_ratio_to_regions_index={k: round(v / best["regions_index"], 3) for k, v in best.items()},
+               context_table_bytes={f"flank{f}": 3 * (4 ** (3 + 2 * f) + 1) * 32 for f in range(4)})
+    if check:                                      # both paths give one table, and it holds every counted locus
+        same = all((pu.context(f, planes=planes, hi=n, path=CONTEXT_PATH_LDS) == pu.context(f, planes=planes, hi=n, path=CONTEXT_PATH_GLOBAL)).all()
+                   for f in range(lds_max + 1))
+        counted = int(((pc + nc) > 0).sum())
+        out["check_context_paths_agree"] = bool(same)
+        out["check_context_holds_the_loci"] = all(int(pu.context(f, planes=planes, hi=n)[:, :, 0].sum()) == counted for f in range(4))
+    pu.close()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--genome-mb", type=float, default=20)
@@ -131,11 +181,16 @@ def main():
     ap.add_argument("--regions", type=int, default=0, metavar="N",
                     help="time the interval sums and the metaplot (pileup -R / -J 20:2000:10): N gene-like intervals of 0.5 - 20 kb, "
                          "and a tiling of the reference in 1 kb windows")
+    ap.add_argument("--context", type=int, default=0, metavar="LOG2",
+                    help="time the k-mer tables (pileup -S 0 .. 3) on both accumulation paths over synthetic planes of 2^LOG2 loci, 5 %% "
+                         "covered, against the interval index build over the same planes; a leg of its own: nothing else is run")
     ap.add_argument("--bedmethyl", action="store_true", help="time what the per-CpG depth classes add (pileup -M, min_valid 1)")
     ap.add_argument("--digest", action="store_true", help="add a sha256 of the records, the loci and the rows of the timed options")
     ap.add_argument("--cpu-baseline", action="store_true",
                     help="time the reference's own projection code (oracle/_ref/ref_align -t) on a bounded sample")
     a = ap.parse_args()
+    if a.context:
+        return context_leg(a.context, a.repeat, a.check)
     if a.asm and not a.partitions:
         ap.error("--asm needs --partitions")
     if a.asm_q and not a.asm:
