@@ -207,6 +207,49 @@ def test_metaplot_chunks_add_up():
         assert (left == R.metaplot(run, start, end, s0, s1, strand.decode(), bins, flank, fb, lo=0, hi=cut)[0]).all(), cut
 
 
+# ---- planes next to 2^31 and 2^32 --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("boundary", [2 ** 31, 2 ** 32], ids=["2^31", "2^32"])
+def test_planes_next_to_a_32_bit_boundary(boundary):
+    """the four blocks of _block_planes with a plane_base that puts the boundary inside the second block, off the block grid:
+    interval edges, plane_base and the metaplot's sequence clamp are coordinates beyond 2^31 / 2^32, and the expectation of the
+    same intervals with their coordinates through 32 bits is another one.  The smallest shape at which a 32-bit coordinate in
+    region_query_kernel / metaplot_kernel shows, on any card; the index of a reference of that size (2^20 blocks, 1024 scan
+    workgroups) runs in test_gpu_pileup_bigref.py.  `pileup -S` cannot be reached this way: it refuses a plane_base + hi beyond
+    the engine's reference, so its only run at such coordinates is the one in test_gpu_pileup_bigref.py."""
+    from bigref import wrap32
+    host, dev, _ = _block_planes()
+    blk, _ = _geometry()
+    n = len(host[0])
+    base = boundary - (blk + 5)
+    assert blk < boundary - base < 2 * blk and (boundary - base) % blk
+    run = R.Running(*host, base=base)
+    start, end = _pairs(_points()) + base
+    more = np.array([(boundary - 1, boundary + 1), (boundary, boundary + 7), (boundary - 7, boundary), (base, base + n)], np.int64).T
+    start, end = np.concatenate([start, more[0]]), np.concatenate([end, more[1]])
+    want = R.region_sums(run, start, end)
+    assert (R.region_sums(run, [base, boundary], [boundary, base + n])[:, :, 0] > 0).all()        # counted loci on both sides of it
+    assert want[-4:-1, :, 0].sum(axis=1).all()                                                    # ... and in the three intervals on it
+    got = _got(_pu().regions(start, end, planes=dev, plane_base=base, hi=n))
+    assert got.shape == want.shape and (got == want).all()
+    casts = (True,) if boundary < 2 ** 32 else (True, False)
+    for signed in casts:
+        assert (R.region_sums(run, wrap32(start, signed), wrap32(end, signed)) != want).any()
+    # the metaplot of a sequence that begins three bases below the boundary: the upstream flank of the first interval is clamped there
+    bins, flank, fb = 5, 12, 3
+    S0, S1 = boundary - 3, base + n
+    iv = [(boundary, boundary + 40, "+"), (boundary + 10, boundary + 31, "-"), (S0, boundary + 5, "."), (S1 - 25, S1, "+"),
+          (boundary + blk - 9, boundary + blk + 9, "-"), (boundary + 3, boundary + 3 + bins - 1, "+")]
+    a, b = (np.array([x[k] for x in iv], np.int64) for k in (0, 1))
+    s0, s1 = np.full(len(iv), S0, np.int64), np.full(len(iv), S1, np.int64)
+    strand = "".join(x[2] for x in iv)
+    tab, used = R.metaplot(run, a, b, s0, s1, strand, bins, flank, fb)
+    assert used == len(iv) - 1 and (tab[:, 0, 0] < used).all() and tab[:, :, 1].sum(axis=0).all()
+    rows, n_used = _pu().metaplot(a, b, s0, s1, strand.encode(), bins, flank, fb, planes=dev, plane_base=base, hi=n)
+    assert n_used == used and (_meta_table(rows, bins + 2 * fb) == tab).all()
+    for signed in casts:
+        assert (R.metaplot(run, *(wrap32(x, signed) for x in (a, b, s0, s1)), strand, bins, flank, fb)[0] != tab).any()
+
+
 # ---- real records ----------------------------------------------------------------------------------------------------------------------
 def _tagged_reads():
     if "reads" not in _CACHE:

@@ -166,3 +166,113 @@ def test_expected_side_sees_a_32_bit_locus(small, B, name):
         assert genome[1][1][g - int(off[1])] == "G" and any(o + off[s] == g and m == 2 for s, o, _p, m in want["records"])
     if name == "contig_at_B":
         assert g == off[1]
+
+
+# ---- the newer outputs (-G, -D, -E, -M, -L, -P, -R / -J, -S): what makes their big cases worth the memory -------------------------------
+COORD_OUTPUTS = ("patterns2", "patterns4", "bedmethyl", "domains0", "domains1", "domains2", "asm_regions0", "asm_regions1", "asm_regions2")
+
+
+def _expected_rows(what):
+    """the small job's expected rows of one coordinate-carrying output, from its CPU restatement"""
+    n = int(R.offsets_of(R.small_job()[0])[-1])
+    if what.startswith("patterns"):
+        return R.expected_patterns(int(what[-1]))
+    if what == "bedmethyl":
+        return R.expected_bedmethyl(0)
+    if what.startswith("domains"):
+        return R.expected_domains(R.oracle_loci(), int(what[-1]), 0, n)[0]
+    return R.expected_asm_regions(R.expected_asm_rows(), int(what[-1]), 0, n)[0]
+
+
+def test_small_job_fills_the_newer_outputs(small):
+    genome, _reads, want, _n = small
+    assert R.expected_thresholds() == want["thresholds"] == [128, 128, 128]
+    assert len(R.expected_patterns(2)) >= 1000 and len(R.expected_patterns(4)) >= 1000       # min_reads 1, span 150
+    assert R.expected_patterns(2)["k"].tolist() == [2] * len(R.expected_patterns(2))
+    assert len(R.expected_bedmethyl(0)) >= 1000 and len(R.expected_bedmethyl(0)) > len(R.expected_bedmethyl(1)) > 0
+    sets = R.expected_bedmethyl_counters()
+    assert all(len(s) > 100 for s in sets) and set(sets[1]) <= set(sets[0]) and set(sets[2]) <= set(sets[0])
+    assert len(R.expected_bedmethyl(0, 1)) > 100 and len(R.expected_bedmethyl(0, 2)) > 100
+    pairs = R.expected_linkage_pairs()
+    assert len(pairs) >= 1000 and max(pairs) == R.LINKAGE_DIST and len(R.expected_linkage(0)) == R.LINKAGE_DIST - 1
+    hist = R.expected_readpos_histograms()
+    assert (hist.sum(axis=(1, 2)) > 1000).all() and hist[:, :R.PROFILE_D].any() and hist[:, R.PROFILE_D:-1].any() and hist[:, -1].any()
+    assert len(R.expected_readpos(0)) == 3 * (2 * R.PROFILE_D + 1) > len(R.expected_readpos(1)) > 1000
+    for flank in R.CONTEXT_FLANKS:
+        tab = R.expected_context(flank)
+        assert (tab[:, :, 0].sum(axis=1) == [(R.oracle_loci()["motif"] == c).sum() for c in range(3)]).all()
+    assert R.expected_context(3)[:, -1, 0].sum() > 0            # a covered cytosine within 5 bases of a sequence end: row `other`
+    chains = np.concatenate([_expected_rows("asm_regions%d" % c) for c in range(3)])
+    assert (chains["n_loci"] >= 2).sum() >= 3 and (chains["sign"] > 0).any() and (chains["sign"] < 0).any()
+    pv = R.expected_asm_rows()["pvalue"]
+    assert (pv <= R.ASM_MAX_P).any() and (pv > R.ASM_MAX_P).any() and not (np.abs(pv / R.ASM_MAX_P - 1) < 1e-6).any()   # the p filter decides, far from ties
+    assert all(len(_expected_rows("domains%d" % c)) >= 5 for c in range(3))
+    start, end, s0, s1, strand = R.meta_intervals()
+    tab, used = R.expected_metaplot(start, end, s0, s1, strand)
+    nb, fb = tab.shape[1], R.META["flank_bins"]
+    assert used == len(start) == 6 and set(strand) == set(b"+-.")
+    assert (tab[:, :fb - 1, 0] < used).all() and (tab[:, nb - fb + 1:, 0] < used).all()       # both flanks hit the sequence clamp ...
+    assert (tab[:, fb:nb - fb, 0] == used).all() and tab[:, :, 1].sum(axis=0).all()            # ... the bodies never, and no bin is empty
+
+
+@pytest.mark.parametrize("name", R.PLACEMENTS)
+def test_newer_outputs_have_rows_on_both_sides_of_the_placed_locus(small, name):
+    genome, reads, want, _n = small
+    P, g = R.placement(name, B32, genome, reads, want)
+    assert R.placement(name, R.B31, genome, reads, want)[1] == g                            # the locus is the same at either boundary
+    n = int(R.offsets_of(genome)[-1])
+    for k in (2, 4):
+        p = R.expected_patterns(k)
+        assert (p["start"] < g).sum() >= 100 and (p["start"] >= g).sum() >= 100
+        if name == "cpg_at_B":
+            assert ((p["start"] < g) & (g < p["end"])).sum() >= 1 and (p["start"] == g).sum() >= 1
+    b = R.expected_bedmethyl(0)
+    assert (b["gpos"] < g).sum() >= 100 and (b["gpos"] >= g).sum() >= 100
+    if name == "cpg_at_B":
+        assert (b["gpos"] == g).sum() == 1
+        assert R.linkage_straddlers(g) >= 1                     # pairs of one record with members on both sides of B
+    start, end = R.intervals(g)
+    for min_cov in R.REGION_MIN_COVS:
+        filled = R.expected_regions(start, end, min_cov)[:, :, 0].sum(axis=1) > 0
+        assert ((start < g) & (g < end) & filled).any() and ((start == g) & filled).any() and ((end == g) & filled).any()
+    assert ((end - start) == n).any() and len(start) == 21 + 3 + 1
+    blk = R.region_block()
+    assert {g - 1, g, g + 1, g - blk, g + blk, g - blk - 1, g + blk + 1} <= set(start.tolist()) | set(end.tolist())
+    for what in COORD_OUTPUTS[3:]:                              # a segment and a chain of every context contain the placed locus
+        rows = _expected_rows(what)
+        assert ((rows["start"] <= g) & (g < rows["end"])).sum() == 1, what
+    for c in range(3):                                          # ... and either side of it has loci that are counted
+        loci = R.oracle_loci()
+        assert ((loci["gpos"] < g) & (loci["motif"] == c)).sum() >= 100 and ((loci["gpos"] >= g) & (loci["motif"] == c)).sum() >= 100
+
+
+@pytest.mark.parametrize("B,name", R.CASES, ids=R.CASE_IDS)
+def test_expected_side_of_the_newer_outputs_sees_a_32_bit_locus(small, B, name):
+    """for every output that carries coordinates, the expectation whose coordinates went through 32 bits is another one: rows by
+    their own fields, the sums of -R / -J by the intervals they are asked for"""
+    genome, reads, want, _n = small
+    P, g = R.placement(name, B, genome, reads, want)
+    n = int(R.offsets_of(genome)[-1])
+    casts = (True,) if B < B32 else (True, False)
+    for what in COORD_OUTPUTS:
+        rows = _expected_rows(what)
+        big = R.translate(rows, P)
+        fields = [f for f in R.COORDS if f in rows.dtype.names]
+        assert all((big[f] - P == rows[f]).all() for f in fields) and R.same_rows(big, big.copy()), what
+        others = [f for f in rows.dtype.names if f not in fields]
+        assert all(big[f].tobytes() == rows[f].tobytes() for f in others), what
+        for signed in casts:
+            bad = R.truncate32(big, signed)
+            assert not R.same_rows(bad, big), what
+            with pytest.raises(AssertionError):
+                R.assert_same_rows(bad, big, what)
+    start, end = R.intervals(g)
+    m = R.meta_intervals()
+    want_sums = R.expected_regions(start + P, end + P, base=P)
+    assert (want_sums == R.expected_regions(start, end)).all()  # untranslated: the sums do not know where the planes lie
+    want_meta, used = R.expected_metaplot(*(x + P for x in m[:4]), m[4], base=P)
+    assert used == 6 and (want_meta == R.expected_metaplot(*m)[0]).all()
+    for signed in casts:
+        assert (R.expected_regions(R.wrap32(start + P, signed), R.wrap32(end + P, signed), base=P) != want_sums).any()
+        a, b, s0, s1 = (R.wrap32(x + P, signed) for x in m[:4])
+        assert (R.expected_metaplot(a, b, s0, s1, m[4], base=P)[0] != want_meta).any()
