@@ -132,6 +132,7 @@ def lib():
         "hm_pileup_fetch_asm_q": (i64, [vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, vp, i64, vp, vp, i64, vp, i64]),
         "hm_pileup_fetch_asm_regions": (i64, [vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, C.c_double, i64, i32, i32,
                                               C.POINTER(i64), vp, i64]),
+        "hm_pileup_load_loci": (i64, [vp, i32, vp, i64]),
         "hm_pileup_control_sums": (C.c_int, [vp, vp, vp, vp, i64, i64, vp]),
         "hm_pileup_site_histogram": (i64, [vp, vp, vp, vp, i64, i64, i64, vp, vp, i64]),
         "hm_sites_table": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp]),

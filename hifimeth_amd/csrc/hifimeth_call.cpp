@@ -12,6 +12,7 @@
 //     hifimeth-hip tagtest IN.bam CALLS.bin OUT.bam   (apply hm_call_t records, read_id = record index)
 //     hifimeth-hip pileup [OPTIONS] REF.fa MOD.bam PREFIX   (hifimeth_pileup.cpp)
 //     hifimeth-hip corr [-c N] A.cov.bed B.cov.bed          (Pearson r of two pileup outputs, hifimeth_pileup.cpp)
+//     hifimeth-hip diff [OPTIONS] REF.fa PREFIX1 PREFIX2 OUT (two pileups' *.cov.bed tested locus by locus, hifimeth_pileup.cpp)
 //     hifimeth-hip modstats IN.bam                    (MM/ML parser + per-context histograms + adaptive thresholds)
 //     hifimeth-hip modlist IN.bam                     (the MM/ML parser's output per record: test seam against the
 //                                                      reference parser's fixture, tests/golden/modparse.json)
@@ -101,8 +102,12 @@ void usage() {
             "               records in fewer CPU seconds, but not the bytes zlib writes at that level\n"
             "  -S <int>     bases per engine slab (pipeline granularity, default 6291456; results do not depend on it)\n"
             "  -T <0|1>     conv1..conv4 once per site (0) / once per read position (1); default: per context, from the site\n"
-            "               density of the head of BAM\n",
-            kName, kName, kName);
+            "               density of the head of BAM\n\n"
+            "OTHER COMMANDS (each prints its own usage):\n"
+            "  %s pileup [OPTIONS] reference mod-bam output-prefix          per-locus methylation of one sample\n"
+            "  %s diff [OPTIONS] reference prefix1 prefix2 output-prefix    two pileups tested for differential methylation\n"
+            "  %s corr [-c <min coverage>] bed1 bed2                        Pearson correlation of two pileups\n",
+            kName, kName, kName, kName, kName, kName);
 }
 
 // host threads this process may really use: the affinity mask, capped by the cgroup CPU quota (a container that is granted
@@ -892,6 +897,7 @@ int cmd_fastats(int argc, char** argv);  // hifimeth_pileup.cpp
 int cmd_thresholds(int argc, char** argv);
 int cmd_corr(int argc, char** argv);     // hifimeth_pileup.cpp
 int cmd_cov2bed(int argc, char** argv);  // hifimeth_pileup.cpp
+int cmd_diff(int argc, char** argv);     // hifimeth_pileup.cpp
 int cmd_sample(int argc, char** argv);   // hifimeth_pileup.cpp
 int cmd_eval(int argc, char** argv);     // hifimeth_pileup.cpp
 
@@ -910,6 +916,7 @@ int main(int argc, char** argv) {
     if (cmd == "modlist") return cmd_modlist(argc, argv);
     if (cmd == "corr") return cmd_corr(argc, argv);
     if (cmd == "cov2bed") return cmd_cov2bed(argc, argv);
+    if (cmd == "diff") return cmd_diff(argc, argv);
     if (cmd == "sample") return cmd_sample(argc, argv);
     if (cmd == "eval") return cmd_eval(argc, argv);
     usage();

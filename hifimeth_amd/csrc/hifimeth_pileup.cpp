@@ -1354,7 +1354,7 @@ int fit_domains(hm_pileup_t* pe, const Fasta& fa, PileupOptions& o, int64_t A[3]
 // occurs, the q-values (hm_asm_qvalues), then the rows of write_asm with their q looked up (56 B per row on the device and here),
 // and <prefix>.asm.summary.tsv from the table's weights.  1 done, -1 engine error (hm_pileup_last_error), 0 another error (message
 // printed).
-int write_asm_q(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, FILE* out[3], int threads) {
+int write_asm_q(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, const std::string& tag, FILE* out[3], int threads) {
     static const char* cn[3] = {"CpG", "CHG", "CHH"};
     int64_t n_loci = 0;
     for (size_t s = 0; s < fa.names.size(); ++s) n_loci += fa.length[s];
@@ -1378,7 +1378,7 @@ int write_asm_q(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, FILE* 
     std::vector<double> big_q(big.size());
     uint64_t m[3];
     if (hm_asm_qvalues(tab.data(), n_tab, big.data(), n_big, big_q.data(), m) != HM_OK) {
-        fprintf(stderr, "ERROR: asm: the table of the tested loci is not one the engine wrote\n");
+        fprintf(stderr, "ERROR: %s: the table of the tested loci is not one the engine wrote\n", tag.c_str());
         return 0;
     }
     const bool ok = write_rows<hm_asmq_t>(
@@ -1399,12 +1399,31 @@ int write_asm_q(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, FILE* 
     };
     for (const hm_asm_bin_t& t : tab) tally(t.bin / (HM_ASM_PAIRS * HM_ASM_PAIRS), t.count, t.qvalue);
     for (size_t i = 0; i < big.size(); ++i) tally(std::min(big[i].motif, 2u), 1, big_q[i]);
-    const std::string path = o.prefix + ".asm.summary.tsv";
+    const std::string path = o.prefix + "." + tag + ".summary.tsv";
     FILE* f = fopen(path.c_str(), "w");
     if (!f) { fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str()); return 0; }
     for (int c = 0; c < 3; ++c)
         fprintf(f, "%s\t%llu\t%llu\t%llu\n", cn[c], (unsigned long long)m[c], (unsigned long long)below[c][0], (unsigned long long)below[c][1]);
     fclose(f);
+    return 1;
+}
+
+// Every output of the test between the engine's two partitions, under the file tag `tag` -- "asm" for the two haplotypes of
+// `pileup -H -A`, "diff" for the two samples of `diff`: <prefix>.<tag>.<ctx>.bed (write_asm, or under -Q write_asm_q with
+// <prefix>.<tag>.summary.tsv) and under -G <prefix>.<tag>.regions.<ctx>.bed (write_asm_regions).  1 done, 0 an error whose message
+// is printed, -1 / -2 an engine error (hm_pileup_last_error) in the rows / in the regions.
+int write_partition_tests(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, const std::string& tag) {
+    {
+        CtxFiles out;
+        if (!out.open(o.prefix, tag + ".", ".bed")) return 0;
+        const int rc = o.asm_q ? write_asm_q(pe, fa, o, tag, out.f, o.threads) : write_asm(pe, fa, o.asm_min_cov, out.f, o.threads) ? 1 : -1;
+        if (rc != 1) return rc;
+    }
+    if (o.asm_regions) {
+        CtxFiles out;
+        if (!out.open(o.prefix, tag + ".regions.", ".bed")) return 0;
+        if (!write_asm_regions(pe, fa, o, out.f)) return -2;
+    }
     return 1;
 }
 }  // namespace
@@ -2013,17 +2032,10 @@ int cmd_pileup(int argc, char** argv) {
         if (!out.open(o.prefix, tags[t], ".cov.bed")) return EXIT_FAILURE;
         if (!write_bed(pe, fa, planes[3 * t], planes[3 * t + 1], planes[3 * t + 2], out.f, o.threads)) return die("loci");
     }
-    if (o.asm_test) {
-        CtxFiles out;
-        if (!out.open(o.prefix, "asm.", ".bed")) return EXIT_FAILURE;
-        const int rc = o.asm_q ? write_asm_q(pe, fa, o, out.f, o.threads) : write_asm(pe, fa, o.asm_min_cov, out.f, o.threads) ? 1 : -1;
-        if (rc < 0) return die("asm");
+    if (o.asm_test) {  // -Q and -G need -A
+        const int rc = write_partition_tests(pe, fa, o, "asm");
+        if (rc < 0) return die(rc == -1 ? "asm" : "asm regions");
         if (rc == 0) return EXIT_FAILURE;
-    }
-    if (o.asm_regions) {
-        CtxFiles out;
-        if (!out.open(o.prefix, "asm.regions.", ".bed")) return EXIT_FAILURE;
-        if (!write_asm_regions(pe, fa, o, out.f)) return die("asm regions");
     }
     if (o.domains) {
         if (o.domain_fit_iter) {
@@ -2067,5 +2079,245 @@ int cmd_pileup(int argc, char** argv) {
                                : "## %llu records in %.2f s: [producer thread: BAM read %.2f s, MM/ML parse %.2f s] overlapped with "
                                  "[staging %.2f s, GPU projection %.2f s]; thresholds + count + BED %.2f s\n",
             (unsigned long long)n_records, secs(t_start, clk::now()), t_read, t_parse, t_submit, t_gpu, secs(t_loop, clk::now()));
+    return 0;
+}
+
+// ---- diff [OPTIONS] reference prefix1 prefix2 out-prefix (ours) -----------------------------------------------------------------------
+// Two-sample differential methylation from two pileups: the rows of <prefix1>.<ctx>.cov.bed go into the engine's partition 1, those
+// of <prefix2>.<ctx>.cov.bed into partition 2 (hm_pileup_load_loci), and the per-locus test, its q-values and the regions of
+// `pileup -H -A [-Q] [-G]` are written for sample 1 against sample 2 as <out>.diff.* (DESIGN.md section 10).  Files and not two BAMs:
+// each sample keeps the thresholds its own pileup inferred, and files from pileup_dist or cov2bed compare as well.
+namespace {
+
+void diff_usage(const char* exe) {
+    fprintf(stderr,
+            "USAGE:\n  %s diff [OPTIONS] reference prefix1 prefix2 output-prefix\n\n"
+            "DESCRIPTION:\n  Test two samples for differential methylation, locus by locus, from the files two `pileup` runs wrote:\n"
+            "  <prefix1>.<ctx>.cov.bed against <prefix2>.<ctx>.cov.bed for ctx in CpG, CHG, CHH (plain or gzip; a row is chrom, start,\n"
+            "  start + 1, a percentage that is not read, methylated calls, unmethylated calls; further columns are ignored).  A context\n"
+            "  without both files is skipped.  Writes <output-prefix>.diff.<ctx>.bed: chrom, start, end, sample 1 %% - sample 2 %%, two-sided\n"
+            "  Fisher exact p-value, pcov1, ncov1, pcov2, ncov2 for every locus where each sample has at least -a calls; a locus the two\n"
+            "  samples list under different contexts goes to the later one of CpG, CHG, CHH\n\n"
+            "OPTIONAL ARGUMENTS (as the same letters of `pileup -H -A`):\n"
+            "  -a <int>\n    Minimum coverage (pcov + ncov) of each sample at a tested locus\n    Default: 5\n"
+            "  -Q\n    A tenth column, the Benjamini-Hochberg q-value of the p-value among all tested loci of the context, and\n"
+            "    <output-prefix>.diff.summary.tsv: ctx, tested loci, loci with q <= 0.05, loci with q <= 0.01\n"
+            "  -G\n    Chain the tested loci of each context into regions and write <output-prefix>.diff.regions.<ctx>.bed: chrom, start, end,\n"
+            "    loci, + or -, sample 1 %% - sample 2 %% of the pooled counts, smallest p-value, pcov1, ncov1, pcov2, ncov2 summed over the loci\n"
+            "  -s <p>\n    With -G: largest p-value of a locus in a region, in (0, 1]\n    Default: 0.01\n"
+            "  -g <bp>\n    With -G: largest distance between consecutive loci of a region, >= 1\n    Default: 500\n"
+            "  -n <int>\n    With -G: smallest number of loci of a region, >= 1\n    Default: 3\n"
+            "  -t <CPU threads>\n    Number of CPU threads\n    Default: 8\n"
+            "  -d <int>\n    GPU ordinal\n    Default: 0\n",
+            exe);
+}
+
+// a whole field as a non-negative decimal integer of at most 18 digits -> true; a sign, a blank or anything else: false
+bool parse_count(const char* a, const char* b, long long& v) {
+    if (a == b || b - a > 18) return false;
+    v = 0;
+    for (; a < b; ++a) {
+        if (*a < '0' || *a > '9') return false;
+        v = v * 10 + (*a - '0');
+    }
+    return true;
+}
+
+// One <prefix>.<ctx>.cov.bed, plain or gzip, into partition `part` with motif `motif`: read in blocks of whole lines, each block
+// parsed by `threads` workers over contiguous runs of lines and handed to the engine run by run.  Empty lines are skipped.  false
+// with a message naming the file and, for a bad line, its number.
+bool load_cov_bed(hm_pileup_t* pe, const Fasta& fa, const std::vector<int64_t>& seq_start, const std::string& path, int part, uint32_t motif,
+                  int threads, uint64_t& n_rows) {
+    constexpr size_t BLOCK = size_t(32) << 20;
+    gzFile in = gzopen(path.c_str(), "rb");
+    if (!in) { fprintf(stderr, "ERROR: cannot open %s\n", path.c_str()); return false; }
+    struct Part {
+        std::vector<hm_locus_t> rows;
+        long long lines = 0, bad_line = 0;  // lines seen; the 1-based one among them that is bad, 0: none
+        std::string what;
+    };
+    std::vector<Part> parts((size_t)threads);
+    std::vector<size_t> cut((size_t)threads + 1);
+    std::string buf;
+    long long lines_before = 0;
+    bool eof = false, ok = true;
+    while (ok && !eof) {
+        const size_t have = buf.size();
+        buf.resize(have + BLOCK);
+        const int got = gzread(in, &buf[have], (unsigned)BLOCK);
+        if (got < 0) { fprintf(stderr, "ERROR: %s: cannot read (not a gzip or text file?)\n", path.c_str()); ok = false; break; }
+        buf.resize(have + (size_t)got);
+        eof = (size_t)got < BLOCK;
+        size_t end = buf.size();  // the block ends behind its last newline; the rest waits for the next read
+        if (!eof) {
+            const size_t nl = buf.rfind('\n');
+            if (nl == std::string::npos) continue;  // a line longer than a block: read on
+            end = nl + 1;
+        }
+        for (int k = 0; k <= threads; ++k) {  // worker k takes the lines that start in [cut[k], cut[k + 1])
+            size_t at = end * (size_t)k / (size_t)threads;
+            if (at > 0 && at < end) {
+                const void* nl = memchr(buf.data() + at - 1, '\n', end - at + 1);
+                at = nl ? (size_t)(static_cast<const char*>(nl) - buf.data()) + 1 : end;
+            }
+            cut[(size_t)k] = at;
+        }
+        parallel_run(threads, threads, [&](int k) {
+            Part& P = parts[(size_t)k];
+            P.rows.clear();
+            P.lines = P.bad_line = 0;
+            std::string last;
+            int sid = -1;
+            const char* p = buf.data() + cut[(size_t)k];
+            const char* const stop = buf.data() + cut[(size_t)k + 1];
+            while (p < stop) {
+                const char* nl = static_cast<const char*>(memchr(p, '\n', (size_t)(stop - p)));
+                const char* e = nl ? nl : stop;
+                const char* next = nl ? nl + 1 : stop;
+                if (e > p && e[-1] == '\r') --e;
+                ++P.lines;
+                if (e == p) { p = next; continue; }
+                const auto bad = [&](const std::string& what) { P.bad_line = P.lines; P.what = what; };
+                const char* col[7];  // starts of columns 1 .. 6 and the end of column 6
+                int nc = 0;
+                col[nc++] = p;
+                for (const char* q = p; q < e && nc < 7; ++q)
+                    if (*q == '\t') col[nc++] = q + 1;
+                if (nc < 6) { bad("fewer than 6 tab-separated columns"); return; }
+                if (nc == 6) col[6] = e + 1;
+                if (sid < 0 || last.size() != (size_t)(col[1] - 1 - col[0]) || memcmp(last.data(), col[0], last.size()) != 0) {
+                    last.assign(col[0], col[1] - 1);
+                    sid = fa.find(last);
+                    if (sid < 0) { bad("unknown sequence " + last); return; }
+                }
+                long long start = 0, stop1 = 0, pc = 0, nc_ = 0;
+                if (!parse_count(col[1], col[2] - 1, start) || start >= fa.length[(size_t)sid]) {
+                    bad("start is not an integer inside " + last + " (" + std::to_string(fa.length[(size_t)sid]) + " bases)");
+                    return;
+                }
+                if (!parse_count(col[2], col[3] - 1, stop1) || stop1 != start + 1) { bad("end is not start + 1"); return; }
+                if (!parse_count(col[4], col[5] - 1, pc) || !parse_count(col[5], col[6] - 1, nc_) || pc > INT32_MAX || nc_ > INT32_MAX) {
+                    bad("the counts in columns 5 and 6 must be integers in 0 .. 2147483647");
+                    return;
+                }
+                P.rows.push_back(hm_locus_t{seq_start[(size_t)sid] + start, (int32_t)pc, (int32_t)nc_, motif, 0});
+                p = next;
+            }
+        });
+        for (const Part& P : parts) {
+            if (P.bad_line) {
+                fprintf(stderr, "ERROR: %s:%lld: %s\n", path.c_str(), lines_before + P.bad_line, P.what.c_str());
+                ok = false;
+                break;
+            }
+            lines_before += P.lines;
+            const int64_t rc = hm_pileup_load_loci(pe, part, P.rows.data(), (int64_t)P.rows.size());
+            if (rc < 0) { fprintf(stderr, "ERROR: %s: %s\n", path.c_str(), hm_pileup_last_error(pe)); ok = false; break; }
+            n_rows += (uint64_t)rc;
+        }
+        buf.erase(0, end);
+    }
+    gzclose(in);
+    return ok;
+}
+
+// <prefix>.<ctx>.cov.bed, or that name with .gz behind it, whichever can be opened; empty if neither
+std::string find_cov_bed(const std::string& prefix, const char* ctx) {
+    for (const char* gz : {"", ".gz"}) {
+        const std::string path = prefix + "." + ctx + ".cov.bed" + gz;
+        if (FILE* f = fopen(path.c_str(), "rb")) { fclose(f); return path; }
+    }
+    return std::string();
+}
+
+}  // namespace
+
+int cmd_diff(int argc, char** argv) {
+    static const char* cn[3] = {"CpG", "CHG", "CHH"};
+    PileupOptions o;
+    int i = 2;
+    for (; i < argc; ++i) {
+        const std::string a = argv[i];
+        if (a == "-h") { diff_usage(argv[0]); return 0; }
+        if (a.size() < 2 || a[0] != '-') break;
+        if (a == "-Q") { o.asm_q = true; continue; }
+        if (a == "-G") { o.asm_regions = true; continue; }
+        if (i + 1 >= argc) { diff_usage(argv[0]); return EXIT_FAILURE; }
+        const char* v = argv[++i];
+        char* end = nullptr;
+        errno = 0;
+        if (a == "-t") o.threads = std::max(1, atoi(v));
+        else if (a == "-d") o.device = atoi(v);
+        else if (a == "-a") o.asm_min_cov = atoi(v);
+        else if (a == "-s") {
+            o.region_option_given = true;
+            o.region_max_p = strtod(v, &end);
+            if (end == v || *end || errno || !(o.region_max_p > 0.0 && o.region_max_p <= 1.0)) o.region_option_bad = true;
+        } else if (a == "-g" || a == "-n") {
+            o.region_option_given = true;
+            const long long x = strtoll(v, &end, 10);
+            if (end == v || *end || errno || x < 1 || (a == "-n" && x > INT_MAX)) o.region_option_bad = true;
+            else if (a == "-g") o.region_max_gap = x;
+            else o.region_min_loci = (int)x;
+        } else { fprintf(stderr, "ERROR: unrecognised option %s\n", a.c_str()); diff_usage(argv[0]); return EXIT_FAILURE; }
+    }
+    if (argc - i != 4) { diff_usage(argv[0]); return EXIT_FAILURE; }
+    const char* bad = o.asm_min_cov < 1 ? "-a must be >= 1"
+                      : o.region_option_given && !o.asm_regions ? "-s, -g and -n need -G"
+                      : o.region_option_bad ? "-s must be in (0, 1], -g and -n integers >= 1" : nullptr;
+    if (bad) { fprintf(stderr, "ERROR: %s\n", bad); diff_usage(argv[0]); return EXIT_FAILURE; }
+    o.ref = argv[i];
+    const std::string sample[2] = {argv[i + 1], argv[i + 2]};
+    o.prefix = argv[i + 3];
+    fprintf(stderr, "\n\n====================> Parameters:\nCPU threads: %d\nGenomic reference: %s\nsample 1: %s.<ctx>.cov.bed\nsample 2: %s.<ctx>.cov.bed\n"
+                    "output prefix: %s\ndiff: min sample coverage %d -> %s.diff.*\n",
+            o.threads, o.ref.c_str(), sample[0].c_str(), sample[1].c_str(), o.prefix.c_str(), o.asm_min_cov, o.prefix.c_str());
+    if (o.asm_q) fprintf(stderr, "diff: Benjamini-Hochberg q-values per context -> tenth column, %s.diff.summary.tsv\n", o.prefix.c_str());
+    if (o.asm_regions)
+        fprintf(stderr, "diff: regions of >= %d loci with p <= %g and one sign, gaps <= %lld -> %s.diff.regions.*\n", o.region_min_loci, o.region_max_p,
+                o.region_max_gap, o.prefix.c_str());
+    fprintf(stderr, "\n\n");
+
+    using clk = std::chrono::steady_clock;
+    const auto t_start = clk::now();
+    std::string files[3][2];  // found before the reference is read and the engine exists: a job without input needs neither
+    int n_ctx = 0;
+    for (int c = 0; c < 3; ++c) {
+        for (int s = 0; s < 2; ++s) files[c][s] = find_cov_bed(sample[s], cn[c]);
+        if (!files[c][0].empty() && !files[c][1].empty()) { ++n_ctx; continue; }
+        for (int s = 0; s < 2; ++s)
+            if (files[c][s].empty()) fprintf(stderr, "Skip context %s: %s.%s.cov.bed is missing\n", cn[c], sample[s].c_str(), cn[c]);
+        files[c][0].clear();
+    }
+    if (!n_ctx) { fprintf(stderr, "ERROR: no context has a cov.bed file of both samples\n"); return EXIT_FAILURE; }
+    Fasta fa;
+    std::string err;
+    if (!load_fasta(o.ref, fa, err)) { fprintf(stderr, "ERROR: %s\n", err.c_str()); return EXIT_FAILURE; }
+    if (fa.names.empty()) { fprintf(stderr, "ERROR: no sequence in %s\n", o.ref.c_str()); return EXIT_FAILURE; }
+    fprintf(stderr, "Load %zu sequences (%zu bases) from %s\n", fa.names.size(), fa.bases.size(), o.ref.c_str());
+    std::vector<int64_t> seq_start(fa.names.size() + 1, 0);
+    for (size_t s = 0; s < fa.names.size(); ++s) seq_start[s + 1] = seq_start[s] + fa.length[s];
+
+    hm_pileup_t* pe = nullptr;
+    if (hm_pileup_create(&pe, o.device) != HM_OK) { fprintf(stderr, "ERROR: %s\n", hm_pileup_last_error(nullptr)); return EXIT_FAILURE; }
+    std::unique_ptr<hm_pileup_t, decltype(&hm_pileup_destroy)> engine(pe, hm_pileup_destroy);  // destroyed on every way out
+    auto die = [&](const std::string& what) {
+        fprintf(stderr, "ERROR: %s: %s\n", what.c_str(), hm_pileup_last_error(pe));
+        return EXIT_FAILURE;
+    };
+    if (hm_pileup_set_option(pe, "partitions", 2) != HM_OK) return die("partitions");
+    if (hm_pileup_set_reference(pe, (int32_t)fa.names.size(), fa.length.data(), fa.bases.data()) != HM_OK) return die("reference");
+    uint64_t n_rows[2] = {0, 0};
+    for (int c = 0; c < 3; ++c)
+        for (int s = 0; s < 2 && !files[c][0].empty(); ++s)
+            if (!load_cov_bed(pe, fa, seq_start, files[c][s], s + 1, (uint32_t)c, o.threads, n_rows[s])) return EXIT_FAILURE;
+    const auto t_load = clk::now();
+    const int rc = write_partition_tests(pe, fa, o, "diff");
+    if (rc < 0) return die(rc == -1 ? "diff" : "diff regions");
+    if (rc == 0) return EXIT_FAILURE;
+    engine.reset();
+    const auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+    fprintf(stderr, "## %llu + %llu covered loci of %d contexts in %.2f s: parse + load %.2f s; test + BED %.2f s\n", (unsigned long long)n_rows[0],
+            (unsigned long long)n_rows[1], n_ctx, secs(t_start, clk::now()), secs(t_start, t_load), secs(t_load, clk::now()));
     return 0;
 }

@@ -19,6 +19,8 @@
 //   project_kernel  thread per column      : motif tests, plane lookup, wave-aggregated append of 12-byte records
 //   count_kernel<CountPlanes>    thread per record : atomic add into pcov / ncov, atomic max into the motif key
 //   count_kernel<CountHpPlanes>  the same + one more atomic add into the record's haplotype planes (partitions = 2 only)
+//   load_loci_kernel  thread per row       : (`diff`) the rows of a *.cov.bed file added into one partition's planes and the combined
+//                   ones, the key raised to the row's motif; bad rows (outside the reference, negative, a locus twice) counted
 //   The column kernels (identity, project, pattern, depth) and MemberSel see the staged batch as one BatchView; the tiled ones
 //   walk it with walk_columns, test a CpG member with cpg_columns / cpg_call and append with stage_record / flush_stage.
 //   pattern_kernel  thread per column      : (`pileup -E`) a CpG member that heads a window of k reference CpGs looks the other
@@ -444,6 +446,45 @@ __global__ __launch_bounds__(TPB) void count_kernel(const PRec* __restrict__ rec
             if (r.hp() == 1u) atomicAdd(pos ? &pl.pcov1[g] : &pl.ncov1[g], 1);
             else if (r.hp() == 2u) atomicAdd(pos ? &pl.pcov2[g] : &pl.ncov2[g], 1);
         }
+    }
+}
+
+// ---- counts from elsewhere (`diff`, hm_pileup_load_loci): rows of a *.cov.bed file into the planes of one partition -------------
+// A thread per row, grid-stride.  A row is checked before anything is written -- gpos inside [0, total), both counts >= 0,
+// motif <= 3, in this order, the first failure names the row -- and a bad row adds nothing.  A row without a count is skipped.
+// Every other row adds to its partition's planes and to the combined ones and raises the key to its motif (`order` bits stay 0);
+// the old values of the partition's two adds say whether the locus held a count of this partition already: a duplicate, which
+// still adds.  c[LOAD_ADDED] counts the rows that added, c[LOAD_BAD_*] the bad ones by kind: summed per wavefront, one global
+// atomic per wavefront and non-zero counter.  Integer adds only: the planes do not depend on row order or launch geometry.
+enum LoadCounter { LOAD_ADDED = 0, LOAD_BAD_GPOS, LOAD_BAD_COUNT, LOAD_BAD_MOTIF, LOAD_BAD_DUP, LOAD_COUNTERS };
+constexpr int64_t LOAD_SLAB_ROWS = int64_t(1) << 20, LOAD_SLAB_MAX = int64_t(1) << 24;  // 24 MB of rows on the device by default
+
+struct LoadPlanes : CountPlanes {  // the combined planes + those of the partition the rows go to
+    int32_t *part_pcov, *part_ncov;
+};
+
+__global__ __launch_bounds__(TPB) void load_loci_kernel(const hm_locus_t* __restrict__ rows, int64_t n, int64_t total, LoadPlanes pl,
+                                                         unsigned long long* __restrict__ c) {
+    uint32_t mine[LOAD_COUNTERS] = {0u, 0u, 0u, 0u, 0u};
+    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
+        const hm_locus_t r = rows[i];
+        if (r.gpos < 0 || r.gpos >= total) { ++mine[LOAD_BAD_GPOS]; continue; }
+        if (r.pcov < 0 || r.ncov < 0) { ++mine[LOAD_BAD_COUNT]; continue; }
+        if (r.motif > 3u) { ++mine[LOAD_BAD_MOTIF]; continue; }
+        if (r.pcov == 0 && r.ncov == 0) continue;
+        const int64_t g = r.gpos;
+        const int32_t old_p = atomicAdd(&pl.part_pcov[g], r.pcov);
+        const int32_t old_n = atomicAdd(&pl.part_ncov[g], r.ncov);
+        if (r.pcov) atomicAdd(&pl.pcov[g], r.pcov);
+        if (r.ncov) atomicAdd(&pl.ncov[g], r.ncov);
+        atomicMax(&pl.key[g], r.motif);
+        ++mine[LOAD_ADDED];
+        if (old_p != 0 || old_n != 0) ++mine[LOAD_BAD_DUP];
+    }
+    for (int k = 0; k < LOAD_COUNTERS; ++k) {
+        uint32_t v = mine[k];
+        for (int d = 32; d; d >>= 1) v += __shfl_down(v, d);
+        if ((threadIdx.x & 63) == 0 && v) atomicAdd(&c[k], (unsigned long long)v);
     }
 }
 
@@ -2058,8 +2099,14 @@ struct hm_pileup {
     // the sequence starts, and the device's CU count (0: not asked yet)
     DevBuf d_cxtab{EXACT}, d_cxoff{EXACT};
     int n_cus = 0;
+    // `diff` (hm_pileup_load_loci), allocated by the first load: one slab of LOAD_SLAB_ROWS rows, whatever a call brings, and the
+    // kernel's LOAD_COUNTERS counters.  The three flags are the engine's side of the rule "counts come from records or from
+    // loads, never both": a record was ever staged; a load has gone through; a load met a bad row (the planes mean nothing now)
+    DevBuf d_load{EXACT}, d_loadcnt{EXACT};
+    bool staged_any = false, loaded = false, load_failed = false;
+    int64_t load_slab = LOAD_SLAB_ROWS;  // option "load_slab": rows per slab of the next load
     uint32_t thr_packed = 0;   // the three thresholds of the last hm_pileup_count
-    bool counted = false;     // hm_pileup_count has run since hm_pileup_set_reference: what the -E, -M and -L fetches wait for
+    bool counted = false;    // hm_pileup_count has run since hm_pileup_set_reference: what the -E, -M and -L fetches wait for
     int64_t n_recs = 0;
     bool bins_ready = false;
 
@@ -2098,6 +2145,9 @@ const std::vector<double>& host_lfact() {
 
 inline int grid_for(int64_t n, int cap = 1 << 20) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + TPB - 1) / TPB, cap)); }
 
+// what every call over the engine's own planes answers once hm_pileup_load_loci has met a bad row
+const char* const LOAD_FAILED_TEXT = "a load of this engine met bad rows (hm_pileup_load_loci): its planes mean nothing";
+
 // the (pcov, ncov, key) arguments of a call over a plane range: each the caller's plane or, where NULL, the engine's own (with
 // pcov NULL plane_base is 0); false (error recorded) if there are none
 bool range_planes(hm_pileup* p, const void* pcov, const void* ncov, const void* key, int64_t& plane_base, RangePlanes& s) {
@@ -2105,6 +2155,10 @@ bool range_planes(hm_pileup* p, const void* pcov, const void* ncov, const void* 
     s.nc = ncov ? static_cast<const int32_t*>(ncov) : p->ncov;
     s.ky = key ? static_cast<const uint32_t*>(key) : p->key;
     if (!pcov) plane_base = 0;
+    if ((!pcov || !ncov || !key) && p->load_failed) {
+        pfail(p, HM_ESTATE, LOAD_FAILED_TEXT);
+        return false;
+    }
     if (s.pc && s.nc && s.ky) return true;
     pfail(p, HM_ESTATE, "no planes");
     return false;
@@ -2217,6 +2271,7 @@ int asm_planes(hm_pileup* p, const char* who, const void* pcov1, const void* nco
     if (given) return HM_OK;
     if (p->partitions != 2 || !p->hp_pcov[0] || !p->hp_pcov[1] || !p->key)
         return pfail(p, HM_ESTATE, w + " without partition planes (option partitions = 2, then hm_pileup_set_reference)");
+    if (p->load_failed) return pfail(p, HM_ESTATE, w + ": " + LOAD_FAILED_TEXT);
     if (!p->seq_off.empty() && hi > p->seq_off.back()) return pfail(p, HM_EINVAL, w + ": range past the reference");
     s = AsmPlanes{p->hp_pcov[0], p->hp_ncov[0], p->hp_pcov[1], p->hp_ncov[1], p->key};
     plane_base = 0;
@@ -2375,6 +2430,7 @@ int stage_alignment(hm_pileup* p, uint32_t order, int32_t flag, int32_t sid, int
                     const uint8_t* seq4, int32_t n_cigar, const uint32_t* cigar, int64_t n_entries, const void* entries, int32_t hp,
                     PRead& r, BatchMark& mark) {
     if (!p) return HM_EINVAL;
+    if (p->loaded || p->load_failed) return pfail(p, HM_ESTATE, "hm_pileup_submit_read on an engine whose counts were loaded (hm_pileup_load_loci)");
     if (hp < 0 || hp > 2) return pfail(p, HM_EINVAL, "haplotype partition must be 0, 1 or 2");
     if (hp && p->partitions != 2) return pfail(p, HM_ESTATE, "haplotype partition given but the partitions option is off");
     if (p->seq_off.empty()) return pfail(p, HM_ESTATE, "hm_pileup_submit_read before hm_pileup_set_reference");
@@ -2464,6 +2520,7 @@ void commit_read(hm_pileup* p, const PRead& r, const uint8_t* seq4) {
     p->slab.insert(p->slab.end(), seq4, seq4 + (r.l_qseq + 1) / 2);
     p->plane_len += r.l_qseq;
     p->reads.push_back(r);
+    p->staged_any = true;
 }
 
 }  // namespace
@@ -2533,6 +2590,10 @@ int hm_pileup_set_option(hm_pileup_t* p, const char* key, double value) {
         if (!(value >= 0.0 && value <= (double)INT32_MAX) || value != std::floor(value))
             return pfail(p, HM_EINVAL, k + " must be an integer >= 0");
         (k == "trim5" ? p->trim.n5 : p->trim.n3) = (int32_t)std::min(value, (double)(1 << 22));
+    } else if (k == "load_slab") {  // the device holds one slab of rows whatever a load brings; at any time
+        if (!(value >= 1.0 && value <= (double)LOAD_SLAB_MAX) || value != std::floor(value))
+            return pfail(p, HM_EINVAL, "load_slab must be an integer in 1 .. 2^24");
+        p->load_slab = (int64_t)value;
     } else return pfail(p, HM_EINVAL, "unknown option " + k);
     return HM_OK;
 }
@@ -2877,6 +2938,52 @@ int64_t hm_pileup_fetch_loci(hm_pileup_t* p, const void* pcov, const void* ncov,
     if (!range_planes(p, pcov, ncov, key, plane_base, s)) return HM_ESTATE;
     if (hi == lo) return 0;
     return compact_rows(p, LociSel{s, plane_base}, lo, hi, out, cap, no_hook, no_hook);
+}
+
+// ---- `diff` -----------------------------------------------------------------------------------------------------------------------
+int64_t hm_pileup_load_loci(hm_pileup_t* p, int32_t part, const hm_locus_t* rows, int64_t n) {
+    if (!p) return HM_EINVAL;
+    if ((part != 1 && part != 2) || n < 0 || (n && !rows)) return pfail(p, HM_EINVAL, "hm_pileup_load_loci: part must be 1 or 2, n >= 0, rows not NULL");
+    if (p->load_failed) return pfail(p, HM_ESTATE, std::string("hm_pileup_load_loci: ") + LOAD_FAILED_TEXT);
+    if (p->partitions != 2 || p->seq_off.empty() || !p->pcov || !p->hp_pcov[0] || !p->hp_pcov[1])
+        return pfail(p, HM_ESTATE, "hm_pileup_load_loci needs option partitions = 2 and hm_pileup_set_reference");
+    if (p->staged_any) return pfail(p, HM_ESTATE, "hm_pileup_load_loci on an engine that has staged records: counts come from records or from loads, not both");
+    if (n == 0) return 0;
+    const int64_t slab = p->load_slab;
+    unsigned long long c[LOAD_COUNTERS] = {0, 0, 0, 0, 0};
+    const int rc = guarded(p, [&] {
+        p->d_load.reserve(sizeof(hm_locus_t) * (size_t)slab);
+        p->d_loadcnt.reserve(sizeof c);
+        HIP_TRY(hipMemsetAsync(p->d_loadcnt.p, 0, sizeof c, p->stream));
+        const LoadPlanes pl{{p->pcov, p->ncov, p->key}, p->hp_pcov[part - 1], p->hp_ncov[part - 1]};
+        for (int64_t at = 0; at < n; at += slab) {  // the copy of a slab follows the kernel over the one before it in the stream
+            const int64_t m = std::min(slab, n - at);
+            HIP_TRY(hipMemcpyAsync(p->d_load.p, rows + at, sizeof(hm_locus_t) * (size_t)m, hipMemcpyHostToDevice, p->stream));
+            hipLaunchKernelGGL(load_loci_kernel, dim3(grid_for(m, 4096)), dim3(TPB), 0, p->stream, p->d_load.as<hm_locus_t>(), m,
+                               p->seq_off.back(), pl, p->d_loadcnt.as<unsigned long long>());
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipMemcpyAsync(c, p->d_loadcnt.p, sizeof c, hipMemcpyDeviceToHost, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        return HM_OK;
+    });
+    if (rc < 0) return rc;
+    const unsigned long long bad = c[LOAD_BAD_GPOS] + c[LOAD_BAD_COUNT] + c[LOAD_BAD_MOTIF] + c[LOAD_BAD_DUP];
+    if (bad) {
+        p->load_failed = true;
+        static const char* kind[LOAD_COUNTERS] = {"", "gpos outside the reference", "negative count", "motif above 3",
+                                                  "locus given twice for one part"};
+        std::string msg = "hm_pileup_load_loci: " + std::to_string(bad) + " bad rows";
+        const char* sep = ": ";
+        for (int k = LOAD_BAD_GPOS; k < LOAD_COUNTERS; ++k) {
+            if (!c[k]) continue;
+            msg += sep + std::to_string(c[k]) + " " + kind[k];
+            sep = ", ";
+        }
+        return pfail(p, HM_EDATA, msg);
+    }
+    p->loaded = true;
+    return (int64_t)c[LOAD_ADDED];
 }
 
 // ---- `pileup -E` ------------------------------------------------------------------------------------------------------------------

@@ -27,6 +27,10 @@ rows with pvalue <= max_p and a difference of the same sign, at most max_gap apa
 rows with the pooled counts (ASM_REGION_DTYPE); `pu.asm_regions_bed(rows)` is the text of <prefix>.asm.regions.<ctx>.bed, and
 `stitch_asm_regions(parts, ...)` -- host only -- joins the chains of adjacent ranges into what one fetch over their union returns.
 
+Two samples instead of two haplotypes (`hifimeth-hip diff`): on an engine made with partitions=True that never saw a read,
+`pu.load_loci(1, *read_cov_bed(path1, names, offsets))` and the same for part 2 put two samples' <prefix>.<ctx>.cov.bed rows into
+the partition planes; the three paragraphs above then hold for sample 1 against sample 2, unchanged.
+
 Binomial test per locus (`pileup -B control` / `-e r,r,r`): is a locus methylated at all, against the caller's false-positive
 rate?  `pu.control_sums(lo, hi)` over an unmethylated control sequence gives the rates (`rates_from_sums`), `pu.site_histogram()`
 counts the loci per (motif, pcov, pcov + ncov), `sites_table(rates, bins, big)` -- host only, the C library's -- solves p-values
@@ -102,6 +106,7 @@ There is no CPU fallback: construction fails without the HIP library and a gfx95
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -733,6 +738,55 @@ def locate(offsets, gpos) -> Tuple[np.ndarray, np.ndarray]:
     return sid, gpos - offsets[sid]
 
 
+def read_cov_bed(path: str, fasta_names: Sequence[str], offsets, motif: Optional[int] = None):
+    """`diff`: one <prefix>.<ctx>.cov.bed, plain or gzip -> (gpos, pcov, ncov, motif) as int64, int32, int32, uint32 arrays, the
+    arguments of MethylationPileup.load_loci.  offsets = the n + 1 sequence starts of the concatenated reference; motif = the
+    file's context index (0 CpG, 1 CHG, 2 CHH), by default read from the file name.  A row is chrom, start, start + 1, a column
+    that is not read, pcov, ncov; further columns (cov2bed's motif) are ignored and empty lines skipped.  ValueError naming file and
+    line for fewer than 6 tab-separated columns, an unknown sequence, a start that is no integer inside the sequence,
+    end != start + 1, or a count that is not a plain decimal integer in 0 .. 2^31 - 1."""
+    import gzip
+    if motif is None:
+        found = [c for c, n in enumerate(CTX_NAMES) if (".%s.cov.bed" % n) in os.path.basename(path)]
+        if len(found) != 1:
+            raise ValueError(f"{path}: the context is not in the file name, give motif")
+        motif = found[0]
+    offsets = np.asarray(offsets, np.int64)
+    sid_of = {n: i for i, n in enumerate(fasta_names)}
+    with open(path, "rb") as f:
+        gz = f.read(2) == b"\x1f\x8b"
+    gpos, pcov, ncov = [], [], []
+
+    def number(text):                                         # digits only, at most 18 of them: what the CLI takes
+        return int(text) if text.isascii() and text.isdigit() and len(text) <= 18 else None
+
+    with (gzip.open(path, "rt", newline="\n") if gz else open(path, "r", newline="\n")) as f:   # a line ends at \n, as in the CLI
+        for no, line in enumerate(f, 1):
+            line = line.rstrip("\n")
+            if line.endswith("\r"):
+                line = line[:-1]
+            if not line:
+                continue
+            col = line.split("\t")
+            bad = lambda what: ValueError(f"{path}:{no}: {what}")  # noqa: E731
+            if len(col) < 6:
+                raise bad("fewer than 6 tab-separated columns")
+            if col[0] not in sid_of:
+                raise bad(f"unknown sequence {col[0]}")
+            sid = sid_of[col[0]]
+            start, end, p, n = number(col[1]), number(col[2]), number(col[4]), number(col[5])
+            if start is None or start >= offsets[sid + 1] - offsets[sid]:
+                raise bad(f"start is not an integer inside {col[0]} ({int(offsets[sid + 1] - offsets[sid])} bases)")
+            if end != start + 1:
+                raise bad("end is not start + 1")
+            if p is None or n is None or p > 0x7fffffff or n > 0x7fffffff:
+                raise bad("the counts in columns 5 and 6 must be integers in 0 .. 2147483647")
+            gpos.append(int(offsets[sid]) + start)
+            pcov.append(p)
+            ncov.append(n)
+    return (np.array(gpos, np.int64), np.array(pcov, np.int32), np.array(ncov, np.int32), np.full(len(gpos), motif, np.uint32))
+
+
 class MethylationPileup:
     def __init__(self, genome: Sequence[Tuple[str, str]], device: int = 0, min_mapq: int = 0, min_pi: float = 0.0,
                  planes=None, partitions: bool = False, partition_planes=None, bases=None, patterns: int = 0,
@@ -910,6 +964,18 @@ class MethylationPileup:
         else:
             ptrs = [None, None, None]
         return self._rows(self._L.hm_pileup_fetch_loci, LOCUS_DTYPE, *ptrs, plane_base, lo, hi)
+
+    def load_loci(self, part: int, gpos, pcov, ncov, motif) -> int:
+        """`diff` (hm_pileup_load_loci): counts from elsewhere -- the rows of a sample's *.cov.bed, as read_cov_bed returns them
+        -- added into partition `part` (1 or 2) and the combined planes; motif an array or one context index for all rows.  Needs
+        partitions=True and an engine that never saw a read; afterwards loci(), asm(), asm_histogram(), asm_regions() and the
+        other plane fetches work as after count(), part 1 against part 2.  -> the number of rows that added a count.
+        HifimethError for a row outside the reference, a negative count, a motif above 3 or a locus given twice for one part:
+        the engine's planes are then void and it refuses further loads and fetches."""
+        gpos = np.ascontiguousarray(gpos, np.int64)
+        rows = np.zeros(len(gpos), LOCUS_DTYPE)
+        rows["gpos"], rows["pcov"], rows["ncov"], rows["motif"] = gpos, pcov, ncov, motif
+        return self._check(self._L.hm_pileup_load_loci(self._h, part, rows.ctypes.data_as(C.c_void_p), len(rows)))
 
     def bed(self, loci: np.ndarray) -> dict:
         """the text of <prefix>.{CpG,CHG,CHH}.cov.bed (pileup.cpp:562-590)"""

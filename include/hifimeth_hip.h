@@ -210,6 +210,7 @@ int hm_reset_timing(hm_engine_t* e);
  *   per-locus pcov / ncov / motif           (pileup.cpp:519-560)                     -> hm_pileup_count
  *   rows of <prefix>.<ctx>.cov.bed          (pileup.cpp:562-590)                     -> hm_pileup_fetch_loci
  *   (ours) haplotype difference per locus, rows of <prefix>.asm.<ctx>.bed         -> hm_pileup_fetch_asm
+ *   (ours) two samples' *.cov.bed rows into the haplotype planes (`diff`)         -> hm_pileup_load_loci
  * The whole genome's counters stay resident in HBM (12 B per reference base, 28 B with the haplotype partitions) and the
  * projected calls wait in HBM (12 B each) until the thresholds are known -- the reference spills them to a temporary file.
  * MM/ML parsing and BED text formatting stay on the host (hm_bam.h).                                           */
@@ -238,7 +239,8 @@ const char* hm_pileup_last_error(const hm_pileup_t* p); /* p may be NULL: error 
 /* options: "min_mapq" (-q, default 0), "min_pi" (-f, default 0.0), "partitions" (0 default, or 2: haplotype-resolved
  * counting, see hm_pileup_submit_read_hp; must be set before hm_pileup_set_reference / hm_pileup_use_planes, else HM_ESTATE),
  * "patterns" and "pattern_span" (read-level CpG patterns), "bedmethyl" (per-CpG depth classes), "linkage" (co-methylation by
- * distance), "profile" (methylation by position in the read) and "trim5" / "trim3" (end trimming), all near the end of this header */
+ * distance), "profile" (methylation by position in the read) and "trim5" / "trim3" (end trimming), all near the end of this header;
+ * "load_slab" (hm_pileup_load_loci) */
 int hm_pileup_set_option(hm_pileup_t* p, const char* key, double value);
 /* HbnDatabase: n_seqs upper-cased sequences back to back in `bases` (seq_len[i] bytes each).  Allocates and
  * zeroes the per-locus planes unless hm_pileup_use_planes was called before. */
@@ -402,6 +404,30 @@ int64_t hm_pileup_fetch_asm_regions(hm_pileup_t* p, const void* pcov1, const voi
                                     const void* key, int64_t plane_base, int64_t lo, int64_t hi, int32_t min_cov, int32_t ctx,
                                     double max_p, int64_t max_gap, int32_t min_loci, int32_t keep_edges, int64_t* n_ctx_rows,
                                     hm_asm_region_t* out, int64_t cap);
+
+/* ---- two samples instead of two haplotypes (`diff`): counts loaded into the partition planes -------------------
+ * The three families above are functions of two pairs of count planes and a key plane; they know nothing about haplotypes.  This
+ * call fills those planes from rows -- the rows of two samples' <prefix>.<ctx>.cov.bed files -- instead of from records, and the
+ * engine then answers every fetch that works after hm_pileup_count (hm_pileup_fetch_loci, the asm family, regions, context,
+ * domains, sites) as if part 1 and part 2 were HP 1 and HP 2.
+ * rows[0, n): HOST memory, any order.  Each row is checked in this order, and the first failure names it: gpos in [0, total
+ * reference length); pcov >= 0 and ncov >= 0; motif <= 3.  A row that passes and has pcov + ncov == 0 is ignored.  Every other
+ * row ADDS pcov / ncov to the planes of `part` (1 or 2) and to the combined planes -- which so hold the pooled sample -- and
+ * raises the key plane at gpos to max(key, motif): where the two samples disagree about a locus' context the LARGER code wins;
+ * the `order` bits of the key stay 0.  A row that adds to a locus that already held a count of the SAME part -- from this call or
+ * an earlier one -- is a duplicate.  The pooled counts of a locus must stay below 2^31 (not checked).
+ * Returns the number of rows that added a count.  If any row was bad (out of range, negative, motif, duplicate): HM_EDATA,
+ * hm_pileup_last_error gives their number and the number of each kind, and the planes mean nothing any more (the good rows and
+ * the duplicates were added): every further load, and every fetch over the engine's own planes, returns HM_ESTATE.
+ * HM_ESTATE also without option "partitions" = 2, before hm_pileup_set_reference (planes registered with hm_pileup_use_planes /
+ * _use_partition_planes are loaded into, but the reference gives the length), and on an engine that ever staged a record:
+ * counts come from records or from loads, never both, and after a successful load hm_pileup_submit_read* return HM_ESTATE.
+ * HM_EINVAL for part outside {1, 2}, n < 0, or rows NULL with n > 0.  May be called any number of times, for either part, in any
+ * interleaving.  The rows go through one device slab of "load_slab" rows (option, 1 .. 2^24, default 2^20 = 24 MB; may be set at
+ * any time), slab by slab on the engine's stream: no device memory grows with n.  All adds are integer atomics: the planes depend
+ * on neither row order, slab size nor launch geometry.  Not here: pileup_dist (one card holds both samples of a human genome at
+ * 28 B per base), more than two samples, replicates. */
+int64_t hm_pileup_load_loci(hm_pileup_t* p, int32_t part, const hm_locus_t* rows, int64_t n);
 
 /* ---- per-locus binomial test (`pileup -B / -e`): is a locus methylated at all ------------------------
  * Against a false-positive rate e per context -- given, or measured on an unmethylated control sequence as sum(pcov) /

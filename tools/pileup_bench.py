@@ -29,9 +29,13 @@ error-free: the column kernel and the record count run at full size, the deletio
 `--digest`: a sha256 of every output that must not depend on the build -- the records of one pass (sorted by order, gpos, motif: the
 append order is not fixed), the loci of the combined set and of each partition, and the rows of `--patterns`, `--bedmethyl` (each set)
 and `--linkage` -- under "digest" in the JSON object, for comparing two builds of the library (HM_LIB_PATH) byte for byte.
+`--load`: the loader of `diff` (hm_pileup_load_loci) on an engine of its own behind the main run: 2^24 rows on distinct loci of a
+reference of 2^28 bases, part 1 in ascending order (a *.cov.bed file's) and part 2 shuffled, whole calls -- the H2D of 24 bytes per row
+from pageable memory slab by slab, the kernel, the counters' download -- in rows per second, beside the main run's `records_per_s_count`
+(count_kernel over its resident 12-byte records: no H2D, one or two atomic adds and an atomic max per record) as the yardstick.
 `--parts N` (with `--domains`): the same segments chained from N equal pieces next to the single fetch (three stateless passes per piece).
 
-    python tools/pileup_bench.py --genome-mb 20 --coverage 10 [--partitions [--asm [--asm-q] [--asm-regions]]] [--sites] [--domains [--fit] [--parts N]] [--patterns K] [--bedmethyl] [--linkage D] [--readpos D]
+    python tools/pileup_bench.py --genome-mb 20 --coverage 10 [--partitions [--asm [--asm-q] [--asm-regions]]] [--sites] [--domains [--fit] [--parts N]] [--patterns K] [--bedmethyl] [--linkage D] [--readpos D] [--load]
 """
 import argparse
 import ctypes as C
@@ -148,6 +152,38 @@ def context_leg(log2_loci, repeat, check):
     print(json.dumps(out))
 
 
+def load_leg(check):
+    """`diff`: hm_pileup_load_loci of LOAD_ROWS rows into a reference of LOAD_BASES bases -> the leg's entries of the JSON object"""
+    from hifimeth_amd.pileup import LOCUS_DTYPE
+    LOAD_BASES, LOAD_ROWS = 1 << 28, 1 << 24
+    rng = np.random.default_rng(11)
+    step = LOAD_BASES // LOAD_ROWS
+    rows = np.zeros(LOAD_ROWS, LOCUS_DTYPE)
+    rows["gpos"] = np.arange(LOAD_ROWS, dtype=np.int64) * step + rng.integers(0, step, LOAD_ROWS)   # distinct and ascending
+    rows["pcov"], rows["ncov"] = rng.integers(1, 30, LOAD_ROWS), rng.integers(0, 30, LOAD_ROWS)
+    rows["motif"] = rng.integers(0, 3, LOAD_ROWS)
+    shuffled = rows[rng.permutation(LOAD_ROWS)]
+    pu = MethylationPileup([("chr1", LOAD_BASES)], partitions=True, bases=np.full(LOAD_BASES, ord("N"), np.uint8))
+    none = np.zeros(1, LOCUS_DTYPE)
+    assert pu._L.hm_pileup_load_loci(pu._h, 1, none.ctypes.data_as(C.c_void_p), 1) == 0       # warm-up: the slab, the code object
+    secs = {}
+    for name, part, r in (("sorted", 1, rows), ("shuffled", 2, shuffled)):
+        t0 = time.perf_counter()
+        n = pu._L.hm_pileup_load_loci(pu._h, part, r.ctypes.data_as(C.c_void_p), LOAD_ROWS)
+        secs[name] = time.perf_counter() - t0
+        assert n == LOAD_ROWS, pu._L.hm_pileup_last_error(pu._h)
+    out = dict(load_rows=LOAD_ROWS, load_reference_bases=LOAD_BASES, load_call_s={k: round(v, 4) for k, v in secs.items()},
+               load_rows_per_s={k: round(LOAD_ROWS / v) for k, v in secs.items()})
+    if check:                                      # the pooled planes hold both parts' counts, each part's its own
+        pooled, parts = pu.loci(), [pu.loci(partition=k) for k in (1, 2)]
+        out["check_load_planes_hold_the_rows"] = bool(
+            all(len(x) == LOAD_ROWS and (x["gpos"] == rows["gpos"]).all() for x in [pooled] + parts)
+            and (parts[0]["pcov"] == rows["pcov"]).all() and (parts[1]["ncov"] == rows["ncov"]).all()
+            and (pooled["pcov"] == 2 * rows["pcov"]).all() and (pooled["motif"] == rows["motif"]).all())
+    pu.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--genome-mb", type=float, default=20)
@@ -184,6 +220,9 @@ def main():
     ap.add_argument("--context", type=int, default=0, metavar="LOG2",
                     help="time the k-mer tables (pileup -S 0 .. 3) on both accumulation paths over synthetic planes of 2^LOG2 loci, 5 %% "
                          "covered, against the interval index build over the same planes; a leg of its own: nothing else is run")
+    ap.add_argument("--load", action="store_true",
+                    help="time the loader of `diff` (hm_pileup_load_loci): 2^24 rows into a reference of 2^28 bases on an engine of its own, "
+                         "reported beside records_per_s_count of this run")
     ap.add_argument("--bedmethyl", action="store_true", help="time what the per-CpG depth classes add (pileup -M, min_valid 1)")
     ap.add_argument("--digest", action="store_true", help="add a sha256 of the records, the loci and the rows of the timed options")
     ap.add_argument("--cpu-baseline", action="store_true",
@@ -578,6 +617,10 @@ def main():
         out["digest"] = digest
     if a.cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(genome, chrom, starts, staged, a.read_len)
+    if a.load:
+        pu.close()                                 # the leg's engine holds 28 B per base of its own reference
+        out.update(load_leg(a.check))
+        out["load_rows_per_s_to_count_records_per_s"] = {k: round(v / out["records_per_s_count"], 3) for k, v in out["load_rows_per_s"].items()}
     print(json.dumps(out))
 
 
