@@ -39,6 +39,7 @@
 
 #include "../../include/hifimeth_hip.h"
 #include "hm_bam.h"
+#include "hm_cli.h"
 
 using namespace hmbam;
 
@@ -891,15 +892,6 @@ int cmd_modlist(int argc, char** argv) {
 }
 
 }  // namespace
-
-int cmd_pileup(int argc, char** argv);   // hifimeth_pileup.cpp
-int cmd_fastats(int argc, char** argv);  // hifimeth_pileup.cpp
-int cmd_thresholds(int argc, char** argv);
-int cmd_corr(int argc, char** argv);     // hifimeth_pileup.cpp
-int cmd_cov2bed(int argc, char** argv);  // hifimeth_pileup.cpp
-int cmd_diff(int argc, char** argv);     // hifimeth_pileup.cpp
-int cmd_sample(int argc, char** argv);   // hifimeth_pileup.cpp
-int cmd_eval(int argc, char** argv);     // hifimeth_pileup.cpp
 
 int main(int argc, char** argv) {
     if (argc < 2) { usage(); return EXIT_FAILURE; }
