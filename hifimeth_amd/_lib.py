@@ -133,6 +133,11 @@ def lib():
         "hm_pileup_fetch_asm_regions": (i64, [vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, C.c_double, i64, i32, i32,
                                               C.POINTER(i64), vp, i64]),
         "hm_pileup_load_loci": (i64, [vp, i32, vp, i64]),
+        "hm_pileup_group_sample": (C.c_int, [vp, i32]),
+        "hm_pileup_load_sample_loci": (i64, [vp, vp, i64]),
+        "hm_pileup_fetch_groups": (i64, [vp, i64, i64, i32, vp, i64]),
+        "hm_pileup_group_planes": (C.c_int, [vp, i32, i64, i64, vp, vp]),
+        "hm_group_qvalues": (C.c_int, [vp, i64, vp, vp]),
         "hm_pileup_control_sums": (C.c_int, [vp, vp, vp, vp, i64, i64, vp]),
         "hm_pileup_site_histogram": (i64, [vp, vp, vp, vp, i64, i64, i64, vp, vp, i64]),
         "hm_sites_table": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp]),

@@ -1115,7 +1115,8 @@ bool parse_count(const char* a, const char* b, long long& v) {
     return true;
 }
 
-// One <prefix>.<ctx>.cov.bed, plain or gzip, into partition `part` with motif `motif`: read in blocks of whole lines, each block
+// One <prefix>.<ctx>.cov.bed, plain or gzip, into partition `part` -- or, with part 0, into the open sample of `groupdiff`
+// (hm_pileup_load_sample_loci) -- with motif `motif`: read in blocks of whole lines, each block
 // parsed by `threads` workers over contiguous runs of lines and handed to the engine run by run.  Empty lines are skipped.  false
 // with a message naming the file and, for a bad line, its number.
 bool load_cov_bed(hm_pileup_t* pe, const Fasta& fa, const std::vector<int64_t>& seq_start, const std::string& path, int part, uint32_t motif,
@@ -1203,7 +1204,8 @@ bool load_cov_bed(hm_pileup_t* pe, const Fasta& fa, const std::vector<int64_t>& 
                 break;
             }
             lines_before += P.lines;
-            const int64_t rc = hm_pileup_load_loci(pe, part, P.rows.data(), (int64_t)P.rows.size());
+            const int64_t rc = part ? hm_pileup_load_loci(pe, part, P.rows.data(), (int64_t)P.rows.size())
+                                    : hm_pileup_load_sample_loci(pe, P.rows.data(), (int64_t)P.rows.size());
             if (rc < 0) { fprintf(stderr, "ERROR: %s: %s\n", path.c_str(), hm_pileup_last_error(pe)); ok = false; break; }
             n_rows += (uint64_t)rc;
         }
@@ -1279,5 +1281,148 @@ int cmd_diff(int argc, char** argv) {
     const auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
     fprintf(stderr, "## %llu + %llu covered loci of %d contexts in %.2f s: parse + load %.2f s; test + BED %.2f s\n", (unsigned long long)n_rows[0],
             (unsigned long long)n_rows[1], n_ctx, secs(t_start, clk::now()), secs(t_start, t_load), secs(t_load, clk::now()));
+    return 0;
+}
+
+// ---- groupdiff [OPTIONS] reference a1,a2,... b1,b2,... out-prefix (ours) --------------------------------------------------------------
+// Differential methylation between two groups of replicates: every list element is a prefix as `diff` takes it, every sample is
+// loaded as one sample of its group (hm_pileup_group_sample, hm_pileup_load_sample_loci), and the loci with at least -r counting
+// samples on both sides are tested with the spread between the replicates (hm_pileup_fetch_groups).  The rows
+// of the whole reference wait on the host (64 B each) for their q-values (hm_group_qvalues) and are then written.
+namespace {
+struct GroupQRow {  // what write_rows formats: the row and its q, named by gpos and motif as every row
+    int64_t gpos;
+    uint32_t motif;
+    const hm_group_t* g;
+    double q;
+};
+
+std::vector<std::string> split_list(const std::string& text) {
+    std::vector<std::string> items(1);
+    for (const char c : text) {
+        if (c == ',') items.emplace_back();
+        else items.back() += c;
+    }
+    return items;
+}
+}  // namespace
+
+int cmd_groupdiff(int argc, char** argv) {
+    static const char* cn[3] = {"CpG", "CHG", "CHH"};
+    PileupOptions o;
+    int first = 0, status = 0;
+    if (!parse_command_line(CMD_GROUPDIFF, argc, argv, o, first, status)) return status;
+    o.ref = argv[first];
+    const std::vector<std::string> group[2] = {split_list(argv[first + 1]), split_list(argv[first + 2])};
+    o.prefix = argv[first + 3];
+    fprintf(stderr, "\n\n====================> Parameters:\nCPU threads: %d\nGenomic reference: %s\n", o.threads, o.ref.c_str());
+    for (int g = 0; g < 2; ++g)
+        for (size_t i = 0; i < group[g].size(); ++i) fprintf(stderr, "group %d sample %zu: %s.<ctx>.cov.bed\n", g + 1, i + 1, group[g][i].c_str());
+    fprintf(stderr, "output prefix: %s\ngroupdiff: min sample coverage %lld, min replicates per group %lld -> %s.groups.*\n\n\n", o.prefix.c_str(),
+            o.group_min_cov, o.group_min_reps, o.prefix.c_str());
+
+    using clk = std::chrono::steady_clock;
+    const auto t_start = clk::now();
+    for (int g = 0; g < 2; ++g) {
+        for (const std::string& s : group[g])
+            if (s.empty()) { fprintf(stderr, "ERROR: an empty prefix in the list of group %d\n", g + 1); return EXIT_FAILURE; }
+        if ((long long)group[g].size() < o.group_min_reps) {
+            fprintf(stderr, "ERROR: group %d has %zu samples, fewer than -r %lld\n", g + 1, group[g].size(), o.group_min_reps);
+            return EXIT_FAILURE;
+        }
+        if (group[g].size() > 255) { fprintf(stderr, "ERROR: group %d has more than 255 samples\n", g + 1); return EXIT_FAILURE; }
+    }
+    std::vector<std::string> files[3][2];  // found before the reference is read and the engine exists, as in `diff`
+    int n_ctx = 0;
+    for (int c = 0; c < 3; ++c) {
+        bool all = true;
+        for (int g = 0; g < 2; ++g)
+            for (const std::string& s : group[g]) {
+                files[c][g].push_back(find_cov_bed(s, cn[c]));
+                if (!files[c][g].back().empty()) continue;
+                fprintf(stderr, "Skip context %s: %s.%s.cov.bed is missing\n", cn[c], s.c_str(), cn[c]);
+                all = false;
+            }
+        if (all) ++n_ctx;
+        else files[c][0].clear();
+    }
+    if (!n_ctx) { fprintf(stderr, "ERROR: no context has a cov.bed file of every sample\n"); return EXIT_FAILURE; }
+    Fasta fa;
+    std::string err;
+    if (!load_fasta(o.ref, fa, err)) { fprintf(stderr, "ERROR: %s\n", err.c_str()); return EXIT_FAILURE; }
+    if (fa.names.empty()) { fprintf(stderr, "ERROR: no sequence in %s\n", o.ref.c_str()); return EXIT_FAILURE; }
+    fprintf(stderr, "Load %zu sequences (%zu bases) from %s\n", fa.names.size(), fa.bases.size(), o.ref.c_str());
+    std::vector<int64_t> seq_start(fa.names.size() + 1, 0);
+    for (size_t s = 0; s < fa.names.size(); ++s) seq_start[s + 1] = seq_start[s] + fa.length[s];
+
+    hm_pileup_t* pe = nullptr;
+    if (hm_pileup_create(&pe, o.device) != HM_OK) { fprintf(stderr, "ERROR: %s\n", hm_pileup_last_error(nullptr)); return EXIT_FAILURE; }
+    std::unique_ptr<hm_pileup_t, decltype(&hm_pileup_destroy)> engine(pe, hm_pileup_destroy);  // destroyed on every way out
+    auto die = [&](const std::string& what) { return engine_error(pe, what); };
+    if (hm_pileup_set_option(pe, "partitions", 2) != HM_OK || hm_pileup_set_option(pe, "groups", 1) != HM_OK ||
+        hm_pileup_set_option(pe, "group_min_cov", (double)o.group_min_cov) != HM_OK)
+        return die("groups");
+    if (hm_pileup_set_reference(pe, (int32_t)fa.names.size(), fa.length.data(), fa.bases.data()) != HM_OK) return die("reference");
+    uint64_t n_rows[2] = {0, 0};
+    for (int g = 0; g < 2; ++g)
+        for (size_t i = 0; i < group[g].size(); ++i) {  // a sample's contexts share its seen bitmap: one locus, one context
+            if (hm_pileup_group_sample(pe, g + 1) < 0) return die("group sample");
+            for (int c = 0; c < 3; ++c)
+                if (!files[c][0].empty() && !load_cov_bed(pe, fa, seq_start, files[c][g][i], 0, (uint32_t)c, o.threads, n_rows[g])) return EXIT_FAILURE;
+        }
+    const auto t_load = clk::now();
+
+    std::vector<hm_group_t> rows;
+    for (size_t s = 0; s < fa.names.size(); ++s) {
+        const int64_t n = hm_pileup_fetch_groups(pe, seq_start[s], seq_start[s + 1], (int32_t)o.group_min_reps, nullptr, 0);
+        if (n < 0) return die("groups");
+        if (n == 0) continue;
+        rows.resize(rows.size() + (size_t)n);
+        if (hm_pileup_fetch_groups(pe, seq_start[s], seq_start[s + 1], (int32_t)o.group_min_reps, rows.data() + rows.size() - n, n) != n) return die("groups");
+    }
+    engine.reset();
+    std::vector<double> q(rows.size());
+    uint64_t m[3];
+    if (hm_group_qvalues(rows.data(), (int64_t)rows.size(), q.data(), m) != HM_OK) {
+        fprintf(stderr, "ERROR: groupdiff: the tested loci are not rows the engine wrote\n");
+        return EXIT_FAILURE;
+    }
+    {
+        CtxFiles out;
+        if (!out.open(o.prefix, "groups.", ".bed")) return EXIT_FAILURE;
+        write_rows<GroupQRow>(
+            fa, out.f, o.threads,
+            [&](int64_t lo, int64_t hi, GroupQRow* dst, int64_t cap) {  // the rows are ascending in gpos
+                const auto at = [&](int64_t g) {
+                    return std::lower_bound(rows.begin(), rows.end(), g, [](const hm_group_t& r, int64_t v) { return r.gpos < v; }) - rows.begin();
+                };
+                const int64_t a = at(lo), b = at(hi);
+                for (int64_t i = a; dst && b - a <= cap && i < b; ++i) dst[i - a] = GroupQRow{rows[(size_t)i].gpos, rows[(size_t)i].motif, &rows[(size_t)i], q[(size_t)i]};
+                return b - a;
+            },
+            [](const GroupQRow& r, int64_t k, char (&buf)[320]) {
+                const hm_group_t& g = *r.g;
+                return snprintf(buf, sizeof buf, "\t%lld\t%lld\t%g\t%.6g\t%.6g\t%d\t%d\t%d\t%d\t%d\t%d\t%.6g\n", (long long)k, (long long)k + 1, g.diff,
+                                g.pvalue, r.q, (int)g.m1, g.pcov1, g.ncov1, (int)g.m2, g.pcov2, g.ncov2, g.phi);
+            });
+    }
+    uint64_t tally[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};  // loci with q <= 0.05, q <= 0.01, phi > 1
+    for (size_t i = 0; i < rows.size(); ++i) {
+        const uint32_t c = std::min(rows[i].motif, 2u);
+        tally[c][0] += q[i] <= 0.05;
+        tally[c][1] += q[i] <= 0.01;
+        tally[c][2] += rows[i].phi > 1.0;
+    }
+    const std::string path = o.prefix + ".groups.summary.tsv";
+    FILE* f = fopen(path.c_str(), "w");
+    if (!f) { fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str()); return EXIT_FAILURE; }
+    for (int c = 0; c < 3; ++c)
+        fprintf(f, "%s\t%llu\t%llu\t%llu\t%llu\n", cn[c], (unsigned long long)m[c], (unsigned long long)tally[c][0], (unsigned long long)tally[c][1],
+                (unsigned long long)tally[c][2]);
+    fclose(f);
+    const auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+    fprintf(stderr, "## %zu + %zu samples, %llu + %llu counting loci of %d contexts, %zu tested in %.2f s: parse + load %.2f s; test + BED %.2f s\n",
+            group[0].size(), group[1].size(), (unsigned long long)n_rows[0], (unsigned long long)n_rows[1], n_ctx, rows.size(), secs(t_start, clk::now()),
+            secs(t_start, t_load), secs(t_load, clk::now()));
     return 0;
 }

@@ -1,4 +1,4 @@
-// hifimeth_pileup_opts.cpp -- the options of `pileup` and `diff`: one table that is parser and usage text at once, two strict number
+// hifimeth_pileup_opts.cpp -- the options of `pileup`, `diff` and `groupdiff`: one table that is parser and usage text at once, two strict number
 // parsers, and the checks between options as one ordered list.  A new option is one row here, a field of PileupOptions, a rule if
 // it depends on another option, and its cases in tools/make_cli_options.py.
 #include "hifimeth_pileup_opts.h"
@@ -266,6 +266,15 @@ const Option OPTIONS[] = {
     {'T', "<0|1>", lenient<&O::trunk>, "conv1..conv4 once per site (0) / once per read position (1)\n    Default: per context, from the first batch"},
 };
 const char DIFF_FLAGS[] = "aQGsgntd";
+// `groupdiff` has two rows of its own, which neither `pileup -h` nor `diff -h` prints, and takes -t and -d from the table above
+const Option GROUP_OPTIONS[] = {
+    {'a', "<int>", integer<&O::group_min_cov, 1, (1 << 20) - 1>,
+     "Minimum coverage (pcov + ncov) a sample needs at a locus to count there, in [1, 1048575]\n    Default: 5"},
+    {'r', "<int>", integer<&O::group_min_reps, 1, 255>,
+     "Minimum number of counting samples in each group at a tested locus, in [1, 255]; a locus also needs three\n"
+     "    counting samples in all\n    Default: 2"},
+};
+const char GROUP_FLAGS[] = "artd";
 
 const char PILEUP_HEADER[] =
     "USAGE:\n"
@@ -289,8 +298,29 @@ const char DIFF_HEADER[] =
     "\n"
     "OPTIONAL ARGUMENTS (as the same letters of `pileup -H -A`):\n";
 
+const char GROUP_HEADER[] =
+    "USAGE:\n"
+    "  $0 groupdiff [OPTIONS] reference a1,a2,... b1,b2,... output-prefix\n"
+    "\n"
+    "DESCRIPTION:\n"
+    "  Test two groups of replicates for differential methylation, locus by locus.  Every element of the two comma-separated lists\n"
+    "  is a prefix as `diff` takes it: <prefix>.<ctx>.cov.bed for ctx in CpG, CHG, CHH, plain or gzip.  A context is skipped unless\n"
+    "  every sample of both groups has its file.  A sample counts at a locus with at least -a calls; a locus is tested with\n"
+    "  at least -r counting samples in each group.  The test is the binomial likelihood ratio D of the pooled group counts, divided\n"
+    "  by the dispersion phi = max(1, Pearson X2 of the samples around their group / nu), against F(1, nu), nu = counting samples - 2.\n"
+    "  Writes <output-prefix>.groups.<ctx>.bed: chrom, start, end, group 1 % - group 2 %, p-value, Benjamini-Hochberg q-value within\n"
+    "  the context, m1, pcov1, ncov1, m2, pcov2, ncov2 (counting samples and their pooled calls), phi; and\n"
+    "  <output-prefix>.groups.summary.tsv: ctx, tested loci, loci with q <= 0.05, loci with q <= 0.01, loci with phi > 1\n"
+    "\n"
+    "OPTIONAL ARGUMENTS:\n";
+
 const Option* find_option(Command cmd, char letter) {
     if (cmd == CMD_DIFF && !strchr(DIFF_FLAGS, letter)) return nullptr;
+    if (cmd == CMD_GROUPDIFF) {
+        if (!strchr(GROUP_FLAGS, letter)) return nullptr;
+        for (const Option& opt : GROUP_OPTIONS)
+            if (opt.letter == letter) return &opt;
+    }
     for (const Option& opt : OPTIONS)
         if (opt.letter == letter) return &opt;
     return nullptr;
@@ -304,13 +334,14 @@ void print_text(const char* text, const char* exe) {  // $0: the program
 }
 
 void usage(Command cmd, const char* exe) {
-    print_text(cmd == CMD_DIFF ? DIFF_HEADER : PILEUP_HEADER, exe);
+    print_text(cmd == CMD_DIFF ? DIFF_HEADER : cmd == CMD_GROUPDIFF ? GROUP_HEADER : PILEUP_HEADER, exe);
     const auto row = [&](const Option& opt) {
         fprintf(stderr, "  -%c%s%s\n    ", opt.letter, opt.metavar ? " " : "", opt.metavar ? opt.metavar : "");
         print_text(cmd == CMD_DIFF && opt.diff_help ? opt.diff_help : opt.help, exe);
         fputc('\n', stderr);
     };
     if (cmd == CMD_DIFF) for (const char* f = DIFF_FLAGS; *f; ++f) row(*find_option(cmd, *f));
+    else if (cmd == CMD_GROUPDIFF) for (const char* f = GROUP_FLAGS; *f; ++f) row(*find_option(cmd, *f));
     else for (const Option& opt : OPTIONS) row(opt);
 }
 
@@ -327,7 +358,7 @@ struct Parsed {
 // of this list is the precedence: the groups asm, call, sites, domains, patterns, bedmethyl, linkage, profile, intervals, context,
 // and inside each group the order below.  It is not uniform -- patterns, linkage, profile and context report a bad value before a
 // missing parent, asm, domains, bedmethyl and intervals the missing parent first -- and tests/golden/cli_options.json pins it.
-// `diff` runs the rules marked CMD_DIFF.
+// `diff` runs the rules marked CMD_DIFF, `groupdiff` those marked CMD_GROUPDIFF.
 struct Rule {
     int commands;
     bool (*fires)(const Parsed& p);
@@ -366,6 +397,7 @@ const Rule RULES[] = {
      "-C must be an integer >= 1, -J bins[:flank_bp:flank_bins] with bins in [1, 1000] and flank_bp a multiple of flank_bins in [1, 1000]"},
     {CMD_PILEUP, [](const Parsed& p) { return p.any_bad("SO"); }, "-S must be an integer in [0, 3], -O an integer >= 1"},
     {CMD_PILEUP, [](const Parsed& p) { return p.any_seen("O") && p.o.context_flank < 0; }, "-O needs -S"},
+    {CMD_GROUPDIFF, [](const Parsed& p) { return p.any_bad("ar"); }, "-a must be an integer in [1, 1048575], -r an integer in [1, 255]"},
 };
 
 }  // namespace
@@ -382,7 +414,7 @@ bool parse_command_line(Command cmd, int argc, char** argv, PileupOptions& o, in
         if (opt && !opt->metavar) { opt->parse(nullptr, o); continue; }
         if (i + 1 >= argc) return leave(EXIT_FAILURE);
         if (!opt) {  // pileup's message has never ended its line; the fixture keeps it so until that is changed on purpose
-            fprintf(stderr, "ERROR: unrecognised option %s%s", a, cmd == CMD_DIFF ? "\n" : "");
+            fprintf(stderr, "ERROR: unrecognised option %s%s", a, cmd == CMD_PILEUP ? "" : "\n");
             return leave(EXIT_FAILURE);
         }
         p.seen += opt->letter;
@@ -390,7 +422,7 @@ bool parse_command_line(Command cmd, int argc, char** argv, PileupOptions& o, in
         if (opt->fatal) { fputs(opt->fatal, stderr); return leave(EXIT_FAILURE); }
         p.bad += opt->letter;
     }
-    if (argc - i != (cmd == CMD_DIFF ? 4 : 3)) return leave(EXIT_FAILURE);
+    if (argc - i != (cmd == CMD_PILEUP ? 3 : 4)) return leave(EXIT_FAILURE);
     // ahead of the rules although its rule comes tenth: it only writes the weights, which every earlier way out discards
     p.levels_bad = o.domains && !p.any_bad("uxj") && levels_ok && !levels_ok(o);
     for (const Rule& r : RULES)

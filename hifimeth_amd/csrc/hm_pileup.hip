@@ -488,6 +488,59 @@ __global__ __launch_bounds__(TPB) void load_loci_kernel(const hm_locus_t* __rest
     }
 }
 
+// ---- replicate groups (`groupdiff`, hm_pileup_load_sample_loci): the rows of ONE sample of a group ---------------------------------
+// As load_loci_kernel, with one more check (a sample's count stays below 2^20, so q = floor(k^2 2^20 / n) needs no more than 60
+// bits) and three more planes.  The sample's seen bitmap -- cleared when the sample is opened -- takes the locus' bit first: the
+// old bit says whether this sample gave the locus before, a duplicate, which adds nothing.  A row below the sample minimum
+// coverage keeps its bit and adds nothing.  Every other row adds its counts as load_loci_kernel does, q to the group's moment
+// plane and 1 to the locus' byte of the group's sample-count plane: an add to the aligned word that holds the byte, which never
+// carries since a group has at most 255 samples.
+enum GroupLoadCounter { GLOAD_ADDED = 0, GLOAD_BAD_GPOS, GLOAD_BAD_COUNT, GLOAD_BAD_BIG, GLOAD_BAD_MOTIF, GLOAD_BAD_DUP, GLOAD_COUNTERS };
+constexpr int32_t GROUP_COUNT_LIMIT = 1 << 20;  // a sample's pcov + ncov at a locus stays below this
+constexpr int GROUP_MAX_SAMPLES = 255;          // per group: the sample counts are bytes
+
+struct GroupLoadPlanes : LoadPlanes {
+    unsigned long long* moment;  // Q_g
+    uint32_t* samples;           // m_g, four loci per word
+    uint32_t* seen;              // 32 loci per word
+    int32_t min_cov;
+};
+
+__global__ __launch_bounds__(TPB) void load_sample_kernel(const hm_locus_t* __restrict__ rows, int64_t n, int64_t total, GroupLoadPlanes pl,
+                                                           unsigned long long* __restrict__ c) {
+    uint32_t mine[GLOAD_COUNTERS] = {0u, 0u, 0u, 0u, 0u, 0u};
+    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
+        const hm_locus_t r = rows[i];
+        if (r.gpos < 0 || r.gpos >= total) { ++mine[GLOAD_BAD_GPOS]; continue; }
+        if (r.pcov < 0 || r.ncov < 0) { ++mine[GLOAD_BAD_COUNT]; continue; }
+        if ((int64_t)r.pcov + r.ncov >= GROUP_COUNT_LIMIT) { ++mine[GLOAD_BAD_BIG]; continue; }
+        if (r.motif > 3u) { ++mine[GLOAD_BAD_MOTIF]; continue; }
+        if (r.pcov == 0 && r.ncov == 0) continue;
+        const int64_t g = r.gpos;
+        const uint32_t bit = 1u << (g & 31);
+        if (atomicOr(&pl.seen[g >> 5], bit) & bit) { ++mine[GLOAD_BAD_DUP]; continue; }
+        const int32_t cov = r.pcov + r.ncov;
+        if (cov < pl.min_cov) continue;
+        if (r.pcov) {
+            atomicAdd(&pl.part_pcov[g], r.pcov);
+            atomicAdd(&pl.pcov[g], r.pcov);
+            atomicAdd(&pl.moment[g], ((unsigned long long)r.pcov * (unsigned long long)r.pcov << 20) / (unsigned long long)cov);
+        }
+        if (r.ncov) {
+            atomicAdd(&pl.part_ncov[g], r.ncov);
+            atomicAdd(&pl.ncov[g], r.ncov);
+        }
+        atomicMax(&pl.key[g], r.motif);
+        atomicAdd(&pl.samples[g >> 2], 1u << (8 * (g & 3)));
+        ++mine[GLOAD_ADDED];
+    }
+    for (int k = 0; k < GLOAD_COUNTERS; ++k) {
+        uint32_t v = mine[k];
+        for (int d = 32; d; d >>= 1) v += __shfl_down(v, d);
+        if ((threadIdx.x & 63) == 0 && v) atomicAdd(&c[k], (unsigned long long)v);
+    }
+}
+
 // ---- resident records joined with per-locus truth labels (`hifimeth eval`, src/app/hifimeth/eval.cpp:469-560) ----
 // labels[g]: -1 no truth, 0 unmethylated, 1 methylated.  bins[(motif * 2 + label) * 256 + prob] counts the records whose
 // locus carries a label; workgroup-private histogram in LDS, one global atomic per non-empty bin and workgroup.
@@ -1284,6 +1337,129 @@ struct AsmSel {
         return true;
     }
 };
+
+// ---- replicate groups (`groupdiff`, hm_pileup_fetch_groups; include/hifimeth_hip.h has the definition) ---------------------------
+struct GroupPlanes {  // the partition planes hold K_g and N_g - K_g; with them the moment Q_g and the sample count m_g of each group
+    AsmPlanes a;
+    const unsigned long long *q1, *q2;
+    const uint8_t *m1, *m2;
+};
+
+// the loci with min_reps counting samples in each group and at least one degree of freedom; D, phi, pvalue by group_test_kernel
+struct GroupSel {
+    using Row = hm_group_t;
+    GroupPlanes s;
+    int32_t min_reps;
+    __device__ bool selects(int m1, int m2) const { return m1 >= min_reps && m2 >= min_reps && m1 + m2 >= 3; }
+    __device__ bool pred(int64_t i) const { return selects(s.m1[i], s.m2[i]); }
+    __device__ bool take(int64_t i, Row& r) const {
+        const int m1 = s.m1[i], m2 = s.m2[i];
+        if (!selects(m1, m2)) return false;
+        r.gpos = i;
+        r.pcov1 = s.a.p1[i];
+        r.ncov1 = s.a.n1[i];
+        r.pcov2 = s.a.p2[i];
+        r.ncov2 = s.a.n2[i];
+        r.motif = s.a.ky[i] & 3u;
+        r.m1 = (uint16_t)m1;
+        r.m2 = (uint16_t)m2;
+        r.diff = r.D = r.phi = r.pvalue = 0.0;
+        return true;
+    }
+};
+
+// x log(x / e) + e - x for a count x and its expectation e > 0, given d = x - e to full precision (the caller has it as an exact
+// integer over N): Loader's series in v = d / (x + e) where the three terms would cancel, the plain form elsewhere.  >= 0.
+__device__ __forceinline__ double deviance_part(double x, double e, double d) {
+    if (fabs(d) < 0.1 * (x + e)) {
+        const double v = d / (x + e), v2 = v * v;
+        double s = d * v, ej = 2.0 * x * v;
+        for (int j = 1; j < 1000; ++j) {
+            ej *= v2;
+            const double s1 = s + ej / (double)(2 * j + 1);
+            if (s1 == s) break;
+            s = s1;
+        }
+        return s;
+    }
+    return x == 0.0 ? e : x * log(x / e) - d;
+}
+
+// The continued fraction of the incomplete beta function, modified Lentz: I_x(a, b) = x^a (1 - x)^b / (a B(a, b)) * beta_cf(a, b, x),
+// quick for x < (a + 1) / (a + b + 2)
+__device__ __forceinline__ double beta_cf(double a, double b, double x) {
+    const double tiny = 1e-300, qab = a + b, qap = a + 1.0, qam = a - 1.0;
+    double c = 1.0, d = 1.0 - qab * x / qap;
+    if (fabs(d) < tiny) d = tiny;
+    d = 1.0 / d;
+    double h = d;
+    for (int m = 1; m <= 2000; ++m) {
+        const double m2 = 2.0 * m;
+        double aa = m * (b - m) * x / ((qam + m2) * (a + m2));
+        d = 1.0 + aa * d;
+        if (fabs(d) < tiny) d = tiny;
+        c = 1.0 + aa / c;
+        if (fabs(c) < tiny) c = tiny;
+        d = 1.0 / d;
+        h *= d * c;
+        aa = -(a + m) * (qab + m) * x / ((a + m2) * (qap + m2));
+        d = 1.0 + aa * d;
+        if (fabs(d) < tiny) d = tiny;
+        c = 1.0 + aa / c;
+        if (fabs(c) < tiny) c = tiny;
+        d = 1.0 / d;
+        const double del = d * c;
+        h *= del;
+        if (fabs(del - 1.0) < 1.2e-16) break;
+    }
+    return h;
+}
+
+// One thread per tested row.  coef[nu] = Gamma((nu + 1) / 2) / (sqrt(pi) Gamma(nu / 2 + 1)) = 1 / (a B(a, 1/2)), a = nu / 2, from the host.
+// D: with E_g = N_g K / N the four "observed - expected" sum to 0, so D = 2 sum deviance_part(observed, expected) over the four
+// cells, each >= 0 -- nothing cancels between the cells, and K_g - E_g = (K_g N - N_g K) / N has an exact integer numerator.
+// X2: Q_g 2^-20 - K_g^2 / N_g = (Q_g N_g - K_g^2 2^20) / (N_g 2^20), the numerator exact in 128 bits.
+__global__ __launch_bounds__(TPB) void group_test_kernel(hm_group_t* __restrict__ rows, int64_t n_rows, GroupPlanes s,
+                                                          const double* __restrict__ coef) {
+    const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (i >= n_rows) return;
+    const hm_group_t r = rows[i];
+    const int64_t Kg[2] = {r.pcov1, r.pcov2}, Ng[2] = {(int64_t)r.pcov1 + r.ncov1, (int64_t)r.pcov2 + r.ncov2};
+    const unsigned long long Qg[2] = {s.q1[r.gpos], s.q2[r.gpos]};
+    const int64_t K = Kg[0] + Kg[1], N = Ng[0] + Ng[1];
+    const int nu = (int)r.m1 + (int)r.m2 - 2;
+    rows[i].diff = __dsub_rn(__ddiv_rn(__dmul_rn(100.0, (double)Kg[0]), (double)Ng[0]), __ddiv_rn(__dmul_rn(100.0, (double)Kg[1]), (double)Ng[1]));
+    double D = 0.0, X2 = 0.0;
+    const int64_t num = Kg[0] * Ng[1] - Ng[0] * Kg[1];  // (K_1 - E_1) N = -(K_2 - E_2) N
+    if (num != 0) {
+        for (int g = 0; g < 2; ++g) {
+            const double d = (double)(g ? -num : num) / (double)N;
+            const double e = (double)Ng[g] * (double)K / (double)N, f = (double)Ng[g] * (double)(N - K) / (double)N;
+            D += deviance_part((double)Kg[g], e, d) + deviance_part((double)(Ng[g] - Kg[g]), f, -d);
+        }
+        D *= 2.0;
+    }
+    for (int g = 0; g < 2; ++g) {
+        if (Kg[g] == 0 || Kg[g] == Ng[g]) continue;
+        const __int128 a = (__int128)Qg[g] * (__int128)Ng[g] - ((__int128)(Kg[g] * Kg[g]) << 20);
+        if (a <= 0) continue;
+        const double ad = (double)(uint64_t)(a >> 64) * 18446744073709551616.0 + (double)(uint64_t)a;
+        X2 += ad * (double)Ng[g] / (1048576.0 * (double)(Kg[g] * (Ng[g] - Kg[g])));
+    }
+    const double phi = fmax(1.0, X2 / (double)nu);
+    rows[i].D = D;
+    rows[i].phi = phi;
+    if (D == 0.0) {
+        rows[i].pvalue = 1.0;
+        return;
+    }
+    const double F = D / phi, a = 0.5 * (double)nu;
+    const double x = (double)nu / ((double)nu + F), y = F / ((double)nu + F);
+    const double xa = y < 0.5 ? exp(a * log1p(-y)) : pow(x, a);
+    const double front = coef[nu] * xa * sqrt(y);
+    const double p = x < (a + 1.0) / (a + 2.5) ? front * beta_cf(a, 0.5, x) : 1.0 - 2.0 * a * front * beta_cf(0.5, a, y);
+    rows[i].pvalue = p > 1.0 ? 1.0 : p >= DBL_MIN ? p : DBL_MIN;  // never 0, as asm_test_kernel's
+}
 
 // the non-empty bins of bins[0, n) in ascending index: the skeleton over the bin array instead of a plane range
 struct BinsSel {
@@ -2105,6 +2281,13 @@ struct hm_pileup {
     DevBuf d_load{EXACT}, d_loadcnt{EXACT};
     bool staged_any = false, loaded = false, load_failed = false;
     int64_t load_slab = LOAD_SLAB_ROWS;  // option "load_slab": rows per slab of the next load
+    // `groupdiff` ("groups" = 1), all of it only with the option on: per group the moment plane (8 B per base) and the sample-count
+    // plane (1 B), and the open sample's seen bitmap (1 bit), resident from hm_pileup_set_reference on; the samples opened per
+    // group, the group of the open one (0: none yet) and the table of 1 / (a B(a, 1/2)) by degrees of freedom for the fetch
+    int groups = 0;
+    int32_t group_min_cov = 5;
+    DevBuf d_gmoment[2]{DevBuf(EXACT), DevBuf(EXACT)}, d_gsamples[2]{DevBuf(EXACT), DevBuf(EXACT)}, d_gseen{EXACT}, d_gcoef{EXACT};
+    int group_samples[2] = {0, 0}, group_open = 0;
     uint32_t thr_packed = 0;   // the three thresholds of the last hm_pileup_count
     bool counted = false;    // hm_pileup_count has run since hm_pileup_set_reference: what the -E, -M and -L fetches wait for
     int64_t n_recs = 0;
@@ -2430,7 +2613,8 @@ int stage_alignment(hm_pileup* p, uint32_t order, int32_t flag, int32_t sid, int
                     const uint8_t* seq4, int32_t n_cigar, const uint32_t* cigar, int64_t n_entries, const void* entries, int32_t hp,
                     PRead& r, BatchMark& mark) {
     if (!p) return HM_EINVAL;
-    if (p->loaded || p->load_failed) return pfail(p, HM_ESTATE, "hm_pileup_submit_read on an engine whose counts were loaded (hm_pileup_load_loci)");
+    if (p->loaded || p->load_failed || p->group_open)
+        return pfail(p, HM_ESTATE, "hm_pileup_submit_read on an engine whose counts were loaded (hm_pileup_load_loci, hm_pileup_group_sample)");
     if (hp < 0 || hp > 2) return pfail(p, HM_EINVAL, "haplotype partition must be 0, 1 or 2");
     if (hp && p->partitions != 2) return pfail(p, HM_ESTATE, "haplotype partition given but the partitions option is off");
     if (p->seq_off.empty()) return pfail(p, HM_ESTATE, "hm_pileup_submit_read before hm_pileup_set_reference");
@@ -2559,7 +2743,7 @@ int hm_pileup_set_option(hm_pileup_t* p, const char* key, double value) {
     // what is sized or listed when the reference arrives (the partition planes, the reference CpGs and their counters, the
     // linkage histograms) is decided before that; the planes also before the caller hands in planes of their own
     const bool partitions = k == "partitions";
-    if (partitions || k == "patterns" || k == "pattern_span" || k == "bedmethyl" || k == "linkage" || k == "profile" || k == "trim5" || k == "trim3") {
+    if (partitions || k == "groups" || k == "patterns" || k == "pattern_span" || k == "bedmethyl" || k == "linkage" || k == "profile" || k == "trim5" || k == "trim3") {
         if (!p->seq_off.empty() || (partitions && !p->own_planes))
             return pfail(p, HM_ESTATE, k + " must be set before hm_pileup_set_reference" + (partitions ? " / hm_pileup_use_planes" : ""));
     }
@@ -2567,6 +2751,7 @@ int hm_pileup_set_option(hm_pileup_t* p, const char* key, double value) {
     else if (k == "min_pi") p->min_pi = value;
     else if (partitions) {
         if (value != 0.0 && value != 2.0) return pfail(p, HM_EINVAL, "partitions must be 0 or 2");
+        if (value == 0.0 && p->groups) return pfail(p, HM_ESTATE, "partitions cannot be switched off under option groups");
         p->partitions = (int)value;
     } else if (k == "patterns") {
         if (value != 0.0 && value != 2.0 && value != 3.0 && value != 4.0) return pfail(p, HM_EINVAL, "patterns must be 0, 2, 3 or 4");
@@ -2590,6 +2775,15 @@ int hm_pileup_set_option(hm_pileup_t* p, const char* key, double value) {
         if (!(value >= 0.0 && value <= (double)INT32_MAX) || value != std::floor(value))
             return pfail(p, HM_EINVAL, k + " must be an integer >= 0");
         (k == "trim5" ? p->trim.n5 : p->trim.n3) = (int32_t)std::min(value, (double)(1 << 22));
+    } else if (k == "groups") {  // the moment and sample-count planes are sized when the reference arrives
+        if (value != 0.0 && value != 1.0) return pfail(p, HM_EINVAL, "groups must be 0 or 1");
+        if (value == 1.0 && p->partitions != 2) return pfail(p, HM_ESTATE, "groups needs option partitions = 2 set before it");
+        p->groups = (int)value;
+    } else if (k == "group_min_cov") {
+        if (!(value >= 1.0 && value < (double)GROUP_COUNT_LIMIT) || value != std::floor(value))
+            return pfail(p, HM_EINVAL, "group_min_cov must be an integer in 1 .. 2^20 - 1");
+        if (p->group_open) return pfail(p, HM_ESTATE, "group_min_cov must be set before the first hm_pileup_group_sample");
+        p->group_min_cov = (int32_t)value;
     } else if (k == "load_slab") {  // the device holds one slab of rows whatever a load brings; at any time
         if (!(value >= 1.0 && value <= (double)LOAD_SLAB_MAX) || value != std::floor(value))
             return pfail(p, HM_EINVAL, "load_slab must be an integer in 1 .. 2^24");
@@ -2660,6 +2854,18 @@ int hm_pileup_set_reference(hm_pileup_t* p, int32_t n_seqs, const int64_t* seq_l
                 HIP_TRY(hipMemsetAsync(p->hp_pcov[k], 0, bytes, p->stream));
                 HIP_TRY(hipMemsetAsync(p->hp_ncov[k], 0, bytes, p->stream));
             }
+        }
+        if (p->groups) {  // sized in whole words: the kernel adds to the word that holds a locus' byte or bit
+            const size_t n = (size_t)std::max<int64_t>(total, 1);
+            for (int k = 0; k < 2; ++k) {
+                p->d_gmoment[k].reserve(8 * n);
+                p->d_gsamples[k].reserve(4 * ((n + 3) / 4));
+                HIP_TRY(hipMemsetAsync(p->d_gmoment[k].p, 0, 8 * n, p->stream));
+                HIP_TRY(hipMemsetAsync(p->d_gsamples[k].p, 0, 4 * ((n + 3) / 4), p->stream));
+            }
+            p->d_gseen.reserve(4 * ((n + 31) / 32));
+            HIP_TRY(hipMemsetAsync(p->d_gseen.p, 0, 4 * ((n + 31) / 32), p->stream));
+            p->group_samples[0] = p->group_samples[1] = p->group_open = 0;
         }
         if (p->patterns || p->bedmethyl) {
             const int rc = list_reference_cpgs(p);
@@ -2948,6 +3154,7 @@ int64_t hm_pileup_load_loci(hm_pileup_t* p, int32_t part, const hm_locus_t* rows
     if (p->partitions != 2 || p->seq_off.empty() || !p->pcov || !p->hp_pcov[0] || !p->hp_pcov[1])
         return pfail(p, HM_ESTATE, "hm_pileup_load_loci needs option partitions = 2 and hm_pileup_set_reference");
     if (p->staged_any) return pfail(p, HM_ESTATE, "hm_pileup_load_loci on an engine that has staged records: counts come from records or from loads, not both");
+    if (p->group_open) return pfail(p, HM_ESTATE, "hm_pileup_load_loci on an engine that opened a group sample (hm_pileup_group_sample)");
     if (n == 0) return 0;
     const int64_t slab = p->load_slab;
     unsigned long long c[LOAD_COUNTERS] = {0, 0, 0, 0, 0};
@@ -2984,6 +3191,153 @@ int64_t hm_pileup_load_loci(hm_pileup_t* p, int32_t part, const hm_locus_t* rows
     }
     p->loaded = true;
     return (int64_t)c[LOAD_ADDED];
+}
+
+// ---- `groupdiff` ------------------------------------------------------------------------------------------------------------------
+namespace {
+// what the group calls share: the option, the reference, an engine that is not void
+int group_ready(hm_pileup* p, const char* who) {
+    const std::string w = who;
+    if (!p->groups || p->seq_off.empty() || !p->d_gseen.p) return pfail(p, HM_ESTATE, w + " needs option groups = 1 and hm_pileup_set_reference");
+    if (p->load_failed) return pfail(p, HM_ESTATE, w + ": " + LOAD_FAILED_TEXT);
+    if (!p->pcov || !p->hp_pcov[0] || !p->hp_pcov[1]) return pfail(p, HM_ESTATE, w + " without partition planes");
+    return HM_OK;
+}
+
+// 1 / (a B(a, 1/2)) = Gamma((nu + 1) / 2) / (sqrt(pi) Gamma(nu / 2 + 1)) for nu = 0 .. 2 GROUP_MAX_SAMPLES - 2, by the recurrence
+// c(nu + 2) = c(nu) (nu + 1) / (nu + 2) from c(1) = 2 / pi, c(2) = 1 / 2 in long double, rounded once: uploaded once per engine
+void ensure_group_coef(hm_pileup* p) {
+    if (p->d_gcoef.p) return;
+    static const std::vector<double> tab = [] {
+        std::vector<long double> c((size_t)2 * GROUP_MAX_SAMPLES - 1);
+        c[0] = 1.0L;
+        c[1] = 2.0L / 3.14159265358979323846264338327950288L;
+        for (size_t nu = 2; nu < c.size(); ++nu) c[nu] = c[nu - 2] * (long double)(nu - 1) / (long double)nu;
+        return std::vector<double>(c.begin(), c.end());
+    }();
+    p->d_gcoef.reserve(sizeof(double) * tab.size());
+    HIP_TRY(hipMemcpyAsync(p->d_gcoef.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+}
+}  // namespace
+
+int hm_pileup_group_sample(hm_pileup_t* p, int32_t part) {
+    if (!p) return HM_EINVAL;
+    if (part != 1 && part != 2) return pfail(p, HM_EINVAL, "hm_pileup_group_sample: part must be 1 or 2");
+    const int rc = group_ready(p, "hm_pileup_group_sample");
+    if (rc != HM_OK) return rc;
+    if (p->staged_any || p->loaded)
+        return pfail(p, HM_ESTATE, "hm_pileup_group_sample on an engine that staged records or used hm_pileup_load_loci: counts come from one source");
+    if (p->group_samples[part - 1] >= GROUP_MAX_SAMPLES) return pfail(p, HM_ESTATE, "hm_pileup_group_sample: a group holds at most 255 samples");
+    const int cleared = guarded(p, [&] {
+        HIP_TRY(hipMemsetAsync(p->d_gseen.p, 0, 4 * (((size_t)std::max<int64_t>(p->seq_off.back(), 1) + 31) / 32), p->stream));
+        return HM_OK;
+    });
+    if (cleared != HM_OK) return cleared;
+    p->group_open = part;
+    return p->group_samples[part - 1]++;
+}
+
+int64_t hm_pileup_load_sample_loci(hm_pileup_t* p, const hm_locus_t* rows, int64_t n) {
+    if (!p) return HM_EINVAL;
+    if (n < 0 || (n && !rows)) return pfail(p, HM_EINVAL, "hm_pileup_load_sample_loci: n >= 0, rows not NULL");
+    const int ready = group_ready(p, "hm_pileup_load_sample_loci");
+    if (ready != HM_OK) return ready;
+    if (!p->group_open) return pfail(p, HM_ESTATE, "hm_pileup_load_sample_loci before hm_pileup_group_sample");
+    if (n == 0) return 0;
+    const int64_t slab = p->load_slab;
+    const int g = p->group_open - 1;
+    unsigned long long c[GLOAD_COUNTERS] = {0, 0, 0, 0, 0, 0};
+    const int rc = guarded(p, [&] {
+        p->d_load.reserve(sizeof(hm_locus_t) * (size_t)slab);
+        p->d_loadcnt.reserve(sizeof c);
+        HIP_TRY(hipMemsetAsync(p->d_loadcnt.p, 0, sizeof c, p->stream));
+        const GroupLoadPlanes pl{{{p->pcov, p->ncov, p->key}, p->hp_pcov[g], p->hp_ncov[g]}, p->d_gmoment[g].as<unsigned long long>(),
+                                 p->d_gsamples[g].as<uint32_t>(), p->d_gseen.as<uint32_t>(), p->group_min_cov};
+        for (int64_t at = 0; at < n; at += slab) {  // as hm_pileup_load_loci: a slab's copy follows the kernel over the one before
+            const int64_t m = std::min(slab, n - at);
+            HIP_TRY(hipMemcpyAsync(p->d_load.p, rows + at, sizeof(hm_locus_t) * (size_t)m, hipMemcpyHostToDevice, p->stream));
+            hipLaunchKernelGGL(load_sample_kernel, dim3(grid_for(m, 4096)), dim3(TPB), 0, p->stream, p->d_load.as<hm_locus_t>(), m,
+                               p->seq_off.back(), pl, p->d_loadcnt.as<unsigned long long>());
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipMemcpyAsync(c, p->d_loadcnt.p, sizeof c, hipMemcpyDeviceToHost, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        return HM_OK;
+    });
+    if (rc < 0) return rc;
+    unsigned long long bad = 0;
+    for (int k = GLOAD_BAD_GPOS; k < GLOAD_COUNTERS; ++k) bad += c[k];
+    if (bad) {
+        p->load_failed = true;
+        static const char* kind[GLOAD_COUNTERS] = {"", "gpos outside the reference", "negative count", "count above 2^20 - 1", "motif above 3",
+                                                   "locus given twice in one sample"};
+        std::string msg = "hm_pileup_load_sample_loci: " + std::to_string(bad) + " bad rows";
+        const char* sep = ": ";
+        for (int k = GLOAD_BAD_GPOS; k < GLOAD_COUNTERS; ++k) {
+            if (!c[k]) continue;
+            msg += sep + std::to_string(c[k]) + " " + kind[k];
+            sep = ", ";
+        }
+        return pfail(p, HM_EDATA, msg);
+    }
+    return (int64_t)c[GLOAD_ADDED];
+}
+
+namespace {
+int group_range(hm_pileup* p, const char* who, int64_t lo, int64_t hi) {
+    const int rc = group_ready(p, who);
+    if (rc != HM_OK) return rc;
+    if (lo < 0 || hi < lo || hi > p->seq_off.back()) return pfail(p, HM_EINVAL, std::string(who) + ": bad range");
+    return HM_OK;
+}
+GroupPlanes group_planes(hm_pileup* p) {
+    return GroupPlanes{AsmPlanes{p->hp_pcov[0], p->hp_ncov[0], p->hp_pcov[1], p->hp_ncov[1], p->key}, p->d_gmoment[0].as<unsigned long long>(),
+                       p->d_gmoment[1].as<unsigned long long>(), p->d_gsamples[0].as<uint8_t>(), p->d_gsamples[1].as<uint8_t>()};
+}
+}  // namespace
+
+int64_t hm_pileup_fetch_groups(hm_pileup_t* p, int64_t lo, int64_t hi, int32_t min_reps, hm_group_t* out, int64_t cap) {
+    if (!p) return HM_EINVAL;
+    if (min_reps < 1 || min_reps > GROUP_MAX_SAMPLES) return pfail(p, HM_EINVAL, "hm_pileup_fetch_groups: min_reps must be in 1 .. 255");
+    const int rc = group_range(p, "hm_pileup_fetch_groups", lo, hi);
+    if (rc != HM_OK) return rc;
+    if (hi == lo) return 0;
+    const GroupPlanes s = group_planes(p);
+    return compact_rows_to(
+        p, GroupSel{s, min_reps}, lo, hi, [&](int64_t total) { return fits(total, out, cap) ? out : nullptr; }, [&] { ensure_group_coef(p); },
+        [&](hm_group_t* rows, int64_t total) {
+            hipLaunchKernelGGL(group_test_kernel, row_grid(total), dim3(TPB), 0, p->stream, rows, total, s, p->d_gcoef.as<double>());
+        });
+}
+
+int hm_pileup_group_planes(hm_pileup_t* p, int32_t part, int64_t lo, int64_t hi, uint64_t* moment, uint8_t* samples) {
+    if (!p) return HM_EINVAL;
+    if (part != 1 && part != 2) return pfail(p, HM_EINVAL, "hm_pileup_group_planes: part must be 1 or 2");
+    const int rc = group_range(p, "hm_pileup_group_planes", lo, hi);
+    if (rc != HM_OK || hi == lo) return rc;
+    return guarded(p, [&] {
+        const size_t n = (size_t)(hi - lo);
+        if (moment) HIP_TRY(hipMemcpyAsync(moment, p->d_gmoment[part - 1].as<unsigned long long>() + lo, 8 * n, hipMemcpyDeviceToHost, p->stream));
+        if (samples) HIP_TRY(hipMemcpyAsync(samples, p->d_gsamples[part - 1].as<uint8_t>() + lo, n, hipMemcpyDeviceToHost, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        return HM_OK;
+    });
+}
+
+int hm_group_qvalues(const hm_group_t* rows, int64_t n, double* q, uint64_t m[3]) {
+    if (n < 0 || (n && (!rows || !q)) || !m) return HM_EINVAL;
+    for (int64_t i = 0; i < n; ++i)
+        if (rows[i].motif > 3u || !(rows[i].pvalue >= DBL_MIN && rows[i].pvalue <= 1.0)) return HM_EINVAL;
+    std::vector<BhEntry> ent;
+    for (uint32_t c = 0; c < 3; ++c) {
+        ent.clear();
+        for (int64_t i = 0; i < n; ++i)
+            if (std::min(rows[i].motif, 2u) == c) ent.push_back(BhEntry{rows[i].pvalue, 1, i});
+        m[c] = ent.size();
+        bh_qvalues(ent, m[c], [&](int64_t where, double v) { q[where] = v; });
+    }
+    return HM_OK;
 }
 
 // ---- `pileup -E` ------------------------------------------------------------------------------------------------------------------

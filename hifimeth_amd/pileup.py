@@ -31,6 +31,12 @@ Two samples instead of two haplotypes (`hifimeth-hip diff`): on an engine made w
 `pu.load_loci(1, *read_cov_bed(path1, names, offsets))` and the same for part 2 put two samples' <prefix>.<ctx>.cov.bed rows into
 the partition planes; the three paragraphs above then hold for sample 1 against sample 2, unchanged.
 
+Replicates (`hifimeth-hip groupdiff`): on an engine made with partitions=True, groups=True, `pu.begin_sample(part)` opens the next
+sample of group 1 or 2 and `pu.load_sample_loci(*read_cov_bed(...))` adds its rows; `pu.group_tests(min_reps=2)` returns the loci
+with enough replicates on both sides (GROUP_DTYPE: pooled counts, diff, likelihood ratio D, dispersion phi, pvalue of the F test on
+D / phi), `group_qvalues(rows)` their BH q per context, `pu.groups_bed(rows, q)` and `groups_summary_tsv(rows, q, m)` the text of
+<prefix>.groups.<ctx>.bed and <prefix>.groups.summary.tsv.  include/hifimeth_hip.h has the definition of the statistic.
+
 Binomial test per locus (`pileup -B control` / `-e r,r,r`): is a locus methylated at all, against the caller's false-positive
 rate?  `pu.control_sums(lo, hi)` over an unmethylated control sequence gives the rates (`rates_from_sums`), `pu.site_histogram()`
 counts the loci per (motif, pcov, pcov + ncov), `sites_table(rates, bins, big)` -- host only, the C library's -- solves p-values
@@ -119,6 +125,8 @@ LOCUS_DTYPE = np.dtype([("gpos", "<i8"), ("pcov", "<i4"), ("ncov", "<i4"), ("mot
 ASM_DTYPE = np.dtype([("gpos", "<i8"), ("pcov1", "<i4"), ("ncov1", "<i4"), ("pcov2", "<i4"), ("ncov2", "<i4"), ("motif", "<u4"),
                       ("reserved", "<u4"), ("diff", "<f8"), ("pvalue", "<f8")])     # hm_asm_t, 48 bytes
 ASMQ_DTYPE = np.dtype(ASM_DTYPE.descr + [("qvalue", "<f8")])                          # hm_asmq_t, 56 bytes
+GROUP_DTYPE = np.dtype([("gpos", "<i8"), ("pcov1", "<i4"), ("ncov1", "<i4"), ("pcov2", "<i4"), ("ncov2", "<i4"), ("motif", "<u4"),
+                        ("m1", "<u2"), ("m2", "<u2"), ("diff", "<f8"), ("D", "<f8"), ("phi", "<f8"), ("pvalue", "<f8")])  # hm_group_t, 64 bytes
 ASM_BIN_DTYPE = np.dtype([("bin", "<u4"), ("reserved", "<u4"), ("count", "<u8"), ("pvalue", "<f8"), ("qvalue", "<f8")])  # hm_asm_bin_t, 32 bytes
 ASM_REGION_DTYPE = np.dtype([("start", "<i8"), ("end", "<i8"), ("pcov1", "<i8"), ("ncov1", "<i8"), ("pcov2", "<i8"), ("ncov2", "<i8"),
                              ("n_loci", "<i4"), ("sign", "<i4"), ("motif", "<u4"), ("flags", "<u4"), ("diff", "<f8"),
@@ -288,6 +296,24 @@ def asm_summary_tsv(table: AsmTable) -> str:
     q = np.concatenate([table.tab["qvalue"], table.big_q])
     return "".join("%s\t%d\t%d\t%d\n" % (CTX_NAMES[c], int(table.m[c]), int(w[(ctx == c) & (q <= 0.05)].sum()),
                                           int(w[(ctx == c) & (q <= 0.01)].sum())) for c in range(3))
+
+
+def group_qvalues(rows: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """`groupdiff` (hm_group_qvalues, host only): -> (q, m): q[i] = the Benjamini-Hochberg value of rows[i]["pvalue"] among the rows
+    of its context (equal p gives equal q), m[ctx] = tested loci per context.  rows: what group_tests returned for the whole job."""
+    rows = np.ascontiguousarray(rows, GROUP_DTYPE)
+    q = np.full(len(rows), np.nan)
+    m = np.zeros(3, np.uint64)
+    if lib().hm_group_qvalues(rows.ctypes.data_as(C.c_void_p), len(rows), q.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p)) != 0:
+        raise HifimethError("hm_group_qvalues: a motif above 3 or a p outside [DBL_MIN, 1]")
+    return q, m
+
+
+def groups_summary_tsv(rows: np.ndarray, q: np.ndarray, m) -> str:
+    """the text of <prefix>.groups.summary.tsv: ctx, tested loci, loci with q <= 0.05, loci with q <= 0.01, loci with phi > 1"""
+    ctx = np.minimum(rows["motif"], 2)
+    return "".join("%s\t%d\t%d\t%d\t%d\n" % (CTX_NAMES[c], int(m[c]), int(((ctx == c) & (q <= 0.05)).sum()), int(((ctx == c) & (q <= 0.01)).sum()),
+                                              int(((ctx == c) & (rows["phi"] > 1.0)).sum())) for c in range(3))
 
 
 def stitch_asm_regions(parts, max_gap: int, min_loci: int, keep_edges: bool = False) -> Tuple[np.ndarray, int]:
@@ -791,7 +817,7 @@ class MethylationPileup:
     def __init__(self, genome: Sequence[Tuple[str, str]], device: int = 0, min_mapq: int = 0, min_pi: float = 0.0,
                  planes=None, partitions: bool = False, partition_planes=None, bases=None, patterns: int = 0,
                  pattern_span: int = PATTERN_SPAN, bedmethyl: bool = False, linkage: int = 0, profile: int = 0,
-                 trim: Tuple[int, int] = (0, 0)):
+                 trim: Tuple[int, int] = (0, 0), groups: bool = False, group_min_cov: int = 5):
         """genome: [(name, SEQUENCE)].  bases: optional, the concatenated upper-case bases of the whole reference as a
         C-contiguous uint8 buffer (ndarray, bytes, memoryview), handed to the engine as it is -- for references of gigabases,
         where joining, upper-casing and encoding strings would copy them three times; the second member of each genome entry
@@ -807,7 +833,9 @@ class MethylationPileup:
         (+6 144 B per distance, whatever the depth).
         profile: 0, or D in 1 .. 2 048: also count every projected call by its position in the read, the D bases at either end one
         row each (+3 x (2 D + 1) x 2 048 B: 12.6 MB at 1 024).
-        trim: (n5, n3): the entries in the first n5 and the last n3 bases of every read are dropped."""
+        trim: (n5, n3): the entries in the first n5 and the last n3 bases of every read are dropped.
+        groups (needs partitions=True): replicate groups -- begin_sample / load_sample_loci / group_tests (+18.125 B per reference
+        base); group_min_cov: the coverage a sample needs at a locus to count there."""
         self._L = lib()
         self._h = C.c_void_p()
         if self._L.hm_pileup_create(C.byref(self._h), device) != 0:
@@ -841,6 +869,9 @@ class MethylationPileup:
         if tuple(trim) != (0, 0):
             self._check(self._L.hm_pileup_set_option(self._h, b"trim5", float(trim[0])))
             self._check(self._L.hm_pileup_set_option(self._h, b"trim3", float(trim[1])))
+        if groups:
+            self._check(self._L.hm_pileup_set_option(self._h, b"groups", 1.0))
+            self._check(self._L.hm_pileup_set_option(self._h, b"group_min_cov", float(group_min_cov)))
         if planes is not None:
             self._check(self._L.hm_pileup_use_planes(self._h, *(C.c_void_p(t.data_ptr()) for t in planes)))
         if bases is None:
@@ -976,6 +1007,45 @@ class MethylationPileup:
         rows = np.zeros(len(gpos), LOCUS_DTYPE)
         rows["gpos"], rows["pcov"], rows["ncov"], rows["motif"] = gpos, pcov, ncov, motif
         return self._check(self._L.hm_pileup_load_loci(self._h, part, rows.ctypes.data_as(C.c_void_p), len(rows)))
+
+    def begin_sample(self, part: int) -> int:
+        """`groupdiff` (hm_pileup_group_sample): opens the next sample of group `part` (1 or 2); load_sample_loci then adds its rows.
+        -> the sample's index within its group.  Needs groups=True and an engine that never saw a read or a load_loci."""
+        return self._check(self._L.hm_pileup_group_sample(self._h, part))
+
+    def load_sample_loci(self, gpos, pcov, ncov, motif) -> int:
+        """`groupdiff` (hm_pileup_load_sample_loci): rows of the open sample, as read_cov_bed returns them; any number of calls.
+        A locus with pcov + ncov >= group_min_cov adds its counts to the group's partition planes and the combined ones, its
+        moment floor(pcov^2 2^20 / (pcov + ncov)) and one sample.  -> the number of rows that added.  HifimethError for a row
+        outside the reference, a negative count, a count of 2^20 or more, a motif above 3 or a locus twice in this sample: the
+        engine is then void."""
+        gpos = np.ascontiguousarray(gpos, np.int64)
+        rows = np.zeros(len(gpos), LOCUS_DTYPE)
+        rows["gpos"], rows["pcov"], rows["ncov"], rows["motif"] = gpos, pcov, ncov, motif
+        return self._check(self._L.hm_pileup_load_sample_loci(self._h, rows.ctypes.data_as(C.c_void_p), len(rows)))
+
+    def group_planes(self, part: int, lo: int = 0, hi: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """-> (moment uint64, samples uint8) of group `part` over [lo, hi): the sum of the counting samples' moments and their number"""
+        hi = self.n_loci if hi is None else hi
+        moment, samples = np.zeros(max(hi - lo, 0), np.uint64), np.zeros(max(hi - lo, 0), np.uint8)
+        self._check(self._L.hm_pileup_group_planes(self._h, part, lo, hi, moment.ctypes.data_as(C.c_void_p), samples.ctypes.data_as(C.c_void_p)))
+        return moment, samples
+
+    def group_tests(self, lo: int = 0, hi: Optional[int] = None, min_reps: int = 2) -> np.ndarray:
+        """`groupdiff` (hm_pileup_fetch_groups): the loci of [lo, hi) with at least min_reps counting samples in each group and
+        m1 + m2 >= 3, ascending (GROUP_DTYPE): the pooled counts, diff, the binomial likelihood ratio D, the dispersion phi
+        = max(1, Pearson X2 / nu) and pvalue = P(F(1, nu) >= D / phi), nu = m1 + m2 - 2."""
+        hi = self.n_loci if hi is None else hi
+        return self._rows(self._L.hm_pileup_fetch_groups, GROUP_DTYPE, lo, hi, min_reps)
+
+    def groups_bed(self, rows: np.ndarray, q: np.ndarray) -> dict:
+        """the text of <prefix>.groups.{CpG,CHG,CHH}.bed: chrom, k, k+1, diff, p, q, m1, pcov1, ncov1, m2, pcov2, ncov2, phi"""
+        sid, soff = locate(self.offsets, rows["gpos"])
+        text = {k: [] for k in CTX_NAMES}
+        for s, k, r, qv in zip(sid, soff, rows, q):
+            text[CTX_NAMES[min(int(r["motif"]), 2)]].append("%s\t%d\t%d\t%g\t%.6g\t%.6g\t%d\t%d\t%d\t%d\t%d\t%d\t%.6g\n" % (
+                self.names[s], k, k + 1, r["diff"], r["pvalue"], qv, r["m1"], r["pcov1"], r["ncov1"], r["m2"], r["pcov2"], r["ncov2"], r["phi"]))
+        return {k: "".join(v) for k, v in text.items()}
 
     def bed(self, loci: np.ndarray) -> dict:
         """the text of <prefix>.{CpG,CHG,CHH}.cov.bed (pileup.cpp:562-590)"""

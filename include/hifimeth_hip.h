@@ -211,6 +211,7 @@ int hm_reset_timing(hm_engine_t* e);
  *   rows of <prefix>.<ctx>.cov.bed          (pileup.cpp:562-590)                     -> hm_pileup_fetch_loci
  *   (ours) haplotype difference per locus, rows of <prefix>.asm.<ctx>.bed         -> hm_pileup_fetch_asm
  *   (ours) two samples' *.cov.bed rows into the haplotype planes (`diff`)         -> hm_pileup_load_loci
+ *   (ours) two groups of replicates, tested with their spread (`groupdiff`)       -> hm_pileup_group_sample, hm_pileup_fetch_groups
  * The whole genome's counters stay resident in HBM (12 B per reference base, 28 B with the haplotype partitions) and the
  * projected calls wait in HBM (12 B each) until the thresholds are known -- the reference spills them to a temporary file.
  * MM/ML parsing and BED text formatting stay on the host (hm_bam.h).                                           */
@@ -240,7 +241,7 @@ const char* hm_pileup_last_error(const hm_pileup_t* p); /* p may be NULL: error 
  * counting, see hm_pileup_submit_read_hp; must be set before hm_pileup_set_reference / hm_pileup_use_planes, else HM_ESTATE),
  * "patterns" and "pattern_span" (read-level CpG patterns), "bedmethyl" (per-CpG depth classes), "linkage" (co-methylation by
  * distance), "profile" (methylation by position in the read) and "trim5" / "trim3" (end trimming), all near the end of this header;
- * "load_slab" (hm_pileup_load_loci) */
+ * "load_slab" (hm_pileup_load_loci); "groups" and "group_min_cov" (hm_pileup_group_sample) */
 int hm_pileup_set_option(hm_pileup_t* p, const char* key, double value);
 /* HbnDatabase: n_seqs upper-cased sequences back to back in `bases` (seq_len[i] bytes each).  Allocates and
  * zeroes the per-locus planes unless hm_pileup_use_planes was called before. */
@@ -426,8 +427,64 @@ int64_t hm_pileup_fetch_asm_regions(hm_pileup_t* p, const void* pcov1, const voi
  * interleaving.  The rows go through one device slab of "load_slab" rows (option, 1 .. 2^24, default 2^20 = 24 MB; may be set at
  * any time), slab by slab on the engine's stream: no device memory grows with n.  All adds are integer atomics: the planes depend
  * on neither row order, slab size nor launch geometry.  Not here: pileup_dist (one card holds both samples of a human genome at
- * 28 B per base), more than two samples, replicates. */
+ * 28 B per base), more than two samples (replicates in two groups: hm_pileup_group_sample below). */
 int64_t hm_pileup_load_loci(hm_pileup_t* p, int32_t part, const hm_locus_t* rows, int64_t n);
+
+/* ---- replicate groups (`groupdiff`): several samples per part, tested with their spread ---------------------
+ * Sample i of group g in {1, 2} has, at a locus, k_i methylated and n_i total calls.  The sample COUNTS at the locus when
+ * n_i >= c, the per-sample minimum coverage (option "group_min_cov").  Over the counting samples of a group:
+ *   m_g = their number,  K_g = sum k_i,  N_g = sum n_i,  Q_g = sum q_i,  q_i = floor(k_i^2 * 2^20 / n_i)
+ * q_i is an integer (n_i < 2^20, so k_i^2 * 2^20 < 2^60), which makes Q_g -- the one moment the statistic needs beyond the pooled
+ * counts -- additive over samples in integer atomics, exactly as the planes are.  A locus is TESTED when m_1 >= r, m_2 >= r and
+ * nu = m_1 + m_2 - 2 >= 1 (r = min_reps).  With ph_g = K_g / N_g, ph_0 = (K_1 + K_2) / (N_1 + N_2) and 0 * log(.) = 0:
+ *   diff = 100 K_1 / N_1 - 100 K_2 / N_2                       (rounded as hm_asm_t's diff)
+ *   D    = 2 sum_g [ K_g log(ph_g / ph_0) + (N_g - K_g) log((1 - ph_g) / (1 - ph_0)) ]       the binomial likelihood ratio, 1 df, >= 0
+ *   X2   = sum_g (Q_g 2^-20 - K_g^2 / N_g) / (ph_g (1 - ph_g))    Pearson's statistic of the two-proportion fit; a group with ph_g
+ *                                                              in {0, 1} contributes 0, a negative term (the floor in q_i) counts 0
+ *   phi  = max(1, X2 / nu),   F = D / phi,   pvalue = P(F(1, nu) >= F) = I_{nu / (nu + F)}(nu / 2, 1 / 2)
+ * pvalue is exactly 1 when D == 0 and never 0 (below DBL_MIN it is reported as DBL_MIN).  With phi floored at 1 a locus is never
+ * more significant than under the plain binomial model.  This is this library's own definition, not another tool's.
+ *
+ * Option "groups" (0 default, 1): needs "partitions" = 2 and must be set before hm_pileup_set_reference (else HM_ESTATE), which then
+ * also allocates and zeroes, per group, a uint64 moment plane (Q_g) and a uint8 sample-count plane (m_g), and one `seen` bitmap of
+ * 1 bit per base: 18.125 B per reference base more.  Without the option nothing is allocated.  Option "group_min_cov" (c: integer
+ * >= 1, default 5): HM_ESTATE once a sample has been opened. */
+typedef struct {            /* one tested locus = one row of <prefix>.groups.<ctx>.bed; 64 bytes */
+    int64_t gpos;
+    int32_t pcov1, ncov1, pcov2, ncov2;   /* K_1, N_1 - K_1, K_2, N_2 - K_2 */
+    uint32_t motif;
+    uint16_t m1, m2;
+    double diff, D, phi, pvalue;
+} hm_group_t;
+/* Opens the next sample of group `part` (1 or 2) and clears the seen bitmap: the rows of hm_pileup_load_sample_loci belong to it
+ * until the next call.  Returns the sample's index within its group (0, 1, ...).  HM_EINVAL for a bad part; HM_ESTATE without option
+ * "groups" or before hm_pileup_set_reference, on an engine voided by a bad row, on one that staged records or used
+ * hm_pileup_load_loci, and for the 256th sample of a group (the sample counts are bytes). */
+int hm_pileup_group_sample(hm_pileup_t* p, int32_t part);
+/* rows[0, n) of the open sample: HOST memory, any order, any number of calls; they pass through the slab of hm_pileup_load_loci
+ * (option "load_slab").  Each row is checked in this order, the first failure names it: gpos in [0, total reference length);
+ * pcov >= 0 and ncov >= 0; pcov + ncov < 2^20; motif <= 3.  A row that passes and has no count is ignored.  A row whose seen bit
+ * was already set -- the locus came before in THIS sample -- is a duplicate and adds nothing; the same locus in another sample
+ * is the point of the exercise.  A row with pcov + ncov < c sets its bit and adds nothing.  Every other row adds pcov / ncov to
+ * the group's partition planes and to the combined planes, raises the key to its motif (as hm_pileup_load_loci), adds q_i to the
+ * group's moment plane and 1 to its sample count.  Integer atomics only: the planes depend on neither row order, slab size nor
+ * launch geometry.  Returns the number of rows that added.  Any bad row: HM_EDATA, hm_pileup_last_error gives the number of each
+ * kind, and the engine is void as after hm_pileup_load_loci.  HM_ESTATE before hm_pileup_group_sample; once a sample has been
+ * opened hm_pileup_load_loci and hm_pileup_submit_read* return HM_ESTATE, and the other way round.  HM_EINVAL for n < 0 or rows NULL with
+ * n > 0.  The other fetches over the engine's planes see the pooled group counts: hm_pileup_fetch_asm is the pooled Fisher test. */
+int64_t hm_pileup_load_sample_loci(hm_pileup_t* p, const hm_locus_t* rows, int64_t n);
+/* The tested loci of the engine's planes [lo, hi) in ascending order, with diff, D, phi and pvalue computed on the device (fp64;
+ * the incomplete beta function by its continued fraction).  Returns their number (may exceed cap, or out NULL: then nothing is
+ * written).  hi == lo returns 0.  HM_ESTATE without option "groups", before hm_pileup_set_reference or on a voided engine;
+ * HM_EINVAL for min_reps outside 1 .. 255, lo < 0, lo > hi or hi past the reference. */
+int64_t hm_pileup_fetch_groups(hm_pileup_t* p, int64_t lo, int64_t hi, int32_t min_reps, hm_group_t* out, int64_t cap);
+/* The moment and sample-count planes of group `part` over [lo, hi), copied to HOST memory: moment[hi - lo] and samples[hi - lo],
+ * either may be NULL.  For tests and for callers that keep their own statistics.  Errors as hm_pileup_fetch_groups. */
+int hm_pileup_group_planes(hm_pileup_t* p, int32_t part, int64_t lo, int64_t hi, uint64_t* moment, uint8_t* samples);
+/* Host only.  q[i] = the Benjamini-Hochberg value of rows[i].pvalue among the rows of its context, min(motif, 2) (R's
+ * p.adjust(method = "BH")): equal p gives equal q.  m[ctx] receives the number of rows per context.  HM_EINVAL for a motif above 3
+ * or a pvalue outside [DBL_MIN, 1]. */
+int hm_group_qvalues(const hm_group_t* rows, int64_t n, double* q, uint64_t m[3]);
 
 /* ---- per-locus binomial test (`pileup -B / -e`): is a locus methylated at all ------------------------
  * Against a false-positive rate e per context -- given, or measured on an unmethylated control sequence as sum(pcov) /
