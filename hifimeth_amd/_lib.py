@@ -138,6 +138,12 @@ def lib():
         "hm_pileup_fetch_groups": (i64, [vp, i64, i64, i32, vp, i64]),
         "hm_pileup_group_planes": (C.c_int, [vp, i32, i64, i64, vp, vp]),
         "hm_group_qvalues": (C.c_int, [vp, i64, vp, vp]),
+        "hm_sample_geometry": (C.c_int, [vp]),
+        "hm_sample_open": (C.c_int, [vp]),
+        "hm_sample_load": (i64, [vp, vp, i64]),
+        "hm_sample_fetch_sums": (i64, [vp, i64, i64, i32, vp]),
+        "hm_sample_plane": (C.c_int, [vp, i32, i64, i64, vp]),
+        "hm_sample_corr": (C.c_int, [vp, i64, vp, vp, vp]),
         "hm_pileup_control_sums": (C.c_int, [vp, vp, vp, vp, i64, i64, vp]),
         "hm_pileup_site_histogram": (i64, [vp, vp, vp, vp, i64, i64, i64, vp, vp, i64]),
         "hm_sites_table": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp]),

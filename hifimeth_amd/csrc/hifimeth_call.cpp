@@ -14,6 +14,7 @@
 //     hifimeth-hip corr [-c N] A.cov.bed B.cov.bed          (Pearson r of two pileup outputs, hifimeth_pileup.cpp)
 //     hifimeth-hip diff [OPTIONS] REF.fa PREFIX1 PREFIX2 OUT (two pileups' *.cov.bed tested locus by locus, hifimeth_pileup.cpp)
 //     hifimeth-hip groupdiff [OPTIONS] REF.fa A1,A2,.. B1,B2,.. OUT (two groups of replicate pileups, hifimeth_pileup.cpp)
+//     hifimeth-hip samplecorr [OPTIONS] REF.fa S1,S2,..,SN OUT (N pileups' correlation matrix per context, hifimeth_pileup.cpp)
 //     hifimeth-hip modstats IN.bam                    (MM/ML parser + per-context histograms + adaptive thresholds)
 //     hifimeth-hip modlist IN.bam                     (the MM/ML parser's output per record: test seam against the
 //                                                      reference parser's fixture, tests/golden/modparse.json)
@@ -109,8 +110,9 @@ void usage() {
             "  %s pileup [OPTIONS] reference mod-bam output-prefix          per-locus methylation of one sample\n"
             "  %s diff [OPTIONS] reference prefix1 prefix2 output-prefix    two pileups tested for differential methylation\n"
             "  %s groupdiff [OPTIONS] reference a1,a2,... b1,b2,... output-prefix   two groups of replicate pileups tested likewise\n"
+            "  %s samplecorr [OPTIONS] reference s1,s2,...,sN output-prefix   the correlation matrix of N pileups, per context\n"
             "  %s corr [-c <min coverage>] bed1 bed2                        Pearson correlation of two pileups\n",
-            kName, kName, kName, kName, kName, kName, kName);
+            kName, kName, kName, kName, kName, kName, kName, kName);
 }
 
 // host threads this process may really use: the affinity mask, capped by the cgroup CPU quota (a container that is granted
@@ -912,6 +914,7 @@ int main(int argc, char** argv) {
     if (cmd == "cov2bed") return cmd_cov2bed(argc, argv);
     if (cmd == "diff") return cmd_diff(argc, argv);
     if (cmd == "groupdiff") return cmd_groupdiff(argc, argv);
+    if (cmd == "samplecorr") return cmd_samplecorr(argc, argv);
     if (cmd == "sample") return cmd_sample(argc, argv);
     if (cmd == "eval") return cmd_eval(argc, argv);
     usage();

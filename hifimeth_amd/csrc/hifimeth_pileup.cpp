@@ -1116,7 +1116,7 @@ bool parse_count(const char* a, const char* b, long long& v) {
 }
 
 // One <prefix>.<ctx>.cov.bed, plain or gzip, into partition `part` -- or, with part 0, into the open sample of `groupdiff`
-// (hm_pileup_load_sample_loci) -- with motif `motif`: read in blocks of whole lines, each block
+// (hm_pileup_load_sample_loci), with part -1 into that of `samplecorr` (hm_sample_load) -- with motif `motif`: read in blocks of whole lines, each block
 // parsed by `threads` workers over contiguous runs of lines and handed to the engine run by run.  Empty lines are skipped.  false
 // with a message naming the file and, for a bad line, its number.
 bool load_cov_bed(hm_pileup_t* pe, const Fasta& fa, const std::vector<int64_t>& seq_start, const std::string& path, int part, uint32_t motif,
@@ -1204,8 +1204,9 @@ bool load_cov_bed(hm_pileup_t* pe, const Fasta& fa, const std::vector<int64_t>& 
                 break;
             }
             lines_before += P.lines;
-            const int64_t rc = part ? hm_pileup_load_loci(pe, part, P.rows.data(), (int64_t)P.rows.size())
-                                    : hm_pileup_load_sample_loci(pe, P.rows.data(), (int64_t)P.rows.size());
+            const int64_t rc = part > 0   ? hm_pileup_load_loci(pe, part, P.rows.data(), (int64_t)P.rows.size())
+                               : part < 0 ? hm_sample_load(pe, P.rows.data(), (int64_t)P.rows.size())
+                                          : hm_pileup_load_sample_loci(pe, P.rows.data(), (int64_t)P.rows.size());
             if (rc < 0) { fprintf(stderr, "ERROR: %s: %s\n", path.c_str(), hm_pileup_last_error(pe)); ok = false; break; }
             n_rows += (uint64_t)rc;
         }
@@ -1424,5 +1425,127 @@ int cmd_groupdiff(int argc, char** argv) {
     fprintf(stderr, "## %zu + %zu samples, %llu + %llu counting loci of %d contexts, %zu tested in %.2f s: parse + load %.2f s; test + BED %.2f s\n",
             group[0].size(), group[1].size(), (unsigned long long)n_rows[0], (unsigned long long)n_rows[1], n_ctx, rows.size(), secs(t_start, clk::now()),
             secs(t_start, t_load), secs(t_load, clk::now()));
+    return 0;
+}
+
+// ---- samplecorr [OPTIONS] reference s1,s2,...,sN out-prefix (ours) -------------------------------------------------------------------
+// The sample-by-sample correlation matrix per context: every list element is a prefix as `diff` takes it, every sample's rows go
+// into its own level plane (hm_sample_open, hm_sample_load), and one fetch over the whole reference gives the exact
+// integer sums of every pair (hm_sample_fetch_sums), from which hm_sample_corr makes r and the means.
+int cmd_samplecorr(int argc, char** argv) {
+    static const char* cn[3] = {"CpG", "CHG", "CHH"};
+    PileupOptions o;
+    int first = 0, status = 0;
+    if (!parse_command_line(CMD_SAMPLECORR, argc, argv, o, first, status)) return status;
+    o.ref = argv[first];
+    const std::vector<std::string> sample = split_list(argv[first + 1]);
+    o.prefix = argv[first + 2];
+    const int N = (int)sample.size();
+    if (sample.size() < 2 || sample.size() > HM_SAMPLE_MAX) {  // before any file is opened
+        fprintf(stderr, "ERROR: samplecorr takes 2 to %d samples, the list names %zu\n", HM_SAMPLE_MAX, sample.size());
+        command_usage(CMD_SAMPLECORR, argv[0]);
+        return EXIT_FAILURE;
+    }
+    for (const std::string& s : sample)
+        if (s.empty()) { fprintf(stderr, "ERROR: an empty prefix in the list of samples\n"); return EXIT_FAILURE; }
+    fprintf(stderr, "\n\n====================> Parameters:\nCPU threads: %d\nGenomic reference: %s\n", o.threads, o.ref.c_str());
+    for (int i = 0; i < N; ++i) fprintf(stderr, "sample %d: %s.<ctx>.cov.bed\n", i + 1, sample[(size_t)i].c_str());
+    fprintf(stderr, "output prefix: %s\nsamplecorr: min sample coverage %lld, %s -> %s.samplecorr.*\n\n\n", o.prefix.c_str(), o.sample_min_cov,
+            o.sample_complete ? "loci where all samples count" : "loci where both samples of a pair count", o.prefix.c_str());
+
+    using clk = std::chrono::steady_clock;
+    const auto t_start = clk::now();
+    std::vector<std::string> files[3];  // found before the reference is read and the engine exists, as in `diff`
+    int n_ctx = 0;
+    for (int c = 0; c < 3; ++c) {
+        bool all = true;
+        for (const std::string& s : sample) {
+            files[c].push_back(find_cov_bed(s, cn[c]));
+            if (!files[c].back().empty()) continue;
+            fprintf(stderr, "Skip context %s: %s.%s.cov.bed is missing\n", cn[c], s.c_str(), cn[c]);
+            all = false;
+        }
+        if (all) ++n_ctx;
+        else files[c].clear();
+    }
+    if (!n_ctx) { fprintf(stderr, "ERROR: no context has a cov.bed file of every sample\n"); return EXIT_FAILURE; }
+    Fasta fa;
+    std::string err;
+    if (!load_fasta(o.ref, fa, err)) { fprintf(stderr, "ERROR: %s\n", err.c_str()); return EXIT_FAILURE; }
+    if (fa.names.empty()) { fprintf(stderr, "ERROR: no sequence in %s\n", o.ref.c_str()); return EXIT_FAILURE; }
+    fprintf(stderr, "Load %zu sequences (%zu bases) from %s\n", fa.names.size(), fa.bases.size(), o.ref.c_str());
+    std::vector<int64_t> seq_start(fa.names.size() + 1, 0);
+    for (size_t s = 0; s < fa.names.size(); ++s) seq_start[s + 1] = seq_start[s] + fa.length[s];
+
+    hm_pileup_t* pe = nullptr;
+    if (hm_pileup_create(&pe, o.device) != HM_OK) { fprintf(stderr, "ERROR: %s\n", hm_pileup_last_error(nullptr)); return EXIT_FAILURE; }
+    std::unique_ptr<hm_pileup_t, decltype(&hm_pileup_destroy)> engine(pe, hm_pileup_destroy);  // destroyed on every way out
+    auto die = [&](const std::string& what) { return engine_error(pe, what); };
+    if (hm_pileup_set_option(pe, "samples", (double)N) != HM_OK || hm_pileup_set_option(pe, "sample_min_cov", (double)o.sample_min_cov) != HM_OK)
+        return die("samples");
+    if (hm_pileup_set_reference(pe, (int32_t)fa.names.size(), fa.length.data(), fa.bases.data()) != HM_OK) return die("reference");
+    uint64_t n_rows = 0;
+    for (int i = 0; i < N; ++i) {  // a sample's contexts share its plane: one locus, one context
+        if (hm_sample_open(pe) < 0) return die("sample");
+        for (int c = 0; c < 3; ++c)
+            if (!files[c].empty() && !load_cov_bed(pe, fa, seq_start, files[c][(size_t)i], -1, (uint32_t)c, o.threads, n_rows)) return EXIT_FAILURE;
+    }
+    const auto t_load = clk::now();
+
+    // the samples file always reports a sample's own counting loci: the diagonal of the pairwise sums
+    const size_t pairs = (size_t)N * (size_t)(N + 1) / 2;
+    std::vector<hm_sample_pair_t> own(3 * pairs), sums;
+    if (hm_sample_fetch_sums(pe, 0, seq_start.back(), 0, own.data()) != (int64_t)own.size()) return die("sample sums");
+    if (o.sample_complete) {
+        sums.resize(own.size());
+        if (hm_sample_fetch_sums(pe, 0, seq_start.back(), 1, sums.data()) != (int64_t)sums.size()) return die("sample sums");
+    }
+    engine.reset();
+    const std::vector<hm_sample_pair_t>& e = o.sample_complete ? sums : own;
+    std::vector<double> r(e.size()), mi(e.size()), mj(e.size()), own_mean(own.size());
+    if (hm_sample_corr(e.data(), (int64_t)e.size(), r.data(), mi.data(), mj.data()) != HM_OK ||
+        hm_sample_corr(own.data(), (int64_t)own.size(), nullptr, own_mean.data(), nullptr) != HM_OK) {
+        fprintf(stderr, "ERROR: samplecorr: hm_sample_corr refused the sums\n");
+        return EXIT_FAILURE;
+    }
+    // entry of context c and pair i <= j: context-major, then i, then j
+    const auto at = [&](int c, int i, int j) { return (size_t)c * pairs + (size_t)i * (size_t)N - (size_t)i * (size_t)(i - 1) / 2 + (size_t)(j - i); };
+    const auto open_out = [&](const std::string& path) {
+        FILE* f = fopen(path.c_str(), "w");
+        if (!f) fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str());
+        return f;
+    };
+    FILE* fs = open_out(o.prefix + ".samplecorr.samples.tsv");
+    if (!fs) return EXIT_FAILURE;
+    fprintf(fs, "ctx\tsample\tn\tmean\n");
+    for (int c = 0; c < 3; ++c) {
+        if (files[c].empty()) continue;
+        for (int i = 0; i < N; ++i)
+            fprintf(fs, "%s\t%s\t%llu\t%.6g\n", cn[c], sample[(size_t)i].c_str(), (unsigned long long)own[at(c, i, i)].n, own_mean[at(c, i, i)]);
+        FILE* f = open_out(o.prefix + ".samplecorr." + cn[c] + ".tsv");
+        if (!f) { fclose(fs); return EXIT_FAILURE; }
+        fprintf(f, "sample_i\tsample_j\tn\tmean_i\tmean_j\tr\n");
+        for (int i = 0; i < N; ++i)
+            for (int j = i + 1; j < N; ++j) {
+                const size_t k = at(c, i, j);
+                fprintf(f, "%s\t%s\t%llu\t%.6g\t%.6g\t%.6g\n", sample[(size_t)i].c_str(), sample[(size_t)j].c_str(), (unsigned long long)e[k].n, mi[k], mj[k], r[k]);
+            }
+        fclose(f);
+        f = open_out(o.prefix + ".samplecorr." + cn[c] + ".matrix.tsv");
+        if (!f) { fclose(fs); return EXIT_FAILURE; }
+        fprintf(f, "sample");
+        for (const std::string& s : sample) fprintf(f, "\t%s", s.c_str());
+        fputc('\n', f);
+        for (int i = 0; i < N; ++i) {
+            fputs(sample[(size_t)i].c_str(), f);
+            for (int j = 0; j < N; ++j) fprintf(f, "\t%.6g", r[at(c, std::min(i, j), std::max(i, j))]);
+            fputc('\n', f);
+        }
+        fclose(f);
+    }
+    fclose(fs);
+    const auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+    fprintf(stderr, "## %d samples, %llu rows of %d contexts in %.2f s: parse + load %.2f s; sums + tables %.2f s\n", N, (unsigned long long)n_rows, n_ctx,
+            secs(t_start, clk::now()), secs(t_start, t_load), secs(t_load, clk::now()));
     return 0;
 }

@@ -1,4 +1,4 @@
-// hifimeth_pileup_opts.cpp -- the options of `pileup`, `diff` and `groupdiff`: one table that is parser and usage text at once, two strict number
+// hifimeth_pileup_opts.cpp -- the options of `pileup`, `diff`, `groupdiff` and `samplecorr`: one table that is parser and usage text at once, two strict number
 // parsers, and the checks between options as one ordered list.  A new option is one row here, a field of PileupOptions, a rule if
 // it depends on another option, and its cases in tools/make_cli_options.py.
 #include "hifimeth_pileup_opts.h"
@@ -275,6 +275,14 @@ const Option GROUP_OPTIONS[] = {
      "    counting samples in all\n    Default: 2"},
 };
 const char GROUP_FLAGS[] = "artd";
+// and so has `samplecorr`
+const Option SAMPLE_OPTIONS[] = {
+    {'a', "<int>", integer<&O::sample_min_cov, 1, (1 << 20) - 1>,
+     "Minimum coverage (pcov + ncov) a sample needs at a locus to count there, in [1, 1048575]\n    Default: 5"},
+    {'k', nullptr, flag<&O::sample_complete>,
+     "Complete mode: every pair is taken over the loci where all samples count, not over those where its two samples count"},
+};
+const char SAMPLE_FLAGS[] = "aktd";
 
 const char PILEUP_HEADER[] =
     "USAGE:\n"
@@ -314,11 +322,32 @@ const char GROUP_HEADER[] =
     "\n"
     "OPTIONAL ARGUMENTS:\n";
 
+const char SAMPLE_HEADER[] =
+    "USAGE:\n"
+    "  $0 samplecorr [OPTIONS] reference s1,s2,...,sN output-prefix\n"
+    "\n"
+    "DESCRIPTION:\n"
+    "  The sample-by-sample correlation matrix of 2 to 64 pileups, per context.  Every element of the comma-separated list is a\n"
+    "  prefix as `diff` takes it: <prefix>.<ctx>.cov.bed for ctx in CpG, CHG, CHH, plain or gzip.  A context is skipped unless every\n"
+    "  sample has its file.  A sample counts at a locus with at least -a calls; its level there is floor(pcov * 32768 / (pcov + ncov)).\n"
+    "  r is Pearson's correlation of the levels of two samples over the loci where both count (with -k: where all samples count),\n"
+    "  from exact integer sums; nan with fewer than two such loci or a sample that is constant over them.\n"
+    "  Writes <output-prefix>.samplecorr.<ctx>.tsv: sample_i, sample_j, shared loci n, mean level of i and of j over them in\n"
+    "  percent, r, for every pair i < j; <output-prefix>.samplecorr.<ctx>.matrix.tsv: the N x N matrix of r under the samples' names;\n"
+    "  and <output-prefix>.samplecorr.samples.tsv: ctx, sample, its counting loci, its mean level over them in percent\n"
+    "\n"
+    "OPTIONAL ARGUMENTS:\n";
+
 const Option* find_option(Command cmd, char letter) {
     if (cmd == CMD_DIFF && !strchr(DIFF_FLAGS, letter)) return nullptr;
     if (cmd == CMD_GROUPDIFF) {
         if (!strchr(GROUP_FLAGS, letter)) return nullptr;
         for (const Option& opt : GROUP_OPTIONS)
+            if (opt.letter == letter) return &opt;
+    }
+    if (cmd == CMD_SAMPLECORR) {
+        if (!strchr(SAMPLE_FLAGS, letter)) return nullptr;
+        for (const Option& opt : SAMPLE_OPTIONS)
             if (opt.letter == letter) return &opt;
     }
     for (const Option& opt : OPTIONS)
@@ -334,7 +363,7 @@ void print_text(const char* text, const char* exe) {  // $0: the program
 }
 
 void usage(Command cmd, const char* exe) {
-    print_text(cmd == CMD_DIFF ? DIFF_HEADER : cmd == CMD_GROUPDIFF ? GROUP_HEADER : PILEUP_HEADER, exe);
+    print_text(cmd == CMD_DIFF ? DIFF_HEADER : cmd == CMD_GROUPDIFF ? GROUP_HEADER : cmd == CMD_SAMPLECORR ? SAMPLE_HEADER : PILEUP_HEADER, exe);
     const auto row = [&](const Option& opt) {
         fprintf(stderr, "  -%c%s%s\n    ", opt.letter, opt.metavar ? " " : "", opt.metavar ? opt.metavar : "");
         print_text(cmd == CMD_DIFF && opt.diff_help ? opt.diff_help : opt.help, exe);
@@ -342,6 +371,7 @@ void usage(Command cmd, const char* exe) {
     };
     if (cmd == CMD_DIFF) for (const char* f = DIFF_FLAGS; *f; ++f) row(*find_option(cmd, *f));
     else if (cmd == CMD_GROUPDIFF) for (const char* f = GROUP_FLAGS; *f; ++f) row(*find_option(cmd, *f));
+    else if (cmd == CMD_SAMPLECORR) for (const char* f = SAMPLE_FLAGS; *f; ++f) row(*find_option(cmd, *f));
     else for (const Option& opt : OPTIONS) row(opt);
 }
 
@@ -358,7 +388,7 @@ struct Parsed {
 // of this list is the precedence: the groups asm, call, sites, domains, patterns, bedmethyl, linkage, profile, intervals, context,
 // and inside each group the order below.  It is not uniform -- patterns, linkage, profile and context report a bad value before a
 // missing parent, asm, domains, bedmethyl and intervals the missing parent first -- and tests/golden/cli_options.json pins it.
-// `diff` runs the rules marked CMD_DIFF, `groupdiff` those marked CMD_GROUPDIFF.
+// `diff` runs the rules marked CMD_DIFF, `groupdiff` those marked CMD_GROUPDIFF, `samplecorr` those marked CMD_SAMPLECORR.
 struct Rule {
     int commands;
     bool (*fires)(const Parsed& p);
@@ -398,9 +428,12 @@ const Rule RULES[] = {
     {CMD_PILEUP, [](const Parsed& p) { return p.any_bad("SO"); }, "-S must be an integer in [0, 3], -O an integer >= 1"},
     {CMD_PILEUP, [](const Parsed& p) { return p.any_seen("O") && p.o.context_flank < 0; }, "-O needs -S"},
     {CMD_GROUPDIFF, [](const Parsed& p) { return p.any_bad("ar"); }, "-a must be an integer in [1, 1048575], -r an integer in [1, 255]"},
+    {CMD_SAMPLECORR, [](const Parsed& p) { return p.any_bad("a"); }, "-a must be an integer in [1, 1048575]"},
 };
 
 }  // namespace
+
+void command_usage(Command cmd, const char* exe) { usage(cmd, exe); }
 
 bool parse_command_line(Command cmd, int argc, char** argv, PileupOptions& o, int& first, int& status, bool (*levels_ok)(PileupOptions&)) {
     const auto leave = [&](int code) { usage(cmd, argv[0]); status = code; return false; };
@@ -422,7 +455,7 @@ bool parse_command_line(Command cmd, int argc, char** argv, PileupOptions& o, in
         if (opt->fatal) { fputs(opt->fatal, stderr); return leave(EXIT_FAILURE); }
         p.bad += opt->letter;
     }
-    if (argc - i != (cmd == CMD_PILEUP ? 3 : 4)) return leave(EXIT_FAILURE);
+    if (argc - i != (cmd == CMD_PILEUP || cmd == CMD_SAMPLECORR ? 3 : 4)) return leave(EXIT_FAILURE);
     // ahead of the rules although its rule comes tenth: it only writes the weights, which every earlier way out discards
     p.levels_bad = o.domains && !p.any_bad("uxj") && levels_ok && !levels_ok(o);
     for (const Rule& r : RULES)

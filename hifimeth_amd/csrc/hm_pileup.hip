@@ -541,6 +541,133 @@ __global__ __launch_bounds__(TPB) void load_sample_kernel(const hm_locus_t* __re
     }
 }
 
+// ---- N samples (`samplecorr`, hm_sample_load): the rows of ONE sample into its uint16 level plane ---------------------------
+// The checks of load_sample_kernel in the same order.  The stored value of a locus is 0 (nothing seen), u + 1 with the level
+// u = floor(k 2^15 / n) in [0, 32768] (the sample counts there), or SAMPLE_BELOW (seen, below the minimum coverage).  There are no
+// 16-bit atomics: the value goes in by a compare-and-swap on the aligned 32-bit word that holds the locus and its neighbour, retried
+// while only the neighbour's half changed.  A half that is not 0 -- before the first try or after a lost one -- is a duplicate, which
+// adds nothing: of two rows of one locus exactly one wins, in one slab or in two.  The winner raises the key and, if the sample counts,
+// adds its counts to the combined planes.  Which of two duplicate rows wins depends on the launch, but a duplicate voids the engine.
+enum SampleLoadCounter { SLOAD_WROTE = 0, SLOAD_BAD_GPOS, SLOAD_BAD_COUNT, SLOAD_BAD_BIG, SLOAD_BAD_MOTIF, SLOAD_BAD_DUP, SLOAD_COUNTERS };
+constexpr int SAMPLE_MAX = HM_SAMPLE_MAX, SAMPLE_TILE = HM_SAMPLE_TILE;
+constexpr uint32_t SAMPLE_BELOW = 0xFFFFu;
+
+struct SampleLoadPlanes : CountPlanes {
+    uint32_t* level;  // the open sample's plane, two loci per word
+    int32_t min_cov;
+};
+
+__global__ __launch_bounds__(TPB) void sample_load_kernel(const hm_locus_t* __restrict__ rows, int64_t n, int64_t total, SampleLoadPlanes pl,
+                                                           unsigned long long* __restrict__ c) {
+    uint32_t mine[SLOAD_COUNTERS] = {0u, 0u, 0u, 0u, 0u, 0u};
+    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
+        const hm_locus_t r = rows[i];
+        if (r.gpos < 0 || r.gpos >= total) { ++mine[SLOAD_BAD_GPOS]; continue; }
+        if (r.pcov < 0 || r.ncov < 0) { ++mine[SLOAD_BAD_COUNT]; continue; }
+        if ((int64_t)r.pcov + r.ncov >= GROUP_COUNT_LIMIT) { ++mine[SLOAD_BAD_BIG]; continue; }
+        if (r.motif > 3u) { ++mine[SLOAD_BAD_MOTIF]; continue; }
+        if (r.pcov == 0 && r.ncov == 0) continue;
+        const int64_t g = r.gpos;
+        const int32_t cov = r.pcov + r.ncov;
+        const bool counts = cov >= pl.min_cov;
+        const uint32_t value = counts ? (uint32_t)(((unsigned long long)r.pcov << 15) / (unsigned long long)cov) + 1u : SAMPLE_BELOW;
+        const int shift = 16 * (int)(g & 1);
+        uint32_t* word = &pl.level[g >> 1];
+        uint32_t old = *word;
+        bool wrote = false;
+        while (((old >> shift) & 0xFFFFu) == 0u) {
+            const uint32_t prev = atomicCAS(word, old, old | (value << shift));
+            if (prev == old) { wrote = true; break; }
+            old = prev;
+        }
+        if (!wrote) { ++mine[SLOAD_BAD_DUP]; continue; }
+        atomicMax(&pl.key[g], r.motif);
+        if (counts) {
+            if (r.pcov) atomicAdd(&pl.pcov[g], r.pcov);
+            if (r.ncov) atomicAdd(&pl.ncov[g], r.ncov);
+        }
+        ++mine[SLOAD_WROTE];
+    }
+    for (int k = 0; k < SLOAD_COUNTERS; ++k) {
+        uint32_t v = mine[k];
+        for (int d = 32; d; d >>= 1) v += __shfl_down(v, d);
+        if ((threadIdx.x & 63) == 0 && v) atomicAdd(&c[k], (unsigned long long)v);
+    }
+}
+
+// ---- the pair sums of M samples over [lo, hi) (hm_sample_fetch_sums; include/hifimeth_hip.h has the definition) ------------
+// Workgroup (x, y, z) walks the tiles x, x + gridDim.x, ... of SAMPLE_TILE positions (tiles start at multiples of SAMPLE_TILE, the
+// range cuts the first and the last) for context z; thread t of it owns pair y * TPB + t of the M (M + 1) / 2 pairs i <= j, in
+// the order of the output, and keeps its six sums in registers across all its tiles.  Per tile, thread t reads position t: the
+// key and the M stored values, plane after plane, so a wavefront reads 128 contiguous bytes of each plane.  A position that can add
+// -- of context z, and with a value in any sample, or in `complete` mode a counting value in all M -- puts its values into LDS,
+// one row per position, and its row number on a list (the order of the list is open: the sums are integers).  Rows are `pitch`
+// 32-bit words apart, pitch odd, so the 64 rows a wavefront writes fall into 64 different banks; in the walk all threads read the
+// same row, and the words of the samples i and j of neighbouring pairs are neighbours.  Each thread then walks the list.  u <= 2^15,
+// so a product fits 32 bits and each sum advances by one 32 x 32 + 64-bit multiply-add.  One 64-bit atomicAdd per sum at the end, into
+// table[(z * pairs + pair) * 6 + {n, si, sj, sii, sjj, sij}]: integer adds only, so the table depends on neither the grid nor the order.
+__global__ __launch_bounds__(TPB) void sample_sums_kernel(const uint16_t* __restrict__ planes, int64_t stride, int M, const uint32_t* __restrict__ key,
+                                                           int64_t lo, int64_t hi, int complete, unsigned long long* __restrict__ table) {
+    static_assert(SAMPLE_TILE == TPB, "thread t reads position t of a tile");
+    extern __shared__ uint32_t sample_lds[];
+    const int pitch = ((M + 1) / 2) | 1;                     // words per row
+    uint16_t* const vals = reinterpret_cast<uint16_t*>(sample_lds);  // [SAMPLE_TILE][2 * pitch]
+    int* const list = reinterpret_cast<int*>(sample_lds + SAMPLE_TILE * pitch);  // [SAMPLE_TILE], then the count
+    int* const count = list + SAMPLE_TILE;
+    const uint32_t ctx = blockIdx.z;
+    const int pairs = M * (M + 1) / 2;
+    int pair = (int)blockIdx.y * TPB + (int)threadIdx.x, pi = 0, pj = 0;
+    const bool owner = pair < pairs;
+    if (owner) {
+        int left = pair;
+        while (left >= M - pi) { left -= M - pi; ++pi; }
+        pj = pi + left;
+    }
+    unsigned long long n = 0, si = 0, sj = 0, sii = 0, sjj = 0, sij = 0;
+    const int64_t first = lo / SAMPLE_TILE, last = (hi + SAMPLE_TILE - 1) / SAMPLE_TILE;
+    for (int64_t tile = first + blockIdx.x; tile < last; tile += gridDim.x) {
+        if (threadIdx.x == 0) *count = 0;
+        __syncthreads();
+        const int64_t g = tile * SAMPLE_TILE + threadIdx.x;
+        if (g >= lo && g < hi && min(key[g] & 3u, 2u) == ctx) {
+            uint16_t* const row = vals + (size_t)threadIdx.x * 2 * pitch;
+            bool any = false, all = true;
+            for (int s = 0; s < M; ++s) {
+                const uint16_t v = planes[(int64_t)s * stride + g];
+                row[s] = v;
+                any |= v != 0;
+                all &= v != 0 && v != SAMPLE_BELOW;
+            }
+            if (complete ? all : any) list[atomicAdd(count, 1)] = (int)threadIdx.x;
+        }
+        __syncthreads();
+        const int m = *count;
+        if (owner) {
+            for (int k = 0; k < m; ++k) {
+                const uint16_t* const row = vals + (size_t)list[k] * 2 * pitch;
+                const uint32_t vi = row[pi], vj = row[pj];
+                if (vi == 0u || vi == SAMPLE_BELOW || vj == 0u || vj == SAMPLE_BELOW) continue;
+                const uint32_t ui = vi - 1u, uj = vj - 1u;
+                n += 1;
+                si += ui;
+                sj += uj;
+                sii += (unsigned long long)(ui * ui);
+                sjj += (unsigned long long)(uj * uj);
+                sij += (unsigned long long)(ui * uj);
+            }
+        }
+        __syncthreads();
+    }
+    if (!owner || n == 0) return;
+    unsigned long long* const t = table + ((size_t)ctx * pairs + pair) * 6;
+    atomicAdd(&t[0], n);
+    atomicAdd(&t[1], si);
+    atomicAdd(&t[2], sj);
+    atomicAdd(&t[3], sii);
+    atomicAdd(&t[4], sjj);
+    atomicAdd(&t[5], sij);
+}
+
 // ---- resident records joined with per-locus truth labels (`hifimeth eval`, src/app/hifimeth/eval.cpp:469-560) ----
 // labels[g]: -1 no truth, 0 unmethylated, 1 methylated.  bins[(motif * 2 + label) * 256 + prob] counts the records whose
 // locus carries a label; workgroup-private histogram in LDS, one global atomic per non-empty bin and workgroup.
@@ -2288,6 +2415,13 @@ struct hm_pileup {
     int32_t group_min_cov = 5;
     DevBuf d_gmoment[2]{DevBuf(EXACT), DevBuf(EXACT)}, d_gsamples[2]{DevBuf(EXACT), DevBuf(EXACT)}, d_gseen{EXACT}, d_gcoef{EXACT};
     int group_samples[2] = {0, 0}, group_open = 0;
+    // `samplecorr` ("samples" = N), all of it only with the option on: N uint16 level planes of sample_stride values each (2 N B
+    // per base), resident from hm_pileup_set_reference on; the samples opened so far (the last one is the open one); the table of
+    // a fetch, 3 x N (N + 1) / 2 x 6 uint64
+    int samples = 0, samples_open = 0;
+    int32_t sample_min_cov = 5;
+    int64_t sample_stride = 0;
+    DevBuf d_slevel{EXACT}, d_stable{EXACT};
     uint32_t thr_packed = 0;   // the three thresholds of the last hm_pileup_count
     bool counted = false;    // hm_pileup_count has run since hm_pileup_set_reference: what the -E, -M and -L fetches wait for
     int64_t n_recs = 0;
@@ -2613,8 +2747,8 @@ int stage_alignment(hm_pileup* p, uint32_t order, int32_t flag, int32_t sid, int
                     const uint8_t* seq4, int32_t n_cigar, const uint32_t* cigar, int64_t n_entries, const void* entries, int32_t hp,
                     PRead& r, BatchMark& mark) {
     if (!p) return HM_EINVAL;
-    if (p->loaded || p->load_failed || p->group_open)
-        return pfail(p, HM_ESTATE, "hm_pileup_submit_read on an engine whose counts were loaded (hm_pileup_load_loci, hm_pileup_group_sample)");
+    if (p->loaded || p->load_failed || p->group_open || p->samples_open)
+        return pfail(p, HM_ESTATE, "hm_pileup_submit_read on an engine whose counts were loaded (hm_pileup_load_loci, hm_pileup_group_sample, hm_sample_open)");
     if (hp < 0 || hp > 2) return pfail(p, HM_EINVAL, "haplotype partition must be 0, 1 or 2");
     if (hp && p->partitions != 2) return pfail(p, HM_ESTATE, "haplotype partition given but the partitions option is off");
     if (p->seq_off.empty()) return pfail(p, HM_ESTATE, "hm_pileup_submit_read before hm_pileup_set_reference");
@@ -2743,7 +2877,7 @@ int hm_pileup_set_option(hm_pileup_t* p, const char* key, double value) {
     // what is sized or listed when the reference arrives (the partition planes, the reference CpGs and their counters, the
     // linkage histograms) is decided before that; the planes also before the caller hands in planes of their own
     const bool partitions = k == "partitions";
-    if (partitions || k == "groups" || k == "patterns" || k == "pattern_span" || k == "bedmethyl" || k == "linkage" || k == "profile" || k == "trim5" || k == "trim3") {
+    if (partitions || k == "groups" || k == "samples" || k == "patterns" || k == "pattern_span" || k == "bedmethyl" || k == "linkage" || k == "profile" || k == "trim5" || k == "trim3") {
         if (!p->seq_off.empty() || (partitions && !p->own_planes))
             return pfail(p, HM_ESTATE, k + " must be set before hm_pileup_set_reference" + (partitions ? " / hm_pileup_use_planes" : ""));
     }
@@ -2784,6 +2918,15 @@ int hm_pileup_set_option(hm_pileup_t* p, const char* key, double value) {
             return pfail(p, HM_EINVAL, "group_min_cov must be an integer in 1 .. 2^20 - 1");
         if (p->group_open) return pfail(p, HM_ESTATE, "group_min_cov must be set before the first hm_pileup_group_sample");
         p->group_min_cov = (int32_t)value;
+    } else if (k == "samples") {  // the level planes are sized when the reference arrives
+        if (value != 0.0 && (!(value >= 2.0 && value <= (double)SAMPLE_MAX) || value != std::floor(value)))
+            return pfail(p, HM_EINVAL, "samples must be 0 or an integer in 2 .. 64");
+        p->samples = (int)value;
+    } else if (k == "sample_min_cov") {
+        if (!(value >= 1.0 && value < (double)GROUP_COUNT_LIMIT) || value != std::floor(value))
+            return pfail(p, HM_EINVAL, "sample_min_cov must be an integer in 1 .. 2^20 - 1");
+        if (p->samples_open) return pfail(p, HM_ESTATE, "sample_min_cov must be set before the first hm_sample_open");
+        p->sample_min_cov = (int32_t)value;
     } else if (k == "load_slab") {  // the device holds one slab of rows whatever a load brings; at any time
         if (!(value >= 1.0 && value <= (double)LOAD_SLAB_MAX) || value != std::floor(value))
             return pfail(p, HM_EINVAL, "load_slab must be an integer in 1 .. 2^24");
@@ -2866,6 +3009,13 @@ int hm_pileup_set_reference(hm_pileup_t* p, int32_t n_seqs, const int64_t* seq_l
             p->d_gseen.reserve(4 * ((n + 31) / 32));
             HIP_TRY(hipMemsetAsync(p->d_gseen.p, 0, 4 * ((n + 31) / 32), p->stream));
             p->group_samples[0] = p->group_samples[1] = p->group_open = 0;
+        }
+        if (p->samples) {  // a plane is a whole number of words: the kernel swaps the word that holds a locus
+            p->sample_stride = (std::max<int64_t>(total, 1) + 1) & ~int64_t(1);
+            const size_t bytes = 2 * (size_t)p->sample_stride * (size_t)p->samples;
+            p->d_slevel.reserve(bytes);
+            HIP_TRY(hipMemsetAsync(p->d_slevel.p, 0, bytes, p->stream));
+            p->samples_open = 0;
         }
         if (p->patterns || p->bedmethyl) {
             const int rc = list_reference_cpgs(p);
@@ -3154,7 +3304,8 @@ int64_t hm_pileup_load_loci(hm_pileup_t* p, int32_t part, const hm_locus_t* rows
     if (p->partitions != 2 || p->seq_off.empty() || !p->pcov || !p->hp_pcov[0] || !p->hp_pcov[1])
         return pfail(p, HM_ESTATE, "hm_pileup_load_loci needs option partitions = 2 and hm_pileup_set_reference");
     if (p->staged_any) return pfail(p, HM_ESTATE, "hm_pileup_load_loci on an engine that has staged records: counts come from records or from loads, not both");
-    if (p->group_open) return pfail(p, HM_ESTATE, "hm_pileup_load_loci on an engine that opened a group sample (hm_pileup_group_sample)");
+    if (p->group_open || p->samples_open)
+        return pfail(p, HM_ESTATE, "hm_pileup_load_loci on an engine that opened a sample (hm_pileup_group_sample, hm_sample_open)");
     if (n == 0) return 0;
     const int64_t slab = p->load_slab;
     unsigned long long c[LOAD_COUNTERS] = {0, 0, 0, 0, 0};
@@ -3226,8 +3377,8 @@ int hm_pileup_group_sample(hm_pileup_t* p, int32_t part) {
     if (part != 1 && part != 2) return pfail(p, HM_EINVAL, "hm_pileup_group_sample: part must be 1 or 2");
     const int rc = group_ready(p, "hm_pileup_group_sample");
     if (rc != HM_OK) return rc;
-    if (p->staged_any || p->loaded)
-        return pfail(p, HM_ESTATE, "hm_pileup_group_sample on an engine that staged records or used hm_pileup_load_loci: counts come from one source");
+    if (p->staged_any || p->loaded || p->samples_open)
+        return pfail(p, HM_ESTATE, "hm_pileup_group_sample on an engine that staged records or used hm_pileup_load_loci / hm_sample_open: counts come from one source");
     if (p->group_samples[part - 1] >= GROUP_MAX_SAMPLES) return pfail(p, HM_ESTATE, "hm_pileup_group_sample: a group holds at most 255 samples");
     const int cleared = guarded(p, [&] {
         HIP_TRY(hipMemsetAsync(p->d_gseen.p, 0, 4 * (((size_t)std::max<int64_t>(p->seq_off.back(), 1) + 31) / 32), p->stream));
@@ -3336,6 +3487,152 @@ int hm_group_qvalues(const hm_group_t* rows, int64_t n, double* q, uint64_t m[3]
             if (std::min(rows[i].motif, 2u) == c) ent.push_back(BhEntry{rows[i].pvalue, 1, i});
         m[c] = ent.size();
         bh_qvalues(ent, m[c], [&](int64_t where, double v) { q[where] = v; });
+    }
+    return HM_OK;
+}
+
+// ---- `samplecorr` -----------------------------------------------------------------------------------------------------------------
+namespace {
+// what the sample calls share: the option, the reference, an engine that is not void
+int sample_ready(hm_pileup* p, const char* who) {
+    const std::string w = who;
+    if (!p->samples || p->seq_off.empty() || !p->d_slevel.p) return pfail(p, HM_ESTATE, w + " needs option samples = N and hm_pileup_set_reference");
+    if (p->load_failed) return pfail(p, HM_ESTATE, w + ": " + LOAD_FAILED_TEXT);
+    if (!p->pcov || !p->ncov || !p->key) return pfail(p, HM_ESTATE, w + " without planes");
+    return HM_OK;
+}
+int sample_range(hm_pileup* p, const char* who, int64_t lo, int64_t hi) {
+    const int rc = sample_ready(p, who);
+    if (rc != HM_OK) return rc;
+    if (lo < 0 || hi < lo || hi > p->seq_off.back()) return pfail(p, HM_EINVAL, std::string(who) + ": bad range");
+    return HM_OK;
+}
+}  // namespace
+
+int hm_sample_geometry(int64_t out[2]) {
+    if (!out) return HM_EINVAL;
+    out[0] = HM_SAMPLE_TILE;
+    out[1] = HM_SAMPLE_MAX;
+    return HM_OK;
+}
+
+int hm_sample_open(hm_pileup_t* p) {
+    if (!p) return HM_EINVAL;
+    const int rc = sample_ready(p, "hm_sample_open");
+    if (rc != HM_OK) return rc;
+    if (p->staged_any || p->loaded || p->group_open)
+        return pfail(p, HM_ESTATE, "hm_sample_open on an engine that staged records or used hm_pileup_load_loci / hm_pileup_group_sample: counts come from one source");
+    if (p->samples_open >= p->samples) return pfail(p, HM_ESTATE, "hm_sample_open: all " + std::to_string(p->samples) + " samples of option samples are open");
+    return p->samples_open++;
+}
+
+int64_t hm_sample_load(hm_pileup_t* p, const hm_locus_t* rows, int64_t n) {
+    if (!p) return HM_EINVAL;
+    if (n < 0 || (n && !rows)) return pfail(p, HM_EINVAL, "hm_sample_load: n >= 0, rows not NULL");
+    const int ready = sample_ready(p, "hm_sample_load");
+    if (ready != HM_OK) return ready;
+    if (!p->samples_open) return pfail(p, HM_ESTATE, "hm_sample_load before hm_sample_open");
+    if (n == 0) return 0;
+    const int64_t slab = p->load_slab;
+    unsigned long long c[SLOAD_COUNTERS] = {0, 0, 0, 0, 0, 0};
+    const int rc = guarded(p, [&] {
+        p->d_load.reserve(sizeof(hm_locus_t) * (size_t)slab);
+        p->d_loadcnt.reserve(sizeof c);
+        HIP_TRY(hipMemsetAsync(p->d_loadcnt.p, 0, sizeof c, p->stream));
+        const SampleLoadPlanes pl{{p->pcov, p->ncov, p->key}, p->d_slevel.as<uint32_t>() + (p->samples_open - 1) * (p->sample_stride / 2),
+                                  p->sample_min_cov};
+        for (int64_t at = 0; at < n; at += slab) {  // as hm_pileup_load_loci: a slab's copy follows the kernel over the one before
+            const int64_t m = std::min(slab, n - at);
+            HIP_TRY(hipMemcpyAsync(p->d_load.p, rows + at, sizeof(hm_locus_t) * (size_t)m, hipMemcpyHostToDevice, p->stream));
+            hipLaunchKernelGGL(sample_load_kernel, dim3(grid_for(m, 4096)), dim3(TPB), 0, p->stream, p->d_load.as<hm_locus_t>(), m,
+                               p->seq_off.back(), pl, p->d_loadcnt.as<unsigned long long>());
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipMemcpyAsync(c, p->d_loadcnt.p, sizeof c, hipMemcpyDeviceToHost, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        return HM_OK;
+    });
+    if (rc < 0) return rc;
+    unsigned long long bad = 0;
+    for (int k = SLOAD_BAD_GPOS; k < SLOAD_COUNTERS; ++k) bad += c[k];
+    if (bad) {
+        p->load_failed = true;
+        static const char* kind[SLOAD_COUNTERS] = {"", "gpos outside the reference", "negative count", "count above 2^20 - 1", "motif above 3",
+                                                   "locus given twice in one sample"};
+        std::string msg = "hm_sample_load: " + std::to_string(bad) + " bad rows";
+        const char* sep = ": ";
+        for (int k = SLOAD_BAD_GPOS; k < SLOAD_COUNTERS; ++k) {
+            if (!c[k]) continue;
+            msg += sep + std::to_string(c[k]) + " " + kind[k];
+            sep = ", ";
+        }
+        return pfail(p, HM_EDATA, msg);
+    }
+    return (int64_t)c[SLOAD_WROTE];
+}
+
+int64_t hm_sample_fetch_sums(hm_pileup_t* p, int64_t lo, int64_t hi, int32_t complete, hm_sample_pair_t* out) {
+    if (!p) return HM_EINVAL;
+    if (complete != 0 && complete != 1) return pfail(p, HM_EINVAL, "hm_sample_fetch_sums: complete must be 0 or 1");
+    const int rc = sample_range(p, "hm_sample_fetch_sums", lo, hi);
+    if (rc != HM_OK) return rc;
+    const int M = p->samples_open, pairs = M * (M + 1) / 2;
+    if (!pairs) return 0;
+    if (!out) return pfail(p, HM_EINVAL, "hm_sample_fetch_sums: out is NULL");
+    std::vector<unsigned long long> table((size_t)3 * pairs * 6, 0);
+    if (hi > lo) {
+        const int done = guarded(p, [&] {
+            const size_t bytes = sizeof(unsigned long long) * table.size();
+            p->d_stable.reserve(sizeof(unsigned long long) * 3 * 6 * (size_t)(SAMPLE_MAX * (SAMPLE_MAX + 1) / 2));
+            HIP_TRY(hipMemsetAsync(p->d_stable.p, 0, bytes, p->stream));
+            const int64_t tiles = (hi + SAMPLE_TILE - 1) / SAMPLE_TILE - lo / SAMPLE_TILE;
+            const int pitch = ((M + 1) / 2) | 1;
+            const size_t lds = sizeof(uint32_t) * ((size_t)SAMPLE_TILE * pitch + SAMPLE_TILE + 1);
+            const dim3 grid((unsigned)std::min<int64_t>(tiles, 1024), (unsigned)((pairs + TPB - 1) / TPB), 3);
+            hipLaunchKernelGGL(sample_sums_kernel, grid, dim3(TPB), lds, p->stream, p->d_slevel.as<uint16_t>(), p->sample_stride, M, p->key, lo, hi,
+                               (int)complete, p->d_stable.as<unsigned long long>());
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(table.data(), p->d_stable.p, bytes, hipMemcpyDeviceToHost, p->stream));
+            HIP_TRY(hipStreamSynchronize(p->stream));
+            return HM_OK;
+        });
+        if (done != HM_OK) return done;
+    }
+    hm_sample_pair_t* e = out;
+    const unsigned long long* t = table.data();
+    for (uint32_t c = 0; c < 3; ++c)
+        for (int i = 0; i < M; ++i)
+            for (int j = i; j < M; ++j, ++e, t += 6) *e = hm_sample_pair_t{i, j, c, 0, t[0], t[1], t[2], t[3], t[4], t[5]};
+    return (int64_t)3 * pairs;
+}
+
+int hm_sample_plane(hm_pileup_t* p, int32_t s, int64_t lo, int64_t hi, uint16_t* out) {
+    if (!p) return HM_EINVAL;
+    const int rc = sample_range(p, "hm_sample_plane", lo, hi);
+    if (rc != HM_OK) return rc;
+    if (s < 0 || s >= p->samples) return pfail(p, HM_EINVAL, "hm_sample_plane: no such sample");
+    if (hi == lo) return HM_OK;
+    if (!out) return pfail(p, HM_EINVAL, "hm_sample_plane: out is NULL");
+    return guarded(p, [&] {
+        HIP_TRY(hipMemcpyAsync(out, p->d_slevel.as<uint16_t>() + (int64_t)s * p->sample_stride + lo, 2 * (size_t)(hi - lo), hipMemcpyDeviceToHost, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        return HM_OK;
+    });
+}
+
+int hm_sample_corr(const hm_sample_pair_t* e, int64_t n, double* r, double* mean_i, double* mean_j) {
+    if (n < 0 || (n && !e)) return HM_EINVAL;
+    const double nan = std::nan("");
+    for (int64_t k = 0; k < n; ++k) {
+        using u128 = unsigned __int128;  // wraps instead of overflowing on sums no engine wrote; exact below 2^127, as every engine's are
+        const u128 cnt = e[k].n, si = e[k].si, sj = e[k].sj;
+        const __int128 num = (__int128)(cnt * e[k].sij - si * sj);
+        const __int128 va = (__int128)(cnt * e[k].sii - si * si);
+        const __int128 vb = (__int128)(cnt * e[k].sjj - sj * sj);
+        if (r) r[k] = e[k].n < 2 || va <= 0 || vb <= 0 ? nan : (double)num / (std::sqrt((double)va) * std::sqrt((double)vb));
+        const double denom = (double)e[k].n * 32768.0;
+        if (mean_i) mean_i[k] = e[k].n ? 100.0 * (double)e[k].si / denom : nan;
+        if (mean_j) mean_j[k] = e[k].n ? 100.0 * (double)e[k].sj / denom : nan;
     }
     return HM_OK;
 }

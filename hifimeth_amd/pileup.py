@@ -37,6 +37,12 @@ with enough replicates on both sides (GROUP_DTYPE: pooled counts, diff, likeliho
 D / phi), `group_qvalues(rows)` their BH q per context, `pu.groups_bed(rows, q)` and `groups_summary_tsv(rows, q, m)` the text of
 <prefix>.groups.<ctx>.bed and <prefix>.groups.summary.tsv.  include/hifimeth_hip.h has the definition of the statistic.
 
+N samples (`hifimeth-hip samplecorr`): on an engine made with samples=N, `pu.open_sample()` opens the next sample and
+`pu.load_sample(*read_cov_bed(...))` writes its rows into its uint16 level plane; `pu.sample_sums(lo, hi, complete=False)` returns
+the integer sums of every pair i <= j per context (SAMPLE_PAIR_DTYPE), `sample_corr(entries)` Pearson's r of the quantised levels
+and the two mean levels, `samplecorr_tsv`, `samplecorr_matrix_tsv` and `samplecorr_samples_tsv` the text of
+<prefix>.samplecorr.<ctx>.tsv, <prefix>.samplecorr.<ctx>.matrix.tsv and <prefix>.samplecorr.samples.tsv.
+
 Binomial test per locus (`pileup -B control` / `-e r,r,r`): is a locus methylated at all, against the caller's false-positive
 rate?  `pu.control_sums(lo, hi)` over an unmethylated control sequence gives the rates (`rates_from_sums`), `pu.site_histogram()`
 counts the loci per (motif, pcov, pcov + ncov), `sites_table(rates, bins, big)` -- host only, the C library's -- solves p-values
@@ -127,6 +133,9 @@ ASM_DTYPE = np.dtype([("gpos", "<i8"), ("pcov1", "<i4"), ("ncov1", "<i4"), ("pco
 ASMQ_DTYPE = np.dtype(ASM_DTYPE.descr + [("qvalue", "<f8")])                          # hm_asmq_t, 56 bytes
 GROUP_DTYPE = np.dtype([("gpos", "<i8"), ("pcov1", "<i4"), ("ncov1", "<i4"), ("pcov2", "<i4"), ("ncov2", "<i4"), ("motif", "<u4"),
                         ("m1", "<u2"), ("m2", "<u2"), ("diff", "<f8"), ("D", "<f8"), ("phi", "<f8"), ("pvalue", "<f8")])  # hm_group_t, 64 bytes
+SAMPLE_PAIR_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("ctx", "<u4"), ("reserved", "<u4"), ("n", "<u8"), ("si", "<u8"), ("sj", "<u8"),
+                              ("sii", "<u8"), ("sjj", "<u8"), ("sij", "<u8")])  # hm_sample_pair_t, 64 bytes
+SAMPLE_MAX = 64  # HM_SAMPLE_MAX
 ASM_BIN_DTYPE = np.dtype([("bin", "<u4"), ("reserved", "<u4"), ("count", "<u8"), ("pvalue", "<f8"), ("qvalue", "<f8")])  # hm_asm_bin_t, 32 bytes
 ASM_REGION_DTYPE = np.dtype([("start", "<i8"), ("end", "<i8"), ("pcov1", "<i8"), ("ncov1", "<i8"), ("pcov2", "<i8"), ("ncov2", "<i8"),
                              ("n_loci", "<i4"), ("sign", "<i4"), ("motif", "<u4"), ("flags", "<u4"), ("diff", "<f8"),
@@ -314,6 +323,57 @@ def groups_summary_tsv(rows: np.ndarray, q: np.ndarray, m) -> str:
     ctx = np.minimum(rows["motif"], 2)
     return "".join("%s\t%d\t%d\t%d\t%d\n" % (CTX_NAMES[c], int(m[c]), int(((ctx == c) & (q <= 0.05)).sum()), int(((ctx == c) & (q <= 0.01)).sum()),
                                               int(((ctx == c) & (rows["phi"] > 1.0)).sum())) for c in range(3))
+
+
+def sample_geometry() -> Tuple[int, int]:
+    """-> (HM_SAMPLE_TILE, HM_SAMPLE_MAX) of the library: the positions a workgroup of sample_sums takes at a time, the most samples"""
+    out = np.zeros(2, np.int64)
+    lib().hm_sample_geometry(out.ctypes.data_as(C.c_void_p))
+    return int(out[0]), int(out[1])
+
+
+def sample_corr(entries: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """`samplecorr` (hm_sample_corr, host only): -> (r, mean_i, mean_j) per entry of sample_sums: Pearson's r of the quantised
+    levels from the exact 128-bit num, va, vb (NaN when n < 2 or a variance is 0) and the mean levels in percent (NaN when n = 0)"""
+    entries = np.ascontiguousarray(entries, SAMPLE_PAIR_DTYPE)
+    r, mi, mj = (np.full(len(entries), np.nan) for _ in range(3))
+    if lib().hm_sample_corr(entries.ctypes.data_as(C.c_void_p), len(entries), *(a.ctypes.data_as(C.c_void_p) for a in (r, mi, mj))) != 0:
+        raise HifimethError("hm_sample_corr: bad argument")
+    return r, mi, mj
+
+
+def _sample_pairs(entries: np.ndarray, ctx: int):
+    """the entries of context `ctx` with their r and means -> {(i, j): (entry, r, mean_i, mean_j)}"""
+    e = np.ascontiguousarray(entries, SAMPLE_PAIR_DTYPE)
+    e = e[e["ctx"] == ctx]
+    return {(int(x["i"]), int(x["j"])): (x, *v) for x, *v in zip(e, *sample_corr(e))}
+
+
+def samplecorr_tsv(names: Sequence[str], entries: np.ndarray, ctx: int) -> str:
+    """the text of <prefix>.samplecorr.<ctx>.tsv: a header, then per pair i < j in index order sample_i, sample_j, n, mean_i,
+    mean_j, r.  entries: what sample_sums returned for the whole reference; names: the samples' in index order."""
+    pairs = _sample_pairs(entries, ctx)
+    return "sample_i\tsample_j\tn\tmean_i\tmean_j\tr\n" + "".join(
+        "%s\t%s\t%d\t%.6g\t%.6g\t%.6g\n" % (names[i], names[j], int(x["n"]), mi, mj, r) for (i, j), (x, r, mi, mj) in sorted(pairs.items()) if i < j)
+
+
+def samplecorr_matrix_tsv(names: Sequence[str], entries: np.ndarray, ctx: int) -> str:
+    """the text of <prefix>.samplecorr.<ctx>.matrix.tsv: `sample` and the N names, then per sample its name and N values of r; the
+    diagonal is the r of the diagonal entry, 1 when the sample has variance and nan otherwise"""
+    pairs = _sample_pairs(entries, ctx)
+    n = len(names)
+    return "sample\t" + "\t".join(names) + "\n" + "".join(
+        names[i] + "".join("\t%.6g" % pairs[(min(i, j), max(i, j))][1] for j in range(n)) + "\n" for i in range(n))
+
+
+def samplecorr_samples_tsv(names: Sequence[str], entries: np.ndarray, contexts: Sequence[int] = (0, 1, 2)) -> str:
+    """the text of <prefix>.samplecorr.samples.tsv: a header, then per context of `contexts` and sample ctx, sample, counting loci,
+    mean level in percent, from the diagonal entries of sample_sums(complete=False)"""
+    text = "ctx\tsample\tn\tmean\n"
+    for c in contexts:
+        pairs = _sample_pairs(entries, c)
+        text += "".join("%s\t%s\t%d\t%.6g\n" % (CTX_NAMES[c], names[i], int(pairs[(i, i)][0]["n"]), pairs[(i, i)][2]) for i in range(len(names)))
+    return text
 
 
 def stitch_asm_regions(parts, max_gap: int, min_loci: int, keep_edges: bool = False) -> Tuple[np.ndarray, int]:
@@ -817,7 +877,8 @@ class MethylationPileup:
     def __init__(self, genome: Sequence[Tuple[str, str]], device: int = 0, min_mapq: int = 0, min_pi: float = 0.0,
                  planes=None, partitions: bool = False, partition_planes=None, bases=None, patterns: int = 0,
                  pattern_span: int = PATTERN_SPAN, bedmethyl: bool = False, linkage: int = 0, profile: int = 0,
-                 trim: Tuple[int, int] = (0, 0), groups: bool = False, group_min_cov: int = 5):
+                 trim: Tuple[int, int] = (0, 0), groups: bool = False, group_min_cov: int = 5, samples: int = 0,
+                 sample_min_cov: int = 5):
         """genome: [(name, SEQUENCE)].  bases: optional, the concatenated upper-case bases of the whole reference as a
         C-contiguous uint8 buffer (ndarray, bytes, memoryview), handed to the engine as it is -- for references of gigabases,
         where joining, upper-casing and encoding strings would copy them three times; the second member of each genome entry
@@ -835,7 +896,9 @@ class MethylationPileup:
         row each (+3 x (2 D + 1) x 2 048 B: 12.6 MB at 1 024).
         trim: (n5, n3): the entries in the first n5 and the last n3 bases of every read are dropped.
         groups (needs partitions=True): replicate groups -- begin_sample / load_sample_loci / group_tests (+18.125 B per reference
-        base); group_min_cov: the coverage a sample needs at a locus to count there."""
+        base); group_min_cov: the coverage a sample needs at a locus to count there.
+        samples: 0, or N in 2 .. 64: N samples' level planes -- open_sample / load_sample / sample_sums (+2 N B per reference
+        base); sample_min_cov: the coverage a sample needs at a locus to count there."""
         self._L = lib()
         self._h = C.c_void_p()
         if self._L.hm_pileup_create(C.byref(self._h), device) != 0:
@@ -872,6 +935,9 @@ class MethylationPileup:
         if groups:
             self._check(self._L.hm_pileup_set_option(self._h, b"groups", 1.0))
             self._check(self._L.hm_pileup_set_option(self._h, b"group_min_cov", float(group_min_cov)))
+        if samples:
+            self._check(self._L.hm_pileup_set_option(self._h, b"samples", float(samples)))
+            self._check(self._L.hm_pileup_set_option(self._h, b"sample_min_cov", float(sample_min_cov)))
         if planes is not None:
             self._check(self._L.hm_pileup_use_planes(self._h, *(C.c_void_p(t.data_ptr()) for t in planes)))
         if bases is None:
@@ -1046,6 +1112,37 @@ class MethylationPileup:
             text[CTX_NAMES[min(int(r["motif"]), 2)]].append("%s\t%d\t%d\t%g\t%.6g\t%.6g\t%d\t%d\t%d\t%d\t%d\t%d\t%.6g\n" % (
                 self.names[s], k, k + 1, r["diff"], r["pvalue"], qv, r["m1"], r["pcov1"], r["ncov1"], r["m2"], r["pcov2"], r["ncov2"], r["phi"]))
         return {k: "".join(v) for k, v in text.items()}
+
+    def open_sample(self) -> int:
+        """`samplecorr` (hm_sample_open): opens the next sample; load_sample then writes its rows.  -> its index.  Needs
+        samples=N and an engine that never saw a read, a load_loci or a begin_sample."""
+        return self._check(self._L.hm_sample_open(self._h))
+
+    def load_sample(self, gpos, pcov, ncov, motif) -> int:
+        """`samplecorr` (hm_sample_load): rows of the open sample, as read_cov_bed returns them; any number of calls.  A
+        locus stores floor(pcov 2^15 / (pcov + ncov)) + 1 if pcov + ncov >= sample_min_cov (its counts then also go to the combined
+        planes), else 0xFFFF.  -> the number of rows that wrote a value.  HifimethError for a row outside the reference, a negative
+        count, a count of 2^20 or more, a motif above 3 or a locus twice in this sample: the engine is then void."""
+        gpos = np.ascontiguousarray(gpos, np.int64)
+        rows = np.zeros(len(gpos), LOCUS_DTYPE)
+        rows["gpos"], rows["pcov"], rows["ncov"], rows["motif"] = gpos, pcov, ncov, motif
+        return self._check(self._L.hm_sample_load(self._h, rows.ctypes.data_as(C.c_void_p), len(rows)))
+
+    def sample_plane(self, s: int, lo: int = 0, hi: Optional[int] = None) -> np.ndarray:
+        """-> the stored uint16 values of sample s over [lo, hi): 0 nothing seen, level + 1, or 0xFFFF seen below sample_min_cov"""
+        hi = self.n_loci if hi is None else hi
+        out = np.zeros(max(hi - lo, 0), np.uint16)
+        self._check(self._L.hm_sample_plane(self._h, s, lo, hi, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def sample_sums(self, lo: int = 0, hi: Optional[int] = None, complete: bool = False) -> np.ndarray:
+        """`samplecorr` (hm_sample_fetch_sums): per context and pair i <= j of the samples opened so far, context-major, the
+        exact integer sums n, si, sj, sii, sjj, sij over the loci of [lo, hi) where both count -- complete: where all count
+        (SAMPLE_PAIR_DTYPE).  Additive over adjacent ranges."""
+        hi = self.n_loci if hi is None else hi
+        out = np.zeros(3 * (SAMPLE_MAX * (SAMPLE_MAX + 1) // 2), SAMPLE_PAIR_DTYPE)
+        n = self._check(self._L.hm_sample_fetch_sums(self._h, lo, hi, int(complete), out.ctypes.data_as(C.c_void_p)))
+        return out[:n].copy()
 
     def bed(self, loci: np.ndarray) -> dict:
         """the text of <prefix>.{CpG,CHG,CHH}.cov.bed (pileup.cpp:562-590)"""

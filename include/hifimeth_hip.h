@@ -212,6 +212,7 @@ int hm_reset_timing(hm_engine_t* e);
  *   (ours) haplotype difference per locus, rows of <prefix>.asm.<ctx>.bed         -> hm_pileup_fetch_asm
  *   (ours) two samples' *.cov.bed rows into the haplotype planes (`diff`)         -> hm_pileup_load_loci
  *   (ours) two groups of replicates, tested with their spread (`groupdiff`)       -> hm_pileup_group_sample, hm_pileup_fetch_groups
+ *   (ours) N samples' correlation matrix per context (`samplecorr`)               -> hm_sample_open, hm_sample_fetch_sums
  * The whole genome's counters stay resident in HBM (12 B per reference base, 28 B with the haplotype partitions) and the
  * projected calls wait in HBM (12 B each) until the thresholds are known -- the reference spills them to a temporary file.
  * MM/ML parsing and BED text formatting stay on the host (hm_bam.h).                                           */
@@ -241,7 +242,8 @@ const char* hm_pileup_last_error(const hm_pileup_t* p); /* p may be NULL: error 
  * counting, see hm_pileup_submit_read_hp; must be set before hm_pileup_set_reference / hm_pileup_use_planes, else HM_ESTATE),
  * "patterns" and "pattern_span" (read-level CpG patterns), "bedmethyl" (per-CpG depth classes), "linkage" (co-methylation by
  * distance), "profile" (methylation by position in the read) and "trim5" / "trim3" (end trimming), all near the end of this header;
- * "load_slab" (hm_pileup_load_loci); "groups" and "group_min_cov" (hm_pileup_group_sample) */
+ * "load_slab" (hm_pileup_load_loci); "groups" and "group_min_cov" (hm_pileup_group_sample); "samples" and "sample_min_cov"
+ * (hm_sample_open) */
 int hm_pileup_set_option(hm_pileup_t* p, const char* key, double value);
 /* HbnDatabase: n_seqs upper-cased sequences back to back in `bases` (seq_len[i] bytes each).  Allocates and
  * zeroes the per-locus planes unless hm_pileup_use_planes was called before. */
@@ -485,6 +487,62 @@ int hm_pileup_group_planes(hm_pileup_t* p, int32_t part, int64_t lo, int64_t hi,
  * p.adjust(method = "BH")): equal p gives equal q.  m[ctx] receives the number of rows per context.  HM_EINVAL for a motif above 3
  * or a pvalue outside [DBL_MIN, 1]. */
 int hm_group_qvalues(const hm_group_t* rows, int64_t n, double* q, uint64_t m[3]);
+
+/* ---- N samples (`samplecorr`): the sample-by-sample correlation matrix per context ---------------------------
+ * There are N samples, 2 <= N <= 64 (HM_SAMPLE_MAX).  Sample s has, at a locus, k methylated and n total calls.  It COUNTS there
+ * when n >= c, the per-sample minimum coverage (option "sample_min_cov", default 5, range 1 .. 2^20 - 1), and its LEVEL there is
+ * the integer u = floor(k * 2^15 / n) in [0, 32768].  The context of a locus is min(key & 3, 2), as everywhere else.
+ * For a context, a pair i <= j and a set of loci, take the loci where both i and j count -- in COMPLETE mode the loci where all
+ * the samples opened so far count -- and over those loci
+ *   n = their number,  si = sum u_i,  sj = sum u_j,  sii = sum u_i^2,  sjj = sum u_j^2,  sij = sum u_i u_j
+ * All six are uint64 and exact: with u^2 <= 2^30 none overflows below 2^33 loci.  The diagonal i = j carries a sample's own locus
+ * count and moments.  With num = n sij - si sj, va = n sii - si^2 and vb = n sjj - sj^2 computed exactly in 128-bit integers and
+ * each converted to double once,
+ *   r = num / (sqrt(va) * sqrt(vb)),  NaN when n < 2, va = 0 or vb = 0;   mean level in percent = 100 si / (n 2^15), NaN when n = 0
+ * This is Pearson's r of the QUANTISED levels u, not of the ratios k / n: this library's own definition, not another tool's.  The
+ * sums are integers, so they depend on no order; floating point appears in hm_sample_corr only, on the host.
+ *
+ * Option "samples" (0 default, or N in 2 .. 64): must be set before hm_pileup_set_reference (else HM_ESTATE), which then also
+ * allocates and zeroes N uint16 level planes, 2 N bytes per reference base; a reference that does not fit fails as for the other
+ * planes.  Without the option nothing is allocated.  It needs neither "partitions" nor "groups".  Option "sample_min_cov" (c):
+ * HM_ESTATE once a sample has been opened.  A plane stores per locus 0 (nothing seen), u + 1 (the sample counts), or 0xFFFF (seen,
+ * below c).  The calls of this family are named hm_sample_*; those that take the engine take the hm_pileup_t they belong to. */
+#define HM_SAMPLE_MAX 64   /* samples of one engine */
+#define HM_SAMPLE_TILE 256 /* consecutive positions a workgroup of hm_sample_fetch_sums takes at a time; tiles start at multiples of it */
+int hm_sample_geometry(int64_t out[2]); /* out[0] = HM_SAMPLE_TILE, out[1] = HM_SAMPLE_MAX as the library was built */
+typedef struct {            /* the sums of one context and one pair i <= j; 64 bytes */
+    int32_t i, j;
+    uint32_t ctx, reserved;
+    uint64_t n, si, sj, sii, sjj, sij;
+} hm_sample_pair_t;
+/* Opens the next sample: the rows of hm_sample_load belong to it until the next call.  Returns its index 0 .. N - 1.
+ * HM_ESTATE without option "samples" or before hm_pileup_set_reference, on an engine voided by a bad row, on one that staged a
+ * record or used hm_pileup_load_loci / hm_pileup_group_sample, and for sample N + 1.  Once a sample is open, hm_pileup_load_loci,
+ * hm_pileup_group_sample and hm_pileup_submit_read* return HM_ESTATE. */
+int hm_sample_open(hm_pileup_t* p);
+/* rows[0, n) of the open sample: HOST memory, any order, any number of calls; they pass through the slab of hm_pileup_load_loci
+ * (option "load_slab").  Each row is checked as hm_pileup_load_sample_loci checks it, in this order, the first failure names it:
+ * gpos in [0, total reference length); pcov >= 0 and ncov >= 0; pcov + ncov < 2^20; motif <= 3.  A row that passes and has no
+ * count is ignored.  A row whose locus already holds a non-zero value of THIS sample is a duplicate and adds nothing -- counting
+ * or not, and of two rows of one locus in one call exactly one is the duplicate.  Every other row writes the sample's value at
+ * its locus and raises the key to its motif; if the sample counts there it also adds pcov / ncov to the engine's combined planes,
+ * so hm_pileup_fetch_loci sees the pooled counting samples.  The planes depend on neither row order, slab size nor launch
+ * geometry.  Returns the number of rows that wrote a value.  Any bad row (duplicates are one kind): HM_EDATA,
+ * hm_pileup_last_error gives the number of each kind, and the engine is void as after hm_pileup_load_loci.  HM_ESTATE before
+ * hm_sample_open; HM_EINVAL for n < 0 or rows NULL with n > 0. */
+int64_t hm_sample_load(hm_pileup_t* p, const hm_locus_t* rows, int64_t n);
+/* The sums over the loci of [lo, hi) for the M samples opened so far: 3 M (M + 1) / 2 entries into out (HOST memory), context-major,
+ * then i, then j >= i; returns their number.  complete: 0 pairwise, 1 complete mode.  hi == lo gives all-zero sums.  The sums over
+ * [lo, m) plus those over [m, hi) equal those over [lo, hi), entry for entry.  HM_EINVAL for lo < 0, lo > hi, hi past the
+ * reference, complete outside {0, 1} or out NULL; HM_ESTATE without option "samples", before hm_pileup_set_reference or on a
+ * voided engine. */
+int64_t hm_sample_fetch_sums(hm_pileup_t* p, int64_t lo, int64_t hi, int32_t complete, hm_sample_pair_t* out);
+/* The stored values of sample s (0 .. N - 1; an unopened one is all 0) over [lo, hi), copied to HOST memory: out[hi - lo].  For
+ * tests, as hm_pileup_group_planes.  Errors as hm_sample_fetch_sums; HM_EINVAL for a bad s. */
+int hm_sample_plane(hm_pileup_t* p, int32_t s, int64_t lo, int64_t hi, uint16_t* out);
+/* Host only.  r[k], mean_i[k], mean_j[k] of e[k] by the formula above, k in [0, n); each of the three may be NULL.  HM_EINVAL for
+ * n < 0 or e NULL with n > 0. */
+int hm_sample_corr(const hm_sample_pair_t* e, int64_t n, double* r, double* mean_i, double* mean_j);
 
 /* ---- per-locus binomial test (`pileup -B / -e`): is a locus methylated at all ------------------------
  * Against a false-positive rate e per context -- given, or measured on an unmethylated control sequence as sum(pcov) /
