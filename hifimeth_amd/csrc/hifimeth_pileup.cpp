@@ -1115,12 +1115,27 @@ bool parse_count(const char* a, const char* b, long long& v) {
     return true;
 }
 
-// One <prefix>.<ctx>.cov.bed, plain or gzip, into partition `part` -- or, with part 0, into the open sample of `groupdiff`
-// (hm_pileup_load_sample_loci), with part -1 into that of `samplecorr` (hm_sample_load) -- with motif `motif`: read in blocks of whole lines, each block
-// parsed by `threads` workers over contiguous runs of lines and handed to the engine run by run.  Empty lines are skipped.  false
+using clk = std::chrono::steady_clock;
+double secs(clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); }
+
+// What `diff`, `groupdiff` and `samplecorr` do before their first load.  The files are found before the reference is read and the
+// engine exists: a job without input needs neither.
+struct CovJob {
+    std::vector<std::string> files[3];  // per context the file of every sample, in the order of `samples`; empty: context skipped
+    int n_ctx = 0;
+    Fasta fa;
+    std::vector<int64_t> seq_start;
+    std::unique_ptr<hm_pileup_t, decltype(&hm_pileup_destroy)> engine{nullptr, hm_pileup_destroy};  // destroyed on every way out
+};
+
+// One <prefix>.<ctx>.cov.bed, plain or gzip, with motif `motif`: read in blocks of whole lines, each block parsed by `threads` workers
+// over contiguous runs of lines and handed run by run to `load`, the engine call of the command (hm_pileup_load_loci for a partition,
+// hm_pileup_load_sample_loci, hm_sample_load), which answers the rows it took or an error of the job's engine.  Empty lines are skipped.  false
 // with a message naming the file and, for a bad line, its number.
-bool load_cov_bed(hm_pileup_t* pe, const Fasta& fa, const std::vector<int64_t>& seq_start, const std::string& path, int part, uint32_t motif,
-                  int threads, uint64_t& n_rows) {
+using LoadCall = std::function<int64_t(const hm_locus_t*, int64_t)>;
+bool load_cov_bed(const CovJob& job, const std::string& path, const LoadCall& load, uint32_t motif, int threads, uint64_t& n_rows) {
+    const Fasta& fa = job.fa;
+    const std::vector<int64_t>& seq_start = job.seq_start;
     constexpr size_t BLOCK = size_t(32) << 20;
     gzFile in = gzopen(path.c_str(), "rb");
     if (!in) { fprintf(stderr, "ERROR: cannot open %s\n", path.c_str()); return false; }
@@ -1204,10 +1219,8 @@ bool load_cov_bed(hm_pileup_t* pe, const Fasta& fa, const std::vector<int64_t>& 
                 break;
             }
             lines_before += P.lines;
-            const int64_t rc = part > 0   ? hm_pileup_load_loci(pe, part, P.rows.data(), (int64_t)P.rows.size())
-                               : part < 0 ? hm_sample_load(pe, P.rows.data(), (int64_t)P.rows.size())
-                                          : hm_pileup_load_sample_loci(pe, P.rows.data(), (int64_t)P.rows.size());
-            if (rc < 0) { fprintf(stderr, "ERROR: %s: %s\n", path.c_str(), hm_pileup_last_error(pe)); ok = false; break; }
+            const int64_t rc = load(P.rows.data(), (int64_t)P.rows.size());
+            if (rc < 0) { fprintf(stderr, "ERROR: %s: %s\n", path.c_str(), hm_pileup_last_error(job.engine.get())); ok = false; break; }
             n_rows += (uint64_t)rc;
         }
         buf.erase(0, end);
@@ -1225,15 +1238,48 @@ std::string find_cov_bed(const std::string& prefix, const char* ctx) {
     return std::string();
 }
 
+// A context counts if every sample has its file ("a cov.bed file of <whose>").  The engine gets `options` -- a refusal is reported
+// as `what` -- and then the reference.  -> 0, or the exit status behind a message.
+int open_cov_job(const PileupOptions& o, const std::vector<std::string>& samples, const char* whose, const char* what,
+                 std::initializer_list<std::pair<const char*, double>> options, CovJob& job) {
+    static const char* cn[3] = {"CpG", "CHG", "CHH"};
+    for (int c = 0; c < 3; ++c) {
+        bool all = true;
+        for (const std::string& s : samples) {
+            job.files[c].push_back(find_cov_bed(s, cn[c]));
+            if (!job.files[c].back().empty()) continue;
+            fprintf(stderr, "Skip context %s: %s.%s.cov.bed is missing\n", cn[c], s.c_str(), cn[c]);
+            all = false;
+        }
+        if (all) ++job.n_ctx;
+        else job.files[c].clear();
+    }
+    if (!job.n_ctx) { fprintf(stderr, "ERROR: no context has a cov.bed file of %s\n", whose); return EXIT_FAILURE; }
+    Fasta& fa = job.fa;
+    std::string err;
+    if (!load_fasta(o.ref, fa, err)) { fprintf(stderr, "ERROR: %s\n", err.c_str()); return EXIT_FAILURE; }
+    if (fa.names.empty()) { fprintf(stderr, "ERROR: no sequence in %s\n", o.ref.c_str()); return EXIT_FAILURE; }
+    fprintf(stderr, "Load %zu sequences (%zu bases) from %s\n", fa.names.size(), fa.bases.size(), o.ref.c_str());
+    job.seq_start.assign(fa.names.size() + 1, 0);
+    for (size_t s = 0; s < fa.names.size(); ++s) job.seq_start[s + 1] = job.seq_start[s] + fa.length[s];
+
+    hm_pileup_t* pe = nullptr;
+    if (hm_pileup_create(&pe, o.device) != HM_OK) { fprintf(stderr, "ERROR: %s\n", hm_pileup_last_error(nullptr)); return EXIT_FAILURE; }
+    job.engine.reset(pe);
+    for (const auto& opt : options)
+        if (hm_pileup_set_option(pe, opt.first, opt.second) != HM_OK) return engine_error(pe, what);
+    if (hm_pileup_set_reference(pe, (int32_t)fa.names.size(), fa.length.data(), fa.bases.data()) != HM_OK) return engine_error(pe, "reference");
+    return 0;
+}
+
 }  // namespace
 
 int cmd_diff(int argc, char** argv) {
-    static const char* cn[3] = {"CpG", "CHG", "CHH"};
     PileupOptions o;
     int first = 0, status = 0;
     if (!parse_command_line(CMD_DIFF, argc, argv, o, first, status)) return status;
     o.ref = argv[first];
-    const std::string sample[2] = {argv[first + 1], argv[first + 2]};
+    const std::vector<std::string> sample = {argv[first + 1], argv[first + 2]};
     o.prefix = argv[first + 3];
     fprintf(stderr, "\n\n====================> Parameters:\nCPU threads: %d\nGenomic reference: %s\nsample 1: %s.<ctx>.cov.bed\nsample 2: %s.<ctx>.cov.bed\n"
                     "output prefix: %s\ndiff: min sample coverage %d -> %s.diff.*\n",
@@ -1244,44 +1290,23 @@ int cmd_diff(int argc, char** argv) {
                 o.region_max_gap, o.prefix.c_str());
     fprintf(stderr, "\n\n");
 
-    using clk = std::chrono::steady_clock;
     const auto t_start = clk::now();
-    std::string files[3][2];  // found before the reference is read and the engine exists: a job without input needs neither
-    int n_ctx = 0;
-    for (int c = 0; c < 3; ++c) {
-        for (int s = 0; s < 2; ++s) files[c][s] = find_cov_bed(sample[s], cn[c]);
-        if (!files[c][0].empty() && !files[c][1].empty()) { ++n_ctx; continue; }
-        for (int s = 0; s < 2; ++s)
-            if (files[c][s].empty()) fprintf(stderr, "Skip context %s: %s.%s.cov.bed is missing\n", cn[c], sample[s].c_str(), cn[c]);
-        files[c][0].clear();
-    }
-    if (!n_ctx) { fprintf(stderr, "ERROR: no context has a cov.bed file of both samples\n"); return EXIT_FAILURE; }
-    Fasta fa;
-    std::string err;
-    if (!load_fasta(o.ref, fa, err)) { fprintf(stderr, "ERROR: %s\n", err.c_str()); return EXIT_FAILURE; }
-    if (fa.names.empty()) { fprintf(stderr, "ERROR: no sequence in %s\n", o.ref.c_str()); return EXIT_FAILURE; }
-    fprintf(stderr, "Load %zu sequences (%zu bases) from %s\n", fa.names.size(), fa.bases.size(), o.ref.c_str());
-    std::vector<int64_t> seq_start(fa.names.size() + 1, 0);
-    for (size_t s = 0; s < fa.names.size(); ++s) seq_start[s + 1] = seq_start[s] + fa.length[s];
-
-    hm_pileup_t* pe = nullptr;
-    if (hm_pileup_create(&pe, o.device) != HM_OK) { fprintf(stderr, "ERROR: %s\n", hm_pileup_last_error(nullptr)); return EXIT_FAILURE; }
-    std::unique_ptr<hm_pileup_t, decltype(&hm_pileup_destroy)> engine(pe, hm_pileup_destroy);  // destroyed on every way out
-    auto die = [&](const std::string& what) { return engine_error(pe, what); };
-    if (hm_pileup_set_option(pe, "partitions", 2) != HM_OK) return die("partitions");
-    if (hm_pileup_set_reference(pe, (int32_t)fa.names.size(), fa.length.data(), fa.bases.data()) != HM_OK) return die("reference");
+    CovJob job;
+    if (const int failed = open_cov_job(o, sample, "both samples", "partitions", {{"partitions", 2}}, job)) return failed;
+    hm_pileup_t* pe = job.engine.get();
     uint64_t n_rows[2] = {0, 0};
     for (int c = 0; c < 3; ++c)
-        for (int s = 0; s < 2 && !files[c][0].empty(); ++s)
-            if (!load_cov_bed(pe, fa, seq_start, files[c][s], s + 1, (uint32_t)c, o.threads, n_rows[s])) return EXIT_FAILURE;
+        for (int s = 0; s < 2 && !job.files[c].empty(); ++s) {
+            const LoadCall load = [&](const hm_locus_t* rows, int64_t n) { return hm_pileup_load_loci(pe, s + 1, rows, n); };
+            if (!load_cov_bed(job, job.files[c][(size_t)s], load, (uint32_t)c, o.threads, n_rows[s])) return EXIT_FAILURE;
+        }
     const auto t_load = clk::now();
-    const int rc = write_partition_tests(pe, fa, o, "diff");
-    if (rc < 0) return die(rc == -1 ? "diff" : "diff regions");
+    const int rc = write_partition_tests(pe, job.fa, o, "diff");
+    if (rc < 0) return engine_error(pe, rc == -1 ? "diff" : "diff regions");
     if (rc == 0) return EXIT_FAILURE;
-    engine.reset();
-    const auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+    job.engine.reset();
     fprintf(stderr, "## %llu + %llu covered loci of %d contexts in %.2f s: parse + load %.2f s; test + BED %.2f s\n", (unsigned long long)n_rows[0],
-            (unsigned long long)n_rows[1], n_ctx, secs(t_start, clk::now()), secs(t_start, t_load), secs(t_load, clk::now()));
+            (unsigned long long)n_rows[1], job.n_ctx, secs(t_start, clk::now()), secs(t_start, t_load), secs(t_load, clk::now()));
     return 0;
 }
 
@@ -1322,7 +1347,6 @@ int cmd_groupdiff(int argc, char** argv) {
     fprintf(stderr, "output prefix: %s\ngroupdiff: min sample coverage %lld, min replicates per group %lld -> %s.groups.*\n\n\n", o.prefix.c_str(),
             o.group_min_cov, o.group_min_reps, o.prefix.c_str());
 
-    using clk = std::chrono::steady_clock;
     const auto t_start = clk::now();
     for (int g = 0; g < 2; ++g) {
         for (const std::string& s : group[g])
@@ -1333,44 +1357,24 @@ int cmd_groupdiff(int argc, char** argv) {
         }
         if (group[g].size() > 255) { fprintf(stderr, "ERROR: group %d has more than 255 samples\n", g + 1); return EXIT_FAILURE; }
     }
-    std::vector<std::string> files[3][2];  // found before the reference is read and the engine exists, as in `diff`
-    int n_ctx = 0;
-    for (int c = 0; c < 3; ++c) {
-        bool all = true;
-        for (int g = 0; g < 2; ++g)
-            for (const std::string& s : group[g]) {
-                files[c][g].push_back(find_cov_bed(s, cn[c]));
-                if (!files[c][g].back().empty()) continue;
-                fprintf(stderr, "Skip context %s: %s.%s.cov.bed is missing\n", cn[c], s.c_str(), cn[c]);
-                all = false;
-            }
-        if (all) ++n_ctx;
-        else files[c][0].clear();
-    }
-    if (!n_ctx) { fprintf(stderr, "ERROR: no context has a cov.bed file of every sample\n"); return EXIT_FAILURE; }
-    Fasta fa;
-    std::string err;
-    if (!load_fasta(o.ref, fa, err)) { fprintf(stderr, "ERROR: %s\n", err.c_str()); return EXIT_FAILURE; }
-    if (fa.names.empty()) { fprintf(stderr, "ERROR: no sequence in %s\n", o.ref.c_str()); return EXIT_FAILURE; }
-    fprintf(stderr, "Load %zu sequences (%zu bases) from %s\n", fa.names.size(), fa.bases.size(), o.ref.c_str());
-    std::vector<int64_t> seq_start(fa.names.size() + 1, 0);
-    for (size_t s = 0; s < fa.names.size(); ++s) seq_start[s + 1] = seq_start[s] + fa.length[s];
-
-    hm_pileup_t* pe = nullptr;
-    if (hm_pileup_create(&pe, o.device) != HM_OK) { fprintf(stderr, "ERROR: %s\n", hm_pileup_last_error(nullptr)); return EXIT_FAILURE; }
-    std::unique_ptr<hm_pileup_t, decltype(&hm_pileup_destroy)> engine(pe, hm_pileup_destroy);  // destroyed on every way out
+    std::vector<std::string> sample = group[0];  // the files of a context: group 1's samples, then group 2's
+    sample.insert(sample.end(), group[1].begin(), group[1].end());
+    CovJob job;
+    if (const int failed = open_cov_job(o, sample, "every sample", "groups",
+                                        {{"partitions", 2}, {"groups", 1}, {"group_min_cov", (double)o.group_min_cov}}, job))
+        return failed;
+    hm_pileup_t* pe = job.engine.get();
+    const Fasta& fa = job.fa;
+    const std::vector<int64_t>& seq_start = job.seq_start;
     auto die = [&](const std::string& what) { return engine_error(pe, what); };
-    if (hm_pileup_set_option(pe, "partitions", 2) != HM_OK || hm_pileup_set_option(pe, "groups", 1) != HM_OK ||
-        hm_pileup_set_option(pe, "group_min_cov", (double)o.group_min_cov) != HM_OK)
-        return die("groups");
-    if (hm_pileup_set_reference(pe, (int32_t)fa.names.size(), fa.length.data(), fa.bases.data()) != HM_OK) return die("reference");
+    const LoadCall load = [&](const hm_locus_t* rows, int64_t n) { return hm_pileup_load_sample_loci(pe, rows, n); };
     uint64_t n_rows[2] = {0, 0};
-    for (int g = 0; g < 2; ++g)
-        for (size_t i = 0; i < group[g].size(); ++i) {  // a sample's contexts share its seen bitmap: one locus, one context
-            if (hm_pileup_group_sample(pe, g + 1) < 0) return die("group sample");
-            for (int c = 0; c < 3; ++c)
-                if (!files[c][0].empty() && !load_cov_bed(pe, fa, seq_start, files[c][g][i], 0, (uint32_t)c, o.threads, n_rows[g])) return EXIT_FAILURE;
-        }
+    for (size_t i = 0; i < sample.size(); ++i) {  // a sample's contexts share its seen bitmap: one locus, one context
+        const int g = i < group[0].size() ? 0 : 1;
+        if (hm_pileup_group_sample(pe, g + 1) < 0) return die("group sample");
+        for (int c = 0; c < 3; ++c)
+            if (!job.files[c].empty() && !load_cov_bed(job, job.files[c][i], load, (uint32_t)c, o.threads, n_rows[g])) return EXIT_FAILURE;
+    }
     const auto t_load = clk::now();
 
     std::vector<hm_group_t> rows;
@@ -1381,7 +1385,7 @@ int cmd_groupdiff(int argc, char** argv) {
         rows.resize(rows.size() + (size_t)n);
         if (hm_pileup_fetch_groups(pe, seq_start[s], seq_start[s + 1], (int32_t)o.group_min_reps, rows.data() + rows.size() - n, n) != n) return die("groups");
     }
-    engine.reset();
+    job.engine.reset();
     std::vector<double> q(rows.size());
     uint64_t m[3];
     if (hm_group_qvalues(rows.data(), (int64_t)rows.size(), q.data(), m) != HM_OK) {
@@ -1421,9 +1425,8 @@ int cmd_groupdiff(int argc, char** argv) {
         fprintf(f, "%s\t%llu\t%llu\t%llu\t%llu\n", cn[c], (unsigned long long)m[c], (unsigned long long)tally[c][0], (unsigned long long)tally[c][1],
                 (unsigned long long)tally[c][2]);
     fclose(f);
-    const auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
     fprintf(stderr, "## %zu + %zu samples, %llu + %llu counting loci of %d contexts, %zu tested in %.2f s: parse + load %.2f s; test + BED %.2f s\n",
-            group[0].size(), group[1].size(), (unsigned long long)n_rows[0], (unsigned long long)n_rows[1], n_ctx, rows.size(), secs(t_start, clk::now()),
+            group[0].size(), group[1].size(), (unsigned long long)n_rows[0], (unsigned long long)n_rows[1], job.n_ctx, rows.size(), secs(t_start, clk::now()),
             secs(t_start, t_load), secs(t_load, clk::now()));
     return 0;
 }
@@ -1453,54 +1456,30 @@ int cmd_samplecorr(int argc, char** argv) {
     fprintf(stderr, "output prefix: %s\nsamplecorr: min sample coverage %lld, %s -> %s.samplecorr.*\n\n\n", o.prefix.c_str(), o.sample_min_cov,
             o.sample_complete ? "loci where all samples count" : "loci where both samples of a pair count", o.prefix.c_str());
 
-    using clk = std::chrono::steady_clock;
     const auto t_start = clk::now();
-    std::vector<std::string> files[3];  // found before the reference is read and the engine exists, as in `diff`
-    int n_ctx = 0;
-    for (int c = 0; c < 3; ++c) {
-        bool all = true;
-        for (const std::string& s : sample) {
-            files[c].push_back(find_cov_bed(s, cn[c]));
-            if (!files[c].back().empty()) continue;
-            fprintf(stderr, "Skip context %s: %s.%s.cov.bed is missing\n", cn[c], s.c_str(), cn[c]);
-            all = false;
-        }
-        if (all) ++n_ctx;
-        else files[c].clear();
-    }
-    if (!n_ctx) { fprintf(stderr, "ERROR: no context has a cov.bed file of every sample\n"); return EXIT_FAILURE; }
-    Fasta fa;
-    std::string err;
-    if (!load_fasta(o.ref, fa, err)) { fprintf(stderr, "ERROR: %s\n", err.c_str()); return EXIT_FAILURE; }
-    if (fa.names.empty()) { fprintf(stderr, "ERROR: no sequence in %s\n", o.ref.c_str()); return EXIT_FAILURE; }
-    fprintf(stderr, "Load %zu sequences (%zu bases) from %s\n", fa.names.size(), fa.bases.size(), o.ref.c_str());
-    std::vector<int64_t> seq_start(fa.names.size() + 1, 0);
-    for (size_t s = 0; s < fa.names.size(); ++s) seq_start[s + 1] = seq_start[s] + fa.length[s];
-
-    hm_pileup_t* pe = nullptr;
-    if (hm_pileup_create(&pe, o.device) != HM_OK) { fprintf(stderr, "ERROR: %s\n", hm_pileup_last_error(nullptr)); return EXIT_FAILURE; }
-    std::unique_ptr<hm_pileup_t, decltype(&hm_pileup_destroy)> engine(pe, hm_pileup_destroy);  // destroyed on every way out
+    CovJob job;
+    if (const int failed = open_cov_job(o, sample, "every sample", "samples", {{"samples", (double)N}, {"sample_min_cov", (double)o.sample_min_cov}}, job))
+        return failed;
+    hm_pileup_t* pe = job.engine.get();
     auto die = [&](const std::string& what) { return engine_error(pe, what); };
-    if (hm_pileup_set_option(pe, "samples", (double)N) != HM_OK || hm_pileup_set_option(pe, "sample_min_cov", (double)o.sample_min_cov) != HM_OK)
-        return die("samples");
-    if (hm_pileup_set_reference(pe, (int32_t)fa.names.size(), fa.length.data(), fa.bases.data()) != HM_OK) return die("reference");
+    const LoadCall load = [&](const hm_locus_t* rows, int64_t n) { return hm_sample_load(pe, rows, n); };
     uint64_t n_rows = 0;
     for (int i = 0; i < N; ++i) {  // a sample's contexts share its plane: one locus, one context
         if (hm_sample_open(pe) < 0) return die("sample");
         for (int c = 0; c < 3; ++c)
-            if (!files[c].empty() && !load_cov_bed(pe, fa, seq_start, files[c][(size_t)i], -1, (uint32_t)c, o.threads, n_rows)) return EXIT_FAILURE;
+            if (!job.files[c].empty() && !load_cov_bed(job, job.files[c][(size_t)i], load, (uint32_t)c, o.threads, n_rows)) return EXIT_FAILURE;
     }
     const auto t_load = clk::now();
 
     // the samples file always reports a sample's own counting loci: the diagonal of the pairwise sums
     const size_t pairs = (size_t)N * (size_t)(N + 1) / 2;
     std::vector<hm_sample_pair_t> own(3 * pairs), sums;
-    if (hm_sample_fetch_sums(pe, 0, seq_start.back(), 0, own.data()) != (int64_t)own.size()) return die("sample sums");
+    if (hm_sample_fetch_sums(pe, 0, job.seq_start.back(), 0, own.data()) != (int64_t)own.size()) return die("sample sums");
     if (o.sample_complete) {
         sums.resize(own.size());
-        if (hm_sample_fetch_sums(pe, 0, seq_start.back(), 1, sums.data()) != (int64_t)sums.size()) return die("sample sums");
+        if (hm_sample_fetch_sums(pe, 0, job.seq_start.back(), 1, sums.data()) != (int64_t)sums.size()) return die("sample sums");
     }
-    engine.reset();
+    job.engine.reset();
     const std::vector<hm_sample_pair_t>& e = o.sample_complete ? sums : own;
     std::vector<double> r(e.size()), mi(e.size()), mj(e.size()), own_mean(own.size());
     if (hm_sample_corr(e.data(), (int64_t)e.size(), r.data(), mi.data(), mj.data()) != HM_OK ||
@@ -1519,7 +1498,7 @@ int cmd_samplecorr(int argc, char** argv) {
     if (!fs) return EXIT_FAILURE;
     fprintf(fs, "ctx\tsample\tn\tmean\n");
     for (int c = 0; c < 3; ++c) {
-        if (files[c].empty()) continue;
+        if (job.files[c].empty()) continue;
         for (int i = 0; i < N; ++i)
             fprintf(fs, "%s\t%s\t%llu\t%.6g\n", cn[c], sample[(size_t)i].c_str(), (unsigned long long)own[at(c, i, i)].n, own_mean[at(c, i, i)]);
         FILE* f = open_out(o.prefix + ".samplecorr." + cn[c] + ".tsv");
@@ -1544,8 +1523,7 @@ int cmd_samplecorr(int argc, char** argv) {
         fclose(f);
     }
     fclose(fs);
-    const auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
-    fprintf(stderr, "## %d samples, %llu rows of %d contexts in %.2f s: parse + load %.2f s; sums + tables %.2f s\n", N, (unsigned long long)n_rows, n_ctx,
+    fprintf(stderr, "## %d samples, %llu rows of %d contexts in %.2f s: parse + load %.2f s; sums + tables %.2f s\n", N, (unsigned long long)n_rows, job.n_ctx,
             secs(t_start, clk::now()), secs(t_start, t_load), secs(t_load, clk::now()));
     return 0;
 }

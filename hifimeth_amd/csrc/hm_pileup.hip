@@ -19,8 +19,10 @@
 //   project_kernel  thread per column      : motif tests, plane lookup, wave-aggregated append of 12-byte records
 //   count_kernel<CountPlanes>    thread per record : atomic add into pcov / ncov, atomic max into the motif key
 //   count_kernel<CountHpPlanes>  the same + one more atomic add into the record's haplotype planes (partitions = 2 only)
-//   load_loci_kernel  thread per row       : (`diff`) the rows of a *.cov.bed file added into one partition's planes and the combined
-//                   ones, the key raised to the row's motif; bad rows (outside the reference, negative, a locus twice) counted
+//   load_rows_kernel<Sink>  thread per row : (`diff`, `groupdiff`, `samplecorr`) the rows of a *.cov.bed file checked and the bad ones
+//                   (outside the reference, negative, too big, a locus twice) counted by kind; the sink says where a good row goes:
+//                   LoadPlanes one partition's planes and the combined ones, GroupLoadPlanes also a group's moment and sample-count
+//                   planes, SampleLoadPlanes one sample's uint16 level plane
 //   The column kernels (identity, project, pattern, depth) and MemberSel see the staged batch as one BatchView; the tiled ones
 //   walk it with walk_columns, test a CpG member with cpg_columns / cpg_call and append with stage_record / flush_stage.
 //   pattern_kernel  thread per column      : (`pileup -E`) a CpG member that heads a window of k reference CpGs looks the other
@@ -449,130 +451,92 @@ __global__ __launch_bounds__(TPB) void count_kernel(const PRec* __restrict__ rec
     }
 }
 
-// ---- counts from elsewhere (`diff`, hm_pileup_load_loci): rows of a *.cov.bed file into the planes of one partition -------------
-// A thread per row, grid-stride.  A row is checked before anything is written -- gpos inside [0, total), both counts >= 0,
-// motif <= 3, in this order, the first failure names the row -- and a bad row adds nothing.  A row without a count is skipped.
-// Every other row adds to its partition's planes and to the combined ones and raises the key to its motif (`order` bits stay 0);
-// the old values of the partition's two adds say whether the locus held a count of this partition already: a duplicate, which
-// still adds.  c[LOAD_ADDED] counts the rows that added, c[LOAD_BAD_*] the bad ones by kind: summed per wavefront, one global
-// atomic per wavefront and non-zero counter.  Integer adds only: the planes do not depend on row order or launch geometry.
-enum LoadCounter { LOAD_ADDED = 0, LOAD_BAD_GPOS, LOAD_BAD_COUNT, LOAD_BAD_MOTIF, LOAD_BAD_DUP, LOAD_COUNTERS };
+// ---- counts from elsewhere (`diff`, `groupdiff`, `samplecorr`): rows of a *.cov.bed file into the engine's planes ----------------
+// load_rows_kernel<Sink>: a thread per row, grid-stride.  A row is checked before anything is written -- gpos inside [0, total),
+// both counts >= 0, for a LIMITED sink pcov + ncov < 2^20, motif <= 3, in this order, the first failure names the row -- and a bad
+// row adds nothing.  A row without a count is skipped.  Every other row goes to the sink's take(), which says where a row of its
+// loader goes and answers ROW_ADDED, ROW_DUP, both or nothing.  c[LOAD_ADDED] counts the rows that added, c[LOAD_BAD_*] the bad ones
+// by kind: summed per wavefront, one global atomic per wavefront and non-zero counter.  Every sink writes by integer atomics only:
+// the planes do not depend on row order or launch geometry.
+enum LoadCounter { LOAD_ADDED = 0, LOAD_BAD_GPOS, LOAD_BAD_COUNT, LOAD_BAD_BIG, LOAD_BAD_MOTIF, LOAD_BAD_DUP, LOAD_COUNTERS };
+constexpr uint32_t ROW_ADDED = 1u << LOAD_ADDED, ROW_DUP = 1u << LOAD_BAD_DUP;
 constexpr int64_t LOAD_SLAB_ROWS = int64_t(1) << 20, LOAD_SLAB_MAX = int64_t(1) << 24;  // 24 MB of rows on the device by default
-
-struct LoadPlanes : CountPlanes {  // the combined planes + those of the partition the rows go to
-    int32_t *part_pcov, *part_ncov;
-};
-
-__global__ __launch_bounds__(TPB) void load_loci_kernel(const hm_locus_t* __restrict__ rows, int64_t n, int64_t total, LoadPlanes pl,
-                                                         unsigned long long* __restrict__ c) {
-    uint32_t mine[LOAD_COUNTERS] = {0u, 0u, 0u, 0u, 0u};
-    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
-        const hm_locus_t r = rows[i];
-        if (r.gpos < 0 || r.gpos >= total) { ++mine[LOAD_BAD_GPOS]; continue; }
-        if (r.pcov < 0 || r.ncov < 0) { ++mine[LOAD_BAD_COUNT]; continue; }
-        if (r.motif > 3u) { ++mine[LOAD_BAD_MOTIF]; continue; }
-        if (r.pcov == 0 && r.ncov == 0) continue;
-        const int64_t g = r.gpos;
-        const int32_t old_p = atomicAdd(&pl.part_pcov[g], r.pcov);
-        const int32_t old_n = atomicAdd(&pl.part_ncov[g], r.ncov);
-        if (r.pcov) atomicAdd(&pl.pcov[g], r.pcov);
-        if (r.ncov) atomicAdd(&pl.ncov[g], r.ncov);
-        atomicMax(&pl.key[g], r.motif);
-        ++mine[LOAD_ADDED];
-        if (old_p != 0 || old_n != 0) ++mine[LOAD_BAD_DUP];
-    }
-    for (int k = 0; k < LOAD_COUNTERS; ++k) {
-        uint32_t v = mine[k];
-        for (int d = 32; d; d >>= 1) v += __shfl_down(v, d);
-        if ((threadIdx.x & 63) == 0 && v) atomicAdd(&c[k], (unsigned long long)v);
-    }
-}
-
-// ---- replicate groups (`groupdiff`, hm_pileup_load_sample_loci): the rows of ONE sample of a group ---------------------------------
-// As load_loci_kernel, with one more check (a sample's count stays below 2^20, so q = floor(k^2 2^20 / n) needs no more than 60
-// bits) and three more planes.  The sample's seen bitmap -- cleared when the sample is opened -- takes the locus' bit first: the
-// old bit says whether this sample gave the locus before, a duplicate, which adds nothing.  A row below the sample minimum
-// coverage keeps its bit and adds nothing.  Every other row adds its counts as load_loci_kernel does, q to the group's moment
-// plane and 1 to the locus' byte of the group's sample-count plane: an add to the aligned word that holds the byte, which never
-// carries since a group has at most 255 samples.
-enum GroupLoadCounter { GLOAD_ADDED = 0, GLOAD_BAD_GPOS, GLOAD_BAD_COUNT, GLOAD_BAD_BIG, GLOAD_BAD_MOTIF, GLOAD_BAD_DUP, GLOAD_COUNTERS };
 constexpr int32_t GROUP_COUNT_LIMIT = 1 << 20;  // a sample's pcov + ncov at a locus stays below this
 constexpr int GROUP_MAX_SAMPLES = 255;          // per group: the sample counts are bytes
+constexpr int SAMPLE_MAX = HM_SAMPLE_MAX, SAMPLE_TILE = HM_SAMPLE_TILE;
+constexpr uint32_t SAMPLE_BELOW = 0xFFFFu;
 
+// `diff` (hm_pileup_load_loci): the combined planes + those of the partition the rows go to.  A row adds to its partition's planes
+// and to the combined ones and raises the key to its motif (`order` bits stay 0); the old values of the partition's two adds say
+// whether the locus held a count of this partition already: a duplicate, which still adds.
+struct LoadPlanes : CountPlanes {
+    static constexpr bool LIMITED = false;
+    int32_t *part_pcov, *part_ncov;
+
+    __device__ uint32_t take(const hm_locus_t& r) const {
+        const int64_t g = r.gpos;
+        const int32_t old_p = atomicAdd(&part_pcov[g], r.pcov);
+        const int32_t old_n = atomicAdd(&part_ncov[g], r.ncov);
+        if (r.pcov) atomicAdd(&pcov[g], r.pcov);
+        if (r.ncov) atomicAdd(&ncov[g], r.ncov);
+        atomicMax(&key[g], r.motif);
+        return old_p != 0 || old_n != 0 ? ROW_ADDED | ROW_DUP : ROW_ADDED;
+    }
+};
+
+// `groupdiff` (hm_pileup_load_sample_loci): the rows of ONE sample of a group.  LIMITED: a sample's count stays below 2^20, so
+// q = floor(k^2 2^20 / n) needs no more than 60 bits.  The sample's seen bitmap -- cleared when the sample is opened -- takes the
+// locus' bit first: the old bit says whether this sample gave the locus before, a duplicate, which adds nothing.  A row below the
+// sample minimum coverage keeps its bit and adds nothing.  Every other row adds its counts as LoadPlanes does, q to the group's
+// moment plane and 1 to the locus' byte of the group's sample-count plane: an add to the aligned word that holds the byte, which
+// never carries since a group has at most 255 samples.
 struct GroupLoadPlanes : LoadPlanes {
+    static constexpr bool LIMITED = true;
     unsigned long long* moment;  // Q_g
     uint32_t* samples;           // m_g, four loci per word
     uint32_t* seen;              // 32 loci per word
     int32_t min_cov;
-};
 
-__global__ __launch_bounds__(TPB) void load_sample_kernel(const hm_locus_t* __restrict__ rows, int64_t n, int64_t total, GroupLoadPlanes pl,
-                                                           unsigned long long* __restrict__ c) {
-    uint32_t mine[GLOAD_COUNTERS] = {0u, 0u, 0u, 0u, 0u, 0u};
-    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
-        const hm_locus_t r = rows[i];
-        if (r.gpos < 0 || r.gpos >= total) { ++mine[GLOAD_BAD_GPOS]; continue; }
-        if (r.pcov < 0 || r.ncov < 0) { ++mine[GLOAD_BAD_COUNT]; continue; }
-        if ((int64_t)r.pcov + r.ncov >= GROUP_COUNT_LIMIT) { ++mine[GLOAD_BAD_BIG]; continue; }
-        if (r.motif > 3u) { ++mine[GLOAD_BAD_MOTIF]; continue; }
-        if (r.pcov == 0 && r.ncov == 0) continue;
+    __device__ uint32_t take(const hm_locus_t& r) const {
         const int64_t g = r.gpos;
         const uint32_t bit = 1u << (g & 31);
-        if (atomicOr(&pl.seen[g >> 5], bit) & bit) { ++mine[GLOAD_BAD_DUP]; continue; }
+        if (atomicOr(&seen[g >> 5], bit) & bit) return ROW_DUP;
         const int32_t cov = r.pcov + r.ncov;
-        if (cov < pl.min_cov) continue;
+        if (cov < min_cov) return 0u;
         if (r.pcov) {
-            atomicAdd(&pl.part_pcov[g], r.pcov);
-            atomicAdd(&pl.pcov[g], r.pcov);
-            atomicAdd(&pl.moment[g], ((unsigned long long)r.pcov * (unsigned long long)r.pcov << 20) / (unsigned long long)cov);
+            atomicAdd(&part_pcov[g], r.pcov);
+            atomicAdd(&pcov[g], r.pcov);
+            atomicAdd(&moment[g], ((unsigned long long)r.pcov * (unsigned long long)r.pcov << 20) / (unsigned long long)cov);
         }
         if (r.ncov) {
-            atomicAdd(&pl.part_ncov[g], r.ncov);
-            atomicAdd(&pl.ncov[g], r.ncov);
+            atomicAdd(&part_ncov[g], r.ncov);
+            atomicAdd(&ncov[g], r.ncov);
         }
-        atomicMax(&pl.key[g], r.motif);
-        atomicAdd(&pl.samples[g >> 2], 1u << (8 * (g & 3)));
-        ++mine[GLOAD_ADDED];
+        atomicMax(&key[g], r.motif);
+        atomicAdd(&samples[g >> 2], 1u << (8 * (g & 3)));
+        return ROW_ADDED;
     }
-    for (int k = 0; k < GLOAD_COUNTERS; ++k) {
-        uint32_t v = mine[k];
-        for (int d = 32; d; d >>= 1) v += __shfl_down(v, d);
-        if ((threadIdx.x & 63) == 0 && v) atomicAdd(&c[k], (unsigned long long)v);
-    }
-}
-
-// ---- N samples (`samplecorr`, hm_sample_load): the rows of ONE sample into its uint16 level plane ---------------------------
-// The checks of load_sample_kernel in the same order.  The stored value of a locus is 0 (nothing seen), u + 1 with the level
-// u = floor(k 2^15 / n) in [0, 32768] (the sample counts there), or SAMPLE_BELOW (seen, below the minimum coverage).  There are no
-// 16-bit atomics: the value goes in by a compare-and-swap on the aligned 32-bit word that holds the locus and its neighbour, retried
-// while only the neighbour's half changed.  A half that is not 0 -- before the first try or after a lost one -- is a duplicate, which
-// adds nothing: of two rows of one locus exactly one wins, in one slab or in two.  The winner raises the key and, if the sample counts,
-// adds its counts to the combined planes.  Which of two duplicate rows wins depends on the launch, but a duplicate voids the engine.
-enum SampleLoadCounter { SLOAD_WROTE = 0, SLOAD_BAD_GPOS, SLOAD_BAD_COUNT, SLOAD_BAD_BIG, SLOAD_BAD_MOTIF, SLOAD_BAD_DUP, SLOAD_COUNTERS };
-constexpr int SAMPLE_MAX = HM_SAMPLE_MAX, SAMPLE_TILE = HM_SAMPLE_TILE;
-constexpr uint32_t SAMPLE_BELOW = 0xFFFFu;
-
-struct SampleLoadPlanes : CountPlanes {
-    uint32_t* level;  // the open sample's plane, two loci per word
-    int32_t min_cov;
 };
 
-__global__ __launch_bounds__(TPB) void sample_load_kernel(const hm_locus_t* __restrict__ rows, int64_t n, int64_t total, SampleLoadPlanes pl,
-                                                           unsigned long long* __restrict__ c) {
-    uint32_t mine[SLOAD_COUNTERS] = {0u, 0u, 0u, 0u, 0u, 0u};
-    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
-        const hm_locus_t r = rows[i];
-        if (r.gpos < 0 || r.gpos >= total) { ++mine[SLOAD_BAD_GPOS]; continue; }
-        if (r.pcov < 0 || r.ncov < 0) { ++mine[SLOAD_BAD_COUNT]; continue; }
-        if ((int64_t)r.pcov + r.ncov >= GROUP_COUNT_LIMIT) { ++mine[SLOAD_BAD_BIG]; continue; }
-        if (r.motif > 3u) { ++mine[SLOAD_BAD_MOTIF]; continue; }
-        if (r.pcov == 0 && r.ncov == 0) continue;
+// `samplecorr` (hm_sample_load): the rows of ONE sample into its uint16 level plane, LIMITED as a group's.  The stored value of a
+// locus is 0 (nothing seen), u + 1 with the level u = floor(k 2^15 / n) in [0, 32768] (the sample counts there), or SAMPLE_BELOW
+// (seen, below the minimum coverage).  There are no 16-bit atomics: the value goes in by a compare-and-swap on the aligned 32-bit
+// word that holds the locus and its neighbour, retried while only the neighbour's half changed.  A half that is not 0 -- before the
+// first try or after a lost one -- is a duplicate, which adds nothing: of two rows of one locus exactly one wins, in one slab or in
+// two.  The winner raises the key and, if the sample counts, adds its counts to the combined planes.  Which of two duplicate rows
+// wins depends on the launch, but a duplicate voids the engine.
+struct SampleLoadPlanes : CountPlanes {
+    static constexpr bool LIMITED = true;
+    uint32_t* level;  // the open sample's plane, two loci per word
+    int32_t min_cov;
+
+    __device__ uint32_t take(const hm_locus_t& r) const {
         const int64_t g = r.gpos;
         const int32_t cov = r.pcov + r.ncov;
-        const bool counts = cov >= pl.min_cov;
+        const bool counts = cov >= min_cov;
         const uint32_t value = counts ? (uint32_t)(((unsigned long long)r.pcov << 15) / (unsigned long long)cov) + 1u : SAMPLE_BELOW;
         const int shift = 16 * (int)(g & 1);
-        uint32_t* word = &pl.level[g >> 1];
+        uint32_t* word = &level[g >> 1];
         uint32_t old = *word;
         bool wrote = false;
         while (((old >> shift) & 0xFFFFu) == 0u) {
@@ -580,15 +544,33 @@ __global__ __launch_bounds__(TPB) void sample_load_kernel(const hm_locus_t* __re
             if (prev == old) { wrote = true; break; }
             old = prev;
         }
-        if (!wrote) { ++mine[SLOAD_BAD_DUP]; continue; }
-        atomicMax(&pl.key[g], r.motif);
+        if (!wrote) return ROW_DUP;
+        atomicMax(&key[g], r.motif);
         if (counts) {
-            if (r.pcov) atomicAdd(&pl.pcov[g], r.pcov);
-            if (r.ncov) atomicAdd(&pl.ncov[g], r.ncov);
+            if (r.pcov) atomicAdd(&pcov[g], r.pcov);
+            if (r.ncov) atomicAdd(&ncov[g], r.ncov);
         }
-        ++mine[SLOAD_WROTE];
+        return ROW_ADDED;
     }
-    for (int k = 0; k < SLOAD_COUNTERS; ++k) {
+};
+
+template <class Sink>
+__global__ __launch_bounds__(TPB) void load_rows_kernel(const hm_locus_t* __restrict__ rows, int64_t n, int64_t total, Sink sink,
+                                                         unsigned long long* __restrict__ c) {
+    uint32_t mine[LOAD_COUNTERS] = {0u, 0u, 0u, 0u, 0u, 0u};
+    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
+        const hm_locus_t r = rows[i];
+        if (r.gpos < 0 || r.gpos >= total) { ++mine[LOAD_BAD_GPOS]; continue; }
+        if (r.pcov < 0 || r.ncov < 0) { ++mine[LOAD_BAD_COUNT]; continue; }
+        if constexpr (Sink::LIMITED)
+            if ((int64_t)r.pcov + r.ncov >= GROUP_COUNT_LIMIT) { ++mine[LOAD_BAD_BIG]; continue; }
+        if (r.motif > 3u) { ++mine[LOAD_BAD_MOTIF]; continue; }
+        if (r.pcov == 0 && r.ncov == 0) continue;
+        const uint32_t did = sink.take(r);
+        if (did & ROW_ADDED) ++mine[LOAD_ADDED];
+        if (did & ROW_DUP) ++mine[LOAD_BAD_DUP];
+    }
+    for (int k = 0; k < LOAD_COUNTERS; ++k) {
         uint32_t v = mine[k];
         for (int d = 32; d; d >>= 1) v += __shfl_down(v, d);
         if ((threadIdx.x & 63) == 0 && v) atomicAdd(&c[k], (unsigned long long)v);
@@ -2402,8 +2384,8 @@ struct hm_pileup {
     // the sequence starts, and the device's CU count (0: not asked yet)
     DevBuf d_cxtab{EXACT}, d_cxoff{EXACT};
     int n_cus = 0;
-    // `diff` (hm_pileup_load_loci), allocated by the first load: one slab of LOAD_SLAB_ROWS rows, whatever a call brings, and the
-    // kernel's LOAD_COUNTERS counters.  The three flags are the engine's side of the rule "counts come from records or from
+    // the loads of `diff`, `groupdiff` and `samplecorr` (load_rows), allocated by the first load: one slab of load_slab rows, whatever
+    // a call brings, and the kernel's LOAD_COUNTERS counters.  The three flags are the engine's side of the rule "counts come from records or from
     // loads, never both": a record was ever staged; a load has gone through; a load met a bad row (the planes mean nothing now)
     DevBuf d_load{EXACT}, d_loadcnt{EXACT};
     bool staged_any = false, loaded = false, load_failed = false;
@@ -2839,6 +2821,73 @@ void commit_read(hm_pileup* p, const PRead& r, const uint8_t* seq4) {
     p->plane_len += r.l_qseq;
     p->reads.push_back(r);
     p->staged_any = true;
+}
+
+// ---- `diff`, `groupdiff`, `samplecorr`: what their calls share ----------------------------------------------------------------------
+// The rows of one load through load_rows_kernel<Sink>, slab by slab: the copy of a slab follows the kernel over the one before it
+// in the stream.  -> the number of rows that added, or HM_EDATA with the bad rows by kind behind `who` (a duplicate in the words
+// of dup_text) on an engine that is void from then on.
+template <class Sink>
+int64_t load_rows(hm_pileup* p, const char* who, const hm_locus_t* rows, int64_t n, const Sink& sink, const char* dup_text) {
+    if (n == 0) return 0;
+    const int64_t slab = p->load_slab;
+    unsigned long long c[LOAD_COUNTERS] = {0, 0, 0, 0, 0, 0};
+    const int rc = guarded(p, [&] {
+        p->d_load.reserve(sizeof(hm_locus_t) * (size_t)slab);
+        p->d_loadcnt.reserve(sizeof c);
+        HIP_TRY(hipMemsetAsync(p->d_loadcnt.p, 0, sizeof c, p->stream));
+        for (int64_t at = 0; at < n; at += slab) {
+            const int64_t m = std::min(slab, n - at);
+            HIP_TRY(hipMemcpyAsync(p->d_load.p, rows + at, sizeof(hm_locus_t) * (size_t)m, hipMemcpyHostToDevice, p->stream));
+            hipLaunchKernelGGL(load_rows_kernel<Sink>, dim3(grid_for(m, 4096)), dim3(TPB), 0, p->stream, p->d_load.as<hm_locus_t>(), m,
+                               p->seq_off.back(), sink, p->d_loadcnt.as<unsigned long long>());
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipMemcpyAsync(c, p->d_loadcnt.p, sizeof c, hipMemcpyDeviceToHost, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        return HM_OK;
+    });
+    if (rc < 0) return rc;
+    unsigned long long bad = 0;
+    for (int k = LOAD_BAD_GPOS; k < LOAD_COUNTERS; ++k) bad += c[k];
+    if (!bad) return (int64_t)c[LOAD_ADDED];
+    p->load_failed = true;
+    const char* const kind[LOAD_COUNTERS] = {"", "gpos outside the reference", "negative count", "count above 2^20 - 1", "motif above 3", dup_text};
+    std::string msg = std::string(who) + ": " + std::to_string(bad) + " bad rows";
+    const char* sep = ": ";
+    for (int k = LOAD_BAD_GPOS; k < LOAD_COUNTERS; ++k) {
+        if (!c[k]) continue;
+        msg += sep + std::to_string(c[k]) + " " + kind[k];
+        sep = ", ";
+    }
+    return pfail(p, HM_EDATA, msg);
+}
+
+// What the group and the sample calls share: the option on with the reference set (which allocates what the option keeps
+// resident), an engine that is not void, the planes the rows go to; each with the words that follow the caller's name.
+struct OptionNeeds {
+    bool resident, planes;
+    const char *needs, *without;
+};
+OptionNeeds group_needs(const hm_pileup* p) {
+    return {p->groups && p->d_gseen.p, p->pcov && p->hp_pcov[0] && p->hp_pcov[1], " needs option groups = 1 and hm_pileup_set_reference",
+            " without partition planes"};
+}
+OptionNeeds sample_needs(const hm_pileup* p) {
+    return {p->samples && p->d_slevel.p, p->pcov && p->ncov && p->key, " needs option samples = N and hm_pileup_set_reference", " without planes"};
+}
+int option_ready(hm_pileup* p, const char* who, const OptionNeeds& o) {
+    const std::string w = who;
+    if (!o.resident || p->seq_off.empty()) return pfail(p, HM_ESTATE, w + o.needs);
+    if (p->load_failed) return pfail(p, HM_ESTATE, w + ": " + LOAD_FAILED_TEXT);
+    if (!o.planes) return pfail(p, HM_ESTATE, w + o.without);
+    return HM_OK;
+}
+int option_range(hm_pileup* p, const char* who, const OptionNeeds& o, int64_t lo, int64_t hi) {
+    const int rc = option_ready(p, who, o);
+    if (rc != HM_OK) return rc;
+    if (lo < 0 || hi < lo || hi > p->seq_off.back()) return pfail(p, HM_EINVAL, std::string(who) + ": bad range");
+    return HM_OK;
 }
 
 }  // namespace
@@ -3306,55 +3355,14 @@ int64_t hm_pileup_load_loci(hm_pileup_t* p, int32_t part, const hm_locus_t* rows
     if (p->staged_any) return pfail(p, HM_ESTATE, "hm_pileup_load_loci on an engine that has staged records: counts come from records or from loads, not both");
     if (p->group_open || p->samples_open)
         return pfail(p, HM_ESTATE, "hm_pileup_load_loci on an engine that opened a sample (hm_pileup_group_sample, hm_sample_open)");
-    if (n == 0) return 0;
-    const int64_t slab = p->load_slab;
-    unsigned long long c[LOAD_COUNTERS] = {0, 0, 0, 0, 0};
-    const int rc = guarded(p, [&] {
-        p->d_load.reserve(sizeof(hm_locus_t) * (size_t)slab);
-        p->d_loadcnt.reserve(sizeof c);
-        HIP_TRY(hipMemsetAsync(p->d_loadcnt.p, 0, sizeof c, p->stream));
-        const LoadPlanes pl{{p->pcov, p->ncov, p->key}, p->hp_pcov[part - 1], p->hp_ncov[part - 1]};
-        for (int64_t at = 0; at < n; at += slab) {  // the copy of a slab follows the kernel over the one before it in the stream
-            const int64_t m = std::min(slab, n - at);
-            HIP_TRY(hipMemcpyAsync(p->d_load.p, rows + at, sizeof(hm_locus_t) * (size_t)m, hipMemcpyHostToDevice, p->stream));
-            hipLaunchKernelGGL(load_loci_kernel, dim3(grid_for(m, 4096)), dim3(TPB), 0, p->stream, p->d_load.as<hm_locus_t>(), m,
-                               p->seq_off.back(), pl, p->d_loadcnt.as<unsigned long long>());
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipMemcpyAsync(c, p->d_loadcnt.p, sizeof c, hipMemcpyDeviceToHost, p->stream));
-        HIP_TRY(hipStreamSynchronize(p->stream));
-        return HM_OK;
-    });
-    if (rc < 0) return rc;
-    const unsigned long long bad = c[LOAD_BAD_GPOS] + c[LOAD_BAD_COUNT] + c[LOAD_BAD_MOTIF] + c[LOAD_BAD_DUP];
-    if (bad) {
-        p->load_failed = true;
-        static const char* kind[LOAD_COUNTERS] = {"", "gpos outside the reference", "negative count", "motif above 3",
-                                                  "locus given twice for one part"};
-        std::string msg = "hm_pileup_load_loci: " + std::to_string(bad) + " bad rows";
-        const char* sep = ": ";
-        for (int k = LOAD_BAD_GPOS; k < LOAD_COUNTERS; ++k) {
-            if (!c[k]) continue;
-            msg += sep + std::to_string(c[k]) + " " + kind[k];
-            sep = ", ";
-        }
-        return pfail(p, HM_EDATA, msg);
-    }
-    p->loaded = true;
-    return (int64_t)c[LOAD_ADDED];
+    const LoadPlanes sink{{p->pcov, p->ncov, p->key}, p->hp_pcov[part - 1], p->hp_ncov[part - 1]};
+    const int64_t added = load_rows(p, "hm_pileup_load_loci", rows, n, sink, "locus given twice for one part");
+    if (n && added >= 0) p->loaded = true;
+    return added;
 }
 
 // ---- `groupdiff` ------------------------------------------------------------------------------------------------------------------
 namespace {
-// what the group calls share: the option, the reference, an engine that is not void
-int group_ready(hm_pileup* p, const char* who) {
-    const std::string w = who;
-    if (!p->groups || p->seq_off.empty() || !p->d_gseen.p) return pfail(p, HM_ESTATE, w + " needs option groups = 1 and hm_pileup_set_reference");
-    if (p->load_failed) return pfail(p, HM_ESTATE, w + ": " + LOAD_FAILED_TEXT);
-    if (!p->pcov || !p->hp_pcov[0] || !p->hp_pcov[1]) return pfail(p, HM_ESTATE, w + " without partition planes");
-    return HM_OK;
-}
-
 // 1 / (a B(a, 1/2)) = Gamma((nu + 1) / 2) / (sqrt(pi) Gamma(nu / 2 + 1)) for nu = 0 .. 2 GROUP_MAX_SAMPLES - 2, by the recurrence
 // c(nu + 2) = c(nu) (nu + 1) / (nu + 2) from c(1) = 2 / pi, c(2) = 1 / 2 in long double, rounded once: uploaded once per engine
 void ensure_group_coef(hm_pileup* p) {
@@ -3375,7 +3383,7 @@ void ensure_group_coef(hm_pileup* p) {
 int hm_pileup_group_sample(hm_pileup_t* p, int32_t part) {
     if (!p) return HM_EINVAL;
     if (part != 1 && part != 2) return pfail(p, HM_EINVAL, "hm_pileup_group_sample: part must be 1 or 2");
-    const int rc = group_ready(p, "hm_pileup_group_sample");
+    const int rc = option_ready(p, "hm_pileup_group_sample", group_needs(p));
     if (rc != HM_OK) return rc;
     if (p->staged_any || p->loaded || p->samples_open)
         return pfail(p, HM_ESTATE, "hm_pileup_group_sample on an engine that staged records or used hm_pileup_load_loci / hm_sample_open: counts come from one source");
@@ -3392,56 +3400,16 @@ int hm_pileup_group_sample(hm_pileup_t* p, int32_t part) {
 int64_t hm_pileup_load_sample_loci(hm_pileup_t* p, const hm_locus_t* rows, int64_t n) {
     if (!p) return HM_EINVAL;
     if (n < 0 || (n && !rows)) return pfail(p, HM_EINVAL, "hm_pileup_load_sample_loci: n >= 0, rows not NULL");
-    const int ready = group_ready(p, "hm_pileup_load_sample_loci");
+    const int ready = option_ready(p, "hm_pileup_load_sample_loci", group_needs(p));
     if (ready != HM_OK) return ready;
     if (!p->group_open) return pfail(p, HM_ESTATE, "hm_pileup_load_sample_loci before hm_pileup_group_sample");
-    if (n == 0) return 0;
-    const int64_t slab = p->load_slab;
     const int g = p->group_open - 1;
-    unsigned long long c[GLOAD_COUNTERS] = {0, 0, 0, 0, 0, 0};
-    const int rc = guarded(p, [&] {
-        p->d_load.reserve(sizeof(hm_locus_t) * (size_t)slab);
-        p->d_loadcnt.reserve(sizeof c);
-        HIP_TRY(hipMemsetAsync(p->d_loadcnt.p, 0, sizeof c, p->stream));
-        const GroupLoadPlanes pl{{{p->pcov, p->ncov, p->key}, p->hp_pcov[g], p->hp_ncov[g]}, p->d_gmoment[g].as<unsigned long long>(),
-                                 p->d_gsamples[g].as<uint32_t>(), p->d_gseen.as<uint32_t>(), p->group_min_cov};
-        for (int64_t at = 0; at < n; at += slab) {  // as hm_pileup_load_loci: a slab's copy follows the kernel over the one before
-            const int64_t m = std::min(slab, n - at);
-            HIP_TRY(hipMemcpyAsync(p->d_load.p, rows + at, sizeof(hm_locus_t) * (size_t)m, hipMemcpyHostToDevice, p->stream));
-            hipLaunchKernelGGL(load_sample_kernel, dim3(grid_for(m, 4096)), dim3(TPB), 0, p->stream, p->d_load.as<hm_locus_t>(), m,
-                               p->seq_off.back(), pl, p->d_loadcnt.as<unsigned long long>());
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipMemcpyAsync(c, p->d_loadcnt.p, sizeof c, hipMemcpyDeviceToHost, p->stream));
-        HIP_TRY(hipStreamSynchronize(p->stream));
-        return HM_OK;
-    });
-    if (rc < 0) return rc;
-    unsigned long long bad = 0;
-    for (int k = GLOAD_BAD_GPOS; k < GLOAD_COUNTERS; ++k) bad += c[k];
-    if (bad) {
-        p->load_failed = true;
-        static const char* kind[GLOAD_COUNTERS] = {"", "gpos outside the reference", "negative count", "count above 2^20 - 1", "motif above 3",
-                                                   "locus given twice in one sample"};
-        std::string msg = "hm_pileup_load_sample_loci: " + std::to_string(bad) + " bad rows";
-        const char* sep = ": ";
-        for (int k = GLOAD_BAD_GPOS; k < GLOAD_COUNTERS; ++k) {
-            if (!c[k]) continue;
-            msg += sep + std::to_string(c[k]) + " " + kind[k];
-            sep = ", ";
-        }
-        return pfail(p, HM_EDATA, msg);
-    }
-    return (int64_t)c[GLOAD_ADDED];
+    const GroupLoadPlanes sink{{{p->pcov, p->ncov, p->key}, p->hp_pcov[g], p->hp_ncov[g]}, p->d_gmoment[g].as<unsigned long long>(),
+                               p->d_gsamples[g].as<uint32_t>(), p->d_gseen.as<uint32_t>(), p->group_min_cov};
+    return load_rows(p, "hm_pileup_load_sample_loci", rows, n, sink, "locus given twice in one sample");
 }
 
 namespace {
-int group_range(hm_pileup* p, const char* who, int64_t lo, int64_t hi) {
-    const int rc = group_ready(p, who);
-    if (rc != HM_OK) return rc;
-    if (lo < 0 || hi < lo || hi > p->seq_off.back()) return pfail(p, HM_EINVAL, std::string(who) + ": bad range");
-    return HM_OK;
-}
 GroupPlanes group_planes(hm_pileup* p) {
     return GroupPlanes{AsmPlanes{p->hp_pcov[0], p->hp_ncov[0], p->hp_pcov[1], p->hp_ncov[1], p->key}, p->d_gmoment[0].as<unsigned long long>(),
                        p->d_gmoment[1].as<unsigned long long>(), p->d_gsamples[0].as<uint8_t>(), p->d_gsamples[1].as<uint8_t>()};
@@ -3451,7 +3419,7 @@ GroupPlanes group_planes(hm_pileup* p) {
 int64_t hm_pileup_fetch_groups(hm_pileup_t* p, int64_t lo, int64_t hi, int32_t min_reps, hm_group_t* out, int64_t cap) {
     if (!p) return HM_EINVAL;
     if (min_reps < 1 || min_reps > GROUP_MAX_SAMPLES) return pfail(p, HM_EINVAL, "hm_pileup_fetch_groups: min_reps must be in 1 .. 255");
-    const int rc = group_range(p, "hm_pileup_fetch_groups", lo, hi);
+    const int rc = option_range(p, "hm_pileup_fetch_groups", group_needs(p), lo, hi);
     if (rc != HM_OK) return rc;
     if (hi == lo) return 0;
     const GroupPlanes s = group_planes(p);
@@ -3465,7 +3433,7 @@ int64_t hm_pileup_fetch_groups(hm_pileup_t* p, int64_t lo, int64_t hi, int32_t m
 int hm_pileup_group_planes(hm_pileup_t* p, int32_t part, int64_t lo, int64_t hi, uint64_t* moment, uint8_t* samples) {
     if (!p) return HM_EINVAL;
     if (part != 1 && part != 2) return pfail(p, HM_EINVAL, "hm_pileup_group_planes: part must be 1 or 2");
-    const int rc = group_range(p, "hm_pileup_group_planes", lo, hi);
+    const int rc = option_range(p, "hm_pileup_group_planes", group_needs(p), lo, hi);
     if (rc != HM_OK || hi == lo) return rc;
     return guarded(p, [&] {
         const size_t n = (size_t)(hi - lo);
@@ -3492,23 +3460,6 @@ int hm_group_qvalues(const hm_group_t* rows, int64_t n, double* q, uint64_t m[3]
 }
 
 // ---- `samplecorr` -----------------------------------------------------------------------------------------------------------------
-namespace {
-// what the sample calls share: the option, the reference, an engine that is not void
-int sample_ready(hm_pileup* p, const char* who) {
-    const std::string w = who;
-    if (!p->samples || p->seq_off.empty() || !p->d_slevel.p) return pfail(p, HM_ESTATE, w + " needs option samples = N and hm_pileup_set_reference");
-    if (p->load_failed) return pfail(p, HM_ESTATE, w + ": " + LOAD_FAILED_TEXT);
-    if (!p->pcov || !p->ncov || !p->key) return pfail(p, HM_ESTATE, w + " without planes");
-    return HM_OK;
-}
-int sample_range(hm_pileup* p, const char* who, int64_t lo, int64_t hi) {
-    const int rc = sample_ready(p, who);
-    if (rc != HM_OK) return rc;
-    if (lo < 0 || hi < lo || hi > p->seq_off.back()) return pfail(p, HM_EINVAL, std::string(who) + ": bad range");
-    return HM_OK;
-}
-}  // namespace
-
 int hm_sample_geometry(int64_t out[2]) {
     if (!out) return HM_EINVAL;
     out[0] = HM_SAMPLE_TILE;
@@ -3518,7 +3469,7 @@ int hm_sample_geometry(int64_t out[2]) {
 
 int hm_sample_open(hm_pileup_t* p) {
     if (!p) return HM_EINVAL;
-    const int rc = sample_ready(p, "hm_sample_open");
+    const int rc = option_ready(p, "hm_sample_open", sample_needs(p));
     if (rc != HM_OK) return rc;
     if (p->staged_any || p->loaded || p->group_open)
         return pfail(p, HM_ESTATE, "hm_sample_open on an engine that staged records or used hm_pileup_load_loci / hm_pileup_group_sample: counts come from one source");
@@ -3529,52 +3480,18 @@ int hm_sample_open(hm_pileup_t* p) {
 int64_t hm_sample_load(hm_pileup_t* p, const hm_locus_t* rows, int64_t n) {
     if (!p) return HM_EINVAL;
     if (n < 0 || (n && !rows)) return pfail(p, HM_EINVAL, "hm_sample_load: n >= 0, rows not NULL");
-    const int ready = sample_ready(p, "hm_sample_load");
+    const int ready = option_ready(p, "hm_sample_load", sample_needs(p));
     if (ready != HM_OK) return ready;
     if (!p->samples_open) return pfail(p, HM_ESTATE, "hm_sample_load before hm_sample_open");
-    if (n == 0) return 0;
-    const int64_t slab = p->load_slab;
-    unsigned long long c[SLOAD_COUNTERS] = {0, 0, 0, 0, 0, 0};
-    const int rc = guarded(p, [&] {
-        p->d_load.reserve(sizeof(hm_locus_t) * (size_t)slab);
-        p->d_loadcnt.reserve(sizeof c);
-        HIP_TRY(hipMemsetAsync(p->d_loadcnt.p, 0, sizeof c, p->stream));
-        const SampleLoadPlanes pl{{p->pcov, p->ncov, p->key}, p->d_slevel.as<uint32_t>() + (p->samples_open - 1) * (p->sample_stride / 2),
-                                  p->sample_min_cov};
-        for (int64_t at = 0; at < n; at += slab) {  // as hm_pileup_load_loci: a slab's copy follows the kernel over the one before
-            const int64_t m = std::min(slab, n - at);
-            HIP_TRY(hipMemcpyAsync(p->d_load.p, rows + at, sizeof(hm_locus_t) * (size_t)m, hipMemcpyHostToDevice, p->stream));
-            hipLaunchKernelGGL(sample_load_kernel, dim3(grid_for(m, 4096)), dim3(TPB), 0, p->stream, p->d_load.as<hm_locus_t>(), m,
-                               p->seq_off.back(), pl, p->d_loadcnt.as<unsigned long long>());
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipMemcpyAsync(c, p->d_loadcnt.p, sizeof c, hipMemcpyDeviceToHost, p->stream));
-        HIP_TRY(hipStreamSynchronize(p->stream));
-        return HM_OK;
-    });
-    if (rc < 0) return rc;
-    unsigned long long bad = 0;
-    for (int k = SLOAD_BAD_GPOS; k < SLOAD_COUNTERS; ++k) bad += c[k];
-    if (bad) {
-        p->load_failed = true;
-        static const char* kind[SLOAD_COUNTERS] = {"", "gpos outside the reference", "negative count", "count above 2^20 - 1", "motif above 3",
-                                                   "locus given twice in one sample"};
-        std::string msg = "hm_sample_load: " + std::to_string(bad) + " bad rows";
-        const char* sep = ": ";
-        for (int k = SLOAD_BAD_GPOS; k < SLOAD_COUNTERS; ++k) {
-            if (!c[k]) continue;
-            msg += sep + std::to_string(c[k]) + " " + kind[k];
-            sep = ", ";
-        }
-        return pfail(p, HM_EDATA, msg);
-    }
-    return (int64_t)c[SLOAD_WROTE];
+    const SampleLoadPlanes sink{{p->pcov, p->ncov, p->key}, p->d_slevel.as<uint32_t>() + (p->samples_open - 1) * (p->sample_stride / 2),
+                                p->sample_min_cov};
+    return load_rows(p, "hm_sample_load", rows, n, sink, "locus given twice in one sample");
 }
 
 int64_t hm_sample_fetch_sums(hm_pileup_t* p, int64_t lo, int64_t hi, int32_t complete, hm_sample_pair_t* out) {
     if (!p) return HM_EINVAL;
     if (complete != 0 && complete != 1) return pfail(p, HM_EINVAL, "hm_sample_fetch_sums: complete must be 0 or 1");
-    const int rc = sample_range(p, "hm_sample_fetch_sums", lo, hi);
+    const int rc = option_range(p, "hm_sample_fetch_sums", sample_needs(p), lo, hi);
     if (rc != HM_OK) return rc;
     const int M = p->samples_open, pairs = M * (M + 1) / 2;
     if (!pairs) return 0;
@@ -3608,7 +3525,7 @@ int64_t hm_sample_fetch_sums(hm_pileup_t* p, int64_t lo, int64_t hi, int32_t com
 
 int hm_sample_plane(hm_pileup_t* p, int32_t s, int64_t lo, int64_t hi, uint16_t* out) {
     if (!p) return HM_EINVAL;
-    const int rc = sample_range(p, "hm_sample_plane", lo, hi);
+    const int rc = option_range(p, "hm_sample_plane", sample_needs(p), lo, hi);
     if (rc != HM_OK) return rc;
     if (s < 0 || s >= p->samples) return pfail(p, HM_EINVAL, "hm_sample_plane: no such sample");
     if (hi == lo) return HM_OK;

@@ -1062,6 +1062,13 @@ class MethylationPileup:
             ptrs = [None, None, None]
         return self._rows(self._L.hm_pileup_fetch_loci, LOCUS_DTYPE, *ptrs, plane_base, lo, hi)
 
+    def _load(self, call, gpos, pcov, ncov, motif, *lead) -> int:
+        """the rows of a load as one LOCUS_DTYPE array, given to the engine call `call` behind its leading arguments"""
+        gpos = np.ascontiguousarray(gpos, np.int64)
+        rows = np.zeros(len(gpos), LOCUS_DTYPE)
+        rows["gpos"], rows["pcov"], rows["ncov"], rows["motif"] = gpos, pcov, ncov, motif
+        return self._check(call(self._h, *lead, rows.ctypes.data_as(C.c_void_p), len(rows)))
+
     def load_loci(self, part: int, gpos, pcov, ncov, motif) -> int:
         """`diff` (hm_pileup_load_loci): counts from elsewhere -- the rows of a sample's *.cov.bed, as read_cov_bed returns them
         -- added into partition `part` (1 or 2) and the combined planes; motif an array or one context index for all rows.  Needs
@@ -1069,10 +1076,7 @@ class MethylationPileup:
         other plane fetches work as after count(), part 1 against part 2.  -> the number of rows that added a count.
         HifimethError for a row outside the reference, a negative count, a motif above 3 or a locus given twice for one part:
         the engine's planes are then void and it refuses further loads and fetches."""
-        gpos = np.ascontiguousarray(gpos, np.int64)
-        rows = np.zeros(len(gpos), LOCUS_DTYPE)
-        rows["gpos"], rows["pcov"], rows["ncov"], rows["motif"] = gpos, pcov, ncov, motif
-        return self._check(self._L.hm_pileup_load_loci(self._h, part, rows.ctypes.data_as(C.c_void_p), len(rows)))
+        return self._load(self._L.hm_pileup_load_loci, gpos, pcov, ncov, motif, part)
 
     def begin_sample(self, part: int) -> int:
         """`groupdiff` (hm_pileup_group_sample): opens the next sample of group `part` (1 or 2); load_sample_loci then adds its rows.
@@ -1085,10 +1089,7 @@ class MethylationPileup:
         moment floor(pcov^2 2^20 / (pcov + ncov)) and one sample.  -> the number of rows that added.  HifimethError for a row
         outside the reference, a negative count, a count of 2^20 or more, a motif above 3 or a locus twice in this sample: the
         engine is then void."""
-        gpos = np.ascontiguousarray(gpos, np.int64)
-        rows = np.zeros(len(gpos), LOCUS_DTYPE)
-        rows["gpos"], rows["pcov"], rows["ncov"], rows["motif"] = gpos, pcov, ncov, motif
-        return self._check(self._L.hm_pileup_load_sample_loci(self._h, rows.ctypes.data_as(C.c_void_p), len(rows)))
+        return self._load(self._L.hm_pileup_load_sample_loci, gpos, pcov, ncov, motif)
 
     def group_planes(self, part: int, lo: int = 0, hi: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
         """-> (moment uint64, samples uint8) of group `part` over [lo, hi): the sum of the counting samples' moments and their number"""
@@ -1123,10 +1124,7 @@ class MethylationPileup:
         locus stores floor(pcov 2^15 / (pcov + ncov)) + 1 if pcov + ncov >= sample_min_cov (its counts then also go to the combined
         planes), else 0xFFFF.  -> the number of rows that wrote a value.  HifimethError for a row outside the reference, a negative
         count, a count of 2^20 or more, a motif above 3 or a locus twice in this sample: the engine is then void."""
-        gpos = np.ascontiguousarray(gpos, np.int64)
-        rows = np.zeros(len(gpos), LOCUS_DTYPE)
-        rows["gpos"], rows["pcov"], rows["ncov"], rows["motif"] = gpos, pcov, ncov, motif
-        return self._check(self._L.hm_sample_load(self._h, rows.ctypes.data_as(C.c_void_p), len(rows)))
+        return self._load(self._L.hm_sample_load, gpos, pcov, ncov, motif)
 
     def sample_plane(self, s: int, lo: int = 0, hi: Optional[int] = None) -> np.ndarray:
         """-> the stored uint16 values of sample s over [lo, hi): 0 nothing seen, level + 1, or 0xFFFF seen below sample_min_cov"""
