@@ -466,27 +466,48 @@ constexpr int GROUP_MAX_SAMPLES = 255;          // per group: the sample counts 
 constexpr int SAMPLE_MAX = HM_SAMPLE_MAX, SAMPLE_TILE = HM_SAMPLE_TILE;
 constexpr uint32_t SAMPLE_BELOW = 0xFFFFu;
 
-// `diff` (hm_pileup_load_loci): the combined planes + those of the partition the rows go to.  A row adds to its partition's planes
-// and to the combined ones and raises the key to its motif (`order` bits stay 0); the old values of the partition's two adds say
-// whether the locus held a count of this partition already: a duplicate, which still adds.
+// THE DUPLICATE RULE, the same for the three sinks.  A row that passes the checks and carries a count is a duplicate exactly when
+// an earlier or concurrent row of the same locus was given to the same target: the partition for `diff`, the open sample for the
+// other two; the window runs from when the target's planes were last cleared or opened, across slabs and across calls.  Of k such
+// rows on one locus exactly k - 1 count in c[LOAD_BAD_DUP], whatever the launch geometry, the row order or the slab size, because
+// each sink decides by the old value of ONE atomic operation on ONE word per locus and target: an atomicOr on a seen bitmap
+// (`diff`: the partition's, `groupdiff`: the open sample's) or a compare-and-swap on the level word (`samplecorr`).  Exactly one
+// of the k rows finds the locus unseen.  What a duplicate adds is the sink's own business: in `diff` it still adds, in the other
+// two it adds nothing and which row wins is open.
+
+// `diff` (hm_pileup_load_loci): the combined planes + those of the partition the rows go to.  A row takes its locus' bit in the
+// seen bitmap of its target first -- the old bit says whether the locus came before: a duplicate, which still adds -- then adds
+// to its partition's planes and to the combined ones and raises the key to its motif (`order` bits stay 0).  Counts that a
+// caller's planes held before the first load are not rows: they make nothing a duplicate.
 struct LoadPlanes : CountPlanes {
     static constexpr bool LIMITED = false;
     int32_t *part_pcov, *part_ncov;
+    uint32_t* seen;  // the target's bitmap, 32 loci per word: the partition's for `diff`, the open sample's for a group
 
+    __device__ bool seen_before(int64_t g) const {
+        const uint32_t bit = 1u << (g & 31);
+        return atomicOr(&seen[g >> 5], bit) & bit;
+    }
     __device__ uint32_t take(const hm_locus_t& r) const {
         const int64_t g = r.gpos;
-        const int32_t old_p = atomicAdd(&part_pcov[g], r.pcov);
-        const int32_t old_n = atomicAdd(&part_ncov[g], r.ncov);
-        if (r.pcov) atomicAdd(&pcov[g], r.pcov);
-        if (r.ncov) atomicAdd(&ncov[g], r.ncov);
+        const bool dup = seen_before(g);
+        if (r.pcov) {
+            atomicAdd(&part_pcov[g], r.pcov);
+            atomicAdd(&pcov[g], r.pcov);
+        }
+        if (r.ncov) {
+            atomicAdd(&part_ncov[g], r.ncov);
+            atomicAdd(&ncov[g], r.ncov);
+        }
         atomicMax(&key[g], r.motif);
-        return old_p != 0 || old_n != 0 ? ROW_ADDED | ROW_DUP : ROW_ADDED;
+        return dup ? ROW_ADDED | ROW_DUP : ROW_ADDED;
     }
 };
 
 // `groupdiff` (hm_pileup_load_sample_loci): the rows of ONE sample of a group.  LIMITED: a sample's count stays below 2^20, so
-// q = floor(k^2 2^20 / n) needs no more than 60 bits.  The sample's seen bitmap -- cleared when the sample is opened -- takes the
-// locus' bit first: the old bit says whether this sample gave the locus before, a duplicate, which adds nothing.  A row below the
+// q = floor(k^2 2^20 / n) needs no more than 60 bits.  `seen` is the open SAMPLE's bitmap -- cleared when the sample is opened --
+// never the partition's: a group's samples share a partition on purpose.  It takes the locus' bit first: the old bit says
+// whether this sample gave the locus before, a duplicate, which adds nothing.  A row below the
 // sample minimum coverage keeps its bit and adds nothing.  Every other row adds its counts as LoadPlanes does, q to the group's
 // moment plane and 1 to the locus' byte of the group's sample-count plane: an add to the aligned word that holds the byte, which
 // never carries since a group has at most 255 samples.
@@ -494,13 +515,11 @@ struct GroupLoadPlanes : LoadPlanes {
     static constexpr bool LIMITED = true;
     unsigned long long* moment;  // Q_g
     uint32_t* samples;           // m_g, four loci per word
-    uint32_t* seen;              // 32 loci per word
     int32_t min_cov;
 
     __device__ uint32_t take(const hm_locus_t& r) const {
         const int64_t g = r.gpos;
-        const uint32_t bit = 1u << (g & 31);
-        if (atomicOr(&seen[g >> 5], bit) & bit) return ROW_DUP;
+        if (seen_before(g)) return ROW_DUP;
         const int32_t cov = r.pcov + r.ncov;
         if (cov < min_cov) return 0u;
         if (r.pcov) {
@@ -2391,7 +2410,9 @@ struct hm_pileup {
     bool staged_any = false, loaded = false, load_failed = false;
     int64_t load_slab = LOAD_SLAB_ROWS;  // option "load_slab": rows per slab of the next load
     // `groupdiff` ("groups" = 1), all of it only with the option on: per group the moment plane (8 B per base) and the sample-count
-    // plane (1 B), and the open sample's seen bitmap (1 bit), resident from hm_pileup_set_reference on; the samples opened per
+    // plane (1 B), and the open sample's seen bitmap (1 bit), resident from hm_pileup_set_reference on (d_gseen is the seen
+    // bitmap of whichever loader the engine has: the first hm_pileup_load_loci makes it the two partitions' bitmaps, part k's at
+    // word k * seen_words(p), 0.25 B per base, and no sample can be opened after that); the samples opened per
     // group, the group of the open one (0: none yet) and the table of 1 / (a B(a, 1/2)) by degrees of freedom for the fetch
     int groups = 0;
     int32_t group_min_cov = 5;
@@ -2441,6 +2462,9 @@ const std::vector<double>& host_lfact() {
     }();
     return tab;
 }
+
+// words of one seen bitmap, 32 loci each: whole words, the load kernel ORs into the word that holds a locus' bit
+inline size_t seen_words(const hm_pileup* p) { return ((size_t)std::max<int64_t>(p->seq_off.back(), 1) + 31) / 32; }
 
 inline int grid_for(int64_t n, int cap = 1 << 20) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + TPB - 1) / TPB, cap)); }
 
@@ -2998,7 +3022,12 @@ int hm_pileup_use_partition_planes(hm_pileup_t* p, int32_t part, void* pcov, voi
     if (p->partitions != 2) return pfail(p, HM_ESTATE, "hm_pileup_use_partition_planes without the partitions option");
     p->hp_pcov[part - 1] = static_cast<int32_t*>(pcov);
     p->hp_ncov[part - 1] = static_cast<int32_t*>(ncov);
-    return HM_OK;
+    if (!p->loaded || p->d_gseen.cap < 2 * 4 * seen_words(p)) return HM_OK;  // no seen bitmaps yet: the next load clears both
+    return guarded(p, [&] {        // other planes: no row has been given to them
+        HIP_TRY(hipMemsetAsync(p->d_gseen.as<uint32_t>() + (size_t)(part - 1) * seen_words(p), 0, 4 * seen_words(p), p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        return HM_OK;
+    });
 }
 
 int hm_pileup_partition_planes(hm_pileup_t* p, int32_t part, void** pcov, void** ncov) {
@@ -3355,7 +3384,17 @@ int64_t hm_pileup_load_loci(hm_pileup_t* p, int32_t part, const hm_locus_t* rows
     if (p->staged_any) return pfail(p, HM_ESTATE, "hm_pileup_load_loci on an engine that has staged records: counts come from records or from loads, not both");
     if (p->group_open || p->samples_open)
         return pfail(p, HM_ESTATE, "hm_pileup_load_loci on an engine that opened a sample (hm_pileup_group_sample, hm_sample_open)");
-    const LoadPlanes sink{{p->pcov, p->ncov, p->key}, p->hp_pcov[part - 1], p->hp_ncov[part - 1]};
+    // the first rows of this engine (or of a longer reference): d_gseen becomes the two partitions' seen bitmaps, cleared
+    if (n && (!p->loaded || p->d_gseen.cap < 2 * 4 * seen_words(p))) {
+        const int made = guarded(p, [&] {
+            p->d_gseen.reserve(2 * 4 * seen_words(p));
+            HIP_TRY(hipMemsetAsync(p->d_gseen.p, 0, 2 * 4 * seen_words(p), p->stream));
+            return HM_OK;
+        });
+        if (made != HM_OK) return made;
+    }
+    const LoadPlanes sink{{p->pcov, p->ncov, p->key}, p->hp_pcov[part - 1], p->hp_ncov[part - 1],
+                          p->d_gseen.as<uint32_t>() + (size_t)(part - 1) * seen_words(p)};
     const int64_t added = load_rows(p, "hm_pileup_load_loci", rows, n, sink, "locus given twice for one part");
     if (n && added >= 0) p->loaded = true;
     return added;
@@ -3404,8 +3443,8 @@ int64_t hm_pileup_load_sample_loci(hm_pileup_t* p, const hm_locus_t* rows, int64
     if (ready != HM_OK) return ready;
     if (!p->group_open) return pfail(p, HM_ESTATE, "hm_pileup_load_sample_loci before hm_pileup_group_sample");
     const int g = p->group_open - 1;
-    const GroupLoadPlanes sink{{{p->pcov, p->ncov, p->key}, p->hp_pcov[g], p->hp_ncov[g]}, p->d_gmoment[g].as<unsigned long long>(),
-                               p->d_gsamples[g].as<uint32_t>(), p->d_gseen.as<uint32_t>(), p->group_min_cov};
+    const GroupLoadPlanes sink{{{p->pcov, p->ncov, p->key}, p->hp_pcov[g], p->hp_ncov[g], p->d_gseen.as<uint32_t>()},
+                               p->d_gmoment[g].as<unsigned long long>(), p->d_gsamples[g].as<uint32_t>(), p->group_min_cov};
     return load_rows(p, "hm_pileup_load_sample_loci", rows, n, sink, "locus given twice in one sample");
 }
 

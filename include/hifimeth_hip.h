@@ -417,8 +417,17 @@ int64_t hm_pileup_fetch_asm_regions(hm_pileup_t* p, const void* pcov1, const voi
  * reference length); pcov >= 0 and ncov >= 0; motif <= 3.  A row that passes and has pcov + ncov == 0 is ignored.  Every other
  * row ADDS pcov / ncov to the planes of `part` (1 or 2) and to the combined planes -- which so hold the pooled sample -- and
  * raises the key plane at gpos to max(key, motif): where the two samples disagree about a locus' context the LARGER code wins;
- * the `order` bits of the key stay 0.  A row that adds to a locus that already held a count of the SAME part -- from this call or
- * an earlier one -- is a duplicate.  The pooled counts of a locus must stay below 2^31 (not checked).
+ * the `order` bits of the key stay 0.
+ * THE DUPLICATE RULE, for this call and for hm_pileup_load_sample_loci and hm_sample_load below.  A row that passes the checks and
+ * carries a count is a duplicate exactly when an earlier or concurrent row of the same locus was given to the same TARGET: here
+ * the part, there the open sample.  The window runs from when the target's planes were last cleared or opened (here: the
+ * first call with rows, or hm_pileup_use_partition_planes for that part after it), across slabs and across calls.  Of k such
+ * rows on one locus exactly k - 1 are counted as duplicates, whatever the launch geometry, the order of the rows or
+ * "load_slab": the engine decides by one atomic operation on one word per locus and target (here a bit of the part's seen
+ * bitmap: 1 bit per base and part, +0.25 B per reference base from the first call with rows on).  What a duplicate adds is
+ * each call's own: here it still adds; in the other two it adds nothing and which row wins is open.  Counts that planes
+ * registered with hm_pileup_use_partition_planes held beforehand are not rows and make nothing a duplicate.  The pooled counts
+ * of a locus must stay below 2^31 (not checked).
  * Returns the number of rows that added a count.  If any row was bad (out of range, negative, motif, duplicate): HM_EDATA,
  * hm_pileup_last_error gives their number and the number of each kind, and the planes mean nothing any more (the good rows and
  * the duplicates were added): every further load, and every fetch over the engine's own planes, returns HM_ESTATE.
@@ -429,7 +438,7 @@ int64_t hm_pileup_fetch_asm_regions(hm_pileup_t* p, const void* pcov1, const voi
  * interleaving.  The rows go through one device slab of "load_slab" rows (option, 1 .. 2^24, default 2^20 = 24 MB; may be set at
  * any time), slab by slab on the engine's stream: no device memory grows with n.  All adds are integer atomics: the planes depend
  * on neither row order, slab size nor launch geometry.  Not here: pileup_dist (one card holds both samples of a human genome at
- * 28 B per base), more than two samples (replicates in two groups: hm_pileup_group_sample below). */
+ * 28.25 B per base), more than two samples (replicates in two groups: hm_pileup_group_sample below). */
 int64_t hm_pileup_load_loci(hm_pileup_t* p, int32_t part, const hm_locus_t* rows, int64_t n);
 
 /* ---- replicate groups (`groupdiff`): several samples per part, tested with their spread ---------------------
@@ -449,8 +458,9 @@ int64_t hm_pileup_load_loci(hm_pileup_t* p, int32_t part, const hm_locus_t* rows
  *
  * Option "groups" (0 default, 1): needs "partitions" = 2 and must be set before hm_pileup_set_reference (else HM_ESTATE), which then
  * also allocates and zeroes, per group, a uint64 moment plane (Q_g) and a uint8 sample-count plane (m_g), and one `seen` bitmap of
- * 1 bit per base: 18.125 B per reference base more.  Without the option nothing is allocated.  Option "group_min_cov" (c: integer
- * >= 1, default 5): HM_ESTATE once a sample has been opened. */
+ * 1 bit per base (the open sample's: a group's samples share a part on purpose, so nothing is decided per part here):
+ * 18.125 B per reference base more.  Without the option nothing is allocated.  Option "group_min_cov" (c: integer >= 1,
+ * default 5): HM_ESTATE once a sample has been opened. */
 typedef struct {            /* one tested locus = one row of <prefix>.groups.<ctx>.bed; 64 bytes */
     int64_t gpos;
     int32_t pcov1, ncov1, pcov2, ncov2;   /* K_1, N_1 - K_1, K_2, N_2 - K_2 */
