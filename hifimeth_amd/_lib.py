@@ -144,6 +144,9 @@ def lib():
         "hm_sample_fetch_sums": (i64, [vp, i64, i64, i32, vp]),
         "hm_sample_plane": (C.c_int, [vp, i32, i64, i64, vp]),
         "hm_sample_corr": (C.c_int, [vp, i64, vp, vp, vp]),
+        "hm_sample_fetch_intervals": (i64, [vp, i64, i64, i32, i32, vp, vp, i64, vp]),
+        "hm_sample_interval_test": (C.c_int, [vp, i64, i32, vp, i64, i32, vp]),
+        "hm_sample_qvalues": (C.c_int, [vp, i64, vp]),
         "hm_pileup_control_sums": (C.c_int, [vp, vp, vp, vp, i64, i64, vp]),
         "hm_pileup_site_histogram": (i64, [vp, vp, vp, vp, i64, i64, i64, vp, vp, i64]),
         "hm_sites_table": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp]),

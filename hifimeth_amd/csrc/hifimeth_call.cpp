@@ -15,6 +15,7 @@
 //     hifimeth-hip diff [OPTIONS] REF.fa PREFIX1 PREFIX2 OUT (two pileups' *.cov.bed tested locus by locus, hifimeth_pileup.cpp)
 //     hifimeth-hip groupdiff [OPTIONS] REF.fa A1,A2,.. B1,B2,.. OUT (two groups of replicate pileups, hifimeth_pileup.cpp)
 //     hifimeth-hip samplecorr [OPTIONS] REF.fa S1,S2,..,SN OUT (N pileups' correlation matrix per context, hifimeth_pileup.cpp)
+//     hifimeth-hip regiondiff -R IV.bed [OPTIONS] REF.fa A1,A2,.. B1,B2,.. OUT (two groups tested over given intervals, hifimeth_pileup.cpp)
 //     hifimeth-hip modstats IN.bam                    (MM/ML parser + per-context histograms + adaptive thresholds)
 //     hifimeth-hip modlist IN.bam                     (the MM/ML parser's output per record: test seam against the
 //                                                      reference parser's fixture, tests/golden/modparse.json)
@@ -111,8 +112,9 @@ void usage() {
             "  %s diff [OPTIONS] reference prefix1 prefix2 output-prefix    two pileups tested for differential methylation\n"
             "  %s groupdiff [OPTIONS] reference a1,a2,... b1,b2,... output-prefix   two groups of replicate pileups tested likewise\n"
             "  %s samplecorr [OPTIONS] reference s1,s2,...,sN output-prefix   the correlation matrix of N pileups, per context\n"
+            "  %s regiondiff -R bed [OPTIONS] reference a1,a2,... b1,b2,... output-prefix   two groups of replicate pileups tested over given intervals\n"
             "  %s corr [-c <min coverage>] bed1 bed2                        Pearson correlation of two pileups\n",
-            kName, kName, kName, kName, kName, kName, kName, kName);
+            kName, kName, kName, kName, kName, kName, kName, kName, kName);
 }
 
 // host threads this process may really use: the affinity mask, capped by the cgroup CPU quota (a container that is granted
@@ -915,6 +917,7 @@ int main(int argc, char** argv) {
     if (cmd == "diff") return cmd_diff(argc, argv);
     if (cmd == "groupdiff") return cmd_groupdiff(argc, argv);
     if (cmd == "samplecorr") return cmd_samplecorr(argc, argv);
+    if (cmd == "regiondiff") return cmd_regiondiff(argc, argv);
     if (cmd == "sample") return cmd_sample(argc, argv);
     if (cmd == "eval") return cmd_eval(argc, argv);
     usage();

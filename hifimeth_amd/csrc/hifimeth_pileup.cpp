@@ -1527,3 +1527,138 @@ int cmd_samplecorr(int argc, char** argv) {
             secs(t_start, clk::now()), secs(t_start, t_load), secs(t_load, clk::now()));
     return 0;
 }
+
+// ---- regiondiff -R intervals.bed [OPTIONS] reference a1,a2,... b1,b2,... out-prefix (ours) ------------------------------------------
+// Two groups of replicates tested over given intervals: every sample's rows go into its own level plane as `samplecorr` loads
+// them, group 1's samples first; per context the intervals are fetched in chunks (hm_sample_fetch_intervals: per interval and
+// sample the counting loci and the sum of their levels, exact), tested on the host (hm_sample_interval_test: Welch's t-test on the
+// samples' interval levels) and given q-values among the tested intervals of the context (hm_sample_qvalues).
+namespace {
+// %.6g, with every NaN as `nan` whatever its sign
+std::string g6(double v) {
+    if (v != v) return "nan";
+    char buf[40];
+    snprintf(buf, sizeof buf, "%.6g", v);
+    return buf;
+}
+}  // namespace
+
+int cmd_regiondiff(int argc, char** argv) {
+    static const char* cn[3] = {"CpG", "CHG", "CHH"};
+    PileupOptions o;
+    int first = 0, status = 0;
+    if (!parse_command_line(CMD_REGIONDIFF, argc, argv, o, first, status)) return status;
+    o.ref = argv[first];
+    const std::vector<std::string> group[2] = {split_list(argv[first + 1]), split_list(argv[first + 2])};
+    o.prefix = argv[first + 3];
+    const size_t N = group[0].size() + group[1].size();
+    if (N > HM_SAMPLE_MAX) {  // before any file is opened
+        fprintf(stderr, "ERROR: regiondiff takes 2 to %d samples in all, the lists name %zu\n", HM_SAMPLE_MAX, N);
+        command_usage(CMD_REGIONDIFF, argv[0]);
+        return EXIT_FAILURE;
+    }
+    for (int g = 0; g < 2; ++g) {
+        for (const std::string& s : group[g])
+            if (s.empty()) { fprintf(stderr, "ERROR: an empty prefix in the list of group %d\n", g + 1); return EXIT_FAILURE; }
+        if ((long long)group[g].size() < o.region_min_reps) {
+            fprintf(stderr, "ERROR: group %d has %zu samples, fewer than -r %lld\n", g + 1, group[g].size(), o.region_min_reps);
+            return EXIT_FAILURE;
+        }
+    }
+    fprintf(stderr, "\n\n====================> Parameters:\nCPU threads: %d\nGenomic reference: %s\nintervals: %s\n", o.threads, o.ref.c_str(), o.intervals.c_str());
+    for (int g = 0; g < 2; ++g)
+        for (size_t i = 0; i < group[g].size(); ++i) fprintf(stderr, "group %d sample %zu: %s.<ctx>.cov.bed\n", g + 1, i + 1, group[g][i].c_str());
+    fprintf(stderr, "output prefix: %s\nregiondiff: min sample coverage %lld, min loci per sample %lld, min samples per group %lld, %s -> %s.regiondiff.*\n\n\n",
+            o.prefix.c_str(), o.sample_min_cov, o.region_min_sample_loci, o.region_min_reps,
+            o.sample_complete ? "loci where all samples count" : "loci where the sample counts", o.prefix.c_str());
+
+    const auto t_start = clk::now();
+    std::vector<std::string> sample = group[0];  // the files of a context: group 1's samples, then group 2's
+    sample.insert(sample.end(), group[1].begin(), group[1].end());
+    std::vector<uint8_t> member(N, 2);
+    std::fill(member.begin(), member.begin() + (long)group[0].size(), (uint8_t)1);
+    CovJob job;
+    if (const int failed = open_cov_job(o, sample, "every sample", "samples", {{"samples", (double)N}, {"sample_min_cov", (double)o.sample_min_cov}}, job))
+        return failed;
+    hm_pileup_t* pe = job.engine.get();
+    const Fasta& fa = job.fa;
+    auto die = [&](const std::string& what) { return engine_error(pe, what); };
+    Intervals iv;
+    if (!read_intervals(o.intervals, fa, iv)) return EXIT_FAILURE;
+    const size_t n = iv.sid.size();
+    std::vector<int64_t> start(n), end(n);
+    for (size_t i = 0; i < n; ++i) {
+        start[i] = job.seq_start[(size_t)iv.sid[i]] + iv.start[i];
+        end[i] = job.seq_start[(size_t)iv.sid[i]] + iv.end[i];
+    }
+    const LoadCall load = [&](const hm_locus_t* rows, int64_t k) { return hm_sample_load(pe, rows, k); };
+    uint64_t n_rows = 0;
+    for (size_t i = 0; i < N; ++i) {  // a sample's contexts share its plane: one locus, one context
+        if (hm_sample_open(pe) < 0) return die("sample");
+        for (int c = 0; c < 3; ++c)
+            if (!job.files[c].empty() && !load_cov_bed(job, job.files[c][i], load, (uint32_t)c, o.threads, n_rows)) return EXIT_FAILURE;
+    }
+    const auto t_load = clk::now();
+
+    // the sums of a chunk of intervals wait on the host, 16 N bytes each: chunks of at most 512 MB whatever the file's length
+    const size_t chunk = std::max<size_t>(1, (size_t(1) << 29) / (sizeof(hm_sample_interval_t) * N));
+    std::vector<hm_sample_interval_t> sums(std::min(chunk, n) * N);
+    std::vector<hm_sample_test_t> tests[3];
+    std::vector<double> q[3];
+    for (int c = 0; c < 3; ++c) {
+        if (job.files[c].empty()) continue;
+        tests[c].resize(n);
+        for (size_t a = 0; a < n; a += chunk) {
+            const size_t m = std::min(chunk, n - a);
+            if (hm_sample_fetch_intervals(pe, 0, job.seq_start.back(), c, o.sample_complete ? 1 : 0, start.data() + a, end.data() + a, (int64_t)m,
+                                          sums.data()) != (int64_t)(m * N))
+                return die("interval sums");
+            if (hm_sample_interval_test(sums.data(), (int64_t)m, (int32_t)N, member.data(), o.region_min_sample_loci, (int32_t)o.region_min_reps,
+                                        tests[c].data() + a) != HM_OK) {
+                fprintf(stderr, "ERROR: regiondiff: hm_sample_interval_test refused the sums\n");
+                return EXIT_FAILURE;
+            }
+        }
+        std::vector<double> pv(n);
+        for (size_t i = 0; i < n; ++i) pv[i] = tests[c][i].pvalue;
+        q[c].resize(n);
+        if (hm_sample_qvalues(pv.data(), (int64_t)n, q[c].data()) != HM_OK) {
+            fprintf(stderr, "ERROR: regiondiff: hm_sample_qvalues refused the p-values\n");
+            return EXIT_FAILURE;
+        }
+    }
+    job.engine.reset();
+    const auto open_out = [&](const std::string& path) {
+        FILE* f = fopen(path.c_str(), "w");
+        if (!f) fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str());
+        return f;
+    };
+    FILE* fs = open_out(o.prefix + ".regiondiff.summary.tsv");
+    if (!fs) return EXIT_FAILURE;
+    fprintf(fs, "ctx\tintervals\ttested\tq<=0.05\tq<=0.01\n");
+    size_t tested_all = 0;
+    for (int c = 0; c < 3; ++c) {
+        if (job.files[c].empty()) continue;
+        FILE* f = open_out(o.prefix + ".regiondiff." + cn[c] + ".tsv");
+        if (!f) { fclose(fs); return EXIT_FAILURE; }
+        fprintf(f, "#chrom\tstart\tend\tname\tstrand\tm1\tm2\tloci1\tloci2\tmean1\tmean2\tdiff\tt\tdf\tp\tq\n");
+        unsigned long long tested = 0, q05 = 0, q01 = 0;
+        for (size_t i = 0; i < n; ++i) {
+            const hm_sample_test_t& r = tests[c][i];
+            fprintf(f, "%s\t%lld\t%lld\t%s\t%c\t%d\t%d\t%llu\t%llu\t%s\t%s\t%s\t%s\t%s\t%s\t%s\n", fa.names[(size_t)iv.sid[i]].c_str(), (long long)iv.start[i],
+                    (long long)iv.end[i], iv.name[i].c_str(), iv.strand[i], r.m1, r.m2, (unsigned long long)r.n1, (unsigned long long)r.n2, g6(r.mean1).c_str(),
+                    g6(r.mean2).c_str(), g6(r.mean1 - r.mean2).c_str(), g6(r.t).c_str(), g6(r.df).c_str(), g6(r.pvalue).c_str(), g6(q[c][i]).c_str());
+            tested += r.t == r.t;
+            q05 += q[c][i] <= 0.05;
+            q01 += q[c][i] <= 0.01;
+        }
+        fclose(f);
+        fprintf(fs, "%s\t%zu\t%llu\t%llu\t%llu\n", cn[c], n, tested, q05, q01);
+        tested_all += tested;
+    }
+    fclose(fs);
+    fprintf(stderr, "## %zu + %zu samples, %llu rows of %d contexts, %zu intervals, %zu tests in %.2f s: parse + load %.2f s; sums + tests + tables %.2f s\n",
+            group[0].size(), group[1].size(), (unsigned long long)n_rows, job.n_ctx, n, tested_all, secs(t_start, clk::now()), secs(t_start, t_load),
+            secs(t_load, clk::now()));
+    return 0;
+}

@@ -1,4 +1,4 @@
-// hifimeth_pileup_opts.cpp -- the options of `pileup`, `diff`, `groupdiff` and `samplecorr`: one table that is parser and usage text at once, two strict number
+// hifimeth_pileup_opts.cpp -- the options of `pileup`, `diff`, `groupdiff`, `samplecorr` and `regiondiff`: one table that is parser and usage text at once, two strict number
 // parsers, and the checks between options as one ordered list.  A new option is one row here, a field of PileupOptions, a rule if
 // it depends on another option, and its cases in tools/make_cli_options.py.
 #include "hifimeth_pileup_opts.h"
@@ -283,6 +283,22 @@ const Option SAMPLE_OPTIONS[] = {
      "Complete mode: every pair is taken over the loci where all samples count, not over those where its two samples count"},
 };
 const char SAMPLE_FLAGS[] = "aktd";
+// and `regiondiff` five
+const Option REGION_OPTIONS[] = {
+    {'R', "<bed>", [](const char* v, O& o) { o.intervals = v; return true; },
+     "The intervals to test, fixed before looking at the data: a BED file (plain or gzip) of at least 3 tab-separated columns,\n"
+     "    name in column 4, strand in column 6; empty lines and lines starting with #, track or browser are skipped.  Intervals may\n"
+     "    overlap, nest and come in any order.  Mandatory"},
+    {'a', "<int>", integer<&O::sample_min_cov, 1, (1 << 20) - 1>,
+     "Minimum coverage (pcov + ncov) a sample needs at a locus to count there, in [1, 1048575]\n    Default: 5"},
+    {'k', nullptr, flag<&O::sample_complete>,
+     "Complete mode: a locus is taken only where all samples of both groups count, not wherever the sample itself counts"},
+    {'l', "<int>", integer<&O::region_min_sample_loci, 1, LLONG_MAX>,
+     "Minimum number of counting loci a sample needs in an interval to be used there, >= 1\n    Default: 3"},
+    {'r', "<int>", integer<&O::region_min_reps, 2, 64>,
+     "Minimum number of used samples in each group of a tested interval, in [2, 64]\n    Default: 2"},
+};
+const char REGION_FLAGS[] = "Raklrtd";
 
 const char PILEUP_HEADER[] =
     "USAGE:\n"
@@ -338,6 +354,24 @@ const char SAMPLE_HEADER[] =
     "\n"
     "OPTIONAL ARGUMENTS:\n";
 
+const char REGION_HEADER[] =
+    "USAGE:\n"
+    "  $0 regiondiff -R intervals.bed [OPTIONS] reference a1,a2,... b1,b2,... output-prefix\n"
+    "\n"
+    "DESCRIPTION:\n"
+    "  Test two groups of replicates for differential methylation over given intervals (promoters, gene bodies, tiles).  Every\n"
+    "  element of the two comma-separated lists is a prefix as `diff` takes it: <prefix>.<ctx>.cov.bed for ctx in CpG, CHG, CHH,\n"
+    "  plain or gzip; the groups hold 2 to 64 samples together and at least -r each.  A context is skipped unless every sample has\n"
+    "  its file.  A sample counts at a locus with at least -a calls; its level there is floor(pcov * 32768 / (pcov + ncov)), and its\n"
+    "  level in an interval the mean of those over its counting loci, if it has at least -l.  An interval is tested with at least -r\n"
+    "  such samples in each group, by Welch's t-test on the samples' interval levels: the spread between replicates is the yardstick.\n"
+    "  Writes <output-prefix>.regiondiff.<ctx>.tsv: a header line, then per interval in input order chrom, start, end, name, strand,\n"
+    "  m1, m2 (used samples), loci1, loci2 (their counting loci), mean1, mean2 (percent), diff = mean1 - mean2, t, df, p and the\n"
+    "  Benjamini-Hochberg q-value among the tested intervals of the context (nan where not tested); and\n"
+    "  <output-prefix>.regiondiff.summary.tsv: ctx, intervals, tested, intervals with q <= 0.05, with q <= 0.01\n"
+    "\n"
+    "ARGUMENTS:\n";
+
 const Option* find_option(Command cmd, char letter) {
     if (cmd == CMD_DIFF && !strchr(DIFF_FLAGS, letter)) return nullptr;
     if (cmd == CMD_GROUPDIFF) {
@@ -348,6 +382,11 @@ const Option* find_option(Command cmd, char letter) {
     if (cmd == CMD_SAMPLECORR) {
         if (!strchr(SAMPLE_FLAGS, letter)) return nullptr;
         for (const Option& opt : SAMPLE_OPTIONS)
+            if (opt.letter == letter) return &opt;
+    }
+    if (cmd == CMD_REGIONDIFF) {
+        if (!strchr(REGION_FLAGS, letter)) return nullptr;
+        for (const Option& opt : REGION_OPTIONS)
             if (opt.letter == letter) return &opt;
     }
     for (const Option& opt : OPTIONS)
@@ -363,7 +402,8 @@ void print_text(const char* text, const char* exe) {  // $0: the program
 }
 
 void usage(Command cmd, const char* exe) {
-    print_text(cmd == CMD_DIFF ? DIFF_HEADER : cmd == CMD_GROUPDIFF ? GROUP_HEADER : cmd == CMD_SAMPLECORR ? SAMPLE_HEADER : PILEUP_HEADER, exe);
+    print_text(cmd == CMD_DIFF ? DIFF_HEADER : cmd == CMD_GROUPDIFF ? GROUP_HEADER : cmd == CMD_SAMPLECORR ? SAMPLE_HEADER :
+               cmd == CMD_REGIONDIFF ? REGION_HEADER : PILEUP_HEADER, exe);
     const auto row = [&](const Option& opt) {
         fprintf(stderr, "  -%c%s%s\n    ", opt.letter, opt.metavar ? " " : "", opt.metavar ? opt.metavar : "");
         print_text(cmd == CMD_DIFF && opt.diff_help ? opt.diff_help : opt.help, exe);
@@ -372,6 +412,7 @@ void usage(Command cmd, const char* exe) {
     if (cmd == CMD_DIFF) for (const char* f = DIFF_FLAGS; *f; ++f) row(*find_option(cmd, *f));
     else if (cmd == CMD_GROUPDIFF) for (const char* f = GROUP_FLAGS; *f; ++f) row(*find_option(cmd, *f));
     else if (cmd == CMD_SAMPLECORR) for (const char* f = SAMPLE_FLAGS; *f; ++f) row(*find_option(cmd, *f));
+    else if (cmd == CMD_REGIONDIFF) for (const char* f = REGION_FLAGS; *f; ++f) row(*find_option(cmd, *f));
     else for (const Option& opt : OPTIONS) row(opt);
 }
 
@@ -388,7 +429,8 @@ struct Parsed {
 // of this list is the precedence: the groups asm, call, sites, domains, patterns, bedmethyl, linkage, profile, intervals, context,
 // and inside each group the order below.  It is not uniform -- patterns, linkage, profile and context report a bad value before a
 // missing parent, asm, domains, bedmethyl and intervals the missing parent first -- and tests/golden/cli_options.json pins it.
-// `diff` runs the rules marked CMD_DIFF, `groupdiff` those marked CMD_GROUPDIFF, `samplecorr` those marked CMD_SAMPLECORR.
+// `diff` runs the rules marked CMD_DIFF, `groupdiff` those marked CMD_GROUPDIFF, `samplecorr` those marked CMD_SAMPLECORR,
+// `regiondiff` those marked CMD_REGIONDIFF.
 struct Rule {
     int commands;
     bool (*fires)(const Parsed& p);
@@ -429,6 +471,9 @@ const Rule RULES[] = {
     {CMD_PILEUP, [](const Parsed& p) { return p.any_seen("O") && p.o.context_flank < 0; }, "-O needs -S"},
     {CMD_GROUPDIFF, [](const Parsed& p) { return p.any_bad("ar"); }, "-a must be an integer in [1, 1048575], -r an integer in [1, 255]"},
     {CMD_SAMPLECORR, [](const Parsed& p) { return p.any_bad("a"); }, "-a must be an integer in [1, 1048575]"},
+    {CMD_REGIONDIFF, [](const Parsed& p) { return p.o.intervals.empty(); }, "regiondiff needs -R (the intervals to test)"},
+    {CMD_REGIONDIFF, [](const Parsed& p) { return p.any_bad("alr"); },
+     "-a must be an integer in [1, 1048575], -l an integer >= 1, -r an integer in [2, 64]"},
 };
 
 }  // namespace

@@ -10,6 +10,7 @@ int cmd_pileup(int argc, char** argv);  // hifimeth_pileup.cpp
 int cmd_diff(int argc, char** argv);
 int cmd_groupdiff(int argc, char** argv);
 int cmd_samplecorr(int argc, char** argv);
+int cmd_regiondiff(int argc, char** argv);
 int cmd_corr(int argc, char** argv);  // hifimeth_tools.cpp
 int cmd_cov2bed(int argc, char** argv);
 int cmd_sample(int argc, char** argv);

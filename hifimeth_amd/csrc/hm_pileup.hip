@@ -56,6 +56,9 @@
 //   region_block_sums / RegionScan / region_query / metaplot   sums over given intervals (`pileup -R`, `-J`): twelve sums per block of
 //                   HM_REGION_BLOCK loci, their scan by the row-scan skeleton above, then a wavefront per interval (or per bin and
 //                   stride of intervals) reads the index and sums the loci of its two partial blocks
+//   sample_block_sums / SampleIvScan / sample_query   the same over the N level planes of `samplecorr` (`regiondiff`): per block and
+//                   sample the counting loci and the sum of their levels, one scan over all samples' blocks, a wavefront per
+//                   interval; the M samples of 64 positions are reduced through a tile in LDS (sample_wave_add)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -667,6 +670,152 @@ __global__ __launch_bounds__(TPB) void sample_sums_kernel(const uint16_t* __rest
     atomicAdd(&t[3], sii);
     atomicAdd(&t[4], sjj);
     atomicAdd(&t[5], sij);
+}
+
+// ---- the sums of M samples over given intervals (hm_sample_fetch_intervals; include/hifimeth_hip.h has the definition) ----------
+// The shape of `pileup -R` carried over to M planes: per block of HM_REGION_BLOCK positions and sample the pair (n, su) of the
+// call's context and mode (sample_block_sums_kernel), their running sum (the row scan with SampleIvScan), then a wavefront per
+// interval that walks the loci of at most two partial blocks and takes the whole blocks between from two reads of the index.
+// The index is SAMPLE-major, idx[s * nblk + b], and scanned as ONE sequence of M * nblk pairs: a query only ever subtracts two
+// entries of one sample, so the running sum may run on from one sample into the next, and the scan's element stays one pair (a
+// row of 2 M = 128 values per block, as RegionScan keeps its twelve, would not fit the registers).
+//
+// The M-sample reduction (sample_wave_add) goes through LDS, in two phases per 64 consecutive positions.  Phase 1, lane =
+// position: the lane reads its key once and its M values once, plane after plane -- 64 consecutive uint16 of one plane per
+// wavefront load -- and writes each into row t of the wavefront's tile; a position of another context writes zeros.  The ballot
+// of "this position can add" (in complete mode: all M count) is the same 64-bit mask in every lane.  Phase 2, lane = (sample s,
+// part q): with P the power of two >= M and G = 64 / P, lane s * G + q reads the words q, q + G, ... of row s, two positions
+// each, and adds what counts to its own (n, su).  Rows are 32 + G words apart, so the 64 lanes of a read fall on the banks
+// lane + G * step: no conflict within either half of the wavefront.  The G parts of a sample are added once per interval (or
+// block), by log2 G shuffles.  Against a cross-lane sum per sample and chunk (12 M shuffle steps per chunk), the walk costs
+// 32 / G LDS reads per chunk whatever M is.  The two phases are ordered by wavefront-scope fences: the tile is the wavefront's own.
+struct SampleIvPlanes {
+    const uint16_t* planes;
+    int64_t stride;
+    const uint32_t* key;
+    int M, G;  // samples opened; parts per sample = 64 / (the power of two >= max(M, 2))
+    uint32_t ctx;
+    int complete;
+    __host__ __device__ int pitch() const { return 32 + G; }  // words per tile row
+};
+using SamplePair = hm_sample_interval_t;
+
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// One wavefront adds the loci of [a, b) -- the same in all its lanes, inside the planes -- to the (n, su) of lane (s, q); `tile`
+// is the wavefront's M rows of pitch() words
+__device__ __forceinline__ void sample_wave_add(const SampleIvPlanes& v, uint32_t* tile, int64_t a, int64_t b, unsigned long long& n,
+                                                unsigned long long& su) {
+    const int lane = threadIdx.x & 63, q = lane & (v.G - 1), s = lane / v.G, pitch = v.pitch();
+    uint16_t* const half = reinterpret_cast<uint16_t*>(tile);
+    for (int64_t g0 = a; g0 < b; g0 += 64) {
+        const int64_t g = g0 + lane;
+        const bool mine = g < b && min(v.key[g] & 3u, 2u) == v.ctx;
+        if (__ballot(mine) == 0ull) continue;
+        bool all = mine;
+        for (int t = 0; t < v.M; ++t) {
+            const uint32_t x = mine ? v.planes[(int64_t)t * v.stride + g] : 0u;
+            half[t * 2 * pitch + lane] = (uint16_t)x;
+            all = all && x != 0u && x != SAMPLE_BELOW;
+        }
+        const unsigned long long ok = __ballot(v.complete ? all : mine);
+        wave_lds_sync();
+        if (ok != 0ull && s < v.M) {
+            for (int w = q; w < 32; w += v.G) {
+                const uint32_t word = tile[s * pitch + w], bits = (uint32_t)(ok >> (2 * w)) & 3u;
+                const uint32_t x0 = word & 0xFFFFu, x1 = word >> 16;
+                if ((bits & 1u) && x0 != 0u && x0 != SAMPLE_BELOW) {
+                    n += 1;
+                    su += x0 - 1u;
+                }
+                if ((bits & 2u) && x1 != 0u && x1 != SAMPLE_BELOW) {
+                    n += 1;
+                    su += x1 - 1u;
+                }
+            }
+        }
+        wave_lds_sync();
+    }
+}
+
+// the G parts of every sample added up: lane (s, 0) holds the sample's sums
+__device__ __forceinline__ void sample_parts_sum(int G, unsigned long long& n, unsigned long long& su) {
+    for (int d = G >> 1; d; d >>= 1) {
+        n += __shfl_xor(n, d);
+        su += __shfl_xor(su, d);
+    }
+}
+
+// idx[s * nblk + blockIdx.x] = (n, su) of sample s over block blockIdx.x of [lo, hi): each wavefront takes a quarter of the block
+__global__ __launch_bounds__(TPB) void sample_block_sums_kernel(SampleIvPlanes v, int64_t lo, int64_t hi, int64_t nblk, SamplePair* __restrict__ idx) {
+    extern __shared__ uint32_t sample_iv_lds[];
+    __shared__ unsigned long long part[TPB / 64][2 * SAMPLE_MAX];
+    constexpr int64_t QUARTER = HM_REGION_BLOCK / (TPB / 64);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, s = lane / v.G;
+    const int64_t a = lo + (int64_t)blockIdx.x * HM_REGION_BLOCK + w * QUARTER, b = min(hi, a + QUARTER);
+    unsigned long long n = 0, su = 0;
+    if (a < b) sample_wave_add(v, sample_iv_lds + w * v.M * v.pitch(), a, b, n, su);
+    sample_parts_sum(v.G, n, su);
+    if ((lane & (v.G - 1)) == 0 && s < v.M) {
+        part[w][2 * s] = n;
+        part[w][2 * s + 1] = su;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < v.M) {
+        SamplePair t{0, 0};
+        for (int k = 0; k < TPB / 64; ++k) {
+            t.n += part[k][2 * threadIdx.x];
+            t.su += part[k][2 * threadIdx.x + 1];
+        }
+        idx[(int64_t)threadIdx.x * nblk + blockIdx.x] = t;
+    }
+}
+
+// the M * nblk pairs of the index -> their inclusive scan, in place
+struct SampleIvScan {
+    using T = SamplePair;
+    SamplePair* idx;
+    __host__ __device__ __forceinline__ static T identity() { return T{0, 0}; }
+    __device__ __forceinline__ static T shfl_up(const T& v, int d) {
+        return T{(uint64_t)__shfl_up((unsigned long long)v.n, d), (uint64_t)__shfl_up((unsigned long long)v.su, d)};
+    }
+    __device__ __forceinline__ static T op(const T& a, const T& b) { return T{a.n + b.n, a.su + b.su}; }
+    __device__ __forceinline__ T load(int64_t j) const { return idx[j]; }
+    __device__ __forceinline__ void store(int64_t j, const T& f) const { idx[j] = f; }
+};
+
+// out[i * M + s] = (n, su) of sample s over interval i clamped to [lo, hi): a wavefront per interval, over a grid stride.  Within
+// one block the loci of [a, b) themselves; else the loci from a to the end of a's block and from the start of b's block to b, and
+// for the whole blocks between them prefix(b's block - 1) - prefix(a's block) of the sample's own stretch of the index.
+__global__ __launch_bounds__(TPB) void sample_query_kernel(SampleIvPlanes v, int64_t lo, int64_t hi, int64_t nblk, const SamplePair* __restrict__ idx,
+                                                            const int64_t* __restrict__ start, const int64_t* __restrict__ end, int64_t n_iv,
+                                                            SamplePair* __restrict__ out) {
+    extern __shared__ uint32_t sample_iv_lds[];
+    const int lane = threadIdx.x & 63, s = lane / v.G;
+    const bool owner = (lane & (v.G - 1)) == 0 && s < v.M;
+    uint32_t* const tile = sample_iv_lds + (threadIdx.x >> 6) * v.M * v.pitch();
+    for (int64_t i = (int64_t)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6); i < n_iv; i += (int64_t)gridDim.x * (TPB / 64)) {
+        const int64_t a = min(max(start[i], lo), hi), b = min(max(end[i], lo), hi);
+        unsigned long long n = 0, su = 0;
+        if (a < b) {
+            const int64_t ba = (a - lo) / HM_REGION_BLOCK, bb = (b - lo) / HM_REGION_BLOCK;
+            sample_wave_add(v, tile, a, ba == bb ? b : lo + (ba + 1) * HM_REGION_BLOCK, n, su);
+            if (ba != bb) {
+                sample_wave_add(v, tile, lo + bb * HM_REGION_BLOCK, b, n, su);
+                if (owner && bb > ba + 1) {
+                    const SamplePair hiw = idx[(int64_t)s * nblk + bb - 1], low = idx[(int64_t)s * nblk + ba];
+                    n += hiw.n - low.n;
+                    su += hiw.su - low.su;
+                }
+            }
+        }
+        sample_parts_sum(v.G, n, su);
+        if (owner) out[i * v.M + s] = SamplePair{n, su};
+    }
 }
 
 // ---- resident records joined with per-locus truth labels (`hifimeth eval`, src/app/hifimeth/eval.cpp:469-560) ----
@@ -1514,8 +1663,8 @@ __device__ __forceinline__ double deviance_part(double x, double e, double d) {
 }
 
 // The continued fraction of the incomplete beta function, modified Lentz: I_x(a, b) = x^a (1 - x)^b / (a B(a, b)) * beta_cf(a, b, x),
-// quick for x < (a + 1) / (a + b + 2)
-__device__ __forceinline__ double beta_cf(double a, double b, double x) {
+// quick for x < (a + 1) / (a + b + 2).  Host and device: hm_sample_interval_test runs it on the host.
+__host__ __device__ __forceinline__ double beta_cf(double a, double b, double x) {
     const double tiny = 1e-300, qab = a + b, qap = a + 1.0, qam = a - 1.0;
     double c = 1.0, d = 1.0 - qab * x / qap;
     if (fabs(d) < tiny) d = tiny;
@@ -2425,6 +2574,9 @@ struct hm_pileup {
     int32_t sample_min_cov = 5;
     int64_t sample_stride = 0;
     DevBuf d_slevel{EXACT}, d_stable{EXACT};
+    // `regiondiff` (hm_sample_fetch_intervals), allocated by the first call: the index of the range, context and mode in hand
+    // (16 M B per HM_REGION_BLOCK positions), the caller's intervals, and the M pairs per interval
+    DevBuf d_sividx{EXACT}, d_siviv{HALF}, d_sivout{HALF};
     uint32_t thr_packed = 0;   // the three thresholds of the last hm_pileup_count
     bool counted = false;    // hm_pileup_count has run since hm_pileup_set_reference: what the -E, -M and -L fetches wait for
     int64_t n_recs = 0;
@@ -4482,6 +4634,123 @@ int64_t hm_pileup_fetch_context(hm_pileup_t* p, const void* pcov, const void* nc
 int64_t hm_pileup_fetch_context_path(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t plane_base, int64_t lo,
                                      int64_t hi, int64_t min_cov, int32_t flank, int32_t path, hm_region_sum_t* out, int64_t cap) {
     return fetch_context(p, pcov, ncov, key, plane_base, lo, hi, min_cov, flank, path, out, cap);
+}
+
+// ---- `regiondiff` -----------------------------------------------------------------------------------------------------------------
+int64_t hm_sample_fetch_intervals(hm_pileup_t* p, int64_t lo, int64_t hi, int32_t ctx, int32_t complete, const int64_t* start,
+                                  const int64_t* end, int64_t n_iv, hm_sample_interval_t* out) {
+    if (!p) return HM_EINVAL;
+    const char* who = "hm_sample_fetch_intervals";
+    if (complete != 0 && complete != 1) return pfail(p, HM_EINVAL, std::string(who) + ": complete must be 0 or 1");
+    if (ctx < 0 || ctx > 2) return pfail(p, HM_EINVAL, std::string(who) + ": ctx must be 0, 1 or 2");
+    const int rc = option_range(p, who, sample_needs(p), lo, hi);
+    if (rc != HM_OK) return rc;
+    if (n_iv < 0 || (n_iv && (!start || !end || !out))) return pfail(p, HM_EINVAL, std::string(who) + ": n_iv >= 0, start, end and out not NULL");
+    for (int64_t i = 0; i < n_iv; ++i)
+        if (start[i] > end[i]) return pfail(p, HM_EINVAL, std::string(who) + ": interval " + std::to_string(i) + " has start > end");
+    const int M = p->samples_open;
+    if (!M || !n_iv) return 0;
+    std::fill(out, out + n_iv * M, hm_sample_interval_t{0, 0});
+    if (hi == lo) return n_iv * M;
+    const int done = guarded(p, [&] {
+        hipStream_t st = p->stream;
+        int P = 2;
+        while (P < M) P <<= 1;
+        const SampleIvPlanes v{p->d_slevel.as<uint16_t>(), p->sample_stride, p->key, M, 64 / P, (uint32_t)ctx, (int)complete};
+        const int64_t nblk = (hi - lo + HM_REGION_BLOCK - 1) / HM_REGION_BLOCK;
+        const size_t iv_bytes = sizeof(int64_t) * (size_t)n_iv, out_bytes = sizeof(SamplePair) * (size_t)n_iv * (size_t)M;
+        const size_t lds = sizeof(uint32_t) * (TPB / 64) * (size_t)M * (size_t)v.pitch();
+        p->d_sividx.reserve(sizeof(SamplePair) * (size_t)M * (size_t)nblk);
+        p->d_siviv.reserve(2 * iv_bytes);
+        p->d_sivout.reserve(out_bytes);
+        SamplePair* idx = p->d_sividx.as<SamplePair>();
+        int64_t* iv = p->d_siviv.as<int64_t>();
+        HIP_TRY(hipMemcpyAsync(iv, start, iv_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(iv + n_iv, end, iv_bytes, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(sample_block_sums_kernel, dim3((unsigned)nblk), dim3(TPB), lds, st, v, lo, hi, nblk, idx);
+        HIP_TRY(hipGetLastError());
+        row_scan(p, SampleIvScan{idx}, (int64_t)M * nblk);
+        // at most 2^14 workgroups: 65 536 wavefronts share the intervals beyond that
+        hipLaunchKernelGGL(sample_query_kernel, dim3(grid_for(n_iv * 64, 1 << 14)), dim3(TPB), lds, st, v, lo, hi, nblk, idx, iv, iv + n_iv, n_iv,
+                           p->d_sivout.as<SamplePair>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(out, p->d_sivout.p, out_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return HM_OK;
+    });
+    return done != HM_OK ? done : n_iv * M;
+}
+
+int hm_sample_interval_test(const hm_sample_interval_t* sums, int64_t n_iv, int32_t M, const uint8_t* group, int64_t min_loci,
+                            int32_t min_reps, hm_sample_test_t* out) {
+    if (n_iv < 0 || M < 1 || M > SAMPLE_MAX || !group || (n_iv && (!sums || !out)) || min_loci < 1 || min_reps < 2 || min_reps > SAMPLE_MAX)
+        return HM_EINVAL;
+    for (int s = 0; s < M; ++s)
+        if (group[s] > 2) return HM_EINVAL;
+    const double nan = std::nan("");
+    for (int64_t i = 0; i < n_iv; ++i) {
+        const hm_sample_interval_t* e = sums + i * M;
+        double x[SAMPLE_MAX], mean[2], var[2];
+        int m[2] = {0, 0};
+        uint64_t loci[2] = {0, 0};
+        for (int g = 0; g < 2; ++g) {
+            double sum = 0.0;
+            for (int s = 0; s < M; ++s) {
+                x[s] = nan;
+                if (group[s] != g + 1 || e[s].n < (uint64_t)min_loci) continue;
+                x[s] = 100.0 * (double)e[s].su / ((double)e[s].n * 32768.0);
+                sum += x[s];
+                loci[g] += e[s].n;
+                ++m[g];
+            }
+            mean[g] = m[g] ? sum / (double)m[g] : nan;
+            double ss = 0.0;
+            for (int s = 0; s < M; ++s)
+                if (x[s] == x[s]) ss += (x[s] - mean[g]) * (x[s] - mean[g]);
+            var[g] = m[g] > 1 ? ss / (double)(m[g] - 1) : nan;
+        }
+        hm_sample_test_t& r = out[i];
+        r = hm_sample_test_t{m[0], m[1], loci[0], loci[1], mean[0], mean[1], nan, nan, nan};
+        if (m[0] < min_reps || m[1] < min_reps) continue;
+        const double a1 = var[0] / (double)m[0], a2 = var[1] / (double)m[1], se2 = a1 + a2, d = mean[0] - mean[1];
+        if (se2 == 0.0) {
+            if (d == 0.0) {
+                r.t = 0.0;
+                r.df = (double)(m[0] + m[1] - 2);
+                r.pvalue = 1.0;
+            } else {
+                r.t = d > 0.0 ? INFINITY : -INFINITY;
+            }
+            continue;
+        }
+        r.t = d / std::sqrt(se2);
+        r.df = se2 * se2 / (a1 * a1 / (double)(m[0] - 1) + a2 * a2 / (double)(m[1] - 1));
+        if (r.t == 0.0) {
+            r.pvalue = 1.0;
+            continue;
+        }
+        // the tail of group_test_kernel with F = t^2 and a real nu: 1 / (a B(a, 1/2)) = Gamma(a + 1/2) / (sqrt(pi) Gamma(a + 1)), a <= 63
+        const double F = r.t * r.t, a = 0.5 * r.df;
+        const double xx = r.df / (r.df + F), y = F / (r.df + F);
+        const double xa = y < 0.5 ? std::exp(a * std::log1p(-y)) : std::pow(xx, a);
+        const double front = std::tgamma(a + 0.5) / (1.7724538509055160273 * std::tgamma(a + 1.0)) * xa * std::sqrt(y);
+        const double pv = xx < (a + 1.0) / (a + 2.5) ? front * beta_cf(a, 0.5, xx) : 1.0 - 2.0 * a * front * beta_cf(0.5, a, y);
+        r.pvalue = pv > 1.0 ? 1.0 : pv >= DBL_MIN ? pv : DBL_MIN;
+    }
+    return HM_OK;
+}
+
+int hm_sample_qvalues(const double* pv, int64_t n, double* q) {
+    if (n < 0 || (n && (!pv || !q))) return HM_EINVAL;
+    std::vector<BhEntry> ent;
+    for (int64_t i = 0; i < n; ++i) {
+        q[i] = std::nan("");
+        if (pv[i] != pv[i]) continue;
+        if (!(pv[i] >= DBL_MIN && pv[i] <= 1.0)) return HM_EINVAL;
+        ent.push_back(BhEntry{pv[i], 1, i});
+    }
+    bh_qvalues(ent, ent.size(), [&](int64_t where, double v) { q[where] = v; });
+    return HM_OK;
 }
 
 }  // extern "C"

@@ -43,6 +43,11 @@ the integer sums of every pair i <= j per context (SAMPLE_PAIR_DTYPE), `sample_c
 and the two mean levels, `samplecorr_tsv`, `samplecorr_matrix_tsv` and `samplecorr_samples_tsv` the text of
 <prefix>.samplecorr.<ctx>.tsv, <prefix>.samplecorr.<ctx>.matrix.tsv and <prefix>.samplecorr.samples.tsv.
 
+Two groups of samples over given intervals (`hifimeth-hip regiondiff`): on the same planes, `pu.sample_intervals(start, end, ctx)`
+returns per interval and sample the counting loci and the sum of their levels, `sample_interval_test(sums, group)` Welch's t-test of
+the two groups on the samples' interval levels (SAMPLE_TEST_DTYPE), `sample_qvalues(p)` the BH q-values among the tested intervals,
+`regiondiff_tsv` and `regiondiff_summary_tsv` the text of <prefix>.regiondiff.<ctx>.tsv and <prefix>.regiondiff.summary.tsv.
+
 Binomial test per locus (`pileup -B control` / `-e r,r,r`): is a locus methylated at all, against the caller's false-positive
 rate?  `pu.control_sums(lo, hi)` over an unmethylated control sequence gives the rates (`rates_from_sums`), `pu.site_histogram()`
 counts the loci per (motif, pcov, pcov + ncov), `sites_table(rates, bins, big)` -- host only, the C library's -- solves p-values
@@ -136,6 +141,8 @@ GROUP_DTYPE = np.dtype([("gpos", "<i8"), ("pcov1", "<i4"), ("ncov1", "<i4"), ("p
 SAMPLE_PAIR_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("ctx", "<u4"), ("reserved", "<u4"), ("n", "<u8"), ("si", "<u8"), ("sj", "<u8"),
                               ("sii", "<u8"), ("sjj", "<u8"), ("sij", "<u8")])  # hm_sample_pair_t, 64 bytes
 SAMPLE_MAX = 64  # HM_SAMPLE_MAX
+SAMPLE_TEST_DTYPE = np.dtype([("m1", "<i4"), ("m2", "<i4"), ("n1", "<u8"), ("n2", "<u8"), ("mean1", "<f8"), ("mean2", "<f8"), ("t", "<f8"),
+                              ("df", "<f8"), ("pvalue", "<f8")])  # hm_sample_test_t, 64 bytes
 ASM_BIN_DTYPE = np.dtype([("bin", "<u4"), ("reserved", "<u4"), ("count", "<u8"), ("pvalue", "<f8"), ("qvalue", "<f8")])  # hm_asm_bin_t, 32 bytes
 ASM_REGION_DTYPE = np.dtype([("start", "<i8"), ("end", "<i8"), ("pcov1", "<i8"), ("ncov1", "<i8"), ("pcov2", "<i8"), ("ncov2", "<i8"),
                              ("n_loci", "<i4"), ("sign", "<i4"), ("motif", "<u4"), ("flags", "<u4"), ("diff", "<f8"),
@@ -374,6 +381,56 @@ def samplecorr_samples_tsv(names: Sequence[str], entries: np.ndarray, contexts: 
         pairs = _sample_pairs(entries, c)
         text += "".join("%s\t%s\t%d\t%.6g\n" % (CTX_NAMES[c], names[i], int(pairs[(i, i)][0]["n"]), pairs[(i, i)][2]) for i in range(len(names)))
     return text
+
+
+def sample_interval_test(sums: np.ndarray, group: Sequence[int], min_loci: int = 3, min_reps: int = 2) -> np.ndarray:
+    """`regiondiff` (hm_sample_interval_test, host only): sums = what sample_intervals returned, (n_iv, M, 2) uint64; group[s] = 1
+    or 2, or 0 for a sample that takes no part.  -> SAMPLE_TEST_DTYPE [n_iv]: per interval the used samples of each group (those
+    with >= min_loci counting loci), their loci, the groups' mean levels in percent, and Welch's t, df and two-sided p-value; NaN
+    where fewer than min_reps samples of a group are used, and p NaN where the samples of both groups do not vary at all but the
+    means differ.  include/hifimeth_hip.h has the definition."""
+    sums = np.ascontiguousarray(sums, np.uint64)
+    assert sums.ndim == 3 and sums.shape[2] == 2
+    group = np.ascontiguousarray(group, np.uint8)
+    assert group.size == sums.shape[1]
+    out = np.zeros(sums.shape[0], SAMPLE_TEST_DTYPE)
+    if lib().hm_sample_interval_test(sums.ctypes.data_as(C.c_void_p), sums.shape[0], sums.shape[1], group.ctypes.data_as(C.c_void_p),
+                                     min_loci, min_reps, out.ctypes.data_as(C.c_void_p)) != 0:
+        raise HifimethError("hm_sample_interval_test: bad argument")
+    return out
+
+
+def sample_qvalues(p: np.ndarray) -> np.ndarray:
+    """`regiondiff` (hm_sample_qvalues, host only): the Benjamini-Hochberg q-values of p among its finite entries; NaN stays NaN"""
+    p = np.ascontiguousarray(p, np.float64).reshape(-1)
+    q = np.full(p.size, np.nan)
+    if lib().hm_sample_qvalues(p.ctypes.data_as(C.c_void_p), p.size, q.ctypes.data_as(C.c_void_p)) != 0:
+        raise HifimethError("hm_sample_qvalues: a p-value outside [DBL_MIN, 1]")
+    return q
+
+
+def _g6(v: float) -> str:
+    return "nan" if v != v else "%.6g" % v
+
+
+def regiondiff_tsv(regions: "Regions", names: Sequence[str], tests: np.ndarray, q: np.ndarray) -> str:
+    """the text of <prefix>.regiondiff.<ctx>.tsv: the header, then per interval in input order chrom, start, end, name, strand, m1,
+    m2, loci1, loci2, mean1, mean2, diff, t, df, p, q (nan where not tested); tests = sample_interval_test's rows of the context,
+    q = sample_qvalues(tests["pvalue"])"""
+    head = "#chrom\tstart\tend\tname\tstrand\tm1\tm2\tloci1\tloci2\tmean1\tmean2\tdiff\tt\tdf\tp\tq\n"
+    return head + "".join(
+        "%s\t%d\t%d\t%s\t%s\t%d\t%d\t%d\t%d\t" % (names[regions.sid[i]], regions.start[i], regions.end[i], regions.name[i], regions.strand[i],
+                                                int(r["m1"]), int(r["m2"]), int(r["n1"]), int(r["n2"]))
+        + "\t".join(_g6(float(v)) for v in (r["mean1"], r["mean2"], r["mean1"] - r["mean2"], r["t"], r["df"], r["pvalue"], q[i])) + "\n"
+        for i, r in enumerate(tests))
+
+
+def regiondiff_summary_tsv(tests: dict, q: dict) -> str:
+    """the text of <prefix>.regiondiff.summary.tsv: the header, then per context of `tests` (keyed 0, 1, 2, in that order) ctx,
+    intervals, tested intervals, those with q <= 0.05 and with q <= 0.01"""
+    return "ctx\tintervals\ttested\tq<=0.05\tq<=0.01\n" + "".join(
+        "%s\t%d\t%d\t%d\t%d\n" % (CTX_NAMES[c], len(tests[c]), int((~np.isnan(tests[c]["t"])).sum()), int((q[c] <= 0.05).sum()), int((q[c] <= 0.01).sum()))
+        for c in sorted(tests))
 
 
 def stitch_asm_regions(parts, max_gap: int, min_loci: int, keep_edges: bool = False) -> Tuple[np.ndarray, int]:
@@ -1141,6 +1198,19 @@ class MethylationPileup:
         out = np.zeros(3 * (SAMPLE_MAX * (SAMPLE_MAX + 1) // 2), SAMPLE_PAIR_DTYPE)
         n = self._check(self._L.hm_sample_fetch_sums(self._h, lo, hi, int(complete), out.ctypes.data_as(C.c_void_p)))
         return out[:n].copy()
+
+    def sample_intervals(self, start, end, ctx: int, lo: int = 0, hi: Optional[int] = None, complete: bool = False) -> np.ndarray:
+        """`regiondiff` (hm_sample_fetch_intervals): per interval [start[i], end[i]) -- GLOBAL locus coordinates, clamped to
+        [lo, hi) -- and sample opened so far, the number of loci of context ctx at which the sample counts (complete: at which
+        all count) and the sum of its levels there: uint64 (n_iv, M, 2), exact.  Additive over adjacent ranges."""
+        hi = self.n_loci if hi is None else hi
+        a, b = (np.ascontiguousarray(x, np.int64).reshape(-1) for x in (start, end))
+        assert a.size == b.size
+        out = np.zeros((a.size, SAMPLE_MAX, 2), np.uint64)
+        n = self._check(self._L.hm_sample_fetch_intervals(self._h, lo, hi, ctx, int(complete), a.ctypes.data_as(C.c_void_p),
+                                                          b.ctypes.data_as(C.c_void_p), a.size, out.ctypes.data_as(C.c_void_p)))
+        m = n // a.size if a.size else 0
+        return out.reshape(-1)[:2 * n].reshape(a.size, m, 2).copy()
 
     def bed(self, loci: np.ndarray) -> dict:
         """the text of <prefix>.{CpG,CHG,CHH}.cov.bed (pileup.cpp:562-590)"""

@@ -213,6 +213,7 @@ int hm_reset_timing(hm_engine_t* e);
  *   (ours) two samples' *.cov.bed rows into the haplotype planes (`diff`)         -> hm_pileup_load_loci
  *   (ours) two groups of replicates, tested with their spread (`groupdiff`)       -> hm_pileup_group_sample, hm_pileup_fetch_groups
  *   (ours) N samples' correlation matrix per context (`samplecorr`)               -> hm_sample_open, hm_sample_fetch_sums
+ *   (ours) two groups of samples tested over given intervals (`regiondiff`)       -> hm_sample_fetch_intervals, hm_sample_interval_test
  * The whole genome's counters stay resident in HBM (12 B per reference base, 28 B with the haplotype partitions) and the
  * projected calls wait in HBM (12 B each) until the thresholds are known -- the reference spills them to a temporary file.
  * MM/ML parsing and BED text formatting stay on the host (hm_bam.h).                                           */
@@ -553,6 +554,49 @@ int hm_sample_plane(hm_pileup_t* p, int32_t s, int64_t lo, int64_t hi, uint16_t*
 /* Host only.  r[k], mean_i[k], mean_j[k] of e[k] by the formula above, k in [0, n); each of the three may be NULL.  HM_EINVAL for
  * n < 0 or e NULL with n > 0. */
 int hm_sample_corr(const hm_sample_pair_t* e, int64_t n, double* r, double* mean_i, double* mean_j);
+
+/* ---- N samples over given intervals (`regiondiff`): a two-group test of each interval ------------------------
+ * The planes are those of the family above.  M is the number of samples opened so far.  For interval i = [start, end), in global
+ * plane coordinates and clamped to [lo, hi), a context ctx and a sample s < M, take the loci g of the interval with
+ * min(key[g] & 3, 2) == ctx at which s counts (its plane value is neither 0 nor 0xFFFF) -- in COMPLETE mode only the loci at which
+ * all M samples count -- and over those loci
+ *   n = their number,  su = the sum of the levels u = value - 1
+ * Both are uint64 and exact; they are sums of integers, so they depend on neither the launch geometry nor the order of the
+ * intervals, and the sums over [lo, m) plus those over [m, hi) equal those over [lo, hi) for every interval and sample.
+ * The index the call builds (per sample a running sum over blocks of HM_REGION_BLOCK positions, 16 M bytes per block) lives in a
+ * buffer of the engine that grows on demand and is rebuilt by every call; an engine that never calls this allocates none. */
+typedef struct {            /* one (interval, sample); 16 bytes */
+    uint64_t n, su;
+} hm_sample_interval_t;
+/* The sums of n_iv intervals (start[i], end[i]: HOST memory; any order; they may overlap, repeat, be empty or lie outside
+ * [lo, hi)) into out[i * M + s] (HOST memory); returns n_iv * M (0 with no sample open).  hi == lo gives zeros.  HM_EINVAL for
+ * lo < 0, lo > hi, hi past the reference, ctx outside 0 .. 2, complete outside {0, 1}, n_iv < 0, start, end or out NULL with
+ * n_iv > 0, or an interval with start > end; HM_ESTATE without option "samples", before hm_pileup_set_reference or on a voided
+ * engine, as hm_sample_fetch_sums. */
+int64_t hm_sample_fetch_intervals(hm_pileup_t* p, int64_t lo, int64_t hi, int32_t ctx, int32_t complete, const int64_t* start,
+                                  const int64_t* end, int64_t n_iv, hm_sample_interval_t* out);
+/* Host only: Welch's t-test of two groups of samples on their interval levels.  This is this library's own statistic -- a t-test
+ * on per-sample interval means, as tile-based tools do it -- not another tool's.  sums[i * M + s] as above; group[s] is 1 or 2,
+ * or 0 for a sample that takes no part.  Sample s is USED in interval i when n_s >= min_loci (>= 1); its level there is
+ * x_s = 100 su_s / (n_s 2^15) percent.  Per group g: m_g = its used samples, n_g = the sum of their n_s, mean_g = the mean of
+ * their x_s (NaN when m_g = 0), V_g = their sample variance (two passes, samples in ascending index).  An interval is TESTED
+ * when m_1 >= min_reps and m_2 >= min_reps, min_reps in 2 .. 64.  With se2 = V_1 / m_1 + V_2 / m_2:
+ *   t = (mean_1 - mean_2) / sqrt(se2),  df = se2^2 / ((V_1 / m_1)^2 / (m_1 - 1) + (V_2 / m_2)^2 / (m_2 - 1))  (Welch-Satterthwaite),
+ *   pvalue = I_{df / (df + t^2)}(df / 2, 1 / 2), two-sided, never below DBL_MIN.
+ * se2 = 0 with equal means: t = 0, df = m_1 + m_2 - 2, pvalue = 1; with unequal means: t = +-inf, df = NaN, pvalue = NaN (the
+ * data give no yardstick; the interval takes no part in hm_sample_qvalues).  An untested interval has t = df = pvalue = NaN.
+ * HM_EINVAL for n_iv < 0, M outside 1 .. 64, a NULL pointer with n_iv > 0, group NULL or a group value above 2, min_loci < 1 or
+ * min_reps outside 2 .. 64. */
+typedef struct {            /* one interval; 64 bytes */
+    int32_t m1, m2;
+    uint64_t n1, n2;
+    double mean1, mean2, t, df, pvalue;
+} hm_sample_test_t;
+int hm_sample_interval_test(const hm_sample_interval_t* sums, int64_t n_iv, int32_t M, const uint8_t* group, int64_t min_loci,
+                            int32_t min_reps, hm_sample_test_t* out);
+/* Host only: Benjamini-Hochberg q-values of p[0, n) among its finite entries, as hm_group_qvalues; q[i] = NaN where p[i] is NaN,
+ * equal p give equal q.  HM_EINVAL for n < 0, a NULL pointer with n > 0, or a p that is neither NaN nor in [DBL_MIN, 1]. */
+int hm_sample_qvalues(const double* p, int64_t n, double* q);
 
 /* ---- per-locus binomial test (`pileup -B / -e`): is a locus methylated at all ------------------------
  * Against a false-positive rate e per context -- given, or measured on an unmethylated control sequence as sum(pcov) /

@@ -184,6 +184,46 @@ def load_leg(check):
     return out
 
 
+def sample_intervals_leg(check):
+    """`regiondiff`: hm_sample_fetch_intervals of N = 6 samples over 2^20 tiles of 256 bases of a reference of 2^28 bases, one
+    context, both modes, beside hm_pileup_fetch_regions on the same intervals over the combined planes (all three contexts at
+    once, twelve sums per interval) in the same run; a leg of its own: nothing else is run.  Both calls include the copies of the
+    intervals to the device and of the sums back."""
+    BASES, TILE, N, ROWS = 1 << 28, 256, 6, 1 << 23
+    rng = np.random.default_rng(13)
+    step = BASES // ROWS
+    pu = MethylationPileup([("chr1", BASES)], samples=N, bases=np.full(BASES, ord("N"), np.uint8))
+    g = np.arange(ROWS, dtype=np.int64) * step + rng.integers(0, step, ROWS)          # a locus per 32 bases, the same in every sample
+    motif = rng.integers(0, 3, ROWS)
+    for s in range(N):
+        cov = rng.integers(1, 30, ROWS)
+        p = rng.binomial(cov, 0.6)
+        assert pu.open_sample() == s and pu.load_sample(g, p, cov - p, motif) == ROWS
+    start = np.arange(0, BASES, TILE, dtype=np.int64)
+    end = start + TILE
+    pu.sample_intervals(start[:8], end[:8], 0)                # warm-up: the code objects, the buffers
+    pu.regions(start[:8], end[:8])
+    secs = {}
+    for name, call in (("sample_intervals_pairwise", lambda: pu.sample_intervals(start, end, 0)),
+                       ("sample_intervals_complete", lambda: pu.sample_intervals(start, end, 0, complete=True)),
+                       ("fetch_regions", lambda: pu.regions(start, end, min_cov=1))):
+        t0 = time.perf_counter()
+        got = call()
+        secs[name] = time.perf_counter() - t0
+        if name == "sample_intervals_pairwise":
+            sums = got
+    out = dict(sample_intervals_samples=N, sample_intervals_reference_bases=BASES, sample_intervals_tiles=len(start), sample_intervals_tile=TILE,
+               sample_intervals_call_s={k: round(v, 4) for k, v in secs.items()},
+               sample_intervals_tiles_per_s={k: round(len(start) / v) for k, v in secs.items()})
+    if check:                                      # every counting locus of context 0 lies in exactly one tile
+        planes = [pu.sample_plane(s) for s in range(N)]
+        key0 = np.zeros(BASES, bool)
+        key0[g[motif == 0]] = True
+        out["check_tiles_hold_the_loci"] = bool(all(int(sums[:, s, 0].sum()) == int(((planes[s] != 0) & (planes[s] != 0xFFFF) & key0).sum()) for s in range(N)))
+    pu.close()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--genome-mb", type=float, default=20)
@@ -227,9 +267,14 @@ def main():
     ap.add_argument("--digest", action="store_true", help="add a sha256 of the records, the loci and the rows of the timed options")
     ap.add_argument("--cpu-baseline", action="store_true",
                     help="time the reference's own projection code (oracle/_ref/ref_align -t) on a bounded sample")
+    ap.add_argument("--sample-intervals", action="store_true",
+                    help="time the interval sums of `regiondiff` (hm_sample_fetch_intervals): 6 samples, 2^20 tiles of 256 bases over 2^28 bases, "
+                         "against hm_pileup_fetch_regions on the same tiles over the combined planes; a leg of its own: nothing else is run")
     a = ap.parse_args()
     if a.context:
         return context_leg(a.context, a.repeat, a.check)
+    if a.sample_intervals:
+        return sample_intervals_leg(a.check)
     if a.asm and not a.partitions:
         ap.error("--asm needs --partitions")
     if a.asm_q and not a.asm:
