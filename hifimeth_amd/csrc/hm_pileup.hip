@@ -3066,6 +3066,23 @@ int option_range(hm_pileup* p, const char* who, const OptionNeeds& o, int64_t lo
     return HM_OK;
 }
 
+// What a job leaves on an engine beside its options and the caller's planes, dropped when hm_pileup_set_reference has accepted its
+// arguments: the staged batch; the resident records and pattern windows (their device counters are zeroed with the histograms and
+// in list_reference_cpgs); the 768 bins, which the next ensure_bins zeroes; the thresholds of the last count; the three flags of
+// "counts come from one source", and with `loaded` the seen bits, since the first load of an engine that has not loaded clears
+// both bitmaps; the opened samples; the error text.  The tables that hm_pileup_set_reference sizes are zeroed there.
+void drop_job(hm_pileup* p) {
+    clear_batch(p);
+    p->n_recs = p->n_precs = 0;
+    p->bins_ready = false;
+    p->counted = false;
+    p->thr_packed = p->linkage_thr = 0;
+    p->staged_any = p->loaded = p->load_failed = false;
+    p->group_samples[0] = p->group_samples[1] = p->group_open = 0;
+    p->samples_open = 0;
+    p->err.clear();
+}
+
 }  // namespace
 
 extern "C" {
@@ -3193,15 +3210,16 @@ int hm_pileup_partition_planes(hm_pileup_t* p, int32_t part, void** pcov, void**
 
 int hm_pileup_set_reference(hm_pileup_t* p, int32_t n_seqs, const int64_t* seq_len, const char* bases) {
     if (!p || n_seqs <= 0 || !seq_len || !bases) return pfail(p, HM_EINVAL, "hm_pileup_set_reference: bad argument");
-    p->seq_off.assign(1, 0);
+    std::vector<int64_t> seq_off(1, 0);  // the engine keeps its own until every argument has passed
     for (int i = 0; i < n_seqs; ++i) {
         if (seq_len[i] < 0) return pfail(p, HM_EINVAL, "negative sequence length");
-        p->seq_off.push_back(p->seq_off.back() + seq_len[i]);
+        seq_off.push_back(seq_off.back() + seq_len[i]);
+        if (seq_off.back() >= (int64_t(1) << 40)) return pfail(p, HM_EINVAL, "reference longer than 2^40 bases");
     }
-    const int64_t total = p->seq_off.back();
-    if (total >= (int64_t(1) << 40)) return pfail(p, HM_EINVAL, "reference longer than 2^40 bases");
+    const int64_t total = seq_off.back();
     return guarded(p, [&] {
-        p->counted = false;
+        drop_job(p);
+        p->seq_off = std::move(seq_off);
         p->d_ref.reserve((size_t)total + 4);
         HIP_TRY(hipMemcpyAsync(p->d_ref.p, bases, (size_t)total, hipMemcpyHostToDevice, p->stream));
         if (p->own_planes) {
@@ -3219,7 +3237,7 @@ int hm_pileup_set_reference(hm_pileup_t* p, int32_t n_seqs, const int64_t* seq_l
         if (p->partitions == 2) {
             const size_t bytes = (size_t)std::max<int64_t>(total, 1) * 4;
             for (int k = 0; k < 2; ++k) {
-                if (p->hp_pcov[k]) continue;  // caller-owned (hm_pileup_use_partition_planes)
+                if (p->hp_pcov[k] && p->hp_pcov[k] != p->d_hp_pcov[k].as<int32_t>()) continue;  // caller-owned (hm_pileup_use_partition_planes)
                 p->d_hp_pcov[k].reserve(bytes);
                 p->d_hp_ncov[k].reserve(bytes);
                 p->hp_pcov[k] = p->d_hp_pcov[k].as<int32_t>();
@@ -3238,14 +3256,12 @@ int hm_pileup_set_reference(hm_pileup_t* p, int32_t n_seqs, const int64_t* seq_l
             }
             p->d_gseen.reserve(4 * ((n + 31) / 32));
             HIP_TRY(hipMemsetAsync(p->d_gseen.p, 0, 4 * ((n + 31) / 32), p->stream));
-            p->group_samples[0] = p->group_samples[1] = p->group_open = 0;
         }
         if (p->samples) {  // a plane is a whole number of words: the kernel swaps the word that holds a locus
             p->sample_stride = (std::max<int64_t>(total, 1) + 1) & ~int64_t(1);
             const size_t bytes = 2 * (size_t)p->sample_stride * (size_t)p->samples;
             p->d_slevel.reserve(bytes);
             HIP_TRY(hipMemsetAsync(p->d_slevel.p, 0, bytes, p->stream));
-            p->samples_open = 0;
         }
         if (p->patterns || p->bedmethyl) {
             const int rc = list_reference_cpgs(p);

@@ -960,11 +960,7 @@ class MethylationPileup:
         self._h = C.c_void_p()
         if self._L.hm_pileup_create(C.byref(self._h), device) != 0:
             raise HifimethError(self._L.hm_pileup_last_error(None).decode())
-        self.names = [n for n, _ in genome]
-        self.lengths = np.array([int(s) if isinstance(s, (int, np.integer)) else len(s) for _, s in genome], np.int64)
-        self.offsets = np.concatenate([[0], np.cumsum(self.lengths)])
         self._planes = planes
-        self._order = 0
         self.partitions = bool(partitions)
         self._check(self._L.hm_pileup_set_option(self._h, b"min_mapq", float(min_mapq)))
         self._check(self._L.hm_pileup_set_option(self._h, b"min_pi", float(min_pi)))
@@ -997,15 +993,27 @@ class MethylationPileup:
             self._check(self._L.hm_pileup_set_option(self._h, b"sample_min_cov", float(sample_min_cov)))
         if planes is not None:
             self._check(self._L.hm_pileup_use_planes(self._h, *(C.c_void_p(t.data_ptr()) for t in planes)))
+        self.set_reference(genome, bases)
+
+    def set_reference(self, genome: Sequence[Tuple[str, str]], bases=None):
+        """hm_pileup_set_reference: `genome` and `bases` as for the constructor, which ends with this call.  A later call
+        re-targets the engine: it keeps its options and the caller's planes (which stay the caller's to zero, and must hold the new
+        reference) and is otherwise a new engine on `genome` -- staged and resident records, histograms, every table, the seen
+        bits, the opened samples and a void state are dropped.  A call that fails leaves engine and object as they were."""
+        lengths = np.array([int(s) if isinstance(s, (int, np.integer)) else len(s) for _, s in genome], np.int64)
         if bases is None:
             if any(isinstance(s, (int, np.integer)) for _, s in genome):
                 raise HifimethError("a genome entry that gives a length needs `bases`")
             bases = "".join(s for _, s in genome).upper().encode()
         flat = np.frombuffer(bases, np.uint8) if not isinstance(bases, np.ndarray) else bases
-        if flat.dtype != np.uint8 or flat.ndim != 1 or not flat.flags.c_contiguous or flat.size != self.n_loci:
-            raise HifimethError("bases: one contiguous uint8 per reference base expected (%d)" % self.n_loci)
-        self._check(self._L.hm_pileup_set_reference(self._h, len(genome), self.lengths.ctypes.data_as(C.c_void_p),
+        if flat.dtype != np.uint8 or flat.ndim != 1 or not flat.flags.c_contiguous or flat.size != int(lengths.sum()):
+            raise HifimethError("bases: one contiguous uint8 per reference base expected (%d)" % int(lengths.sum()))
+        self._check(self._L.hm_pileup_set_reference(self._h, len(genome), lengths.ctypes.data_as(C.c_void_p),
                                                     flat.ctypes.data_as(C.c_void_p)))
+        self.names = [n for n, _ in genome]
+        self.lengths = lengths
+        self.offsets = np.concatenate([[0], np.cumsum(lengths)])
+        self._order = 0
 
     def close(self):
         if self._h:

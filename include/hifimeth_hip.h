@@ -247,7 +247,20 @@ const char* hm_pileup_last_error(const hm_pileup_t* p); /* p may be NULL: error 
  * (hm_sample_open) */
 int hm_pileup_set_option(hm_pileup_t* p, const char* key, double value);
 /* HbnDatabase: n_seqs upper-cased sequences back to back in `bases` (seq_len[i] bytes each).  Allocates and
- * zeroes the per-locus planes unless hm_pileup_use_planes was called before. */
+ * zeroes the per-locus planes unless hm_pileup_use_planes was called before.
+ * A LATER CALL re-targets the engine.  After it returns HM_OK the engine cannot be told from a newly created one on which the
+ * same options, the same hm_pileup_use_planes and the same hm_pileup_use_partition_planes were applied, followed by this one call:
+ *  - options persist, and an option that must be set before hm_pileup_set_reference still answers HM_ESTATE;
+ *  - caller-owned planes stay registered; the call does not touch them: they are the caller's to zero, and must hold the new
+ *    reference;
+ *  - dropped: records submitted and not yet run; resident records and pattern windows (hm_pileup_num_records is 0); the 768
+ *    histogram bins; the engine's own planes and every table this call allocates (partition, group and sample planes, the
+ *    pattern, bedmethyl, linkage and read-position tables), zeroed and sized for the new reference; the thresholds of the last
+ *    hm_pileup_count; "a record was staged", "rows were loaded" and "a load met a bad row" (counts come from one source per
+ *    reference, not per engine); all seen bits of the loaders; the samples opened (hm_pileup_group_sample and hm_sample_open
+ *    start at 0 again); the error text.
+ * Device memory is kept and reused; it grows only where the new reference needs more.  A call that fails on its arguments
+ * (HM_EINVAL: n_seqs <= 0, a NULL pointer, a negative length, 2^40 bases or more) leaves the engine as it was. */
 int hm_pileup_set_reference(hm_pileup_t* p, int32_t n_seqs, const int64_t* seq_len, const char* bases);
 /* Count into caller-owned DEVICE planes of total-reference-length elements (int32 pcov, int32 ncov, uint32 key),
  * e.g. torch tensors that a RCCL reduce-scatter will consume.  The caller zeroes them. */
