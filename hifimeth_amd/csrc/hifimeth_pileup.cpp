@@ -27,6 +27,8 @@
 
 using namespace hmbam;
 
+static const char* const CTX_NAME[3] = {"CpG", "CHG", "CHH"};  // the contexts, as files and messages name them
+
 // CIGAR of a record as uint32 ops.  A CIGAR of more than 65535 operations does not fit the 16-bit n_cigar_op field: the
 // record then carries the placeholder <l_seq>S<ref_len>N and the real operations in a CG:B,I tag (SAMv1 section 4.2.2);
 // htslib's sam_read1 -- what the reference's pileup reads with -- swaps them back in, and so does this.
@@ -81,18 +83,17 @@ bool mapped_and_sorted(const BamHeader& h) {
 
 // s_resolve_scaled_prob_threshold (pileup.cpp:355-436, eval.cpp:213-305): the three thresholds with the reference's messages
 void report_thresholds(const uint64_t* bins, uint8_t thr[3]) {
-    static const char* cn[3] = {"CpG", "CHG", "CHH"};
     for (int c = 0; c < 3; ++c) {
         uint64_t samples = 0;
         const int t = resolve_threshold(bins + 256 * c, &samples);
-        fprintf(stderr, "%s samples: %llu\n", cn[c], (unsigned long long)samples);
+        fprintf(stderr, "%s samples: %llu\n", CTX_NAME[c], (unsigned long long)samples);
         const uint64_t* a = bins + 256 * c;  // the fallback branch: window narrower than 50 bins or < 10000 samples
         int st = 20, en = 256 - 20;
         while (st < 256 && a[st] < 10) ++st;
         while (en && a[en - 1] < 10) --en;
         const bool fallback = samples < 10000 || en - st < 50;
         if (fallback) fprintf(stderr, "Not enough samples for inferring scaled probability threshold, set it to 128\n");
-        else fprintf(stderr, "%s scaled probability threshold: %d\n", cn[c], t);
+        else fprintf(stderr, "%s scaled probability threshold: %d\n", CTX_NAME[c], t);
         thr[c] = (uint8_t)t;
     }
 }
@@ -109,24 +110,24 @@ uint32_t row_ctx(const Row& r) { return r.motif < 3 ? r.motif : 2; }
 inline uint32_t row_ctx(const hm_pattern_t&) { return 0; }
 inline uint32_t row_ctx(const hm_bedmethyl_t&) { return 0; }
 
-// The three files <prefix>.<tag><ctx>.<suffix> of one output, closed when their owner goes.
+// An output file, closed when its owner goes; empty (message printed) if it cannot be opened.
+struct CloseFile { void operator()(FILE* f) const { fclose(f); } };
+using OutFile = std::unique_ptr<FILE, CloseFile>;
+OutFile open_out(const std::string& path) {
+    OutFile f(fopen(path.c_str(), "w"));
+    if (!f) fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str());
+    return f;
+}
+
+// The three files <prefix>.<tag><ctx>.<suffix> of one output.
 struct CtxFiles {
+    OutFile own[3];
     FILE* f[3] = {nullptr, nullptr, nullptr};
-    CtxFiles() = default;
-    CtxFiles(const CtxFiles&) = delete;
-    CtxFiles& operator=(const CtxFiles&) = delete;
-    ~CtxFiles() {
-        for (FILE* x : f)
-            if (x) fclose(x);
-    }
     // false (message printed) if one of them cannot be opened
     bool open(const std::string& prefix, const std::string& tag, const char* suffix) {
-        static const char* cn[3] = {"CpG", "CHG", "CHH"};
         for (int c = 0; c < 3; ++c) {
-            const std::string path = prefix + "." + tag + cn[c] + suffix;
-            if ((f[c] = fopen(path.c_str(), "w"))) continue;
-            fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str());
-            return false;
+            own[c] = open_out(prefix + "." + tag + CTX_NAME[c] + suffix);
+            if (!(f[c] = own[c].get())) return false;
         }
         return true;
     }
@@ -267,9 +268,9 @@ bool write_linkage(hm_pileup_t* pe, const PileupOptions& o) {
     std::vector<hm_linkage_t> rows((size_t)o.linkage);
     const int64_t n = hm_pileup_fetch_linkage(pe, o.linkage_min_pairs, rows.data(), (int64_t)rows.size());
     if (n < 0) return false;
-    const std::string path = o.prefix + ".linkage.CpG.tsv";
-    FILE* f = fopen(path.c_str(), "w");
-    if (!f) { fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str()); return false; }
+    OutFile out = open_out(o.prefix + ".linkage.CpG.tsv");
+    if (!out) return false;
+    FILE* f = out.get();
     fprintf(f, "#dist\tn\tn_uu\tn_um\tn_mu\tn_mm\tconcordance\tr\n");
     for (int64_t i = 0; i < n; ++i) {
         const hm_linkage_t& r = rows[(size_t)i];
@@ -278,7 +279,7 @@ bool write_linkage(hm_pileup_t* pe, const PileupOptions& o) {
         fprintf(f, "%u\t%llu\t%llu\t%llu\t%llu\t%llu\t%.6g\t%.6g\n", r.dist, (unsigned long long)(r.n_uu + r.n_um + r.n_mu + r.n_mm),
                 (unsigned long long)r.n_uu, (unsigned long long)r.n_um, (unsigned long long)r.n_mu, (unsigned long long)r.n_mm, st[0], st[1]);
     }
-    return fclose(f) == 0;
+    return fclose(out.release()) == 0;
 }
 
 // <prefix>.readpos.tsv: the header, then one row per context and bin with at least -y calls; percent as cov.bed's fourth column,
@@ -288,20 +289,19 @@ bool write_readpos(hm_pileup_t* pe, const PileupOptions& o) {
     std::vector<hm_readpos_t> rows(3 * (2 * (size_t)o.profile + 1));
     const int64_t n = hm_pileup_fetch_readpos(pe, o.profile_min_calls, rows.data(), (int64_t)rows.size());
     if (n < 0) return false;
-    const std::string path = o.prefix + ".readpos.tsv";
-    FILE* f = fopen(path.c_str(), "w");
-    if (!f) { fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str()); return false; }
-    static const char* const ctx[3] = {"CpG", "CHG", "CHH"};
+    OutFile out = open_out(o.prefix + ".readpos.tsv");
+    if (!out) return false;
+    FILE* f = out.get();
     static const char* const end[3] = {"5p", "3p", "interior"};
     fprintf(f, "#context\tend\tdist\tn\tn_m\tn_u\tpercent\tmean_ml\n");
     for (int64_t i = 0; i < n; ++i) {
         const hm_readpos_t& r = rows[(size_t)i];
         double st[2] = {NAN, NAN};
         hm_readpos_stats(&r, st);
-        fprintf(f, "%s\t%s\t%u\t%llu\t%llu\t%llu\t%g\t%.6g\n", ctx[r.motif % 3], end[r.end % 3], r.dist, (unsigned long long)(r.n_m + r.n_u),
+        fprintf(f, "%s\t%s\t%u\t%llu\t%llu\t%llu\t%g\t%.6g\n", CTX_NAME[r.motif % 3], end[r.end % 3], r.dist, (unsigned long long)(r.n_m + r.n_u),
                 (unsigned long long)r.n_m, (unsigned long long)r.n_u, st[0], st[1]);
     }
-    return fclose(f) == 0;
+    return fclose(out.release()) == 0;
 }
 
 // -R: the intervals of a BED file in input order, in sequence coordinates
@@ -480,10 +480,9 @@ bool write_domains(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, con
 // sums of all sequences (hm_pileup_domain_sums: no segment is built), then hm_domain_refit and the stop rule.  1 done, -1 engine
 // error (hm_pileup_last_error), 0 another error (message printed).
 int fit_domains(hm_pileup_t* pe, const Fasta& fa, PileupOptions& o, int64_t A[3], int64_t B[3], int64_t S) {
-    static const char* cn[3] = {"CpG", "CHG", "CHH"};
-    const std::string path = o.prefix + ".domains.fit.tsv";
-    FILE* f = fopen(path.c_str(), "w");
-    if (!f) { fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str()); return 0; }
+    const OutFile out = open_out(o.prefix + ".domains.fit.tsv");
+    if (!out) return 0;
+    FILE* f = out.get();
     struct Iter { double lo, hi; int64_t A, B; };
     for (int c = 0; c < 3; ++c) {
         if (std::isnan(o.domain_lo[c])) continue;
@@ -496,17 +495,17 @@ int fit_domains(hm_pileup_t* pe, const Fasta& fa, PileupOptions& o, int64_t A[3]
                 int64_t one[6];
                 const int64_t lo = off, hi = off + fa.length[s];
                 off = hi;
-                if (hm_pileup_domain_sums(pe, nullptr, nullptr, nullptr, 0, lo, hi, c, cur.A, cur.B, S, o.domain_max_gap, one) < 0) { fclose(f); return -1; }
+                if (hm_pileup_domain_sums(pe, nullptr, nullptr, nullptr, 0, lo, hi, c, cur.A, cur.B, S, o.domain_max_gap, one) < 0) return -1;
                 for (int k = 0; k < 6; ++k) sums[k] += one[k];
             }
-            fprintf(f, "%s\t%zu\t%.17g\t%.17g\t%lld\t%lld", cn[c], seen.size(), cur.lo, cur.hi, (long long)cur.A, (long long)cur.B);
+            fprintf(f, "%s\t%zu\t%.17g\t%.17g\t%lld\t%lld", CTX_NAME[c], seen.size(), cur.lo, cur.hi, (long long)cur.A, (long long)cur.B);
             for (int k = 0; k < 6; ++k) fprintf(f, "\t%lld", (long long)sums[k]);
             fputc('\n', f);
             seen.push_back(cur);
             Iter next = cur;
             int64_t s_unused = 0;
             const int rc = hm_domain_refit(sums, o.domain_penalty, &next.lo, &next.hi);
-            if (rc != HM_OK && rc != HM_EDATA) { fclose(f); fprintf(stderr, "ERROR: hm_domain_refit failed\n"); return 0; }
+            if (rc != HM_OK && rc != HM_EDATA) { fprintf(stderr, "ERROR: hm_domain_refit failed\n"); return 0; }
             if (rc == HM_EDATA) { status = sums[2] == 0 || sums[5] == 0 ? "one_state" : "degenerate"; break; }
             if (hm_domain_scores(next.lo, next.hi, o.domain_penalty, &next.A, &next.B, &s_unused) != HM_OK) { status = "degenerate"; break; }
             const auto same = [&](const Iter& x) { return x.A == next.A && x.B == next.B; };
@@ -522,19 +521,17 @@ int fit_domains(hm_pileup_t* pe, const Fasta& fa, PileupOptions& o, int64_t A[3]
                 result = next;
             } else result = cur = next;
         }
-        fprintf(f, "%s\t%s\t%.17g\t%.17g\n", cn[c], status, result.lo, result.hi);
-        fprintf(stderr, "domains: %s levels fitted in %zu iteration%s (%s): %.17g:%.17g\n", cn[c], seen.size(), seen.size() == 1 ? "" : "s", status,
+        fprintf(f, "%s\t%s\t%.17g\t%.17g\n", CTX_NAME[c], status, result.lo, result.hi);
+        fprintf(stderr, "domains: %s levels fitted in %zu iteration%s (%s): %.17g:%.17g\n", CTX_NAME[c], seen.size(), seen.size() == 1 ? "" : "s", status,
                 result.lo, result.hi);
         o.domain_lo[c] = result.lo;
         o.domain_hi[c] = result.hi;
         int64_t s_again = 0;
         if (hm_domain_scores(result.lo, result.hi, o.domain_penalty, &A[c], &B[c], &s_again) != HM_OK) {
-            fclose(f);
-            fprintf(stderr, "ERROR: the fitted %s levels are no valid pair\n", cn[c]);
+            fprintf(stderr, "ERROR: the fitted %s levels are no valid pair\n", CTX_NAME[c]);
             return 0;
         }
     }
-    fclose(f);
     return 1;
 }
 
@@ -543,7 +540,6 @@ int fit_domains(hm_pileup_t* pe, const Fasta& fa, PileupOptions& o, int64_t A[3]
 // and <prefix>.asm.summary.tsv from the table's weights.  1 done, -1 engine error (hm_pileup_last_error), 0 another error (message
 // printed).
 int write_asm_q(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, const std::string& tag, FILE* out[3], int threads) {
-    static const char* cn[3] = {"CpG", "CHG", "CHH"};
     int64_t n_loci = 0;
     for (size_t s = 0; s < fa.names.size(); ++s) n_loci += fa.length[s];
     const int min_cov = o.asm_min_cov;
@@ -587,12 +583,10 @@ int write_asm_q(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, const 
     };
     for (const hm_asm_bin_t& t : tab) tally(t.bin / (HM_ASM_PAIRS * HM_ASM_PAIRS), t.count, t.qvalue);
     for (size_t i = 0; i < big.size(); ++i) tally(std::min(big[i].motif, 2u), 1, big_q[i]);
-    const std::string path = o.prefix + "." + tag + ".summary.tsv";
-    FILE* f = fopen(path.c_str(), "w");
-    if (!f) { fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str()); return 0; }
+    const OutFile f = open_out(o.prefix + "." + tag + ".summary.tsv");
+    if (!f) return 0;
     for (int c = 0; c < 3; ++c)
-        fprintf(f, "%s\t%llu\t%llu\t%llu\n", cn[c], (unsigned long long)m[c], (unsigned long long)below[c][0], (unsigned long long)below[c][1]);
-    fclose(f);
+        fprintf(f.get(), "%s\t%llu\t%llu\t%llu\n", CTX_NAME[c], (unsigned long long)m[c], (unsigned long long)below[c][0], (unsigned long long)below[c][1]);
     return 1;
 }
 
@@ -741,7 +735,6 @@ bool fused_record_loop(const PileupOptions& o, BgzfReader& in, hm_pileup_t* pe, 
 // whole reference, the table, then the rows (40 B per row on the device and here), and
 // <prefix>.sites.rates.tsv.  1 done, -1 engine error (hm_pileup_last_error), 0 another error (message printed).
 int write_sites(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, int control_sid, int threads) {
-    static const char* cn[3] = {"CpG", "CHG", "CHH"};
     std::vector<int64_t> start(fa.names.size() + 1, 0);
     for (size_t s = 0; s < fa.names.size(); ++s) start[s + 1] = start[s] + fa.length[s];
     uint64_t sums[6] = {0, 0, 0, 0, 0, 0};
@@ -751,8 +744,8 @@ int write_sites(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, int co
         for (int c = 0; c < 3; ++c) rates[c] = sums[c] + sums[3 + c] ? (double)sums[c] / (double)(sums[c] + sums[3 + c]) : std::nan("");
     }
     for (int c = 0; c < 3; ++c) {
-        if (std::isnan(rates[c])) fprintf(stderr, "WARNING: %s is not tested: %s\n", cn[c], control_sid >= 0 ? "the control sequence has no calls in this context" : "its rate is nan");
-        else fprintf(stderr, "%s false-positive rate: %.17g\n", cn[c], rates[c]);
+        if (std::isnan(rates[c])) fprintf(stderr, "WARNING: %s is not tested: %s\n", CTX_NAME[c], control_sid >= 0 ? "the control sequence has no calls in this context" : "its rate is nan");
+        else fprintf(stderr, "%s false-positive rate: %.17g\n", CTX_NAME[c], rates[c]);
     }
     std::vector<uint64_t> bins((size_t)HM_SITE_BINS, 0);
     std::vector<hm_locus_t> big;
@@ -785,18 +778,13 @@ int write_sites(hm_pileup_t* pe, const Fasta& fa, const PileupOptions& o, int co
                             r.pvalue, r.qvalue);
         });
     if (!ok) return -1;
-    const std::string path = o.prefix + ".sites.rates.tsv";
-    FILE* f = fopen(path.c_str(), "w");
-    if (!f) {
-        fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str());
-        return 0;
-    }
+    const OutFile f = open_out(o.prefix + ".sites.rates.tsv");
+    if (!f) return 0;
     for (int c = 0; c < 3; ++c) {
         char rate[64] = "nan";
         if (!std::isnan(rates[c])) snprintf(rate, sizeof rate, "%.17g", rates[c]);
-        fprintf(f, "%s\t%llu\t%llu\t%s\t%llu\n", cn[c], (unsigned long long)sums[c], (unsigned long long)sums[3 + c], rate, (unsigned long long)m[c]);
+        fprintf(f.get(), "%s\t%llu\t%llu\t%s\t%llu\n", CTX_NAME[c], (unsigned long long)sums[c], (unsigned long long)sums[3 + c], rate, (unsigned long long)m[c]);
     }
-    fclose(f);
     return 1;
 }
 
@@ -857,19 +845,16 @@ int write_outputs(hm_pileup_t* pe, const Fasta& fa, PileupOptions& o, const Inte
         if (!write_domains(pe, fa, o, o.dom_A, o.dom_B, o.dom_S, out.f)) return engine_error(pe, "domains");
     }
     if (o.patterns) {
-        FILE* out[3] = {fopen((o.prefix + ".patterns.CpG.bed").c_str(), "w"), nullptr, nullptr};
-        if (!out[0]) { fprintf(stderr, "ERROR: cannot open %s.patterns.CpG.bed for writing\n", o.prefix.c_str()); return EXIT_FAILURE; }
-        const bool ok = write_patterns(pe, fa, o, out);
-        fclose(out[0]);
-        if (!ok) return engine_error(pe, "patterns");
+        const OutFile f = open_out(o.prefix + ".patterns.CpG.bed");
+        if (!f) return EXIT_FAILURE;
+        FILE* out[3] = {f.get(), nullptr, nullptr};
+        if (!write_patterns(pe, fa, o, out)) return engine_error(pe, "patterns");
     }
     for (int part = 0; o.bedmethyl && part <= (o.haplotypes ? 2 : 0); ++part) {
-        const std::string path = o.prefix + (part ? ".hap" + std::to_string(part) : std::string()) + ".bedmethyl.CpG.bed";
-        FILE* out[3] = {fopen(path.c_str(), "w"), nullptr, nullptr};
-        if (!out[0]) { fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str()); return EXIT_FAILURE; }
-        const bool ok = write_bedmethyl(pe, fa, o, part, out);
-        fclose(out[0]);
-        if (!ok) return engine_error(pe, "bedmethyl");
+        const OutFile f = open_out(o.prefix + (part ? ".hap" + std::to_string(part) : std::string()) + ".bedmethyl.CpG.bed");
+        if (!f) return EXIT_FAILURE;
+        FILE* out[3] = {f.get(), nullptr, nullptr};
+        if (!write_bedmethyl(pe, fa, o, part, out)) return engine_error(pe, "bedmethyl");
     }
     if (o.linkage && !write_linkage(pe, o)) return engine_error(pe, "linkage");
     if (o.profile && !write_readpos(pe, o)) return engine_error(pe, "readpos");
@@ -1122,7 +1107,7 @@ double secs(clk::time_point a, clk::time_point b) { return std::chrono::duration
 // engine exists: a job without input needs neither.
 struct CovJob {
     std::vector<std::string> files[3];  // per context the file of every sample, in the order of `samples`; empty: context skipped
-    int n_ctx = 0;
+    int n_ctx = 0, threads = 1;  // -t
     Fasta fa;
     std::vector<int64_t> seq_start;
     std::unique_ptr<hm_pileup_t, decltype(&hm_pileup_destroy)> engine{nullptr, hm_pileup_destroy};  // destroyed on every way out
@@ -1242,19 +1227,19 @@ std::string find_cov_bed(const std::string& prefix, const char* ctx) {
 // as `what` -- and then the reference.  -> 0, or the exit status behind a message.
 int open_cov_job(const PileupOptions& o, const std::vector<std::string>& samples, const char* whose, const char* what,
                  std::initializer_list<std::pair<const char*, double>> options, CovJob& job) {
-    static const char* cn[3] = {"CpG", "CHG", "CHH"};
     for (int c = 0; c < 3; ++c) {
         bool all = true;
         for (const std::string& s : samples) {
-            job.files[c].push_back(find_cov_bed(s, cn[c]));
+            job.files[c].push_back(find_cov_bed(s, CTX_NAME[c]));
             if (!job.files[c].back().empty()) continue;
-            fprintf(stderr, "Skip context %s: %s.%s.cov.bed is missing\n", cn[c], s.c_str(), cn[c]);
+            fprintf(stderr, "Skip context %s: %s.%s.cov.bed is missing\n", CTX_NAME[c], s.c_str(), CTX_NAME[c]);
             all = false;
         }
         if (all) ++job.n_ctx;
         else job.files[c].clear();
     }
     if (!job.n_ctx) { fprintf(stderr, "ERROR: no context has a cov.bed file of %s\n", whose); return EXIT_FAILURE; }
+    job.threads = o.threads;
     Fasta& fa = job.fa;
     std::string err;
     if (!load_fasta(o.ref, fa, err)) { fprintf(stderr, "ERROR: %s\n", err.c_str()); return EXIT_FAILURE; }
@@ -1269,6 +1254,76 @@ int open_cov_job(const PileupOptions& o, const std::vector<std::string>& samples
     for (const auto& opt : options)
         if (hm_pileup_set_option(pe, opt.first, opt.second) != HM_OK) return engine_error(pe, what);
     if (hm_pileup_set_reference(pe, (int32_t)fa.names.size(), fa.length.data(), fa.bases.data()) != HM_OK) return engine_error(pe, "reference");
+    return 0;
+}
+
+std::vector<std::string> split_list(const std::string& text) {
+    std::vector<std::string> items(1);
+    for (const char c : text) {
+        if (c == ',') items.emplace_back();
+        else items.back() += c;
+    }
+    return items;
+}
+
+// The samples of `samplecorr` (one comma list) or of `groupdiff` and `regiondiff` (one list per group): every element a prefix as
+// `diff` takes it.  The checks print their message and answer false; each command runs them where it always has.
+struct SampleSet {
+    std::vector<std::string> group[2];  // the lists as given; group[1] stays empty for one list
+    std::vector<std::string> sample;    // the files of a context: group 1's samples, then group 2's
+    std::vector<uint8_t> member;        // the group of every sample, 1 or 2
+    const int lists;
+    SampleSet(const char* list1, const char* list2 = nullptr) : lists(list2 ? 2 : 1) {
+        for (int g = 0; g < lists; ++g) {
+            group[g] = split_list(g ? list2 : list1);
+            sample.insert(sample.end(), group[g].begin(), group[g].end());
+            member.insert(member.end(), group[g].size(), (uint8_t)(g + 1));
+        }
+    }
+    // at least `min` and at most HM_SAMPLE_MAX samples in all, else the message and the command's usage
+    bool count_fits(Command cmd, const char* command, size_t min, const char* argv0) const {
+        if (sample.size() >= min && sample.size() <= HM_SAMPLE_MAX) return true;
+        fprintf(stderr, lists == 2 ? "ERROR: %s takes 2 to %d samples in all, the lists name %zu\n" : "ERROR: %s takes 2 to %d samples, the list names %zu\n",
+                command, HM_SAMPLE_MAX, sample.size());
+        command_usage(cmd, argv0);
+        return false;
+    }
+    // list by list: no empty prefix, at least min_reps samples (-r), at most max_group (0: any number)
+    bool lists_fit(long long min_reps, size_t max_group) const {
+        for (int g = 0; g < lists; ++g) {
+            for (const std::string& s : group[g]) {
+                if (!s.empty()) continue;
+                if (lists == 2) fprintf(stderr, "ERROR: an empty prefix in the list of group %d\n", g + 1);
+                else fprintf(stderr, "ERROR: an empty prefix in the list of samples\n");
+                return false;
+            }
+            if ((long long)group[g].size() < min_reps) {
+                fprintf(stderr, "ERROR: group %d has %zu samples, fewer than -r %lld\n", g + 1, group[g].size(), min_reps);
+                return false;
+            }
+            if (max_group && group[g].size() > max_group) { fprintf(stderr, "ERROR: group %d has more than %zu samples\n", g + 1, max_group); return false; }
+        }
+        return true;
+    }
+    void echo() const {
+        for (int g = 0; g < lists; ++g)
+            for (size_t i = 0; i < group[g].size(); ++i) {
+                if (lists == 2) fprintf(stderr, "group %d ", g + 1);
+                fprintf(stderr, "sample %zu: %s.<ctx>.cov.bed\n", i + 1, group[g][i].c_str());
+            }
+    }
+};
+
+// Every sample of the set in turn: open_sample(i) announces it to the engine (0, or the exit status behind its message), then the
+// files of its contexts go through `load`, their rows counted in n_rows_of(i).  A sample's contexts share its plane or seen
+// bitmap: one locus, one context.  -> 0, or the exit status behind a message.
+int load_samples(const CovJob& job, const SampleSet& set, const std::function<int(size_t)>& open_sample, const LoadCall& load,
+                 const std::function<uint64_t&(size_t)>& n_rows_of) {
+    for (size_t i = 0; i < set.sample.size(); ++i) {
+        if (const int failed = open_sample(i)) return failed;
+        for (int c = 0; c < 3; ++c)
+            if (!job.files[c].empty() && !load_cov_bed(job, job.files[c][i], load, (uint32_t)c, job.threads, n_rows_of(i))) return EXIT_FAILURE;
+    }
     return 0;
 }
 
@@ -1322,59 +1377,35 @@ struct GroupQRow {  // what write_rows formats: the row and its q, named by gpos
     const hm_group_t* g;
     double q;
 };
-
-std::vector<std::string> split_list(const std::string& text) {
-    std::vector<std::string> items(1);
-    for (const char c : text) {
-        if (c == ',') items.emplace_back();
-        else items.back() += c;
-    }
-    return items;
-}
 }  // namespace
 
 int cmd_groupdiff(int argc, char** argv) {
-    static const char* cn[3] = {"CpG", "CHG", "CHH"};
     PileupOptions o;
     int first = 0, status = 0;
     if (!parse_command_line(CMD_GROUPDIFF, argc, argv, o, first, status)) return status;
     o.ref = argv[first];
-    const std::vector<std::string> group[2] = {split_list(argv[first + 1]), split_list(argv[first + 2])};
+    const SampleSet set(argv[first + 1], argv[first + 2]);
     o.prefix = argv[first + 3];
     fprintf(stderr, "\n\n====================> Parameters:\nCPU threads: %d\nGenomic reference: %s\n", o.threads, o.ref.c_str());
-    for (int g = 0; g < 2; ++g)
-        for (size_t i = 0; i < group[g].size(); ++i) fprintf(stderr, "group %d sample %zu: %s.<ctx>.cov.bed\n", g + 1, i + 1, group[g][i].c_str());
+    set.echo();
     fprintf(stderr, "output prefix: %s\ngroupdiff: min sample coverage %lld, min replicates per group %lld -> %s.groups.*\n\n\n", o.prefix.c_str(),
             o.group_min_cov, o.group_min_reps, o.prefix.c_str());
 
     const auto t_start = clk::now();
-    for (int g = 0; g < 2; ++g) {
-        for (const std::string& s : group[g])
-            if (s.empty()) { fprintf(stderr, "ERROR: an empty prefix in the list of group %d\n", g + 1); return EXIT_FAILURE; }
-        if ((long long)group[g].size() < o.group_min_reps) {
-            fprintf(stderr, "ERROR: group %d has %zu samples, fewer than -r %lld\n", g + 1, group[g].size(), o.group_min_reps);
-            return EXIT_FAILURE;
-        }
-        if (group[g].size() > 255) { fprintf(stderr, "ERROR: group %d has more than 255 samples\n", g + 1); return EXIT_FAILURE; }
-    }
-    std::vector<std::string> sample = group[0];  // the files of a context: group 1's samples, then group 2's
-    sample.insert(sample.end(), group[1].begin(), group[1].end());
+    if (!set.lists_fit(o.group_min_reps, 255)) return EXIT_FAILURE;
     CovJob job;
-    if (const int failed = open_cov_job(o, sample, "every sample", "groups",
+    if (const int failed = open_cov_job(o, set.sample, "every sample", "groups",
                                         {{"partitions", 2}, {"groups", 1}, {"group_min_cov", (double)o.group_min_cov}}, job))
         return failed;
     hm_pileup_t* pe = job.engine.get();
     const Fasta& fa = job.fa;
     const std::vector<int64_t>& seq_start = job.seq_start;
     auto die = [&](const std::string& what) { return engine_error(pe, what); };
-    const LoadCall load = [&](const hm_locus_t* rows, int64_t n) { return hm_pileup_load_sample_loci(pe, rows, n); };
     uint64_t n_rows[2] = {0, 0};
-    for (size_t i = 0; i < sample.size(); ++i) {  // a sample's contexts share its seen bitmap: one locus, one context
-        const int g = i < group[0].size() ? 0 : 1;
-        if (hm_pileup_group_sample(pe, g + 1) < 0) return die("group sample");
-        for (int c = 0; c < 3; ++c)
-            if (!job.files[c].empty() && !load_cov_bed(job, job.files[c][i], load, (uint32_t)c, o.threads, n_rows[g])) return EXIT_FAILURE;
-    }
+    if (const int failed = load_samples(
+            job, set, [&](size_t i) { return hm_pileup_group_sample(pe, set.member[i]) < 0 ? die("group sample") : 0; },
+            [&](const hm_locus_t* rows, int64_t n) { return hm_pileup_load_sample_loci(pe, rows, n); }, [&](size_t i) -> uint64_t& { return n_rows[set.member[i] - 1]; }))
+        return failed;
     const auto t_load = clk::now();
 
     std::vector<hm_group_t> rows;
@@ -1418,15 +1449,13 @@ int cmd_groupdiff(int argc, char** argv) {
         tally[c][1] += q[i] <= 0.01;
         tally[c][2] += rows[i].phi > 1.0;
     }
-    const std::string path = o.prefix + ".groups.summary.tsv";
-    FILE* f = fopen(path.c_str(), "w");
-    if (!f) { fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str()); return EXIT_FAILURE; }
+    const OutFile f = open_out(o.prefix + ".groups.summary.tsv");
+    if (!f) return EXIT_FAILURE;
     for (int c = 0; c < 3; ++c)
-        fprintf(f, "%s\t%llu\t%llu\t%llu\t%llu\n", cn[c], (unsigned long long)m[c], (unsigned long long)tally[c][0], (unsigned long long)tally[c][1],
+        fprintf(f.get(), "%s\t%llu\t%llu\t%llu\t%llu\n", CTX_NAME[c], (unsigned long long)m[c], (unsigned long long)tally[c][0], (unsigned long long)tally[c][1],
                 (unsigned long long)tally[c][2]);
-    fclose(f);
     fprintf(stderr, "## %zu + %zu samples, %llu + %llu counting loci of %d contexts, %zu tested in %.2f s: parse + load %.2f s; test + BED %.2f s\n",
-            group[0].size(), group[1].size(), (unsigned long long)n_rows[0], (unsigned long long)n_rows[1], job.n_ctx, rows.size(), secs(t_start, clk::now()),
+            set.group[0].size(), set.group[1].size(), (unsigned long long)n_rows[0], (unsigned long long)n_rows[1], job.n_ctx, rows.size(), secs(t_start, clk::now()),
             secs(t_start, t_load), secs(t_load, clk::now()));
     return 0;
 }
@@ -1436,23 +1465,17 @@ int cmd_groupdiff(int argc, char** argv) {
 // into its own level plane (hm_sample_open, hm_sample_load), and one fetch over the whole reference gives the exact
 // integer sums of every pair (hm_sample_fetch_sums), from which hm_sample_corr makes r and the means.
 int cmd_samplecorr(int argc, char** argv) {
-    static const char* cn[3] = {"CpG", "CHG", "CHH"};
     PileupOptions o;
     int first = 0, status = 0;
     if (!parse_command_line(CMD_SAMPLECORR, argc, argv, o, first, status)) return status;
     o.ref = argv[first];
-    const std::vector<std::string> sample = split_list(argv[first + 1]);
+    const SampleSet set(argv[first + 1]);
+    const std::vector<std::string>& sample = set.sample;
     o.prefix = argv[first + 2];
     const int N = (int)sample.size();
-    if (sample.size() < 2 || sample.size() > HM_SAMPLE_MAX) {  // before any file is opened
-        fprintf(stderr, "ERROR: samplecorr takes 2 to %d samples, the list names %zu\n", HM_SAMPLE_MAX, sample.size());
-        command_usage(CMD_SAMPLECORR, argv[0]);
-        return EXIT_FAILURE;
-    }
-    for (const std::string& s : sample)
-        if (s.empty()) { fprintf(stderr, "ERROR: an empty prefix in the list of samples\n"); return EXIT_FAILURE; }
+    if (!set.count_fits(CMD_SAMPLECORR, "samplecorr", 2, argv[0]) || !set.lists_fit(0, 0)) return EXIT_FAILURE;  // before any file is opened
     fprintf(stderr, "\n\n====================> Parameters:\nCPU threads: %d\nGenomic reference: %s\n", o.threads, o.ref.c_str());
-    for (int i = 0; i < N; ++i) fprintf(stderr, "sample %d: %s.<ctx>.cov.bed\n", i + 1, sample[(size_t)i].c_str());
+    set.echo();
     fprintf(stderr, "output prefix: %s\nsamplecorr: min sample coverage %lld, %s -> %s.samplecorr.*\n\n\n", o.prefix.c_str(), o.sample_min_cov,
             o.sample_complete ? "loci where all samples count" : "loci where both samples of a pair count", o.prefix.c_str());
 
@@ -1462,13 +1485,11 @@ int cmd_samplecorr(int argc, char** argv) {
         return failed;
     hm_pileup_t* pe = job.engine.get();
     auto die = [&](const std::string& what) { return engine_error(pe, what); };
-    const LoadCall load = [&](const hm_locus_t* rows, int64_t n) { return hm_sample_load(pe, rows, n); };
     uint64_t n_rows = 0;
-    for (int i = 0; i < N; ++i) {  // a sample's contexts share its plane: one locus, one context
-        if (hm_sample_open(pe) < 0) return die("sample");
-        for (int c = 0; c < 3; ++c)
-            if (!job.files[c].empty() && !load_cov_bed(job, job.files[c][(size_t)i], load, (uint32_t)c, o.threads, n_rows)) return EXIT_FAILURE;
-    }
+    if (const int failed = load_samples(
+            job, set, [&](size_t) { return hm_sample_open(pe) < 0 ? die("sample") : 0; },
+            [&](const hm_locus_t* rows, int64_t n) { return hm_sample_load(pe, rows, n); }, [&](size_t) -> uint64_t& { return n_rows; }))
+        return failed;
     const auto t_load = clk::now();
 
     // the samples file always reports a sample's own counting loci: the diagonal of the pairwise sums
@@ -1489,29 +1510,26 @@ int cmd_samplecorr(int argc, char** argv) {
     }
     // entry of context c and pair i <= j: context-major, then i, then j
     const auto at = [&](int c, int i, int j) { return (size_t)c * pairs + (size_t)i * (size_t)N - (size_t)i * (size_t)(i - 1) / 2 + (size_t)(j - i); };
-    const auto open_out = [&](const std::string& path) {
-        FILE* f = fopen(path.c_str(), "w");
-        if (!f) fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str());
-        return f;
-    };
-    FILE* fs = open_out(o.prefix + ".samplecorr.samples.tsv");
-    if (!fs) return EXIT_FAILURE;
+    const OutFile samples_file = open_out(o.prefix + ".samplecorr.samples.tsv");
+    if (!samples_file) return EXIT_FAILURE;
+    FILE* fs = samples_file.get();
     fprintf(fs, "ctx\tsample\tn\tmean\n");
     for (int c = 0; c < 3; ++c) {
         if (job.files[c].empty()) continue;
         for (int i = 0; i < N; ++i)
-            fprintf(fs, "%s\t%s\t%llu\t%.6g\n", cn[c], sample[(size_t)i].c_str(), (unsigned long long)own[at(c, i, i)].n, own_mean[at(c, i, i)]);
-        FILE* f = open_out(o.prefix + ".samplecorr." + cn[c] + ".tsv");
-        if (!f) { fclose(fs); return EXIT_FAILURE; }
+            fprintf(fs, "%s\t%s\t%llu\t%.6g\n", CTX_NAME[c], sample[(size_t)i].c_str(), (unsigned long long)own[at(c, i, i)].n, own_mean[at(c, i, i)]);
+        OutFile table = open_out(o.prefix + ".samplecorr." + CTX_NAME[c] + ".tsv");
+        if (!table) return EXIT_FAILURE;
+        FILE* f = table.get();
         fprintf(f, "sample_i\tsample_j\tn\tmean_i\tmean_j\tr\n");
         for (int i = 0; i < N; ++i)
             for (int j = i + 1; j < N; ++j) {
                 const size_t k = at(c, i, j);
                 fprintf(f, "%s\t%s\t%llu\t%.6g\t%.6g\t%.6g\n", sample[(size_t)i].c_str(), sample[(size_t)j].c_str(), (unsigned long long)e[k].n, mi[k], mj[k], r[k]);
             }
-        fclose(f);
-        f = open_out(o.prefix + ".samplecorr." + cn[c] + ".matrix.tsv");
-        if (!f) { fclose(fs); return EXIT_FAILURE; }
+        table = open_out(o.prefix + ".samplecorr." + CTX_NAME[c] + ".matrix.tsv");
+        if (!table) return EXIT_FAILURE;
+        f = table.get();
         fprintf(f, "sample");
         for (const std::string& s : sample) fprintf(f, "\t%s", s.c_str());
         fputc('\n', f);
@@ -1520,9 +1538,7 @@ int cmd_samplecorr(int argc, char** argv) {
             for (int j = 0; j < N; ++j) fprintf(f, "\t%.6g", r[at(c, std::min(i, j), std::max(i, j))]);
             fputc('\n', f);
         }
-        fclose(f);
     }
-    fclose(fs);
     fprintf(stderr, "## %d samples, %llu rows of %d contexts in %.2f s: parse + load %.2f s; sums + tables %.2f s\n", N, (unsigned long long)n_rows, job.n_ctx,
             secs(t_start, clk::now()), secs(t_start, t_load), secs(t_load, clk::now()));
     return 0;
@@ -1544,41 +1560,23 @@ std::string g6(double v) {
 }  // namespace
 
 int cmd_regiondiff(int argc, char** argv) {
-    static const char* cn[3] = {"CpG", "CHG", "CHH"};
     PileupOptions o;
     int first = 0, status = 0;
     if (!parse_command_line(CMD_REGIONDIFF, argc, argv, o, first, status)) return status;
     o.ref = argv[first];
-    const std::vector<std::string> group[2] = {split_list(argv[first + 1]), split_list(argv[first + 2])};
+    const SampleSet set(argv[first + 1], argv[first + 2]);
     o.prefix = argv[first + 3];
-    const size_t N = group[0].size() + group[1].size();
-    if (N > HM_SAMPLE_MAX) {  // before any file is opened
-        fprintf(stderr, "ERROR: regiondiff takes 2 to %d samples in all, the lists name %zu\n", HM_SAMPLE_MAX, N);
-        command_usage(CMD_REGIONDIFF, argv[0]);
-        return EXIT_FAILURE;
-    }
-    for (int g = 0; g < 2; ++g) {
-        for (const std::string& s : group[g])
-            if (s.empty()) { fprintf(stderr, "ERROR: an empty prefix in the list of group %d\n", g + 1); return EXIT_FAILURE; }
-        if ((long long)group[g].size() < o.region_min_reps) {
-            fprintf(stderr, "ERROR: group %d has %zu samples, fewer than -r %lld\n", g + 1, group[g].size(), o.region_min_reps);
-            return EXIT_FAILURE;
-        }
-    }
+    const size_t N = set.sample.size();
+    if (!set.count_fits(CMD_REGIONDIFF, "regiondiff", 0, argv[0]) || !set.lists_fit(o.region_min_reps, 0)) return EXIT_FAILURE;  // before any file is opened
     fprintf(stderr, "\n\n====================> Parameters:\nCPU threads: %d\nGenomic reference: %s\nintervals: %s\n", o.threads, o.ref.c_str(), o.intervals.c_str());
-    for (int g = 0; g < 2; ++g)
-        for (size_t i = 0; i < group[g].size(); ++i) fprintf(stderr, "group %d sample %zu: %s.<ctx>.cov.bed\n", g + 1, i + 1, group[g][i].c_str());
+    set.echo();
     fprintf(stderr, "output prefix: %s\nregiondiff: min sample coverage %lld, min loci per sample %lld, min samples per group %lld, %s -> %s.regiondiff.*\n\n\n",
             o.prefix.c_str(), o.sample_min_cov, o.region_min_sample_loci, o.region_min_reps,
             o.sample_complete ? "loci where all samples count" : "loci where the sample counts", o.prefix.c_str());
 
     const auto t_start = clk::now();
-    std::vector<std::string> sample = group[0];  // the files of a context: group 1's samples, then group 2's
-    sample.insert(sample.end(), group[1].begin(), group[1].end());
-    std::vector<uint8_t> member(N, 2);
-    std::fill(member.begin(), member.begin() + (long)group[0].size(), (uint8_t)1);
     CovJob job;
-    if (const int failed = open_cov_job(o, sample, "every sample", "samples", {{"samples", (double)N}, {"sample_min_cov", (double)o.sample_min_cov}}, job))
+    if (const int failed = open_cov_job(o, set.sample, "every sample", "samples", {{"samples", (double)N}, {"sample_min_cov", (double)o.sample_min_cov}}, job))
         return failed;
     hm_pileup_t* pe = job.engine.get();
     const Fasta& fa = job.fa;
@@ -1591,13 +1589,11 @@ int cmd_regiondiff(int argc, char** argv) {
         start[i] = job.seq_start[(size_t)iv.sid[i]] + iv.start[i];
         end[i] = job.seq_start[(size_t)iv.sid[i]] + iv.end[i];
     }
-    const LoadCall load = [&](const hm_locus_t* rows, int64_t k) { return hm_sample_load(pe, rows, k); };
     uint64_t n_rows = 0;
-    for (size_t i = 0; i < N; ++i) {  // a sample's contexts share its plane: one locus, one context
-        if (hm_sample_open(pe) < 0) return die("sample");
-        for (int c = 0; c < 3; ++c)
-            if (!job.files[c].empty() && !load_cov_bed(job, job.files[c][i], load, (uint32_t)c, o.threads, n_rows)) return EXIT_FAILURE;
-    }
+    if (const int failed = load_samples(
+            job, set, [&](size_t) { return hm_sample_open(pe) < 0 ? die("sample") : 0; },
+            [&](const hm_locus_t* rows, int64_t k) { return hm_sample_load(pe, rows, k); }, [&](size_t) -> uint64_t& { return n_rows; }))
+        return failed;
     const auto t_load = clk::now();
 
     // the sums of a chunk of intervals wait on the host, 16 N bytes each: chunks of at most 512 MB whatever the file's length
@@ -1613,7 +1609,7 @@ int cmd_regiondiff(int argc, char** argv) {
             if (hm_sample_fetch_intervals(pe, 0, job.seq_start.back(), c, o.sample_complete ? 1 : 0, start.data() + a, end.data() + a, (int64_t)m,
                                           sums.data()) != (int64_t)(m * N))
                 return die("interval sums");
-            if (hm_sample_interval_test(sums.data(), (int64_t)m, (int32_t)N, member.data(), o.region_min_sample_loci, (int32_t)o.region_min_reps,
+            if (hm_sample_interval_test(sums.data(), (int64_t)m, (int32_t)N, set.member.data(), o.region_min_sample_loci, (int32_t)o.region_min_reps,
                                         tests[c].data() + a) != HM_OK) {
                 fprintf(stderr, "ERROR: regiondiff: hm_sample_interval_test refused the sums\n");
                 return EXIT_FAILURE;
@@ -1628,19 +1624,16 @@ int cmd_regiondiff(int argc, char** argv) {
         }
     }
     job.engine.reset();
-    const auto open_out = [&](const std::string& path) {
-        FILE* f = fopen(path.c_str(), "w");
-        if (!f) fprintf(stderr, "ERROR: cannot open %s for writing\n", path.c_str());
-        return f;
-    };
-    FILE* fs = open_out(o.prefix + ".regiondiff.summary.tsv");
-    if (!fs) return EXIT_FAILURE;
+    const OutFile summary = open_out(o.prefix + ".regiondiff.summary.tsv");
+    if (!summary) return EXIT_FAILURE;
+    FILE* fs = summary.get();
     fprintf(fs, "ctx\tintervals\ttested\tq<=0.05\tq<=0.01\n");
     size_t tested_all = 0;
     for (int c = 0; c < 3; ++c) {
         if (job.files[c].empty()) continue;
-        FILE* f = open_out(o.prefix + ".regiondiff." + cn[c] + ".tsv");
-        if (!f) { fclose(fs); return EXIT_FAILURE; }
+        const OutFile table = open_out(o.prefix + ".regiondiff." + CTX_NAME[c] + ".tsv");
+        if (!table) return EXIT_FAILURE;
+        FILE* f = table.get();
         fprintf(f, "#chrom\tstart\tend\tname\tstrand\tm1\tm2\tloci1\tloci2\tmean1\tmean2\tdiff\tt\tdf\tp\tq\n");
         unsigned long long tested = 0, q05 = 0, q01 = 0;
         for (size_t i = 0; i < n; ++i) {
@@ -1652,13 +1645,11 @@ int cmd_regiondiff(int argc, char** argv) {
             q05 += q[c][i] <= 0.05;
             q01 += q[c][i] <= 0.01;
         }
-        fclose(f);
-        fprintf(fs, "%s\t%zu\t%llu\t%llu\t%llu\n", cn[c], n, tested, q05, q01);
+        fprintf(fs, "%s\t%zu\t%llu\t%llu\t%llu\n", CTX_NAME[c], n, tested, q05, q01);
         tested_all += tested;
     }
-    fclose(fs);
     fprintf(stderr, "## %zu + %zu samples, %llu rows of %d contexts, %zu intervals, %zu tests in %.2f s: parse + load %.2f s; sums + tests + tables %.2f s\n",
-            group[0].size(), group[1].size(), (unsigned long long)n_rows, job.n_ctx, n, tested_all, secs(t_start, clk::now()), secs(t_start, t_load),
+            set.group[0].size(), set.group[1].size(), (unsigned long long)n_rows, job.n_ctx, n, tested_all, secs(t_start, clk::now()), secs(t_start, t_load),
             secs(t_load, clk::now()));
     return 0;
 }

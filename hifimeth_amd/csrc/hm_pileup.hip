@@ -53,12 +53,10 @@
 //                   path as two scans over a monoid (reduce per workgroup, one workgroup scans the aggregates, re-scan), segment
 //                   heads compacted, one thread per segment (domain_build_part_kernel); for the fit of the levels (`-D -Y`) the
 //                   rows' counters summed by state behind the two scans instead (domain_sums_kernel)
-//   region_block_sums / RegionScan / region_query / metaplot   sums over given intervals (`pileup -R`, `-J`): twelve sums per block of
-//                   HM_REGION_BLOCK loci, their scan by the row-scan skeleton above, then a wavefront per interval (or per bin and
-//                   stride of intervals) reads the index and sums the loci of its two partial blocks
-//   sample_block_sums / SampleIvScan / sample_query   the same over the N level planes of `samplecorr` (`regiondiff`): per block and
-//                   sample the counting loci and the sum of their levels, one scan over all samples' blocks, a wavefront per
-//                   interval; the M samples of 64 positions are reduced through a tile in LDS (sample_wave_add)
+//   block_split / *_block_sums / RegionScan, SampleIvScan / *_query / metaplot   sums over given intervals: the sums per block of
+//                   HM_REGION_BLOCK loci (twelve for `pileup -R`, `-J`; a pair per sample of the level planes for `regiondiff`), their
+//                   scan by the row-scan skeleton above, then a wavefront per interval (or per bin and stride of intervals) reads the
+//                   index and sums the loci of its two partial blocks (region_add over its lanes; sample_wave_add through LDS)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -673,22 +671,15 @@ __global__ __launch_bounds__(TPB) void sample_sums_kernel(const uint16_t* __rest
 }
 
 // ---- the sums of M samples over given intervals (hm_sample_fetch_intervals; include/hifimeth_hip.h has the definition) ----------
-// The shape of `pileup -R` carried over to M planes: per block of HM_REGION_BLOCK positions and sample the pair (n, su) of the
-// call's context and mode (sample_block_sums_kernel), their running sum (the row scan with SampleIvScan), then a wavefront per
-// interval that walks the loci of at most two partial blocks and takes the whole blocks between from two reads of the index.
-// The index is SAMPLE-major, idx[s * nblk + b], and scanned as ONE sequence of M * nblk pairs: a query only ever subtracts two
-// entries of one sample, so the running sum may run on from one sample into the next, and the scan's element stays one pair (a
-// row of 2 M = 128 values per block, as RegionScan keeps its twelve, would not fit the registers).
-//
-// The M-sample reduction (sample_wave_add) goes through LDS, in two phases per 64 consecutive positions.  Phase 1, lane =
-// position: the lane reads its key once and its M values once, plane after plane -- 64 consecutive uint16 of one plane per
-// wavefront load -- and writes each into row t of the wavefront's tile; a position of another context writes zeros.  The ballot
-// of "this position can add" (in complete mode: all M count) is the same 64-bit mask in every lane.  Phase 2, lane = (sample s,
-// part q): with P the power of two >= M and G = 64 / P, lane s * G + q reads the words q, q + G, ... of row s, two positions
-// each, and adds what counts to its own (n, su).  Rows are 32 + G words apart, so the 64 lanes of a read fall on the banks
-// lane + G * step: no conflict within either half of the wavefront.  The G parts of a sample are added once per interval (or
-// block), by log2 G shuffles.  Against a cross-lane sum per sample and chunk (12 M shuffle steps per chunk), the walk costs
-// 32 / G LDS reads per chunk whatever M is.  The two phases are ordered by wavefront-scope fences: the tile is the wavefront's own.
+// The interval skeleton (block_split here, the host side with `pileup -R / -J`) over M planes: per block and sample the pair (n, su)
+// of the call's context and mode.  The index is SAMPLE-major, idx[s * nblk + b], and scanned as ONE sequence of M * nblk pairs: a
+// query only ever subtracts two entries of one sample, so the running sum may run on from one sample into the next, and the
+// scan's element stays one pair (a row of 2 M = 128 values per block, as RegionScan keeps its twelve, would not fit the registers).
+// The M-sample reduction (sample_wave_add; DESIGN.md section 10 has the reasoning) goes through LDS, in two phases per 64
+// positions.  Phase 1, lane = position: the key once and the M values once, each into row t of the wavefront's tile (zeros for
+// another context); the ballot of "can add" is one mask in every lane.  Phase 2, lane = (sample s, part q): with P the power of
+// two >= M and G = 64 / P, lane s * G + q reads the words q, q + G, ... of row s, two positions each.  Rows are 32 + G words
+// apart: no bank conflict.  The phases are ordered by wavefront-scope fences: the tile is the wavefront's own.
 struct SampleIvPlanes {
     const uint16_t* planes;
     int64_t stride;
@@ -699,6 +690,17 @@ struct SampleIvPlanes {
     __host__ __device__ int pitch() const { return 32 + G; }  // words per tile row
 };
 using SamplePair = hm_sample_interval_t;
+
+// [a, b), lo <= a <= b, cut at the blocks of HM_REGION_BLOCK positions from lo (`pileup -R` and `regiondiff` both): the loci of
+// [a, head_end) and of [tail_begin, b) are summed one by one, the whole blocks between them, if row_last > row_first, are
+// prefix(row_last) - prefix(row_first) of the scanned index.  Within one block the head is [a, b) and the tail empty; a's
+// remainder runs to its block's end, so that nothing is ever subtracted from a partial sum.
+struct BlockSplit { int64_t head_end, tail_begin, row_first, row_last; };
+__device__ __forceinline__ BlockSplit block_split(int64_t lo, int64_t a, int64_t b) {
+    const int64_t ba = (a - lo) / HM_REGION_BLOCK, bb = (b - lo) / HM_REGION_BLOCK;
+    if (ba == bb) return BlockSplit{b, b, ba, ba};
+    return BlockSplit{lo + (ba + 1) * HM_REGION_BLOCK, lo + bb * HM_REGION_BLOCK, ba, bb - 1};
+}
 
 __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -788,9 +790,7 @@ struct SampleIvScan {
     __device__ __forceinline__ void store(int64_t j, const T& f) const { idx[j] = f; }
 };
 
-// out[i * M + s] = (n, su) of sample s over interval i clamped to [lo, hi): a wavefront per interval, over a grid stride.  Within
-// one block the loci of [a, b) themselves; else the loci from a to the end of a's block and from the start of b's block to b, and
-// for the whole blocks between them prefix(b's block - 1) - prefix(a's block) of the sample's own stretch of the index.
+// out[i * M + s] = (n, su) of sample s over interval i clamped to [lo, hi): a wavefront per interval, over a grid stride
 __global__ __launch_bounds__(TPB) void sample_query_kernel(SampleIvPlanes v, int64_t lo, int64_t hi, int64_t nblk, const SamplePair* __restrict__ idx,
                                                             const int64_t* __restrict__ start, const int64_t* __restrict__ end, int64_t n_iv,
                                                             SamplePair* __restrict__ out) {
@@ -801,17 +801,13 @@ __global__ __launch_bounds__(TPB) void sample_query_kernel(SampleIvPlanes v, int
     for (int64_t i = (int64_t)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6); i < n_iv; i += (int64_t)gridDim.x * (TPB / 64)) {
         const int64_t a = min(max(start[i], lo), hi), b = min(max(end[i], lo), hi);
         unsigned long long n = 0, su = 0;
-        if (a < b) {
-            const int64_t ba = (a - lo) / HM_REGION_BLOCK, bb = (b - lo) / HM_REGION_BLOCK;
-            sample_wave_add(v, tile, a, ba == bb ? b : lo + (ba + 1) * HM_REGION_BLOCK, n, su);
-            if (ba != bb) {
-                sample_wave_add(v, tile, lo + bb * HM_REGION_BLOCK, b, n, su);
-                if (owner && bb > ba + 1) {
-                    const SamplePair hiw = idx[(int64_t)s * nblk + bb - 1], low = idx[(int64_t)s * nblk + ba];
-                    n += hiw.n - low.n;
-                    su += hiw.su - low.su;
-                }
-            }
+        const BlockSplit sp = block_split(lo, a, b);
+        sample_wave_add(v, tile, a, sp.head_end, n, su);
+        if (sp.tail_begin < b) sample_wave_add(v, tile, sp.tail_begin, b, n, su);
+        if (owner && sp.row_last > sp.row_first) {  // the sample's own stretch of the index
+            const SamplePair hiw = idx[(int64_t)s * nblk + sp.row_last], low = idx[(int64_t)s * nblk + sp.row_first];
+            n += hiw.n - low.n;
+            su += hiw.su - low.su;
         }
         sample_parts_sum(v.G, n, su);
         if (owner) out[i * v.M + s] = SamplePair{n, su};
@@ -2195,8 +2191,7 @@ __global__ __launch_bounds__(TPB) void domain_sums_kernel(const DomRow* __restri
 // ---- sums over given intervals, metaplots (`pileup -R`, `pileup -J`; include/hifimeth_hip.h has the definition) ----------------
 // Twelve int64 quantities, k = 4 * context + {n_loci, pcov, ncov, ppm}: hm_region_sum_t[3] as one array.  The index of a range
 // [lo, hi) is idx[b * 12 + k] = the sum over the blocks 0 .. b of HM_REGION_BLOCK loci (region_block_sums_kernel, then the row scan
-// above in place with RegionScan: no workgroup waits for another).  A query is answered by ONE wavefront: the loci of at most two
-// partial blocks, strided over its lanes, and two reads of the index.
+// above in place with RegionScan: no workgroup waits for another).  ONE wavefront answers a query: block_split, its loci over the lanes.
 constexpr int REGION_LANES = 12;
 static_assert(HM_REGION_BLOCK >= TPB && (HM_REGION_BLOCK & (HM_REGION_BLOCK - 1)) == 0, "a block is a power of two of whole workgroup passes");
 static_assert(HM_REGION_SCAN_BLOCKS == SCAN_ROWS, "the header names the row scan's partition");
@@ -2247,10 +2242,20 @@ __device__ __forceinline__ int64_t wave_lane_totals(const RegionAcc& a, int64_t 
     return whole;
 }
 
+// ... and of the workgroup: thread k < REGION_LANES returns quantity k's total over all its wavefronts (the others 0)
+__device__ __forceinline__ int64_t block_lane_totals(const RegionAcc& a, int64_t whole) {
+    __shared__ int64_t part[TPB / 64][REGION_LANES];
+    const int64_t v = wave_lane_totals(a, whole);
+    if ((threadIdx.x & 63) < REGION_LANES) part[threadIdx.x >> 6][threadIdx.x & 63] = v;
+    __syncthreads();
+    int64_t t = 0;
+    for (int w = 0; threadIdx.x < REGION_LANES && w < TPB / 64; ++w) t += part[w][threadIdx.x];
+    return t;
+}
+
 // idx[blockIdx.x * 12 + k] = quantity k summed over block blockIdx.x of [lo, hi)
 __global__ __launch_bounds__(TPB) void region_block_sums_kernel(RangePlanes s, int64_t lo, int64_t hi, int64_t min_cov,
                                                                  int64_t* __restrict__ idx) {
-    __shared__ int64_t part[TPB / 64][REGION_LANES];
     const int64_t base = lo + (int64_t)blockIdx.x * HM_REGION_BLOCK;
     RegionAcc a{};
 #pragma unroll 4
@@ -2258,14 +2263,8 @@ __global__ __launch_bounds__(TPB) void region_block_sums_kernel(RangePlanes s, i
         const int64_t i = base + k * TPB + threadIdx.x;
         if (i < hi) region_add(s, min_cov, i, a);
     }
-    const int64_t v = wave_lane_totals(a, 0);
-    if ((threadIdx.x & 63) < REGION_LANES) part[threadIdx.x >> 6][threadIdx.x & 63] = v;
-    __syncthreads();
-    if (threadIdx.x < REGION_LANES) {
-        int64_t t = 0;
-        for (int w = 0; w < TPB / 64; ++w) t += part[w][threadIdx.x];
-        idx[(int64_t)blockIdx.x * REGION_LANES + threadIdx.x] = t;
-    }
+    const int64_t t = block_lane_totals(a, 0);
+    if (threadIdx.x < REGION_LANES) idx[(int64_t)blockIdx.x * REGION_LANES + threadIdx.x] = t;
 }
 
 // the block sums -> their inclusive scan, in place: an element is loaded and stored by the one thread that owns it
@@ -2303,18 +2302,14 @@ struct RegionIndex {  // of the planes' range [lo, hi) under min_cov
     const int64_t* idx;
 };
 
-// One wavefront adds the sums over [a, b), lo <= a <= b <= hi, both the same in all its lanes: the loci from a to the end of a's
-// block and from the start of b's block to b into the lanes' partial sums, the blocks between them from the index into `whole` of
-// lane k < 12 -- prefix(b) - prefix(a) with a's remainder taken to its block's end, so that nothing is subtracted.  Within one
-// block the loci of [a, b) themselves.
+// One wavefront adds the sums over [a, b), lo <= a <= b <= hi, both the same in all its lanes: the loci of block_split's head and
+// tail into the lanes' partial sums, its whole blocks from the index into `whole` of lane k < 12
 __device__ __forceinline__ void wave_range_add(const RegionIndex& ix, int64_t a, int64_t b, RegionAcc& acc, int64_t& whole) {
     const int lane = threadIdx.x & 63;
-    const int64_t ba = (a - ix.lo) / HM_REGION_BLOCK, bb = (b - ix.lo) / HM_REGION_BLOCK;
-    const int64_t head_end = ba == bb ? b : ix.lo + (ba + 1) * HM_REGION_BLOCK;
-    for (int64_t i = a + lane; i < head_end; i += 64) region_add(ix.s, ix.min_cov, i, acc);
-    if (ba == bb) return;
-    for (int64_t i = ix.lo + bb * HM_REGION_BLOCK + lane; i < b; i += 64) region_add(ix.s, ix.min_cov, i, acc);
-    if (lane < REGION_LANES && bb > ba + 1) whole += ix.idx[(bb - 1) * REGION_LANES + lane] - ix.idx[ba * REGION_LANES + lane];
+    const BlockSplit sp = block_split(ix.lo, a, b);
+    for (int64_t i = a + lane; i < sp.head_end; i += 64) region_add(ix.s, ix.min_cov, i, acc);
+    for (int64_t i = sp.tail_begin + lane; i < b; i += 64) region_add(ix.s, ix.min_cov, i, acc);
+    if (lane < REGION_LANES && sp.row_last > sp.row_first) whole += ix.idx[sp.row_last * REGION_LANES + lane] - ix.idx[sp.row_first * REGION_LANES + lane];
 }
 
 __device__ __forceinline__ int64_t clamp_to(int64_t x, int64_t lo, int64_t hi) { return min(max(x, lo), hi); }
@@ -2364,7 +2359,6 @@ __host__ __device__ inline void metabin_range(const MetaGeom& m, const MetaIv& r
 // intervals (blockIdx.y), then one reduction and at most twelve 64-bit atomics per workgroup.  Integers: exact in any order.
 __global__ __launch_bounds__(TPB) void metaplot_kernel(RegionIndex ix, int64_t plane_base, MetaGeom m, const MetaIv* __restrict__ iv,
                                                         int64_t n, unsigned long long* __restrict__ tab) {
-    __shared__ int64_t part[TPB / 64][REGION_LANES];
     RegionAcc acc{};
     int64_t whole = 0;
     for (int64_t i = (int64_t)blockIdx.y * (TPB / 64) + (threadIdx.x >> 6); i < n; i += (int64_t)gridDim.y * (TPB / 64)) {
@@ -2372,14 +2366,8 @@ __global__ __launch_bounds__(TPB) void metaplot_kernel(RegionIndex ix, int64_t p
         metabin_range(m, iv[i], (int)blockIdx.x, a, b);
         wave_range_add(ix, clamp_to(a - plane_base, ix.lo, ix.hi), clamp_to(b - plane_base, ix.lo, ix.hi), acc, whole);
     }
-    const int64_t v = wave_lane_totals(acc, whole);
-    if ((threadIdx.x & 63) < REGION_LANES) part[threadIdx.x >> 6][threadIdx.x & 63] = v;
-    __syncthreads();
-    if (threadIdx.x < REGION_LANES) {
-        int64_t t = 0;
-        for (int w = 0; w < TPB / 64; ++w) t += part[w][threadIdx.x];
-        if (t) atomicAdd(&tab[(int64_t)blockIdx.x * REGION_LANES + threadIdx.x], (unsigned long long)t);
-    }
+    const int64_t t = block_lane_totals(acc, whole);
+    if (t) atomicAdd(&tab[(int64_t)blockIdx.x * REGION_LANES + threadIdx.x], (unsigned long long)t);
 }
 
 // ---- methylation by the k-mer around the cytosine (`pileup -S`; include/hifimeth_hip.h has the definition) ----------------------
@@ -2545,9 +2533,9 @@ struct hm_pileup {
     int profile = 0;
     Trim trim{0, 0};
     DevBuf d_rphist{EXACT}, d_rptab{EXACT}, d_rpadd{EXACT};
-    // `pileup -R / -J`, allocated by the first call that needs them: the index of the range in hand (96 B per HM_REGION_BLOCK loci),
-    // the caller's intervals, and the sums per interval or the metaplot's table
-    DevBuf d_rgidx{EXACT}, d_rgiv{HALF}, d_rgout{HALF};
+    // the interval fetch in hand (`pileup -R / -J`, `regiondiff`), whichever ran last, allocated by the first: the index of its range
+    // (per HM_REGION_BLOCK loci 96 B, or 16 M B for M samples), the caller's intervals, the sums per interval or the metaplot's table
+    DevBuf d_ividx{EXACT}, d_iviv{HALF}, d_ivout{HALF};
     // `pileup -S`, allocated by the first hm_pileup_fetch_context: the table of the flank in hand (6 KB at flank 0, 25 MB at 3),
     // the sequence starts, and the device's CU count (0: not asked yet)
     DevBuf d_cxtab{EXACT}, d_cxoff{EXACT};
@@ -2574,9 +2562,6 @@ struct hm_pileup {
     int32_t sample_min_cov = 5;
     int64_t sample_stride = 0;
     DevBuf d_slevel{EXACT}, d_stable{EXACT};
-    // `regiondiff` (hm_sample_fetch_intervals), allocated by the first call: the index of the range, context and mode in hand
-    // (16 M B per HM_REGION_BLOCK positions), the caller's intervals, and the M pairs per interval
-    DevBuf d_sividx{EXACT}, d_siviv{HALF}, d_sivout{HALF};
     uint32_t thr_packed = 0;   // the three thresholds of the last hm_pileup_count
     bool counted = false;    // hm_pileup_count has run since hm_pileup_set_reference: what the -E, -M and -L fetches wait for
     int64_t n_recs = 0;
@@ -4430,29 +4415,64 @@ int64_t hm_pileup_fetch_sites(hm_pileup_t* p, const void* pcov, const void* ncov
 
 }  // extern "C"
 
-// ---- `pileup -R / -J` ------------------------------------------------------------------------------------------------------------
+// ---- the interval fetches: `pileup -R / -J` and, further down, `regiondiff` ---------------------------------------------------------
+// One skeleton: check the intervals, stage them, build the index (the block sums, then their scan), one query kernel, the sums
+// back.  A fetch plugs in its scan (RegionScan, SampleIvScan), its two kernels and its own argument checks.
 namespace {
 
-// the index of the non-empty [lo, hi) of the planes `s` under min_cov, in d_rgidx: the block sums, then their scan; under the
-// caller's guard
-RegionIndex build_region_index(hm_pileup* p, const RangePlanes& s, int64_t lo, int64_t hi, int64_t min_cov) {
-    const int64_t nblk = (hi - lo + HM_REGION_BLOCK - 1) / HM_REGION_BLOCK;
-    p->d_rgidx.reserve(sizeof(int64_t) * REGION_LANES * (size_t)nblk);
-    int64_t* idx = p->d_rgidx.as<int64_t>();
-    hipLaunchKernelGGL(region_block_sums_kernel, dim3((unsigned)nblk), dim3(TPB), 0, p->stream, s, lo, hi, min_cov, idx);
-    HIP_TRY(hipGetLastError());
-    row_scan(p, RegionScan{idx}, nblk);
-    return RegionIndex{s, lo, hi, min_cov, idx};
+// the caller's n intervals: n >= 0, the arrays and the output there (else `bad`, the call's words for it), start <= end in each
+int check_intervals(hm_pileup* p, const char* who, const char* bad, const int64_t* start, const int64_t* end, int64_t n, bool has_out) {
+    if (n < 0 || (n && (!start || !end)) || !has_out) return pfail(p, HM_EINVAL, std::string(who) + ": " + bad);
+    for (int64_t i = 0; i < n; ++i)
+        if (start[i] > end[i]) return pfail(p, HM_EINVAL, std::string(who) + ": interval " + std::to_string(i) + " has start > end");
+    return HM_OK;
 }
 
-// what both fetches check first; the planes into `s`
+// start and end as the two halves of d_iviv -> where each is on the device, and room for the sums; under the caller's guard
+std::pair<const int64_t*, const int64_t*> stage_intervals(hm_pileup* p, const int64_t* start, const int64_t* end, int64_t n, size_t out_bytes) {
+    const size_t bytes = sizeof(int64_t) * (size_t)n;
+    p->d_ivout.reserve(out_bytes);
+    p->d_iviv.reserve(2 * bytes);
+    int64_t* iv = p->d_iviv.as<int64_t>();
+    HIP_TRY(hipMemcpyAsync(iv, start, bytes, hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(hipMemcpyAsync(iv + n, end, bytes, hipMemcpyHostToDevice, p->stream));
+    return {iv, iv + n};
+}
+
+// the query kernel's launch checked, then its sums from d_ivout to the caller; under the caller's guard
+int sums_back(hm_pileup* p, void* out, size_t bytes) {
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, p->d_ivout.p, bytes, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    return HM_OK;
+}
+
+// the index in d_ividx, n elements of the scan Sc: launch(idx) starts the block-sums kernel, then their scan in place; under the caller's guard
+template <class Sc, class Launch>
+Sc build_index(hm_pileup* p, int64_t n, Launch launch) {
+    p->d_ividx.reserve(sizeof(typename Sc::T) * (size_t)n);
+    const Sc sc{p->d_ividx.as<std::remove_pointer_t<decltype(Sc::idx)>>()};
+    launch(sc.idx);
+    HIP_TRY(hipGetLastError());
+    row_scan(p, sc, n);
+    return sc;
+}
+
+// ... of the non-empty [lo, hi) of the planes `s` under min_cov
+RegionIndex build_region_index(hm_pileup* p, const RangePlanes& s, int64_t lo, int64_t hi, int64_t min_cov) {
+    const int64_t nblk = (hi - lo + HM_REGION_BLOCK - 1) / HM_REGION_BLOCK;
+    return RegionIndex{s, lo, hi, min_cov, build_index<RegionScan>(p, nblk, [&](int64_t* idx) {
+        hipLaunchKernelGGL(region_block_sums_kernel, dim3((unsigned)nblk), dim3(TPB), 0, p->stream, s, lo, hi, min_cov, idx);
+    }).idx};
+}
+
+// what both fetches of `pileup -R / -J` check first; the planes into `s`
 int region_call(hm_pileup* p, const char* who, const void* pcov, const void* ncov, const void* key, int64_t& plane_base, int64_t lo,
                 int64_t hi, int64_t min_cov, const int64_t* start, const int64_t* end, int64_t n, bool has_out, RangePlanes& s) {
     if (lo < 0 || hi < lo || n < 0 || (n && (!start || !end)) || !has_out) return pfail(p, HM_EINVAL, std::string(who) + ": bad argument");
     if (hi - lo >= (int64_t(1) << 31) * HM_REGION_BLOCK) return pfail(p, HM_EINVAL, std::string(who) + ": range too large");
     if (min_cov < 1) return pfail(p, HM_EINVAL, std::string(who) + ": min_cov must be >= 1");
-    for (int64_t i = 0; i < n; ++i)
-        if (start[i] > end[i]) return pfail(p, HM_EINVAL, std::string(who) + ": interval " + std::to_string(i) + " has start > end");
+    if (const int rc = check_intervals(p, who, "bad argument", start, end, n, has_out)) return rc;  // only start > end is left to find
     return range_planes(p, pcov, ncov, key, plane_base, s) ? HM_OK : HM_ESTATE;
 }
 
@@ -4477,18 +4497,11 @@ int hm_pileup_fetch_regions(hm_pileup_t* p, const void* pcov, const void* ncov, 
     if (hi == lo) return HM_OK;
     return guarded(p, [&] {
         hipStream_t st = p->stream;
-        const size_t iv_bytes = sizeof(int64_t) * (size_t)n, out_bytes = sizeof(hm_region_sum_t) * 3 * (size_t)n;
-        p->d_rgiv.reserve(2 * iv_bytes);
-        p->d_rgout.reserve(out_bytes);
-        int64_t* iv = p->d_rgiv.as<int64_t>();
-        HIP_TRY(hipMemcpyAsync(iv, start, iv_bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(iv + n, end, iv_bytes, hipMemcpyHostToDevice, st));
+        const size_t out_bytes = sizeof(hm_region_sum_t) * 3 * (size_t)n;
+        const auto [d_start, d_end] = stage_intervals(p, start, end, n, out_bytes);
         const RegionIndex ix = build_region_index(p, s, lo, hi, min_cov);
-        hipLaunchKernelGGL(region_query_kernel, dim3(grid_for(n * 64)), dim3(TPB), 0, st, ix, plane_base, iv, iv + n, n, p->d_rgout.as<int64_t>());
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(out, p->d_rgout.p, out_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return HM_OK;
+        hipLaunchKernelGGL(region_query_kernel, dim3(grid_for(n * 64)), dim3(TPB), 0, st, ix, plane_base, d_start, d_end, n, p->d_ivout.as<int64_t>());
+        return sums_back(p, out, out_bytes);
     });
 }
 
@@ -4528,20 +4541,17 @@ int hm_pileup_fetch_metaplot(hm_pileup_t* p, const void* pcov, const void* ncov,
     const int gr = guarded(p, [&] {
         hipStream_t st = p->stream;
         const size_t iv_bytes = sizeof(MetaIv) * used.size(), tab_bytes = sizeof(int64_t) * tab.size();
-        p->d_rgiv.reserve(iv_bytes);
-        p->d_rgout.reserve(tab_bytes);
-        HIP_TRY(hipMemcpyAsync(p->d_rgiv.p, used.data(), iv_bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(p->d_rgout.p, 0, tab_bytes, st));
+        p->d_iviv.reserve(iv_bytes);
+        p->d_ivout.reserve(tab_bytes);
+        HIP_TRY(hipMemcpyAsync(p->d_iviv.p, used.data(), iv_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(p->d_ivout.p, 0, tab_bytes, st));
         const RegionIndex ix = build_region_index(p, s, lo, hi, min_cov);
         // about 4 096 workgroups in all: enough to fill the device, few enough that a bin sees few atomics
         const int64_t waves = ((int64_t)used.size() + TPB / 64 - 1) / (TPB / 64);
         const unsigned gy = (unsigned)std::max<int64_t>(1, std::min<int64_t>(waves, (4096 + nb - 1) / nb));
-        hipLaunchKernelGGL(metaplot_kernel, dim3((unsigned)nb, gy), dim3(TPB), 0, st, ix, plane_base, m, p->d_rgiv.as<MetaIv>(),
-                           (int64_t)used.size(), p->d_rgout.as<unsigned long long>());
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(tab.data(), p->d_rgout.p, tab_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return HM_OK;
+        hipLaunchKernelGGL(metaplot_kernel, dim3((unsigned)nb, gy), dim3(TPB), 0, st, ix, plane_base, m, p->d_iviv.as<MetaIv>(),
+                           (int64_t)used.size(), p->d_ivout.as<unsigned long long>());
+        return sums_back(p, tab.data(), tab_bytes);
     });
     if (gr != HM_OK) return gr;
     for (int c = 0; c < 3; ++c)
@@ -4652,7 +4662,7 @@ int64_t hm_pileup_fetch_context_path(hm_pileup_t* p, const void* pcov, const voi
     return fetch_context(p, pcov, ncov, key, plane_base, lo, hi, min_cov, flank, path, out, cap);
 }
 
-// ---- `regiondiff` -----------------------------------------------------------------------------------------------------------------
+// ---- `regiondiff`: the interval fetch over the M level planes (the skeleton is with `pileup -R / -J` above) ---------------------------
 int64_t hm_sample_fetch_intervals(hm_pileup_t* p, int64_t lo, int64_t hi, int32_t ctx, int32_t complete, const int64_t* start,
                                   const int64_t* end, int64_t n_iv, hm_sample_interval_t* out) {
     if (!p) return HM_EINVAL;
@@ -4661,9 +4671,7 @@ int64_t hm_sample_fetch_intervals(hm_pileup_t* p, int64_t lo, int64_t hi, int32_
     if (ctx < 0 || ctx > 2) return pfail(p, HM_EINVAL, std::string(who) + ": ctx must be 0, 1 or 2");
     const int rc = option_range(p, who, sample_needs(p), lo, hi);
     if (rc != HM_OK) return rc;
-    if (n_iv < 0 || (n_iv && (!start || !end || !out))) return pfail(p, HM_EINVAL, std::string(who) + ": n_iv >= 0, start, end and out not NULL");
-    for (int64_t i = 0; i < n_iv; ++i)
-        if (start[i] > end[i]) return pfail(p, HM_EINVAL, std::string(who) + ": interval " + std::to_string(i) + " has start > end");
+    if (const int bad = check_intervals(p, who, "n_iv >= 0, start, end and out not NULL", start, end, n_iv, !n_iv || out)) return bad;
     const int M = p->samples_open;
     if (!M || !n_iv) return 0;
     std::fill(out, out + n_iv * M, hm_sample_interval_t{0, 0});
@@ -4674,25 +4682,16 @@ int64_t hm_sample_fetch_intervals(hm_pileup_t* p, int64_t lo, int64_t hi, int32_
         while (P < M) P <<= 1;
         const SampleIvPlanes v{p->d_slevel.as<uint16_t>(), p->sample_stride, p->key, M, 64 / P, (uint32_t)ctx, (int)complete};
         const int64_t nblk = (hi - lo + HM_REGION_BLOCK - 1) / HM_REGION_BLOCK;
-        const size_t iv_bytes = sizeof(int64_t) * (size_t)n_iv, out_bytes = sizeof(SamplePair) * (size_t)n_iv * (size_t)M;
+        const size_t out_bytes = sizeof(SamplePair) * (size_t)n_iv * (size_t)M;
         const size_t lds = sizeof(uint32_t) * (TPB / 64) * (size_t)M * (size_t)v.pitch();
-        p->d_sividx.reserve(sizeof(SamplePair) * (size_t)M * (size_t)nblk);
-        p->d_siviv.reserve(2 * iv_bytes);
-        p->d_sivout.reserve(out_bytes);
-        SamplePair* idx = p->d_sividx.as<SamplePair>();
-        int64_t* iv = p->d_siviv.as<int64_t>();
-        HIP_TRY(hipMemcpyAsync(iv, start, iv_bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(iv + n_iv, end, iv_bytes, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(sample_block_sums_kernel, dim3((unsigned)nblk), dim3(TPB), lds, st, v, lo, hi, nblk, idx);
-        HIP_TRY(hipGetLastError());
-        row_scan(p, SampleIvScan{idx}, (int64_t)M * nblk);
+        const auto [d_start, d_end] = stage_intervals(p, start, end, n_iv, out_bytes);
+        const SamplePair* idx = build_index<SampleIvScan>(p, (int64_t)M * nblk, [&](SamplePair* sums) {
+            hipLaunchKernelGGL(sample_block_sums_kernel, dim3((unsigned)nblk), dim3(TPB), lds, st, v, lo, hi, nblk, sums);
+        }).idx;
         // at most 2^14 workgroups: 65 536 wavefronts share the intervals beyond that
-        hipLaunchKernelGGL(sample_query_kernel, dim3(grid_for(n_iv * 64, 1 << 14)), dim3(TPB), lds, st, v, lo, hi, nblk, idx, iv, iv + n_iv, n_iv,
-                           p->d_sivout.as<SamplePair>());
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(out, p->d_sivout.p, out_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return HM_OK;
+        hipLaunchKernelGGL(sample_query_kernel, dim3(grid_for(n_iv * 64, 1 << 14)), dim3(TPB), lds, st, v, lo, hi, nblk, idx, d_start, d_end, n_iv,
+                           p->d_ivout.as<SamplePair>());
+        return sums_back(p, out, out_bytes);
     });
     return done != HM_OK ? done : n_iv * M;
 }

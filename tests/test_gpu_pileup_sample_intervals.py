@@ -230,6 +230,53 @@ def test_other_fetches_in_between_change_nothing():
         pu.close()
 
 
+@pytest.mark.parametrize("m", [2, 3])
+def test_interval_fetches_share_their_buffers(m):
+    """regions, metaplot and sample_intervals keep their index, intervals and sums in ONE set of device buffers, those of
+    whichever ran last.  In rotation on one engine, with all the interval classes and then one interval (the buffers grow, then
+    serve a smaller call), every answer equals -- exactly -- that of an engine whose first interval fetch it is."""
+    block, _ = _geometry()
+    ref = I.loaded(3, block, 3)
+    assert ref.total == 3 * block + 777                          # three blocks and a remainder
+    classes = I.interval_classes(ref, 0, block, 0, ref.total)
+    start, end = np.array([c[1] for c in classes]), np.array([c[2] for c in classes])
+    one = [c[0] for c in classes].index("the whole range")
+    picks = (slice(None), slice(one, one + 1))                   # all the classes, then one interval: the smaller call after the larger
+    meta = dict(bins=4, flank=8, flank_bins=2)
+
+    def calls(pick):
+        s, e = start[pick], end[pick]
+        a, b = np.clip(s, 0, ref.total), np.clip(e, 0, ref.total)
+        z, t = np.zeros_like(a), np.full_like(a, ref.total)
+        return (("sample_intervals CpG", lambda pu: pu.sample_intervals(s, e, 0).tobytes()),
+                ("regions", lambda pu: pu.regions(a, b).tobytes()),
+                ("sample_intervals CHG complete", lambda pu: pu.sample_intervals(s, e, 1, complete=True).tobytes()),
+                ("metaplot", lambda pu: (lambda rows, used: rows.tobytes() + bytes([used]))(*pu.metaplot(a, b, z, t, **meta))))
+
+    want = {}
+    for k, pick in enumerate(picks):
+        for name, call in calls(pick):
+            fresh = _load(_engine(3), 3, m)
+            want[k, name] = call(fresh)
+            fresh.close()
+            assert any(want[k, name]), (k, name)
+    assert want[0, "regions"] != want[1, "regions"] and want[0, "metaplot"] != want[1, "metaplot"]
+    pu = _load(_engine(3), 3, m)
+    try:
+        others = [pu.sample_sums().tobytes(), pu.loci().tobytes()]
+        for rounds in range(2):
+            for k, pick in enumerate(picks):
+                for name, call in calls(pick):
+                    assert call(pu) == want[k, name], (rounds, k, name)
+                    assert call(pu) == want[k, name], (rounds, k, name, "again")
+                assert [pu.sample_sums().tobytes(), pu.loci().tobytes()] == others
+        for name, call in calls(picks[0])[::-1]:                 # ... and each large call straight after the small one of another kind
+            assert calls(picks[1])[0][1](pu) == want[1, "sample_intervals CpG"]
+            assert call(pu) == want[0, name], name
+    finally:
+        pu.close()
+
+
 # ---- 4. errors and states -----------------------------------------------------------------------------------------------------------------
 def test_errors_and_states():
     from hifimeth_amd.pileup import MethylationPileup
