@@ -138,6 +138,9 @@ def lib():
         "hm_pileup_fetch_groups": (i64, [vp, i64, i64, i32, vp, i64]),
         "hm_pileup_group_planes": (C.c_int, [vp, i32, i64, i64, vp, vp]),
         "hm_group_qvalues": (C.c_int, [vp, i64, vp, vp]),
+        "hm_dmr_fetch_regions": (i64, [vp, i64, i64, i32, i32, C.c_double, C.c_double, i64, i32, i32, C.POINTER(i64),
+                                       C.POINTER(i64), vp, i64]),
+        "hm_dmr_p_cutoff": (C.c_int, [vp, vp, i64, C.c_double, vp]),
         "hm_sample_geometry": (C.c_int, [vp]),
         "hm_sample_open": (C.c_int, [vp]),
         "hm_sample_load": (i64, [vp, vp, i64]),

@@ -16,6 +16,7 @@
 //     hifimeth-hip groupdiff [OPTIONS] REF.fa A1,A2,.. B1,B2,.. OUT (two groups of replicate pileups, hifimeth_pileup.cpp)
 //     hifimeth-hip samplecorr [OPTIONS] REF.fa S1,S2,..,SN OUT (N pileups' correlation matrix per context, hifimeth_pileup.cpp)
 //     hifimeth-hip regiondiff -R IV.bed [OPTIONS] REF.fa A1,A2,.. B1,B2,.. OUT (two groups tested over given intervals, hifimeth_pileup.cpp)
+//     hifimeth-hip groupdmr [OPTIONS] REF.fa A1,A2,.. B1,B2,.. OUT (regions that differ between two groups, hifimeth_pileup.cpp)
 //     hifimeth-hip modstats IN.bam                    (MM/ML parser + per-context histograms + adaptive thresholds)
 //     hifimeth-hip modlist IN.bam                     (the MM/ML parser's output per record: test seam against the
 //                                                      reference parser's fixture, tests/golden/modparse.json)
@@ -113,8 +114,9 @@ void usage() {
             "  %s groupdiff [OPTIONS] reference a1,a2,... b1,b2,... output-prefix   two groups of replicate pileups tested likewise\n"
             "  %s samplecorr [OPTIONS] reference s1,s2,...,sN output-prefix   the correlation matrix of N pileups, per context\n"
             "  %s regiondiff -R bed [OPTIONS] reference a1,a2,... b1,b2,... output-prefix   two groups of replicate pileups tested over given intervals\n"
+            "  %s groupdmr [OPTIONS] reference a1,a2,... b1,b2,... output-prefix   regions that differ between two groups of replicate pileups\n"
             "  %s corr [-c <min coverage>] bed1 bed2                        Pearson correlation of two pileups\n",
-            kName, kName, kName, kName, kName, kName, kName, kName, kName);
+            kName, kName, kName, kName, kName, kName, kName, kName, kName, kName);
 }
 
 // host threads this process may really use: the affinity mask, capped by the cgroup CPU quota (a container that is granted
@@ -918,6 +920,7 @@ int main(int argc, char** argv) {
     if (cmd == "groupdiff") return cmd_groupdiff(argc, argv);
     if (cmd == "samplecorr") return cmd_samplecorr(argc, argv);
     if (cmd == "regiondiff") return cmd_regiondiff(argc, argv);
+    if (cmd == "groupdmr") return cmd_groupdmr(argc, argv);
     if (cmd == "sample") return cmd_sample(argc, argv);
     if (cmd == "eval") return cmd_eval(argc, argv);
     usage();

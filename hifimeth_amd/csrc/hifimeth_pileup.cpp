@@ -1377,55 +1377,41 @@ struct GroupQRow {  // what write_rows formats: the row and its q, named by gpos
     const hm_group_t* g;
     double q;
 };
-}  // namespace
 
-int cmd_groupdiff(int argc, char** argv) {
-    PileupOptions o;
-    int first = 0, status = 0;
-    if (!parse_command_line(CMD_GROUPDIFF, argc, argv, o, first, status)) return status;
-    o.ref = argv[first];
-    const SampleSet set(argv[first + 1], argv[first + 2]);
-    o.prefix = argv[first + 3];
-    fprintf(stderr, "\n\n====================> Parameters:\nCPU threads: %d\nGenomic reference: %s\n", o.threads, o.ref.c_str());
-    set.echo();
-    fprintf(stderr, "output prefix: %s\ngroupdiff: min sample coverage %lld, min replicates per group %lld -> %s.groups.*\n\n\n", o.prefix.c_str(),
-            o.group_min_cov, o.group_min_reps, o.prefix.c_str());
-
-    const auto t_start = clk::now();
+// What `groupdiff` and `groupdmr` share up to the first fetch: the lists checked against -r, the engine with the groups planes, and
+// every sample loaded as one sample of its group; n_rows[g] = the counting loci group g + 1 added.  -> 0, or the exit status
+// behind a message.
+int load_groups(const PileupOptions& o, const SampleSet& set, CovJob& job, uint64_t n_rows[2]) {
     if (!set.lists_fit(o.group_min_reps, 255)) return EXIT_FAILURE;
-    CovJob job;
     if (const int failed = open_cov_job(o, set.sample, "every sample", "groups",
                                         {{"partitions", 2}, {"groups", 1}, {"group_min_cov", (double)o.group_min_cov}}, job))
         return failed;
     hm_pileup_t* pe = job.engine.get();
-    const Fasta& fa = job.fa;
-    const std::vector<int64_t>& seq_start = job.seq_start;
-    auto die = [&](const std::string& what) { return engine_error(pe, what); };
-    uint64_t n_rows[2] = {0, 0};
-    if (const int failed = load_samples(
-            job, set, [&](size_t i) { return hm_pileup_group_sample(pe, set.member[i]) < 0 ? die("group sample") : 0; },
-            [&](const hm_locus_t* rows, int64_t n) { return hm_pileup_load_sample_loci(pe, rows, n); }, [&](size_t i) -> uint64_t& { return n_rows[set.member[i] - 1]; }))
-        return failed;
-    const auto t_load = clk::now();
+    return load_samples(
+        job, set, [&](size_t i) { return hm_pileup_group_sample(pe, set.member[i]) < 0 ? engine_error(pe, "group sample") : 0; },
+        [&](const hm_locus_t* rows, int64_t n) { return hm_pileup_load_sample_loci(pe, rows, n); }, [&](size_t i) -> uint64_t& { return n_rows[set.member[i] - 1]; });
+}
 
-    std::vector<hm_group_t> rows;
-    for (size_t s = 0; s < fa.names.size(); ++s) {
-        const int64_t n = hm_pileup_fetch_groups(pe, seq_start[s], seq_start[s + 1], (int32_t)o.group_min_reps, nullptr, 0);
-        if (n < 0) return die("groups");
+// The tested loci of the whole reference, sequence by sequence, appended to `rows` (64 B each).  false on an engine error.
+bool fetch_group_rows(const CovJob& job, int32_t min_reps, std::vector<hm_group_t>& rows) {
+    hm_pileup_t* pe = job.engine.get();
+    const std::vector<int64_t>& seq_start = job.seq_start;
+    for (size_t s = 0; s < job.fa.names.size(); ++s) {
+        const int64_t n = hm_pileup_fetch_groups(pe, seq_start[s], seq_start[s + 1], min_reps, nullptr, 0);
+        if (n < 0) return false;
         if (n == 0) continue;
         rows.resize(rows.size() + (size_t)n);
-        if (hm_pileup_fetch_groups(pe, seq_start[s], seq_start[s + 1], (int32_t)o.group_min_reps, rows.data() + rows.size() - n, n) != n) return die("groups");
+        if (hm_pileup_fetch_groups(pe, seq_start[s], seq_start[s + 1], min_reps, rows.data() + rows.size() - n, n) != n) return false;
     }
-    job.engine.reset();
-    std::vector<double> q(rows.size());
-    uint64_t m[3];
-    if (hm_group_qvalues(rows.data(), (int64_t)rows.size(), q.data(), m) != HM_OK) {
-        fprintf(stderr, "ERROR: groupdiff: the tested loci are not rows the engine wrote\n");
-        return EXIT_FAILURE;
-    }
+    return true;
+}
+
+// <prefix>.groups.<ctx>.bed and <prefix>.groups.summary.tsv from the tested loci of the job, their q-values and m[ctx] =
+// the tested loci per context (hm_group_qvalues).  false, behind a message, for a file that cannot be opened.
+bool write_group_loci(const PileupOptions& o, const Fasta& fa, const std::vector<hm_group_t>& rows, const std::vector<double>& q, const uint64_t m[3]) {
     {
         CtxFiles out;
-        if (!out.open(o.prefix, "groups.", ".bed")) return EXIT_FAILURE;
+        if (!out.open(o.prefix, "groups.", ".bed")) return false;
         write_rows<GroupQRow>(
             fa, out.f, o.threads,
             [&](int64_t lo, int64_t hi, GroupQRow* dst, int64_t cap) {  // the rows are ascending in gpos
@@ -1450,13 +1436,136 @@ int cmd_groupdiff(int argc, char** argv) {
         tally[c][2] += rows[i].phi > 1.0;
     }
     const OutFile f = open_out(o.prefix + ".groups.summary.tsv");
-    if (!f) return EXIT_FAILURE;
+    if (!f) return false;
     for (int c = 0; c < 3; ++c)
         fprintf(f.get(), "%s\t%llu\t%llu\t%llu\t%llu\n", CTX_NAME[c], (unsigned long long)m[c], (unsigned long long)tally[c][0], (unsigned long long)tally[c][1],
                 (unsigned long long)tally[c][2]);
+    return true;
+}
+}  // namespace
+
+int cmd_groupdiff(int argc, char** argv) {
+    PileupOptions o;
+    int first = 0, status = 0;
+    if (!parse_command_line(CMD_GROUPDIFF, argc, argv, o, first, status)) return status;
+    o.ref = argv[first];
+    const SampleSet set(argv[first + 1], argv[first + 2]);
+    o.prefix = argv[first + 3];
+    fprintf(stderr, "\n\n====================> Parameters:\nCPU threads: %d\nGenomic reference: %s\n", o.threads, o.ref.c_str());
+    set.echo();
+    fprintf(stderr, "output prefix: %s\ngroupdiff: min sample coverage %lld, min replicates per group %lld -> %s.groups.*\n\n\n", o.prefix.c_str(),
+            o.group_min_cov, o.group_min_reps, o.prefix.c_str());
+
+    const auto t_start = clk::now();
+    CovJob job;
+    uint64_t n_rows[2] = {0, 0};
+    if (const int failed = load_groups(o, set, job, n_rows)) return failed;
+    const auto t_load = clk::now();
+
+    std::vector<hm_group_t> rows;
+    if (!fetch_group_rows(job, (int32_t)o.group_min_reps, rows)) return engine_error(job.engine.get(), "groups");
+    job.engine.reset();
+    std::vector<double> q(rows.size());
+    uint64_t m[3];
+    if (hm_group_qvalues(rows.data(), (int64_t)rows.size(), q.data(), m) != HM_OK) {
+        fprintf(stderr, "ERROR: groupdiff: the tested loci are not rows the engine wrote\n");
+        return EXIT_FAILURE;
+    }
+    if (!write_group_loci(o, job.fa, rows, q, m)) return EXIT_FAILURE;
     fprintf(stderr, "## %zu + %zu samples, %llu + %llu counting loci of %d contexts, %zu tested in %.2f s: parse + load %.2f s; test + BED %.2f s\n",
             set.group[0].size(), set.group[1].size(), (unsigned long long)n_rows[0], (unsigned long long)n_rows[1], job.n_ctx, rows.size(), secs(t_start, clk::now()),
             secs(t_start, t_load), secs(t_load, clk::now()));
+    return 0;
+}
+
+// ---- groupdmr [OPTIONS] reference a1,a2,... b1,b2,... out-prefix (ours) ---------------------------------------------------------------
+// Differentially methylated regions between two groups of replicates: loaded as `groupdiff` loads, then per sequence and context
+// the tested loci are chained on the device (hm_dmr_fetch_regions).  Only the regions come to the
+// host, unless -F (the q-values need every p of the job: hm_group_qvalues, hm_dmr_p_cutoff) or -L (the loci are an output) ask
+// for the rows.
+int cmd_groupdmr(int argc, char** argv) {
+    PileupOptions o;
+    int first = 0, status = 0;
+    if (!parse_command_line(CMD_GROUPDMR, argc, argv, o, first, status)) return status;
+    o.ref = argv[first];
+    const SampleSet set(argv[first + 1], argv[first + 2]);
+    o.prefix = argv[first + 3];
+    const bool by_q = o.dmr_max_q > 0.0;
+    fprintf(stderr, "\n\n====================> Parameters:\nCPU threads: %d\nGenomic reference: %s\n", o.threads, o.ref.c_str());
+    set.echo();
+    fprintf(stderr, "output prefix: %s\ngroupdmr: min sample coverage %lld, min replicates per group %lld; regions of >= %lld loci with %s <= %g, |diff| >= %g and one sign, "
+                    "gaps <= %lld -> %s.groupdmr.*\n", o.prefix.c_str(), o.group_min_cov, o.group_min_reps, o.dmr_min_loci, by_q ? "q" : "p",
+            by_q ? o.dmr_max_q : o.dmr_max_p, o.dmr_min_diff, o.dmr_max_gap, o.prefix.c_str());
+    if (o.dmr_loci) fprintf(stderr, "groupdmr: the tested loci as `groupdiff` writes them -> %s.groups.*\n", o.prefix.c_str());
+    fprintf(stderr, "\n\n");
+
+    const auto t_start = clk::now();
+    CovJob job;
+    uint64_t n_rows[2] = {0, 0};
+    if (const int failed = load_groups(o, set, job, n_rows)) return failed;
+    hm_pileup_t* pe = job.engine.get();
+    const Fasta& fa = job.fa;
+    const auto t_load = clk::now();
+
+    double cutoff[3] = {o.dmr_max_p, o.dmr_max_p, o.dmr_max_p};
+    uint64_t tested[3] = {0, 0, 0};
+    if (by_q || o.dmr_loci) {
+        std::vector<hm_group_t> rows;
+        if (!fetch_group_rows(job, (int32_t)o.group_min_reps, rows)) return engine_error(pe, "groups");
+        std::vector<double> q(rows.size());
+        if (hm_group_qvalues(rows.data(), (int64_t)rows.size(), q.data(), tested) != HM_OK ||
+            (by_q && hm_dmr_p_cutoff(rows.data(), q.data(), (int64_t)rows.size(), o.dmr_max_q, cutoff) != HM_OK)) {
+            fprintf(stderr, "ERROR: groupdmr: the tested loci are not rows the engine wrote\n");
+            return EXIT_FAILURE;
+        }
+        if (o.dmr_loci && !write_group_loci(o, fa, rows, q, tested)) return EXIT_FAILURE;
+    }
+
+    CtxFiles out;
+    if (!out.open(o.prefix, "groupdmr.", ".bed")) return EXIT_FAILURE;
+    uint64_t hits[3] = {0, 0, 0}, regions[3] = {0, 0, 0}, loci[3] = {0, 0, 0}, plus[3] = {0, 0, 0};
+    std::vector<hm_group_region_t> rows;
+    for (int c = 0; c < 3; ++c) {
+        if (!(cutoff[c] > 0.0)) continue;  // -F and no locus under it: nothing to chain
+        uint64_t in_ctx = 0;
+        for (size_t s = 0; s < fa.names.size(); ++s) {
+            const int64_t lo = job.seq_start[s], hi = job.seq_start[s + 1];
+            int64_t R = 0, H = 0;
+            const auto fetch = [&](hm_group_region_t* dst, int64_t cap) {
+                return hm_dmr_fetch_regions(pe, lo, hi, (int32_t)o.group_min_reps, c, cutoff[c], o.dmr_min_diff, o.dmr_max_gap,
+                                            (int32_t)o.dmr_min_loci, 0, &R, &H, dst, cap);
+            };
+            int64_t n = fetch(nullptr, 0);
+            if (n > 0) {
+                rows.resize((size_t)n);
+                n = fetch(rows.data(), n);
+            }
+            if (n < 0) return engine_error(pe, "group regions");
+            in_ctx += (uint64_t)R;
+            hits[c] += (uint64_t)H;
+            for (int64_t i = 0; i < n; ++i) {
+                const hm_group_region_t& r = rows[(size_t)i];
+                fprintf(out.f[c], "%s\t%lld\t%lld\t%s_%llu\t%d\t.\t%c\t%g\t%.6g\t%d\t%lld\t%lld\t%d\t%lld\t%lld\t%.6g\n", fa.names[s].c_str(),
+                        (long long)(r.start - lo), (long long)(r.end - lo), CTX_NAME[c], (unsigned long long)++regions[c], r.n_loci, r.sign > 0 ? '+' : '-',
+                        r.diff, r.pmin, (int)r.m1_min, (long long)r.pcov1, (long long)r.ncov1, (int)r.m2_min, (long long)r.pcov2, (long long)r.ncov2, r.phi_max);
+                loci[c] += (uint64_t)r.n_loci;
+                plus[c] += r.sign > 0;
+            }
+        }
+        tested[c] = in_ctx;
+    }
+    job.engine.reset();
+    const OutFile f = open_out(o.prefix + ".groupdmr.summary.tsv");
+    if (!f) return EXIT_FAILURE;
+    for (int c = 0; c < 3; ++c) {
+        char cut[32] = "nan";
+        if (cutoff[c] > 0.0) snprintf(cut, sizeof cut, "%.6g", cutoff[c]);
+        fprintf(f.get(), "%s\t%llu\t%llu\t%s\t%llu\t%llu\t%llu\t%llu\n", CTX_NAME[c], (unsigned long long)tested[c], (unsigned long long)hits[c], cut,
+                (unsigned long long)regions[c], (unsigned long long)loci[c], (unsigned long long)plus[c], (unsigned long long)(regions[c] - plus[c]));
+    }
+    fprintf(stderr, "## %zu + %zu samples, %llu + %llu counting loci of %d contexts, %llu regions in %.2f s: parse + load %.2f s; regions + BED %.2f s\n",
+            set.group[0].size(), set.group[1].size(), (unsigned long long)n_rows[0], (unsigned long long)n_rows[1], job.n_ctx,
+            (unsigned long long)(regions[0] + regions[1] + regions[2]), secs(t_start, clk::now()), secs(t_start, t_load), secs(t_load, clk::now()));
     return 0;
 }
 

@@ -1,4 +1,4 @@
-// hifimeth_pileup_opts.cpp -- the options of `pileup`, `diff`, `groupdiff`, `samplecorr` and `regiondiff`: one table that is parser and usage text at once, two strict number
+// hifimeth_pileup_opts.cpp -- the options of `pileup`, `diff`, `groupdiff`, `samplecorr`, `regiondiff` and `groupdmr`: one table that is parser and usage text at once, two strict number
 // parsers, and the checks between options as one ordered list.  A new option is one row here, a field of PileupOptions, a rule if
 // it depends on another option, and its cases in tools/make_cli_options.py.
 #include "hifimeth_pileup_opts.h"
@@ -299,6 +299,21 @@ const Option REGION_OPTIONS[] = {
      "Minimum number of used samples in each group of a tested interval, in [2, 64]\n    Default: 2"},
 };
 const char REGION_FLAGS[] = "Raklrtd";
+// `groupdmr` takes -a and -r from `groupdiff`'s rows and brings six: its -s, -g and -n are not "With -G"
+template <double O::*Field>
+bool unit_interval(const char* v, O& o) { return whole_double(v, o.*Field) && o.*Field > 0.0 && o.*Field <= 1.0; }
+const Option DMR_OPTIONS[] = {
+    {'s', "<p>", unit_interval<&O::dmr_max_p>, "Largest p-value of a locus in a region, in (0, 1]\n    Default: 0.01"},
+    {'F', "<q>", unit_interval<&O::dmr_max_q>,
+     "Instead of -s: largest Benjamini-Hochberg q-value (within the context, over the whole job) of a locus in a region, in (0, 1]"},
+    {'m', "<pct>", [](const char* v, O& o) { return whole_double(v, o.dmr_min_diff) && o.dmr_min_diff >= 0.0 && o.dmr_min_diff <= 100.0; },
+     "Smallest |group 1 % - group 2 %| of a locus in a region, in [0, 100]\n    Default: 0"},
+    {'g', "<bp>", integer<&O::dmr_max_gap, 1, LLONG_MAX>, "Largest distance between consecutive loci of a region, >= 1\n    Default: 500"},
+    {'n', "<int>", integer<&O::dmr_min_loci, 1, INT_MAX>, "Smallest number of loci of a region, >= 1\n    Default: 3"},
+    {'L', nullptr, flag<&O::dmr_loci>,
+     "Also write <output-prefix>.groups.<ctx>.bed and <output-prefix>.groups.summary.tsv, as `groupdiff` with the same -a -r"},
+};
+const char DMR_FLAGS[] = "arsFmgnLtd";
 
 const char PILEUP_HEADER[] =
     "USAGE:\n"
@@ -372,10 +387,36 @@ const char REGION_HEADER[] =
     "\n"
     "ARGUMENTS:\n";
 
+const char DMR_HEADER[] =
+    "USAGE:\n"
+    "  $0 groupdmr [OPTIONS] reference a1,a2,... b1,b2,... output-prefix\n"
+    "\n"
+    "DESCRIPTION:\n"
+    "  Differentially methylated regions between two groups of replicates.  The samples are given, loaded and tested locus by locus\n"
+    "  as by `groupdiff` (-a, -r; `$0 groupdiff -h` has the test).  Per sequence and context the tested loci are then chained: a region\n"
+    "  is a run of consecutive tested loci that all have p <= -s (or q <= -F), |group 1 % - group 2 %| >= -m and a difference of the\n"
+    "  same sign, each at most -g bases after the one before; a tested locus that does not qualify ends it, a locus that is not\n"
+    "  tested or belongs to another context does nothing.  Regions of at least -n loci are written.\n"
+    "  Writes <output-prefix>.groupdmr.<ctx>.bed: chrom, start, end, name (<ctx>_<number>), loci, ., + or - (the sign of group 1 % -\n"
+    "  group 2 % at every locus), group 1 % - group 2 % of the pooled counts, smallest p-value, then m1, pcov1, ncov1, m2, pcov2, ncov2\n"
+    "  (fewest counting samples of the group at a locus; calls summed over the loci) and the largest phi; and\n"
+    "  <output-prefix>.groupdmr.summary.tsv: ctx, tested loci, qualifying loci, the p cutoff used (nan: none), regions, loci in\n"
+    "  regions, regions +, regions -.  The pooled difference can have the other sign than the loci.  There is no region-level\n"
+    "  p-value: the loci were selected by their p, so a test of the pooled counts would not be one.  The BED file is valid input to\n"
+    "  `regiondiff -R`, which adds the samples' levels per region; its p on regions found from the same samples is descriptive\n"
+    "  only, for the same reason\n"
+    "\n"
+    "OPTIONAL ARGUMENTS:\n";
+
 const Option* find_option(Command cmd, char letter) {
     if (cmd == CMD_DIFF && !strchr(DIFF_FLAGS, letter)) return nullptr;
-    if (cmd == CMD_GROUPDIFF) {
-        if (!strchr(GROUP_FLAGS, letter)) return nullptr;
+    if (cmd == CMD_GROUPDMR) {
+        if (!strchr(DMR_FLAGS, letter)) return nullptr;
+        for (const Option& opt : DMR_OPTIONS)
+            if (opt.letter == letter) return &opt;
+    }
+    if (cmd == CMD_GROUPDIFF || cmd == CMD_GROUPDMR) {
+        if (!strchr(cmd == CMD_GROUPDMR ? DMR_FLAGS : GROUP_FLAGS, letter)) return nullptr;
         for (const Option& opt : GROUP_OPTIONS)
             if (opt.letter == letter) return &opt;
     }
@@ -403,7 +444,7 @@ void print_text(const char* text, const char* exe) {  // $0: the program
 
 void usage(Command cmd, const char* exe) {
     print_text(cmd == CMD_DIFF ? DIFF_HEADER : cmd == CMD_GROUPDIFF ? GROUP_HEADER : cmd == CMD_SAMPLECORR ? SAMPLE_HEADER :
-               cmd == CMD_REGIONDIFF ? REGION_HEADER : PILEUP_HEADER, exe);
+               cmd == CMD_REGIONDIFF ? REGION_HEADER : cmd == CMD_GROUPDMR ? DMR_HEADER : PILEUP_HEADER, exe);
     const auto row = [&](const Option& opt) {
         fprintf(stderr, "  -%c%s%s\n    ", opt.letter, opt.metavar ? " " : "", opt.metavar ? opt.metavar : "");
         print_text(cmd == CMD_DIFF && opt.diff_help ? opt.diff_help : opt.help, exe);
@@ -413,6 +454,7 @@ void usage(Command cmd, const char* exe) {
     else if (cmd == CMD_GROUPDIFF) for (const char* f = GROUP_FLAGS; *f; ++f) row(*find_option(cmd, *f));
     else if (cmd == CMD_SAMPLECORR) for (const char* f = SAMPLE_FLAGS; *f; ++f) row(*find_option(cmd, *f));
     else if (cmd == CMD_REGIONDIFF) for (const char* f = REGION_FLAGS; *f; ++f) row(*find_option(cmd, *f));
+    else if (cmd == CMD_GROUPDMR) for (const char* f = DMR_FLAGS; *f; ++f) row(*find_option(cmd, *f));
     else for (const Option& opt : OPTIONS) row(opt);
 }
 
@@ -430,7 +472,7 @@ struct Parsed {
 // and inside each group the order below.  It is not uniform -- patterns, linkage, profile and context report a bad value before a
 // missing parent, asm, domains, bedmethyl and intervals the missing parent first -- and tests/golden/cli_options.json pins it.
 // `diff` runs the rules marked CMD_DIFF, `groupdiff` those marked CMD_GROUPDIFF, `samplecorr` those marked CMD_SAMPLECORR,
-// `regiondiff` those marked CMD_REGIONDIFF.
+// `regiondiff` those marked CMD_REGIONDIFF, `groupdmr` those marked CMD_GROUPDMR.
 struct Rule {
     int commands;
     bool (*fires)(const Parsed& p);
@@ -469,11 +511,13 @@ const Rule RULES[] = {
      "-C must be an integer >= 1, -J bins[:flank_bp:flank_bins] with bins in [1, 1000] and flank_bp a multiple of flank_bins in [1, 1000]"},
     {CMD_PILEUP, [](const Parsed& p) { return p.any_bad("SO"); }, "-S must be an integer in [0, 3], -O an integer >= 1"},
     {CMD_PILEUP, [](const Parsed& p) { return p.any_seen("O") && p.o.context_flank < 0; }, "-O needs -S"},
-    {CMD_GROUPDIFF, [](const Parsed& p) { return p.any_bad("ar"); }, "-a must be an integer in [1, 1048575], -r an integer in [1, 255]"},
+    {CMD_GROUPDIFF | CMD_GROUPDMR, [](const Parsed& p) { return p.any_bad("ar"); }, "-a must be an integer in [1, 1048575], -r an integer in [1, 255]"},
     {CMD_SAMPLECORR, [](const Parsed& p) { return p.any_bad("a"); }, "-a must be an integer in [1, 1048575]"},
     {CMD_REGIONDIFF, [](const Parsed& p) { return p.o.intervals.empty(); }, "regiondiff needs -R (the intervals to test)"},
     {CMD_REGIONDIFF, [](const Parsed& p) { return p.any_bad("alr"); },
      "-a must be an integer in [1, 1048575], -l an integer >= 1, -r an integer in [2, 64]"},
+    {CMD_GROUPDMR, [](const Parsed& p) { return p.any_seen("s") && p.any_seen("F"); }, "-s and -F exclude each other (the loci are chosen by p, or by q)"},
+    {CMD_GROUPDMR, [](const Parsed& p) { return p.any_bad("sFmgn"); }, "-s and -F must be in (0, 1], -m in [0, 100], -g and -n integers >= 1"},
 };
 
 }  // namespace

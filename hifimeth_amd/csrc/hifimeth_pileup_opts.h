@@ -1,4 +1,4 @@
-// hifimeth_pileup_opts.h -- the command lines of `hifimeth-hip pileup`, `diff`, `groupdiff`, `samplecorr` and `regiondiff`: the options as the rest of the
+// hifimeth_pileup_opts.h -- the command lines of `hifimeth-hip pileup`, `diff`, `groupdiff`, `samplecorr`, `regiondiff` and `groupdmr`: the options as the rest of the
 // front end reads them, and one call that parses, checks and reports (hifimeth_pileup_opts.cpp holds the option table, which is
 // also the usage text, and the ordered list of checks).  Host code without the engine: nothing here opens a file or a device.
 #pragma once
@@ -35,14 +35,17 @@ struct PileupOptions {
     bool kinetics = false;                                         // -K: call on the fly, with `call`'s options
     std::string model_dir;                                         // -m, default <exe_dir>/../weights
     int ctx_mask = 7, min_read_size = 1000, precision = 1, trunk = -1;  // -c -l -p -T (-1: the call engine decides per context)
-    long long group_min_cov = 5, group_min_reps = 2;               // groupdiff -a -r
+    long long group_min_cov = 5, group_min_reps = 2;               // groupdiff -a -r, groupdmr -a -r
+    double dmr_max_p = 0.01, dmr_max_q = 0.0, dmr_min_diff = 0.0;  // groupdmr -s -F (0: chain by p) -m
+    long long dmr_max_gap = 500, dmr_min_loci = 3;                 // groupdmr -g -n
+    bool dmr_loci = false;                                         // groupdmr -L
     long long sample_min_cov = 5;                                  // samplecorr -a -k
     bool sample_complete = false;
     long long region_min_sample_loci = 3, region_min_reps = 2;     // regiondiff -l -r (its -R -a -k: intervals, sample_min_cov, sample_complete)
     std::string ref, bam, prefix;
 };
 
-enum Command { CMD_PILEUP = 1, CMD_DIFF = 2, CMD_GROUPDIFF = 4, CMD_SAMPLECORR = 8, CMD_REGIONDIFF = 16 };
+enum Command { CMD_PILEUP = 1, CMD_DIFF = 2, CMD_GROUPDIFF = 4, CMD_SAMPLECORR = 8, CMD_REGIONDIFF = 16, CMD_GROUPDMR = 32 };
 
 // The whole text as a decimal integer in [lo, hi] -> out, true.  Leading blanks and a sign pass, as strtoll takes them; an empty
 // text, anything behind the number and a value beyond long long do not, and leave `out` alone.
@@ -51,7 +54,7 @@ bool whole_int(const char* text, long long lo, long long hi, long long& out);
 bool whole_double(const char* text, double& out);
 
 // Parses the options of `cmd` from argv[2] on and runs the checks.  true: go on, the positional arguments start at argv[first]
-// (3 for pileup and samplecorr, 4 for diff, groupdiff and regiondiff).  false: the usage, behind an error message if there is one, has been printed; leave with `status`
+// (3 for pileup and samplecorr, 4 for diff, groupdiff, regiondiff and groupdmr).  false: the usage, behind an error message if there is one, has been printed; leave with `status`
 // (0 after -h).  levels_ok turns the levels and penalty of -D into o's integer weights, false if they give none: the one check
 // that needs the library, so pileup brings it.  It runs once the options have parsed, ahead of the rules; it only writes the weights.
 // the usage of `cmd` on stderr, as parse_command_line prints it: for what a command finds wrong with its positional arguments

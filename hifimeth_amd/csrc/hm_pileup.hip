@@ -47,6 +47,7 @@
 //                   (context, p1, n1, p2, n2), the non-empty bins compacted and given their p by asm_test_kernel, q looked up per row
 //   AsmSel<ASM_CTX> / RegionSel   allele-specific regions (`pileup -H -A -G`): the tested rows of one context compacted and tested,
 //                   then a selection over ROW indices: a thread that owns a chain head walks to the chain's tail
+//   GroupCtxSel / RegionSel<GroupChain>   regions between replicate groups (`groupdmr`): the same walk over the group rows of a context
 //   sites_* / SitesSel   binomial test per locus (`pileup -B / -e`): control sums, histogram of (motif, pcov, pcov + ncov) through
 //                   LDS, the loci beyond the histogram listed (SitesBigSel), rows written by table lookup
 //   DomRowSel / rowscan_* / DomHeadSel   methylation domains (`pileup -D`): the rows of one context compacted, a two-state Viterbi
@@ -1641,6 +1642,15 @@ struct GroupSel {
     }
 };
 
+// ... of context `ctx` only (step 1 of `groupdmr`)
+struct GroupCtxSel {
+    using Row = hm_group_t;
+    GroupSel all;
+    uint32_t ctx;
+    __device__ bool pred(int64_t i) const { return all.pred(i) && site_motif(all.s.a.ky[i]) == ctx; }
+    __device__ bool take(int64_t i, Row& r) const { return site_motif(all.s.a.ky[i]) == ctx && all.take(i, r); }
+};
+
 // x log(x / e) + e - x for a count x and its expectation e > 0, given d = x - e to full precision (the caller has it as an exact
 // integer over N): Loader's series in v = d / (x + e) where the three terms would cancel, the plain form elsewhere.  >= 0.
 __device__ __forceinline__ double deviance_part(double x, double e, double d) {
@@ -1825,34 +1835,91 @@ struct RegionRule {
     int64_t max_gap;
     int32_t min_loci, keep_edges;
 };
+struct GroupRegionRule : RegionRule {  // `groupdmr`: a hit also needs |diff| >= min_diff
+    double min_diff;
+};
 
 // +1 / -1: rows[i] is a hit of that sign; 0: it is none
-__device__ __forceinline__ int region_sign(const hm_asm_t* __restrict__ rows, int64_t i, double max_p) {
+__device__ __forceinline__ int region_sign(const hm_asm_t* __restrict__ rows, int64_t i, const RegionRule& rule) {
     const double d = rows[i].diff;
-    return rows[i].pvalue <= max_p ? (d > 0.0) - (d < 0.0) : 0;
+    return rows[i].pvalue <= rule.max_p ? (d > 0.0) - (d < 0.0) : 0;
+}
+__device__ __forceinline__ int region_sign(const hm_group_t* __restrict__ rows, int64_t i, const GroupRegionRule& rule) {
+    const double d = rows[i].diff;
+    return rows[i].pvalue <= rule.max_p && fabs(d) >= rule.min_diff ? (d > 0.0) - (d < 0.0) : 0;
 }
 // rows i - 1 and i, i >= 1, are within max_gap: linked when both are also hits of one sign
-__device__ __forceinline__ bool region_near(const hm_asm_t* __restrict__ rows, int64_t i, const RegionRule& rule) {
+template <class Unit>
+__device__ __forceinline__ bool region_near(const Unit* __restrict__ rows, int64_t i, const RegionRule& rule) {
     return rows[i].gpos - rows[i - 1].gpos <= rule.max_gap;
 }
 // rows[i] starts a chain (of sign s)
-__device__ __forceinline__ bool region_head(const hm_asm_t* __restrict__ rows, int64_t i, const RegionRule& rule, int& s) {
-    s = region_sign(rows, i, rule.max_p);
-    return s != 0 && !(i > 0 && region_sign(rows, i - 1, rule.max_p) == s && region_near(rows, i, rule));
+template <class Unit, class Rule>
+__device__ __forceinline__ bool region_head(const Unit* __restrict__ rows, int64_t i, const Rule& rule, int& s) {
+    s = region_sign(rows, i, rule);
+    return s != 0 && !(i > 0 && region_sign(rows, i - 1, rule) == s && region_near(rows, i, rule));
 }
 // rows[j] continues the chain of sign s that holds rows[j - 1]
-__device__ __forceinline__ bool region_next(const hm_asm_t* __restrict__ rows, int64_t j, int64_t n_rows, int s, const RegionRule& rule) {
-    return j < n_rows && region_sign(rows, j, rule.max_p) == s && region_near(rows, j, rule);
+template <class Unit, class Rule>
+__device__ __forceinline__ bool region_next(const Unit* __restrict__ rows, int64_t j, int64_t n_rows, int s, const Rule& rule) {
+    return j < n_rows && region_sign(rows, j, rule) == s && region_near(rows, j, rule);
 }
 __device__ __forceinline__ bool region_returned(int64_t n_loci, uint32_t flags, const RegionRule& rule) {
     return n_loci >= rule.min_loci || (rule.keep_edges && flags);
 }
 
-struct RegionSel {
+// What a family of rows adds to the walk: the rows it chains (Unit), the chain it returns (Row), its rule, and what a chain carries
+// beyond the four sums and pmin -- started at the chain's head, fed every further row, stored once the chain is returned.
+struct AsmChain {  // `pileup -H -A -G`, `diff -G`: nothing more
+    using Unit = hm_asm_t;
     using Row = hm_asm_region_t;
-    const hm_asm_t* rows;
+    using Rule = RegionRule;
+    __device__ void start(const Unit&) {}
+    __device__ void add(const Unit&) {}
+    __device__ void store(Row&) const {}
+};
+struct GroupChain {  // `groupdmr`: the largest dispersion and the fewest counting samples of each group among the chain's rows
+    using Unit = hm_group_t;
+    using Row = hm_group_region_t;
+    using Rule = GroupRegionRule;
+    double phi_max;
+    uint16_t m1_min, m2_min;
+    __device__ void start(const Unit& r) {
+        phi_max = r.phi;
+        m1_min = r.m1;
+        m2_min = r.m2;
+    }
+    __device__ void add(const Unit& r) {
+        phi_max = r.phi > phi_max ? r.phi : phi_max;
+        m1_min = r.m1 < m1_min ? r.m1 : m1_min;
+        m2_min = r.m2 < m2_min ? r.m2 : m2_min;
+    }
+    __device__ void store(Row& g) const {
+        g.m1_min = m1_min;
+        g.m2_min = m2_min;
+        g.reserved = 0;
+        g.phi_max = phi_max;
+    }
+};
+
+// the hits among the group rows, by row index: what hm_dmr_fetch_regions counts for n_hits
+struct GroupHitSel {
+    using Row = int64_t;
+    const hm_group_t* rows;
+    GroupRegionRule rule;
+    __device__ bool pred(int64_t i) const { return region_sign(rows, i, rule) != 0; }
+    __device__ bool take(int64_t i, Row& r) const {
+        r = i;
+        return pred(i);
+    }
+};
+
+template <class Chain>
+struct RegionSel {
+    using Row = typename Chain::Row;
+    const typename Chain::Unit* rows;
     int64_t n_rows;
-    RegionRule rule;
+    typename Chain::Rule rule;
     uint32_t ctx;
     // The walk stops after min_loci rows: a chain that long is returned whatever its flags, a shorter one has been walked to its tail.
     __device__ bool pred(int64_t i) const {
@@ -1867,6 +1934,8 @@ struct RegionSel {
         if (!region_head(rows, i, rule, s)) return false;
         int64_t P1 = 0, N1 = 0, P2 = 0, N2 = 0;
         double pmin = rows[i].pvalue;
+        Chain more;
+        more.start(rows[i]);
         int64_t j = i;
         do {
             P1 += rows[j].pcov1;
@@ -1875,6 +1944,7 @@ struct RegionSel {
             N2 += rows[j].ncov2;
             const double pv = rows[j].pvalue;
             pmin = pv < pmin ? pv : pmin;
+            more.add(rows[j]);
             ++j;
         } while (region_next(rows, j, n_rows, s, rule));
         g.flags = (i == 0 ? HM_REGION_FIRST : 0u) | (j == n_rows ? HM_REGION_LAST : 0u);
@@ -1888,9 +1958,10 @@ struct RegionSel {
         g.n_loci = (int32_t)(j - i);
         g.sign = s;
         g.motif = ctx;
-        // as asm_test_kernel's diff, on the pooled sums: each haplotype total is >= min_cov >= 1
+        // as the rows' own diff, on the pooled sums: each total is >= 1 (min_cov >= 1; a counting sample has group_min_cov >= 1 calls)
         g.diff = __dsub_rn(__ddiv_rn(__dmul_rn(100.0, (double)P1), (double)(P1 + N1)), __ddiv_rn(__dmul_rn(100.0, (double)P2), (double)(P2 + N2)));
         g.pmin = pmin;
+        more.store(g);
         return true;
     }
 };
@@ -2555,6 +2626,7 @@ struct hm_pileup {
     int32_t group_min_cov = 5;
     DevBuf d_gmoment[2]{DevBuf(EXACT), DevBuf(EXACT)}, d_gsamples[2]{DevBuf(EXACT), DevBuf(EXACT)}, d_gseen{EXACT}, d_gcoef{EXACT};
     int group_samples[2] = {0, 0}, group_open = 0;
+    DevBuf d_grows{HALF};  // hm_dmr_fetch_regions: the tested rows of one context (64 B each), allocated by its first call
     // `samplecorr` ("samples" = N), all of it only with the option on: N uint16 level planes of sample_stride values each (2 N B
     // per base), resident from hm_pileup_set_reference on; the samples opened so far (the last one is the open one); the table of
     // a fetch, 3 x N (N + 1) / 2 x 6 uint64
@@ -3651,6 +3723,57 @@ int hm_group_qvalues(const hm_group_t* rows, int64_t n, double* q, uint64_t m[3]
     return HM_OK;
 }
 
+// ---- `groupdmr` -------------------------------------------------------------------------------------------------------------------
+int64_t hm_dmr_fetch_regions(hm_pileup_t* p, int64_t lo, int64_t hi, int32_t min_reps, int32_t ctx, double max_p, double min_diff,
+                             int64_t max_gap, int32_t min_loci, int32_t keep_edges, int64_t* n_ctx_rows, int64_t* n_hits,
+                             hm_group_region_t* out, int64_t cap) {
+    if (!p) return HM_EINVAL;
+    if (min_reps < 1 || min_reps > GROUP_MAX_SAMPLES) return pfail(p, HM_EINVAL, "hm_dmr_fetch_regions: min_reps must be in 1 .. 255");
+    if (ctx < 0 || ctx > 2) return pfail(p, HM_EINVAL, "hm_dmr_fetch_regions: ctx must be 0, 1 or 2");
+    if (!(max_p > 0.0 && max_p <= 1.0)) return pfail(p, HM_EINVAL, "hm_dmr_fetch_regions: max_p must be in (0, 1]");
+    if (!(min_diff >= 0.0 && min_diff <= 100.0)) return pfail(p, HM_EINVAL, "hm_dmr_fetch_regions: min_diff must be in [0, 100]");
+    if (max_gap < 1 || min_loci < 1) return pfail(p, HM_EINVAL, "hm_dmr_fetch_regions: max_gap and min_loci must be >= 1");
+    const int rc = option_range(p, "hm_dmr_fetch_regions", group_needs(p), lo, hi);
+    if (rc != HM_OK) return rc;
+    if (n_ctx_rows) *n_ctx_rows = 0;
+    if (n_hits) *n_hits = 0;
+    if (hi == lo) return 0;
+    const GroupPlanes s = group_planes(p);
+    return guarded(p, [&]() -> int64_t {
+        const int64_t R = stage_rows(  // the context's rows, tested, stay in d_grows
+            p, GroupCtxSel{GroupSel{s, min_reps}, (uint32_t)ctx}, lo, hi, p->d_grows,
+            [&](int64_t) {
+                ensure_group_coef(p);
+                return true;
+            },
+            [&](hm_group_t* rows, int64_t n) {
+                hipLaunchKernelGGL(group_test_kernel, row_grid(n), dim3(TPB), 0, p->stream, rows, n, s, p->d_gcoef.as<double>());
+            });
+        if (R <= 0) return R;
+        if (n_ctx_rows) *n_ctx_rows = R;
+        const hm_group_t* rows = p->d_grows.as<hm_group_t>();
+        const GroupRegionRule rule{{max_p, max_gap, min_loci, keep_edges != 0}, min_diff};
+        if (n_hits) {  // counted, never written
+            const int64_t hits = stage_rows(p, GroupHitSel{rows, rule}, 0, R, p->d_rows, [](int64_t) { return false; }, no_hook);
+            if (hits < 0) return hits;
+            *n_hits = hits;
+        }
+        return compact_rows(p, RegionSel<GroupChain>{rows, R, rule, (uint32_t)ctx}, 0, R, out, cap, no_hook, no_hook);
+    });
+}
+
+int hm_dmr_p_cutoff(const hm_group_t* rows, const double* q, int64_t n, double max_q, double cutoff[3]) {
+    if (n < 0 || (n && (!rows || !q)) || !cutoff || !(max_q > 0.0 && max_q <= 1.0)) return HM_EINVAL;
+    for (int64_t i = 0; i < n; ++i)
+        if (rows[i].motif > 3u || !(rows[i].pvalue >= DBL_MIN && rows[i].pvalue <= 1.0)) return HM_EINVAL;
+    cutoff[0] = cutoff[1] = cutoff[2] = 0.0;
+    for (int64_t i = 0; i < n; ++i) {
+        double& c = cutoff[std::min(rows[i].motif, 2u)];
+        if (q[i] <= max_q && rows[i].pvalue > c) c = rows[i].pvalue;
+    }
+    return HM_OK;
+}
+
 // ---- `samplecorr` -----------------------------------------------------------------------------------------------------------------
 int hm_sample_geometry(int64_t out[2]) {
     if (!out) return HM_EINVAL;
@@ -4050,7 +4173,7 @@ int64_t hm_pileup_fetch_asm_regions(hm_pileup_t* p, const void* pcov1, const voi
             [&](hm_asm_t* rows, int64_t n) { test_rows(p, rows, n); });
         if (R <= 0) return R;
         if (n_ctx_rows) *n_ctx_rows = R;
-        const RegionSel chains{p->d_arows.as<hm_asm_t>(), R, RegionRule{max_p, max_gap, min_loci, keep_edges != 0}, (uint32_t)ctx};
+        const RegionSel<AsmChain> chains{p->d_arows.as<hm_asm_t>(), R, RegionRule{max_p, max_gap, min_loci, keep_edges != 0}, (uint32_t)ctx};
         return compact_rows(p, chains, 0, R, out, cap, no_hook, no_hook);
     });
 }

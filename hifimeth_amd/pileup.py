@@ -36,6 +36,10 @@ sample of group 1 or 2 and `pu.load_sample_loci(*read_cov_bed(...))` adds its ro
 with enough replicates on both sides (GROUP_DTYPE: pooled counts, diff, likelihood ratio D, dispersion phi, pvalue of the F test on
 D / phi), `group_qvalues(rows)` their BH q per context, `pu.groups_bed(rows, q)` and `groups_summary_tsv(rows, q, m)` the text of
 <prefix>.groups.<ctx>.bed and <prefix>.groups.summary.tsv.  include/hifimeth_hip.h has the definition of the statistic.
+Regions between the groups (`hifimeth-hip groupdmr`): `pu.group_regions(ctx, lo, hi, min_reps, max_p, min_diff, max_gap, min_loci,
+keep_edges)` chains those loci on the device as asm_regions chains the haplotypes' (GROUP_REGION_DTYPE) and returns (rows,
+n_ctx_rows, n_hits); `group_p_cutoff(rows, q, max_q)` turns a q threshold into the max_p of each context, `stitch_group_regions`
+joins adjacent ranges, `pu.group_regions_bed(rows)` and `groupdmr_summary_tsv` are the text of <prefix>.groupdmr.*.
 
 N samples (`hifimeth-hip samplecorr`): on an engine made with samples=N, `pu.open_sample()` opens the next sample and
 `pu.load_sample(*read_cov_bed(...))` writes its rows into its uint16 level plane; `pu.sample_sums(lo, hi, complete=False)` returns
@@ -147,7 +151,10 @@ ASM_BIN_DTYPE = np.dtype([("bin", "<u4"), ("reserved", "<u4"), ("count", "<u8"),
 ASM_REGION_DTYPE = np.dtype([("start", "<i8"), ("end", "<i8"), ("pcov1", "<i8"), ("ncov1", "<i8"), ("pcov2", "<i8"), ("ncov2", "<i8"),
                              ("n_loci", "<i4"), ("sign", "<i4"), ("motif", "<u4"), ("flags", "<u4"), ("diff", "<f8"),
                              ("pmin", "<f8")])                                      # hm_asm_region_t, 80 bytes
-REGION_FIRST, REGION_LAST = 1, 2                                                      # HM_REGION_FIRST, HM_REGION_LAST
+GROUP_REGION_DTYPE = np.dtype([("start", "<i8"), ("end", "<i8"), ("pcov1", "<i8"), ("ncov1", "<i8"), ("pcov2", "<i8"), ("ncov2", "<i8"),
+                               ("n_loci", "<i4"), ("sign", "<i4"), ("motif", "<u4"), ("flags", "<u4"), ("m1_min", "<u2"), ("m2_min", "<u2"),
+                               ("reserved", "<u4"), ("diff", "<f8"), ("pmin", "<f8"), ("phi_max", "<f8")])  # hm_group_region_t, 96 bytes
+REGION_FIRST, REGION_LAST = 1, 2                                                    # HM_REGION_FIRST, HM_REGION_LAST
 ASM_T, ASM_PAIRS = 64, 2080                                                           # HM_ASM_T, HM_ASM_PAIRS
 ASM_BINS = 3 * ASM_PAIRS * ASM_PAIRS                                                  # HM_ASM_BINS
 SITE_DTYPE = np.dtype([("gpos", "<i8"), ("pcov", "<i4"), ("ncov", "<i4"), ("motif", "<u4"), ("reserved", "<u4"), ("pvalue", "<f8"),
@@ -332,6 +339,28 @@ def groups_summary_tsv(rows: np.ndarray, q: np.ndarray, m) -> str:
                                               int(((ctx == c) & (rows["phi"] > 1.0)).sum())) for c in range(3))
 
 
+def group_p_cutoff(rows: np.ndarray, q: np.ndarray, max_q: float) -> np.ndarray:
+    """`groupdmr -F` (hm_dmr_p_cutoff, host only): -> cutoff[3]: per context the largest pvalue among the rows with q <= max_q, 0
+    where there is none.  q is monotone in p, so the rows with q <= max_q are those with pvalue <= cutoff: group_regions with
+    max_p = cutoff[ctx] chains them; a context whose cutoff is 0 has no regions.  rows, q: group_tests' and group_qvalues' of the job."""
+    rows = np.ascontiguousarray(rows, GROUP_DTYPE)
+    q = np.ascontiguousarray(q, np.float64)
+    assert q.shape == (len(rows),)
+    cutoff = np.zeros(3, np.float64)
+    if lib().hm_dmr_p_cutoff(rows.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p), len(rows), float(max_q),
+                               cutoff.ctypes.data_as(C.c_void_p)) != 0:
+        raise HifimethError("hm_dmr_p_cutoff: max_q outside (0, 1], a motif above 3 or a p outside [DBL_MIN, 1]")
+    return cutoff
+
+
+def groupdmr_summary_tsv(tested, hits, cutoff, regions) -> str:
+    """the text of <prefix>.groupdmr.summary.tsv: per context ctx, tested loci, hits, the p cutoff used (nan: none), regions, loci
+    in regions, regions +, regions -.  tested[c], hits[c]: summed over the fetches of context c; regions[c]: all its rows"""
+    return "".join("%s\t%d\t%d\t%s\t%d\t%d\t%d\t%d\n" % (
+        CTX_NAMES[c], tested[c], hits[c], _g6(float(cutoff[c])), len(regions[c]), int(regions[c]["n_loci"].sum()),
+        int((regions[c]["sign"] > 0).sum()), int((regions[c]["sign"] < 0).sum())) for c in range(3))
+
+
 def sample_geometry() -> Tuple[int, int]:
     """-> (HM_SAMPLE_TILE, HM_SAMPLE_MAX) of the library: the positions a workgroup of sample_sums takes at a time, the most samples"""
     out = np.zeros(2, np.int64)
@@ -441,7 +470,26 @@ def stitch_asm_regions(parts, max_gap: int, min_loci: int, keep_edges: bool = Fa
     and the one that holds the next non-empty part's first row (FIRST) are one chain when they have the same sign and
     right.start - (left.end - 1) <= max_gap: sums and n_loci add, pmin is the minimum, diff is recomputed from the sums; a chain
     may span many parts.  FIRST / LAST survive only on a chain that reaches the first / last row of the whole."""
-    parts = [(np.ascontiguousarray(r, ASM_REGION_DTYPE), int(n)) for r, n in parts if int(n)]
+    return _stitch_regions(parts, max_gap, min_loci, keep_edges, ASM_REGION_DTYPE, lambda whole, more: None)
+
+
+def _merge_group_region(whole, more) -> None:
+    for c in ("m1_min", "m2_min"):
+        whole[c] = min(whole[c], more[c])
+    whole["phi_max"] = max(whole["phi_max"], more["phi_max"])
+
+
+def stitch_group_regions(parts, max_gap: int, min_loci: int, keep_edges: bool = False) -> Tuple[np.ndarray, int]:
+    """stitch_asm_regions for group_regions: parts = [(rows, n_ctx_rows)] of group_regions(..., keep_edges=True) over adjacent
+    ranges of one sequence and one context, ascending, all with the same max_p / min_diff / max_gap / min_loci.  -> (rows,
+    n_ctx_rows) equal, byte for byte, to one fetch over the union with this keep_edges.  Where two chains are one, m1_min and
+    m2_min also take the minimum and phi_max the maximum.  Host only."""
+    return _stitch_regions(parts, max_gap, min_loci, keep_edges, GROUP_REGION_DTYPE, _merge_group_region)
+
+
+def _stitch_regions(parts, max_gap: int, min_loci: int, keep_edges: bool, dtype, merge) -> Tuple[np.ndarray, int]:
+    """the walk both stitches share; merge(whole, more) folds in what the family's chains carry beyond sums, n_loci and pmin"""
+    parts = [(np.ascontiguousarray(r, dtype), int(n)) for r, n in parts if int(n)]
     out: List[np.ndarray] = []
     open_ = None                                  # the chain that holds the last row seen so far, if that row is a hit
     for k, (rows, _) in enumerate(parts):
@@ -457,6 +505,7 @@ def stitch_asm_regions(parts, max_gap: int, min_loci: int, keep_edges: bool = Fa
                 open_["flags"] |= g["flags"]
                 P1, N1, P2, N2 = (np.float64(open_[c]) for c in ("pcov1", "ncov1", "pcov2", "ncov2"))
                 open_["diff"] = np.float64(100.0) * P1 / (P1 + N1) - np.float64(100.0) * P2 / (P2 + N2)
+                merge(open_, g)
             else:
                 out.append(g)
                 open_ = g
@@ -465,7 +514,7 @@ def stitch_asm_regions(parts, max_gap: int, min_loci: int, keep_edges: bool = Fa
         if not len(rows) or not int(rows[-1]["flags"]) & REGION_LAST:
             open_ = None
     keep = [g for g in out if g["n_loci"] >= min_loci or (keep_edges and g["flags"])]
-    rows = np.array(keep, ASM_REGION_DTYPE) if keep else np.zeros(0, ASM_REGION_DTYPE)
+    rows = np.array(keep, dtype) if keep else np.zeros(0, dtype)
     return rows, sum(n for _, n in parts)
 
 
@@ -1177,6 +1226,32 @@ class MethylationPileup:
         for s, k, r, qv in zip(sid, soff, rows, q):
             text[CTX_NAMES[min(int(r["motif"]), 2)]].append("%s\t%d\t%d\t%g\t%.6g\t%.6g\t%d\t%d\t%d\t%d\t%d\t%d\t%.6g\n" % (
                 self.names[s], k, k + 1, r["diff"], r["pvalue"], qv, r["m1"], r["pcov1"], r["ncov1"], r["m2"], r["pcov2"], r["ncov2"], r["phi"]))
+        return {k: "".join(v) for k, v in text.items()}
+
+    def group_regions(self, ctx: int, lo: int = 0, hi: Optional[int] = None, min_reps: int = 2, max_p: float = 0.01, min_diff: float = 0.0,
+                      max_gap: int = 500, min_loci: int = 3, keep_edges: bool = False) -> Tuple[np.ndarray, int, int]:
+        """`groupdmr` (hm_dmr_fetch_regions) -> (rows, n_ctx_rows, n_hits): the chains of context ctx among the
+        group_tests() rows of [lo, hi), ascending (GROUP_REGION_DTYPE), the number of those rows and of the hits among them.  A row
+        is a hit when pvalue <= max_p, diff != 0 and |diff| >= min_diff; linking, chains, min_loci, keep_edges and flags as in
+        asm_regions.  Per chain also the largest phi and the fewest counting samples of each group among its rows.  The rows are
+        staged and tested on the device; none comes to the host."""
+        hi = self.n_loci if hi is None else hi
+        n_ctx_rows, n_hits = C.c_int64(0), C.c_int64(0)
+        rows = self._rows(self._L.hm_dmr_fetch_regions, GROUP_REGION_DTYPE, lo, hi, min_reps, ctx, max_p, min_diff, max_gap,
+                          min_loci, int(bool(keep_edges)), C.byref(n_ctx_rows), C.byref(n_hits))
+        return rows, int(n_ctx_rows.value), int(n_hits.value)
+
+    def group_regions_bed(self, rows: np.ndarray) -> dict:
+        """the text of <prefix>.groupdmr.{CpG,CHG,CHH}.bed: chrom, start, end, <ctx>_<k> (k from 1 in the order of rows), n_loci, .,
+        +|-, diff, pmin, m1_min, pcov1, ncov1, m2_min, pcov2, ncov2, phi_max.  rows: every region of the job, per context in file
+        order (sequence by sequence)."""
+        sid, soff = locate(self.offsets, rows["start"])
+        text = {k: [] for k in CTX_NAMES}
+        for s, k, r in zip(sid, soff, rows):
+            name = CTX_NAMES[int(r["motif"])]
+            text[name].append("%s\t%d\t%d\t%s_%d\t%d\t.\t%s\t%g\t%.6g\t%d\t%d\t%d\t%d\t%d\t%d\t%.6g\n" % (
+                self.names[s], k, k + (r["end"] - r["start"]), name, len(text[name]) + 1, r["n_loci"], "+" if r["sign"] > 0 else "-",
+                r["diff"], r["pmin"], r["m1_min"], r["pcov1"], r["ncov1"], r["m2_min"], r["pcov2"], r["ncov2"], r["phi_max"]))
         return {k: "".join(v) for k, v in text.items()}
 
     def open_sample(self) -> int:

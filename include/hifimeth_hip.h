@@ -511,6 +511,39 @@ int hm_pileup_group_planes(hm_pileup_t* p, int32_t part, int64_t lo, int64_t hi,
  * p.adjust(method = "BH")): equal p gives equal q.  m[ctx] receives the number of rows per context.  HM_EINVAL for a motif above 3
  * or a pvalue outside [DBL_MIN, 1]. */
 int hm_group_qvalues(const hm_group_t* rows, int64_t n, double* q, uint64_t m[3]);
+/* Differentially methylated regions between the groups (`groupdmr`): the chains of hm_asm_region_t above, over group rows.  Per
+ * context c and plane range [lo, hi).  ROWS r_0 .. r_{R-1}: the rows hm_pileup_fetch_groups returns for [lo, hi) and min_reps whose
+ * min(motif, 2) == c, ascending in gpos, each with the diff and pvalue of that call, bit for bit (the same kernel, a pure function
+ * of the planes at the locus); a locus of another context, or one that is not tested, is no row and neither links nor breaks
+ * anything.  Row i is a HIT when pvalue_i <= max_p, diff_i != 0 and |diff_i| >= min_diff; its sign is that of diff_i.  LINKED,
+ * CHAIN, start, end, the four sums, diff, pmin, sign, flags and what is returned for (min_loci, keep_edges): word for word as for
+ * hm_asm_region_t -- a tested row of the context that is no hit breaks a chain.  Also per chain: phi_max = the largest phi among
+ * its rows, that row's bits; m1_min / m2_min = the smallest m1 / m2 among its rows.  Comparisons and integer sums only: nothing
+ * depends on launch geometry.  There is no region-level p-value, for the reason given there; a test of the samples' levels over
+ * these regions (hm_sample_interval_test) is descriptive only when it uses the samples the regions were found from. */
+typedef struct {            /* one chain = one row of <prefix>.groupdmr.<ctx>.bed; 96 bytes */
+    int64_t start, end;
+    int64_t pcov1, ncov1, pcov2, ncov2;   /* exact sums of the rows' pooled group counts */
+    int32_t n_loci, sign;
+    uint32_t motif, flags;                /* motif = c; HM_REGION_FIRST / HM_REGION_LAST */
+    uint16_t m1_min, m2_min;              /* fewest counting samples of a group at any locus of the chain */
+    uint32_t reserved;                    /* 0 */
+    double diff, pmin, phi_max;
+} hm_group_region_t;
+/* The chains of context ctx in the engine's planes [lo, hi), ascending in start: those with n_loci >= min_loci and, when
+ * keep_edges != 0, also every chain with flags != 0 whatever its length.  The rows are staged and tested on the device and never
+ * visit the host (64 B per row of the context in a buffer the first call allocates).  Returns the number of regions (may exceed
+ * cap, or out NULL: then nothing is written); *n_ctx_rows receives R and *n_hits the number of hits, either may be NULL.  hi == lo
+ * returns 0.  Errors as hm_pileup_fetch_groups; HM_EINVAL also for ctx outside 0..2, max_p NaN or outside (0, 1], min_diff NaN or
+ * outside [0, 100], max_gap < 1 and min_loci < 1. */
+int64_t hm_dmr_fetch_regions(hm_pileup_t* p, int64_t lo, int64_t hi, int32_t min_reps, int32_t ctx, double max_p, double min_diff,
+                             int64_t max_gap, int32_t min_loci, int32_t keep_edges, int64_t* n_ctx_rows, int64_t* n_hits,
+                             hm_group_region_t* out, int64_t cap);
+/* Host only.  cutoff[c] = the largest pvalue among the rows of context c whose q is <= max_q, or 0 when there is none; q = what
+ * hm_group_qvalues gave for the same rows.  BH q is monotone in p, so {q <= max_q} == {pvalue <= cutoff[c]}: chaining "by q" is
+ * hm_dmr_fetch_regions with max_p = cutoff[c], and a context whose cutoff is 0 has no regions.  HM_EINVAL for max_q NaN
+ * or outside (0, 1] and for what hm_group_qvalues refuses. */
+int hm_dmr_p_cutoff(const hm_group_t* rows, const double* q, int64_t n, double max_q, double cutoff[3]);
 
 /* ---- N samples (`samplecorr`): the sample-by-sample correlation matrix per context ---------------------------
  * There are N samples, 2 <= N <= 64 (HM_SAMPLE_MAX).  Sample s has, at a locus, k methylated and n total calls.  It COUNTS there

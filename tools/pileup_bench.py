@@ -224,6 +224,46 @@ def sample_intervals_leg(check):
     print(json.dumps(out))
 
 
+def group_regions_leg(repeat, check):
+    """`groupdmr`: hm_dmr_fetch_regions of one context over a reference of 2^26 bases with 2^22 loci per sample (3 + 3
+    samples; stretches of 2^12 bases in which group 1 lies above group 2, below it or level with it), beside hm_pileup_fetch_groups
+    over the same range in the same run -- the rows of all three contexts copied to the host, which `groupdmr` without -F and -L
+    never does; a leg of its own: nothing else is run.  Each call is timed `repeat` times after one warm-up call."""
+    BASES, ROWS, STRETCH = 1 << 26, 1 << 22, 1 << 12
+    rng = np.random.default_rng(17)
+    step = BASES // ROWS
+    pu = MethylationPileup([("chr1", BASES)], partitions=True, groups=True, bases=np.full(BASES, ord("N"), np.uint8))
+    g = np.arange(ROWS, dtype=np.int64) * step + rng.integers(0, step, ROWS)          # a locus per 16 bases, the same in every sample
+    motif = rng.choice(3, ROWS, p=[0.6, 0.2, 0.2])
+    state = rng.choice([1, -1, 0], BASES // STRETCH, p=[0.2, 0.2, 0.6])[g // STRETCH]
+    for part in (1, 2):
+        for s in range(3):
+            cov = rng.integers(5, 40, ROWS)
+            p = rng.binomial(cov, 0.5 + (0.3 if part == 1 else -0.3) * state)
+            assert pu.begin_sample(part) == s and pu.load_sample_loci(g, p, cov - p, motif) == ROWS
+    calls = (("fetch_groups", lambda: pu.group_tests(0, BASES, 2)),
+             ("fetch_group_regions", lambda: pu.group_regions(0, 0, BASES, 2, 0.01, 0.0, 500, 3)))
+    secs, got = {}, {}
+    for name, call in calls:
+        call()                                                # warm-up: the code objects, the buffers
+        secs[name] = []
+        for _ in range(repeat):
+            t0 = time.perf_counter()
+            got[name] = call()
+            secs[name].append(time.perf_counter() - t0)
+    rows, (regions, n_ctx_rows, n_hits) = got["fetch_groups"], got["fetch_group_regions"]
+    out = dict(group_regions_reference_bases=BASES, group_regions_loci_per_sample=ROWS, group_regions_tested_rows=len(rows),
+               group_regions_ctx_rows=n_ctx_rows, group_regions_hits=n_hits, group_regions_regions=len(regions),
+               group_regions_call_s={k: [round(x, 4) for x in v] for k, v in secs.items()},
+               group_regions_best_s={k: round(min(v), 4) for k, v in secs.items()})
+    if check:                                      # the context's rows and hits are those of the per-locus fetch
+        r0 = rows[np.minimum(rows["motif"], 2) == 0]
+        out["check_group_regions_counts"] = bool(len(r0) == n_ctx_rows and int(((r0["pvalue"] <= 0.01) & (r0["diff"] != 0)).sum()) == n_hits
+                                                 and int(regions["n_loci"].sum()) <= n_hits and len(regions) > 0)
+    pu.close()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--genome-mb", type=float, default=20)
@@ -270,7 +310,12 @@ def main():
     ap.add_argument("--sample-intervals", action="store_true",
                     help="time the interval sums of `regiondiff` (hm_sample_fetch_intervals): 6 samples, 2^20 tiles of 256 bases over 2^28 bases, "
                          "against hm_pileup_fetch_regions on the same tiles over the combined planes; a leg of its own: nothing else is run")
+    ap.add_argument("--group-regions", action="store_true",
+                    help="time the regions of `groupdmr` (hm_dmr_fetch_regions): 3 + 3 samples of 2^22 loci over 2^26 bases, one context, "
+                         "against hm_pileup_fetch_groups over the same range; a leg of its own: nothing else is run")
     a = ap.parse_args()
+    if a.group_regions:
+        return group_regions_leg(a.repeat, a.check)
     if a.context:
         return context_leg(a.context, a.repeat, a.check)
     if a.sample_intervals:
