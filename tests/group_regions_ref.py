@@ -7,6 +7,9 @@ diff_i != 0 and |diff_i| >= min_diff (with q given: q_i <= max_q instead of the 
 LINKED when both are hits of one sign and gpos_i - gpos_{i-1} <= max_gap.  A CHAIN is a maximal run of consecutively linked hits.
 Returned, ascending: the chains with n_loci >= min_loci and, with keep_edges, every chain that holds the first or the last row.
 
+regions() walks the rows in Python (chains_walk, or chains_union_find as a second formulation); regions_fast() is the same in
+whole-array numpy, for the millions of rows of tests/test_gpu_pileup_group_regions_scale.py.
+
 crafted_rows() are hand-written rows; layout() is what the GPU test loads so that the engine's own rows show every case;
 dataset() is its random 3 + 3 data set and dataset_rows() the rows of that data set from groups_ref.stat_f64."""
 import functools
@@ -107,6 +110,49 @@ def regions(rows, ctx, max_p, min_diff, max_gap, min_loci, keep_edges=False, q=N
     r = rows[sel]
     sign = signs(r, max_p, min_diff, None if q is None else np.asarray(q)[sel], max_q)
     return _select(chains_of(r, sign, max_gap), r, ctx, min_loci, keep_edges), len(r), int(np.count_nonzero(sign))
+
+
+def pooled_diff_of(P1, N1, P2, N2):
+    """pooled_diff on int64 arrays: the same three operations, each rounded once per element"""
+    P1, N1, P2, N2 = (np.asarray(x, np.int64).astype(np.float64) for x in (P1, N1, P2, N2))
+    return np.float64(100.0) * P1 / (P1 + N1) - np.float64(100.0) * P2 / (P2 + N2)
+
+
+def regions_fast(rows, ctx, max_p, min_diff, max_gap, min_loci, keep_edges=False, q=None, max_q=None):
+    """regions() a third time, without a loop over rows or chains, for millions of rows: the links as one mask, a chain's head a hit
+    not linked to the row in front of it, its tail a hit to which the next row is not linked, every per-chain quantity a reduceat
+    over [head, tail + 1).  -> (regions, R, hits), equal to regions()'s byte for byte"""
+    sel = ctx_mask(rows, ctx)
+    r = rows[sel]
+    sign = signs(r, max_p, min_diff, None if q is None else np.asarray(q)[sel], max_q)
+    n, hit = len(r), sign != 0
+    hits = int(np.count_nonzero(hit))
+    if not hits:
+        return np.zeros(0, REGION_DTYPE), n, 0
+    link = hit[1:] & (sign[1:] == sign[:-1]) & (np.diff(r["gpos"]) <= max_gap)
+    head, tail = hit.copy(), hit.copy()
+    head[1:] &= ~link
+    tail[:-1] &= ~link
+    first, last = np.flatnonzero(head), np.flatnonzero(tail)
+    assert len(first) == len(last) and (first <= last).all()
+    flags = np.where(first == 0, FIRST, 0) | np.where(last == n - 1, LAST, 0)
+    keep = (last - first + 1 >= min_loci) | ((flags != 0) if keep_edges else False)
+    first, last, flags = first[keep], last[keep], flags[keep]
+    g = np.zeros(len(first), REGION_DTYPE)
+    if not len(g):
+        return g, n, hits
+    # reduceat reduces [idx[k], idx[k + 1]): heads and ends interleaved, the even results are the chains'; one padding element
+    # so that the end of a chain with the last row is an index
+    idx = np.stack([first, last + 1], axis=1).ravel()
+    over = lambda op, x: op.reduceat(np.concatenate([x, x[:1]]), idx)[::2]
+    g["start"], g["end"] = r["gpos"][first], r["gpos"][last] + 1
+    for f in ("pcov1", "ncov1", "pcov2", "ncov2"):
+        g[f] = over(np.add, r[f].astype(np.int64))
+    g["n_loci"], g["sign"], g["motif"], g["flags"] = last - first + 1, sign[first], ctx, flags
+    g["m1_min"], g["m2_min"] = over(np.minimum, r["m1"]), over(np.minimum, r["m2"])
+    g["diff"] = pooled_diff_of(g["pcov1"], g["ncov1"], g["pcov2"], g["ncov2"])
+    g["pmin"], g["phi_max"] = over(np.minimum, r["pvalue"]), over(np.maximum, r["phi"])
+    return g, n, hits
 
 
 def p_cutoff(p, q, motif, max_q):
