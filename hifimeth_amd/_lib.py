@@ -96,6 +96,7 @@ def lib():
         "hm_batch_release": (C.c_int, [vp]),
         "hm_scan_sites": (i64, [vp, C.c_int, vp, vp, vp, i64]),
         "hm_site_logits": (i64, [vp, C.c_int, vp, i64]),
+        "hm_debug_edge_rows": (C.c_int, [vp, i64, vp]),
         "hm_windows": (C.c_int, [vp, C.c_int, i64, i64, vp]),
         "hm_cnn_logits": (C.c_int, [vp, C.c_int, vp, i64, vp, vp, vp]),
         "hm_debug_layer": (i64, [vp, C.c_int, vp, C.c_int, vp, i64]),

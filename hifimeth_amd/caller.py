@@ -215,6 +215,14 @@ class MethylationCaller:
         got = self._check(self._L.hm_site_logits(self._h, ctx, _vp(out), n), "hm_site_logits")
         return out[:got]
 
+    def edge_rows(self, sites: int) -> np.ndarray:
+        """The edge kernel's rows [sites, 2, 192] uint16 (fp16 bit patterns, [hi 96 | lo 96] per side) of the last read group and
+        context the dense trunk path ran (hm_debug_edge_rows)."""
+        self.sync()
+        out = np.empty((sites, 2, 192), np.uint16)
+        self._check(self._L.hm_debug_edge_rows(self._h, sites, _vp(out)), "hm_debug_edge_rows")
+        return out
+
     def windows(self, ctx: int, first: int = 0, n: Optional[int] = None, fetch: bool = True):
         """get_next_sample_features for sites [first, first+n) of context ctx -> float32 [n, 401, 8]."""
         if n is None:

@@ -47,7 +47,14 @@ struct EdgeGeo {
     static constexpr int R1 = -201 + 2 * (2 * (L2 - 1) - 1), R2 = -203 + 4 * (2 * (L3 - 1) - 1), R3 = -207 + 8 * (2 * (C4_LEN - 1) - 1);
     static constexpr int LEFT = -199;
     static constexpr int X_LEFT = -201, X_RIGHT = -201 + 2 * (L1 - 1);  // first feature row of conv1's first / last output
+    // An E1 row is conv1 over the K1 feature rows from its own position on, so the E1 rows a site's chains read (LEFT; R1, and R1 + 2
+    // where conv2's last window does not end on the padding) and conv1's two padded outputs draw on TWO spans of EG_XROWS feature rows:
+    // [X_LEFT, X_LEFT + 16) and [R1, R1 + 16), with the right padding in slot X_PAD of the right span (slot 16 = the row's pad chunk)
+    static constexpr int NE1 = PAD2 ? 2 : 3;               // interior E1 rows per site
+    static constexpr int X_PAD = X_RIGHT + K1 - 1 - R1;    // slot of the right span that lies on conv1's zero padding
 };
+static_assert(EdgeGeo<11>::X_RIGHT - EdgeGeo<11>::R1 == 2 && EdgeGeo<11>::X_PAD == 12 && EdgeGeo<13>::X_RIGHT - EdgeGeo<13>::R1 == 4 && EdgeGeo<13>::X_PAD == 16 &&
+              EdgeGeo<11>::LEFT - EdgeGeo<11>::X_LEFT == 2, "feature spans of the edge kernel's E1 rows");
 static_assert(EdgeGeo<11>::PAD2 && EdgeGeo<11>::PAD3 && !EdgeGeo<11>::PAD4 && EdgeGeo<11>::R1 == 189 && EdgeGeo<11>::R2 == 185 && EdgeGeo<11>::R3 == 169, "k1 = 11 edge geometry");
 static_assert(!EdgeGeo<13>::PAD2 && !EdgeGeo<13>::PAD3 && EdgeGeo<13>::PAD4 && EdgeGeo<13>::R1 == 185 && EdgeGeo<13>::R2 == 177 && EdgeGeo<13>::R3 == 169, "k1 = 13 edge geometry");
 

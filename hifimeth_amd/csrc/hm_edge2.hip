@@ -116,7 +116,12 @@ struct E2Site {
 
 }  // namespace
 
-template <int K1>
+// E1C (engine option edge_impl = 2, the default): the kernel COMPUTES the E1 rows its chains read -- LEFT, R1 and, for K1 = 13, R1 + 2:
+// conv1 over feature rows the kernel builds anyway -- instead of gathering them from the trunk's E1 map: the trunk then stores no E1
+// row and the map does not exist.  Same folded weights, same stacked product in ascending k-block order from the bias, ReLU + split4
+// as trunk3_kernel's conv1 (no padding correction: these rows lie inside the window; a position outside the read has all-zero feature
+// rows there as here), written straight into the map set conv2 reads: the same bytes as the gathered rows.
+template <int K1, bool E1C>
 __global__ __launch_bounds__(512) void edge2_kernel(SiteRange sr, const RInfo* __restrict__ rinfo, const uint8_t* __restrict__ bases,
                                                      const uint32_t* __restrict__ kin, CtxWeights W, TrunkMaps mp,
                                                      uint16_t* __restrict__ edge4, int32_t* __restrict__ e4row) {
@@ -131,6 +136,9 @@ __global__ __launch_bounds__(512) void edge2_kernel(SiteRange sr, const RInfo* _
     half_t* sp_hi = smem + 2 * E2_MSET;
     half_t* sp_lo = sp_hi + E2_SPLANE;
     half_t* xb = sp_lo + E2_SPLANE;                  // feature rows of conv1's edge outputs: [pseudo-row][16 rows][8 halves] + pad
+    // LDS plan: two map sets of 96 rows (E1C: conv2's holds the rows conv1 computed), the two output planes, the feature rows -- E1C
+    // needs no more of them: the E1 rows' spans are the 16 rows a pseudo-row has always had (EdgeGeo)
+    static_assert(sizeof(smem) == 2 * 51200 + 2 * 17408 + 17408 && EdgeGeo<K1>::X_PAD <= EG_XROWS && 2 * (EdgeGeo<K1>::NE1 - 2) + K1 <= EG_XROWS, "LDS plan");
     if ((int)blockIdx.x * EG_S >= n_sites) return;
     // (every per-lane constant is re-derived from an opaque copy of the thread index at the top of each pass: hoisted out of the
     //  pass loop, the DMA source arithmetic and the weight pointers of all layers would sit in registers for the whole launch)
@@ -175,7 +183,8 @@ __global__ __launch_bounds__(512) void edge2_kernel(SiteRange sr, const RInfo* _
             (&rt[0][0])[tid] = (int32_t)((int64_t)view * mp.view_rows + nd.ri.map_off + TR_PAD + off + delta);
         }
     };
-    // feature rows of conv1's first / last output: K1 rows per pseudo-row, the one on the zero padding all zeros.
+    // feature rows of conv1's first / last output: K1 rows per pseudo-row, the one on the zero padding all zeros (E1C: all 16 rows of
+    // the two spans of EdgeGeo, which hold the E1 rows' feature rows as well).
     // Thread t of NT: rows [NR (t % PER), + NR) of pseudo-row t / PER (PER = 16 / NR) -- the site's descriptor is read once, all loads
     // are issued before the first is used (clamped addresses, no branches); `between()` runs after the loads are issued.
     auto build_rows = [&](const E2Site* si, const int t, auto nt_, auto between) __attribute__((always_inline)) {
@@ -189,9 +198,9 @@ __global__ __launch_bounds__(512) void edge2_kernel(SiteRange sr, const RInfo* _
 #pragma unroll
         for (int u = 0; u < NR; ++u) {
             const int tt = t0 + u;
-            const int x = es.off + (side ? G::X_RIGHT : G::X_LEFT) + tt;
-            const bool is_pad = side ? tt == K1 - 1 : tt == 0;
-            live[u] = tt < K1 && !is_pad && x >= 0 && x < es.L;
+            const int x = es.off + (side ? (E1C ? G::R1 : G::X_RIGHT) : G::X_LEFT) + tt;
+            const bool is_pad = side ? tt == (E1C ? G::X_PAD : K1 - 1) : tt == 0;
+            live[u] = (E1C || tt < K1) && !is_pad && x >= 0 && x < es.L;
             const int xc = min(max(x, 0), es.L - 1);
             const int64_t j = es.bo + (es.view ? es.L - 1 - xc : xc);
             b[u] = bases[j];
@@ -262,37 +271,67 @@ __global__ __launch_bounds__(512) void edge2_kernel(SiteRange sr, const RInfo* _
         const int col = wave * 16 + 4 * lk;
         h.bz = *reinterpret_cast<const float4*>(W.c1f_bias + col);
     };
-    auto conv1 = [&](const Head1& h) __attribute__((always_inline)) {
+    auto conv1 = [&](const Head1& h, half_t* e1set) __attribute__((always_inline)) {
         // the folded bn0 constant must not count for the tap on the zero padding (c1f_corr, hm_weights.cpp): first output row (left
         // chains), last output row (right chains); requested here, used in the epilogue
         const float4 c0 = *reinterpret_cast<const float4*>(W.c1f_corr + wave * 16 + 4 * lk);
         const float4 c1 = *reinterpret_cast<const float4*>(W.c1f_corr + 128 + wave * 16 + 4 * lk);
-        f32x4 acc[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i] = f32x4{h.bz.x, h.bz.y, h.bz.z, h.bz.w};
         // window row of tap slot 4 kb + lk: slots >= K1 walk the same rows again with the lo halves
         auto stack_off = [&](int kb) __attribute__((always_inline)) {
             int t = 4 * kb + lk;
             t = t >= 2 * K1 ? 0 : t >= K1 ? t - K1 : t;
             return t * TR_WRS;
         };
-        const int a0 = li * E2_XRS;
-        half8 x[2][4];
+        // NT m-tiles of 16 outputs: tile i's output li starts at halves xa(i) of the feature-row buffer
+        auto tiles = [&](auto nt_, f32x4 (&acc)[4], auto xa) __attribute__((always_inline)) {
+            constexpr int NT = decltype(nt_)::value;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) x[0][i] = *reinterpret_cast<const half8*>(xb + a0 + i * (16 * E2_XRS) + stack_off(0));
+            for (int i = 0; i < NT; ++i) acc[i] = f32x4{h.bz.x, h.bz.y, h.bz.z, h.bz.w};
+            half8 x[2][NT];
 #pragma unroll
-        for (int kb = 0; kb < KB1; ++kb) {
-            if (kb + 1 < KB1) {
-                const int bo = stack_off(kb + 1);
+            for (int i = 0; i < NT; ++i) x[0][i] = *reinterpret_cast<const half8*>(xb + xa(i) + stack_off(0));
 #pragma unroll
-                for (int i = 0; i < 4; ++i) x[(kb + 1) & 1][i] = *reinterpret_cast<const half8*>(xb + a0 + i * (16 * E2_XRS) + bo);
+            for (int kb = 0; kb < KB1; ++kb) {
+                if (kb + 1 < KB1) {
+                    const int bo = stack_off(kb + 1);
+#pragma unroll
+                    for (int i = 0; i < NT; ++i) x[(kb + 1) & 1][i] = *reinterpret_cast<const half8*>(xb + xa(i) + bo);
+                }
+#pragma unroll
+                for (int i = 0; i < NT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(h.w[kb], x[kb & 1][i], acc[i], 0, 0, 0);
             }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(h.w[kb], x[kb & 1][i], acc[i], 0, 0, 0);
-        }
+        };
+        const int a0 = li * E2_XRS;
+        f32x4 acc[4];
+        // the two padded outputs (E1C: the right span starts at R1, the last output's rows X_RIGHT - R1 slots into it)
+        tiles(std::integral_constant<int, 4>{}, acc, [&](int i) __attribute__((always_inline)) {
+            return a0 + i * (16 * E2_XRS) + (E1C && i >= 2 ? (G::X_RIGHT - G::R1) * TR_WRS : 0);
+        });
         const EpiSpecC1 epi{sp_hi, sp_lo, nullptr, c0, c1};
 #pragma unroll
         for (int i = 0; i < 4; ++i) epi(i * 16 + li, wave * 16 + 4 * lk, acc[i]);
+        if constexpr (E1C) {
+            // the interior E1 rows, as map-set rows of conv2: [0, 32) LEFT, [32, 64) R1, [64, 96) R1 + 2 (K1 = 13); tile j = set rows
+            // 16 j .. + 15 reads the left span 2 slots in (LEFT - X_LEFT), the right span 0 or 2 slots in
+            auto xa = [&](int j) __attribute__((always_inline)) {
+                return a0 + (j < 4 ? j : j - 2) * (16 * E2_XRS) + (j < 2 ? (G::LEFT - G::X_LEFT) * TR_WRS : j < 4 ? 0 : 2 * TR_WRS);
+            };
+            auto store = [&](int j, const f32x4& a) __attribute__((always_inline)) {
+                half4 hh, ll;
+                split4(a, hh, ll);
+                half_t* o = e1set + (j * 16 + li) * E2_MRS + wave * 16 + 4 * lk;
+                *reinterpret_cast<half4*>(o) = hh;
+                *reinterpret_cast<half4*>(o + 128) = ll;
+            };
+            tiles(std::integral_constant<int, 4>{}, acc, xa);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) store(j, acc[j]);
+            if constexpr (G::NE1 == 3) {
+                tiles(std::integral_constant<int, 2>{}, acc, [&](int i) __attribute__((always_inline)) { return xa(4 + i); });
+#pragma unroll
+                for (int j = 0; j < 2; ++j) store(4 + j, acc[j]);
+            }
+        }
     };
 
     // ---- conv2..conv4 ------------------------------------------------------------------------------------------------------------------
@@ -394,10 +433,12 @@ __global__ __launch_bounds__(512) void edge2_kernel(SiteRange sr, const RInfo* _
         desc_c();
         desc_d(s0, sinfo2[0], rowtab[0]);
         load_head1(h1);
+        // slot 16 of a pseudo-row's span is the row's pad chunk: the right padding of K1 = 13 (X_PAD) lies there; nothing else writes it
+        if (E1C && tid < EG_M) *reinterpret_cast<uint4*>(xb + tid * E2_XRS + EG_XROWS * TR_WRS) = make_uint4(0u, 0u, 0u, 0u);
         __syncthreads();
         build_rows(sinfo2[0], tid, std::integral_constant<int, NW * 64>{}, [] {});
         e2_vmwait<0>();
-        dma_maps(L2t{}, rowtab[0][0], 0, wave, NW8{});
+        if constexpr (!E1C) dma_maps(L2t{}, rowtab[0][0], 0, wave, NW8{});
         e2_vmwait<0>();
     }
     int cur = 0, sel = 0;
@@ -418,7 +459,7 @@ __global__ __launch_bounds__(512) void edge2_kernel(SiteRange sr, const RInfo* _
         desc_a(sn);
         // conv2's weights: requested here, behind nothing but conv1's (the vector-memory path idles through conv1 otherwise)
         e2_for<0, 12>([&](auto k_) __attribute__((always_inline)) { load_kb(L2t{}, k_, lw); });
-        conv1(h1);
+        conv1(h1, mset + (size_t)sel * E2_MSET);   // (E1C: conv2's map set was last read by the previous pass's conv3)
         ETS(1);
         e2_vmwait<0>();
         e2_barrier();
@@ -483,8 +524,8 @@ __global__ __launch_bounds__(512) void edge2_kernel(SiteRange sr, const RInfo* _
             }, [&](auto b_) __attribute__((always_inline)) {  // the next pass's conv2 map rows
                 constexpr int b = decltype(b_)::value, NP = (E2L<K1, 2>::NI + NWC - 1) / NWC;
                 static_assert(NP < E2L<K1, 4>::NB, "the pieces fit the layer's blocks");
-                if constexpr (b >= 1 && b - 1 < NP) dma_issue(L2t{}, ds, sel ^ 1, wave + NWC * (b - 1));
-                if constexpr (b < NP) ds = dma_src(L2t{}, rowtab[cur ^ 1][0], wave + NWC * b);
+                if constexpr (!E1C && b >= 1 && b - 1 < NP) dma_issue(L2t{}, ds, sel ^ 1, wave + NWC * (b - 1));
+                if constexpr (!E1C && b < NP) ds = dma_src(L2t{}, rowtab[cur ^ 1][0], wave + NWC * b);
             });
             const EpiEdgeOut epi{reinterpret_cast<half_t*>(edge4) + (size_t)s0 * (4 * C4_CH), nullptr, nvalid};
 #pragma unroll
@@ -512,11 +553,16 @@ __global__ __launch_bounds__(512) void edge2_kernel(SiteRange sr, const RInfo* _
 }
 
 void launch_edge2(hipStream_t st, int k1, const SiteRange& sr, const RInfo* rinfo, const uint8_t* bases, const uint32_t* kin,
-                  const CtxWeights& w, const TrunkMaps& maps, uint16_t* edge4, int32_t* e4row, int grid) {
+                  const CtxWeights& w, const TrunkMaps& maps, uint16_t* edge4, int32_t* e4row, int grid, bool own_e1) {
     if (sr.cap <= 0) return;
     const dim3 g(sr.totals ? grid : max(1, min((sr.cap + EG_S - 1) / EG_S, grid))), b(512);
-    if (k1 == 11) hipLaunchKernelGGL(edge2_kernel<11>, g, b, 0, st, sr, rinfo, bases, kin, w, maps, edge4, e4row);
-    else hipLaunchKernelGGL(edge2_kernel<13>, g, b, 0, st, sr, rinfo, bases, kin, w, maps, edge4, e4row);
+    if (own_e1) {
+        if (k1 == 11) hipLaunchKernelGGL((edge2_kernel<11, true>), g, b, 0, st, sr, rinfo, bases, kin, w, maps, edge4, e4row);
+        else hipLaunchKernelGGL((edge2_kernel<13, true>), g, b, 0, st, sr, rinfo, bases, kin, w, maps, edge4, e4row);
+    } else {
+        if (k1 == 11) hipLaunchKernelGGL((edge2_kernel<11, false>), g, b, 0, st, sr, rinfo, bases, kin, w, maps, edge4, e4row);
+        else hipLaunchKernelGGL((edge2_kernel<13, false>), g, b, 0, st, sr, rinfo, bases, kin, w, maps, edge4, e4row);
+    }
 }
 
 }  // namespace hm

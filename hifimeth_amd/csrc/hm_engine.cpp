@@ -133,7 +133,10 @@ struct hm_engine {
     // 3: the streaming trunk as a sliding window (hm_trunk3.hip: 112 rows per layer and tile, 14 % fewer MFMAs), 1: streaming 4-wave trunk
     // kernel (hm_convs.h), 2: the same on 8 waves, 0: the 8-wave ConvH form; byte-identical maps
     int trunk_impl = 3;
-    int edge_impl = 1;   // dense-trunk path, precision 1: 1 = edge2_kernel (hm_edge2.hip), 0 = edge_kernel (hm_trunk.hip); bit-identical
+    // dense-trunk path, precision 1: 2 = edge2_kernel computing the E1 rows its chains read itself (hm_edge2.hip, E1C): with trunk_impl 3 the
+    // trunk then stores no E1 row and the E1 map is not allocated (trunk_stores_e1); 1 = edge2_kernel gathering them from the E1 map,
+    // 0 = edge_kernel (hm_trunk.hip); bit-identical
+    int edge_impl = 2;
     // dense-trunk path, precision 1: 2 = the split tail (hm_tail_s.hip: conv5 + conv6, then conv7 .. softmax batched over 16 sites),
     // 1 = one kernel with resident weights (hm_tail_r.hip), 0 = tail_kernel_h (streams them per pass); bit-identical
     // 3 (default) = the strip tail (hm_tail_p.hip) for CHH -- 16 sites of one residue class per pass sharing a strip of E4 rows in LDS --
@@ -182,7 +185,9 @@ struct hm_engine {
 namespace {
 
 // Device bytes per base of a read group: E1..E3 maps (2 views x 512 B each), E4 (2 x 384 B), the sites' edge rows (768 B) and map-row
-// numbers, row lists -- times the 25 % head-room DevBuf::reserve adds.
+// numbers, row lists -- times the 25 % head-room DevBuf::reserve adds.  The budget is that of the option set with the largest footprint:
+// the default kernels (edge_impl 2 with trunk_impl 3) allocate no E1 map and stay 1 280 B per base under it, but options may be switched
+// on a live engine after the group size has been fixed, and an engine must then still fit "a quarter of free memory".
 constexpr int64_t GROUP_BYTES_PER_BASE = (3 * 2 * 512 + 2 * 384 + 768 + 4 + 8 + 2 * 4 + 8 + 4 + TAIL_STRIP_HANDOVER_BYTES) * 5 / 4;  // (+ the strip tail's marks per map row, its sorted order and
                                                                                                             //  the rows handed to its second kernel, sized per base: a base is at most one site)
 
@@ -553,6 +558,10 @@ void enqueue_upload(hm_batch* b) {
     b->ran = b->have_totals = b->have_calls = false;
 }
 
+// Does any selected kernel touch the E1 map?  Not when the sliding-window trunk feeds the edge kernel that computes its own E1 rows; strict
+// fp32, the older trunks (which always store their rows), the gathering edge kernels and the conv3_w16 diagnostic keep it.
+bool trunk_stores_e1(const hm_engine* e) { return e->precision == 0 || e->trunk_impl != 3 || e->edge_impl != 2 || e->conv3_w16 != 0; }
+
 // Dense trunk path: per read group and context  trunk (conv1..conv4 once per view position) -> edge (the two conv4 rows
 // per site that are not samples of the maps) -> tail (gathers its conv4 rows).  Every launch is sized by host-known
 // quantities (tiles) or reads its site range from the scanned chunk counters on the device.
@@ -563,7 +572,8 @@ void run_trunk_path(hm_batch* b, std::vector<TimedSpan>* spans, int ctx_mask) {
         max_rows = std::max(max_rows, g.rows);
         max_bases = std::max(max_bases, g.bases);
     }
-    for (int i = 0; i < 3; ++i) e->grp.d_map[i].reserve((size_t)max_rows * 2 * 256 * sizeof(uint16_t));
+    const bool store_e1 = trunk_stores_e1(e);
+    for (int i = store_e1 ? 0 : 1; i < 3; ++i) e->grp.d_map[i].reserve((size_t)max_rows * 2 * 256 * sizeof(uint16_t));
     e->grp.d_e4.reserve((size_t)max_rows * 2 * C4_CH * sizeof(float));
     e->grp.d_rowlist.reserve(std::max((size_t)(max_rows / TR_OWN + 1) * 2 * 3 * TR_OWN, trunk3_rowlist_bytes((max_rows / TR_OWN + 1) * 2)));
     e->grp.d_dump.reserve(trunk3_dump_bytes(e->num_cu));
@@ -583,7 +593,7 @@ void run_trunk_path(hm_batch* b, std::vector<TimedSpan>* spans, int ctx_mask) {
     }
     const int32_t* offs = b->d_offs.as<int32_t>();
     for (const auto& g : b->groups) {
-        const TrunkMaps maps{{e->grp.d_map[0].as<uint16_t>(), e->grp.d_map[1].as<uint16_t>(), e->grp.d_map[2].as<uint16_t>()},
+        const TrunkMaps maps{{store_e1 ? e->grp.d_map[0].as<uint16_t>() : nullptr, e->grp.d_map[1].as<uint16_t>(), e->grp.d_map[2].as<uint16_t>()},
                              e->grp.d_e4.as<uint16_t>(), g.rows, e->d_zeros.as<uint16_t>(), e->grp.d_rowlist.as<uint8_t>()};
         const int n_tiles = g.tile_hi - g.tile_lo;
         for (int c = 0; c < 3; ++c) {
@@ -616,7 +626,7 @@ void run_trunk_path(hm_batch* b, std::vector<TimedSpan>* spans, int ctx_mask) {
                 if (e->trunk_impl == 3)
                     launch_trunk3(e->stream, dm.k1, b->d_tiles.as<TrunkTile>() + g.tile_lo, n_tiles, n_views, c, b->d_rinfo.as<RInfo>(),
                                   b->d_bases.as<uint8_t>(), b->d_kin.as<uint32_t>(), b->d_sctx.as<uint8_t>(), b->total_bases, dm.w, maps, e->grp.d_dump.as<uint16_t>(),
-                                  b->d_totals.as<int32_t>() + TOT_LIST_STEPS, b->d_tcost.as<int32_t>() + g.cost_lo, e->num_cu, e->conv3_w16 != 0);
+                                  b->d_totals.as<int32_t>() + TOT_LIST_STEPS, b->d_tcost.as<int32_t>() + g.cost_lo, e->num_cu, e->conv3_w16 != 0, store_e1);
                 else if (e->trunk_impl)
                     launch_trunk2(e->stream, dm.k1, b->d_tiles.as<TrunkTile>() + g.tile_lo, n_tiles, n_views, c, b->d_rinfo.as<RInfo>(),
                                   b->d_bases.as<uint8_t>(), b->d_kin.as<uint32_t>(), b->d_sctx.as<uint8_t>(), dm.w, maps, e->num_cu,
@@ -628,9 +638,9 @@ void run_trunk_path(hm_batch* b, std::vector<TimedSpan>* spans, int ctx_mask) {
             }
             {
                 Span sp(e, spans, K_EDGE, c);
-                if (e->edge_impl == 1)
+                if (e->edge_impl >= 1)
                     launch_edge2(e->stream, dm.k1, sr, b->d_rinfo.as<RInfo>(), b->d_bases.as<uint8_t>(), b->d_kin.as<uint32_t>(), dm.w,
-                                 maps, e->grp.d_edge4.as<uint16_t>(), e->grp.d_e4row.as<int32_t>(), e->num_cu);
+                                 maps, e->grp.d_edge4.as<uint16_t>(), e->grp.d_e4row.as<int32_t>(), e->num_cu, e->edge_impl == 2);
                 else
                     launch_edge(e->stream, dm.k1, sr, b->d_rinfo.as<RInfo>(), b->d_bases.as<uint8_t>(), b->d_kin.as<uint32_t>(), dm.w,
                                 maps, e->grp.d_edge4.as<uint16_t>(), e->grp.d_e4row.as<int32_t>(), e->num_cu);
@@ -914,7 +924,7 @@ int hm_set_option(hm_engine_t* e, const char* key, int64_t value) {
         if (value < 1 || value > 1024) return fail(e, HM_EINVAL, "num_cu must be 1..1024");
         e->num_cu = (int)value;
     } else if (k == "edge_impl") {
-        if (value < 0 || value > 1) return fail(e, HM_EINVAL, "edge_impl must be 0 or 1");
+        if (value < 0 || value > 2) return fail(e, HM_EINVAL, "edge_impl must be 0, 1 or 2");
         e->edge_impl = (int)value;
     } else if (k == "tail_impl") {
         if (value < 0 || value > 3) return fail(e, HM_EINVAL, "tail_impl must be 0, 1, 2 or 3");
@@ -1223,6 +1233,21 @@ int64_t hm_site_logits(hm_engine_t* e, int ctx, float* logits, int64_t cap) {
             logits[2 * i + 1] = lg[2 * u + 1];
         }
         return n;
+    });
+}
+
+int hm_debug_edge_rows(hm_engine_t* e, int64_t sites, uint16_t* rows) {
+    if (!e || sites < 0 || (sites > 0 && !rows)) return HM_EINVAL;
+    hm_batch* b = legacy(e);
+    if (!b->ran) return fail(e, HM_ESTATE, "hm_debug_edge_rows: hm_run first");
+    int rc = hm_sync(e);
+    if (rc < 0) return rc;
+    const size_t bytes = (size_t)sites * 4 * C4_CH * sizeof(uint16_t);
+    if (bytes > e->grp.d_edge4.cap) return fail(e, HM_EINVAL, "hm_debug_edge_rows: the edge-row buffer holds fewer sites");
+    if (sites == 0) return HM_OK;
+    return guarded(e, [&] {
+        HIP_TRY(hipMemcpy(rows, e->grp.d_edge4.p, bytes, hipMemcpyDeviceToHost));
+        return (int)HM_OK;
     });
 }
 

@@ -71,9 +71,9 @@ void launch_trunk(hipStream_t st, int k1, const TrunkTile* tiles, int n_tiles, i
 void launch_edge(hipStream_t st, int k1, const SiteRange& sr, const RInfo* rinfo, const uint8_t* bases,
                  const uint32_t* kin, const CtxWeights& w, const TrunkMaps& maps, uint16_t* edge4, int32_t* e4row, int grid);
 // the same edge rows with taps read in place, zero taps skipped and map rows / weights streamed a layer ahead (hm_edge2.hip):
-// bit-identical results
+// bit-identical results.  own_e1: the kernel computes the E1 rows its chains read itself (same bytes) and never touches maps.e[0]
 void launch_edge2(hipStream_t st, int k1, const SiteRange& sr, const RInfo* rinfo, const uint8_t* bases, const uint32_t* kin,
-                  const CtxWeights& w, const TrunkMaps& maps, uint16_t* edge4, int32_t* e4row, int grid);
+                  const CtxWeights& w, const TrunkMaps& maps, uint16_t* edge4, int32_t* e4row, int grid, bool own_e1 = false);
 void launch_tail_gather(hipStream_t st, const SiteRange& sr, const CtxWeights& w, const TrunkMaps& maps, const uint16_t* edge4,
                         const int32_t* e4row, float* logits, float* p, uint8_t* ml, int grid);
 // the same tail with conv5..conv7's weights resident in registers (hm_tail_r.hip): bit-identical results
@@ -111,8 +111,9 @@ size_t trunk3_rowlist_bytes(int64_t n_work);
 size_t trunk3_dump_bytes(int grid);
 void launch_trunk3(hipStream_t st, int k1, const TrunkTile* tiles, int n_tiles, int n_views, int ctx, const RInfo* rinfo,
                    const uint8_t* bases, const uint32_t* kin, const uint8_t* sctx, int64_t n_bases, const CtxWeights& w, const TrunkMaps& maps,
-                   uint16_t* dump, int32_t* list_steps, const int32_t* tcost, int grid, bool w3_single = false);   // n_bases: bytes of sctx
-// (w3_single: conv3 with plain fp16 weights -- its w_lo x_hi product dropped -- engine option conv3_w16 = 1)
+                   uint16_t* dump, int32_t* list_steps, const int32_t* tcost, int grid, bool w3_single = false, bool store_e1 = true);   // n_bases: bytes of sctx
+// (w3_single: conv3 with plain fp16 weights -- its w_lo x_hi product dropped -- engine option conv3_w16 = 1;
+//  store_e1 = false: no E1 row leaves the kernel -- conv2's stream has no copy slots, maps.e[0] is not touched: for an edge kernel with own_e1)
 // the same path in strict fp32 (precision 0; hm_trunk_f32.hip): fp32 maps and edge rows, v_mfma_f32_16x16x4_f32
 void launch_trunk_f32(hipStream_t st, int k1, const TrunkTile* tiles, int n_tiles, int n_views, int ctx, const RInfo* rinfo,
                       const uint8_t* bases, const uint32_t* kin, const uint8_t* sctx, const CtxWeights& w,

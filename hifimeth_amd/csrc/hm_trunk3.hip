@@ -307,7 +307,9 @@ __global__ __launch_bounds__(64) void rowlist3_kernel(const TrunkTile* __restric
 // ------------------------------------------------------------------------------------------------------------------------
 // W3LO = false (engine option conv3_w16 = 1, with trunk_impl 3; precision = 2 drops w_lo in conv8 + fc1 instead): conv3 runs with plain fp16 WEIGHTS --
 // its w_lo x_hi product is dropped, 12 of a tile's 53 MFMAs per position; activations stay hi + lo everywhere
-template <int K1, bool W3LO = true>
+// E1S = false (the edge kernel computes its E1 rows itself: launch_edge2 own_e1): no E1 row leaves the kernel -- conv2's stream carries no
+// copy slots, a constant step stores no E1 row, mp.e[0] is never formed into an address; the E1 lists of the records are ignored
+template <int K1, bool W3LO = true, bool E1S = true>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void trunk3_kernel(const TrunkTile* __restrict__ tiles, int n_tiles, int n_views, int ctx, const RInfo* __restrict__ rinfo,
                    const uint8_t* __restrict__ bases, const uint32_t* __restrict__ kin, CtxWeights W, TrunkMaps mp, half_t* __restrict__ dump,
@@ -501,7 +503,7 @@ void trunk3_kernel(const TrunkTile* __restrict__ tiles, int n_tiles, int n_views
         const int wn = cur_warm ? w : w + 1;
         const bool last = wn >= w1;
         // (a read's warm-up step starts 112 rows in front of the read's region: these bases may lie in front of it -- only rows inside are stored)
-        half_t* g1 = cur_calib ? dump_rows : reinterpret_cast<half_t*>(mp.e[0]) + (grow0 + T3_S2) * 256;   // plane A row 0 as E1 = position u + 24
+        half_t* g1 = cur_calib || !E1S ? dump_rows : reinterpret_cast<half_t*>(mp.e[0]) + (grow0 + T3_S2) * 256;   // plane A row 0 as E1 = position u + 24
         half_t* g2 = cur_calib ? dump_rows : reinterpret_cast<half_t*>(mp.e[1]) + (grow0 + T3_S3) * 256;   // plane B row 0 = position u + 16
         half_t* g3 = cur_calib ? dump_rows : reinterpret_cast<half_t*>(mp.e[2]) + grow0 * 256;             // plane A row 0 as E3 = position u
         const uint8_t* rl = reinterpret_cast<const uint8_t*>(rlist[buf]);
@@ -544,7 +546,7 @@ void trunk3_kernel(const TrunkTile* __restrict__ tiles, int n_tiles, int n_views
             }
             // the E1 .. E3 rows the lists flag (the fill entries -- the last new row -- once)
 #pragma unroll
-            for (int l = 0; l < 3; ++l) {
+            for (int l = E1S ? 0 : 1; l < 3; ++l) {
                 const uint8_t* rows = rl + 128 * l;
                 half_t* g = l == 0 ? g1 : l == 1 ? g2 : g3;
                 const int fill = first_new[l] + TR_OWN - 1, ch = t & 31;
@@ -603,7 +605,8 @@ void trunk3_kernel(const TrunkTile* __restrict__ tiles, int n_tiles, int n_views
         __syncthreads();
         TS(2);
         build_desc2(cur_warm, cur_calib != 0);
-        L2::run(a_hi, a_lo, wr, EpiTrunk3{b_hi + T3_H2 * TR_RS, b_lo + T3_H2 * TR_RS}, wf(2), W.bias[2], nt0, nt0, Cp23{{rl, g1}, (int)((cw >> 8) & 255)});
+        if constexpr (E1S) L2::run(a_hi, a_lo, wr, EpiTrunk3{b_hi + T3_H2 * TR_RS, b_lo + T3_H2 * TR_RS}, wf(2), W.bias[2], nt0, nt0, Cp23{{rl, g1}, (int)((cw >> 8) & 255)});
+        else L2::run(a_hi, a_lo, wr, EpiTrunk3{b_hi + T3_H2 * TR_RS, b_lo + T3_H2 * TR_RS}, wf(2), W.bias[2], nt0, nt0);
         // E1's last rows wait in H1 for the next step (conv3 is about to overwrite them)
         move_rows<T3_H1, NW * 64>(h1_hi, h1_lo, a_hi + T3_M * TR_RS, a_lo + T3_M * TR_RS, threadIdx.x);
         TS(3);
@@ -698,10 +701,20 @@ size_t trunk3_dump_bytes(int grid) { return ((size_t)(1 + grid) * TR_OWN * 2 * C
 
 void launch_trunk3(hipStream_t st, int k1, const TrunkTile* tiles, int n_tiles, int n_views, int ctx, const RInfo* rinfo,
                    const uint8_t* bases, const uint32_t* kin, const uint8_t* sctx, int64_t n_bases, const CtxWeights& w, const TrunkMaps& maps,
-                   uint16_t* dump, int32_t* list_steps, const int32_t* tcost, int grid, bool w3_single) {
+                   uint16_t* dump, int32_t* list_steps, const int32_t* tcost, int grid, bool w3_single, bool store_e1) {
     if (n_tiles <= 0) return;
     const int n_work = n_tiles * n_views;
     const dim3 g(min(n_work, grid));
+    if (!store_e1 && !w3_single) {   // (the diagnostic conv3_w16 build keeps its E1 stores)
+        if (k1 == 11) {
+            hipLaunchKernelGGL(rowlist3_kernel<11>, dim3((2 * n_work + T3_RPB) / T3_RPB), dim3(64), 0, st, tiles, n_tiles, n_work, ctx, rinfo, sctx, n_bases, maps.rowlist);
+            hipLaunchKernelGGL((trunk3_kernel<11, true, false>), g, dim3(256), 0, st, tiles, n_tiles, n_views, ctx, rinfo, bases, kin, w, maps, reinterpret_cast<half_t*>(dump), list_steps, tcost);
+        } else {
+            hipLaunchKernelGGL(rowlist3_kernel<13>, dim3((2 * n_work + T3_RPB) / T3_RPB), dim3(64), 0, st, tiles, n_tiles, n_work, ctx, rinfo, sctx, n_bases, maps.rowlist);
+            hipLaunchKernelGGL((trunk3_kernel<13, true, false>), g, dim3(256), 0, st, tiles, n_tiles, n_views, ctx, rinfo, bases, kin, w, maps, reinterpret_cast<half_t*>(dump), list_steps, tcost);
+        }
+        return;
+    }
     if (k1 == 11) {
         hipLaunchKernelGGL(rowlist3_kernel<11>, dim3((2 * n_work + T3_RPB) / T3_RPB), dim3(64), 0, st, tiles, n_tiles, n_work, ctx, rinfo, sctx, n_bases, maps.rowlist);
         if (w3_single) hipLaunchKernelGGL((trunk3_kernel<11, false>), g, dim3(256), 0, st, tiles, n_tiles, n_views, ctx, rinfo, bases, kin, w, maps, reinterpret_cast<half_t*>(dump), list_steps, tcost);

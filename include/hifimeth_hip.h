@@ -106,7 +106,8 @@ const char* hm_last_error(const hm_engine_t* e); /* e may be NULL: error of a fa
  * on the host when that batch is queued and then fixed for the engine's lifetime, so the calls never depend on host timing --
  * default; 1 = conv1..conv4 once per read position; 0 = once per site; every precision has both forms), "trunk_mask" (0..7: that
  * choice made by the caller, see hm_trunk_mask_for_reads), "trunk_impl" (3 = the streaming trunk as a sliding window over
- * consecutive tiles, default; 1 = streaming 4-wave trunk kernel; 2 = the same on 8 waves; 0 = the 8-wave ConvH form; byte-identical results), "edge_impl" (1 = edge2_kernel, default; 0 = round 2's
+ * consecutive tiles, default; 1 = streaming 4-wave trunk kernel; 2 = the same on 8 waves; 0 = the 8-wave ConvH form; byte-identical results), "edge_impl" (2 = edge2_kernel computing the E1 rows its chains read, default: with
+ * trunk_impl 3 no E1 map is stored or allocated; 1 = edge2_kernel gathering them from the E1 map; 0 = round 2's
  * edge_kernel; byte-identical), "tail_impl" (3 = the strip tail for CHH (16 sites of one E4-row residue class per pass share one strip of rows in LDS; hm_tail_p.hip) and 1 for the sparse contexts, default; 1 = tail with register-resident weights; 2 = the split tail: conv5 + conv6, then conv7 .. softmax over 16 sites per pass ("tail_slice": sites per launch pair); 0 = the streaming tail; byte-identical),
  * "group_bases" (reads per trunk group; default 0 = sized when the first read is staged so that a group's buffers, 5.8 KB per base, take at most a quarter of the device's free memory, and at most 16 Mi bases), "num_cu" (workgroups of the persistent kernels), "conv3_w16" (diagnostic: conv3 of the dense trunk with plain fp16 weights -- measured ABOVE the 1e-3 bar,
  * part of no mode), "stamps" (diagnostic) */
@@ -179,6 +180,10 @@ int64_t hm_scan_sites(hm_engine_t* e, int ctx, int32_t* read_id, int32_t* qoff, 
 /* logits [n][2] (l0, l1) the CNN computed for the sites of one context after hm_run, in hm_scan_sites order, whichever kernels
  * ran (per site, dense trunk, any tail); returns n, HM_EINVAL when n > cap */
 int64_t hm_site_logits(hm_engine_t* e, int ctx, float* logits, int64_t cap);
+/* the edge kernel's rows -- conv4 rows 0 and 24 per site, [site][side][hi 96 | lo 96] fp16 bit patterns (precision 1, 2) -- of the LAST
+ * read group and context the dense trunk path ran (the buffer is reused by every group and context: run one context in one group to
+ * see all its sites, in hm_scan_sites order); copies `sites` x 384 halves, HM_EINVAL if the buffer holds fewer (debug / tests) */
+int hm_debug_edge_rows(hm_engine_t* e, int64_t sites, uint16_t* rows);
 /* get_next_sample_features: raw 401x8 fp32 windows of sites [first, first+n) of context ctx;
  * out_host may be NULL (device-only run for timing) */
 int hm_windows(hm_engine_t* e, int ctx, int64_t first, int64_t n, float* out_host);

@@ -1,5 +1,5 @@
 """Diagnostic: where an edge2_kernel pass's ticks go.  Needs the stamped build (make -C hifimeth_amd/csrc stamp) and
-HM_LIB_PATH=hifimeth_amd/libhifimeth_hip_stamp.so.  Prints the mean s_memtime ticks per pass (32 sites) that the waves of
+HM_LIB_PATH=hifimeth_amd/libhifimeth_hip_stamp.so; an optional argument sets the engine option edge_impl.  Prints the mean s_memtime ticks per pass (32 sites) that the waves of
 workgroup 0 spend in each phase -- shares of a pass, not a fixed unit of time."""
 import ctypes as C
 import sys
@@ -13,6 +13,9 @@ from hifimeth_amd.synth import synth_reads  # noqa: E402
 reads = synth_reads(400, seed=5)
 mc = MethylationCaller(device=0, timing=True)
 mc.set_option("trunk", 1)
+if len(sys.argv) > 1:   # edge_impl: 2 = the kernel computes its E1 rows (default), 1 = it gathers them from the trunk's map
+    mc.set_option("edge_impl", int(sys.argv[1]))
+    print("edge_impl", int(sys.argv[1]))
 mc.submit_all(reads)
 mc.upload()
 mc.run()
