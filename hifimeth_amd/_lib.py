@@ -179,6 +179,8 @@ def lib():
         "hm_context_geometry": (C.c_int, [vp]),
         "hm_pileup_fetch_context": (i64, [vp, vp, vp, vp, i64, i64, i64, i64, i32, vp, i64]),
         "hm_pileup_fetch_context_path": (i64, [vp, vp, vp, vp, i64, i64, i64, i64, i32, i32, vp, i64]),
+        "hm_smooth_fetch": (i64, [vp, i32, i32, i64, i64, i32, i32, i64, vp, i64]),
+        "hm_smooth_stats": (C.c_int, [vp, i32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -17,6 +17,7 @@
 //     hifimeth-hip samplecorr [OPTIONS] REF.fa S1,S2,..,SN OUT (N pileups' correlation matrix per context, hifimeth_pileup.cpp)
 //     hifimeth-hip regiondiff -R IV.bed [OPTIONS] REF.fa A1,A2,.. B1,B2,.. OUT (two groups tested over given intervals, hifimeth_pileup.cpp)
 //     hifimeth-hip groupdmr [OPTIONS] REF.fa A1,A2,.. B1,B2,.. OUT (regions that differ between two groups, hifimeth_pileup.cpp)
+//     hifimeth-hip smooth [OPTIONS] REF.fa PREFIX OUT (kernel-smoothed levels of one pileup's *.cov.bed, hifimeth_pileup.cpp)
 //     hifimeth-hip modstats IN.bam                    (MM/ML parser + per-context histograms + adaptive thresholds)
 //     hifimeth-hip modlist IN.bam                     (the MM/ML parser's output per record: test seam against the
 //                                                      reference parser's fixture, tests/golden/modparse.json)
@@ -115,8 +116,9 @@ void usage() {
             "  %s samplecorr [OPTIONS] reference s1,s2,...,sN output-prefix   the correlation matrix of N pileups, per context\n"
             "  %s regiondiff -R bed [OPTIONS] reference a1,a2,... b1,b2,... output-prefix   two groups of replicate pileups tested over given intervals\n"
             "  %s groupdmr [OPTIONS] reference a1,a2,... b1,b2,... output-prefix   regions that differ between two groups of replicate pileups\n"
+            "  %s smooth [OPTIONS] reference prefix output-prefix             kernel-smoothed methylation level per locus of one pileup\n"
             "  %s corr [-c <min coverage>] bed1 bed2                        Pearson correlation of two pileups\n",
-            kName, kName, kName, kName, kName, kName, kName, kName, kName, kName);
+            kName, kName, kName, kName, kName, kName, kName, kName, kName, kName, kName);
 }
 
 // host threads this process may really use: the affinity mask, capped by the cgroup CPU quota (a container that is granted
@@ -921,6 +923,7 @@ int main(int argc, char** argv) {
     if (cmd == "samplecorr") return cmd_samplecorr(argc, argv);
     if (cmd == "regiondiff") return cmd_regiondiff(argc, argv);
     if (cmd == "groupdmr") return cmd_groupdmr(argc, argv);
+    if (cmd == "smooth") return cmd_smooth(argc, argv);
     if (cmd == "sample") return cmd_sample(argc, argv);
     if (cmd == "eval") return cmd_eval(argc, argv);
     usage();

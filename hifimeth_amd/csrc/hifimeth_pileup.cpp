@@ -7,6 +7,7 @@
 #include <zlib.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cerrno>
 #include <climits>
 #include <chrono>
@@ -109,6 +110,7 @@ template <class Row>
 uint32_t row_ctx(const Row& r) { return r.motif < 3 ? r.motif : 2; }
 inline uint32_t row_ctx(const hm_pattern_t&) { return 0; }
 inline uint32_t row_ctx(const hm_bedmethyl_t&) { return 0; }
+inline uint32_t row_ctx(const hm_smooth_t&) { return 0; }  // one context per file: the caller's
 
 // An output file, closed when its owner goes; empty (message printed) if it cannot be opened.
 struct CloseFile { void operator()(FILE* f) const { fclose(f); } };
@@ -1362,6 +1364,71 @@ int cmd_diff(int argc, char** argv) {
     job.engine.reset();
     fprintf(stderr, "## %llu + %llu covered loci of %d contexts in %.2f s: parse + load %.2f s; test + BED %.2f s\n", (unsigned long long)n_rows[0],
             (unsigned long long)n_rows[1], job.n_ctx, secs(t_start, clk::now()), secs(t_start, t_load), secs(t_load, clk::now()));
+    return 0;
+}
+
+// ---- smooth [OPTIONS] reference prefix out-prefix (ours) ------------------------------------------------------------------------------
+// Kernel-smoothed levels of one sample: the rows of <prefix>.<ctx>.cov.bed go into the engine's partition 1 as `diff` loads them,
+// and per context with a file the rows of hm_smooth_fetch are written sequence by sequence, the chunks `diff` fetches in
+// (DESIGN.md section 10).
+int cmd_smooth(int argc, char** argv) {
+    PileupOptions o;
+    int first = 0, status = 0;
+    if (!parse_command_line(CMD_SMOOTH, argc, argv, o, first, status)) return status;
+    o.ref = argv[first];
+    const std::vector<std::string> sample = {argv[first + 1]};
+    o.prefix = argv[first + 2];
+    const int32_t h = (int32_t)o.smooth_half_width, min_cov = (int32_t)o.smooth_min_cov;
+    fprintf(stderr, "\n\n====================> Parameters:\nCPU threads: %d\nGenomic reference: %s\nsample: %s.<ctx>.cov.bed\noutput prefix: %s\n"
+                    "smooth: triangular kernel of half-width %d, min coverage %d, min loci per window %lld -> %s.smooth.*\n\n\n",
+            o.threads, o.ref.c_str(), sample[0].c_str(), o.prefix.c_str(), h, min_cov, o.smooth_min_loci, o.prefix.c_str());
+
+    const auto t_start = clk::now();
+    CovJob job;
+    if (const int failed = open_cov_job(o, sample, "the sample", "partitions", {{"partitions", 2}}, job)) return failed;
+    hm_pileup_t* pe = job.engine.get();
+    uint64_t n_rows = 0;
+    const LoadCall load = [&](const hm_locus_t* rows, int64_t n) { return hm_pileup_load_loci(pe, 1, rows, n); };
+    for (int c = 0; c < 3; ++c)
+        if (!job.files[c].empty() && !load_cov_bed(job, job.files[c][0], load, (uint32_t)c, o.threads, n_rows)) return EXIT_FAILURE;
+    const auto t_load = clk::now();
+
+    uint64_t counting[3] = {0, 0, 0}, written[3] = {0, 0, 0};
+    for (int c = 0; c < 3; ++c) {
+        if (job.files[c].empty()) continue;
+        const OutFile f = open_out(o.prefix + ".smooth." + CTX_NAME[c] + ".bed");
+        if (!f) return EXIT_FAILURE;
+        FILE* const out[3] = {f.get(), f.get(), f.get()};
+        std::atomic<bool> ok{true};
+        const bool done = write_rows<hm_smooth_t>(
+            job.fa, out, o.threads,
+            [&](int64_t lo, int64_t hi, hm_smooth_t* dst, int64_t cap) -> int64_t {
+                const int64_t n = hm_smooth_fetch(pe, 1, c, lo, hi, h, min_cov, o.smooth_min_loci, dst, cap);
+                if (dst || n < 0) return n;
+                // the first of the two calls per sequence: the counting loci are the rows under -i 1
+                const int64_t all = o.smooth_min_loci > 1 ? hm_smooth_fetch(pe, 1, c, lo, hi, h, min_cov, 1, nullptr, 0) : n;
+                if (all < 0) return all;
+                counting[c] += (uint64_t)all;
+                written[c] += (uint64_t)n;
+                return n;
+            },
+            [&](const hm_smooth_t& r, int64_t k, char (&buf)[320]) {
+                double st[2] = {0, 0};
+                if (hm_smooth_stats(&r, h, st) != HM_OK) ok = false;
+                return snprintf(buf, sizeof buf, "\t%lld\t%lld\t%g\t%d\t%d\t%lld\t%.3f\n", (long long)k, (long long)k + 1, st[0], r.pcov, r.ncov,
+                                (long long)r.loci, st[1]);
+            });
+        if (!done) return engine_error(pe, "smooth");
+        if (!ok) { fprintf(stderr, "ERROR: smooth: a row without a call in its window\n"); return EXIT_FAILURE; }
+    }
+    const OutFile summary = open_out(o.prefix + ".smooth.summary.tsv");
+    if (!summary) return EXIT_FAILURE;
+    for (int c = 0; c < 3; ++c)
+        if (!job.files[c].empty())
+            fprintf(summary.get(), "%s\t%llu\t%llu\t%d\n", CTX_NAME[c], (unsigned long long)counting[c], (unsigned long long)written[c], h);
+    job.engine.reset();
+    fprintf(stderr, "## %llu covered loci of %d contexts in %.2f s: parse + load %.2f s; smooth + BED %.2f s\n", (unsigned long long)n_rows, job.n_ctx,
+            secs(t_start, clk::now()), secs(t_start, t_load), secs(t_load, clk::now()));
     return 0;
 }
 

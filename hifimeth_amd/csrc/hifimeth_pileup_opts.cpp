@@ -1,4 +1,4 @@
-// hifimeth_pileup_opts.cpp -- the options of `pileup`, `diff`, `groupdiff`, `samplecorr`, `regiondiff` and `groupdmr`: one table that is parser and usage text at once, two strict number
+// hifimeth_pileup_opts.cpp -- the options of `pileup`, `diff`, `groupdiff`, `samplecorr`, `regiondiff`, `groupdmr` and `smooth`: one table that is parser and usage text at once, two strict number
 // parsers, and the checks between options as one ordered list.  A new option is one row here, a field of PileupOptions, a rule if
 // it depends on another option, and its cases in tools/make_cli_options.py.
 #include "hifimeth_pileup_opts.h"
@@ -314,6 +314,16 @@ const Option DMR_OPTIONS[] = {
      "Also write <output-prefix>.groups.<ctx>.bed and <output-prefix>.groups.summary.tsv, as `groupdiff` with the same -a -r"},
 };
 const char DMR_FLAGS[] = "arsFmgnLtd";
+// `smooth` brings three
+const Option SMOOTH_OPTIONS[] = {
+    {'W', "<bp>", integer<&O::smooth_half_width, 1, 16384>,
+     "Half-width of the triangular kernel in bases, in [1, 16384]: a locus d < bp bases away has the weight bp - d\n    Default: 500"},
+    {'a', "<int>", integer<&O::smooth_min_cov, 1, INT_MAX>,
+     "Minimum coverage (pcov + ncov) of a locus that counts: as a row and in the windows of the others, >= 1\n    Default: 1"},
+    {'i', "<int>", integer<&O::smooth_min_loci, 1, LLONG_MAX>,
+     "Smallest number of counting loci in the window of a row that is written, the locus itself included, >= 1\n    Default: 1"},
+};
+const char SMOOTH_FLAGS[] = "Waitd";
 
 const char PILEUP_HEADER[] =
     "USAGE:\n"
@@ -408,6 +418,22 @@ const char DMR_HEADER[] =
     "\n"
     "OPTIONAL ARGUMENTS:\n";
 
+const char SMOOTH_HEADER[] =
+    "USAGE:\n"
+    "  $0 smooth [OPTIONS] reference prefix output-prefix\n"
+    "\n"
+    "DESCRIPTION:\n"
+    "  Kernel-smoothed methylation levels of one sample, from the files a `pileup` run wrote: <prefix>.<ctx>.cov.bed for ctx in CpG,\n"
+    "  CHG, CHH, plain or gzip, read as `diff` reads them; a context without its file is skipped.  A locus counts with at least -a\n"
+    "  calls.  Every counting locus borrows from the counting loci of its context and sequence less than -W bases away, each\n"
+    "  weighted by -W minus its distance (a triangular kernel): P and N are the weighted sums of their methylated and unmethylated\n"
+    "  calls, all in integers.  Nothing crosses a sequence end; loci of other contexts or below -a in between are ignored.\n"
+    "  Writes <output-prefix>.smooth.<ctx>.bed: chrom, start, end, the smoothed level 100 P / (P + N), the locus' own pcov and ncov,\n"
+    "  the counting loci in its window, and the effective coverage (P + N) / -W, for every counting locus with at least -i loci in\n"
+    "  its window; and <output-prefix>.smooth.summary.tsv: ctx, counting loci, rows written, -W\n"
+    "\n"
+    "OPTIONAL ARGUMENTS:\n";
+
 const Option* find_option(Command cmd, char letter) {
     if (cmd == CMD_DIFF && !strchr(DIFF_FLAGS, letter)) return nullptr;
     if (cmd == CMD_GROUPDMR) {
@@ -423,6 +449,11 @@ const Option* find_option(Command cmd, char letter) {
     if (cmd == CMD_SAMPLECORR) {
         if (!strchr(SAMPLE_FLAGS, letter)) return nullptr;
         for (const Option& opt : SAMPLE_OPTIONS)
+            if (opt.letter == letter) return &opt;
+    }
+    if (cmd == CMD_SMOOTH) {
+        if (!strchr(SMOOTH_FLAGS, letter)) return nullptr;
+        for (const Option& opt : SMOOTH_OPTIONS)
             if (opt.letter == letter) return &opt;
     }
     if (cmd == CMD_REGIONDIFF) {
@@ -444,7 +475,7 @@ void print_text(const char* text, const char* exe) {  // $0: the program
 
 void usage(Command cmd, const char* exe) {
     print_text(cmd == CMD_DIFF ? DIFF_HEADER : cmd == CMD_GROUPDIFF ? GROUP_HEADER : cmd == CMD_SAMPLECORR ? SAMPLE_HEADER :
-               cmd == CMD_REGIONDIFF ? REGION_HEADER : cmd == CMD_GROUPDMR ? DMR_HEADER : PILEUP_HEADER, exe);
+               cmd == CMD_REGIONDIFF ? REGION_HEADER : cmd == CMD_GROUPDMR ? DMR_HEADER : cmd == CMD_SMOOTH ? SMOOTH_HEADER : PILEUP_HEADER, exe);
     const auto row = [&](const Option& opt) {
         fprintf(stderr, "  -%c%s%s\n    ", opt.letter, opt.metavar ? " " : "", opt.metavar ? opt.metavar : "");
         print_text(cmd == CMD_DIFF && opt.diff_help ? opt.diff_help : opt.help, exe);
@@ -455,6 +486,7 @@ void usage(Command cmd, const char* exe) {
     else if (cmd == CMD_SAMPLECORR) for (const char* f = SAMPLE_FLAGS; *f; ++f) row(*find_option(cmd, *f));
     else if (cmd == CMD_REGIONDIFF) for (const char* f = REGION_FLAGS; *f; ++f) row(*find_option(cmd, *f));
     else if (cmd == CMD_GROUPDMR) for (const char* f = DMR_FLAGS; *f; ++f) row(*find_option(cmd, *f));
+    else if (cmd == CMD_SMOOTH) for (const char* f = SMOOTH_FLAGS; *f; ++f) row(*find_option(cmd, *f));
     else for (const Option& opt : OPTIONS) row(opt);
 }
 
@@ -472,7 +504,7 @@ struct Parsed {
 // and inside each group the order below.  It is not uniform -- patterns, linkage, profile and context report a bad value before a
 // missing parent, asm, domains, bedmethyl and intervals the missing parent first -- and tests/golden/cli_options.json pins it.
 // `diff` runs the rules marked CMD_DIFF, `groupdiff` those marked CMD_GROUPDIFF, `samplecorr` those marked CMD_SAMPLECORR,
-// `regiondiff` those marked CMD_REGIONDIFF, `groupdmr` those marked CMD_GROUPDMR.
+// `regiondiff` those marked CMD_REGIONDIFF, `groupdmr` those marked CMD_GROUPDMR, `smooth` those marked CMD_SMOOTH.
 struct Rule {
     int commands;
     bool (*fires)(const Parsed& p);
@@ -518,6 +550,7 @@ const Rule RULES[] = {
      "-a must be an integer in [1, 1048575], -l an integer >= 1, -r an integer in [2, 64]"},
     {CMD_GROUPDMR, [](const Parsed& p) { return p.any_seen("s") && p.any_seen("F"); }, "-s and -F exclude each other (the loci are chosen by p, or by q)"},
     {CMD_GROUPDMR, [](const Parsed& p) { return p.any_bad("sFmgn"); }, "-s and -F must be in (0, 1], -m in [0, 100], -g and -n integers >= 1"},
+    {CMD_SMOOTH, [](const Parsed& p) { return p.any_bad("Wai"); }, "-W must be an integer in [1, 16384], -a an integer in [1, 2147483647], -i an integer >= 1"},
 };
 
 }  // namespace
@@ -544,7 +577,7 @@ bool parse_command_line(Command cmd, int argc, char** argv, PileupOptions& o, in
         if (opt->fatal) { fputs(opt->fatal, stderr); return leave(EXIT_FAILURE); }
         p.bad += opt->letter;
     }
-    if (argc - i != (cmd == CMD_PILEUP || cmd == CMD_SAMPLECORR ? 3 : 4)) return leave(EXIT_FAILURE);
+    if (argc - i != (cmd == CMD_PILEUP || cmd == CMD_SAMPLECORR || cmd == CMD_SMOOTH ? 3 : 4)) return leave(EXIT_FAILURE);
     // ahead of the rules although its rule comes tenth: it only writes the weights, which every earlier way out discards
     p.levels_bad = o.domains && !p.any_bad("uxj") && levels_ok && !levels_ok(o);
     for (const Rule& r : RULES)

@@ -1,4 +1,4 @@
-// hifimeth_pileup_opts.h -- the command lines of `hifimeth-hip pileup`, `diff`, `groupdiff`, `samplecorr`, `regiondiff` and `groupdmr`: the options as the rest of the
+// hifimeth_pileup_opts.h -- the command lines of `hifimeth-hip pileup`, `diff`, `groupdiff`, `samplecorr`, `regiondiff`, `groupdmr` and `smooth`: the options as the rest of the
 // front end reads them, and one call that parses, checks and reports (hifimeth_pileup_opts.cpp holds the option table, which is
 // also the usage text, and the ordered list of checks).  Host code without the engine: nothing here opens a file or a device.
 #pragma once
@@ -42,10 +42,11 @@ struct PileupOptions {
     long long sample_min_cov = 5;                                  // samplecorr -a -k
     bool sample_complete = false;
     long long region_min_sample_loci = 3, region_min_reps = 2;     // regiondiff -l -r (its -R -a -k: intervals, sample_min_cov, sample_complete)
+    long long smooth_half_width = 500, smooth_min_cov = 1, smooth_min_loci = 1;  // smooth -W -a -i
     std::string ref, bam, prefix;
 };
 
-enum Command { CMD_PILEUP = 1, CMD_DIFF = 2, CMD_GROUPDIFF = 4, CMD_SAMPLECORR = 8, CMD_REGIONDIFF = 16, CMD_GROUPDMR = 32 };
+enum Command { CMD_PILEUP = 1, CMD_DIFF = 2, CMD_GROUPDIFF = 4, CMD_SAMPLECORR = 8, CMD_REGIONDIFF = 16, CMD_GROUPDMR = 32, CMD_SMOOTH = 64 };
 
 // The whole text as a decimal integer in [lo, hi] -> out, true.  Leading blanks and a sign pass, as strtoll takes them; an empty
 // text, anything behind the number and a value beyond long long do not, and leave `out` alone.
@@ -54,7 +55,7 @@ bool whole_int(const char* text, long long lo, long long hi, long long& out);
 bool whole_double(const char* text, double& out);
 
 // Parses the options of `cmd` from argv[2] on and runs the checks.  true: go on, the positional arguments start at argv[first]
-// (3 for pileup and samplecorr, 4 for diff, groupdiff, regiondiff and groupdmr).  false: the usage, behind an error message if there is one, has been printed; leave with `status`
+// (3 for pileup, samplecorr and smooth, 4 for diff, groupdiff, regiondiff and groupdmr).  false: the usage, behind an error message if there is one, has been printed; leave with `status`
 // (0 after -h).  levels_ok turns the levels and penalty of -D into o's integer weights, false if they give none: the one check
 // that needs the library, so pileup brings it.  It runs once the options have parsed, ahead of the rules; it only writes the weights.
 // the usage of `cmd` on stderr, as parse_command_line prints it: for what a command finds wrong with its positional arguments

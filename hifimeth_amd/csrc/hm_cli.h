@@ -12,6 +12,7 @@ int cmd_groupdiff(int argc, char** argv);
 int cmd_samplecorr(int argc, char** argv);
 int cmd_regiondiff(int argc, char** argv);
 int cmd_groupdmr(int argc, char** argv);
+int cmd_smooth(int argc, char** argv);
 int cmd_corr(int argc, char** argv);  // hifimeth_tools.cpp
 int cmd_cov2bed(int argc, char** argv);
 int cmd_sample(int argc, char** argv);

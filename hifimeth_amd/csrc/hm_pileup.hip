@@ -58,6 +58,8 @@
 //                   HM_REGION_BLOCK loci (twelve for `pileup -R`, `-J`; a pair per sample of the level planes for `regiondiff`), their
 //                   scan by the row-scan skeleton above, then a wavefront per interval (or per bin and stride of intervals) reads the
 //                   index and sums the loci of its two partial blocks (region_add over its lanes; sample_wave_add through LDS)
+//   smooth_prefix_kernel / SmoothSel   kernel-smoothed levels (`smooth`): per position the running sums and first moments of the
+//                   counting loci of one context, restarted every HM_SMOOTH_SPAN positions; a row is a few differences of them
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -2441,6 +2443,128 @@ __global__ __launch_bounds__(TPB) void metaplot_kernel(RegionIndex ix, int64_t p
     if (t) atomicAdd(&tab[(int64_t)blockIdx.x * REGION_LANES + threadIdx.x], (unsigned long long)t);
 }
 
+// ---- kernel-smoothed levels (`smooth`; include/hifimeth_hip.h has the definition) ------------------------------------------------
+// The triangular kernel is a box convolved with a box, so the weighted sums of a window are differences of two running sums over
+// the counting loci: the plain sum of v and its first moment, the sum of (j - origin) v, for v = pcov and ncov (and the plain count).
+// The running sums RESTART every HM_SMOOTH_SPAN = 2 * 16384 positions of the span [a, b) the fetch reads, and a block's moments are
+// measured from the block's first position: with counts below 2^31 a plain sum stays below 2^46 and a moment below 2^61, whatever the
+// range, and one half of a window (at most 16384 positions) lies in at most two blocks.  One record of five sums per POSITION of the
+// span (40 B), written by smooth_prefix_kernel, one workgroup per block; a row is then SmoothSel's handful of lookups, whatever h.
+constexpr int SMOOTH_TPB = 256, SMOOTH_ITEMS = 4;  // threads of a workgroup (1024 spill: 128 registers do not hold a pass); consecutive positions per thread and pass
+static_assert(HM_SMOOTH_SPAN >= 2 * HM_SMOOTH_MAX_HALF_WIDTH && HM_SMOOTH_SPAN % (SMOOTH_TPB * SMOOTH_ITEMS) == 0, "a half window lies in two blocks; a block is whole passes");
+
+struct SmoothPre {  // over the counting loci from the block's first position to this one: their number, sum pcov, sum ncov, the two moments
+    int64_t n, vp, vn, mp, mn;
+};
+__device__ __forceinline__ SmoothPre smooth_sum(const SmoothPre& x, const SmoothPre& y) {
+    return SmoothPre{x.n + y.n, x.vp + y.vp, x.vn + y.vn, x.mp + y.mp, x.mn + y.mn};
+}
+__device__ __forceinline__ SmoothPre smooth_diff(const SmoothPre& x, const SmoothPre& y) {
+    return SmoothPre{x.n - y.n, x.vp - y.vp, x.vn - y.vn, x.mp - y.mp, x.mn - y.mn};
+}
+
+// pre[i - a] for the positions i of block blockIdx.x of [a, b): per pass a thread sums its SMOOTH_ITEMS positions, the wavefronts scan
+// those sums by shuffles, their totals meet in LDS (two buffers: one barrier per pass), and the block's running sum is carried on
+__global__ __launch_bounds__(SMOOTH_TPB) void smooth_prefix_kernel(RangePlanes s, int64_t a, int64_t b, uint32_t ctx, int64_t min_cov,
+                                                                    SmoothPre* __restrict__ pre) {
+    __shared__ SmoothPre wtot[2][SMOOTH_TPB / 64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t base = a + (int64_t)blockIdx.x * HM_SMOOTH_SPAN;
+    SmoothPre carry{0, 0, 0, 0, 0};
+    for (int pass = 0; pass < HM_SMOOTH_SPAN / (SMOOTH_TPB * SMOOTH_ITEMS); ++pass) {
+        const int64_t d0 = (int64_t)pass * (SMOOTH_TPB * SMOOTH_ITEMS) + (int64_t)threadIdx.x * SMOOTH_ITEMS;
+        SmoothPre v[SMOOTH_ITEMS], run{0, 0, 0, 0, 0};
+#pragma unroll
+        for (int k = 0; k < SMOOTH_ITEMS; ++k) {
+            const int64_t d = d0 + k, i = base + d;
+            if (i < b) {
+                const int64_t p = s.pc[i], n = s.nc[i];
+                if (p + n >= min_cov && (s.ky[i] & 3u) == ctx) run = smooth_sum(run, SmoothPre{1, p, n, d * p, d * n});
+            }
+            v[k] = run;
+        }
+        SmoothPre inc = run;  // the inclusive scan of `run` over the wavefront
+        for (int d = 1; d < 64; d <<= 1) {
+            const SmoothPre t{__shfl_up(inc.n, d), __shfl_up(inc.vp, d), __shfl_up(inc.vn, d), __shfl_up(inc.mp, d), __shfl_up(inc.mn, d)};
+            if (lane >= d) inc = smooth_sum(inc, t);
+        }
+        if (lane == 63) wtot[pass & 1][w] = inc;
+        __syncthreads();
+        SmoothPre before = smooth_sum(carry, smooth_diff(inc, run));  // everything of the block in front of this thread's positions
+        for (int j = 0; j < SMOOTH_TPB / 64; ++j) {
+            const SmoothPre t = wtot[pass & 1][j];
+            if (j < w) before = smooth_sum(before, t);
+            carry = smooth_sum(carry, t);
+        }
+#pragma unroll
+        for (int k = 0; k < SMOOTH_ITEMS; ++k) {
+            const int64_t i = base + d0 + k;
+            if (i < b) pre[i - a] = smooth_sum(before, v[k]);
+        }
+    }
+}
+
+// The rows of `smooth`: the counting loci of context ctx with at least min_loci counting loci in their window.  g is the plane index
+// and the global position at once (the engine's own planes).  [a, b) is the span `pre` covers: every window of [lo, hi) lies in it.
+struct SmoothSel {
+    using Row = hm_smooth_t;
+    RangePlanes s;
+    const SmoothPre* pre;
+    int64_t a;
+    const int64_t* seq_off;  // n_seqs + 1
+    int n_seqs;
+    uint32_t ctx;
+    int64_t h, min_cov, min_loci;
+    // the counting loci j of [x, y], a <= x <= y < x + HM_SMOOTH_MAX_HALF_WIDTH, each with the weight c0 + sg j (sg = +-1), added to
+    // (L, P, N).  In a block that starts at B the weight is (c0 + sg B) + sg (j - B): |c0 + sg B| < 2^16 for both halves of a window,
+    // so the products stay below 2^62
+    __device__ void add_part(int64_t x, int64_t y, int64_t c0, int64_t sg, int64_t& L, int64_t& P, int64_t& N) const {
+        for (int64_t blk = (x - a) / HM_SMOOTH_SPAN; blk <= (y - a) / HM_SMOOTH_SPAN; ++blk) {  // one or two
+            const int64_t B = a + blk * HM_SMOOTH_SPAN, first = max(x, B), last = min(y, B + HM_SMOOTH_SPAN - 1);
+            SmoothPre t = pre[last - a];
+            if (first > B) t = smooth_diff(t, pre[first - 1 - a]);
+            const int64_t k = c0 + sg * B;
+            L += t.n;
+            P += k * t.vp + sg * t.mp;
+            N += k * t.vn + sg * t.mn;
+        }
+    }
+    __device__ bool counts(int64_t g, int32_t& p, int32_t& n) const {
+        p = s.pc[g];
+        n = s.nc[g];
+        return (int64_t)p + n >= min_cov && (s.ky[g] & 3u) == ctx;
+    }
+    // the window of the counting locus g, cut at its sequence: [x, g] with the weights h - g + j, (g, y] with h + g - j
+    __device__ void window(int64_t g, int64_t& L, int64_t& P, int64_t& N) const {
+        int slo = 0, shi = n_seqs;  // seq_off[slo] <= g < seq_off[shi]
+        while (shi - slo > 1) {
+            const int mid = (slo + shi) >> 1;
+            if (seq_off[mid] <= g) slo = mid; else shi = mid;
+        }
+        const int64_t x = max(seq_off[slo], g - h + 1), y = min(seq_off[shi] - 1, g + h - 1);
+        L = P = N = 0;
+        add_part(x, g, h - g, 1, L, P, N);
+        if (y > g) add_part(g + 1, y, h + g, -1, L, P, N);
+    }
+    __device__ bool pred(int64_t g) const {
+        int32_t p, n;
+        if (!counts(g, p, n)) return false;
+        if (min_loci <= 1) return true;
+        int64_t L, P, N;
+        window(g, L, P, N);
+        return L >= min_loci;
+    }
+    __device__ bool take(int64_t g, Row& r) const {
+        int32_t p, n;
+        if (!counts(g, p, n)) return false;
+        int64_t L, P, N;
+        window(g, L, P, N);
+        if (L < min_loci) return false;
+        r = Row{g, p, n, L, P, N};
+        return true;
+    }
+};
+
 // ---- methylation by the k-mer around the cytosine (`pileup -S`; include/hifimeth_hip.h has the definition) ----------------------
 // tab[((c * (K + 1) + row) * 4 + q]: context c, row = the k-mer's code or K for `other`, q = n_loci, pcov, ncov, ppm -- three
 // tables of K + 1 hm_region_sum_t as one array of 64-bit counters.  The kernel streams pcov / ncov; only a locus with a count looks
@@ -2610,6 +2734,9 @@ struct hm_pileup {
     // `pileup -S`, allocated by the first hm_pileup_fetch_context: the table of the flank in hand (6 KB at flank 0, 25 MB at 3),
     // the sequence starts, and the device's CU count (0: not asked yet)
     DevBuf d_cxtab{EXACT}, d_cxoff{EXACT};
+    // `smooth`, allocated by the first hm_smooth_fetch: the running sums of the span in hand, 40 B per position (the sequence
+    // starts go through d_cxoff)
+    DevBuf d_smooth{HALF};
     int n_cus = 0;
     // the loads of `diff`, `groupdiff` and `samplecorr` (load_rows), allocated by the first load: one slab of load_slab rows, whatever
     // a call brings, and the kernel's LOAD_COUNTERS counters.  The three flags are the engine's side of the rule "counts come from records or from
@@ -4693,6 +4820,54 @@ int hm_region_stats(const hm_region_sum_t* w, double out[2]) {
     if (!w || !out || w->n_loci <= 0 || w->pcov < 0 || w->ncov < 0 || w->pcov + w->ncov <= 0 || w->ppm < 0) return HM_EINVAL;
     out[0] = 100.0 * (double)w->pcov / (double)(w->pcov + w->ncov);
     out[1] = (double)w->ppm / (double)w->n_loci / 1e4;
+    return HM_OK;
+}
+
+// ---- `smooth` -----------------------------------------------------------------------------------------------------------------------
+int64_t hm_smooth_fetch(hm_pileup_t* p, int32_t part, int32_t ctx, int64_t lo, int64_t hi, int32_t half_width, int32_t min_cov,
+                        int64_t min_loci, hm_smooth_t* out, int64_t cap) {
+    if (!p) return HM_EINVAL;
+    const std::string who = "hm_smooth_fetch";
+    if (part < 0 || part > 2) return pfail(p, HM_EINVAL, who + ": part must be 0, 1 or 2");
+    if (ctx < 0 || ctx > 2) return pfail(p, HM_EINVAL, who + ": ctx must be 0, 1 or 2");
+    if (half_width < 1 || half_width > HM_SMOOTH_MAX_HALF_WIDTH) return pfail(p, HM_EINVAL, who + ": half_width must be in [1, 16384]");
+    if (min_cov < 1 || min_loci < 1) return pfail(p, HM_EINVAL, who + ": min_cov and min_loci must be >= 1");
+    if (lo < 0 || hi < lo) return pfail(p, HM_EINVAL, who + ": bad range");
+    int64_t plane_base = 0;
+    RangePlanes s;
+    if (!range_planes(p, nullptr, nullptr, nullptr, plane_base, s)) return HM_ESTATE;
+    if (p->seq_off.empty()) return pfail(p, HM_ESTATE, who + " before hm_pileup_set_reference");
+    if (part) {
+        if (p->partitions != 2 || !p->hp_pcov[part - 1] || !p->hp_ncov[part - 1])
+            return pfail(p, HM_ESTATE, who + " without partition planes (option partitions = 2, then hm_pileup_set_reference)");
+        s.pc = p->hp_pcov[part - 1];
+        s.nc = p->hp_ncov[part - 1];
+    }
+    const int64_t total = p->seq_off.back(), h = half_width;
+    if (hi > total) return pfail(p, HM_EINVAL, who + ": range past the reference");
+    if (hi == lo) return 0;
+    // the planes are read over every window of [lo, hi): the span [a, b), and the running sums cover exactly that
+    const int64_t a = std::max<int64_t>(0, lo - h + 1), b = std::min(total, hi + h - 1);
+    const int built = guarded(p, [&] {
+        p->d_smooth.reserve(sizeof(SmoothPre) * (size_t)(b - a));
+        p->d_cxoff.reserve(8 * p->seq_off.size());
+        HIP_TRY(hipMemcpyAsync(p->d_cxoff.p, p->seq_off.data(), 8 * p->seq_off.size(), hipMemcpyHostToDevice, p->stream));
+        const int64_t nblk = (b - a + HM_SMOOTH_SPAN - 1) / HM_SMOOTH_SPAN;
+        hipLaunchKernelGGL(smooth_prefix_kernel, dim3((unsigned)nblk), dim3(SMOOTH_TPB), 0, p->stream, s, a, b, (uint32_t)ctx, (int64_t)min_cov,
+                           p->d_smooth.as<SmoothPre>());
+        HIP_TRY(hipGetLastError());
+        return HM_OK;
+    });
+    if (built != HM_OK) return built;
+    const SmoothSel sel{s, p->d_smooth.as<SmoothPre>(), a, p->d_cxoff.as<int64_t>(), (int)p->seq_off.size() - 1, (uint32_t)ctx, h, min_cov, min_loci};
+    return compact_rows(p, sel, lo, hi, out, cap, no_hook, no_hook);
+}
+
+int hm_smooth_stats(const hm_smooth_t* r, int32_t half_width, double out[2]) {
+    if (!r || !out || half_width < 1 || r->wp < 0 || r->wn < 0 || (r->wp == 0 && r->wn == 0)) return HM_EINVAL;
+    const double wp = (double)r->wp, wn = (double)r->wn;
+    out[0] = 100.0 * wp / (wp + wn);
+    out[1] = (wp + wn) / half_width;
     return HM_OK;
 }
 

@@ -173,6 +173,7 @@ READPOS_DTYPE = np.dtype([("motif", "<u4"), ("end", "<u4"), ("dist", "<u4"), ("r
 READPOS_MAX = 2048                                       # the largest `pileup -P`
 REGION_SUM_DTYPE = np.dtype([("n_loci", "<i8"), ("pcov", "<i8"), ("ncov", "<i8"), ("ppm", "<i8")])                       # hm_region_sum_t, 32 bytes
 METABIN_DTYPE = np.dtype([("motif", "<i4"), ("bin", "<i4"), ("n_regions", "<i8")] + REGION_SUM_DTYPE.descr)           # hm_metabin_t, 48 bytes
+SMOOTH_DTYPE = np.dtype([("gpos", "<i8"), ("pcov", "<i4"), ("ncov", "<i4"), ("loci", "<i8"), ("wp", "<i8"), ("wn", "<i8")])  # hm_smooth_t, 40 bytes
 METAPLOT_MAX_BINS = 1000                                 # the largest `pileup -J` bins (and flank_bins)
 CONTEXT_MAX_FLANK = 3                                    # the largest `pileup -S`: k = 9
 CONTEXT_PATH_AUTO, CONTEXT_PATH_LDS, CONTEXT_PATH_GLOBAL = -1, 0, 1                   # HM_CONTEXT_PATH_*
@@ -847,6 +848,18 @@ def region_stats(row) -> Tuple[float, float]:
     out = np.zeros(2, np.float64)
     if lib().hm_region_stats(w.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)) != 0:
         raise HifimethError("hm_region_stats: n_loci > 0 expected")
+    return tuple(float(x) for x in out)
+
+
+def smooth_stats(row, half_width: int) -> Tuple[float, float]:
+    """one SMOOTH_DTYPE row -> (smoothed level in percent, effective coverage) by the C library (host only: no GPU is needed):
+    100 wp / (wp + wn) and (wp + wn) / half_width"""
+    r = np.zeros(1, SMOOTH_DTYPE)
+    for k in SMOOTH_DTYPE.names:
+        r[k] = row[k]
+    out = np.zeros(2, np.float64)
+    if lib().hm_smooth_stats(r.ctypes.data_as(C.c_void_p), half_width, out.ctypes.data_as(C.c_void_p)) != 0:
+        raise HifimethError("hm_smooth_stats: half_width >= 1 and wp + wn > 0 expected")
     return tuple(float(x) for x in out)
 
 
@@ -1530,6 +1543,15 @@ class MethylationPileup:
         else:
             out = self._rows(lambda *a: self._L.hm_pileup_fetch_context_path(*args, path, *a[1:]), REGION_SUM_DTYPE)
         return np.stack([out[k] for k in REGION_SUM_DTYPE.names], axis=-1).reshape(3, -1, 4)
+
+    def fetch_smooth(self, ctx: int, lo: int = 0, hi: Optional[int] = None, half_width: int = 500, min_cov: int = 1, min_loci: int = 1,
+                     partition: int = 0) -> np.ndarray:
+        """`smooth` (hm_smooth_fetch): the counting loci of context ctx in [lo, hi), ascending (SMOOTH_DTYPE) -- key motif ctx,
+        pcov + ncov >= min_cov -- each with the loci of its window and the sums of their pcov and ncov under the triangular kernel of
+        half-width half_width in [1, 16384], cut at its sequence; rows with fewer than min_loci loci in the window are left out.
+        partition 1 / 2: that partition's counts.  After count() or load_loci()."""
+        hi = self.n_loci if hi is None else hi
+        return self._rows(self._L.hm_smooth_fetch, SMOOTH_DTYPE, partition, ctx, lo, hi, half_width, min_cov, min_loci)
 
     def bedmethyl(self, lo: int = 0, hi: Optional[int] = None, min_valid: int = 1, partition: int = 0) -> np.ndarray:
         """the reference CpGs of [lo, hi), ascending (BEDMETHYL_DTYPE), at which a read was classed and n_mod + n_canon >= min_valid

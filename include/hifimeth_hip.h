@@ -219,6 +219,7 @@ int hm_reset_timing(hm_engine_t* e);
  *   (ours) two groups of replicates, tested with their spread (`groupdiff`)       -> hm_pileup_group_sample, hm_pileup_fetch_groups
  *   (ours) N samples' correlation matrix per context (`samplecorr`)               -> hm_sample_open, hm_sample_fetch_sums
  *   (ours) two groups of samples tested over given intervals (`regiondiff`)       -> hm_sample_fetch_intervals, hm_sample_interval_test
+ *   (ours) kernel-smoothed level per locus of one sample (`smooth`)               -> hm_smooth_fetch
  * The whole genome's counters stay resident in HBM (12 B per reference base, 28 B with the haplotype partitions) and the
  * projected calls wait in HBM (12 B each) until the thresholds are known -- the reference spills them to a temporary file.
  * MM/ML parsing and BED text formatting stay on the host (hm_bam.h).                                           */
@@ -1058,6 +1059,47 @@ int64_t hm_pileup_fetch_context(hm_pileup_t* p, const void* pcov, const void* nc
  * (tools/pileup_bench.py --context) and lets a test reach the one the default does not take. */
 int64_t hm_pileup_fetch_context_path(hm_pileup_t* p, const void* pcov, const void* ncov, const void* key, int64_t plane_base, int64_t lo,
                                      int64_t hi, int64_t min_cov, int32_t flank, int32_t path, hm_region_sum_t* out, int64_t cap);
+
+/* ---- kernel-smoothed levels per locus (`smooth`) ------------------------------------------------------------------
+ * A locus at 5-10x coverage says little on its own; its neighbours of the same context say more.  Everything here is integer-exact:
+ * a reference with arbitrary-precision integers reproduces every row bit for bit, whatever the range of the fetch.
+ * A LOCUS COUNTS when key & 3 == ctx and pcov + ncov >= min_cov (>= 1).  For a counting locus at global position g of the sequence
+ * [S0, S1) and a half-width h in [1, HM_SMOOTH_MAX_HALF_WIDTH], the WINDOW is the counting loci j of the same context with
+ * max(S0, g - h + 1) <= j <= min(S1 - 1, g + h - 1); locus j has the weight w_j = h - |j - g|, the triangular kernel in integers 1 .. h
+ * (a locus exactly h away has weight 0 and is outside).  The row of g: loci = the number of loci of the window, g included;
+ * wp = sum w_j pcov_j; wn = sum w_j ncov_j.  wp / (wp + wn) is the local-constant binomial likelihood fit under that kernel.  Nothing
+ * crosses a sequence boundary; loci of other contexts and loci below min_cov between the counting ones are ignored; with h = 1 the
+ * row is the locus itself (loci 1, wp = pcov, wn = ncov).  With counts below 2^31 (the bound of hm_pileup_load_loci) wp and wn stay
+ * below 2^60.
+ * HOW: the triangular kernel is a box convolved with a box, so a row is a few differences of running sums over the counting loci:
+ * their number, sum pcov, sum ncov and the two first moments sum (j - origin) pcov, sum (j - origin) ncov.  The call writes these five
+ * per POSITION of the span it reads, 40 B each, into a buffer the first call allocates (it grows with the largest span, freed with
+ * the engine).  The sums restart every HM_SMOOTH_SPAN positions of the span and a block's moments are measured from the block's
+ * start, so every intermediate stays below 2^62 for any legal input and any range; a half window lies in at most two blocks, and
+ * the cost of a row does not depend on h.  The rows then go through the selection skeleton of every row fetch.
+ * A fetch over [lo, hi) READS the planes over [lo - h + 1, hi + h - 1) clamped to the reference: its rows are the slice of the
+ * whole-reference fetch, whatever the chunk.  Not here: smoothing while `pileup` runs, pileup_dist, smoothed levels as the input of
+ * groupdiff or samplecorr, other kernels than the triangle. */
+#define HM_SMOOTH_MAX_HALF_WIDTH 16384
+#define HM_SMOOTH_SPAN 32768 /* positions after which the running sums restart: 2 * HM_SMOOTH_MAX_HALF_WIDTH */
+typedef struct {            /* one counting locus = one row of <prefix>.smooth.<ctx>.bed; 40 bytes */
+    int64_t gpos;
+    int32_t pcov, ncov;     /* the locus' own counts */
+    int64_t loci, wp, wn;   /* the window: its loci, and the weighted sums of their pcov and ncov */
+} hm_smooth_t;
+/* The counting loci of context ctx (0 CpG, 1 CHG, 2 CHH) in [lo, hi) whose window holds at least min_loci loci, ascending in gpos.
+ * part 0: the engine's combined planes; 1 or 2: that partition's pcov / ncov with the combined key plane.  Works after
+ * hm_pileup_count and after a successful hm_pileup_load_loci.  Returns the number of rows; when that exceeds cap, or out is NULL,
+ * nothing is written (as hm_pileup_fetch_loci).  It changes nothing another fetch reads.  HM_EINVAL for ctx outside [0, 2], part
+ * outside [0, 2], half_width outside [1, HM_SMOOTH_MAX_HALF_WIDTH], min_cov < 1, min_loci < 1, lo < 0, hi < lo or hi beyond the
+ * reference; HM_ESTATE where hm_pileup_fetch_loci over the engine's own planes gives it (no planes; after a load that met a bad
+ * row), before hm_pileup_set_reference, and for part 1 / 2 without partition planes. */
+int64_t hm_smooth_fetch(hm_pileup_t* p, int32_t part, int32_t ctx, int64_t lo, int64_t hi, int32_t half_width, int32_t min_cov,
+                        int64_t min_loci, hm_smooth_t* out, int64_t cap);
+/* Host only, fp64: the one implementation behind every front end.  out[0] = the smoothed level in percent, 100 wp / (wp + wn), each
+ * integer converted to double first; out[1] = (wp + wn) / half_width, the effective number of calls at full weight.  HM_EINVAL for
+ * half_width < 1, a negative sum or wp + wn == 0. */
+int hm_smooth_stats(const hm_smooth_t* r, int32_t half_width, double out[2]);
 
 #ifdef __cplusplus
 }

@@ -1,15 +1,18 @@
 #!/usr/bin/env python3
-"""Record what `hifimeth-hip pileup` and `hifimeth-hip diff` do with their command lines: tests/golden/cli_options.json.
+"""Record what `hifimeth-hip pileup` and `hifimeth-hip diff` do with their command lines: tests/golden/cli_options.json; and what
+`hifimeth-hip smooth` does with its: tests/golden/cli_options_smooth.json, a file of the same form.
 
 Every case names input files that do not exist, so a bad command line ends in the usage text, a good `pileup` one at
-`ERROR: cannot open no.bam` after the whole `Parameters:` echo, and a good `diff` one after its echo at "no context has a cov.bed
-file of both samples".  No case writes a file or creates an engine, so the matrix runs without a GPU in a few seconds.
+`ERROR: cannot open no.bam` after the whole `Parameters:` echo, and a good `diff` or `smooth` one after its echo at "no context has a
+cov.bed file of both samples" (`smooth`: "of the sample").  No case writes a file or creates an engine, so the matrix runs without a GPU in a few seconds.
 
 Per command the fixture holds rows [arguments after the command word, exit code, 1 if the usage text follows, stderr before `USAGE:`
 (all of it when there is none)].  What repeats is stored once: the `-h` text of each command; the frame of its echo without options
 (the lines down to `output prefix:` and what follows them stand in a row as <HEAD> and <TAIL>); and the texts in front of the usage,
 which a row names by their index in "messages".  The executable's path, its directory and the output prefix are replaced by the
 tokens EXE, EXEDIR and PREFIX.  tests/test_cli_options_cpu.py replays the file (load() undoes the folding).
+tests/test_pileup_smooth_cpu.py replays the second file.  matrix() and record() take the commands of the first file unless told
+otherwise; the first file comes out of this tool byte for byte as it was before `smooth` had its own.
 
 usage: python tools/make_cli_options.py [path of hifimeth-hip]      (default: hifimeth_amd/bin/hifimeth-hip of this tree)
 """
@@ -22,7 +25,10 @@ from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 FIXTURE = os.path.join(ROOT, "tests", "golden", "cli_options.json")
-POSITIONALS = {"pileup": ["ref.fa", "no.bam", "PREFIX"], "diff": ["ref.fa", "a", "b", "PREFIX"]}
+POSITIONALS = {"pileup": ["ref.fa", "no.bam", "PREFIX"], "diff": ["ref.fa", "a", "b", "PREFIX"], "smooth": ["ref.fa", "a", "PREFIX"]}
+SMOOTH_FIXTURE = os.path.join(ROOT, "tests", "golden", "cli_options_smooth.json")
+COMMANDS = ("pileup", "diff")          # the commands of FIXTURE
+SMOOTH_COMMANDS = ("smooth",)          # ... and of SMOOTH_FIXTURE
 
 LLMAX = 9223372036854775807
 JUNK = ["x", "5x", "2.5", "", " 5", "+5", "-3", str(LLMAX + 1)]   # the last one: ERANGE
@@ -105,12 +111,23 @@ DIFF_LINES = [
     "!ref.fa", "!ref.fa a b", "!ref.fa a b PREFIX more", "!-Q ref.fa a b", "!-s x ref.fa a b", "!-Z 1 ref.fa a b",
     "", "-Q", "-G", "-a 7", "-t 3 -d 1", "-G -s 0.05 -g 250 -n 4", "-t 3 -d 1 -a 7 -Q -G -s 0.05 -g 250 -n 4",
 ]
+SMOOTH = {
+    "-W": ([], ends(1, 16384) + ["500"]), "-a": ([], ends(1, 2147483647)), "-i": ([], ends(1, LLMAX)),
+    "-t": ([], ["0", "1", "16"]), "-d": ([], ["0", "3", "-1"]),
+}
+SMOOTH_LINES = [
+    "-W x -a 0", "-a 0 -W x", "-i 0 -t 3", "-W 16 -W 0", "-W 0 -W 16",
+    "!", "!-h", "!-W 7 -h", "!-W x -h", "!-h -W x", "!-Z 1 -h", "-i -h", "!-W", "!-W 7 -i", "-Z 1", "!-Z", "-Z", "-Wa 5", "--help 1", "-H 1", "-Q 1",
+    "-s .1", "-q 5", "!- ref.fa a PREFIX", "!a ref.fa a PREFIX b", "!ref.fa -W a PREFIX", "!ref.fa", "!ref.fa a", "!ref.fa a PREFIX more",
+    "!-W 7 ref.fa a", "!-W x ref.fa a", "!-Z 1 ref.fa a",
+    "", "-W 16", "-W 16384 -a 3 -i 5", "-t 3 -d 1", "-t 3 -d 1 -W 1 -a 2 -i 2",
+]
 # one way to make each pileup check fire, in the order the checks run: neighbours go into the matrix in both orders
 GROUP_BAD = ["-A", "-l 5", "-B c -e 0,0,0", "-u .1:.8", "-w x", "-v 1", "-z -1", "-y x", "-C 2", "-O 0"]
 
 
-def matrix():
-    """[(command, [arguments])], without duplicates, in a fixed order"""
+def matrix(commands=COMMANDS):
+    """[(command, [arguments])] of `commands`, without duplicates, in a fixed order"""
     cases = []
 
     def add(cmd, args, positionals=True):
@@ -118,7 +135,9 @@ def matrix():
         if case not in cases:
             cases.append(case)
 
-    for cmd, table, lines in (("pileup", PILEUP, PILEUP_LINES), ("diff", DIFF, DIFF_LINES)):
+    for cmd, table, lines in (("pileup", PILEUP, PILEUP_LINES), ("diff", DIFF, DIFF_LINES), ("smooth", SMOOTH, SMOOTH_LINES)):
+        if cmd not in commands:
+            continue
         for flag, (parents, values) in table.items():
             add(cmd, parents + [flag])                      # a valued flag swallows the first positional here
             for v in (values or []) + (JUNK if values and flag not in LENIENT else []):
@@ -127,7 +146,7 @@ def matrix():
             # "!": the line is the whole command line, positionals included; a list: arguments that hold blanks
             words = line if isinstance(line, list) else line.lstrip("!").split()
             add(cmd, words, positionals=isinstance(line, list) or not line.startswith("!"))
-    for a, b in zip(GROUP_BAD, GROUP_BAD[1:] + GROUP_BAD[:1]):
+    for a, b in zip(GROUP_BAD, GROUP_BAD[1:] + GROUP_BAD[:1]) if "pileup" in commands else ():
         add("pileup", a.split() + b.split())
         add("pileup", b.split() + a.split())
     return cases
@@ -158,13 +177,13 @@ def unfold(text, frame):
     return text.replace("<HEAD>", frame[0]).replace("<TAIL>", frame[1])
 
 
-def record(exe):
-    """the fixture as a dict, from the binary `exe`"""
+def record(exe, commands=COMMANDS):
+    """the fixture of `commands` as a dict, from the binary `exe`"""
     exe = os.path.abspath(exe)
     with tempfile.TemporaryDirectory() as tmp:
         prefix = os.path.join(tmp, "out")
         usage, frames = {}, {}
-        for cmd in ("pileup", "diff"):
+        for cmd in commands:
             code, text, before = run_case(exe, cmd, ["-h"], prefix)
             assert code == 0 and text and before == "", (cmd, code, before)
             usage[cmd] = text
@@ -172,12 +191,12 @@ def record(exe):
             cut = before.index("output prefix: PREFIX\n") + len("output prefix: PREFIX\n")
             assert code == 1 and text is None
             frames[cmd] = [before[:cut], before[cut:]]
-        cases = matrix()
+        cases = matrix(commands)
         with ThreadPoolExecutor(8) as pool:
             results = list(pool.map(lambda c: run_case(exe, c[0], c[1], prefix), cases))
         assert not os.listdir(tmp), os.listdir(tmp)           # no case creates a file
     messages = sorted({before for (_, text, before) in results if text is not None})
-    rows = {"pileup": [], "diff": []}
+    rows = {cmd: [] for cmd in commands}
     for (cmd, args), (code, text, before) in zip(cases, results):
         assert text is None or text == usage[cmd], (cmd, args)   # there is one usage text per command
         rows[cmd].append([args, code, int(text is not None), fold(before, frames[cmd]) if text is None else messages.index(before)])
@@ -212,7 +231,8 @@ def load(path=FIXTURE):
 
 if __name__ == "__main__":
     exe = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "hifimeth_amd", "bin", "hifimeth-hip")
-    fixture = record(exe)
-    dump(fixture, FIXTURE)
-    n_usage = sum(r[2] for rows in fixture["cases"].values() for r in rows)
-    print(f"cli_options.json: {sum(map(len, fixture['cases'].values()))} cases, {n_usage} end in the usage text, {os.path.getsize(FIXTURE)} bytes")
+    for path, commands in ((FIXTURE, COMMANDS), (SMOOTH_FIXTURE, SMOOTH_COMMANDS)):
+        fixture = record(exe, commands)
+        dump(fixture, path)
+        n_usage = sum(r[2] for rows in fixture["cases"].values() for r in rows)
+        print(f"{os.path.basename(path)}: {sum(map(len, fixture['cases'].values()))} cases, {n_usage} end in the usage text, {os.path.getsize(path)} bytes")
